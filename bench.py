@@ -28,6 +28,12 @@ scaling), every rank pre-processes the same frames, and per-rank raw matches are
 `value` counts frames x (total templates / 3000) per second, `frames_per_sec` is the plain frame rate.
 
 Prints ONE JSON line on rank 0.
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what the headline needs: set up, prime and warm up, time the K
+steps and print the line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, `step_ms`, `config`).  Everything
+else above -- `roofline`, `kernel_ms_per_step`, `config.label_density`, `host_frames*`, `extra`, `cpu_baseline*` -- comes with `--full`,
+which also puts HIP events around the dominant kernel in the timed steps (`--no-events` leaves them out).  `--dump-outputs DIR` writes
+the matches of the last timed step (see dump_outputs); the inputs are seeded, so runs with the same arguments compare output for output.
 """
 import argparse
 import json
@@ -118,6 +124,30 @@ def cpu_baseline_all_cores(bank, frames, threshold, budget_s=8.0):
     dt = time.perf_counter() - t0
     return {"value": n / dt, "unit": "frames/s", "cores": cores, "kind": "port",
             "sample": "%d frames over %d threads, %d templates, %.1f s" % (n, cores, bank.num_templates(), dt)}
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, matches):
+    """What the timed path hands its caller for one step (per frame, MATCH_DTYPE records in upstream order) as float64 arrays
+    <path>/<name>.npy, one per record field plus `frame` (the record's frame index) and `matches_per_frame`; every value is exact in
+    float64.  Above DUMP_MAX_BYTES in all, a fixed seeded sample of the records is written and `sample_index` holds their positions
+    in the concatenated list."""
+    from linemod_pose_estimation_amd.detector import MATCH_DTYPE
+    os.makedirs(path, exist_ok=True)
+    counts = np.asarray([len(m) for m in matches], np.int64)
+    rec = np.concatenate([np.asarray(m, MATCH_DTYPE) for m in matches]) if len(matches) else np.zeros(0, MATCH_DTYPE)
+    arrays = {"matches_per_frame": counts.astype(np.float64), "frame": np.repeat(np.arange(len(matches)), counts).astype(np.float64)}
+    arrays.update({k: rec[k].astype(np.float64) for k in MATCH_DTYPE.names})
+    n_cols = len(arrays) - 1
+    if 8 * (len(counts) + n_cols * len(rec)) > DUMP_MAX_BYTES:
+        cap = (DUMP_MAX_BYTES - 8 * len(counts)) // (8 * (n_cols + 1))
+        keep = np.sort(np.random.default_rng(0).choice(len(rec), cap, replace=False))
+        arrays = {k: (v if k == "matches_per_frame" else v[keep]) for k, v in arrays.items()}
+        arrays["sample_index"] = keep.astype(np.float64)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
 
 
 def run_pipelined(det, k, B, threshold, uploads=None, stamps=None, collect_cap=1 << 16, collect=None):
@@ -322,7 +352,13 @@ def main():
     ap.add_argument("--no-extra", action="store_true", help="skip the secondary workload lines (host frames, busy scene, low threshold)")
     ap.add_argument("--no-configs", action="store_true", help="skip the per-config lines (config 0 / 3 / 4 / 5 shapes, device group) inside `extra`")
     ap.add_argument("--no-events", action="store_true", help="no HIP events in the timed region (roofline then uses the untimed pass)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: per-kernel breakdown and roofline (HIP events around the dominant kernel in the timed steps), "
+                         "label density, the secondary workload lines and the CPU baselines; without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the matches of the last timed step as DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # stdout carries exactly ONE JSON line: native libraries (RCCL prints a version banner on stdout when the process group is
     # created) get stderr as their fd 1 for the rest of the run, the JSON line goes to the saved descriptor
@@ -396,20 +432,22 @@ def main():
             return run_sharded(sm, k, B, args.threshold, None, stamps)
         raw_det = sm.det
 
-    # 1. untimed pass, one step in flight, HIP events around every kernel: per-kernel breakdown and the dominant kernel's name
-    for _ in range(2):
-        out = step()
-    raw_det.set_profiling(True)
-    raw_det.reset_profiling()
-    n_prof = 4
-    for _ in range(n_prof):
-        out = step()
-    breakdown = {k: v[0] / float(n_prof) for k, v in raw_det.kernel_times().items()}  # ms per step
-    raw_det_launches = {k: v[1] // n_prof for k, v in raw_det.kernel_times().items()}
-    dom = max(breakdown, key=breakdown.get)
-    # from here on exactly the timed configuration: events only around the dominant kernel (each timed launch adds two event
-    # records to its stream)
-    raw_det.set_profiling(False if args.no_events else dom)
+    if args.full:
+        # 1. untimed pass, one step in flight, HIP events around every kernel: per-kernel breakdown and the dominant kernel's name
+        for _ in range(2):
+            out = step()
+        raw_det.set_profiling(True)
+        raw_det.reset_profiling()
+        n_prof = 4
+        for _ in range(n_prof):
+            out = step()
+        breakdown = {k: v[0] / float(n_prof) for k, v in raw_det.kernel_times().items()}  # ms per step
+        raw_det_launches = {k: v[1] // n_prof for k, v in raw_det.kernel_times().items()}
+        dom = max(breakdown, key=breakdown.get)
+        # from here on exactly the timed configuration: events only around the dominant kernel (each timed launch adds two event
+        # records to its stream)
+        raw_det.set_profiling(False if args.no_events else dom)
+    # (a plain run skips 1. and has no events in its timed steps)
     # 2. untimed priming, pipelined like the timed steps.  The first concurrent uses of the device lanes / the communication
     # stream block the submitting thread for 5-7 ms a few times per process while the HIP runtime grows its signal pools
     # (seen inside hipMemcpyAsync/hipMemsetAsync of the matching stage; gone after ~20 steps, scripts/sharded_experiment.py);
@@ -436,7 +474,7 @@ def main():
     dist_extra = None
     line = None
 
-    if rank == 0:
+    if rank == 0 and args.full:
         times = raw_det.kernel_times()
         dom_ms, dom_n = times[dom]
         alg = raw_det.algorithmic_bytes(dom, B)
@@ -516,10 +554,9 @@ def main():
             "hbm": {"algorithmic_bytes_per_launch": alg / lps, "algorithmic_gbs": hbm_achieved, "algorithmic_frac_of_peak": hbm_achieved / HBM_PEAK_GBS,
                     "measured_bytes_per_launch": traffic, "measured_gbs": (traffic / (excl_ms * 1e-3) / 1e9) if traffic else None,
                     "measured_frac_of_peak": (traffic / (excl_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if traffic else None, "peak": HBM_PEAK_GBS}})
+    if rank == 0:
         fps = B * args.steps / dt
         value = fps * (n_total / float(TEMPLATES_PER_GPU))
-        dens = {"cg_l0": float((raw_det.debug_quantized(0, 0, 0) != 0).mean()), "cg_l1": float((raw_det.debug_quantized(0, 1, 0) != 0).mean()),
-                "dn_l0": float((raw_det.debug_quantized(0, 0, 1) != 0).mean())}
         st = raw_det.stats()
         line = {
             "metric": "rgbd_frames_per_sec_matched",
@@ -532,21 +569,26 @@ def main():
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "u8", "data": "synthetic",
             "config": {"workload": "BASELINE configs[1]: 640x480 RGB-D, ColorGradient+DepthNormal, T={5,8}, %d templates/GPU" % args.templates,
-                       "input": "device-resident (frames uploaded once before the timed region; host-frame rates: host_frames*)",
+                       "input": "device-resident (frames uploaded once before the timed region; host-frame rates with --full: host_frames*)",
                        "frames_per_step": B, "templates_per_gpu": args.templates, "templates_total": n_total,
                        "threshold": args.threshold, "device_lanes": raw_det.max_outstanding // 2, "hipgraph": bool(args.hipgraph), "hw_queues": hwq,
                        "parallelism": "template-shard x%d + all-gather" % world,
                        "matches_per_frame": float(np.mean([len(m) for m in out])),
                        "coarse_candidates_per_frame": st["candidates"] / float(B), "scene_texture": args.texture,
-                       "score_no_prune": os.environ.get("LMX_SCORE_NO_PRUNE", "0") not in ("", "0"),
-                       "label_density": dens},
-            "roofline": roofline,
-            "kernel_ms_per_step": breakdown,
+                       "score_no_prune": os.environ.get("LMX_SCORE_NO_PRUNE", "0") not in ("", "0")},
             "template_cells_per_sec": value * TEMPLATES_PER_GPU * 1200.0,   # N x 1200 coarse cells x frames/s
         }
+        if args.full:
+            line["config"]["label_density"] = {"cg_l0": float((raw_det.debug_quantized(0, 0, 0) != 0).mean()),
+                                               "cg_l1": float((raw_det.debug_quantized(0, 1, 0) != 0).mean()),
+                                               "dn_l0": float((raw_det.debug_quantized(0, 0, 1) != 0).mean())}
+            line["roofline"] = roofline
+            line["kernel_ms_per_step"] = breakdown
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, out)
         if not use_dist:
             det.close()
-    if use_dist and not args.no_extra:
+    if use_dist and args.full and not args.no_extra:
         # The secondary lines of the multi-rank job run on EVERY rank (collectives inside) and have never met more than one rank on hardware: the
         # headline above must not depend on them.  It is complete at this point (rank 0 holds it); if the secondary lines have not finished after
         # LMX_BENCH_EXTRA_DEADLINE_S seconds (a rank that failed alone would leave the others inside a collective), rank 0 prints the line without
@@ -573,7 +615,7 @@ def main():
         finished.set()
         watchdog.cancel()
     if rank == 0:
-        if not args.no_extra and world == 1 and not use_dist:
+        if args.full and not args.no_extra and world == 1 and not use_dist:
             # the boundary the reference actually has: fresh host frames on every call.  Three distinct batches (the 64 scenes in
             # three orders, separate host arrays) rotate, so every step transfers data that is not on the device yet.
             perms = [np.random.default_rng(s).permutation(B) for s in (1, 2, 3)]
@@ -904,7 +946,7 @@ def main():
             if "host_frames" in dist_extra:
                 line["host_frames"] = dist_extra.pop("host_frames")
             line["extra"] = dist_extra
-        if not args.no_cpu_baseline and world == 1:  # the host baseline is timed at N=1 only (rank 0), as the contract asks
+        if args.full and not args.no_cpu_baseline and world == 1:  # the host baseline is timed at N=1 only (rank 0), as the contract asks
             line["cpu_baseline"] = cpu_baseline(bank, frames, args.threshold)
             line["cpu_baseline_all_cores"] = cpu_baseline_all_cores(bank, frames, args.threshold)
             end_to_end = line.get("host_frames", {}).get("value")

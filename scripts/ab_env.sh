@@ -4,7 +4,7 @@ var=$1; shift
 rounds=${ROUNDS:-3}
 for r in $(seq $rounds); do
   for v in "$@"; do
-    env $var=$v python bench.py --no-cpu-baseline --no-extra 2>/dev/null | python -c "
+    env $var=$v python bench.py --full --no-cpu-baseline --no-extra 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('%-28s %7.0f frames/s  %.4f ms/step ' % ('$var=$v', d['value'], d['ms_per_step']), {k: round(v, 4) for k, v in d['kernel_ms_per_step'].items() if v})"

@@ -6,7 +6,7 @@ a=$1; b=$2; rounds=${3:-2}
 for r in $(seq $rounds); do
   for w in A B; do
     lib=$a; [ $w = B ] && lib=$b
-    LMX_SO_PATH=$lib python bench.py --no-cpu-baseline --no-extra 2>/dev/null | python -c "
+    LMX_SO_PATH=$lib python bench.py --full --no-cpu-baseline --no-extra 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$w default  %7.0f frames/s  %.4f ms/step ' % (d['value'], d['ms_per_step']), {k: round(v, 4) for k, v in d['kernel_ms_per_step'].items() if v})"

@@ -4,7 +4,7 @@ out=gpurun_out/${1:-pad}
 mkdir -p $out
 run() {  # name, env...
   name=$1; shift
-  env "$@" python3 bench.py --no-extra --no-cpu-baseline --steps 300 > $out/$name.json 2> $out/$name.err
+  env "$@" python3 bench.py --full --no-extra --no-cpu-baseline --steps 300 > $out/$name.json 2> $out/$name.err
   python3 - <<PY
 import json
 j = json.loads(open("$out/$name.json").read().strip().splitlines()[-1])

@@ -12,12 +12,12 @@ cd /tmp && export TMPDIR=/tmp
 cd $root
 export GPU_MAX_HW_QUEUES=${GPU_MAX_HW_QUEUES:-8}
 export LMX_SCORE_NO_PRUNE=1
-python3 bench.py --no-cpu-baseline --no-extra --no-overlap > $out/bench.json 2> $out/bench.err || { tail -5 $out/bench.err; exit 1; }
-rocprofv3 --output-format csv --kernel-trace --stats -d $out/kt1 -o kt1 -- python3 bench.py --no-cpu-baseline --no-extra --no-overlap > $out/bench_kt_one_lane.json 2> $out/kt1.err || exit 1
+python3 bench.py --full --no-cpu-baseline --no-extra --no-overlap > $out/bench.json 2> $out/bench.err || { tail -5 $out/bench.err; exit 1; }
+rocprofv3 --output-format csv --kernel-trace --stats -d $out/kt1 -o kt1 -- python3 bench.py --full --no-cpu-baseline --no-extra --no-overlap > $out/bench_kt_one_lane.json 2> $out/kt1.err || exit 1
 i=0
 for set in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SMEM SQ_WAVE_CYCLES" \
            "FETCH_SIZE" "WRITE_SIZE" "TCC_REQ_sum TCC_HIT_sum TCC_MISS_sum" "TCP_TCC_READ_REQ_sum TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_LATENCY_sum"; do
   i=$((i+1))
-  rocprofv3 --output-format csv --pmc $set --kernel-trace -d $out/pmc$i -o p -- python3 bench.py --no-cpu-baseline --no-overlap --no-events --no-extra --steps 4 --warmup 1 > /dev/null 2> $out/pmc$i.err || echo "PMC pass $i ($set) failed"
+  rocprofv3 --output-format csv --pmc $set --kernel-trace -d $out/pmc$i -o p -- python3 bench.py --full --no-cpu-baseline --no-overlap --no-events --no-extra --steps 4 --warmup 1 > /dev/null 2> $out/pmc$i.err || echo "PMC pass $i ($set) failed"
 done
 python3 scripts/pmc_summary2.py $out > $out/summary.txt && grep -A12 "k_score_coarse" $out/summary.txt | head -20

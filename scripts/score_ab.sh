@@ -3,9 +3,9 @@
 out=gpurun_out/${1:-score_ab}
 mkdir -p $out
 for v in u8 sb; do
-  LMX_SCORE_KERNEL=$v python3 bench.py --no-extra --no-cpu-baseline --no-overlap --steps 200 > $out/one_lane_$v.json 2> $out/one_lane_$v.err
-  LMX_SCORE_KERNEL=$v python3 bench.py --no-extra --no-cpu-baseline --steps 400 > $out/lanes_$v.json 2> $out/lanes_$v.err
-  LMX_SCORE_KERNEL=$v python3 bench.py --no-extra --no-cpu-baseline --steps 200 --texture 1.0 > $out/busy_$v.json 2> $out/busy_$v.err
+  LMX_SCORE_KERNEL=$v python3 bench.py --full --no-extra --no-cpu-baseline --no-overlap --steps 200 > $out/one_lane_$v.json 2> $out/one_lane_$v.err
+  LMX_SCORE_KERNEL=$v python3 bench.py --full --no-extra --no-cpu-baseline --steps 400 > $out/lanes_$v.json 2> $out/lanes_$v.err
+  LMX_SCORE_KERNEL=$v python3 bench.py --full --no-extra --no-cpu-baseline --steps 200 --texture 1.0 > $out/busy_$v.json 2> $out/busy_$v.err
 done
 python3 - <<PY
 import json

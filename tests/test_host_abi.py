@@ -322,14 +322,17 @@ def test_renderer_params_sidecar_reader_and_writer(tmp_path):
     assert L.lmx_renderer_params_load(str(bad).encode(), C.byref(q)) == _lib.LMX_ERR_PARSE and b"incomplete" in L.lmx_last_error()
 
 
-def test_renderer_params_reader_on_the_reference_file():
+def test_renderer_params_reader_on_the_reference_file(tmp_path):
     """The complete side-car the reference ships (config/data/boxNew_longDistance_linemod_xtion_renderer_params.yml, 2 MB, 2652 templates =
-    26 directions x 6 distances x 17 in-plane rotations) through lmx_renderer_params_load; only where the reference checkout exists
-    (the build container), the committed 6-template sample above is what travels."""
+    26 directions x 6 distances x 17 in-plane rotations) through lmx_renderer_params_load.  The file is committed xz-compressed under
+    tests/golden/ (byte-identical once unpacked)."""
     import ctypes as C
-    path = "/root/reference/config/data/boxNew_longDistance_linemod_xtion_renderer_params.yml"
-    if not os.path.exists(path):
-        pytest.skip("reference checkout not present")
+    import lzma
+    from conftest import ROOT
+    name = "boxNew_longDistance_linemod_xtion_renderer_params.yml"
+    path = str(tmp_path / name)
+    with lzma.open(os.path.join(ROOT, "tests", "golden", name + ".xz")) as src, open(path, "wb") as dst:
+        dst.write(src.read())
     L = _lib.lib()
     p = C.POINTER(_lib.RendererParams)()
     _lib.check(L.lmx_renderer_params_load(path.encode(), C.byref(p)))
