@@ -131,6 +131,13 @@ typedef struct lmx_ctx_desc {
  * copy threads).  Without this flag every source, pinned or not, is copied before the call returns ("callee copies, never retains
  * pointers": the boundary's contract). */
 #define LMX_CTX_ASYNC_INPUT 4
+/* Gray colour sources: every ColorGradient source is 8UC1 (a MONO8 camera frame) instead of 8UC3, and the colour pyramid holds one
+ * byte per pixel.  Quantisation runs over one plane; the results equal, bit for bit, those of the same image copied into B, G and R
+ * on a context without the flag (upstream's strongest-channel rule picks channel 0 of three equal channels; blur, Sobel and pyrDown
+ * work per channel).  A gray context refuses 8UC3 colour sources (LMX_ERR_SHAPE), and lmx_ctx_upload_raw takes only `mono` colour
+ * sources (there is no colour-to-gray conversion); a context without the flag refuses 8UC1 colour sources as before.  Combines with
+ * every other flag and passes through lmx_group_desc.flags to the members. */
+#define LMX_CTX_GRAY 8
 
 /* ---- bank ---------------------------------------------------------------------------------------------- */
 lmx_status lmx_bank_create(const lmx_bank_desc* desc, lmx_bank** out);
@@ -489,7 +496,7 @@ lmx_status lmx_ctx_collect_clusters(lmx_ctx* ctx, int32_t n_frames, lmx_match_t*
 enum {
   LMX_DBG_QUANTIZED = 0,     /* u8 [H_l][W_l] one-hot labels after quantize(), A.2/A.4 */
   LMX_DBG_LINEAR_MEMORY = 1, /* u8 [8][T*T][W'H'] in upstream linearize() layout, A.7 */
-  LMX_DBG_PYRAMID_BGR = 2,   /* u8 [H_l][W_l][3] colour source at level l (pyrDown chain), A.3 */
+  LMX_DBG_PYRAMID_BGR = 2,   /* u8 [H_l][W_l][3] colour source at level l (pyrDown chain), A.3; [H_l][W_l] on a gray context */
   LMX_DBG_DEPTH = 3          /* u16 [H][W] level-0 depth in mm as the DepthNormal modality sees it */
 };
 lmx_status lmx_ctx_debug_read(lmx_ctx* ctx, int32_t frame, int32_t what, int32_t level, int32_t modality, void* out,

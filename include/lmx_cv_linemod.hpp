@@ -206,9 +206,9 @@ class Detector {
  public:
   typedef std::vector<Template> TemplatePyramid;
 
-  Detector() : foreign_depth_(false), bank_(NULL), shared_(NULL), ctx_(NULL), ctx_w_(0), ctx_h_(0), device_(0), max_candidates_(0) {}
+  Detector() : foreign_depth_(false), bank_(NULL), shared_(NULL), device_(0), max_candidates_(0) {}
   Detector(const std::vector<Ptr<Modality> >& modalities, const std::vector<int>& T_pyramid)
-      : modalities_(modalities), T_at_level_(T_pyramid), foreign_depth_(false), bank_(NULL), shared_(NULL), ctx_(NULL), ctx_w_(0), ctx_h_(0), device_(0), max_candidates_(0) {}
+      : modalities_(modalities), T_at_level_(T_pyramid), foreign_depth_(false), bank_(NULL), shared_(NULL), device_(0), max_candidates_(0) {}
   ~Detector() { drop(); }
 
   // liblmx extension (no upstream analogue): the whole of the reference's readLinemod(filename) in one call.  The templates come from the
@@ -261,8 +261,13 @@ class Detector {
     // Upstream never runs out of room, so neither may the drop-in: when the device's candidate / match lists overflow (default
     // 16384 per frame; a low threshold on a cluttered scene yields more) the context is re-acquired with lists sized from the
     // counts the failed call reports, and the call repeated.  The larger size sticks to this detector (and is part of the cache key).
+    // a CV_8UC1 ColorGradient source (a MONO8 camera frame) is matched on a gray context (LMX_CTX_GRAY): the same matches as the frame
+    // copied into B, G and R, at a third of the colour bytes.  Gray and BGR calls may alternate: each kind keeps a context of its own.
+    bool gray = false;
+    for (size_t i = 0; i < sources.size(); ++i)
+      if (modalities_[i]->desc().type == LMX_MOD_COLOR_GRADIENT && sources[i].channels() == 1) gray = true;
     for (int attempt = 0;; ++attempt) {
-      lmx_ctx* ctx = context(sources[0].cols, sources[0].rows);
+      lmx_ctx* ctx = context(sources[0].cols, sources[0].rows, gray);
       bool regrow = false;
       {
         CtxLock lock(ctx);   // the context may be shared with another Detector of the same bank (lmx_ctx_acquire): match + read-backs as one unit
@@ -298,7 +303,7 @@ class Detector {
         }
       }
       if (!regrow) break;
-      if (ctx_) { lmx_ctx_unref(ctx_); ctx_ = NULL; }   // outside the lock: the next turn acquires a context with the larger lists
+      if (ctx_[gray]) { lmx_ctx_unref(ctx_[gray]); ctx_[gray] = NULL; }   // outside the lock: the next turn acquires a context with the larger lists
     }
   }
 
@@ -477,21 +482,25 @@ class Detector {
     }
     return bank_;
   }
-  // the device context: process-wide cache keyed by the bank's content and the frame size (see header comment)
-  lmx_ctx* context(int w, int h) const {
-    if (ctx_ && w == ctx_w_ && h == ctx_h_) return ctx_;
-    if (ctx_) { lmx_ctx_unref(ctx_); ctx_ = NULL; }
+  // the device context: process-wide cache keyed by the bank's content, the frame size and the flags (see header comment); one slot for
+  // BGR sources, one for gray ones (LMX_CTX_GRAY)
+  lmx_ctx* context(int w, int h, bool gray) const {
+    lmx_ctx*& c = ctx_[gray ? 1 : 0];
+    if (c && w == ctx_w_[gray] && h == ctx_h_[gray]) return c;
+    if (c) { lmx_ctx_unref(c); c = NULL; }
     lmx_ctx_desc d;
     std::memset(&d, 0, sizeof(d));
     d.device = device_; d.width = w; d.height = h; d.max_batch = 1; d.max_candidates = max_candidates_;
+    d.flags = gray ? LMX_CTX_GRAY : 0;
     int32_t hit = 0;
-    lmx_check(lmx_ctx_acquire(bank(), &d, &ctx_, &hit));
+    lmx_check(lmx_ctx_acquire(bank(), &d, &c, &hit));
     ctx_cached_ = hit != 0;
-    ctx_w_ = w; ctx_h_ = h;
-    return ctx_;
+    ctx_w_[gray] = w; ctx_h_[gray] = h;
+    return c;
   }
   void invalidate() const {
-    if (ctx_) { lmx_ctx_unref(ctx_); ctx_ = NULL; }
+    for (int k = 0; k < 2; ++k)
+      if (ctx_[k]) { lmx_ctx_unref(ctx_[k]); ctx_[k] = NULL; }
     tcache_.clear();
   }
   void drop() {
@@ -505,8 +514,8 @@ class Detector {
   bool foreign_depth_;
   mutable lmx_bank* bank_;           // private, modifiable bank (built by read / readClass / addTemplate), or NULL
   mutable const lmx_bank* shared_;   // load(): the cached bank of a templates file, shared and read-only, or NULL
-  mutable lmx_ctx* ctx_;
-  mutable int ctx_w_, ctx_h_;
+  mutable lmx_ctx* ctx_[2] = {NULL, NULL};   // [0]: BGR sources, [1]: gray sources
+  mutable int ctx_w_[2] = {0, 0}, ctx_h_[2] = {0, 0};
   mutable bool ctx_cached_ = false;
   int device_;
   mutable int max_candidates_;

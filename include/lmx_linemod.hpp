@@ -128,8 +128,12 @@ class Detector {
     std::vector<const char*> cids;
     for (const std::string& c : class_ids) cids.push_back(c.c_str());
     if (buf_.size() < 4096) buf_.resize(4096);
+    // a one-channel 8-bit source can only be a gray ColorGradient frame (depth is 16-bit): it is matched on a gray context (LMX_CTX_GRAY),
+    // with the matches of the frame copied into B, G and R.  Gray and BGR calls may alternate: each kind keeps a context of its own.
+    bool gray = false;
+    for (const Image& s : sources) gray = gray || (s.channels == 1 && s.elem_size == 1);
     for (int attempt = 0;; ++attempt) {
-      ensure_ctx(sources[0].cols, sources[0].rows);
+      ensure_ctx(sources[0].cols, sources[0].rows, gray);
       size_t n = 0;
       lmx_status st = lmx_match(ctx_, imgs.data(), (int)imgs.size(), threshold, cids.empty() ? nullptr : cids.data(), (int)cids.size(),
                                 buf_.data(), buf_.size(), &n);
@@ -144,7 +148,7 @@ class Detector {
         while (grown < need && grown < (1 << 26)) grown *= 2;
         if (grown > max_candidates_ && grown > 16384) {
           max_candidates_ = grown;
-          lmx_ctx_destroy(ctx_); ctx_ = nullptr;
+          lmx_ctx_destroy(ctx_); ctx_ = nullptr; slot_[gray] = nullptr;
           continue;
         }
       }
@@ -170,22 +174,29 @@ class Detector {
 
  private:
   void reset() {
-    if (ctx_) lmx_ctx_destroy(ctx_);
+    for (int k = 0; k < 2; ++k)
+      if (slot_[k]) lmx_ctx_destroy(slot_[k]);
     if (bank_) lmx_bank_destroy(bank_);
-    ctx_ = nullptr; bank_ = nullptr;
+    slot_[0] = slot_[1] = nullptr; ctx_ = nullptr; bank_ = nullptr;
   }
-  void ensure_ctx(int w, int h) {
-    if (ctx_ && w == w_ && h == h_) return;
-    if (ctx_) { lmx_ctx_destroy(ctx_); ctx_ = nullptr; }
-    lmx_ctx_desc d;
-    std::memset(&d, 0, sizeof(d));
-    d.device = device_; d.width = w; d.height = h; d.max_batch = max_batch_; d.max_candidates = max_candidates_; d.stream = stream_;
-    check(lmx_ctx_create(bank_, &d, &ctx_));
-    w_ = w; h_ = h;
+  // ctx_ = the context of the current call: slot_[0] for BGR sources, slot_[1] for gray ones (LMX_CTX_GRAY)
+  void ensure_ctx(int w, int h, bool gray) {
+    lmx_ctx*& c = slot_[gray ? 1 : 0];
+    if (c && (w != w_[gray] || h != h_[gray])) { lmx_ctx_destroy(c); c = nullptr; }
+    if (!c) {
+      lmx_ctx_desc d;
+      std::memset(&d, 0, sizeof(d));
+      d.device = device_; d.width = w; d.height = h; d.max_batch = max_batch_; d.max_candidates = max_candidates_; d.stream = stream_;
+      d.flags = gray ? LMX_CTX_GRAY : 0;
+      check(lmx_ctx_create(bank_, &d, &c));
+      w_[gray] = w; h_[gray] = h;
+    }
+    ctx_ = c;
   }
   lmx_bank* bank_ = nullptr;
   lmx_ctx* ctx_ = nullptr;
-  int device_ = 0, max_batch_ = 1, max_candidates_ = 0, w_ = 0, h_ = 0;
+  lmx_ctx* slot_[2] = {nullptr, nullptr};
+  int device_ = 0, max_batch_ = 1, max_candidates_ = 0, w_[2] = {0, 0}, h_[2] = {0, 0};
   void* stream_ = nullptr;
   std::vector<lmx_match_t> buf_;
 };

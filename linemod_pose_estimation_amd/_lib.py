@@ -27,6 +27,7 @@ SYMBOLS = [
  LMX_ERR_PARSE, LMX_ERR_NOT_FOUND) = range(9)
 LMX_MOD_COLOR_GRADIENT, LMX_MOD_DEPTH_NORMAL = 0, 1
 LMX_DBG_QUANTIZED, LMX_DBG_LINEAR_MEMORY, LMX_DBG_PYRAMID_BGR = 0, 1, 2
+LMX_CTX_GRAY = 8   # include/lmx.h: ColorGradient sources are 8UC1 (gray), the colour pyramid one byte per pixel
 LMX_NORMAL_LUT_SIZE = 8000
 LMX_LUT_DEFAULT, LMX_LUT_USER, LMX_LUT_SIDECAR, LMX_LUT_UNKNOWN = range(4)
 

@@ -19,6 +19,10 @@
 // The same source compiles for the CPU with LMX_CQ_HOST defined (tests/cpp/cq_host.cpp): the 256 threads of a workgroup are emulated stage by
 // stage -- stages only communicate through LDS across barriers -- and the result is compared with the oracle on this container's CPU
 // (tests/test_color_kernel_host.py), borders, ragged tiles and both tile heights included.
+//
+// NC (trailing template parameter, default 3): colour planes of the source.  NC = 1 is the gray context's path (LMX_CTX_GRAY): the source rows
+// are the one plane (no de-interleave), every filter runs over one plane, Sobel needs no strongest-channel select and pyrDown writes one byte per
+// pixel; tests/cpp/cq_host_gray.cpp + tests/test_gray_color_kernel_host.py check it against the oracle on the gray image copied into B, G, R.
 #pragma once
 
 #include <stdint.h>
@@ -129,42 +133,76 @@ CQ_FN uint32_t orientation_label8(int dx, int dy) {
 }
 
 constexpr int TW = 64;   // tile width in output pixels
-template <int TH>
+// NC = colour planes of the source: 3 (BGR, interleaved) or 1 (a gray frame, LMX_CTX_GRAY).  Blur, Sobel and pyrDown work per plane and the
+// strongest-channel rule picks channel 0 of three equal planes, so NC = 1 on a gray image equals NC = 3 on that image copied into B, G and R.
+template <int TH, int NC = 3>
 struct Geo {   // sizes of one 64 x TH tile's working set; LDS layout
+  static_assert(NC == 3 || NC == 1, "BGR or gray sources");
   static constexpr int IW = TW + 10, IH = TH + 10, IS = 76;   // clamped source tile, halo 5: 74 x IH bytes per channel plane, row stride 76 (19 dwords)
   static constexpr int SH = TH + 4, SW = TW + 4;              // smoothed region, halo 2 (row stride 68 = 17 dwords)
   static constexpr int QH = TH + 2, QS = 68;                  // label region, halo 1: 66 columns used, row stride 68
   static constexpr int HP = IH / 2;                           // row pairs of the blur's horizontal pass (rows 2p, 2p + 1)
   static constexpr int PP = TH / 2 + 2;                       // row pairs of pyrDown's horizontal pass: pair q = rows (2q + 1, 2q + 2), q = 1 .. TH/2 + 2, stored at q - 1
-  static constexpr size_t SZ_IN = (size_t)3 * IH * IS, SZ_SM = (size_t)3 * SH * SW, SZ_H = (size_t)3 * HP * SW * 4, SZ_PH = (size_t)3 * PP * 32 * 4;
+  static constexpr size_t SZ_IN = (size_t)NC * IH * IS, SZ_SM = (size_t)NC * SH * SW, SZ_H = (size_t)NC * HP * SW * 4, SZ_PH = (size_t)NC * PP * 32 * 4;
   static constexpr size_t SZ_OH = (size_t)QH * QS * 4, SZ_FL = (size_t)QH * QS;
   // region 1: s_in (A -> Ph, Bh), then s_sm (Bv -> D).   region 2: s_ph (Ph -> Pv), then s_h (Bh -> Bv), then s_oh + s_fl (D -> E).
   static constexpr size_t OFF_R2 = (SZ_IN + 15) & ~(size_t)15;
   static constexpr size_t OFF_FL = OFF_R2 + SZ_OH;
-  static constexpr size_t LDS_BYTES = OFF_R2 + SZ_H;          // 26 720 bytes at TH = 32 (six workgroups per CU), 16 536 at TH = 16
+  // region 2 is as large as its largest tenant: s_h for three planes, s_oh + s_fl (one label plane whatever NC) for one
+  static constexpr size_t SZ_R2 = SZ_H > SZ_OH + SZ_FL ? (SZ_H > SZ_PH ? SZ_H : SZ_PH) : (SZ_OH + SZ_FL > SZ_PH ? SZ_OH + SZ_FL : SZ_PH);
+  // NC = 3: 26 720 bytes at TH = 32 (six workgroups per CU), 16 536 at TH = 16.  NC = 1: 14 760 at TH = 32, 8 104 at TH = 16
+  static constexpr size_t LDS_BYTES = OFF_R2 + SZ_R2;
   static_assert(TH % 4 == 0 && IH % 2 == 0, "row pairs");
-  static_assert(SZ_SM <= SZ_IN && SZ_PH <= SZ_H && SZ_OH + SZ_FL <= SZ_H, "tenants fit their regions");
+  static_assert(SZ_SM <= SZ_IN && SZ_PH <= SZ_R2 && SZ_H <= SZ_R2 && SZ_OH + SZ_FL <= SZ_R2, "tenants fit their regions");
 };
 
 // One tile.  `tid` runs over the 256 threads of the workgroup inside every stage; `run(stage)` calls stage(tid) for the calling thread and
 // ends with a barrier on the device, and loops tid over 0..255 on the host.
-template <int TH, bool TRAIN, typename Run>
+template <int TH, bool TRAIN, int NC = 3, typename Run>
 CQ_FN void color_quantize_tile(int tile_x, int tile_y, const uint8_t* __restrict__ src /* frame */, uint8_t* __restrict__ dst /* frame */,
                                uint8_t* __restrict__ pyr_dst /* frame or null */, float* __restrict__ mag_dst /* frame, TRAIN only */, int H, int W, float thr_sq,
                                uint8_t* __restrict__ s_raw, Run run) {
-  typedef Geo<TH> G;
+  typedef Geo<TH, NC> G;
   constexpr int IH = G::IH, IS = G::IS, SH = G::SH, SW = G::SW, QH = G::QH, QS = G::QS, HP = G::HP, PP = G::PP;
-  uint32_t* const s_in32 = reinterpret_cast<uint32_t*>(s_raw);                    // [3 * IH][19]
-  uint8_t* const s_in = s_raw;                                                    // [3 * IH][IS]
-  uint32_t* const s_r2 = reinterpret_cast<uint32_t*>(s_raw + G::OFF_R2);         // s_ph [3 * PP][32] | s_h [3 * HP][SW] | s_oh [QH][QS]
-  uint8_t* const s_sm = s_raw;                                                    // [3 * SH][SW]
+  uint32_t* const s_in32 = reinterpret_cast<uint32_t*>(s_raw);                    // [NC * IH][19]
+  uint8_t* const s_in = s_raw;                                                    // [NC * IH][IS]
+  uint32_t* const s_r2 = reinterpret_cast<uint32_t*>(s_raw + G::OFF_R2);         // s_ph [NC * PP][32] | s_h [NC * HP][SW] | s_oh [QH][QS]
+  uint8_t* const s_sm = s_raw;                                                    // [NC * SH][SW]
   uint8_t* const s_fl = s_raw + G::OFF_FL;                                        // [QH][QS]
   const int x0 = tile_x * TW, y0 = tile_y * TH;
 
   // ---- A: the clamped source tile (BORDER_REPLICATE of the blur), de-interleaved into three byte planes -------------------------------
   run([&](int tid) {
     if (LMX_CQ_SKIP & 1) return;
-    if (x0 >= 5 && x0 + IS - 5 <= W) {
+    if constexpr (NC == 1) {
+      // gray: the plane is the source row itself.  Interior columns: one dword per task, loaded as it lies (the segment starts at byte
+      // x0 - 5: not dword aligned, which the unaligned-access mode serves with one load, like the three dwords of the BGR path); all of a
+      // thread's loads are in flight before the first LDS store.  Columns near the image's sides: byte by byte, clamped.
+      if (x0 >= 5 && x0 + IS - 5 <= W) {
+        constexpr int NT = (IH * (IS / 4) + 255) / 256;
+        uint32_t d[NT];
+#pragma unroll
+        for (int k = 0; k < NT; ++k) {
+          const int i = tid + 256 * k;
+          if (i < IH * (IS / 4)) {
+            const int ly = i / (IS / 4), t = i - ly * (IS / 4);
+            const int gy = clampi(y0 - 5 + ly, 0, H - 1);
+            d[k] = load_u32(src + umul24((uint32_t)gy, (uint32_t)W) + (uint32_t)((x0 - 5) + 4 * t));
+          }
+        }
+#pragma unroll
+        for (int k = 0; k < NT; ++k) {
+          const int i = tid + 256 * k;
+          if (i < IH * (IS / 4)) s_in32[i] = d[k];   // [ly][t] = i: the plane's rows are 19 dwords, like the tasks
+        }
+      } else {
+        for (int i = tid; i < IH * IS; i += 256) {
+          const int ly = i / IS, lx = i - ly * IS;
+          const int gy = clampi(y0 - 5 + ly, 0, H - 1), gx = clampi(x0 - 5 + lx, 0, W - 1);
+          s_in[i] = src[(size_t)gy * W + gx];
+        }
+      }
+    } else if (x0 >= 5 && x0 + IS - 5 <= W) {
       // interior columns: 4 pixels = 3 dwords per task (the row segment starts at byte 3 * (x0 - 5): not dword aligned), de-interleaved with
       // v_perm_b32 into one dword per plane
       // a thread's tasks (IH * 19 / 256: three, for 30 threads of the tall tile four) are unrolled so that all their loads are in flight before
@@ -217,9 +255,9 @@ CQ_FN void color_quantize_tile(int tile_x, int tile_y, const uint8_t* __restrict
     const bool edge_x = X0 == 0 || X0 + 32 >= Wd;        // block-uniform: the tile holds output column 0 or Wd - 1
     const bool w_even = (W & 1) == 0, h_even = (H & 1) == 0;
     run([&](int tid) {
-      for (int i = tid; i < 3 * PP * 16; i += 256) {
+      for (int i = tid; i < NC * PP * 16; i += 256) {
         const int R = i >> 4, j = i & 15;                           // R = c * PP + (q - 1)
-        const int c = (R >= PP) + (R >= 2 * PP);
+        const int c = NC == 1 ? 0 : (R >= PP) + (R >= 2 * PP);
         const uint32_t* rowA = s_in32 + (2 * R + 3 + 6 * c) * (IS / 4) + j;   // tile row c * IH + 2q + 1  (IH - 2 PP = 6)
         const uint32_t* rowB = rowA + IS / 4;
         uint32_t wa0 = b4(0, 0, 0, 1), wa1 = b4(4, 6, 4, 1), wb0 = b4(0, 1, 4, 6), wb1 = b4(4, 1, 0, 0);
@@ -238,7 +276,7 @@ CQ_FN void color_quantize_tile(int tile_x, int tile_y, const uint8_t* __restrict
         *reinterpret_cast<u32x2*>(s_r2 + R * 32 + 2 * j) = out;
       }
     });
-    // Pv: vertical pass on the row pairs, two neighbouring output pixels (6 bytes of the BGR-interleaved next-level image) per thread
+    // Pv: vertical pass on the row pairs, two neighbouring output pixels (6 bytes of the BGR-interleaved next-level image, 2 of a gray one) per thread
     run([&](int tid) {
       const int Yl = tid >> 4, xp = tid & 15;
       const int Y = Y0 + Yl, X = X0 + 2 * xp;
@@ -246,21 +284,27 @@ CQ_FN void color_quantize_tile(int tile_x, int tile_y, const uint8_t* __restrict
         uint32_t w0 = h2(1, 4), w1 = h2(6, 4), w2 = h2(1, 0);
         if (Y == 0) { w0 = 0; w1 = h2(6, 8); w2 = h2(2, 0); }
         if (Y == Hd - 1 && h_even) { w1 = h2(7, 4); w2 = 0; }
-        uint32_t px[2][3];
+        uint32_t px[2][NC];
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
+        for (int c = 0; c < NC; ++c) {
           const uint32_t* p = s_r2 + (c * PP + Yl) * 32 + 2 * xp;     // pairs q = Yl + 1, + 2, + 3
           const u32x2 p0 = *reinterpret_cast<const u32x2*>(p), p1 = *reinterpret_cast<const u32x2*>(p + 32), p2 = *reinterpret_cast<const u32x2*>(p + 64);
           px[0][c] = udot2(p0.x, w0, udot2(p1.x, w1, udot2(p2.x, w2, 128u)));   // <= 255 * 256 + 128: the result is byte 1
           px[1][c] = udot2(p0.y, w0, udot2(p1.y, w1, udot2(p2.y, w2, 128u)));
         }
-        uint8_t* out = pyr_dst + (umul24((uint32_t)Y, (uint32_t)Wd) + (uint32_t)X) * 3u;
-        const uint32_t bg0 = perm(px[0][1], px[0][0], 0x0c0c0501u);      // b0 g0 . .
-        if (X + 1 < Wd) {
-          store_u32(out, perm(perm(px[1][0], px[0][2], 0x05010c0cu), bg0, 0x07060100u));   // b0 g0 r0 b1
-          store_u16(out + 4, perm(px[1][2], px[1][1], 0x0c0c0501u));                        // g1 r1
+        if constexpr (NC == 1) {
+          uint8_t* out = pyr_dst + umul24((uint32_t)Y, (uint32_t)Wd) + (uint32_t)X;
+          if (X + 1 < Wd) store_u16(out, perm(px[1][0], px[0][0], 0x0c0c0501u));   // p0 p1
+          else out[0] = (uint8_t)(px[0][0] >> 8);
         } else {
-          out[0] = (uint8_t)(px[0][0] >> 8); out[1] = (uint8_t)(px[0][1] >> 8); out[2] = (uint8_t)(px[0][2] >> 8);
+          uint8_t* out = pyr_dst + (umul24((uint32_t)Y, (uint32_t)Wd) + (uint32_t)X) * 3u;
+          const uint32_t bg0 = perm(px[0][1], px[0][0], 0x0c0c0501u);      // b0 g0 . .
+          if (X + 1 < Wd) {
+            store_u32(out, perm(perm(px[1][0], px[0][2], 0x05010c0cu), bg0, 0x07060100u));   // b0 g0 r0 b1
+            store_u16(out + 4, perm(px[1][2], px[1][1], 0x0c0c0501u));                        // g1 r1
+          } else {
+            out[0] = (uint8_t)(px[0][0] >> 8); out[1] = (uint8_t)(px[0][1] >> 8); out[2] = (uint8_t)(px[0][2] >> 8);
+          }
         }
       }
     });
@@ -271,8 +315,8 @@ CQ_FN void color_quantize_tile(int tile_x, int tile_y, const uint8_t* __restrict
   // the weight vector shifted by o bytes, a third dword for o >= 2), results (<= 65 280) packed per column as (row 2p, row 2p + 1).
   run([&](int tid) {
     if (LMX_CQ_SKIP & 4) return;
-    int R = tid / 17, xq = tid - R * 17;                    // R = c * HP + p: source rows 2R, 2R + 1 of the flat [3 * IH] plane stack
-    for (int i = tid; i < 3 * HP * 17; i += 256) {
+    int R = tid / 17, xq = tid - R * 17;                    // R = c * HP + p: source rows 2R, 2R + 1 of the flat [NC * IH] plane stack
+    for (int i = tid; i < NC * HP * 17; i += 256) {
       const uint32_t* rowA = s_in32 + (2 * R) * (IS / 4) + xq;
       const uint32_t* rowB = rowA + IS / 4;
       const uint32_t a0 = rowA[0], a1 = rowA[1], a2 = rowA[2], c0 = rowB[0], c1 = rowB[1], c2 = rowB[2];
@@ -294,8 +338,8 @@ CQ_FN void color_quantize_tile(int tile_x, int tile_y, const uint8_t* __restrict
   run([&](int tid) {
     if (LMX_CQ_SKIP & 8) return;
     int Rv = tid / 17, xq = tid - Rv * 17;                  // Rv = c * (SH / 2) + a
-    for (int i = tid; i < 3 * (SH / 2) * 17; i += 256) {
-      const int c = (Rv >= SH / 2) + (Rv >= SH);
+    for (int i = tid; i < NC * (SH / 2) * 17; i += 256) {
+      const int c = NC == 1 ? 0 : (Rv >= SH / 2) + (Rv >= SH);
       const uint32_t* p = s_r2 + (Rv + 3 * c) * SW + 4 * xq;     // pair c * HP + a  (HP - SH / 2 = 3)
       const u32x4 p0 = *reinterpret_cast<const u32x4*>(p), p1 = *reinterpret_cast<const u32x4*>(p + SW), p2 = *reinterpret_cast<const u32x4*>(p + 2 * SW),
                   p3 = *reinterpret_cast<const u32x4*>(p + 3 * SW);
@@ -344,10 +388,11 @@ CQ_FN void color_quantize_tile(int tile_x, int tile_y, const uint8_t* __restrict
         s_fl[ly * QS + lx] = (uint8_t)sign_mask(thr_i - bm);   // 0xff iff bm > thr_i
       };
       // strongest channel; upstream picks the first channel whose magnitude is >= both others: a later one only wins with a strictly greater one
-      auto strongest = [](const int (&dx)[3], const int (&dy)[3], int& bdx, int& bdy, int& bm) {
+      // (one plane: nothing to choose)
+      auto strongest = [](const int (&dx)[NC], const int (&dy)[NC], int& bdx, int& bdy, int& bm) {
         bm = mul24(dx[0], dx[0]) + mul24(dy[0], dy[0]); bdx = dx[0]; bdy = dy[0];
 #pragma unroll
-        for (int c = 1; c < 3; ++c) {
+        for (int c = 1; c < NC; ++c) {
           const int m = mul24(dx[c], dx[c]) + mul24(dy[c], dy[c]);
           const uint32_t gt = (uint32_t)sign_mask(bm - m);   // all ones iff m > bm (both < 2^22)
           bm = (int)select_mask((uint32_t)m, (uint32_t)bm, gt);
@@ -360,13 +405,13 @@ CQ_FN void color_quantize_tile(int tile_x, int tile_y, const uint8_t* __restrict
         const int cxm = INTERIOR ? lxq : clampi(gx - 1, 0, W - 1) - (x0 - 2);
         const int cxc = INTERIOR ? lxq + 1 : clampi(gx, 0, W - 1) - (x0 - 2);
         const int cxp = INTERIOR ? lxq + 2 : clampi(gx + 1, 0, W - 1) - (x0 - 2);
-        int Rw[3][3], Dw[3][3];  // [row slot][channel]: a + 2b + c and c - a of the row's three columns
+        int Rw[3][NC], Dw[3][NC];  // [row slot][channel]: a + 2b + c and c - a of the row's three columns
 #pragma unroll
         for (int k = 0; k < DROWS + 3; ++k) {
           if (k < count + 2) {  // wave-uniform
             const int rr = INTERIOR ? start + k : clampi(y0 - 2 + start + k, 0, H - 1) - (y0 - 2);
 #pragma unroll
-            for (int c = 0; c < 3; ++c) {
+            for (int c = 0; c < NC; ++c) {
               const uint8_t* row = s_sm + (c * SH + rr) * SW;
               // (Tried: ONE unaligned dword read per row and channel instead of three byte reads, a + 2b + c and c - a as dot4s.  Unaligned LDS
               // reads compile to a single ds_read_b32 on gfx950 but run far slower than three ds_read_u8: the kernel went from 0.145 to 0.215 ms
@@ -376,9 +421,9 @@ CQ_FN void color_quantize_tile(int tile_x, int tile_y, const uint8_t* __restrict
               Dw[k % 3][c] = cc - a;
             }
             if (k >= 2) {
-              int dx[3], dy[3];
+              int dx[NC], dy[NC];
 #pragma unroll
-              for (int c = 0; c < 3; ++c) {
+              for (int c = 0; c < NC; ++c) {
                 dx[c] = Dw[(k - 2) % 3][c] + 2 * Dw[(k - 1) % 3][c] + Dw[k % 3][c];
                 dy[c] = Rw[k % 3][c] - Rw[(k - 2) % 3][c];
               }
@@ -397,9 +442,9 @@ CQ_FN void color_quantize_tile(int tile_x, int tile_y, const uint8_t* __restrict
                            INTERIOR ? lxe + 2 : clampi(gx + 1, 0, W - 1) - (x0 - 2)};
         const int ry[3] = {INTERIOR ? ly : clampi(gy - 1, 0, H - 1) - (y0 - 2), INTERIOR ? ly + 1 : clampi(gy, 0, H - 1) - (y0 - 2),
                            INTERIOR ? ly + 2 : clampi(gy + 1, 0, H - 1) - (y0 - 2)};
-        int dx[3], dy[3];
+        int dx[NC], dy[NC];
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
+        for (int c = 0; c < NC; ++c) {
           int Rr[3], Dr[3];
 #pragma unroll
           for (int k = 0; k < 3; ++k) {

@@ -336,8 +336,7 @@ int upload_threads(const lmx_ctx* c) {
 
 // One modality's frames written straight into the frame set's host-visible device buffers (see FrameSet::store_buf).
 void store_modality(lmx_ctx* c, lmx_ctx::FrameSet& fs, int m, int n_frames, const lmx_image* sources) {
-  const bool cg = c->bank->mods[m].type == LMX_MOD_COLOR_GRADIENT;
-  const size_t row_bytes = (size_t)c->desc.width * (cg ? 3 : 2);
+  const size_t row_bytes = (size_t)c->desc.width * c->src_px_bytes(m);
   const int H = c->desc.height;
   // on the calling thread: one thread's non-temporal stores already fill the link's write direction (the microbenchmark: 45.7
   // GB/s with 1 thread, 44.5 with 8), and waking pool threads costs more than it could save
@@ -356,8 +355,7 @@ void store_modality(lmx_ctx* c, lmx_ctx::FrameSet& fs, int m, int n_frames, cons
 // Bands are numbered through the frames of the batch; `end` says who takes which (lmx_ctx.hpp).
 void lmx_ctx::store_modality_streamed(lmx_ctx::FrameSet& fs, int m, int n_frames, const lmx_image* sources, uint32_t seq, int end) {
   lmx_ctx* c = this;
-  const bool cg = c->bank->mods[m].type == LMX_MOD_COLOR_GRADIENT;
-  const size_t row_bytes = (size_t)c->desc.width * (cg ? 3 : 2);
+  const size_t row_bytes = (size_t)c->desc.width * c->src_px_bytes(m);   // the bands are rows, whatever a row's bytes (StreamWait counts rows)
   const int H = c->desc.height;
   // rows per progress update.  Every update costs two store fences (15 updates per modality at 32 rows: +5.5 us per 640x480 RGB-D frame, measured);
   // what streaming hides is the kernel's launch latency and everything but its last band, and the last band's tiles run in one round of
@@ -411,6 +409,7 @@ static lmx_status ctx_create_impl(lmx_ctx* c) {
   for (int lane = 1; lane < c->n_lanes; ++lane) LMX_HIP(hipStreamCreateWithFlags(&c->lane_stream[lane], hipStreamNonBlocking));
   LMX_HIP(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
   c->n_sets = c->n_lanes + 1;
+  c->color_ch = (c->desc.flags & LMX_CTX_GRAY) ? 1 : 3;
 
   lmx_status st = build_geometry(c);
   if (st != LMX_OK) return st;
@@ -419,17 +418,17 @@ static lmx_status ctx_create_impl(lmx_ctx* c) {
     const lmx_modality_desc& md = c->bank->mods[m];
     for (int set = 0; set < c->n_sets; ++set) {
       if (md.type == LMX_MOD_COLOR_GRADIENT) {
-        if ((st = dev_alloc(c, &c->sets[set].bgr[m], (size_t)F * c->desc.width * c->desc.height * 3, false)) != LMX_OK) return st;
+        if ((st = dev_alloc(c, &c->sets[set].bgr[m], (size_t)F * c->desc.width * c->desc.height * c->color_ch, false)) != LMX_OK) return st;
       } else {
         if ((st = dev_alloc(c, &c->sets[set].depth[m], (size_t)F * c->desc.width * c->desc.height, false)) != LMX_OK) return st;
       }
     }
-    c->frame_bytes[m] = (size_t)c->desc.width * c->desc.height * (md.type == LMX_MOD_COLOR_GRADIENT ? 3 : 2);
+    c->frame_bytes[m] = (size_t)c->desc.width * c->desc.height * c->src_px_bytes(m);
     for (int lane = 0; lane < c->n_lanes; ++lane) {
       FrameBuffers& fb = c->lane_fb[lane];  // the uploaded frames belong to the frame sets, everything derived from them is per lane
       for (int l = 0; l < c->L; ++l) {
         const LevelGeom& g = c->kp.geom[l];
-        if (md.type == LMX_MOD_COLOR_GRADIENT && l > 0 && (st = dev_alloc(c, &c->lane_bgr[lane][m][l], (size_t)F * g.W * g.H * 3, false)) != LMX_OK) return st;
+        if (md.type == LMX_MOD_COLOR_GRADIENT && l > 0 && (st = dev_alloc(c, &c->lane_bgr[lane][m][l], (size_t)F * g.W * g.H * c->color_ch, false)) != LMX_OK) return st;
         if ((st = dev_alloc(c, &fb.quant[l][m], (size_t)F * g.W * g.H, false)) != LMX_OK) return st;
         // pads must read as zero: clear once, kernels only ever write the matrices.  Byte + nibble-packed response memories
         // exist for the coarsest level only; finer levels keep the linearised spread image
@@ -688,8 +687,7 @@ lmx_status lmx_ctx_upload(lmx_ctx* c, int32_t n_frames, const lmx_image* sources
   const bool async_input = (c->desc.flags & LMX_CTX_ASYNC_INPUT) != 0;
   size_t off = 0;
   for (int m = 0; m < c->M; ++m) {
-    const bool cg = c->bank->mods[m].type == LMX_MOD_COLOR_GRADIENT;
-    const size_t row_bytes = (size_t)W * (cg ? 3 : 2);
+    const size_t row_bytes = (size_t)W * c->src_px_bytes(m);
     // LMX_PINNED_MODE (measurement switch): "pull" = one kernel pulls every pinned image, "dma" = one hipMemcpyAsync per image,
     // "stage" = treat pinned sources like pageable ones
     // Pinned caller memory is read in place only when the caller asked for it (LMX_CTX_ASYNC_INPUT: no host copy at all, the
@@ -733,7 +731,7 @@ lmx_status lmx_ctx_upload(lmx_ctx* c, int32_t n_frames, const lmx_image* sources
   off = 0;
   for (int m = 0; m < c->M; ++m) {
     const bool cg = c->bank->mods[m].type == LMX_MOD_COLOR_GRADIENT;
-    const size_t row_bytes = (size_t)W * (cg ? 3 : 2);
+    const size_t row_bytes = (size_t)W * c->src_px_bytes(m);
     uint8_t* dst = cg ? fs.bgr[m] : reinterpret_cast<uint8_t*>(fs.depth[m]);
     if (!direct[m]) {
       LMX_HIP(hipMemcpyAsync(dst, fs.h_stage + off, c->frame_bytes[m] * n_frames, hipMemcpyHostToDevice, c->copy_stream));
@@ -853,10 +851,11 @@ lmx_status ctx_check_sources(lmx_ctx* c, int n_frames, const lmx_image* sources,
     for (int m = 0; m < c->M; ++m) {
       const lmx_image& im = sources[(size_t)f * c->M + m];
       const bool cg = c->bank->mods[m].type == LMX_MOD_COLOR_GRADIENT;
-      const int want_ch = cg ? 3 : 1, want_es = cg ? 1 : 2;
+      const int want_ch = cg ? c->color_ch : 1, want_es = cg ? 1 : 2;
       if (!im.data || im.rows != H || im.cols != W) { set_error("frame %d source %d: size %dx%d != context %dx%d", f, m, im.cols, im.rows, W, H); return LMX_ERR_SHAPE; }
       if (im.channels != want_ch || im.elem_size != want_es) {
-        set_error("frame %d source %d: %s wants %s", f, m, cg ? "ColorGradient" : "DepthNormal", cg ? "8UC3" : "16UC1");
+        set_error("frame %d source %d: %s wants %s", f, m, cg ? "ColorGradient" : "DepthNormal",
+                  cg ? (c->color_ch == 1 ? "8UC1 (gray context)" : "8UC3") : "16UC1");
         return LMX_ERR_SHAPE;
       }
       if (im.row_stride_bytes < (size_t)W * want_ch * want_es) { set_error("frame %d source %d: row stride too small", f, m); return LMX_ERR_INVALID_ARG; }
@@ -875,8 +874,7 @@ void ctx_stage_sources(lmx_ctx* c, CopyPool* pool, uint8_t* base, int n_frames, 
   const int W = c->desc.width, H = c->desc.height;
   size_t off = 0;
   for (int m = 0; m < c->M; ++m) {
-    const bool cg = c->bank->mods[m].type == LMX_MOD_COLOR_GRADIENT;
-    const size_t row_bytes = (size_t)W * (cg ? 3 : 2);
+    const size_t row_bytes = (size_t)W * c->src_px_bytes(m);
     const int bands = n_frames >= 8 ? 1 : std::max(1, std::min(8, H / 64));
     for (int f = 0; f < n_frames; ++f) {
       const lmx_image& im = sources[(size_t)f * c->M + m];
@@ -971,6 +969,10 @@ lmx_status lmx_ctx_upload_raw(lmx_ctx* c, int32_t n_frames, const lmx_image* sou
   for (int m = 0; m < c->M; ++m) {
     const bool cg = c->bank->mods[m].type == LMX_MOD_COLOR_GRADIENT;
     const int ch = cg ? (pre->mono ? 1 : 3) : 1, es = cg ? 1 : (pre->depth_float_m ? 4 : 2);
+    if (cg && c->color_ch == 1 && !pre->mono) {   // no colour-to-gray conversion: upstream defines none
+      set_error("source %d: a gray context (LMX_CTX_GRAY) takes MONO8 colour sources only (lmx_pre_desc.mono = 1)", m);
+      return LMX_ERR_SHAPE;
+    }
     for (int f = 0; f < n_frames; ++f) {
       const lmx_image& im = sources[(size_t)f * c->M + m];
       const bool full = im.rows == pre->src_height && im.cols == pre->src_width;
@@ -1042,7 +1044,7 @@ lmx_status lmx_ctx_upload_raw(lmx_ctx* c, int32_t n_frames, const lmx_image* sou
     c->cur_stream = c->pre_stream;
     ScopedKernel k(c, K_PRE);
     if (c->bank->mods[m].type == LMX_MOD_COLOR_GRADIENT)
-      launch_pre_color(c->pre_stream, fs.d_raw + off, fs.bgr[m], r.sh, r.sw, r.ch, H, W, r.cx, r.cy, pre->blur3 ? 1 : 0, n_frames);
+      launch_pre_color(c->pre_stream, fs.d_raw + off, fs.bgr[m], r.sh, r.sw, r.ch, H, W, r.cx, r.cy, pre->blur3 ? 1 : 0, n_frames, c->color_ch);
     else
       launch_pre_depth(c->pre_stream, fs.d_raw + off, fs.depth[m], r.sh, r.sw, H, W, r.cx, r.cy, pre->depth_float_m ? 1 : 0, n_frames);
     off += r.bytes * n_frames;

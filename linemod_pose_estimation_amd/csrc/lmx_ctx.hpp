@@ -127,6 +127,8 @@ struct lmx_ctx {
   hipStream_t cur_stream = nullptr;  // stream of the stage being issued (ScopedKernel records its events there)
   int last_slot = 0;
   int L = 0, M = 0, F = 0;
+  int color_ch = 3;        // bytes per pixel of a ColorGradient source and of the colour pyramid: 3, or 1 with LMX_CTX_GRAY
+  int src_px_bytes(int m) const { return bank->mods[m].type == LMX_MOD_COLOR_GRADIENT ? color_ch : 2; }   // level-0 source bytes per pixel
   uint32_t cap_total = 0;  // capacity of the shared candidate / match lists (max_candidates * max_batch)
   KernelParams kp{};
   ModalityBuffers mb[kMaxModalities];

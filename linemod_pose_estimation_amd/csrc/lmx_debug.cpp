@@ -76,7 +76,7 @@ lmx_status lmx_ctx_debug_read(lmx_ctx* c, int32_t frame, int32_t what, int32_t l
     }
   } else if (what == LMX_DBG_PYRAMID_BGR) {
     if (c->bank->mods[modality].type != LMX_MOD_COLOR_GRADIENT) { set_error("debug_read: modality %d has no colour pyramid", modality); return LMX_ERR_INVALID_ARG; }
-    const size_t n = (size_t)g.W * g.H * 3;
+    const size_t n = (size_t)g.W * g.H * c->color_ch;   // [H_l][W_l][3], or [H_l][W_l] for a gray context
     if (out_bytes < n) { set_error("debug_read: buffer too small"); return LMX_ERR_INVALID_ARG; }
     LMX_HIP(hipMemcpy(out, c->mb[modality].bgr[level] + (size_t)frame * n, n, hipMemcpyDeviceToHost));
   } else if (what == LMX_DBG_DEPTH) {
@@ -163,8 +163,9 @@ lmx_status lmx_ctx_algorithmic_bytes(lmx_ctx* c, int32_t id, int32_t n_frames, d
   for (int m = 0; m < M; ++m) (b->mods[m].type == LMX_MOD_COLOR_GRADIENT ? n_cg : n_dn)++;
   switch (id) {
     case K_PRE: v = 0; break;  // depends on the raw frame size passed to upload_raw
-    case K_COLOR_QUANTIZE:  // 3 B in + 1 B out per pixel, + 3/4 B for the pyrDown output of the next level
-      for (int l = 0; l < L; ++l) v += n_cg * (4.0 + (l + 1 < L ? 0.75 : 0.0)) * c->kp.geom[l].W * c->kp.geom[l].H;
+    case K_COLOR_QUANTIZE:  // 3 B in + 1 B out per pixel, + 3/4 B for the pyrDown output of the next level (gray: 1 B in, 1/4 B pyrDown)
+      for (int l = 0; l < L; ++l)
+        v += n_cg * (c->color_ch + 1.0 + (l + 1 < L ? c->color_ch * 0.25 : 0.0)) * c->kp.geom[l].W * c->kp.geom[l].H;
       break;
     case K_DEPTH_QUANTIZE: v = n_dn * 3.0 * g0.W * g0.H; break;
     case K_NN_DOWN:

@@ -40,7 +40,7 @@ static lmx_status issue_pre(lmx_ctx* c, int32_t n_frames, hipStream_t s) {
         // the level-l kernel also writes the pyrDown'ed source of level l+1 (upstream: ColorGradientPyramid::pyrDown)
         ScopedKernel k(c, K_COLOR_QUANTIZE);
         launch_color_quantize(s, c->mb[m].bgr[l], c->kp.fb.quant[l][m], l + 1 < c->L ? c->mb[m].bgr[l + 1] : nullptr, g.H, g.W, n_frames,
-                              md.weak_threshold, nullptr, first ? reinterpret_cast<uint32_t*>(c->d_out) : nullptr);
+                              md.weak_threshold, nullptr, first ? reinterpret_cast<uint32_t*>(c->d_out) : nullptr, nullptr, c->color_ch);
         first = false;
       } else {
         if (l == 0) {
@@ -171,10 +171,10 @@ static lmx_status issue_small(lmx_ctx* c, int slot, int32_t n_frames, float thre
       const lmx_modality_desc& dn = c->bank->mods[1];
       ScopedKernel k(c, K_DEPTH_QUANTIZE);
       launch_small_depth_color(s, c->mb[1].depth, c->kp.fb.quant[0][1], c->kp.fb.quant[1][1], g0.H, g0.W, dn.distance_threshold, dn.difference_threshold, c->d_normal_bins,
-                               c->mb[0].bgr[1], c->kp.fb.quant[1][0], nullptr, g1.H, g1.W, cg.weak_threshold, n_frames, stream ? &wd : nullptr);
+                               c->mb[0].bgr[1], c->kp.fb.quant[1][0], nullptr, g1.H, g1.W, cg.weak_threshold, n_frames, stream ? &wd : nullptr, c->color_ch);
     } else {
       ScopedKernel k(c, K_COLOR_QUANTIZE);
-      launch_color_quantize(s, c->mb[0].bgr[1], c->kp.fb.quant[1][0], nullptr, g1.H, g1.W, n_frames, cg.weak_threshold, nullptr, nullptr);
+      launch_color_quantize(s, c->mb[0].bgr[1], c->kp.fb.quant[1][0], nullptr, g1.H, g1.W, n_frames, cg.weak_threshold, nullptr, nullptr, nullptr, c->color_ch);
     }
   };
   // spread of both levels, score, refine (+ read-back)
@@ -215,7 +215,7 @@ static lmx_status issue_small(lmx_ctx* c, int slot, int32_t n_frames, float thre
   auto launch_first = [&]() {
     ScopedKernel k(c, K_COLOR_QUANTIZE);
     launch_color_quantize(s, c->mb[0].bgr[0], c->kp.fb.quant[0][0], c->mb[0].bgr[1], g0.H, g0.W, n_frames, cg.weak_threshold, nullptr, reinterpret_cast<uint32_t*>(c->d_out),
-                          stream ? &wc : nullptr);
+                          stream ? &wc : nullptr, c->color_ch);
   };
   // With a helper thread the FIRST launch is its job too and this thread starts storing at once: a launch costs ~7 us (~120 us when the call finds
   // the device idle after a pause), the first tiles need the first band of rows anyway.  In a loop: 84.9 against 88.4 us per call; after a

@@ -388,7 +388,8 @@ struct StreamWait {
 void launch_color_quantize(hipStream_t s, const uint8_t* bgr, uint8_t* quant, uint8_t* pyr_next /* may be null */, int H, int W,
                            int n_frames, float weak_threshold, float* mag_out = nullptr /* trainer: squared magnitude per pixel */,
                            uint32_t* clear16 = nullptr /* 16 dwords zeroed by the first workgroup: the output slot's header */,
-                           const StreamWait* wait = nullptr /* small batches: the frame is still being stored by the host */);
+                           const StreamWait* wait = nullptr /* small batches: the frame is still being stored by the host */,
+                           int n_ch = 3 /* colour planes of bgr and pyr_next: 3, or 1 for a gray context (LMX_CTX_GRAY) */);
 lmx_status train_add_template(lmx_bank* bank, int device, const lmx_image* sources, int n_sources, const char* class_id,
                               const lmx_image* object_mask, int32_t* template_id, int32_t* bounding_box);
 void launch_depth_quantize(hipStream_t s, const uint16_t* depth, uint8_t* quant, uint8_t* quant_half, int H, int W, int n_frames, int distance_threshold,
@@ -440,7 +441,7 @@ struct SpreadBatch {
 };
 bool launch_spread_linearize_all(hipStream_t s, const SpreadBatch& b, int n_modalities, const LevelGeom& g, int n_frames);
 void launch_pre_color(hipStream_t s, const uint8_t* src, uint8_t* dst, int SH, int SW, int SC, int H, int W, int crop_x, int crop_y, int blur3,
-                      int n_frames);
+                      int n_frames, int dst_ch /* 3: BGR frame; 1: gray frame (LMX_CTX_GRAY, SC must be 1) */);
 void launch_pre_depth(hipStream_t s, const void* src, uint16_t* dst, int SH, int SW, int H, int W, int crop_x, int crop_y, int is_float,
                       int n_frames);
 void launch_debug_orientation_label(hipStream_t s, const short* dx, const short* dy, uint8_t* out, size_t n);
@@ -458,8 +459,9 @@ bool launch_refine(hipStream_t s, const DeviceBankView& bank, const KernelParams
 // Fused launches of the small-batch chain (lmx_enqueue.cpp issue_small): depth quantiser of level 0 + colour quantiser of level 1, and the
 // spread of both levels of a two-level bank.
 bool launch_small_depth_color(hipStream_t s, const uint16_t* depth, uint8_t* dq, uint8_t* dq_half, int H, int W, int distance_threshold, int difference_threshold,
-                              const uint8_t* lut_bins, const uint8_t* bgr1, uint8_t* cq1, uint8_t* pyr2, int H1, int W1, float weak_threshold, int n_frames,
-                              const StreamWait* wait = nullptr /* the depth frame is still being stored by the host */);
+                              const uint8_t* lut_bins, const uint8_t* col1, uint8_t* cq1, uint8_t* pyr2, int H1, int W1, float weak_threshold, int n_frames,
+                              const StreamWait* wait = nullptr /* the depth frame is still being stored by the host */,
+                              int n_ch = 3 /* colour planes of col1 / pyr2 (1: gray context) */);
 bool launch_small_spread(hipStream_t s, const SpreadBatch& b0, const LevelGeom& g0, const SpreadBatch& b1, const LevelGeom& g1, int n_mod, int n_frames);
 
 }  // namespace lmx

@@ -171,12 +171,13 @@ struct CqRun {   // one stage of the tile for the calling thread, then the barri
   }
 };
 
-template <int TH, bool TRAIN>
+// NC: colour planes of src and pyr_dst (3 = BGR; 1 = gray, LMX_CTX_GRAY).  The streamed wait counts rows, the same for both.
+template <int TH, bool TRAIN, int NC = 3>
 __device__ __forceinline__ void color_quantize_body(const uint3 bid, const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
                                                     uint8_t* __restrict__ pyr_dst, float* __restrict__ mag_dst, int H, int W, float thr_sq,
                                                     uint32_t* __restrict__ clear16, int n_frames_x, const StreamWait wait = StreamWait()) {
   static_assert(TH == 16 || TH == 32, "tile heights the launchers use");
-  __shared__ __align__(16) uint8_t s_raw[cq::Geo<TH>::LDS_BYTES];
+  __shared__ __align__(16) uint8_t s_raw[cq::Geo<TH, NC>::LDS_BYTES];
   // first kernel of a batch's chain: clears the output slot's 64-byte header (candidate / match counters) in passing, which
   // saves the chain a separate memset kernel (4 us + a launch gap, 10 % of a single-frame step)
   if (clear16 != nullptr && (bid.x | bid.y | bid.z) == 0) clear_slot_counters(clear16, (int)threadIdx.x);
@@ -185,16 +186,16 @@ __device__ __forceinline__ void color_quantize_body(const uint3 bid, const uint8
   // streamed input: the tile reads source rows y0 - 5 .. y0 + TH + 4 of its frame
   if (wait.flag != nullptr && !stream_wait_rows(wait, (uint32_t)(frame * H + max(0, tile_y * TH - 5)), (uint32_t)(frame * H + min(H, tile_y * TH + TH + 5)))) return;
   const size_t px = (size_t)H * W;
-  cq::color_quantize_tile<TH, TRAIN>(tile_x, tile_y, src + (size_t)frame * px * 3, dst + (size_t)frame * px,
-                                     pyr_dst ? pyr_dst + (size_t)frame * (H >> 1) * (W >> 1) * 3 : nullptr, TRAIN ? mag_dst + (size_t)frame * px : nullptr, H, W, thr_sq,
-                                     s_raw, CqRun{});
+  cq::color_quantize_tile<TH, TRAIN, NC>(tile_x, tile_y, src + (size_t)frame * px * NC, dst + (size_t)frame * px,
+                                         pyr_dst ? pyr_dst + (size_t)frame * (H >> 1) * (W >> 1) * NC : nullptr, TRAIN ? mag_dst + (size_t)frame * px : nullptr, H, W, thr_sq,
+                                         s_raw, CqRun{});
 }
-template <int TH, bool TRAIN>
+template <int TH, bool TRAIN, int NC = 3>
 __global__ __launch_bounds__(256) void k_color_quantize(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
                                                         uint8_t* __restrict__ pyr_dst, float* __restrict__ mag_dst, int H, int W, float thr_sq,
                                                         uint32_t* __restrict__ clear16, int n_frames_x, StreamWait wait) {
   if (LMX_PRIO_QUANT) __builtin_amdgcn_s_setprio(LMX_PRIO_QUANT);
-  color_quantize_body<TH, TRAIN>(make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), src, dst, pyr_dst, mag_dst, H, W, thr_sq, clear16, n_frames_x, wait);
+  color_quantize_body<TH, TRAIN, NC>(make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), src, dst, pyr_dst, mag_dst, H, W, thr_sq, clear16, n_frames_x, wait);
 }
 
 // =========================================================================================================
@@ -499,11 +500,11 @@ __global__ __launch_bounds__(256) void k_depth_quantize(const uint16_t* __restri
 // body, the rest the colour body; static LDS of both bodies adds up (~40 KB), which does not matter at this size.
 struct SmallQuantArgs {
   const uint16_t* depth; uint8_t* dq; uint8_t* dq_half; int H, W, distance_threshold, difference_threshold; const uint8_t* lut_bins;
-  const uint8_t* bgr1; uint8_t* cq1; uint8_t* pyr2; int H1, W1; float thr_sq;
+  const uint8_t* col1; uint8_t* cq1; uint8_t* pyr2; int H1, W1; float thr_sq;   // col1 / pyr2: NC colour planes (k_small_depth_color's NC)
   int n_depth, dtx, dty, ctx, cty;
   StreamWait wait;   // for the depth workgroups
 };
-template <typename IntT>
+template <typename IntT, int NC = 3>
 __global__ __launch_bounds__(256) void k_small_depth_color(SmallQuantArgs a) {
   if ((int)blockIdx.x < a.n_depth) {
     const int b = (int)blockIdx.x, per = a.dtx * a.dty, f = b / per, t = b - f * per;
@@ -511,7 +512,7 @@ __global__ __launch_bounds__(256) void k_small_depth_color(SmallQuantArgs a) {
                               a.difference_threshold, a.lut_bins, nullptr, 0, a.wait);
   } else {
     const int b = (int)blockIdx.x - a.n_depth, per = a.ctx * a.cty, f = b / per, t = b - f * per;
-    color_quantize_body<CQ_TH, false>(make_uint3((unsigned)(t % a.ctx), (unsigned)(t / a.ctx), (unsigned)f), a.bgr1, a.cq1, a.pyr2, nullptr, a.H1, a.W1, a.thr_sq, nullptr, 0);
+    color_quantize_body<CQ_TH, false, NC>(make_uint3((unsigned)(t % a.ctx), (unsigned)(t / a.ctx), (unsigned)f), a.col1, a.cq1, a.pyr2, nullptr, a.H1, a.W1, a.thr_sq, nullptr, 0);
   }
 }
 
@@ -1642,20 +1643,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
 
 // =========================================================================================================
 // node-side steps in front of match(), on the device.
-// k_pre_color: (MONO8 -> BGR) + GaussianBlur 3x3 (sigma 0 -> [1 2 1]/4 per axis, exact: (sum + 8) >> 4, BORDER_REFLECT_101
+// k_pre_color<DC>: (MONO8 -> BGR, or MONO8 -> MONO8 with DC = 1 for a gray context) + GaussianBlur 3x3 (sigma 0 -> [1 2 1]/4 per axis, exact: (sum + 8) >> 4, BORDER_REFLECT_101
 // on the FULL frame) + crop, written straight into the level-0 colour buffer.  One thread per output byte.
 // k_pre_depth: float metres -> u16 millimetres like convertTo(CV_16UC1, 1000.0): v = z * 1000.f, cvRound (half to even),
 // saturate; NaN / Inf / |v| >= 2^31 take x86's "integer indefinite" and saturate to 0 (upstream behaviour on x86-64).
 // =========================================================================================================
+template <int DC>
 __global__ __launch_bounds__(256) void k_pre_color(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int SH, int SW, int SC, int H,
                                                    int W, int crop_x, int crop_y, int blur3) {
   const int frame = blockIdx.z;
   src += (size_t)frame * SH * SW * SC;
-  dst += (size_t)frame * H * W * 3;
+  dst += (size_t)frame * H * W * DC;
   const int j = blockIdx.x * 256 + threadIdx.x;
   const int y = blockIdx.y;
-  if (j >= W * 3) return;
-  const int x = j / 3, c = j - x * 3;
+  if (j >= W * DC) return;
+  const int x = j / DC, c = j - x * DC;
   const int sc = SC == 1 ? 0 : c;
   const int sy = crop_y + y, sx = crop_x + x;
   int v;
@@ -1671,7 +1673,7 @@ __global__ __launch_bounds__(256) void k_pre_color(const uint8_t* __restrict__ s
   } else {
     v = src[((size_t)sy * SW + sx) * SC + sc];
   }
-  dst[((size_t)y * W + x) * 3 + c] = (uint8_t)v;
+  dst[((size_t)y * W + x) * DC + c] = (uint8_t)v;
 }
 
 __global__ __launch_bounds__(256) void k_pre_depth(const void* __restrict__ src, uint16_t* __restrict__ dst, int SH, int SW, int H, int W,
@@ -1789,8 +1791,9 @@ void launch_copy_bytes(hipStream_t s, void* dst, const void* src, size_t bytes) 
 }
 
 void launch_pre_color(hipStream_t s, const uint8_t* src, uint8_t* dst, int SH, int SW, int SC, int H, int W, int crop_x, int crop_y, int blur3,
-                      int n_frames) {
-  hipLaunchKernelGGL(k_pre_color, dim3((W * 3 + 255) / 256, H, n_frames), dim3(256), 0, s, src, dst, SH, SW, SC, H, W, crop_x, crop_y, blur3);
+                      int n_frames, int dst_ch) {
+  if (dst_ch == 1) hipLaunchKernelGGL(k_pre_color<1>, dim3((W + 255) / 256, H, n_frames), dim3(256), 0, s, src, dst, SH, SW, SC, H, W, crop_x, crop_y, blur3);
+  else hipLaunchKernelGGL(k_pre_color<3>, dim3((W * 3 + 255) / 256, H, n_frames), dim3(256), 0, s, src, dst, SH, SW, SC, H, W, crop_x, crop_y, blur3);
 }
 void launch_pre_depth(hipStream_t s, const void* src, uint16_t* dst, int SH, int SW, int H, int W, int crop_x, int crop_y, int is_float,
                       int n_frames) {
@@ -1811,7 +1814,7 @@ static size_t lds_pad(const char* env, size_t dflt) {
 }
 
 void launch_color_quantize(hipStream_t s, const uint8_t* bgr, uint8_t* quant, uint8_t* pyr_next, int H, int W, int n_frames, float weak_threshold,
-                           float* mag_out, uint32_t* clear16, const StreamWait* wait) {
+                           float* mag_out, uint32_t* clear16, const StreamWait* wait, int n_ch) {
   const StreamWait sw = wait ? *wait : StreamWait();
   const bool xcd = n_frames >= 8;   // XCD-aware tile placement, see tile_of_block
   // batches take the tall tile (less halo per output); one or two frames per call keep 16 rows: twice the workgroups for a launch that
@@ -1825,6 +1828,13 @@ void launch_color_quantize(hipStream_t s, const uint8_t* bgr, uint8_t* quant, ui
   const float thr_sq = weak_threshold * weak_threshold;
   const int nfx = xcd ? n_frames : 0;
   // the trainer's instantiation also writes the squared magnitudes (extractTemplate ranks candidates by them)
+  if (n_ch == 1) {   // gray context: the one-plane tile, same tile choice
+    if (tall && mag_out) hipLaunchKernelGGL((k_color_quantize<CQ_TH_TALL, true, 1>), grid, dim3(256), pad, s, bgr, quant, pyr_next, mag_out, H, W, thr_sq, clear16, nfx, sw);
+    else if (tall) hipLaunchKernelGGL((k_color_quantize<CQ_TH_TALL, false, 1>), grid, dim3(256), pad, s, bgr, quant, pyr_next, mag_out, H, W, thr_sq, clear16, nfx, sw);
+    else if (mag_out) hipLaunchKernelGGL((k_color_quantize<CQ_TH, true, 1>), grid, dim3(256), pad, s, bgr, quant, pyr_next, mag_out, H, W, thr_sq, clear16, nfx, sw);
+    else hipLaunchKernelGGL((k_color_quantize<CQ_TH, false, 1>), grid, dim3(256), pad, s, bgr, quant, pyr_next, mag_out, H, W, thr_sq, clear16, nfx, sw);
+    return;
+  }
   if (tall && mag_out) hipLaunchKernelGGL((k_color_quantize<CQ_TH_TALL, true>), grid, dim3(256), pad, s, bgr, quant, pyr_next, mag_out, H, W, thr_sq, clear16, nfx, sw);
   else if (tall) hipLaunchKernelGGL((k_color_quantize<CQ_TH_TALL, false>), grid, dim3(256), pad, s, bgr, quant, pyr_next, mag_out, H, W, thr_sq, clear16, nfx, sw);
   else if (mag_out) hipLaunchKernelGGL((k_color_quantize<CQ_TH, true>), grid, dim3(256), pad, s, bgr, quant, pyr_next, mag_out, H, W, thr_sq, clear16, nfx, sw);
@@ -1972,17 +1982,23 @@ bool launch_refine(hipStream_t s, const DeviceBankView& bank, const KernelParams
 
 // ---- fused launches of the small-batch chain (one or two frames per call) -------------------------------------------------------
 bool launch_small_depth_color(hipStream_t s, const uint16_t* depth, uint8_t* dq, uint8_t* dq_half, int H, int W, int distance_threshold, int difference_threshold,
-                              const uint8_t* lut_bins, const uint8_t* bgr1, uint8_t* cq1, uint8_t* pyr2, int H1, int W1, float weak_threshold, int n_frames,
-                              const StreamWait* wait) {
+                              const uint8_t* lut_bins, const uint8_t* col1, uint8_t* cq1, uint8_t* pyr2, int H1, int W1, float weak_threshold, int n_frames,
+                              const StreamWait* wait, int n_ch) {
   SmallQuantArgs a;
   a.wait = wait ? *wait : StreamWait();
   a.depth = depth; a.dq = dq; a.dq_half = dq_half; a.H = H; a.W = W; a.distance_threshold = distance_threshold; a.difference_threshold = difference_threshold;
-  a.lut_bins = lut_bins; a.bgr1 = bgr1; a.cq1 = cq1; a.pyr2 = pyr2; a.H1 = H1; a.W1 = W1; a.thr_sq = weak_threshold * weak_threshold;
+  a.lut_bins = lut_bins; a.col1 = col1; a.cq1 = cq1; a.pyr2 = pyr2; a.H1 = H1; a.W1 = W1; a.thr_sq = weak_threshold * weak_threshold;
   a.dtx = (W + 63) / 64; a.dty = (H + DQ_TH - 1) / DQ_TH; a.ctx = (W1 + CQ_TW - 1) / CQ_TW; a.cty = (H1 + CQ_TH - 1) / CQ_TH;
   a.n_depth = a.dtx * a.dty * n_frames;
   const unsigned grid = (unsigned)(a.n_depth + a.ctx * a.cty * n_frames);
-  if (difference_threshold <= 200) hipLaunchKernelGGL(k_small_depth_color<int>, dim3(grid), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(k_small_depth_color<long long>, dim3(grid), dim3(256), 0, s, a);
+  if (n_ch == 1) {
+    if (difference_threshold <= 200) hipLaunchKernelGGL((k_small_depth_color<int, 1>), dim3(grid), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((k_small_depth_color<long long, 1>), dim3(grid), dim3(256), 0, s, a);
+  } else if (difference_threshold <= 200) {
+    hipLaunchKernelGGL(k_small_depth_color<int>, dim3(grid), dim3(256), 0, s, a);
+  } else {
+    hipLaunchKernelGGL(k_small_depth_color<long long>, dim3(grid), dim3(256), 0, s, a);
+  }
   return true;
 }
 

@@ -170,12 +170,15 @@ lmx_status train_add_template(lmx_bank* bank, int device, const lmx_image* sourc
   if (n_sources != M) { set_error("sources.size()=%d != modalities.size()=%d", n_sources, M); return LMX_ERR_SHAPE; }
   const int H0 = sources[0].rows, W0 = sources[0].cols;
   if (H0 < 16 || W0 < 16) { set_error("source image too small"); return LMX_ERR_SHAPE; }
+  // ColorGradient sources are 8UC3, or 8UC1 (a gray image: the one-plane quantiser, whose templates equal those of the image copied into
+  // B, G and R)
   for (int m = 0; m < M; ++m) {
     const bool cg = bank->mods[m].type == LMX_MOD_COLOR_GRADIENT;
     const lmx_image& im = sources[m];
-    if (!im.data || im.rows != H0 || im.cols != W0 || im.channels != (cg ? 3 : 1) || im.elem_size != (cg ? 1 : 2) ||
-        im.row_stride_bytes < (size_t)W0 * (cg ? 3 : 2)) {
-      set_error("source %d: expected %s of size %dx%d", m, cg ? "8UC3" : "16UC1", W0, H0);
+    const bool ch_ok = cg ? (im.channels == 3 || im.channels == 1) : im.channels == 1;
+    if (!im.data || im.rows != H0 || im.cols != W0 || !ch_ok || im.elem_size != (cg ? 1 : 2) ||
+        im.row_stride_bytes < (size_t)W0 * (cg ? im.channels : 2)) {
+      set_error("source %d: expected %s of size %dx%d", m, cg ? "8UC3 or 8UC1" : "16UC1", W0, H0);
       return LMX_ERR_SHAPE;
     }
   }
@@ -212,8 +215,9 @@ lmx_status train_add_template(lmx_bank* bank, int device, const lmx_image* sourc
     for (int m = 0; m < M; ++m) {
       const lmx_modality_desc& md = bank->mods[m];
       const bool cg = md.type == LMX_MOD_COLOR_GRADIENT;
-      const size_t px0 = (size_t)H0 * W0, row_bytes = (size_t)W0 * (cg ? 3 : 2);
-      std::vector<uint8_t> packed(px0 * (cg ? 3 : 2));
+      const int px_bytes = cg ? sources[m].channels : 2;   // colour: 3 (BGR) or 1 (gray)
+      const size_t px0 = (size_t)H0 * W0, row_bytes = (size_t)W0 * px_bytes;
+      std::vector<uint8_t> packed(px0 * px_bytes);
       for (int y = 0; y < H0; ++y) std::memcpy(&packed[(size_t)y * row_bytes], (const uint8_t*)sources[m].data + (size_t)y * sources[m].row_stride_bytes, row_bytes);
       void* d_src = dmalloc(packed.size());
       if (!d_src) { set_error("hipMalloc failed"); return LMX_ERR_HIP; }
@@ -229,9 +233,9 @@ lmx_status train_add_template(lmx_bank* bank, int device, const lmx_image* sourc
         labels[m][l].resize((size_t)h * w);
         if (cg) {
           float* d_mag = (float*)dmalloc((size_t)h * w * 4);
-          uint8_t* d_next = l + 1 < L ? (uint8_t*)dmalloc((size_t)(h / 2) * (w / 2) * 3) : nullptr;
+          uint8_t* d_next = l + 1 < L ? (uint8_t*)dmalloc((size_t)(h / 2) * (w / 2) * px_bytes) : nullptr;
           if (!d_mag || (l + 1 < L && !d_next)) { set_error("hipMalloc failed"); return LMX_ERR_HIP; }
-          launch_color_quantize(nullptr, d_cur_src, d_q, d_next, h, w, 1, md.weak_threshold, d_mag);
+          launch_color_quantize(nullptr, d_cur_src, d_q, d_next, h, w, 1, md.weak_threshold, d_mag, nullptr, nullptr, px_bytes);
           TR_HIP(hipDeviceSynchronize());
           mags[m][l].resize((size_t)h * w);
           TR_HIP(hipMemcpy(mags[m][l].data(), d_mag, (size_t)h * w * 4, hipMemcpyDeviceToHost));

@@ -201,7 +201,7 @@ class Detector:
     rgbdDetector::linemod_detection (/root/reference/src/rgbdDetector.cpp:33)."""
 
     def __init__(self, bank, width, height, device=0, max_batch=1, max_candidates=0, shard_rank=0, shard_world=1, stream=None, hipgraph=False, overlap=False,
-                 async_input=False):
+                 async_input=False, gray=False):
         if isinstance(bank, TemplateBank):
             self.native_bank = NativeBank.from_bank(bank)
             self.bank = bank
@@ -211,7 +211,10 @@ class Detector:
         else:
             raise TypeError("bank must be a TemplateBank or NativeBank")
         self.width, self.height, self.max_batch = width, height, max_batch
-        desc = _lib.CtxDesc(device, width, height, max_batch, max_candidates, shard_rank, shard_world, stream, (1 if hipgraph else 0) | (2 if overlap else 0) | (4 if async_input else 0))
+        # gray (LMX_CTX_GRAY): ColorGradient sources are uint8 HxW (a MONO8 frame) instead of HxWx3; matches equal those of the frame copied into B, G, R
+        self.gray = bool(gray)
+        desc = _lib.CtxDesc(device, width, height, max_batch, max_candidates, shard_rank, shard_world, stream,
+                            (1 if hipgraph else 0) | (2 if overlap else 0) | (4 if async_input else 0) | (_lib.LMX_CTX_GRAY if gray else 0))
         self.h = C.c_void_p()
         _lib.check(_lib.lib().lmx_ctx_create(self.native_bank.h, C.byref(desc), C.byref(self.h)))
         self._class_ids = self.native_bank.class_ids()
@@ -412,8 +415,9 @@ class Detector:
         return out
 
     def debug_pyramid_bgr(self, frame, level, modality=0):
+        """Colour source of pyramid level `level`: (H_l, W_l, 3), or (H_l, W_l) on a gray detector."""
         H, W = self.level_shape(level)
-        out = np.empty((H, W, 3), np.uint8)
+        out = np.empty((H, W) if self.gray else (H, W, 3), np.uint8)
         _lib.check(_lib.lib().lmx_ctx_debug_read(self.h, frame, _lib.LMX_DBG_PYRAMID_BGR, level, modality, out.ctypes.data, out.nbytes))
         return out
 

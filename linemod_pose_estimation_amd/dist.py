@@ -65,7 +65,7 @@ class ShardedMatcher:
     gathered blocks to the host and merge, the others return None from `finish` (a job whose consumer lives on rank 0)."""
 
     def __init__(self, bank, width, height, max_batch=1, gather_capacity=8192, max_candidates=0, group=None, overlap=True, result_ranks=None, frame_groups=1,
-                 hipgraph=False):
+                 hipgraph=False, gray=False):
         from .detector import Detector
         self.group = group
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
@@ -88,7 +88,7 @@ class ShardedMatcher:
             dist.all_gather_into_tensor(torch.empty(256 * self.world, dtype=torch.uint8, device=self.device), warm, group=group)
             torch.cuda.synchronize(self.device)
         self.det = Detector(bank, width, height, device=self.device.index, max_batch=(max_batch + self.G - 1) // self.G, max_candidates=max_candidates,
-                            shard_rank=self.shard, shard_world=self.R, overlap=overlap, hipgraph=hipgraph)
+                            shard_rank=self.shard, shard_world=self.R, overlap=overlap, hipgraph=hipgraph, gray=gray)
         self.depth = self.det.max_outstanding
         self.capacity = gather_capacity          # for ring entries (re)allocated from now on
         self.wants_result = result_ranks is None or self.rank in result_ranks
@@ -214,14 +214,15 @@ class DeviceGroup:
     path is the C++ one the reference's caller would use; this class only marshals frames and results."""
 
     def __init__(self, bank, width, height, n_members, devices=None, max_batch=1, gather_capacity=8192, max_candidates=0, collective="rccl",
-                 overlap=True, hipgraph=False, frame_groups=1):
+                 overlap=True, hipgraph=False, frame_groups=1, gray=False):
         import ctypes as C
         from .detector import NativeBank
         from .bank import TemplateBank
         self.native_bank = NativeBank.from_bank(bank) if isinstance(bank, TemplateBank) else bank
         devs = list(devices) if devices is not None else list(range(n_members))
         self._devs = (C.c_int32 * n_members)(*devs)
-        desc = _lib.GroupDesc(n_members, self._devs, width, height, max_batch, max_candidates, gather_capacity, (1 if hipgraph else 0) | (2 if overlap else 0), None, 0, 0, 0,
+        desc = _lib.GroupDesc(n_members, self._devs, width, height, max_batch, max_candidates, gather_capacity,
+                              (1 if hipgraph else 0) | (2 if overlap else 0) | (_lib.LMX_CTX_GRAY if gray else 0), None, 0, 0, 0,
                               {"rccl": 0, "peer_copy": 1}[collective], frame_groups)
         self.h = C.c_void_p()
         _lib.check(_lib.lib().lmx_group_create(self.native_bank.h, C.byref(desc), C.byref(self.h)))
