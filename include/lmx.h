@@ -492,6 +492,36 @@ lmx_status lmx_ctx_set_cluster_sidecar(lmx_ctx* ctx, const double* obj_origin_di
 lmx_status lmx_ctx_collect_clusters(lmx_ctx* ctx, int32_t n_frames, lmx_match_t* matches, size_t cap_matches, size_t* match_offsets,
                                     lmx_cluster_t* clusters, size_t cap_clusters, size_t* cluster_offsets, int32_t* members, size_t cap_members);
 
+/* ---- training from a mesh: the reference's trainer (src/renderer.cpp:239-349, launch/start_object_renderer.launch) ----------------
+ * The trainer renders the object's mesh from a list of view points, hands image + depth + silhouette to Detector::addTemplate and
+ * writes `*_templates.yml` plus the `*_renderer_params.yml` side-car.  Here the renderer is a z-buffer rasteriser on the device
+ * (csrc/lmx_mesh.hip; upstream's is OpenGL): per view (R, distance) the mesh is seen with X_cam = R X_obj + (0, 0, distance) through
+ * the pinhole u = fx X / Z + cx, v = fy Y / Z + cy; a pixel is covered when its centre lies inside a triangle, the nearest triangle
+ * wins (the lowest triangle index among equal depths), depth is perspective-correct, the shade of a face is Lambertian, two-sided,
+ * 0.25 ambient: gray = rint(40 + 190 * (0.25 + 0.75 |n . l| / |n|)), depth_mm = rint(1000 z), both 0 off the object, mask 255 on it,
+ * rect = {x, y, w, h} of the covered pixels ({0, 0, 0, 0} when none).  All of it in double, bit-identical on every run and batch size.
+ * A view that puts a vertex at Z <= 0.01 is invalid: the call returns LMX_ERR_INVALID_ARG, the error text names the view's index,
+ * and lmx_bank_train_mesh adds nothing to the bank.  The views themselves (upstream's RendererIterator) are the caller's input. */
+typedef struct lmx_mesh_camera { int32_t width, height; double fx, fy, cx, cy; double light[3]; } lmx_mesh_camera;
+typedef struct lmx_mesh_view   { double R[9]; double distance; } lmx_mesh_view;        /* X_cam = R X_obj + (0,0,distance) */
+/* Renderer3d + RendererIterator::render as the trainers use them (src/renderer.cpp:239-275); outputs are host arrays, any may be NULL:
+ * gray u8, depth_mm u16, mask u8 [n_views][height][width], rects int32 [n_views][4]. */
+lmx_status lmx_mesh_render(int32_t device, const double* triangles /*[n][3][3] m*/, int32_t n_triangles, const lmx_mesh_camera* cam,
+                           const lmx_mesh_view* views, int32_t n_views, uint8_t* gray, uint16_t* depth_mm, uint8_t* mask, int32_t* rects);
+/* The trainer loop of src/renderer.cpp:262-329: render, addTemplate(sources, class_id, mask), keep the pose of every accepted view.
+ * Views are rendered and quantised in batches on the device (the pixels never cross PCIe; the gray render feeds the one-plane colour
+ * quantiser, whose templates equal those of the frame copied into B, G and R, so the result equals a loop of lmx_bank_add_template over
+ * the rendered views: templates are appended in view order, a view addTemplate rejects adds nothing).  ColorGradient modalities get
+ * the gray render, DepthNormal modalities the depth.  template_ids[v] = the new template id of view v, or -1.
+ * *side_car (free with lmx_renderer_params_free) holds one entry per ACCEPTED view, filled as src/renderer.cpp:278-323 does:
+ * Rect = silhouette rect, Ori_dist = the view's distance, R = the view's rotation, T = (0, 0, distance),
+ * K = (fx, 0, width / 2; 0, fy, height / 2; 0, 0, 1) through float, D = Ori_dist - float(depth_mm[height / 2][width / 2]) / 1000.0f,
+ * renderer_width / _height / _focal_length_* from the camera; the iterator's scalars (renderer_n_points, _angle_step, _radius_*,
+ * _near, _far) start at 0 and are the caller's to set. */
+lmx_status lmx_bank_train_mesh(lmx_bank* bank, int32_t device, const double* triangles, int32_t n_triangles, const lmx_mesh_camera* cam,
+                               const lmx_mesh_view* views, int32_t n_views, const char* class_id,
+                               int32_t* template_ids /*[n_views], -1 = rejected; may be NULL*/, lmx_renderer_params** side_car /*may be NULL*/);
+
 /* ---- introspection (stage-level parity tests, profiling) ------------------------------------------------- */
 enum {
   LMX_DBG_QUANTIZED = 0,     /* u8 [H_l][W_l] one-hot labels after quantize(), A.2/A.4 */

@@ -89,6 +89,27 @@ class Detector {
   }
   void write(const std::string& filename) const { check(lmx_bank_save_yaml(bank_, filename.c_str())); }
 
+  // A detector that starts empty: cv::linemod::Detector(modalities, T) as the reference's trainers build it (src/renderer.cpp:179-185).
+  void create(const std::vector<lmx_modality_desc>& modalities, const std::vector<int>& T) {
+    reset();
+    std::vector<int32_t> t(T.begin(), T.end());
+    lmx_bank_desc d;
+    d.pyramid_levels = (int32_t)t.size(); d.T = t.data(); d.n_modalities = (int32_t)modalities.size(); d.modalities = modalities.data();
+    check(lmx_bank_create(&d, &bank_));
+  }
+
+  // The trainer loop of src/renderer.cpp:262-329 (lmx_bank_train_mesh): renders `triangles` ([n][3][3] doubles, metres) from every view on
+  // the device and adds a template per view addTemplate accepts, in view order.  -> the template id per view (-1: rejected).  `side_car`
+  // (may be null) receives the renderer-params side-car of the accepted views; free it with lmx_renderer_params_free.
+  std::vector<int> addTemplatesFromMesh(const std::vector<double>& triangles, const lmx_mesh_camera& camera, const std::vector<lmx_mesh_view>& views,
+                                        const std::string& class_id, lmx_renderer_params** side_car = nullptr) {
+    if (triangles.size() % 9 != 0) throw Exception(LMX_ERR_SHAPE, "addTemplatesFromMesh: triangles must hold 9 doubles per triangle");
+    std::vector<int32_t> ids(views.size(), -1);
+    check(lmx_bank_train_mesh(bank_, device_, triangles.data(), (int32_t)(triangles.size() / 9), &camera, views.data(), (int32_t)views.size(),
+                              class_id.c_str(), ids.data(), side_car));
+    return std::vector<int>(ids.begin(), ids.end());
+  }
+
   // Device placement (no upstream analogue).  Called lazily by match() with the frame size of the first call.
   void setDevice(int device, int max_batch = 1, int max_candidates = 0, void* stream = nullptr) {
     device_ = device; max_batch_ = max_batch; max_candidates_ = max_candidates; stream_ = stream;

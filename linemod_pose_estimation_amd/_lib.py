@@ -14,7 +14,7 @@ SYMBOLS = [
     "lmx_yaml_open", "lmx_yaml_close", "lmx_yaml_root", "lmx_yaml_kind", "lmx_yaml_scalar", "lmx_yaml_size", "lmx_yaml_item", "lmx_yaml_key", "lmx_yaml_get",
     "lmx_group_unique_id", "lmx_group_create", "lmx_group_destroy", "lmx_group_size", "lmx_group_frame_groups", "lmx_merge_gathered_groups", "lmx_group_gather_capacity", "lmx_group_match_batch",
     "lmx_group_upload", "lmx_group_submit", "lmx_group_finish", "lmx_group_depth", "lmx_group_collective_name", "lmx_ctx_export_oldest_on",
-    "lmx_bank_create", "lmx_bank_add_class", "lmx_bank_add_template", "lmx_bank_load_yaml", "lmx_bank_save_yaml", "lmx_bank_destroy",
+    "lmx_bank_create", "lmx_bank_add_class", "lmx_bank_add_template", "lmx_mesh_render", "lmx_bank_train_mesh", "lmx_bank_load_yaml", "lmx_bank_save_yaml", "lmx_bank_destroy",
     "lmx_bank_pyramid_levels", "lmx_bank_T", "lmx_bank_num_modalities", "lmx_bank_modality", "lmx_bank_num_classes",
     "lmx_bank_class_id", "lmx_bank_num_templates", "lmx_bank_get_template",
     "lmx_ctx_create", "lmx_ctx_destroy", "lmx_match", "lmx_match_batch", "lmx_ctx_upload", "lmx_ctx_upload_masks", "lmx_match_masked", "lmx_ctx_upload_wait", "lmx_host_alloc", "lmx_host_free", "lmx_ctx_upload_raw", "lmx_ctx_enqueue",
@@ -64,6 +64,15 @@ class RendererParams(C.Structure):
                 ("renderer_n_points", C.c_int32), ("renderer_angle_step", C.c_int32), ("renderer_width", C.c_int32), ("renderer_height", C.c_int32),
                 ("renderer_radius_min", C.c_double), ("renderer_radius_max", C.c_double), ("renderer_radius_step", C.c_double),
                 ("renderer_focal_length_x", C.c_double), ("renderer_focal_length_y", C.c_double), ("renderer_near", C.c_double), ("renderer_far", C.c_double)]
+
+
+class MeshCamera(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("light", C.c_double * 3)]
+
+
+class MeshView(C.Structure):
+    _fields_ = [("R", C.c_double * 9), ("distance", C.c_double)]
 
 
 class GroupDesc(C.Structure):
@@ -118,6 +127,9 @@ def lib():
     L.lmx_bank_create.argtypes = [C.POINTER(BankDesc), C.POINTER(vp)]
     L.lmx_bank_add_class.argtypes = [vp, C.c_char_p, C.c_int32, i32p, i32p, C.c_int64]
     L.lmx_bank_add_template.argtypes = [vp, C.c_int32, C.POINTER(Image), C.c_int32, C.c_char_p, C.POINTER(Image), i32p, i32p]
+    L.lmx_mesh_render.argtypes = [C.c_int32, vp, C.c_int32, C.POINTER(MeshCamera), C.POINTER(MeshView), C.c_int32, vp, vp, vp, vp]
+    L.lmx_bank_train_mesh.argtypes = [vp, C.c_int32, vp, C.c_int32, C.POINTER(MeshCamera), C.POINTER(MeshView), C.c_int32, C.c_char_p, vp,
+                                      C.POINTER(C.POINTER(RendererParams))]
     L.lmx_default_normal_lut.argtypes = [vp]
     L.lmx_bank_set_normal_lut.argtypes = [vp, vp]
     L.lmx_bank_get_normal_lut.argtypes = [vp, vp]

@@ -464,4 +464,44 @@ bool launch_small_depth_color(hipStream_t s, const uint16_t* depth, uint8_t* dq,
                               int n_ch = 3 /* colour planes of col1 / pyr2 (1: gray context) */);
 bool launch_small_spread(hipStream_t s, const SpreadBatch& b0, const LevelGeom& g0, const SpreadBatch& b1, const LevelGeom& g1, int n_mod, int n_frames);
 
+// ---- mesh rasteriser + batched trainer (lmx_mesh.hip, lmx_train.cpp) -----------------------------------------------
+namespace mr { struct Camera; struct Tri; }
+// Per-view state words the rasteriser kernels keep (int32, one 128-byte line per view)
+constexpr int kMeshStateWords = 32;
+constexpr int MS_INVALID = 0;        // a vertex at Z <= 0.01: the view is invalid
+constexpr int MS_UNION = 1;          // union of the triangles' clamped boxes {x0, y0, x1, y1}: tiles outside it only write zeros
+constexpr int MS_LEVEL = 5;          // [kMaxLevels] silhouette boxes {xmin, ymin, xmax, ymax} of the mask at pyramid level l (xmax = -1: empty)
+constexpr int MS_CENTRE_DEPTH = 21;  // depth_mm[H / 2][W / 2] (the side-car's D)
+// The window of a level the trainer's host half looks at: the silhouette box grown by 2, clamped (train_add_template derives the same on
+// the host); an empty mask gives a 4x4 corner, which shows "no candidates" like any other window.
+__host__ __device__ inline void mesh_window(const int32_t* box, int w, int h, int* x0, int* y0, int* ww, int* wh) {
+  if (box[2] >= 0) {
+    *x0 = box[0] - 2 > 0 ? box[0] - 2 : 0; *y0 = box[1] - 2 > 0 ? box[1] - 2 : 0;
+    *ww = (box[2] + 3 < w ? box[2] + 3 : w) - *x0; *wh = (box[3] + 3 < h ? box[3] + 3 : h) - *y0;
+  } else {
+    *x0 = 0; *y0 = 0; *ww = w < 4 ? w : 4; *wh = h < 4 ? h : 4;
+  }
+}
+// One level of a view's slot in the packed read-back: float magnitudes of the ColorGradient modalities, one label plane per modality, the
+// level's mask; rounded up to 4 bytes
+__host__ __device__ inline size_t mesh_pack_level_bytes(int ww, int wh, int n_mod, int n_cg) {
+  return (((size_t)ww * wh * (size_t)(4 * n_cg + n_mod + 1)) + 3) & ~(size_t)3;
+}
+struct MeshPackArgs {
+  const uint8_t* quant[kMaxLevels][kMaxModalities];   // label images, [n_views] frames each (DepthNormal: level 0 only)
+  const float* mag[kMaxLevels][kMaxModalities];       // squared magnitudes (ColorGradient) or null (DepthNormal)
+  const uint8_t* mask0;
+  const int32_t* state;
+  uint8_t* out;          // device-visible pinned host memory, slot_bytes per view
+  size_t slot_bytes;
+  int32_t n_levels, n_mod, n_cg, W, H;
+};
+void launch_mesh_raster(hipStream_t s, const double* d_tri, int n_tri, const mr::Camera& cam, const double* d_views /* [n_views][10] */, int n_views,
+                        int n_levels, mr::Tri* d_work /* [n_views][n_tri] */, int32_t* d_state /* [n_views][kMeshStateWords] */,
+                        uint8_t* gray, uint16_t* depth, uint8_t* mask /* [n_views][H][W] each, any may be null */);
+void launch_mesh_pack(hipStream_t s, const MeshPackArgs& a, int n_views);
+lmx_status mesh_check_args(const char* what, const double* triangles, int32_t n_triangles, const lmx_mesh_camera* cam, const lmx_mesh_view* views,
+                           int32_t n_views, mr::Camera* out);
+int mesh_first_invalid_view(const double* triangles, int32_t n_triangles, const lmx_mesh_view* views, int32_t n_views);
+
 }  // namespace lmx

@@ -8,11 +8,15 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "lmx_internal.hpp"
+#include "lmx_mesh_raster.hpp"
 
 namespace lmx {
 namespace {
@@ -351,6 +355,315 @@ lmx_status train_add_template(lmx_bank* bank, int device, const lmx_image* sourc
   return LMX_OK;
 }
 
+
+// ---- batched trainer over rendered views (lmx_bank_train_mesh) -------------------------------------------------------------------------
+// The trainer loop of the reference (src/renderer.cpp:262-329) with the renderer and the per-pixel half of addTemplate on the device, B views
+// per pass: k_mesh_* render gray / depth / mask into device memory, the quantisers run with n_frames = B (the gray render through the
+// one-plane colour quantiser), k_mesh_pack writes each view's windows (silhouette box grown by 2, per level: the same window
+// train_add_template derives on the host) of magnitudes, labels and mask into a pinned host buffer.  One stream, one synchronisation per
+// batch; the host half (extract_color / extract_depth / select_scattered / crop: the functions above, unchanged) runs on a few threads,
+// one view each, while the device works on the next batch.  Templates are appended to the bank in view order when every batch is done.
+namespace {
+
+constexpr int kMeshTrainBatch = 32;   // views per pass: 32 x ~100 covered tiles fill the 256 CUs; two pinned read-back buffers of 32 worst-case slots
+constexpr int kMeshTrainThreads = 8;  // host selection threads: a fixed small pool, never sized by the machine (LMX_TRAIN_THREADS = 1 .. 16 overrides)
+
+struct ViewResult {
+  bool accepted = false;
+  lmx_status status = LMX_OK;
+  std::string error;
+  std::vector<int32_t> templates, features;   // [L*M][5] with feat_begin relative to this view, [n][3]
+};
+
+// extractTemplate per (modality, level) on one view's packed windows, then cropTemplates: the host half of train_add_template
+void select_view(const lmx_bank* bank, const uint8_t* slot, const int32_t* state, int W0, int H0, ViewResult& out) {
+  const int L = (int)bank->T.size(), M = (int)bank->mods.size();
+  int n_cg = 0;
+  for (int m = 0; m < M; ++m) n_cg += bank->mods[m].type == LMX_MOD_COLOR_GRADIENT;
+  struct Win { int x0, y0, w, h; size_t off; };
+  std::vector<Win> wins(L);
+  size_t off = 0;
+  for (int l = 0; l < L; ++l) {
+    Win& w = wins[l];
+    mesh_window(state + MS_LEVEL + 4 * l, W0 >> l, H0 >> l, &w.x0, &w.y0, &w.w, &w.h);
+    w.off = off;
+    off += mesh_pack_level_bytes(w.w, w.h, M, n_cg);
+  }
+  std::vector<std::vector<Feat>> tp((size_t)L * M);
+  for (int m = 0, cg_index = 0; m < M; ++m) {
+    const lmx_modality_desc& md = bank->mods[m];
+    const bool cg = md.type == LMX_MOD_COLOR_GRADIENT;
+    size_t num_features = (size_t)md.num_features;
+    int extract_threshold = md.extract_threshold;
+    for (int l = 0; l < L; ++l) {
+      if (l > 0) { num_features /= 2; extract_threshold /= 2; }
+      if (num_features > 63) { out.status = LMX_ERR_SHAPE; out.error = "num_features " + std::to_string(num_features) + " > 63"; return; }
+      const Win& w = wins[l];
+      const size_t n = (size_t)w.w * w.h;
+      const uint8_t* base = slot + w.off;
+      const uint8_t* labp = base + n * 4 * n_cg + n * m;
+      const uint8_t* mskp = base + n * 4 * n_cg + n * M;
+      const std::vector<uint8_t> lab(labp, labp + n), msk(mskp, mskp + n);
+      std::vector<Feat>& f = tp[(size_t)l * M + m];
+      bool ok;
+      if (cg) {
+        const float* mgp = reinterpret_cast<const float*>(base + n * 4 * cg_index);
+        const std::vector<float> mg(mgp, mgp + n);
+        ok = extract_color(lab, mg, msk, w.h, w.w, num_features, md.strong_threshold, f);
+      } else {
+        ok = extract_depth(lab, msk, w.h, w.w, num_features, extract_threshold, f);
+      }
+      for (Feat& ft : f) { ft.x += w.x0; ft.y += w.y0; }
+      if (!ok) return;   // upstream: addTemplate returns -1, nothing is added
+    }
+    cg_index += cg;
+  }
+  int min_x = INT32_MAX, min_y = INT32_MAX, max_x = INT32_MIN, max_y = INT32_MIN;
+  for (int k = 0; k < L * M; ++k) {
+    const int level = k / M;
+    for (const Feat& f : tp[k]) {
+      const int x = f.x << level, y = f.y << level;
+      min_x = std::min(min_x, x); min_y = std::min(min_y, y); max_x = std::max(max_x, x); max_y = std::max(max_y, y);
+    }
+  }
+  if (min_x % 2 == 1) --min_x;
+  if (min_y % 2 == 1) --min_y;
+  int32_t fb = 0;
+  for (int k = 0; k < L * M; ++k) {
+    const int level = k / M;
+    const int ox = min_x >> level, oy = min_y >> level;
+    out.templates.insert(out.templates.end(), {(max_x - min_x) >> level, (max_y - min_y) >> level, level, fb, (int32_t)tp[k].size()});
+    for (const Feat& f : tp[k]) out.features.insert(out.features.end(), {f.x - ox, f.y - oy, f.label});
+    fb += (int32_t)tp[k].size();
+  }
+  out.accepted = true;
+}
+
+struct MeshTrainBuffers {   // everything a call allocates: freed in one place
+  std::vector<void*> dev, pinned;
+  hipStream_t stream = nullptr;
+  ~MeshTrainBuffers() {
+    if (stream) { (void)hipStreamSynchronize(stream); }
+    for (void* p : dev) (void)hipFree(p);
+    for (void* p : pinned) (void)hipHostFree(p);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+};
+
+}  // namespace
+
+lmx_status train_mesh(lmx_bank* bank, int device, const double* triangles, int n_tri, const lmx_mesh_camera* cam, const mr::Camera& dc,
+                      const lmx_mesh_view* views, int n_views, const char* class_id, int32_t* template_ids, lmx_renderer_params** side_car) {
+  const int L = (int)bank->T.size(), M = (int)bank->mods.size();
+  const int W0 = dc.W, H0 = dc.H;
+  if (H0 < 16 || W0 < 16) { set_error("source image too small"); return LMX_ERR_SHAPE; }
+  if (L < 1 || L > kMaxLevels || M < 1 || M > kMaxModalities) { set_error("lmx_bank_train_mesh: %d pyramid levels x %d modalities are not supported", L, M); return LMX_ERR_SHAPE; }
+  if ((H0 >> (L - 1)) < 1 || (W0 >> (L - 1)) < 1) { set_error("image too small for %d pyramid levels", L); return LMX_ERR_SHAPE; }
+  int n_cg = 0;
+  bool any_dn = false;
+  for (int m = 0; m < M; ++m) {
+    if (bank->mods[m].type == LMX_MOD_COLOR_GRADIENT) ++n_cg;
+    else if (bank->mods[m].type == LMX_MOD_DEPTH_NORMAL) any_dn = true;
+    else { set_error("lmx_bank_train_mesh: unknown modality type %d", bank->mods[m].type); return LMX_ERR_INVALID_ARG; }
+  }
+  // side-car of the accepted views, filled as we go and handed over at the end
+  std::unique_ptr<lmx_renderer_params, void (*)(lmx_renderer_params*)> side(nullptr, lmx_renderer_params_free);
+  if (side_car) {
+    *side_car = nullptr;
+    side.reset(new lmx_renderer_params());
+    std::memset(side.get(), 0, sizeof(lmx_renderer_params));
+    side->renderer_width = W0; side->renderer_height = H0;
+    side->renderer_focal_length_x = cam->fx; side->renderer_focal_length_y = cam->fy;
+  }
+  if (n_views == 0) { if (side_car) *side_car = side.release(); return LMX_OK; }
+  const int bad = mesh_first_invalid_view(triangles, n_tri, views, n_views);
+  if (bad >= 0) { set_error("lmx_bank_train_mesh: view %d puts a vertex at or behind the camera (Z <= 0.01); nothing was added", bad); return LMX_ERR_INVALID_ARG; }
+
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available; this library has no CPU path"); return LMX_ERR_NO_DEVICE; }
+  TR_HIP(hipSetDevice(device));
+  MeshTrainBuffers buf;
+  TR_HIP(hipStreamCreateWithFlags(&buf.stream, hipStreamNonBlocking));
+  hipStream_t s = buf.stream;
+  // a view's slot in the packed read-back must hold whole levels (worst case); large frames take fewer views per pass so that the two
+  // pinned buffers stay below ~2 x 192 MB (640x480 RGB-D: 2.7 MB per slot, the full batch)
+  size_t slot_bytes = 0;
+  for (int l = 0; l < L; ++l) slot_bytes += mesh_pack_level_bytes(W0 >> l, H0 >> l, M, n_cg);
+  slot_bytes = (slot_bytes + 255) & ~(size_t)255;
+  const int fit = (int)std::max<size_t>(4, ((size_t)192 << 20) / slot_bytes);
+  const int B = std::min(n_views, std::min(kMeshTrainBatch, fit));
+  const size_t px0 = (size_t)W0 * H0;
+  size_t device_bytes = 0;
+  auto dmalloc = [&](size_t bytes) -> void* {
+    void* p = nullptr;
+    if (hipMalloc(&p, std::max<size_t>(bytes, 256) + 64) != hipSuccess) return nullptr;
+    buf.dev.push_back(p); device_bytes += std::max<size_t>(bytes, 256) + 64;
+    return p;
+  };
+#define TM_ALLOC(var, type, bytes) type var = (type)dmalloc(bytes); if (!var) { set_error("hipMalloc of %zu bytes failed", (size_t)(bytes)); return LMX_ERR_HIP; }
+  TM_ALLOC(d_tri, double*, (size_t)n_tri * 9 * sizeof(double));
+  TM_ALLOC(d_views, double*, (size_t)B * 10 * sizeof(double));
+  TM_ALLOC(d_work, mr::Tri*, (size_t)B * n_tri * sizeof(mr::Tri));
+  TM_ALLOC(d_state, int32_t*, (size_t)B * kMeshStateWords * 4);
+  TM_ALLOC(d_mask, uint8_t*, px0 * B);
+  uint8_t* d_gray = nullptr;
+  uint16_t* d_depth = nullptr;
+  uint8_t* d_bins = nullptr;
+  if (n_cg) { d_gray = (uint8_t*)dmalloc(px0 * B); if (!d_gray) { set_error("hipMalloc failed"); return LMX_ERR_HIP; } }
+  if (any_dn) {
+    d_depth = (uint16_t*)dmalloc(px0 * B * 2);
+    d_bins = (uint8_t*)dmalloc(kNormalBinsDeviceBytes);
+    if (!d_depth || !d_bins) { set_error("hipMalloc failed"); return LMX_ERR_HIP; }
+    std::vector<uint8_t> bins(kNormalBinsDeviceBytes);   // zero-initialised: the trailing entry stays 0
+    if (!normal_lut_to_bins(bank->normal_lut.data(), bins.data())) { set_error("bank holds an invalid normal LUT"); return LMX_ERR_INVALID_ARG; }
+    TR_HIP(hipMemcpy(d_bins, bins.data(), bins.size(), hipMemcpyHostToDevice));
+  }
+  TR_HIP(hipMemcpy(d_tri, triangles, (size_t)n_tri * 9 * sizeof(double), hipMemcpyHostToDevice));
+  // label images (+ magnitudes, + the one-plane pyrDown chain) per modality and level; a DepthNormal modality keeps level 0 only (its
+  // coarser levels are level 0 sub-sampled, which k_mesh_pack reads directly)
+  MeshPackArgs pa;
+  std::memset(&pa, 0, sizeof(pa));
+  uint8_t* d_pyr[kMaxModalities][kMaxLevels] = {};
+  for (int l = 0; l < L; ++l) {
+    const size_t pxl = (size_t)(W0 >> l) * (H0 >> l);
+    for (int m = 0; m < M; ++m) {
+      const bool cg = bank->mods[m].type == LMX_MOD_COLOR_GRADIENT;
+      if (!cg && l > 0) continue;
+      void* q = dmalloc(pxl * B);
+      void* mg = cg ? dmalloc(pxl * B * 4) : nullptr;
+      void* py = (cg && l > 0) ? dmalloc(pxl * B) : nullptr;
+      if (!q || (cg && !mg) || (cg && l > 0 && !py)) { set_error("hipMalloc failed"); return LMX_ERR_HIP; }
+      pa.quant[l][m] = (const uint8_t*)q; pa.mag[l][m] = (const float*)mg; d_pyr[m][l] = (uint8_t*)py;
+    }
+  }
+  uint8_t* h_pack[2] = {nullptr, nullptr};
+  int32_t* h_state[2] = {nullptr, nullptr};
+  for (int k = 0; k < (n_views > B ? 2 : 1); ++k) {
+    void* p = nullptr;
+    TR_HIP(hipHostMalloc(&p, slot_bytes * B, hipHostMallocDefault));
+    buf.pinned.push_back(p); h_pack[k] = (uint8_t*)p;
+    TR_HIP(hipHostMalloc(&p, (size_t)B * kMeshStateWords * 4, hipHostMallocDefault));
+    buf.pinned.push_back(p); h_state[k] = (int32_t*)p;
+  }
+  pa.mask0 = d_mask; pa.state = d_state; pa.slot_bytes = slot_bytes; pa.n_levels = L; pa.n_mod = M; pa.n_cg = n_cg; pa.W = W0; pa.H = H0;
+
+  auto issue = [&](int first, int n, int k) -> lmx_status {
+    TR_HIP(hipMemcpyAsync(d_views, views + first, (size_t)n * 10 * sizeof(double), hipMemcpyHostToDevice, s));
+    launch_mesh_raster(s, d_tri, n_tri, dc, d_views, n, L, d_work, d_state, d_gray, d_depth, d_mask);
+    for (int m = 0; m < M; ++m) {
+      const lmx_modality_desc& md = bank->mods[m];
+      if (md.type == LMX_MOD_COLOR_GRADIENT) {
+        const uint8_t* src = d_gray;
+        for (int l = 0; l < L; ++l) {
+          uint8_t* next = l + 1 < L ? d_pyr[m][l + 1] : nullptr;
+          launch_color_quantize(s, src, (uint8_t*)pa.quant[l][m], next, H0 >> l, W0 >> l, n, md.weak_threshold, (float*)pa.mag[l][m], nullptr, nullptr, 1);
+          src = next;
+        }
+      } else {
+        launch_depth_quantize(s, d_depth, (uint8_t*)pa.quant[0][m], nullptr, H0, W0, n, md.distance_threshold, md.difference_threshold, d_bins);
+      }
+    }
+    MeshPackArgs a = pa;
+    void* dp = nullptr;
+    TR_HIP(hipHostGetDevicePointer(&dp, h_pack[k], 0));
+    a.out = (uint8_t*)dp;
+    launch_mesh_pack(s, a, n);
+    TR_HIP(hipGetLastError());
+    TR_HIP(hipMemcpyAsync(h_state[k], d_state, (size_t)n * kMeshStateWords * 4, hipMemcpyDeviceToHost, s));
+    return LMX_OK;
+  };
+
+  // LMX_MESH_TRAIN_TIMING=1: one line on stderr per call (scripts/mesh_train_bench.py reads it): where the call's wall time went
+  const bool timing = std::getenv("LMX_MESH_TRAIN_TIMING") != nullptr;
+  using clk = std::chrono::steady_clock;
+  auto ms_since = [](clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
+  const clk::time_point t_call = clk::now();
+  double wait_ms = 0.0, select_ms = 0.0;
+  int n_batches = 0;
+  int n_threads = kMeshTrainThreads;
+  if (const char* e = std::getenv("LMX_TRAIN_THREADS")) n_threads = std::min(16, std::max(1, std::atoi(e)));
+  CopyPool pool(n_threads - 1);
+  std::vector<int32_t> templates, features, ids;
+  ids.assign((size_t)n_views, -1);
+  std::vector<int> accepted_views;
+  std::vector<int32_t> acc_rect;
+  std::vector<uint16_t> acc_centre;
+  const int32_t existing = lmx_bank_num_templates(bank, class_id);
+  int32_t next_id = existing, fb = 0;
+  lmx_status st = issue(0, std::min(B, n_views), 0);
+  if (st != LMX_OK) return st;
+  for (int first = 0, k = 0; first < n_views; first += B, k ^= 1) {
+    const int n = std::min(B, n_views - first);
+    const clk::time_point t_wait = clk::now();
+    TR_HIP(hipStreamSynchronize(s));   // batch `first` is in h_pack[k] / h_state[k]; the device buffers are free again
+    wait_ms += ms_since(t_wait); ++n_batches;
+    if (first + B < n_views) {
+      st = issue(first + B, std::min(B, n_views - first - B), k ^ 1);
+      if (st != LMX_OK) return st;
+    }
+    std::vector<ViewResult> res((size_t)n);
+    const int32_t* stw = h_state[k];
+    for (int i = 0; i < n; ++i)
+      if (stw[(size_t)i * kMeshStateWords + MS_INVALID]) {
+        set_error("lmx_bank_train_mesh: view %d puts a vertex at or behind the camera (Z <= 0.01); nothing was added", first + i);
+        return LMX_ERR_INVALID_ARG;
+      }
+    const uint8_t* pack = h_pack[k];
+    const clk::time_point t_sel = clk::now();
+    pool.parallel_for(n, [&](int i) {
+      try {
+        select_view(bank, pack + (size_t)i * slot_bytes, stw + (size_t)i * kMeshStateWords, W0, H0, res[(size_t)i]);
+      } catch (const std::exception& e) {
+        res[(size_t)i].status = LMX_ERR_INVALID_ARG; res[(size_t)i].error = e.what();
+      }
+    });
+    select_ms += ms_since(t_sel);
+    for (int i = 0; i < n; ++i) {
+      ViewResult& r = res[(size_t)i];
+      if (r.status != LMX_OK) { set_error("lmx_bank_train_mesh: view %d: %s", first + i, r.error.c_str()); return r.status; }
+      if (!r.accepted) continue;
+      for (size_t t = 0; t < r.templates.size(); t += 5) r.templates[t + 3] += fb;
+      templates.insert(templates.end(), r.templates.begin(), r.templates.end());
+      features.insert(features.end(), r.features.begin(), r.features.end());
+      fb += (int32_t)(r.features.size() / 3);
+      ids[(size_t)(first + i)] = next_id++;
+      accepted_views.push_back(first + i);
+      const int32_t* b = stw + (size_t)i * kMeshStateWords + MS_LEVEL;
+      acc_rect.insert(acc_rect.end(), {b[0], b[1], b[2] - b[0] + 1, b[3] - b[1] + 1});   // an accepted view has covered pixels
+      acc_centre.push_back((uint16_t)stw[(size_t)i * kMeshStateWords + MS_CENTRE_DEPTH]);
+    }
+  }
+  const size_t n_acc = accepted_views.size();
+  if (side_car) {
+    lmx_renderer_params* p = side.get();
+    p->n_templates = n_acc;
+    p->obj_origin_dists = new double[n_acc](); p->rects = new int32_t[n_acc * 4](); p->distances = new double[n_acc]();
+    p->R = new double[n_acc * 9](); p->T = new double[n_acc * 3](); p->K = new double[n_acc * 9]();
+    for (size_t i = 0; i < n_acc; ++i) {
+      const lmx_mesh_view& v = views[accepted_views[i]];
+      p->obj_origin_dists[i] = v.distance;
+      std::memcpy(p->rects + i * 4, &acc_rect[i * 4], 16);
+      p->distances[i] = v.distance - double((float)acc_centre[i] / 1000.0f);   // src/renderer.cpp:284
+      std::memcpy(p->R + i * 9, v.R, sizeof(v.R));
+      p->T[i * 3 + 0] = 0.0; p->T[i * 3 + 1] = 0.0; p->T[i * 3 + 2] = v.distance;
+      const double K[9] = {(double)(float)cam->fx, 0.0, (double)((float)W0 / 2.0f), 0.0, (double)(float)cam->fy, (double)((float)H0 / 2.0f), 0.0, 0.0, 1.0};
+      std::memcpy(p->K + i * 9, K, sizeof(K));
+    }
+  }
+  if (n_acc) {
+    st = lmx_bank_add_class(bank, class_id, (int32_t)n_acc, templates.data(), features.data(), fb);
+    if (st != LMX_OK) return st;
+  }
+  if (template_ids) std::memcpy(template_ids, ids.data(), ids.size() * sizeof(int32_t));
+  if (side_car) *side_car = side.release();
+  if (timing)
+    std::fprintf(stderr, "lmx_bank_train_mesh timing: views %d accepted %zu batches %d of %d total_ms %.3f device_wait_ms %.3f host_select_ms %.3f (%d threads) "
+                 "device_bytes %zu pinned_bytes %zu\n", n_views, n_acc, n_batches, B, ms_since(t_call), wait_ms, select_ms, pool.threads(), device_bytes,
+                 (slot_bytes * B + (size_t)B * kMeshStateWords * 4) * (n_views > B ? 2 : 1));
+  return LMX_OK;
+}
+#undef TM_ALLOC
+
 }  // namespace lmx
 
 extern "C" lmx_status lmx_bank_add_template(lmx_bank* bank, int32_t device, const lmx_image* sources, int32_t n_sources, const char* class_id,
@@ -358,5 +671,17 @@ extern "C" lmx_status lmx_bank_add_template(lmx_bank* bank, int32_t device, cons
   return lmx::guarded("lmx_bank_add_template", [&]() -> lmx_status {
   if (!bank || !sources || !class_id || !template_id) { lmx::set_error("lmx_bank_add_template: null argument"); return LMX_ERR_INVALID_ARG; }
   return lmx::train_add_template(bank, device, sources, n_sources, class_id, object_mask, template_id, bounding_box);
+  });
+}
+
+extern "C" lmx_status lmx_bank_train_mesh(lmx_bank* bank, int32_t device, const double* triangles, int32_t n_triangles, const lmx_mesh_camera* cam,
+                                          const lmx_mesh_view* views, int32_t n_views, const char* class_id, int32_t* template_ids,
+                                          lmx_renderer_params** side_car) {
+  return lmx::guarded("lmx_bank_train_mesh", [&]() -> lmx_status {
+  if (!bank || !class_id) { lmx::set_error("lmx_bank_train_mesh: null argument"); return LMX_ERR_INVALID_ARG; }
+  lmx::mr::Camera dc;
+  const lmx_status st = lmx::mesh_check_args("lmx_bank_train_mesh", triangles, n_triangles, cam, views, n_views, &dc);
+  if (st != LMX_OK) return st;
+  return lmx::train_mesh(bank, device, triangles, n_triangles, cam, dc, views, n_views, class_id, template_ids, side_car);
   });
 }

@@ -59,6 +59,48 @@ class PreparedBatch:
         return out
 
 
+MESH_LIGHT = (0.35, -0.45, -0.82)   # the light direction of the mesh renderer's default camera
+
+
+def _mesh_args(triangles, views, width, height, fx, fy, cx, cy, light):
+    """-> (triangles float64 [n,3,3], lmx_mesh_camera, lmx_mesh_view array) for lmx_mesh_render / lmx_bank_train_mesh."""
+    tri = np.ascontiguousarray(triangles, np.float64)
+    if tri.ndim != 3 or tri.shape[1:] != (3, 3):
+        raise TypeError("triangles must be [n, 3, 3] (metres, object frame)")
+    cam = _lib.MeshCamera(int(width), int(height), float(fx), float(fy), width / 2.0 if cx is None else float(cx), height / 2.0 if cy is None else float(cy),
+                          (C.c_double * 3)(*[float(v) for v in light]))
+    packed = np.empty((len(views), 10), np.float64)
+    for i, (R, dist) in enumerate(views):
+        packed[i, :9] = np.asarray(R, np.float64).reshape(9)
+        packed[i, 9] = dist
+    return tri, cam, packed
+
+
+def render_views(triangles, views, width=640, height=480, fx=826.119324, fy=826.119324, cx=None, cy=None, light=MESH_LIGHT, device=0):
+    """lmx_mesh_render: the mesh (`triangles` [n,3,3], metres) seen from every (R [3,3], distance) of `views` with X_cam = R X_obj +
+    (0, 0, distance) -> (gray u8 [n,H,W], depth u16 mm [n,H,W], mask u8 [n,H,W], rects int32 [n,4] (x, y, w, h))."""
+    tri, cam, packed = _mesh_args(triangles, views, width, height, fx, fy, cx, cy, light)
+    n = len(views)
+    gray = np.empty((n, height, width), np.uint8)
+    depth = np.empty((n, height, width), np.uint16)
+    mask = np.empty((n, height, width), np.uint8)
+    rects = np.zeros((n, 4), np.int32)
+    _lib.check(_lib.lib().lmx_mesh_render(device, tri.ctypes.data, tri.shape[0], C.byref(cam), packed.ctypes.data_as(C.POINTER(_lib.MeshView)), n,
+                                          gray.ctypes.data, depth.ctypes.data, mask.ctypes.data, rects.ctypes.data))
+    return gray, depth, mask, rects
+
+
+def _side_car_dict(p):
+    """lmx_renderer_params -> dict of numpy arrays (copies) and the renderer_* scalars."""
+    n = int(p.n_templates)
+    arr = lambda ptr, shape, dt: (np.ctypeslib.as_array(ptr, shape=shape).astype(dt) if n else np.zeros(shape, dt))  # noqa: E731
+    out = {"obj_origin_dists": arr(p.obj_origin_dists, (n,), np.float64), "rects": arr(p.rects, (n, 4), np.int32), "distances": arr(p.distances, (n,), np.float64),
+           "R": arr(p.R, (n, 3, 3), np.float64), "T": arr(p.T, (n, 3), np.float64), "K": arr(p.K, (n, 3, 3), np.float64)}
+    for k, _ in _lib.RendererParams._fields_[7:]:
+        out[k] = getattr(p, k)
+    return out
+
+
 class NativeBank:
     """Owns an lmx_bank handle (host template state of cv::linemod::Detector)."""
 
@@ -134,6 +176,32 @@ class NativeBank:
                                                     C.byref(mask_img) if mask_img is not None else None, C.byref(tid), bb))
         del keep
         return tid.value, tuple(bb)
+
+    def train_mesh(self, triangles, views, width=640, height=480, fx=826.119324, fy=826.119324, cx=None, cy=None, class_id="obj", light=MESH_LIGHT,
+                   device=0, save_side_car=None, side_car_scalars=None):
+        """lmx_bank_train_mesh, the reference's trainer loop (src/renderer.cpp:262-329): renders every (R, distance) of `views` on the
+        device and adds a template per view addTemplate accepts, in view order.  -> list of dicts per ACCEPTED view {view, rect, distance}
+        (what meshsynth.train_bank returns); `.last_template_ids` = int32 [n_views] (-1: rejected), `.last_side_car` = the renderer-params
+        side-car of the accepted views as a dict (obj_origin_dists, rects, distances, R, T, K, renderer_*).  save_side_car: also write it
+        as a *_renderer_params.yml, with `side_car_scalars` (renderer_n_points, renderer_radius_min, ...) set first."""
+        tri, cam, packed = _mesh_args(triangles, views, width, height, fx, fy, cx, cy, light)
+        ids = np.full(len(views), -1, np.int32)
+        side = C.POINTER(_lib.RendererParams)()
+        L = _lib.lib()
+        _lib.check(L.lmx_bank_train_mesh(self.h, device, tri.ctypes.data, tri.shape[0], C.byref(cam), packed.ctypes.data_as(C.POINTER(_lib.MeshView)),
+                                         len(views), class_id.encode(), ids.ctypes.data, C.byref(side)))
+        try:
+            for k, v in (side_car_scalars or {}).items():
+                setattr(side.contents, k, v)
+            self.last_side_car = _side_car_dict(side.contents)
+            if save_side_car is not None:
+                _lib.check(L.lmx_renderer_params_save(side, str(save_side_car).encode()))
+        finally:
+            L.lmx_renderer_params_free(side)
+        self.last_template_ids = ids
+        sc = self.last_side_car
+        acc = np.nonzero(ids >= 0)[0]
+        return [{"view": int(v), "rect": tuple(int(x) for x in sc["rects"][k]), "distance": float(sc["obj_origin_dists"][k])} for k, v in enumerate(acc)]
 
     @classmethod
     def load_yaml(cls, path):

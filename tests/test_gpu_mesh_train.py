@@ -1,0 +1,307 @@
+"""Training a bank from a mesh on the device: lmx_mesh_render (the rasteriser kernels, csrc/lmx_mesh.hip) against meshsynth.render_view, every
+byte; lmx_bank_train_mesh (batched renderer + trainer) against the committed banks over the whole 2652-view grid and against a loop of
+lmx_bank_add_template over host renders (rejections, order, modalities, levels, classes); the side-car; the command line; the C++ facade."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import golden_util as G
+import mesh_cases as mc
+from conftest import ROOT
+from linemod_pose_estimation_amd import Detector, NativeBank, _lib, meshsynth as ms, render_views
+
+pytestmark = pytest.mark.gpu
+
+F = ms.ENSENSO["fx"]
+
+
+def gpu_render(tri, cam, views):
+    return render_views(tri, views, cam["width"], cam["height"], cam["fx"], cam["fy"], cam["cx"], cam["cy"], mc.LIGHT)
+
+
+def assert_render_equal(got, exp, what):
+    for name, a, b in zip(("rects", "mask", "depth", "gray"), (got[3], got[2], got[1], got[0]), (exp[3], exp[2], exp[1], exp[0])):
+        assert np.array_equal(a, b), (what, name, np.argwhere(a != b)[:5])
+
+
+CASES = mc.cases()
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
+def test_render_views_equals_meshraster_c(case):
+    """1. one batched call and calls of 1 and 2 views per case."""
+    name, tri, cam, views = case
+    exp = mc.expected(tri, cam, views)
+    assert_render_equal(gpu_render(tri, cam, views), exp, name)
+    for n in (1, 2):
+        if n <= len(views):
+            assert_render_equal(gpu_render(tri, cam, views[-n:]), tuple(e[-n:] for e in exp), (name, n))
+    if name == "chip_ties_degenerates":
+        plain = gpu_render(ms.load_mesh("memoryChip2"), cam, views)
+        assert_render_equal(gpu_render(tri, cam, views), plain, name + " vs the plain mesh")
+
+
+def test_render_views_batch_edges():
+    """1. 65 views in one call (two full device batches and one view), a strided pick of the grid."""
+    cpu, views = ms.load_mesh("cpu_binary"), ms.view_grid()
+    cam = mc.camera(320, 240, F / 2)
+    vs = [views[i] for i in range(3, 2652, 41)][:65]
+    assert len(vs) == 65
+    assert_render_equal(gpu_render(cpu, cam, vs), mc.expected(cpu, cam, vs), "65 views")
+
+
+def same_bank(a, b):
+    assert a.T == b.T and [m["type"] for m in a.modalities] == [m["type"] for m in b.modalities]
+    ca, cb = sorted(a.classes, key=lambda c: c[0]), sorted(b.classes, key=lambda c: c[0])
+    assert [c[0] for c in ca] == [c[0] for c in cb]
+    for (cid, ta, fa), (_, tb, fb) in zip(ca, cb):
+        assert ta.shape == tb.shape and np.array_equal(ta, tb), (cid, ta.shape, tb.shape)
+        assert np.array_equal(fa, fb), cid
+
+
+@pytest.mark.parametrize("name", ["memoryChip2", "cpu_binary"])
+def test_full_grid_equals_the_committed_bank(name):
+    """2. all 2652 views: every template's width, height, level, feature list; rects, distances, accepted-view indices."""
+    bank, rects, dists, views_idx = ms.load_bank(name)
+    tri, views = ms.load_mesh(name), ms.view_grid()
+    nb = NativeBank.create(bank.T, bank.modalities)
+    meta = nb.train_mesh(tri, views)
+    assert [m["view"] for m in meta] == list(views_idx) and len(meta) == 2652
+    assert np.array_equal(np.asarray([m["rect"] for m in meta], np.int32), rects)
+    assert np.array_equal(np.asarray([m["distance"] for m in meta], np.float32), dists.astype(np.float32))
+    assert np.array_equal(nb.last_template_ids, np.arange(2652))
+    same_bank(nb.to_bank(), bank)
+
+
+def loop_reference(tri, views, width, height, f, modalities=("ColorGradient", "DepthNormal"), T=(5, 8), class_id="obj", nb=None):
+    """The parent path: a loop of NativeBank.add_template over meshsynth.training_view -> (bank, ids per view, meta)."""
+    if nb is None:
+        b = ms.empty_bank(modalities, T)
+        nb = NativeBank.create(b.T, b.modalities)
+    ids, meta = [], []
+    for i, (R, dist) in enumerate(views):
+        bgr, depth, mask, rect = ms.training_view(tri, R, dist, width, height, f, f)
+        tid, _ = nb.add_template([bgr if m == "ColorGradient" else depth for m in modalities], class_id, mask)
+        ids.append(tid)
+        if tid >= 0:
+            meta.append({"view": i, "rect": rect, "distance": dist})
+    return nb, np.asarray(ids, np.int32), meta
+
+
+@pytest.mark.parametrize("mesh,width,height,div,n_accepted", [("cpu_binary", 224, 160, 3, 56), ("memoryChip2", 160, 120, 4, 61), ("cpu_binary", 320, 240, 2, 201),
+                                                            ("cpu_binary", 160, 120, 4, 0)])
+def test_rejections_and_order_equal_the_per_view_loop(mesh, width, height, div, n_accepted):
+    """3. configurations in which the trainer rejects views (every 13th view of the grid, 204 views)."""
+    tri = ms.load_mesh(mesh)
+    views = ms.view_grid()[::13]
+    assert len(views) == 204
+    ref, ref_ids, ref_meta = loop_reference(tri, views, width, height, F / div)
+    b = ms.empty_bank()
+    nb = NativeBank.create(b.T, b.modalities)
+    meta = nb.train_mesh(tri, views, width, height, F / div, F / div)
+    print("accepted %d of %d" % (len(meta), len(views)))
+    assert np.array_equal(nb.last_template_ids, ref_ids)
+    assert meta == ref_meta
+    assert len(meta) == n_accepted                   # the oracle trainer's counts: both accepted and rejected views (resp. none)
+    if n_accepted:
+        assert 0 < len(meta) < len(views)
+    else:
+        assert nb.class_ids() == []                  # bank stays empty, the call succeeded
+    same_bank(nb.to_bank(), ref.to_bank())
+
+
+def test_modalities_levels_classes_and_appending_equal_the_per_view_loop():
+    """4. ColorGradient-only bank, a three-level bank, two classes by two calls, a second call appending to an existing class."""
+    chip, cpu = ms.load_mesh("memoryChip2"), ms.load_mesh("cpu_binary")
+    grid = ms.view_grid()
+    views = [grid[i] for i in range(11, 2652, 89)]
+    assert len(views) == 30
+    for mods, T in ((("ColorGradient",), (5, 8)), (("ColorGradient", "DepthNormal"), (5, 8, 10))):
+        ref, ref_ids, ref_meta = loop_reference(chip, views, 640, 480, F, mods, T)
+        b = ms.empty_bank(mods, T)
+        nb = NativeBank.create(b.T, b.modalities)
+        meta = nb.train_mesh(chip, views)
+        assert len(meta) == 30 and meta == ref_meta and np.array_equal(nb.last_template_ids, ref_ids)
+        same_bank(nb.to_bank(), ref.to_bank())
+    # two classes into one bank, then more views appended to the first class
+    ref, _, _ = loop_reference(chip, views[:12], 640, 480, F, class_id="chip")
+    loop_reference(cpu, views[:9], 640, 480, F, class_id="cpu", nb=ref)
+    _, ref_ids, _ = loop_reference(chip, views[12:20], 640, 480, F, class_id="chip", nb=ref)
+    b = ms.empty_bank()
+    nb = NativeBank.create(b.T, b.modalities)
+    nb.train_mesh(chip, views[:12], class_id="chip")
+    nb.train_mesh(cpu, views[:9], class_id="cpu")
+    nb.train_mesh(chip, views[12:20], class_id="chip")
+    assert np.array_equal(nb.last_template_ids, ref_ids) and list(ref_ids) == list(range(12, 20))
+    assert nb.class_ids() == ["chip", "cpu"]
+    same_bank(nb.to_bank(), ref.to_bank())
+
+
+def test_large_frames_take_smaller_batches_and_equal_the_per_view_loop():
+    """1280x960: the pinned read-back buffers cap the device batch below 32 views (17 here), so 40 views cross two batch edges."""
+    chip, grid = ms.load_mesh("memoryChip2"), ms.view_grid()
+    views = [grid[i] for i in range(5, 2652, 67)]
+    assert len(views) == 40
+    ref, ref_ids, ref_meta = loop_reference(chip, views, 1280, 960, 2 * F)
+    b = ms.empty_bank()
+    nb = NativeBank.create(b.T, b.modalities)
+    meta = nb.train_mesh(chip, views, 1280, 960, 2 * F, 2 * F)
+    assert len(meta) == 40 and meta == ref_meta and np.array_equal(nb.last_template_ids, ref_ids)
+    same_bank(nb.to_bank(), ref.to_bank())
+
+
+def test_side_car_fields_roundtrip_and_cluster_chain(tmp_path):
+    """5. the renderer-params side-car of a trained bank; save -> load; the cluster chain fed from it == fed from the fixture."""
+    import ctypes as C
+    bank, rects, dists, views_idx = ms.load_bank("memoryChip2")
+    chip, grid = ms.load_mesh("memoryChip2"), ms.view_grid()
+    n = 442
+    views = grid[:n]
+    b = ms.empty_bank()
+    nb = NativeBank.create(b.T, b.modalities)
+    yml = tmp_path / "chip_renderer_params.yml"
+    meta = nb.train_mesh(chip, views, save_side_car=yml, side_car_scalars={"renderer_radius_min": 0.4, "renderer_radius_max": 0.65, "renderer_radius_step": 0.05})
+    sc = nb.last_side_car
+    assert len(meta) == n and sc["rects"].shape == (n, 4)
+    assert np.array_equal(sc["rects"], rects[:n]) and np.array_equal(sc["obj_origin_dists"], np.asarray([v[1] for v in views]))
+    assert np.array_equal(sc["R"], np.stack([v[0] for v in views]))
+    assert np.array_equal(sc["T"], np.asarray([(0.0, 0.0, v[1]) for v in views]))
+    K = np.asarray([[np.float32(F), 0, np.float32(640) / np.float32(2)], [0, np.float32(F), np.float32(480) / np.float32(2)], [0, 0, 1]], np.float64)
+    assert np.array_equal(sc["K"], np.broadcast_to(K, (n, 3, 3)))
+    centre = np.asarray([ms.render_view(chip, R, d, F, F, 640, 480)[1][240, 320] for R, d in views[::17]])
+    assert centre.min() > 0       # the chip covers the image centre: D is a real distance
+    D = np.asarray([d - float(np.float32(c) / np.float32(1000.0)) for (R, d), c in zip(views[::17], centre)])
+    assert np.array_equal(sc["distances"][::17], D)
+    assert (sc["renderer_width"], sc["renderer_height"], sc["renderer_focal_length_x"], sc["renderer_focal_length_y"]) == (640, 480, F, F)
+    assert (sc["renderer_n_points"], sc["renderer_angle_step"], sc["renderer_near"], sc["renderer_far"]) == (0, 0, 0.0, 0.0)
+    # save -> load
+    L = _lib.lib()
+    p = C.POINTER(_lib.RendererParams)()
+    _lib.check(L.lmx_renderer_params_load(str(yml).encode(), C.byref(p)))
+    try:
+        q = p.contents
+        assert q.n_templates == n and q.renderer_width == 640 and q.renderer_radius_step == 0.05
+        assert np.array_equal(np.ctypeslib.as_array(q.rects, shape=(n, 4)), sc["rects"])
+        ld = np.ctypeslib.as_array(q.obj_origin_dists, shape=(n,)).copy()
+        assert np.array_equal(ld, sc["obj_origin_dists"].astype(np.float32).astype(np.float64))     # Ori_dist passes through a float
+        assert np.array_equal(np.ctypeslib.as_array(q.R, shape=(n, 9)), sc["R"].reshape(n, 9))
+    finally:
+        L.lmx_renderer_params_free(p)
+    # the cluster chain: side-car of the trained bank vs the committed fixture's rects / distances
+    trained = nb.to_bank()
+    sources, truth = ms.make_scene(chip, views, seed=40, n_instances=3)
+    outs = []
+    for bk, d_, r_ in ((trained, ld, sc["rects"]), (trained, dists[:n].astype(np.float64), rects[:n])):
+        det = Detector(bk, 640, 480, max_candidates=1 << 17)
+        det.set_cluster_sidecar(d_, r_, 10, 0.4, 0.05, 0)      # size threshold 0, as the carmine node passes
+        det.upload([sources])
+        det.enqueue(1, 80.0)
+        m, c, mem = det.collect_clusters(1, cap_total=1 << 16)[0]
+        outs.append((m, c, mem))
+        det.close()
+    assert len(outs[0][0]) > 5 and len(outs[0][1]) >= 1
+    for a, b_ in zip(outs[0], outs[1]):
+        assert np.array_equal(a, b_)
+
+
+def test_command_line_trains_the_golden_case(tmp_path):
+    """6. scripts/train_mesh.py -> the yml pair; readLinemod on it finds the committed case's matches."""
+    case = os.path.join(ROOT, "tests", "golden", "case_mesh_chip_320x240.npz")
+    z, bank, sources = G.load(case)
+    yml, params = tmp_path / "chip_templates.yml", tmp_path / "chip_renderer_params.yml"
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "train_mesh.py"), os.path.join(ms.MESH_DIR, "memoryChip2.npz"), str(yml), str(params),
+                          "--width", "320", "--height", "240", "--fx", repr(F / 2), "--max-views", "204"], capture_output=True, text=True, cwd=ROOT, timeout=600)
+    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-2000:]
+    assert "204 views, %d templates" % bank.num_templates() in res.stdout
+    same_bank(NativeBank.load_yaml(yml).to_bank(), bank)
+    det = Detector.readLinemod(str(yml), 320, 240)
+    G.same_matches(det.match(sources, float(z["threshold"])), z["matches"])
+    det.close()
+    assert "Template 0:" in params.read_text() and "renderer_radius_min" in params.read_text()
+
+
+def test_stl_reader_binary_and_ascii(tmp_path):
+    """The command line's STL reader: a binary and an ASCII file of the same triangles give the triangles back."""
+    sys.path.insert(0, os.path.join(ROOT, "scripts"))
+    import train_mesh as tm
+    tri = ms.load_mesh("memoryChip2")[:50].astype(np.float32)
+    rec = np.zeros(len(tri), np.dtype([("n", "<f4", 3), ("v", "<f4", (3, 3)), ("attr", "<u2")]))
+    rec["v"] = tri
+    (tmp_path / "b.stl").write_bytes(b"solid binary".ljust(80, b" ") + np.uint32(len(tri)).tobytes() + rec.tobytes())
+    txt = "solid a\n" + "".join("facet normal 0 0 0\n outer loop\n" + "".join("  vertex %r %r %r\n" % tuple(float(c) for c in v) for v in t) + " endloop\nendfacet\n" for t in tri) + "endsolid a\n"
+    (tmp_path / "a.stl").write_text(txt)
+    assert np.array_equal(tm.load_mesh(str(tmp_path / "b.stl")), tri.astype(np.float64))
+    assert np.array_equal(tm.load_mesh(str(tmp_path / "a.stl")), tri.astype(np.float64))
+
+
+def test_cpp_facade_trains_the_same_bank(tmp_path):
+    """7. tests/cpp/mesh_train_main.cpp (Detector::addTemplatesFromMesh) == Python: template count, first and last template."""
+    exe = str(tmp_path / "mesh_train_main")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "mesh_train_main.cpp"),
+                           "-o", exe, "-L", _lib.CSRC, "-llmx", "-Wl,-rpath," + _lib.CSRC, "-Wl,-rpath-link,/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib"])
+    cpu = ms.load_mesh("cpu_binary")
+    views = ms.view_grid()[::13][:60]
+    np.ascontiguousarray(cpu, np.float64).tofile(tmp_path / "tri.f64")
+    mc.pack_views(views).tofile(tmp_path / "views.f64")
+    res = subprocess.run([exe, str(tmp_path / "tri.f64"), str(tmp_path / "views.f64"), "224", "160", repr(F / 3), str(tmp_path / "out.yml")], capture_output=True, text=True, timeout=300)
+    assert res.returncode == 0, res.stderr
+    b = ms.empty_bank()
+    nb = NativeBank.create(b.T, b.modalities)
+    meta = nb.train_mesh(cpu, views, 224, 160, F / 3, F / 3)
+    assert 0 < len(meta) < len(views)
+    lines = res.stdout.strip().splitlines()
+    assert lines[0] == "views %d accepted %d templates %d side_car %d" % (len(views), len(meta), len(meta), len(meta))
+    got = nb.to_bank()
+
+    def fmt(tag, tid):
+        return ["%s %d %d %d %d" % (tag, w, h, lv, len(f)) + "".join(" %d,%d,%d" % tuple(x) for x in f) for w, h, lv, f in got.get_templates("obj", tid)]
+    assert lines[1:] == fmt("first", 0) + fmt("last", len(meta) - 1)
+    same_bank(NativeBank.load_yaml(tmp_path / "out.yml").to_bank(), got)
+
+
+def test_cv_facade_trains_the_same_bank(tmp_path):
+    """7b. the cv::linemod-shaped facade (tests/cpp/cv_mesh_train_main.cpp: Detector(modalities, T), addTemplatesFromMesh, writeLinemod)
+    writes the bank Python trains."""
+    exe = str(tmp_path / "cv_mesh_train_main")
+    subprocess.check_call(["g++", "-std=c++11", "-O1", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "tests", "cpp", "cv_standin"), "-I", os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "tests", "cpp", "cv_mesh_train_main.cpp"), "-o", exe, "-pthread", "-L", _lib.CSRC, "-llmx", "-Wl,-rpath," + _lib.CSRC,
+                           "-Wl,-rpath-link,/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib"])
+    cpu = ms.load_mesh("cpu_binary")
+    views = ms.view_grid()[::13][:60]
+    np.ascontiguousarray(cpu, np.float64).tofile(tmp_path / "tri.f64")
+    mc.pack_views(views).tofile(tmp_path / "views.f64")
+    res = subprocess.run([exe, str(tmp_path / "tri.f64"), str(tmp_path / "views.f64"), "224", "160", repr(F / 3), str(tmp_path / "out.yml")], capture_output=True, text=True, timeout=300)
+    assert res.returncode == 0, res.stderr
+    b = ms.empty_bank()
+    nb = NativeBank.create(b.T, b.modalities)
+    meta = nb.train_mesh(cpu, views, 224, 160, F / 3, F / 3)
+    assert 0 < len(meta) < len(views)
+    assert res.stdout.strip().splitlines()[0] == "views %d accepted %d templates %d" % (len(views), len(meta), len(meta))
+    same_bank(NativeBank.load_yaml(tmp_path / "out.yml").to_bank(), nb.to_bank())
+
+
+def test_invalid_view_in_a_batch_leaves_the_bank_unchanged():
+    """8. a view that puts a vertex behind the camera, in the middle of the second device batch."""
+    chip, grid = ms.load_mesh("memoryChip2"), ms.view_grid()
+    views = [grid[i] for i in range(0, 50)]
+    R_bad = mc.view_reaching_behind(chip, grid, 0.02)
+    b = ms.empty_bank()
+    nb = NativeBank.create(b.T, b.modalities)
+    nb.train_mesh(chip, views[:5])
+    before = nb.to_bank()
+    bad = views[:40] + [(R_bad, 0.02)] + views[40:]
+    with pytest.raises(_lib.LmxError) as e:
+        nb.train_mesh(chip, bad)
+    assert e.value.status == _lib.LMX_ERR_INVALID_ARG and "view 40 " in str(e.value)
+    same_bank(nb.to_bank(), before)
+    with pytest.raises(_lib.LmxError) as e:
+        render_views(chip, bad)
+    assert e.value.status == _lib.LMX_ERR_INVALID_ARG and "view 40 " in str(e.value)
+    # the next valid call works and gives what it gives on a fresh bank
+    nb.train_mesh(chip, views[5:50])
+    fresh = NativeBank.create(b.T, b.modalities)
+    fresh.train_mesh(chip, views)
+    same_bank(nb.to_bank(), fresh.to_bank())
