@@ -534,6 +534,15 @@ lmx_status lmx_ctx_debug_read(lmx_ctx* ctx, int32_t frame, int32_t what, int32_t
 /* Test hook for the float stage: the 16-bin orientation label (0..16, before upstream's '& 7') the device code assigns to
  * n gradients (dx[i], dy[i]) -- fastAtan2 in degrees, times 16/360, round half to even. */
 lmx_status lmx_debug_orientation_labels(int32_t device, const int16_t* dx, const int16_t* dy, size_t n, uint8_t* out);
+/* Test hook for the depth path's float stage: the median bin BEFORE the 5x5 median (0 = no label, k + 1 = label 1 << k) that the depth
+ * quantiser's device code gives n tap tuples.  taps: n x 9 values, the pixel's depth d and then its eight neighbours at distance 5 in the
+ * order (dy, dx) = (-5,-5) (-5,0) (-5,5) (0,-5) (0,5) (5,-5) (5,0) (5,5); any values, a tuple need not come from an image.  variant picks the
+ * code: the int32 form (what a context runs for difference_threshold <= 200), the 64-bit form (larger thresholds), or the int32 form's
+ * look-up as the pipelined loop of interior tiles does it.  The int32 variants refuse difference_threshold > 200 (LMX_ERR_INVALID_ARG).
+ * normal_lut: 8000 labels as lmx_bank_set_normal_lut takes them, or NULL for the default table. */
+enum { LMX_DBG_DEPTH_INT = 0, LMX_DBG_DEPTH_INT64 = 1, LMX_DBG_DEPTH_PIPELINED = 2 };
+lmx_status lmx_debug_depth_normal_bins(int32_t device, const uint16_t* taps, size_t n, int32_t distance_threshold, int32_t difference_threshold,
+                                       int32_t variant, const uint8_t* normal_lut, uint8_t* out_bins);
 /* Test hooks: the permutation produced by the library's restatement of libstdc++'s std::sort (csrc/lmx_sort_emul.hpp, the code the
  * device runs to reproduce upstream's order of ties) for Match::operator< and for the clusters' score-descending comparator. */
 lmx_status lmx_debug_introsort_perm(const float* similarity, const int32_t* template_id, int32_t n, int32_t* perm);

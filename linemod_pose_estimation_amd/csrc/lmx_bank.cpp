@@ -66,6 +66,11 @@ bool normal_lut_to_bins(const uint8_t* lut, uint8_t* bins) {
   return true;
 }
 
+bool normal_bins_device_image(const uint8_t* lut, std::vector<uint8_t>& out) {
+  out.assign(kNormalBinsDeviceBytes, 0);   // the trailing entry stays 0
+  return normal_lut_to_bins(lut, out.data());
+}
+
 // 8000 raw bytes, or text with 8000 integers separated by anything that is not a digit (C initialiser syntax of OpenCV's
 // normal_lut.i: braces, commas, comments are skipped)
 lmx_status normal_lut_from_file(const char* path, std::vector<uint8_t>& out) {

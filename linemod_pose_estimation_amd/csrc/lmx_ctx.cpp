@@ -447,8 +447,8 @@ static lmx_status ctx_create_impl(lmx_ctx* c) {
   }
   if ((st = build_device_bank(c)) != LMX_OK) return st;
   {
-    std::vector<uint8_t> bins(lmx::kNormalBinsDeviceBytes);   // zero-initialised: the trailing entry stays 0
-    if (!normal_lut_to_bins(c->bank->normal_lut.data(), bins.data())) { set_error("bank holds an invalid normal LUT"); return LMX_ERR_INVALID_ARG; }
+    std::vector<uint8_t> bins;
+    if (!normal_bins_device_image(c->bank->normal_lut.data(), bins)) { set_error("bank holds an invalid normal LUT"); return LMX_ERR_INVALID_ARG; }
     const uint8_t* d_bins = nullptr;
     if ((st = dev_upload(c, &d_bins, bins)) != LMX_OK) return st;
     c->d_normal_bins = const_cast<uint8_t*>(d_bins);

@@ -115,6 +115,55 @@ lmx_status lmx_debug_orientation_labels(int32_t device, const int16_t* dx, const
   return st;
 }
 
+lmx_status lmx_debug_depth_normal_bins(int32_t device, const uint16_t* taps, size_t n, int32_t distance_threshold, int32_t difference_threshold,
+                                       int32_t variant, const uint8_t* normal_lut, uint8_t* out_bins) {
+  if (n > 0 && (!taps || !out_bins)) { set_error("lmx_debug_depth_normal_bins: null argument"); return LMX_ERR_INVALID_ARG; }
+  if (variant != LMX_DBG_DEPTH_INT && variant != LMX_DBG_DEPTH_INT64 && variant != LMX_DBG_DEPTH_PIPELINED) {
+    set_error("lmx_debug_depth_normal_bins: unknown variant %d", variant);
+    return LMX_ERR_INVALID_ARG;
+  }
+  if (variant != LMX_DBG_DEPTH_INT64 && difference_threshold > 200) {
+    set_error("lmx_debug_depth_normal_bins: the int32 forms hold for difference_threshold <= 200 only (got %d)", difference_threshold);
+    return LMX_ERR_INVALID_ARG;
+  }
+  if (n > ((size_t)1 << 28)) { set_error("lmx_debug_depth_normal_bins: at most 2^28 tuples per call"); return LMX_ERR_INVALID_ARG; }
+  std::vector<uint8_t> lut(LMX_NORMAL_LUT_SIZE), bins;
+  if (normal_lut) std::memcpy(lut.data(), normal_lut, LMX_NORMAL_LUT_SIZE);
+  else default_normal_lut(lut.data());
+  if (!normal_bins_device_image(lut.data(), bins)) { set_error("lmx_debug_depth_normal_bins: a table entry is neither 0 nor one bit"); return LMX_ERR_INVALID_ARG; }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available; this library has no CPU path"); return LMX_ERR_NO_DEVICE; }
+  if (n == 0) return LMX_OK;
+  LMX_HIP(hipSetDevice(device));
+  // tuple c's nine values go to elements 45 (c / 5) + c % 5 + 5 k, k = 0..8 (launch_debug_depth_normal_bins)
+  const size_t groups = (n + kDebugDepthPatchGroup - 1) / kDebugDepthPatchGroup;
+  std::vector<uint16_t> patches(groups * kDebugDepthPatchElems, 0);
+  for (size_t c = 0; c < n; ++c) {
+    uint16_t* p = &patches[(c / kDebugDepthPatchGroup) * kDebugDepthPatchElems + c % kDebugDepthPatchGroup];
+    const uint16_t* t = taps + 9 * c;   // d, then the eight neighbours in DepthTaps order: the pixel sits in the middle of them
+    for (int k = 0; k < 4; ++k) p[5 * k] = t[1 + k];
+    p[20] = t[0];
+    for (int k = 4; k < 8; ++k) p[5 * (k + 1)] = t[1 + k];
+  }
+  uint16_t* d_patches = nullptr;
+  uint8_t *d_bins = nullptr, *d_out = nullptr;
+  auto run = [&]() -> lmx_status {
+    LMX_HIP(hipMalloc((void**)&d_patches, patches.size() * 2));
+    LMX_HIP(hipMalloc((void**)&d_bins, bins.size()));
+    LMX_HIP(hipMalloc((void**)&d_out, n));
+    LMX_HIP(hipMemcpy(d_patches, patches.data(), patches.size() * 2, hipMemcpyHostToDevice));
+    LMX_HIP(hipMemcpy(d_bins, bins.data(), bins.size(), hipMemcpyHostToDevice));
+    launch_debug_depth_normal_bins(nullptr, d_patches, n, distance_threshold, difference_threshold, variant, d_bins, d_out);
+    LMX_HIP(hipGetLastError());
+    LMX_HIP(hipDeviceSynchronize());
+    LMX_HIP(hipMemcpy(out_bins, d_out, n, hipMemcpyDeviceToHost));
+    return LMX_OK;
+  };
+  const lmx_status st = run();
+  (void)hipFree(d_patches); (void)hipFree(d_bins); (void)hipFree(d_out);
+  return st;
+}
+
 lmx_status lmx_ctx_stats(lmx_ctx* c, int64_t* n_candidates, int64_t* n_raw_matches) {
   if (!c) { set_error("lmx_ctx_stats: null context"); return LMX_ERR_INVALID_ARG; }
   if (n_candidates) *n_candidates = c->stat_cands;

@@ -364,6 +364,8 @@ enum KernelId {
 // The depth quantiser's table on the device: the bank's NORMAL_LUT as median bins plus ONE trailing zero entry, the address of every pixel whose
 // bin is 0 without a look-up (far, no valid neighbours, index past the table) -- the kernel's look-up is then an unconditional load.
 constexpr size_t kNormalBinsDeviceBytes = (size_t)LMX_NORMAL_LUT_SIZE + 1;
+// that table for a NORMAL_LUT of labels (normal_lut_to_bins + the trailing zero); false if an entry is not one-hot/0
+bool normal_bins_device_image(const uint8_t* lut, std::vector<uint8_t>& out /* resized to kNormalBinsDeviceBytes */);
 
 // Streamed input of the one-frame call (lmx_match with a fresh host frame, the reference's own pattern: ..._service.cpp:339-344).  The
 // quantisers of level 0 are launched BEFORE the host has written the frame into the frame set's host-visible device buffer; the calling thread
@@ -445,6 +447,13 @@ void launch_pre_color(hipStream_t s, const uint8_t* src, uint8_t* dst, int SH, i
 void launch_pre_depth(hipStream_t s, const void* src, uint16_t* dst, int SH, int SW, int H, int W, int crop_x, int crop_y, int is_float,
                       int n_frames);
 void launch_debug_orientation_label(hipStream_t s, const short* dx, const short* dy, uint8_t* out, size_t n);
+// Test hook of the depth quantiser's float stage: the bin before the median of n tap tuples, through the production device functions.
+// `patches` holds the tuples so that those functions' addressing resolves (layout: kDebugDepthPatch* below); variant = LMX_DBG_DEPTH_*.
+constexpr int kDebugDepthPatchW = 3;        // row stride: the nine taps p1 + 5 (j W + i), i, j in {-1, 0, 1}, are p1 - 20, - 15, .. + 20
+constexpr int kDebugDepthPatchGroup = 5;    // five tuples interleave into one run of 45 elements: tuple c's p1 = 45 (c / 5) + c % 5 + 20
+constexpr int kDebugDepthPatchElems = 45;
+void launch_debug_depth_normal_bins(hipStream_t s, const uint16_t* patches, size_t n, int distance_threshold, int difference_threshold, int variant,
+                                    const uint8_t* lut_bins /* device, kNormalBinsDeviceBytes */, uint8_t* out);
 void launch_pack_nibbles(hipStream_t s, const uint8_t* lm, uint8_t* lmn, const LevelGeom& g, int n_frames);
 void launch_score_coarse(hipStream_t s, const DeviceBankView& bank, const LevelGeom& g, const uint8_t* const* lm_mod /*[M] device ptrs*/,
                          int n_frames, float threshold, const int32_t* class_slot, Candidate* cands /* cand_list_entries(cap) */,

@@ -1706,6 +1706,29 @@ __global__ void k_debug_orientation_label(const short* __restrict__ dx, const sh
   out[i] = (uint32_t)(q16 & 7) == cq::orientation_label8(dx[i], dy[i]) ? (uint8_t)q16 : (uint8_t)0xff;
 }
 
+// Debug/test entry: the bin before the median that the production device functions give n tap tuples (the pixel and its eight neighbours,
+// any values), for comparison with a per-tuple reference at the rounding boundaries of the float stage and at the edges of the integer
+// bounds.  The functions address a pixel's taps as p1 + 5 (j W + i); with row stride W = 3 these are p1 - 20, - 15, .. + 20, in
+// DepthTaps order, so five tuples interleave into 45 elements (kDebugDepthPatch*) and the functions run unchanged on them.
+__global__ __launch_bounds__(256) void k_debug_depth_normal_bins(const uint16_t* __restrict__ patches, size_t n, int W, int distance_threshold,
+                                                                 int difference_threshold, int variant, const uint8_t* __restrict__ lut_bins,
+                                                                 uint8_t* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const size_t g = i / kDebugDepthPatchGroup;
+  const uint16_t* p1 = patches + g * kDebugDepthPatchElems + (i - g * kDebugDepthPatchGroup) + 20;
+  int bin;
+  if (variant == LMX_DBG_DEPTH_INT) {
+    bin = depth_bin_at<int>(p1, W, distance_threshold, difference_threshold, lut_bins);
+  } else if (variant == LMX_DBG_DEPTH_INT64) {
+    bin = depth_bin_at<long long>(p1, W, distance_threshold, difference_threshold, lut_bins);
+  } else {   // LMX_DBG_DEPTH_PIPELINED: the look-up of depth_quantize_body's interior loop (no early exit for far pixels, the entry behind the table)
+    const int idx = depth_lut_index_lean(depth_load_taps(p1, W), distance_threshold, difference_threshold);
+    bin = lut_bins[idx >= 0 ? idx : LMX_NORMAL_LUT_SIZE];
+  }
+  out[i] = (uint8_t)bin;
+}
+
 // Read-back by kernel instead of by DMA.  hipMemcpyAsync(DeviceToHost) was seen to block the submitting thread for 5-11 ms
 // now and then when copies from two streams are in flight (ROCm 7.2, MI355X), which a pipelined caller pays in full; a copy
 // kernel writing through the host mapping of the pinned buffer is queued like any other kernel.  `dst` may be pinned host
@@ -1802,6 +1825,13 @@ void launch_pre_depth(hipStream_t s, const void* src, uint16_t* dst, int SH, int
 
 void launch_debug_orientation_label(hipStream_t s, const short* dx, const short* dy, uint8_t* out, size_t n) {
   hipLaunchKernelGGL(k_debug_orientation_label, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dx, dy, out, n);
+}
+
+void launch_debug_depth_normal_bins(hipStream_t s, const uint16_t* patches, size_t n, int distance_threshold, int difference_threshold, int variant,
+                                    const uint8_t* lut_bins, uint8_t* out) {
+  static_assert(kDebugDepthPatchElems == 5 * kDebugDepthPatchW * 2 + 5 * 2 + kDebugDepthPatchGroup, "taps at p1 - 20 .. p1 + 20, five tuples interleaved");
+  hipLaunchKernelGGL(k_debug_depth_normal_bins, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, patches, n, kDebugDepthPatchW, distance_threshold,
+                     difference_threshold, variant, lut_bins, out);
 }
 
 // ---- launchers --------------------------------------------------------------------------------------------

@@ -246,8 +246,8 @@ lmx_status train_add_template(lmx_bank* bank, int device, const lmx_image* sourc
           d_cur_src = d_next;
         } else {
           if (l == 0) {
-            std::vector<uint8_t> bins(lmx::kNormalBinsDeviceBytes);   // zero-initialised: the trailing entry stays 0
-            if (!normal_lut_to_bins(bank->normal_lut.data(), bins.data())) { set_error("bank holds an invalid normal LUT"); return LMX_ERR_INVALID_ARG; }
+            std::vector<uint8_t> bins;
+            if (!normal_bins_device_image(bank->normal_lut.data(), bins)) { set_error("bank holds an invalid normal LUT"); return LMX_ERR_INVALID_ARG; }
             uint8_t* d_bins = (uint8_t*)dmalloc(bins.size());
             if (!d_bins) { set_error("hipMalloc failed"); return LMX_ERR_HIP; }
             TR_HIP(hipMemcpy(d_bins, bins.data(), bins.size(), hipMemcpyHostToDevice));
@@ -514,8 +514,8 @@ lmx_status train_mesh(lmx_bank* bank, int device, const double* triangles, int n
     d_depth = (uint16_t*)dmalloc(px0 * B * 2);
     d_bins = (uint8_t*)dmalloc(kNormalBinsDeviceBytes);
     if (!d_depth || !d_bins) { set_error("hipMalloc failed"); return LMX_ERR_HIP; }
-    std::vector<uint8_t> bins(kNormalBinsDeviceBytes);   // zero-initialised: the trailing entry stays 0
-    if (!normal_lut_to_bins(bank->normal_lut.data(), bins.data())) { set_error("bank holds an invalid normal LUT"); return LMX_ERR_INVALID_ARG; }
+    std::vector<uint8_t> bins;
+    if (!normal_bins_device_image(bank->normal_lut.data(), bins)) { set_error("bank holds an invalid normal LUT"); return LMX_ERR_INVALID_ARG; }
     TR_HIP(hipMemcpy(d_bins, bins.data(), bins.size(), hipMemcpyHostToDevice));
   }
   TR_HIP(hipMemcpy(d_tri, triangles, (size_t)n_tri * 9 * sizeof(double), hipMemcpyHostToDevice));

@@ -200,6 +200,81 @@ def quantized_normals(depth, distance_threshold=2000, difference_threshold=50, n
     return median5(out), out
 
 
+# Per-tuple form of the stage before the median: a pixel of quantizedNormals sees the image only through nine values (its depth and
+# the eight neighbours at distance 5), so the stage is a function of that tuple and can be evaluated where no image is at hand --
+# at the rounding boundaries of the float chain and at the edges of the integer ranges (tests/depth_cases.py).
+TAP_OFFSETS = ((-5, -5), (-5, 0), (-5, 5), (0, -5), (0, 5), (5, -5), (5, 0), (5, 5))   # (j = dy, i = dx) of taps[:, 1:], upstream's order
+
+
+def _ulps(x, k):
+    """float32 array x moved by k units in the last place (k in {-1, 0, 1}; x > 0 where k != 0)."""
+    if k == 0:
+        return x
+    return np.nextafter(x, F32(np.inf) if k > 0 else F32(-np.inf)).astype(F32)
+
+
+def normal_bin_of_taps(taps, dist_thr, diff_thr, lut=None, s_ulps=0, inv_ulps=0, detail=False):
+    """taps: [n, 9] integers, the pixel's depth then its eight neighbours in TAP_OFFSETS order; dist_thr, diff_thr: scalars or [n].
+    -> (bin, idx, ss): the median bin before the median (0 = no label, k + 1 = label 1 << k), the flat NORMAL_LUT index of the
+    look-up (-1 where there is none: far pixel, s == 0, index past the table) and the float32 sum of squares.
+    int64 accumulation like upstream's `long`, then float32 with numpy's correctly rounded sqrt and divide in the written order.
+    s_ulps / inv_ulps move s / inv by that many float32 ulps: the mutants a test must be able to tell from the real thing."""
+    t = np.asarray(taps).astype(np.int64).reshape(-1, 9)
+    dist = np.broadcast_to(np.asarray(dist_thr, np.int64), t.shape[:1])
+    thr = np.broadcast_to(np.asarray(diff_thr, np.int64), t.shape[:1])
+    d = t[:, 0]
+    A0 = np.zeros_like(d); A1 = np.zeros_like(d); A3 = np.zeros_like(d); b0 = np.zeros_like(d); b1 = np.zeros_like(d)
+    for k, (j, i) in enumerate(TAP_OFFSETS):
+        delta = t[:, 1 + k] - d
+        f = (np.abs(delta) < thr).astype(np.int64)
+        A0 += f * (i * i); A1 += f * (i * j); A3 += f * (j * j)
+        b0 += f * i * delta; b1 += f * j * delta
+    det = A0 * A3 - A1 * A1
+    ddx = A3 * b0 - A1 * b1
+    ddy = -A1 * b0 + A0 * b1
+    nx = (1150 * ddx).astype(F32)
+    ny = (1150 * ddy).astype(F32)
+    nz = (-det * d).astype(F32)
+    ss = (((nx * nx).astype(F32) + (ny * ny).astype(F32)).astype(F32) + (nz * nz).astype(F32)).astype(F32)
+    s = np.sqrt(ss).astype(F32)
+    pos = s > 0
+    s = np.where(pos, _ulps(np.where(pos, s, F32(1)), s_ulps), s).astype(F32)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        inv = (F32(1.0) / s).astype(F32)
+        inv = np.where(pos, _ulps(np.where(pos, inv, F32(1)), inv_ulps), inv).astype(F32)
+        v1 = ((nx * inv).astype(F32) * F32(10) + F32(10)).astype(F32)
+        v2 = ((ny * inv).astype(F32) * F32(10) + F32(10)).astype(F32)
+        v3 = ((nz * inv).astype(F32) * F32(20) + F32(20)).astype(F32)
+    good = (d < dist) & pos
+    v1i = np.where(good, v1, 0).astype(np.int64)   # truncation toward zero
+    v2i = np.where(good, v2, 0).astype(np.int64)
+    v3i = np.where(good, v3, 0).astype(np.int64)
+    flat = (v3i * 20 + v2i) * 20 + v1i
+    look = good & (flat >= 0) & (flat < 8000)
+    idx = np.where(look, flat, -1)
+    table = (default_normal_lut() if lut is None else np.asarray(lut, np.uint8)).reshape(8000)
+    lab = np.where(look, table[np.clip(idx, 0, 7999)], 0).astype(np.uint8)
+    bins = label_to_bin(lab)
+    if detail:
+        return bins, idx, ss, dict(det=det, ddx=ddx, ddy=ddy, far=~(d < dist), v1=v1i, v2=v2i, v3=v3i, good=good,
+                                   mask=sum(((np.abs(t[:, 1 + k] - d) < thr).astype(np.int64) << k) for k in range(8)))
+    return bins, idx, ss
+
+
+def label_to_bin(lab):
+    """0 -> 0, 1 << k -> k + 1: the order of the label VALUES, which is what the median sorts by."""
+    lab = np.asarray(lab, np.uint8)
+    out = np.zeros(lab.shape, np.uint8)
+    for k in range(8):
+        out[lab == (1 << k)] = k + 1
+    return out
+
+
+def bin_to_label(b):
+    b = np.asarray(b).astype(np.int64)
+    return np.where(b > 0, 1 << np.maximum(b - 1, 0), 0).astype(np.uint8)
+
+
 # ---- A.5 - A.7 -----------------------------------------------------------------------------------------------
 def spread(q, T):
     H, W = q.shape
