@@ -550,6 +550,24 @@ lmx_status lmx_debug_introsort_perm_score(const double* score, int32_t n, int32_
 /* The permutation the DEVICE's workgroup-parallel form of the same algorithm (csrc/lmx_sort_block.hpp, what k_f2_finalize_cluster runs
  * for Detector::match's std::sort) produces for n <= 2048 (similarity, template_id) pairs: must equal lmx_debug_introsort_perm's. */
 lmx_status lmx_debug_device_sort_perm(int32_t device, const float* similarity, const int32_t* template_id, int32_t n, int32_t* perm);
+/* Test hook: the device consumer chain of lmx_ctx_collect_clusters (k_f2_finalize_cluster, csrc/lmx_f2.hip: the same kernel, the same
+ * launch) on records the CALLER supplies instead of a slot an enqueue wrote.  Stand-alone, no context: the records are copied to the
+ * device behind a slot header that counts n_records, the slot's capacity is n_records.  A record belongs to frame `frame`; records
+ * whose frame is outside 0 .. n_frames - 1 are ignored, frames may be interleaved in any order, order_key must be unique per frame.
+ * Outputs (host arrays, all required): matches [n_frames][2048], clusters [n_frames][2048], members [n_frames][2048] and
+ * counts [n_frames][4] = {final matches, clusters, members, status}, exactly as the kernel wrote them -- NO host completion:
+ *   status 0: the frame is complete; members index the frame's matches, member_begin is relative to the frame's members row;
+ *   status 1: more than 2048 records; counts[0] = the frame's record count, nothing else is written;
+ *   status 2: a template_id outside the side-car, or a vote bin outside +-2^16 / a depth ring outside +-2^18; counts[0] = final
+ *             matches, the frame's matches row is valid, no clusters.
+ * (lmx_ctx_collect_clusters finishes status 1 and 2 frames on the host.)  Parameters and side-car are validated as by
+ * lmx_ctx_set_cluster_sidecar; n_frames must be 1..8.  Every record's x and y must fit an int16 and its class_index a uint16
+ * (LMX_ERR_INVALID_ARG otherwise): the kernel holds them in LDS at that width, which the records of an enqueue always satisfy
+ * (image coordinates, class slots).  LMX_ERR_NO_DEVICE without a GPU. */
+lmx_status lmx_debug_device_finalize_cluster(int32_t device, const lmx_raw_match_t* records, size_t n_records, int32_t n_frames,
+                                             const double* obj_origin_dists, const int32_t* rects, size_t n_templates,
+                                             const lmx_cluster_params* params, lmx_match_t* matches, lmx_cluster_t* clusters, int32_t* members,
+                                             uint32_t* counts);
 /* Counters of the last collect(): coarse candidates and refined matches summed over frames. */
 lmx_status lmx_ctx_stats(lmx_ctx* ctx, int64_t* n_candidates, int64_t* n_raw_matches);
 

@@ -281,6 +281,79 @@ lmx_status lmx_debug_device_sort_perm(int32_t device, const float* similarity, c
   (void)hipFree(d_sim); (void)hipFree(d_tid); (void)hipFree(d_perm); (void)hipFree(d_spill);
   return st;
 }
+// The whole device consumer chain (k_f2_finalize_cluster, as lmx_ctx_collect_clusters launches it) on a caller's record list: the records
+// become a raw-match slot of their own (16-dword header with [1] = n_records, cap = n_records), the kernel's outputs and per-frame count
+// words come back as written -- no host completion, so a test sees which path the kernel took.
+lmx_status lmx_debug_device_finalize_cluster(int32_t device, const lmx_raw_match_t* records, size_t n_records, int32_t n_frames,
+                                             const double* obj_origin_dists, const int32_t* rects, size_t n_templates, const lmx_cluster_params* params,
+                                             lmx_match_t* matches, lmx_cluster_t* clusters, int32_t* members, uint32_t* counts) {
+  if ((n_records && !records) || !obj_origin_dists || !rects || n_templates == 0 || !params || !matches || !clusters || !members || !counts) {
+    set_error("lmx_debug_device_finalize_cluster: invalid argument");
+    return LMX_ERR_INVALID_ARG;
+  }
+  if (n_frames < 1 || n_frames > 8) { set_error("lmx_debug_device_finalize_cluster: n_frames must be 1..8 (got %d)", n_frames); return LMX_ERR_INVALID_ARG; }
+  if (n_records > ((size_t)1 << 24) || n_templates > ((size_t)1 << 24)) { set_error("lmx_debug_device_finalize_cluster: at most 2^24 records and templates"); return LMX_ERR_INVALID_ARG; }
+  if (params->vote_row_col_step <= 0) { set_error("vote_row_col_step must be positive"); return LMX_ERR_INVALID_ARG; }
+  if (params->cluster_size_thresh < 0) { set_error("cluster_size_thresh must not be negative"); return LMX_ERR_INVALID_ARG; }
+  if (lmx_status vs = check_vote_rings(obj_origin_dists, n_templates, params)) return vs;
+  for (size_t i = 0; i < n_records; ++i) {   // the kernel keeps x, y as int16 and class_index as uint16 in LDS
+    const lmx_raw_match_t& r = records[i];
+    if (r.x < -32768 || r.x > 32767 || r.y < -32768 || r.y > 32767 || r.class_index < 0 || r.class_index > 65535) {
+      set_error("lmx_debug_device_finalize_cluster: record %zu: x, y must fit an int16 and class_index a uint16", i);
+      return LMX_ERR_INVALID_ARG;
+    }
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available; this library has no CPU path"); return LMX_ERR_NO_DEVICE; }
+  LMX_HIP(hipSetDevice(device));
+  const size_t F = (size_t)n_frames;
+  uint32_t hdr[16] = {0};
+  hdr[1] = (uint32_t)n_records;
+  uint32_t *d_hdr = nullptr, *d_counts = nullptr;
+  lmx_raw_match_t* d_recs = nullptr;
+  lmx_match_t* d_matches = nullptr;
+  lmx_cluster_t* d_clusters = nullptr;
+  int32_t *d_members = nullptr, *d_rects = nullptr;
+  uint8_t* d_scratch = nullptr;
+  double* d_dists = nullptr;
+  auto run = [&]() -> lmx_status {
+    LMX_HIP(hipMalloc((void**)&d_hdr, sizeof(hdr)));
+    LMX_HIP(hipMalloc((void**)&d_recs, std::max<size_t>(n_records, 1) * sizeof(lmx_raw_match_t)));
+    LMX_HIP(hipMalloc((void**)&d_matches, F * F2_MAX * sizeof(lmx_match_t)));
+    LMX_HIP(hipMalloc((void**)&d_clusters, F * F2_MAX * sizeof(lmx_cluster_t)));
+    LMX_HIP(hipMalloc((void**)&d_members, F * F2_MAX * sizeof(int32_t)));
+    LMX_HIP(hipMalloc((void**)&d_counts, F * 4 * sizeof(uint32_t)));
+    LMX_HIP(hipMalloc((void**)&d_scratch, F * F2_MAX * 32));
+    LMX_HIP(hipMalloc((void**)&d_dists, n_templates * sizeof(double)));
+    LMX_HIP(hipMalloc((void**)&d_rects, n_templates * 4 * sizeof(int32_t)));
+    LMX_HIP(hipMemcpy(d_hdr, hdr, sizeof(hdr), hipMemcpyHostToDevice));
+    if (n_records) LMX_HIP(hipMemcpy(d_recs, records, n_records * sizeof(lmx_raw_match_t), hipMemcpyHostToDevice));
+    LMX_HIP(hipMemcpy(d_dists, obj_origin_dists, n_templates * sizeof(double), hipMemcpyHostToDevice));
+    LMX_HIP(hipMemcpy(d_rects, rects, n_templates * 4 * sizeof(int32_t), hipMemcpyHostToDevice));
+    LMX_HIP(hipMemset(d_matches, 0, F * F2_MAX * sizeof(lmx_match_t)));
+    LMX_HIP(hipMemset(d_clusters, 0, F * F2_MAX * sizeof(lmx_cluster_t)));
+    LMX_HIP(hipMemset(d_members, 0, F * F2_MAX * sizeof(int32_t)));
+    LMX_HIP(hipMemset(d_counts, 0xff, F * 4 * sizeof(uint32_t)));   // a frame the kernel did not report on stays recognisable
+    F2Params p{};
+    p.recs = d_recs; p.hdr = d_hdr; p.cap = (uint32_t)n_records; p.n_frames = n_frames;
+    p.out_matches = d_matches; p.out_counts = d_counts; p.out_clusters = d_clusters; p.out_members = d_members; p.scratch = d_scratch;
+    p.dists = d_dists; p.rects = d_rects; p.n_templates = (uint32_t)n_templates;
+    p.step = params->vote_row_col_step; p.size_thresh = params->cluster_size_thresh; p.do_clusters = 1;
+    p.radius_min = params->renderer_radius_min; p.radius_step = params->renderer_radius_step;
+    launch_f2(nullptr, p);
+    LMX_HIP(hipGetLastError());
+    LMX_HIP(hipDeviceSynchronize());
+    LMX_HIP(hipMemcpy(matches, d_matches, F * F2_MAX * sizeof(lmx_match_t), hipMemcpyDeviceToHost));
+    LMX_HIP(hipMemcpy(clusters, d_clusters, F * F2_MAX * sizeof(lmx_cluster_t), hipMemcpyDeviceToHost));
+    LMX_HIP(hipMemcpy(members, d_members, F * F2_MAX * sizeof(int32_t), hipMemcpyDeviceToHost));
+    LMX_HIP(hipMemcpy(counts, d_counts, F * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return LMX_OK;
+  };
+  const lmx_status st = run();
+  (void)hipFree(d_hdr); (void)hipFree(d_recs); (void)hipFree(d_matches); (void)hipFree(d_clusters); (void)hipFree(d_members);
+  (void)hipFree(d_counts); (void)hipFree(d_scratch); (void)hipFree(d_dists); (void)hipFree(d_rects);
+  return st;
+}
 lmx_status lmx_debug_introsort_perm_score(const double* score, int32_t n, int32_t* perm) {
   if (n < 0 || (n > 0 && (!score || !perm))) { set_error("lmx_debug_introsort_perm_score: invalid argument"); return LMX_ERR_INVALID_ARG; }
   for (int32_t i = 0; i < n; ++i) perm[i] = i;

@@ -607,6 +607,35 @@ def cluster_matches(matches, obj_origin_dists, rects, vote_row_col_step, rendere
     return clusters[:n.value].copy(), members
 
 
+F2_MAX = 2048   # records per frame the device chain takes (csrc/lmx_internal.hpp)
+
+
+def debug_device_finalize_cluster(records, n_frames, obj_origin_dists, rects, vote_row_col_step, renderer_radius_min, renderer_radius_step,
+                                  cluster_size_thresh=2, device=0, with_counts=False):
+    """Test hook (lmx_debug_device_finalize_cluster): the kernel behind Detector.collect_clusters on a caller's RAW_MATCH_DTYPE records
+    (all frames in one list, tagged by `frame`) -> list per frame of (matches, clusters, members, status), cut to the counts the
+    kernel reported and otherwise as it wrote them: no host completion.  status 1 (more than F2_MAX records): all three are empty;
+    status 2 (side-car / range): matches only.  with_counts: also the kernel's count words, uint32 [n_frames][4]."""
+    records = np.ascontiguousarray(records, RAW_MATCH_DTYPE)
+    dists = np.ascontiguousarray(obj_origin_dists, np.float64)
+    rects = np.ascontiguousarray(rects, np.int32).reshape(-1, 4)
+    pp = _lib.ClusterParams(int(vote_row_col_step), float(renderer_radius_min), float(renderer_radius_step), int(cluster_size_thresh))
+    nf = max(1, int(n_frames))
+    m = np.zeros((nf, F2_MAX), MATCH_DTYPE)
+    cl = np.zeros((nf, F2_MAX), CLUSTER_DTYPE)
+    mem = np.zeros((nf, F2_MAX), np.int32)
+    counts = np.zeros((nf, 4), np.uint32)
+    _lib.check(_lib.lib().lmx_debug_device_finalize_cluster(device, records.ctypes.data, len(records), int(n_frames), dists.ctypes.data, rects.ctypes.data,
+                                                            len(dists), C.byref(pp), m.ctypes.data, cl.ctypes.data, mem.ctypes.data, counts.ctypes.data))
+    out = []
+    for f in range(n_frames):
+        n_m, n_c, n_mem, status = (int(v) for v in counts[f])
+        if status == 1:   # counts[0] is the record count here, not a number of matches written
+            n_m = 0
+        out.append((m[f, :n_m].copy(), cl[f, :n_c].copy(), mem[f, :n_mem].copy(), status))
+    return (out, counts) if with_counts else out
+
+
 GATHER_HEADER_BYTES = 64
 
 

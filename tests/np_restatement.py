@@ -419,3 +419,94 @@ def match(bank, sources, threshold):
                 cands = keep
             out += [(x, y, F32(s), cid, tid) for x, y, s in cands]
     return out
+
+
+# ---- node-side steps in front of match() (lmx_ctx_upload_raw; the oracle's pre_color / pre_depth) ----------------------------------------
+def pre_color(src, crop_xy, size_wh, blur3=True):
+    """(MONO8 -> BGR) + GaussianBlur 3x3 (sigma 0: [1 2 1] / 4 per axis, on 8U exactly (sum + 8) >> 4, BORDER_REFLECT_101) on the FULL
+    frame, then the crop.  src: u8 HxW or HxWx3 -> u8 [H, W, 3]."""
+    img = np.asarray(src, np.uint8)
+    if img.ndim == 2:
+        img = np.repeat(img[:, :, None], 3, axis=2)
+    if blur3:
+        p = np.pad(img.astype(np.int32), ((1, 1), (1, 1), (0, 0)), mode="reflect")
+        h = p[:, :-2] + 2 * p[:, 1:-1] + p[:, 2:]
+        v = h[:-2] + 2 * h[1:-1] + h[2:]
+        img = ((v + 8) >> 4).astype(np.uint8)
+    (cx, cy), (W, H) = crop_xy, size_wh
+    return np.ascontiguousarray(img[cy:cy + H, cx:cx + W])
+
+
+def pre_depth(z, crop_xy, size_wh):
+    """convertTo(CV_16UC1, 1000.0) of float metres: the float32 product, cvRound (half to even), saturate to u16; NaN, Inf and products
+    outside (-2^31, 2^31) give 0 (x86's integer indefinite, saturated)."""
+    with np.errstate(over="ignore", invalid="ignore"):
+        v = np.asarray(z, np.float32) * np.float32(1000.0)
+        assert v.dtype == np.float32
+        ok = (v > np.float32(-2147483648.0)) & (v < np.float32(2147483648.0))
+        r = np.clip(np.rint(np.where(ok, v, np.float32(0)).astype(np.float64)), 0, 65535)
+    (cx, cy), (W, H) = crop_xy, size_wh
+    return np.ascontiguousarray(np.where(ok, r, 0).astype(np.uint16)[cy:cy + H, cx:cx + W])
+
+
+def _z_with_product(target, span=4):
+    """float32 z near target / 1000 whose float32 product z * 1000.f is exactly `target`, or None."""
+    z0 = np.float32(np.float64(target) / 1000.0)
+    cand = [z0]
+    lo = hi = z0
+    for _ in range(span):
+        lo, hi = np.nextafter(lo, np.float32(-np.inf)), np.nextafter(hi, np.float32(np.inf))
+        cand += [lo, hi]
+    for z in cand:
+        if np.float32(z) * np.float32(1000.0) == np.float32(target) and np.float64(np.float32(target)) == np.float64(target):
+            return np.float32(z)
+    return None
+
+
+def pre_depth_special_values(k_range=range(0, 3000, 7)):
+    """The float32 inputs at which float-metre -> u16-millimetre conversion can go wrong.  -> (table float32 [n], n_even, n_odd): the
+    number of z found whose product is exactly k + 0.5 with k even / odd (ties: half to even decides)."""
+    up, dn = (lambda z: np.nextafter(np.float32(z), np.float32(np.inf))), (lambda z: np.nextafter(np.float32(z), np.float32(-np.inf)))
+    out, n_even, n_odd = [], 0, 0
+    for k in k_range:
+        z = _z_with_product(k + 0.5)
+        if z is None:
+            continue
+        if (k % 2 == 0 and n_even >= 40) or (k % 2 == 1 and n_odd >= 40):
+            continue
+        n_even, n_odd = n_even + (k % 2 == 0), n_odd + (k % 2 == 1)
+        out += [z, up(z), dn(z)]
+        if k < 200:
+            out += [-z, -up(z), -dn(z)]                      # negative ties and their neighbours
+    out += [-0.0, 0.0, -1e-4, -4e-4, -4.9e-4, -6e-4, -1e-3, -1.4e-3, -1.6e-3, -0.3]                          # small negatives, -0.0
+    out += [1e-45, -1e-45, 1e-40, -1e-40, 1.1754942e-38, 1.17549435e-38]                                     # denormals, the smallest normal
+    for target in (65534.5, 65535.0, 65535.5, 70000.0):     # the saturation: the z whose product is the target where one exists (not
+        z = _z_with_product(target)                          # every float is a product z * 1000.f), and the z on either side of it
+        if z is None:
+            z = np.float32(target / 1000.0)
+            while np.float32(z) * np.float32(1000.0) > np.float32(target):
+                z = dn(z)
+        out += [z, up(z), dn(z)]
+    z = np.float32(2147483.648)
+    while np.float32(z) * np.float32(1000.0) >= np.float32(2147483648.0):
+        z = dn(z)
+    while np.float32(up(z)) * np.float32(1000.0) < np.float32(2147483648.0):
+        z = up(z)
+    out += [z, up(z), -z, -up(z)]                            # the largest product below 2^31, the first one that reaches it
+    out += [3e38, -3e38, 3.5e35, np.inf, -np.inf, np.nan]   # products that overflow to Inf
+    return np.asarray(out, np.float32), n_even, n_odd
+
+
+def pre_special_frames(SW, SH, seed):
+    """Raw frames for the node-side steps: a BGR noise frame with runs of 0 and 255 (the blur's rounding and its reflected border see
+    extremes next to noise) and a float32 depth plane tiled with pre_depth_special_values().  -> (bgr, z, table, n_even, n_odd)."""
+    rng = np.random.default_rng(seed)
+    bgr = rng.integers(0, 256, (SH, SW, 3), dtype=np.uint8)
+    for _ in range(60):
+        y, x, n, c = int(rng.integers(0, SH)), int(rng.integers(0, SW)), int(rng.integers(2, 40)), int(rng.integers(0, 4))
+        bgr[y, x:x + n, slice(0, 3) if c == 3 else slice(c, c + 1)] = rng.choice([0, 255])   # all channels, or one
+    bgr[[0, 1, -2, -1], ::3] = 255       # extremes on the rows and columns the reflected border reads twice
+    bgr[::5, [0, 1, -2, -1]] = 0
+    table, n_even, n_odd = pre_depth_special_values()
+    z = table[(np.arange(SH)[:, None] * SW + np.arange(SW)[None, :]) % len(table)]
+    return np.ascontiguousarray(bgr), np.ascontiguousarray(z), table, n_even, n_odd

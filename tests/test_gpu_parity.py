@@ -490,6 +490,50 @@ def test_upload_raw_node_side_preprocessing(mono):
     det.close()
 
 
+PRE_CROPS = [(0, 0), (24, 16), (24, 0), (0, 16), (11, 7)]
+
+
+@pytest.mark.parametrize("kind", ["bgr", "mono_on_bgr_context", "mono_on_gray_context"])
+def test_upload_raw_pixels_at_every_crop_and_depth_special_values(kind):
+    """k_pre_color and k_pre_depth pixel for pixel: a 184x176 raw frame cropped to a 160x160 context at crops that touch the source's
+    left / right / top / bottom edges and at an odd offset, with and without the 3x3 blur; BGR and MONO8 sources, BGR and gray contexts.
+    Colour: noise with runs of 0 and 255 against the oracle's pre_color AND a numpy restatement (reflect-pad the full frame, [1 2 1] in
+    both axes, (sum + 8) >> 4, crop).  Depth: a float32 plane tiled with the values at which `z * 1000.f -> cvRound -> saturate` can go
+    wrong -- products that are exact ties k + 0.5 (k even and odd) and their neighbours one ulp either way, negative ties, small
+    negatives, -0.0, denormals, the 65535 saturation, the 2^31 limit, products that overflow to Inf, Inf and NaN -- against the numpy
+    restatement (float32 product, range test, rint in float64, clip) and the oracle's pre_depth."""
+    import np_restatement as npr
+    from test_gpu_gray import rep3
+    W, H, SW, SH = 160, 160, 184, 176
+    gray_ctx, mono = kind == "mono_on_gray_context", kind != "bgr"
+    bgr, z, table, n_even, n_odd = npr.pre_special_frames(SW, SH, 71)
+    assert n_even >= 32 and n_odd >= 32, (n_even, n_odd)       # enough exact ties of either parity among the inputs
+    bank = synth.make_bank(10, seed=72, size_range=(20.0, 36.0))
+    det = Detector(bank, W, H, max_batch=2, gray=gray_ctx)
+    colors = [np.ascontiguousarray(bgr[:, :, 1]), np.ascontiguousarray(bgr[::-1, ::-1, 2])] if mono else [bgr, np.ascontiguousarray(bgr[::-1, ::-1])]
+    depths = [z, np.ascontiguousarray(z[::-1, ::-1])]
+    all_bits = np.unique(table.view(np.uint32))
+    for crop in PRE_CROPS:
+        for f in range(2):     # every crop of either frame holds every special value
+            assert np.array_equal(np.unique(depths[f][crop[1]:crop[1] + H, crop[0]:crop[0] + W].view(np.uint32)), all_bits)
+        ref_d = [npr.pre_depth(d, crop, (W, H)) for d in depths]
+        for f in range(2):
+            assert np.array_equal(o.pre_depth(depths[f], crop, (W, H)), ref_d[f]), crop
+        for blur in (True, False):
+            det.upload_raw([[colors[f], depths[f]] for f in range(2)], (SW, SH), crop, blur3=blur, mono=mono, depth_float_m=True)
+            det.enqueue(2, 90.0)
+            det.collect(2)
+            for f in range(2):
+                ref_c = npr.pre_color(colors[f], crop, (W, H), blur)
+                assert np.array_equal(o.pre_color(colors[f], crop, (W, H), blur), ref_c), (crop, blur, f)
+                if mono:
+                    assert np.array_equal(ref_c, rep3(ref_c[..., 0]))
+                got_c = det.debug_pyramid_bgr(f, 0, 0)
+                assert np.array_equal(got_c, ref_c[..., 0] if gray_ctx else ref_c), (crop, blur, f)
+                assert np.array_equal(det.debug_depth(f, 1), ref_d[f]), (crop, blur, f)
+    det.close()
+
+
 def test_add_template_trainer_parity(tmp_path):
     """lmx_bank_add_template (device quantisation + host feature selection) builds the same template
     pyramids, ids and bounding boxes as the oracle's restatement of Detector::addTemplate; failures return -1 and add

@@ -350,3 +350,27 @@ def test_orientation_label_is_an_exact_integer_rule_over_the_sobel_domain():
     q = np.where(dy < 0, 16 - q, q)
     assert np.array_equal(q, ref)
     assert (mx * 1282).max() < 2 ** 23  # the device multiplies with v_mul_i32_i24
+
+
+def test_node_side_steps_oracle_equals_numpy_restatement():
+    """The oracle's pre_color / pre_depth (the checker of lmx_ctx_upload_raw) against the numpy restatements of tests/np_restatement.py on
+    the inputs tests/test_gpu_parity.py gives the kernels: crops at every edge of the source, the depth table of rounding ties,
+    saturation, the 2^31 limit, overflow, Inf and NaN.  Also pins the table itself: enough exact ties of either parity."""
+    npr = R
+    W, H, SW, SH = 160, 160, 184, 176
+    bgr, z, table, n_even, n_odd = npr.pre_special_frames(SW, SH, 71)
+    assert n_even >= 32 and n_odd >= 32
+    with np.errstate(over="ignore", invalid="ignore"):
+        prod = table * np.float32(1000.0)
+        ties = prod[np.isfinite(prod) & (np.abs(prod) < 4000) & (prod - np.floor(prod) == 0.5)]
+    k = np.floor(ties[ties > 0]).astype(np.int64)
+    assert (k % 2 == 0).sum() >= 32 and (k % 2 == 1).sum() >= 32 and (ties < 0).sum() >= 8
+    full = npr.pre_depth(z, (0, 0), (SW, SH))
+    pos = np.isin(z, table[np.isin(prod, ties[ties > 0])])
+    assert (full[pos] % 2 == 0).all() and pos.sum() > 1000          # every positive tie went to the even neighbour
+    assert set(np.unique(full[~np.isfinite(z)])) == {0} and full.max() == 65535
+    for crop in [(0, 0), (24, 16), (24, 0), (0, 16), (11, 7)]:
+        assert np.array_equal(o.pre_depth(z, crop, (W, H)), npr.pre_depth(z, crop, (W, H)))
+        for blur in (True, False):
+            for src in (bgr, np.ascontiguousarray(bgr[:, :, 1])):
+                assert np.array_equal(o.pre_color(src, crop, (W, H), blur), npr.pre_color(src, crop, (W, H), blur)), (crop, blur, src.ndim)
