@@ -2,26 +2,13 @@
 // lmx_bank_create / _add_class / accessors / NORMAL_LUT handling -- and the library's error string.
 // Reference call sites: /root/reference/src/renderer.cpp:179-185,308 (ctor, addTemplate), src/rgbdDetector.cpp:1668-1680 (readLinemod).
 
-#include <algorithm>
-#include <atomic>
-#include <chrono>
-#include <condition_variable>
-#include <mutex>
-#include <shared_mutex>
-#include <thread>
 #include <cctype>
-#include <cmath>
-#include <cstdlib>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
-#include <functional>
-#include <map>
-#include <memory>
 #include <string>
 #include <vector>
-
-#include <sys/stat.h>
 
 #include "lmx_ctx.hpp"
 

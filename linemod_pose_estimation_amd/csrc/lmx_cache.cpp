@@ -2,22 +2,12 @@
 // fingerprint, the compact binary bank file, the process-wide bank cache behind lmx_bank_load_yaml_cached and the device-context
 // cache behind lmx_ctx_acquire.
 
-#include <algorithm>
 #include <atomic>
-#include <chrono>
-#include <condition_variable>
-#include <mutex>
-#include <shared_mutex>
-#include <thread>
-#include <cctype>
-#include <cmath>
-#include <cstdlib>
-#include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
-#include <functional>
-#include <map>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <vector>
 

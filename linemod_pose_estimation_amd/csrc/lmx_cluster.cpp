@@ -3,25 +3,10 @@
 // of the same chain is csrc/lmx_f2.hip.
 
 #include <algorithm>
-#include <atomic>
-#include <chrono>
-#include <condition_variable>
-#include <mutex>
-#include <shared_mutex>
-#include <thread>
-#include <cctype>
 #include <cmath>
-#include <cstdlib>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
-#include <functional>
 #include <map>
-#include <memory>
-#include <string>
 #include <vector>
-
-#include <sys/stat.h>
 
 #include "lmx_ctx.hpp"
 

@@ -5,23 +5,10 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
-#include <condition_variable>
-#include <mutex>
-#include <shared_mutex>
-#include <thread>
-#include <cctype>
-#include <cmath>
-#include <cstdlib>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
-#include <functional>
-#include <map>
-#include <memory>
-#include <string>
+#include <utility>
 #include <vector>
-
-#include <sys/stat.h>
 
 #include "lmx_ctx.hpp"
 
@@ -79,7 +66,7 @@ static lmx_status collect_impl(lmx_ctx* c, int32_t n_frames, std::vector<std::ve
   using clk = std::chrono::steady_clock;
   const clk::time_point t0 = clk::now();
   bool seen = false;
-  if (c->pub_seq[slot] != 0 && !c->env_no_header_poll && c->profiling == 0) {
+  if (c->pub_seq[slot] != 0 && !c->env.no_header_poll && c->profiling == 0) {
     // one or two frames per call: k_refine's last workgroup publishes the slot and then its sequence number (word 7 of the pinned header);
     // spinning on that word sees the result a few microseconds before the event's wake-up does.  Bounded: 200 us, then the event as always
     const volatile uint32_t* word = reinterpret_cast<const volatile uint32_t*>(c->h_out_slot[slot]) + 7;
@@ -99,7 +86,7 @@ static lmx_status collect_impl(lmx_ctx* c, int32_t n_frames, std::vector<std::ve
   if (c->outstanding == 0) drain_profiling(c);  // every recorded event has completed
   const uint32_t n_cand = reinterpret_cast<uint32_t*>(c->h_out)[0];
   const uint32_t n_match = reinterpret_cast<uint32_t*>(c->h_out)[1];
-  if (c->env_debug_collect) {
+  if (c->env.debug_collect) {
     // diagnostics: the device-side slot against its pinned host mirror once the slot's event has completed
     uint32_t dev[16];
     if (hipMemcpy(dev, d_slot, 64, hipMemcpyDeviceToHost) == hipSuccess && (dev[0] != n_cand || dev[1] != n_match))
@@ -109,7 +96,7 @@ static lmx_status collect_impl(lmx_ctx* c, int32_t n_frames, std::vector<std::ve
   if (reinterpret_cast<uint32_t*>(c->h_out)[6] != 0) {
     // a workgroup of a level-0 quantiser gave up waiting for rows of a streamed frame store (StreamWait): the batch ran on incomplete input
     set_error("the input frame never reached the device: a quantiser waited %u us for the host's stores (streamed upload of lmx_match); nothing was matched",
-              c->stream_timeout_ticks / 100u);
+              c->env.stream_timeout_ticks / 100u);
     return LMX_ERR_HIP;
   }
   if (n_cand > c->cap_total || n_match > c->cap_total) {
@@ -138,11 +125,11 @@ static lmx_status collect_impl(lmx_ctx* c, int32_t n_frames, std::vector<std::ve
   } else {
     for (int f = 0; f < n_frames; ++f) finalize_frame(per_frame[f], fin[f]);
   }
-  if (c->trace_match) {
+  if (c->env.match_trace) {
     c->tm_acc[lmx_ctx::TM_WAIT] += std::chrono::duration<double>(t1 - t0).count();
     c->tm_acc[lmx_ctx::TM_FINALIZE] += std::chrono::duration<double>(clk::now() - t1).count();
   }
-  if (c->trace_collect) {
+  if (c->env.collect_trace) {
     auto us = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
     size_t n_final = 0;
     for (int f = 0; f < n_frames; ++f) n_final += fin[f].size();

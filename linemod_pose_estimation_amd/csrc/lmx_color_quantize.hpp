@@ -38,10 +38,6 @@
 #define CQ_FN __device__ __forceinline__
 #endif
 
-#ifndef LMX_CQ_SKIP
-#define LMX_CQ_SKIP 0   // timing experiments only (scripts/build_variants.py color): bit k compiles one stage's work out -- A 1, P 2, Bh 4, Bv 8, D 16, E 32; results are wrong
-#endif
-
 namespace lmx {
 namespace cq {
 
@@ -173,7 +169,6 @@ CQ_FN void color_quantize_tile(int tile_x, int tile_y, const uint8_t* __restrict
 
   // ---- A: the clamped source tile (BORDER_REPLICATE of the blur), de-interleaved into three byte planes -------------------------------
   run([&](int tid) {
-    if (LMX_CQ_SKIP & 1) return;
     if constexpr (NC == 1) {
       // gray: the plane is the source row itself.  Interior columns: one dword per task, loaded as it lies (the segment starts at byte
       // x0 - 5: not dword aligned, which the unaligned-access mode serves with one load, like the three dwords of the BGR path); all of a
@@ -250,7 +245,7 @@ CQ_FN void color_quantize_tile(int tile_x, int tile_y, const uint8_t* __restrict
   // an even length -- and the clamped halo of s_in is never read.  Ph: horizontal pass on bytes, two outputs from three dwords; the five
   // bytes of output 2j start at byte 3 of dword j, those of output 2j + 1 at byte 1 of dword j + 1, so the weights sit in shifted byte lanes
   // instead of the data being funnel-shifted.  Results (<= 4080) are stored as row pairs for the vertical dot2.
-  if (pyr_dst != nullptr && !(LMX_CQ_SKIP & 2)) {
+  if (pyr_dst != nullptr) {
     const int Hd = H >> 1, Wd = W >> 1, X0 = x0 >> 1, Y0 = y0 >> 1;
     const bool edge_x = X0 == 0 || X0 + 32 >= Wd;        // block-uniform: the tile holds output column 0 or Wd - 1
     const bool w_even = (W & 1) == 0, h_even = (H & 1) == 0;
@@ -314,7 +309,6 @@ CQ_FN void color_quantize_tile(int tile_x, int tile_y, const uint8_t* __restrict
   // smoothed columns; a thread takes two rows (a row pair) x four columns: six dwords, twenty dot4 (window offset o inside the first dword ->
   // the weight vector shifted by o bytes, a third dword for o >= 2), results (<= 65 280) packed per column as (row 2p, row 2p + 1).
   run([&](int tid) {
-    if (LMX_CQ_SKIP & 4) return;
     int R = tid / 17, xq = tid - R * 17;                    // R = c * HP + p: source rows 2R, 2R + 1 of the flat [NC * IH] plane stack
     for (int i = tid; i < NC * HP * 17; i += 256) {
       const uint32_t* rowA = s_in32 + (2 * R) * (IS / 4) + xq;
@@ -336,7 +330,6 @@ CQ_FN void color_quantize_tile(int tile_x, int tile_y, const uint8_t* __restrict
   // ---- Bv: vertical pass on the row pairs, (sum + 2^15) >> 16.  Smoothed rows 2a and 2a + 1 of four columns from four pairs each:
   // row 2a = rows 2a .. 2a+6 = pairs a .. a+3 with weights (k0 k1)(k2 k3)(k4 k5)(k6 .), row 2a + 1 = the same pairs with (. k0)(k1 k2)(k3 k4)(k5 k6).
   run([&](int tid) {
-    if (LMX_CQ_SKIP & 8) return;
     int Rv = tid / 17, xq = tid - Rv * 17;                  // Rv = c * (SH / 2) + a
     for (int i = tid; i < NC * (SH / 2) * 17; i += 256) {
       const int c = NC == 1 ? 0 : (Rv >= SH / 2) + (Rv >= SH);
@@ -365,7 +358,6 @@ CQ_FN void color_quantize_tile(int tile_x, int tile_y, const uint8_t* __restrict
   //   s_oh = 1 << 4 * label   (one vote for the 3 x 3 histogram of stage E, packed 4-bit counters)     s_fl = 0xff if the flag holds, else 0
   // Image-border pixels carry label 0 (upstream zeroes the first / last row and column before the vote).
   run([&](int tid) {
-    if (LMX_CQ_SKIP & 16) return;
     const int thr_i = (int)fminf(floorf(thr_sq), 1.0e9f);   // integer m: (float)m > thr_sq  <=>  m > floor(thr_sq)
     const int w = uniform(tid >> 6), lxq = tid & 63;        // wave-uniform: row indices, clamps and tests go to the scalar unit
     constexpr int DROWS = QH / 4;                           // QH = 4 * DROWS + 2: waves 0 and 1 take one row more
@@ -416,7 +408,7 @@ CQ_FN void color_quantize_tile(int tile_x, int tile_y, const uint8_t* __restrict
               // (Tried: ONE unaligned dword read per row and channel instead of three byte reads, a + 2b + c and c - a as dot4s.  Unaligned LDS
               // reads compile to a single ds_read_b32 on gfx950 but run far slower than three ds_read_u8: the kernel went from 0.145 to 0.215 ms
               // per step in a same-box A/B, profiles/r04_color_quantize_ab.txt.  Byte reads stay.)
-              const int a = (LMX_CQ_SKIP & 128) ? row[cxc] : row[cxm], b = row[cxc], cc = (LMX_CQ_SKIP & 128) ? row[cxc] : row[cxp];   // (bit 128: timing experiment, one read instead of three)
+              const int a = row[cxm], b = row[cxc], cc = row[cxp];
               Rw[k % 3][c] = a + 2 * b + cc;
               Dw[k % 3][c] = cc - a;
             }
@@ -470,7 +462,6 @@ CQ_FN void color_quantize_tile(int tile_x, int tile_y, const uint8_t* __restrict
   // pixel: packed 4-bit counts (<= 9); "some bin >= 5" is (cnt + 0x33333333) & 0x88888888, at most one bin can.  No winner: ffs gives 0, the
   // shift count wraps to 31 and the stored low byte is 0 -- no compare.
   run([&](int tid) {
-    if (LMX_CQ_SKIP & 32) return;
     const uint32_t* const s_oh = s_r2;
     const int seg = tid >> 6, lx = tid & 63;
     const int gx = x0 + lx;

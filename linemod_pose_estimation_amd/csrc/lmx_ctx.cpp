@@ -5,24 +5,12 @@
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
-#include <condition_variable>
-#include <mutex>
-#include <shared_mutex>
-#include <thread>
-#include <cctype>
-#include <cmath>
-#include <cstdlib>
-#include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
-#include <functional>
-#include <map>
-#include <memory>
 #include <string>
+#include <thread>
 #include <vector>
-
-#include <sys/stat.h>
 
 #include "lmx_ctx.hpp"
 
@@ -82,8 +70,7 @@ static lmx_status build_geometry(lmx_ctx* c) {
     g.ls_zero_off = (uint32_t)T * T * g.cells;
     g.ls_stride = round_up(g.ls_zero_off + pad, 256);
     g.ls_bands = 0; g.ls_band_stride = 0;
-    const bool flat_only = getenv("LMX_LS_FLAT") != nullptr;    // A/B switch (scripts/ls_ab.sh, tests)
-    if (l < c->L - 1 && g.Wc % 16 == 0 && g.Wc >= 32 && !flat_only) {
+    if (l < c->L - 1 && g.Wc % 16 == 0 && g.Wc >= 32 && !c->env.ls_flat) {
       const uint32_t rows = (uint32_t)T * T * g.Hc;
       if (rows < (1u << 17) && g.Wc < 4096 && level_features_pack(c->bank, l, c->L, c->M, T, g.Hc)) {
         g.ls_bands = (uint32_t)g.Wc / 16;
@@ -328,7 +315,7 @@ lmx_status sync_lanes(lmx_ctx* c) {
 }
 
 int upload_threads(const lmx_ctx* c) {
-  if (c->env_upload_threads >= 1) return c->env_upload_threads;
+  if (c->env.upload_threads >= 1) return c->env.upload_threads;
   const unsigned hw = std::thread::hardware_concurrency();
   return (int)std::max(1u, std::min(8u, hw ? hw / 2 : 1u));
 }
@@ -360,7 +347,7 @@ void lmx_ctx::store_modality_streamed(lmx_ctx::FrameSet& fs, int m, int n_frames
   // rows per progress update.  Every update costs two store fences (15 updates per modality at 32 rows: +5.5 us per 640x480 RGB-D frame, measured);
   // what streaming hides is the kernel's launch latency and everything but its last band, and the last band's tiles run in one round of
   // workgroups whatever its height
-  const int band = c->stream_band_rows;
+  const int band = c->env.stream_band_rows;
   const int per_frame = (H + band - 1) / band, n_bands = per_frame * n_frames;
   uint32_t* flag = fs.store_flag + 32 * m + (end < 0 ? 16 : 0);
   for (int k = 0;; ++k) {
@@ -384,6 +371,40 @@ void lmx_ctx::stream_reset_hi(lmx_ctx::FrameSet& fs, int m, int n_frames, uint32
   lmx::stream_store_flag(fs.store_flag + 32 * m + 16, (seq << 20) | (uint32_t)(n_frames * desc.height));
   stream_claim[m].store(0, std::memory_order_relaxed);
 }
+
+namespace lmx {
+
+// The one place where a context reads its environment (CtxEnv in lmx_ctx.hpp says what each switch does).
+CtxEnv read_ctx_env() {
+  CtxEnv v;
+  v.ls_flat = std::getenv("LMX_LS_FLAT") != nullptr;
+  v.no_store_upload = std::getenv("LMX_NO_STORE_UPLOAD") != nullptr;
+  v.no_stream_store = std::getenv("LMX_NO_STREAM_STORE") != nullptr;
+  if (const char* e = std::getenv("LMX_STREAM_TIMEOUT_US")) v.stream_timeout_ticks = (uint32_t)std::max(100L, std::min(std::atol(e), 20000000L)) * 100u;
+  v.test_drop_stream = std::getenv("LMX_TEST_DROP_STREAM_STORE") != nullptr;
+  if (const char* e = std::getenv("LMX_STREAM_BAND_ROWS")) v.stream_band_rows = (int)std::max(8L, std::min(std::atol(e), 4096L));
+  v.match_trace = std::getenv("LMX_MATCH_TRACE") != nullptr;
+  v.collect_trace = std::getenv("LMX_COLLECT_TRACE") != nullptr;
+  if (const char* pm = std::getenv("LMX_PINNED_MODE")) v.pinned_mode = std::strcmp(pm, "dma") == 0 ? 1 : (std::strcmp(pm, "stage") == 0 ? 2 : 0);
+  v.no_small_chain = std::getenv("LMX_NO_SMALL_CHAIN") != nullptr;
+  if (const char* e = std::getenv("LMX_CAND_STRIPES")) {
+    const int n = std::atoi(e);
+    if (n >= 1 && n <= kCandStripes && (n & (n - 1)) == 0) v.cand_stripes = n;
+  }
+  v.debug_collect = std::getenv("LMX_DEBUG_COLLECT") != nullptr;
+  v.no_header_poll = std::getenv("LMX_NO_HEADER_POLL") != nullptr;
+  v.no_launch_thread = std::getenv("LMX_NO_LAUNCH_THREAD") != nullptr;
+  v.one_store_thread = std::getenv("LMX_ONE_STORE_THREAD") != nullptr;
+  v.no_delegate_first = std::getenv("LMX_NO_DELEGATE_FIRST_LAUNCH") != nullptr;
+  if (const char* e = std::getenv("LMX_UPLOAD_THREADS")) v.upload_threads = std::max(0, std::min(std::atoi(e), 64));
+  if (const char* e = std::getenv("LMX_SCORE_KERNEL")) v.score_variant = std::strcmp(e, "generic") == 0 ? 0 : (std::strcmp(e, "u8") == 0 ? 1 : 2);
+  if (const char* e = std::getenv("LMX_SCORE_NO_PRUNE")) v.score_no_prune = *e && std::strcmp(e, "0") != 0;
+  if (const char* e = std::getenv("LMX_COLOR_TILE")) v.color_tile = std::atoi(e);
+  if (const char* e = std::getenv("LMX_GRAPH_DOT")) { v.graph_dot = true; v.graph_dot_dir = e; }
+  return v;
+}
+
+}  // namespace lmx
 
 static lmx_status ctx_create_impl(lmx_ctx* c) {
   int ndev = 0;
@@ -487,7 +508,7 @@ static lmx_status ctx_create_impl(lmx_ctx* c) {
   {
     // host-writable device buffers for the direct-store upload of small batches; graphs bake the frame pointers in, so not with them
     hipDeviceProp_t prop;
-    c->store_ok = std::getenv("LMX_NO_STORE_UPLOAD") == nullptr && !(c->desc.flags & LMX_CTX_HIPGRAPH) &&
+    c->store_ok = !c->env.no_store_upload && !(c->desc.flags & LMX_CTX_HIPGRAPH) &&
                   hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.isLargeBar;
     for (int set = 0; set < c->n_sets && c->store_ok; ++set)
       for (int m = 0; m < c->M && c->store_ok; ++m) {
@@ -501,7 +522,7 @@ static lmx_status ctx_create_impl(lmx_ctx* c) {
         }
       }
     // progress words of streamed stores: one 128-byte line per modality, host-visible like the frames
-    c->stream_ok = c->store_ok && std::getenv("LMX_NO_STREAM_STORE") == nullptr;
+    c->stream_ok = c->store_ok && !c->env.no_stream_store;
     for (int set = 0; set < c->n_sets && c->stream_ok; ++set) {
       void* p = nullptr;
       if (hipExtMallocWithFlags(&p, 128 * kMaxModalities, hipDeviceMallocFinegrained) != hipSuccess) { (void)hipGetLastError(); c->stream_ok = false; break; }
@@ -512,10 +533,6 @@ static lmx_status ctx_create_impl(lmx_ctx* c) {
         lmx::stream_store_flag(c->sets[set].store_flag + 32 * m + 16, 0u);   // first row of the part stored from the bottom (sequence 0: never a call's)
       }
     }
-    if (const char* e = std::getenv("LMX_STREAM_TIMEOUT_US")) c->stream_timeout_ticks = (uint32_t)std::max(100L, std::min(std::atol(e), 20000000L)) * 100u;
-    c->env_test_drop_stream = std::getenv("LMX_TEST_DROP_STREAM_STORE") != nullptr;
-    if (const char* e = std::getenv("LMX_STREAM_BAND_ROWS")) c->stream_band_rows = (int)std::max(8L, std::min(std::atol(e), 4096L));
-    c->trace_match = std::getenv("LMX_MATCH_TRACE") != nullptr;
   }
   select_set(c, 0);
   LMX_HIP(hipStreamSynchronize(c->stream));
@@ -527,7 +544,7 @@ extern "C" {
 // ---- context ----------------------------------------------------------------------------------------------
 void lmx_ctx_destroy(lmx_ctx* c) {
   if (!c) return;
-  if (c->trace_match && c->tm_n > 0) {
+  if (c->env.match_trace && c->tm_n > 0) {
     static const char* names[lmx_ctx::TM_COUNT] = {"upload (deferred)", "launch colour L0", "store colour", "launch depth L0 + colour L1", "store depth", "launch spread, score, refine",
                                                    "wait for the slot", "finalise"};
     std::fprintf(stderr, "lmx_match trace (%ld calls, streamed stores %s): host us per call:", c->tm_n, c->stream_ok ? "on" : "off");
@@ -590,25 +607,9 @@ lmx_status lmx_ctx_create(const lmx_bank* bank, const lmx_ctx_desc* desc, lmx_ct
   c->bank = bank; c->desc = *desc;
   if (c->desc.shard_world <= 1) { c->desc.shard_world = 1; c->desc.shard_rank = 0; }
   c->L = (int)bank->T.size(); c->M = (int)bank->mods.size(); c->F = desc->max_batch;
-  c->trace_collect = std::getenv("LMX_COLLECT_TRACE") != nullptr;
-  if (const char* pm = std::getenv("LMX_PINNED_MODE")) c->env_pinned_mode = std::strcmp(pm, "dma") == 0 ? 1 : (std::strcmp(pm, "stage") == 0 ? 2 : 0);
-  c->env_no_small_chain = std::getenv("LMX_NO_SMALL_CHAIN") != nullptr;
-  if (const char* e = std::getenv("LMX_CAND_STRIPES")) {
-    const int v = std::atoi(e);
-    if (v >= 1 && v <= lmx::kCandStripes && (v & (v - 1)) == 0) c->cand_stripes = v;
-  }
-  c->env_debug_collect = std::getenv("LMX_DEBUG_COLLECT") != nullptr;
-  c->env_no_header_poll = std::getenv("LMX_NO_HEADER_POLL") != nullptr;
-  c->env_no_launch_thread = std::getenv("LMX_NO_LAUNCH_THREAD") != nullptr;
-  c->env_one_store_thread = std::getenv("LMX_ONE_STORE_THREAD") != nullptr;
-  c->env_no_delegate_first = std::getenv("LMX_NO_DELEGATE_FIRST_LAUNCH") != nullptr;
-  if (const char* e = std::getenv("LMX_UPLOAD_THREADS")) c->env_upload_threads = std::max(0, std::min(std::atoi(e), 64));
-  {
-    const char* e = std::getenv("LMX_SCORE_KERNEL");
-    c->dbank.score_variant = (std::getenv("LMX_SCORE_GENERIC") != nullptr || (e && std::strcmp(e, "generic") == 0)) ? 0 : ((e && std::strcmp(e, "u8") == 0) ? 1 : 2);
-    const char* np = std::getenv("LMX_SCORE_NO_PRUNE");
-    c->dbank.score_no_prune = (np && *np && std::strcmp(np, "0") != 0) ? 1 : 0;
-  }
+  c->env = read_ctx_env();
+  c->dbank.score_variant = c->env.score_variant;
+  c->dbank.score_no_prune = c->env.score_no_prune ? 1 : 0;
   lmx_status st = ctx_create_impl(c);
   if (st != LMX_OK) { const std::string keep = lmx_last_error(); lmx_ctx_destroy(c); set_error("%s", keep.c_str()); return st; }
   *out = c;
@@ -694,7 +695,7 @@ lmx_status lmx_ctx_upload(lmx_ctx* c, int32_t n_frames, const lmx_image* sources
     // transfer is a kernel pulling over PCIe).  Otherwise pinned sources are staged like pageable ones: measured, the staging copy
     // with non-temporal stores + one DMA per modality moves 54.5 GB/s end to end, the pull kernel 44 GB/s (it competes with the
     // compute kernels for CUs) and per-image DMA calls 32 GB/s (profiles/r02_host_frame_transfer_modes.txt).
-    const int pinned_mode = c->env_pinned_mode < 0 ? (async_input ? 0 : 2) : c->env_pinned_mode;
+    const int pinned_mode = c->env.pinned_mode < 0 ? (async_input ? 0 : 2) : c->env.pinned_mode;
     bool all_pinned = pinned_mode != 2;
     for (int f = 0; f < n_frames && all_pinned; ++f) {
       const lmx_image& im = sources[(size_t)f * c->M + m];
@@ -738,7 +739,7 @@ lmx_status lmx_ctx_upload(lmx_ctx* c, int32_t n_frames, const lmx_image* sources
     } else {
       // caller-owned pinned images: one kernel pulls all frames of the modality over PCIe (per-image DMA calls were measured at
       // 32 GB/s against 57 GB/s for this form)
-      if (c->env_pinned_mode == 1) {
+      if (c->env.pinned_mode == 1) {
         for (int f = 0; f < n_frames; ++f) {
           const lmx_image& im = sources[(size_t)f * c->M + m];
           if (im.row_stride_bytes == row_bytes)

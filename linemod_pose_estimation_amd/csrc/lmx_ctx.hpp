@@ -10,10 +10,12 @@
 //   lmx_debug.cpp    introspection, per-kernel timing, test hooks
 #pragma once
 
+#include <algorithm>
 #include <atomic>
 #include <memory>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "lmx_internal.hpp"
@@ -36,6 +38,38 @@ struct ModalityBuffers {
 
 struct ProfEvent { int kernel; hipEvent_t start, stop; };
 
+// The LMX_* environment switches of a context.  read_ctx_env() fills this ONCE, when lmx_ctx_create starts:
+// a per-upload or per-launch getenv is a libc lock and a string scan on the hot path, and a context never changes its mind half way.
+// A switch without a value here is on when the variable is set, whatever it holds.
+struct CtxEnv {
+  bool ls_flat = false;            // LMX_LS_FLAT: flat linearised spread images at every level, no banded layout (A/B switch: scripts/ls_ab.sh, tests)
+  bool no_store_upload = false;    // LMX_NO_STORE_UPLOAD: small batches go through staging + DMA like large ones
+  // lmx_match with a fresh host frame: the level-0 quantisers are launched first and wait, tile by tile, for the rows the calling thread is still
+  // storing (StreamWait in lmx_internal.hpp).  LMX_NO_STREAM_STORE restores "store, then launch"; LMX_STREAM_TIMEOUT_US (100 .. 20 000 000) bounds
+  // a workgroup's wait (default one second: a missing store is an error reported by collect, never a hang); LMX_TEST_DROP_STREAM_STORE is the test
+  // hook that leaves the depth rows out
+  bool no_stream_store = false;
+  uint32_t stream_timeout_ticks = 100000000u;
+  bool test_drop_stream = false;
+  int stream_band_rows = 96;       // LMX_STREAM_BAND_ROWS (8 .. 4096): rows per progress update; 48 and 96 measured best, profiles/r04_single_frame_latency.txt
+  bool match_trace = false;        // LMX_MATCH_TRACE: host-side phases of the one-frame call, averaged, printed when the context is destroyed
+  // LMX_COLLECT_TRACE: collect() prints its host-side split to stderr -- wait for the slot, fetch of the records beyond the first slice,
+  // grouping by frame, restore insertion order + std::sort + std::unique
+  bool collect_trace = false;
+  int pinned_mode = -1;            // LMX_PINNED_MODE = dma | stage | anything else: 1 per-image DMA, 2 stage, 0 pull kernel; -1 (unset) = by flags
+  bool no_small_chain = false;     // LMX_NO_SMALL_CHAIN: one or two frames per call take the plain chain (A/B switch)
+  int cand_stripes = 0;            // LMX_CAND_STRIPES = 1, 2, 4, ... 64 fixes the stripes of the candidate list in use; 0 = by batch size (lmx_ctx::stripes_for)
+  bool debug_collect = false;      // LMX_DEBUG_COLLECT
+  bool no_header_poll = false, no_launch_thread = false, one_store_thread = false, no_delegate_first = false;   // LMX_NO_HEADER_POLL, LMX_NO_LAUNCH_THREAD, LMX_ONE_STORE_THREAD, LMX_NO_DELEGATE_FIRST_LAUNCH: A/B switches
+  int upload_threads = 0;          // LMX_UPLOAD_THREADS (0 .. 64); 0 = by the number of cores (upload_threads())
+  int score_variant = 2;           // LMX_SCORE_KERNEL = generic | u8 | sb (anything else): 0 | 1 | 2, see score_kernel_variant
+  bool score_no_prune = false;     // LMX_SCORE_NO_PRUNE set, not empty and not "0": the scoring kernels do similarity()'s full work
+  int color_tile = 0;              // LMX_COLOR_TILE = 16 | 32 pins the colour quantiser's tile height (A/B switch); 0 = by batch size (launch_color_quantize)
+  bool graph_dot = false;          // LMX_GRAPH_DOT = <directory>: one .dot file per captured hipGraph chain (diagnostics)
+  std::string graph_dot_dir;
+};
+CtxEnv read_ctx_env();   // lmx_ctx.cpp
+
 }  // namespace lmx
 
 using namespace lmx;   // internal header: every includer is a translation unit of the library's host side
@@ -52,10 +86,7 @@ struct lmx_ctx {
   // outstanding, so each stream always has the next batch queued behind the running one and the other lanes' kernels fill the
   // tail of every kernel (the last, partially filled wave of workgroups).  kp.fb / mb[].bgr[l>=1] / d_cands always hold the view of the lane
   // of the most recent enqueue.
-#ifndef LMX_LANES
-#define LMX_LANES 3
-#endif
-  static constexpr int kLanes = LMX_LANES;  // measured at 64 frames per batch: 1 lane 118 k, 2: 134.7 k, 3: 138.9 k, 4: 137.2 k frames/s (round 2); round 4's kernels: 2: 154.2 k, 3: 154.3 k, 4: 152.9 k, 5: 143.5 k
+  static constexpr int kLanes = 3;  // measured at 64 frames per batch: 1 lane 118 k, 2: 134.7 k, 3: 138.9 k, 4: 137.2 k frames/s (round 2); round 4's kernels: 2: 154.2 k, 3: 154.3 k, 4: 152.9 k, 5: 143.5 k
   int n_lanes = 1;
   hipStream_t lane_stream[kLanes] = {};
   // Host-frame boundary (the reference hands match() host images every call): uploads rotate over `n_sets` frame sets, each
@@ -94,24 +125,18 @@ struct lmx_ctx {
   uint8_t* h_mask_stage = nullptr;          // pinned [F][H][W], one modality at a time
   hipEvent_t mask_h2d = nullptr;
   static constexpr int kStoreFrames = 2;
+  lmx::CtxEnv env;                          // the context's LMX_* environment switches
   bool store_ok = false;                    // large-BAR device, buffers allocated, not switched off (LMX_NO_STORE_UPLOAD)
-  // lmx_match with a fresh host frame: the level-0 quantisers are launched first and wait, tile by tile, for the rows the calling thread is still
-  // storing (StreamWait in lmx_internal.hpp).  LMX_NO_STREAM_STORE=1 restores "store, then launch"; LMX_STREAM_TIMEOUT_US bounds a workgroup's wait
-  // (default one second: a missing store is an error reported by collect, never a hang); LMX_TEST_DROP_STREAM_STORE=1 is the test hook that leaves
-  // the depth rows out.  All read once, when the context is created.
-  // LMX_MATCH_TRACE=1 (read once): host-side phases of the one-frame call, averaged, printed when the context is destroyed
-  bool trace_match = false;
   enum { TM_UPLOAD, TM_LAUNCH_COLOR, TM_STORE_COLOR, TM_LAUNCH_DEPTH, TM_STORE_DEPTH, TM_LAUNCH_REST, TM_WAIT, TM_FINALIZE, TM_COUNT };
   double tm_acc[TM_COUNT] = {};
   long tm_n = 0;
-  bool stream_ok = false, env_test_drop_stream = false;
-  uint32_t stream_seq = 0, stream_timeout_ticks = 100000000u;
+  bool stream_ok = false;                   // store_ok, progress words allocated, not switched off (LMX_NO_STREAM_STORE): see CtxEnv
+  uint32_t stream_seq = 0;
   // `end` 0: the calling thread stores every band, top to bottom.  +1 / -1: two threads share the modality, this one claims bands from the top /
   // from the bottom (stream_claim[m], reset by the caller before the second thread is started) until none is left; see StreamWait::flag_hi
   void store_modality_streamed(lmx_ctx::FrameSet& fs, int m, int n_frames, const lmx_image* sources, uint32_t seq, int end = 0);
   void stream_reset_hi(lmx_ctx::FrameSet& fs, int m, int n_frames, uint32_t seq);   // "nothing stored from the bottom yet" for this call
   std::atomic<int> stream_claim[lmx::kMaxModalities];
-  int stream_band_rows = 96;        // LMX_STREAM_BAND_ROWS (rows per progress update; 48 and 96 measured best, profiles/r04_single_frame_latency.txt)
   FrameSet sets[kSets];
   int n_sets = 2;
   int cur_set = 0;                  // the set the next enqueue reads (= the most recent upload)
@@ -198,19 +223,9 @@ struct lmx_ctx {
   double k_ms[K_COUNT] = {0};
   int64_t k_launches[K_COUNT] = {0};
   float last_threshold = 0.f;
-  // LMX_COLLECT_TRACE=1 (read once, at context creation): collect() prints its host-side split to stderr -- wait for the slot, fetch of
-  // the records beyond the first slice, grouping by frame, restore insertion order + std::sort + std::unique
-  bool trace_collect = false;
-  // the rest of the LMX_* environment a context consults, read ONCE when it is created (a per-upload or per-launch getenv is a libc
-  // lock and a string scan on the hot path): LMX_PINNED_MODE (0 pull kernel, 1 per-image DMA, 2 stage; -1 = by flags),
-  // LMX_NO_SMALL_CHAIN, LMX_DEBUG_COLLECT, LMX_UPLOAD_THREADS
-  int env_pinned_mode = -1;
-  bool env_no_small_chain = false, env_debug_collect = false, env_no_header_poll = false, env_no_launch_thread = false, env_one_store_thread = false, env_no_delegate_first = false;   // LMX_NO_HEADER_POLL, LMX_NO_LAUNCH_THREAD: A/B switches
-  int cand_stripes = 0;   // stripes of the candidate list in use; 0 = by batch size (stripes_for), LMX_CAND_STRIPES = 1, 2, 4, ... 64 fixes it (A/B switch, read once)
-  // One or two frames per call: few candidates, and every workgroup of k_refine starts by reading all stripe counters -- 64 lines cost the
+  // Stripes of the candidate list in use.  One or two frames per call: few candidates, and every workgroup of k_refine starts by reading all stripe counters -- 64 lines cost the
   // call 2 us, 8 cost nothing measurable (profiles/r03_single_frame_stripes.txt); batches: 64, where the appends would otherwise queue
-  int stripes_for(int n_frames) const { return cand_stripes ? cand_stripes : (n_frames <= kStoreFrames ? 8 : lmx::kCandStripes); }
-  int env_upload_threads = 0;
+  int stripes_for(int n_frames) const { return env.cand_stripes ? env.cand_stripes : (n_frames <= kStoreFrames ? 8 : lmx::kCandStripes); }
 
   uint32_t* d_cand_count() { return reinterpret_cast<uint32_t*>(d_out); }
   uint32_t* d_match_count() { return reinterpret_cast<uint32_t*>(d_out + 4); }

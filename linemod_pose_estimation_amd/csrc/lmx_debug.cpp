@@ -2,25 +2,8 @@
 // figure of SURVEY.md 8(d), and the test hooks of the std::sort restatement (csrc/lmx_sort_emul.hpp, lmx_sort_block.hpp).
 
 #include <algorithm>
-#include <atomic>
-#include <chrono>
-#include <condition_variable>
-#include <mutex>
-#include <shared_mutex>
-#include <thread>
-#include <cctype>
-#include <cmath>
-#include <cstdlib>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
-#include <functional>
-#include <map>
-#include <memory>
-#include <string>
 #include <vector>
-
-#include <sys/stat.h>
 
 #include "lmx_ctx.hpp"
 #include "lmx_sort_emul.hpp"

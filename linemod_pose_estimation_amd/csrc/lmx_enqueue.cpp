@@ -3,25 +3,14 @@
 // lmx_match / lmx_match_batch / lmx_match_masked (the drop-in calls).
 
 #include <algorithm>
-#include <atomic>
 #include <chrono>
-#include <condition_variable>
-#include <mutex>
-#include <shared_mutex>
-#include <thread>
-#include <cctype>
-#include <cmath>
-#include <cstdlib>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <functional>
-#include <map>
-#include <memory>
+#include <mutex>
+#include <shared_mutex>
 #include <string>
 #include <vector>
-
-#include <sys/stat.h>
 
 #include "lmx_ctx.hpp"
 
@@ -40,7 +29,7 @@ static lmx_status issue_pre(lmx_ctx* c, int32_t n_frames, hipStream_t s) {
         // the level-l kernel also writes the pyrDown'ed source of level l+1 (upstream: ColorGradientPyramid::pyrDown)
         ScopedKernel k(c, K_COLOR_QUANTIZE);
         launch_color_quantize(s, c->mb[m].bgr[l], c->kp.fb.quant[l][m], l + 1 < c->L ? c->mb[m].bgr[l + 1] : nullptr, g.H, g.W, n_frames,
-                              md.weak_threshold, nullptr, first ? reinterpret_cast<uint32_t*>(c->d_out) : nullptr, nullptr, c->color_ch);
+                              md.weak_threshold, nullptr, first ? reinterpret_cast<uint32_t*>(c->d_out) : nullptr, nullptr, c->color_ch, c->env.color_tile);
         first = false;
       } else {
         if (l == 0) {
@@ -131,7 +120,7 @@ static bool small_chain_ok(const lmx_ctx* c, int n_frames) {
   if (n_frames > lmx_ctx::kStoreFrames || c->L != 2 || c->M < 1 || c->M > 2) return false;
   if (c->bank->mods[0].type != LMX_MOD_COLOR_GRADIENT) return false;
   if (c->M == 2 && c->bank->mods[1].type != LMX_MOD_DEPTH_NORMAL) return false;
-  return !c->env_no_small_chain;   // A/B switch (LMX_NO_SMALL_CHAIN, read when the context was created)
+  return !c->env.no_small_chain;   // A/B switch (LMX_NO_SMALL_CHAIN, read when the context was created)
 }
 
 static lmx_status issue_small(lmx_ctx* c, int slot, int32_t n_frames, float threshold, hipStream_t s, lmx_ctx::FrameSet& fs, const lmx_image* sources) {
@@ -144,18 +133,18 @@ static lmx_status issue_small(lmx_ctx* c, int slot, int32_t n_frames, float thre
   using clk = std::chrono::steady_clock;
   clk::time_point tp = clk::now();
   auto lap = [&](int phase) {
-    if (!c->trace_match) return;
+    if (!c->env.match_trace) return;
     const clk::time_point now = clk::now();
     c->tm_acc[phase] += std::chrono::duration<double>(now - tp).count();
     tp = now;
   };
   const bool stream = sources != nullptr && c->stream_ok && (size_t)n_frames * c->desc.height < (1u << 20);
   StreamWait wc, wd;
-  const bool use_helper = stream && !c->env_no_launch_thread && c->profiling == 0;
-  const bool two_ended = use_helper && !c->env_one_store_thread;   // both threads store, each modality from both ends
+  const bool use_helper = stream && !c->env.no_launch_thread && c->profiling == 0;
+  const bool two_ended = use_helper && !c->env.one_store_thread;   // both threads store, each modality from both ends
   if (stream) {
     c->stream_seq = (c->stream_seq % 4095u) + 1u;   // 1 .. 4095: never the value the flag words were initialised with
-    wc.flag = fs.store_flag; wc.seq = c->stream_seq; wc.timeout_ticks = c->stream_timeout_ticks; wc.fail = reinterpret_cast<uint32_t*>(c->d_out) + 6;
+    wc.flag = fs.store_flag; wc.seq = c->stream_seq; wc.timeout_ticks = c->env.stream_timeout_ticks; wc.fail = reinterpret_cast<uint32_t*>(c->d_out) + 6;
     wd = wc;
     wd.flag = fs.store_flag + 32;
     if (two_ended) {
@@ -174,7 +163,7 @@ static lmx_status issue_small(lmx_ctx* c, int slot, int32_t n_frames, float thre
                                c->mb[0].bgr[1], c->kp.fb.quant[1][0], nullptr, g1.H, g1.W, cg.weak_threshold, n_frames, stream ? &wd : nullptr, c->color_ch);
     } else {
       ScopedKernel k(c, K_COLOR_QUANTIZE);
-      launch_color_quantize(s, c->mb[0].bgr[1], c->kp.fb.quant[1][0], nullptr, g1.H, g1.W, n_frames, cg.weak_threshold, nullptr, nullptr, nullptr, c->color_ch);
+      launch_color_quantize(s, c->mb[0].bgr[1], c->kp.fb.quant[1][0], nullptr, g1.H, g1.W, n_frames, cg.weak_threshold, nullptr, nullptr, nullptr, c->color_ch, c->env.color_tile);
     }
   };
   // spread of both levels, score, refine (+ read-back)
@@ -215,12 +204,12 @@ static lmx_status issue_small(lmx_ctx* c, int slot, int32_t n_frames, float thre
   auto launch_first = [&]() {
     ScopedKernel k(c, K_COLOR_QUANTIZE);
     launch_color_quantize(s, c->mb[0].bgr[0], c->kp.fb.quant[0][0], c->mb[0].bgr[1], g0.H, g0.W, n_frames, cg.weak_threshold, nullptr, reinterpret_cast<uint32_t*>(c->d_out),
-                          stream ? &wc : nullptr, c->color_ch);
+                          stream ? &wc : nullptr, c->color_ch, c->env.color_tile);
   };
   // With a helper thread the FIRST launch is its job too and this thread starts storing at once: a launch costs ~7 us (~120 us when the call finds
   // the device idle after a pause), the first tiles need the first band of rows anyway.  In a loop: 84.9 against 88.4 us per call; after a
   // one-second pause the call stays at 190-270 us either way (profiles/r04_single_frame_latency.txt, r04M).  LMX_NO_DELEGATE_FIRST_LAUNCH=1: as before.
-  const bool delegate_first = use_helper && !c->env_no_delegate_first;
+  const bool delegate_first = use_helper && !c->env.no_delegate_first;
   if (!delegate_first) launch_first();
   lap(lmx_ctx::TM_LAUNCH_COLOR);
   if (use_helper) {
@@ -235,7 +224,7 @@ static lmx_status issue_small(lmx_ctx* c, int slot, int32_t n_frames, float thre
     // ~36 GB/s out of the caller's memory, the link takes ~45).  Both threads take the COLOUR frame first -- this thread from the top, the helper,
     // once its launches are out, from the bottom -- and then the depth frame the same way: the colour chain is one kernel longer (level 1 is
     // quantised from level 0's pyrDown), so it should not be the one that ends with the last byte of the call.
-    const bool store_depth = c->M == 2 && !c->env_test_drop_stream;
+    const bool store_depth = c->M == 2 && !c->env.test_drop_stream;
     const int end = two_ended ? 1 : 0;
     const std::function<void()> job = [&]() {
       if (hipSetDevice(c->device) != hipSuccess) { rest_st = LMX_ERR_HIP; rest_msg = "hipSetDevice failed on the launch thread"; return; }
@@ -260,7 +249,7 @@ static lmx_status issue_small(lmx_ctx* c, int slot, int32_t n_frames, float thre
   if (c->M == 2 && sources && !stream) { store_modality(c, fs, 1, n_frames, sources); lap(lmx_ctx::TM_STORE_DEPTH); }   // lands while the colour kernel runs
   launch_second();
   lap(lmx_ctx::TM_LAUNCH_DEPTH);
-  if (c->M == 2 && stream && !c->env_test_drop_stream) { c->store_modality_streamed(fs, 1, n_frames, sources, wd.seq); lap(lmx_ctx::TM_STORE_DEPTH); }
+  if (c->M == 2 && stream && !c->env.test_drop_stream) { c->store_modality_streamed(fs, 1, n_frames, sources, wd.seq); lap(lmx_ctx::TM_STORE_DEPTH); }
   const lmx_status pst = launch_rest();
   lap(lmx_ctx::TM_LAUNCH_REST);
   return pst;
@@ -273,17 +262,17 @@ static lmx_status issue_small(lmx_ctx* c, int slot, int32_t n_frames, float thre
 static std::shared_mutex g_capture_mutex;
 
 // Stream capture of one stage (or of both, back to back) into an executable graph.
-static lmx_status capture_graph(hipStream_t s, hipGraphExec_t* exec, const std::function<lmx_status()>& issue) {
+static lmx_status capture_graph(const lmx_ctx* c, hipStream_t s, hipGraphExec_t* exec, const std::function<lmx_status()>& issue) {
   hipGraph_t graph = nullptr;
   LMX_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
   lmx_status st = issue();
   hipError_t e = hipStreamEndCapture(s, &graph);
   if (st != LMX_OK) { if (graph) (void)hipGraphDestroy(graph); return st; }
   if (e != hipSuccess) { set_error("hipStreamEndCapture failed: %s", hipGetErrorString(e)); return LMX_ERR_HIP; }
-  if (const char* dot = std::getenv("LMX_GRAPH_DOT")) {  // diagnostics: one .dot file per captured chain
+  if (c->env.graph_dot) {  // LMX_GRAPH_DOT, diagnostics: one .dot file per captured chain
     static int n_dot = 0;
     char path[512];
-    snprintf(path, sizeof(path), "%s/lmx_graph_%d.dot", dot, n_dot++);
+    snprintf(path, sizeof(path), "%s/lmx_graph_%d.dot", c->env.graph_dot_dir.c_str(), n_dot++);
     (void)hipGraphDebugDotPrint(graph, path, hipGraphDebugDotFlagsVerbose);
   }
   LMX_HIP(hipGraphInstantiate(exec, graph, nullptr, nullptr, 0));
@@ -300,7 +289,7 @@ static lmx_status ensure_graph(lmx_ctx* c, int slot, int set, int32_t n_frames, 
     if (ge.slot == slot && ge.set == set && ge.n_frames == n_frames && ge.threshold_bits == tbits) { *out = ge.exec; return LMX_OK; }
   std::unique_lock<std::shared_mutex> capture_lock(g_capture_mutex);
   hipGraphExec_t exec = nullptr;
-  lmx_status st = capture_graph(sa, &exec, [&]() {
+  lmx_status st = capture_graph(c, sa, &exec, [&]() {
     lmx_status r = issue_pre(c, n_frames, sa);
     return r != LMX_OK ? r : issue_post(c, slot, n_frames, threshold, sa);
   });
@@ -425,7 +414,7 @@ lmx_status lmx_match_batch(lmx_ctx* c, int32_t n_frames, const lmx_image* source
   c->deferred_frames = -1;   // "upload may leave the direct stores of a small batch to the enqueue below" (the sources outlive both calls)
   const std::chrono::steady_clock::time_point t_call = std::chrono::steady_clock::now();
   lmx_status st = lmx_ctx_upload(c, n_frames, sources, n_sources);
-  if (c->trace_match) { c->tm_acc[lmx_ctx::TM_UPLOAD] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_call).count(); c->tm_n += 1; }
+  if (c->env.match_trace) { c->tm_acc[lmx_ctx::TM_UPLOAD] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_call).count(); c->tm_n += 1; }
   if (c->deferred_frames == -1) c->deferred_frames = 0;
   if (st == LMX_OK) st = lmx_ctx_enqueue(c, n_frames, threshold, class_ids, n_class_ids);
   if (c->deferred_sources) {   // the enqueue failed before it consumed them: the set must still hold what upload promised

@@ -391,7 +391,8 @@ void launch_color_quantize(hipStream_t s, const uint8_t* bgr, uint8_t* quant, ui
                            int n_frames, float weak_threshold, float* mag_out = nullptr /* trainer: squared magnitude per pixel */,
                            uint32_t* clear16 = nullptr /* 16 dwords zeroed by the first workgroup: the output slot's header */,
                            const StreamWait* wait = nullptr /* small batches: the frame is still being stored by the host */,
-                           int n_ch = 3 /* colour planes of bgr and pyr_next: 3, or 1 for a gray context (LMX_CTX_GRAY) */);
+                           int n_ch = 3 /* colour planes of bgr and pyr_next: 3, or 1 for a gray context (LMX_CTX_GRAY) */,
+                           int forced_tile = 0 /* tile height 16 | 32 pinned by the context's LMX_COLOR_TILE; 0 = chosen by batch size */);
 lmx_status train_add_template(lmx_bank* bank, int device, const lmx_image* sources, int n_sources, const char* class_id,
                               const lmx_image* object_mask, int32_t* template_id, int32_t* bounding_box);
 void launch_depth_quantize(hipStream_t s, const uint16_t* depth, uint8_t* quant, uint8_t* quant_half, int H, int W, int n_frames, int distance_threshold,

@@ -24,30 +24,11 @@
 // divide/sqrt (depth_lut_index_lean spells the same two expansions out without their out-of-range steps).
 
 #include <algorithm>
-#include <cstdlib>
-#include <cstring>
 #include <type_traits>
 
 #include "lmx_internal.hpp"
 #include "lmx_color_quantize.hpp"
 
-// Wave priorities (s_setprio 0..3) of the memory-bound kernels against the issue-bound quantisers of the other lanes; experiment switches,
-// see DESIGN.md section 8 (round 4) for what was measured
-#ifndef LMX_PRIO_SCORE
-#define LMX_PRIO_SCORE 0
-#endif
-#ifndef LMX_PRIO_REFINE
-#define LMX_PRIO_REFINE 0
-#endif
-#ifndef LMX_SC_EXIT
-#define LMX_SC_EXIT 0
-#endif
-#ifndef LMX_PRIO_QUANT
-#define LMX_PRIO_QUANT 0
-#endif
-#ifndef LMX_PRIO_SPREAD
-#define LMX_PRIO_SPREAD 0
-#endif
 namespace lmx {
 
 namespace {
@@ -194,7 +175,6 @@ template <int TH, bool TRAIN, int NC = 3>
 __global__ __launch_bounds__(256) void k_color_quantize(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
                                                         uint8_t* __restrict__ pyr_dst, float* __restrict__ mag_dst, int H, int W, float thr_sq,
                                                         uint32_t* __restrict__ clear16, int n_frames_x, StreamWait wait) {
-  if (LMX_PRIO_QUANT) __builtin_amdgcn_s_setprio(LMX_PRIO_QUANT);
   color_quantize_body<TH, TRAIN, NC>(make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), src, dst, pyr_dst, mag_dst, H, W, thr_sq, clear16, n_frames_x, wait);
 }
 
@@ -205,9 +185,6 @@ __global__ __launch_bounds__(256) void k_color_quantize(const uint8_t* __restric
 // Index = (v3 * 20 + v2) * 20 + v1 like C lays the array out; v1, v2 = (int)(n * 10 + 10) and v3 = (int)(nz * 20 + 20) lie in
 // [0, 20] (|n| <= 1 up to rounding, nz <= 0), a flat index >= 8000 (upstream: out-of-bounds read) gives bin 0.
 // =========================================================================================================
-// Products of the LSQ: with IntT = int every operand is below 2^23 in magnitude and every product below 2^31 (bounds in the
-// comment of depth_bin_at), so the full-rate 24-bit multiplier gives the exact value; long long keeps the generic multiply.
-__device__ __forceinline__ int lsq_mul(int a, int b) { return __mul24(a, b); }
 __device__ __forceinline__ long long lsq_mul(long long a, long long b) { return a * b; }
 
 // Median bin of the pixel at p1 (which lies inside the r = 5 frame of the image; row stride W) before the median, 0 for far
@@ -224,19 +201,10 @@ __device__ __forceinline__ long long lsq_mul(long long a, long long b) { return 
 //    the delta sums,  det = 625 (a0 a3 - a1^2),  ddx = 125 (a3 B0 - a1 B1),  ddy = 125 (a0 B1 - a1 B0)  ->  nx = 143750 X, ny = 143750 Y,
 //    nz = -625 (D d): ten 24-bit multiplies instead of fourteen (three of them 32-bit).  |X|, |Y| <= 8 * 6 * 200 < 2^23, D d <= 36 * 65535 <
 //    2^23, and the results are the generic form's 1150 ddx, 1150 ddy, -det d (< 2^31, bounds above).
-//  * LMX_DQ_LEAN_NORM: sqrtf and 1.0f / s are LLVM's correctly rounded expansions with the steps that only serve operands outside this
+//  * the norm and its reciprocal: sqrtf and 1.0f / s are LLVM's correctly rounded expansions with the steps that only serve operands outside this
 //    kernel's range removed: the sum of squares is an integer-valued float in [1, 2^65) or 0 (returned before), s in [1, 2^33): no
 //    denormal pre-scaling of the square root's argument, v_div_scale returns its operands unscaled (VCC clear) and v_div_fixup passes the
 //    quotient through.  What is left is the same v_sqrt_f32 + two-sided ulp correction and the same v_rcp_f32 + three Newton steps.
-#ifndef LMX_DQ_LEAN
-#define LMX_DQ_LEAN 1
-#endif
-#ifndef LMX_DQ_LEAN_NORM
-#define LMX_DQ_LEAN_NORM 1
-#endif
-#ifndef LMX_DQ_PIPE
-#define LMX_DQ_PIPE 1
-#endif
 // 24-bit multiplies as instructions: __mul24 is a pattern the compiler may (and here does) turn back into the quarter-rate v_mul_lo_u32 or a
 // 64-bit v_mad_u64_u32 once it has proved the operands small
 __device__ __forceinline__ int mul24_vv(int a, int b) { int r; asm("v_mul_i32_i24 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
@@ -276,7 +244,6 @@ __device__ __forceinline__ int depth_lut_index_lean(const DepthTaps& tp, int dis
   float ny = (float)mul24_sv(143750, Y);
   float nz = (float)mul24_sv(-625, mul24_vv(D, d));
   const float ss = nx * nx + ny * ny + nz * nz;   // 0 (-> bin 0: sqrtf(ss) > 0 <=> ss > 0) or an integer-valued float >= 1
-#if LMX_DQ_LEAN_NORM
   float s = __builtin_amdgcn_sqrtf(ss);
   {
     const float sd = __int_as_float(__float_as_int(s) - 1), su = __int_as_float(__float_as_int(s) + 1);
@@ -292,10 +259,6 @@ __device__ __forceinline__ int depth_lut_index_lean(const DepthTaps& tp, int dis
     q = __builtin_fmaf(__builtin_fmaf(-s, q, 1.0f), rc, q);
     inv = __builtin_fmaf(__builtin_fmaf(-s, q, 1.0f), rc, q);
   }
-#else
-  const float s = sqrtf(ss);
-  const float inv = 1.0f / s;
-#endif
   nx *= inv; ny *= inv; nz *= inv;
   const int v1 = (int)(nx * 10 + 10);
   const int v2 = (int)(ny * 10 + 10);
@@ -314,7 +277,8 @@ __device__ __forceinline__ int depth_bin_at_lean(const uint16_t* __restrict__ p1
 template <typename IntT>
 __device__ __forceinline__ int depth_bin_at(const uint16_t* __restrict__ p1, int W, int distance_threshold, int difference_threshold,
                                             const uint8_t* __restrict__ lut_bins) {
-  if constexpr (LMX_DQ_LEAN && std::is_same<IntT, int>::value) return depth_bin_at_lean(p1, W, distance_threshold, difference_threshold, lut_bins);
+  // the int32 form is the lean one above; what follows runs for long long only
+  if constexpr (std::is_same<IntT, int>::value) return depth_bin_at_lean(p1, W, distance_threshold, difference_threshold, lut_bins);
   const int r = 5;
   // three row pointers, column offsets are immediates: 3 address computations for the 9 loads
   const uint16_t* p0 = p1 - (size_t)r * W;
@@ -407,7 +371,7 @@ __device__ __forceinline__ void depth_quantize_body(const uint3 bid, const uint1
     unsigned long long* q = &s_oh[ly][lx];
     constexpr int NI = (RH * RW + 255) / 256;             // items per thread; only the last one can fall outside the region
     static_assert((NI - 1) * 256 < RH * RW, "every thread's first NI - 1 items are inside");
-    if constexpr (LMX_DQ_PIPE && LMX_DQ_LEAN && std::is_same<IntT, int>::value) {
+    if constexpr (std::is_same<IntT, int>::value) {
       // Software pipeline: the nine loads of item i + 1 are issued before item i is computed, and item i's table look-up is consumed one
       // iteration later -- one memory round trip per item on the critical path instead of three (pixel, neighbours, table).  What a wave of
       // the one-frame call spends its time on (a tile then has its CU to itself: nothing else hides the latency), and cheaper in the
@@ -489,7 +453,6 @@ template <typename IntT>
 __global__ __launch_bounds__(256) void k_depth_quantize(const uint16_t* __restrict__ src, uint8_t* __restrict__ dst, uint8_t* __restrict__ dst_half,
                                                         int H, int W, int distance_threshold, int difference_threshold,
                                                         const uint8_t* __restrict__ lut_bins, uint32_t* __restrict__ clear16, int n_frames_x) {
-  if (LMX_PRIO_QUANT) __builtin_amdgcn_s_setprio(LMX_PRIO_QUANT);
   depth_quantize_body<IntT>(make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), src, dst, dst_half, H, W, distance_threshold, difference_threshold, lut_bins, clear16,
                             n_frames_x);
 }
@@ -799,7 +762,6 @@ __device__ __forceinline__ void spread_linearize_t_body(const uint3 bid, const S
 }
 template <int T>
 __global__ __launch_bounds__(256) void k_spread_linearize_t(SpreadBatch batch, LevelGeom g, int n_frames_x) {
-  if (LMX_PRIO_SPREAD) __builtin_amdgcn_s_setprio(LMX_PRIO_SPREAD);
   spread_linearize_t_body<T>(make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), batch, g, n_frames_x);
 }
 // Small batches: both pyramid levels of a two-level bank in ONE launch (see k_small_depth_color): workgroups [0, n0) spread level 0,
@@ -1309,8 +1271,6 @@ __device__ __forceinline__ void score_pass_sb(const ScoreParams& p, const uint8_
 
 template <bool PRUNE>
 __global__ __launch_bounds__(64 * SC_WAVES_PER_BLOCK) void k_score_coarse_sb(ScoreParams p) {
-  if (LMX_PRIO_SCORE) __builtin_amdgcn_s_setprio(LMX_PRIO_SCORE);
-  if (LMX_SC_EXIT == 1) return;   // latency experiments (scripts/build_variants.py scexit): where a one-frame launch spends its time
   const int lane = threadIdx.x & 63;
   int frame, tblock;  // XCD-aware frame placement, as in k_score_coarse
   if (p.xcd_frames) {
@@ -1332,13 +1292,8 @@ __global__ __launch_bounds__(64 * SC_WAVES_PER_BLOCK) void k_score_coarse_sb(Sco
   const int raw_threshold = (int)(2 * nf + (p.threshold / 100.f) * (2 * nf) + 0.5f);
   const uint8_t* lm_frame = p.lm[0] + (size_t)frame * p.mod_stride;
   lmx_cu32_const* row = (lmx_cu32_const*)(uintptr_t)(p.blk_off + (size_t)g * (SB_BLOCK * SB_MAX_BLOCKS));
-  const int n_blocks = LMX_SC_EXIT == 3 ? 1 : (int)((si.groups >> 16) & 0xffu);
-  if (LMX_SC_EXIT == 2) { const uint32_t r0 = row[0]; if ((uint32_t)positions + r0 == 0xfffffff1u) p.stripes[0] = r0; return; }   // template info, class filter and the first table dword loaded
+  const int n_blocks = (int)((si.groups >> 16) & 0xffu);
   int pbase = 0;
-  if (LMX_SC_EXIT == 3 || LMX_SC_EXIT == 4) {   // one pass of two chunks only (3: its first block only)
-    score_pass_sb<2, PRUNE>(p, lm_frame, row, n_blocks, g, frame, lane, pbase, positions, raw_threshold, nf);
-    return;
-  }
   for (; pbase + SC_CHUNK_POS < positions; pbase += 2 * SC_CHUNK_POS) score_pass_sb<2, PRUNE>(p, lm_frame, row, n_blocks, g, frame, lane, pbase, positions, raw_threshold, nf);
   if (pbase < positions) score_pass_sb<1, PRUNE>(p, lm_frame, row, n_blocks, g, frame, lane, pbase, positions, raw_threshold, nf);
 }
@@ -1348,10 +1303,7 @@ __global__ __launch_bounds__(64 * SC_WAVES_PER_BLOCK) void k_score_coarse_sb(Sco
 // similarityLocal is 256 cells = 4 per lane (lane -> row lane>>2, columns 4*(lane&3)..+3), again as packed u8 sums that meet in
 // LDS; argmax with upstream's first-maximum rule by a wave max-reduction over (score << 8 | 255 - cell).
 // =========================================================================================================
-#ifndef LMX_RF_UNROLL
-#define LMX_RF_UNROLL 8
-#endif
-constexpr int RF_UNROLL = LMX_RF_UNROLL;  // gathers in flight per wave and batch; a wave's share of a modality is 16 (4, 8 and 16 timed the same)
+constexpr int RF_UNROLL = 8;  // gathers in flight per wave and batch; a wave's share of a modality is 16 (4, 8 and 16 timed the same)
 
 // Response of orientation o to a spread byte v, without a table: with M_k[o] = the set of source bits whose response is >= k
 // (nested: M_4 in M_3 in M_2 in M_1, read off SIMILARITY_LUT, asymmetric high nibble included),
@@ -1403,7 +1355,6 @@ struct RefineParams {
 // not its total work.  Wave w takes features [16w, 16w+16) of every modality, the four partial patch sums meet in LDS, and
 // every wave then evaluates the same arg-max, which keeps the control flow uniform without a broadcast.
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_refine(RefineParams p) {
-  if (LMX_PRIO_REFINE) __builtin_amdgcn_s_setprio(LMX_PRIO_REFINE);
   __shared__ uint32_t s_part[2][4][2][64];  // [parity of the level step][wave][lo, hi][lane]
   __shared__ uint32_t s_mid[2][4][2][64];   // the same for the early-exit test between two modalities
   __shared__ uint4 s_masks[8];              // per orientation: M_1, M_2, M_3 replicated into every byte, and o
@@ -1835,40 +1786,33 @@ void launch_debug_depth_normal_bins(hipStream_t s, const uint16_t* patches, size
 }
 
 // ---- launchers --------------------------------------------------------------------------------------------
-// Extra (unused) dynamic LDS per workgroup of the issue-bound per-pixel kernels: caps how many of their workgroups a CU holds, which
-// leaves wave slots for the memory-bound scoring kernel of ANOTHER device lane to run beside them (device lanes).
-// LMX_LDS_PAD_COLOR / _DEPTH / _SPREAD (bytes) override the defaults for experiments.
-static size_t lds_pad(const char* env, size_t dflt) {
-  const char* e = std::getenv(env);
-  return e ? (size_t)std::strtoul(e, nullptr, 10) : dflt;
+// Run-time choice between template instantiations: f gets std::true_type or std::false_type, so that a launch whose template arguments
+// depend on several run-time conditions writes its argument list once.
+template <class F>
+static void with_bool(bool b, F&& f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
 }
 
+// forced_tile: 0 = choose, CQ_TH / CQ_TH_TALL pin the tile height (a context's LMX_COLOR_TILE)
 void launch_color_quantize(hipStream_t s, const uint8_t* bgr, uint8_t* quant, uint8_t* pyr_next, int H, int W, int n_frames, float weak_threshold,
-                           float* mag_out, uint32_t* clear16, const StreamWait* wait, int n_ch) {
+                           float* mag_out, uint32_t* clear16, const StreamWait* wait, int n_ch, int forced_tile) {
   const StreamWait sw = wait ? *wait : StreamWait();
   const bool xcd = n_frames >= 8;   // XCD-aware tile placement, see tile_of_block
   // batches take the tall tile (less halo per output); one or two frames per call keep 16 rows: twice the workgroups for a launch that
-  // does not fill the GPU anyway.  LMX_COLOR_TILE=16|32 pins it (A/B switch, read once).
-  static const int forced = []() { const char* e = std::getenv("LMX_COLOR_TILE"); return e ? std::atoi(e) : 0; }();
-  const bool tall = forced ? forced == CQ_TH_TALL : (xcd && H >= 2 * CQ_TH_TALL);
+  // does not fill the GPU anyway
+  const bool tall = forced_tile ? forced_tile == CQ_TH_TALL : (xcd && H >= 2 * CQ_TH_TALL);
   const int th = tall ? CQ_TH_TALL : CQ_TH;
   const int tx = (W + CQ_TW - 1) / CQ_TW, ty = (H + th - 1) / th;
   dim3 grid = xcd ? dim3((unsigned)(tx * ty * 8 * ((n_frames + 7) / 8))) : dim3(tx, ty, n_frames);
-  static const size_t pad = lds_pad("LMX_LDS_PAD_COLOR", 0);
   const float thr_sq = weak_threshold * weak_threshold;
   const int nfx = xcd ? n_frames : 0;
-  // the trainer's instantiation also writes the squared magnitudes (extractTemplate ranks candidates by them)
-  if (n_ch == 1) {   // gray context: the one-plane tile, same tile choice
-    if (tall && mag_out) hipLaunchKernelGGL((k_color_quantize<CQ_TH_TALL, true, 1>), grid, dim3(256), pad, s, bgr, quant, pyr_next, mag_out, H, W, thr_sq, clear16, nfx, sw);
-    else if (tall) hipLaunchKernelGGL((k_color_quantize<CQ_TH_TALL, false, 1>), grid, dim3(256), pad, s, bgr, quant, pyr_next, mag_out, H, W, thr_sq, clear16, nfx, sw);
-    else if (mag_out) hipLaunchKernelGGL((k_color_quantize<CQ_TH, true, 1>), grid, dim3(256), pad, s, bgr, quant, pyr_next, mag_out, H, W, thr_sq, clear16, nfx, sw);
-    else hipLaunchKernelGGL((k_color_quantize<CQ_TH, false, 1>), grid, dim3(256), pad, s, bgr, quant, pyr_next, mag_out, H, W, thr_sq, clear16, nfx, sw);
-    return;
-  }
-  if (tall && mag_out) hipLaunchKernelGGL((k_color_quantize<CQ_TH_TALL, true>), grid, dim3(256), pad, s, bgr, quant, pyr_next, mag_out, H, W, thr_sq, clear16, nfx, sw);
-  else if (tall) hipLaunchKernelGGL((k_color_quantize<CQ_TH_TALL, false>), grid, dim3(256), pad, s, bgr, quant, pyr_next, mag_out, H, W, thr_sq, clear16, nfx, sw);
-  else if (mag_out) hipLaunchKernelGGL((k_color_quantize<CQ_TH, true>), grid, dim3(256), pad, s, bgr, quant, pyr_next, mag_out, H, W, thr_sq, clear16, nfx, sw);
-  else hipLaunchKernelGGL((k_color_quantize<CQ_TH, false>), grid, dim3(256), pad, s, bgr, quant, pyr_next, mag_out, H, W, thr_sq, clear16, nfx, sw);
+  // gray context: the one-plane tile, same tile choice; the trainer's instantiation (mag_out) also writes the squared magnitudes
+  // (extractTemplate ranks candidates by them)
+  with_bool(n_ch == 1, [&](auto gray) { with_bool(tall, [&](auto tall_c) { with_bool(mag_out != nullptr, [&](auto train) {
+    constexpr int TH = decltype(tall_c)::value ? CQ_TH_TALL : CQ_TH, NC = decltype(gray)::value ? 1 : 3;
+    hipLaunchKernelGGL((k_color_quantize<TH, decltype(train)::value, NC>), grid, dim3(256), 0, s, bgr, quant, pyr_next, mag_out, H, W, thr_sq, clear16, nfx, sw);
+  }); }); });
 }
 
 // quant_half (or null): also writes the next pyramid level's label image, upstream's nearest-neighbour pyrDown dst(y, x) = src(2y, 2x)
@@ -1878,11 +1822,10 @@ void launch_depth_quantize(hipStream_t s, const uint16_t* depth, uint8_t* quant,
   const bool xcd = n_frames >= 8;   // XCD-aware tile placement, see tile_of_block
   dim3 grid = xcd ? dim3((unsigned)(tx * ty * 8 * ((n_frames + 7) / 8))) : dim3(tx, ty, n_frames);
   const int nfx = xcd ? n_frames : 0;
-  static const size_t pad = lds_pad("LMX_LDS_PAD_DEPTH", 0);
   if (difference_threshold <= 200)
-    hipLaunchKernelGGL(k_depth_quantize<int>, grid, dim3(256), pad, s, depth, quant, quant_half, H, W, distance_threshold, difference_threshold, lut_bins, clear16, nfx);
+    hipLaunchKernelGGL(k_depth_quantize<int>, grid, dim3(256), 0, s, depth, quant, quant_half, H, W, distance_threshold, difference_threshold, lut_bins, clear16, nfx);
   else
-    hipLaunchKernelGGL(k_depth_quantize<long long>, grid, dim3(256), pad, s, depth, quant, quant_half, H, W, distance_threshold, difference_threshold,
+    hipLaunchKernelGGL(k_depth_quantize<long long>, grid, dim3(256), 0, s, depth, quant, quant_half, H, W, distance_threshold, difference_threshold,
                        lut_bins, clear16, nfx);
 }
 
@@ -1911,8 +1854,7 @@ template <int T>
 static void launch_spread_linearize_t(hipStream_t s, const SpreadBatch& b, int n_mod, const LevelGeom& g, int n_frames) {
   constexpr int ND = (T + 2) / 4 + 2;
   const int Wd = g.W / 4 + ND;
-  static const size_t pad = lds_pad("LMX_LDS_PAD_SPREAD", 0);
-  size_t smem = 2048 + (size_t)(2 * T - 1 + T) * Wd * 4 + (size_t)T * g.W + pad;
+  size_t smem = 2048 + (size_t)(2 * T - 1 + T) * Wd * 4 + (size_t)T * g.W;
   if (n_frames >= 8)
     hipLaunchKernelGGL(k_spread_linearize_t<T>, dim3((unsigned)(g.Hc * 8 * ((n_frames + 7) / 8)), n_mod, 1), dim3(256), smem, s, b, g, n_frames);
   else
@@ -1957,7 +1899,7 @@ void launch_pack_nibbles(hipStream_t s, const uint8_t* lm, uint8_t* lmn, const L
 }
 
 // 0 = generic k_score_coarse, 1 = k_score_coarse_u8, 2 = k_score_coarse_sb (default when the bank qualifies).  The context chooses once,
-// when it is created (DeviceBankView::score_variant; environment LMX_SCORE_KERNEL = generic | u8 | sb, LMX_SCORE_GENERIC=1 = "generic").
+// when it is created (DeviceBankView::score_variant; environment LMX_SCORE_KERNEL = generic | u8 | sb).
 int score_kernel_variant(const DeviceBankView& bank) { return bank.uni_ok ? bank.score_variant : 0; }
 
 void launch_score_coarse(hipStream_t s, const DeviceBankView& bank, const LevelGeom& g, const uint8_t* const* lm_mod, int n_frames,
@@ -1980,15 +1922,13 @@ void launch_score_coarse(hipStream_t s, const DeviceBankView& bank, const LevelG
   p.sinfo = bank.sinfo;
   const int variant = score_kernel_variant(bank);
   const dim3 grid((unsigned)(p.blocks_per_frame * frame_slots)), block(64 * SC_WAVES_PER_BLOCK);
-  if (bank.score_no_prune) {   // LMX_SCORE_NO_PRUNE: similarity()'s full work, same candidates (see score_pass)
-    if (variant == 2) hipLaunchKernelGGL(k_score_coarse_sb<false>, grid, block, 0, s, p);
-    else if (variant == 1) hipLaunchKernelGGL(k_score_coarse_u8<false>, grid, block, 0, s, p);
-    else hipLaunchKernelGGL(k_score_coarse<false>, grid, block, 0, s, p);
-  } else {
-    if (variant == 2) hipLaunchKernelGGL(k_score_coarse_sb<true>, grid, block, 0, s, p);
-    else if (variant == 1) hipLaunchKernelGGL(k_score_coarse_u8<true>, grid, block, 0, s, p);
-    else hipLaunchKernelGGL(k_score_coarse<true>, grid, block, 0, s, p);
-  }
+  with_bool(bank.score_no_prune, [&](auto no_prune) {   // LMX_SCORE_NO_PRUNE: similarity()'s full work, same candidates (see score_pass)
+    constexpr bool PRUNE = !decltype(no_prune)::value;
+    void (*kernel)(ScoreParams) = k_score_coarse_sb<PRUNE>;
+    if (variant == 1) kernel = k_score_coarse_u8<PRUNE>;
+    else if (variant != 2) kernel = k_score_coarse<PRUNE>;
+    hipLaunchKernelGGL(kernel, grid, block, 0, s, p);
+  });
 }
 
 bool launch_refine(hipStream_t s, const DeviceBankView& bank, const KernelParams& kp, int n_frames, float threshold,
@@ -2021,14 +1961,10 @@ bool launch_small_depth_color(hipStream_t s, const uint16_t* depth, uint8_t* dq,
   a.dtx = (W + 63) / 64; a.dty = (H + DQ_TH - 1) / DQ_TH; a.ctx = (W1 + CQ_TW - 1) / CQ_TW; a.cty = (H1 + CQ_TH - 1) / CQ_TH;
   a.n_depth = a.dtx * a.dty * n_frames;
   const unsigned grid = (unsigned)(a.n_depth + a.ctx * a.cty * n_frames);
-  if (n_ch == 1) {
-    if (difference_threshold <= 200) hipLaunchKernelGGL((k_small_depth_color<int, 1>), dim3(grid), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_small_depth_color<long long, 1>), dim3(grid), dim3(256), 0, s, a);
-  } else if (difference_threshold <= 200) {
-    hipLaunchKernelGGL(k_small_depth_color<int>, dim3(grid), dim3(256), 0, s, a);
-  } else {
-    hipLaunchKernelGGL(k_small_depth_color<long long>, dim3(grid), dim3(256), 0, s, a);
-  }
+  with_bool(n_ch == 1, [&](auto gray) { with_bool(difference_threshold <= 200, [&](auto small_thr) {
+    using IntT = std::conditional_t<decltype(small_thr)::value, int, long long>;   // see depth_bin_at
+    hipLaunchKernelGGL((k_small_depth_color<IntT, decltype(gray)::value ? 1 : 3>), dim3(grid), dim3(256), 0, s, a);
+  }); });
   return true;
 }
 

@@ -239,7 +239,7 @@ lmx_status train_add_template(lmx_bank* bank, int device, const lmx_image* sourc
           float* d_mag = (float*)dmalloc((size_t)h * w * 4);
           uint8_t* d_next = l + 1 < L ? (uint8_t*)dmalloc((size_t)(h / 2) * (w / 2) * px_bytes) : nullptr;
           if (!d_mag || (l + 1 < L && !d_next)) { set_error("hipMalloc failed"); return LMX_ERR_HIP; }
-          launch_color_quantize(nullptr, d_cur_src, d_q, d_next, h, w, 1, md.weak_threshold, d_mag, nullptr, nullptr, px_bytes);
+          launch_color_quantize(nullptr, d_cur_src, d_q, d_next, h, w, 1, md.weak_threshold, d_mag, nullptr, nullptr, px_bytes, 0);
           TR_HIP(hipDeviceSynchronize());
           mags[m][l].resize((size_t)h * w);
           TR_HIP(hipMemcpy(mags[m][l].data(), d_mag, (size_t)h * w * 4, hipMemcpyDeviceToHost));
@@ -556,7 +556,7 @@ lmx_status train_mesh(lmx_bank* bank, int device, const double* triangles, int n
         const uint8_t* src = d_gray;
         for (int l = 0; l < L; ++l) {
           uint8_t* next = l + 1 < L ? d_pyr[m][l + 1] : nullptr;
-          launch_color_quantize(s, src, (uint8_t*)pa.quant[l][m], next, H0 >> l, W0 >> l, n, md.weak_threshold, (float*)pa.mag[l][m], nullptr, nullptr, 1);
+          launch_color_quantize(s, src, (uint8_t*)pa.quant[l][m], next, H0 >> l, W0 >> l, n, md.weak_threshold, (float*)pa.mag[l][m], nullptr, nullptr, 1, 0);
           src = next;
         }
       } else {

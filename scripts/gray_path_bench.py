@@ -8,7 +8,7 @@ alternating runs (--rounds of each), every line the median of its rounds:
              the plane into three channels there (the bench's config0_cg_only.raw_mono_752x480 line), the gray one keeps one
   one_frame  lmx_match with one fresh host frame per call (the reference's own pattern), microseconds per call
 and the per-kernel time of k_color_quantize and k_pre (HIP events around every kernel, one batch in flight).  --tiles also times
-k_color_quantize with each tile height pinned (LMX_COLOR_TILE=16 / 32, read once per process: one child process each).
+k_color_quantize with each tile height pinned (LMX_COLOR_TILE=16 / 32, read when a context is created: one child process each).
 Needs a GPU.  usage: gray_path_bench.py [--rounds 3] [--steps 30] [--tiles]"""
 import argparse
 import json

@@ -72,6 +72,7 @@ PATHS = [
     ("batch_of_nine", 160, 160, ("ColorGradient", "DepthNormal"), (5, 8), 50, 9, "enqueue", 0, False, False),        # n >= 8: tile placement by frame
     ("row_padded", 240, 160, ("ColorGradient", "DepthNormal"), (5, 8), 200, 2, "match_batch", 24, False, False),
     ("gray_context", 160, 160, ("ColorGradient", "DepthNormal"), (5, 8), 50, 1, "match", 0, False, True),
+    ("gray_context_long_form", 160, 160, ("ColorGradient", "DepthNormal"), (5, 8), 201, 1, "match", 0, False, True),   # the 64-bit form fused with the one-plane colour tile
     ("long_form_201", 160, 160, ("ColorGradient", "DepthNormal"), (5, 8), 201, 2, "enqueue", 0, False, False),       # the 64-bit kernel
     ("long_form_5000_match", 240, 160, ("ColorGradient", "DepthNormal"), (5, 8), 5000, 1, "match", 0, False, False),
     ("depth_only_one_level", 120, 80, ("DepthNormal",), (5,), 50, 1, "match", 0, False, False),                      # no interior tile, ragged last tiles

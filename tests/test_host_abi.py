@@ -29,6 +29,23 @@ def _same_bank(a, b):
         assert np.array_equal(ta, tb) and np.array_equal(fa, fb)
 
 
+def test_environment_table_matches_the_getenv_calls():
+    """INTEGRATION.md section 7 lists exactly the LMX_* variables the library's sources read."""
+    csrc = os.path.join(ROOT, "linemod_pose_estimation_amd", "csrc")
+    read = set()
+    for name in sorted(os.listdir(csrc)):
+        if name.endswith((".cpp", ".hip", ".hpp")):
+            read |= set(re.findall(r'getenv\(\s*"(LMX_[A-Z0-9_]+)"', open(os.path.join(csrc, name)).read()))
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    section = doc[doc.index("## 7. Environment variables"):]
+    rows = [ln for ln in section.splitlines() if ln.startswith("|")]
+    listed = set()
+    for ln in rows:
+        listed |= set(re.findall(r"\bLMX_[A-Z0-9_]+", re.split(r"(?<!\\)\|", ln)[1]))
+    assert read and listed
+    assert read == listed, (sorted(read - listed), sorted(listed - read))
+
+
 def test_library_exports_every_declared_symbol():
     hdr = open(os.path.join(ROOT, "include", "lmx.h")).read()
     hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
