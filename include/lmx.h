@@ -568,6 +568,16 @@ lmx_status lmx_debug_device_finalize_cluster(int32_t device, const lmx_raw_match
                                              const double* obj_origin_dists, const int32_t* rects, size_t n_templates,
                                              const lmx_cluster_params* params, lmx_match_t* matches, lmx_cluster_t* clusters, int32_t* members,
                                              uint32_t* counts);
+/* Test hook, no device needed: one of the tables a context of width x height frames, max_batch frames per batch and shard
+ * shard_rank of shard_world (1: the whole bank) would put on the device for `bank` -- the bytes DeviceBankView's pointers see
+ * (csrc/lmx_bank_tables.hpp defines every format); ls_flat != 0 as under LMX_LS_FLAT.  LMX_TAB_SUMMARY is uint32 words:
+ * {G, nf_max_coarse, uni_ok, uni_mod_block_bytes, L, M, classes, 0}, then 16 words per pyramid level {W, H, T, Wc, Hc, cells,
+ * ori_stride, mod_stride, zero_off, nib_ori_stride, nib_mod_stride, nib_zero_off, ls_stride, ls_zero_off, ls_bands, ls_band_stride}.
+ * *n_bytes = the table's size, *fnv1a = the 64-bit FNV-1a hash of its bytes (either may be NULL); out may be NULL to ask for those
+ * alone, else out_bytes must hold the table.  Geometry errors are reported as lmx_ctx_create reports them. */
+enum { LMX_TAB_INFO = 0, LMX_TAB_LINFO, LMX_TAB_COARSE_OFF, LMX_TAB_COARSE_UNI, LMX_TAB_COARSE_BLK, LMX_TAB_SINFO, LMX_TAB_FEAT, LMX_TAB_FEAT_COUNT, LMX_TAB_SUMMARY };
+lmx_status lmx_debug_bank_tables(const lmx_bank* bank, int32_t width, int32_t height, int32_t max_batch, int32_t shard_rank, int32_t shard_world,
+                                 int32_t ls_flat, int32_t table, void* out, size_t out_bytes, size_t* n_bytes, uint64_t* fnv1a);
 /* Counters of the last collect(): coarse candidates and refined matches summed over frames. */
 lmx_status lmx_ctx_stats(lmx_ctx* ctx, int64_t* n_candidates, int64_t* n_raw_matches);
 

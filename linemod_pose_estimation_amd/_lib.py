@@ -18,7 +18,7 @@ SYMBOLS = [
     "lmx_bank_pyramid_levels", "lmx_bank_T", "lmx_bank_num_modalities", "lmx_bank_modality", "lmx_bank_num_classes",
     "lmx_bank_class_id", "lmx_bank_num_templates", "lmx_bank_get_template",
     "lmx_ctx_create", "lmx_ctx_destroy", "lmx_match", "lmx_match_batch", "lmx_ctx_upload", "lmx_ctx_upload_masks", "lmx_match_masked", "lmx_ctx_upload_wait", "lmx_host_alloc", "lmx_host_free", "lmx_ctx_upload_raw", "lmx_ctx_enqueue",
-    "lmx_ctx_collect", "lmx_ctx_collect_flat", "lmx_ctx_raw_matches", "lmx_merge_raw", "lmx_ctx_export_raw", "lmx_ctx_export_raw_on", "lmx_ctx_release", "lmx_ctx_max_outstanding", "lmx_stream_copy", "lmx_stream_copy_blocks", "lmx_merge_gathered", "lmx_ctx_sync", "lmx_renderer_params_load", "lmx_renderer_params_save", "lmx_renderer_params_free", "lmx_cluster_matches", "lmx_ctx_set_cluster_sidecar", "lmx_ctx_collect_clusters", "lmx_ctx_debug_read", "lmx_debug_orientation_labels", "lmx_debug_depth_normal_bins", "lmx_debug_introsort_perm", "lmx_debug_introsort_perm_score", "lmx_debug_device_sort_perm", "lmx_debug_device_finalize_cluster", "lmx_ctx_stats",
+    "lmx_ctx_collect", "lmx_ctx_collect_flat", "lmx_ctx_raw_matches", "lmx_merge_raw", "lmx_ctx_export_raw", "lmx_ctx_export_raw_on", "lmx_ctx_release", "lmx_ctx_max_outstanding", "lmx_stream_copy", "lmx_stream_copy_blocks", "lmx_merge_gathered", "lmx_ctx_sync", "lmx_renderer_params_load", "lmx_renderer_params_save", "lmx_renderer_params_free", "lmx_cluster_matches", "lmx_ctx_set_cluster_sidecar", "lmx_ctx_collect_clusters", "lmx_ctx_debug_read", "lmx_debug_orientation_labels", "lmx_debug_depth_normal_bins", "lmx_debug_introsort_perm", "lmx_debug_introsort_perm_score", "lmx_debug_device_sort_perm", "lmx_debug_device_finalize_cluster", "lmx_debug_bank_tables", "lmx_ctx_stats",
     "lmx_num_kernels", "lmx_kernel_name", "lmx_ctx_device_kernel_name", "lmx_ctx_set_profiling", "lmx_ctx_kernel_time", "lmx_ctx_reset_profiling",
     "lmx_ctx_algorithmic_bytes", "lmx_last_error", "lmx_version",
 ]
@@ -28,6 +28,9 @@ SYMBOLS = [
 LMX_MOD_COLOR_GRADIENT, LMX_MOD_DEPTH_NORMAL = 0, 1
 LMX_DBG_QUANTIZED, LMX_DBG_LINEAR_MEMORY, LMX_DBG_PYRAMID_BGR = 0, 1, 2
 LMX_DBG_DEPTH_INT, LMX_DBG_DEPTH_INT64, LMX_DBG_DEPTH_PIPELINED = 0, 1, 2   # variants of lmx_debug_depth_normal_bins
+# table selectors of lmx_debug_bank_tables
+(LMX_TAB_INFO, LMX_TAB_LINFO, LMX_TAB_COARSE_OFF, LMX_TAB_COARSE_UNI, LMX_TAB_COARSE_BLK, LMX_TAB_SINFO, LMX_TAB_FEAT, LMX_TAB_FEAT_COUNT,
+ LMX_TAB_SUMMARY) = range(9)
 LMX_CTX_GRAY = 8   # include/lmx.h: ColorGradient sources are 8UC1 (gray), the colour pyramid one byte per pixel
 LMX_NORMAL_LUT_SIZE = 8000
 LMX_LUT_DEFAULT, LMX_LUT_USER, LMX_LUT_SIDECAR, LMX_LUT_UNKNOWN = range(4)
@@ -240,6 +243,8 @@ def lib():
     L.lmx_debug_introsort_perm_score.argtypes = [vp, C.c_int32, vp]
     L.lmx_debug_device_sort_perm.argtypes = [C.c_int32, vp, vp, C.c_int32, vp]
     L.lmx_debug_device_finalize_cluster.argtypes = [C.c_int32, vp, C.c_size_t, C.c_int32, vp, vp, C.c_size_t, C.POINTER(ClusterParams), vp, vp, vp, vp]
+    L.lmx_debug_bank_tables.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_size_t, C.POINTER(C.c_size_t),
+                                        C.POINTER(C.c_uint64)]
     L.lmx_ctx_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.lmx_kernel_name.argtypes = [C.c_int32]
     L.lmx_kernel_name.restype = C.c_char_p

@@ -279,12 +279,12 @@ lmx_status lmx_bank_get_template(const lmx_bank* bank, const char* class_id, int
   const ClassData& cd = it->second;
   const int per = (int)(bank->T.size() * bank->mods.size());
   if (template_id < 0 || template_id >= cd.n_pyramids || k < 0 || k >= per) { set_error("template index out of range"); return LMX_ERR_INVALID_ARG; }
-  const int32_t* t = &cd.templates[((size_t)template_id * per + k) * 5];
-  if (width) *width = t[0];
-  if (height) *height = t[1];
-  if (pyramid_level) *pyramid_level = t[2];
-  if (features) *features = &cd.features[(size_t)t[3] * 3];
-  if (n_features) *n_features = t[4];
+  const TemplateRow t = template_row(cd, per, template_id, k);
+  if (width) *width = t.width;
+  if (height) *height = t.height;
+  if (pyramid_level) *pyramid_level = t.level;
+  if (features) *features = template_features(cd, t);
+  if (n_features) *n_features = t.feat_count;
   return LMX_OK;
 }
 

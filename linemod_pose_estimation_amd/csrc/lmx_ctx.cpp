@@ -1,4 +1,4 @@
-// liblmx.so, device context: creation (geometry, the device-resident bank, per-lane workspaces, output slots), destruction, and the
+// liblmx.so, device context: creation (the upload of the bank's tables, per-lane workspaces, output slots), destruction, and the
 // upload paths in front of the kernel chain (host frames, masks, raw camera frames); the hooks device groups use.
 // Mirrors the call surface of cv::linemod::Detector as the reference uses it (/root/reference/src/rgbdDetector.cpp:31-34); see
 // include/lmx.h for the per-function mapping.  There is no CPU compute path: without a usable HIP device every compute call fails.
@@ -18,254 +18,19 @@ using namespace lmx;
 
 namespace lmx {
 
-static uint32_t round_up(uint32_t v, uint32_t a) { return (v + a - 1) / a * a; }
-
-// True when every feature of pyramid level l packs into the banded table entry (label:3 | matrix row:17 | column:12).
-static bool level_features_pack(const lmx_bank* b, int l, int L, int M, int T, int Hc) {
-  const int per = L * M;
-  for (const auto& kv : b->classes) {
-    const ClassData& cd = kv.second;
-    for (long t = 0; t < cd.n_pyramids; ++t)
-      for (int m = 0; m < M; ++m) {
-        const int32_t* tm = &cd.templates[((size_t)t * per + (size_t)l * M + m) * 5];
-        for (int f = 0; f < tm[4]; ++f) {
-          const int32_t* ft = &cd.features[((size_t)tm[3] + f) * 3];
-          if (ft[0] < 0 || ft[1] < 0 || ft[0] / T >= 4096) return false;
-          if ((long)((ft[1] % T) * T + (ft[0] % T)) * Hc + ft[1] / T >= (1L << 17)) return false;
-        }
-      }
-  }
-  return true;
-}
-
-static lmx_status build_geometry(lmx_ctx* c) {
-  int W = c->desc.width, H = c->desc.height;
-  for (int l = 0; l < c->L; ++l) {
-    if (l > 0) { W /= 2; H /= 2; }
-    const int T = c->bank->T[l];
-    if (T < 1 || T > 16) { set_error("T=%d at level %d unsupported (1..16)", T, l); return LMX_ERR_INVALID_ARG; }
-    if (W <= 0 || H <= 0 || W % T != 0 || H % T != 0) {
-      set_error("image size %dx%d at pyramid level %d is not a multiple of T=%d (upstream linearize CV_Assert)", W, H, l, T);
-      return LMX_ERR_SHAPE;
-    }
-    if (l + 1 < c->L && (W < 4 || H < 4)) {  // the fused pyrDown reflects at most two pixels across a border
-      set_error("image size %dx%d at pyramid level %d is too small to be downsampled again", W, H, l);
-      return LMX_ERR_SHAPE;
-    }
-    if (((long)W * H) % 16 != 0) {
-      set_error("rows*cols = %ld at level %d is not a multiple of 16 (upstream computeResponseMaps CV_Assert)", (long)W * H, l);
-      return LMX_ERR_SHAPE;
-    }
-    LevelGeom& g = c->kp.geom[l];
-    g.W = W; g.H = H; g.T = T; g.Wc = W / T; g.Hc = H / T;
-    g.cells = (uint32_t)g.Wc * g.Hc;
-    const uint32_t pad = g.cells + std::max<uint32_t>(16u * g.Wc + 64u, 2048u);
-    g.ori_stride = round_up((uint32_t)T * T * g.cells + pad, 256);
-    g.mod_stride = 8 * g.ori_stride + 8192;
-    g.zero_off = (uint32_t)T * T * g.cells;
-    const uint32_t nib_bytes = ((uint32_t)T * T * g.cells + 1) / 2;
-    g.nib_ori_stride = round_up(nib_bytes + g.cells / 2 + 2048 + 64, 256);
-    g.nib_mod_stride = 8 * g.nib_ori_stride + 8192;
-    g.nib_zero_off = round_up(nib_bytes + 32, 4);
-    g.ls_zero_off = (uint32_t)T * T * g.cells;
-    g.ls_stride = round_up(g.ls_zero_off + pad, 256);
-    g.ls_bands = 0; g.ls_band_stride = 0;
-    if (l < c->L - 1 && g.Wc % 16 == 0 && g.Wc >= 32 && !c->env.ls_flat) {
-      const uint32_t rows = (uint32_t)T * T * g.Hc;
-      if (rows < (1u << 17) && g.Wc < 4096 && level_features_pack(c->bank, l, c->L, c->M, T, g.Hc)) {
-        g.ls_bands = (uint32_t)g.Wc / 16;
-        g.ls_band_stride = (rows + 17) * 32;
-        g.ls_zero_off = (rows + 1) * 32;          // band 0, the 16 never-written rows behind the image
-        g.ls_stride = round_up(g.ls_bands * g.ls_band_stride, 256);
-      }
-    }
-  }
-  return LMX_OK;
-}
-
-static lmx_status build_device_bank(lmx_ctx* c) {
-  const lmx_bank* b = c->bank;
-  const int L = c->L, M = c->M, per = L * M;
-  const int world = std::max(1, c->desc.shard_world), rank = c->desc.shard_rank;
-  std::vector<TemplateInfo> info;
-  std::vector<TemplateLevelInfo> linfo;
-  std::vector<uint32_t> coarse, uni, blk;
-  std::vector<ScoreInfo> sinfo;
-  uint32_t pending_groups = 0;
-  bool uni_ok = true;
-  const uint32_t uni_block = (uint32_t)c->F * c->kp.geom[L - 1].nib_mod_stride;
-  std::vector<std::vector<FeatEntry>> feat_l(L);
-  std::vector<std::vector<uint8_t>> cnt_l(L);
-  int ci = 0, nf_max = 0;
-  c->class_names.clear();
-  for (const auto& kv : b->classes) {
-    const ClassData& cd = kv.second;
-    c->class_names.push_back(kv.first);
-    const long n = cd.n_pyramids;
-    const int begin = (int)((rank * n) / world), end = (int)(((rank + 1) * n) / world);
-    for (int t = begin; t < end; ++t) {
-      TemplateInfo ti;
-      ti.class_index = ci; ti.template_id = t; ti.class_slot = 0; ti.pad = 0;
-      info.push_back(ti);
-      for (int l = 0; l < L; ++l) {
-        const LevelGeom& g = c->kp.geom[l];
-        TemplateLevelInfo li{};
-        const int32_t* t0 = &cd.templates[((size_t)t * per + (size_t)l * M) * 5];
-        li.width = t0[0]; li.height = t0[1];
-        int nf_total = 0;
-        for (int m = 0; m < M; ++m) {
-          const int32_t* tm = &cd.templates[((size_t)t * per + (size_t)l * M + m) * 5];
-          const int fb = tm[3], fc = tm[4];
-          nf_total += fc;
-          std::vector<FeatEntry> ent(kFeatStride);
-          std::vector<uint32_t> offs(kFeatStride, (g.nib_zero_off >> 2) << 3);  // (dword index << 3) | nibble shift 0
-          for (int f = 0; f < fc; ++f) {
-            const int32_t* ft = &cd.features[((size_t)fb + f) * 3];
-            const int x = ft[0], y = ft[1], label = ft[2];
-            // accessLinearMemory: flat element index inside one orientation's [T*T][cells] matrix
-            const uint32_t e0 = (uint32_t)((y % g.T) * g.T + (x % g.T)) * g.cells + (uint32_t)(y / g.T) * g.Wc + (uint32_t)(x / g.T);
-            // finer levels (refinement): label in the top 3 bits, element index into the linearised spread image below
-            ent[f].off = ((uint32_t)label << 29) | e0;
-            if (g.ls_bands)   // banded image: row and column of the matrix instead of the flat index (build_geometry checked the ranges)
-              ent[f].off = ((uint32_t)label << 29) | ((uint32_t)((y % g.T) * g.T + (x % g.T)) * g.Hc + (uint32_t)(y / g.T)) << 12 | (uint32_t)(x / g.T);
-            ent[f].x = (int16_t)x; ent[f].y = (int16_t)y;
-            // coarsest level (scoring): (aligned dword index << 3) | (e0 & 7) into the nibble-packed memories;
-            // upstream similarity() skips out-of-image features
-            if (x < g.W && y < g.H) offs[f] = ((((uint32_t)label * g.nib_ori_stride) >> 2) + (e0 >> 3)) << 3 | (e0 & 7u);
-          }
-          for (int f = fc; f < kFeatStride; ++f) { ent[f].off = g.ls_zero_off; ent[f].x = 0; ent[f].y = 0; }
-          ent[kFeatStride - 1].y = (int16_t)fc;   // entry 63 is always padding (<= 63 features): k_refine reads the row's feature count from it
-          feat_l[l].insert(feat_l[l].end(), ent.begin(), ent.end());
-          cnt_l[l].push_back((uint8_t)fc);
-          if (l == L - 1) {
-            coarse.insert(coarse.end(), offs.begin(), offs.end());
-            nf_max = std::max(nf_max, fc);
-          }
-        }
-        li.nf_total = nf_total;
-        if (l == L - 1) {
-          // unified table (see DeviceBankView): the last M rows of `coarse` are this template's.  Order: modalities interleaved
-          // in groups of 3 (round robin), then regrouped by nibble shift (entry & 7): triples with ONE shift come first ("fast"
-          // groups: the kernel sums the three dwords before the funnel shift), emitted round robin over the shift classes so
-          // that the modalities stay mixed; the leftovers (< 3 per class) follow as mixed groups, the last one padded with
-          // zero-run entries.  Entry 63 = fast groups | all groups << 8.
-          std::vector<uint32_t> row(kFeatStride, (g.nib_zero_off >> 2) << 3);
-          uint32_t row_groups = 0;
-          if (nf_total <= kFeatStride - 1) {
-            std::vector<int> next(M, 0), cnt(M);
-            for (int m = 0; m < M; ++m) cnt[m] = cd.templates[((size_t)t * per + (size_t)l * M + m) * 5 + 4];
-            std::vector<uint32_t> cls[8];
-            for (bool any = true; any;) {
-              any = false;
-              for (int m = 0; m < M; ++m)
-                for (int u = 0; u < 3 && next[m] < cnt[m]; ++u, any = true) {
-                  const uint32_t e = coarse[coarse.size() - (size_t)(M - m) * kFeatStride + next[m]++] + ((((uint64_t)m * uni_block) >> 2) << 3);
-                  cls[e & 7u].push_back(e);
-                }
-            }
-            int n = 0, n_fast = 0;
-            size_t taken[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            for (bool any = true; any;) {
-              any = false;
-              for (int k = 0; k < 8; ++k)
-                if (cls[k].size() - taken[k] >= 3) {
-                  for (int u = 0; u < 3; ++u) row[n++] = cls[k][taken[k]++];
-                  ++n_fast;
-                  any = true;
-                }
-            }
-            for (int k = 0; k < 8; ++k)
-              while (taken[k] < cls[k].size()) row[n++] = cls[k][taken[k]++];
-            // final encoding of the unified table: byte offset (< 2^27, checked below) | funnel-shift bits (4 * nibble) << 27,
-            // so that the kernel needs one scalar instruction for each
-            for (int i = 0; i < kFeatStride - 1; ++i) row[i] = ((row[i] >> 3) << 2) | ((row[i] & 7u) * 4u) << 27;
-            const int n_groups = (n + 2) / 3;
-            row[kFeatStride - 1] = (uint32_t)n_fast | ((uint32_t)n_groups << 8);
-            row_groups = row[kFeatStride - 1];
-            // scalar-block row (k_score_coarse_sb): the same full triples in the same order, then one padded triple per shift class
-            // that has leftovers; 5 groups per 16-dword block
-            const uint32_t zero_entry = g.nib_zero_off & ~3u;   // byte offset of the zero run (modality 0's block; any shift reads zeros)
-            std::vector<uint32_t> brow((size_t)SB_BLOCK * SB_MAX_BLOCKS, zero_entry);
-            struct Grp { uint32_t off[3]; uint32_t shift; int real; };
-            std::vector<Grp> grps;
-            size_t tk[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            for (bool any = true; any;) {
-              any = false;
-              for (int k = 0; k < 8; ++k)
-                if (cls[k].size() - tk[k] >= 3) {
-                  Grp gr;
-                  for (int u = 0; u < 3; ++u) gr.off[u] = (cls[k][tk[k]++] >> 3) << 2;
-                  gr.shift = (uint32_t)k * 4u; gr.real = 3;
-                  grps.push_back(gr);
-                  any = true;
-                }
-            }
-            for (int k = 0; k < 8; ++k)
-              if (tk[k] < cls[k].size()) {
-                Grp gr;
-                gr.real = 0;
-                for (int u = 0; u < 3; ++u) {
-                  if (tk[k] < cls[k].size()) { gr.off[u] = (cls[k][tk[k]++] >> 3) << 2; gr.real += 1; }
-                  else gr.off[u] = zero_entry;
-                }
-                gr.shift = (uint32_t)k * 4u;
-                grps.push_back(gr);
-              }
-            const int n_blocks = ((int)grps.size() + SB_GROUPS - 1) / SB_GROUPS;
-            if (n_blocks > SB_MAX_BLOCKS) uni_ok = false;   // cannot happen for <= 63 features (<= 21 full + 8 padded groups)
-            else {
-              int consumed = 0;
-              for (int bi = 0; bi < n_blocks; ++bi) {
-                uint32_t meta = 0;
-                for (int q = 0; q < SB_GROUPS; ++q) {
-                  const size_t gi = (size_t)bi * SB_GROUPS + q;
-                  if (gi >= grps.size()) continue;
-                  for (int u = 0; u < 3; ++u) brow[(size_t)bi * SB_BLOCK + 3 * q + u] = grps[gi].off[u];
-                  meta |= grps[gi].shift << (5 * q);
-                  consumed += grps[gi].real;
-                }
-                brow[(size_t)bi * SB_BLOCK + SB_BLOCK - 1] = meta | ((uint32_t)consumed << 25);
-              }
-              row_groups |= (uint32_t)n_blocks << 16;
-              blk.insert(blk.end(), brow.begin(), brow.end());
-            }
-          } else {
-            uni_ok = false;
-          }
-          if (blk.size() < (uni.size() / kFeatStride + 1) * (size_t)SB_BLOCK * SB_MAX_BLOCKS) blk.resize((uni.size() / kFeatStride + 1) * (size_t)SB_BLOCK * SB_MAX_BLOCKS, 0u);
-          uni.insert(uni.end(), row.begin(), row.end());
-          pending_groups = row_groups;
-        }
-        const int wf = (li.width - 1) / g.T + 1, hf = (li.height - 1) / g.T + 1;
-        const long pos = (long)(g.Hc - hf) * g.Wc + (g.Wc - wf) + 1;
-        li.positions = (int32_t)std::max<long>(0, std::min<long>(pos, (long)g.cells));
-        linfo.push_back(li);
-        if (l == L - 1) sinfo.push_back(ScoreInfo{li.positions, li.nf_total, ci, pending_groups});
-      }
-    }
-    ++ci;
-  }
-  c->n_classes = ci;
+// The device-resident bank: the tables lmx_bank_tables.cpp builds, uploaded.
+static lmx_status upload_bank_tables(lmx_ctx* c) {
+  BankTables t;
+  build_bank_tables(*c->bank, c->kp.geom, c->F, c->desc.shard_rank, c->desc.shard_world, &t);
+  c->class_names = std::move(t.class_names);
+  c->n_classes = (int)c->class_names.size();
   DeviceBankView& d = c->dbank;
-  d.G = (int)info.size(); d.L = L; d.M = M; d.nf_max_coarse = nf_max;
-  lmx_status st;
-  if ((st = dev_upload(c, &d.info, info)) != LMX_OK) return st;
-  if ((st = dev_upload(c, &d.linfo, linfo)) != LMX_OK) return st;
-  if ((st = dev_upload(c, &d.coarse_off, coarse)) != LMX_OK) return st;
-  if ((st = dev_upload(c, &d.coarse_uni, uni)) != LMX_OK) return st;
-  if ((st = dev_upload(c, &d.coarse_blk, blk)) != LMX_OK) return st;
-  if ((st = dev_upload(c, &d.sinfo, sinfo)) != LMX_OK) return st;
-  d.uni_ok = (uni_ok && (uint64_t)M * uni_block + c->kp.geom[L - 1].nib_mod_stride < (1u << 27)) ? 1 : 0;  // byte offsets inside one frame's block
-  d.uni_mod_block_bytes = uni_block;
-  std::vector<FeatEntry> feat_all;
-  std::vector<uint8_t> cnt_all;
-  for (int l = 0; l < L; ++l) {
-    feat_all.insert(feat_all.end(), feat_l[l].begin(), feat_l[l].end());
-    cnt_all.insert(cnt_all.end(), cnt_l[l].begin(), cnt_l[l].end());
-  }
-  if ((st = dev_upload(c, &d.feat, feat_all)) != LMX_OK) return st;
-  if ((st = dev_upload(c, &d.feat_count, cnt_all)) != LMX_OK) return st;
-  return LMX_OK;
+  d.G = t.G; d.L = c->L; d.M = c->M; d.nf_max_coarse = t.nf_max_coarse; d.uni_ok = t.uni_ok; d.uni_mod_block_bytes = t.uni_mod_block_bytes;
+  lmx_status st = LMX_OK;
+  auto up = [&](auto** p, const auto& v) { if (st == LMX_OK) st = dev_upload(c, p, v); };
+  up(&d.info, t.info); up(&d.linfo, t.linfo); up(&d.coarse_off, t.coarse_off); up(&d.coarse_uni, t.coarse_uni); up(&d.coarse_blk, t.coarse_blk);
+  up(&d.sinfo, t.sinfo); up(&d.feat, t.feat); up(&d.feat_count, t.feat_count);
+  return st;
 }
 
 bool get_events(lmx_ctx* c, hipEvent_t* a, hipEvent_t* b) {
@@ -329,11 +94,41 @@ void store_modality(lmx_ctx* c, lmx_ctx::FrameSet& fs, int m, int n_frames, cons
   // GB/s with 1 thread, 44.5 with 8), and waking pool threads costs more than it could save
   for (int f = 0; f < n_frames; ++f) {
     const lmx_image& im = sources[(size_t)f * c->M + m];
-    uint8_t* dst = fs.store_buf[m] + (size_t)f * c->frame_bytes[m];
-    if (im.row_stride_bytes == row_bytes) stream_copy(dst, im.data, row_bytes * H);
-    else
-      for (int y = 0; y < H; ++y) stream_copy(dst + (size_t)y * row_bytes, (const uint8_t*)im.data + (size_t)y * im.row_stride_bytes, row_bytes);
+    copy_rows(fs.store_buf[m] + (size_t)f * c->frame_bytes[m], im.data, row_bytes, im.row_stride_bytes, H);
   }
+}
+
+// One copy of `rows` source rows into packed rows of a staging area: the unit the upload threads share.
+struct RowCopy { uint8_t* dst; const uint8_t* src; size_t row_bytes, src_stride; int rows; };
+
+// The copy tasks of one modality's images (frame f: sources[f * M + m], rows x row_bytes) into frames frame_bytes apart at dst.  bands = 0:
+// one task per image for batches, row bands for a few frames (a single 640x480 RGB-D frame is still 1.5 MB: 60 us on one thread, a third of
+// the whole single-frame call).
+static void add_copy_tasks(std::vector<RowCopy>& tasks, const lmx_image* sources, int M, int m, int n_frames, uint8_t* dst, size_t frame_bytes, size_t row_bytes, int rows,
+                           int bands = 0) {
+  if (bands < 1) bands = n_frames >= 8 ? 1 : std::max(1, std::min(8, rows / 64));
+  for (int f = 0; f < n_frames; ++f) {
+    const lmx_image& im = sources[(size_t)f * M + m];
+    for (int b = 0; b < bands; ++b) {
+      const int y0 = (int)((long)rows * b / bands), y1 = (int)((long)rows * (b + 1) / bands);
+      tasks.push_back(RowCopy{dst + (size_t)f * frame_bytes + (size_t)y0 * row_bytes, (const uint8_t*)im.data + (size_t)y0 * im.row_stride_bytes, row_bytes, im.row_stride_bytes, y1 - y0});
+    }
+  }
+}
+// ... run, on the pool's threads and this one, or on this thread alone (pool = null)
+static void run_copy_tasks(const std::vector<RowCopy>& tasks, CopyPool* pool) {
+  const std::function<void(int)> run = [&](int i) { copy_rows(tasks[i].dst, tasks[i].src, tasks[i].row_bytes, tasks[i].src_stride, tasks[i].rows); };
+  if (pool) pool->parallel_for((int)tasks.size(), run);
+  else
+    for (int i = 0; i < (int)tasks.size(); ++i) run(i);
+}
+static CopyPool* upload_pool(lmx_ctx* c) {
+  if (!c->pool) c->pool.reset(new CopyPool(upload_threads(c) - 1));
+  return c->pool.get();
+}
+// Modality m's level-0 frames of a frame set, as bytes.
+static uint8_t* set_frames(const lmx_ctx* c, const lmx_ctx::FrameSet& fs, int m) {
+  return c->bank->mods[m].type == LMX_MOD_COLOR_GRADIENT ? fs.bgr[m] : reinterpret_cast<uint8_t*>(fs.depth[m]);
 }
 
 }  // namespace lmx
@@ -361,9 +156,7 @@ void lmx_ctx::store_modality_streamed(lmx_ctx::FrameSet& fs, int m, int n_frames
     const int f = b / per_frame, y = (b - f * per_frame) * band, y1 = std::min(H, y + band);
     const lmx_image& im = sources[(size_t)f * c->M + m];
     uint8_t* dst = fs.store_buf[m] + (size_t)f * c->frame_bytes[m];
-    if (im.row_stride_bytes == row_bytes) lmx::stream_copy(dst + (size_t)y * row_bytes, (const uint8_t*)im.data + (size_t)y * row_bytes, row_bytes * (size_t)(y1 - y));
-    else
-      for (int r = y; r < y1; ++r) lmx::stream_copy(dst + (size_t)r * row_bytes, (const uint8_t*)im.data + (size_t)r * im.row_stride_bytes, row_bytes);
+    lmx::copy_rows(dst + (size_t)y * row_bytes, (const uint8_t*)im.data + (size_t)y * im.row_stride_bytes, row_bytes, im.row_stride_bytes, y1 - y);
     lmx::stream_store_flag(flag, (seq << 20) | (uint32_t)(f * H + (end < 0 ? y : y1)));
   }
 }
@@ -432,7 +225,7 @@ static lmx_status ctx_create_impl(lmx_ctx* c) {
   c->n_sets = c->n_lanes + 1;
   c->color_ch = (c->desc.flags & LMX_CTX_GRAY) ? 1 : 3;
 
-  lmx_status st = build_geometry(c);
+  lmx_status st = build_geometry(*c->bank, c->desc.width, c->desc.height, c->env.ls_flat, c->kp.geom);
   if (st != LMX_OK) return st;
   const int F = c->F;
   for (int m = 0; m < c->M; ++m) {
@@ -466,7 +259,7 @@ static lmx_status ctx_create_impl(lmx_ctx* c) {
       }
     }
   }
-  if ((st = build_device_bank(c)) != LMX_OK) return st;
+  if ((st = upload_bank_tables(c)) != LMX_OK) return st;
   {
     std::vector<uint8_t> bins;
     if (!normal_bins_device_image(c->bank->normal_lut.data(), bins)) { set_error("bank holds an invalid normal LUT"); return LMX_ERR_INVALID_ARG; }
@@ -661,9 +454,8 @@ lmx_status lmx_ctx_upload(lmx_ctx* c, int32_t n_frames, const lmx_image* sources
   st = begin_set_upload(c, set);
   if (st != LMX_OK) return st;
   lmx_ctx::FrameSet& fs = c->sets[set];
-  // staging: one task per (modality, frame); pinned sources (hipHostMalloc / hipHostRegister'ed caller memory) skip it
-  struct Task { uint8_t* dst; const uint8_t* src; size_t row_bytes, src_stride; int rows; };
-  std::vector<Task> tasks;
+  // staging (add_copy_tasks); pinned sources (hipHostMalloc / hipHostRegister'ed caller memory) skip it
+  std::vector<RowCopy> tasks;
   fs.stored = false;
   if (c->store_ok && n_frames <= lmx_ctx::kStoreFrames && !(c->desc.flags & LMX_CTX_ASYNC_INPUT)) {
     // Direct store (see FrameSet::store_buf): the lanes that still read this set's previous frames are waited for on the HOST here
@@ -705,35 +497,14 @@ lmx_status lmx_ctx_upload(lmx_ctx* c, int32_t n_frames, const lmx_image* sources
     }
     direct[m] = all_pinned ? 1 : 0;
     if (!all_pinned && !fs.h_stage) { set_error("lmx_ctx_upload: this context is a member of a device group and is fed through lmx_group_upload"); return LMX_ERR_INVALID_ARG; }
-    if (!all_pinned) {
-      // one task per image for batches, row bands for a few frames (a single 640x480 RGB-D frame is still 1.5 MB: 60 us on one
-      // thread, a third of the whole single-frame call)
-      const int bands = n_frames >= 8 ? 1 : std::max(1, std::min(8, H / 64));
-      for (int f = 0; f < n_frames; ++f) {
-        const lmx_image& im = sources[(size_t)f * c->M + m];
-        for (int b = 0; b < bands; ++b) {
-          const int y0 = (int)((long)H * b / bands), y1 = (int)((long)H * (b + 1) / bands);
-          tasks.push_back(Task{fs.h_stage + off + (size_t)f * c->frame_bytes[m] + (size_t)y0 * row_bytes, (const uint8_t*)im.data + (size_t)y0 * im.row_stride_bytes, row_bytes,
-                               im.row_stride_bytes, y1 - y0});
-        }
-      }
-    }
+    if (!all_pinned) add_copy_tasks(tasks, sources, c->M, m, n_frames, fs.h_stage + off, c->frame_bytes[m], row_bytes, H);
     off += c->frame_bytes[m] * c->F;
   }
-  if (!tasks.empty()) {
-    if (!c->pool) c->pool.reset(new CopyPool(upload_threads(c) - 1));
-    c->pool->parallel_for((int)tasks.size(), [&](int i) {
-      const Task& t = tasks[i];
-      if (t.src_stride == t.row_bytes) stream_copy(t.dst, t.src, t.row_bytes * t.rows);
-      else
-        for (int y = 0; y < t.rows; ++y) stream_copy(t.dst + (size_t)y * t.row_bytes, t.src + (size_t)y * t.src_stride, t.row_bytes);
-    });
-  }
+  if (!tasks.empty()) run_copy_tasks(tasks, upload_pool(c));
   off = 0;
   for (int m = 0; m < c->M; ++m) {
-    const bool cg = c->bank->mods[m].type == LMX_MOD_COLOR_GRADIENT;
     const size_t row_bytes = (size_t)W * c->src_px_bytes(m);
-    uint8_t* dst = cg ? fs.bgr[m] : reinterpret_cast<uint8_t*>(fs.depth[m]);
+    uint8_t* dst = set_frames(c, fs, m);
     if (!direct[m]) {
       LMX_HIP(hipMemcpyAsync(dst, fs.h_stage + off, c->frame_bytes[m] * n_frames, hipMemcpyHostToDevice, c->copy_stream));
     } else {
@@ -866,36 +637,16 @@ lmx_status ctx_check_sources(lmx_ctx* c, int n_frames, const lmx_image* sources,
 
 // Copies every source of a batch into a pinned staging area with the layout of FrameSet::h_stage (modality m at offset
 // sum_{m' < m} frame_bytes[m'] * stride_frames, frames back to back, rows packed; stride_frames = the context's max_batch, or the group's
-// when a device group stages a batch for members that each take a slice of it): one task per image for batches, row bands for a few
-// frames (a single 640x480 RGB-D frame is still 1.5 MB: 60 us on one thread).
+// when a device group stages a batch for members that each take a slice of it).
 void ctx_stage_sources(lmx_ctx* c, CopyPool* pool, uint8_t* base, int n_frames, const lmx_image* sources, int stride_frames) {
   if (stride_frames < 1) stride_frames = c->F;
-  struct Task { uint8_t* dst; const uint8_t* src; size_t row_bytes, src_stride; int rows; };
-  std::vector<Task> tasks;
-  const int W = c->desc.width, H = c->desc.height;
+  std::vector<RowCopy> tasks;
   size_t off = 0;
   for (int m = 0; m < c->M; ++m) {
-    const size_t row_bytes = (size_t)W * c->src_px_bytes(m);
-    const int bands = n_frames >= 8 ? 1 : std::max(1, std::min(8, H / 64));
-    for (int f = 0; f < n_frames; ++f) {
-      const lmx_image& im = sources[(size_t)f * c->M + m];
-      for (int b = 0; b < bands; ++b) {
-        const int y0 = (int)((long)H * b / bands), y1 = (int)((long)H * (b + 1) / bands);
-        tasks.push_back(Task{base + off + (size_t)f * c->frame_bytes[m] + (size_t)y0 * row_bytes, (const uint8_t*)im.data + (size_t)y0 * im.row_stride_bytes, row_bytes,
-                             im.row_stride_bytes, y1 - y0});
-      }
-    }
+    add_copy_tasks(tasks, sources, c->M, m, n_frames, base + off, c->frame_bytes[m], (size_t)c->desc.width * c->src_px_bytes(m), c->desc.height);
     off += c->frame_bytes[m] * (size_t)stride_frames;
   }
-  auto run = [&](int i) {
-    const Task& t = tasks[i];
-    if (t.src_stride == t.row_bytes) stream_copy(t.dst, t.src, t.row_bytes * t.rows);
-    else
-      for (int y = 0; y < t.rows; ++y) stream_copy(t.dst + (size_t)y * t.row_bytes, t.src + (size_t)y * t.src_stride, t.row_bytes);
-  };
-  if (pool) pool->parallel_for((int)tasks.size(), run);
-  else
-    for (int i = 0; i < (int)tasks.size(); ++i) run(i);
+  run_copy_tasks(tasks, pool);
 }
 
 lmx_status ctx_begin_staged_upload(lmx_ctx* c) {
@@ -912,8 +663,7 @@ lmx_status ctx_finish_staged_upload(lmx_ctx* c, int n_frames, const uint8_t* pin
   fs.stored = false;
   size_t off = 0;
   for (int m = 0; m < c->M; ++m) {
-    const bool cg = c->bank->mods[m].type == LMX_MOD_COLOR_GRADIENT;
-    uint8_t* dst = cg ? fs.bgr[m] : reinterpret_cast<uint8_t*>(fs.depth[m]);
+    uint8_t* dst = set_frames(c, fs, m);
     // a member of a frame group takes its slice [first_frame, first_frame + n_frames) of the staged batch; none at all when the batch
     // has fewer frames than groups (the set still becomes current: the members' sets advance in lock step)
     if (n_frames > 0)
@@ -1002,30 +752,14 @@ lmx_status lmx_ctx_upload_raw(lmx_ctx* c, int32_t n_frames, const lmx_image* sou
     fs.raw_bytes = total;
   }
   // staging with non-temporal stores on the upload threads (one task per image), like lmx_ctx_upload
-  struct Task { uint8_t* dst; const uint8_t* src; size_t row_bytes, src_stride; int rows; };
-  std::vector<Task> tasks;
+  std::vector<RowCopy> tasks;
   size_t off = 0;
   for (int m = 0; m < c->M; ++m) {
     const Raw& r = raw[m];
-    const size_t row_bytes = (size_t)r.sw * r.ch * r.es;
-    for (int f = 0; f < n_frames; ++f) {
-      const lmx_image& im = sources[(size_t)f * c->M + m];
-      tasks.push_back(Task{fs.h_raw + off + (size_t)f * r.bytes, (const uint8_t*)im.data, row_bytes, im.row_stride_bytes, r.sh});
-    }
+    add_copy_tasks(tasks, sources, c->M, m, n_frames, fs.h_raw + off, r.bytes, (size_t)r.sw * r.ch * r.es, r.sh, 1);
     off += r.bytes * n_frames;
   }
-  auto run = [&](int i) {
-    const Task& t = tasks[i];
-    if (t.src_stride == t.row_bytes) stream_copy(t.dst, t.src, t.row_bytes * t.rows);
-    else
-      for (int y = 0; y < t.rows; ++y) stream_copy(t.dst + (size_t)y * t.row_bytes, t.src + (size_t)y * t.src_stride, t.row_bytes);
-  };
-  if (tasks.size() > 2) {
-    if (!c->pool) c->pool.reset(new CopyPool(upload_threads(c) - 1));
-    c->pool->parallel_for((int)tasks.size(), run);
-  } else {
-    for (int i = 0; i < (int)tasks.size(); ++i) run(i);
-  }
+  run_copy_tasks(tasks, tasks.size() > 2 ? upload_pool(c) : nullptr);
   if (!c->pre_stream) {
     LMX_HIP(hipStreamCreateWithFlags(&c->pre_stream, hipStreamNonBlocking));
     LMX_HIP(hipEventCreateWithFlags(&c->raw_dma_done, hipEventDisableTiming));

@@ -1,13 +1,15 @@
 // The device context of liblmx.so (struct lmx_ctx) and the helpers its translation units share.  Nothing here crosses the C ABI
 // (include/lmx.h).  The host side of the library is split along the context's life:
 //   lmx_bank.cpp     host bank: create / add_class / accessors / NORMAL_LUT, lmx_last_error
-//   lmx_ctx.cpp      context create / destroy, geometry and the device-resident bank, uploads (frames, masks, raw camera frames),
-//                    the hooks device groups use (lmx_group.cpp)
+//   lmx_bank_tables.cpp  (+ .hpp, no HIP) the level geometry and every table the scoring / refinement kernels read, as pure functions of the bank
+//   lmx_ctx.cpp      context create / destroy, the upload of those tables, uploads (frames, masks, raw camera frames; one builder of
+//                    row-band copy tasks for all of them), the hooks device groups use (lmx_group.cpp)
 //   lmx_enqueue.cpp  the per-batch kernel chain (plain, small-batch, hipGraph), lmx_ctx_enqueue, lmx_match / lmx_match_batch
 //   lmx_collect.cpp  read-back and finalisation (std::sort + std::unique), the device-side consumer chain, gather-block export / merge
 //   lmx_cluster.cpp  the reference's voting / cluster / NMS chain on the host
 //   lmx_cache.cpp    bank fingerprint, binary bank files, the per-request caches (lmx_bank_load_yaml_cached, lmx_ctx_acquire)
 //   lmx_debug.cpp    introspection, per-kernel timing, test hooks
+//   lmx_hostcopy.cpp (no HIP) non-temporal host copies: stream_copy, copy_rows, the progress word of a streamed store
 #pragma once
 
 #include <algorithm>

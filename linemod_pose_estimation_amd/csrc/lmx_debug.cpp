@@ -147,6 +147,43 @@ lmx_status lmx_debug_depth_normal_bins(int32_t device, const uint16_t* taps, siz
   return st;
 }
 
+lmx_status lmx_debug_bank_tables(const lmx_bank* bank, int32_t width, int32_t height, int32_t max_batch, int32_t shard_rank, int32_t shard_world, int32_t ls_flat,
+                                 int32_t table, void* out, size_t out_bytes, size_t* n_bytes, uint64_t* fnv1a) {
+  return lmx::guarded("lmx_debug_bank_tables", [&]() -> lmx_status {
+  if (!bank || bank->T.empty() || bank->T.size() > (size_t)kMaxLevels || bank->mods.empty() || bank->mods.size() > (size_t)kMaxModalities || max_batch < 1 ||
+      shard_world < 1 || shard_rank < 0 || shard_rank >= shard_world) {
+    set_error("lmx_debug_bank_tables: invalid argument");
+    return LMX_ERR_INVALID_ARG;
+  }
+  const int L = (int)bank->T.size();
+  LevelGeom geom[kMaxLevels] = {};
+  if (lmx_status st = build_geometry(*bank, width, height, ls_flat != 0, geom)) return st;
+  BankTables t;
+  build_bank_tables(*bank, geom, max_batch, shard_rank, shard_world, &t);
+  static_assert(sizeof(LevelGeom) == 64, "LMX_TAB_SUMMARY documents 16 words per level");
+  std::vector<uint32_t> summary = {(uint32_t)t.G, (uint32_t)t.nf_max_coarse, (uint32_t)t.uni_ok, t.uni_mod_block_bytes, (uint32_t)L, (uint32_t)bank->mods.size(), (uint32_t)t.class_names.size(), 0u};
+  summary.resize(8 + 16 * (size_t)L);
+  std::memcpy(summary.data() + 8, geom, (size_t)L * sizeof(LevelGeom));
+  auto bytes = [](const auto& v) { return std::pair<const void*, size_t>(v.data(), v.size() * sizeof(v[0])); };
+  const std::pair<const void*, size_t> tables[] = {bytes(t.info),  bytes(t.linfo), bytes(t.coarse_off),  bytes(t.coarse_uni), bytes(t.coarse_blk),
+                                                   bytes(t.sinfo), bytes(t.feat),  bytes(t.feat_count), bytes(summary)};   // LMX_TAB_* order
+  if (table < 0 || table > LMX_TAB_SUMMARY) { set_error("lmx_debug_bank_tables: unknown table %d", table); return LMX_ERR_INVALID_ARG; }
+  const void* p = tables[table].first;
+  const size_t n = tables[table].second;
+  if (n_bytes) *n_bytes = n;
+  if (fnv1a) {
+    uint64_t h = 0xcbf29ce484222325ull;
+    for (size_t i = 0; i < n; ++i) h = (h ^ static_cast<const uint8_t*>(p)[i]) * 0x100000001b3ull;
+    *fnv1a = h;
+  }
+  if (out) {
+    if (out_bytes < n) { set_error("lmx_debug_bank_tables: the table has %zu bytes, the buffer %zu", n, out_bytes); return LMX_ERR_INVALID_ARG; }
+    if (n) std::memcpy(out, p, n);
+  }
+  return LMX_OK;
+  });
+}
+
 lmx_status lmx_ctx_stats(lmx_ctx* c, int64_t* n_candidates, int64_t* n_raw_matches) {
   if (!c) { set_error("lmx_ctx_stats: null context"); return LMX_ERR_INVALID_ARG; }
   if (n_candidates) *n_candidates = c->stat_cands;
@@ -211,16 +248,14 @@ lmx_status lmx_ctx_algorithmic_bytes(lmx_ctx* c, int32_t id, int32_t n_frames, d
     case K_PACK_NIBBLES: v = spread_writes_nibbles(c->kp.geom[L - 1]) ? 0.0 : M * 12.0 * c->kp.geom[L - 1].W * c->kp.geom[L - 1].H; break;  // generic path only
     case K_SCORE_COARSE: {
       const LevelGeom& g = c->kp.geom[L - 1];
-      const int world = c->desc.shard_world, rank = c->desc.shard_rank;
       for (const auto& kv : b->classes) {
         const ClassData& cd = kv.second;
-        const long n = cd.n_pyramids;
-        for (long t = (rank * n) / world; t < ((rank + 1) * n) / world; ++t)
+        long begin, end;
+        shard_range(cd.n_pyramids, c->desc.shard_rank, c->desc.shard_world, &begin, &end);
+        for (long t = begin; t < end; ++t)
           for (int m = 0; m < M; ++m) {
-            const int32_t* tm = &cd.templates[((size_t)t * per + (size_t)(L - 1) * M + m) * 5];
-            const int wf = (tm[0] - 1) / g.T + 1, hf = (tm[1] - 1) / g.T + 1;
-            const double pos = std::max<long>(0, (long)(g.Hc - hf) * g.Wc + (g.Wc - wf) + 1);
-            v += tm[4] * pos + 3.0 * g.cells;
+            const TemplateRow tm = template_row(cd, per, t, (L - 1) * M + m);
+            v += tm.feat_count * (double)template_positions(g, tm.width, tm.height) + 3.0 * g.cells;
           }
       }
       break;

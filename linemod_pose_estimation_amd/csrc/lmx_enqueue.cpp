@@ -16,6 +16,37 @@
 
 using namespace lmx;
 
+static SpreadBatch spread_batch(const lmx_ctx* c, int l) {
+  SpreadBatch sb{};
+  for (int m = 0; m < c->M; ++m) {
+    sb.quant[m] = c->kp.fb.quant[l][m]; sb.lm[m] = c->kp.fb.lm[l][m]; sb.ls[m] = c->kp.fb.ls[l][m];
+    sb.lmn[m] = l == c->L - 1 ? c->kp.fb.lmn[m] : nullptr;
+  }
+  return sb;
+}
+
+// Spread + linearise of level l: all modalities in one launch when the level has a fast kernel, one launch per modality otherwise; at the
+// coarsest level the generic kernel's byte memories are packed to nibbles behind it.
+static void issue_spread_level(lmx_ctx* c, hipStream_t s, int l, int n_frames) {
+  const LevelGeom& g = c->kp.geom[l];
+  const SpreadBatch sb = spread_batch(c, l);
+  bool batched;
+  {
+    ScopedKernel k(c, K_SPREAD_LINEARIZE);
+    batched = launch_spread_linearize_all(s, sb, c->M, g, n_frames);
+  }
+  for (int m = 0; m < c->M; ++m) {
+    if (!batched) {
+      ScopedKernel k(c, K_SPREAD_LINEARIZE);
+      launch_spread_linearize(s, sb.quant[m], sb.lm[m], sb.ls[m], sb.lmn[m], g, n_frames);
+    }
+    if (l == c->L - 1 && !spread_writes_nibbles(g)) {
+      ScopedKernel k(c, K_PACK_NIBBLES);
+      launch_pack_nibbles(s, c->kp.fb.lm[l][m], c->kp.fb.lmn[m], g, n_frames);
+    }
+  }
+}
+
 // The per-batch chain in two stages.  No host synchronisation and no allocation in either, so they can run eagerly or inside a
 // stream capture (hipGraph).  Stage 1 (pre-processing): every level/modality -> quantised images, spread images, memories.
 static lmx_status issue_pre(lmx_ctx* c, int32_t n_frames, hipStream_t s) {
@@ -49,27 +80,7 @@ static lmx_status issue_pre(lmx_ctx* c, int32_t n_frames, hipStream_t s) {
     // Detector::match(..., masks): labels outside a modality's mask are dropped before they are spread (upstream quantize(): copyTo(dst, mask))
     for (int m = 0; m < c->M; ++m)
       if (c->sets[c->cur_set].masked[m]) launch_apply_mask(s, c->kp.fb.quant[l][m], c->sets[c->cur_set].mask[m], g.H, g.W, c->desc.width, c->desc.height, l, n_frames);
-    // spread + linearise of the level: all modalities in one launch when the level has a fast kernel
-    SpreadBatch sb{};
-    for (int m = 0; m < c->M; ++m) {
-      sb.quant[m] = c->kp.fb.quant[l][m]; sb.lm[m] = c->kp.fb.lm[l][m]; sb.ls[m] = c->kp.fb.ls[l][m];
-      sb.lmn[m] = l == c->L - 1 ? c->kp.fb.lmn[m] : nullptr;
-    }
-    bool batched;
-    {
-      ScopedKernel k(c, K_SPREAD_LINEARIZE);
-      batched = launch_spread_linearize_all(s, sb, c->M, g, n_frames);
-    }
-    for (int m = 0; m < c->M; ++m) {
-      if (!batched) {
-        ScopedKernel k(c, K_SPREAD_LINEARIZE);
-        launch_spread_linearize(s, sb.quant[m], sb.lm[m], sb.ls[m], sb.lmn[m], g, n_frames);
-      }
-      if (l == c->L - 1 && !spread_writes_nibbles(g)) {
-        ScopedKernel k(c, K_PACK_NIBBLES);
-        launch_pack_nibbles(s, c->kp.fb.lm[l][m], c->kp.fb.lmn[m], g, n_frames);
-      }
-    }
+    issue_spread_level(c, s, l, n_frames);
   }
   LMX_HIP(hipGetLastError());
   return LMX_OK;
@@ -168,34 +179,12 @@ static lmx_status issue_small(lmx_ctx* c, int slot, int32_t n_frames, float thre
   };
   // spread of both levels, score, refine (+ read-back)
   auto launch_rest = [&]() -> lmx_status {
-    SpreadBatch sb[2] = {};
-    for (int l = 0; l < 2; ++l)
-      for (int m = 0; m < c->M; ++m) {
-        sb[l].quant[m] = c->kp.fb.quant[l][m]; sb[l].lm[m] = c->kp.fb.lm[l][m]; sb[l].ls[m] = c->kp.fb.ls[l][m];
-        sb[l].lmn[m] = l == 1 ? c->kp.fb.lmn[m] : nullptr;
-      }
     bool fused;
     {
       ScopedKernel k(c, K_SPREAD_LINEARIZE);
-      fused = launch_small_spread(s, sb[0], g0, sb[1], g1, c->M, n_frames);
+      fused = launch_small_spread(s, spread_batch(c, 0), g0, spread_batch(c, 1), g1, c->M, n_frames);
     }
-    for (int l = 0; l < 2 && !fused; ++l) {   // no fused kernel for this pair of T / these widths: level by level, like issue_pre
-      bool batched;
-      {
-        ScopedKernel k(c, K_SPREAD_LINEARIZE);
-        batched = launch_spread_linearize_all(s, sb[l], c->M, c->kp.geom[l], n_frames);
-      }
-      for (int m = 0; m < c->M; ++m) {
-        if (!batched) {
-          ScopedKernel k(c, K_SPREAD_LINEARIZE);
-          launch_spread_linearize(s, sb[l].quant[m], sb[l].lm[m], sb[l].ls[m], sb[l].lmn[m], c->kp.geom[l], n_frames);
-        }
-        if (l == 1 && !spread_writes_nibbles(g1)) {
-          ScopedKernel k(c, K_PACK_NIBBLES);
-          launch_pack_nibbles(s, c->kp.fb.lm[l][m], c->kp.fb.lmn[m], g1, n_frames);
-        }
-      }
-    }
+    for (int l = 0; l < 2 && !fused; ++l) issue_spread_level(c, s, l, n_frames);   // no fused kernel for this pair of T / these widths: level by level, like issue_pre
     LMX_HIP(hipGetLastError());
     return issue_post(c, slot, n_frames, threshold, s);
   };

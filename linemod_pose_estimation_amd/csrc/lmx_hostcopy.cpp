@@ -42,4 +42,9 @@ void stream_copy(void* dst, const void* src, size_t n) {
   else std::memcpy(dst, src, n);
 }
 
+void copy_rows(void* dst, const void* src, size_t row_bytes, size_t src_stride, int rows) {
+  if (src_stride == row_bytes) { stream_copy(dst, src, row_bytes * (size_t)rows); return; }
+  for (int y = 0; y < rows; ++y) stream_copy(static_cast<uint8_t*>(dst) + (size_t)y * row_bytes, static_cast<const uint8_t*>(src) + (size_t)y * src_stride, row_bytes);
+}
+
 }  // namespace lmx

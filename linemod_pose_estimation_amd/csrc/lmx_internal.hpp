@@ -18,46 +18,12 @@
 #include <vector>
 
 #include "lmx.h"
+#include "lmx_bank_tables.hpp"   // the host bank, LevelGeom and the kernels' table entries (no HIP)
 
 namespace lmx {
 
-// ---- host bank (mirrors cv::linemod::Detector's template state) ---------------------------
-struct ClassData {
-  std::string id;
-  int32_t n_pyramids = 0;
-  std::vector<int32_t> templates;  // [n_pyramids * L*M][5] {width, height, pyramid_level, feat_begin, feat_count}
-  std::vector<int32_t> features;   // [n][3] {x, y, label}
-};
-
-}  // namespace lmx
-
-struct lmx_bank {
-  std::vector<int32_t> T;
-  std::vector<lmx_modality_desc> mods;
-  std::map<std::string, lmx::ClassData> classes;  // std::map: upstream iterates classes in key order (A.10)
-  std::vector<uint8_t> normal_lut;                // DepthNormal NORMAL_LUT[20][20][20] (one-hot labels), see include/lmx.h
-  int32_t normal_lut_origin = 0;                  // LMX_LUT_*
-  uint32_t lut_epoch = 0;                         // bumped by everything that replaces normal_lut (same size, new content)
-  // lmx_bank_fingerprint hashes every template and feature (3.5 MB for 3000 templates: 2.8 ms), and lmx_ctx_acquire asks for it on every
-  // request: remembered together with a signature of what it covered (element counts and lut_epoch: the API only appends templates or
-  // replaces the table).  Copy-constructible on purpose (lmx_ctx_acquire keeps a private copy of the caller's bank).
-  struct FingerprintCache {
-    std::atomic<uint64_t> value{0}, signature{0};
-    FingerprintCache() = default;
-    FingerprintCache(const FingerprintCache& o) : value(o.value.load(std::memory_order_relaxed)), signature(o.signature.load(std::memory_order_relaxed)) {}
-    FingerprintCache& operator=(const FingerprintCache& o) {
-      value.store(o.value.load(std::memory_order_relaxed), std::memory_order_relaxed);
-      signature.store(o.signature.load(std::memory_order_relaxed), std::memory_order_relaxed);
-      return *this;
-    }
-  };
-  mutable FingerprintCache fp_cache;
-};
-
-namespace lmx {
-
-void set_error(const char* fmt, ...);
 void stream_copy(void* dst, const void* src, size_t n);   // lmx_hostcopy.cpp: copy into pinned staging with non-temporal stores
+void copy_rows(void* dst, const void* src, size_t row_bytes, size_t src_stride, int rows);   // lmx_hostcopy.cpp: rows of an image to packed rows, one stream_copy when it is dense
 void stream_store_flag(uint32_t* flag, uint32_t value);    // lmx_hostcopy.cpp: the progress word of a streamed frame store (see StreamWait)
 lmx_status yaml_load(const char* path, lmx_bank** out);
 lmx_status yaml_save(const lmx_bank* bank, const char* path);
@@ -200,44 +166,6 @@ lmx_status ctx_finish_staged_upload(lmx_ctx* c, int n_frames, const uint8_t* pin
 lmx_status ctx_prepare_graph(lmx_ctx* c, int n_frames, float threshold);           // LMX_CTX_HIPGRAPH: capture the next enqueue's chain now if it is not cached
 lmx_status ctx_drop_newest(lmx_ctx* c);                                            // undo the most recent enqueue (waits for it, frees its slot)
 
-// ---- device-side geometry --------------------------------------------------------------------------------
-constexpr int kMaxLevels = 4;
-constexpr int kMaxModalities = 4;
-constexpr int SB_GROUPS = 5, SB_BLOCK = 16, SB_MAX_BLOCKS = 6;   // scalar-block table of k_score_coarse_sb: <= 30 groups per template
-constexpr int kFeatStride = 64;  // feature-table entries per (template, modality, level); upstream caps features at 63
-
-struct LevelGeom {
-  int32_t W, H;          // image size at this level
-  int32_t T;             // sampling step
-  int32_t Wc, Hc;        // W/T, H/T  (linear-memory "width"/"height")
-  uint32_t cells;        // Wc*Hc      (length of one linear memory)
-  uint32_t ori_stride;   // bytes per orientation block: T*T*cells + zero pad, multiple of 256
-  uint32_t mod_stride;   // bytes per (frame, modality) at this level: 8*ori_stride + tail pad
-  uint32_t zero_off;     // offset (within a modality block) of a run of >= cells+4096 zero bytes
-  // nibble-packed memories of the coarsest level (two responses per byte), read by k_score_coarse:
-  //   orientation o, byte i  =  elem(2i) | elem(2i + 1) << 4,  elem = the orientation's flat T*T*cells array, zero past its end.
-  //   A feature whose first element index e0 is not a multiple of 8 starts in the middle of a dword: the kernel loads aligned
-  //   dwords and funnel-shifts by 4 * (e0 & 7) bits with the neighbour lane's dword (v_alignbit_b32), so one copy serves
-  //   every alignment.  Table entry = (dword index << 3) | (e0 & 7).
-  uint32_t nib_ori_stride;    // bytes per orientation block incl. zero pad, multiple of 256
-  uint32_t nib_mod_stride;    // bytes per (frame, modality): 8 * nib_ori_stride + tail pad
-  uint32_t nib_zero_off;      // byte offset (multiple of 4) of a zero run (>= cells/2 + 2048 bytes) inside the block
-  // finer levels keep NO response maps: only the spread image in linearize() order, one byte per cell.  k_refine derives the
-  // 0..4 response of a feature's orientation from the spread byte with four nested bit masks (it touches a few hundred bytes
-  // per candidate, so 8x fewer bytes are written and kept per frame than with materialised linear memories).
-  uint32_t ls_stride;         // bytes per (frame, modality), multiple of 256
-  uint32_t ls_zero_off;       // start of a zero run large enough for one patch
-  // Banded form of that image (ls_bands > 0; Wc % 16 == 0, Wc >= 32).  View upstream's linear memories of one (frame, modality)
-  // as ONE matrix of R = T*T*Hc rows x Wc columns (row = grid * Hc + cell row; flat index = row * Wc + column, a column past
-  // Wc continues in the next row exactly as in the flat array).  Band k keeps columns 16k .. 16k+31 of every row in 32 bytes:
-  //     byte (k * ls_band_stride + (row + 1) * 32 + c)  =  flat element row * Wc + 16k + c,      0 <= c < 32,
-  // so every cell is stored twice and the 16 x 16 patch k_refine gathers for a feature (any origin) is 16 consecutive 32-byte
-  // rows of one band: 4-5 cache lines instead of 16-17 (the gathers miss L2; round 2 measured the flat form at 5.4 TB/s of HBM
-  // fetches, 730 lines per candidate).  Row 0 of a band is slack for the writer, rows R+1 .. R+16 stay zero.
-  uint32_t ls_bands;          // 0: flat form
-  uint32_t ls_band_stride;    // bytes per band: (R + 17) * 32
-};
-
 // Coarse candidate written by k_score_coarse, consumed by k_refine.
 struct Candidate {
   uint32_t g;      // shard-local template index (all classes concatenated)
@@ -283,32 +211,6 @@ inline lmx_status guarded(const char* what, F&& body) noexcept {
     return LMX_ERR_INVALID_ARG;
   }
 }
-
-// Fine-level feature table entry (refinement needs x,y for upstream's out-of-bounds skip).
-struct FeatEntry {
-  uint32_t off;    // finer levels: label << 29 | (grid_row*cells + lm_index) into the linearised spread image
-  int16_t x, y;
-};
-
-struct TemplateInfo {    // per shard-local template g
-  int32_t class_index;
-  int32_t template_id;   // id within its class (global, not shard-local)
-  int32_t class_slot;    // unused on device; slot is taken from the per-call class_slot table
-  int32_t pad;
-};
-
-struct TemplateLevelInfo {  // per (g, level)
-  int32_t width, height;    // of template l*M+0 (upstream uses tp[start] for the refinement clamp)
-  int32_t nf_total;         // sum over modalities of features.size() at this level
-  int32_t positions;        // template_positions at this level (only the coarsest is used)
-};
-
-struct ScoreInfo {           // per shard-local template: everything k_score_coarse_u8 needs, one 16-byte scalar load
-  int32_t positions;        // template_positions at the coarsest level
-  int32_t nf_total;         // features at the coarsest level, all modalities
-  int32_t class_index;
-  uint32_t groups;          // fast groups | all groups << 8 of the unified table row | blocks of the scalar-block row << 16
-};
 
 struct DeviceBankView {
   int32_t G;                        // templates in this shard

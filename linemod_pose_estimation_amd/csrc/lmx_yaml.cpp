@@ -474,13 +474,11 @@ lmx_status yaml_save(const lmx_bank* bank, const char* path) {
     for (int t = 0; t < cd.n_pyramids; ++t) {
       std::fprintf(f, "         -\n            template_id: %d\n            templates:\n", t);
       for (int k = 0; k < per; ++k) {
-        const int32_t* tm = &cd.templates[((size_t)t * per + k) * 5];
+        const TemplateRow tm = template_row(cd, per, t, k);
         std::fprintf(f, "               -\n                  width: %d\n                  height: %d\n                  pyramid_level: %d\n                  features:\n",
-                     tm[0], tm[1], tm[2]);
-        for (int i = 0; i < tm[4]; ++i) {
-          const int32_t* ft = &cd.features[((size_t)tm[3] + i) * 3];
-          std::fprintf(f, "                     - [ %d, %d, %d ]\n", ft[0], ft[1], ft[2]);
-        }
+                     tm.width, tm.height, tm.level);
+        const int32_t* ft = template_features(cd, tm);
+        for (int i = 0; i < tm.feat_count; ++i, ft += 3) std::fprintf(f, "                     - [ %d, %d, %d ]\n", ft[0], ft[1], ft[2]);
       }
     }
   }

@@ -249,6 +249,16 @@ class NativeBank:
             bank.classes.append((cid.decode(), templates, np.concatenate(feats, 0) if feats else np.zeros((0, 3), np.int32)))
         return bank
 
+    def debug_tables(self, table, width, height, max_batch=1, shard_rank=0, shard_world=1, ls_flat=False):
+        """Test hook (lmx_debug_bank_tables), no device needed: -> (bytes of table `table` (_lib.LMX_TAB_*) as a context with these
+        parameters would upload it, as a uint8 array; the library's FNV-1a 64 of them)."""
+        n, h = C.c_size_t(), C.c_uint64()
+        args = (self.h, width, height, max_batch, shard_rank, shard_world, 1 if ls_flat else 0, table)
+        _lib.check(_lib.lib().lmx_debug_bank_tables(*args, None, 0, C.byref(n), None))
+        out = np.empty(n.value, np.uint8)
+        _lib.check(_lib.lib().lmx_debug_bank_tables(*args, out.ctypes.data, out.nbytes, C.byref(n), C.byref(h)))
+        return out, h.value
+
     def class_ids(self):
         L = _lib.lib()
         return [L.lmx_bank_class_id(self.h, i).decode() for i in range(L.lmx_bank_num_classes(self.h))]

@@ -510,3 +510,90 @@ def pre_special_frames(SW, SH, seed):
     table, n_even, n_odd = pre_depth_special_values()
     z = table[(np.arange(SH)[:, None] * SW + np.arange(SW)[None, :]) % len(table)]
     return np.ascontiguousarray(bgr), np.ascontiguousarray(z), table, n_even, n_odd
+
+
+# ---- the device bank's tables (csrc/lmx_bank_tables.hpp), from the bank's flat arrays ----------------------------------------
+# What the scoring and refinement kernels are told about a bank, restated from the formats' documentation with whole-array numpy:
+# tests/test_bank_tables.py decodes the library's tables (lmx_debug_bank_tables) and compares them with these.  `g` is one pyramid
+# level's geometry as a dict of the LevelGeom fields (GEOM_FIELDS, the order of the hook's summary words).
+GEOM_FIELDS = ("W", "H", "T", "Wc", "Hc", "cells", "ori_stride", "mod_stride", "zero_off", "nib_ori_stride", "nib_mod_stride", "nib_zero_off",
+               "ls_stride", "ls_zero_off", "ls_bands", "ls_band_stride")
+FEAT_STRIDE, SB_GROUPS, SB_BLOCK, SB_MAX_BLOCKS = 64, 5, 16, 6
+NONE = np.int64(1) << 40   # "no entry" in a padded multiset: above every 32-bit table entry, so it sorts last
+
+
+def shard_features(bank, rank, world):
+    """The templates shard `rank` of `world` holds, classes in key order, as padded arrays: class_index, template_id [G]; wh [G, L, 2];
+    count [L, G, M]; x, y, label, valid [L, G, M, 64] (valid = the feature exists)."""
+    L, M = len(bank.T), len(bank.modalities)
+    ranges = bank.shard(rank, world)
+    ci_all, tid_all, wh_all, per_level = [], [], [], [[] for _ in range(L)]
+    for ci, (cid, t, f) in enumerate(sorted(bank.classes, key=lambda c: c[0])):
+        b, e = ranges[cid]
+        t = np.asarray(t, np.int64).reshape(-1, L * M, 5)[b:e]
+        f = np.concatenate([np.asarray(f, np.int64).reshape(-1, 3), np.zeros((1, 3), np.int64)])   # the last row stands for "no feature"
+        ci_all.append(np.full(e - b, ci)); tid_all.append(np.arange(b, e)); wh_all.append(t[:, ::M, :2])
+        for l in range(L):
+            rows = t[:, l * M:(l + 1) * M]
+            valid = np.arange(FEAT_STRIDE) < rows[..., 4, None]
+            per_level[l].append((f[np.where(valid, rows[..., 3, None] + np.arange(FEAT_STRIDE), len(f) - 1)], valid, rows[..., 4]))
+    cat = lambda parts, shape: np.concatenate(parts) if parts else np.zeros(shape, np.int64)
+    ff = np.stack([cat([p[0] for p in lv], (0, M, FEAT_STRIDE, 3)) for lv in per_level])
+    return dict(class_index=cat(ci_all, (0,)), template_id=cat(tid_all, (0,)), wh=cat(wh_all, (0, L, 2)), x=ff[..., 0], y=ff[..., 1], label=ff[..., 2],
+                valid=np.stack([cat([p[1] for p in lv], (0, M, FEAT_STRIDE)) for lv in per_level]).astype(bool),
+                count=np.stack([cat([p[2] for p in lv], (0, M)) for lv in per_level]))
+
+
+def linear_index(g, x, y):
+    """accessLinearMemory: the element of a feature at (x, y) in one orientation's [T * T][Hc * Wc] linear memories, placement 0."""
+    T = g["T"]
+    return ((y % T) * T + x % T) * g["cells"] + (y // T) * g["Wc"] + x // T
+
+
+def template_positions(g, w, h):
+    """Placements of a w x h template on the level's grid of cells (C++ integer division: a width of 0 spans one cell)."""
+    wf, hf = np.where(w > 0, (w - 1) // g["T"] + 1, 1), np.where(h > 0, (h - 1) // g["T"] + 1, 1)
+    return np.maximum(0, (g["Hc"] - hf) * g["Wc"] + (g["Wc"] - wf) + 1)
+
+
+def coarse_address(g, x, y, label, valid):
+    """Where the scoring kernels read a coarsest-level feature in ONE modality's nibble-packed memories (two elements per byte, orientation
+    blocks nib_ori_stride apart): -> (byte offset of the aligned dword that holds element e0, nibble of e0 inside it).  A feature outside the
+    image (upstream similarity() skips it) and every padding entry point at the block's zero run, nibble 0."""
+    e0 = linear_index(g, x, y)
+    inside = valid & (x < g["W"]) & (y < g["H"])
+    return np.where(inside, label * g["nib_ori_stride"] + 4 * (e0 // 8), g["nib_zero_off"] // 4 * 4), np.where(inside, e0 % 8, 0)
+
+
+def feat_entries(g, x, y, label, valid, count):
+    """k_refine's rows [.., 64] as (off, x, y): label << 29 over the flat element index, or over row << 12 | column of the banded image's
+    matrix (row = grid * Hc + cell row); padding = the level's zero run, and entry 63's y = the row's feature count."""
+    T = g["T"]
+    low = (((y % T) * T + x % T) * g["Hc"] + y // T) << 12 | x // T if g["ls_bands"] else linear_index(g, x, y)
+    off = np.where(valid, label << 29 | low, g["ls_zero_off"])
+    ex, ey = np.where(valid, x, 0), np.where(valid, y, 0)
+    ey[..., FEAT_STRIDE - 1] = count
+    return off, ex, ey
+
+
+def coarse_group_plan(nibble, valid):
+    """How a template's coarsest-level features (nibble [G, n], valid [G, n]: all modalities) form groups of three.  Full triples of one
+    nibble class come first, taken round robin over the classes 0..7; then one group per class that has leftovers, in class order.
+    -> n_fast [G]; group_class, group_real [G, 30] (-1 / 0 behind the template's groups); n_groups [G]."""
+    G = nibble.shape[0]
+    cnt = np.stack([(valid & (nibble == k)).sum(1) for k in range(8)], 1)
+    full, left = cnt // 3, cnt % 3
+    cap = SB_GROUPS * SB_MAX_BLOCKS + 8
+    group_class, group_real, n = np.full((G, cap), -1), np.zeros((G, cap), np.int64), np.zeros(G, np.int64)
+    rows = np.arange(G)
+    for r in range(int(full.max()) if G else 0):
+        for k in range(8):
+            sel = full[:, k] > r
+            group_class[rows[sel], n[sel]] = k; group_real[rows[sel], n[sel]] = 3
+            n += sel
+    n_fast = n.copy()
+    for k in range(8):
+        sel = left[:, k] > 0
+        group_class[rows[sel], n[sel]] = k; group_real[rows[sel], n[sel]] = left[sel, k]
+        n += sel
+    return n_fast, group_class, group_real, n

@@ -699,6 +699,42 @@ def test_host_frames_pipelined_fresh_frames_every_step(mode):
         arena.close()
 
 
+@pytest.mark.parametrize("mode", ["default", "no_store_upload", "pinned_async", "pinned_dma"])
+def test_upload_delivers_the_callers_pixels(mode, monkeypatch):
+    """Every host path of lmx_ctx_upload moves exactly the caller's pixels: upload, upload_wait, then level 0's colour and depth of every
+    frame read back -- no enqueue.  128 x 128 frames (H / 64 = 2 row bands per image below 8 frames, whole images from 8 on), max_batch 9,
+    odd frames with 12 bytes of row padding; 1, 2 frames take the direct store in the default context, 3, 7 the staging in row bands, 8, 9
+    in whole images; LMX_NO_STORE_UPLOAD stages the small batches too; pinned sources are pulled by a kernel (LMX_CTX_ASYNC_INPUT) or
+    copied image by image (LMX_PINNED_MODE=dma)."""
+    from linemod_pose_estimation_amd import PinnedArena
+    W = H = 128
+    bank = synth.make_bank(4, modalities=("ColorGradient", "DepthNormal"), T=(4, 8), seed=5, size_range=(20.0, 40.0))
+    if mode == "no_store_upload":
+        monkeypatch.setenv("LMX_NO_STORE_UPLOAD", "1")
+    if mode == "pinned_dma":
+        monkeypatch.setenv("LMX_PINNED_MODE", "dma")
+    arena = PinnedArena(6 * 9 * ((W * 3 + 12) * H + (W * 2 + 12) * H + 512)) if mode.startswith("pinned") else None
+    det = Detector(bank, W, H, max_batch=9, async_input=(mode == "pinned_async"))
+    rng = np.random.default_rng(77)
+    for n_frames in (1, 2, 3, 7, 8, 9):
+        frames = []
+        for f in range(n_frames):
+            pad = f % 2   # colour rows 4 pixels, depth rows 6 pixels longer than the image: 12 bytes each
+            colour, depth = rng.integers(0, 256, (H, W + 4 * pad, 3), dtype=np.uint8), rng.integers(0, 65536, (H, W + 6 * pad), dtype=np.uint16)
+            if arena is not None:
+                colour, depth = arena.put(colour), arena.put(depth)
+            frames.append([colour[:, :W], depth[:, :W]])
+            assert frames[f][0].strides[0] == W * 3 + 12 * pad and frames[f][1].strides[0] == W * 2 + 12 * pad
+        det.upload(frames)
+        det.upload_wait()
+        for f in range(n_frames):
+            assert np.array_equal(det.debug_pyramid_bgr(f, 0, 0), frames[f][0]), (n_frames, f)
+            assert np.array_equal(det.debug_depth(f, 1), frames[f][1]), (n_frames, f)
+    det.close()
+    if arena is not None:
+        arena.close()
+
+
 def test_overlapped_lanes_give_identical_results():
     """LMX_CTX_OVERLAP: the two output slots run on two streams with their own intermediate buffers.  Different thresholds,
     batch sizes and a class-filter change in flight, re-uploads between rounds, stage read-back after an enqueue on either
