@@ -454,6 +454,17 @@ typedef struct lmx_cluster_t {
 lmx_status lmx_cluster_matches(const lmx_match_t* matches, size_t n_matches, const double* obj_origin_dists, const int32_t* rects,
                                size_t n_templates, const lmx_cluster_params* params, lmx_cluster_t* clusters, size_t cap_clusters,
                                size_t* n_clusters, int32_t* members, size_t cap_members);
+/* As lmx_cluster_matches, but a cluster's score is the mean of match_values[i] over its members (in voting order) instead of the mean
+ * similarity: with match_values[i] = (double)matches[i].similarity the two are equal bit for bit.  This is the slot of the reference's
+ * second cluster score, getClusterScore over depth_normal_diff_calc (src/rgbdDetector.cpp:147-282, 576-584; commented out at both call
+ * sites, :109-112 and :123-126, for its cost), with the normal term left out: that score is 1 / exp(mean depth difference in metres), exp is monotonic, so
+ * match_values[i] = -(double)sum_abs_mm / (n_valid * 1000.0) of lmx_depth_diff_matches ranks the clusters in the same order.  A match
+ * with n_valid == 0 has no such value; what it gets is the caller's choice (-HUGE_VAL sends every cluster that holds one to the end:
+ * the Python helper's choice; leaving such matches out before the call is the other).  A cluster whose mean is NaN is refused
+ * (LMX_ERR_INVALID_ARG): the score order would be undefined. */
+lmx_status lmx_cluster_matches_scored(const lmx_match_t* matches, size_t n_matches, const double* match_values, const double* obj_origin_dists,
+                                      const int32_t* rects, size_t n_templates, const lmx_cluster_params* params, lmx_cluster_t* clusters,
+                                      size_t cap_clusters, size_t* n_clusters, int32_t* members, size_t cap_members);
 
 /* The renderer-params side-car that the consumer chain reads next to the matches: `<object>_renderer_params.yml`, written by the
  * reference's trainers (writeLinemodTemplateParams, src/renderer.cpp:72-130) and read by readLinemodTemplateParams
@@ -521,6 +532,43 @@ lmx_status lmx_mesh_render(int32_t device, const double* triangles /*[n][3][3] m
 lmx_status lmx_bank_train_mesh(lmx_bank* bank, int32_t device, const double* triangles, int32_t n_triangles, const lmx_mesh_camera* cam,
                                const lmx_mesh_view* views, int32_t n_views, const char* class_id,
                                int32_t* template_ids /*[n_views], -1 = rejected; may be NULL*/, lmx_renderer_params** side_car /*may be NULL*/);
+
+/* ---- depth check of matches against the rendered depth of their templates ------------------------------------------------------------
+ * The depth half of the reference's depth_normal_diff_calc (src/rgbdDetector.cpp:147-282): lay the template's rendered depth over the
+ * scene depth at the match position and average the absolute difference where both are valid.  Upstream re-renders the view per match;
+ * a template's view never changes, so here the renders are made ONCE, cropped to their silhouette boxes and kept on the device
+ * (lmx_depth_templates), and each match of a frame costs one pass over its crop (csrc/lmx_verify.hip, k_depth_diff: one workgroup per
+ * match).  Definition (csrc/lmx_depth_verify.hpp), for a crop t[h][w], a scene s[H][W] (both uint16 mm, 0 = not on the object / no
+ * measurement) and a match at (x, y), any int32: crop pixel (i, j) meets scene pixel (x + j, y + i); it counts iff t != 0, the scene
+ * pixel lies inside the image and s != 0.
+ *   n_template = crop pixels with t != 0;  n_valid = counting pixels;  sum_abs_mm = sum of |t - s| over them.
+ * Mean difference in mm = sum_abs_mm / n_valid; n_valid == 0 (nothing to compare, e.g. a crop entirely outside the image) is reported
+ * as such.  Deviations from the reference: no vertical flip of the render, pixels outside the scene are skipped instead of
+ * asserting, the difference is the signed one made absolute, and no 0 / 0.
+ * The object owns a non-blocking stream and the buffers the scene frames, the match list and the results pass through (they grow on
+ * demand); a mutex serialises calls on one object.  An object without any crop pixel touches no device until a call needs one. */
+typedef struct lmx_depth_templates lmx_depth_templates;
+typedef struct lmx_depth_diff_t { int64_t sum_abs_mm; int32_t n_valid; int32_t n_template; } lmx_depth_diff_t;
+/* views[i] is template i's view (for a bank from lmx_bank_train_mesh: side_car->R[i], side_car->T[i][2]).  Renders on the device in
+ * batches and keeps each view's silhouette box of the depth; a view that covers no pixel yields a 0 x 0 crop; a view with a vertex at
+ * Z <= 0.01 fails the whole call (LMX_ERR_INVALID_ARG, the text names the view) before any device work. */
+lmx_status lmx_depth_templates_from_mesh(int32_t device, const double* triangles, int32_t n_triangles, const lmx_mesh_camera* cam,
+                                         const lmx_mesh_view* views, int32_t n_views, lmx_depth_templates** out);
+/* ready-made crops (e.g. from the reference's own OpenGL trainer): crops[i] is [sizes[2i+1]][sizes[2i]] uint16, dense rows; sides
+ * 0 .. 16384; a crop with a side of 0 is empty (kept as 0 x 0, its pointer is not read) */
+lmx_status lmx_depth_templates_from_crops(int32_t device, const uint16_t* const* crops, const int32_t* sizes, int32_t n, lmx_depth_templates** out);
+int32_t    lmx_depth_templates_count(const lmx_depth_templates* templates);
+lmx_status lmx_depth_templates_rect(const lmx_depth_templates* templates, int32_t id, int32_t rect[4]);   /* from_mesh: silhouette box; from_crops: {0,0,w,h} */
+lmx_status lmx_depth_templates_get(const lmx_depth_templates* templates, int32_t id, uint16_t* out /*[h][w]*/);  /* reads the crop back from the device */
+/* bytes of device memory the templates occupy: the crops, rows padded to 16 bytes, and 24 bytes of table per template.  Not n x W x H.
+ * The per-call buffers (scene frames, match list, results) are not counted. */
+size_t     lmx_depth_templates_device_bytes(const lmx_depth_templates* templates);
+void       lmx_depth_templates_free(lmx_depth_templates* templates);
+/* depth[f]: 16-bit one-channel host images, all of one size, any row stride.  Frame f's matches are matches[offsets[f] .. offsets[f+1])
+ * (offsets[0] == 0, non-decreasing).  class_index >= 0: matches of other classes get {0, 0, 0} and their template ids are not looked at.
+ * out[i] belongs to matches[i].  A template_id outside [0, count) fails the call before any launch; the text names the match. */
+lmx_status lmx_depth_diff_matches(lmx_depth_templates* templates, const lmx_image* depth, int32_t n_frames, const lmx_match_t* matches,
+                                  const size_t* offsets, int32_t class_index, lmx_depth_diff_t* out);
 
 /* ---- introspection (stage-level parity tests, profiling) ------------------------------------------------- */
 enum {

@@ -12,10 +12,12 @@
 // With LMX_HAVE_OPENCV defined, overloads taking cv::Mat are provided (the only place OpenCV types appear).
 #pragma once
 
+#include <cmath>
 #include <cstring>
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "lmx.h"
@@ -220,6 +222,72 @@ class Detector {
   int device_ = 0, max_batch_ = 1, max_candidates_ = 0, w_[2] = {0, 0}, h_[2] = {0, 0};
   void* stream_ = nullptr;
   std::vector<lmx_match_t> buf_;
+};
+
+// Device-resident depth renders of a bank's templates and the depth check of matches against them (lmx_depth_templates_*,
+// lmx_depth_diff_matches): the depth half of rgbdDetector::depth_normal_diff_calc (src/rgbdDetector.cpp:147-282) without its per-match
+// re-render.  Template ids are the bank's: with fromMesh, views[i] is template i's view (side_car->R[i], side_car->T[i][2] of
+// Detector::addTemplatesFromMesh).
+class DepthTemplates {
+ public:
+  DepthTemplates() {}
+  ~DepthTemplates() { reset(); }
+  DepthTemplates(const DepthTemplates&) = delete;
+  DepthTemplates& operator=(const DepthTemplates&) = delete;
+  DepthTemplates(DepthTemplates&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+  DepthTemplates& operator=(DepthTemplates&& o) noexcept {
+    if (this != &o) { reset(); h_ = o.h_; o.h_ = nullptr; }
+    return *this;
+  }
+
+  void fromMesh(const std::vector<double>& triangles, const lmx_mesh_camera& camera, const std::vector<lmx_mesh_view>& views, int device = 0) {
+    if (triangles.size() % 9 != 0) throw Exception(LMX_ERR_SHAPE, "DepthTemplates::fromMesh: triangles must hold 9 doubles per triangle");
+    reset();
+    check(lmx_depth_templates_from_mesh(device, triangles.data(), (int32_t)(triangles.size() / 9), &camera, views.data(), (int32_t)views.size(), &h_));
+  }
+  // crops[i]: sizes[i].first x sizes[i].second (width x height) uint16 millimetres, dense rows, 0 = not on the object
+  void fromCrops(const std::vector<const uint16_t*>& crops, const std::vector<std::pair<int, int> >& sizes, int device = 0) {
+    if (crops.size() != sizes.size()) throw Exception(LMX_ERR_SHAPE, "DepthTemplates::fromCrops: one size per crop");
+    std::vector<int32_t> wh;
+    for (const std::pair<int, int>& s : sizes) { wh.push_back(s.first); wh.push_back(s.second); }
+    reset();
+    check(lmx_depth_templates_from_crops(device, crops.data(), wh.data(), (int32_t)crops.size(), &h_));
+  }
+  int count() const { return lmx_depth_templates_count(h_); }
+  size_t deviceBytes() const { return lmx_depth_templates_device_bytes(h_); }
+
+  // One frame: out[i] belongs to matches[i] ({sum_abs_mm, n_valid, n_template}; mean difference in mm = sum_abs_mm / n_valid).
+  // class_index >= 0: only that class's matches are looked at, the others get zeros.
+  std::vector<lmx_depth_diff_t> diff(const Image& depth, const std::vector<lmx_match_t>& matches, int class_index = -1) {
+    std::vector<lmx_depth_diff_t> out(matches.size());
+    const lmx_image img = depth.c();
+    const size_t offsets[2] = {0, matches.size()};
+    check(lmx_depth_diff_matches(h_, &img, 1, matches.data(), offsets, class_index, out.data()));
+    return out;
+  }
+  // A batch: frame f's matches are matches[offsets[f] .. offsets[f + 1]).
+  std::vector<lmx_depth_diff_t> diff(const std::vector<Image>& depth, const std::vector<lmx_match_t>& matches, const std::vector<size_t>& offsets,
+                                     int class_index = -1) {
+    if (offsets.size() != depth.size() + 1 || offsets.back() != matches.size()) throw Exception(LMX_ERR_SHAPE, "DepthTemplates::diff: offsets must hold one entry per frame plus one and end at matches.size()");
+    std::vector<lmx_image> imgs;
+    for (const Image& d : depth) imgs.push_back(d.c());
+    std::vector<lmx_depth_diff_t> out(matches.size());
+    check(lmx_depth_diff_matches(h_, imgs.data(), (int32_t)imgs.size(), matches.data(), offsets.data(), class_index, out.data()));
+    return out;
+  }
+  // The value lmx_cluster_matches_scored ranks by: minus the mean difference in metres (-HUGE_VAL when nothing could be compared).
+  static double value(const lmx_depth_diff_t& d) {
+    return d.n_valid > 0 ? -(double)d.sum_abs_mm / (d.n_valid * 1000.0) : -HUGE_VAL;
+  }
+
+  lmx_depth_templates* handle() const { return h_; }
+
+ private:
+  void reset() {
+    if (h_) lmx_depth_templates_free(h_);
+    h_ = nullptr;
+  }
+  lmx_depth_templates* h_ = nullptr;
 };
 
 // The reference's readLinemod (src/rgbdDetector.cpp:1668-1680) with the same shape.

@@ -21,6 +21,8 @@ SYMBOLS = [
     "lmx_ctx_collect", "lmx_ctx_collect_flat", "lmx_ctx_raw_matches", "lmx_merge_raw", "lmx_ctx_export_raw", "lmx_ctx_export_raw_on", "lmx_ctx_release", "lmx_ctx_max_outstanding", "lmx_stream_copy", "lmx_stream_copy_blocks", "lmx_merge_gathered", "lmx_ctx_sync", "lmx_renderer_params_load", "lmx_renderer_params_save", "lmx_renderer_params_free", "lmx_cluster_matches", "lmx_ctx_set_cluster_sidecar", "lmx_ctx_collect_clusters", "lmx_ctx_debug_read", "lmx_debug_orientation_labels", "lmx_debug_depth_normal_bins", "lmx_debug_introsort_perm", "lmx_debug_introsort_perm_score", "lmx_debug_device_sort_perm", "lmx_debug_device_finalize_cluster", "lmx_debug_bank_tables", "lmx_ctx_stats",
     "lmx_num_kernels", "lmx_kernel_name", "lmx_ctx_device_kernel_name", "lmx_ctx_set_profiling", "lmx_ctx_kernel_time", "lmx_ctx_reset_profiling",
     "lmx_ctx_algorithmic_bytes", "lmx_last_error", "lmx_version",
+    "lmx_cluster_matches_scored", "lmx_depth_templates_from_mesh", "lmx_depth_templates_from_crops", "lmx_depth_templates_count", "lmx_depth_templates_rect",
+    "lmx_depth_templates_get", "lmx_depth_templates_device_bytes", "lmx_depth_templates_free", "lmx_depth_diff_matches",
 ]
 
 (LMX_OK, LMX_ERR_INVALID_ARG, LMX_ERR_SHAPE, LMX_ERR_NO_DEVICE, LMX_ERR_HIP, LMX_ERR_OVERFLOW, LMX_ERR_IO,
@@ -77,6 +79,10 @@ class MeshCamera(C.Structure):
 
 class MeshView(C.Structure):
     _fields_ = [("R", C.c_double * 9), ("distance", C.c_double)]
+
+
+class DepthDiff(C.Structure):
+    _fields_ = [("sum_abs_mm", C.c_int64), ("n_valid", C.c_int32), ("n_template", C.c_int32)]
 
 
 class GroupDesc(C.Structure):
@@ -234,6 +240,18 @@ def lib():
     L.lmx_renderer_params_free.restype = None
     L.lmx_cluster_matches.argtypes = [vp, C.c_size_t, vp, vp, C.c_size_t, C.POINTER(ClusterParams), vp, C.c_size_t,
                                       C.POINTER(C.c_size_t), vp, C.c_size_t]
+    L.lmx_cluster_matches_scored.argtypes = [vp, C.c_size_t, vp, vp, vp, C.c_size_t, C.POINTER(ClusterParams), vp, C.c_size_t,
+                                             C.POINTER(C.c_size_t), vp, C.c_size_t]
+    L.lmx_depth_templates_from_mesh.argtypes = [C.c_int32, vp, C.c_int32, C.POINTER(MeshCamera), C.POINTER(MeshView), C.c_int32, C.POINTER(vp)]
+    L.lmx_depth_templates_from_crops.argtypes = [C.c_int32, C.POINTER(vp), i32p, C.c_int32, C.POINTER(vp)]
+    L.lmx_depth_templates_count.argtypes = [vp]
+    L.lmx_depth_templates_rect.argtypes = [vp, C.c_int32, i32p]
+    L.lmx_depth_templates_get.argtypes = [vp, C.c_int32, vp]
+    L.lmx_depth_templates_device_bytes.argtypes = [vp]
+    L.lmx_depth_templates_device_bytes.restype = C.c_size_t
+    L.lmx_depth_templates_free.argtypes = [vp]
+    L.lmx_depth_templates_free.restype = None
+    L.lmx_depth_diff_matches.argtypes = [vp, C.POINTER(Image), C.c_int32, vp, C.POINTER(C.c_size_t), C.c_int32, vp]
     L.lmx_ctx_set_cluster_sidecar.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(ClusterParams)]
     L.lmx_ctx_collect_clusters.argtypes = [vp, C.c_int32, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t), vp, C.c_size_t]
     L.lmx_ctx_debug_read.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_size_t]

@@ -62,14 +62,14 @@ float box_overlap_ratio(const int* p, const int* q) {
   const float total = (float)wadd(wmul(p[2], p[3]), wmul(q[2], q[3])) - shared;
   return shared / total;
 }
-}  // namespace
 
-extern "C" lmx_status lmx_cluster_matches(const lmx_match_t* matches, size_t n_matches, const double* obj_origin_dists, const int32_t* rects,
-                                          size_t n_templates, const lmx_cluster_params* pp, lmx_cluster_t* clusters, size_t cap_clusters,
-                                          size_t* n_clusters, int32_t* members, size_t cap_members) {
-  return lmx::guarded("lmx_cluster_matches", [&]() -> lmx_status {
+// The chain behind lmx_cluster_matches and lmx_cluster_matches_scored.  match_values: what a cluster's score is the mean of, per match; null =
+// the matches' similarities (cluster_scoring's similarity_score_calc).
+lmx_status cluster_chain(const char* what, const lmx_match_t* matches, size_t n_matches, const double* match_values, const double* obj_origin_dists,
+                         const int32_t* rects, size_t n_templates, const lmx_cluster_params* pp, lmx_cluster_t* clusters, size_t cap_clusters,
+                         size_t* n_clusters, int32_t* members, size_t cap_members) {
   if ((n_matches && !matches) || !obj_origin_dists || !rects || !pp || !n_clusters || (cap_clusters && !clusters) || (cap_members && !members)) {
-    lmx::set_error("lmx_cluster_matches: null argument");
+    lmx::set_error("%s: null argument", what);
     return LMX_ERR_INVALID_ARG;
   }
   if (pp->vote_row_col_step <= 0) { lmx::set_error("vote_row_col_step must be positive"); return LMX_ERR_INVALID_ARG; }
@@ -96,8 +96,10 @@ extern "C" lmx_status lmx_cluster_matches(const lmx_match_t* matches, size_t n_m
     c.index = it->first;
     double sum_score = 0.0;
     int num = 0;
-    for (int32_t mi : it->second) { sum_score += matches[mi].similarity; num++; }
+    for (int32_t mi : it->second) { sum_score += match_values ? match_values[mi] : matches[mi].similarity; num++; }
     c.score = sum_score / num;
+    // only the caller's values are refused: lmx_cluster_matches passes a NaN similarity on, as k_f2_finalize_cluster does
+    if (match_values && std::isnan(c.score)) { lmx::set_error("%s: the mean value of cluster {%d, %d, %d} is not a number", what, c.index[0], c.index[1], c.index[2]); return LMX_ERR_INVALID_ARG; }
     c.members = it->second;
     cd.push_back(c);
   }
@@ -144,5 +146,26 @@ extern "C" lmx_status lmx_cluster_matches(const lmx_match_t* matches, size_t n_m
   *n_clusters = nc;
   if (st != LMX_OK) lmx::set_error("%zu clusters / %zu members exceed the output capacity", nc, nm);
   return st;
+}
+}  // namespace
+
+extern "C" lmx_status lmx_cluster_matches(const lmx_match_t* matches, size_t n_matches, const double* obj_origin_dists, const int32_t* rects,
+                                          size_t n_templates, const lmx_cluster_params* pp, lmx_cluster_t* clusters, size_t cap_clusters,
+                                          size_t* n_clusters, int32_t* members, size_t cap_members) {
+  return lmx::guarded("lmx_cluster_matches", [&]() -> lmx_status {
+    return cluster_chain("lmx_cluster_matches", matches, n_matches, nullptr, obj_origin_dists, rects, n_templates, pp, clusters, cap_clusters, n_clusters,
+                         members, cap_members);
+  });
+}
+
+// The reference's other cluster score (cluster_scoring over depth_normal_diff_calc, src/rgbdDetector.cpp:118-144, 147-282): the mean of a
+// per-match value the caller computed, e.g. from lmx_depth_diff_matches.
+extern "C" lmx_status lmx_cluster_matches_scored(const lmx_match_t* matches, size_t n_matches, const double* match_values, const double* obj_origin_dists,
+                                                 const int32_t* rects, size_t n_templates, const lmx_cluster_params* pp, lmx_cluster_t* clusters,
+                                                 size_t cap_clusters, size_t* n_clusters, int32_t* members, size_t cap_members) {
+  return lmx::guarded("lmx_cluster_matches_scored", [&]() -> lmx_status {
+    if (n_matches && !match_values) { lmx::set_error("lmx_cluster_matches_scored: null argument"); return LMX_ERR_INVALID_ARG; }
+    return cluster_chain("lmx_cluster_matches_scored", matches, n_matches, match_values, obj_origin_dists, rects, n_templates, pp, clusters, cap_clusters,
+                         n_clusters, members, cap_members);
   });
 }

@@ -617,6 +617,130 @@ def cluster_matches(matches, obj_origin_dists, rects, vote_row_col_step, rendere
     return clusters[:n.value].copy(), members
 
 
+def cluster_matches_scored(matches, match_values, obj_origin_dists, rects, vote_row_col_step, renderer_radius_min, renderer_radius_step, cluster_size_thresh=2):
+    """lmx_cluster_matches_scored: `cluster_matches` with a cluster's score = the mean of match_values over its members instead of the mean
+    similarity (the slot of the reference's depth_normal_diff_calc score; feed it `depth_values(DepthTemplates.diff(...))`).  With
+    match_values = matches["similarity"] it equals cluster_matches bit for bit.  Returns (clusters, members)."""
+    matches = np.ascontiguousarray(matches, MATCH_DTYPE)
+    values = np.ascontiguousarray(match_values, np.float64)
+    if values.shape != (len(matches),):
+        raise ValueError("match_values must hold one value per match")
+    dists = np.ascontiguousarray(obj_origin_dists, np.float64)
+    rects = np.ascontiguousarray(rects, np.int32).reshape(-1, 4)
+    pp = _lib.ClusterParams(int(vote_row_col_step), float(renderer_radius_min), float(renderer_radius_step), int(cluster_size_thresh))
+    clusters = np.zeros(max(1, len(matches)), CLUSTER_DTYPE)
+    members = np.zeros(max(1, len(matches)), np.int32)
+    n = C.c_size_t()
+    _lib.check(_lib.lib().lmx_cluster_matches_scored(matches.ctypes.data, len(matches), values.ctypes.data, dists.ctypes.data, rects.ctypes.data, len(dists),
+                                                     C.byref(pp), clusters.ctypes.data, len(clusters), C.byref(n), members.ctypes.data, len(members)))
+    return clusters[:n.value].copy(), members
+
+
+DEPTH_DIFF_DTYPE = np.dtype([("sum_abs_mm", "<i8"), ("n_valid", "<i4"), ("n_template", "<i4")])
+
+
+def depth_values(diffs):
+    """Per-match values for cluster_matches_scored from DepthTemplates.diff results: minus the mean absolute depth difference in metres,
+    -(sum_abs_mm / (n_valid * 1000)).  The reference's getClusterScore (src/rgbdDetector.cpp:576-584) is 1 / exp(mean difference in m) with
+    the normal term left out; exp is monotonic, so clusters rank the same.  A match with n_valid == 0 (nothing to compare) gets -inf:
+    a cluster that holds one goes to the end."""
+    diffs = np.asarray(diffs, DEPTH_DIFF_DTYPE)
+    out = np.full(len(diffs), -np.inf)
+    ok = diffs["n_valid"] > 0
+    out[ok] = -(diffs["sum_abs_mm"][ok].astype(np.float64) / (diffs["n_valid"][ok].astype(np.float64) * 1000.0))
+    return out
+
+
+class DepthTemplates:
+    """Device-resident depth renders of a bank's templates, cropped to their silhouette boxes (lmx_depth_templates), and the depth check
+    of matches against them (lmx_depth_diff_matches): the depth half of the reference's depth_normal_diff_calc
+    (src/rgbdDetector.cpp:147-282) without the per-match re-render."""
+
+    def __init__(self, handle):
+        self.h = C.c_void_p(handle)
+
+    @classmethod
+    def from_mesh(cls, triangles, views, width, height, fx, fy, cx=None, cy=None, light=MESH_LIGHT, device=0):
+        """One template per (R, distance) of `views`, in order: for a bank from NativeBank.train_mesh, zip(last_side_car["R"],
+        last_side_car["T"][:, 2]).  Any iterable of pairs."""
+        views = list(views)
+        tri, cam, packed = _mesh_args(triangles, views, width, height, fx, fy, cx, cy, light)
+        h = C.c_void_p()
+        _lib.check(_lib.lib().lmx_depth_templates_from_mesh(device, tri.ctypes.data, tri.shape[0], C.byref(cam), packed.ctypes.data_as(C.POINTER(_lib.MeshView)),
+                                                            len(views), C.byref(h)))
+        return cls(h.value)
+
+    @classmethod
+    def from_crops(cls, crops, device=0):
+        """Ready-made crops: a list of uint16 [h, w] arrays (0 = not on the object); empty arrays are allowed."""
+        keep = []
+        for c in crops:
+            c = np.ascontiguousarray(c, np.uint16)
+            if c.ndim != 2:
+                raise TypeError("a crop must be a uint16 [h, w] array")
+            keep.append(c)
+        n = len(keep)
+        ptrs = (C.c_void_p * max(1, n))(*[c.ctypes.data if c.size else None for c in keep])
+        sizes = (C.c_int32 * max(2, 2 * n))(*[v for c in keep for v in (c.shape[1], c.shape[0])])
+        h = C.c_void_p()
+        _lib.check(_lib.lib().lmx_depth_templates_from_crops(device, ptrs, sizes, n, C.byref(h)))
+        return cls(h.value)
+
+    def __len__(self):
+        return int(_lib.lib().lmx_depth_templates_count(self.h))
+
+    def rect(self, i):
+        """(x, y, w, h): from_mesh: the silhouette box in the rendered view; from_crops: (0, 0, w, h)."""
+        r = (C.c_int32 * 4)()
+        _lib.check(_lib.lib().lmx_depth_templates_rect(self.h, int(i), r))
+        return tuple(r)
+
+    def crop(self, i):
+        """Template i's crop, read back from the device: uint16 [h, w]."""
+        _, _, w, h = self.rect(i)
+        out = np.zeros((h, w), np.uint16)
+        _lib.check(_lib.lib().lmx_depth_templates_get(self.h, int(i), out.ctypes.data))
+        return out
+
+    @property
+    def device_bytes(self):
+        return int(_lib.lib().lmx_depth_templates_device_bytes(self.h))
+
+    def diff(self, depth_frames, matches, offsets=None, class_index=-1):
+        """depth_frames: a uint16 [H, W] array or a list of them (all of one size; rows may be strided); matches: MATCH_DTYPE records of
+        all frames back to back, frame f's at offsets[f]:offsets[f + 1] (default: one frame holding all).  -> DEPTH_DIFF_DTYPE array, one
+        record per match; with class_index >= 0 the matches of other classes get zeros."""
+        if isinstance(depth_frames, np.ndarray) and depth_frames.ndim == 2:
+            depth_frames = [depth_frames]
+        frames = list(depth_frames)
+        matches = np.ascontiguousarray(matches, MATCH_DTYPE)
+        if offsets is None:
+            if len(frames) != 1:
+                raise ValueError("offsets are needed with more than one frame")
+            offsets = [0, len(matches)]
+        if len(offsets) != len(frames) + 1 or int(offsets[-1]) != len(matches):
+            raise ValueError("offsets must have one entry per frame plus one and end at len(matches)")
+        for d in frames:
+            if d.dtype != np.uint16 or d.ndim != 2 or d.strides[1] != 2:
+                raise TypeError("depth frames must be uint16 HxW with contiguous rows (the row stride may be larger)")
+        imgs = (_lib.Image * max(1, len(frames)))(*[_lib.Image(d.ctypes.data, d.shape[0], d.shape[1], 1, 2, d.strides[0]) for d in frames])
+        offs = (C.c_size_t * len(offsets))(*[int(v) for v in offsets])
+        out = np.zeros(len(matches), DEPTH_DIFF_DTYPE)
+        _lib.check(_lib.lib().lmx_depth_diff_matches(self.h, imgs, len(frames), matches.ctypes.data, offs, int(class_index), out.ctypes.data))
+        return out
+
+    def close(self):
+        if getattr(self, "h", None):
+            _lib.lib().lmx_depth_templates_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 F2_MAX = 2048   # records per frame the device chain takes (csrc/lmx_internal.hpp)
 
 
