@@ -569,6 +569,45 @@ void       lmx_depth_templates_free(lmx_depth_templates* templates);
  * out[i] belongs to matches[i].  A template_id outside [0, count) fails the call before any launch; the text names the match. */
 lmx_status lmx_depth_diff_matches(lmx_depth_templates* templates, const lmx_image* depth, int32_t n_frames, const lmx_match_t* matches,
                                   const size_t* offsets, int32_t class_index, lmx_depth_diff_t* out);
+/* The value lmx_cluster_matches_scored and lmx_ctx_collect_clusters_depth average per cluster: minus the mean absolute difference in
+ * metres, -((double)sum_abs_mm / ((double)n_valid * 1000.0)), or no_value when n_valid == 0 (and for a NULL diff).  One expression
+ * (csrc/lmx_depth_verify.hpp, dv::value) for the device chain, the host fallback and every caller. */
+double     lmx_depth_value(const lmx_depth_diff_t* diff, double no_value);
+
+/* ---- depth-scored clusters on the device, straight from the raw-match slot ------------------------------------------------------------
+ * lmx_ctx_collect_clusters ranks clusters by mean similarity; the composition lmx_ctx_collect + lmx_depth_diff_matches +
+ * lmx_cluster_matches_scored ranks them by the depth difference but goes through the host's match list twice.  These two calls keep the
+ * depth score on the device:
+ *     lmx_ctx_enqueue(ctx, n, threshold, ...);
+ *     lmx_depth_templates_upload_scene(templates, depth, n);            // returns at once: the transfer overlaps the match kernels
+ *     lmx_ctx_collect_clusters_depth(ctx, n, templates, -1, -HUGE_VAL, ...);
+ * upload_scene: depth[f] as lmx_depth_diff_matches takes them (16-bit, one channel, one size, any row stride).  The frames are staged into
+ * the object's pinned buffer, their copies are queued on the object's stream and an event is recorded behind them; there is NO host
+ * synchronisation.  The object remembers the scene (frame count, width, height) until the next upload_scene replaces it, which first waits
+ * for the previous copies to leave the staging buffer; lmx_depth_diff_matches uses the same buffers and FORGETS the uploaded scene whenever it stages
+ * frames of its own, that is whenever it has a match to check (a call without one returns early and leaves the scene): after any call of
+ * it, upload the scene again.
+ * collect_clusters_depth: lmx_ctx_collect_clusters for the oldest outstanding enqueue (same outputs, same context locking) with
+ *   diffs[i]          = the depth check of matches[i] against scene frame f (parallel to matches; may be NULL; written when matches is),
+ *   clusters[k].score = the mean over the cluster's members, in voting order, of lmx_depth_value(diffs[i], no_value).
+ * On the context's consumer stream: wait for the scene's event, k_depth_diff_records (one workgroup per RAW record: which of two duplicate
+ * records std::unique keeps is decided by the sort that follows), the scored form of k_f2_finalize_cluster, one synchronisation.  Frames
+ * the device chain hands back (more than 2048 records, a bin outside the packed range) are finished on the host inside the call
+ * (k_depth_diff on the resident scene + lmx_cluster_matches_scored), with the errors lmx_ctx_collect_clusters reports for them.
+ * For EVERY input matches, diffs, clusters (score included) and members equal, bit for bit,
+ *     lmx_ctx_collect;  lmx_depth_diff_matches(templates, depth, n, matches, offsets, class_index, diffs);
+ *     per frame lmx_cluster_matches_scored with match_values[i] = lmx_depth_value(&diffs[i], no_value)
+ * -- that composition stays the one to use for values the caller computes himself (the normal term of depth_normal_diff_calc, a learned
+ * score) and for matches he filtered before clustering.  class_index >= 0: matches of other classes get zero diffs, hence no_value.
+ * no_value: -HUGE_VAL sends every cluster that holds a match with nothing to compare to the end (the Python helper depth_values' choice).
+ * LMX_ERR_INVALID_ARG, the enqueue staying outstanding, when: no side-car is set; templates lives on another device; no scene is uploaded,
+ * or its frame count / width / height differ from the enqueue's frame count / the context's frame size; lmx_depth_templates_count differs
+ * from the side-car's n_templates; no_value is NaN.  The object's mutex is held for the whole call. */
+lmx_status lmx_depth_templates_upload_scene(lmx_depth_templates* templates, const lmx_image* depth, int32_t n_frames);
+lmx_status lmx_ctx_collect_clusters_depth(lmx_ctx* ctx, int32_t n_frames, lmx_depth_templates* templates, int32_t class_index, double no_value,
+                                          lmx_match_t* matches, size_t cap_matches, size_t* match_offsets,
+                                          lmx_depth_diff_t* diffs /* parallel to matches; may be NULL */,
+                                          lmx_cluster_t* clusters, size_t cap_clusters, size_t* cluster_offsets, int32_t* members, size_t cap_members);
 
 /* ---- introspection (stage-level parity tests, profiling) ------------------------------------------------- */
 enum {
@@ -616,6 +655,15 @@ lmx_status lmx_debug_device_finalize_cluster(int32_t device, const lmx_raw_match
                                              const double* obj_origin_dists, const int32_t* rects, size_t n_templates,
                                              const lmx_cluster_params* params, lmx_match_t* matches, lmx_cluster_t* clusters, int32_t* members,
                                              uint32_t* counts);
+/* The same hook for the scored form (lmx_ctx_collect_clusters_depth): depth[n_frames] becomes templates' uploaded scene, then
+ * k_depth_diff_records and k_f2_finalize_cluster_scored run on the stand-alone slot.  diffs [n_frames][2048] comes back next to matches
+ * (a frame's row is valid where its matches row is); everything else as above, again without host completion.  templates need not hold
+ * n_templates crops: a record whose template_id it does not hold gets a zero diff. */
+lmx_status lmx_debug_device_finalize_cluster_depth(int32_t device, const lmx_raw_match_t* records, size_t n_records, int32_t n_frames,
+                                                   lmx_depth_templates* templates, const lmx_image* depth, int32_t class_index, double no_value,
+                                                   const double* obj_origin_dists, const int32_t* rects, size_t n_templates,
+                                                   const lmx_cluster_params* params, lmx_match_t* matches, lmx_depth_diff_t* diffs,
+                                                   lmx_cluster_t* clusters, int32_t* members, uint32_t* counts);
 /* Test hook, no device needed: one of the tables a context of width x height frames, max_batch frames per batch and shard
  * shard_rank of shard_world (1: the whole bank) would put on the device for `bank` -- the bytes DeviceBankView's pointers see
  * (csrc/lmx_bank_tables.hpp defines every format); ls_flat != 0 as under LMX_LS_FLAT.  LMX_TAB_SUMMARY is uint32 words:

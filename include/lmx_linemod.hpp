@@ -275,9 +275,15 @@ class DepthTemplates {
     check(lmx_depth_diff_matches(h_, imgs.data(), (int32_t)imgs.size(), matches.data(), offsets.data(), class_index, out.data()));
     return out;
   }
-  // The value lmx_cluster_matches_scored ranks by: minus the mean difference in metres (-HUGE_VAL when nothing could be compared).
-  static double value(const lmx_depth_diff_t& d) {
-    return d.n_valid > 0 ? -(double)d.sum_abs_mm / (d.n_valid * 1000.0) : -HUGE_VAL;
+  // The value lmx_cluster_matches_scored and collectClustersDepth rank by: minus the mean difference in metres (no_value when nothing
+  // could be compared).
+  static double value(const lmx_depth_diff_t& d, double no_value = -HUGE_VAL) { return lmx_depth_value(&d, no_value); }
+
+  // The scene of the next collectClustersDepth: returns without waiting, so call it right after the enqueue.
+  void uploadScene(const std::vector<Image>& depth) {
+    std::vector<lmx_image> imgs;
+    for (const Image& d : depth) imgs.push_back(d.c());
+    check(lmx_depth_templates_upload_scene(h_, imgs.data(), (int32_t)imgs.size()));
   }
 
   lmx_depth_templates* handle() const { return h_; }

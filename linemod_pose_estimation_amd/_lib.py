@@ -23,6 +23,7 @@ SYMBOLS = [
     "lmx_ctx_algorithmic_bytes", "lmx_last_error", "lmx_version",
     "lmx_cluster_matches_scored", "lmx_depth_templates_from_mesh", "lmx_depth_templates_from_crops", "lmx_depth_templates_count", "lmx_depth_templates_rect",
     "lmx_depth_templates_get", "lmx_depth_templates_device_bytes", "lmx_depth_templates_free", "lmx_depth_diff_matches",
+    "lmx_depth_value", "lmx_depth_templates_upload_scene", "lmx_ctx_collect_clusters_depth", "lmx_debug_device_finalize_cluster_depth",
 ]
 
 (LMX_OK, LMX_ERR_INVALID_ARG, LMX_ERR_SHAPE, LMX_ERR_NO_DEVICE, LMX_ERR_HIP, LMX_ERR_OVERFLOW, LMX_ERR_IO,
@@ -252,6 +253,13 @@ def lib():
     L.lmx_depth_templates_free.argtypes = [vp]
     L.lmx_depth_templates_free.restype = None
     L.lmx_depth_diff_matches.argtypes = [vp, C.POINTER(Image), C.c_int32, vp, C.POINTER(C.c_size_t), C.c_int32, vp]
+    L.lmx_depth_value.argtypes = [C.POINTER(DepthDiff), C.c_double]
+    L.lmx_depth_value.restype = C.c_double
+    L.lmx_depth_templates_upload_scene.argtypes = [vp, C.POINTER(Image), C.c_int32]
+    L.lmx_ctx_collect_clusters_depth.argtypes = [vp, C.c_int32, vp, C.c_int32, C.c_double, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, vp, C.c_size_t,
+                                                 C.POINTER(C.c_size_t), vp, C.c_size_t]
+    L.lmx_debug_device_finalize_cluster_depth.argtypes = [C.c_int32, vp, C.c_size_t, C.c_int32, vp, C.POINTER(Image), C.c_int32, C.c_double, vp, vp, C.c_size_t,
+                                                          C.POINTER(ClusterParams), vp, vp, vp, vp, vp]
     L.lmx_ctx_set_cluster_sidecar.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(ClusterParams)]
     L.lmx_ctx_collect_clusters.argtypes = [vp, C.c_int32, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t), vp, C.c_size_t]
     L.lmx_ctx_debug_read.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_size_t]

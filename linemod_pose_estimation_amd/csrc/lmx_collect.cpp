@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "lmx_ctx.hpp"
+#include "lmx_depth_verify.hpp"
 
 using namespace lmx;
 
@@ -195,17 +196,31 @@ lmx_status lmx_ctx_set_cluster_sidecar(lmx_ctx* c, const double* obj_origin_dist
   return LMX_OK;
 }
 
-lmx_status lmx_ctx_collect_clusters(lmx_ctx* c, int32_t n_frames, lmx_match_t* matches, size_t cap_matches, size_t* match_offsets, lmx_cluster_t* clusters,
-                                    size_t cap_clusters, size_t* cluster_offsets, int32_t* members, size_t cap_members) {
-  return lmx::guarded("lmx_ctx_collect_clusters", [&]() -> lmx_status {
-  if (!c || !match_offsets || !cluster_offsets || (cap_matches > 0 && !matches) || (cap_clusters > 0 && !clusters) || (cap_members > 0 && !members)) {
-    set_error("lmx_ctx_collect_clusters: null argument");
-    return LMX_ERR_INVALID_ARG;
-  }
-  if (!c->f2_sidecar) { set_error("lmx_ctx_collect_clusters: call lmx_ctx_set_cluster_sidecar first"); return LMX_ERR_INVALID_ARG; }
-  if (c->outstanding < 1) { set_error("lmx_ctx_collect_clusters: nothing enqueued"); return LMX_ERR_INVALID_ARG; }
+// What lmx_ctx_collect_clusters_depth adds to lmx_ctx_collect_clusters; null = the unscored call
+struct DepthScore {
+  lmx_depth_templates* templates;
+  int32_t class_index;
+  double no_value;
+  lmx_depth_diff_t* diffs;   // parallel to the caller's matches; may be null
+};
+
+// The body of lmx_ctx_collect_clusters and lmx_ctx_collect_clusters_depth (`what` names the entry point in messages).  With `depth`, the
+// caller holds the templates' mutex.
+static lmx_status collect_clusters_impl(const char* what, lmx_ctx* c, int32_t n_frames, const DepthScore* depth, lmx_match_t* matches, size_t cap_matches,
+                                        size_t* match_offsets, lmx_cluster_t* clusters, size_t cap_clusters, size_t* cluster_offsets, int32_t* members,
+                                        size_t cap_members) {
+  if (!c->f2_sidecar) { set_error("%s: call lmx_ctx_set_cluster_sidecar first", what); return LMX_ERR_INVALID_ARG; }
+  if (c->outstanding < 1) { set_error("%s: nothing enqueued", what); return LMX_ERR_INVALID_ARG; }
   const int slot = (c->head + c->n_slots - c->outstanding) % c->n_slots;  // oldest outstanding enqueue
-  if (n_frames != c->slot_frames[slot]) { set_error("lmx_ctx_collect_clusters: n_frames=%d but the enqueue had %d", n_frames, c->slot_frames[slot]); return LMX_ERR_INVALID_ARG; }
+  if (n_frames != c->slot_frames[slot]) { set_error("%s: n_frames=%d but the enqueue had %d", what, n_frames, c->slot_frames[slot]); return LMX_ERR_INVALID_ARG; }
+  if (depth) {   // every refusal comes before the enqueue is consumed: it stays outstanding
+    const DepthSceneInfo sc = depth_templates_scene(depth->templates);
+    if (sc.device != c->device) { set_error("%s: the templates live on device %d, the context on device %d", what, sc.device, c->device); return LMX_ERR_INVALID_ARG; }
+    if ((size_t)sc.count != c->f2_templates) { set_error("%s: %d depth templates but the side-car holds %zu templates", what, sc.count, c->f2_templates); return LMX_ERR_INVALID_ARG; }
+    if (sc.n_frames < 1) { set_error("%s: no scene uploaded: call lmx_depth_templates_upload_scene first", what); return LMX_ERR_INVALID_ARG; }
+    if (sc.n_frames != n_frames) { set_error("%s: the uploaded scene holds %d frames, the enqueue had %d", what, sc.n_frames, n_frames); return LMX_ERR_INVALID_ARG; }
+    if (sc.W != c->desc.width || sc.H != c->desc.height) { set_error("%s: the uploaded scene is %d x %d, the context's frames are %d x %d", what, sc.W, sc.H, c->desc.width, c->desc.height); return LMX_ERR_INVALID_ARG; }
+  }
   LMX_HIP(hipSetDevice(c->device));
   for (int f = 0; f <= n_frames; ++f) match_offsets[f] = cluster_offsets[f] = 0;
   const size_t F = (size_t)c->F;
@@ -222,6 +237,11 @@ lmx_status lmx_ctx_collect_clusters(lmx_ctx* c, int32_t n_frames, lmx_match_t* m
     if ((st = dev_alloc(c, &c->d_f2_scratch, F * F2_MAX * 32, false)) != LMX_OK) return st;
     LMX_HIP(hipStreamCreateWithFlags(&c->f2_stream, hipStreamNonBlocking));
     LMX_HIP(hipStreamSynchronize(c->stream));
+  }
+  if (depth && !c->h_f2_diffs) {
+    LMX_HIP(hipHostMalloc((void**)&c->h_f2_diffs, F * F2_MAX * sizeof(lmx_depth_diff_t), hipHostMallocMapped));
+    LMX_HIP(hipHostGetDevicePointer((void**)&c->d_f2_diffs, c->h_f2_diffs, 0));
+    if (lmx_status st = dev_alloc(c, &c->d_f2_diff_scratch, F * 2 * F2_MAX, false)) return st;
   }
   LMX_HIP(hipEventSynchronize(c->done[slot]));
   c->outstanding -= 1;
@@ -244,7 +264,21 @@ lmx_status lmx_ctx_collect_clusters(lmx_ctx* c, int32_t n_frames, lmx_match_t* m
   p.dists = c->d_f2_dists; p.rects = c->d_f2_rects; p.n_templates = (uint32_t)c->f2_templates;
   p.step = c->f2_params.vote_row_col_step; p.size_thresh = c->f2_params.cluster_size_thresh; p.do_clusters = 1;
   p.radius_min = c->f2_params.renderer_radius_min; p.radius_step = c->f2_params.renderer_radius_step;
-  launch_f2(s, p);
+  if (depth) {
+    if (n_match > c->f2_rec_diffs_cap) {   // nothing reads the old buffer: every call ends synchronised
+      if (c->d_f2_rec_diffs) (void)hipFree(c->d_f2_rec_diffs);
+      c->d_f2_rec_diffs = nullptr; c->f2_rec_diffs_cap = 0;
+      const size_t cap = std::max<size_t>(n_match, 4096);
+      LMX_HIP(hipMalloc((void**)&c->d_f2_rec_diffs, cap * sizeof(lmx_depth_diff_t)));
+      c->f2_rec_diffs_cap = cap;
+    }
+    // the scene's copies, one workgroup per raw record (the count is the header's, read above), the scored chain: one synchronisation
+    if (lmx_status st = depth_launch_records(depth->templates, s, p.recs, n_match, depth->class_index, c->d_f2_rec_diffs)) return st;
+    p.diffs = c->d_f2_rec_diffs; p.out_diffs = c->d_f2_diffs; p.diff_scratch = c->d_f2_diff_scratch; p.no_value = depth->no_value;
+    launch_f2_scored(s, p);
+  } else {
+    launch_f2(s, p);
+  }
   LMX_HIP(hipGetLastError());
   LMX_HIP(hipStreamSynchronize(s));
   const uint32_t* counts = reinterpret_cast<const uint32_t*>(c->h_f2_out + off_counts);
@@ -265,12 +299,15 @@ lmx_status lmx_ctx_collect_clusters(lmx_ctx* c, int32_t n_frames, lmx_match_t* m
   std::vector<lmx_match_t> fm;
   std::vector<lmx_cluster_t> fc;
   std::vector<int32_t> fmem;
+  std::vector<lmx_depth_diff_t> fd;
+  std::vector<double> fv;
   for (int f = 0; f < n_frames; ++f) {
     size_t nm = 0, nc = 0, nmem = 0;
     if (counts[(size_t)f * 4 + 3] == 0) {
       nm = counts[(size_t)f * 4 + 0]; nc = counts[(size_t)f * 4 + 1]; nmem = counts[(size_t)f * 4 + 2];
       if (cap_matches) fm.assign(all_m + (size_t)F2_MAX * f, all_m + (size_t)F2_MAX * f + nm);
       else fm.clear();
+      if (depth && depth->diffs && cap_matches) fd.assign(c->h_f2_diffs + (size_t)F2_MAX * f, c->h_f2_diffs + (size_t)F2_MAX * f + nm);
       fc.assign(all_c + (size_t)F2_MAX * f, all_c + (size_t)F2_MAX * f + nc);
       fmem.assign(all_mem + (size_t)F2_MAX * f, all_mem + (size_t)F2_MAX * f + nmem);
     } else {
@@ -283,15 +320,27 @@ lmx_status lmx_ctx_collect_clusters(lmx_ctx* c, int32_t n_frames, lmx_match_t* m
       for (size_t i = 0; i < nm; ++i) fm[i] = fin[i].m;
       fc.resize(std::max<size_t>(nm, 1)); fmem.resize(std::max<size_t>(nm, 1));
       size_t got = 0;
-      lmx_status hs = lmx_cluster_matches(fm.data(), nm, c->f2_host_dists.data(), c->f2_host_rects.data(), c->f2_templates, &c->f2_params, fc.data(), fc.size(), &got,
-                                          fmem.data(), fmem.size());
+      lmx_status hs;
+      if (depth) {   // the final matches against the resident scene (k_depth_diff), then the host chain on their values
+        fd.resize(std::max<size_t>(nm, 1)); fv.resize(std::max<size_t>(nm, 1));
+        if ((hs = depth_diff_resident(depth->templates, fm.data(), nm, f, depth->class_index, fd.data())) != LMX_OK) return hs;
+        for (size_t i = 0; i < nm; ++i) fv[i] = dv::value(fd[i], depth->no_value);
+        hs = lmx_cluster_matches_scored(fm.data(), nm, fv.data(), c->f2_host_dists.data(), c->f2_host_rects.data(), c->f2_templates, &c->f2_params, fc.data(),
+                                        fc.size(), &got, fmem.data(), fmem.size());
+      } else {
+        hs = lmx_cluster_matches(fm.data(), nm, c->f2_host_dists.data(), c->f2_host_rects.data(), c->f2_templates, &c->f2_params, fc.data(), fc.size(), &got,
+                                 fmem.data(), fmem.size());
+      }
       if (hs != LMX_OK) return hs;
       nc = got; nmem = 0;
       for (size_t i = 0; i < nc; ++i) nmem += (size_t)fc[i].member_count;
     }
     if (cap_matches) {
       if (mpos + nm > cap_matches) st = LMX_ERR_OVERFLOW;
-      else if (nm) std::memcpy(matches + mpos, fm.data(), nm * sizeof(lmx_match_t));   // (an empty vector's data() may be null)
+      else if (nm) {
+        std::memcpy(matches + mpos, fm.data(), nm * sizeof(lmx_match_t));   // (an empty vector's data() may be null)
+        if (depth && depth->diffs) std::memcpy(depth->diffs + mpos, fd.data(), nm * sizeof(lmx_depth_diff_t));
+      }
     }
     if (cpos + nc <= cap_clusters && mempos + nmem <= cap_members) {
       for (size_t i = 0; i < nc; ++i) { clusters[cpos + i] = fc[i]; clusters[cpos + i].member_begin += (int32_t)mempos; }
@@ -304,6 +353,33 @@ lmx_status lmx_ctx_collect_clusters(lmx_ctx* c, int32_t n_frames, lmx_match_t* m
   }
   if (st != LMX_OK) set_error("%zu matches / %zu clusters / %zu members exceed the output capacity", mpos, cpos, mempos);
   return st;
+}
+
+lmx_status lmx_ctx_collect_clusters(lmx_ctx* c, int32_t n_frames, lmx_match_t* matches, size_t cap_matches, size_t* match_offsets, lmx_cluster_t* clusters,
+                                    size_t cap_clusters, size_t* cluster_offsets, int32_t* members, size_t cap_members) {
+  return lmx::guarded("lmx_ctx_collect_clusters", [&]() -> lmx_status {
+  if (!c || !match_offsets || !cluster_offsets || (cap_matches > 0 && !matches) || (cap_clusters > 0 && !clusters) || (cap_members > 0 && !members)) {
+    set_error("lmx_ctx_collect_clusters: null argument");
+    return LMX_ERR_INVALID_ARG;
+  }
+  return collect_clusters_impl("lmx_ctx_collect_clusters", c, n_frames, nullptr, matches, cap_matches, match_offsets, clusters, cap_clusters, cluster_offsets,
+                               members, cap_members);
+  });
+}
+
+lmx_status lmx_ctx_collect_clusters_depth(lmx_ctx* c, int32_t n_frames, lmx_depth_templates* templates, int32_t class_index, double no_value,
+                                          lmx_match_t* matches, size_t cap_matches, size_t* match_offsets, lmx_depth_diff_t* diffs, lmx_cluster_t* clusters,
+                                          size_t cap_clusters, size_t* cluster_offsets, int32_t* members, size_t cap_members) {
+  return lmx::guarded("lmx_ctx_collect_clusters_depth", [&]() -> lmx_status {
+  if (no_value != no_value) { set_error("lmx_ctx_collect_clusters_depth: no_value is not a number (the score order would be undefined)"); return LMX_ERR_INVALID_ARG; }
+  if (!c || !templates || !match_offsets || !cluster_offsets || (cap_matches > 0 && !matches) || (cap_clusters > 0 && !clusters) || (cap_members > 0 && !members)) {
+    set_error("lmx_ctx_collect_clusters_depth: null argument");
+    return LMX_ERR_INVALID_ARG;
+  }
+  std::lock_guard<std::mutex> lk(depth_templates_mutex(templates));   // held for the whole call: the scene and the object's buffers stay put
+  const DepthScore depth{templates, class_index, no_value, diffs};
+  return collect_clusters_impl("lmx_ctx_collect_clusters_depth", c, n_frames, &depth, matches, cap_matches, match_offsets, clusters, cap_clusters,
+                               cluster_offsets, members, cap_members);
   });
 }
 

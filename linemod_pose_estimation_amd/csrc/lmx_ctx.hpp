@@ -217,6 +217,12 @@ struct lmx_ctx {
   int32_t* d_f2_members = nullptr;
   uint8_t* d_f2_scratch = nullptr;
   hipStream_t f2_stream = nullptr;       // the kernel's own stream: a lane's stream may already hold later batches
+  // the scored form (lmx_ctx_collect_clusters_depth), allocated on its first call
+  lmx_depth_diff_t* h_f2_diffs = nullptr;        // pinned, mapped: [F][F2_MAX] diffs in final-match order
+  lmx_depth_diff_t* d_f2_diffs = nullptr;        // its device view
+  lmx_depth_diff_t* d_f2_diff_scratch = nullptr; // [F][2][F2_MAX]
+  lmx_depth_diff_t* d_f2_rec_diffs = nullptr;    // one per raw record of the slot being collected; grows on demand
+  size_t f2_rec_diffs_cap = 0;
   // stats / profiling
   int64_t stat_cands = 0, stat_matches = 0;
   uint32_t profiling = 0;  // bitmask over kernel ids

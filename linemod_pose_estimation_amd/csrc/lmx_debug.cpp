@@ -302,22 +302,25 @@ lmx_status lmx_debug_device_sort_perm(int32_t device, const float* similarity, c
 // The whole device consumer chain (k_f2_finalize_cluster, as lmx_ctx_collect_clusters launches it) on a caller's record list: the records
 // become a raw-match slot of their own (16-dword header with [1] = n_records, cap = n_records), the kernel's outputs and per-frame count
 // words come back as written -- no host completion, so a test sees which path the kernel took.
-lmx_status lmx_debug_device_finalize_cluster(int32_t device, const lmx_raw_match_t* records, size_t n_records, int32_t n_frames,
-                                             const double* obj_origin_dists, const int32_t* rects, size_t n_templates, const lmx_cluster_params* params,
-                                             lmx_match_t* matches, lmx_cluster_t* clusters, int32_t* members, uint32_t* counts) {
+// templates != null: the scored form -- k_depth_diff_records on the stand-alone slot against the templates' resident scene, then
+// k_f2_finalize_cluster_scored; diffs [n_frames][2048] comes back next to matches.  The templates' mutex is the caller's to hold.
+static lmx_status debug_finalize_cluster(const char* what, int32_t device, const lmx_raw_match_t* records, size_t n_records, int32_t n_frames, lmx_depth_templates* templates,
+                                         int32_t class_index, double no_value, const double* obj_origin_dists, const int32_t* rects, size_t n_templates,
+                                         const lmx_cluster_params* params, lmx_match_t* matches, lmx_depth_diff_t* diffs, lmx_cluster_t* clusters,
+                                         int32_t* members, uint32_t* counts) {
   if ((n_records && !records) || !obj_origin_dists || !rects || n_templates == 0 || !params || !matches || !clusters || !members || !counts) {
-    set_error("lmx_debug_device_finalize_cluster: invalid argument");
+    set_error("%s: invalid argument", what);
     return LMX_ERR_INVALID_ARG;
   }
-  if (n_frames < 1 || n_frames > 8) { set_error("lmx_debug_device_finalize_cluster: n_frames must be 1..8 (got %d)", n_frames); return LMX_ERR_INVALID_ARG; }
-  if (n_records > ((size_t)1 << 24) || n_templates > ((size_t)1 << 24)) { set_error("lmx_debug_device_finalize_cluster: at most 2^24 records and templates"); return LMX_ERR_INVALID_ARG; }
+  if (n_frames < 1 || n_frames > 8) { set_error("%s: n_frames must be 1..8 (got %d)", what, n_frames); return LMX_ERR_INVALID_ARG; }
+  if (n_records > ((size_t)1 << 24) || n_templates > ((size_t)1 << 24)) { set_error("%s: at most 2^24 records and templates", what); return LMX_ERR_INVALID_ARG; }
   if (params->vote_row_col_step <= 0) { set_error("vote_row_col_step must be positive"); return LMX_ERR_INVALID_ARG; }
   if (params->cluster_size_thresh < 0) { set_error("cluster_size_thresh must not be negative"); return LMX_ERR_INVALID_ARG; }
   if (lmx_status vs = check_vote_rings(obj_origin_dists, n_templates, params)) return vs;
   for (size_t i = 0; i < n_records; ++i) {   // the kernel keeps x, y as int16 and class_index as uint16 in LDS
     const lmx_raw_match_t& r = records[i];
     if (r.x < -32768 || r.x > 32767 || r.y < -32768 || r.y > 32767 || r.class_index < 0 || r.class_index > 65535) {
-      set_error("lmx_debug_device_finalize_cluster: record %zu: x, y must fit an int16 and class_index a uint16", i);
+      set_error("%s: record %zu: x, y must fit an int16 and class_index a uint16", what, i);
       return LMX_ERR_INVALID_ARG;
     }
   }
@@ -334,6 +337,7 @@ lmx_status lmx_debug_device_finalize_cluster(int32_t device, const lmx_raw_match
   int32_t *d_members = nullptr, *d_rects = nullptr;
   uint8_t* d_scratch = nullptr;
   double* d_dists = nullptr;
+  lmx_depth_diff_t *d_rec_diffs = nullptr, *d_diffs = nullptr, *d_diff_scratch = nullptr;
   auto run = [&]() -> lmx_status {
     LMX_HIP(hipMalloc((void**)&d_hdr, sizeof(hdr)));
     LMX_HIP(hipMalloc((void**)&d_recs, std::max<size_t>(n_records, 1) * sizeof(lmx_raw_match_t)));
@@ -352,15 +356,28 @@ lmx_status lmx_debug_device_finalize_cluster(int32_t device, const lmx_raw_match
     LMX_HIP(hipMemset(d_clusters, 0, F * F2_MAX * sizeof(lmx_cluster_t)));
     LMX_HIP(hipMemset(d_members, 0, F * F2_MAX * sizeof(int32_t)));
     LMX_HIP(hipMemset(d_counts, 0xff, F * 4 * sizeof(uint32_t)));   // a frame the kernel did not report on stays recognisable
+    if (templates) {
+      LMX_HIP(hipMalloc((void**)&d_rec_diffs, std::max<size_t>(n_records, 1) * sizeof(lmx_depth_diff_t)));
+      LMX_HIP(hipMalloc((void**)&d_diffs, F * F2_MAX * sizeof(lmx_depth_diff_t)));
+      LMX_HIP(hipMalloc((void**)&d_diff_scratch, F * 2 * F2_MAX * sizeof(lmx_depth_diff_t)));
+      LMX_HIP(hipMemset(d_diffs, 0, F * F2_MAX * sizeof(lmx_depth_diff_t)));
+    }
     F2Params p{};
     p.recs = d_recs; p.hdr = d_hdr; p.cap = (uint32_t)n_records; p.n_frames = n_frames;
     p.out_matches = d_matches; p.out_counts = d_counts; p.out_clusters = d_clusters; p.out_members = d_members; p.scratch = d_scratch;
     p.dists = d_dists; p.rects = d_rects; p.n_templates = (uint32_t)n_templates;
     p.step = params->vote_row_col_step; p.size_thresh = params->cluster_size_thresh; p.do_clusters = 1;
     p.radius_min = params->renderer_radius_min; p.radius_step = params->renderer_radius_step;
-    launch_f2(nullptr, p);
+    if (templates) {
+      if (lmx_status ds = depth_launch_records(templates, nullptr, d_recs, (uint32_t)n_records, class_index, d_rec_diffs)) return ds;
+      p.diffs = d_rec_diffs; p.out_diffs = d_diffs; p.diff_scratch = d_diff_scratch; p.no_value = no_value;
+      launch_f2_scored(nullptr, p);
+    } else {
+      launch_f2(nullptr, p);
+    }
     LMX_HIP(hipGetLastError());
     LMX_HIP(hipDeviceSynchronize());
+    if (templates) LMX_HIP(hipMemcpy(diffs, d_diffs, F * F2_MAX * sizeof(lmx_depth_diff_t), hipMemcpyDeviceToHost));
     LMX_HIP(hipMemcpy(matches, d_matches, F * F2_MAX * sizeof(lmx_match_t), hipMemcpyDeviceToHost));
     LMX_HIP(hipMemcpy(clusters, d_clusters, F * F2_MAX * sizeof(lmx_cluster_t), hipMemcpyDeviceToHost));
     LMX_HIP(hipMemcpy(members, d_members, F * F2_MAX * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -370,7 +387,29 @@ lmx_status lmx_debug_device_finalize_cluster(int32_t device, const lmx_raw_match
   const lmx_status st = run();
   (void)hipFree(d_hdr); (void)hipFree(d_recs); (void)hipFree(d_matches); (void)hipFree(d_clusters); (void)hipFree(d_members);
   (void)hipFree(d_counts); (void)hipFree(d_scratch); (void)hipFree(d_dists); (void)hipFree(d_rects);
+  (void)hipFree(d_rec_diffs); (void)hipFree(d_diffs); (void)hipFree(d_diff_scratch);
   return st;
+}
+lmx_status lmx_debug_device_finalize_cluster(int32_t device, const lmx_raw_match_t* records, size_t n_records, int32_t n_frames,
+                                             const double* obj_origin_dists, const int32_t* rects, size_t n_templates, const lmx_cluster_params* params,
+                                             lmx_match_t* matches, lmx_cluster_t* clusters, int32_t* members, uint32_t* counts) {
+  return debug_finalize_cluster("lmx_debug_device_finalize_cluster", device, records, n_records, n_frames, nullptr, -1, 0.0, obj_origin_dists, rects, n_templates, params, matches, nullptr, clusters,
+                                members, counts);
+}
+// The scored form of the same hook: `depth` (n_frames 16UC1 host frames) becomes the templates' resident scene, then k_depth_diff_records and
+// k_f2_finalize_cluster_scored run on the stand-alone slot as lmx_ctx_collect_clusters_depth launches them.  No host completion.
+lmx_status lmx_debug_device_finalize_cluster_depth(int32_t device, const lmx_raw_match_t* records, size_t n_records, int32_t n_frames,
+                                                   lmx_depth_templates* templates, const lmx_image* depth, int32_t class_index, double no_value,
+                                                   const double* obj_origin_dists, const int32_t* rects, size_t n_templates, const lmx_cluster_params* params,
+                                                   lmx_match_t* matches, lmx_depth_diff_t* diffs, lmx_cluster_t* clusters, int32_t* members, uint32_t* counts) {
+  if (!templates || !depth || !diffs) { set_error("lmx_debug_device_finalize_cluster_depth: invalid argument"); return LMX_ERR_INVALID_ARG; }
+  if (no_value != no_value) { set_error("lmx_debug_device_finalize_cluster_depth: no_value is not a number"); return LMX_ERR_INVALID_ARG; }
+  if (n_frames < 1 || n_frames > 8) { set_error("lmx_debug_device_finalize_cluster_depth: n_frames must be 1..8 (got %d)", n_frames); return LMX_ERR_INVALID_ARG; }
+  if (depth_templates_scene(templates).device != device) { set_error("lmx_debug_device_finalize_cluster_depth: the templates live on another device"); return LMX_ERR_INVALID_ARG; }
+  std::lock_guard<std::mutex> lk(depth_templates_mutex(templates));   // held from the upload to the last launch: nobody replaces the scene between
+  if (lmx_status st = depth_upload_scene(templates, depth, n_frames)) return st;
+  return debug_finalize_cluster("lmx_debug_device_finalize_cluster_depth", device, records, n_records, n_frames, templates, class_index, no_value, obj_origin_dists, rects, n_templates, params, matches, diffs,
+                                clusters, members, counts);
 }
 lmx_status lmx_debug_introsort_perm_score(const double* score, int32_t n, int32_t* perm) {
   if (n < 0 || (n > 0 && (!score || !perm))) { set_error("lmx_debug_introsort_perm_score: invalid argument"); return LMX_ERR_INVALID_ARG; }

@@ -1,6 +1,7 @@
 // Depth check of a match against the rendered depth of its template (lmx_depth_diff_matches, include/lmx.h): the arithmetic of one pixel,
-// one row and one match, shared by the HIP kernel (lmx_verify.hip, k_depth_diff) and -- compiled with LMX_DV_HOST -- by a plain CPU build
-// (tests/cpp/depth_verify_host.cpp).  The reference's form is depth_normal_diff_calc (src/rgbdDetector.cpp:147-282), the depth half.
+// one row and one match, shared by the HIP kernels (lmx_verify.hip, k_depth_diff and k_depth_diff_records; lmx_f2.hip for value()) and --
+// compiled with LMX_DV_HOST -- by plain CPU builds (tests/cpp/depth_verify_host.cpp, tests/cpp/depth_value_host.cpp).
+// The reference's form is depth_normal_diff_calc (src/rgbdDetector.cpp:147-282), the depth half.
 //
 // A template crop t[h][w] and a scene depth image s[H][W], both uint16 millimetres; 0 = "not on the object" in the crop, "no measurement"
 // in the scene.  The crop's top-left corner lies at the match position (x, y), any int32:
@@ -114,6 +115,13 @@ LMX_DV_FN Sums diff_match_vectors(const uint16_t* crop, int32_t h, int32_t pitch
     }
   }
   return a;
+}
+
+// What a cluster's depth score is the mean of (lmx_cluster_matches_scored, the scored form of k_f2_finalize_cluster): minus the mean absolute
+// difference in metres, or no_value for a match that had nothing to compare.  Diff: lmx_depth_diff_t or anything with its fields.
+template <typename Diff>
+LMX_DV_FN double value(const Diff& d, double no_value) {
+  return d.n_valid > 0 ? -((double)d.sum_abs_mm / ((double)d.n_valid * 1000.0)) : no_value;
 }
 
 }  // namespace dv

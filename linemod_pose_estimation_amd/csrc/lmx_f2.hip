@@ -19,9 +19,13 @@
 //   G  std::sort by score desc (emulated) + greedy IoU suppression at 0.4 with the reference's int/float arithmetic   lane 0
 // Frames with more than F2_MAX records are flagged and finished by the host path (lmx_cluster_matches), so the result is the
 // reference's for every input.
+// The SCORED instantiation (lmx_ctx_collect_clusters_depth) ranks clusters by the reference's other score, the depth difference of
+// depth_normal_diff_calc: every raw record comes with a lmx_depth_diff_t (k_depth_diff_records, lmx_verify.hip) that travels with it through
+// B - D in two rows of device memory (LDS is full) and lands next to its final match; F averages dv::value of it instead of the similarity.
 #include <hip/hip_runtime.h>
 
 #include "lmx_internal.hpp"
+#include "lmx_depth_verify.hpp"
 #include "lmx_sort_block.hpp"
 #include "lmx_sort_emul.hpp"
 
@@ -88,7 +92,8 @@ __global__ __launch_bounds__(256) void k_debug_block_sort(const float* sim, cons
   for (int i = threadIdx.x; i < n; i += 256) perm[i] = s_tag[i];
 }
 
-__global__ __launch_bounds__(256) void k_f2_finalize_cluster(F2Params p) {
+template <bool SCORED>
+__device__ __forceinline__ void f2_finalize_cluster(const F2Params& p) {
   constexpr int NMAX = F2_MAX;
   constexpr int PER = (NMAX + 255) / 256;   // items per thread
   __shared__ unsigned long long s_key[NMAX];
@@ -104,6 +109,10 @@ __global__ __launch_bounds__(256) void k_f2_finalize_cluster(F2Params p) {
   const int tid = threadIdx.x, frame = blockIdx.x;
   uint32_t* counts = p.out_counts + (size_t)frame * 4;
   lmx_match_t* out_m = p.out_matches + (size_t)frame * NMAX;
+  // SCORED: this frame's diffs by insertion position (written at the load step, read at the compaction) and by final position (written
+  // there, read by lane 0 in F); each read has a __syncthreads() between it and the write
+  lmx_depth_diff_t* const d_parked = SCORED ? p.diff_scratch + (size_t)frame * 2 * NMAX : nullptr;
+  lmx_depth_diff_t* const d_final = SCORED ? d_parked + NMAX : nullptr;
   if (tid == 0) { s_n = 0; s_nfinal = 0; }
   __syncthreads();
   // A: this frame's records (order arbitrary), identified by their index in the slot's list
@@ -154,7 +163,9 @@ __global__ __launch_bounds__(256) void k_f2_finalize_cluster(F2Params p) {
     __syncthreads();
     cnt = 0;
     for (int i = tid; i < n; i += 256) {
-      const lmx_raw_match_t r = p.recs[rec_of_pos[cnt++]];
+      const lmx_raw_match_t r = p.recs[rec_of_pos[cnt]];
+      if constexpr (SCORED) d_parked[i] = p.diffs[rec_of_pos[cnt]];
+      ++cnt;
       s_sim[i] = r.similarity; s_tid[i] = r.template_id; s_x[i] = (short)r.x; s_y[i] = (short)r.y; s_cls[i] = (unsigned short)r.class_index;
     }
   }
@@ -208,6 +219,11 @@ __global__ __launch_bounds__(256) void k_f2_finalize_cluster(F2Params p) {
       lmx_match_t m;
       m.x = r_x[cnt]; m.y = r_y[cnt]; m.similarity = r_sim[cnt]; m.template_id = r_tid[cnt]; m.class_index = r_cls[cnt];
       out_m[d] = m;
+      if constexpr (SCORED) {
+        const lmx_depth_diff_t dd = d_parked[s_perm[j]];   // s_perm is not touched by this step
+        d_final[d] = dd;
+        p.out_diffs[(size_t)frame * NMAX + d] = dd;
+      }
     }
   }
   __syncthreads();
@@ -265,7 +281,8 @@ __global__ __launch_bounds__(256) void k_f2_finalize_cluster(F2Params p) {
         int X = 0, Y = 0, Wd = 0, Ht = 0;
         for (int k = b; k < e; ++k) {
           const int j = (int)(s_key[k] & 2047u);
-          sum += (double)s_sim[j];
+          if constexpr (SCORED) sum += dv::value(d_final[j], p.no_value);
+          else sum += (double)s_sim[j];
           const int32_t* r = p.rects + (size_t)s_tid[j] * 4;
           X += s_x[j]; Y += s_y[j]; Wd += r[2]; Ht += r[3];
         }
@@ -309,12 +326,20 @@ __global__ __launch_bounds__(256) void k_f2_finalize_cluster(F2Params p) {
   }
 }
 
+// the two instantiations as kernels of their own (the unscored one keeps the name profiles know)
+__global__ __launch_bounds__(256) void k_f2_finalize_cluster(F2Params p) { f2_finalize_cluster<false>(p); }
+__global__ __launch_bounds__(256) void k_f2_finalize_cluster_scored(F2Params p) { f2_finalize_cluster<true>(p); }
+
 void launch_debug_block_sort(hipStream_t s, const float* sim, const int* tid, int n, int* perm, unsigned long long* spill) {
   hipLaunchKernelGGL(k_debug_block_sort, dim3(1), dim3(256), 0, s, sim, tid, n, perm, spill);
 }
 
 void launch_f2(hipStream_t s, const F2Params& p) {
   hipLaunchKernelGGL(k_f2_finalize_cluster, dim3((unsigned)p.n_frames), dim3(256), 0, s, p);
+}
+
+void launch_f2_scored(hipStream_t s, const F2Params& p) {
+  hipLaunchKernelGGL(k_f2_finalize_cluster_scored, dim3((unsigned)p.n_frames), dim3(256), 0, s, p);
 }
 
 }  // namespace lmx

@@ -10,6 +10,10 @@
 //                  narrower than 64 vectors packs several rows into a wave; waves take rows (groups of rows) in turn.  Scene pixels are
 //                  read as uint16 under the in-image predicate of lmx_depth_verify.hpp and nowhere else.  Per-lane sums are 64-bit;
 //                  wave shuffles, then LDS across the four waves, then one 16-byte store.  No atomics, no workgroup waits for another.
+//   k_depth_diff_records   the same walk (depth_diff_walk, shared by both kernels), one workgroup per RAW record of an output slot, against
+//                  the scene lmx_depth_templates_upload_scene left on the device: the input of the scored consumer chain (lmx_f2.hip)
+//   scene          one pinned staging buffer and one device buffer per object.  lmx_depth_diff_matches stages the frames that have matches
+//                  and waits for its results; upload_scene stages all frames, records an event behind their copies and returns
 #include <algorithm>
 #include <cstring>
 #include <memory>
@@ -65,34 +69,33 @@ __device__ __forceinline__ uint4 load_global_16(const uint16_t* p) {
 #endif
 }
 
-__global__ __launch_bounds__(256) void k_depth_diff(const DepthCrop* __restrict__ crops, const DepthJob* __restrict__ jobs,
-                                                    const uint16_t* __restrict__ scene, int W, int H, lmx_depth_diff_t* __restrict__ out) {
+// The crop walk of one match at (x, y) against one scene frame, by a whole 256-lane workgroup: both kernels below end in it.  Every lane of
+// the workgroup must arrive (it holds a barrier); lane 0 stores the 16-byte result.
+__device__ __forceinline__ void depth_diff_walk(const DepthCrop c, int32_t x, int32_t y, const uint16_t* __restrict__ frame, int W, int H,
+                                                lmx_depth_diff_t* __restrict__ out) {
   __shared__ unsigned long long s_sum[4];
   __shared__ int s_valid[4], s_templ[4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const DepthJob job = jobs[blockIdx.x];
-  const DepthCrop c = crops[job.template_id];
   if (c.w <= 0 || c.h <= 0) {   // an empty crop: the same for every lane of the workgroup, before any barrier
-    if (tid == 0) *reinterpret_cast<int4*>(&out[blockIdx.x]) = make_int4(0, 0, 0, 0);
+    if (tid == 0) *reinterpret_cast<int4*>(out) = make_int4(0, 0, 0, 0);
     return;
   }
   const int vpr = c.pitch / dv::kPitchAlign;        // vectors in a row
   const int lanes_per_row = vpr < 64 ? vpr : 64;
   const int rows_per_pass = 64 / lanes_per_row;     // rows a wave takes at once
   const int sub = lane / lanes_per_row, v0 = lane - sub * lanes_per_row;
-  const uint16_t* frame = scene + (size_t)job.frame * H * W;
   dv::Sums a = {0, 0, 0};
   for (int row0 = wave * rows_per_pass; row0 < c.h; row0 += 4 * rows_per_pass) {
     const int i = row0 + sub;
     if (sub >= rows_per_pass || i >= c.h) continue;
     int32_t Y = 0;
-    const bool row_in = dv::scene_row(job.y, i, H, &Y);
+    const bool row_in = dv::scene_row(y, i, H, &Y);
     const uint16_t* trow = c.data + (size_t)i * c.pitch;
     const uint16_t* srow = frame + (size_t)Y * W;     // Y = 0 when the row lies outside: never read then
     for (int v = v0; v < vpr; v += lanes_per_row) {
       const uint4 q = load_global_16(trow + v * dv::kPitchAlign);   // past w: the padding, zeros
       const uint32_t word[4] = {q.x, q.y, q.z, q.w};
-      dv::add_vector(word, row_in, job.x, v * dv::kPitchAlign, W, srow, &a);
+      dv::add_vector(word, row_in, x, v * dv::kPitchAlign, W, srow, &a);
     }
   }
   unsigned long long sum = a.sum_abs_mm;
@@ -108,8 +111,28 @@ __global__ __launch_bounds__(256) void k_depth_diff(const DepthCrop* __restrict_
     sum = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
     nv = s_valid[0] + s_valid[1] + s_valid[2] + s_valid[3];
     nt = s_templ[0] + s_templ[1] + s_templ[2] + s_templ[3];
-    *reinterpret_cast<int4*>(&out[blockIdx.x]) = make_int4((int)(uint32_t)sum, (int)(uint32_t)(sum >> 32), nv, nt);
+    *reinterpret_cast<int4*>(out) = make_int4((int)(uint32_t)sum, (int)(uint32_t)(sum >> 32), nv, nt);
   }
+}
+
+__global__ __launch_bounds__(256) void k_depth_diff(const DepthCrop* __restrict__ crops, const DepthJob* __restrict__ jobs,
+                                                    const uint16_t* __restrict__ scene, int W, int H, lmx_depth_diff_t* __restrict__ out) {
+  const DepthJob job = jobs[blockIdx.x];
+  depth_diff_walk(crops[job.template_id], job.x, job.y, scene + (size_t)job.frame * H * W, W, H, &out[blockIdx.x]);
+}
+
+// One workgroup per RAW record of an output slot (the device consumer chain carries the result through its sorts: lmx_f2.hip, SCORED).  A
+// record that is no job -- a template the table does not hold, a frame the scene does not hold, another class -- gets zeros without a look at
+// the table or the scene; the three tests are the same for every lane and come before any barrier.
+__global__ __launch_bounds__(256) void k_depth_diff_records(const DepthCrop* __restrict__ crops, int32_t count, const lmx_raw_match_t* __restrict__ recs,
+                                                            const uint16_t* __restrict__ scene, int32_t n_frames, int W, int H, int32_t class_index,
+                                                            lmx_depth_diff_t* __restrict__ diffs) {
+  const lmx_raw_match_t r = recs[blockIdx.x];
+  if (r.template_id < 0 || r.template_id >= count || r.frame < 0 || r.frame >= n_frames || (class_index >= 0 && r.class_index != class_index)) {
+    if (threadIdx.x == 0) *reinterpret_cast<int4*>(&diffs[blockIdx.x]) = make_int4(0, 0, 0, 0);
+    return;
+  }
+  depth_diff_walk(crops[r.template_id], r.x, r.y, scene + (size_t)r.frame * H * W, W, H, &diffs[blockIdx.x]);
 }
 
 }  // namespace
@@ -136,6 +159,10 @@ struct lmx_depth_templates {
   lmx::DepthCrop* d_table = nullptr;
   uint16_t *d_scene = nullptr, *h_scene = nullptr;
   size_t scene_cap = 0;                  // bytes
+  // the scene lmx_depth_templates_upload_scene left on the device (scene_frames 0: none); scene_ready is recorded behind its copies
+  int32_t scene_frames = 0, scene_W = 0, scene_H = 0;
+  hipEvent_t scene_ready = nullptr;
+  bool scene_pending = false;            // scene_ready has been recorded and h_scene may still be read by a copy
   lmx::DepthJob *d_jobs = nullptr, *h_jobs = nullptr;
   lmx_depth_diff_t *d_out = nullptr, *h_out = nullptr;
   size_t jobs_cap = 0;                   // entries
@@ -148,6 +175,7 @@ struct lmx_depth_templates {
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { lmx::set_error("no HIP device available; this library has no CPU path"); return LMX_ERR_NO_DEVICE; }
     DV_HIP(hipSetDevice(device));
     if (!s) DV_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    if (!scene_ready) DV_HIP(hipEventCreateWithFlags(&scene_ready, hipEventDisableTiming));
     if (!d_table && !table.empty()) {
       DV_HIP(hipMalloc(&d_table, table.size() * sizeof(lmx::DepthCrop)));
       DV_HIP(hipMemcpyAsync(d_table, table.data(), table.size() * sizeof(lmx::DepthCrop), hipMemcpyHostToDevice, s));
@@ -155,8 +183,17 @@ struct lmx_depth_templates {
     }
     return LMX_OK;
   }
+  // The staging buffer is free again: the copies of the previous upload_scene have left it.
+  lmx_status wait_scene_copies() {
+    if (scene_pending) { DV_HIP(hipEventSynchronize(scene_ready)); scene_pending = false; }
+    return LMX_OK;
+  }
+  // A call failed with copies of earlier frames possibly still queued: nothing may read the staging buffer once the call has returned, since
+  // no event stands behind those copies for the next call to wait on.  The error already set is the one reported.
+  void drain_after_error() { (void)hipStreamSynchronize(s); }
   lmx_status grow_scene(size_t bytes) {
     if (bytes <= scene_cap) return LMX_OK;
+    DV_HIP(hipStreamSynchronize(s));     // nothing queued may still use the buffers that go
     (void)hipFree(d_scene); (void)hipHostFree(h_scene);
     d_scene = h_scene = nullptr; scene_cap = 0;
     const size_t cap = bytes;
@@ -186,6 +223,7 @@ struct lmx_depth_templates {
     for (void* p : chunks) (void)hipFree(p);
     (void)hipFree(d_table); (void)hipFree(d_scene); (void)hipFree(d_jobs); (void)hipFree(d_out);
     (void)hipHostFree(h_scene); (void)hipHostFree(h_jobs); (void)hipHostFree(h_out);
+    if (scene_ready) (void)hipEventDestroy(scene_ready);
     if (s) (void)hipStreamDestroy(s);
   }
 };
@@ -353,6 +391,119 @@ extern "C" void lmx_depth_templates_free(lmx_depth_templates* t) {
   delete t;
 }
 
+namespace {
+// 16UC1 host frames of one size, any row stride: what lmx_depth_diff_matches and lmx_depth_templates_upload_scene take
+lmx_status check_depth_frames(const char* what, const lmx_image* depth, int32_t n_frames) {
+  using namespace lmx;
+  const int32_t W = depth[0].cols, H = depth[0].rows;
+  for (int32_t f = 0; f < n_frames; ++f) {
+    const lmx_image& im = depth[f];
+    if (!im.data) { set_error("%s: depth image %d has no data", what, f); return LMX_ERR_INVALID_ARG; }
+    if (im.channels != 1 || im.elem_size != 2) { set_error("%s: depth image %d must be one channel of 2 bytes (got %d x %d bytes)", what, f, im.channels, im.elem_size); return LMX_ERR_SHAPE; }
+    if (im.rows <= 0 || im.cols <= 0 || im.row_stride_bytes < (size_t)im.cols * 2) { set_error("%s: depth image %d is %d x %d with a row stride of %zu bytes", what, f, im.cols, im.rows, im.row_stride_bytes); return LMX_ERR_SHAPE; }
+    if (im.rows != H || im.cols != W) { set_error("%s: depth image %d is %d x %d, image 0 is %d x %d", what, f, im.cols, im.rows, W, H); return LMX_ERR_SHAPE; }
+  }
+  return LMX_OK;
+}
+
+// Stage frame `f` of the caller into slot `slot` of the pinned buffer and queue its copy to the same slot on the device.
+lmx_status queue_frame(lmx_depth_templates* t, const lmx_image& im, int32_t slot, int32_t W, int32_t H) {
+  const size_t frame_bytes = (size_t)W * H * sizeof(uint16_t);
+  uint8_t* h = reinterpret_cast<uint8_t*>(t->h_scene) + frame_bytes * slot;
+  lmx::copy_rows(h, im.data, (size_t)W * 2, im.row_stride_bytes, H);
+  DV_HIP(hipMemcpyAsync(reinterpret_cast<uint8_t*>(t->d_scene) + frame_bytes * slot, h, frame_bytes, hipMemcpyHostToDevice, t->s));
+  return LMX_OK;
+}
+
+// The device half of a depth check on the host's match list: the first n entries of h_jobs against the W x H frames already in d_scene
+// (a job's frame is its slot there): job upload, k_depth_diff, read-back into h_out.  The object's mutex is the caller's to hold.
+lmx_status run_jobs(lmx_depth_templates* t, size_t n, int32_t W, int32_t H) {
+  hipStream_t s = t->s;
+  DV_HIP(hipMemcpyAsync(t->d_jobs, t->h_jobs, n * sizeof(lmx::DepthJob), hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(lmx::k_depth_diff, dim3((unsigned)n), dim3(256), 0, s, t->d_table, t->d_jobs, t->d_scene, W, H, t->d_out);
+  DV_HIP(hipGetLastError());
+  DV_HIP(hipMemcpyAsync(t->h_out, t->d_out, n * sizeof(lmx_depth_diff_t), hipMemcpyDeviceToHost, s));
+  DV_HIP(hipStreamSynchronize(s));
+  return LMX_OK;
+}
+}  // namespace
+
+extern "C" double lmx_depth_value(const lmx_depth_diff_t* diff, double no_value) { return diff ? lmx::dv::value(*diff, no_value) : no_value; }
+
+extern "C" lmx_status lmx_depth_templates_upload_scene(lmx_depth_templates* t, const lmx_image* depth, int32_t n_frames) {
+  return lmx::guarded("lmx_depth_templates_upload_scene", [&]() -> lmx_status {
+    if (!t || !depth) { lmx::set_error("lmx_depth_templates_upload_scene: null argument"); return LMX_ERR_INVALID_ARG; }
+    std::lock_guard<std::mutex> lk(t->m);
+    return lmx::depth_upload_scene(t, depth, n_frames);
+  });
+}
+
+namespace lmx {
+
+std::mutex& depth_templates_mutex(lmx_depth_templates* t) { return t->m; }
+
+DepthSceneInfo depth_templates_scene(const lmx_depth_templates* t) {
+  return DepthSceneInfo{t->device, (int32_t)t->table.size(), t->scene_frames, t->scene_W, t->scene_H};
+}
+
+lmx_status depth_upload_scene(lmx_depth_templates* t, const lmx_image* depth, int32_t n_frames) {
+  if (n_frames < 1) { set_error("lmx_depth_templates_upload_scene: n_frames = %d", n_frames); return LMX_ERR_INVALID_ARG; }
+  if (lmx_status st = check_depth_frames("lmx_depth_templates_upload_scene", depth, n_frames)) return st;
+  const int32_t W = depth[0].cols, H = depth[0].rows;
+  if (lmx_status st = t->ensure_device()) return st;
+  if (lmx_status st = t->wait_scene_copies()) return st;   // the previous scene's copies still read the staging buffer
+  t->scene_frames = 0;
+  if (lmx_status st = t->grow_scene((size_t)W * H * sizeof(uint16_t) * (size_t)n_frames)) return st;
+  for (int32_t f = 0; f < n_frames; ++f)   // each frame on its way while the next is staged
+    if (lmx_status st = queue_frame(t, depth[f], f, W, H)) { t->drain_after_error(); return st; }
+  if (hipError_t e = hipEventRecord(t->scene_ready, t->s)) {
+    t->drain_after_error();
+    set_error("hipEventRecord failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
+    return LMX_ERR_HIP;
+  }
+  t->scene_pending = true;
+  t->scene_frames = n_frames; t->scene_W = W; t->scene_H = H;
+  return LMX_OK;   // no host synchronisation: the transfer overlaps whatever the caller queued before
+}
+
+lmx_status depth_launch_records(lmx_depth_templates* t, hipStream_t s, const lmx_raw_match_t* d_recs, uint32_t n_records, int32_t class_index,
+                                lmx_depth_diff_t* d_diffs) {
+  if (t->scene_frames < 1) { set_error("no scene uploaded: call lmx_depth_templates_upload_scene first"); return LMX_ERR_INVALID_ARG; }
+  DV_HIP(hipStreamWaitEvent(s, t->scene_ready, 0));
+  if (n_records == 0) return LMX_OK;
+  hipLaunchKernelGGL(k_depth_diff_records, dim3(n_records), dim3(256), 0, s, t->d_table, (int32_t)t->table.size(), d_recs, t->d_scene, t->scene_frames,
+                     t->scene_W, t->scene_H, class_index, d_diffs);
+  DV_HIP(hipGetLastError());
+  return LMX_OK;
+}
+
+lmx_status depth_diff_resident(lmx_depth_templates* t, const lmx_match_t* matches, size_t n, int32_t frame, int32_t class_index, lmx_depth_diff_t* out) {
+  if (n == 0) return LMX_OK;
+  if (frame < 0 || frame >= t->scene_frames) { set_error("frame %d is not in the uploaded scene (%d frames)", frame, t->scene_frames); return LMX_ERR_INVALID_ARG; }
+  if (n > 0x7fffffffull) { set_error("%zu matches in one frame", n); return LMX_ERR_INVALID_ARG; }
+  std::memset(out, 0, n * sizeof(lmx_depth_diff_t));
+  const size_t count = t->table.size();
+  t->sel.clear();
+  for (size_t i = 0; i < n; ++i) {
+    const lmx_match_t& m = matches[i];
+    if (class_index >= 0 && m.class_index != class_index) continue;
+    if (m.template_id < 0 || (size_t)m.template_id >= count) continue;   // zeros, as k_depth_diff_records gives; the cluster step refuses the id
+    t->sel.push_back((uint32_t)i);
+  }
+  const size_t n_sel = t->sel.size();
+  if (n_sel == 0) return LMX_OK;
+  if (lmx_status st = t->grow_jobs(n_sel)) return st;
+  for (size_t k = 0; k < n_sel; ++k) {
+    const lmx_match_t& m = matches[t->sel[k]];
+    t->h_jobs[k] = DepthJob{m.x, m.y, m.template_id, frame};
+  }
+  if (lmx_status st = run_jobs(t, n_sel, t->scene_W, t->scene_H)) return st;   // on the object's stream, behind the scene's copies
+  for (size_t k = 0; k < n_sel; ++k) out[t->sel[k]] = t->h_out[k];
+  return LMX_OK;
+}
+
+}  // namespace lmx
+
 extern "C" lmx_status lmx_depth_diff_matches(lmx_depth_templates* t, const lmx_image* depth, int32_t n_frames, const lmx_match_t* matches,
                                              const size_t* offsets, int32_t class_index, lmx_depth_diff_t* out) {
   return lmx::guarded("lmx_depth_diff_matches", [&]() -> lmx_status {
@@ -364,14 +515,8 @@ extern "C" lmx_status lmx_depth_diff_matches(lmx_depth_templates* t, const lmx_i
     if (offsets[0] != 0) { set_error("lmx_depth_diff_matches: offsets[0] = %zu (expected 0)", offsets[0]); return LMX_ERR_INVALID_ARG; }
     for (int32_t f = 0; f < n_frames; ++f)
       if (offsets[f + 1] < offsets[f]) { set_error("lmx_depth_diff_matches: offsets[%d] = %zu is below offsets[%d] = %zu", f + 1, offsets[f + 1], f, offsets[f]); return LMX_ERR_INVALID_ARG; }
+    if (lmx_status st = check_depth_frames("lmx_depth_diff_matches", depth, n_frames)) return st;
     const int32_t W = depth[0].cols, H = depth[0].rows;
-    for (int32_t f = 0; f < n_frames; ++f) {
-      const lmx_image& im = depth[f];
-      if (!im.data) { set_error("lmx_depth_diff_matches: depth image %d has no data", f); return LMX_ERR_INVALID_ARG; }
-      if (im.channels != 1 || im.elem_size != 2) { set_error("lmx_depth_diff_matches: depth image %d must be one channel of 2 bytes (got %d x %d bytes)", f, im.channels, im.elem_size); return LMX_ERR_SHAPE; }
-      if (im.rows <= 0 || im.cols <= 0 || im.row_stride_bytes < (size_t)im.cols * 2) { set_error("lmx_depth_diff_matches: depth image %d is %d x %d with a row stride of %zu bytes", f, im.cols, im.rows, im.row_stride_bytes); return LMX_ERR_SHAPE; }
-      if (im.rows != H || im.cols != W) { set_error("lmx_depth_diff_matches: depth image %d is %d x %d, image 0 is %d x %d", f, im.cols, im.rows, W, H); return LMX_ERR_SHAPE; }
-    }
     const size_t n_matches = offsets[n_frames];
     if (n_matches == 0) return LMX_OK;
     if (!matches || !out) { set_error("lmx_depth_diff_matches: null argument"); return LMX_ERR_INVALID_ARG; }
@@ -396,25 +541,20 @@ extern "C" lmx_status lmx_depth_diff_matches(lmx_depth_templates* t, const lmx_i
     if (n_sel == 0) return LMX_OK;
     if (lmx_status st = t->ensure_device()) return st;
     const size_t frame_bytes = (size_t)W * H * sizeof(uint16_t);
+    // the frames that have matches take the place of an uploaded scene: staged row by row into pinned memory, each on its way while the
+    // next is staged
+    if (lmx_status st = t->wait_scene_copies()) return st;
+    t->scene_frames = 0;
     if (lmx_status st = t->grow_scene(frame_bytes * n_slots)) return st;
     if (lmx_status st = t->grow_jobs(n_sel)) return st;
-    hipStream_t s = t->s;
-    // the frames that have matches: staged row by row into pinned memory, each on its way while the next is staged
-    for (int32_t f = 0; f < n_frames; ++f) {
-      if (t->slot[f] < 0) continue;
-      uint8_t* h = reinterpret_cast<uint8_t*>(t->h_scene) + frame_bytes * t->slot[f];
-      copy_rows(h, depth[f].data, (size_t)W * 2, depth[f].row_stride_bytes, H);
-      DV_HIP(hipMemcpyAsync(reinterpret_cast<uint8_t*>(t->d_scene) + frame_bytes * t->slot[f], h, frame_bytes, hipMemcpyHostToDevice, s));
-    }
+    for (int32_t f = 0; f < n_frames; ++f)
+      if (t->slot[f] >= 0)
+        if (lmx_status st = queue_frame(t, depth[f], t->slot[f], W, H)) { t->drain_after_error(); return st; }
     for (size_t k = 0; k < n_sel; ++k) {
       const lmx_match_t& m = matches[t->sel[k]];
       t->h_jobs[k] = DepthJob{m.x, m.y, m.template_id, t->sel_slot[k]};
     }
-    DV_HIP(hipMemcpyAsync(t->d_jobs, t->h_jobs, n_sel * sizeof(DepthJob), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_depth_diff, dim3((unsigned)n_sel), dim3(256), 0, s, t->d_table, t->d_jobs, t->d_scene, W, H, t->d_out);
-    DV_HIP(hipGetLastError());
-    DV_HIP(hipMemcpyAsync(t->h_out, t->d_out, n_sel * sizeof(lmx_depth_diff_t), hipMemcpyDeviceToHost, s));
-    DV_HIP(hipStreamSynchronize(s));
+    if (lmx_status st = run_jobs(t, n_sel, W, H)) { t->drain_after_error(); return st; }
     for (size_t k = 0; k < n_sel; ++k) out[t->sel[k]] = t->h_out[k];
     return LMX_OK;
   });

@@ -450,6 +450,21 @@ class Detector:
             out.append((m[mo[f]:mo[f + 1]].copy(), c, mem))
         return out
 
+    def collect_clusters_depth(self, n_frames, templates, class_index=-1, no_value=-np.inf, cap_total=1 << 16):
+        """collect_clusters with the clusters ranked by the depth score (lmx_ctx_collect_clusters_depth): `templates` is a DepthTemplates
+        whose upload_scene(depth_frames) was called after the enqueue.  -> list per frame of (matches, diffs, clusters, members), equal
+        to collect + templates.diff + cluster_matches_scored(depth_values(diffs)) bit for bit; no_value is what a match with nothing to
+        compare contributes to its cluster's mean."""
+        m = np.zeros(cap_total, MATCH_DTYPE)
+        d = np.zeros(cap_total, DEPTH_DIFF_DTYPE)
+        cl = np.zeros(cap_total, CLUSTER_DTYPE)
+        mem = np.zeros(cap_total, np.int32)
+        mo = (C.c_size_t * (n_frames + 1))()
+        co = (C.c_size_t * (n_frames + 1))()
+        _lib.check(_lib.lib().lmx_ctx_collect_clusters_depth(self.h, n_frames, templates.h, int(class_index), float(no_value), m.ctypes.data, cap_total, mo,
+                                                             d.ctypes.data, cl.ctypes.data, cap_total, co, mem.ctypes.data, cap_total))
+        return [(m[mo[f]:mo[f + 1]].copy(), d[mo[f]:mo[f + 1]].copy(), cl[co[f]:co[f + 1]].copy(), mem) for f in range(n_frames)]
+
     def raw_matches_ptrs(self):
         rec, cnt, cap = C.c_void_p(), C.c_void_p(), C.c_size_t()
         _lib.check(_lib.lib().lmx_ctx_raw_matches(self.h, C.byref(rec), C.byref(cnt), C.byref(cap)))
@@ -651,6 +666,17 @@ def depth_values(diffs):
     return out
 
 
+def _depth_images(depth_frames):
+    """A uint16 [H, W] array or a list of them -> (the list, its lmx_image descriptors)."""
+    if isinstance(depth_frames, np.ndarray) and depth_frames.ndim == 2:
+        depth_frames = [depth_frames]
+    frames = list(depth_frames)
+    for d in frames:
+        if d.dtype != np.uint16 or d.ndim != 2 or d.strides[1] != 2:
+            raise TypeError("depth frames must be uint16 HxW with contiguous rows (the row stride may be larger)")
+    return frames, (_lib.Image * max(1, len(frames)))(*[_lib.Image(d.ctypes.data, d.shape[0], d.shape[1], 1, 2, d.strides[0]) for d in frames])
+
+
 class DepthTemplates:
     """Device-resident depth renders of a bank's templates, cropped to their silhouette boxes (lmx_depth_templates), and the depth check
     of matches against them (lmx_depth_diff_matches): the depth half of the reference's depth_normal_diff_calc
@@ -710,9 +736,7 @@ class DepthTemplates:
         """depth_frames: a uint16 [H, W] array or a list of them (all of one size; rows may be strided); matches: MATCH_DTYPE records of
         all frames back to back, frame f's at offsets[f]:offsets[f + 1] (default: one frame holding all).  -> DEPTH_DIFF_DTYPE array, one
         record per match; with class_index >= 0 the matches of other classes get zeros."""
-        if isinstance(depth_frames, np.ndarray) and depth_frames.ndim == 2:
-            depth_frames = [depth_frames]
-        frames = list(depth_frames)
+        frames, imgs = _depth_images(depth_frames)
         matches = np.ascontiguousarray(matches, MATCH_DTYPE)
         if offsets is None:
             if len(frames) != 1:
@@ -720,14 +744,17 @@ class DepthTemplates:
             offsets = [0, len(matches)]
         if len(offsets) != len(frames) + 1 or int(offsets[-1]) != len(matches):
             raise ValueError("offsets must have one entry per frame plus one and end at len(matches)")
-        for d in frames:
-            if d.dtype != np.uint16 or d.ndim != 2 or d.strides[1] != 2:
-                raise TypeError("depth frames must be uint16 HxW with contiguous rows (the row stride may be larger)")
-        imgs = (_lib.Image * max(1, len(frames)))(*[_lib.Image(d.ctypes.data, d.shape[0], d.shape[1], 1, 2, d.strides[0]) for d in frames])
         offs = (C.c_size_t * len(offsets))(*[int(v) for v in offsets])
         out = np.zeros(len(matches), DEPTH_DIFF_DTYPE)
         _lib.check(_lib.lib().lmx_depth_diff_matches(self.h, imgs, len(frames), matches.ctypes.data, offs, int(class_index), out.ctypes.data))
         return out
+
+    def upload_scene(self, depth_frames):
+        """The scene of the next Detector.collect_clusters_depth (lmx_depth_templates_upload_scene): a uint16 [H, W] array or a list of
+        them, one per frame of the enqueue.  Returns without waiting for the transfer: call it right after Detector.enqueue.  A later
+        upload_scene replaces the scene; diff() forgets it whenever it has a match to check."""
+        frames, imgs = _depth_images(depth_frames)
+        _lib.check(_lib.lib().lmx_depth_templates_upload_scene(self.h, imgs, len(frames)))
 
     def close(self):
         if getattr(self, "h", None):
@@ -767,6 +794,36 @@ def debug_device_finalize_cluster(records, n_frames, obj_origin_dists, rects, vo
         if status == 1:   # counts[0] is the record count here, not a number of matches written
             n_m = 0
         out.append((m[f, :n_m].copy(), cl[f, :n_c].copy(), mem[f, :n_mem].copy(), status))
+    return (out, counts) if with_counts else out
+
+
+def debug_device_finalize_cluster_depth(records, n_frames, templates, depth_frames, obj_origin_dists, rects, vote_row_col_step, renderer_radius_min,
+                                        renderer_radius_step, cluster_size_thresh=2, class_index=-1, no_value=-np.inf, device=0, with_counts=False):
+    """Test hook (lmx_debug_device_finalize_cluster_depth): debug_device_finalize_cluster for the kernels behind
+    Detector.collect_clusters_depth; depth_frames (one per frame) become `templates`' uploaded scene.  -> list per frame of
+    (matches, diffs, clusters, members, status)."""
+    records = np.ascontiguousarray(records, RAW_MATCH_DTYPE)
+    dists = np.ascontiguousarray(obj_origin_dists, np.float64)
+    rects = np.ascontiguousarray(rects, np.int32).reshape(-1, 4)
+    pp = _lib.ClusterParams(int(vote_row_col_step), float(renderer_radius_min), float(renderer_radius_step), int(cluster_size_thresh))
+    frames, imgs = _depth_images(depth_frames)
+    if len(frames) != n_frames:
+        raise ValueError("one depth frame per frame")
+    nf = max(1, int(n_frames))
+    m = np.zeros((nf, F2_MAX), MATCH_DTYPE)
+    d = np.zeros((nf, F2_MAX), DEPTH_DIFF_DTYPE)
+    cl = np.zeros((nf, F2_MAX), CLUSTER_DTYPE)
+    mem = np.zeros((nf, F2_MAX), np.int32)
+    counts = np.zeros((nf, 4), np.uint32)
+    _lib.check(_lib.lib().lmx_debug_device_finalize_cluster_depth(device, records.ctypes.data, len(records), int(n_frames), templates.h, imgs, int(class_index),
+                                                                  float(no_value), dists.ctypes.data, rects.ctypes.data, len(dists), C.byref(pp), m.ctypes.data,
+                                                                  d.ctypes.data, cl.ctypes.data, mem.ctypes.data, counts.ctypes.data))
+    out = []
+    for f in range(n_frames):
+        n_m, n_c, n_mem, status = (int(v) for v in counts[f])
+        if status == 1:   # counts[0] is the record count here, not a number of matches written
+            n_m = 0
+        out.append((m[f, :n_m].copy(), d[f, :n_m].copy(), cl[f, :n_c].copy(), mem[f, :n_mem].copy(), status))
     return (out, counts) if with_counts else out
 
 
