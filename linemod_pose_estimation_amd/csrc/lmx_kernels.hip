@@ -1196,6 +1196,36 @@ __global__ __launch_bounds__(64 * SC_WAVES_PER_BLOCK) void k_score_coarse_u8(Sco
 // ---------------------------------------------------------------------------------------------------------
 typedef const uint32_t __attribute__((address_space(4))) lmx_cu32_const;   // constant address space: uniform loads become s_load
 
+constexpr int SB_SEG0 = 3;   // groups in the first of the two segments of a block behind the first one; the second takes the other SB_GROUPS - SB_SEG0
+
+// Groups [G0, G0 + NG) of one block: the loads of every live chunk are issued before the first add (one wave-uniform branch per
+// chunk and phase), the NG shifted nibble dwords (<= 12 per nibble, <= 60 per byte for five) are summed before they join the
+// accumulators (<= 252).
+template <int NCH, int G0, int NG>
+__device__ __forceinline__ void score_segment_sb(__amdgpu_buffer_rsrc_t rsrc, const uint32_t (&off)[SB_BLOCK - 1], uint32_t meta, const uint32_t (&lane_off)[NCH],
+                                                 const bool (&chunk_on)[NCH], uint32_t (&acc_lo)[NCH], uint32_t (&acc_hi)[NCH]) {
+  uint32_t v[NCH][3 * NG];
+#pragma unroll
+  for (int k = 0; k < NCH; ++k)
+    if (chunk_on[k]) {
+#pragma unroll
+      for (int i = 0; i < 3 * NG; ++i) v[k][i] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)lane_off[k], (int)off[3 * G0 + i], 0);
+    }
+#pragma unroll
+  for (int k = 0; k < NCH; ++k)
+    if (chunk_on[k]) {
+      uint32_t lo = 0, hi = 0;
+#pragma unroll
+      for (int q = 0; q < NG; ++q) {
+        const uint32_t nib = shifted_dword(v[k][3 * q] + v[k][3 * q + 1] + v[k][3 * q + 2], (meta >> (5 * (G0 + q))) & 31u);
+        lo += nib & 0x0f0f0f0fu;
+        hi += (nib >> 4) & 0x0f0f0f0fu;
+      }
+      acc_lo[k] += lo;
+      acc_hi[k] += hi;
+    }
+}
+
 template <int NCH, bool PRUNE>
 __device__ __forceinline__ void score_pass_sb(const ScoreParams& p, const uint8_t* lm_frame, lmx_cu32_const* row, int n_blocks, int g, int frame, int lane,
                                               int pbase, int positions, int raw_threshold, int nf_total) {
@@ -1222,38 +1252,45 @@ __device__ __forceinline__ void score_pass_sb(const ScoreParams& p, const uint8_
     lane_off[k] = (uint32_t)(k * SC_CHUNK_LANES + lane) * 4u;
   }
   if (!refresh()) return;
-  for (int b = 0; b < n_blocks; ++b) {
-    lmx_cu32_const* blk = row + b * SB_BLOCK;
-    uint32_t off[SB_BLOCK - 1];
-#pragma unroll
-    for (int i = 0; i < SB_BLOCK - 1; ++i) off[i] = blk[i];
-    const uint32_t meta = blk[SB_BLOCK - 1];
-    uint32_t v[NCH][SB_BLOCK - 1];
-#pragma unroll
-    for (int k = 0; k < NCH; ++k)
-      if (chunk_on[k]) {
-#pragma unroll
-        for (int i = 0; i < SB_BLOCK - 1; ++i) v[k][i] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)lane_off[k], (int)off[i], 0);
-      }
-#pragma unroll
-    for (int k = 0; k < NCH; ++k)
-      if (chunk_on[k]) {
-        uint32_t nib[SB_GROUPS];
-#pragma unroll
-        for (int q = 0; q < SB_GROUPS; ++q) nib[q] = shifted_dword(v[k][3 * q] + v[k][3 * q + 1] + v[k][3 * q + 2], (meta >> (5 * q)) & 31u);
-        // nibbles <= 12 each: five of them (<= 60 per byte) are summed before they join the accumulators (<= 252)
-        acc_lo[k] += (nib[0] & 0x0f0f0f0fu) + (nib[1] & 0x0f0f0f0fu) + (nib[2] & 0x0f0f0f0fu) + (nib[3] & 0x0f0f0f0fu) + (nib[4] & 0x0f0f0f0fu);
-        acc_hi[k] += ((nib[0] >> 4) & 0x0f0f0f0fu) + ((nib[1] >> 4) & 0x0f0f0f0fu) + ((nib[2] >> 4) & 0x0f0f0f0fu) + ((nib[3] >> 4) & 0x0f0f0f0fu) +
-                     ((nib[4] >> 4) & 0x0f0f0f0fu);
-      }
-    const int need = raw_threshold + 1 - 4 * (nf_total - (int)(meta >> 25));
+  // One segment = NG whole groups of the block, then the exact bound test.  meta >> 25 counts the real features through the END of the
+  // block; the groups behind the segment hold at most 3 each, so at least that many less have been consumed by its end.  A count that is
+  // too low only lowers `need`: a mid-block test prunes nothing but what is provably dead.  (Padding sits in a row's trailing leftover
+  // groups only -- build_bank_tables -- so the bound is tight everywhere else.)
+  auto segment = [&](auto g0, auto ng, const uint32_t (&off)[SB_BLOCK - 1], uint32_t meta) {
+    constexpr int G0 = decltype(g0)::value, NG = decltype(ng)::value;
+    score_segment_sb<NCH, G0, NG>(rsrc, off, meta, lane_off, chunk_on, acc_lo, acc_hi);
+    const int need = raw_threshold + 1 - 4 * (nf_total - ((int)(meta >> 25) - 3 * (SB_GROUPS - G0 - NG)));
     if (PRUNE && need > 0) {
 #pragma unroll
       for (int k = 0; k < NCH; ++k)
         if (chunk_on[k]) alive[k] = alive[k] && ((bytes_ge(acc_lo[k], need) | bytes_ge(acc_hi[k], need)) != 0);
-      if (!refresh()) return;
+      return refresh();
     }
-  }
+    return true;
+  };
+  using std::integral_constant;
+  // the block's 16 dwords arrive with one s_load_dwordx16 whatever its segments
+  auto block = [&](int b, auto segmented) {
+    lmx_cu32_const* blk = row + b * SB_BLOCK;
+    uint32_t off[SB_BLOCK - 1];
+#pragma unroll
+    for (int i = 0; i < SB_BLOCK - 1; ++i) off[i] = blk[i];
+    uint32_t meta = blk[SB_BLOCK - 1];
+    asm volatile("" : "+s"(meta));   // keeps the row's last dword in the one 16-dword load (the compiler otherwise splits it off behind the buffer loads)
+    if constexpr (!decltype(segmented)::value) {
+      return segment(integral_constant<int, 0>{}, integral_constant<int, SB_GROUPS>{}, off, meta);
+    } else {
+      // 3 + 2 groups: tests after groups 8, 10, 13, 15, ...  (2 + 2 + 1 loads 4 % less and is 0.5 % faster alone, but slower beside the
+      // other lanes' kernels; one group per segment loads 19 % less than a whole block and is 12 % SLOWER: DESIGN section 3)
+      return segment(integral_constant<int, 0>{}, integral_constant<int, SB_SEG0>{}, off, meta) &&
+             segment(integral_constant<int, SB_SEG0>{}, integral_constant<int, SB_GROUPS - SB_SEG0>{}, off, meta);
+    }
+  };
+  // The first block decides for a quarter of the chunks and no earlier test buys anything (profiles/r09_score_schedule_sim.txt): all 15
+  // loads in flight at once, one test.  The full-work build runs every block this way.
+  if (PRUNE && !block(0, std::false_type{})) return;
+  for (int b = PRUNE ? 1 : 0; b < n_blocks; ++b)
+    if (!block(b, std::bool_constant<PRUNE>{})) return;
   // the last block's test ran with need = raw_threshold + 1 (every feature consumed): a lane is alive iff one of its placements passes
 #pragma unroll
   for (int k = 0; k < NCH; ++k) {

@@ -6,32 +6,64 @@ robin -> blocks of 5 triples, leftovers padded) and of what a per-frame BLOCK or
              (sum over the block's real features of the frame's mean response of (modality, label), divided by their number)
 Every processed block costs 15 loads per live chunk, padded entries included, as in the kernel.
 usage: python scripts/sim_score_blocks.py synth|mesh [threshold] [texture]"""
+import os
 import sys
 
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 from linemod_pose_estimation_amd import synth  # noqa: E402
 from oracle import oracle as o  # noqa: E402
 
-kind = sys.argv[1] if len(sys.argv) > 1 else "synth"
-thr = float(sys.argv[2]) if len(sys.argv) > 2 else 92.0
-tex = float(sys.argv[3]) if len(sys.argv) > 3 else 0.6
 W, H, T = 640, 480, 8
-if kind == "mesh":
-    from linemod_pose_estimation_amd import meshsynth as ms
-    bank, _, _, _ = ms.load_bank("memoryChip2")
-    chip, cpu, views = ms.load_mesh("memoryChip2"), ms.load_mesh("cpu_binary"), ms.view_grid()
-    frames = [ms.make_scene(chip, views, seed=7000 + f, n_instances=3, other_tri=cpu, n_other=2, texture=tex)[0] for f in range(3)]
-else:
-    bank = synth.make_bank(3000, seed=20250215)
-    frames = [synth.make_scene(bank, W, H, seed=3000 + f, texture=tex)[0] for f in range(3)]
-od = o.OracleDetector(bank)
-cid, tarr, farr = bank.classes[0]
 L, M = 2, 2
 Wc, Hc = W // 2 // T, H // 2 // T
 cells = Wc * Hc
-rng = np.random.default_rng(0)
-tsel = rng.choice(bank.num_templates(), 300, replace=False)
+
+
+def workload(kind, tex):
+    """-> (bank, three frames): the bench bank and scenes (synth) or the rendered chip bank and scenes (mesh)"""
+    if kind == "mesh":
+        from linemod_pose_estimation_amd import meshsynth as ms
+        bank, _, _, _ = ms.load_bank("memoryChip2")
+        chip, cpu, views = ms.load_mesh("memoryChip2"), ms.load_mesh("cpu_binary"), ms.view_grid()
+        return bank, [ms.make_scene(chip, views, seed=7000 + f, n_instances=3, other_tri=cpu, n_other=2, texture=tex)[0] for f in range(3)]
+    bank = synth.make_bank(3000, seed=20250215)
+    return bank, [synth.make_scene(bank, W, H, seed=3000 + f, texture=tex)[0] for f in range(3)]
+
+
+def rows_of(bank, frames, thr, n_templates=300):
+    """Every (frame, sampled template) with placements: yields (feats per modality as (m, label, e0), the table's arrival order, flat
+    memories [m][label] with a zero tail, placements, raw threshold, feature count, the frame's mean response [m][label])"""
+    od = o.OracleDetector(bank)
+    cid, tarr, farr = bank.classes[0]
+    tsel = np.random.default_rng(0).choice(bank.num_templates(), n_templates, replace=False)
+    for fr in frames:
+        od.match(fr, thr)
+        lm = [od.linear_memory(1, m, (H // 2, W // 2)).astype(np.int32) for m in range(M)]
+        flat = [np.concatenate([x.reshape(8, -1), np.zeros((8, cells + 64), np.int32)], 1) for x in lm]
+        mean_resp = [[float(flat[m][l][:T * T * cells].mean()) for l in range(8)] for m in range(M)]
+        for t in tsel:
+            feats = []
+            for m in range(M):
+                w, h, lv, fb, fc = tarr[(t * L + 1) * M + m]
+                f = farr[fb:fb + fc]
+                e0 = ((f[:, 1] % T) * T + (f[:, 0] % T)) * cells + (f[:, 1] // T) * Wc + (f[:, 0] // T)
+                feats.append([(m, int(l), int(e)) for (l, e) in zip(f[:, 2], e0)])
+            w, h = tarr[(t * L + 1) * M][0], tarr[(t * L + 1) * M][1]
+            wf, hf = (w - 1) // T + 1, (h - 1) // T + 1
+            pos = max(0, min((Hc - hf) * Wc + (Wc - wf) + 1, cells))
+            if pos == 0:
+                continue
+            inter = []
+            i = [0, 0]
+            while i[0] < len(feats[0]) or i[1] < len(feats[1]):
+                for m in range(M):
+                    for _ in range(3):
+                        if i[m] < len(feats[m]):
+                            inter.append(feats[m][i[m]])
+                            i[m] += 1
+            nf = len(inter)
+            yield feats, inter, flat, pos, int(2 * nf + thr / 100 * 2 * nf + 0.5), nf, mean_resp
 
 
 def blocks_of(arrival):
@@ -76,36 +108,15 @@ def loads_of(blocks, order, flat, pos, raw_thr, nf):
     return loads
 
 
-tot = {"table": 0, "sorted": 0, "perframe": 0}
-nblk = {"table": 0, "sorted": 0}
-n = 0
-for fr in frames:
-    od.match(fr, thr)
-    lm = [od.linear_memory(1, m, (H // 2, W // 2)).astype(np.int32) for m in range(M)]
-    flat = [np.concatenate([x.reshape(8, -1), np.zeros((8, cells + 64), np.int32)], 1) for x in lm]
-    mean_resp = [[float(flat[m][l][:T * T * cells].mean()) for l in range(8)] for m in range(M)]
-    for t in tsel:
-        feats = []
-        for m in range(M):
-            w, h, lv, fb, fc = tarr[(t * L + 1) * M + m]
-            f = farr[fb:fb + fc]
-            e0 = ((f[:, 1] % T) * T + (f[:, 0] % T)) * cells + (f[:, 1] // T) * Wc + (f[:, 0] // T)
-            feats.append([(m, int(l), int(e)) for (l, e) in zip(f[:, 2], e0)])
-        w, h = tarr[(t * L + 1) * M][0], tarr[(t * L + 1) * M][1]
-        wf, hf = (w - 1) // T + 1, (h - 1) // T + 1
-        pos = max(0, min((Hc - hf) * Wc + (Wc - wf) + 1, cells))
-        if pos == 0:
-            continue
-        inter = []
-        i = [0, 0]
-        while i[0] < len(feats[0]) or i[1] < len(feats[1]):
-            for m in range(M):
-                for _ in range(3):
-                    if i[m] < len(feats[m]):
-                        inter.append(feats[m][i[m]])
-                        i[m] += 1
-        nf = len(inter)
-        raw_thr = int(2 * nf + thr / 100 * 2 * nf + 0.5)
+def main():
+    kind = sys.argv[1] if len(sys.argv) > 1 else "synth"
+    thr = float(sys.argv[2]) if len(sys.argv) > 2 else 92.0
+    tex = float(sys.argv[3]) if len(sys.argv) > 3 else 0.6
+    bank, frames = workload(kind, tex)
+    tot = {"table": 0, "sorted": 0, "perframe": 0}
+    nblk = {"table": 0, "sorted": 0}
+    n = 0
+    for feats, inter, flat, pos, raw_thr, nf, mean_resp in rows_of(bank, frames, thr):
         b_tab = blocks_of(inter)
         b_sorted = blocks_of(sorted(feats[1], key=lambda ft: ft[1]) + feats[0])
         tot["table"] += loads_of(b_tab, range(len(b_tab)), flat, pos, raw_thr, nf)
@@ -118,5 +129,9 @@ for fr in frames:
         nblk["table"] += len(b_tab)
         nblk["sorted"] += len(b_sorted)
         n += 1
-print(kind, "thr", thr, "tex", tex, "templates", n, " loads per wave:", "  ".join("%s %.1f" % (k, v / n) for k, v in tot.items()),
-      " blocks per row: table %.2f sorted %.2f" % (nblk["table"] / n, nblk["sorted"] / n))
+    print(kind, "thr", thr, "tex", tex, "templates", n, " loads per wave:", "  ".join("%s %.1f" % (k, v / n) for k, v in tot.items()),
+          " blocks per row: table %.2f sorted %.2f" % (nblk["table"] / n, nblk["sorted"] / n))
+
+
+if __name__ == "__main__":
+    main()
