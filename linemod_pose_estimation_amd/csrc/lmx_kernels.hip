@@ -10,7 +10,7 @@
 //   k_spread_linearize_t  a10+a11+a12 spread(T) + computeResponseMaps + linearize x8, one pass, LDS strip, T in {4, 5, 8};
 //                         finer levels: linearised spread bytes only; coarsest level: nibble-packed response memories
 //   k_spread_linearize, k_pack_nibbles   the same for any T / width (byte memories, then two responses per byte)
-//   k_score_coarse_sb     a13+a14+a15 similarity + addSimilarities + threshold scan, one wave per (frame, template), for banks
+//   k_score_coarse_sb     a13+a14+a15 similarity + addSimilarities + threshold scan, one wave per (template, one or two frames), for banks
 //                         with <= 63 coarsest-level features per template (every bank the reference trains): feature table as
 //                         16-dword scalar blocks; k_score_coarse_u8 = its predecessor, k_score_coarse = the generic version
 //   k_refine              a16  similarityLocal + argmax + threshold, one workgroup per candidate; for one or two frames per call
@@ -813,24 +813,30 @@ constexpr int SC_CHUNK_LANES = 63;    // lanes of a chunk that own placements (l
 constexpr int SC_CHUNK_POS = SC_CHUNK_LANES * 8;  // 504 placements per chunk
 
 struct ScoreParams {
+  // what k_score_coarse_sb reads comes first, so that its kernel arguments arrive with one batch of adjacent scalar loads
+  const ScoreInfo* sinfo;          // [G]
+  const uint32_t* blk_off;         // [G][SB_MAX_BLOCKS][SB_BLOCK] scalar-block table (k_score_coarse_sb), or null
+  const int32_t* class_slot;       // [n_classes] -> slot or -1
+  Candidate* cands;      // striped list: kCandStripes stripes of cap / kCandStripes entries, then the spill region (cap entries)
+  uint32_t* stripes;     // kCandStripes + 1 counters, kStripeWords apart
+  uint32_t mod_stride;             // nib_mod_stride
+  int32_t G;
+  int32_t n_frames, xcd_frames;
+  float threshold_frac;  // threshold / 100.f, divided on the host (the same correctly rounded float division the kernels make)
+  uint32_t cap;
+  uint32_t stripe_cap;   // cap / n_stripes
+  uint32_t n_stripes;    // stripes in use (power of two <= kCandStripes); the spill counter is always counter kCandStripes
+  const uint8_t* lm[kMaxModalities];
+  // the other two kernels
   const TemplateInfo* info;
   const TemplateLevelInfo* linfo;  // [G][L]
   const uint32_t* coarse_off;      // [G][M][kFeatStride] nibble-packed offsets
   const uint32_t* uni_off;         // [G][kFeatStride] unified modality-interleaved table (k_score_coarse_u8), or null
-  const uint32_t* blk_off;         // [G][SB_MAX_BLOCKS][SB_BLOCK] scalar-block table (k_score_coarse_sb), or null
-  const ScoreInfo* sinfo;          // [G]
   const uint8_t* feat_count_coarse;  // [G][M] features per (template, modality) at the coarsest level
-  const int32_t* class_slot;       // [n_classes] -> slot or -1
-  const uint8_t* lm[kMaxModalities];
-  uint32_t mod_stride;             // nib_mod_stride
-  int32_t G, L, M;
+  int32_t L, M;
   int32_t nf_max;
-  int32_t n_frames, blocks_per_frame, xcd_frames;
+  int32_t blocks_per_frame;
   float threshold;
-  Candidate* cands;      // striped list: kCandStripes stripes of cap / kCandStripes entries, then the spill region (cap entries)
-  uint32_t* stripes;     // kCandStripes + 1 counters, kStripeWords apart
-  uint32_t cap;
-  uint32_t n_stripes;    // stripes in use (power of two <= kCandStripes); the spill counter is always counter kCandStripes
 };
 
 // The passing placements of one chunk (bit q of pass_mask: the lane's placement j0 + q, raw sum raw8[q]) join the candidate list with
@@ -849,7 +855,7 @@ __device__ __forceinline__ void append_candidates(const ScoreParams& p, int g, i
   }
   const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
   if (total == 0) return;
-  const uint32_t sc = p.cap / p.n_stripes;
+  const uint32_t sc = p.stripe_cap;
   const uint32_t stripe = ((uint32_t)g + 5u * (uint32_t)frame + seq) & (p.n_stripes - 1u);
   uint32_t base = 0;
   if (lane == 0) base = atomicAdd(p.stripes + (size_t)stripe * kStripeWords, total);
@@ -1196,6 +1202,7 @@ __global__ __launch_bounds__(64 * SC_WAVES_PER_BLOCK) void k_score_coarse_u8(Sco
 // ---------------------------------------------------------------------------------------------------------
 typedef const uint32_t __attribute__((address_space(4))) lmx_cu32_const;   // constant address space: uniform loads become s_load
 
+constexpr int SB_FPW = 2;    // frames of its XCD slot that one wave scores (1, 2, 4 and 8 measured: profiles/r10_score_frames_ab.txt)
 constexpr int SB_SEG0 = 3;   // groups in the first of the two segments of a block behind the first one; the second takes the other SB_GROUPS - SB_SEG0
 
 // Groups [G0, G0 + NG) of one block: the loads of every live chunk are issued before the first add (one wave-uniform branch per
@@ -1292,47 +1299,69 @@ __device__ __forceinline__ void score_pass_sb(const ScoreParams& p, const uint8_
   for (int b = PRUNE ? 1 : 0; b < n_blocks; ++b)
     if (!block(b, std::bool_constant<PRUNE>{})) return;
   // the last block's test ran with need = raw_threshold + 1 (every feature consumed): a lane is alive iff one of its placements passes
+  // The few waves that come here work out their lane masks here: with a lane index it can see through, the compiler hoists two dozen
+  // comparisons of the lane with constants in front of the pass and frame loops, and their masks then occupy SGPRs for the wave's whole life.
+  int lane_here = lane;
+  asm volatile("" : "+v"(lane_here));
 #pragma unroll
   for (int k = 0; k < NCH; ++k) {
     if (!chunk_on[k]) continue;   // uniform: the append below is a wave-wide operation (dead lanes pass nothing)
-    const int j0 = pbase + (k * SC_CHUNK_LANES + lane) * 8;
+    const int j0 = pbase + (k * SC_CHUNK_LANES + lane_here) * 8;
     uint32_t raw8[8], pass = 0;
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
       raw8[q] = (((q & 1) ? acc_hi[k] : acc_lo[k]) >> (8 * (q >> 1))) & 0xffu;  // nibble q of the lane's dword
       if (alive[k] && j0 + q < positions && (int)raw8[q] > raw_threshold) pass |= 1u << q;
     }
-    append_candidates(p, g, frame, lane, j0, raw8, pass, (uint32_t)(pbase / SC_CHUNK_POS + k));
+    append_candidates(p, g, frame, lane_here, j0, raw8, pass, (uint32_t)(pbase / SC_CHUNK_POS + k));
   }
 }
 
-template <bool PRUNE>
+// One wave scores its template on up to FPW frames.  What a wave does before its first buffer load -- decoding its work, the kernel
+// arguments, ScoreInfo, the class filter behind it, the raw threshold -- is a chain of dependent scalar-memory round trips and, with one
+// frame per wave, 40 % of its scalar instructions; all of it depends on the template or on the launch alone.
+// Grid: x = 8 * template blocks and y = frame groups when the batch has eight frames or more (x & 7 = the XCD slot k, whose frames are
+// k, k + 8, ...: the linear workgroup index keeps index % 8 == k, see k_score_coarse; a wave takes FPW successive frames of its slot),
+// else x = template blocks and y = frames, FPW = 1.  No division anywhere: what is the same for every wave of the launch comes ready
+// from the host (threshold_frac, stripe_cap).  The passes run inside the frame loop, and a frame's first block comes from the scalar
+// cache again: the other order, with the first block's sixteen dwords and the pass's lane masks kept across the frames, needs more
+// SGPRs than there are (106 with 31-45 spilled to VGPR lanes, against 91 here).
+template <bool PRUNE, int FPW>
 __global__ __launch_bounds__(64 * SC_WAVES_PER_BLOCK) void k_score_coarse_sb(ScoreParams p) {
   const int lane = threadIdx.x & 63;
-  int frame, tblock;  // XCD-aware frame placement, as in k_score_coarse
+  // everything the way to the first buffer load needs from the kernel arguments, asked for at once: left alone, the compiler fetches each
+  // argument behind the early exit in front of its first use, a scalar-memory round trip of its own every time
+  asm volatile("" ::"s"(p.sinfo), "s"(p.blk_off), "s"(p.class_slot), "s"(p.stripes), "s"(p.G), "s"(p.n_frames), "s"(p.xcd_frames), "s"(p.threshold_frac), "s"(p.mod_stride), "s"(p.lm[0]));
+  int frame0, tblock;
   if (p.xcd_frames) {
-    const int k = blockIdx.x & 7, sidx = blockIdx.x >> 3;
-    frame = k + 8 * (sidx / p.blocks_per_frame);
-    tblock = sidx % p.blocks_per_frame;
-    if (frame >= p.n_frames) return;
+    tblock = blockIdx.x >> 3;
+    frame0 = (blockIdx.x & 7) + 8 * FPW * blockIdx.y;
   } else {
-    frame = blockIdx.x / p.blocks_per_frame;
-    tblock = blockIdx.x % p.blocks_per_frame;
+    tblock = blockIdx.x;
+    frame0 = blockIdx.y;
   }
+  if (frame0 >= p.n_frames) return;
   const int g = __builtin_amdgcn_readfirstlane(tblock * SC_WAVES_PER_BLOCK + (threadIdx.x >> 6));
   if (g >= p.G) return;
-  const ScoreInfo si = p.sinfo[g];
-  if (p.class_slot[si.class_index] < 0) return;
-  const int positions = si.positions;
-  const int nf = si.nf_total;
+  // once per wave, whatever its frames: the template's ScoreInfo, the class filter, the raw threshold, the row and its block count
+  // (both tables through the constant address space, like the row: scalar loads whatever stands in front of them)
+  lmx_cu32_const* sip = (lmx_cu32_const*)(uintptr_t)(p.sinfo + g);
+  const int positions = (int)sip[0], nf = (int)sip[1], class_index = (int)sip[2];
+  const uint32_t groups = sip[3];
+  if ((int)((lmx_cu32_const*)(uintptr_t)p.class_slot)[class_index] < 0) return;
   if (positions <= 0 || nf <= 0) return;
-  const int raw_threshold = (int)(2 * nf + (p.threshold / 100.f) * (2 * nf) + 0.5f);
-  const uint8_t* lm_frame = p.lm[0] + (size_t)frame * p.mod_stride;
+  const int raw_threshold = (int)(2 * nf + p.threshold_frac * (2 * nf) + 0.5f);
   lmx_cu32_const* row = (lmx_cu32_const*)(uintptr_t)(p.blk_off + (size_t)g * (SB_BLOCK * SB_MAX_BLOCKS));
-  const int n_blocks = (int)((si.groups >> 16) & 0xffu);
-  int pbase = 0;
-  for (; pbase + SC_CHUNK_POS < positions; pbase += 2 * SC_CHUNK_POS) score_pass_sb<2, PRUNE>(p, lm_frame, row, n_blocks, g, frame, lane, pbase, positions, raw_threshold, nf);
-  if (pbase < positions) score_pass_sb<1, PRUNE>(p, lm_frame, row, n_blocks, g, frame, lane, pbase, positions, raw_threshold, nf);
+  const int n_blocks = (int)((groups >> 16) & 0xffu);
+  // per frame only the base of the buffer descriptor moves; every accumulator and live flag starts afresh inside score_pass_sb
+  const uint8_t* lm_frame = p.lm[0] + (size_t)frame0 * p.mod_stride;
+  const int frame_end = FPW == 1 ? frame0 + 1 : min(p.n_frames, frame0 + 8 * FPW);
+#pragma unroll 1
+  for (int frame = frame0; frame < frame_end; frame += 8, lm_frame += 8 * (size_t)p.mod_stride) {
+    int pbase = 0;
+    for (; pbase + SC_CHUNK_POS < positions; pbase += 2 * SC_CHUNK_POS) score_pass_sb<2, PRUNE>(p, lm_frame, row, n_blocks, g, frame, lane, pbase, positions, raw_threshold, nf);
+    if (pbase < positions) score_pass_sb<1, PRUNE>(p, lm_frame, row, n_blocks, g, frame, lane, pbase, positions, raw_threshold, nf);
+  }
 }
 
 // =========================================================================================================
@@ -1948,7 +1977,9 @@ void launch_score_coarse(hipStream_t s, const DeviceBankView& bank, const LevelG
   p.mod_stride = g.nib_mod_stride;
   p.G = bank.G; p.L = bank.L; p.M = bank.M; p.nf_max = bank.nf_max_coarse;
   p.threshold = threshold;
+  p.threshold_frac = threshold / 100.f;
   p.cands = cands; p.stripes = stripes_of_header(header); p.cap = cap; p.n_stripes = (uint32_t)n_stripes;
+  p.stripe_cap = cap / (uint32_t)n_stripes;
   if (bank.G <= 0) return;
   p.n_frames = n_frames;
   p.blocks_per_frame = (bank.G + SC_WAVES_PER_BLOCK - 1) / SC_WAVES_PER_BLOCK;
@@ -1958,12 +1989,23 @@ void launch_score_coarse(hipStream_t s, const DeviceBankView& bank, const LevelG
   p.blk_off = bank.uni_ok ? bank.coarse_blk : nullptr;
   p.sinfo = bank.sinfo;
   const int variant = score_kernel_variant(bank);
-  const dim3 grid((unsigned)(p.blocks_per_frame * frame_slots)), block(64 * SC_WAVES_PER_BLOCK);
+  const dim3 block(64 * SC_WAVES_PER_BLOCK);
   with_bool(bank.score_no_prune, [&](auto no_prune) {   // LMX_SCORE_NO_PRUNE: similarity()'s full work, same candidates (see score_pass)
     constexpr bool PRUNE = !decltype(no_prune)::value;
-    void (*kernel)(ScoreParams) = k_score_coarse_sb<PRUNE>;
-    if (variant == 1) kernel = k_score_coarse_u8<PRUNE>;
-    else if (variant != 2) kernel = k_score_coarse<PRUNE>;
+    if (variant == 2) {
+      // k_score_coarse_sb: a wave scores its template on up to SB_FPW frames of its XCD slot (frames k, k + 8, ...); a batch with one frame per
+      // slot, and the small batches that keep one frame per wave, run the one-frame build
+      const int per_slot = (n_frames + 7) / 8;
+      const int fpw = p.xcd_frames && per_slot > 1 ? SB_FPW : 1;
+      const dim3 grid = p.xcd_frames ? dim3(8u * (unsigned)p.blocks_per_frame, (unsigned)((per_slot + fpw - 1) / fpw)) : dim3((unsigned)p.blocks_per_frame, (unsigned)n_frames);
+      void (*kernel)(ScoreParams) = k_score_coarse_sb<PRUNE, SB_FPW>;
+      if (fpw == 1) kernel = k_score_coarse_sb<PRUNE, 1>;
+      hipLaunchKernelGGL(kernel, grid, block, 0, s, p);
+      return;
+    }
+    const dim3 grid((unsigned)(p.blocks_per_frame * frame_slots));
+    void (*kernel)(ScoreParams) = k_score_coarse_u8<PRUNE>;
+    if (variant != 1) kernel = k_score_coarse<PRUNE>;
     hipLaunchKernelGGL(kernel, grid, block, 0, s, p);
   });
 }
