@@ -457,8 +457,9 @@ lmx_status lmx_cluster_matches(const lmx_match_t* matches, size_t n_matches, con
 /* As lmx_cluster_matches, but a cluster's score is the mean of match_values[i] over its members (in voting order) instead of the mean
  * similarity: with match_values[i] = (double)matches[i].similarity the two are equal bit for bit.  This is the slot of the reference's
  * second cluster score, getClusterScore over depth_normal_diff_calc (src/rgbdDetector.cpp:147-282, 576-584; commented out at both call
- * sites, :109-112 and :123-126, for its cost), with the normal term left out: that score is 1 / exp(mean depth difference in metres), exp is monotonic, so
- * match_values[i] = -(double)sum_abs_mm / (n_valid * 1000.0) of lmx_depth_diff_matches ranks the clusters in the same order.  A match
+ * sites, :109-112 and :123-126, for its cost).  With the depth term alone that score is 1 / exp(mean depth difference in metres), exp is monotonic, so
+ * match_values[i] = -(double)sum_abs_mm / (n_valid * 1000.0) of lmx_depth_diff_matches ranks the clusters in the same order; with the normal
+ * term too, match_values[i] = lmx_match_value of lmx_normal_diff_matches' two results (the section on the normal term below).  A match
  * with n_valid == 0 has no such value; what it gets is the caller's choice (-HUGE_VAL sends every cluster that holds one to the end:
  * the Python helper's choice; leaving such matches out before the call is the other).  A cluster whose mean is NaN is refused
  * (LMX_ERR_INVALID_ARG): the score order would be undefined. */
@@ -597,8 +598,9 @@ double     lmx_depth_value(const lmx_depth_diff_t* diff, double no_value);
  * For EVERY input matches, diffs, clusters (score included) and members equal, bit for bit,
  *     lmx_ctx_collect;  lmx_depth_diff_matches(templates, depth, n, matches, offsets, class_index, diffs);
  *     per frame lmx_cluster_matches_scored with match_values[i] = lmx_depth_value(&diffs[i], no_value)
- * -- that composition stays the one to use for values the caller computes himself (the normal term of depth_normal_diff_calc, a learned
- * score) and for matches he filtered before clustering.  class_index >= 0: matches of other classes get zero diffs, hence no_value.
+ * -- that composition stays the one to use for values the caller computes himself (a learned score) and for matches he filtered before
+ * clustering; the normal term of depth_normal_diff_calc has entry points of its own: lmx_normal_diff_matches and
+ * lmx_ctx_collect_clusters_depth_normal below.  class_index >= 0: matches of other classes get zero diffs, hence no_value.
  * no_value: -HUGE_VAL sends every cluster that holds a match with nothing to compare to the end (the Python helper depth_values' choice).
  * LMX_ERR_INVALID_ARG, the enqueue staying outstanding, when: no side-car is set; templates lives on another device; no scene is uploaded,
  * or its frame count / width / height differ from the enqueue's frame count / the context's frame size; lmx_depth_templates_count differs
@@ -608,6 +610,68 @@ lmx_status lmx_ctx_collect_clusters_depth(lmx_ctx* ctx, int32_t n_frames, lmx_de
                                           lmx_match_t* matches, size_t cap_matches, size_t* match_offsets,
                                           lmx_depth_diff_t* diffs /* parallel to matches; may be NULL */,
                                           lmx_cluster_t* clusters, size_t cap_clusters, size_t* cluster_offsets, int32_t* members, size_t cap_members);
+
+/* ---- the normal term of the second cluster score ------------------------------------------------------------------------------------------
+ * The other half of depth_normal_diff_calc (src/rgbdDetector.cpp:284-359): the mean angle between the surface normals of the template's
+ * rendered depth and of the scene depth over the pixels both cover.  The depth term cannot tell a wall at the right distance from the
+ * object; this one can.  Definition (csrc/lmx_normal_verify.hpp; the repository's own: the reference takes its normals from OpenCV's rgbd
+ * module, RGBD_NORMALS_METHOD_LINEMOD, which is not part of it -- DESIGN.md, deviations):
+ *   normal of a pixel   for a uint16-mm image D (reads outside the image or crop give 0): invalid iff d = D[y][x] is 0 or >= distance_threshold;
+ *                       else DepthNormal's least squares over the eight taps at offsets +-5 (a tap counts iff |tap - d| < difference_threshold),
+ *                       det / ddx / ddy in 64-bit integers as the depth quantiser computes them; nx = (float)fx * (float)ddx,
+ *                       ny = (float)fy * (float)ddy, nz = -(float)(det * d); s = sqrtf(nx*nx + ny*ny + nz*nz) without contraction; invalid
+ *                       unless s > 0; q_c = (int16)rintf((n_c * (1.0f / s)) * 16384.0f).  Stored as four int16 {qx, qy, qz, valid}, all zeros
+ *                       when invalid.  Bit-equal between the CPU build of the header and gfx950.
+ *   angle of a pair     integer differences of the stored normals, c2 = dx^2 + dy^2 + dz^2 in 64 bits, c = sqrtf((float)c2),
+ *                       i = min(16384, (int)rintf(c * 0.5f)), angle in microradians = table[i], table[i] = llrint(2e6 * asin(min(1, i / 16384.0)))
+ *                       (lmx_normal_angle_table: built on the host in double and uploaded; resolution 122 urad; identical normals give 0).
+ *   sums of a match     a crop pixel counts iff it counts for the depth term and both normals are valid: n_normal of them, sum_angle_urad
+ *                       their angles' sum in 64 bits (order-independent, hence the same for every reduction shape).
+ *   value of a match    lmx_match_value = -(sum_abs_mm / (n_valid * 1000.0) + sum_angle_urad / (n_normal * 1e6)) in double, no_value when
+ *                       n_valid == 0 or n_normal == 0 (or a NULL argument).  A cluster's score is the mean of it over the members in voting
+ *                       order: the logarithm of the reference's 1 / exp(a) * 1 / exp(b), so clusters rank in the same order, and
+ *                       exp(score) is the reference's number when every member has something to compare.
+ * Template normals are computed on the crop, zero-extended: outside the silhouette the render is 0 anyway; an object that touches the
+ * render's border is a documented deviation.
+ * enable_normals computes the normals of every crop once (k_normal_map_crops) and keeps them next to the crops; a second call with other
+ * parameters recomputes.  lmx_depth_templates_device_bytes then also counts 8 bytes per crop element (rows padded as the depth crops':
+ * four times the crops' bytes) and 8 bytes of table per template.  An object that never calls it allocates and launches nothing new.
+ * Scene normals are computed once per scene (k_normal_map_frames), when a normal-scored call first needs them, behind the scene's event.
+ * fx, fy: focal lengths in pixels, above 0 and at most 1e6 (no float of the normal can overflow); both thresholds >= 1 (upstream's
+ * DepthNormal: 50 and 2000). */
+typedef struct lmx_normal_params { double fx, fy; int32_t difference_threshold, distance_threshold; } lmx_normal_params;
+typedef struct lmx_normal_diff_t { int64_t sum_angle_urad; int32_t n_normal; int32_t reserved; } lmx_normal_diff_t;
+lmx_status lmx_normal_angle_table(uint32_t* out /*[16385]*/);
+lmx_status lmx_depth_templates_enable_normals(lmx_depth_templates* templates, const lmx_normal_params* params);
+/* reads template id's normals back from the device; LMX_ERR_INVALID_ARG before enable_normals */
+lmx_status lmx_depth_templates_get_normals(const lmx_depth_templates* templates, int32_t id, int16_t* out /*[h][w][4]*/);
+/* lmx_depth_diff_matches with both terms in one pass over each crop (k_verify_diff): the same arguments, the same staging, the same rule
+ * that the uploaded scene is forgotten, the same errors, plus LMX_ERR_INVALID_ARG before enable_normals.  out[i] and, unless it is NULL,
+ * ddiffs[i] belong to matches[i]; ddiffs equals what lmx_depth_diff_matches gives, bit for bit. */
+lmx_status lmx_normal_diff_matches(lmx_depth_templates* templates, const lmx_image* depth, int32_t n_frames, const lmx_match_t* matches,
+                                   const size_t* offsets, int32_t class_index, lmx_depth_diff_t* ddiffs /* may be NULL */, lmx_normal_diff_t* out);
+double     lmx_match_value(const lmx_depth_diff_t* ddiff, const lmx_normal_diff_t* ndiff, double no_value);
+/* lmx_ctx_collect_clusters_depth with both terms:
+ *     lmx_ctx_enqueue;  lmx_depth_templates_upload_scene;  lmx_ctx_collect_clusters_depth_normal
+ *   ndiffs[i]         = the normal sums of matches[i] (parallel to matches; may be NULL; written when matches is),
+ *   clusters[k].score = the mean over the cluster's members, in voting order, of lmx_match_value(diffs[i], ndiffs[i], no_value).
+ * On the consumer stream: wait for the scene's event, k_normal_map_frames if the scene has no normals yet, k_verify_diff_records, the
+ * third form of k_f2_finalize_cluster, one synchronisation; frames the device chain hands back are finished on the host inside the call.
+ * Equal, bit for bit, to lmx_ctx_collect + lmx_normal_diff_matches + per frame lmx_cluster_matches_scored on lmx_match_value.  Every
+ * condition of lmx_ctx_collect_clusters_depth holds; LMX_ERR_INVALID_ARG, the enqueue staying outstanding, also before enable_normals. */
+lmx_status lmx_ctx_collect_clusters_depth_normal(lmx_ctx* ctx, int32_t n_frames, lmx_depth_templates* templates, int32_t class_index, double no_value,
+                                                 lmx_match_t* matches, size_t cap_matches, size_t* match_offsets,
+                                                 lmx_depth_diff_t* diffs /* parallel to matches; may be NULL */,
+                                                 lmx_normal_diff_t* ndiffs /* parallel to matches; may be NULL */,
+                                                 lmx_cluster_t* clusters, size_t cap_clusters, size_t* cluster_offsets, int32_t* members, size_t cap_members);
+/* Device time of the object's kernels that run per call: with profiling on, a pair of events surrounds each launch; kernel_time waits for
+ * the launches in flight and returns the sum of their times and their number since profiling was switched on.  Off (the default) no
+ * event is created or recorded. */
+enum { LMX_DT_K_NORMAL_MAP_FRAMES = 0, LMX_DT_K_VERIFY_DIFF_RECORDS = 1, LMX_DT_K_VERIFY_DIFF = 2, LMX_DT_K_DEPTH_DIFF_RECORDS = 3 };
+lmx_status lmx_depth_templates_set_profiling(lmx_depth_templates* templates, int32_t on);
+lmx_status lmx_depth_templates_kernel_time(lmx_depth_templates* templates, int32_t kernel, double* total_ms, int64_t* launches);
+/* Test hook: the normals of frame `frame` of the uploaded scene as the device holds them (computed now if no call has needed them yet). */
+lmx_status lmx_debug_scene_normals(lmx_depth_templates* templates, int32_t frame, int16_t* out /*[H][W][4]*/);
 
 /* ---- introspection (stage-level parity tests, profiling) ------------------------------------------------- */
 enum {

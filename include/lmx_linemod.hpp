@@ -279,6 +279,35 @@ class DepthTemplates {
   // could be compared).
   static double value(const lmx_depth_diff_t& d, double no_value = -HUGE_VAL) { return lmx_depth_value(&d, no_value); }
 
+  // The normal term (lmx_depth_templates_enable_normals): computes and keeps the normals of every crop; needed before normals(),
+  // normalDiff() and lmx_ctx_collect_clusters_depth_normal.  fx, fy: the focal lengths of the camera whose depth frames are checked.
+  void enableNormals(double fx, double fy, int difference_threshold = 50, int distance_threshold = 2000) {
+    const lmx_normal_params p = {fx, fy, difference_threshold, distance_threshold};
+    check(lmx_depth_templates_enable_normals(h_, &p));
+  }
+  // Template id's normals, read back from the device: [h][w][4] int16 = {qx, qy, qz, valid}, a unit normal times 16384.
+  std::vector<int16_t> normals(int id) const {
+    int32_t r[4] = {0, 0, 0, 0};
+    check(lmx_depth_templates_rect(h_, id, r));
+    std::vector<int16_t> out((size_t)r[2] * (size_t)r[3] * 4);
+    check(lmx_depth_templates_get_normals(h_, id, out.data()));
+    return out;
+  }
+  // diff() with both terms in one pass over each crop: out[i] belongs to matches[i]; ddiffs (may be null) receives what diff() gives.
+  std::vector<lmx_normal_diff_t> normalDiff(const std::vector<Image>& depth, const std::vector<lmx_match_t>& matches, const std::vector<size_t>& offsets,
+                                            std::vector<lmx_depth_diff_t>* ddiffs = nullptr, int class_index = -1) {
+    if (offsets.size() != depth.size() + 1 || offsets.back() != matches.size()) throw Exception(LMX_ERR_SHAPE, "DepthTemplates::normalDiff: offsets must hold one entry per frame plus one and end at matches.size()");
+    std::vector<lmx_image> imgs;
+    for (const Image& d : depth) imgs.push_back(d.c());
+    std::vector<lmx_normal_diff_t> out(matches.size());
+    if (ddiffs) ddiffs->resize(matches.size());
+    check(lmx_normal_diff_matches(h_, imgs.data(), (int32_t)imgs.size(), matches.data(), offsets.data(), class_index, ddiffs ? ddiffs->data() : nullptr, out.data()));
+    return out;
+  }
+  // The value lmx_ctx_collect_clusters_depth_normal ranks by: minus (mean depth difference in metres + mean normal angle in radians);
+  // exp of a cluster's score is the reference's getClusterScore when every member has something to compare.
+  static double value(const lmx_depth_diff_t& d, const lmx_normal_diff_t& n, double no_value = -HUGE_VAL) { return lmx_match_value(&d, &n, no_value); }
+
   // The scene of the next collectClustersDepth: returns without waiting, so call it right after the enqueue.
   void uploadScene(const std::vector<Image>& depth) {
     std::vector<lmx_image> imgs;

@@ -2,9 +2,10 @@
 rgbdDetector::linemod_detection / cv::linemod::Detector::match call surface.
 
 Only what the hot path needs lives here: csrc/ (HIP kernels + C ABI -> liblmx.so), the host-side mirror of the
-reference interface (detector.py; NativeBank.train_mesh / render_views: the trainer from a mesh; DepthTemplates: the depth check of matches), the bank container (bank.py), the synthetic bank/scene generator the tests
+reference interface (detector.py; NativeBank.train_mesh / render_views: the trainer from a mesh; DepthTemplates: the depth check of matches and, after enable_normals, the normal term), the bank container (bank.py), the synthetic bank/scene generator the tests
 and bench use (synth.py) and the template-shard helper for multi-GPU runs (dist.py).
 """
 from .bank import TemplateBank  # noqa: F401
 from .detector import Detector, NativeBank, PinnedArena, linemod_detection, merge_raw, render_views, MATCH_DTYPE, RAW_MATCH_DTYPE  # noqa: F401
 from .detector import DepthTemplates, DEPTH_DIFF_DTYPE, cluster_matches_scored, depth_values  # noqa: F401
+from .detector import NORMAL_DIFF_DTYPE, normal_values, normal_angle_table  # noqa: F401

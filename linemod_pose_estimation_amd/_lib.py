@@ -24,6 +24,8 @@ SYMBOLS = [
     "lmx_cluster_matches_scored", "lmx_depth_templates_from_mesh", "lmx_depth_templates_from_crops", "lmx_depth_templates_count", "lmx_depth_templates_rect",
     "lmx_depth_templates_get", "lmx_depth_templates_device_bytes", "lmx_depth_templates_free", "lmx_depth_diff_matches",
     "lmx_depth_value", "lmx_depth_templates_upload_scene", "lmx_ctx_collect_clusters_depth", "lmx_debug_device_finalize_cluster_depth",
+    "lmx_normal_angle_table", "lmx_depth_templates_enable_normals", "lmx_depth_templates_get_normals", "lmx_normal_diff_matches", "lmx_match_value",
+    "lmx_ctx_collect_clusters_depth_normal", "lmx_debug_scene_normals", "lmx_depth_templates_set_profiling", "lmx_depth_templates_kernel_time",
 ]
 
 (LMX_OK, LMX_ERR_INVALID_ARG, LMX_ERR_SHAPE, LMX_ERR_NO_DEVICE, LMX_ERR_HIP, LMX_ERR_OVERFLOW, LMX_ERR_IO,
@@ -84,6 +86,14 @@ class MeshView(C.Structure):
 
 class DepthDiff(C.Structure):
     _fields_ = [("sum_abs_mm", C.c_int64), ("n_valid", C.c_int32), ("n_template", C.c_int32)]
+
+
+class NormalDiff(C.Structure):
+    _fields_ = [("sum_angle_urad", C.c_int64), ("n_normal", C.c_int32), ("reserved", C.c_int32)]
+
+
+class NormalParams(C.Structure):
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("difference_threshold", C.c_int32), ("distance_threshold", C.c_int32)]
 
 
 class GroupDesc(C.Structure):
@@ -260,6 +270,17 @@ def lib():
                                                  C.POINTER(C.c_size_t), vp, C.c_size_t]
     L.lmx_debug_device_finalize_cluster_depth.argtypes = [C.c_int32, vp, C.c_size_t, C.c_int32, vp, C.POINTER(Image), C.c_int32, C.c_double, vp, vp, C.c_size_t,
                                                           C.POINTER(ClusterParams), vp, vp, vp, vp, vp]
+    L.lmx_normal_angle_table.argtypes = [vp]
+    L.lmx_depth_templates_enable_normals.argtypes = [vp, C.POINTER(NormalParams)]
+    L.lmx_depth_templates_get_normals.argtypes = [vp, C.c_int32, vp]
+    L.lmx_normal_diff_matches.argtypes = [vp, C.POINTER(Image), C.c_int32, vp, C.POINTER(C.c_size_t), C.c_int32, vp, vp]
+    L.lmx_match_value.argtypes = [C.POINTER(DepthDiff), C.POINTER(NormalDiff), C.c_double]
+    L.lmx_match_value.restype = C.c_double
+    L.lmx_ctx_collect_clusters_depth_normal.argtypes = [vp, C.c_int32, vp, C.c_int32, C.c_double, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, vp, vp, C.c_size_t,
+                                                        C.POINTER(C.c_size_t), vp, C.c_size_t]
+    L.lmx_debug_scene_normals.argtypes = [vp, C.c_int32, vp]
+    L.lmx_depth_templates_set_profiling.argtypes = [vp, C.c_int32]
+    L.lmx_depth_templates_kernel_time.argtypes = [vp, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     L.lmx_ctx_set_cluster_sidecar.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(ClusterParams)]
     L.lmx_ctx_collect_clusters.argtypes = [vp, C.c_int32, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t), vp, C.c_size_t]
     L.lmx_ctx_debug_read.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_size_t]

@@ -12,6 +12,7 @@
 
 #include "lmx_ctx.hpp"
 #include "lmx_depth_verify.hpp"
+#include "lmx_normal_verify.hpp"
 
 using namespace lmx;
 
@@ -196,12 +197,14 @@ lmx_status lmx_ctx_set_cluster_sidecar(lmx_ctx* c, const double* obj_origin_dist
   return LMX_OK;
 }
 
-// What lmx_ctx_collect_clusters_depth adds to lmx_ctx_collect_clusters; null = the unscored call
+// What lmx_ctx_collect_clusters_depth and lmx_ctx_collect_clusters_depth_normal add to lmx_ctx_collect_clusters; null = the unscored call
 struct DepthScore {
   lmx_depth_templates* templates;
   int32_t class_index;
   double no_value;
   lmx_depth_diff_t* diffs;   // parallel to the caller's matches; may be null
+  bool normal;               // score by lmx_match_value of both terms instead of lmx_depth_value
+  lmx_normal_diff_t* ndiffs; // normal only: parallel to the caller's matches; may be null
 };
 
 // The body of lmx_ctx_collect_clusters and lmx_ctx_collect_clusters_depth (`what` names the entry point in messages).  With `depth`, the
@@ -217,6 +220,7 @@ static lmx_status collect_clusters_impl(const char* what, lmx_ctx* c, int32_t n_
     const DepthSceneInfo sc = depth_templates_scene(depth->templates);
     if (sc.device != c->device) { set_error("%s: the templates live on device %d, the context on device %d", what, sc.device, c->device); return LMX_ERR_INVALID_ARG; }
     if ((size_t)sc.count != c->f2_templates) { set_error("%s: %d depth templates but the side-car holds %zu templates", what, sc.count, c->f2_templates); return LMX_ERR_INVALID_ARG; }
+    if (depth->normal && !sc.normals) { set_error("%s: call lmx_depth_templates_enable_normals first", what); return LMX_ERR_INVALID_ARG; }
     if (sc.n_frames < 1) { set_error("%s: no scene uploaded: call lmx_depth_templates_upload_scene first", what); return LMX_ERR_INVALID_ARG; }
     if (sc.n_frames != n_frames) { set_error("%s: the uploaded scene holds %d frames, the enqueue had %d", what, sc.n_frames, n_frames); return LMX_ERR_INVALID_ARG; }
     if (sc.W != c->desc.width || sc.H != c->desc.height) { set_error("%s: the uploaded scene is %d x %d, the context's frames are %d x %d", what, sc.W, sc.H, c->desc.width, c->desc.height); return LMX_ERR_INVALID_ARG; }
@@ -242,6 +246,11 @@ static lmx_status collect_clusters_impl(const char* what, lmx_ctx* c, int32_t n_
     LMX_HIP(hipHostMalloc((void**)&c->h_f2_diffs, F * F2_MAX * sizeof(lmx_depth_diff_t), hipHostMallocMapped));
     LMX_HIP(hipHostGetDevicePointer((void**)&c->d_f2_diffs, c->h_f2_diffs, 0));
     if (lmx_status st = dev_alloc(c, &c->d_f2_diff_scratch, F * 2 * F2_MAX, false)) return st;
+  }
+  if (depth && depth->normal && !c->h_f2_ndiffs) {
+    LMX_HIP(hipHostMalloc((void**)&c->h_f2_ndiffs, F * F2_MAX * sizeof(lmx_normal_diff_t), hipHostMallocMapped));
+    LMX_HIP(hipHostGetDevicePointer((void**)&c->d_f2_ndiffs, c->h_f2_ndiffs, 0));
+    if (lmx_status st = dev_alloc(c, &c->d_f2_ndiff_scratch, F * 2 * F2_MAX, false)) return st;
   }
   LMX_HIP(hipEventSynchronize(c->done[slot]));
   c->outstanding -= 1;
@@ -272,10 +281,23 @@ static lmx_status collect_clusters_impl(const char* what, lmx_ctx* c, int32_t n_
       LMX_HIP(hipMalloc((void**)&c->d_f2_rec_diffs, cap * sizeof(lmx_depth_diff_t)));
       c->f2_rec_diffs_cap = cap;
     }
+    if (depth->normal && n_match > c->f2_rec_ndiffs_cap) {
+      if (c->d_f2_rec_ndiffs) (void)hipFree(c->d_f2_rec_ndiffs);
+      c->d_f2_rec_ndiffs = nullptr; c->f2_rec_ndiffs_cap = 0;
+      const size_t cap = std::max<size_t>(n_match, 4096);
+      LMX_HIP(hipMalloc((void**)&c->d_f2_rec_ndiffs, cap * sizeof(lmx_normal_diff_t)));
+      c->f2_rec_ndiffs_cap = cap;
+    }
     // the scene's copies, one workgroup per raw record (the count is the header's, read above), the scored chain: one synchronisation
-    if (lmx_status st = depth_launch_records(depth->templates, s, p.recs, n_match, depth->class_index, c->d_f2_rec_diffs)) return st;
+    if (lmx_status st = depth_launch_records(depth->templates, s, p.recs, n_match, depth->class_index, c->d_f2_rec_diffs,
+                                             depth->normal ? c->d_f2_rec_ndiffs : nullptr)) return st;
     p.diffs = c->d_f2_rec_diffs; p.out_diffs = c->d_f2_diffs; p.diff_scratch = c->d_f2_diff_scratch; p.no_value = depth->no_value;
-    launch_f2_scored(s, p);
+    if (depth->normal) {
+      p.ndiffs = c->d_f2_rec_ndiffs; p.out_ndiffs = c->d_f2_ndiffs; p.ndiff_scratch = c->d_f2_ndiff_scratch;
+      launch_f2_normal(s, p);
+    } else {
+      launch_f2_scored(s, p);
+    }
   } else {
     launch_f2(s, p);
   }
@@ -300,6 +322,7 @@ static lmx_status collect_clusters_impl(const char* what, lmx_ctx* c, int32_t n_
   std::vector<lmx_cluster_t> fc;
   std::vector<int32_t> fmem;
   std::vector<lmx_depth_diff_t> fd;
+  std::vector<lmx_normal_diff_t> fn;
   std::vector<double> fv;
   for (int f = 0; f < n_frames; ++f) {
     size_t nm = 0, nc = 0, nmem = 0;
@@ -308,6 +331,7 @@ static lmx_status collect_clusters_impl(const char* what, lmx_ctx* c, int32_t n_
       if (cap_matches) fm.assign(all_m + (size_t)F2_MAX * f, all_m + (size_t)F2_MAX * f + nm);
       else fm.clear();
       if (depth && depth->diffs && cap_matches) fd.assign(c->h_f2_diffs + (size_t)F2_MAX * f, c->h_f2_diffs + (size_t)F2_MAX * f + nm);
+      if (depth && depth->ndiffs && cap_matches) fn.assign(c->h_f2_ndiffs + (size_t)F2_MAX * f, c->h_f2_ndiffs + (size_t)F2_MAX * f + nm);
       fc.assign(all_c + (size_t)F2_MAX * f, all_c + (size_t)F2_MAX * f + nc);
       fmem.assign(all_mem + (size_t)F2_MAX * f, all_mem + (size_t)F2_MAX * f + nmem);
     } else {
@@ -323,8 +347,9 @@ static lmx_status collect_clusters_impl(const char* what, lmx_ctx* c, int32_t n_
       lmx_status hs;
       if (depth) {   // the final matches against the resident scene (k_depth_diff), then the host chain on their values
         fd.resize(std::max<size_t>(nm, 1)); fv.resize(std::max<size_t>(nm, 1));
-        if ((hs = depth_diff_resident(depth->templates, fm.data(), nm, f, depth->class_index, fd.data())) != LMX_OK) return hs;
-        for (size_t i = 0; i < nm; ++i) fv[i] = dv::value(fd[i], depth->no_value);
+        if (depth->normal) fn.resize(std::max<size_t>(nm, 1));
+        if ((hs = depth_diff_resident(depth->templates, fm.data(), nm, f, depth->class_index, fd.data(), depth->normal ? fn.data() : nullptr)) != LMX_OK) return hs;
+        for (size_t i = 0; i < nm; ++i) fv[i] = depth->normal ? nv::value(fd[i], fn[i], depth->no_value) : dv::value(fd[i], depth->no_value);
         hs = lmx_cluster_matches_scored(fm.data(), nm, fv.data(), c->f2_host_dists.data(), c->f2_host_rects.data(), c->f2_templates, &c->f2_params, fc.data(),
                                         fc.size(), &got, fmem.data(), fmem.size());
       } else {
@@ -340,6 +365,7 @@ static lmx_status collect_clusters_impl(const char* what, lmx_ctx* c, int32_t n_
       else if (nm) {
         std::memcpy(matches + mpos, fm.data(), nm * sizeof(lmx_match_t));   // (an empty vector's data() may be null)
         if (depth && depth->diffs) std::memcpy(depth->diffs + mpos, fd.data(), nm * sizeof(lmx_depth_diff_t));
+        if (depth && depth->ndiffs) std::memcpy(depth->ndiffs + mpos, fn.data(), nm * sizeof(lmx_normal_diff_t));
       }
     }
     if (cpos + nc <= cap_clusters && mempos + nmem <= cap_members) {
@@ -377,8 +403,25 @@ lmx_status lmx_ctx_collect_clusters_depth(lmx_ctx* c, int32_t n_frames, lmx_dept
     return LMX_ERR_INVALID_ARG;
   }
   std::lock_guard<std::mutex> lk(depth_templates_mutex(templates));   // held for the whole call: the scene and the object's buffers stay put
-  const DepthScore depth{templates, class_index, no_value, diffs};
+  const DepthScore depth{templates, class_index, no_value, diffs, false, nullptr};
   return collect_clusters_impl("lmx_ctx_collect_clusters_depth", c, n_frames, &depth, matches, cap_matches, match_offsets, clusters, cap_clusters,
+                               cluster_offsets, members, cap_members);
+  });
+}
+
+lmx_status lmx_ctx_collect_clusters_depth_normal(lmx_ctx* c, int32_t n_frames, lmx_depth_templates* templates, int32_t class_index, double no_value,
+                                                 lmx_match_t* matches, size_t cap_matches, size_t* match_offsets, lmx_depth_diff_t* diffs,
+                                                 lmx_normal_diff_t* ndiffs, lmx_cluster_t* clusters, size_t cap_clusters, size_t* cluster_offsets,
+                                                 int32_t* members, size_t cap_members) {
+  return lmx::guarded("lmx_ctx_collect_clusters_depth_normal", [&]() -> lmx_status {
+  if (no_value != no_value) { set_error("lmx_ctx_collect_clusters_depth_normal: no_value is not a number (the score order would be undefined)"); return LMX_ERR_INVALID_ARG; }
+  if (!c || !templates || !match_offsets || !cluster_offsets || (cap_matches > 0 && !matches) || (cap_clusters > 0 && !clusters) || (cap_members > 0 && !members)) {
+    set_error("lmx_ctx_collect_clusters_depth_normal: null argument");
+    return LMX_ERR_INVALID_ARG;
+  }
+  std::lock_guard<std::mutex> lk(depth_templates_mutex(templates));   // held for the whole call: the scene and the object's buffers stay put
+  const DepthScore depth{templates, class_index, no_value, diffs, true, ndiffs};
+  return collect_clusters_impl("lmx_ctx_collect_clusters_depth_normal", c, n_frames, &depth, matches, cap_matches, match_offsets, clusters, cap_clusters,
                                cluster_offsets, members, cap_members);
   });
 }

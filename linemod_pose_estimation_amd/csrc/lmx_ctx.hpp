@@ -223,6 +223,12 @@ struct lmx_ctx {
   lmx_depth_diff_t* d_f2_diff_scratch = nullptr; // [F][2][F2_MAX]
   lmx_depth_diff_t* d_f2_rec_diffs = nullptr;    // one per raw record of the slot being collected; grows on demand
   size_t f2_rec_diffs_cap = 0;
+  // the same four for the normal sums of lmx_ctx_collect_clusters_depth_normal (nothing allocated before its first call)
+  lmx_normal_diff_t* h_f2_ndiffs = nullptr;
+  lmx_normal_diff_t* d_f2_ndiffs = nullptr;
+  lmx_normal_diff_t* d_f2_ndiff_scratch = nullptr;
+  lmx_normal_diff_t* d_f2_rec_ndiffs = nullptr;
+  size_t f2_rec_ndiffs_cap = 0;
   // stats / profiling
   int64_t stat_cands = 0, stat_matches = 0;
   uint32_t profiling = 0;  // bitmask over kernel ids

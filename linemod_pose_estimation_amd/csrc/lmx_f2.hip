@@ -22,10 +22,14 @@
 // The SCORED instantiation (lmx_ctx_collect_clusters_depth) ranks clusters by the reference's other score, the depth difference of
 // depth_normal_diff_calc: every raw record comes with a lmx_depth_diff_t (k_depth_diff_records, lmx_verify.hip) that travels with it through
 // B - D in two rows of device memory (LDS is full) and lands next to its final match; F averages dv::value of it instead of the similarity.
+// The NORMAL instantiation (lmx_ctx_collect_clusters_depth_normal) carries a lmx_normal_diff_t (k_verify_diff_records) the same way in two
+// rows of its own -- the 64 KB of LDS the sorts need at 2048 records leave no room for a second 16-byte payload, and an index into the
+// per-record arrays would make lane 0's loop in F chase it through the unsorted list -- and averages nv::value of the pair.
 #include <hip/hip_runtime.h>
 
 #include "lmx_internal.hpp"
 #include "lmx_depth_verify.hpp"
+#include "lmx_normal_verify.hpp"
 #include "lmx_sort_block.hpp"
 #include "lmx_sort_emul.hpp"
 
@@ -92,8 +96,11 @@ __global__ __launch_bounds__(256) void k_debug_block_sort(const float* sim, cons
   for (int i = threadIdx.x; i < n; i += 256) perm[i] = s_tag[i];
 }
 
-template <bool SCORED>
+enum { F2_SIMILARITY = 0, F2_DEPTH = 1, F2_DEPTH_NORMAL = 2 };   // what a cluster's score is the mean of
+
+template <int MODE>
 __device__ __forceinline__ void f2_finalize_cluster(const F2Params& p) {
+  constexpr bool SCORED = MODE != F2_SIMILARITY, NORMAL = MODE == F2_DEPTH_NORMAL;
   constexpr int NMAX = F2_MAX;
   constexpr int PER = (NMAX + 255) / 256;   // items per thread
   __shared__ unsigned long long s_key[NMAX];
@@ -113,6 +120,8 @@ __device__ __forceinline__ void f2_finalize_cluster(const F2Params& p) {
   // there, read by lane 0 in F); each read has a __syncthreads() between it and the write
   lmx_depth_diff_t* const d_parked = SCORED ? p.diff_scratch + (size_t)frame * 2 * NMAX : nullptr;
   lmx_depth_diff_t* const d_final = SCORED ? d_parked + NMAX : nullptr;
+  lmx_normal_diff_t* const n_parked = NORMAL ? p.ndiff_scratch + (size_t)frame * 2 * NMAX : nullptr;   // the same two rows for the normal sums
+  lmx_normal_diff_t* const n_final = NORMAL ? n_parked + NMAX : nullptr;
   if (tid == 0) { s_n = 0; s_nfinal = 0; }
   __syncthreads();
   // A: this frame's records (order arbitrary), identified by their index in the slot's list
@@ -165,6 +174,7 @@ __device__ __forceinline__ void f2_finalize_cluster(const F2Params& p) {
     for (int i = tid; i < n; i += 256) {
       const lmx_raw_match_t r = p.recs[rec_of_pos[cnt]];
       if constexpr (SCORED) d_parked[i] = p.diffs[rec_of_pos[cnt]];
+      if constexpr (NORMAL) n_parked[i] = p.ndiffs[rec_of_pos[cnt]];
       ++cnt;
       s_sim[i] = r.similarity; s_tid[i] = r.template_id; s_x[i] = (short)r.x; s_y[i] = (short)r.y; s_cls[i] = (unsigned short)r.class_index;
     }
@@ -224,6 +234,11 @@ __device__ __forceinline__ void f2_finalize_cluster(const F2Params& p) {
         d_final[d] = dd;
         p.out_diffs[(size_t)frame * NMAX + d] = dd;
       }
+      if constexpr (NORMAL) {
+        const lmx_normal_diff_t nd = n_parked[s_perm[j]];
+        n_final[d] = nd;
+        p.out_ndiffs[(size_t)frame * NMAX + d] = nd;
+      }
     }
   }
   __syncthreads();
@@ -281,7 +296,8 @@ __device__ __forceinline__ void f2_finalize_cluster(const F2Params& p) {
         int X = 0, Y = 0, Wd = 0, Ht = 0;
         for (int k = b; k < e; ++k) {
           const int j = (int)(s_key[k] & 2047u);
-          if constexpr (SCORED) sum += dv::value(d_final[j], p.no_value);
+          if constexpr (NORMAL) sum += nv::value(d_final[j], n_final[j], p.no_value);
+          else if constexpr (SCORED) sum += dv::value(d_final[j], p.no_value);
           else sum += (double)s_sim[j];
           const int32_t* r = p.rects + (size_t)s_tid[j] * 4;
           X += s_x[j]; Y += s_y[j]; Wd += r[2]; Ht += r[3];
@@ -326,9 +342,10 @@ __device__ __forceinline__ void f2_finalize_cluster(const F2Params& p) {
   }
 }
 
-// the two instantiations as kernels of their own (the unscored one keeps the name profiles know)
-__global__ __launch_bounds__(256) void k_f2_finalize_cluster(F2Params p) { f2_finalize_cluster<false>(p); }
-__global__ __launch_bounds__(256) void k_f2_finalize_cluster_scored(F2Params p) { f2_finalize_cluster<true>(p); }
+// the three instantiations as kernels of their own (the unscored one keeps the name profiles know)
+__global__ __launch_bounds__(256) void k_f2_finalize_cluster(F2Params p) { f2_finalize_cluster<F2_SIMILARITY>(p); }
+__global__ __launch_bounds__(256) void k_f2_finalize_cluster_scored(F2Params p) { f2_finalize_cluster<F2_DEPTH>(p); }
+__global__ __launch_bounds__(256) void k_f2_finalize_cluster_normal(F2Params p) { f2_finalize_cluster<F2_DEPTH_NORMAL>(p); }
 
 void launch_debug_block_sort(hipStream_t s, const float* sim, const int* tid, int n, int* perm, unsigned long long* spill) {
   hipLaunchKernelGGL(k_debug_block_sort, dim3(1), dim3(256), 0, s, sim, tid, n, perm, spill);
@@ -340,6 +357,10 @@ void launch_f2(hipStream_t s, const F2Params& p) {
 
 void launch_f2_scored(hipStream_t s, const F2Params& p) {
   hipLaunchKernelGGL(k_f2_finalize_cluster_scored, dim3((unsigned)p.n_frames), dim3(256), 0, s, p);
+}
+
+void launch_f2_normal(hipStream_t s, const F2Params& p) {
+  hipLaunchKernelGGL(k_f2_finalize_cluster_normal, dim3((unsigned)p.n_frames), dim3(256), 0, s, p);
 }
 
 }  // namespace lmx

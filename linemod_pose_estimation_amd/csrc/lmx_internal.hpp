@@ -322,21 +322,29 @@ struct F2Params {
   lmx_depth_diff_t* out_diffs;       // [n_frames][F2_MAX] in final-match order, next to out_matches (written, never read: may be mapped host memory)
   lmx_depth_diff_t* diff_scratch;    // [n_frames][2][F2_MAX] device memory: a frame's diffs by insertion position, then by final position
   double no_value;
+  // the NORMAL form only (launch_f2_normal): the same three for the normal sums; the score is the mean of nv::value(diff, ndiff, no_value)
+  const lmx_normal_diff_t* ndiffs;
+  lmx_normal_diff_t* out_ndiffs;
+  lmx_normal_diff_t* ndiff_scratch;
 };
 void launch_f2(hipStream_t s, const F2Params& p);
 void launch_f2_scored(hipStream_t s, const F2Params& p);
+void launch_f2_normal(hipStream_t s, const F2Params& p);
 
 // ---- depth check against a resident scene (lmx_verify.hip), for the scored consumer chain (lmx_collect.cpp, lmx_debug.cpp) --------------
-struct DepthSceneInfo { int32_t device, count, n_frames, W, H; };   // n_frames 0: no scene uploaded
+struct DepthSceneInfo { int32_t device, count, n_frames, W, H, normals; };   // n_frames 0: no scene uploaded; normals: enable_normals was called
 std::mutex& depth_templates_mutex(lmx_depth_templates* t);
 DepthSceneInfo depth_templates_scene(const lmx_depth_templates* t);   // the four below: the object's mutex is the caller's to hold
 // lmx_depth_templates_upload_scene without taking the mutex (depth must not be null)
 lmx_status depth_upload_scene(lmx_depth_templates* t, const lmx_image* depth, int32_t n_frames);
-// `s` waits for the scene's copies, then k_depth_diff_records: d_diffs[i] for d_recs[i], i < n_records (no launch for 0)
+// `s` waits for the scene's copies, then k_depth_diff_records: d_diffs[i] for d_recs[i], i < n_records (no launch for 0).  With d_ndiffs:
+// the scene's normals on `s` if nobody has computed them, then k_verify_diff_records, which fills both
 lmx_status depth_launch_records(lmx_depth_templates* t, hipStream_t s, const lmx_raw_match_t* d_recs, uint32_t n_records, int32_t class_index,
-                                lmx_depth_diff_t* d_diffs);
+                                lmx_depth_diff_t* d_diffs, lmx_normal_diff_t* d_ndiffs = nullptr);
 // host matches of scene frame `frame` through k_depth_diff (synchronous); other classes and template ids outside the table get zeros
-lmx_status depth_diff_resident(lmx_depth_templates* t, const lmx_match_t* matches, size_t n, int32_t frame, int32_t class_index, lmx_depth_diff_t* out);
+// (nout: the normal sums too, through k_verify_diff)
+lmx_status depth_diff_resident(lmx_depth_templates* t, const lmx_match_t* matches, size_t n, int32_t frame, int32_t class_index, lmx_depth_diff_t* out,
+                               lmx_normal_diff_t* nout = nullptr);
 void launch_debug_block_sort(hipStream_t s, const float* sim, const int* tid, int n, int* perm, unsigned long long* spill);
 
 struct PullEntry { uint64_t src; uint64_t row_stride; };  // one caller-owned pinned image (device-visible address)

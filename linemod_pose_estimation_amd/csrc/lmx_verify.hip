@@ -14,12 +14,21 @@
 //                  the scene lmx_depth_templates_upload_scene left on the device: the input of the scored consumer chain (lmx_f2.hip)
 //   scene          one pinned staging buffer and one device buffer per object.  lmx_depth_diff_matches stages the frames that have matches
 //                  and waits for its results; upload_scene stages all frames, records an event behind their copies and returns
+// The normal term (lmx_depth_templates_enable_normals, lmx_normal_diff_matches; arithmetic: lmx_normal_verify.hpp), only for an object that
+// enabled it:
+//   k_normal_map_crops / k_normal_map_frames   depth -> packed normals, one pixel per lane, the nine depth reads straight from L2 under the
+//                  in-image predicate, one 8-byte store per pixel.  Crops: once per enable_normals, all crops in one launch, into chunks that
+//                  mirror the depth chunks (same pitch: the padding's normals are zeros).  Scene frames: once per scene, when a normal-scored
+//                  call first needs them, on that call's stream behind the scene's event
+//   k_verify_diff / k_verify_diff_records   the walk of k_depth_diff with both terms in one pass (verify_diff_walk): the two stored
+//                  normals of a pixel are read next to its two depths, their angle comes out of the chord table in global memory
 #include <algorithm>
 #include <cstring>
 #include <memory>
 
 #include "lmx_internal.hpp"
 #include "lmx_depth_verify.hpp"
+#include "lmx_normal_verify.hpp"
 #include "lmx_mesh_raster.hpp"
 
 namespace lmx {
@@ -31,6 +40,7 @@ struct DepthCrop {          // table entry: 24 bytes per template
 };
 struct DepthJob { int32_t x, y, template_id, frame; };   // frame: index among the frames uploaded for this call
 static_assert(sizeof(DepthCrop) == 24 && sizeof(DepthJob) == 16 && sizeof(lmx_depth_diff_t) == 16, "layouts the kernels rely on");
+static_assert(sizeof(lmx_normal_diff_t) == 16 && sizeof(nv::Packed) == 8, "layouts the kernels rely on");
 
 constexpr int kCropBatch = 32;   // views rendered per batch (as lmx_mesh_render)
 struct CropBatch { uint64_t dst_elem[kCropBatch]; };   // where view v's crop starts in the batch's chunk, in elements
@@ -135,6 +145,137 @@ __global__ __launch_bounds__(256) void k_depth_diff_records(const DepthCrop* __r
   depth_diff_walk(crops[r.template_id], r.x, r.y, scene + (size_t)r.frame * H * W, W, H, &diffs[blockIdx.x]);
 }
 
+// ---- the normal term ---------------------------------------------------------------------------------------------------------------------
+// Normals of one w x h depth image with rows of `pitch` elements into dst[h][pitch], by the workgroups blockIdx.x, blockIdx.x + gridDim.x, ...
+// of 256 pixels each; elements past w (a crop's padding) get zeros.  Every depth read lies inside [0, w) x [0, h) (nv::depth_or_zero).
+__device__ __forceinline__ void normal_map_image(const uint16_t* __restrict__ src, int w, int h, int pitch, nv::Packed* __restrict__ dst, const nv::Params p) {
+  const int n = h * pitch;   // <= 2^28 (dv::kMaxCropSide) for a crop, W * H of a camera frame for the scene
+  for (int q = blockIdx.x * 256 + threadIdx.x; q < n; q += gridDim.x * 256) {
+    const int y = q / pitch, x = q - y * pitch;
+    dst[q] = x < w ? nv::normal_at(src, w, h, (size_t)pitch, x, y, p) : (nv::Packed)0;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_normal_map_crops(const DepthCrop* __restrict__ crops, nv::Packed* const* __restrict__ normals, nv::Params p) {
+  const DepthCrop c = crops[blockIdx.y];
+  if (c.w <= 0 || c.h <= 0) return;
+  normal_map_image(c.data, c.w, c.h, c.pitch, normals[blockIdx.y], p);
+}
+
+__global__ __launch_bounds__(256) void k_normal_map_frames(const uint16_t* __restrict__ scene, int W, int H, nv::Packed* __restrict__ out, nv::Params p) {
+  const size_t frame = (size_t)blockIdx.y * H * W;
+  normal_map_image(scene + frame, W, H, W, out + frame, p);
+}
+
+// depth_diff_walk with both terms: the same lanes take the same vectors, the depth sums are dv's own (add_template_pixel, add_met_pixel).
+// A lane reads its eight crop normals as four aligned 16-byte vectors next to the crop's depths; the scene's depth and the scene's normal
+// of a pixel are read side by side, each under the in-image predicate and nowhere else (the normal where the crop's normal is valid, which
+// implies t != 0), so the chain of dependent loads is crop -> scene -> table.  Every lane of the workgroup must arrive; lane 0 stores the
+// two 16-byte results.
+__device__ __forceinline__ void verify_diff_walk(const DepthCrop c, const nv::Packed* __restrict__ cn, int32_t x, int32_t y, const uint16_t* __restrict__ frame,
+                                                 const nv::Packed* __restrict__ fn, int W, int H, const uint32_t* __restrict__ table,
+                                                 lmx_depth_diff_t* __restrict__ out, lmx_normal_diff_t* __restrict__ nout) {
+  __shared__ unsigned long long s_sum[4], s_ang[4];
+  __shared__ int s_valid[4], s_templ[4], s_norm[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (c.w <= 0 || c.h <= 0) {   // an empty crop: the same for every lane of the workgroup, before any barrier
+    if (tid == 0) { *reinterpret_cast<int4*>(out) = make_int4(0, 0, 0, 0); *reinterpret_cast<int4*>(nout) = make_int4(0, 0, 0, 0); }
+    return;
+  }
+  const int vpr = c.pitch / dv::kPitchAlign;
+  const int lanes_per_row = vpr < 64 ? vpr : 64;
+  const int rows_per_pass = 64 / lanes_per_row;
+  const int sub = lane / lanes_per_row, v0 = lane - sub * lanes_per_row;
+  dv::Sums a = {0, 0, 0};
+  nv::Sums b = {0, 0};
+  for (int row0 = wave * rows_per_pass; row0 < c.h; row0 += 4 * rows_per_pass) {
+    const int i = row0 + sub;
+    if (sub >= rows_per_pass || i >= c.h) continue;
+    int32_t Y = 0;
+    const bool row_in = dv::scene_row(y, i, H, &Y);
+    const uint16_t* trow = c.data + (size_t)i * c.pitch;
+    const nv::Packed* nrow = cn + (size_t)i * c.pitch;
+    const uint16_t* srow = frame + (size_t)Y * W;     // Y = 0 when the row lies outside: never read then
+    const nv::Packed* snrow = fn + (size_t)Y * W;
+    for (int v = v0; v < vpr; v += lanes_per_row) {
+      const int col0 = v * dv::kPitchAlign;
+      const uint4 q = load_global_16(trow + col0);    // past w: the padding, zeros
+      const uint32_t word[4] = {q.x, q.y, q.z, q.w};
+      // the crop's eight normals: 64 contiguous, 16-byte aligned bytes (the padding's are zeros, like its depths)
+      nv::Packed tn[dv::kPitchAlign], sn[dv::kPitchAlign];
+#pragma unroll
+      for (int k = 0; k < dv::kPitchAlign / 2; ++k) {
+        const uint4 n2 = load_global_16(reinterpret_cast<const uint16_t*>(nrow + col0 + 2 * k));
+        tn[2 * k] = (nv::Packed)n2.x | ((nv::Packed)n2.y << 32);
+        tn[2 * k + 1] = (nv::Packed)n2.z | ((nv::Packed)n2.w << 32);
+      }
+      uint16_t t[dv::kPitchAlign], s[dv::kPitchAlign];
+#pragma unroll
+      for (int e = 0; e < dv::kPitchAlign; ++e) {     // every load first: neither scene read waits for the other
+        t[e] = (uint16_t)(word[e >> 1] >> (16 * (e & 1)));
+        int32_t X = 0;
+        const bool in = row_in && dv::scene_col(x, col0 + e, W, &X);
+        s[e] = (in && t[e] != 0) ? srow[X] : (uint16_t)0;
+        sn[e] = (in && nv::valid(tn[e])) ? snrow[X] : (nv::Packed)0;     // a valid crop normal has t != 0
+      }
+#pragma unroll
+      for (int e = 0; e < dv::kPitchAlign; ++e) {
+        dv::add_template_pixel(t[e], &a);
+        dv::add_met_pixel(t[e], s[e], &a);
+        if (s[e] != 0) nv::add_met_normals(tn[e], sn[e], table, &b);     // s != 0 only where the pixel met the scene
+      }
+    }
+  }
+  unsigned long long sum = a.sum_abs_mm, ang = b.sum_angle_urad;
+  int nvld = a.n_valid, nt = a.n_template, nn = b.n_normal;
+  for (int off = 32; off > 0; off >>= 1) {
+    sum += __shfl_down(sum, off, 64);
+    ang += __shfl_down(ang, off, 64);
+    nvld += __shfl_down(nvld, off, 64);
+    nt += __shfl_down(nt, off, 64);
+    nn += __shfl_down(nn, off, 64);
+  }
+  if (lane == 0) { s_sum[wave] = sum; s_ang[wave] = ang; s_valid[wave] = nvld; s_templ[wave] = nt; s_norm[wave] = nn; }
+  __syncthreads();
+  if (tid == 0) {
+    sum = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
+    ang = s_ang[0] + s_ang[1] + s_ang[2] + s_ang[3];
+    nvld = s_valid[0] + s_valid[1] + s_valid[2] + s_valid[3];
+    nt = s_templ[0] + s_templ[1] + s_templ[2] + s_templ[3];
+    nn = s_norm[0] + s_norm[1] + s_norm[2] + s_norm[3];
+    *reinterpret_cast<int4*>(out) = make_int4((int)(uint32_t)sum, (int)(uint32_t)(sum >> 32), nvld, nt);
+    *reinterpret_cast<int4*>(nout) = make_int4((int)(uint32_t)ang, (int)(uint32_t)(ang >> 32), nn, 0);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_verify_diff(const DepthCrop* __restrict__ crops, nv::Packed* const* __restrict__ normals, const DepthJob* __restrict__ jobs,
+                                                     const uint16_t* __restrict__ scene, const nv::Packed* __restrict__ scene_normals, int W, int H,
+                                                     const uint32_t* __restrict__ table, lmx_depth_diff_t* __restrict__ out, lmx_normal_diff_t* __restrict__ nout) {
+  const DepthJob job = jobs[blockIdx.x];
+  const size_t frame = (size_t)job.frame * H * W;
+  verify_diff_walk(crops[job.template_id], normals[job.template_id], job.x, job.y, scene + frame, scene_normals + frame, W, H, table, &out[blockIdx.x],
+                   &nout[blockIdx.x]);
+}
+
+// One workgroup per RAW record, as k_depth_diff_records: a record that is no job gets zeros in both results.
+__global__ __launch_bounds__(256) void k_verify_diff_records(const DepthCrop* __restrict__ crops, nv::Packed* const* __restrict__ normals, int32_t count,
+                                                             const lmx_raw_match_t* __restrict__ recs, const uint16_t* __restrict__ scene,
+                                                             const nv::Packed* __restrict__ scene_normals, int32_t n_frames, int W, int H, int32_t class_index,
+                                                             const uint32_t* __restrict__ table, lmx_depth_diff_t* __restrict__ diffs,
+                                                             lmx_normal_diff_t* __restrict__ ndiffs) {
+  const lmx_raw_match_t r = recs[blockIdx.x];
+  if (r.template_id < 0 || r.template_id >= count || r.frame < 0 || r.frame >= n_frames || (class_index >= 0 && r.class_index != class_index)) {
+    if (threadIdx.x == 0) {
+      *reinterpret_cast<int4*>(&diffs[blockIdx.x]) = make_int4(0, 0, 0, 0);
+      *reinterpret_cast<int4*>(&ndiffs[blockIdx.x]) = make_int4(0, 0, 0, 0);
+    }
+    return;
+  }
+  const size_t frame = (size_t)r.frame * H * W;
+  verify_diff_walk(crops[r.template_id], normals[r.template_id], r.x, r.y, scene + frame, scene_normals + frame, W, H, table, &diffs[blockIdx.x],
+                   &ndiffs[blockIdx.x]);
+}
+
 }  // namespace
 }  // namespace lmx
 
@@ -169,6 +310,50 @@ struct lmx_depth_templates {
   std::vector<uint32_t> sel;             // scratch of a call: the matches it computes
   std::vector<int32_t> sel_slot;         // scratch of a call: the uploaded frame of each of them
   std::vector<int32_t> slot;             // scratch of a call: frame -> uploaded frame, or -1
+  // the normal term (lmx_depth_templates_enable_normals): nothing below is allocated, and no kernel of it launched, before that call
+  bool normals_on = false;
+  bool ncrops_ready = false;             // the crops' normals for nparams are on the device (an object without pixels defers them)
+  lmx::nv::Params nparams = {0.0f, 0.0f, 0, 0};
+  lmx::nv::Packed* d_ncrops = nullptr;   // every crop's normals back to back, each [h][pitch] as its depth crop (8 bytes for 2)
+  std::vector<lmx::nv::Packed*> ntable;  // host copy of d_ntable: where template i's normals start (null for an empty crop)
+  lmx::nv::Packed** d_ntable = nullptr;
+  uint32_t* d_angle = nullptr;           // the chord -> angle table, nv::kAngleTableSize entries
+  lmx::nv::Packed* d_scene_normals = nullptr;   // [frames][H][W] next to d_scene, computed when first needed
+  size_t scene_normals_cap = 0;          // bytes
+  bool scene_normals_valid = false;      // they belong to the frames now in d_scene
+  hipEvent_t normals_ready = nullptr;    // recorded behind the kernel that computed them (it may run on a caller's stream)
+  lmx_normal_diff_t *d_nout = nullptr, *h_nout = nullptr;   // as d_out / h_out
+  size_t nout_cap = 0;
+  // lmx_depth_templates_set_profiling: a pair of events around each launch of the kernels below, read out by ..._kernel_time
+  enum { PK_NORMAL_MAP_FRAMES, PK_VERIFY_DIFF_RECORDS, PK_VERIFY_DIFF, PK_DEPTH_DIFF_RECORDS, PK_COUNT };
+  struct ProfEvent { int kernel; hipEvent_t start, stop; };
+  bool profiling = false;
+  std::vector<ProfEvent> prof_pending;
+  double prof_ms[PK_COUNT] = {};
+  int64_t prof_launches[PK_COUNT] = {};
+  // around a launch on stream `on`: begin returns the slot end takes (-1: profiling is off or an event could not be made)
+  int prof_begin(int kernel, hipStream_t on) {
+    if (!profiling) return -1;
+    ProfEvent e{kernel, nullptr, nullptr};
+    if (hipEventCreate(&e.start) != hipSuccess || hipEventCreate(&e.stop) != hipSuccess || hipEventRecord(e.start, on) != hipSuccess) {
+      if (e.start) (void)hipEventDestroy(e.start);
+      if (e.stop) (void)hipEventDestroy(e.stop);
+      return -1;
+    }
+    prof_pending.push_back(e);
+    return (int)prof_pending.size() - 1;
+  }
+  void prof_end(int slot, hipStream_t on) {
+    if (slot >= 0) (void)hipEventRecord(prof_pending[(size_t)slot].stop, on);
+  }
+  void prof_drain() {
+    for (const ProfEvent& e : prof_pending) {
+      float ms = 0.0f;
+      if (hipEventSynchronize(e.stop) == hipSuccess && hipEventElapsedTime(&ms, e.start, e.stop) == hipSuccess) { prof_ms[e.kernel] += ms; prof_launches[e.kernel] += 1; }
+      (void)hipEventDestroy(e.start); (void)hipEventDestroy(e.stop);
+    }
+    prof_pending.clear();
+  }
 
   lmx_status ensure_device() {
     int ndev = 0;
@@ -214,6 +399,60 @@ struct lmx_depth_templates {
     jobs_cap = cap;
     return LMX_OK;
   }
+  lmx_status grow_nout(size_t n) {
+    if (n <= nout_cap) return LMX_OK;
+    (void)hipFree(d_nout); (void)hipHostFree(h_nout);
+    d_nout = h_nout = nullptr; nout_cap = 0;
+    const size_t cap = std::max(n, (size_t)1024);
+    DV_HIP(hipMalloc(&d_nout, cap * sizeof(lmx_normal_diff_t)));
+    DV_HIP(hipHostMalloc(&h_nout, cap * sizeof(lmx_normal_diff_t), hipHostMallocDefault));
+    nout_cap = cap;
+    return LMX_OK;
+  }
+  // The normals of the first n_frames W x H frames of d_scene, on stream `on` (which already waits for the frames' copies, or is the
+  // object's own stream that carries them); every later user waits for normals_ready.
+  lmx_status compute_scene_normals(hipStream_t on, int32_t n_frames, int32_t W, int32_t H) {
+    const size_t bytes = (size_t)W * H * (size_t)n_frames * sizeof(lmx::nv::Packed);
+    if (bytes > scene_normals_cap) {     // every call that read the old buffer ended synchronised
+      (void)hipFree(d_scene_normals);
+      d_scene_normals = nullptr; scene_normals_cap = 0;
+      DV_HIP(hipMalloc(&d_scene_normals, bytes));
+      scene_normals_cap = bytes;
+    }
+    const unsigned gx = (unsigned)std::min<size_t>(((size_t)W * H + 255) / 256, 4096);
+    const int pe = prof_begin(PK_NORMAL_MAP_FRAMES, on);
+    hipLaunchKernelGGL(lmx::k_normal_map_frames, dim3(gx, (unsigned)n_frames), dim3(256), 0, on, d_scene, W, H, d_scene_normals, nparams);
+    prof_end(pe, on);
+    DV_HIP(hipGetLastError());
+    DV_HIP(hipEventRecord(normals_ready, on));
+    return LMX_OK;
+  }
+  // what every normal-scored call needs next to ensure_device(): the angle table and the event
+  lmx_status ensure_normal_device() {
+    if (!normals_ready) DV_HIP(hipEventCreateWithFlags(&normals_ready, hipEventDisableTiming));
+    if (!d_angle) {
+      std::vector<uint32_t> tab(lmx::nv::kAngleTableSize);
+      lmx::nv::build_angle_table(tab.data());
+      DV_HIP(hipMalloc(&d_angle, tab.size() * sizeof(uint32_t)));
+      DV_HIP(hipMemcpyAsync(d_angle, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+      DV_HIP(hipStreamSynchronize(s));   // tab goes when this returns
+    }
+    return LMX_OK;
+  }
+  // Stream `on` is about to read the normals of the n_frames W x H frames in d_scene: compute them there if nobody has (behind the scene's
+  // copies: `behind_copies` is null when `on` is the stream that carries them), or wait for whoever did.
+  lmx_status scene_normals_on(hipStream_t on, hipEvent_t behind_copies, int32_t n_frames, int32_t W, int32_t H) {
+    if (scene_normals_valid) { DV_HIP(hipStreamWaitEvent(on, normals_ready, 0)); return LMX_OK; }
+    if (behind_copies) DV_HIP(hipStreamWaitEvent(on, behind_copies, 0));
+    if (lmx_status st = compute_scene_normals(on, n_frames, W, H)) return st;
+    scene_normals_valid = true;
+    return LMX_OK;
+  }
+  void free_normal_crops() {
+    (void)hipFree(d_ncrops); (void)hipFree(d_ntable);
+    d_ncrops = nullptr; d_ntable = nullptr;
+    ntable.clear();
+  }
   void add(const uint16_t* data, int32_t w, int32_t h, const int32_t rect[4]) {
     table.push_back(lmx::DepthCrop{data, w, h, w > 0 ? lmx::dv::crop_pitch(w) : 0, 0});
     rects.insert(rects.end(), rect, rect + 4);
@@ -223,6 +462,10 @@ struct lmx_depth_templates {
     for (void* p : chunks) (void)hipFree(p);
     (void)hipFree(d_table); (void)hipFree(d_scene); (void)hipFree(d_jobs); (void)hipFree(d_out);
     (void)hipHostFree(h_scene); (void)hipHostFree(h_jobs); (void)hipHostFree(h_out);
+    prof_drain();
+    free_normal_crops();
+    (void)hipFree(d_angle); (void)hipFree(d_scene_normals); (void)hipFree(d_nout); (void)hipHostFree(h_nout);
+    if (normals_ready) (void)hipEventDestroy(normals_ready);
     if (scene_ready) (void)hipEventDestroy(scene_ready);
     if (s) (void)hipStreamDestroy(s);
   }
@@ -382,7 +625,10 @@ extern "C" lmx_status lmx_depth_templates_get(const lmx_depth_templates* ct, int
 }
 
 extern "C" size_t lmx_depth_templates_device_bytes(const lmx_depth_templates* t) {
-  return t ? t->atlas_bytes + t->table.size() * sizeof(lmx::DepthCrop) : 0;
+  if (!t) return 0;
+  const size_t depth = t->atlas_bytes + t->table.size() * sizeof(lmx::DepthCrop);
+  // with normals: 8 bytes per crop element next to its 2, one address per template
+  return t->normals_on ? depth + t->atlas_bytes * (sizeof(lmx::nv::Packed) / sizeof(uint16_t)) + t->table.size() * sizeof(lmx::nv::Packed*) : depth;
 }
 
 extern "C" void lmx_depth_templates_free(lmx_depth_templates* t) {
@@ -417,14 +663,61 @@ lmx_status queue_frame(lmx_depth_templates* t, const lmx_image& im, int32_t slot
 
 // The device half of a depth check on the host's match list: the first n entries of h_jobs against the W x H frames already in d_scene
 // (a job's frame is its slot there): job upload, k_depth_diff, read-back into h_out.  The object's mutex is the caller's to hold.
-lmx_status run_jobs(lmx_depth_templates* t, size_t n, int32_t W, int32_t H) {
+// With `normals`: k_verify_diff instead, against the normals of the n_frames frames there (computed first if nobody has), h_nout too.
+lmx_status run_jobs(lmx_depth_templates* t, size_t n, int32_t W, int32_t H, bool normals = false, int32_t n_frames = 0) {
   hipStream_t s = t->s;
   DV_HIP(hipMemcpyAsync(t->d_jobs, t->h_jobs, n * sizeof(lmx::DepthJob), hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(lmx::k_depth_diff, dim3((unsigned)n), dim3(256), 0, s, t->d_table, t->d_jobs, t->d_scene, W, H, t->d_out);
+  if (normals) {
+    if (lmx_status st = t->scene_normals_on(s, nullptr, n_frames, W, H)) return st;
+    const int pe = t->prof_begin(lmx_depth_templates::PK_VERIFY_DIFF, s);
+    hipLaunchKernelGGL(lmx::k_verify_diff, dim3((unsigned)n), dim3(256), 0, s, t->d_table, t->d_ntable, t->d_jobs, t->d_scene, t->d_scene_normals, W, H,
+                       t->d_angle, t->d_out, t->d_nout);
+    t->prof_end(pe, s);
+  } else {
+    hipLaunchKernelGGL(lmx::k_depth_diff, dim3((unsigned)n), dim3(256), 0, s, t->d_table, t->d_jobs, t->d_scene, W, H, t->d_out);
+  }
   DV_HIP(hipGetLastError());
   DV_HIP(hipMemcpyAsync(t->h_out, t->d_out, n * sizeof(lmx_depth_diff_t), hipMemcpyDeviceToHost, s));
+  if (normals) DV_HIP(hipMemcpyAsync(t->h_nout, t->d_nout, n * sizeof(lmx_normal_diff_t), hipMemcpyDeviceToHost, s));
   DV_HIP(hipStreamSynchronize(s));
   return LMX_OK;
+}
+
+// What lmx_depth_templates_enable_normals needs before any normal-scored call works on the device: normals of every crop.
+lmx_status compute_crop_normals(lmx_depth_templates* t) {
+  using namespace lmx;
+  if (lmx_status st = t->ensure_device()) return st;
+  if (lmx_status st = t->ensure_normal_device()) return st;
+  DV_HIP(hipStreamSynchronize(t->s));
+  t->free_normal_crops();
+  t->ncrops_ready = false;
+  const size_t n = t->table.size(), elems = t->atlas_bytes / sizeof(uint16_t);
+  if (n == 0) { t->ncrops_ready = true; return LMX_OK; }
+  if (elems) DV_HIP(hipMalloc(&t->d_ncrops, elems * sizeof(nv::Packed)));
+  DV_HIP(hipMalloc(&t->d_ntable, n * sizeof(nv::Packed*)));
+  t->ntable.assign(n, nullptr);
+  size_t at = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const DepthCrop& c = t->table[i];
+    if (c.w <= 0 || c.h <= 0) continue;
+    t->ntable[i] = t->d_ncrops + at;
+    at += (size_t)c.h * (size_t)c.pitch;
+  }
+  DV_HIP(hipMemcpyAsync(t->d_ntable, t->ntable.data(), n * sizeof(nv::Packed*), hipMemcpyHostToDevice, t->s));
+  for (size_t first = 0; first < n; first += 32768) {   // blockIdx.y: at most 65535
+    const unsigned cnt = (unsigned)std::min<size_t>(32768, n - first);
+    hipLaunchKernelGGL(k_normal_map_crops, dim3(32, cnt), dim3(256), 0, t->s, t->d_table + first, t->d_ntable + first, t->nparams);
+    DV_HIP(hipGetLastError());
+  }
+  DV_HIP(hipStreamSynchronize(t->s));   // ntable's bytes have left the host
+  t->ncrops_ready = true;
+  return LMX_OK;
+}
+// Before a normal-scored call touches the device: the object's stream, the angle table, the crops' normals.
+lmx_status ensure_normals(lmx_depth_templates* t) {
+  if (lmx_status st = t->ensure_device()) return st;
+  if (lmx_status st = t->ensure_normal_device()) return st;
+  return t->ncrops_ready ? LMX_OK : compute_crop_normals(t);
 }
 }  // namespace
 
@@ -443,7 +736,7 @@ namespace lmx {
 std::mutex& depth_templates_mutex(lmx_depth_templates* t) { return t->m; }
 
 DepthSceneInfo depth_templates_scene(const lmx_depth_templates* t) {
-  return DepthSceneInfo{t->device, (int32_t)t->table.size(), t->scene_frames, t->scene_W, t->scene_H};
+  return DepthSceneInfo{t->device, (int32_t)t->table.size(), t->scene_frames, t->scene_W, t->scene_H, t->normals_on ? 1 : 0};
 }
 
 lmx_status depth_upload_scene(lmx_depth_templates* t, const lmx_image* depth, int32_t n_frames) {
@@ -453,6 +746,7 @@ lmx_status depth_upload_scene(lmx_depth_templates* t, const lmx_image* depth, in
   if (lmx_status st = t->ensure_device()) return st;
   if (lmx_status st = t->wait_scene_copies()) return st;   // the previous scene's copies still read the staging buffer
   t->scene_frames = 0;
+  t->scene_normals_valid = false;
   if (lmx_status st = t->grow_scene((size_t)W * H * sizeof(uint16_t) * (size_t)n_frames)) return st;
   for (int32_t f = 0; f < n_frames; ++f)   // each frame on its way while the next is staged
     if (lmx_status st = queue_frame(t, depth[f], f, W, H)) { t->drain_after_error(); return st; }
@@ -467,21 +761,38 @@ lmx_status depth_upload_scene(lmx_depth_templates* t, const lmx_image* depth, in
 }
 
 lmx_status depth_launch_records(lmx_depth_templates* t, hipStream_t s, const lmx_raw_match_t* d_recs, uint32_t n_records, int32_t class_index,
-                                lmx_depth_diff_t* d_diffs) {
+                                lmx_depth_diff_t* d_diffs, lmx_normal_diff_t* d_ndiffs) {
   if (t->scene_frames < 1) { set_error("no scene uploaded: call lmx_depth_templates_upload_scene first"); return LMX_ERR_INVALID_ARG; }
+  if (d_ndiffs) {
+    if (!t->normals_on) { set_error("call lmx_depth_templates_enable_normals first"); return LMX_ERR_INVALID_ARG; }
+    if (lmx_status st = ensure_normals(t)) return st;
+  }
   DV_HIP(hipStreamWaitEvent(s, t->scene_ready, 0));
   if (n_records == 0) return LMX_OK;
+  if (d_ndiffs) {   // the scene's normals first, on this stream, if this is the scene's first normal-scored call
+    if (lmx_status st = t->scene_normals_on(s, nullptr, t->scene_frames, t->scene_W, t->scene_H)) return st;
+    const int pe = t->prof_begin(lmx_depth_templates::PK_VERIFY_DIFF_RECORDS, s);
+    hipLaunchKernelGGL(k_verify_diff_records, dim3(n_records), dim3(256), 0, s, t->d_table, t->d_ntable, (int32_t)t->table.size(), d_recs, t->d_scene,
+                       t->d_scene_normals, t->scene_frames, t->scene_W, t->scene_H, class_index, t->d_angle, d_diffs, d_ndiffs);
+    t->prof_end(pe, s);
+    DV_HIP(hipGetLastError());
+    return LMX_OK;
+  }
+  const int pe = t->prof_begin(lmx_depth_templates::PK_DEPTH_DIFF_RECORDS, s);
   hipLaunchKernelGGL(k_depth_diff_records, dim3(n_records), dim3(256), 0, s, t->d_table, (int32_t)t->table.size(), d_recs, t->d_scene, t->scene_frames,
                      t->scene_W, t->scene_H, class_index, d_diffs);
+  t->prof_end(pe, s);
   DV_HIP(hipGetLastError());
   return LMX_OK;
 }
 
-lmx_status depth_diff_resident(lmx_depth_templates* t, const lmx_match_t* matches, size_t n, int32_t frame, int32_t class_index, lmx_depth_diff_t* out) {
+lmx_status depth_diff_resident(lmx_depth_templates* t, const lmx_match_t* matches, size_t n, int32_t frame, int32_t class_index, lmx_depth_diff_t* out,
+                               lmx_normal_diff_t* nout) {
   if (n == 0) return LMX_OK;
   if (frame < 0 || frame >= t->scene_frames) { set_error("frame %d is not in the uploaded scene (%d frames)", frame, t->scene_frames); return LMX_ERR_INVALID_ARG; }
   if (n > 0x7fffffffull) { set_error("%zu matches in one frame", n); return LMX_ERR_INVALID_ARG; }
   std::memset(out, 0, n * sizeof(lmx_depth_diff_t));
+  if (nout) std::memset(nout, 0, n * sizeof(lmx_normal_diff_t));
   const size_t count = t->table.size();
   t->sel.clear();
   for (size_t i = 0; i < n; ++i) {
@@ -497,30 +808,39 @@ lmx_status depth_diff_resident(lmx_depth_templates* t, const lmx_match_t* matche
     const lmx_match_t& m = matches[t->sel[k]];
     t->h_jobs[k] = DepthJob{m.x, m.y, m.template_id, frame};
   }
-  if (lmx_status st = run_jobs(t, n_sel, t->scene_W, t->scene_H)) return st;   // on the object's stream, behind the scene's copies
+  if (nout) {
+    if (!t->normals_on) { set_error("call lmx_depth_templates_enable_normals first"); return LMX_ERR_INVALID_ARG; }
+    if (lmx_status st = ensure_normals(t)) return st;
+    if (lmx_status st = t->grow_nout(n_sel)) return st;
+  }
+  if (lmx_status st = run_jobs(t, n_sel, t->scene_W, t->scene_H, nout != nullptr, t->scene_frames)) return st;   // on the object's stream, behind the scene's copies
   for (size_t k = 0; k < n_sel; ++k) out[t->sel[k]] = t->h_out[k];
+  if (nout)
+    for (size_t k = 0; k < n_sel; ++k) nout[t->sel[k]] = t->h_nout[k];
   return LMX_OK;
 }
 
 }  // namespace lmx
 
-extern "C" lmx_status lmx_depth_diff_matches(lmx_depth_templates* t, const lmx_image* depth, int32_t n_frames, const lmx_match_t* matches,
-                                             const size_t* offsets, int32_t class_index, lmx_depth_diff_t* out) {
-  return lmx::guarded("lmx_depth_diff_matches", [&]() -> lmx_status {
+namespace {
+// The body of lmx_depth_diff_matches (nout null) and lmx_normal_diff_matches (nout: the normal sums; out may then be null).
+lmx_status diff_matches_impl(const char* what, lmx_depth_templates* t, const lmx_image* depth, int32_t n_frames, const lmx_match_t* matches,
+                             const size_t* offsets, int32_t class_index, lmx_depth_diff_t* out, lmx_normal_diff_t* nout, bool normals) {
     using namespace lmx;
-    if (!t) { set_error("lmx_depth_diff_matches: null argument"); return LMX_ERR_INVALID_ARG; }
-    if (n_frames < 0) { set_error("lmx_depth_diff_matches: n_frames = %d", n_frames); return LMX_ERR_INVALID_ARG; }
+    if (!t) { set_error("%s: null argument", what); return LMX_ERR_INVALID_ARG; }
+    if (normals && !t->normals_on) { set_error("%s: call lmx_depth_templates_enable_normals first", what); return LMX_ERR_INVALID_ARG; }
+    if (n_frames < 0) { set_error("%s: n_frames = %d", what, n_frames); return LMX_ERR_INVALID_ARG; }
     if (n_frames == 0) return LMX_OK;
-    if (!depth || !offsets) { set_error("lmx_depth_diff_matches: null argument"); return LMX_ERR_INVALID_ARG; }
-    if (offsets[0] != 0) { set_error("lmx_depth_diff_matches: offsets[0] = %zu (expected 0)", offsets[0]); return LMX_ERR_INVALID_ARG; }
+    if (!depth || !offsets) { set_error("%s: null argument", what); return LMX_ERR_INVALID_ARG; }
+    if (offsets[0] != 0) { set_error("%s: offsets[0] = %zu (expected 0)", what, offsets[0]); return LMX_ERR_INVALID_ARG; }
     for (int32_t f = 0; f < n_frames; ++f)
-      if (offsets[f + 1] < offsets[f]) { set_error("lmx_depth_diff_matches: offsets[%d] = %zu is below offsets[%d] = %zu", f + 1, offsets[f + 1], f, offsets[f]); return LMX_ERR_INVALID_ARG; }
-    if (lmx_status st = check_depth_frames("lmx_depth_diff_matches", depth, n_frames)) return st;
+      if (offsets[f + 1] < offsets[f]) { set_error("%s: offsets[%d] = %zu is below offsets[%d] = %zu", what, f + 1, offsets[f + 1], f, offsets[f]); return LMX_ERR_INVALID_ARG; }
+    if (lmx_status st = check_depth_frames(what, depth, n_frames)) return st;
     const int32_t W = depth[0].cols, H = depth[0].rows;
     const size_t n_matches = offsets[n_frames];
     if (n_matches == 0) return LMX_OK;
-    if (!matches || !out) { set_error("lmx_depth_diff_matches: null argument"); return LMX_ERR_INVALID_ARG; }
-    if (n_matches > 0x7fffffffull) { set_error("lmx_depth_diff_matches: %zu matches in one call", n_matches); return LMX_ERR_INVALID_ARG; }   // sel holds uint32, the grid is n_sel wide
+    if (!matches || (normals ? !nout : !out)) { set_error("%s: null argument", what); return LMX_ERR_INVALID_ARG; }
+    if (n_matches > 0x7fffffffull) { set_error("%s: %zu matches in one call", what, n_matches); return LMX_ERR_INVALID_ARG; }   // sel holds uint32, the grid is n_sel wide
     std::lock_guard<std::mutex> lk(t->m);
     const size_t count = t->table.size();
     t->sel.clear();
@@ -531,22 +851,26 @@ extern "C" lmx_status lmx_depth_diff_matches(lmx_depth_templates* t, const lmx_i
       for (size_t i = offsets[f]; i < offsets[f + 1]; ++i) {
         const lmx_match_t& m = matches[i];
         if (class_index >= 0 && m.class_index != class_index) continue;
-        if (m.template_id < 0 || (size_t)m.template_id >= count) { set_error("lmx_depth_diff_matches: match %zu: template_id %d outside [0, %zu)", i, m.template_id, count); return LMX_ERR_INVALID_ARG; }
+        if (m.template_id < 0 || (size_t)m.template_id >= count) { set_error("%s: match %zu: template_id %d outside [0, %zu)", what, i, m.template_id, count); return LMX_ERR_INVALID_ARG; }
         if (t->slot[f] < 0) t->slot[f] = n_slots++;
         t->sel.push_back((uint32_t)i);
         t->sel_slot.push_back(t->slot[f]);
       }
-    std::memset(out, 0, n_matches * sizeof(lmx_depth_diff_t));
+    if (out) std::memset(out, 0, n_matches * sizeof(lmx_depth_diff_t));
+    if (normals) std::memset(nout, 0, n_matches * sizeof(lmx_normal_diff_t));
     const size_t n_sel = t->sel.size();
     if (n_sel == 0) return LMX_OK;
-    if (lmx_status st = t->ensure_device()) return st;
+    if (lmx_status st = normals ? ensure_normals(t) : t->ensure_device()) return st;
     const size_t frame_bytes = (size_t)W * H * sizeof(uint16_t);
     // the frames that have matches take the place of an uploaded scene: staged row by row into pinned memory, each on its way while the
     // next is staged
     if (lmx_status st = t->wait_scene_copies()) return st;
     t->scene_frames = 0;
+    t->scene_normals_valid = false;
     if (lmx_status st = t->grow_scene(frame_bytes * n_slots)) return st;
     if (lmx_status st = t->grow_jobs(n_sel)) return st;
+    if (normals)
+      if (lmx_status st = t->grow_nout(n_sel)) return st;
     for (int32_t f = 0; f < n_frames; ++f)
       if (t->slot[f] >= 0)
         if (lmx_status st = queue_frame(t, depth[f], t->slot[f], W, H)) { t->drain_after_error(); return st; }
@@ -554,8 +878,116 @@ extern "C" lmx_status lmx_depth_diff_matches(lmx_depth_templates* t, const lmx_i
       const lmx_match_t& m = matches[t->sel[k]];
       t->h_jobs[k] = DepthJob{m.x, m.y, m.template_id, t->sel_slot[k]};
     }
-    if (lmx_status st = run_jobs(t, n_sel, W, H)) { t->drain_after_error(); return st; }
-    for (size_t k = 0; k < n_sel; ++k) out[t->sel[k]] = t->h_out[k];
+    if (lmx_status st = run_jobs(t, n_sel, W, H, normals, n_slots)) { t->drain_after_error(); return st; }
+    t->scene_normals_valid = false;   // they belong to staged frames that are no scene
+    if (out)
+      for (size_t k = 0; k < n_sel; ++k) out[t->sel[k]] = t->h_out[k];
+    if (normals)
+      for (size_t k = 0; k < n_sel; ++k) nout[t->sel[k]] = t->h_nout[k];
+    return LMX_OK;
+}
+}  // namespace
+
+extern "C" lmx_status lmx_depth_diff_matches(lmx_depth_templates* t, const lmx_image* depth, int32_t n_frames, const lmx_match_t* matches,
+                                             const size_t* offsets, int32_t class_index, lmx_depth_diff_t* out) {
+  return lmx::guarded("lmx_depth_diff_matches", [&]() -> lmx_status {
+    return diff_matches_impl("lmx_depth_diff_matches", t, depth, n_frames, matches, offsets, class_index, out, nullptr, false);
+  });
+}
+
+extern "C" lmx_status lmx_normal_diff_matches(lmx_depth_templates* t, const lmx_image* depth, int32_t n_frames, const lmx_match_t* matches,
+                                              const size_t* offsets, int32_t class_index, lmx_depth_diff_t* ddiffs, lmx_normal_diff_t* out) {
+  return lmx::guarded("lmx_normal_diff_matches", [&]() -> lmx_status {
+    return diff_matches_impl("lmx_normal_diff_matches", t, depth, n_frames, matches, offsets, class_index, ddiffs, out, true);
+  });
+}
+
+extern "C" double lmx_match_value(const lmx_depth_diff_t* ddiff, const lmx_normal_diff_t* ndiff, double no_value) {
+  return ddiff && ndiff ? lmx::nv::value(*ddiff, *ndiff, no_value) : no_value;
+}
+
+extern "C" lmx_status lmx_normal_angle_table(uint32_t* out) {
+  if (!out) { lmx::set_error("lmx_normal_angle_table: null argument"); return LMX_ERR_INVALID_ARG; }
+  lmx::nv::build_angle_table(out);
+  return LMX_OK;
+}
+
+extern "C" lmx_status lmx_depth_templates_enable_normals(lmx_depth_templates* t, const lmx_normal_params* params) {
+  return lmx::guarded("lmx_depth_templates_enable_normals", [&]() -> lmx_status {
+    using namespace lmx;
+    if (!t || !params) { set_error("lmx_depth_templates_enable_normals: null argument"); return LMX_ERR_INVALID_ARG; }
+    const float fx = (float)params->fx, fy = (float)params->fy;
+    if (!(fx > 0.0f) || !(fy > 0.0f) || !(fx <= 1.0e6f) || !(fy <= 1.0e6f)) {   // 1e6 x |ddx| < 1e9 squared stays a finite float
+      set_error("lmx_depth_templates_enable_normals: fx = %g, fy = %g (focal lengths in pixels: above 0, at most 1e6)", params->fx, params->fy);
+      return LMX_ERR_INVALID_ARG;
+    }
+    if (params->difference_threshold < 1 || params->distance_threshold < 1) {
+      set_error("lmx_depth_templates_enable_normals: difference_threshold = %d, distance_threshold = %d (both >= 1)", params->difference_threshold,
+                params->distance_threshold);
+      return LMX_ERR_INVALID_ARG;
+    }
+    std::lock_guard<std::mutex> lk(t->m);
+    const nv::Params np = {fx, fy, params->difference_threshold, params->distance_threshold};
+    if (t->normals_on && t->ncrops_ready && std::memcmp(&np, &t->nparams, sizeof(np)) == 0) return LMX_OK;
+    t->nparams = np;
+    t->normals_on = true;
+    t->ncrops_ready = false;
+    t->scene_normals_valid = false;
+    if (t->atlas_bytes == 0) return LMX_OK;   // no pixel to take a normal of: nothing needs the device yet
+    if (lmx_status st = compute_crop_normals(t)) { t->normals_on = false; return st; }
+    return LMX_OK;
+  });
+}
+
+extern "C" lmx_status lmx_depth_templates_get_normals(const lmx_depth_templates* ct, int32_t id, int16_t* out) {
+  return lmx::guarded("lmx_depth_templates_get_normals", [&]() -> lmx_status {
+    lmx_depth_templates* t = const_cast<lmx_depth_templates*>(ct);
+    if (!t) { lmx::set_error("lmx_depth_templates_get_normals: null argument"); return LMX_ERR_INVALID_ARG; }
+    if (!t->normals_on) { lmx::set_error("lmx_depth_templates_get_normals: call lmx_depth_templates_enable_normals first"); return LMX_ERR_INVALID_ARG; }
+    if (id < 0 || (size_t)id >= t->table.size()) { lmx::set_error("lmx_depth_templates_get_normals: id %d outside [0, %zu)", id, t->table.size()); return LMX_ERR_INVALID_ARG; }
+    const lmx::DepthCrop& c = t->table[id];
+    if (c.w <= 0 || c.h <= 0) return LMX_OK;
+    if (!out) { lmx::set_error("lmx_depth_templates_get_normals: null argument"); return LMX_ERR_INVALID_ARG; }
+    std::lock_guard<std::mutex> lk(t->m);
+    if (lmx_status st = ensure_normals(t)) return st;
+    DV_HIP(hipMemcpy2DAsync(out, (size_t)c.w * 8, t->ntable[id], (size_t)c.pitch * 8, (size_t)c.w * 8, (size_t)c.h, hipMemcpyDeviceToHost, t->s));
+    DV_HIP(hipStreamSynchronize(t->s));
+    return LMX_OK;
+  });
+}
+
+extern "C" lmx_status lmx_depth_templates_set_profiling(lmx_depth_templates* t, int32_t on) {
+  if (!t) { lmx::set_error("lmx_depth_templates_set_profiling: null argument"); return LMX_ERR_INVALID_ARG; }
+  std::lock_guard<std::mutex> lk(t->m);
+  t->prof_drain();
+  if (on && !t->profiling)
+    for (int k = 0; k < lmx_depth_templates::PK_COUNT; ++k) { t->prof_ms[k] = 0.0; t->prof_launches[k] = 0; }
+  t->profiling = on != 0;
+  return LMX_OK;
+}
+
+extern "C" lmx_status lmx_depth_templates_kernel_time(lmx_depth_templates* t, int32_t kernel, double* total_ms, int64_t* launches) {
+  if (!t || !total_ms || !launches) { lmx::set_error("lmx_depth_templates_kernel_time: null argument"); return LMX_ERR_INVALID_ARG; }
+  if (kernel < 0 || kernel >= lmx_depth_templates::PK_COUNT) { lmx::set_error("lmx_depth_templates_kernel_time: kernel %d outside [0, %d)", kernel, (int)lmx_depth_templates::PK_COUNT); return LMX_ERR_INVALID_ARG; }
+  std::lock_guard<std::mutex> lk(t->m);
+  t->prof_drain();   // waits for the launches still in flight
+  *total_ms = t->prof_ms[kernel];
+  *launches = t->prof_launches[kernel];
+  return LMX_OK;
+}
+
+extern "C" lmx_status lmx_debug_scene_normals(lmx_depth_templates* t, int32_t frame, int16_t* out) {
+  return lmx::guarded("lmx_debug_scene_normals", [&]() -> lmx_status {
+    if (!t || !out) { lmx::set_error("lmx_debug_scene_normals: null argument"); return LMX_ERR_INVALID_ARG; }
+    std::lock_guard<std::mutex> lk(t->m);
+    if (!t->normals_on) { lmx::set_error("lmx_debug_scene_normals: call lmx_depth_templates_enable_normals first"); return LMX_ERR_INVALID_ARG; }
+    if (t->scene_frames < 1) { lmx::set_error("lmx_debug_scene_normals: no scene uploaded: call lmx_depth_templates_upload_scene first"); return LMX_ERR_INVALID_ARG; }
+    if (frame < 0 || frame >= t->scene_frames) { lmx::set_error("lmx_debug_scene_normals: frame %d is not in the uploaded scene (%d frames)", frame, t->scene_frames); return LMX_ERR_INVALID_ARG; }
+    if (lmx_status st = ensure_normals(t)) return st;
+    if (lmx_status st = t->scene_normals_on(t->s, nullptr, t->scene_frames, t->scene_W, t->scene_H)) return st;
+    const size_t px = (size_t)t->scene_W * t->scene_H;
+    DV_HIP(hipMemcpyAsync(out, t->d_scene_normals + px * frame, px * sizeof(lmx::nv::Packed), hipMemcpyDeviceToHost, t->s));
+    DV_HIP(hipStreamSynchronize(t->s));
     return LMX_OK;
   });
 }

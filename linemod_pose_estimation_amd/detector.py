@@ -465,6 +465,22 @@ class Detector:
                                                              d.ctypes.data, cl.ctypes.data, cap_total, co, mem.ctypes.data, cap_total))
         return [(m[mo[f]:mo[f + 1]].copy(), d[mo[f]:mo[f + 1]].copy(), cl[co[f]:co[f + 1]].copy(), mem) for f in range(n_frames)]
 
+    def collect_clusters_depth_normal(self, n_frames, templates, class_index=-1, no_value=-np.inf, cap_total=1 << 16):
+        """collect_clusters_depth with the normal term in the score (lmx_ctx_collect_clusters_depth_normal): `templates` is a DepthTemplates
+        after enable_normals whose upload_scene(depth_frames) was called after the enqueue.  -> list per frame of (matches, diffs, ndiffs,
+        clusters, members), equal to collect + templates.normal_diff + cluster_matches_scored(normal_values(diffs, ndiffs)) bit for bit.
+        exp(score) is the reference's getClusterScore when every member has something to compare."""
+        m = np.zeros(cap_total, MATCH_DTYPE)
+        d = np.zeros(cap_total, DEPTH_DIFF_DTYPE)
+        nd = np.zeros(cap_total, NORMAL_DIFF_DTYPE)
+        cl = np.zeros(cap_total, CLUSTER_DTYPE)
+        mem = np.zeros(cap_total, np.int32)
+        mo = (C.c_size_t * (n_frames + 1))()
+        co = (C.c_size_t * (n_frames + 1))()
+        _lib.check(_lib.lib().lmx_ctx_collect_clusters_depth_normal(self.h, n_frames, templates.h, int(class_index), float(no_value), m.ctypes.data, cap_total,
+                                                                    mo, d.ctypes.data, nd.ctypes.data, cl.ctypes.data, cap_total, co, mem.ctypes.data, cap_total))
+        return [(m[mo[f]:mo[f + 1]].copy(), d[mo[f]:mo[f + 1]].copy(), nd[mo[f]:mo[f + 1]].copy(), cl[co[f]:co[f + 1]].copy(), mem) for f in range(n_frames)]
+
     def raw_matches_ptrs(self):
         rec, cnt, cap = C.c_void_p(), C.c_void_p(), C.c_size_t()
         _lib.check(_lib.lib().lmx_ctx_raw_matches(self.h, C.byref(rec), C.byref(cnt), C.byref(cap)))
@@ -666,6 +682,31 @@ def depth_values(diffs):
     return out
 
 
+NORMAL_DIFF_DTYPE = np.dtype([("sum_angle_urad", "<i8"), ("n_normal", "<i4"), ("reserved", "<i4")])
+
+
+def normal_values(ddiffs, ndiffs):
+    """Per-match values for cluster_matches_scored from DepthTemplates.normal_diff results (lmx_match_value): minus (the mean absolute depth
+    difference in metres + the mean normal angle in radians); -inf for a match with n_valid == 0 or n_normal == 0.  The mean of it over a
+    cluster is the logarithm of the reference's getClusterScore, 1 / exp(depth term) * 1 / exp(normal term)."""
+    ddiffs = np.asarray(ddiffs, DEPTH_DIFF_DTYPE)
+    ndiffs = np.asarray(ndiffs, NORMAL_DIFF_DTYPE)
+    if ddiffs.shape != ndiffs.shape:
+        raise ValueError("one depth diff and one normal diff per match")
+    out = np.full(len(ddiffs), -np.inf)
+    ok = (ddiffs["n_valid"] > 0) & (ndiffs["n_normal"] > 0)
+    out[ok] = -(ddiffs["sum_abs_mm"][ok].astype(np.float64) / (ddiffs["n_valid"][ok].astype(np.float64) * 1000.0)
+                + ndiffs["sum_angle_urad"][ok].astype(np.float64) / (ndiffs["n_normal"][ok].astype(np.float64) * 1e6))
+    return out
+
+
+def normal_angle_table():
+    """lmx_normal_angle_table: uint32 [16385], half chord in 1 / 16384 -> angle in microradians."""
+    out = np.zeros(16385, np.uint32)
+    _lib.check(_lib.lib().lmx_normal_angle_table(out.ctypes.data))
+    return out
+
+
 def _depth_images(depth_frames):
     """A uint16 [H, W] array or a list of them -> (the list, its lmx_image descriptors)."""
     if isinstance(depth_frames, np.ndarray) and depth_frames.ndim == 2:
@@ -749,12 +790,66 @@ class DepthTemplates:
         _lib.check(_lib.lib().lmx_depth_diff_matches(self.h, imgs, len(frames), matches.ctypes.data, offs, int(class_index), out.ctypes.data))
         return out
 
+    def enable_normals(self, fx, fy, difference_threshold=50, distance_threshold=2000):
+        """Compute and keep the normals of every crop (lmx_depth_templates_enable_normals): needed before normals(), normal_diff() and
+        Detector.collect_clusters_depth_normal.  fx, fy: the focal lengths of the camera whose depth frames are checked."""
+        p = _lib.NormalParams(float(fx), float(fy), int(difference_threshold), int(distance_threshold))
+        _lib.check(_lib.lib().lmx_depth_templates_enable_normals(self.h, C.byref(p)))
+
+    def normals(self, i):
+        """Template i's normals, read back from the device: int16 [h, w, 4] = (qx, qy, qz, valid), a unit normal times 16384."""
+        _, _, w, h = self.rect(i)
+        out = np.zeros((h, w, 4), np.int16)
+        _lib.check(_lib.lib().lmx_depth_templates_get_normals(self.h, int(i), out.ctypes.data))
+        return out
+
+    def normal_diff(self, depth_frames, matches, offsets=None, class_index=-1):
+        """diff() with both terms in one pass (lmx_normal_diff_matches) -> (DEPTH_DIFF_DTYPE array, NORMAL_DIFF_DTYPE array), one record
+        per match each; the first equals diff()'s result."""
+        frames, imgs = _depth_images(depth_frames)
+        matches = np.ascontiguousarray(matches, MATCH_DTYPE)
+        if offsets is None:
+            if len(frames) != 1:
+                raise ValueError("offsets are needed with more than one frame")
+            offsets = [0, len(matches)]
+        if len(offsets) != len(frames) + 1 or int(offsets[-1]) != len(matches):
+            raise ValueError("offsets must have one entry per frame plus one and end at len(matches)")
+        offs = (C.c_size_t * len(offsets))(*[int(v) for v in offsets])
+        dd = np.zeros(len(matches), DEPTH_DIFF_DTYPE)
+        nd = np.zeros(len(matches), NORMAL_DIFF_DTYPE)
+        _lib.check(_lib.lib().lmx_normal_diff_matches(self.h, imgs, len(frames), matches.ctypes.data, offs, int(class_index), dd.ctypes.data, nd.ctypes.data))
+        return dd, nd
+
+    KERNELS = ("k_normal_map_frames", "k_verify_diff_records", "k_verify_diff", "k_depth_diff_records")
+
+    def set_profiling(self, on=True):
+        """Time the object's per-call kernels with device events (lmx_depth_templates_set_profiling); switching it on clears the sums."""
+        _lib.check(_lib.lib().lmx_depth_templates_set_profiling(self.h, int(bool(on))))
+
+    def kernel_times(self):
+        """-> {kernel name: (total ms, launches)} since profiling was switched on; waits for the launches in flight."""
+        out = {}
+        for k, name in enumerate(self.KERNELS):
+            ms, n = C.c_double(), C.c_int64()
+            _lib.check(_lib.lib().lmx_depth_templates_kernel_time(self.h, k, C.byref(ms), C.byref(n)))
+            out[name] = (ms.value, n.value)
+        return out
+
+    def debug_scene_normals(self, frame):
+        """Test hook (lmx_debug_scene_normals): the normals of frame `frame` of the uploaded scene, int16 [H, W, 4]."""
+        if getattr(self, "_scene_shape", None) is None:
+            raise ValueError("no scene uploaded through this object")
+        out = np.zeros(self._scene_shape + (4,), np.int16)
+        _lib.check(_lib.lib().lmx_debug_scene_normals(self.h, int(frame), out.ctypes.data))
+        return out
+
     def upload_scene(self, depth_frames):
         """The scene of the next Detector.collect_clusters_depth (lmx_depth_templates_upload_scene): a uint16 [H, W] array or a list of
         them, one per frame of the enqueue.  Returns without waiting for the transfer: call it right after Detector.enqueue.  A later
         upload_scene replaces the scene; diff() forgets it whenever it has a match to check."""
         frames, imgs = _depth_images(depth_frames)
         _lib.check(_lib.lib().lmx_depth_templates_upload_scene(self.h, imgs, len(frames)))
+        self._scene_shape = tuple(frames[0].shape)
 
     def close(self):
         if getattr(self, "h", None):
