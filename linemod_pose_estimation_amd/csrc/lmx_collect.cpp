@@ -207,6 +207,17 @@ struct DepthScore {
   lmx_normal_diff_t* ndiffs; // normal only: parallel to the caller's matches; may be null
 };
 
+// Room for one result of `elem` bytes per raw record of the slot being collected.  Nothing reads the old buffer: every call ends synchronised.
+static lmx_status grow_rec_diffs(void** d, size_t* cap, size_t n, size_t elem) {
+  if (n <= *cap) return LMX_OK;
+  if (*d) (void)hipFree(*d);
+  *d = nullptr; *cap = 0;
+  const size_t want = std::max<size_t>(n, 4096);
+  LMX_HIP(hipMalloc(d, want * elem));
+  *cap = want;
+  return LMX_OK;
+}
+
 // The body of lmx_ctx_collect_clusters and lmx_ctx_collect_clusters_depth (`what` names the entry point in messages).  With `depth`, the
 // caller holds the templates' mutex.
 static lmx_status collect_clusters_impl(const char* what, lmx_ctx* c, int32_t n_frames, const DepthScore* depth, lmx_match_t* matches, size_t cap_matches,
@@ -274,20 +285,9 @@ static lmx_status collect_clusters_impl(const char* what, lmx_ctx* c, int32_t n_
   p.step = c->f2_params.vote_row_col_step; p.size_thresh = c->f2_params.cluster_size_thresh; p.do_clusters = 1;
   p.radius_min = c->f2_params.renderer_radius_min; p.radius_step = c->f2_params.renderer_radius_step;
   if (depth) {
-    if (n_match > c->f2_rec_diffs_cap) {   // nothing reads the old buffer: every call ends synchronised
-      if (c->d_f2_rec_diffs) (void)hipFree(c->d_f2_rec_diffs);
-      c->d_f2_rec_diffs = nullptr; c->f2_rec_diffs_cap = 0;
-      const size_t cap = std::max<size_t>(n_match, 4096);
-      LMX_HIP(hipMalloc((void**)&c->d_f2_rec_diffs, cap * sizeof(lmx_depth_diff_t)));
-      c->f2_rec_diffs_cap = cap;
-    }
-    if (depth->normal && n_match > c->f2_rec_ndiffs_cap) {
-      if (c->d_f2_rec_ndiffs) (void)hipFree(c->d_f2_rec_ndiffs);
-      c->d_f2_rec_ndiffs = nullptr; c->f2_rec_ndiffs_cap = 0;
-      const size_t cap = std::max<size_t>(n_match, 4096);
-      LMX_HIP(hipMalloc((void**)&c->d_f2_rec_ndiffs, cap * sizeof(lmx_normal_diff_t)));
-      c->f2_rec_ndiffs_cap = cap;
-    }
+    if (lmx_status st = grow_rec_diffs((void**)&c->d_f2_rec_diffs, &c->f2_rec_diffs_cap, n_match, sizeof(lmx_depth_diff_t))) return st;
+    if (depth->normal)
+      if (lmx_status st = grow_rec_diffs((void**)&c->d_f2_rec_ndiffs, &c->f2_rec_ndiffs_cap, n_match, sizeof(lmx_normal_diff_t))) return st;
     // the scene's copies, one workgroup per raw record (the count is the header's, read above), the scored chain: one synchronisation
     if (lmx_status st = depth_launch_records(depth->templates, s, p.recs, n_match, depth->class_index, c->d_f2_rec_diffs,
                                              depth->normal ? c->d_f2_rec_ndiffs : nullptr)) return st;

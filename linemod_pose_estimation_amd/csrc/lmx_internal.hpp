@@ -338,7 +338,7 @@ DepthSceneInfo depth_templates_scene(const lmx_depth_templates* t);   // the fou
 // lmx_depth_templates_upload_scene without taking the mutex (depth must not be null)
 lmx_status depth_upload_scene(lmx_depth_templates* t, const lmx_image* depth, int32_t n_frames);
 // `s` waits for the scene's copies, then k_depth_diff_records: d_diffs[i] for d_recs[i], i < n_records (no launch for 0).  With d_ndiffs:
-// the scene's normals on `s` if nobody has computed them, then k_verify_diff_records, which fills both
+// the scene's normals on `s` if nobody has computed them, then k_verify_diff_records (the same walk with both terms), which fills both
 lmx_status depth_launch_records(lmx_depth_templates* t, hipStream_t s, const lmx_raw_match_t* d_recs, uint32_t n_records, int32_t class_index,
                                 lmx_depth_diff_t* d_diffs, lmx_normal_diff_t* d_ndiffs = nullptr);
 // host matches of scene frame `frame` through k_depth_diff (synchronous); other classes and template ids outside the table get zeros

@@ -1,6 +1,7 @@
 // Normal-difference term of a match (lmx_normal_diff_matches, include/lmx.h): the arithmetic of one pixel's normal, one pixel pair's angle,
-// one match's sums and one match's value, shared by the HIP kernels (lmx_verify.hip: k_normal_map_*, k_verify_diff and
-// k_verify_diff_records; lmx_f2.hip for value()) and -- compiled with LMX_NV_HOST -- by plain CPU builds (tests/cpp/normal_verify_host.cpp).
+// one match's sums and one match's value, shared by the HIP kernels (lmx_verify.hip: k_normal_map_*, and add_vector as the inner step of
+// k_verify_diff and k_verify_diff_records; lmx_f2.hip for value()) and -- compiled with LMX_NV_HOST -- by plain CPU builds
+// (tests/cpp/normal_verify_host.cpp).
 // The reference's form is depth_normal_diff_calc (src/rgbdDetector.cpp:147-359), the normal half: the mean angle between the surface normals
 // of the template's rendered depth and of the scene depth over the pixels both cover.  The reference takes its normals from OpenCV's rgbd
 // module (RGBD_NORMALS_METHOD_LINEMOD), which is not part of it; the definition below is this project's own (deviations).
@@ -26,9 +27,11 @@
 #define LMX_DV_HOST
 #endif
 #define LMX_NV_FN inline
+#define LMX_NV_UNROLL
 #include <math.h>
 #else
 #define LMX_NV_FN __host__ __device__ __forceinline__
+#define LMX_NV_UNROLL _Pragma("unroll")
 #endif
 
 #include "lmx_depth_verify.hpp"
@@ -120,6 +123,31 @@ LMX_NV_FN void add_met_normals(Packed t, Packed s, const uint32_t* table, Sums* 
   a->n_normal += 1;
 }
 
+// dv::add_vector with both terms, as the kernel reads a crop row: word[] as there, tn[e] the stored normal of element col0 + e (the
+// padding's normals are zeros, like its depths).  row_in: srow / snrow are the scene row's depths and normals; otherwise neither is read.
+// Both scene reads of an element sit under the in-image predicate and nowhere else: the depth where t != 0, the normal where the crop's
+// normal is valid (which implies t != 0).  Every load comes before every sum, so neither scene read waits for the other and the chain of
+// dependent loads is crop -> scene -> table.
+LMX_NV_FN void add_vector(const uint32_t word[4], const Packed tn[dv::kPitchAlign], bool row_in, int32_t x, int32_t col0, int32_t W, const uint16_t* srow,
+                          const Packed* snrow, const uint32_t* table, dv::Sums* a, Sums* b) {
+  uint16_t t[dv::kPitchAlign], s[dv::kPitchAlign];
+  Packed sn[dv::kPitchAlign];
+  LMX_NV_UNROLL
+  for (int e = 0; e < dv::kPitchAlign; ++e) {
+    t[e] = (uint16_t)(word[e >> 1] >> (16 * (e & 1)));
+    int32_t X = 0;
+    const bool in = row_in && dv::scene_col(x, col0 + e, W, &X);
+    s[e] = (in && t[e] != 0) ? srow[X] : (uint16_t)0;
+    sn[e] = (in && valid(tn[e])) ? snrow[X] : (Packed)0;
+  }
+  LMX_NV_UNROLL
+  for (int e = 0; e < dv::kPitchAlign; ++e) {
+    dv::add_template_pixel(t[e], a);
+    dv::add_met_pixel(t[e], s[e], a);
+    if (s[e] != 0) add_met_normals(tn[e], sn[e], table, b);     // s != 0 only where the pixel met the scene
+  }
+}
+
 // One whole match, pixel by pixel, both terms: the definition the kernel is tested against.  crop / crop_normals: [h][pitch]; scene /
 // scene_normals: [H] rows of scene_pitch elements.  The depth half is dv::diff_match.
 LMX_NV_FN void diff_match(const uint16_t* crop, const Packed* crop_normals, int32_t w, int32_t h, int32_t pitch, const uint16_t* scene,
@@ -139,6 +167,26 @@ LMX_NV_FN void diff_match(const uint16_t* crop, const Packed* crop_normals, int3
       const uint16_t s = scene[(size_t)Y * scene_pitch + (size_t)X];
       dv::add_met_pixel(t, s, &a);
       if (s != 0) add_met_normals(crop_normals[(size_t)i * (size_t)pitch + j], scene_normals[(size_t)Y * scene_pitch + (size_t)X], table, &n);
+    }
+  }
+  *dd = a;
+  *nd = n;
+}
+
+// The same match walked the way the kernel walks it: whole vectors over the padded rows (the padding's depths and normals must be zeros).
+LMX_NV_FN void diff_match_vectors(const uint16_t* crop, const Packed* crop_normals, int32_t h, int32_t pitch, const uint16_t* scene, const Packed* scene_normals,
+                                  int32_t W, int32_t H, size_t scene_pitch, int32_t x, int32_t y, const uint32_t* table, dv::Sums* dd, Sums* nd) {
+  dv::Sums a = {0, 0, 0};
+  Sums n = {0, 0};
+  for (int32_t i = 0; i < h; ++i) {
+    int32_t Y = 0;
+    const bool row_in = dv::scene_row(y, i, H, &Y);
+    for (int32_t c = 0; c < pitch; c += dv::kPitchAlign) {
+      const uint16_t* p = crop + (size_t)i * (size_t)pitch + c;
+      uint32_t word[4];
+      for (int k = 0; k < 4; ++k) word[k] = (uint32_t)p[2 * k] | ((uint32_t)p[2 * k + 1] << 16);
+      add_vector(word, crop_normals + (size_t)i * (size_t)pitch + c, row_in, x, c, W, scene + (size_t)Y * scene_pitch, scene_normals + (size_t)Y * scene_pitch,
+                 table, &a, &n);
     }
   }
   *dd = a;

@@ -10,7 +10,7 @@
 //                  narrower than 64 vectors packs several rows into a wave; waves take rows (groups of rows) in turn.  Scene pixels are
 //                  read as uint16 under the in-image predicate of lmx_depth_verify.hpp and nowhere else.  Per-lane sums are 64-bit;
 //                  wave shuffles, then LDS across the four waves, then one 16-byte store.  No atomics, no workgroup waits for another.
-//   k_depth_diff_records   the same walk (depth_diff_walk, shared by both kernels), one workgroup per RAW record of an output slot, against
+//   k_depth_diff_records   the same walk (diff_walk: one template for all four walk kernels), one workgroup per RAW record of an output slot, against
 //                  the scene lmx_depth_templates_upload_scene left on the device: the input of the scored consumer chain (lmx_f2.hip)
 //   scene          one pinned staging buffer and one device buffer per object.  lmx_depth_diff_matches stages the frames that have matches
 //                  and waits for its results; upload_scene stages all frames, records an event behind their copies and returns
@@ -20,8 +20,10 @@
 //                  in-image predicate, one 8-byte store per pixel.  Crops: once per enable_normals, all crops in one launch, into chunks that
 //                  mirror the depth chunks (same pitch: the padding's normals are zeros).  Scene frames: once per scene, when a normal-scored
 //                  call first needs them, on that call's stream behind the scene's event
-//   k_verify_diff / k_verify_diff_records   the walk of k_depth_diff with both terms in one pass (verify_diff_walk): the two stored
-//                  normals of a pixel are read next to its two depths, their angle comes out of the chord table in global memory
+//   k_verify_diff / k_verify_diff_records   the NORMALS instantiation of the same walk, both terms in one pass (nv::add_vector): the two
+//                  stored normals of a pixel are read next to its two depths, their angle comes out of the chord table in global memory
+// The host half has one launch site for jobs (run_jobs) and one for records (depth_launch_records), one body for both match-list paths
+// (diff_selected) and one guard in front of every normal-scored call (need_normals).
 #include <algorithm>
 #include <cstring>
 #include <memory>
@@ -79,73 +81,7 @@ __device__ __forceinline__ uint4 load_global_16(const uint16_t* p) {
 #endif
 }
 
-// The crop walk of one match at (x, y) against one scene frame, by a whole 256-lane workgroup: both kernels below end in it.  Every lane of
-// the workgroup must arrive (it holds a barrier); lane 0 stores the 16-byte result.
-__device__ __forceinline__ void depth_diff_walk(const DepthCrop c, int32_t x, int32_t y, const uint16_t* __restrict__ frame, int W, int H,
-                                                lmx_depth_diff_t* __restrict__ out) {
-  __shared__ unsigned long long s_sum[4];
-  __shared__ int s_valid[4], s_templ[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (c.w <= 0 || c.h <= 0) {   // an empty crop: the same for every lane of the workgroup, before any barrier
-    if (tid == 0) *reinterpret_cast<int4*>(out) = make_int4(0, 0, 0, 0);
-    return;
-  }
-  const int vpr = c.pitch / dv::kPitchAlign;        // vectors in a row
-  const int lanes_per_row = vpr < 64 ? vpr : 64;
-  const int rows_per_pass = 64 / lanes_per_row;     // rows a wave takes at once
-  const int sub = lane / lanes_per_row, v0 = lane - sub * lanes_per_row;
-  dv::Sums a = {0, 0, 0};
-  for (int row0 = wave * rows_per_pass; row0 < c.h; row0 += 4 * rows_per_pass) {
-    const int i = row0 + sub;
-    if (sub >= rows_per_pass || i >= c.h) continue;
-    int32_t Y = 0;
-    const bool row_in = dv::scene_row(y, i, H, &Y);
-    const uint16_t* trow = c.data + (size_t)i * c.pitch;
-    const uint16_t* srow = frame + (size_t)Y * W;     // Y = 0 when the row lies outside: never read then
-    for (int v = v0; v < vpr; v += lanes_per_row) {
-      const uint4 q = load_global_16(trow + v * dv::kPitchAlign);   // past w: the padding, zeros
-      const uint32_t word[4] = {q.x, q.y, q.z, q.w};
-      dv::add_vector(word, row_in, x, v * dv::kPitchAlign, W, srow, &a);
-    }
-  }
-  unsigned long long sum = a.sum_abs_mm;
-  int nv = a.n_valid, nt = a.n_template;
-  for (int off = 32; off > 0; off >>= 1) {
-    sum += __shfl_down(sum, off, 64);
-    nv += __shfl_down(nv, off, 64);
-    nt += __shfl_down(nt, off, 64);
-  }
-  if (lane == 0) { s_sum[wave] = sum; s_valid[wave] = nv; s_templ[wave] = nt; }
-  __syncthreads();
-  if (tid == 0) {
-    sum = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
-    nv = s_valid[0] + s_valid[1] + s_valid[2] + s_valid[3];
-    nt = s_templ[0] + s_templ[1] + s_templ[2] + s_templ[3];
-    *reinterpret_cast<int4*>(out) = make_int4((int)(uint32_t)sum, (int)(uint32_t)(sum >> 32), nv, nt);
-  }
-}
-
-__global__ __launch_bounds__(256) void k_depth_diff(const DepthCrop* __restrict__ crops, const DepthJob* __restrict__ jobs,
-                                                    const uint16_t* __restrict__ scene, int W, int H, lmx_depth_diff_t* __restrict__ out) {
-  const DepthJob job = jobs[blockIdx.x];
-  depth_diff_walk(crops[job.template_id], job.x, job.y, scene + (size_t)job.frame * H * W, W, H, &out[blockIdx.x]);
-}
-
-// One workgroup per RAW record of an output slot (the device consumer chain carries the result through its sorts: lmx_f2.hip, SCORED).  A
-// record that is no job -- a template the table does not hold, a frame the scene does not hold, another class -- gets zeros without a look at
-// the table or the scene; the three tests are the same for every lane and come before any barrier.
-__global__ __launch_bounds__(256) void k_depth_diff_records(const DepthCrop* __restrict__ crops, int32_t count, const lmx_raw_match_t* __restrict__ recs,
-                                                            const uint16_t* __restrict__ scene, int32_t n_frames, int W, int H, int32_t class_index,
-                                                            lmx_depth_diff_t* __restrict__ diffs) {
-  const lmx_raw_match_t r = recs[blockIdx.x];
-  if (r.template_id < 0 || r.template_id >= count || r.frame < 0 || r.frame >= n_frames || (class_index >= 0 && r.class_index != class_index)) {
-    if (threadIdx.x == 0) *reinterpret_cast<int4*>(&diffs[blockIdx.x]) = make_int4(0, 0, 0, 0);
-    return;
-  }
-  depth_diff_walk(crops[r.template_id], r.x, r.y, scene + (size_t)r.frame * H * W, W, H, &diffs[blockIdx.x]);
-}
-
-// ---- the normal term ---------------------------------------------------------------------------------------------------------------------
+// ---- the normal maps (only for an object that enabled normals) -----------------------------------------------------------------------------------------
 // Normals of one w x h depth image with rows of `pitch` elements into dst[h][pitch], by the workgroups blockIdx.x, blockIdx.x + gridDim.x, ...
 // of 256 pixels each; elements past w (a crop's padding) get zeros.  Every depth read lies inside [0, w) x [0, h) (nv::depth_or_zero).
 __device__ __forceinline__ void normal_map_image(const uint16_t* __restrict__ src, int w, int h, int pitch, nv::Packed* __restrict__ dst, const nv::Params p) {
@@ -167,24 +103,43 @@ __global__ __launch_bounds__(256) void k_normal_map_frames(const uint16_t* __res
   normal_map_image(scene + frame, W, H, W, out + frame, p);
 }
 
-// depth_diff_walk with both terms: the same lanes take the same vectors, the depth sums are dv's own (add_template_pixel, add_met_pixel).
-// A lane reads its eight crop normals as four aligned 16-byte vectors next to the crop's depths; the scene's depth and the scene's normal
-// of a pixel are read side by side, each under the in-image predicate and nowhere else (the normal where the crop's normal is valid, which
-// implies t != 0), so the chain of dependent loads is crop -> scene -> table.  Every lane of the workgroup must arrive; lane 0 stores the
-// two 16-byte results.
-__device__ __forceinline__ void verify_diff_walk(const DepthCrop c, const nv::Packed* __restrict__ cn, int32_t x, int32_t y, const uint16_t* __restrict__ frame,
-                                                 const nv::Packed* __restrict__ fn, int W, int H, const uint32_t* __restrict__ table,
-                                                 lmx_depth_diff_t* __restrict__ out, lmx_normal_diff_t* __restrict__ nout) {
-  __shared__ unsigned long long s_sum[4], s_ang[4];
-  __shared__ int s_valid[4], s_templ[4], s_norm[4];
+// ---- the crop walk ------------------------------------------------------------------------------------------------------------------------------------
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {   // lane 0 gets the sum over the wave's 64 lanes
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  return v;
+}
+
+// The 16-byte result of a match, and with NORMALS the 16 bytes of its normal term.
+template <bool NORMALS>
+__device__ __forceinline__ void store_sums(lmx_depth_diff_t* __restrict__ out, lmx_normal_diff_t* __restrict__ nout, unsigned long long sum, int n_valid,
+                                           int n_template, unsigned long long angle, int n_normal) {
+  *reinterpret_cast<int4*>(out) = make_int4((int)(uint32_t)sum, (int)(uint32_t)(sum >> 32), n_valid, n_template);
+  if constexpr (NORMALS) *reinterpret_cast<int4*>(nout) = make_int4((int)(uint32_t)angle, (int)(uint32_t)(angle >> 32), n_normal, 0);
+}
+
+// The crop walk of one match of template `id` at (x, y) against scene frame `f`, by a whole 256-lane workgroup: all four kernels below end
+// in it.  Lanes run along crop rows, one aligned vector each (dv::add_vector).  With NORMALS both terms in the same pass (nv::add_vector):
+// a lane reads its eight crop normals as four aligned 16-byte vectors next to the crop's depths, the scene's normals next to the scene's
+// depths, the angles out of the chord table; without, normals / scene_normals / table / nout are not looked at.  What is no job (is_job
+// false, or an empty crop) gets zeros without a look at the table or the scene: the same for every lane, before any barrier.  Every lane of
+// the workgroup must arrive (it holds a barrier); lane 0 stores the result.
+template <bool NORMALS>
+__device__ __forceinline__ void diff_walk(const DepthCrop* __restrict__ crops, nv::Packed* const* __restrict__ normals, bool is_job, int32_t id, int32_t x, int32_t y,
+                                          int32_t f, const uint16_t* __restrict__ scene, const nv::Packed* __restrict__ scene_normals, int W, int H,
+                                          const uint32_t* __restrict__ table, lmx_depth_diff_t* __restrict__ out, lmx_normal_diff_t* __restrict__ nout) {
+  __shared__ unsigned long long s_sum[NORMALS ? 8 : 4];   // per wave: sum_abs_mm, then sum_angle_urad
+  __shared__ int s_count[NORMALS ? 12 : 8];               // per wave: n_valid, n_template, then n_normal
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (c.w <= 0 || c.h <= 0) {   // an empty crop: the same for every lane of the workgroup, before any barrier
-    if (tid == 0) { *reinterpret_cast<int4*>(out) = make_int4(0, 0, 0, 0); *reinterpret_cast<int4*>(nout) = make_int4(0, 0, 0, 0); }
+  const DepthCrop c = is_job ? crops[id] : DepthCrop{nullptr, 0, 0, 0, 0};
+  if (c.w <= 0 || c.h <= 0) {
+    if (tid == 0) store_sums<NORMALS>(out, nout, 0, 0, 0, 0, 0);
     return;
   }
-  const int vpr = c.pitch / dv::kPitchAlign;
+  const uint16_t* frame = scene + (size_t)f * H * W;
+  const int vpr = c.pitch / dv::kPitchAlign;        // vectors in a row
   const int lanes_per_row = vpr < 64 ? vpr : 64;
-  const int rows_per_pass = 64 / lanes_per_row;
+  const int rows_per_pass = 64 / lanes_per_row;     // rows a wave takes at once
   const int sub = lane / lanes_per_row, v0 = lane - sub * lanes_per_row;
   dv::Sums a = {0, 0, 0};
   nv::Sums b = {0, 0};
@@ -194,86 +149,84 @@ __device__ __forceinline__ void verify_diff_walk(const DepthCrop c, const nv::Pa
     int32_t Y = 0;
     const bool row_in = dv::scene_row(y, i, H, &Y);
     const uint16_t* trow = c.data + (size_t)i * c.pitch;
-    const nv::Packed* nrow = cn + (size_t)i * c.pitch;
     const uint16_t* srow = frame + (size_t)Y * W;     // Y = 0 when the row lies outside: never read then
-    const nv::Packed* snrow = fn + (size_t)Y * W;
     for (int v = v0; v < vpr; v += lanes_per_row) {
       const int col0 = v * dv::kPitchAlign;
       const uint4 q = load_global_16(trow + col0);    // past w: the padding, zeros
       const uint32_t word[4] = {q.x, q.y, q.z, q.w};
-      // the crop's eight normals: 64 contiguous, 16-byte aligned bytes (the padding's are zeros, like its depths)
-      nv::Packed tn[dv::kPitchAlign], sn[dv::kPitchAlign];
+      if constexpr (NORMALS) {
+        const nv::Packed* nvec = normals[id] + (size_t)i * c.pitch + col0;   // 64 contiguous, 16-byte aligned bytes
+        nv::Packed tn[dv::kPitchAlign];
 #pragma unroll
-      for (int k = 0; k < dv::kPitchAlign / 2; ++k) {
-        const uint4 n2 = load_global_16(reinterpret_cast<const uint16_t*>(nrow + col0 + 2 * k));
-        tn[2 * k] = (nv::Packed)n2.x | ((nv::Packed)n2.y << 32);
-        tn[2 * k + 1] = (nv::Packed)n2.z | ((nv::Packed)n2.w << 32);
-      }
-      uint16_t t[dv::kPitchAlign], s[dv::kPitchAlign];
-#pragma unroll
-      for (int e = 0; e < dv::kPitchAlign; ++e) {     // every load first: neither scene read waits for the other
-        t[e] = (uint16_t)(word[e >> 1] >> (16 * (e & 1)));
-        int32_t X = 0;
-        const bool in = row_in && dv::scene_col(x, col0 + e, W, &X);
-        s[e] = (in && t[e] != 0) ? srow[X] : (uint16_t)0;
-        sn[e] = (in && nv::valid(tn[e])) ? snrow[X] : (nv::Packed)0;     // a valid crop normal has t != 0
-      }
-#pragma unroll
-      for (int e = 0; e < dv::kPitchAlign; ++e) {
-        dv::add_template_pixel(t[e], &a);
-        dv::add_met_pixel(t[e], s[e], &a);
-        if (s[e] != 0) nv::add_met_normals(tn[e], sn[e], table, &b);     // s != 0 only where the pixel met the scene
+        for (int k = 0; k < dv::kPitchAlign / 2; ++k) {
+          const uint4 n2 = load_global_16(reinterpret_cast<const uint16_t*>(nvec + 2 * k));
+          tn[2 * k] = (nv::Packed)n2.x | ((nv::Packed)n2.y << 32);
+          tn[2 * k + 1] = (nv::Packed)n2.z | ((nv::Packed)n2.w << 32);
+        }
+        nv::add_vector(word, tn, row_in, x, col0, W, srow, scene_normals + (srow - scene), table, &a, &b);   // the same row of the scene's normals
+      } else {
+        dv::add_vector(word, row_in, x, col0, W, srow, &a);
       }
     }
   }
-  unsigned long long sum = a.sum_abs_mm, ang = b.sum_angle_urad;
-  int nvld = a.n_valid, nt = a.n_template, nn = b.n_normal;
-  for (int off = 32; off > 0; off >>= 1) {
-    sum += __shfl_down(sum, off, 64);
-    ang += __shfl_down(ang, off, 64);
-    nvld += __shfl_down(nvld, off, 64);
-    nt += __shfl_down(nt, off, 64);
-    nn += __shfl_down(nn, off, 64);
+  const unsigned long long sum = wave_sum<unsigned long long>(a.sum_abs_mm);
+  const int n_valid = wave_sum(a.n_valid), n_template = wave_sum(a.n_template);
+  if (lane == 0) { s_sum[wave] = sum; s_count[wave] = n_valid; s_count[4 + wave] = n_template; }
+  if constexpr (NORMALS) {
+    const unsigned long long angle = wave_sum<unsigned long long>(b.sum_angle_urad);
+    const int n_normal = wave_sum(b.n_normal);
+    if (lane == 0) { s_sum[4 + wave] = angle; s_count[8 + wave] = n_normal; }
   }
-  if (lane == 0) { s_sum[wave] = sum; s_ang[wave] = ang; s_valid[wave] = nvld; s_templ[wave] = nt; s_norm[wave] = nn; }
   __syncthreads();
   if (tid == 0) {
-    sum = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
-    ang = s_ang[0] + s_ang[1] + s_ang[2] + s_ang[3];
-    nvld = s_valid[0] + s_valid[1] + s_valid[2] + s_valid[3];
-    nt = s_templ[0] + s_templ[1] + s_templ[2] + s_templ[3];
-    nn = s_norm[0] + s_norm[1] + s_norm[2] + s_norm[3];
-    *reinterpret_cast<int4*>(out) = make_int4((int)(uint32_t)sum, (int)(uint32_t)(sum >> 32), nvld, nt);
-    *reinterpret_cast<int4*>(nout) = make_int4((int)(uint32_t)ang, (int)(uint32_t)(ang >> 32), nn, 0);
+    unsigned long long total[2] = {0, 0};
+    int count[3] = {0, 0, 0};
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      total[0] += s_sum[w]; count[0] += s_count[w]; count[1] += s_count[4 + w];
+      if constexpr (NORMALS) { total[1] += s_sum[4 + w]; count[2] += s_count[8 + w]; }
+    }
+    store_sums<NORMALS>(out, nout, total[0], count[0], count[1], total[1], count[2]);
   }
+}
+
+// A RAW record of an output slot is a job unless the table does not hold its template, the scene does not hold its frame, or it is of another
+// class (the device consumer chain carries the result, zeros then, through its sorts: lmx_f2.hip, SCORED and NORMAL).
+__device__ __forceinline__ bool record_is_job(const lmx_raw_match_t& r, int32_t count, int32_t n_frames, int32_t class_index) {
+  return r.template_id >= 0 && r.template_id < count && r.frame >= 0 && r.frame < n_frames && (class_index < 0 || r.class_index == class_index);
+}
+
+// The four kernels, one workgroup per match: the depth term alone or both terms, times the two ways of fetching a job -- job j of the host's
+// match list (its frame is its slot among the frames in `scene`), or RAW record j against the scene upload_scene left on the device.
+__global__ __launch_bounds__(256) void k_depth_diff(const DepthCrop* __restrict__ crops, const DepthJob* __restrict__ jobs,
+                                                    const uint16_t* __restrict__ scene, int W, int H, lmx_depth_diff_t* __restrict__ out) {
+  const DepthJob j = jobs[blockIdx.x];
+  diff_walk<false>(crops, nullptr, true, j.template_id, j.x, j.y, j.frame, scene, nullptr, W, H, nullptr, &out[blockIdx.x], nullptr);
+}
+
+__global__ __launch_bounds__(256) void k_depth_diff_records(const DepthCrop* __restrict__ crops, int32_t count, const lmx_raw_match_t* __restrict__ recs,
+                                                            const uint16_t* __restrict__ scene, int32_t n_frames, int W, int H, int32_t class_index,
+                                                            lmx_depth_diff_t* __restrict__ diffs) {
+  const lmx_raw_match_t r = recs[blockIdx.x];
+  diff_walk<false>(crops, nullptr, record_is_job(r, count, n_frames, class_index), r.template_id, r.x, r.y, r.frame, scene, nullptr, W, H, nullptr,
+                   &diffs[blockIdx.x], nullptr);
 }
 
 __global__ __launch_bounds__(256) void k_verify_diff(const DepthCrop* __restrict__ crops, nv::Packed* const* __restrict__ normals, const DepthJob* __restrict__ jobs,
                                                      const uint16_t* __restrict__ scene, const nv::Packed* __restrict__ scene_normals, int W, int H,
                                                      const uint32_t* __restrict__ table, lmx_depth_diff_t* __restrict__ out, lmx_normal_diff_t* __restrict__ nout) {
-  const DepthJob job = jobs[blockIdx.x];
-  const size_t frame = (size_t)job.frame * H * W;
-  verify_diff_walk(crops[job.template_id], normals[job.template_id], job.x, job.y, scene + frame, scene_normals + frame, W, H, table, &out[blockIdx.x],
-                   &nout[blockIdx.x]);
+  const DepthJob j = jobs[blockIdx.x];
+  diff_walk<true>(crops, normals, true, j.template_id, j.x, j.y, j.frame, scene, scene_normals, W, H, table, &out[blockIdx.x], &nout[blockIdx.x]);
 }
 
-// One workgroup per RAW record, as k_depth_diff_records: a record that is no job gets zeros in both results.
 __global__ __launch_bounds__(256) void k_verify_diff_records(const DepthCrop* __restrict__ crops, nv::Packed* const* __restrict__ normals, int32_t count,
                                                              const lmx_raw_match_t* __restrict__ recs, const uint16_t* __restrict__ scene,
                                                              const nv::Packed* __restrict__ scene_normals, int32_t n_frames, int W, int H, int32_t class_index,
                                                              const uint32_t* __restrict__ table, lmx_depth_diff_t* __restrict__ diffs,
                                                              lmx_normal_diff_t* __restrict__ ndiffs) {
   const lmx_raw_match_t r = recs[blockIdx.x];
-  if (r.template_id < 0 || r.template_id >= count || r.frame < 0 || r.frame >= n_frames || (class_index >= 0 && r.class_index != class_index)) {
-    if (threadIdx.x == 0) {
-      *reinterpret_cast<int4*>(&diffs[blockIdx.x]) = make_int4(0, 0, 0, 0);
-      *reinterpret_cast<int4*>(&ndiffs[blockIdx.x]) = make_int4(0, 0, 0, 0);
-    }
-    return;
-  }
-  const size_t frame = (size_t)r.frame * H * W;
-  verify_diff_walk(crops[r.template_id], normals[r.template_id], r.x, r.y, scene + frame, scene_normals + frame, W, H, table, &diffs[blockIdx.x],
-                   &ndiffs[blockIdx.x]);
+  diff_walk<true>(crops, normals, record_is_job(r, count, n_frames, class_index), r.template_id, r.x, r.y, r.frame, scene, scene_normals, W, H, table,
+                  &diffs[blockIdx.x], &ndiffs[blockIdx.x]);
 }
 
 }  // namespace
@@ -306,7 +259,7 @@ struct lmx_depth_templates {
   bool scene_pending = false;            // scene_ready has been recorded and h_scene may still be read by a copy
   lmx::DepthJob *d_jobs = nullptr, *h_jobs = nullptr;
   lmx_depth_diff_t *d_out = nullptr, *h_out = nullptr;
-  size_t jobs_cap = 0;                   // entries
+  size_t jobs_cap = 0, out_cap = 0;      // entries
   std::vector<uint32_t> sel;             // scratch of a call: the matches it computes
   std::vector<int32_t> sel_slot;         // scratch of a call: the uploaded frame of each of them
   std::vector<int32_t> slot;             // scratch of a call: frame -> uploaded frame, or -1
@@ -387,27 +340,23 @@ struct lmx_depth_templates {
     scene_cap = cap;
     return LMX_OK;
   }
-  lmx_status grow_jobs(size_t n) {
-    if (n <= jobs_cap) return LMX_OK;
-    (void)hipFree(d_jobs); (void)hipFree(d_out); (void)hipHostFree(h_jobs); (void)hipHostFree(h_out);
-    d_jobs = h_jobs = nullptr; d_out = h_out = nullptr; jobs_cap = 0;
-    const size_t cap = std::max(n, (size_t)1024);
-    DV_HIP(hipMalloc(&d_jobs, cap * sizeof(lmx::DepthJob)));
-    DV_HIP(hipMalloc(&d_out, cap * sizeof(lmx_depth_diff_t)));
-    DV_HIP(hipHostMalloc(&h_jobs, cap * sizeof(lmx::DepthJob), hipHostMallocDefault));
-    DV_HIP(hipHostMalloc(&h_out, cap * sizeof(lmx_depth_diff_t), hipHostMallocDefault));
-    jobs_cap = cap;
+  // a device array and its pinned twin hold at least n entries
+  template <typename T>
+  static lmx_status grow_pair(T*& d, T*& h, size_t& cap, size_t n) {
+    if (n <= cap) return LMX_OK;
+    (void)hipFree(d); (void)hipHostFree(h);
+    d = h = nullptr; cap = 0;
+    const size_t want = std::max(n, (size_t)1024);
+    DV_HIP(hipMalloc(&d, want * sizeof(T)));
+    DV_HIP(hipHostMalloc(&h, want * sizeof(T), hipHostMallocDefault));
+    cap = want;
     return LMX_OK;
   }
-  lmx_status grow_nout(size_t n) {
-    if (n <= nout_cap) return LMX_OK;
-    (void)hipFree(d_nout); (void)hipHostFree(h_nout);
-    d_nout = h_nout = nullptr; nout_cap = 0;
-    const size_t cap = std::max(n, (size_t)1024);
-    DV_HIP(hipMalloc(&d_nout, cap * sizeof(lmx_normal_diff_t)));
-    DV_HIP(hipHostMalloc(&h_nout, cap * sizeof(lmx_normal_diff_t), hipHostMallocDefault));
-    nout_cap = cap;
-    return LMX_OK;
+  // Room for n jobs and their depth results; for their normal results only when a call asks (an object without normals never does).
+  lmx_status grow_jobs(size_t n, bool normals) {
+    if (lmx_status st = grow_pair(d_jobs, h_jobs, jobs_cap, n)) return st;
+    if (lmx_status st = grow_pair(d_out, h_out, out_cap, n)) return st;
+    return normals ? grow_pair(d_nout, h_nout, nout_cap, n) : LMX_OK;
   }
   // The normals of the first n_frames W x H frames of d_scene, on stream `on` (which already waits for the frames' copies, or is the
   // object's own stream that carries them); every later user waits for normals_ready.
@@ -664,18 +613,18 @@ lmx_status queue_frame(lmx_depth_templates* t, const lmx_image& im, int32_t slot
 // The device half of a depth check on the host's match list: the first n entries of h_jobs against the W x H frames already in d_scene
 // (a job's frame is its slot there): job upload, k_depth_diff, read-back into h_out.  The object's mutex is the caller's to hold.
 // With `normals`: k_verify_diff instead, against the normals of the n_frames frames there (computed first if nobody has), h_nout too.
-lmx_status run_jobs(lmx_depth_templates* t, size_t n, int32_t W, int32_t H, bool normals = false, int32_t n_frames = 0) {
+lmx_status run_jobs(lmx_depth_templates* t, size_t n, int32_t n_frames, int32_t W, int32_t H, bool normals) {
   hipStream_t s = t->s;
   DV_HIP(hipMemcpyAsync(t->d_jobs, t->h_jobs, n * sizeof(lmx::DepthJob), hipMemcpyHostToDevice, s));
-  if (normals) {
+  if (normals)
     if (lmx_status st = t->scene_normals_on(s, nullptr, n_frames, W, H)) return st;
-    const int pe = t->prof_begin(lmx_depth_templates::PK_VERIFY_DIFF, s);
+  const int pe = normals ? t->prof_begin(lmx_depth_templates::PK_VERIFY_DIFF, s) : -1;   // k_depth_diff has no bracket
+  if (normals)
     hipLaunchKernelGGL(lmx::k_verify_diff, dim3((unsigned)n), dim3(256), 0, s, t->d_table, t->d_ntable, t->d_jobs, t->d_scene, t->d_scene_normals, W, H,
                        t->d_angle, t->d_out, t->d_nout);
-    t->prof_end(pe, s);
-  } else {
+  else
     hipLaunchKernelGGL(lmx::k_depth_diff, dim3((unsigned)n), dim3(256), 0, s, t->d_table, t->d_jobs, t->d_scene, W, H, t->d_out);
-  }
+  t->prof_end(pe, s);
   DV_HIP(hipGetLastError());
   DV_HIP(hipMemcpyAsync(t->h_out, t->d_out, n * sizeof(lmx_depth_diff_t), hipMemcpyDeviceToHost, s));
   if (normals) DV_HIP(hipMemcpyAsync(t->h_nout, t->d_nout, n * sizeof(lmx_normal_diff_t), hipMemcpyDeviceToHost, s));
@@ -713,11 +662,37 @@ lmx_status compute_crop_normals(lmx_depth_templates* t) {
   t->ncrops_ready = true;
   return LMX_OK;
 }
-// Before a normal-scored call touches the device: the object's stream, the angle table, the crops' normals.
-lmx_status ensure_normals(lmx_depth_templates* t) {
+// A normal-scored call: refused under the caller's name (`what`, or none) before enable_normals; otherwise, before it touches the device,
+// the object's stream, the angle table and the crops' normals.  With `device` false only the refusal: for the two entry points that check
+// their other arguments, without a device, before they come back here.
+lmx_status need_normals(lmx_depth_templates* t, const char* what, bool device = true) {
+  if (!t->normals_on) {
+    lmx::set_error("%s%scall lmx_depth_templates_enable_normals first", what ? what : "", what ? ": " : "");
+    return LMX_ERR_INVALID_ARG;
+  }
+  if (!device) return LMX_OK;
   if (lmx_status st = t->ensure_device()) return st;
   if (lmx_status st = t->ensure_normal_device()) return st;
   return t->ncrops_ready ? LMX_OK : compute_crop_normals(t);
+}
+
+// The shared end of both match-list paths: matches[sel[k]] as job k against the n_frames W x H frames in d_scene (its frame there is
+// sel_slot[k], or `frame` for all of them when sel_slot is null), then out[sel[k]] / nout[sel[k]] (either may be null; nout decides whether
+// the normal term is computed).  The caller has zeroed out / nout and made the device ready.
+lmx_status diff_selected(lmx_depth_templates* t, const lmx_match_t* matches, const int32_t* sel_slot, int32_t frame, int32_t n_frames, int32_t W, int32_t H,
+                         lmx_depth_diff_t* out, lmx_normal_diff_t* nout) {
+  const size_t n_sel = t->sel.size();
+  if (lmx_status st = t->grow_jobs(n_sel, nout != nullptr)) return st;
+  for (size_t k = 0; k < n_sel; ++k) {
+    const lmx_match_t& m = matches[t->sel[k]];
+    t->h_jobs[k] = lmx::DepthJob{m.x, m.y, m.template_id, sel_slot ? sel_slot[k] : frame};
+  }
+  if (lmx_status st = run_jobs(t, n_sel, n_frames, W, H, nout != nullptr)) return st;
+  for (size_t k = 0; k < n_sel; ++k) {
+    if (out) out[t->sel[k]] = t->h_out[k];
+    if (nout) nout[t->sel[k]] = t->h_nout[k];
+  }
+  return LMX_OK;
 }
 }  // namespace
 
@@ -763,24 +738,20 @@ lmx_status depth_upload_scene(lmx_depth_templates* t, const lmx_image* depth, in
 lmx_status depth_launch_records(lmx_depth_templates* t, hipStream_t s, const lmx_raw_match_t* d_recs, uint32_t n_records, int32_t class_index,
                                 lmx_depth_diff_t* d_diffs, lmx_normal_diff_t* d_ndiffs) {
   if (t->scene_frames < 1) { set_error("no scene uploaded: call lmx_depth_templates_upload_scene first"); return LMX_ERR_INVALID_ARG; }
-  if (d_ndiffs) {
-    if (!t->normals_on) { set_error("call lmx_depth_templates_enable_normals first"); return LMX_ERR_INVALID_ARG; }
-    if (lmx_status st = ensure_normals(t)) return st;
-  }
+  if (d_ndiffs)
+    if (lmx_status st = need_normals(t, nullptr)) return st;
   DV_HIP(hipStreamWaitEvent(s, t->scene_ready, 0));
   if (n_records == 0) return LMX_OK;
-  if (d_ndiffs) {   // the scene's normals first, on this stream, if this is the scene's first normal-scored call
+  if (d_ndiffs)   // the scene's normals first, on this stream, if this is the scene's first normal-scored call
     if (lmx_status st = t->scene_normals_on(s, nullptr, t->scene_frames, t->scene_W, t->scene_H)) return st;
-    const int pe = t->prof_begin(lmx_depth_templates::PK_VERIFY_DIFF_RECORDS, s);
-    hipLaunchKernelGGL(k_verify_diff_records, dim3(n_records), dim3(256), 0, s, t->d_table, t->d_ntable, (int32_t)t->table.size(), d_recs, t->d_scene,
-                       t->d_scene_normals, t->scene_frames, t->scene_W, t->scene_H, class_index, t->d_angle, d_diffs, d_ndiffs);
-    t->prof_end(pe, s);
-    DV_HIP(hipGetLastError());
-    return LMX_OK;
-  }
-  const int pe = t->prof_begin(lmx_depth_templates::PK_DEPTH_DIFF_RECORDS, s);
-  hipLaunchKernelGGL(k_depth_diff_records, dim3(n_records), dim3(256), 0, s, t->d_table, (int32_t)t->table.size(), d_recs, t->d_scene, t->scene_frames,
-                     t->scene_W, t->scene_H, class_index, d_diffs);
+  const int32_t count = (int32_t)t->table.size();
+  const int pe = t->prof_begin(d_ndiffs ? lmx_depth_templates::PK_VERIFY_DIFF_RECORDS : lmx_depth_templates::PK_DEPTH_DIFF_RECORDS, s);
+  if (d_ndiffs)
+    hipLaunchKernelGGL(k_verify_diff_records, dim3(n_records), dim3(256), 0, s, t->d_table, t->d_ntable, count, d_recs, t->d_scene, t->d_scene_normals,
+                       t->scene_frames, t->scene_W, t->scene_H, class_index, t->d_angle, d_diffs, d_ndiffs);
+  else
+    hipLaunchKernelGGL(k_depth_diff_records, dim3(n_records), dim3(256), 0, s, t->d_table, count, d_recs, t->d_scene, t->scene_frames, t->scene_W,
+                       t->scene_H, class_index, d_diffs);
   t->prof_end(pe, s);
   DV_HIP(hipGetLastError());
   return LMX_OK;
@@ -801,23 +772,10 @@ lmx_status depth_diff_resident(lmx_depth_templates* t, const lmx_match_t* matche
     if (m.template_id < 0 || (size_t)m.template_id >= count) continue;   // zeros, as k_depth_diff_records gives; the cluster step refuses the id
     t->sel.push_back((uint32_t)i);
   }
-  const size_t n_sel = t->sel.size();
-  if (n_sel == 0) return LMX_OK;
-  if (lmx_status st = t->grow_jobs(n_sel)) return st;
-  for (size_t k = 0; k < n_sel; ++k) {
-    const lmx_match_t& m = matches[t->sel[k]];
-    t->h_jobs[k] = DepthJob{m.x, m.y, m.template_id, frame};
-  }
-  if (nout) {
-    if (!t->normals_on) { set_error("call lmx_depth_templates_enable_normals first"); return LMX_ERR_INVALID_ARG; }
-    if (lmx_status st = ensure_normals(t)) return st;
-    if (lmx_status st = t->grow_nout(n_sel)) return st;
-  }
-  if (lmx_status st = run_jobs(t, n_sel, t->scene_W, t->scene_H, nout != nullptr, t->scene_frames)) return st;   // on the object's stream, behind the scene's copies
-  for (size_t k = 0; k < n_sel; ++k) out[t->sel[k]] = t->h_out[k];
+  if (t->sel.empty()) return LMX_OK;
   if (nout)
-    for (size_t k = 0; k < n_sel; ++k) nout[t->sel[k]] = t->h_nout[k];
-  return LMX_OK;
+    if (lmx_status st = need_normals(t, nullptr)) return st;
+  return diff_selected(t, matches, nullptr, frame, t->scene_frames, t->scene_W, t->scene_H, out, nout);   // on the object's stream, behind the scene's copies
 }
 
 }  // namespace lmx
@@ -828,7 +786,8 @@ lmx_status diff_matches_impl(const char* what, lmx_depth_templates* t, const lmx
                              const size_t* offsets, int32_t class_index, lmx_depth_diff_t* out, lmx_normal_diff_t* nout, bool normals) {
     using namespace lmx;
     if (!t) { set_error("%s: null argument", what); return LMX_ERR_INVALID_ARG; }
-    if (normals && !t->normals_on) { set_error("%s: call lmx_depth_templates_enable_normals first", what); return LMX_ERR_INVALID_ARG; }
+    if (normals)
+      if (lmx_status st = need_normals(t, what, false)) return st;
     if (n_frames < 0) { set_error("%s: n_frames = %d", what, n_frames); return LMX_ERR_INVALID_ARG; }
     if (n_frames == 0) return LMX_OK;
     if (!depth || !offsets) { set_error("%s: null argument", what); return LMX_ERR_INVALID_ARG; }
@@ -858,9 +817,8 @@ lmx_status diff_matches_impl(const char* what, lmx_depth_templates* t, const lmx
       }
     if (out) std::memset(out, 0, n_matches * sizeof(lmx_depth_diff_t));
     if (normals) std::memset(nout, 0, n_matches * sizeof(lmx_normal_diff_t));
-    const size_t n_sel = t->sel.size();
-    if (n_sel == 0) return LMX_OK;
-    if (lmx_status st = normals ? ensure_normals(t) : t->ensure_device()) return st;
+    if (t->sel.empty()) return LMX_OK;
+    if (lmx_status st = normals ? need_normals(t, what) : t->ensure_device()) return st;
     const size_t frame_bytes = (size_t)W * H * sizeof(uint16_t);
     // the frames that have matches take the place of an uploaded scene: staged row by row into pinned memory, each on its way while the
     // next is staged
@@ -868,23 +826,13 @@ lmx_status diff_matches_impl(const char* what, lmx_depth_templates* t, const lmx
     t->scene_frames = 0;
     t->scene_normals_valid = false;
     if (lmx_status st = t->grow_scene(frame_bytes * n_slots)) return st;
-    if (lmx_status st = t->grow_jobs(n_sel)) return st;
-    if (normals)
-      if (lmx_status st = t->grow_nout(n_sel)) return st;
     for (int32_t f = 0; f < n_frames; ++f)
       if (t->slot[f] >= 0)
         if (lmx_status st = queue_frame(t, depth[f], t->slot[f], W, H)) { t->drain_after_error(); return st; }
-    for (size_t k = 0; k < n_sel; ++k) {
-      const lmx_match_t& m = matches[t->sel[k]];
-      t->h_jobs[k] = DepthJob{m.x, m.y, m.template_id, t->sel_slot[k]};
-    }
-    if (lmx_status st = run_jobs(t, n_sel, W, H, normals, n_slots)) { t->drain_after_error(); return st; }
+    const lmx_status st = diff_selected(t, matches, t->sel_slot.data(), 0, n_slots, W, H, out, normals ? nout : nullptr);
+    if (st != LMX_OK) t->drain_after_error();
     t->scene_normals_valid = false;   // they belong to staged frames that are no scene
-    if (out)
-      for (size_t k = 0; k < n_sel; ++k) out[t->sel[k]] = t->h_out[k];
-    if (normals)
-      for (size_t k = 0; k < n_sel; ++k) nout[t->sel[k]] = t->h_nout[k];
-    return LMX_OK;
+    return st;
 }
 }  // namespace
 
@@ -943,13 +891,13 @@ extern "C" lmx_status lmx_depth_templates_get_normals(const lmx_depth_templates*
   return lmx::guarded("lmx_depth_templates_get_normals", [&]() -> lmx_status {
     lmx_depth_templates* t = const_cast<lmx_depth_templates*>(ct);
     if (!t) { lmx::set_error("lmx_depth_templates_get_normals: null argument"); return LMX_ERR_INVALID_ARG; }
-    if (!t->normals_on) { lmx::set_error("lmx_depth_templates_get_normals: call lmx_depth_templates_enable_normals first"); return LMX_ERR_INVALID_ARG; }
+    if (lmx_status st = need_normals(t, "lmx_depth_templates_get_normals", false)) return st;
     if (id < 0 || (size_t)id >= t->table.size()) { lmx::set_error("lmx_depth_templates_get_normals: id %d outside [0, %zu)", id, t->table.size()); return LMX_ERR_INVALID_ARG; }
     const lmx::DepthCrop& c = t->table[id];
     if (c.w <= 0 || c.h <= 0) return LMX_OK;
     if (!out) { lmx::set_error("lmx_depth_templates_get_normals: null argument"); return LMX_ERR_INVALID_ARG; }
     std::lock_guard<std::mutex> lk(t->m);
-    if (lmx_status st = ensure_normals(t)) return st;
+    if (lmx_status st = need_normals(t, "lmx_depth_templates_get_normals")) return st;
     DV_HIP(hipMemcpy2DAsync(out, (size_t)c.w * 8, t->ntable[id], (size_t)c.pitch * 8, (size_t)c.w * 8, (size_t)c.h, hipMemcpyDeviceToHost, t->s));
     DV_HIP(hipStreamSynchronize(t->s));
     return LMX_OK;
@@ -980,10 +928,10 @@ extern "C" lmx_status lmx_debug_scene_normals(lmx_depth_templates* t, int32_t fr
   return lmx::guarded("lmx_debug_scene_normals", [&]() -> lmx_status {
     if (!t || !out) { lmx::set_error("lmx_debug_scene_normals: null argument"); return LMX_ERR_INVALID_ARG; }
     std::lock_guard<std::mutex> lk(t->m);
-    if (!t->normals_on) { lmx::set_error("lmx_debug_scene_normals: call lmx_depth_templates_enable_normals first"); return LMX_ERR_INVALID_ARG; }
+    if (lmx_status st = need_normals(t, "lmx_debug_scene_normals", false)) return st;
     if (t->scene_frames < 1) { lmx::set_error("lmx_debug_scene_normals: no scene uploaded: call lmx_depth_templates_upload_scene first"); return LMX_ERR_INVALID_ARG; }
     if (frame < 0 || frame >= t->scene_frames) { lmx::set_error("lmx_debug_scene_normals: frame %d is not in the uploaded scene (%d frames)", frame, t->scene_frames); return LMX_ERR_INVALID_ARG; }
-    if (lmx_status st = ensure_normals(t)) return st;
+    if (lmx_status st = need_normals(t, "lmx_debug_scene_normals")) return st;
     if (lmx_status st = t->scene_normals_on(t->s, nullptr, t->scene_frames, t->scene_W, t->scene_H)) return st;
     const size_t px = (size_t)t->scene_W * t->scene_H;
     DV_HIP(hipMemcpyAsync(out, t->d_scene_normals + px * frame, px * sizeof(lmx::nv::Packed), hipMemcpyDeviceToHost, t->s));

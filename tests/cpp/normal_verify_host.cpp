@@ -33,6 +33,15 @@ extern "C" void nv_host_diff(const uint16_t* crop, const uint64_t* crop_normals,
   out[0] = (long long)d.sum_abs_mm; out[1] = d.n_valid; out[2] = d.n_template; out[3] = (long long)n.sum_angle_urad; out[4] = n.n_normal;
 }
 
+// the same match through nv::diff_match_vectors: crop / crop_normals are [h][pitch], pitch a multiple of 8, the padding zeros
+extern "C" void nv_host_diff_vectors(const uint16_t* crop, const uint64_t* crop_normals, int h, int pitch, const uint16_t* scene, const uint64_t* scene_normals,
+                                     int W, int H, size_t scene_pitch, int x, int y, const uint32_t* table, long long* out) {
+  dv::Sums d;
+  nv::Sums n;
+  nv::diff_match_vectors(crop, crop_normals, h, pitch, scene, scene_normals, W, H, scene_pitch, x, y, table, &d, &n);
+  out[0] = (long long)d.sum_abs_mm; out[1] = d.n_valid; out[2] = d.n_template; out[3] = (long long)n.sum_angle_urad; out[4] = n.n_normal;
+}
+
 struct DD { long long sum_abs_mm; int n_valid, n_template; };
 struct ND { long long sum_angle_urad; int n_normal, reserved; };
 extern "C" double nv_host_value(long long sum_abs_mm, int n_valid, long long sum_angle_urad, int n_normal, double no_value) {
@@ -53,6 +62,17 @@ struct Image {
   void normals(const nv::Params& p) {
     for (int y = 0; y < h; ++y)
       for (int x = 0; x < w; ++x) n[(size_t)y * w + x] = nv::normal_at(d.data(), w, h, (size_t)w, x, y, p);
+  }
+};
+
+// An image as the device stores a crop: rows padded with zeros to the pitch, exactly h * pitch elements of each kind.
+struct Padded {
+  int pitch;
+  std::vector<uint16_t> d;
+  std::vector<uint64_t> n;
+  explicit Padded(const Image& im) : pitch(dv::crop_pitch(im.w)), d((size_t)im.h * pitch, 0), n((size_t)im.h * pitch, 0) {
+    for (int y = 0; y < im.h; ++y)
+      for (int x = 0; x < im.w; ++x) { d[(size_t)y * pitch + x] = im.d[(size_t)y * im.w + x]; n[(size_t)y * pitch + x] = im.n[(size_t)y * im.w + x]; }
   }
 };
 
@@ -80,9 +100,10 @@ int main() {
       return fail("plane normal");
   }
   // images of every size the scene test uses, random surfaces with holes, far pixels and the extremes of uint16: the map, then the image
-  // laid over itself everywhere around and across its borders
+  // laid over itself everywhere around and across its borders, pixel by pixel and as the kernel walks it (whole vectors over padded rows;
+  // 505 and 513 lie on both sides of the 64 vectors a wave's lanes cover in one trip)
   int placements = 0, counted = 0;
-  const int widths[] = {1, 5, 6, 11, 12, 64, 65, 70}, heights[] = {1, 6, 11, 13, 37};
+  const int widths[] = {1, 5, 6, 11, 12, 64, 65, 70, 505, 513}, heights[] = {1, 6, 11, 13, 37};
   for (int w : widths)
     for (int h : heights) {
       Image im(w, h), other(w, h);
@@ -93,6 +114,7 @@ int main() {
       }
       im.normals(p);
       other.normals(p);
+      const Padded padded(im);
       const int xs[] = {0, 1, -1, -w / 2 - 1, w - 1, w, -w, INT_MAX, INT_MIN, INT_MAX - w};
       const int ys[] = {0, 1, -1, h - 1, h, -h, INT_MAX, INT_MIN, INT_MAX - h};
       for (int x : xs)
@@ -103,6 +125,12 @@ int main() {
           d0 = dv::diff_match(im.d.data(), w, h, w, other.d.data(), w, h, (size_t)w, x, y);
           if (d.sum_abs_mm != d0.sum_abs_mm || d.n_valid != d0.n_valid || d.n_template != d0.n_template) return fail("depth half differs from dv::diff_match");
           if (n.n_normal > d.n_valid) return fail("n_normal > n_valid");
+          dv::Sums dvec;
+          nv::Sums nvec;
+          nv::diff_match_vectors(padded.d.data(), padded.n.data(), h, padded.pitch, other.d.data(), other.n.data(), w, h, (size_t)w, x, y, table.data(), &dvec, &nvec);
+          if (dvec.sum_abs_mm != d.sum_abs_mm || dvec.n_valid != d.n_valid || dvec.n_template != d.n_template || nvec.sum_angle_urad != n.sum_angle_urad ||
+              nvec.n_normal != n.n_normal)
+            return fail("the vector walk differs from nv::diff_match");
           placements += 1;
           counted += n.n_normal > 0;
         }

@@ -88,6 +88,28 @@ def constructed():
     return crops, scene, matches, expected
 
 
+# Crops wider than the 64 vectors (512 pixels) a wave's lanes cover in one trip along a row: 505 has pitch 512, the last single-trip width;
+# 513 has 65 vectors, so lane 0 alone takes a second trip; 1100 has 138, two trips for most lanes and three for the first ten.
+WIDE_W, WIDE_H = 1200, 12
+WIDE_SIZES = ((505, 1), (505, 5), (513, 1), (513, 5), (1100, 5))
+
+
+def wide_positions(w, h, W=WIDE_W, H=WIDE_H):
+    """Inside at an even and at an odd x, cut by the left and by the right border, y = -2, y = H - 3, entirely outside, x = INT32_MAX - w."""
+    return [(40, 2), (41, 2), (-(w // 2) - 1, 2), (W - (w + 1) // 2, 2), (40, -2), (40, H - 3), (W, 2), (INT32_MAX - w, 2)]
+
+
+@functools.lru_cache(maxsize=None)
+def wide():
+    """-> (crops, scene uint16 [12, 1200], rows int64 [n, 3] (x, y, crop), expected int64 [n, 3]) for the wide crops.  Read-only."""
+    rng = np.random.default_rng(20240619)
+    crops = [_values(rng, (h, w), 0.3) for w, h in WIDE_SIZES]
+    scene = _values(rng, (WIDE_H, WIDE_W), 0.2)
+    rows = np.asarray([(x, y, k) for k, c in enumerate(crops) for (x, y) in wide_positions(c.shape[1], c.shape[0])], np.int64)
+    expected = np.asarray([np_diff(crops[k], scene, x, y) for x, y, k in rows], np.int64)
+    return crops, scene, rows, expected
+
+
 def match_records(dtype, rows, class_index=0):
     """(x, y, crop) rows -> match records of `dtype` (MATCH_DTYPE)."""
     m = np.zeros(len(rows), dtype)

@@ -70,6 +70,18 @@ def test_sum_does_not_wrap_at_2_to_32():
     t.close()
 
 
+def test_rows_wider_than_one_trip_of_a_wave():
+    """Crops of 64, 65 and 138 vectors a row (dvc.WIDE_SIZES): the lanes of a wave take a row's vectors 64 at a time, so 513 pixels are the
+    first width at which a lane takes a second trip along its row, and at 1100 some take three."""
+    crops, scene, rows, expected = dvc.wide()
+    assert [c.shape[::-1] for c in crops] == list(dvc.WIDE_SIZES) and scene.shape == (12, 1200) and len(rows) == 8 * len(crops)
+    assert 2 * (expected[:, 1] > 0).sum() >= len(rows)                   # at least half the placements have something to compare
+    assert (rows[:, 0] == dvc.INT32_MAX - 1100).any() and (rows[:, 0] < 0).any() and (rows[:, 0] & 1).any()
+    t = DepthTemplates.from_crops(crops)
+    assert_rows(as_rows(t.diff(scene, dvc.match_records(MATCH_DTYPE, rows))), expected, rows)
+    t.close()
+
+
 def test_batch_offsets_strided_frames_and_class_filter(constructed):
     t, crops, _, _, _ = constructed
     rng = np.random.default_rng(77)

@@ -190,6 +190,27 @@ def test_holes_in_the_scene_and_in_the_crop(constructed):
     assert d_rows(dd)[0].tolist() + n_rows(nd)[0].tolist() == list(want) and 0 < want[4] < want[1] < want[2] < crop.size
 
 
+def test_rows_wider_than_one_trip_of_a_wave():
+    """Crops of 64, 65 and 138 vectors a row (dvc.WIDE_SIZES): up to one, two and three trips of a wave's 64 lanes along a row, with the
+    crop's normals read next to its depths on every trip.  nvc.wide() says where crops this flat get their normals from."""
+    crops, crop_normals, scene, scene_normals, rows = nvc.wide()
+    table = normal_angle_table()
+    want = np.asarray([nvc.np_normal_diff(crops[k], crop_normals[k], scene, scene_normals, x, y, table) for x, y, k in rows], np.int64)
+    assert [c.shape[::-1] for c in crops] == list(dvc.WIDE_SIZES) and scene.shape == (12, 1200) and len(rows) == 8 * len(crops)
+    assert 2 * (want[:, 1] > 0).sum() >= len(rows) and 2 * (want[:, 4] > 0).sum() >= len(rows)     # half the placements count in each term
+    t = DepthTemplates.from_crops(crops)
+    t.enable_normals(nvc.FX, nvc.FY)
+    for k, n in enumerate(crop_normals):
+        assert np.array_equal(t.normals(k), n), k
+    m = dvc.match_records(MATCH_DTYPE, rows)
+    dd, nd = t.normal_diff(scene, m)
+    got = np.concatenate([d_rows(dd), n_rows(nd)], 1)
+    bad = np.nonzero((got != want).any(1))[0]
+    assert len(bad) == 0, [(rows[i].tolist(), got[i].tolist(), want[i].tolist()) for i in bad[:5]]
+    assert dd.tobytes() == t.diff(scene, m).tobytes()
+    t.close()
+
+
 # ---- 4. no 32-bit wrap ---------------------------------------------------------------------------------------------------------------------------------
 
 def test_angle_sum_does_not_wrap_at_2_to_32():

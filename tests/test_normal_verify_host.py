@@ -32,6 +32,17 @@ def host_diff(lib, crop, crop_n, scene, scene_n, x, y, table):
     return out
 
 
+def host_diff_vectors(lib, crop, crop_n, scene, scene_n, x, y, table):
+    """The same match the way the kernel walks it: whole vectors over rows padded with zeros to the pitch, depths and normals alike."""
+    out = np.zeros(5, np.int64)
+    h, w = crop.shape
+    pitch = (w + 7) // 8 * 8
+    crop_p, crop_np = nvc.padded(crop, pitch), nvc.padded(crop_n, pitch)
+    lib.nv_host_diff_vectors(crop_p.ctypes.data, crop_np.ctypes.data, h, pitch, scene.ctypes.data, scene_n.ctypes.data, scene.shape[1], scene.shape[0],
+                             scene.shape[1], int(x), int(y), table.ctypes.data, out.ctypes.data)
+    return out
+
+
 def test_table():
     t = normal_angle_table()
     assert t.shape == (16385,) and t[0] == 0 and t[8192] == 1047198 and t[16384] == 3141593
@@ -115,6 +126,10 @@ def _pairs():
     out = [(by["plane with holes"], by["noise around the difference threshold"]), (by["noise around the difference threshold"], by["plane with holes"]),
            (by["steps across both thresholds"], by["plane a=3 b=-2"]), (by["any values"], by["any values"]), (by["scene 12x13"], by["scene 70x37"]),
            (by["scene 65x11"], by["scene 64x37"]), (by["plane a=9 b=0"], by["plane a=0 b=-9"])]
+    # rows of 64, 65 and 138 vectors: up to one, two and three trips of a wave's 64 lanes along a row
+    crops, _, scene, _, _ = nvc.wide()
+    assert sorted(c.shape[::-1] for c in crops) == [(505, 1), (505, 5), (513, 1), (513, 5), (1100, 5)]
+    out += [(c, scene) for c in crops] + [(crops[-1][2:3], scene)]                   # and 1100 x 1
     return out
 
 
@@ -135,6 +150,7 @@ def test_match_sums_and_value_equal_the_restatement(nv):
             got = host_diff(nv, crop, cn, scene, sn, x, y, table).tolist()
             want = list(nvc.np_normal_diff(crop, cn, scene, sn, x, y, table))
             assert got == want, (crop.shape, scene.shape, x, y)
+            assert host_diff_vectors(nv, crop, cn, scene, sn, x, y, table).tolist() == want, (crop.shape, scene.shape, x, y)
             for no_value in (-np.inf, -7.5):
                 v = nv.nv_host_value(got[0], got[1], got[3], got[4], no_value)
                 assert v == nvc.np_value(got[0], got[1], got[3], got[4], no_value)
