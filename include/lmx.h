@@ -467,6 +467,37 @@ lmx_status lmx_cluster_matches_scored(const lmx_match_t* matches, size_t n_match
                                       const int32_t* rects, size_t n_templates, const lmx_cluster_params* params, lmx_cluster_t* clusters,
                                       size_t cap_clusters, size_t* n_clusters, int32_t* members, size_t cap_members);
 
+/* ---- the chain for a bank of several classes --------------------------------------------------------------------------------------------
+ * The reference runs one detector per object, each with its own `<object>_renderer_params.yml`
+ * (src/linemod_ensenso_detect_3_mult_detect_service.cpp defines two such nodes).  With one bank of several classes the match list of a frame
+ * holds every object's matches, and the chain above knows no classes: it would vote both objects into one bin, look template ids up in one
+ * side-car and let the NMS suppress one object behind another.  lmx_cluster_matches_classes is the per-class composition:
+ *   for each class c in ascending order with a side-car (classes[c].n_templates > 0):
+ *     M_c = the matches with class_index == c, in the list's order;
+ *     lmx_cluster_matches (match_values NULL) or lmx_cluster_matches_scored (on match_values of M_c) with classes[c];
+ *     every member index mapped back to the match's position in `matches`;
+ *   clusters = class 0's clusters in the chain's own order (score descending, NMS survivors only), then class 1's, ...;
+ *   cluster_class[k] names cluster k's class.  The NMS never crosses classes.
+ * Matches of a class without a side-car (n_templates == 0, or class_index >= n_classes) stay in `matches` and belong to no cluster; a
+ * negative class_index is refused.  Every side-car's parameters are validated as by lmx_cluster_matches, also for a class without a match;
+ * an error names the class.  LMX_ERR_OVERFLOW reports the full counts.
+ * What this is NOT: the output of two single-class detectors.  Detector::match runs ONE std::sort + std::unique over all classes, here as
+ * in cv::linemod, and std::unique removes only ADJACENT duplicates of (x, y, similarity, class): the other class's records sort in between
+ * a class's duplicates, so which template of a duplicate survives, and whether both do, can differ from what a detector of object c alone
+ * keeps.  Per class the set of (x, y, similarity) is the same; template ids, the number of matches, and hence the clusters' member
+ * counts, scores and NMS survivors can differ.  Measured on two mesh-trained objects (profiles/two_object_chain.txt): the per-class
+ * match lists equal the single-class detector's in 8 of 64 frames at threshold 85 and in none at threshold 80, the cluster lists in 48
+ * and in none.  The composition above -- this function against lmx_cluster_matches per class on the SAME list -- is what holds exactly. */
+typedef struct lmx_class_sidecar {
+  const double* obj_origin_dists;   /* [n_templates] */
+  const int32_t* rects;             /* [n_templates][4] */
+  size_t n_templates;               /* 0: the class has no side-car */
+  lmx_cluster_params params;
+} lmx_class_sidecar;
+lmx_status lmx_cluster_matches_classes(const lmx_match_t* matches, size_t n_matches, const double* match_values /* NULL: similarities */,
+                                       const lmx_class_sidecar* classes, int32_t n_classes, lmx_cluster_t* clusters, int32_t* cluster_class,
+                                       size_t cap_clusters, size_t* n_clusters, int32_t* members, size_t cap_members);
+
 /* The renderer-params side-car that the consumer chain reads next to the matches: `<object>_renderer_params.yml`, written by the
  * reference's trainers (writeLinemodTemplateParams, src/renderer.cpp:72-130) and read by readLinemodTemplateParams
  * (src/rgbdDetector.cpp:1681-1749): per template "Template <i>": {R 3x3, T 3x1, K 3x3, D, Ori_dist, Rect}, then the renderer_* scalars.
@@ -664,6 +695,48 @@ lmx_status lmx_ctx_collect_clusters_depth_normal(lmx_ctx* ctx, int32_t n_frames,
                                                  lmx_depth_diff_t* diffs /* parallel to matches; may be NULL */,
                                                  lmx_normal_diff_t* ndiffs /* parallel to matches; may be NULL */,
                                                  lmx_cluster_t* clusters, size_t cap_clusters, size_t* cluster_offsets, int32_t* members, size_t cap_members);
+/* ---- the device chain for a bank of several classes ------------------------------------------------------------------------------------
+ * lmx_cluster_matches_classes on the device, from the raw-match slot: one enqueue quantises the frame once for every object of the bank,
+ * and the consumer chain votes, filters, scores and suppresses per class.  Stages A - D of k_f2_finalize_cluster (insertion order,
+ * std::sort, std::unique: they run over all classes and compare the class already) are shared; the CLASSES forms then pack the class on
+ * top of the vote key (class 4 bits | y / step 16 | x / step 16 | ring 17 | list position 11), take step, ring constants, size threshold
+ * and side-car from a table of 16 classes, and run the emulated std::sort by score and the greedy NMS on one class's clusters at a time.
+ *   lmx_ctx_set_cluster_sidecar_class : class class_index's side-car, validated as by lmx_ctx_set_cluster_sidecar; n_templates == 0 removes
+ *     it.  class_index 0 .. 15; beyond that LMX_ERR_INVALID_ARG (lmx_cluster_matches_classes on the host takes any number of classes).
+ *     State of its own: the un-classed side-car and its three collect calls are not touched and behave as before.
+ *   lmx_ctx_collect_clusters_classes  : lmx_ctx_collect_clusters for the oldest outstanding enqueue (same outputs, same locking) plus
+ *     cluster_class[k], the class of clusters[k]; a frame's clusters are class 0's, then class 1's, ...  Matches of a class without a
+ *     side-car are listed and belong to no cluster.  score == NULL ranks by mean similarity.  With a score, `templates` holds the crops of
+ *     all classes, class c's as templates class_base[c] .. class_base[c + 1] (lmx_depth_templates_append joins per-class objects), its
+ *     upload_scene was called after the enqueue, and a cluster's score is the mean of lmx_depth_value (normals == 0; ndiffs is not
+ *     written) or lmx_match_value (normals != 0, after enable_normals) over its members.  A match whose template_id is outside its
+ *     class's range, or whose class is >= n_classes, gets zero diffs and is never compared with another class's crop.
+ *     Equal, bit for bit, to lmx_ctx_collect + per class (lmx_depth_diff_matches / lmx_normal_diff_matches on a per-class object at
+ *     class_index = c) + lmx_cluster_matches_classes.  Frames of more than 2048 records, with a template_id outside its class's side-car
+ *     or a depth ring outside +-2^16 are finished on the host inside the call.
+ *     LMX_ERR_INVALID_ARG, the enqueue staying outstanding: no class side-car set; n_classes outside 1 .. 16; class_base[0] != 0;
+ *     class_base[n_classes] != lmx_depth_templates_count; a class's range != its side-car's n_templates (0 without one); and every
+ *     condition of lmx_ctx_collect_clusters_depth / _depth_normal on the scene and the normals. */
+typedef struct lmx_class_score {
+  lmx_depth_templates* templates;
+  const int32_t* class_base;   /* [n_classes + 1] */
+  int32_t n_classes;
+  int32_t normals;             /* 0: the depth term alone */
+  double no_value;
+} lmx_class_score;
+lmx_status lmx_ctx_set_cluster_sidecar_class(lmx_ctx* ctx, int32_t class_index, const double* obj_origin_dists, const int32_t* rects, size_t n_templates,
+                                             const lmx_cluster_params* params);
+lmx_status lmx_ctx_collect_clusters_classes(lmx_ctx* ctx, int32_t n_frames, const lmx_class_score* score /* NULL: mean similarity */,
+                                            lmx_match_t* matches, size_t cap_matches, size_t* match_offsets,
+                                            lmx_depth_diff_t* diffs /* parallel to matches; may be NULL */,
+                                            lmx_normal_diff_t* ndiffs /* parallel to matches; may be NULL */,
+                                            lmx_cluster_t* clusters, int32_t* cluster_class, size_t cap_clusters, size_t* cluster_offsets,
+                                            int32_t* members, size_t cap_members);
+/* Moves src's templates (crops, table entries, rects) behind dst's: src's template i becomes dst's template count(dst) + i, src is left
+ * empty and valid.  Both must live on the same device; both mutexes are taken, in address order.  Nothing is copied on the device.  dst's
+ * device table is uploaded again on next use, its crop normals are recomputed on next need if normals are enabled, and a scene uploaded
+ * to dst is forgotten: lmx_depth_templates_upload_scene comes before the next scored call. */
+lmx_status lmx_depth_templates_append(lmx_depth_templates* dst, lmx_depth_templates* src);
 /* Device time of the object's kernels that run per call: with profiling on, a pair of events surrounds each launch; kernel_time waits for
  * the launches in flight and returns the sum of their times and their number since profiling was switched on.  Off (the default) no
  * event is created or recorded. */
@@ -728,6 +801,17 @@ lmx_status lmx_debug_device_finalize_cluster_depth(int32_t device, const lmx_raw
                                                    const double* obj_origin_dists, const int32_t* rects, size_t n_templates,
                                                    const lmx_cluster_params* params, lmx_match_t* matches, lmx_depth_diff_t* diffs,
                                                    lmx_cluster_t* clusters, int32_t* members, uint32_t* counts);
+/* The same hook for the CLASSES forms (lmx_ctx_collect_clusters_classes): `classes` as lmx_cluster_matches_classes takes them, n_classes
+ * 1 .. 16, each validated as by lmx_ctx_set_cluster_sidecar_class.  score == NULL: k_f2_finalize_cluster_classes.  With a score: depth
+ * [n_frames] becomes score->templates' uploaded scene, then the classed record kernel and the scored (normals == 0) or normal-scored
+ * classed chain; class_base is validated against the object's count only, so that a test can give a class a shorter range than its
+ * side-car.  cluster_class [n_frames][2048] comes back next to clusters, diffs and ndiffs [n_frames][2048] next to matches (required with
+ * a score / with normals).  Status 2: a template_id outside its class's side-car or a depth ring outside +-2^16.  No host completion. */
+lmx_status lmx_debug_device_finalize_cluster_classes(int32_t device, const lmx_raw_match_t* records, size_t n_records, int32_t n_frames,
+                                                     const lmx_class_sidecar* classes, int32_t n_classes, const lmx_class_score* score,
+                                                     const lmx_image* depth, lmx_match_t* matches, lmx_depth_diff_t* diffs,
+                                                     lmx_normal_diff_t* ndiffs, lmx_cluster_t* clusters, int32_t* cluster_class, int32_t* members,
+                                                     uint32_t* counts);
 /* Test hook, no device needed: one of the tables a context of width x height frames, max_batch frames per batch and shard
  * shard_rank of shard_world (1: the whole bank) would put on the device for `bank` -- the bytes DeviceBankView's pointers see
  * (csrc/lmx_bank_tables.hpp defines every format); ls_flat != 0 as under LMX_LS_FLAT.  LMX_TAB_SUMMARY is uint32 words:

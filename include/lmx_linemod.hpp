@@ -12,8 +12,10 @@
 // With LMX_HAVE_OPENCV defined, overloads taking cv::Mat are provided (the only place OpenCV types appear).
 #pragma once
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <map>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -69,6 +71,21 @@ struct Image {
   int rows, cols, channels, elem_size;
   size_t step;
   lmx_image c() const { return lmx_image{data, rows, cols, channels, elem_size, step}; }
+};
+
+class DepthTemplates;
+
+// What Detector::collectClustersClasses returns: frame f's matches are matches[match_offsets[f] .. match_offsets[f + 1]) (diffs / ndiffs
+// parallel to them, empty without a score / without normals), its clusters clusters[cluster_offsets[f] .. cluster_offsets[f + 1]) with
+// cluster_class[k] the class of clusters[k]; a cluster's members are members[member_begin .. member_begin + member_count), indices into
+// its frame's matches.
+struct ClassClusters {
+  std::vector<lmx_match_t> matches;
+  std::vector<lmx_depth_diff_t> diffs;
+  std::vector<lmx_normal_diff_t> ndiffs;
+  std::vector<lmx_cluster_t> clusters;
+  std::vector<int32_t> cluster_class, members;
+  std::vector<size_t> match_offsets, cluster_offsets;
 };
 
 class Detector {
@@ -192,10 +209,33 @@ class Detector {
   }
 #endif
 
+  // The two-detector node as one bank of two classes.  Class class_index's `<object>_renderer_params.yml`
+  // side-car and clustering parameters for the per-class consumer chain (lmx_ctx_set_cluster_sidecar_class); class_index is the position
+  // of the class in classIds(), 0 .. 15; empty vectors remove it.  Kept with the detector and handed to its context whenever one is made.
+  void setClusterSidecar(int class_index, const std::vector<double>& obj_origin_dists, const std::vector<int32_t>& rects, const lmx_cluster_params& params) {
+    if (rects.size() != obj_origin_dists.size() * 4) throw Exception(LMX_ERR_SHAPE, "setClusterSidecar: four rect values per origin distance");
+    if (class_index < 0 || class_index >= 16) throw Exception(LMX_ERR_INVALID_ARG, "setClusterSidecar: class_index must be 0 .. 15 (lmx_cluster_matches_classes on the host takes any number)");
+    if (slot_[0]) check(lmx_ctx_set_cluster_sidecar_class(slot_[0], class_index, obj_origin_dists.data(), rects.data(), obj_origin_dists.size(), &params));
+    sidecars_[class_index] = ClassSidecar{obj_origin_dists, rects, params};
+  }
+  // One batch of BGR (+ depth) frames through match and the per-class chain in one enqueue and one collect
+  // (lmx_ctx_collect_clusters_classes): frames[f] holds frame f's sources; setDevice's max_batch must cover frames.size().  templates
+  // null: clusters ranked by mean similarity.  Else the object holds every class's crops, class c's at class_base[c] .. class_base[c + 1]
+  // (DepthTemplates::append), depth[f] is frame f's 16-bit depth image and the score is the depth difference, with normals the normal term
+  // too.  Per class the result is lmx_cluster_matches on that class's matches of the joined list; it is not bit for bit what two
+  // single-class detectors give (include/lmx.h, "What this is NOT").  The call collects the context's OLDEST outstanding enqueue and, when
+  // the collect is refused, releases the oldest one: use it on a context that has nothing outstanding (one driven through context() and
+  // the C API with an enqueue of its own in flight would get, or lose, that one).  Defined behind DepthTemplates.
+  ClassClusters collectClustersClasses(const std::vector<std::vector<Image> >& frames, float threshold, DepthTemplates* templates = nullptr,
+                                       const std::vector<int32_t>& class_base = std::vector<int32_t>(), const std::vector<Image>& depth = std::vector<Image>(),
+                                       bool normals = false, double no_value = -HUGE_VAL, size_t capacity = 1 << 16);
+
   lmx_bank* bank() const { return bank_; }
   lmx_ctx* context() const { return ctx_; }
 
  private:
+  struct ClassSidecar { std::vector<double> dists; std::vector<int32_t> rects; lmx_cluster_params params; };
+  std::map<int, ClassSidecar> sidecars_;
   void reset() {
     for (int k = 0; k < 2; ++k)
       if (slot_[k]) lmx_ctx_destroy(slot_[k]);
@@ -213,6 +253,9 @@ class Detector {
       d.flags = gray ? LMX_CTX_GRAY : 0;
       check(lmx_ctx_create(bank_, &d, &c));
       w_[gray] = w; h_[gray] = h;
+      if (!gray)
+        for (const std::pair<const int, ClassSidecar>& k : sidecars_)
+          check(lmx_ctx_set_cluster_sidecar_class(c, k.first, k.second.dists.data(), k.second.rects.data(), k.second.dists.size(), &k.second.params));
     }
     ctx_ = c;
   }
@@ -315,6 +358,14 @@ class DepthTemplates {
     check(lmx_depth_templates_upload_scene(h_, imgs.data(), (int32_t)imgs.size()));
   }
 
+  // Moves other's templates behind this object's (lmx_depth_templates_append): other's template i becomes template count() + i, other is
+  // left empty.  The classes' objects joined in class order are what Detector::collectClustersClasses scores against.  An object that
+  // holds nothing yet becomes an empty one first.
+  void append(DepthTemplates& other, int device = 0) {
+    if (!h_) check(lmx_depth_templates_from_crops(device, nullptr, nullptr, 0, &h_));
+    check(lmx_depth_templates_append(h_, other.h_));
+  }
+
   lmx_depth_templates* handle() const { return h_; }
 
  private:
@@ -324,6 +375,51 @@ class DepthTemplates {
   }
   lmx_depth_templates* h_ = nullptr;
 };
+
+inline ClassClusters Detector::collectClustersClasses(const std::vector<std::vector<Image> >& frames, float threshold, DepthTemplates* templates,
+                                                      const std::vector<int32_t>& class_base, const std::vector<Image>& depth, bool normals, double no_value,
+                                                      size_t capacity) {
+  if (frames.empty() || frames[0].empty()) throw Exception(LMX_ERR_SHAPE, "collectClustersClasses: no frames");
+  if (templates && (class_base.size() < 2 || depth.size() != frames.size())) throw Exception(LMX_ERR_SHAPE, "collectClustersClasses: class_base needs one entry per class plus one, depth one image per frame");
+  const int n = (int)frames.size();
+  std::vector<lmx_image> imgs;
+  for (const std::vector<Image>& f : frames) {
+    if (f.size() != frames[0].size()) throw Exception(LMX_ERR_SHAPE, "collectClustersClasses: every frame needs the same sources");
+    for (const Image& s : f) imgs.push_back(s.c());
+  }
+  ensure_ctx(frames[0][0].cols, frames[0][0].rows, false);
+  check(lmx_ctx_upload(ctx_, n, imgs.data(), (int32_t)frames[0].size()));
+  check(lmx_ctx_enqueue(ctx_, n, threshold, nullptr, 0));
+  ClassClusters out;
+  out.matches.resize(capacity); out.clusters.resize(capacity); out.cluster_class.resize(capacity); out.members.resize(capacity);
+  out.match_offsets.assign((size_t)n + 1, 0); out.cluster_offsets.assign((size_t)n + 1, 0);
+  lmx_class_score score;
+  lmx_status st = LMX_OK;
+  try {
+    if (templates) {
+      templates->uploadScene(depth);   // returns at once: the transfer overlaps the match kernels
+      out.diffs.resize(capacity);
+      if (normals) out.ndiffs.resize(capacity);
+      score.templates = templates->handle(); score.class_base = class_base.data(); score.n_classes = (int32_t)class_base.size() - 1;
+      score.normals = normals ? 1 : 0; score.no_value = no_value;
+    }
+    st = lmx_ctx_collect_clusters_classes(ctx_, n, templates ? &score : nullptr, out.matches.data(), capacity, out.match_offsets.data(),
+                                          templates ? out.diffs.data() : nullptr, normals ? out.ndiffs.data() : nullptr, out.clusters.data(),
+                                          out.cluster_class.data(), capacity, out.cluster_offsets.data(), out.members.data(), capacity);
+    check(st);
+  } catch (...) {
+    // a refusal leaves the enqueue outstanding (an overflow has consumed it): drop it, so that the next call collects its own
+    if (st != LMX_ERR_OVERFLOW) (void)lmx_ctx_release(ctx_);
+    throw;
+  }
+  const size_t nm = out.match_offsets[(size_t)n], nc = out.cluster_offsets[(size_t)n];
+  size_t nmem = 0;
+  for (size_t k = 0; k < nc; ++k) nmem = std::max(nmem, (size_t)out.clusters[k].member_begin + (size_t)out.clusters[k].member_count);
+  out.matches.resize(nm); out.clusters.resize(nc); out.cluster_class.resize(nc); out.members.resize(nmem);
+  if (templates) out.diffs.resize(nm);
+  if (normals) out.ndiffs.resize(nm);
+  return out;
+}
 
 // The reference's readLinemod (src/rgbdDetector.cpp:1668-1680) with the same shape.
 inline std::shared_ptr<Detector> readLinemod(const std::string& filename) {

@@ -9,3 +9,4 @@ from .bank import TemplateBank  # noqa: F401
 from .detector import Detector, NativeBank, PinnedArena, linemod_detection, merge_raw, render_views, MATCH_DTYPE, RAW_MATCH_DTYPE  # noqa: F401
 from .detector import DepthTemplates, DEPTH_DIFF_DTYPE, cluster_matches_scored, depth_values  # noqa: F401
 from .detector import NORMAL_DIFF_DTYPE, normal_values, normal_angle_table  # noqa: F401
+from .detector import cluster_matches_classes  # noqa: F401

@@ -26,6 +26,8 @@ SYMBOLS = [
     "lmx_depth_value", "lmx_depth_templates_upload_scene", "lmx_ctx_collect_clusters_depth", "lmx_debug_device_finalize_cluster_depth",
     "lmx_normal_angle_table", "lmx_depth_templates_enable_normals", "lmx_depth_templates_get_normals", "lmx_normal_diff_matches", "lmx_match_value",
     "lmx_ctx_collect_clusters_depth_normal", "lmx_debug_scene_normals", "lmx_depth_templates_set_profiling", "lmx_depth_templates_kernel_time",
+    "lmx_cluster_matches_classes", "lmx_ctx_set_cluster_sidecar_class", "lmx_ctx_collect_clusters_classes", "lmx_depth_templates_append",
+    "lmx_debug_device_finalize_cluster_classes",
 ]
 
 (LMX_OK, LMX_ERR_INVALID_ARG, LMX_ERR_SHAPE, LMX_ERR_NO_DEVICE, LMX_ERR_HIP, LMX_ERR_OVERFLOW, LMX_ERR_IO,
@@ -65,6 +67,14 @@ class PreDesc(C.Structure):
 class ClusterParams(C.Structure):
     _fields_ = [("vote_row_col_step", C.c_int32), ("renderer_radius_min", C.c_double), ("renderer_radius_step", C.c_double),
                 ("cluster_size_thresh", C.c_int32)]
+
+
+class ClassSidecar(C.Structure):   # lmx_class_sidecar
+    _fields_ = [("obj_origin_dists", C.c_void_p), ("rects", C.c_void_p), ("n_templates", C.c_size_t), ("params", ClusterParams)]
+
+
+class ClassScore(C.Structure):     # lmx_class_score
+    _fields_ = [("templates", C.c_void_p), ("class_base", C.c_void_p), ("n_classes", C.c_int32), ("normals", C.c_int32), ("no_value", C.c_double)]
 
 
 class RendererParams(C.Structure):
@@ -283,6 +293,13 @@ def lib():
     L.lmx_depth_templates_kernel_time.argtypes = [vp, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     L.lmx_ctx_set_cluster_sidecar.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(ClusterParams)]
     L.lmx_ctx_collect_clusters.argtypes = [vp, C.c_int32, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t), vp, C.c_size_t]
+    L.lmx_cluster_matches_classes.argtypes = [vp, C.c_size_t, vp, C.POINTER(ClassSidecar), C.c_int32, vp, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, C.c_size_t]
+    L.lmx_ctx_set_cluster_sidecar_class.argtypes = [vp, C.c_int32, vp, vp, C.c_size_t, C.POINTER(ClusterParams)]
+    L.lmx_ctx_collect_clusters_classes.argtypes = [vp, C.c_int32, C.POINTER(ClassScore), vp, C.c_size_t, C.POINTER(C.c_size_t), vp, vp, vp, vp, C.c_size_t,
+                                                   C.POINTER(C.c_size_t), vp, C.c_size_t]
+    L.lmx_depth_templates_append.argtypes = [vp, vp]
+    L.lmx_debug_device_finalize_cluster_classes.argtypes = [C.c_int32, vp, C.c_size_t, C.c_int32, C.POINTER(ClassSidecar), C.c_int32, C.POINTER(ClassScore),
+                                                            C.POINTER(Image), vp, vp, vp, vp, vp, vp, vp]
     L.lmx_ctx_debug_read.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_size_t]
     L.lmx_debug_orientation_labels.argtypes = [C.c_int32, vp, vp, C.c_size_t, vp]
     L.lmx_debug_depth_normal_bins.argtypes = [C.c_int32, vp, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, vp, vp]

@@ -169,3 +169,65 @@ extern "C" lmx_status lmx_cluster_matches_scored(const lmx_match_t* matches, siz
                          n_clusters, members, cap_members);
   });
 }
+
+// The per-class composition (include/lmx.h): for every class with a side-car, in ascending order, cluster_chain on that class's matches
+// (in the list's order) with that class's side-car; members mapped back to positions in the whole list; the classes' clusters joined.
+extern "C" lmx_status lmx_cluster_matches_classes(const lmx_match_t* matches, size_t n_matches, const double* match_values, const lmx_class_sidecar* classes,
+                                                  int32_t n_classes, lmx_cluster_t* clusters, int32_t* cluster_class, size_t cap_clusters, size_t* n_clusters,
+                                                  int32_t* members, size_t cap_members) {
+  return lmx::guarded("lmx_cluster_matches_classes", [&]() -> lmx_status {
+    const char* const what = "lmx_cluster_matches_classes";
+    if ((n_matches && !matches) || n_classes < 0 || (n_classes && !classes) || !n_clusters || (cap_clusters && (!clusters || !cluster_class)) ||
+        (cap_members && !members)) {
+      lmx::set_error("%s: null argument", what);
+      return LMX_ERR_INVALID_ARG;
+    }
+    *n_clusters = 0;
+    std::vector<std::vector<int32_t>> of_class((size_t)n_classes);   // positions in `matches`, in its order
+    for (size_t i = 0; i < n_matches; ++i) {
+      const int32_t c = matches[i].class_index;
+      if (c < 0) { lmx::set_error("%s: match %zu: class_index %d is negative", what, i, c); return LMX_ERR_INVALID_ARG; }
+      if (c < n_classes && classes[c].n_templates > 0) of_class[(size_t)c].push_back((int32_t)i);   // else: listed, in no cluster
+    }
+    size_t nc = 0, nm = 0;
+    lmx_status st = LMX_OK;
+    std::vector<lmx_match_t> cm;
+    std::vector<double> cv;
+    std::vector<lmx_cluster_t> cc;
+    std::vector<int32_t> cmem;
+    for (int32_t c = 0; c < n_classes; ++c) {
+      const lmx_class_sidecar& s = classes[c];
+      if (s.n_templates == 0) continue;
+      const std::vector<int32_t>& pos = of_class[(size_t)c];
+      const size_t n = pos.size();
+      cm.resize(n); cc.resize(n); cmem.resize(n);   // a class's clusters and members never exceed its matches
+      for (size_t k = 0; k < n; ++k) cm[k] = matches[pos[k]];
+      if (match_values) { cv.resize(n); for (size_t k = 0; k < n; ++k) cv[k] = match_values[pos[k]]; }
+      size_t got = 0;
+      // with no match of the class the chain still validates the class's parameters and side-car
+      const lmx_status cs = cluster_chain(what, cm.data(), n, match_values ? cv.data() : nullptr, s.obj_origin_dists, s.rects, s.n_templates, &s.params,
+                                          cc.data(), n, &got, cmem.data(), n);
+      if (cs != LMX_OK) {
+        const std::string why = lmx_last_error();
+        lmx::set_error("class %d: %s", c, why.c_str());
+        return cs;
+      }
+      for (size_t k = 0; k < got; ++k) {
+        const size_t cnt = (size_t)cc[k].member_count;
+        if (nc < cap_clusters && nm + cnt <= cap_members) {
+          lmx_cluster_t& o = clusters[nc];
+          o = cc[k];
+          o.member_begin = (int32_t)nm;
+          for (size_t j = 0; j < cnt; ++j) members[nm + j] = pos[(size_t)cmem[(size_t)cc[k].member_begin + j]];
+          cluster_class[nc] = c;
+        } else {
+          st = LMX_ERR_OVERFLOW;
+        }
+        nc += 1; nm += cnt;
+      }
+    }
+    *n_clusters = nc;
+    if (st != LMX_OK) lmx::set_error("%zu clusters / %zu members exceed the output capacity", nc, nm);
+    return st;
+  });
+}

@@ -197,6 +197,77 @@ lmx_status lmx_ctx_set_cluster_sidecar(lmx_ctx* c, const double* obj_origin_dist
   return LMX_OK;
 }
 
+// Rewrites the device table of the per-class side-cars from the context's state (the caller has synchronised the lanes and the chain's stream).
+static lmx_status upload_class_table(lmx_ctx* c) {
+  F2Class tab[F2_CLASSES];
+  for (int k = 0; k < F2_CLASSES; ++k) {
+    const lmx_ctx::ClassSidecar& s = c->f2_class[k];
+    tab[k] = F2Class{s.d_dists, s.d_rects, (uint32_t)s.dists.size(), s.params.vote_row_col_step, s.params.cluster_size_thresh, 0,
+                     s.params.renderer_radius_min, s.params.renderer_radius_step};
+  }
+  if (!c->d_f2_class_table) LMX_HIP(hipMalloc((void**)&c->d_f2_class_table, sizeof(tab)));
+  LMX_HIP(hipMemcpy(c->d_f2_class_table, tab, sizeof(tab), hipMemcpyHostToDevice));
+  return LMX_OK;
+}
+
+lmx_status lmx_ctx_set_cluster_sidecar_class(lmx_ctx* c, int32_t class_index, const double* obj_origin_dists, const int32_t* rects, size_t n_templates,
+                                             const lmx_cluster_params* params) {
+  return lmx::guarded("lmx_ctx_set_cluster_sidecar_class", [&]() -> lmx_status {
+  if (!c) { set_error("lmx_ctx_set_cluster_sidecar_class: invalid argument"); return LMX_ERR_INVALID_ARG; }
+  if (class_index < 0 || class_index >= F2_CLASSES) {
+    set_error("lmx_ctx_set_cluster_sidecar_class: class_index %d: the device chain takes classes 0 .. %d; lmx_cluster_matches_classes on the host takes any number",
+              class_index, F2_CLASSES - 1);
+    return LMX_ERR_INVALID_ARG;
+  }
+  if (n_templates != 0) {
+    if (!obj_origin_dists || !rects || !params) { set_error("lmx_ctx_set_cluster_sidecar_class: invalid argument"); return LMX_ERR_INVALID_ARG; }
+    if (params->vote_row_col_step <= 0) { set_error("vote_row_col_step must be positive"); return LMX_ERR_INVALID_ARG; }
+    if (params->cluster_size_thresh < 0) { set_error("cluster_size_thresh must not be negative"); return LMX_ERR_INVALID_ARG; }   // see lmx_ctx_set_cluster_sidecar
+    if (lmx_status vs = check_vote_rings(obj_origin_dists, n_templates, params)) return vs;
+  }
+  lmx_ctx::ClassSidecar& k = c->f2_class[class_index];
+  if (n_templates == 0 && k.dists.empty()) return LMX_OK;   // nothing to remove
+  LMX_HIP(hipSetDevice(c->device));
+  if (sync_lanes(c) != LMX_OK) return LMX_ERR_HIP;   // a kernel may still read the previous side-car
+  if (c->f2_stream) LMX_HIP(hipStreamSynchronize(c->f2_stream));
+  // the new arrays first: a failure leaves the class's side-car, and the device table that points to it, as they were
+  double* d_dists = nullptr;
+  int32_t* d_rects = nullptr;
+  if (n_templates != 0) {
+    auto fill = [&]() -> lmx_status {
+      LMX_HIP(hipMalloc((void**)&d_dists, n_templates * sizeof(double)));
+      LMX_HIP(hipMalloc((void**)&d_rects, n_templates * 4 * sizeof(int32_t)));
+      LMX_HIP(hipMemcpy(d_dists, obj_origin_dists, n_templates * sizeof(double), hipMemcpyHostToDevice));
+      LMX_HIP(hipMemcpy(d_rects, rects, n_templates * 4 * sizeof(int32_t), hipMemcpyHostToDevice));
+      return LMX_OK;
+    };
+    if (lmx_status st = fill()) { (void)hipFree(d_dists); (void)hipFree(d_rects); return st; }
+  }
+  const lmx_ctx::ClassSidecar before = k;
+  k.d_dists = d_dists; k.d_rects = d_rects; k.dists.clear(); k.rects.clear(); k.params = lmx_cluster_params{};
+  if (n_templates != 0) {
+    k.dists.assign(obj_origin_dists, obj_origin_dists + n_templates);
+    k.rects.assign(rects, rects + n_templates * 4);
+    k.params = *params;
+  }
+  if (lmx_status st = upload_class_table(c)) {   // the device table still names the old arrays: keep them
+    (void)hipFree(d_dists); (void)hipFree(d_rects);
+    k = before;
+    return st;
+  }
+  if (before.d_dists) (void)hipFree(before.d_dists);
+  if (before.d_rects) (void)hipFree(before.d_rects);
+  return LMX_OK;
+  });
+}
+
+// What lmx_ctx_collect_clusters_classes adds: the per-class chain instead of the un-classed one; null = the un-classed calls
+struct ClassChain {
+  const int32_t* class_base;   // with a score only: class c's crops are templates class_base[c] .. class_base[c + 1] of the joined object
+  int32_t n_classes;
+  int32_t* cluster_class;      // parallel to the caller's clusters
+};
+
 // What lmx_ctx_collect_clusters_depth and lmx_ctx_collect_clusters_depth_normal add to lmx_ctx_collect_clusters; null = the unscored call
 struct DepthScore {
   lmx_depth_templates* templates;
@@ -220,17 +291,35 @@ static lmx_status grow_rec_diffs(void** d, size_t* cap, size_t n, size_t elem) {
 
 // The body of lmx_ctx_collect_clusters and lmx_ctx_collect_clusters_depth (`what` names the entry point in messages).  With `depth`, the
 // caller holds the templates' mutex.
-static lmx_status collect_clusters_impl(const char* what, lmx_ctx* c, int32_t n_frames, const DepthScore* depth, lmx_match_t* matches, size_t cap_matches,
+static lmx_status collect_clusters_impl(const char* what, lmx_ctx* c, int32_t n_frames, const DepthScore* depth, const ClassChain* cls, lmx_match_t* matches, size_t cap_matches,
                                         size_t* match_offsets, lmx_cluster_t* clusters, size_t cap_clusters, size_t* cluster_offsets, int32_t* members,
                                         size_t cap_members) {
-  if (!c->f2_sidecar) { set_error("%s: call lmx_ctx_set_cluster_sidecar first", what); return LMX_ERR_INVALID_ARG; }
+  if (cls) {
+    bool any = false;
+    for (const lmx_ctx::ClassSidecar& k : c->f2_class) any = any || !k.dists.empty();
+    if (!any) { set_error("%s: call lmx_ctx_set_cluster_sidecar_class first", what); return LMX_ERR_INVALID_ARG; }
+  } else if (!c->f2_sidecar) { set_error("%s: call lmx_ctx_set_cluster_sidecar first", what); return LMX_ERR_INVALID_ARG; }
   if (c->outstanding < 1) { set_error("%s: nothing enqueued", what); return LMX_ERR_INVALID_ARG; }
   const int slot = (c->head + c->n_slots - c->outstanding) % c->n_slots;  // oldest outstanding enqueue
   if (n_frames != c->slot_frames[slot]) { set_error("%s: n_frames=%d but the enqueue had %d", what, n_frames, c->slot_frames[slot]); return LMX_ERR_INVALID_ARG; }
   if (depth) {   // every refusal comes before the enqueue is consumed: it stays outstanding
     const DepthSceneInfo sc = depth_templates_scene(depth->templates);
     if (sc.device != c->device) { set_error("%s: the templates live on device %d, the context on device %d", what, sc.device, c->device); return LMX_ERR_INVALID_ARG; }
-    if ((size_t)sc.count != c->f2_templates) { set_error("%s: %d depth templates but the side-car holds %zu templates", what, sc.count, c->f2_templates); return LMX_ERR_INVALID_ARG; }
+    if (cls) {   // the joined object holds exactly the classes' side-cars, one class after the other
+      const int32_t* cb = cls->class_base;
+      if (!cb || cls->n_classes < 1 || cls->n_classes > F2_CLASSES) { set_error("%s: class_base must hold n_classes + 1 entries, n_classes 1 .. %d", what, F2_CLASSES); return LMX_ERR_INVALID_ARG; }
+      if (cb[0] != 0) { set_error("%s: class_base[0] = %d, not 0", what, cb[0]); return LMX_ERR_INVALID_ARG; }
+      for (int k = 0; k < F2_CLASSES; ++k) {
+        const size_t have = c->f2_class[k].dists.size();
+        if (k >= cls->n_classes) {
+          if (have) { set_error("%s: class %d has a side-car of %zu templates but class_base ends at class %d", what, k, have, cls->n_classes - 1); return LMX_ERR_INVALID_ARG; }
+        } else if (cb[k + 1] < cb[k] || (size_t)(cb[k + 1] - cb[k]) != have) {
+          set_error("%s: class %d: class_base gives it templates %d .. %d but its side-car holds %zu templates", what, k, cb[k], cb[k + 1], have);
+          return LMX_ERR_INVALID_ARG;
+        }
+      }
+      if (cb[cls->n_classes] != sc.count) { set_error("%s: class_base ends at %d but the object holds %d depth templates", what, cb[cls->n_classes], sc.count); return LMX_ERR_INVALID_ARG; }
+    } else if ((size_t)sc.count != c->f2_templates) { set_error("%s: %d depth templates but the side-car holds %zu templates", what, sc.count, c->f2_templates); return LMX_ERR_INVALID_ARG; }
     if (depth->normal && !sc.normals) { set_error("%s: call lmx_depth_templates_enable_normals first", what); return LMX_ERR_INVALID_ARG; }
     if (sc.n_frames < 1) { set_error("%s: no scene uploaded: call lmx_depth_templates_upload_scene first", what); return LMX_ERR_INVALID_ARG; }
     if (sc.n_frames != n_frames) { set_error("%s: the uploaded scene holds %d frames, the enqueue had %d", what, sc.n_frames, n_frames); return LMX_ERR_INVALID_ARG; }
@@ -252,6 +341,16 @@ static lmx_status collect_clusters_impl(const char* what, lmx_ctx* c, int32_t n_
     if ((st = dev_alloc(c, &c->d_f2_scratch, F * F2_MAX * 32, false)) != LMX_OK) return st;
     LMX_HIP(hipStreamCreateWithFlags(&c->f2_stream, hipStreamNonBlocking));
     LMX_HIP(hipStreamSynchronize(c->stream));
+  }
+  if (cls && !c->h_f2_cluster_class) {
+    LMX_HIP(hipHostMalloc((void**)&c->h_f2_cluster_class, F * F2_MAX * sizeof(int32_t), hipHostMallocMapped));
+    LMX_HIP(hipHostGetDevicePointer((void**)&c->d_f2_cluster_class, c->h_f2_cluster_class, 0));
+  }
+  if (cls && depth && (c->f2_class_base.size() != (size_t)cls->n_classes + 1 || !std::equal(c->f2_class_base.begin(), c->f2_class_base.end(), cls->class_base))) {
+    // (every earlier call that read the old table ended synchronised)
+    if (!c->d_f2_class_base) LMX_HIP(hipMalloc((void**)&c->d_f2_class_base, (F2_CLASSES + 1) * sizeof(int32_t)));
+    LMX_HIP(hipMemcpy(c->d_f2_class_base, cls->class_base, ((size_t)cls->n_classes + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
+    c->f2_class_base.assign(cls->class_base, cls->class_base + cls->n_classes + 1);
   }
   if (depth && !c->h_f2_diffs) {
     LMX_HIP(hipHostMalloc((void**)&c->h_f2_diffs, F * F2_MAX * sizeof(lmx_depth_diff_t), hipHostMallocMapped));
@@ -284,22 +383,25 @@ static lmx_status collect_clusters_impl(const char* what, lmx_ctx* c, int32_t n_
   p.dists = c->d_f2_dists; p.rects = c->d_f2_rects; p.n_templates = (uint32_t)c->f2_templates;
   p.step = c->f2_params.vote_row_col_step; p.size_thresh = c->f2_params.cluster_size_thresh; p.do_clusters = 1;
   p.radius_min = c->f2_params.renderer_radius_min; p.radius_step = c->f2_params.renderer_radius_step;
+  if (cls) { p.classes = c->d_f2_class_table; p.out_cluster_class = c->d_f2_cluster_class; }
   if (depth) {
     if (lmx_status st = grow_rec_diffs((void**)&c->d_f2_rec_diffs, &c->f2_rec_diffs_cap, n_match, sizeof(lmx_depth_diff_t))) return st;
     if (depth->normal)
       if (lmx_status st = grow_rec_diffs((void**)&c->d_f2_rec_ndiffs, &c->f2_rec_ndiffs_cap, n_match, sizeof(lmx_normal_diff_t))) return st;
     // the scene's copies, one workgroup per raw record (the count is the header's, read above), the scored chain: one synchronisation
-    if (lmx_status st = depth_launch_records(depth->templates, s, p.recs, n_match, depth->class_index, c->d_f2_rec_diffs,
-                                             depth->normal ? c->d_f2_rec_ndiffs : nullptr)) return st;
+    if (lmx_status st = cls ? depth_launch_records_classes(depth->templates, s, p.recs, n_match, c->d_f2_class_base, cls->n_classes, c->d_f2_rec_diffs,
+                                                           depth->normal ? c->d_f2_rec_ndiffs : nullptr)
+                            : depth_launch_records(depth->templates, s, p.recs, n_match, depth->class_index, c->d_f2_rec_diffs,
+                                                   depth->normal ? c->d_f2_rec_ndiffs : nullptr)) return st;
     p.diffs = c->d_f2_rec_diffs; p.out_diffs = c->d_f2_diffs; p.diff_scratch = c->d_f2_diff_scratch; p.no_value = depth->no_value;
     if (depth->normal) {
       p.ndiffs = c->d_f2_rec_ndiffs; p.out_ndiffs = c->d_f2_ndiffs; p.ndiff_scratch = c->d_f2_ndiff_scratch;
-      launch_f2_normal(s, p);
+      if (cls) launch_f2_classes(s, p, 2); else launch_f2_normal(s, p);
     } else {
-      launch_f2_scored(s, p);
+      if (cls) launch_f2_classes(s, p, 1); else launch_f2_scored(s, p);
     }
   } else {
-    launch_f2(s, p);
+    if (cls) launch_f2_classes(s, p, 0); else launch_f2(s, p);
   }
   LMX_HIP(hipGetLastError());
   LMX_HIP(hipStreamSynchronize(s));
@@ -324,6 +426,10 @@ static lmx_status collect_clusters_impl(const char* what, lmx_ctx* c, int32_t n_
   std::vector<lmx_depth_diff_t> fd;
   std::vector<lmx_normal_diff_t> fn;
   std::vector<double> fv;
+  std::vector<int32_t> fcls;
+  std::vector<lmx_class_sidecar> host_classes;
+  if (cls && any_host)
+    for (const lmx_ctx::ClassSidecar& k : c->f2_class) host_classes.push_back(lmx_class_sidecar{k.dists.data(), k.rects.data(), k.dists.size(), k.params});
   for (int f = 0; f < n_frames; ++f) {
     size_t nm = 0, nc = 0, nmem = 0;
     if (counts[(size_t)f * 4 + 3] == 0) {
@@ -334,6 +440,7 @@ static lmx_status collect_clusters_impl(const char* what, lmx_ctx* c, int32_t n_
       if (depth && depth->ndiffs && cap_matches) fn.assign(c->h_f2_ndiffs + (size_t)F2_MAX * f, c->h_f2_ndiffs + (size_t)F2_MAX * f + nm);
       fc.assign(all_c + (size_t)F2_MAX * f, all_c + (size_t)F2_MAX * f + nc);
       fmem.assign(all_mem + (size_t)F2_MAX * f, all_mem + (size_t)F2_MAX * f + nmem);
+      if (cls) fcls.assign(c->h_f2_cluster_class + (size_t)F2_MAX * f, c->h_f2_cluster_class + (size_t)F2_MAX * f + nc);
     } else {
       std::vector<const lmx_raw_match_t*> recs;
       for (const lmx_raw_match_t& r : host_recs)
@@ -343,15 +450,21 @@ static lmx_status collect_clusters_impl(const char* what, lmx_ctx* c, int32_t n_
       fm.resize(nm);
       for (size_t i = 0; i < nm; ++i) fm[i] = fin[i].m;
       fc.resize(std::max<size_t>(nm, 1)); fmem.resize(std::max<size_t>(nm, 1));
+      if (cls) fcls.resize(std::max<size_t>(nm, 1));
       size_t got = 0;
       lmx_status hs;
       if (depth) {   // the final matches against the resident scene (k_depth_diff), then the host chain on their values
         fd.resize(std::max<size_t>(nm, 1)); fv.resize(std::max<size_t>(nm, 1));
         if (depth->normal) fn.resize(std::max<size_t>(nm, 1));
-        if ((hs = depth_diff_resident(depth->templates, fm.data(), nm, f, depth->class_index, fd.data(), depth->normal ? fn.data() : nullptr)) != LMX_OK) return hs;
+        hs = cls ? depth_diff_resident_classes(depth->templates, fm.data(), nm, f, cls->class_base, cls->n_classes, fd.data(), depth->normal ? fn.data() : nullptr)
+                 : depth_diff_resident(depth->templates, fm.data(), nm, f, depth->class_index, fd.data(), depth->normal ? fn.data() : nullptr);
+        if (hs != LMX_OK) return hs;
         for (size_t i = 0; i < nm; ++i) fv[i] = depth->normal ? nv::value(fd[i], fn[i], depth->no_value) : dv::value(fd[i], depth->no_value);
-        hs = lmx_cluster_matches_scored(fm.data(), nm, fv.data(), c->f2_host_dists.data(), c->f2_host_rects.data(), c->f2_templates, &c->f2_params, fc.data(),
+        if (cls) hs = lmx_cluster_matches_classes(fm.data(), nm, fv.data(), host_classes.data(), F2_CLASSES, fc.data(), fcls.data(), fc.size(), &got, fmem.data(), fmem.size());
+        else hs = lmx_cluster_matches_scored(fm.data(), nm, fv.data(), c->f2_host_dists.data(), c->f2_host_rects.data(), c->f2_templates, &c->f2_params, fc.data(),
                                         fc.size(), &got, fmem.data(), fmem.size());
+      } else if (cls) {
+        hs = lmx_cluster_matches_classes(fm.data(), nm, nullptr, host_classes.data(), F2_CLASSES, fc.data(), fcls.data(), fc.size(), &got, fmem.data(), fmem.size());
       } else {
         hs = lmx_cluster_matches(fm.data(), nm, c->f2_host_dists.data(), c->f2_host_rects.data(), c->f2_templates, &c->f2_params, fc.data(), fc.size(), &got,
                                  fmem.data(), fmem.size());
@@ -371,6 +484,7 @@ static lmx_status collect_clusters_impl(const char* what, lmx_ctx* c, int32_t n_
     if (cpos + nc <= cap_clusters && mempos + nmem <= cap_members) {
       for (size_t i = 0; i < nc; ++i) { clusters[cpos + i] = fc[i]; clusters[cpos + i].member_begin += (int32_t)mempos; }
       if (nmem) std::memcpy(members + mempos, fmem.data(), nmem * sizeof(int32_t));
+      if (cls && nc) std::memcpy(cls->cluster_class + cpos, fcls.data(), nc * sizeof(int32_t));
     } else {
       st = LMX_ERR_OVERFLOW;
     }
@@ -388,7 +502,7 @@ lmx_status lmx_ctx_collect_clusters(lmx_ctx* c, int32_t n_frames, lmx_match_t* m
     set_error("lmx_ctx_collect_clusters: null argument");
     return LMX_ERR_INVALID_ARG;
   }
-  return collect_clusters_impl("lmx_ctx_collect_clusters", c, n_frames, nullptr, matches, cap_matches, match_offsets, clusters, cap_clusters, cluster_offsets,
+  return collect_clusters_impl("lmx_ctx_collect_clusters", c, n_frames, nullptr, nullptr, matches, cap_matches, match_offsets, clusters, cap_clusters, cluster_offsets,
                                members, cap_members);
   });
 }
@@ -404,7 +518,7 @@ lmx_status lmx_ctx_collect_clusters_depth(lmx_ctx* c, int32_t n_frames, lmx_dept
   }
   std::lock_guard<std::mutex> lk(depth_templates_mutex(templates));   // held for the whole call: the scene and the object's buffers stay put
   const DepthScore depth{templates, class_index, no_value, diffs, false, nullptr};
-  return collect_clusters_impl("lmx_ctx_collect_clusters_depth", c, n_frames, &depth, matches, cap_matches, match_offsets, clusters, cap_clusters,
+  return collect_clusters_impl("lmx_ctx_collect_clusters_depth", c, n_frames, &depth, nullptr, matches, cap_matches, match_offsets, clusters, cap_clusters,
                                cluster_offsets, members, cap_members);
   });
 }
@@ -421,8 +535,30 @@ lmx_status lmx_ctx_collect_clusters_depth_normal(lmx_ctx* c, int32_t n_frames, l
   }
   std::lock_guard<std::mutex> lk(depth_templates_mutex(templates));   // held for the whole call: the scene and the object's buffers stay put
   const DepthScore depth{templates, class_index, no_value, diffs, true, ndiffs};
-  return collect_clusters_impl("lmx_ctx_collect_clusters_depth_normal", c, n_frames, &depth, matches, cap_matches, match_offsets, clusters, cap_clusters,
+  return collect_clusters_impl("lmx_ctx_collect_clusters_depth_normal", c, n_frames, &depth, nullptr, matches, cap_matches, match_offsets, clusters, cap_clusters,
                                cluster_offsets, members, cap_members);
+  });
+}
+
+lmx_status lmx_ctx_collect_clusters_classes(lmx_ctx* c, int32_t n_frames, const lmx_class_score* score, lmx_match_t* matches, size_t cap_matches,
+                                            size_t* match_offsets, lmx_depth_diff_t* diffs, lmx_normal_diff_t* ndiffs, lmx_cluster_t* clusters,
+                                            int32_t* cluster_class, size_t cap_clusters, size_t* cluster_offsets, int32_t* members, size_t cap_members) {
+  return lmx::guarded("lmx_ctx_collect_clusters_classes", [&]() -> lmx_status {
+  const char* const what = "lmx_ctx_collect_clusters_classes";
+  if (!c || !match_offsets || !cluster_offsets || (cap_matches > 0 && !matches) || (cap_clusters > 0 && (!clusters || !cluster_class)) ||
+      (cap_members > 0 && !members) || (score && !score->templates)) {
+    set_error("%s: null argument", what);
+    return LMX_ERR_INVALID_ARG;
+  }
+  if (!score) {
+    const ClassChain cls{nullptr, 0, cluster_class};
+    return collect_clusters_impl(what, c, n_frames, nullptr, &cls, matches, cap_matches, match_offsets, clusters, cap_clusters, cluster_offsets, members, cap_members);
+  }
+  if (score->no_value != score->no_value) { set_error("%s: no_value is not a number (the score order would be undefined)", what); return LMX_ERR_INVALID_ARG; }
+  std::lock_guard<std::mutex> lk(depth_templates_mutex(score->templates));   // held for the whole call: the scene and the object's buffers stay put
+  const DepthScore depth{score->templates, -1, score->no_value, diffs, score->normals != 0, score->normals ? ndiffs : nullptr};
+  const ClassChain cls{score->class_base, score->n_classes, cluster_class};
+  return collect_clusters_impl(what, c, n_frames, &depth, &cls, matches, cap_matches, match_offsets, clusters, cap_clusters, cluster_offsets, members, cap_members);
   });
 }
 

@@ -370,6 +370,13 @@ void lmx_ctx_destroy(lmx_ctx* c) {
   }
   if (c->d_f2_dists) (void)hipFree(c->d_f2_dists);
   if (c->d_f2_rects) (void)hipFree(c->d_f2_rects);
+  for (lmx_ctx::ClassSidecar& k : c->f2_class) {
+    if (k.d_dists) (void)hipFree(k.d_dists);
+    if (k.d_rects) (void)hipFree(k.d_rects);
+  }
+  if (c->d_f2_class_table) (void)hipFree(c->d_f2_class_table);
+  if (c->d_f2_class_base) (void)hipFree(c->d_f2_class_base);
+  if (c->h_f2_cluster_class) (void)hipHostFree(c->h_f2_cluster_class);
   if (c->f2_stream) { (void)hipStreamSynchronize(c->f2_stream); (void)hipStreamDestroy(c->f2_stream); }
   if (c->h_f2_out) (void)hipHostFree(c->h_f2_out);
   if (c->h_f2_diffs) (void)hipHostFree(c->h_f2_diffs);

@@ -229,6 +229,21 @@ struct lmx_ctx {
   lmx_normal_diff_t* d_f2_ndiff_scratch = nullptr;
   lmx_normal_diff_t* d_f2_rec_ndiffs = nullptr;
   size_t f2_rec_ndiffs_cap = 0;
+  // the per-class chain (lmx_ctx_set_cluster_sidecar_class, lmx_ctx_collect_clusters_classes): state of its own next to the un-classed
+  // side-car above.  Host copies per class for the fallback path; the device table of F2_CLASSES entries is rewritten by every set call
+  struct ClassSidecar {
+    std::vector<double> dists;
+    std::vector<int32_t> rects;
+    lmx_cluster_params params{};
+    double* d_dists = nullptr;
+    int32_t* d_rects = nullptr;
+  };
+  ClassSidecar f2_class[F2_CLASSES];
+  F2Class* d_f2_class_table = nullptr;           // [F2_CLASSES]
+  int32_t* d_f2_class_base = nullptr;            // [F2_CLASSES + 1]: the class_base of the last scored call
+  std::vector<int32_t> f2_class_base;            // what d_f2_class_base holds
+  int32_t* h_f2_cluster_class = nullptr;         // pinned, mapped: [F][F2_MAX], next to the clusters of h_f2_out
+  int32_t* d_f2_cluster_class = nullptr;         // its device view
   // stats / profiling
   int64_t stat_cands = 0, stat_matches = 0;
   uint32_t profiling = 0;  // bitmask over kernel ids

@@ -411,6 +411,143 @@ lmx_status lmx_debug_device_finalize_cluster_depth(int32_t device, const lmx_raw
   return debug_finalize_cluster("lmx_debug_device_finalize_cluster_depth", device, records, n_records, n_frames, templates, class_index, no_value, obj_origin_dists, rects, n_templates, params, matches, diffs,
                                 clusters, members, counts);
 }
+// The hook for the CLASSES forms: the records as a slot of their own, the classes' side-cars as the device table, then what
+// lmx_ctx_collect_clusters_classes launches.  No host completion.
+lmx_status lmx_debug_device_finalize_cluster_classes(int32_t device, const lmx_raw_match_t* records, size_t n_records, int32_t n_frames,
+                                                     const lmx_class_sidecar* classes, int32_t n_classes, const lmx_class_score* score, const lmx_image* depth,
+                                                     lmx_match_t* matches, lmx_depth_diff_t* diffs, lmx_normal_diff_t* ndiffs, lmx_cluster_t* clusters,
+                                                     int32_t* cluster_class, int32_t* members, uint32_t* counts) {
+  return lmx::guarded("lmx_debug_device_finalize_cluster_classes", [&]() -> lmx_status {
+  const char* const what = "lmx_debug_device_finalize_cluster_classes";
+  const bool normals = score && score->normals != 0;
+  if ((n_records && !records) || !classes || !matches || !clusters || !cluster_class || !members || !counts ||
+      (score && (!score->templates || !score->class_base || !depth || !diffs)) || (normals && !ndiffs)) {
+    set_error("%s: invalid argument", what);
+    return LMX_ERR_INVALID_ARG;
+  }
+  if (n_classes < 1 || n_classes > F2_CLASSES) { set_error("%s: n_classes must be 1..%d (got %d)", what, F2_CLASSES, n_classes); return LMX_ERR_INVALID_ARG; }
+  if (n_frames < 1 || n_frames > 8) { set_error("%s: n_frames must be 1..8 (got %d)", what, n_frames); return LMX_ERR_INVALID_ARG; }
+  if (n_records > ((size_t)1 << 24)) { set_error("%s: at most 2^24 records", what); return LMX_ERR_INVALID_ARG; }
+  for (int32_t k = 0; k < n_classes; ++k) {
+    const lmx_class_sidecar& sc = classes[k];
+    if (sc.n_templates == 0) continue;
+    lmx_status vs = LMX_OK;
+    if (!sc.obj_origin_dists || !sc.rects || sc.n_templates > ((size_t)1 << 24)) { set_error("invalid side-car (at most 2^24 templates)"); vs = LMX_ERR_INVALID_ARG; }
+    else if (sc.params.vote_row_col_step <= 0) { set_error("vote_row_col_step must be positive"); vs = LMX_ERR_INVALID_ARG; }
+    else if (sc.params.cluster_size_thresh < 0) { set_error("cluster_size_thresh must not be negative"); vs = LMX_ERR_INVALID_ARG; }
+    else vs = check_vote_rings(sc.obj_origin_dists, sc.n_templates, &sc.params);
+    if (vs != LMX_OK) { const std::string why = lmx_last_error(); set_error("%s: class %d: %s", what, k, why.c_str()); return vs; }
+  }
+  for (size_t i = 0; i < n_records; ++i) {   // the kernel keeps x, y as int16 and class_index as uint16 in LDS
+    const lmx_raw_match_t& r = records[i];
+    if (r.x < -32768 || r.x > 32767 || r.y < -32768 || r.y > 32767 || r.class_index < 0 || r.class_index > 65535) {
+      set_error("%s: record %zu: x, y must fit an int16 and class_index a uint16", what, i);
+      return LMX_ERR_INVALID_ARG;
+    }
+  }
+  if (score) {
+    if (score->no_value != score->no_value) { set_error("%s: no_value is not a number", what); return LMX_ERR_INVALID_ARG; }
+    if (score->n_classes < 1 || score->n_classes > F2_CLASSES || score->class_base[0] != 0) { set_error("%s: class_base: n_classes 1..%d, class_base[0] = 0", what, F2_CLASSES); return LMX_ERR_INVALID_ARG; }
+    for (int32_t k = 0; k < score->n_classes; ++k)
+      if (score->class_base[k + 1] < score->class_base[k]) { set_error("%s: class_base must not decrease", what); return LMX_ERR_INVALID_ARG; }
+    const DepthSceneInfo si = depth_templates_scene(score->templates);
+    if (si.device != device) { set_error("%s: the templates live on another device", what); return LMX_ERR_INVALID_ARG; }
+    if (score->class_base[score->n_classes] != si.count) { set_error("%s: class_base ends at %d but the object holds %d depth templates", what, score->class_base[score->n_classes], si.count); return LMX_ERR_INVALID_ARG; }
+    if (normals && !si.normals) { set_error("%s: call lmx_depth_templates_enable_normals first", what); return LMX_ERR_INVALID_ARG; }
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available; this library has no CPU path"); return LMX_ERR_NO_DEVICE; }
+  LMX_HIP(hipSetDevice(device));
+  std::unique_lock<std::mutex> lk;
+  if (score) {   // held from the upload to the last launch: nobody replaces the scene between
+    lk = std::unique_lock<std::mutex>(depth_templates_mutex(score->templates));
+    if (lmx_status st = depth_upload_scene(score->templates, depth, n_frames)) return st;
+  }
+  const size_t F = (size_t)n_frames, R = std::max<size_t>(n_records, 1);
+  std::vector<void*> owned;   // every device buffer of this call
+  auto dev = [&](void** p, size_t bytes) -> hipError_t { const hipError_t e = hipMalloc(p, bytes); if (e == hipSuccess) owned.push_back(*p); return e; };
+  uint32_t hdr[16] = {0};
+  hdr[1] = (uint32_t)n_records;
+  uint32_t *d_hdr = nullptr, *d_counts = nullptr;
+  lmx_raw_match_t* d_recs = nullptr;
+  lmx_match_t* d_matches = nullptr;
+  lmx_cluster_t* d_clusters = nullptr;
+  int32_t *d_members = nullptr, *d_cluster_class = nullptr, *d_class_base = nullptr;
+  uint8_t* d_scratch = nullptr;
+  F2Class* d_table = nullptr;
+  lmx_depth_diff_t *d_rec_diffs = nullptr, *d_diffs = nullptr, *d_diff_scratch = nullptr;
+  lmx_normal_diff_t *d_rec_ndiffs = nullptr, *d_ndiffs = nullptr, *d_ndiff_scratch = nullptr;
+  auto run = [&]() -> lmx_status {
+    LMX_HIP(dev((void**)&d_hdr, sizeof(hdr)));
+    LMX_HIP(dev((void**)&d_recs, R * sizeof(lmx_raw_match_t)));
+    LMX_HIP(dev((void**)&d_matches, F * F2_MAX * sizeof(lmx_match_t)));
+    LMX_HIP(dev((void**)&d_clusters, F * F2_MAX * sizeof(lmx_cluster_t)));
+    LMX_HIP(dev((void**)&d_cluster_class, F * F2_MAX * sizeof(int32_t)));
+    LMX_HIP(dev((void**)&d_members, F * F2_MAX * sizeof(int32_t)));
+    LMX_HIP(dev((void**)&d_counts, F * 4 * sizeof(uint32_t)));
+    LMX_HIP(dev((void**)&d_scratch, F * F2_MAX * 32));
+    LMX_HIP(dev((void**)&d_table, F2_CLASSES * sizeof(F2Class)));
+    F2Class tab[F2_CLASSES] = {};
+    for (int32_t k = 0; k < n_classes; ++k) {
+      const lmx_class_sidecar& sc = classes[k];
+      if (sc.n_templates == 0) continue;
+      double* dd = nullptr;
+      int32_t* dr = nullptr;
+      LMX_HIP(dev((void**)&dd, sc.n_templates * sizeof(double)));
+      LMX_HIP(dev((void**)&dr, sc.n_templates * 4 * sizeof(int32_t)));
+      LMX_HIP(hipMemcpy(dd, sc.obj_origin_dists, sc.n_templates * sizeof(double), hipMemcpyHostToDevice));
+      LMX_HIP(hipMemcpy(dr, sc.rects, sc.n_templates * 4 * sizeof(int32_t), hipMemcpyHostToDevice));
+      tab[k] = F2Class{dd, dr, (uint32_t)sc.n_templates, sc.params.vote_row_col_step, sc.params.cluster_size_thresh, 0, sc.params.renderer_radius_min,
+                       sc.params.renderer_radius_step};
+    }
+    LMX_HIP(hipMemcpy(d_table, tab, sizeof(tab), hipMemcpyHostToDevice));
+    LMX_HIP(hipMemcpy(d_hdr, hdr, sizeof(hdr), hipMemcpyHostToDevice));
+    if (n_records) LMX_HIP(hipMemcpy(d_recs, records, n_records * sizeof(lmx_raw_match_t), hipMemcpyHostToDevice));
+    LMX_HIP(hipMemset(d_matches, 0, F * F2_MAX * sizeof(lmx_match_t)));
+    LMX_HIP(hipMemset(d_clusters, 0, F * F2_MAX * sizeof(lmx_cluster_t)));
+    LMX_HIP(hipMemset(d_cluster_class, 0, F * F2_MAX * sizeof(int32_t)));
+    LMX_HIP(hipMemset(d_members, 0, F * F2_MAX * sizeof(int32_t)));
+    LMX_HIP(hipMemset(d_counts, 0xff, F * 4 * sizeof(uint32_t)));   // a frame the kernel did not report on stays recognisable
+    F2Params p{};
+    p.recs = d_recs; p.hdr = d_hdr; p.cap = (uint32_t)n_records; p.n_frames = n_frames;
+    p.out_matches = d_matches; p.out_counts = d_counts; p.out_clusters = d_clusters; p.out_members = d_members; p.scratch = d_scratch;
+    p.do_clusters = 1; p.classes = d_table; p.out_cluster_class = d_cluster_class;
+    if (score) {
+      LMX_HIP(dev((void**)&d_class_base, (F2_CLASSES + 1) * sizeof(int32_t)));
+      LMX_HIP(hipMemcpy(d_class_base, score->class_base, ((size_t)score->n_classes + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
+      LMX_HIP(dev((void**)&d_rec_diffs, R * sizeof(lmx_depth_diff_t)));
+      LMX_HIP(dev((void**)&d_diffs, F * F2_MAX * sizeof(lmx_depth_diff_t)));
+      LMX_HIP(dev((void**)&d_diff_scratch, F * 2 * F2_MAX * sizeof(lmx_depth_diff_t)));
+      LMX_HIP(hipMemset(d_diffs, 0, F * F2_MAX * sizeof(lmx_depth_diff_t)));
+      if (normals) {
+        LMX_HIP(dev((void**)&d_rec_ndiffs, R * sizeof(lmx_normal_diff_t)));
+        LMX_HIP(dev((void**)&d_ndiffs, F * F2_MAX * sizeof(lmx_normal_diff_t)));
+        LMX_HIP(dev((void**)&d_ndiff_scratch, F * 2 * F2_MAX * sizeof(lmx_normal_diff_t)));
+        LMX_HIP(hipMemset(d_ndiffs, 0, F * F2_MAX * sizeof(lmx_normal_diff_t)));
+      }
+      if (lmx_status ds = depth_launch_records_classes(score->templates, nullptr, d_recs, (uint32_t)n_records, d_class_base, score->n_classes, d_rec_diffs,
+                                                       d_rec_ndiffs)) return ds;
+      p.diffs = d_rec_diffs; p.out_diffs = d_diffs; p.diff_scratch = d_diff_scratch; p.no_value = score->no_value;
+      p.ndiffs = d_rec_ndiffs; p.out_ndiffs = d_ndiffs; p.ndiff_scratch = d_ndiff_scratch;
+    }
+    launch_f2_classes(nullptr, p, score ? (normals ? 2 : 1) : 0);
+    LMX_HIP(hipGetLastError());
+    LMX_HIP(hipDeviceSynchronize());
+    if (score) LMX_HIP(hipMemcpy(diffs, d_diffs, F * F2_MAX * sizeof(lmx_depth_diff_t), hipMemcpyDeviceToHost));
+    if (normals) LMX_HIP(hipMemcpy(ndiffs, d_ndiffs, F * F2_MAX * sizeof(lmx_normal_diff_t), hipMemcpyDeviceToHost));
+    LMX_HIP(hipMemcpy(matches, d_matches, F * F2_MAX * sizeof(lmx_match_t), hipMemcpyDeviceToHost));
+    LMX_HIP(hipMemcpy(clusters, d_clusters, F * F2_MAX * sizeof(lmx_cluster_t), hipMemcpyDeviceToHost));
+    LMX_HIP(hipMemcpy(cluster_class, d_cluster_class, F * F2_MAX * sizeof(int32_t), hipMemcpyDeviceToHost));
+    LMX_HIP(hipMemcpy(members, d_members, F * F2_MAX * sizeof(int32_t), hipMemcpyDeviceToHost));
+    LMX_HIP(hipMemcpy(counts, d_counts, F * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return LMX_OK;
+  };
+  const lmx_status st = run();
+  if (st != LMX_OK) (void)hipDeviceSynchronize();
+  for (void* q : owned) (void)hipFree(q);
+  return st;
+  });
+}
 lmx_status lmx_debug_introsort_perm_score(const double* score, int32_t n, int32_t* perm) {
   if (n < 0 || (n > 0 && (!score || !perm))) { set_error("lmx_debug_introsort_perm_score: invalid argument"); return LMX_ERR_INVALID_ARG; }
   for (int32_t i = 0; i < n; ++i) perm[i] = i;

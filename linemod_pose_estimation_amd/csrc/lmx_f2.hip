@@ -83,6 +83,8 @@ __device__ __forceinline__ unsigned long long match_sort_key(float similarity, i
   return ((unsigned long long)(~b) << 32) | (unsigned long long)((uint32_t)template_id ^ 0x80000000u);
 }
 
+enum { F2_SIMILARITY = 0, F2_DEPTH = 1, F2_DEPTH_NORMAL = 2 };   // what a cluster's score is the mean of
+
 // test hook (lmx_debug_device_sort_perm): the permutation sortblk::sort produces for n <= F2_MAX (similarity, template_id) pairs
 __global__ __launch_bounds__(256) void k_debug_block_sort(const float* sim, const int* tid_in, int n, int* perm, unsigned long long* spill) {
   __shared__ unsigned long long s_key[F2_MAX];
@@ -96,9 +98,128 @@ __global__ __launch_bounds__(256) void k_debug_block_sort(const float* sim, cons
   for (int i = threadIdx.x; i < n; i += 256) perm[i] = s_tag[i];
 }
 
-enum { F2_SIMILARITY = 0, F2_DEPTH = 1, F2_DEPTH_NORMAL = 2 };   // what a cluster's score is the mean of
-
+// Stages E - G of the CLASSES forms (lmx_ctx_collect_clusters_classes): the chain below per class, as lmx_cluster_matches_classes composes
+// it on the host.  The vote key carries the class on top -- class 4 bits | y / step 16 | x / step 16 | ring 17 | list position 11, all
+// offset-binary; x and y come from a short, so with step >= 1 sixteen bits lose nothing -- and step, ring constants, size threshold and
+// side-car are the class's own (p.classes).  A match whose class has no side-car gets the all-ones key of the padding and is left out of
+// the runs; n_valid counts the others, since class 15 at y = x = 32767, ring 2^16 - 1, position 2047 has that key too.  The emulated
+// std::sort by score and the greedy NMS take ONE class's clusters at a time (libstdc++'s order of ties depends on the array it sorts, so
+// sorting the joined list would not be the composition), and the classes' survivors are written one class after the other.
+// s_valid and s_bad are the two LDS words stages A - D are done with.
 template <int MODE>
+__device__ __forceinline__ void f2_cluster_classes(const F2Params& p, int frame, int nf, unsigned long long* s_key, const float* s_sim, const int* s_tid,
+                                                   const short* s_x, const short* s_y, const unsigned short* s_cls, unsigned short* s_perm,
+                                                   unsigned short* s_keep, int* s_valid, int* s_bad, const lmx_depth_diff_t* d_final,
+                                                   const lmx_normal_diff_t* n_final, uint32_t* counts) {
+  constexpr bool SCORED = MODE != F2_SIMILARITY, NORMAL = MODE == F2_DEPTH_NORMAL;
+  constexpr int NMAX = F2_MAX;
+  const int tid = threadIdx.x;
+  const F2Class* const tab = p.classes;
+  if (tid == 0) { *s_valid = 0; *s_bad = 0; }
+  __syncthreads();
+  int nf2 = 1;
+  while (nf2 < nf) nf2 <<= 1;
+  for (int j = tid; j < nf2; j += 256) {
+    unsigned long long key = ~0ull;
+    if (j < nf) {
+      const int c = s_cls[j];
+      if (c < F2_CLASSES && tab[c].n_templates != 0) {
+        const int t = s_tid[j];
+        if (t < 0 || (uint32_t)t >= tab[c].n_templates) { atomicOr(s_bad, 1); }
+        else {
+          const int iy = s_y[j] / tab[c].step, ix = s_x[j] / tab[c].step;
+          const float depth = (float)tab[c].dists[t];
+          const float ring_step = (float)tab[c].radius_step;
+          const int ring = (int)((depth - tab[c].radius_min) / ring_step);   // float - double -> double, / float -> double, like the reference
+          const long long fr = (long long)ring + (1 << 16);
+          if (fr < 0 || fr >= (1 << 17)) atomicOr(s_bad, 2);
+          else {
+            key = ((unsigned long long)c << 60) | ((unsigned long long)(iy + (1 << 15)) << 44) | ((unsigned long long)(ix + (1 << 15)) << 28) |
+                  ((unsigned long long)fr << 11) | (unsigned long long)j;
+            atomicAdd(s_valid, 1);
+          }
+        }
+      }
+    }
+    s_key[j] = key;
+  }
+  __syncthreads();
+  if (*s_bad) {   // a template id outside its class's side-car / a ring outside the packed range: host path
+    if (tid == 0) { counts[0] = (uint32_t)nf; counts[1] = 0; counts[2] = 0; counts[3] = 2; }
+    return;
+  }
+  bitonic_sort_u64(s_key, nf2, tid, 256);
+  if (tid == 0) {
+    const int nv = *s_valid;   // the sorted keys 0 .. nv - 1 are the matches that vote
+    lmx_cluster_t* out_c = p.out_clusters + (size_t)frame * NMAX;
+    int32_t* out_cls = p.out_cluster_class + (size_t)frame * NMAX;
+    int32_t* out_mem = p.out_members + (size_t)frame * NMAX;
+    double* c_score = reinterpret_cast<double*>(p.scratch + (size_t)frame * NMAX * 32);
+    unsigned long long* c_range = reinterpret_cast<unsigned long long*>(p.scratch + (size_t)frame * NMAX * 32 + (size_t)NMAX * 8);   // begin << 32 | count
+    int* c_rect = reinterpret_cast<int*>(p.scratch + (size_t)frame * NMAX * 32 + (size_t)NMAX * 16);
+    int n_out = 0, n_mem = 0;
+    for (int b = 0; b < nv;) {
+      // F for the class whose key range starts at b: its clusters are the runs of equal key up to the next class
+      const int c = (int)(s_key[b] >> 60);
+      const int size_thresh = tab[c].size_thresh;
+      const int32_t* const rects = tab[c].rects;
+      int nc = 0;
+      while (b < nv && (int)(s_key[b] >> 60) == c) {
+        int e = b + 1;
+        while (e < nv && (s_key[e] >> 11) == (s_key[b] >> 11)) ++e;
+        const int cnt = e - b;
+        if (cnt > size_thresh) {
+          double sum = 0.0;
+          int X = 0, Y = 0, Wd = 0, Ht = 0;
+          for (int k = b; k < e; ++k) {
+            const int j = (int)(s_key[k] & 2047u);
+            if constexpr (NORMAL) sum += nv::value(d_final[j], n_final[j], p.no_value);
+            else if constexpr (SCORED) sum += dv::value(d_final[j], p.no_value);
+            else sum += (double)s_sim[j];
+            const int32_t* r = rects + (size_t)s_tid[j] * 4;
+            X += s_x[j]; Y += s_y[j]; Wd += r[2]; Ht += r[3];
+          }
+          c_range[nc] = ((unsigned long long)b << 32) | (unsigned)cnt;
+          c_score[nc] = sum / cnt;
+          c_rect[4 * nc + 0] = div_by_size(X, cnt); c_rect[4 * nc + 1] = div_by_size(Y, cnt);
+          c_rect[4 * nc + 2] = div_by_size(Wd, cnt); c_rect[4 * nc + 3] = div_by_size(Ht, cnt);
+          ++nc;
+        }
+        b = e;
+      }
+      // G on this class's clusters alone
+      for (int i = 0; i < nc; ++i) { s_perm[i] = (unsigned short)i; s_keep[i] = 0; }
+      sortemu::sort(s_perm, nc, [&](unsigned short a, unsigned short b2) { return c_score[a] > c_score[b2]; });
+      for (int a = 0; a < nc; ++a) {
+        if (s_keep[s_perm[a]]) continue;
+        for (int q = a + 1; q < nc; ++q)
+          if (!s_keep[s_perm[q]]) {
+            const double v = (double)box_iou(&c_rect[4 * s_perm[a]], &c_rect[4 * s_perm[q]]);
+            if (v > 0.4) s_keep[s_perm[q]] = 1;
+          }
+      }
+      for (int a = 0; a < nc; ++a) {
+        const int ci = s_perm[a];
+        if (s_keep[ci]) continue;
+        const int first = (int)(c_range[ci] >> 32), cnt = (int)(c_range[ci] & 0xffffffffu);
+        lmx_cluster_t o;
+        const unsigned long long key = s_key[first];
+        o.index[0] = (int)((key >> 44) & 0xffff) - (1 << 15);
+        o.index[1] = (int)((key >> 28) & 0xffff) - (1 << 15);
+        o.index[2] = (int)((key >> 11) & 0x1ffff) - (1 << 16);
+        for (int k = 0; k < 4; ++k) o.rect[k] = c_rect[4 * ci + k];
+        o.score = c_score[ci];
+        o.member_begin = n_mem; o.member_count = cnt;
+        for (int k = first; k < first + cnt; ++k) out_mem[n_mem++] = (int32_t)(s_key[k] & 2047u);
+        out_cls[n_out] = c;
+        out_c[n_out++] = o;
+      }
+    }
+    counts[0] = (uint32_t)nf; counts[1] = (uint32_t)n_out; counts[2] = (uint32_t)n_mem; counts[3] = 0;
+  }
+}
+
+template <int MODE, bool CLASSES = false>
 __device__ __forceinline__ void f2_finalize_cluster(const F2Params& p) {
   constexpr bool SCORED = MODE != F2_SIMILARITY, NORMAL = MODE == F2_DEPTH_NORMAL;
   constexpr int NMAX = F2_MAX;
@@ -246,6 +367,10 @@ __device__ __forceinline__ void f2_finalize_cluster(const F2Params& p) {
     if (tid == 0) { counts[0] = (uint32_t)nf; counts[1] = 0; counts[2] = 0; counts[3] = 0; }
     return;
   }
+  if constexpr (CLASSES) {   // E - G per class, on the same LDS
+    f2_cluster_classes<MODE>(p, frame, nf, s_key, s_sim, s_tid, s_x, s_y, s_cls, s_perm, s_keep, &s_n, &s_nfinal, d_final, n_final, counts);
+    return;
+  }
   // E: rcd_voting keys.  {y / step, x / step, ring} compared lexicographically as signed ints (std::map<vector<int>, ...>):
   // offset-binary fields of 17 + 17 + 19 bits, the match's position in the final list in the low 11 bits (keeps the order in
   // which matches were voted into a bin)
@@ -346,6 +471,10 @@ __device__ __forceinline__ void f2_finalize_cluster(const F2Params& p) {
 __global__ __launch_bounds__(256) void k_f2_finalize_cluster(F2Params p) { f2_finalize_cluster<F2_SIMILARITY>(p); }
 __global__ __launch_bounds__(256) void k_f2_finalize_cluster_scored(F2Params p) { f2_finalize_cluster<F2_DEPTH>(p); }
 __global__ __launch_bounds__(256) void k_f2_finalize_cluster_normal(F2Params p) { f2_finalize_cluster<F2_DEPTH_NORMAL>(p); }
+// and their CLASSES forms
+__global__ __launch_bounds__(256) void k_f2_finalize_cluster_classes(F2Params p) { f2_finalize_cluster<F2_SIMILARITY, true>(p); }
+__global__ __launch_bounds__(256) void k_f2_finalize_cluster_classes_scored(F2Params p) { f2_finalize_cluster<F2_DEPTH, true>(p); }
+__global__ __launch_bounds__(256) void k_f2_finalize_cluster_classes_normal(F2Params p) { f2_finalize_cluster<F2_DEPTH_NORMAL, true>(p); }
 
 void launch_debug_block_sort(hipStream_t s, const float* sim, const int* tid, int n, int* perm, unsigned long long* spill) {
   hipLaunchKernelGGL(k_debug_block_sort, dim3(1), dim3(256), 0, s, sim, tid, n, perm, spill);
@@ -361,6 +490,12 @@ void launch_f2_scored(hipStream_t s, const F2Params& p) {
 
 void launch_f2_normal(hipStream_t s, const F2Params& p) {
   hipLaunchKernelGGL(k_f2_finalize_cluster_normal, dim3((unsigned)p.n_frames), dim3(256), 0, s, p);
+}
+
+void launch_f2_classes(hipStream_t s, const F2Params& p, int mode) {
+  if (mode == F2_DEPTH_NORMAL) hipLaunchKernelGGL(k_f2_finalize_cluster_classes_normal, dim3((unsigned)p.n_frames), dim3(256), 0, s, p);
+  else if (mode == F2_DEPTH) hipLaunchKernelGGL(k_f2_finalize_cluster_classes_scored, dim3((unsigned)p.n_frames), dim3(256), 0, s, p);
+  else hipLaunchKernelGGL(k_f2_finalize_cluster_classes, dim3((unsigned)p.n_frames), dim3(256), 0, s, p);
 }
 
 }  // namespace lmx

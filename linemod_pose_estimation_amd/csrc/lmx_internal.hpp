@@ -302,6 +302,15 @@ void launch_depth_quantize(hipStream_t s, const uint16_t* depth, uint8_t* quant,
                            uint32_t* clear16 = nullptr);
 // device form of "finalise + cluster" (lmx_f2.hip)
 constexpr int F2_MAX = 2048;   // records per frame the LDS path takes; larger frames are finished by the host
+// One class's side-car as the CLASSES forms read it; n_templates 0: the class has none, its matches are listed and belong to no cluster
+constexpr int F2_CLASSES = 16;
+struct F2Class {
+  const double* dists;
+  const int32_t* rects;
+  uint32_t n_templates;
+  int32_t step, size_thresh, reserved;
+  double radius_min, radius_step;
+};
 struct F2Params {
   const lmx_raw_match_t* recs;   // the slot's records (all frames of the batch)
   const uint32_t* hdr;           // the slot's header: [1] = records written
@@ -326,10 +335,15 @@ struct F2Params {
   const lmx_normal_diff_t* ndiffs;
   lmx_normal_diff_t* out_ndiffs;
   lmx_normal_diff_t* ndiff_scratch;
+  // the CLASSES forms only (launch_f2_classes): a side-car per class instead of dists .. radius_step above, and each cluster's class
+  const F2Class* classes;            // [F2_CLASSES], device memory
+  int32_t* out_cluster_class;        // [n_frames][F2_MAX], next to out_clusters
 };
 void launch_f2(hipStream_t s, const F2Params& p);
 void launch_f2_scored(hipStream_t s, const F2Params& p);
 void launch_f2_normal(hipStream_t s, const F2Params& p);
+// the per-class chain (lmx_ctx_collect_clusters_classes); mode 0 mean similarity, 1 depth score, 2 depth + normal score
+void launch_f2_classes(hipStream_t s, const F2Params& p, int mode);
 
 // ---- depth check against a resident scene (lmx_verify.hip), for the scored consumer chain (lmx_collect.cpp, lmx_debug.cpp) --------------
 struct DepthSceneInfo { int32_t device, count, n_frames, W, H, normals; };   // n_frames 0: no scene uploaded; normals: enable_normals was called
@@ -345,6 +359,13 @@ lmx_status depth_launch_records(lmx_depth_templates* t, hipStream_t s, const lmx
 // (nout: the normal sums too, through k_verify_diff)
 lmx_status depth_diff_resident(lmx_depth_templates* t, const lmx_match_t* matches, size_t n, int32_t frame, int32_t class_index, lmx_depth_diff_t* out,
                                lmx_normal_diff_t* nout = nullptr);
+// The two above for an object that holds several classes' crops (lmx_depth_templates_append): class c's template i is crop class_base[c] + i.
+// A record or match whose class is >= n_classes, whose template_id is outside [0, class_base[c + 1] - class_base[c]) or whose frame is
+// outside the scene gets zeros and is never walked.  d_class_base: n_classes + 1 entries in device memory; class_base: the same on the host.
+lmx_status depth_launch_records_classes(lmx_depth_templates* t, hipStream_t s, const lmx_raw_match_t* d_recs, uint32_t n_records, const int32_t* d_class_base,
+                                        int32_t n_classes, lmx_depth_diff_t* d_diffs, lmx_normal_diff_t* d_ndiffs = nullptr);
+lmx_status depth_diff_resident_classes(lmx_depth_templates* t, const lmx_match_t* matches, size_t n, int32_t frame, const int32_t* class_base, int32_t n_classes,
+                                       lmx_depth_diff_t* out, lmx_normal_diff_t* nout = nullptr);
 void launch_debug_block_sort(hipStream_t s, const float* sim, const int* tid, int n, int* perm, unsigned long long* spill);
 
 struct PullEntry { uint64_t src; uint64_t row_stride; };  // one caller-owned pinned image (device-visible address)

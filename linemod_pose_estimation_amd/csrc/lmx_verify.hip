@@ -26,7 +26,9 @@
 // (diff_selected) and one guard in front of every normal-scored call (need_normals).
 #include <algorithm>
 #include <cstring>
+#include <functional>
 #include <memory>
+#include <vector>
 
 #include "lmx_internal.hpp"
 #include "lmx_depth_verify.hpp"
@@ -227,6 +229,39 @@ __global__ __launch_bounds__(256) void k_verify_diff_records(const DepthCrop* __
   const lmx_raw_match_t r = recs[blockIdx.x];
   diff_walk<true>(crops, normals, record_is_job(r, count, n_frames, class_index), r.template_id, r.x, r.y, r.frame, scene, scene_normals, W, H, table,
                   &diffs[blockIdx.x], &ndiffs[blockIdx.x]);
+}
+
+// The two record kernels for an object that holds several classes' crops one class after the other (lmx_depth_templates_append): class c's
+// template i is crop class_base[c] + i.  No job, hence zeros and no walk, for a class >= n_classes, a template_id outside its class's range
+// (it would be the next class's crop), a frame outside the scene.
+__device__ __forceinline__ bool record_class_job(const lmx_raw_match_t& r, const int32_t* __restrict__ class_base, int32_t n_classes, int32_t n_frames, int32_t* id) {
+  *id = 0;
+  if (r.class_index < 0 || r.class_index >= n_classes || r.frame < 0 || r.frame >= n_frames) return false;
+  const int32_t first = class_base[r.class_index], end = class_base[r.class_index + 1];
+  if (r.template_id < 0 || r.template_id >= end - first) return false;
+  *id = first + r.template_id;
+  return true;
+}
+
+__global__ __launch_bounds__(256) void k_depth_diff_records_classes(const DepthCrop* __restrict__ crops, const int32_t* __restrict__ class_base, int32_t n_classes,
+                                                                    const lmx_raw_match_t* __restrict__ recs, const uint16_t* __restrict__ scene, int32_t n_frames,
+                                                                    int W, int H, lmx_depth_diff_t* __restrict__ diffs) {
+  const lmx_raw_match_t r = recs[blockIdx.x];
+  int32_t id;
+  const bool is_job = record_class_job(r, class_base, n_classes, n_frames, &id);
+  diff_walk<false>(crops, nullptr, is_job, id, r.x, r.y, r.frame, scene, nullptr, W, H, nullptr, &diffs[blockIdx.x], nullptr);
+}
+
+__global__ __launch_bounds__(256) void k_verify_diff_records_classes(const DepthCrop* __restrict__ crops, nv::Packed* const* __restrict__ normals,
+                                                                     const int32_t* __restrict__ class_base, int32_t n_classes,
+                                                                     const lmx_raw_match_t* __restrict__ recs, const uint16_t* __restrict__ scene,
+                                                                     const nv::Packed* __restrict__ scene_normals, int32_t n_frames, int W, int H,
+                                                                     const uint32_t* __restrict__ table, lmx_depth_diff_t* __restrict__ diffs,
+                                                                     lmx_normal_diff_t* __restrict__ ndiffs) {
+  const lmx_raw_match_t r = recs[blockIdx.x];
+  int32_t id;
+  const bool is_job = record_class_job(r, class_base, n_classes, n_frames, &id);
+  diff_walk<true>(crops, normals, is_job, id, r.x, r.y, r.frame, scene, scene_normals, W, H, table, &diffs[blockIdx.x], &ndiffs[blockIdx.x]);
 }
 
 }  // namespace
@@ -580,6 +615,44 @@ extern "C" size_t lmx_depth_templates_device_bytes(const lmx_depth_templates* t)
   return t->normals_on ? depth + t->atlas_bytes * (sizeof(lmx::nv::Packed) / sizeof(uint16_t)) + t->table.size() * sizeof(lmx::nv::Packed*) : depth;
 }
 
+extern "C" lmx_status lmx_depth_templates_append(lmx_depth_templates* dst, lmx_depth_templates* src) {
+  return lmx::guarded("lmx_depth_templates_append", [&]() -> lmx_status {
+    if (!dst || !src) { lmx::set_error("lmx_depth_templates_append: null argument"); return LMX_ERR_INVALID_ARG; }
+    if (dst == src) { lmx::set_error("lmx_depth_templates_append: an object cannot be appended to itself"); return LMX_ERR_INVALID_ARG; }
+    if (dst->device != src->device) {
+      lmx::set_error("lmx_depth_templates_append: the objects live on devices %d and %d", dst->device, src->device);
+      return LMX_ERR_INVALID_ARG;
+    }
+    std::mutex* const first = std::less<lmx_depth_templates*>()(dst, src) ? &dst->m : &src->m;
+    std::mutex* const second = first == &dst->m ? &src->m : &dst->m;
+    std::lock_guard<std::mutex> lk1(*first);
+    std::lock_guard<std::mutex> lk2(*second);
+    if (src->table.size() + dst->table.size() > 0x7fffffffull) { lmx::set_error("lmx_depth_templates_append: too many templates"); return LMX_ERR_INVALID_ARG; }
+    // nothing queued may still read a table or the normals that go
+    for (lmx_depth_templates* t : {dst, src})
+      if (t->s) {
+        DV_HIP(hipSetDevice(t->device));
+        DV_HIP(hipStreamSynchronize(t->s));
+        t->scene_pending = false;
+        t->prof_drain();
+      }
+    dst->table.insert(dst->table.end(), src->table.begin(), src->table.end());
+    dst->rects.insert(dst->rects.end(), src->rects.begin(), src->rects.end());
+    dst->chunks.insert(dst->chunks.end(), src->chunks.begin(), src->chunks.end());
+    dst->atlas_bytes += src->atlas_bytes;
+    src->table.clear(); src->rects.clear(); src->chunks.clear(); src->atlas_bytes = 0;
+    for (lmx_depth_templates* t : {dst, src}) {
+      if (t->d_table) { (void)hipFree(t->d_table); t->d_table = nullptr; }   // uploaded again by ensure_device
+      if (t->d_ncrops || t->d_ntable) t->free_normal_crops();                  // recomputed by need_normals
+      t->ntable.clear();
+      t->ncrops_ready = false;
+    }
+    dst->scene_frames = 0;                                                     // the scene is forgotten: upload_scene comes before the next scored call
+    dst->scene_normals_valid = false;
+    return LMX_OK;
+  });
+}
+
 extern "C" void lmx_depth_templates_free(lmx_depth_templates* t) {
   if (!t) return;
   if (t->s) (void)hipSetDevice(t->device);
@@ -776,6 +849,40 @@ lmx_status depth_diff_resident(lmx_depth_templates* t, const lmx_match_t* matche
   if (nout)
     if (lmx_status st = need_normals(t, nullptr)) return st;
   return diff_selected(t, matches, nullptr, frame, t->scene_frames, t->scene_W, t->scene_H, out, nout);   // on the object's stream, behind the scene's copies
+}
+
+lmx_status depth_launch_records_classes(lmx_depth_templates* t, hipStream_t s, const lmx_raw_match_t* d_recs, uint32_t n_records, const int32_t* d_class_base,
+                                        int32_t n_classes, lmx_depth_diff_t* d_diffs, lmx_normal_diff_t* d_ndiffs) {
+  if (t->scene_frames < 1) { set_error("no scene uploaded: call lmx_depth_templates_upload_scene first"); return LMX_ERR_INVALID_ARG; }
+  if (d_ndiffs)
+    if (lmx_status st = need_normals(t, nullptr)) return st;
+  DV_HIP(hipStreamWaitEvent(s, t->scene_ready, 0));
+  if (n_records == 0) return LMX_OK;
+  if (d_ndiffs)
+    if (lmx_status st = t->scene_normals_on(s, nullptr, t->scene_frames, t->scene_W, t->scene_H)) return st;
+  const int pe = t->prof_begin(d_ndiffs ? lmx_depth_templates::PK_VERIFY_DIFF_RECORDS : lmx_depth_templates::PK_DEPTH_DIFF_RECORDS, s);
+  if (d_ndiffs)
+    hipLaunchKernelGGL(k_verify_diff_records_classes, dim3(n_records), dim3(256), 0, s, t->d_table, t->d_ntable, d_class_base, n_classes, d_recs, t->d_scene,
+                       t->d_scene_normals, t->scene_frames, t->scene_W, t->scene_H, t->d_angle, d_diffs, d_ndiffs);
+  else
+    hipLaunchKernelGGL(k_depth_diff_records_classes, dim3(n_records), dim3(256), 0, s, t->d_table, d_class_base, n_classes, d_recs, t->d_scene, t->scene_frames,
+                       t->scene_W, t->scene_H, d_diffs);
+  t->prof_end(pe, s);
+  DV_HIP(hipGetLastError());
+  return LMX_OK;
+}
+
+lmx_status depth_diff_resident_classes(lmx_depth_templates* t, const lmx_match_t* matches, size_t n, int32_t frame, const int32_t* class_base, int32_t n_classes,
+                                       lmx_depth_diff_t* out, lmx_normal_diff_t* nout) {
+  // the matches with their crop's index in the joined object for a template id; what record_class_job leaves out becomes id -1: zeros
+  std::vector<lmx_match_t> joined(matches, matches + n);
+  for (lmx_match_t& m : joined) {
+    int32_t id = -1;
+    if (m.class_index >= 0 && m.class_index < n_classes && m.template_id >= 0 && m.template_id < class_base[m.class_index + 1] - class_base[m.class_index])
+      id = class_base[m.class_index] + m.template_id;
+    m.template_id = id;
+  }
+  return depth_diff_resident(t, joined.data(), n, frame, -1, out, nout);
 }
 
 }  // namespace lmx

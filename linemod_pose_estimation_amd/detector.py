@@ -481,6 +481,46 @@ class Detector:
                                                                     mo, d.ctypes.data, nd.ctypes.data, cl.ctypes.data, cap_total, co, mem.ctypes.data, cap_total))
         return [(m[mo[f]:mo[f + 1]].copy(), d[mo[f]:mo[f + 1]].copy(), nd[mo[f]:mo[f + 1]].copy(), cl[co[f]:co[f + 1]].copy(), mem) for f in range(n_frames)]
 
+    def set_cluster_sidecar_class(self, class_index, obj_origin_dists, rects, vote_row_col_step=1, renderer_radius_min=0.0, renderer_radius_step=1.0,
+                                  cluster_size_thresh=2):
+        """Class class_index's side-car of the per-class device chain (lmx_ctx_set_cluster_sidecar_class), class_index 0 .. 15; empty
+        obj_origin_dists remove it.  The un-classed side-car of set_cluster_sidecar is separate state."""
+        d = np.ascontiguousarray(obj_origin_dists, np.float64).reshape(-1)
+        r = np.ascontiguousarray(rects, np.int32).reshape(-1, 4)
+        if len(r) != len(d):
+            raise ValueError("one rect per origin distance")
+        pp = _lib.ClusterParams(int(vote_row_col_step), float(renderer_radius_min), float(renderer_radius_step), int(cluster_size_thresh))
+        _lib.check(_lib.lib().lmx_ctx_set_cluster_sidecar_class(self.h, int(class_index), d.ctypes.data if len(d) else None, r.ctypes.data if len(d) else None,
+                                                                len(d), C.byref(pp)))
+
+    def collect_clusters_classes(self, n_frames, templates=None, class_base=None, normals=False, no_value=-np.inf, cap_total=1 << 16):
+        """collect_clusters for a bank of several classes (lmx_ctx_collect_clusters_classes): votes, filters, scores and suppresses per class
+        with the side-cars of set_cluster_sidecar_class.  -> list per frame of (matches, diffs, ndiffs, clusters, cluster_class, members);
+        a frame's clusters are class 0's, then class 1's, ..., cluster_class names each one's class.  templates None: mean similarity, diffs
+        and ndiffs are None.  Else `templates` is a DepthTemplates holding all classes' crops (DepthTemplates.append), class c's at
+        class_base[c]:class_base[c + 1], whose upload_scene was called after the enqueue; normals adds the normal term (ndiffs is None
+        without).  Equal to collect + per-class diffs + cluster_matches_classes bit for bit; not to two single-class detectors, whose std::unique
+        may keep other templates of a duplicate (include/lmx.h)."""
+        m = np.zeros(cap_total, MATCH_DTYPE)
+        cl = np.zeros(cap_total, CLUSTER_DTYPE)
+        cc = np.zeros(cap_total, np.int32)
+        mem = np.zeros(cap_total, np.int32)
+        mo = (C.c_size_t * (n_frames + 1))()
+        co = (C.c_size_t * (n_frames + 1))()
+        d = nd = score = None
+        if templates is not None:
+            base = np.ascontiguousarray(class_base, np.int32).reshape(-1)
+            if len(base) < 2:
+                raise ValueError("class_base must hold one entry per class plus one")
+            d = np.zeros(cap_total, DEPTH_DIFF_DTYPE)
+            nd = np.zeros(cap_total, NORMAL_DIFF_DTYPE) if normals else None
+            score = C.byref(_lib.ClassScore(templates.h, base.ctypes.data, len(base) - 1, int(bool(normals)), float(no_value)))
+        _lib.check(_lib.lib().lmx_ctx_collect_clusters_classes(self.h, n_frames, score, m.ctypes.data, cap_total, mo, d.ctypes.data if d is not None else None,
+                                                               nd.ctypes.data if nd is not None else None, cl.ctypes.data, cc.ctypes.data, cap_total, co,
+                                                               mem.ctypes.data, cap_total))
+        return [(m[mo[f]:mo[f + 1]].copy(), d[mo[f]:mo[f + 1]].copy() if d is not None else None, nd[mo[f]:mo[f + 1]].copy() if nd is not None else None,
+                 cl[co[f]:co[f + 1]].copy(), cc[co[f]:co[f + 1]].copy(), mem) for f in range(n_frames)]
+
     def raw_matches_ptrs(self):
         rec, cnt, cap = C.c_void_p(), C.c_void_p(), C.c_size_t()
         _lib.check(_lib.lib().lmx_ctx_raw_matches(self.h, C.byref(rec), C.byref(cnt), C.byref(cap)))
@@ -667,6 +707,48 @@ def cluster_matches_scored(matches, match_values, obj_origin_dists, rects, vote_
     return clusters[:n.value].copy(), members
 
 
+def _class_sidecars(classes):
+    """classes: one entry per class index, None (no side-car) or (obj_origin_dists, rects, vote_row_col_step, renderer_radius_min,
+    renderer_radius_step, cluster_size_thresh) -> (lmx_class_sidecar array, the arrays it points into)."""
+    arr = (_lib.ClassSidecar * max(1, len(classes)))()
+    keep = []
+    for k, c in enumerate(classes):
+        if c is None:
+            continue
+        dists, rects, step, rmin, rstep, thresh = c
+        d = np.ascontiguousarray(dists, np.float64).reshape(-1)
+        r = np.ascontiguousarray(rects, np.int32).reshape(-1, 4)
+        if len(r) != len(d):
+            raise ValueError("class %d: one rect per origin distance" % k)
+        keep += [d, r]
+        arr[k] = _lib.ClassSidecar(d.ctypes.data if len(d) else None, r.ctypes.data if len(d) else None, len(d),
+                                   _lib.ClusterParams(int(step), float(rmin), float(rstep), int(thresh)))
+    return arr, keep
+
+
+def cluster_matches_classes(matches, classes, match_values=None):
+    """lmx_cluster_matches_classes: the chain of cluster_matches (match_values None) or cluster_matches_scored per class of a bank of
+    several classes.  classes[c]: None or (obj_origin_dists, rects, vote_row_col_step, renderer_radius_min, renderer_radius_step,
+    cluster_size_thresh).  -> (clusters, cluster_class, members): class 0's clusters in the chain's order, then class 1's, ...; members
+    index `matches`.  Matches of a class without a side-car belong to no cluster; the NMS never crosses classes."""
+    matches = np.ascontiguousarray(matches, MATCH_DTYPE)
+    values = None
+    if match_values is not None:
+        values = np.ascontiguousarray(match_values, np.float64)
+        if values.shape != (len(matches),):
+            raise ValueError("match_values must hold one value per match")
+    arr, keep = _class_sidecars(classes)
+    clusters = np.zeros(max(1, len(matches)), CLUSTER_DTYPE)
+    cluster_class = np.zeros(max(1, len(matches)), np.int32)
+    members = np.zeros(max(1, len(matches)), np.int32)
+    n = C.c_size_t()
+    _lib.check(_lib.lib().lmx_cluster_matches_classes(matches.ctypes.data, len(matches), values.ctypes.data if values is not None else None, arr, len(classes),
+                                                      clusters.ctypes.data, cluster_class.ctypes.data, len(clusters), C.byref(n), members.ctypes.data,
+                                                      len(members)))
+    del keep
+    return clusters[:n.value].copy(), cluster_class[:n.value].copy(), members
+
+
 DEPTH_DIFF_DTYPE = np.dtype([("sum_abs_mm", "<i8"), ("n_valid", "<i4"), ("n_template", "<i4")])
 
 
@@ -851,6 +933,13 @@ class DepthTemplates:
         _lib.check(_lib.lib().lmx_depth_templates_upload_scene(self.h, imgs, len(frames)))
         self._scene_shape = tuple(frames[0].shape)
 
+    def append(self, other):
+        """Move `other`'s templates behind this object's (lmx_depth_templates_append): other's template i becomes template len(self) + i,
+        `other` is left empty.  For the per-class chain: the classes' objects joined in class order, class_base their cumulative counts.
+        An uploaded scene is forgotten."""
+        _lib.check(_lib.lib().lmx_depth_templates_append(self.h, other.h))
+        self._scene_shape = None
+
     def close(self):
         if getattr(self, "h", None):
             _lib.lib().lmx_depth_templates_free(self.h)
@@ -919,6 +1008,43 @@ def debug_device_finalize_cluster_depth(records, n_frames, templates, depth_fram
         if status == 1:   # counts[0] is the record count here, not a number of matches written
             n_m = 0
         out.append((m[f, :n_m].copy(), d[f, :n_m].copy(), cl[f, :n_c].copy(), mem[f, :n_mem].copy(), status))
+    return (out, counts) if with_counts else out
+
+
+def debug_device_finalize_cluster_classes(records, n_frames, classes, templates=None, class_base=None, depth_frames=None, normals=False, no_value=-np.inf,
+                                          device=0, with_counts=False):
+    """Test hook (lmx_debug_device_finalize_cluster_classes): the kernels behind Detector.collect_clusters_classes on a caller's records;
+    classes as cluster_matches_classes takes them.  -> list per frame of (matches, diffs, ndiffs, clusters, cluster_class, members, status);
+    diffs / ndiffs are None without templates / normals.  No host completion."""
+    records = np.ascontiguousarray(records, RAW_MATCH_DTYPE)
+    arr, keep = _class_sidecars(classes)
+    nf = max(1, int(n_frames))
+    m = np.zeros((nf, F2_MAX), MATCH_DTYPE)
+    cl = np.zeros((nf, F2_MAX), CLUSTER_DTYPE)
+    cc = np.zeros((nf, F2_MAX), np.int32)
+    mem = np.zeros((nf, F2_MAX), np.int32)
+    counts = np.zeros((nf, 4), np.uint32)
+    d = nd = score = imgs = None
+    if templates is not None:
+        base = np.ascontiguousarray(class_base, np.int32).reshape(-1)
+        frames, imgs = _depth_images(depth_frames)
+        if len(frames) != n_frames or len(base) < 2:
+            raise ValueError("one depth frame per frame, one class_base entry per class plus one")
+        d = np.zeros((nf, F2_MAX), DEPTH_DIFF_DTYPE)
+        nd = np.zeros((nf, F2_MAX), NORMAL_DIFF_DTYPE) if normals else None
+        score = C.byref(_lib.ClassScore(templates.h, base.ctypes.data, len(base) - 1, int(bool(normals)), float(no_value)))
+    _lib.check(_lib.lib().lmx_debug_device_finalize_cluster_classes(device, records.ctypes.data, len(records), int(n_frames), arr, len(classes), score, imgs,
+                                                                    m.ctypes.data, d.ctypes.data if d is not None else None,
+                                                                    nd.ctypes.data if nd is not None else None, cl.ctypes.data, cc.ctypes.data,
+                                                                    mem.ctypes.data, counts.ctypes.data))
+    del keep
+    out = []
+    for f in range(n_frames):
+        n_m, n_c, n_mem, status = (int(v) for v in counts[f])
+        if status == 1:   # counts[0] is the record count here, not a number of matches written
+            n_m = 0
+        out.append((m[f, :n_m].copy(), d[f, :n_m].copy() if d is not None else None, nd[f, :n_m].copy() if nd is not None else None, cl[f, :n_c].copy(),
+                    cc[f, :n_c].copy(), mem[f, :n_mem].copy(), status))
     return (out, counts) if with_counts else out
 
 
