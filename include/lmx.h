@@ -315,6 +315,24 @@ void lmx_host_free(void* p);
  * LMX_ERR_INVALID_ARG). */
 lmx_status lmx_ctx_enqueue(lmx_ctx* ctx, int32_t n_frames, float threshold, const char* const* class_ids,
                            int32_t n_class_ids);
+/* Per-class match thresholds.  What cv::linemod::Detector::match would produce if it passed thresholds[class] instead of `threshold` to
+ * each matchClass call: classes are visited as for lmx_ctx_enqueue (the class_ids list when given, otherwise every class in the bank's
+ * order), each with its own threshold in the coarse scan, the pruning bounds and the refinement, and one std::sort + std::unique runs over
+ * everything.  thresholds[k] belongs to class index k (lmx_bank_class_id order) whether or not class_ids selects the class; n_thresholds
+ * must equal the bank's class count; NaN is refused.  A bad argument returns LMX_ERR_INVALID_ARG and enqueues nothing.  With all entries
+ * equal to t the result is lmx_ctx_enqueue's at t.  Enqueues with different thresholds may be outstanding together: the values travel in
+ * a table per output slot, and with LMX_CTX_HIPGRAPH one captured chain serves every set of values. */
+lmx_status lmx_ctx_enqueue_thresholds(lmx_ctx* ctx, int32_t n_frames, const float* thresholds, int32_t n_thresholds,
+                                      const char* const* class_ids, int32_t n_class_ids);
+/* lmx_match, lmx_match_batch and lmx_match_masked with per-class thresholds (see lmx_ctx_enqueue_thresholds). */
+lmx_status lmx_match_thresholds(lmx_ctx* ctx, const lmx_image* sources, int32_t n_sources, const float* thresholds, int32_t n_thresholds,
+                                const char* const* class_ids, int32_t n_class_ids, lmx_match_t* out, size_t cap, size_t* n_out);
+lmx_status lmx_match_batch_thresholds(lmx_ctx* ctx, int32_t n_frames, const lmx_image* sources, int32_t n_sources, const float* thresholds,
+                                      int32_t n_thresholds, const char* const* class_ids, int32_t n_class_ids, lmx_match_t* out, size_t cap,
+                                      size_t* n_out);
+lmx_status lmx_match_masked_thresholds(lmx_ctx* ctx, const lmx_image* sources, const lmx_image* masks, int32_t n_sources, const float* thresholds,
+                                       int32_t n_thresholds, const char* const* class_ids, int32_t n_class_ids, lmx_match_t* out, size_t cap,
+                                       size_t* n_out);
 lmx_status lmx_ctx_collect(lmx_ctx* ctx, int32_t n_frames, lmx_match_t* out, size_t cap, size_t* n_out);
 /* Same, frames packed back to back: frame f's matches are out[offsets[f] .. offsets[f+1]); offsets has n_frames+1 entries. */
 lmx_status lmx_ctx_collect_flat(lmx_ctx* ctx, int32_t n_frames, lmx_match_t* out, size_t cap_total, size_t* offsets);
@@ -424,6 +442,9 @@ lmx_status lmx_group_match_batch(lmx_group* group, int32_t n_frames, const lmx_i
  * following batches:  upload(0); submit(0); loop { upload(i+1); submit(i+1); finish(i); } */
 lmx_status lmx_group_upload(lmx_group* group, int32_t n_frames, const lmx_image* sources, int32_t n_sources);
 lmx_status lmx_group_submit(lmx_group* group, int32_t n_frames, float threshold, const char* const* class_ids, int32_t n_class_ids);
+/* lmx_group_submit with per-class thresholds: every member forwards the same array to lmx_ctx_enqueue_thresholds. */
+lmx_status lmx_group_submit_thresholds(lmx_group* group, int32_t n_frames, const float* thresholds, int32_t n_thresholds,
+                                       const char* const* class_ids, int32_t n_class_ids);
 lmx_status lmx_group_finish(lmx_group* group, int32_t n_frames, lmx_match_t* out, size_t cap, size_t* n_out);
 int32_t lmx_group_depth(const lmx_group* group);
 

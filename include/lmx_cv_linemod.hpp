@@ -238,6 +238,32 @@ class Detector {
   // ---- matching: Detector::match(sources, threshold, matches, class_ids, quantized_images, masks) const -----------------------
   void match(const std::vector<Mat>& sources, float threshold, std::vector<Match>& matches, const std::vector<String>& class_ids = std::vector<String>(),
              OutputArrayOfArrays quantized_images = noArray(), const std::vector<Mat>& masks = std::vector<Mat>()) const {
+    match_any(sources, threshold, NULL, matches, class_ids, quantized_images, masks);
+  }
+  // liblmx extension (no upstream analogue), like load(): a threshold per class (lmx_match_masked_thresholds).  The map's keys are the
+  // classes matched, in map order -- upstream's order for an empty class_ids -- each at its own threshold, as if match() passed
+  // thresholds[class] to every matchClass call; one std::sort + std::unique over everything.  A key the detector does not hold throws;
+  // an empty map matches nothing.
+  void match(const std::vector<Mat>& sources, const std::map<String, float>& thresholds, std::vector<Match>& matches,
+             OutputArrayOfArrays quantized_images = noArray(), const std::vector<Mat>& masks = std::vector<Mat>()) const {
+    matches.clear();
+    if (thresholds.empty()) return;
+    const std::vector<String> known = classIds();
+    std::vector<float> thr(known.size(), 0.f);   // one entry per class index; classes the map lacks are not matched, their entry is not read
+    std::vector<String> ids;
+    for (std::map<String, float>::const_iterator it = thresholds.begin(); it != thresholds.end(); ++it) {
+      size_t k = 0;
+      while (k < known.size() && !(known[k] == it->first)) ++k;
+      if (k == known.size()) LMX_CV_THROW(LMX_ERR_INVALID_ARG, "match: a threshold for a class the detector does not hold");
+      thr[k] = it->second;
+      ids.push_back(it->first);
+    }
+    match_any(sources, 0.f, &thr, matches, ids, quantized_images, masks);
+  }
+
+ private:
+  void match_any(const std::vector<Mat>& sources, float threshold, const std::vector<float>* thresholds, std::vector<Match>& matches,
+                 const std::vector<String>& class_ids, OutputArrayOfArrays quantized_images, const std::vector<Mat>& masks) const {
     matches.clear();
     if (sources.size() != modalities_.size()) LMX_CV_THROW(LMX_ERR_SHAPE, "sources.size() != modalities.size()");  // upstream CV_Assert
     if (!masks.empty() && masks.size() != modalities_.size()) LMX_CV_THROW(LMX_ERR_SHAPE, "masks.size() != modalities.size()");  // upstream CV_Assert
@@ -273,8 +299,10 @@ class Detector {
         CtxLock lock(ctx);   // the context may be shared with another Detector of the same bank (lmx_ctx_acquire): match + read-backs as one unit
         if (buf_.size() < 4096) buf_.resize(4096);   // (under the lock: concurrent match() calls on ONE detector share this buffer)
         size_t n = 0;
-        lmx_status st = lmx_match_masked(ctx, imgs.data(), mimgs.empty() ? NULL : &mimgs[0], (int32_t)imgs.size(), threshold, cids.empty() ? NULL : &cids[0],
-                                         (int32_t)cids.size(), &buf_[0], buf_.size(), &n);
+        lmx_status st = thresholds ? lmx_match_masked_thresholds(ctx, imgs.data(), mimgs.empty() ? NULL : &mimgs[0], (int32_t)imgs.size(), &(*thresholds)[0],
+                                                                 (int32_t)thresholds->size(), &cids[0], (int32_t)cids.size(), &buf_[0], buf_.size(), &n)
+                                   : lmx_match_masked(ctx, imgs.data(), mimgs.empty() ? NULL : &mimgs[0], (int32_t)imgs.size(), threshold, cids.empty() ? NULL : &cids[0],
+                                                      (int32_t)cids.size(), &buf_[0], buf_.size(), &n);
         if (st == LMX_ERR_OVERFLOW && n > buf_.size()) { buf_.resize(n); continue; }  // output buffer too small: retry
         if (st == LMX_ERR_OVERFLOW && attempt < 8) {
           int64_t n_cand = 0, n_raw = 0;
@@ -306,6 +334,8 @@ class Detector {
       if (ctx_[gray]) { lmx_ctx_unref(ctx_[gray]); ctx_[gray] = NULL; }   // outside the lock: the next turn acquires a context with the larger lists
     }
   }
+
+ public:
 
   // ---- training: Detector::addTemplate(sources, class_id, object_mask, bounding_box) -----------------------------------------
   int addTemplate(const std::vector<Mat>& sources, const String& class_id, const Mat& object_mask, Rect* bounding_box = NULL) {

@@ -161,6 +161,36 @@ class Detector {
   // Detector::match.  `matches` is cleared first, like upstream.
   void match(const std::vector<Image>& sources, float threshold, std::vector<Match>& matches,
              const std::vector<std::string>& class_ids = std::vector<std::string>()) {
+    match_any(sources, threshold, nullptr, matches, class_ids);
+  }
+  // liblmx extension (no upstream analogue): a threshold per class (lmx_match_thresholds).  The map's keys are the classes matched, in map
+  // order -- upstream's order for an empty class_ids -- each at its own threshold, as if Detector::match passed thresholds[class] to every
+  // matchClass call; one std::sort + std::unique over everything.  A key the bank does not hold throws; an empty map matches nothing.
+  void match(const std::vector<Image>& sources, const std::map<std::string, float>& thresholds, std::vector<Match>& matches) {
+    matches.clear();
+    if (thresholds.empty()) return;
+    std::vector<std::string> ids;
+    const std::vector<float> thr = class_thresholds(thresholds, &ids);
+    match_any(sources, 0.f, &thr, matches, ids);
+  }
+
+ private:
+  // the map as lmx_ctx_enqueue_thresholds takes it: one entry per class index (classes the map lacks are not matched, their entry is not
+  // read), and the keys in map order as the class_ids list
+  std::vector<float> class_thresholds(const std::map<std::string, float>& thresholds, std::vector<std::string>* ids) const {
+    const std::vector<std::string> known = classIds();
+    std::vector<float> thr(known.size(), 0.f);
+    for (const std::pair<const std::string, float>& kv : thresholds) {
+      size_t k = 0;
+      while (k < known.size() && known[k] != kv.first) ++k;
+      if (k == known.size()) throw Exception(LMX_ERR_INVALID_ARG, ("match: a threshold for class \"" + kv.first + "\", which the detector does not hold").c_str());
+      thr[k] = kv.second;
+      ids->push_back(kv.first);
+    }
+    return thr;
+  }
+  void match_any(const std::vector<Image>& sources, float threshold, const std::vector<float>* thresholds, std::vector<Match>& matches,
+                 const std::vector<std::string>& class_ids) {
     matches.clear();
     if (sources.empty()) throw Exception(LMX_ERR_SHAPE, "match: no sources");
     std::vector<lmx_image> imgs;
@@ -175,8 +205,10 @@ class Detector {
     for (int attempt = 0;; ++attempt) {
       ensure_ctx(sources[0].cols, sources[0].rows, gray);
       size_t n = 0;
-      lmx_status st = lmx_match(ctx_, imgs.data(), (int)imgs.size(), threshold, cids.empty() ? nullptr : cids.data(), (int)cids.size(),
-                                buf_.data(), buf_.size(), &n);
+      lmx_status st = thresholds ? lmx_match_thresholds(ctx_, imgs.data(), (int)imgs.size(), thresholds->data(), (int32_t)thresholds->size(), cids.data(), (int)cids.size(),
+                                                        buf_.data(), buf_.size(), &n)
+                                 : lmx_match(ctx_, imgs.data(), (int)imgs.size(), threshold, cids.empty() ? nullptr : cids.data(), (int)cids.size(),
+                                             buf_.data(), buf_.size(), &n);
       if (st == LMX_ERR_OVERFLOW && n > buf_.size()) { buf_.resize(n); continue; }  // output buffer too small: retry
       if (st == LMX_ERR_OVERFLOW && attempt < 8) {
         // the device's candidate / match lists overflowed (upstream has no such limit): rebuild the context with lists sized from
@@ -199,6 +231,7 @@ class Detector {
     }
   }
 
+ public:
 #ifdef LMX_HAVE_OPENCV
   static Image view(const cv::Mat& m) { return Image{m.data, m.rows, m.cols, m.channels(), (int)m.elemSize1(), m.step[0]}; }
   void match(const std::vector<cv::Mat>& sources, float threshold, std::vector<Match>& matches,
@@ -206,6 +239,11 @@ class Detector {
     std::vector<Image> v;
     for (const cv::Mat& m : sources) v.push_back(view(m));
     match(v, threshold, matches, class_ids);
+  }
+  void match(const std::vector<cv::Mat>& sources, const std::map<std::string, float>& thresholds, std::vector<Match>& matches) {
+    std::vector<Image> v;
+    for (const cv::Mat& m : sources) v.push_back(view(m));
+    match(v, thresholds, matches);
   }
 #endif
 
@@ -229,11 +267,19 @@ class Detector {
   ClassClusters collectClustersClasses(const std::vector<std::vector<Image> >& frames, float threshold, DepthTemplates* templates = nullptr,
                                        const std::vector<int32_t>& class_base = std::vector<int32_t>(), const std::vector<Image>& depth = std::vector<Image>(),
                                        bool normals = false, double no_value = -HUGE_VAL, size_t capacity = 1 << 16);
+  // The same with a threshold per class in front of the chain (see the match overload): the map's keys are the classes matched
+  ClassClusters collectClustersClasses(const std::vector<std::vector<Image> >& frames, const std::map<std::string, float>& thresholds,
+                                       DepthTemplates* templates = nullptr, const std::vector<int32_t>& class_base = std::vector<int32_t>(),
+                                       const std::vector<Image>& depth = std::vector<Image>(), bool normals = false, double no_value = -HUGE_VAL,
+                                       size_t capacity = 1 << 16);
 
   lmx_bank* bank() const { return bank_; }
   lmx_ctx* context() const { return ctx_; }
 
  private:
+  ClassClusters collect_clusters_classes(const std::vector<std::vector<Image> >& frames, float threshold, const std::map<std::string, float>* thresholds,
+                                         DepthTemplates* templates, const std::vector<int32_t>& class_base, const std::vector<Image>& depth, bool normals,
+                                         double no_value, size_t capacity);
   struct ClassSidecar { std::vector<double> dists; std::vector<int32_t> rects; lmx_cluster_params params; };
   std::map<int, ClassSidecar> sidecars_;
   void reset() {
@@ -379,6 +425,17 @@ class DepthTemplates {
 inline ClassClusters Detector::collectClustersClasses(const std::vector<std::vector<Image> >& frames, float threshold, DepthTemplates* templates,
                                                       const std::vector<int32_t>& class_base, const std::vector<Image>& depth, bool normals, double no_value,
                                                       size_t capacity) {
+  return collect_clusters_classes(frames, threshold, nullptr, templates, class_base, depth, normals, no_value, capacity);
+}
+inline ClassClusters Detector::collectClustersClasses(const std::vector<std::vector<Image> >& frames, const std::map<std::string, float>& thresholds,
+                                                      DepthTemplates* templates, const std::vector<int32_t>& class_base, const std::vector<Image>& depth, bool normals,
+                                                      double no_value, size_t capacity) {
+  if (thresholds.empty()) throw Exception(LMX_ERR_INVALID_ARG, "collectClustersClasses: an empty threshold map matches no class");
+  return collect_clusters_classes(frames, 0.f, &thresholds, templates, class_base, depth, normals, no_value, capacity);
+}
+inline ClassClusters Detector::collect_clusters_classes(const std::vector<std::vector<Image> >& frames, float threshold, const std::map<std::string, float>* thresholds,
+                                                        DepthTemplates* templates, const std::vector<int32_t>& class_base, const std::vector<Image>& depth,
+                                                        bool normals, double no_value, size_t capacity) {
   if (frames.empty() || frames[0].empty()) throw Exception(LMX_ERR_SHAPE, "collectClustersClasses: no frames");
   if (templates && (class_base.size() < 2 || depth.size() != frames.size())) throw Exception(LMX_ERR_SHAPE, "collectClustersClasses: class_base needs one entry per class plus one, depth one image per frame");
   const int n = (int)frames.size();
@@ -389,7 +446,15 @@ inline ClassClusters Detector::collectClustersClasses(const std::vector<std::vec
   }
   ensure_ctx(frames[0][0].cols, frames[0][0].rows, false);
   check(lmx_ctx_upload(ctx_, n, imgs.data(), (int32_t)frames[0].size()));
-  check(lmx_ctx_enqueue(ctx_, n, threshold, nullptr, 0));
+  if (thresholds) {
+    std::vector<std::string> ids;
+    const std::vector<float> thr = class_thresholds(*thresholds, &ids);
+    std::vector<const char*> cids;
+    for (const std::string& c : ids) cids.push_back(c.c_str());
+    check(lmx_ctx_enqueue_thresholds(ctx_, n, thr.data(), (int32_t)thr.size(), cids.data(), (int32_t)cids.size()));
+  } else {
+    check(lmx_ctx_enqueue(ctx_, n, threshold, nullptr, 0));
+  }
   ClassClusters out;
   out.matches.resize(capacity); out.clusters.resize(capacity); out.cluster_class.resize(capacity); out.members.resize(capacity);
   out.match_offsets.assign((size_t)n + 1, 0); out.cluster_offsets.assign((size_t)n + 1, 0);

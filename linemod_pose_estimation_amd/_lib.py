@@ -28,6 +28,7 @@ SYMBOLS = [
     "lmx_ctx_collect_clusters_depth_normal", "lmx_debug_scene_normals", "lmx_depth_templates_set_profiling", "lmx_depth_templates_kernel_time",
     "lmx_cluster_matches_classes", "lmx_ctx_set_cluster_sidecar_class", "lmx_ctx_collect_clusters_classes", "lmx_depth_templates_append",
     "lmx_debug_device_finalize_cluster_classes",
+    "lmx_ctx_enqueue_thresholds", "lmx_match_thresholds", "lmx_match_batch_thresholds", "lmx_match_masked_thresholds", "lmx_group_submit_thresholds",
 ]
 
 (LMX_OK, LMX_ERR_INVALID_ARG, LMX_ERR_SHAPE, LMX_ERR_NO_DEVICE, LMX_ERR_HIP, LMX_ERR_OVERFLOW, LMX_ERR_IO,
@@ -242,6 +243,14 @@ def lib():
     L.lmx_host_free.restype = None
     L.lmx_ctx_upload_raw.argtypes = [vp, C.c_int32, C.POINTER(Image), C.c_int32, C.POINTER(PreDesc)]
     L.lmx_ctx_enqueue.argtypes = [vp, C.c_int32, C.c_float, C.POINTER(C.c_char_p), C.c_int32]
+    f32p = C.POINTER(C.c_float)
+    L.lmx_ctx_enqueue_thresholds.argtypes = [vp, C.c_int32, f32p, C.c_int32, C.POINTER(C.c_char_p), C.c_int32]
+    L.lmx_match_thresholds.argtypes = [vp, C.POINTER(Image), C.c_int32, f32p, C.c_int32, C.POINTER(C.c_char_p), C.c_int32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.lmx_match_batch_thresholds.argtypes = [vp, C.c_int32, C.POINTER(Image), C.c_int32, f32p, C.c_int32, C.POINTER(C.c_char_p), C.c_int32, vp, C.c_size_t,
+                                             C.POINTER(C.c_size_t)]
+    L.lmx_match_masked_thresholds.argtypes = [vp, C.POINTER(Image), C.POINTER(Image), C.c_int32, f32p, C.c_int32, C.POINTER(C.c_char_p), C.c_int32, vp, C.c_size_t,
+                                              C.POINTER(C.c_size_t)]
+    L.lmx_group_submit_thresholds.argtypes = [vp, C.c_int32, f32p, C.c_int32, C.POINTER(C.c_char_p), C.c_int32]
     L.lmx_ctx_collect.argtypes = [vp, C.c_int32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.lmx_ctx_collect_flat.argtypes = [vp, C.c_int32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.lmx_ctx_raw_matches.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]

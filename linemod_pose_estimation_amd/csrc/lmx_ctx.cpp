@@ -384,6 +384,7 @@ void lmx_ctx_destroy(lmx_ctx* c) {
   if (c->h_f2_ndiffs) (void)hipHostFree(c->h_f2_ndiffs);
   if (c->d_f2_rec_ndiffs) (void)hipFree(c->d_f2_rec_ndiffs);
   if (c->h_mask_stage) (void)hipHostFree(c->h_mask_stage);
+  if (c->h_class_thr) (void)hipHostFree(c->h_class_thr);
   if (c->mask_h2d) (void)hipEventDestroy(c->mask_h2d);
   if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
   delete c;

@@ -167,6 +167,12 @@ struct lmx_ctx {
   int32_t* d_class_slot = nullptr;
   std::vector<int32_t> cur_slots;
   uint8_t* d_normal_bins = nullptr;  // the bank's NORMAL_LUT as median bins (k_depth_quantize)
+  // Per-class thresholds (lmx_ctx_enqueue_thresholds): one table of n_classes entries per OUTPUT SLOT, written on the slot's lane in front of
+  // the chain that reads it, so that up to n_slots enqueues with different thresholds are in flight without a host-side wait.  Allocated by
+  // the first such enqueue; slot_class_thr[k] is what slot k's table holds
+  ClassThreshold* d_class_thr = nullptr;   // [kSlots][max(1, n_classes)]
+  ClassThreshold* h_class_thr = nullptr;   // pinned mirror, the source of the stream-ordered copies
+  std::vector<ClassThreshold> slot_class_thr[2 * kLanes];
   // outputs
   Candidate* d_cands = nullptr;
   // Output slots (two per lane) so that enqueues can run while earlier ones are being collected on the host.
@@ -198,7 +204,7 @@ struct lmx_ctx {
   size_t h_stage_bytes = 0;    // per frame set
   size_t frame_bytes[kMaxModalities] = {0, 0, 0, 0};
   // hipGraph cache (LMX_CTX_HIPGRAPH)
-  struct GraphEntry { int slot; int set; int n_frames; uint32_t threshold_bits; hipGraphExec_t exec; };
+  struct GraphEntry { int slot; int set; int n_frames; uint32_t threshold_bits; hipGraphExec_t exec; bool per_class; };   // per_class: the chain reads the slot's table, threshold_bits is 0
   std::vector<GraphEntry> graphs;
   // device form of finalise + cluster (lmx_ctx_collect_clusters): side-car and output buffers, allocated on first use
   double* d_f2_dists = nullptr;

@@ -87,13 +87,14 @@ static lmx_status issue_pre(lmx_ctx* c, int32_t n_frames, hipStream_t s) {
 }
 
 // Stage 2 (matching): score, refine, queue the read-back (the slot header was cleared by the first kernel of stage 1).
-static lmx_status issue_post(lmx_ctx* c, int slot, int32_t n_frames, float threshold, hipStream_t s) {
+// thr_tab: the slot's per-class threshold table (lmx_ctx_enqueue_thresholds) or null; with a table `threshold` is not read.
+static lmx_status issue_post(lmx_ctx* c, int slot, int32_t n_frames, float threshold, hipStream_t s, const ClassThreshold* thr_tab) {
   c->cur_stream = s;
   {
     const uint8_t* lm_mod[kMaxModalities] = {nullptr, nullptr, nullptr, nullptr};
     for (int m = 0; m < c->M; ++m) lm_mod[m] = c->kp.fb.lmn[m];
     ScopedKernel k(c, K_SCORE_COARSE);
-    launch_score_coarse(s, c->dbank, c->kp.geom[c->L - 1], lm_mod, n_frames, threshold, c->d_class_slot, c->d_cands, c->d_cand_count(), c->cap_total, c->stripes_for(n_frames));
+    launch_score_coarse(s, c->dbank, c->kp.geom[c->L - 1], lm_mod, n_frames, threshold, c->d_class_slot, c->d_cands, c->d_cand_count(), c->cap_total, c->stripes_for(n_frames), thr_tab);
   }
   bool published;
   {
@@ -113,7 +114,7 @@ static lmx_status issue_post(lmx_ctx* c, int slot, int32_t n_frames, float thres
     ScopedKernel k(c, K_REFINE);
     published = launch_refine(s, c->dbank, c->kp, n_frames, threshold, c->d_class_slot, c->d_cands, c->d_cand_count(), c->cap_total, c->stripes_for(n_frames), c->d_records(),
                               c->d_match_count(), fold ? c->h_out_dev[slot] : nullptr, c->d_out, c->d_pub_counter + slot,
-                              (uint32_t)std::min<size_t>(c->h_out_records, lmx_ctx::kFirstSlice), seq);
+                              (uint32_t)std::min<size_t>(c->h_out_records, lmx_ctx::kFirstSlice), seq, thr_tab);
     published = published && fold;
     if (published) c->pub_seq[slot] = seq;
   }
@@ -134,7 +135,8 @@ static bool small_chain_ok(const lmx_ctx* c, int n_frames) {
   return !c->env.no_small_chain;   // A/B switch (LMX_NO_SMALL_CHAIN, read when the context was created)
 }
 
-static lmx_status issue_small(lmx_ctx* c, int slot, int32_t n_frames, float threshold, hipStream_t s, lmx_ctx::FrameSet& fs, const lmx_image* sources) {
+static lmx_status issue_small(lmx_ctx* c, int slot, int32_t n_frames, float threshold, hipStream_t s, lmx_ctx::FrameSet& fs, const lmx_image* sources,
+                              const ClassThreshold* thr_tab) {
   c->cur_stream = s;
   const LevelGeom &g0 = c->kp.geom[0], &g1 = c->kp.geom[1];
   const lmx_modality_desc& cg = c->bank->mods[0];
@@ -186,7 +188,7 @@ static lmx_status issue_small(lmx_ctx* c, int slot, int32_t n_frames, float thre
     }
     for (int l = 0; l < 2 && !fused; ++l) issue_spread_level(c, s, l, n_frames);   // no fused kernel for this pair of T / these widths: level by level, like issue_pre
     LMX_HIP(hipGetLastError());
-    return issue_post(c, slot, n_frames, threshold, s);
+    return issue_post(c, slot, n_frames, threshold, s, thr_tab);
   };
 
   if (sources && !stream) { store_modality(c, fs, 0, n_frames, sources); lap(lmx_ctx::TM_STORE_COLOR); }
@@ -270,17 +272,19 @@ static lmx_status capture_graph(const lmx_ctx* c, hipStream_t s, hipGraphExec_t*
 }
 
 // The executable graph of the whole per-batch chain for (output slot, frame set, batch size, threshold); captured on first use.
-// Expects the lane of `slot` selected and c->d_out pointing at the slot.
-static lmx_status ensure_graph(lmx_ctx* c, int slot, int set, int32_t n_frames, float threshold, hipStream_t sa, hipGraphExec_t* out) {
-  uint32_t tbits;
-  std::memcpy(&tbits, &threshold, 4);
+// Expects the lane of `slot` selected and c->d_out pointing at the slot.  With thr_tab (the slot's per-class table) the key is (slot, set,
+// batch size, "per class"): the captured kernels read the thresholds from the table, which every enqueue rewrites in front of the replay.
+static lmx_status ensure_graph(lmx_ctx* c, int slot, int set, int32_t n_frames, float threshold, hipStream_t sa, hipGraphExec_t* out, const ClassThreshold* thr_tab) {
+  uint32_t tbits = 0;
+  if (!thr_tab) std::memcpy(&tbits, &threshold, 4);
+  const bool per_class = thr_tab != nullptr;
   for (const lmx_ctx::GraphEntry& ge : c->graphs)
-    if (ge.slot == slot && ge.set == set && ge.n_frames == n_frames && ge.threshold_bits == tbits) { *out = ge.exec; return LMX_OK; }
+    if (ge.slot == slot && ge.set == set && ge.n_frames == n_frames && ge.threshold_bits == tbits && ge.per_class == per_class) { *out = ge.exec; return LMX_OK; }
   std::unique_lock<std::shared_mutex> capture_lock(g_capture_mutex);
   hipGraphExec_t exec = nullptr;
   lmx_status st = capture_graph(c, sa, &exec, [&]() {
     lmx_status r = issue_pre(c, n_frames, sa);
-    return r != LMX_OK ? r : issue_post(c, slot, n_frames, threshold, sa);
+    return r != LMX_OK ? r : issue_post(c, slot, n_frames, threshold, sa, thr_tab);
   });
   if (st != LMX_OK) return st;
   if (c->graphs.size() >= 64) {
@@ -288,14 +292,26 @@ static lmx_status ensure_graph(lmx_ctx* c, int slot, int set, int32_t n_frames, 
     (void)hipGraphExecDestroy(c->graphs.front().exec);
     c->graphs.erase(c->graphs.begin());
   }
-  c->graphs.push_back(lmx_ctx::GraphEntry{slot, set, n_frames, tbits, exec});
+  c->graphs.push_back(lmx_ctx::GraphEntry{slot, set, n_frames, tbits, exec, per_class});
   *out = exec;
+  return LMX_OK;
+}
+
+// The per-class tables, one per output slot, and their pinned host mirrors: allocated by the first enqueue that brings thresholds.
+static lmx_status ensure_class_thr(lmx_ctx* c) {
+  if (c->d_class_thr) return LMX_OK;
+  const size_t n = (size_t)lmx_ctx::kSlots * (size_t)std::max(1, c->n_classes);
+  LMX_HIP(hipHostMalloc((void**)&c->h_class_thr, n * sizeof(ClassThreshold), hipHostMallocDefault));
+  ClassThreshold* d = nullptr;
+  lmx_status st = dev_alloc(c, &d, n, false);
+  if (st != LMX_OK) return st;
+  c->d_class_thr = d;
   return LMX_OK;
 }
 
 // Device groups call this for every member from the calling thread before their host threads enqueue in parallel: the capture of a
 // chain that is not cached yet then happens here, with no other thread of the group inside the HIP runtime (see g_capture_mutex).
-lmx_status lmx::ctx_prepare_graph(lmx_ctx* c, int n_frames, float threshold) {
+lmx_status lmx::ctx_prepare_graph(lmx_ctx* c, int n_frames, float threshold, bool per_class) {
   if (!(c->desc.flags & LMX_CTX_HIPGRAPH) || c->profiling != 0) return LMX_OK;
   if (n_frames < 1 || n_frames > c->F || c->outstanding >= c->n_slots) return LMX_OK;   // the enqueue reports it
   for (int m = 0; m < c->M; ++m)
@@ -305,14 +321,19 @@ lmx_status lmx::ctx_prepare_graph(lmx_ctx* c, int n_frames, float threshold) {
   select_lane(c, lane);
   c->d_out = c->d_out_slot[slot];
   hipGraphExec_t exec = nullptr;
-  return ensure_graph(c, slot, c->cur_set, n_frames, threshold, c->lane_stream[lane], &exec);
+  const ClassThreshold* thr_tab = nullptr;
+  if (per_class) {
+    const lmx_status st = ensure_class_thr(c);
+    if (st != LMX_OK) return st;
+    thr_tab = c->d_class_thr + (size_t)slot * (size_t)std::max(1, c->n_classes);
+  }
+  return ensure_graph(c, slot, c->cur_set, n_frames, threshold, c->lane_stream[lane], &exec, thr_tab);
 }
 
-extern "C" {
-
-lmx_status lmx_ctx_enqueue(lmx_ctx* c, int32_t n_frames, float threshold, const char* const* class_ids, int32_t n_class_ids) {
-  return lmx::guarded("lmx_ctx_enqueue", [&]() -> lmx_status {
-  if (!c) { set_error("lmx_ctx_enqueue: null context"); return LMX_ERR_INVALID_ARG; }
+// lmx_ctx_enqueue (thresholds null: `threshold` for every class) and lmx_ctx_enqueue_thresholds (thresholds[k] for class index k, checked by
+// the caller) are one code path: the per-class form only adds the slot's table and hands it down the chain.
+static lmx_status enqueue_chain(lmx_ctx* c, int32_t n_frames, float threshold, const float* thresholds, const char* const* class_ids, int32_t n_class_ids) {
+  const char* const who = thresholds ? "lmx_ctx_enqueue_thresholds" : "lmx_ctx_enqueue";
   if (n_frames < 1 || n_frames > c->F) { set_error("n_frames=%d outside [1,%d]", n_frames, c->F); return LMX_ERR_INVALID_ARG; }
   std::shared_lock<std::shared_mutex> launch_lock(g_capture_mutex);
   LMX_HIP(hipSetDevice(c->device));
@@ -332,7 +353,7 @@ lmx_status lmx_ctx_enqueue(lmx_ctx* c, int32_t n_frames, float threshold, const 
     c->cur_slots = slots;
   }
   if (c->outstanding >= c->n_slots) {
-    set_error("lmx_ctx_enqueue: %d enqueues are already outstanding; collect one first", c->outstanding);
+    set_error("%s: %d enqueues are already outstanding; collect one first", who, c->outstanding);
     return LMX_ERR_INVALID_ARG;
   }
   const int slot = c->head;
@@ -345,10 +366,28 @@ lmx_status lmx_ctx_enqueue(lmx_ctx* c, int32_t n_frames, float threshold, const 
   const int set = c->cur_set;
   lmx_ctx::FrameSet& fset = c->sets[set];
   if (n_frames > fset.n_uploaded) {
-    set_error("lmx_ctx_enqueue: n_frames=%d but the most recent upload holds %d frame(s); an enqueue reads the frames of the latest upload", n_frames, fset.n_uploaded);
+    set_error("%s: n_frames=%d but the most recent upload holds %d frame(s); an enqueue reads the frames of the latest upload", who, n_frames, fset.n_uploaded);
     return LMX_ERR_INVALID_ARG;
   }
   if (fset.h2d_recorded) LMX_HIP(hipStreamWaitEvent(sa, fset.h2d_done, 0));
+  // Per-class thresholds: one table per output slot, written on the lane's stream in front of the chain that reads it, so enqueues still
+  // outstanding (other slots, other tables) are not disturbed and nothing waits on the host.  The slot is free, so the last copy out of its
+  // pinned mirror has finished; a table that already holds these values is left alone.
+  const ClassThreshold* thr_tab = nullptr;
+  if (thresholds) {
+    lmx_status tst = ensure_class_thr(c);
+    if (tst != LMX_OK) return tst;
+    const size_t nc = (size_t)c->n_classes, at = (size_t)slot * std::max<size_t>(1, nc);
+    std::vector<ClassThreshold> tab(nc);
+    for (size_t k = 0; k < nc; ++k) { tab[k].threshold = thresholds[k]; tab[k].frac = thresholds[k] / 100.f; }
+    std::vector<ClassThreshold>& held = c->slot_class_thr[slot];
+    if (nc > 0 && (held.size() != nc || std::memcmp(held.data(), tab.data(), nc * sizeof(ClassThreshold)) != 0)) {
+      std::memcpy(c->h_class_thr + at, tab.data(), nc * sizeof(ClassThreshold));
+      LMX_HIP(hipMemcpyAsync(c->d_class_thr + at, c->h_class_thr + at, nc * sizeof(ClassThreshold), hipMemcpyHostToDevice, sa));
+      held = tab;
+    }
+    thr_tab = c->d_class_thr + at;
+  }
   // Buffer hazards: a lane's intermediates are rewritten by every enqueue on it, in stream order; outputs are per slot.
   bool masked = false;   // masks are rare: the batch then takes the plain chain (no graph, no fused small-batch launches)
   for (int m = 0; m < c->M; ++m) masked = masked || fset.masked[m];
@@ -356,7 +395,7 @@ lmx_status lmx_ctx_enqueue(lmx_ctx* c, int32_t n_frames, float threshold, const 
     // the whole per-batch chain (memset, kernels, read-back) as ONE graph launch; captured once per (slot, n_frames, threshold)
     hipGraphExec_t exec = nullptr;
     launch_lock.unlock();
-    lmx_status gst = ensure_graph(c, slot, set, n_frames, threshold, sa, &exec);
+    lmx_status gst = ensure_graph(c, slot, set, n_frames, threshold, sa, &exec, thr_tab);
     if (gst != LMX_OK) return gst;
     launch_lock.lock();
     LMX_HIP(hipGraphLaunch(exec, sa));
@@ -367,7 +406,7 @@ lmx_status lmx_ctx_enqueue(lmx_ctx* c, int32_t n_frames, float threshold, const 
     if (!src && c->deferred_sources)   // an enqueue for fewer frames than were handed over: store them all first
       for (int m = 0; m < c->M; ++m) store_modality(c, fset, m, c->deferred_frames, c->deferred_sources);
     c->deferred_sources = nullptr; c->deferred_frames = 0;
-    lmx_status st = issue_small(c, slot, n_frames, threshold, sa, fset, src);
+    lmx_status st = issue_small(c, slot, n_frames, threshold, sa, fset, src, thr_tab);
     if (st != LMX_OK) return st;
     // recorded behind the whole chain: an event between two kernels of one stream costs a 5-6 us bubble, a third of what a
     // kernel of this chain takes, and nothing waits to overwrite the set of a one-frame call
@@ -380,7 +419,7 @@ lmx_status lmx_ctx_enqueue(lmx_ctx* c, int32_t n_frames, float threshold, const 
     lmx_status st = issue_pre(c, n_frames, sa);
     // the level-0 quantisers are the only readers of the uploaded frames: the set may be overwritten from here on
     if (st == LMX_OK) LMX_HIP(hipEventRecord(fset.read_done[lane], sa));
-    if (st == LMX_OK) st = issue_post(c, slot, n_frames, threshold, sa);
+    if (st == LMX_OK) st = issue_post(c, slot, n_frames, threshold, sa, thr_tab);
     if (st != LMX_OK) return st;
   }
   fset.read_recorded[lane] = true;
@@ -391,13 +430,19 @@ lmx_status lmx_ctx_enqueue(lmx_ctx* c, int32_t n_frames, float threshold, const 
   c->head = (slot + 1) % c->n_slots;
   c->outstanding += 1;
   return LMX_OK;
-  });
 }
 
-lmx_status lmx_match_batch(lmx_ctx* c, int32_t n_frames, const lmx_image* sources, int32_t n_sources, float threshold,
-                           const char* const* class_ids, int32_t n_class_ids, lmx_match_t* out, size_t cap, size_t* n_out) {
-  return lmx::guarded("lmx_match_batch", [&]() -> lmx_status {
-  if (!c) { set_error("lmx_match: null context"); return LMX_ERR_INVALID_ARG; }
+// thresholds[k] for class index k (the entry points refuse a null array first): one entry per class of the bank, and no entry is a NaN
+static lmx_status check_thresholds(const char* who, const lmx_ctx* c, const float* thresholds, int32_t n_thresholds) {
+  if (n_thresholds != c->n_classes) { set_error("%s: %d thresholds for a bank of %d classes (one per class index, in lmx_bank_class_id order)", who, n_thresholds, c->n_classes); return LMX_ERR_INVALID_ARG; }
+  for (int k = 0; k < n_thresholds; ++k)
+    if (thresholds[k] != thresholds[k]) { set_error("%s: the threshold of class %d (\"%s\") is not a number", who, k, c->class_names[(size_t)k].c_str()); return LMX_ERR_INVALID_ARG; }
+  return LMX_OK;
+}
+
+// The synchronous composite behind lmx_match_batch (thresholds null) and lmx_match_batch_thresholds
+static lmx_status match_batch_chain(lmx_ctx* c, int32_t n_frames, const lmx_image* sources, int32_t n_sources, float threshold, const float* thresholds,
+                                    int32_t n_thresholds, const char* const* class_ids, int32_t n_class_ids, lmx_match_t* out, size_t cap, size_t* n_out) {
   std::lock_guard<std::recursive_mutex> lk(c->call_mutex);   // contexts handed out by lmx_ctx_acquire may be shared between threads
   c->deferred_sources = nullptr;
   c->deferred_frames = -1;   // "upload may leave the direct stores of a small batch to the enqueue below" (the sources outlive both calls)
@@ -405,7 +450,8 @@ lmx_status lmx_match_batch(lmx_ctx* c, int32_t n_frames, const lmx_image* source
   lmx_status st = lmx_ctx_upload(c, n_frames, sources, n_sources);
   if (c->env.match_trace) { c->tm_acc[lmx_ctx::TM_UPLOAD] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_call).count(); c->tm_n += 1; }
   if (c->deferred_frames == -1) c->deferred_frames = 0;
-  if (st == LMX_OK) st = lmx_ctx_enqueue(c, n_frames, threshold, class_ids, n_class_ids);
+  if (st == LMX_OK) st = thresholds ? lmx_ctx_enqueue_thresholds(c, n_frames, thresholds, n_thresholds, class_ids, n_class_ids)
+                                    : lmx_ctx_enqueue(c, n_frames, threshold, class_ids, n_class_ids);
   if (c->deferred_sources) {   // the enqueue failed before it consumed them: the set must still hold what upload promised
     lmx_ctx::FrameSet& fs = c->sets[c->cur_set];
     for (int m = 0; m < c->M; ++m) store_modality(c, fs, m, c->deferred_frames, c->deferred_sources);
@@ -414,6 +460,70 @@ lmx_status lmx_match_batch(lmx_ctx* c, int32_t n_frames, const lmx_image* source
   c->deferred_frames = 0;
   if (st != LMX_OK) return st;
   return lmx_ctx_collect(c, n_frames, out, cap, n_out);
+}
+
+static lmx_status match_masked_chain(lmx_ctx* c, const lmx_image* sources, const lmx_image* masks, int32_t n_sources, float threshold, const float* thresholds,
+                                     int32_t n_thresholds, const char* const* class_ids, int32_t n_class_ids, lmx_match_t* out, size_t cap, size_t* n_out) {
+  if (!masks) return match_batch_chain(c, 1, sources, n_sources, threshold, thresholds, n_thresholds, class_ids, n_class_ids, out, cap, n_out);
+  std::lock_guard<std::recursive_mutex> lk(c->call_mutex);
+  lmx_status st = lmx_ctx_upload(c, 1, sources, n_sources);
+  if (st == LMX_OK) st = lmx_ctx_upload_masks(c, 1, masks, n_sources);
+  if (st == LMX_OK) st = thresholds ? lmx_ctx_enqueue_thresholds(c, 1, thresholds, n_thresholds, class_ids, n_class_ids) : lmx_ctx_enqueue(c, 1, threshold, class_ids, n_class_ids);
+  if (st != LMX_OK) return st;
+  return lmx_ctx_collect(c, 1, out, cap, n_out);
+}
+
+extern "C" {
+
+lmx_status lmx_ctx_enqueue(lmx_ctx* c, int32_t n_frames, float threshold, const char* const* class_ids, int32_t n_class_ids) {
+  return lmx::guarded("lmx_ctx_enqueue", [&]() -> lmx_status {
+  if (!c) { set_error("lmx_ctx_enqueue: null context"); return LMX_ERR_INVALID_ARG; }
+  return enqueue_chain(c, n_frames, threshold, nullptr, class_ids, n_class_ids);
+  });
+}
+
+lmx_status lmx_ctx_enqueue_thresholds(lmx_ctx* c, int32_t n_frames, const float* thresholds, int32_t n_thresholds, const char* const* class_ids, int32_t n_class_ids) {
+  return lmx::guarded("lmx_ctx_enqueue_thresholds", [&]() -> lmx_status {
+  if (!thresholds) { set_error("lmx_ctx_enqueue_thresholds: null thresholds array"); return LMX_ERR_INVALID_ARG; }
+  if (!c) { set_error("lmx_ctx_enqueue_thresholds: null context"); return LMX_ERR_INVALID_ARG; }
+  const lmx_status st = check_thresholds("lmx_ctx_enqueue_thresholds", c, thresholds, n_thresholds);
+  if (st != LMX_OK) return st;
+  return enqueue_chain(c, n_frames, 0.f, thresholds, class_ids, n_class_ids);
+  });
+}
+
+lmx_status lmx_match_batch(lmx_ctx* c, int32_t n_frames, const lmx_image* sources, int32_t n_sources, float threshold,
+                           const char* const* class_ids, int32_t n_class_ids, lmx_match_t* out, size_t cap, size_t* n_out) {
+  return lmx::guarded("lmx_match_batch", [&]() -> lmx_status {
+  if (!c) { set_error("lmx_match: null context"); return LMX_ERR_INVALID_ARG; }
+  return match_batch_chain(c, n_frames, sources, n_sources, threshold, nullptr, 0, class_ids, n_class_ids, out, cap, n_out);
+  });
+}
+
+lmx_status lmx_match_batch_thresholds(lmx_ctx* c, int32_t n_frames, const lmx_image* sources, int32_t n_sources, const float* thresholds, int32_t n_thresholds,
+                                      const char* const* class_ids, int32_t n_class_ids, lmx_match_t* out, size_t cap, size_t* n_out) {
+  return lmx::guarded("lmx_match_batch_thresholds", [&]() -> lmx_status {
+  if (!thresholds) { set_error("lmx_match_batch_thresholds: null thresholds array"); return LMX_ERR_INVALID_ARG; }
+  if (!c) { set_error("lmx_match_batch_thresholds: null context"); return LMX_ERR_INVALID_ARG; }
+  const lmx_status st = check_thresholds("lmx_match_batch_thresholds", c, thresholds, n_thresholds);   // before anything is uploaded
+  if (st != LMX_OK) return st;
+  return match_batch_chain(c, n_frames, sources, n_sources, 0.f, thresholds, n_thresholds, class_ids, n_class_ids, out, cap, n_out);
+  });
+}
+
+lmx_status lmx_match_thresholds(lmx_ctx* c, const lmx_image* sources, int32_t n_sources, const float* thresholds, int32_t n_thresholds, const char* const* class_ids,
+                                int32_t n_class_ids, lmx_match_t* out, size_t cap, size_t* n_out) {
+  return lmx_match_batch_thresholds(c, 1, sources, n_sources, thresholds, n_thresholds, class_ids, n_class_ids, out, cap, n_out);
+}
+
+lmx_status lmx_match_masked_thresholds(lmx_ctx* c, const lmx_image* sources, const lmx_image* masks, int32_t n_sources, const float* thresholds, int32_t n_thresholds,
+                                       const char* const* class_ids, int32_t n_class_ids, lmx_match_t* out, size_t cap, size_t* n_out) {
+  return lmx::guarded("lmx_match_masked_thresholds", [&]() -> lmx_status {
+  if (!thresholds) { set_error("lmx_match_masked_thresholds: null thresholds array"); return LMX_ERR_INVALID_ARG; }
+  if (!c) { set_error("lmx_match_masked_thresholds: null context"); return LMX_ERR_INVALID_ARG; }
+  const lmx_status st = check_thresholds("lmx_match_masked_thresholds", c, thresholds, n_thresholds);
+  if (st != LMX_OK) return st;
+  return match_masked_chain(c, sources, masks, n_sources, 0.f, thresholds, n_thresholds, class_ids, n_class_ids, out, cap, n_out);
   });
 }
 
@@ -431,13 +541,7 @@ lmx_status lmx_match_masked(lmx_ctx* c, const lmx_image* sources, const lmx_imag
                             int32_t n_class_ids, lmx_match_t* out, size_t cap, size_t* n_out) {
   return lmx::guarded("lmx_match_masked", [&]() -> lmx_status {
   if (!c) { set_error("lmx_match_masked: null context"); return LMX_ERR_INVALID_ARG; }
-  if (!masks) return lmx_match(c, sources, n_sources, threshold, class_ids, n_class_ids, out, cap, n_out);
-  std::lock_guard<std::recursive_mutex> lk(c->call_mutex);
-  lmx_status st = lmx_ctx_upload(c, 1, sources, n_sources);
-  if (st == LMX_OK) st = lmx_ctx_upload_masks(c, 1, masks, n_sources);
-  if (st == LMX_OK) st = lmx_ctx_enqueue(c, 1, threshold, class_ids, n_class_ids);
-  if (st != LMX_OK) return st;
-  return lmx_ctx_collect(c, 1, out, cap, n_out);
+  return match_masked_chain(c, sources, masks, n_sources, threshold, nullptr, 0, class_ids, n_class_ids, out, cap, n_out);
   });
 }
 

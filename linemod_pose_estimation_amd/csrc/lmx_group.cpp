@@ -567,9 +567,11 @@ lmx_status lmx_group_upload(lmx_group* g, int32_t n_frames, const lmx_image* sou
   });
 }
 
-lmx_status lmx_group_submit(lmx_group* g, int32_t n_frames, float threshold, const char* const* class_ids, int32_t n_class_ids) {
-  return lmx::guarded("lmx_group_submit", [&]() -> lmx_status {
-  if (!g) { lmx::set_error("lmx_group_submit: null group"); return LMX_ERR_INVALID_ARG; }
+}  // extern "C"
+
+// lmx_group_submit (thresholds null) and lmx_group_submit_thresholds (the array every member forwards) are one code path
+static lmx_status group_submit(lmx_group* g, int32_t n_frames, float threshold, const float* thresholds, int32_t n_thresholds, const char* const* class_ids,
+                               int32_t n_class_ids) {
   if (!g->uploaded) { lmx::set_error("lmx_group_submit: nothing uploaded"); return LMX_ERR_INVALID_ARG; }
   if (g->in_flight >= g->depth) { lmx::set_error("lmx_group_submit: %d batches are already in flight; finish one first", g->in_flight); return LMX_ERR_INVALID_ARG; }
   const int k = g->head;
@@ -588,13 +590,14 @@ lmx_status lmx_group_submit(lmx_group* g, int32_t n_frames, float threshold, con
   // graph captures (first use of a slot / frame set / batch size / threshold) run here, one after the other on the calling thread: a
   // capture that overlaps HIP calls of the group's other host threads fails on ROCm 7.2 (profiles/r03_group_host_cost.txt)
   for (Member& m : g->members)
-    if (share(m) > 0 && (st = lmx::ctx_prepare_graph(m.ctx, share(m), threshold)) != LMX_OK) return st;
+    if (share(m) > 0 && (st = lmx::ctx_prepare_graph(m.ctx, share(m), threshold, thresholds != nullptr)) != LMX_OK) return st;
   {
     Phase ph(g, lmx_group::T_ENQUEUE);
     st = for_members(g, [&](int i) {
       const int n_mine = share(g->members[(size_t)i]);
       if (n_mine == 0) return LMX_OK;
-      lmx_status r = lmx_ctx_enqueue(g->members[(size_t)i].ctx, n_mine, threshold, class_ids, n_class_ids);
+      lmx_status r = thresholds ? lmx_ctx_enqueue_thresholds(g->members[(size_t)i].ctx, n_mine, thresholds, n_thresholds, class_ids, n_class_ids)
+                                : lmx_ctx_enqueue(g->members[(size_t)i].ctx, n_mine, threshold, class_ids, n_class_ids);
       enqueued[(size_t)i] = r == LMX_OK;
       return r;
     });
@@ -614,6 +617,28 @@ lmx_status lmx_group_submit(lmx_group* g, int32_t n_frames, float threshold, con
   g->head = (k + 1) % g->depth;
   g->in_flight += 1;
   return LMX_OK;
+}
+
+extern "C" {
+
+lmx_status lmx_group_submit(lmx_group* g, int32_t n_frames, float threshold, const char* const* class_ids, int32_t n_class_ids) {
+  return lmx::guarded("lmx_group_submit", [&]() -> lmx_status {
+  if (!g) { lmx::set_error("lmx_group_submit: null group"); return LMX_ERR_INVALID_ARG; }
+  return group_submit(g, n_frames, threshold, nullptr, 0, class_ids, n_class_ids);
+  });
+}
+
+lmx_status lmx_group_submit_thresholds(lmx_group* g, int32_t n_frames, const float* thresholds, int32_t n_thresholds, const char* const* class_ids,
+                                       int32_t n_class_ids) {
+  return lmx::guarded("lmx_group_submit_thresholds", [&]() -> lmx_status {
+  // checked here once, so that no member enqueues when the array is bad (the members check again)
+  if (!thresholds) { lmx::set_error("lmx_group_submit_thresholds: null thresholds array"); return LMX_ERR_INVALID_ARG; }
+  if (!g) { lmx::set_error("lmx_group_submit_thresholds: null group"); return LMX_ERR_INVALID_ARG; }
+  const int32_t n_classes = lmx_bank_num_classes(g->bank);
+  if (n_thresholds != n_classes) { lmx::set_error("lmx_group_submit_thresholds: %d thresholds for a bank of %d classes", n_thresholds, n_classes); return LMX_ERR_INVALID_ARG; }
+  for (int32_t k = 0; k < n_thresholds; ++k)
+    if (thresholds[k] != thresholds[k]) { lmx::set_error("lmx_group_submit_thresholds: the threshold of class %d is not a number", k); return LMX_ERR_INVALID_ARG; }
+  return group_submit(g, n_frames, 0.f, thresholds, n_thresholds, class_ids, n_class_ids);
   });
 }
 

@@ -163,7 +163,7 @@ lmx_status ctx_check_sources(lmx_ctx* c, int n_frames, const lmx_image* sources,
 void ctx_stage_sources(lmx_ctx* c, CopyPool* pool, uint8_t* base, int n_frames, const lmx_image* sources, int stride_frames);
 lmx_status ctx_begin_staged_upload(lmx_ctx* c);                                    // host: the next set's previous transfer has left the staging area
 lmx_status ctx_finish_staged_upload(lmx_ctx* c, int n_frames, const uint8_t* pinned, int first_frame, int stride_frames);  // queue the DMAs out of `pinned`, make the set current
-lmx_status ctx_prepare_graph(lmx_ctx* c, int n_frames, float threshold);           // LMX_CTX_HIPGRAPH: capture the next enqueue's chain now if it is not cached
+lmx_status ctx_prepare_graph(lmx_ctx* c, int n_frames, float threshold, bool per_class = false);   // LMX_CTX_HIPGRAPH: capture the next enqueue's chain now if it is not cached (per_class: the chain of lmx_ctx_enqueue_thresholds)
 lmx_status ctx_drop_newest(lmx_ctx* c);                                            // undo the most recent enqueue (waits for it, frees its slot)
 
 // Coarse candidate written by k_score_coarse, consumed by k_refine.
@@ -172,6 +172,13 @@ struct Candidate {
   uint32_t pos;    // raster index r*Wc + c at the coarsest level
   uint32_t raw;    // raw similarity (sum of responses)
   uint32_t frame;  // frame of the batch (candidates of all frames share one list)
+};
+
+// Per-class match thresholds (lmx_ctx_enqueue_thresholds): entry k belongs to class index k.  One 8-byte entry, so that one scalar load
+// brings both values; `frac` is threshold / 100.f divided in float on the host, what launch_score_coarse hands the uniform kernels.
+struct ClassThreshold {
+  float threshold;
+  float frac;
 };
 
 // The candidate list of one output slot, filled by the scoring kernel and read by k_refine.  Appending through ONE counter costs
@@ -408,13 +415,15 @@ void launch_pack_nibbles(hipStream_t s, const uint8_t* lm, uint8_t* lmn, const L
 void launch_score_coarse(hipStream_t s, const DeviceBankView& bank, const LevelGeom& g, const uint8_t* const* lm_mod /*[M] device ptrs*/,
                          int n_frames, float threshold, const int32_t* class_slot, Candidate* cands /* cand_list_entries(cap) */,
                          uint32_t* header /* the slot's; its stripe counters lie in front of it (stripes_of_header) */, uint32_t cap,
-                         int n_stripes /* power of two <= kCandStripes, the same for launch_refine */);
+                         int n_stripes /* power of two <= kCandStripes, the same for launch_refine */,
+                         const ClassThreshold* class_thr = nullptr /* device, [n_classes]: the per-class kernels, `threshold` is not read */);
 // Returns false when nothing was launched (empty shard).  pub_dst != null: the kernel also publishes the slot (header + counted
 // records, <= pub_max) to pub_dst when its last workgroup finishes; pub_counter is that slot's zero-initialised ticket counter.
 bool launch_refine(hipStream_t s, const DeviceBankView& bank, const KernelParams& kp, int n_frames, float threshold,
                    const int32_t* class_slot, const Candidate* cands, uint32_t* header, uint32_t cap, int n_stripes,
                    lmx_raw_match_t* matches, uint32_t* match_count, void* pub_dst = nullptr, const void* pub_src = nullptr, uint32_t* pub_counter = nullptr,
-                   uint32_t pub_max = 0, uint32_t pub_seq = 0 /* written to word 7 of the published header LAST: the host may poll it instead of the slot's event */);
+                   uint32_t pub_max = 0, uint32_t pub_seq = 0 /* written to word 7 of the published header LAST: the host may poll it instead of the slot's event */,
+                   const ClassThreshold* class_thr = nullptr /* as for launch_score_coarse */);
 // Fused launches of the small-batch chain (lmx_enqueue.cpp issue_small): depth quantiser of level 0 + colour quantiser of level 1, and the
 // spread of both levels of a two-level bank.
 bool launch_small_depth_color(hipStream_t s, const uint16_t* depth, uint8_t* dq, uint8_t* dq_half, int H, int W, int distance_threshold, int difference_threshold,

@@ -837,6 +837,9 @@ struct ScoreParams {
   int32_t nf_max;
   int32_t blocks_per_frame;
   float threshold;
+  // the per-class forms only (PER_CLASS): one entry per class index in place of threshold / threshold_frac above; last, so that every
+  // other argument keeps its offset
+  const ClassThreshold* class_thr;
 };
 
 // The passing placements of one chunk (bit q of pass_mask: the lane's placement j0 + q, raw sum raw8[q]) join the candidate list with
@@ -993,7 +996,7 @@ __device__ __forceinline__ void score_pass(const ScoreParams& p, int g, int fram
   }
 }
 
-template <bool PRUNE>
+template <bool PRUNE, bool PER_CLASS = false>
 __global__ __launch_bounds__(64 * SC_WAVES_PER_BLOCK) void k_score_coarse(ScoreParams p) {
   const int lane = threadIdx.x & 63;
   // Workgroups are dealt round-robin over the 8 XCDs (blockIdx % 8 share an XCD and its private 4 MiB L2).  With >= 8
@@ -1016,7 +1019,9 @@ __global__ __launch_bounds__(64 * SC_WAVES_PER_BLOCK) void k_score_coarse(ScoreP
   const int positions = li.positions;
   const int nf = li.nf_total;
   if (positions <= 0 || nf <= 0) return;
-  const int raw_threshold = (int)(2 * nf + (p.threshold / 100.f) * (2 * nf) + 0.5f);
+  int raw_threshold;
+  if constexpr (PER_CLASS) raw_threshold = (int)(2 * nf + p.class_thr[p.info[g].class_index].frac * (2 * nf) + 0.5f);   // the class's threshold / 100.f, divided on the host
+  else raw_threshold = (int)(2 * nf + (p.threshold / 100.f) * (2 * nf) + 0.5f);
   int pbase = 0;
   for (; pbase + 2 * SC_CHUNK_POS < positions; pbase += 3 * SC_CHUNK_POS) score_pass<3, PRUNE>(p, g, frame, lane, pbase, positions, raw_threshold, nf);
   const int rest = positions - pbase;  // <= 2 chunks here (or <= 0 when the last full pass covered everything)
@@ -1155,7 +1160,7 @@ __device__ __forceinline__ void score_pass_u8(const ScoreParams& p, const uint8_
   }
 }
 
-template <bool PRUNE>
+template <bool PRUNE, bool PER_CLASS = false>
 __global__ __launch_bounds__(64 * SC_WAVES_PER_BLOCK) void k_score_coarse_u8(ScoreParams p) {
   const int lane = threadIdx.x & 63;
   int frame, tblock;  // XCD-aware frame placement, as in k_score_coarse
@@ -1174,11 +1179,15 @@ __global__ __launch_bounds__(64 * SC_WAVES_PER_BLOCK) void k_score_coarse_u8(Sco
   // everything about the template, the table row is fetched at the same time, and only the class filter is a second hop.
   const ScoreInfo si = p.sinfo[g];
   const uint32_t my_off = p.uni_off[(size_t)g * kFeatStride + lane];
+  float class_frac = 0.f;
+  if constexpr (PER_CLASS) class_frac = p.class_thr[si.class_index].frac;   // asked for together with the class filter: the second hop stays one
   if (p.class_slot[si.class_index] < 0) return;
   const int positions = si.positions;
   const int nf = si.nf_total;
   if (positions <= 0 || nf <= 0) return;
-  const int raw_threshold = (int)(2 * nf + (p.threshold / 100.f) * (2 * nf) + 0.5f);
+  int raw_threshold;
+  if constexpr (PER_CLASS) raw_threshold = (int)(2 * nf + class_frac * (2 * nf) + 0.5f);
+  else raw_threshold = (int)(2 * nf + (p.threshold / 100.f) * (2 * nf) + 0.5f);
   const uint8_t* lm_frame = p.lm[0] + (size_t)frame * p.mod_stride;
   // at most two chunks (1008 placements) per pass: the load buffer of a round is 12 dwords per chunk, and a third chunk
   // would cost a wave of occupancy
@@ -1201,6 +1210,7 @@ __global__ __launch_bounds__(64 * SC_WAVES_PER_BLOCK) void k_score_coarse_u8(Sco
 // Same exact pruning, same candidates for every input.
 // ---------------------------------------------------------------------------------------------------------
 typedef const uint32_t __attribute__((address_space(4))) lmx_cu32_const;   // constant address space: uniform loads become s_load
+typedef const uint64_t __attribute__((address_space(4))) lmx_cu64_const;   // a ClassThreshold entry as one 8-byte scalar load
 
 constexpr int SB_FPW = 2;    // frames of its XCD slot that one wave scores (1, 2, 4 and 8 measured: profiles/r10_score_frames_ab.txt)
 constexpr int SB_SEG0 = 3;   // groups in the first of the two segments of a block behind the first one; the second takes the other SB_GROUPS - SB_SEG0
@@ -1326,12 +1336,15 @@ __device__ __forceinline__ void score_pass_sb(const ScoreParams& p, const uint8_
 // from the host (threshold_frac, stripe_cap).  The passes run inside the frame loop, and a frame's first block comes from the scalar
 // cache again: the other order, with the first block's sixteen dwords and the pass's lane masks kept across the frames, needs more
 // SGPRs than there are (106 with 31-45 spilled to VGPR lanes, against 91 here).
-template <bool PRUNE, int FPW>
+// PER_CLASS: the threshold is the class's (ScoreParams::class_thr).  Its entry is asked for together with the class filter's word -- both
+// need the class index and nothing else -- so the chain of dependent round trips is as long as the uniform kernel's.
+template <bool PRUNE, int FPW, bool PER_CLASS = false>
 __global__ __launch_bounds__(64 * SC_WAVES_PER_BLOCK) void k_score_coarse_sb(ScoreParams p) {
   const int lane = threadIdx.x & 63;
   // everything the way to the first buffer load needs from the kernel arguments, asked for at once: left alone, the compiler fetches each
   // argument behind the early exit in front of its first use, a scalar-memory round trip of its own every time
   asm volatile("" ::"s"(p.sinfo), "s"(p.blk_off), "s"(p.class_slot), "s"(p.stripes), "s"(p.G), "s"(p.n_frames), "s"(p.xcd_frames), "s"(p.threshold_frac), "s"(p.mod_stride), "s"(p.lm[0]));
+  if constexpr (PER_CLASS) asm volatile("" ::"s"(p.class_thr));
   int frame0, tblock;
   if (p.xcd_frames) {
     tblock = blockIdx.x >> 3;
@@ -1348,9 +1361,17 @@ __global__ __launch_bounds__(64 * SC_WAVES_PER_BLOCK) void k_score_coarse_sb(Sco
   lmx_cu32_const* sip = (lmx_cu32_const*)(uintptr_t)(p.sinfo + g);
   const int positions = (int)sip[0], nf = (int)sip[1], class_index = (int)sip[2];
   const uint32_t groups = sip[3];
+  float frac = p.threshold_frac;
+  if constexpr (PER_CLASS) {
+    // both words are wanted in registers in front of the filter's branch: left alone, the compiler sinks the entry's load behind it
+    const uint64_t entry = ((lmx_cu64_const*)(uintptr_t)p.class_thr)[class_index];
+    const uint32_t slot_word = ((lmx_cu32_const*)(uintptr_t)p.class_slot)[class_index];
+    asm volatile("" ::"s"(entry), "s"(slot_word));
+    frac = __uint_as_float((uint32_t)(entry >> 32));
+  }
   if ((int)((lmx_cu32_const*)(uintptr_t)p.class_slot)[class_index] < 0) return;
   if (positions <= 0 || nf <= 0) return;
-  const int raw_threshold = (int)(2 * nf + p.threshold_frac * (2 * nf) + 0.5f);
+  const int raw_threshold = (int)(2 * nf + frac * (2 * nf) + 0.5f);
   lmx_cu32_const* row = (lmx_cu32_const*)(uintptr_t)(p.blk_off + (size_t)g * (SB_BLOCK * SB_MAX_BLOCKS));
   const int n_blocks = (int)((groups >> 16) & 0xffu);
   // per frame only the base of the buffer descriptor moves; every accumulator and live flag starts afresh inside score_pass_sb
@@ -1414,12 +1435,16 @@ struct RefineParams {
   uint32_t* pub_counter;
   uint32_t pub_max;
   uint32_t pub_seq;      // goes to word 7 of the published header once everything else of the slot is visible to the host
+  const ClassThreshold* class_thr;   // PER_CLASS only: the candidate's class decides its threshold (last: the other offsets stay)
 };
 
 // One workgroup (4 waves) per candidate: the gathers of a candidate are a dependent chain of batches (table entry ->
 // 8 loads in flight -> adds), and with one wave per candidate the kernel's duration was that chain (16 batches per level),
 // not its total work.  Wave w takes features [16w, 16w+16) of every modality, the four partial patch sums meet in LDS, and
 // every wave then evaluates the same arg-max, which keeps the control flow uniform without a broadcast.
+// PER_CLASS: both tests use the threshold of the candidate's class.  The class index is requested with the level infos, right behind the
+// candidate; its table entry arrives while the first modality's rows and gathers are under way, long before the first test.
+template <bool PER_CLASS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_refine(RefineParams p) {
   __shared__ uint32_t s_part[2][4][2][64];  // [parity of the level step][wave][lo, hi][lane]
   __shared__ uint32_t s_mid[2][4][2][64];   // the same for the early-exit test between two modalities
@@ -1493,6 +1518,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     // a second table, and a wave's 16 gathers of a modality are in flight at once.
     const TemplateLevelInfo* lg = p.linfo + (size_t)g * p.L;
     const int nfc = lg[Lc].nf_total;
+    float thr = p.threshold;
+    if constexpr (PER_CLASS) {
+      // the class index travels with nf_total (one round trip for both; left alone, the compiler sinks its load behind the level loop's
+      // entry test, a dependent step of its own), the entry's load is then in flight next to the first level's infos and rows
+      const int class_index = p.info[g].class_index;
+      asm volatile("" ::"v"(nfc), "v"(class_index), "s"(p.class_thr));
+      thr = p.class_thr[class_index].threshold;
+    }
     float sim = (c_raw * 100.f) / (4 * nfc) + 0.5f;
     bool alive = true;
     int step = 0;
@@ -1567,7 +1600,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
 #pragma unroll
           for (int sft = 32; sft >= 1; sft >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, sft, 64));
           const int bound = __builtin_amdgcn_readfirstlane((int)mx) + 4 * (li.nf_total - seen);
-          if ((bound * 100.f) / (4 * li.nf_total) < p.threshold) { alive = false; break; }   // every wave computes the same bound
+          if ((bound * 100.f) / (4 * li.nf_total) < thr) { alive = false; break; }   // every wave computes the same bound
         }
       }
       if (!alive) break;
@@ -1601,7 +1634,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
       x = (x / T - 8 + best_c) * T + off;
       y = (y / T - 8 + best_r) * T + off;
       sim = (best * 100.f) / (4 * li.nf_total);
-      if (sim < p.threshold) alive = false;
+      if (sim < thr) alive = false;
     }
     if (alive && threadIdx.x == 0) {
       // The record waits in LDS: a workgroup reserves room for up to RF_REC_BATCH of its records with ONE atomic (flush_records).  The
@@ -1969,7 +2002,8 @@ void launch_pack_nibbles(hipStream_t s, const uint8_t* lm, uint8_t* lmn, const L
 int score_kernel_variant(const DeviceBankView& bank) { return bank.uni_ok ? bank.score_variant : 0; }
 
 void launch_score_coarse(hipStream_t s, const DeviceBankView& bank, const LevelGeom& g, const uint8_t* const* lm_mod, int n_frames,
-                         float threshold, const int32_t* class_slot, Candidate* cands, uint32_t* header, uint32_t cap, int n_stripes) {
+                         float threshold, const int32_t* class_slot, Candidate* cands, uint32_t* header, uint32_t cap, int n_stripes,
+                         const ClassThreshold* class_thr) {
   ScoreParams p;
   p.info = bank.info; p.linfo = bank.linfo; p.coarse_off = bank.coarse_off; p.class_slot = class_slot;
   p.feat_count_coarse = bank.feat_count + (size_t)(bank.L - 1) * bank.G * bank.M;
@@ -1978,6 +2012,7 @@ void launch_score_coarse(hipStream_t s, const DeviceBankView& bank, const LevelG
   p.G = bank.G; p.L = bank.L; p.M = bank.M; p.nf_max = bank.nf_max_coarse;
   p.threshold = threshold;
   p.threshold_frac = threshold / 100.f;
+  p.class_thr = class_thr;
   p.cands = cands; p.stripes = stripes_of_header(header); p.cap = cap; p.n_stripes = (uint32_t)n_stripes;
   p.stripe_cap = cap / (uint32_t)n_stripes;
   if (bank.G <= 0) return;
@@ -1990,42 +2025,45 @@ void launch_score_coarse(hipStream_t s, const DeviceBankView& bank, const LevelG
   p.sinfo = bank.sinfo;
   const int variant = score_kernel_variant(bank);
   const dim3 block(64 * SC_WAVES_PER_BLOCK);
-  with_bool(bank.score_no_prune, [&](auto no_prune) {   // LMX_SCORE_NO_PRUNE: similarity()'s full work, same candidates (see score_pass)
-    constexpr bool PRUNE = !decltype(no_prune)::value;
+  with_bool(bank.score_no_prune, [&](auto no_prune) { with_bool(class_thr != nullptr, [&](auto per_class) {   // LMX_SCORE_NO_PRUNE: similarity()'s full work, same candidates (see score_pass)
+    constexpr bool PRUNE = !decltype(no_prune)::value, PC = decltype(per_class)::value;
     if (variant == 2) {
       // k_score_coarse_sb: a wave scores its template on up to SB_FPW frames of its XCD slot (frames k, k + 8, ...); a batch with one frame per
       // slot, and the small batches that keep one frame per wave, run the one-frame build
       const int per_slot = (n_frames + 7) / 8;
       const int fpw = p.xcd_frames && per_slot > 1 ? SB_FPW : 1;
       const dim3 grid = p.xcd_frames ? dim3(8u * (unsigned)p.blocks_per_frame, (unsigned)((per_slot + fpw - 1) / fpw)) : dim3((unsigned)p.blocks_per_frame, (unsigned)n_frames);
-      void (*kernel)(ScoreParams) = k_score_coarse_sb<PRUNE, SB_FPW>;
-      if (fpw == 1) kernel = k_score_coarse_sb<PRUNE, 1>;
+      void (*kernel)(ScoreParams) = k_score_coarse_sb<PRUNE, SB_FPW, PC>;
+      if (fpw == 1) kernel = k_score_coarse_sb<PRUNE, 1, PC>;
       hipLaunchKernelGGL(kernel, grid, block, 0, s, p);
       return;
     }
     const dim3 grid((unsigned)(p.blocks_per_frame * frame_slots));
-    void (*kernel)(ScoreParams) = k_score_coarse_u8<PRUNE>;
-    if (variant != 1) kernel = k_score_coarse<PRUNE>;
+    void (*kernel)(ScoreParams) = k_score_coarse_u8<PRUNE, PC>;
+    if (variant != 1) kernel = k_score_coarse<PRUNE, PC>;
     hipLaunchKernelGGL(kernel, grid, block, 0, s, p);
-  });
+  }); });
 }
 
 bool launch_refine(hipStream_t s, const DeviceBankView& bank, const KernelParams& kp, int n_frames, float threshold,
                    const int32_t* class_slot, const Candidate* cands, uint32_t* header, uint32_t cap, int n_stripes,
-                   lmx_raw_match_t* matches, uint32_t* match_count, void* pub_dst, const void* pub_src, uint32_t* pub_counter, uint32_t pub_max, uint32_t pub_seq) {
+                   lmx_raw_match_t* matches, uint32_t* match_count, void* pub_dst, const void* pub_src, uint32_t* pub_counter, uint32_t pub_max, uint32_t pub_seq,
+                   const ClassThreshold* class_thr) {
   RefineParams p;
   p.info = bank.info; p.linfo = bank.linfo; p.feat = bank.feat; p.feat_count = bank.feat_count; p.class_slot = class_slot;
   for (int l = 0; l < kMaxLevels; ++l) {
     p.geom[l] = kp.geom[l];
     for (int m = 0; m < kMaxModalities; ++m) p.ls[l][m] = kp.fb.ls[l][m];
   }
-  p.G = bank.G; p.L = bank.L; p.M = bank.M; p.threshold = threshold;
+  p.G = bank.G; p.L = bank.L; p.M = bank.M; p.threshold = threshold; p.class_thr = class_thr;
   p.cands = cands; p.stripes = stripes_of_header(header); p.header = header; p.cap = cap; p.n_stripes = (uint32_t)n_stripes; p.matches = matches; p.match_count = match_count;
   p.pub_dst = reinterpret_cast<uint4*>(pub_dst); p.pub_src = reinterpret_cast<const uint4*>(pub_src); p.pub_counter = pub_counter; p.pub_max = pub_max; p.pub_seq = pub_seq;
   if (bank.G <= 0) return false;   // nothing launched: the caller publishes with k_publish_records
   (void)n_frames;  // candidates of all frames share one list
   // small batches: few candidates, and every workgroup costs the last one a ticket
-  hipLaunchKernelGGL(k_refine, dim3(n_frames <= 2 ? 512 : 2048), dim3(256), 0, s, p);
+  void (*kernel)(RefineParams) = k_refine<false>;
+  if (class_thr) kernel = k_refine<true>;
+  hipLaunchKernelGGL(kernel, dim3(n_frames <= 2 ? 512 : 2048), dim3(256), 0, s, p);
   return true;
 }
 

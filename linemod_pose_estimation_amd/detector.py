@@ -7,6 +7,7 @@
 Everything computes through the C ABI of liblmx.so (include/lmx.h) on a gfx950 device; there is no CPU path here.
 """
 import ctypes as C
+from collections.abc import Mapping
 
 import numpy as np
 
@@ -272,6 +273,24 @@ class NativeBank:
             pass
 
 
+def class_thresholds(bank_class_ids, thresholds, class_ids=()):
+    """Per-class thresholds given as a mapping class id -> float, for the `..._thresholds` entry points: -> (float array with one entry
+    per class of the bank, in class-index order; class-id array; its length).  The classes matched are those of `class_ids` (in that
+    order) that the mapping holds, or, without `class_ids`, the mapping's keys in sorted order -- the order cv::linemod::Detector::match
+    visits its class map in.  Classes absent from the mapping are not matched; a key the bank does not know is an error, and so is a
+    call that would match no class at all."""
+    known = list(bank_class_ids)
+    unknown = [k for k in thresholds if k not in known]
+    if unknown:
+        raise ValueError("thresholds for classes the bank does not hold: %s" % unknown)
+    visit = [c for c in (class_ids if len(class_ids) else sorted(thresholds, key=lambda s: s.encode())) if c in thresholds]
+    if not visit:
+        raise ValueError("no class to match: the threshold mapping holds none of the classes asked for")
+    arr = (C.c_float * len(known))(*[float(thresholds.get(c, 0.0)) for c in known])   # entries of unmatched classes are never read
+    cids = (C.c_char_p * len(visit))(*[c.encode() for c in visit])
+    return arr, cids, len(visit)
+
+
 class Detector:
     """Device-resident detector: a template bank (or one rank's shard of it) in HBM plus per-frame workspaces.
 
@@ -327,12 +346,18 @@ class Detector:
 
     def match(self, sources, threshold, class_ids=(), cap=1 << 14):
         """One frame through `lmx_match`, the drop-in for Detector::match.  Returns MATCH_DTYPE records in upstream
-        output order (std::sort + std::unique applied)."""
+        output order (std::sort + std::unique applied).  `threshold`: a float, or a mapping class id -> float (per-class thresholds,
+        see class_thresholds); the same holds for match_masked, match_batch and enqueue."""
         L = _lib.lib()
         imgs, keep = _images([sources])
-        cids, ncid = self._cids(class_ids)
         out = np.zeros(cap, MATCH_DTYPE)
         n = C.c_size_t()
+        if isinstance(threshold, Mapping):
+            thr, cids, ncid = class_thresholds(self._class_ids, threshold, class_ids)
+            _lib.check(L.lmx_match_thresholds(self.h, imgs, len(sources), thr, len(thr), cids, ncid, out.ctypes.data, cap, C.byref(n)))
+            del keep
+            return out[:n.value].copy()
+        cids, ncid = self._cids(class_ids)
         _lib.check(L.lmx_match(self.h, imgs, len(sources), C.c_float(threshold), cids, ncid, out.ctypes.data, cap, C.byref(n)))
         del keep
         return out[:n.value].copy()
@@ -349,9 +374,14 @@ class Detector:
                 if m.dtype != np.uint8 or m.ndim != 2 or m.strides[1] != 1:
                     raise TypeError("masks must be uint8 HxW")
                 marr[i] = _lib.Image(m.ctypes.data, m.shape[0], m.shape[1], 1, 1, m.strides[0])
-        cids, ncid = self._cids(class_ids)
         out = np.zeros(cap, MATCH_DTYPE)
         n = C.c_size_t()
+        if isinstance(threshold, Mapping):
+            thr, cids, ncid = class_thresholds(self._class_ids, threshold, class_ids)
+            _lib.check(_lib.lib().lmx_match_masked_thresholds(self.h, imgs, marr, len(sources), thr, len(thr), cids, ncid, out.ctypes.data, cap, C.byref(n)))
+            del keep
+            return out[:n.value].copy()
+        cids, ncid = self._cids(class_ids)
         _lib.check(_lib.lib().lmx_match_masked(self.h, imgs, marr, len(sources), C.c_float(threshold), cids, ncid, out.ctypes.data, cap, C.byref(n)))
         del keep
         return out[:n.value].copy()
@@ -378,11 +408,15 @@ class Detector:
         """n frames through `lmx_match_batch` (per-frame output capacity `cap`)."""
         L = _lib.lib()
         imgs, keep = _images(frames)
-        cids, ncid = self._cids(class_ids)
         out = np.zeros((len(frames), cap), MATCH_DTYPE)
         n_out = (C.c_size_t * len(frames))()
-        _lib.check(L.lmx_match_batch(self.h, len(frames), imgs, len(frames[0]), C.c_float(threshold), cids, ncid,
-                                     out.ctypes.data, cap, n_out))
+        if isinstance(threshold, Mapping):
+            thr, cids, ncid = class_thresholds(self._class_ids, threshold, class_ids)
+            _lib.check(L.lmx_match_batch_thresholds(self.h, len(frames), imgs, len(frames[0]), thr, len(thr), cids, ncid, out.ctypes.data, cap, n_out))
+        else:
+            cids, ncid = self._cids(class_ids)
+            _lib.check(L.lmx_match_batch(self.h, len(frames), imgs, len(frames[0]), C.c_float(threshold), cids, ncid,
+                                         out.ctypes.data, cap, n_out))
         del keep
         return [out[f, :n_out[f]].copy() for f in range(len(frames))]
 
@@ -417,6 +451,10 @@ class Detector:
         del keep
 
     def enqueue(self, n_frames, threshold, class_ids=()):
+        if isinstance(threshold, Mapping):
+            thr, cids, ncid = class_thresholds(self._class_ids, threshold, class_ids)
+            _lib.check(_lib.lib().lmx_ctx_enqueue_thresholds(self.h, n_frames, thr, len(thr), cids, ncid))
+            return
         cids, ncid = self._cids(class_ids)
         _lib.check(_lib.lib().lmx_ctx_enqueue(self.h, n_frames, C.c_float(threshold), cids, ncid))
 

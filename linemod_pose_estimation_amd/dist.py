@@ -241,7 +241,14 @@ class DeviceGroup:
         del keep
 
     def submit(self, n_frames, threshold):
+        """`threshold`: a float, or a mapping class id -> float (per-class thresholds; classes absent from it are not matched)."""
         import ctypes as C
+        from collections.abc import Mapping
+        if isinstance(threshold, Mapping):
+            from .detector import class_thresholds
+            thr, cids, ncid = class_thresholds(self.native_bank.class_ids(), threshold)
+            _lib.check(_lib.lib().lmx_group_submit_thresholds(self.h, n_frames, thr, len(thr), cids, ncid))
+            return
         _lib.check(_lib.lib().lmx_group_submit(self.h, n_frames, C.c_float(threshold), None, 0))
 
     def finish(self, n_frames, cap=4096):
