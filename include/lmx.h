@@ -549,8 +549,9 @@ void lmx_renderer_params_free(lmx_renderer_params* params);
  *   lmx_ctx_collect_clusters    : replaces lmx_ctx_collect for the OLDEST outstanding enqueue.  Frame f's matches are
  *     matches[match_offsets[f] .. match_offsets[f+1]), its clusters clusters[cluster_offsets[f] .. cluster_offsets[f+1]);
  *     a cluster's members are members[member_begin .. member_begin + member_count), indices into ITS FRAME's matches.
- *     matches may be NULL (cap_matches 0) when only clusters are wanted.  Frames with more than 2048 raw records, or whose
- *     bins fall outside +-65536, are finished by the host path transparently. */
+ *     matches may be NULL (cap_matches 0) when only clusters are wanted.  Frames with more than 2048 raw records go to a second
+ *     launch of the large-frame kernels (up to 16384 records; lmx_ctx_chain_stats); frames beyond that, or with a depth ring outside a
+ *     kernel's packed range, are finished by the host path transparently.  The result is the same on every path. */
 lmx_status lmx_ctx_set_cluster_sidecar(lmx_ctx* ctx, const double* obj_origin_dists, const int32_t* rects, size_t n_templates,
                                        const lmx_cluster_params* params);
 lmx_status lmx_ctx_collect_clusters(lmx_ctx* ctx, int32_t n_frames, lmx_match_t* matches, size_t cap_matches, size_t* match_offsets,
@@ -645,7 +646,8 @@ double     lmx_depth_value(const lmx_depth_diff_t* diff, double no_value);
  *   clusters[k].score = the mean over the cluster's members, in voting order, of lmx_depth_value(diffs[i], no_value).
  * On the context's consumer stream: wait for the scene's event, k_depth_diff_records (one workgroup per RAW record: which of two duplicate
  * records std::unique keeps is decided by the sort that follows), the scored form of k_f2_finalize_cluster, one synchronisation.  Frames
- * the device chain hands back (more than 2048 records, a bin outside the packed range) are finished on the host inside the call
+ * of 2049 .. 16384 records are finished by the scored large-frame kernel from the same per-record results (lmx_ctx_chain_stats); frames
+ * the device chain hands back (more than 16384 records, a ring outside the packed range) are finished on the host inside the call
  * (k_depth_diff on the resident scene + lmx_cluster_matches_scored), with the errors lmx_ctx_collect_clusters reports for them.
  * For EVERY input matches, diffs, clusters (score included) and members equal, bit for bit,
  *     lmx_ctx_collect;  lmx_depth_diff_matches(templates, depth, n, matches, offsets, class_index, diffs);
@@ -733,8 +735,9 @@ lmx_status lmx_ctx_collect_clusters_depth_normal(lmx_ctx* ctx, int32_t n_frames,
  *     written) or lmx_match_value (normals != 0, after enable_normals) over its members.  A match whose template_id is outside its
  *     class's range, or whose class is >= n_classes, gets zero diffs and is never compared with another class's crop.
  *     Equal, bit for bit, to lmx_ctx_collect + per class (lmx_depth_diff_matches / lmx_normal_diff_matches on a per-class object at
- *     class_index = c) + lmx_cluster_matches_classes.  Frames of more than 2048 records, with a template_id outside its class's side-car
- *     or a depth ring outside +-2^16 are finished on the host inside the call.
+ *     class_index = c) + lmx_cluster_matches_classes.  Frames of 2049 .. 16384 records are finished by the classed large-frame
+ *     kernels; frames of more than 16384 records, with a template_id outside its class's side-car or a depth ring outside the kernels'
+ *     packed range (+-2^16 up to 2048 records, +-2^13 beyond) are finished on the host inside the call.
  *     LMX_ERR_INVALID_ARG, the enqueue staying outstanding: no class side-car set; n_classes outside 1 .. 16; class_base[0] != 0;
  *     class_base[n_classes] != lmx_depth_templates_count; a class's range != its side-car's n_templates (0 without one); and every
  *     condition of lmx_ctx_collect_clusters_depth / _depth_normal on the scene and the normals. */
@@ -843,8 +846,51 @@ lmx_status lmx_debug_device_finalize_cluster_classes(int32_t device, const lmx_r
 enum { LMX_TAB_INFO = 0, LMX_TAB_LINFO, LMX_TAB_COARSE_OFF, LMX_TAB_COARSE_UNI, LMX_TAB_COARSE_BLK, LMX_TAB_SINFO, LMX_TAB_FEAT, LMX_TAB_FEAT_COUNT, LMX_TAB_SUMMARY };
 lmx_status lmx_debug_bank_tables(const lmx_bank* bank, int32_t width, int32_t height, int32_t max_batch, int32_t shard_rank, int32_t shard_world,
                                  int32_t ls_flat, int32_t table, void* out, size_t out_bytes, size_t* n_bytes, uint64_t* fnv1a);
+/* The large-frame form of the four hooks above: the kernels lmx_ctx_collect_clusters* launch for the frames the LDS kernels hand back
+ * (k_f2_large*, csrc/lmx_f2.hip: one workgroup of 1024 threads per frame, rows in device memory), here on EVERY frame whatever its size, with
+ * the same arguments and no host completion.  Rows are [n_frames][16384].  Exactness: for every frame of at most 16384 records the outputs
+ * equal the reference chain's bit for bit, as the LDS kernels' do -- the same permutation of ties from both sorts, the same double sums.
+ *   status 0: complete;   status 1: more than 16384 records, counts[0] = the record count, nothing else written;
+ *   status 2: a template_id outside the side-car or a depth ring outside the packed vote key: un-classed -2^17 .. 2^17 - 1, classed
+ *             -2^13 .. 2^13 - 1 (the 14-bit list position takes the bits; vote bins y / step, x / step are 16 bits each and always fit);
+ *             counts[0] = final matches, the matches row is valid, no clusters.
+ * lmx_debug_device_sort_perm_large: the permutation of the big sort for n <= 16384 pairs (n > 16384: LMX_ERR_INVALID_ARG); inputs that
+ * exhaust the introsort's depth limit are heap-sorted on the device like the LDS kernel's, so the permutation is std::sort's for them too. */
+lmx_status lmx_debug_device_sort_perm_large(int32_t device, const float* similarity, const int32_t* template_id, int32_t n, int32_t* perm);
+lmx_status lmx_debug_device_finalize_cluster_large(int32_t device, const lmx_raw_match_t* records, size_t n_records, int32_t n_frames,
+                                                   const double* obj_origin_dists, const int32_t* rects, size_t n_templates,
+                                                   const lmx_cluster_params* params, lmx_match_t* matches, lmx_cluster_t* clusters,
+                                                   int32_t* members, uint32_t* counts);
+lmx_status lmx_debug_device_finalize_cluster_large_depth(int32_t device, const lmx_raw_match_t* records, size_t n_records, int32_t n_frames,
+                                                         lmx_depth_templates* templates, const lmx_image* depth, int32_t class_index,
+                                                         double no_value, const double* obj_origin_dists, const int32_t* rects,
+                                                         size_t n_templates, const lmx_cluster_params* params, lmx_match_t* matches,
+                                                         lmx_depth_diff_t* diffs, lmx_cluster_t* clusters, int32_t* members, uint32_t* counts);
+lmx_status lmx_debug_device_finalize_cluster_large_classes(int32_t device, const lmx_raw_match_t* records, size_t n_records, int32_t n_frames,
+                                                           const lmx_class_sidecar* classes, int32_t n_classes, const lmx_class_score* score,
+                                                           const lmx_image* depth, lmx_match_t* matches, lmx_depth_diff_t* diffs,
+                                                           lmx_normal_diff_t* ndiffs, lmx_cluster_t* clusters, int32_t* cluster_class,
+                                                           int32_t* members, uint32_t* counts);
 /* Counters of the last collect(): coarse candidates and refined matches summed over frames. */
 lmx_status lmx_ctx_stats(lmx_ctx* ctx, int64_t* n_candidates, int64_t* n_raw_matches);
+/* Which path completed the frames of the last lmx_ctx_collect_clusters, _depth, _depth_normal or _classes call.  A frame of at most 2048
+ * raw records is completed by the LDS kernel, one of 2049 .. 16384 by the large-frame kernel (unless the context was created with
+ * LMX_F2_LARGE=0 in the environment), a larger one by the host; a frame with a template_id outside its side-car or a depth ring outside a
+ * kernel's packed range (the large kernel's is narrower, see the hooks above) is completed by the host whatever its size.  The result is
+ * the reference's on every path.  max_frame_records: the largest raw record count among the frames beyond 2048 records, 0 if there was
+ * none (the LDS kernel does not report the raw count of a frame it completes).  large_workspace_bytes: the device memory the context
+ * holds for the large-frame kernel -- 0 until its first large frame, then one workspace part of 2.46 MB (2.72 MB with the depth score, 2.98 MB
+ * with both) per large frame of the busiest call so far. */
+typedef struct lmx_chain_stats {
+  int32_t frames;               /* frames of the call */
+  int32_t frames_lds;           /* completed by the LDS kernel */
+  int32_t frames_large;         /* completed by the large-frame kernel */
+  int32_t frames_host_records;  /* completed by the host because of their record count */
+  int32_t frames_host_other;    /* completed by the host for side-car or range reasons */
+  int32_t max_frame_records;
+  int64_t large_workspace_bytes;
+} lmx_chain_stats;
+lmx_status lmx_ctx_chain_stats(lmx_ctx* ctx, lmx_chain_stats* out);
 
 /* Per-kernel HIP-event timing on the context's stream (off by default).  `enabled` is a bitmask over kernel ids
  * (bit k = time kernel k; -1 = all): every timed launch costs two event records, so time only what is reported. */

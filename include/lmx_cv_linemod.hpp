@@ -391,6 +391,13 @@ class Detector {
     }
     return tcache_[key] = out;
   }
+  // Which path completed the frames of the last lmx_ctx_collect_clusters* call on the detector's context for BGR (gray: 8UC1) sources
+  // (lmx_ctx_chain_stats: LDS kernel, large-frame kernel, host); zeros before that context exists
+  lmx_chain_stats chainStats(bool gray = false) const {
+    lmx_chain_stats s = lmx_chain_stats();
+    if (ctx_[gray ? 1 : 0]) lmx_check(lmx_ctx_chain_stats(ctx_[gray ? 1 : 0], &s));
+    return s;
+  }
   int numTemplates() const { return view() ? lmx_bank_num_templates(view(), NULL) : 0; }
   int numTemplates(const String& class_id) const { return view() ? lmx_bank_num_templates(view(), class_id.c_str()) : 0; }
   int numClasses() const { return view() ? lmx_bank_num_classes(view()) : 0; }

@@ -275,6 +275,13 @@ class Detector {
 
   lmx_bank* bank() const { return bank_; }
   lmx_ctx* context() const { return ctx_; }
+  // Which path completed the frames of the context's last lmx_ctx_collect_clusters* call, collectClustersClasses included
+  // (lmx_ctx_chain_stats: LDS kernel, large-frame kernel, host); zeros before a context exists
+  lmx_chain_stats chainStats() const {
+    lmx_chain_stats s = lmx_chain_stats();
+    if (ctx_) check(lmx_ctx_chain_stats(ctx_, &s));
+    return s;
+  }
 
  private:
   ClassClusters collect_clusters_classes(const std::vector<std::vector<Image> >& frames, float threshold, const std::map<std::string, float>* thresholds,

@@ -28,6 +28,8 @@ SYMBOLS = [
     "lmx_ctx_collect_clusters_depth_normal", "lmx_debug_scene_normals", "lmx_depth_templates_set_profiling", "lmx_depth_templates_kernel_time",
     "lmx_cluster_matches_classes", "lmx_ctx_set_cluster_sidecar_class", "lmx_ctx_collect_clusters_classes", "lmx_depth_templates_append",
     "lmx_debug_device_finalize_cluster_classes",
+    "lmx_debug_device_sort_perm_large", "lmx_debug_device_finalize_cluster_large", "lmx_debug_device_finalize_cluster_large_depth",
+    "lmx_debug_device_finalize_cluster_large_classes", "lmx_ctx_chain_stats",
     "lmx_ctx_enqueue_thresholds", "lmx_match_thresholds", "lmx_match_batch_thresholds", "lmx_match_masked_thresholds", "lmx_group_submit_thresholds",
 ]
 
@@ -76,6 +78,11 @@ class ClassSidecar(C.Structure):   # lmx_class_sidecar
 
 class ClassScore(C.Structure):     # lmx_class_score
     _fields_ = [("templates", C.c_void_p), ("class_base", C.c_void_p), ("n_classes", C.c_int32), ("normals", C.c_int32), ("no_value", C.c_double)]
+
+
+class ChainStats(C.Structure):     # lmx_chain_stats
+    _fields_ = [("frames", C.c_int32), ("frames_lds", C.c_int32), ("frames_large", C.c_int32), ("frames_host_records", C.c_int32),
+                ("frames_host_other", C.c_int32), ("max_frame_records", C.c_int32), ("large_workspace_bytes", C.c_int64)]
 
 
 class RendererParams(C.Structure):
@@ -319,6 +326,11 @@ def lib():
     L.lmx_debug_bank_tables.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_size_t, C.POINTER(C.c_size_t),
                                         C.POINTER(C.c_uint64)]
     L.lmx_ctx_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.lmx_ctx_chain_stats.argtypes = [vp, C.POINTER(ChainStats)]
+    L.lmx_debug_device_sort_perm_large.argtypes = L.lmx_debug_device_sort_perm.argtypes
+    L.lmx_debug_device_finalize_cluster_large.argtypes = L.lmx_debug_device_finalize_cluster.argtypes
+    L.lmx_debug_device_finalize_cluster_large_depth.argtypes = L.lmx_debug_device_finalize_cluster_depth.argtypes
+    L.lmx_debug_device_finalize_cluster_large_classes.argtypes = L.lmx_debug_device_finalize_cluster_classes.argtypes
     L.lmx_kernel_name.argtypes = [C.c_int32]
     L.lmx_kernel_name.restype = C.c_char_p
     L.lmx_ctx_device_kernel_name.argtypes = [vp, C.c_int32]

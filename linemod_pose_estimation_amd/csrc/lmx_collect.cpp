@@ -278,7 +278,8 @@ struct DepthScore {
   lmx_normal_diff_t* ndiffs; // normal only: parallel to the caller's matches; may be null
 };
 
-// Room for one result of `elem` bytes per raw record of the slot being collected.  Nothing reads the old buffer: every call ends synchronised.
+// Room for one result of `elem` bytes per raw record of the slot being collected (and, with elem 1, for the large-frame kernel's workspace).
+// Nothing reads the old buffer: every call ends synchronised.
 static lmx_status grow_rec_diffs(void** d, size_t* cap, size_t n, size_t elem) {
   if (n <= *cap) return LMX_OK;
   if (*d) (void)hipFree(*d);
@@ -409,10 +410,47 @@ static lmx_status collect_clusters_impl(const char* what, lmx_ctx* c, int32_t n_
   const lmx_match_t* all_m = reinterpret_cast<const lmx_match_t*>(c->h_f2_out);
   const lmx_cluster_t* all_c = reinterpret_cast<const lmx_cluster_t*>(c->h_f2_out + off_clusters);
   const int32_t* all_mem = reinterpret_cast<const int32_t*>(c->h_f2_out + off_members);
-  // frames the device could not take (too many records, bins outside the packed range): the host path on the slot's records
+  // frames the LDS kernel handed back for their record count and the large-frame kernel takes: a second launch on exactly those, one
+  // workgroup each, on workspace parts allocated for as many (a call without such a frame launches nothing and allocates nothing)
+  std::vector<int32_t> large;
+  std::vector<int> large_part(n_frames, -1);
+  std::vector<uint32_t> lcounts;
+  F2LargeLayout lay{};
+  if (c->env.f2_large)
+    for (int f = 0; f < n_frames; ++f)
+      if (counts[(size_t)f * 4 + 3] == 1 && counts[(size_t)f * 4] <= (uint32_t)F2_LARGE_MAX) { large_part[f] = (int)large.size(); large.push_back(f); }
+  if (!large.empty()) {
+    lay = f2_large_layout(depth != nullptr, depth && depth->normal);
+    if (lmx_status gs = grow_rec_diffs((void**)&c->d_f2l_ws, &c->f2l_ws_bytes, large.size() * (size_t)lay.bytes, 1)) return gs;
+    if (!c->d_f2l_frames) LMX_HIP(hipMalloc((void**)&c->d_f2l_frames, F * sizeof(int32_t)));
+    if (!c->d_f2l_counts) LMX_HIP(hipMalloc((void**)&c->d_f2l_counts, F * 4 * sizeof(uint32_t)));
+    LMX_HIP(hipMemcpy(c->d_f2l_frames, large.data(), large.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    F2LargeParams lp{p, c->d_f2l_frames, c->d_f2l_ws, lay};
+    lp.p.out_counts = c->d_f2l_counts;
+    launch_f2_large(s, lp, (int)large.size(), depth ? (depth->normal ? 2 : 1) : 0, cls != nullptr);
+    LMX_HIP(hipGetLastError());
+    LMX_HIP(hipStreamSynchronize(s));
+    lcounts.resize(large.size() * 4);
+    LMX_HIP(hipMemcpy(lcounts.data(), c->d_f2l_counts, lcounts.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  }
+  // where each frame's result lies: 0 the LDS kernel's pinned rows, 1 the large kernel's workspace part, 2 nowhere yet (the host path)
+  std::vector<int> where(n_frames, 0);
+  lmx_chain_stats cs{};
+  cs.frames = n_frames;
+  for (int f = 0; f < n_frames; ++f) {
+    const uint32_t status = counts[(size_t)f * 4 + 3];
+    if (status == 1) cs.max_frame_records = std::max<int32_t>(cs.max_frame_records, (int32_t)std::min<uint32_t>(counts[(size_t)f * 4], 0x7fffffffu));
+    if (status == 0) { cs.frames_lds += 1; continue; }
+    if (large_part[f] >= 0 && lcounts[(size_t)large_part[f] * 4 + 3] == 0) { where[f] = 1; cs.frames_large += 1; continue; }
+    where[f] = 2;
+    if (status == 1 && large_part[f] < 0) cs.frames_host_records += 1;
+    else cs.frames_host_other += 1;
+  }
+  cs.large_workspace_bytes = (int64_t)c->f2l_ws_bytes;
+  c->chain_stats = cs;
+  // frames no kernel could take (too many records, rings outside the packed range): the host path on the slot's records
   std::vector<lmx_raw_match_t> host_recs;
-  bool any_host = false;
-  for (int f = 0; f < n_frames; ++f) any_host = any_host || counts[(size_t)f * 4 + 3] != 0;
+  const bool any_host = cs.frames_host_records + cs.frames_host_other > 0;
   if (any_host) {
     host_recs.resize(n_match);
     if (n_match) LMX_HIP(hipMemcpy(host_recs.data(), c->d_out_slot[slot] + 64, (size_t)n_match * sizeof(lmx_raw_match_t), hipMemcpyDeviceToHost));
@@ -432,7 +470,20 @@ static lmx_status collect_clusters_impl(const char* what, lmx_ctx* c, int32_t n_
     for (const lmx_ctx::ClassSidecar& k : c->f2_class) host_classes.push_back(lmx_class_sidecar{k.dists.data(), k.rects.data(), k.dists.size(), k.params});
   for (int f = 0; f < n_frames; ++f) {
     size_t nm = 0, nc = 0, nmem = 0;
-    if (counts[(size_t)f * 4 + 3] == 0) {
+    if (where[f] == 1) {   // the large kernel's part of the workspace: read back what its counts say
+      const uint32_t* lc = lcounts.data() + (size_t)large_part[f] * 4;
+      const uint8_t* part = c->d_f2l_ws + (size_t)large_part[f] * lay.bytes;
+      nm = lc[0]; nc = lc[1]; nmem = lc[2];
+      fm.resize(cap_matches ? nm : 0); fc.resize(nc); fmem.resize(nmem);
+      if (cap_matches && nm) {
+        LMX_HIP(hipMemcpy(fm.data(), part + lay.matches, nm * sizeof(lmx_match_t), hipMemcpyDeviceToHost));
+        if (depth && depth->diffs) { fd.resize(nm); LMX_HIP(hipMemcpy(fd.data(), part + lay.diffs, nm * sizeof(lmx_depth_diff_t), hipMemcpyDeviceToHost)); }
+        if (depth && depth->ndiffs) { fn.resize(nm); LMX_HIP(hipMemcpy(fn.data(), part + lay.ndiffs, nm * sizeof(lmx_normal_diff_t), hipMemcpyDeviceToHost)); }
+      }
+      if (nc) LMX_HIP(hipMemcpy(fc.data(), part + lay.clusters, nc * sizeof(lmx_cluster_t), hipMemcpyDeviceToHost));
+      if (nmem) LMX_HIP(hipMemcpy(fmem.data(), part + lay.members, nmem * sizeof(int32_t), hipMemcpyDeviceToHost));
+      if (cls) { fcls.resize(nc); if (nc) LMX_HIP(hipMemcpy(fcls.data(), part + lay.cluster_class, nc * sizeof(int32_t), hipMemcpyDeviceToHost)); }
+    } else if (where[f] == 0) {
       nm = counts[(size_t)f * 4 + 0]; nc = counts[(size_t)f * 4 + 1]; nmem = counts[(size_t)f * 4 + 2];
       if (cap_matches) fm.assign(all_m + (size_t)F2_MAX * f, all_m + (size_t)F2_MAX * f + nm);
       else fm.clear();
@@ -560,6 +611,12 @@ lmx_status lmx_ctx_collect_clusters_classes(lmx_ctx* c, int32_t n_frames, const 
   const ClassChain cls{score->class_base, score->n_classes, cluster_class};
   return collect_clusters_impl(what, c, n_frames, &depth, &cls, matches, cap_matches, match_offsets, clusters, cap_clusters, cluster_offsets, members, cap_members);
   });
+}
+
+lmx_status lmx_ctx_chain_stats(lmx_ctx* c, lmx_chain_stats* out) {
+  if (!c || !out) { set_error("lmx_ctx_chain_stats: null argument"); return LMX_ERR_INVALID_ARG; }
+  *out = c->chain_stats;
+  return LMX_OK;
 }
 
 lmx_status lmx_ctx_raw_matches(lmx_ctx* c, void** d_records, void** d_counts, size_t* capacity) {

@@ -193,6 +193,7 @@ CtxEnv read_ctx_env() {
   if (const char* e = std::getenv("LMX_SCORE_KERNEL")) v.score_variant = std::strcmp(e, "generic") == 0 ? 0 : (std::strcmp(e, "u8") == 0 ? 1 : 2);
   if (const char* e = std::getenv("LMX_SCORE_NO_PRUNE")) v.score_no_prune = *e && std::strcmp(e, "0") != 0;
   if (const char* e = std::getenv("LMX_COLOR_TILE")) v.color_tile = std::atoi(e);
+  if (const char* e = std::getenv("LMX_F2_LARGE")) v.f2_large = std::strcmp(e, "0") != 0;
   if (const char* e = std::getenv("LMX_GRAPH_DOT")) { v.graph_dot = true; v.graph_dot_dir = e; }
   return v;
 }
@@ -383,6 +384,9 @@ void lmx_ctx_destroy(lmx_ctx* c) {
   if (c->d_f2_rec_diffs) (void)hipFree(c->d_f2_rec_diffs);
   if (c->h_f2_ndiffs) (void)hipHostFree(c->h_f2_ndiffs);
   if (c->d_f2_rec_ndiffs) (void)hipFree(c->d_f2_rec_ndiffs);
+  if (c->d_f2l_ws) (void)hipFree(c->d_f2l_ws);
+  if (c->d_f2l_frames) (void)hipFree(c->d_f2l_frames);
+  if (c->d_f2l_counts) (void)hipFree(c->d_f2l_counts);
   if (c->h_mask_stage) (void)hipHostFree(c->h_mask_stage);
   if (c->h_class_thr) (void)hipHostFree(c->h_class_thr);
   if (c->mask_h2d) (void)hipEventDestroy(c->mask_h2d);

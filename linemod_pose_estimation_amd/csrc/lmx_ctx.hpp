@@ -67,6 +67,7 @@ struct CtxEnv {
   int score_variant = 2;           // LMX_SCORE_KERNEL = generic | u8 | sb (anything else): 0 | 1 | 2, see score_kernel_variant
   bool score_no_prune = false;     // LMX_SCORE_NO_PRUNE set, not empty and not "0": the scoring kernels do similarity()'s full work
   int color_tile = 0;              // LMX_COLOR_TILE = 16 | 32 pins the colour quantiser's tile height (A/B switch); 0 = by batch size (launch_color_quantize)
+  bool f2_large = true;            // LMX_F2_LARGE=0: frames of 2049 .. 16384 raw records are finished by the host, as before the large-frame kernels
   bool graph_dot = false;          // LMX_GRAPH_DOT = <directory>: one .dot file per captured hipGraph chain (diagnostics)
   std::string graph_dot_dir;
 };
@@ -250,6 +251,13 @@ struct lmx_ctx {
   std::vector<int32_t> f2_class_base;            // what d_f2_class_base holds
   int32_t* h_f2_cluster_class = nullptr;         // pinned, mapped: [F][F2_MAX], next to the clusters of h_f2_out
   int32_t* d_f2_cluster_class = nullptr;         // its device view
+  // the large-frame kernels (k_f2_large*, frames of F2_MAX + 1 .. F2_LARGE_MAX records): nothing allocated before the first such frame; the
+  // workspace holds one part (F2LargeLayout::bytes) per large frame of a call and grows on demand, like d_f2_rec_diffs
+  uint8_t* d_f2l_ws = nullptr;
+  size_t f2l_ws_bytes = 0;
+  int32_t* d_f2l_frames = nullptr;               // [F] the listed frames
+  uint32_t* d_f2l_counts = nullptr;              // [F][4]
+  lmx_chain_stats chain_stats{};                 // of the last lmx_ctx_collect_clusters* call (lmx_ctx_chain_stats)
   // stats / profiling
   int64_t stat_cands = 0, stat_matches = 0;
   uint32_t profiling = 0;  // bitmask over kernel ids

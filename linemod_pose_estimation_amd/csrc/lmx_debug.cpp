@@ -299,6 +299,63 @@ lmx_status lmx_debug_device_sort_perm(int32_t device, const float* similarity, c
   (void)hipFree(d_sim); (void)hipFree(d_tid); (void)hipFree(d_perm); (void)hipFree(d_spill);
   return st;
 }
+lmx_status lmx_debug_device_sort_perm_large(int32_t device, const float* similarity, const int32_t* template_id, int32_t n, int32_t* perm) {
+  if (n < 0 || n > F2_LARGE_MAX || (n > 0 && (!similarity || !template_id || !perm))) { set_error("lmx_debug_device_sort_perm_large: invalid argument (n <= %d)", F2_LARGE_MAX); return LMX_ERR_INVALID_ARG; }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available; this library has no CPU path"); return LMX_ERR_NO_DEVICE; }
+  if (n == 0) return LMX_OK;
+  LMX_HIP(hipSetDevice(device));
+  float* d_sim = nullptr; int* d_tid = nullptr; int* d_perm = nullptr; uint8_t* d_ws = nullptr;
+  auto run = [&]() -> lmx_status {
+    LMX_HIP(hipMalloc((void**)&d_sim, (size_t)n * 4)); LMX_HIP(hipMalloc((void**)&d_tid, (size_t)n * 4)); LMX_HIP(hipMalloc((void**)&d_perm, (size_t)n * 4));
+    LMX_HIP(hipMalloc((void**)&d_ws, f2_large_layout(false, false).bytes));
+    LMX_HIP(hipMemcpy(d_sim, similarity, (size_t)n * 4, hipMemcpyHostToDevice));
+    LMX_HIP(hipMemcpy(d_tid, template_id, (size_t)n * 4, hipMemcpyHostToDevice));
+    launch_debug_block_sort_large(nullptr, d_sim, d_tid, n, d_perm, d_ws);
+    LMX_HIP(hipGetLastError());
+    LMX_HIP(hipDeviceSynchronize());
+    LMX_HIP(hipMemcpy(perm, d_perm, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return LMX_OK;
+  };
+  const lmx_status st = run();
+  (void)hipFree(d_sim); (void)hipFree(d_tid); (void)hipFree(d_perm); (void)hipFree(d_ws);
+  return st;
+}
+// The large-frame kernels of a hook: every frame listed, one workspace part each (zeroed, as the LDS hooks zero their rows), then each
+// part's output rows copied to the caller's [n_frames][F2_LARGE_MAX] rows.  p.out_counts is the hook's device count words.
+static lmx_status debug_run_large(const F2Params& p, int32_t n_frames, int mode, bool classes, lmx_match_t* matches, lmx_depth_diff_t* diffs, lmx_normal_diff_t* ndiffs,
+                                  lmx_cluster_t* clusters, int32_t* cluster_class, int32_t* members) {
+  const F2LargeLayout lay = f2_large_layout(mode >= 1, mode == 2);
+  const size_t F = (size_t)n_frames, N = (size_t)F2_LARGE_MAX;
+  uint8_t* d_ws = nullptr;
+  int32_t* d_frames = nullptr;
+  auto run = [&]() -> lmx_status {
+    LMX_HIP(hipMalloc((void**)&d_ws, F * lay.bytes));
+    LMX_HIP(hipMalloc((void**)&d_frames, F * sizeof(int32_t)));
+    LMX_HIP(hipMemset(d_ws, 0, F * lay.bytes));
+    std::vector<int32_t> frames(F);
+    for (size_t f = 0; f < F; ++f) frames[f] = (int32_t)f;
+    LMX_HIP(hipMemcpy(d_frames, frames.data(), F * sizeof(int32_t), hipMemcpyHostToDevice));
+    const F2LargeParams lp{p, d_frames, d_ws, lay};
+    launch_f2_large(nullptr, lp, n_frames, mode, classes);
+    LMX_HIP(hipGetLastError());
+    LMX_HIP(hipDeviceSynchronize());
+    for (size_t f = 0; f < F; ++f) {
+      const uint8_t* part = d_ws + f * lay.bytes;
+      LMX_HIP(hipMemcpy(matches + f * N, part + lay.matches, N * sizeof(lmx_match_t), hipMemcpyDeviceToHost));
+      LMX_HIP(hipMemcpy(clusters + f * N, part + lay.clusters, N * sizeof(lmx_cluster_t), hipMemcpyDeviceToHost));
+      LMX_HIP(hipMemcpy(members + f * N, part + lay.members, N * sizeof(int32_t), hipMemcpyDeviceToHost));
+      if (cluster_class) LMX_HIP(hipMemcpy(cluster_class + f * N, part + lay.cluster_class, N * sizeof(int32_t), hipMemcpyDeviceToHost));
+      if (mode >= 1) LMX_HIP(hipMemcpy(diffs + f * N, part + lay.diffs, N * sizeof(lmx_depth_diff_t), hipMemcpyDeviceToHost));
+      if (mode == 2) LMX_HIP(hipMemcpy(ndiffs + f * N, part + lay.ndiffs, N * sizeof(lmx_normal_diff_t), hipMemcpyDeviceToHost));
+    }
+    return LMX_OK;
+  };
+  const lmx_status st = run();
+  if (st != LMX_OK) (void)hipDeviceSynchronize();
+  (void)hipFree(d_ws); (void)hipFree(d_frames);
+  return st;
+}
 // The whole device consumer chain (k_f2_finalize_cluster, as lmx_ctx_collect_clusters launches it) on a caller's record list: the records
 // become a raw-match slot of their own (16-dword header with [1] = n_records, cap = n_records), the kernel's outputs and per-frame count
 // words come back as written -- no host completion, so a test sees which path the kernel took.
@@ -307,7 +364,7 @@ lmx_status lmx_debug_device_sort_perm(int32_t device, const float* similarity, c
 static lmx_status debug_finalize_cluster(const char* what, int32_t device, const lmx_raw_match_t* records, size_t n_records, int32_t n_frames, lmx_depth_templates* templates,
                                          int32_t class_index, double no_value, const double* obj_origin_dists, const int32_t* rects, size_t n_templates,
                                          const lmx_cluster_params* params, lmx_match_t* matches, lmx_depth_diff_t* diffs, lmx_cluster_t* clusters,
-                                         int32_t* members, uint32_t* counts) {
+                                         int32_t* members, uint32_t* counts, bool large = false /* the large-frame kernels on every frame, rows of F2_LARGE_MAX */) {
   if ((n_records && !records) || !obj_origin_dists || !rects || n_templates == 0 || !params || !matches || !clusters || !members || !counts) {
     set_error("%s: invalid argument", what);
     return LMX_ERR_INVALID_ARG;
@@ -371,9 +428,14 @@ static lmx_status debug_finalize_cluster(const char* what, int32_t device, const
     if (templates) {
       if (lmx_status ds = depth_launch_records(templates, nullptr, d_recs, (uint32_t)n_records, class_index, d_rec_diffs)) return ds;
       p.diffs = d_rec_diffs; p.out_diffs = d_diffs; p.diff_scratch = d_diff_scratch; p.no_value = no_value;
-      launch_f2_scored(nullptr, p);
-    } else {
+      if (!large) launch_f2_scored(nullptr, p);
+    } else if (!large) {
       launch_f2(nullptr, p);
+    }
+    if (large) {
+      if (lmx_status ls = debug_run_large(p, n_frames, templates ? 1 : 0, false, matches, diffs, nullptr, clusters, nullptr, members)) return ls;
+      LMX_HIP(hipMemcpy(counts, d_counts, F * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+      return LMX_OK;
     }
     LMX_HIP(hipGetLastError());
     LMX_HIP(hipDeviceSynchronize());
@@ -396,29 +458,48 @@ lmx_status lmx_debug_device_finalize_cluster(int32_t device, const lmx_raw_match
   return debug_finalize_cluster("lmx_debug_device_finalize_cluster", device, records, n_records, n_frames, nullptr, -1, 0.0, obj_origin_dists, rects, n_templates, params, matches, nullptr, clusters,
                                 members, counts);
 }
+lmx_status lmx_debug_device_finalize_cluster_large(int32_t device, const lmx_raw_match_t* records, size_t n_records, int32_t n_frames,
+                                                   const double* obj_origin_dists, const int32_t* rects, size_t n_templates, const lmx_cluster_params* params,
+                                                   lmx_match_t* matches, lmx_cluster_t* clusters, int32_t* members, uint32_t* counts) {
+  return debug_finalize_cluster("lmx_debug_device_finalize_cluster_large", device, records, n_records, n_frames, nullptr, -1, 0.0, obj_origin_dists, rects, n_templates, params, matches,
+                                nullptr, clusters, members, counts, true);
+}
 // The scored form of the same hook: `depth` (n_frames 16UC1 host frames) becomes the templates' resident scene, then k_depth_diff_records and
 // k_f2_finalize_cluster_scored run on the stand-alone slot as lmx_ctx_collect_clusters_depth launches them.  No host completion.
+static lmx_status debug_finalize_cluster_depth(const char* what, bool large, int32_t device, const lmx_raw_match_t* records, size_t n_records, int32_t n_frames,
+                                               lmx_depth_templates* templates, const lmx_image* depth, int32_t class_index, double no_value,
+                                               const double* obj_origin_dists, const int32_t* rects, size_t n_templates, const lmx_cluster_params* params,
+                                               lmx_match_t* matches, lmx_depth_diff_t* diffs, lmx_cluster_t* clusters, int32_t* members, uint32_t* counts) {
+  if (!templates || !depth || !diffs) { set_error("%s: invalid argument", what); return LMX_ERR_INVALID_ARG; }
+  if (no_value != no_value) { set_error("%s: no_value is not a number", what); return LMX_ERR_INVALID_ARG; }
+  if (n_frames < 1 || n_frames > 8) { set_error("%s: n_frames must be 1..8 (got %d)", what, n_frames); return LMX_ERR_INVALID_ARG; }
+  if (depth_templates_scene(templates).device != device) { set_error("%s: the templates live on another device", what); return LMX_ERR_INVALID_ARG; }
+  std::lock_guard<std::mutex> lk(depth_templates_mutex(templates));   // held from the upload to the last launch: nobody replaces the scene between
+  if (lmx_status st = depth_upload_scene(templates, depth, n_frames)) return st;
+  return debug_finalize_cluster(what, device, records, n_records, n_frames, templates, class_index, no_value, obj_origin_dists, rects, n_templates, params, matches, diffs,
+                                clusters, members, counts, large);
+}
 lmx_status lmx_debug_device_finalize_cluster_depth(int32_t device, const lmx_raw_match_t* records, size_t n_records, int32_t n_frames,
                                                    lmx_depth_templates* templates, const lmx_image* depth, int32_t class_index, double no_value,
                                                    const double* obj_origin_dists, const int32_t* rects, size_t n_templates, const lmx_cluster_params* params,
                                                    lmx_match_t* matches, lmx_depth_diff_t* diffs, lmx_cluster_t* clusters, int32_t* members, uint32_t* counts) {
-  if (!templates || !depth || !diffs) { set_error("lmx_debug_device_finalize_cluster_depth: invalid argument"); return LMX_ERR_INVALID_ARG; }
-  if (no_value != no_value) { set_error("lmx_debug_device_finalize_cluster_depth: no_value is not a number"); return LMX_ERR_INVALID_ARG; }
-  if (n_frames < 1 || n_frames > 8) { set_error("lmx_debug_device_finalize_cluster_depth: n_frames must be 1..8 (got %d)", n_frames); return LMX_ERR_INVALID_ARG; }
-  if (depth_templates_scene(templates).device != device) { set_error("lmx_debug_device_finalize_cluster_depth: the templates live on another device"); return LMX_ERR_INVALID_ARG; }
-  std::lock_guard<std::mutex> lk(depth_templates_mutex(templates));   // held from the upload to the last launch: nobody replaces the scene between
-  if (lmx_status st = depth_upload_scene(templates, depth, n_frames)) return st;
-  return debug_finalize_cluster("lmx_debug_device_finalize_cluster_depth", device, records, n_records, n_frames, templates, class_index, no_value, obj_origin_dists, rects, n_templates, params, matches, diffs,
-                                clusters, members, counts);
+  return debug_finalize_cluster_depth("lmx_debug_device_finalize_cluster_depth", false, device, records, n_records, n_frames, templates, depth, class_index, no_value, obj_origin_dists,
+                                      rects, n_templates, params, matches, diffs, clusters, members, counts);
+}
+lmx_status lmx_debug_device_finalize_cluster_large_depth(int32_t device, const lmx_raw_match_t* records, size_t n_records, int32_t n_frames,
+                                                         lmx_depth_templates* templates, const lmx_image* depth, int32_t class_index, double no_value,
+                                                         const double* obj_origin_dists, const int32_t* rects, size_t n_templates, const lmx_cluster_params* params,
+                                                         lmx_match_t* matches, lmx_depth_diff_t* diffs, lmx_cluster_t* clusters, int32_t* members, uint32_t* counts) {
+  return debug_finalize_cluster_depth("lmx_debug_device_finalize_cluster_large_depth", true, device, records, n_records, n_frames, templates, depth, class_index, no_value,
+                                      obj_origin_dists, rects, n_templates, params, matches, diffs, clusters, members, counts);
 }
 // The hook for the CLASSES forms: the records as a slot of their own, the classes' side-cars as the device table, then what
 // lmx_ctx_collect_clusters_classes launches.  No host completion.
-lmx_status lmx_debug_device_finalize_cluster_classes(int32_t device, const lmx_raw_match_t* records, size_t n_records, int32_t n_frames,
-                                                     const lmx_class_sidecar* classes, int32_t n_classes, const lmx_class_score* score, const lmx_image* depth,
-                                                     lmx_match_t* matches, lmx_depth_diff_t* diffs, lmx_normal_diff_t* ndiffs, lmx_cluster_t* clusters,
-                                                     int32_t* cluster_class, int32_t* members, uint32_t* counts) {
-  return lmx::guarded("lmx_debug_device_finalize_cluster_classes", [&]() -> lmx_status {
-  const char* const what = "lmx_debug_device_finalize_cluster_classes";
+static lmx_status debug_finalize_cluster_classes(const char* what, bool large, int32_t device, const lmx_raw_match_t* records, size_t n_records, int32_t n_frames,
+                                                 const lmx_class_sidecar* classes, int32_t n_classes, const lmx_class_score* score, const lmx_image* depth,
+                                                 lmx_match_t* matches, lmx_depth_diff_t* diffs, lmx_normal_diff_t* ndiffs, lmx_cluster_t* clusters,
+                                                 int32_t* cluster_class, int32_t* members, uint32_t* counts) {
+  return lmx::guarded(what, [&]() -> lmx_status {
   const bool normals = score && score->normals != 0;
   if ((n_records && !records) || !classes || !matches || !clusters || !cluster_class || !members || !counts ||
       (score && (!score->templates || !score->class_base || !depth || !diffs)) || (normals && !ndiffs)) {
@@ -530,6 +611,11 @@ lmx_status lmx_debug_device_finalize_cluster_classes(int32_t device, const lmx_r
       p.diffs = d_rec_diffs; p.out_diffs = d_diffs; p.diff_scratch = d_diff_scratch; p.no_value = score->no_value;
       p.ndiffs = d_rec_ndiffs; p.out_ndiffs = d_ndiffs; p.ndiff_scratch = d_ndiff_scratch;
     }
+    if (large) {
+      if (lmx_status ls = debug_run_large(p, n_frames, score ? (normals ? 2 : 1) : 0, true, matches, diffs, ndiffs, clusters, cluster_class, members)) return ls;
+      LMX_HIP(hipMemcpy(counts, d_counts, F * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+      return LMX_OK;
+    }
     launch_f2_classes(nullptr, p, score ? (normals ? 2 : 1) : 0);
     LMX_HIP(hipGetLastError());
     LMX_HIP(hipDeviceSynchronize());
@@ -547,6 +633,20 @@ lmx_status lmx_debug_device_finalize_cluster_classes(int32_t device, const lmx_r
   for (void* q : owned) (void)hipFree(q);
   return st;
   });
+}
+lmx_status lmx_debug_device_finalize_cluster_classes(int32_t device, const lmx_raw_match_t* records, size_t n_records, int32_t n_frames,
+                                                     const lmx_class_sidecar* classes, int32_t n_classes, const lmx_class_score* score, const lmx_image* depth,
+                                                     lmx_match_t* matches, lmx_depth_diff_t* diffs, lmx_normal_diff_t* ndiffs, lmx_cluster_t* clusters,
+                                                     int32_t* cluster_class, int32_t* members, uint32_t* counts) {
+  return debug_finalize_cluster_classes("lmx_debug_device_finalize_cluster_classes", false, device, records, n_records, n_frames, classes, n_classes, score, depth, matches, diffs,
+                                        ndiffs, clusters, cluster_class, members, counts);
+}
+lmx_status lmx_debug_device_finalize_cluster_large_classes(int32_t device, const lmx_raw_match_t* records, size_t n_records, int32_t n_frames,
+                                                           const lmx_class_sidecar* classes, int32_t n_classes, const lmx_class_score* score,
+                                                           const lmx_image* depth, lmx_match_t* matches, lmx_depth_diff_t* diffs, lmx_normal_diff_t* ndiffs,
+                                                           lmx_cluster_t* clusters, int32_t* cluster_class, int32_t* members, uint32_t* counts) {
+  return debug_finalize_cluster_classes("lmx_debug_device_finalize_cluster_large_classes", true, device, records, n_records, n_frames, classes, n_classes, score, depth, matches,
+                                        diffs, ndiffs, clusters, cluster_class, members, counts);
 }
 lmx_status lmx_debug_introsort_perm_score(const double* score, int32_t n, int32_t* perm) {
   if (n < 0 || (n > 0 && (!score || !perm))) { set_error("lmx_debug_introsort_perm_score: invalid argument"); return LMX_ERR_INVALID_ARG; }

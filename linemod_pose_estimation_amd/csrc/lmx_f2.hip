@@ -17,8 +17,8 @@
 //   E  rcd_voting: key = {y / step, x / step, depth ring}; std::map order = bitonic sort by (key, position in the match list)
 //   F  clusters = runs of equal key: size filter, mean similarity (double), mean rect (integer division)       lane 0
 //   G  std::sort by score desc (emulated) + greedy IoU suppression at 0.4 with the reference's int/float arithmetic   lane 0
-// Frames with more than F2_MAX records are flagged and finished by the host path (lmx_cluster_matches), so the result is the
-// reference's for every input.
+// Frames with more than F2_MAX records are flagged (status 1); up to F2_LARGE_MAX records the large-frame form at the end of this file
+// finishes them in a second launch, beyond that the host path (lmx_cluster_matches), so the result is the reference's for every input.
 // The SCORED instantiation (lmx_ctx_collect_clusters_depth) ranks clusters by the reference's other score, the depth difference of
 // depth_normal_diff_calc: every raw record comes with a lmx_depth_diff_t (k_depth_diff_records, lmx_verify.hip) that travels with it through
 // B - D in two rows of device memory (LDS is full) and lands next to its final match; F averages dv::value of it instead of the similarity.
@@ -475,6 +475,385 @@ __global__ __launch_bounds__(256) void k_f2_finalize_cluster_normal(F2Params p) 
 __global__ __launch_bounds__(256) void k_f2_finalize_cluster_classes(F2Params p) { f2_finalize_cluster<F2_SIMILARITY, true>(p); }
 __global__ __launch_bounds__(256) void k_f2_finalize_cluster_classes_scored(F2Params p) { f2_finalize_cluster<F2_DEPTH, true>(p); }
 __global__ __launch_bounds__(256) void k_f2_finalize_cluster_classes_normal(F2Params p) { f2_finalize_cluster<F2_DEPTH_NORMAL, true>(p); }
+
+// ---- the large-frame form: frames of F2_MAX + 1 .. F2_LARGE_MAX records ------------------------------------------------------------------
+// The same stages with the same semantics and the same order of ties, for the frames the kernels above hand back with status 1.  What
+// changes is where the data lives and which stages run on one lane:
+//   * one workgroup of 1024 threads per listed frame; every per-record row (keys, tags, the match fields, the sort's seg / lpos / rpos)
+//     lies in the frame's part of a device-memory workspace (F2LargeLayout) that only this workgroup touches, every write separated from
+//     its reads by a __syncthreads().  LDS holds what is small and hot: the sort's per-range tables (1024 ranges), the cut bits and stage
+//     G's scores, order and suppression flags for up to F2L_GCAP clusters of a class (more: the workspace, on the same code);
+//   * the final list is written to the workspace once (out_matches, out_diffs, out_ndiffs) and stages E - G read it there: no parked and
+//     no final copy of the diffs;
+//   * F gives every run of equal vote key one thread, which sums its members sequentially in voted order (the double sum's order is
+//     observable); block scans find the runs and compact the surviving clusters in std::map order;
+//   * G keeps the sequential std::sort restatement on one lane (on LDS) and the sequential greedy loop over a; the suppression tests of
+//     all q > a of a kept a go across the workgroup; a block scan places the survivors and their member ranges;
+//   * vote keys carry a 14-bit list position: y / step 16 | x / step 16 | ring 18 | position 14 (x and y come from a short, so 16 bits
+//     lose nothing for step >= 1), classed: class 4 | y / step 16 | x / step 16 | ring 14 | position 14.  A ring outside +-2^17 (classed:
+//     +-2^13) gives status 2, as a ring outside the small kernels' range does there;
+//   * depth limit reached (median-of-three killers): the remaining ranges are heap-sorted one per thread, as above -- slow on device
+//     memory (tens of milliseconds for a 16384-record killer), exact, and no input a matcher produces.
+constexpr int F2L_T = 1024;
+constexpr int F2L_GCAP = 4096;   // clusters of one class whose stage G runs on LDS
+using F2LScratch = sortblk::ScratchT<1024, F2L_T>;
+
+struct F2LRows {   // one frame's part of the workspace
+  lmx_match_t* out_m; lmx_cluster_t* out_c; int32_t* out_mem; int32_t* out_cls; lmx_depth_diff_t* out_d; lmx_normal_diff_t* out_n;
+  unsigned long long *key, *spill, *c_range; double* c_score; int* c_rect;
+  float* sim; int *tid, *rec; short *x, *y; unsigned short *cls, *perm, *keep, *seg, *rpos;
+};
+__device__ __forceinline__ F2LRows f2l_rows(uint8_t* w, const F2LargeLayout& l) {
+  F2LRows r;
+  r.out_m = reinterpret_cast<lmx_match_t*>(w + l.matches); r.out_c = reinterpret_cast<lmx_cluster_t*>(w + l.clusters);
+  r.out_mem = reinterpret_cast<int32_t*>(w + l.members); r.out_cls = reinterpret_cast<int32_t*>(w + l.cluster_class);
+  r.out_d = reinterpret_cast<lmx_depth_diff_t*>(w + l.diffs); r.out_n = reinterpret_cast<lmx_normal_diff_t*>(w + l.ndiffs);
+  r.key = reinterpret_cast<unsigned long long*>(w + l.key); r.spill = reinterpret_cast<unsigned long long*>(w + l.spill);
+  r.c_range = reinterpret_cast<unsigned long long*>(w + l.c_range); r.c_score = reinterpret_cast<double*>(w + l.c_score);
+  r.c_rect = reinterpret_cast<int*>(w + l.c_rect);
+  r.sim = reinterpret_cast<float*>(w + l.sim); r.tid = reinterpret_cast<int*>(w + l.tid); r.rec = reinterpret_cast<int*>(w + l.rec);
+  r.x = reinterpret_cast<short*>(w + l.x); r.y = reinterpret_cast<short*>(w + l.y);
+  r.cls = reinterpret_cast<unsigned short*>(w + l.cls); r.perm = reinterpret_cast<unsigned short*>(w + l.perm);
+  r.keep = reinterpret_cast<unsigned short*>(w + l.keep); r.seg = reinterpret_cast<unsigned short*>(w + l.seg);
+  r.rpos = reinterpret_cast<unsigned short*>(w + l.rpos);
+  return r;
+}
+
+// test hook (lmx_debug_device_sort_perm_large): the permutation sortblk::sort produces for n <= F2_LARGE_MAX pairs, on the rows and with
+// the scratch the large kernel gives it
+__global__ __launch_bounds__(F2L_T) void k_debug_block_sort_large(const float* sim, const int* tid_in, int n, int* perm, uint8_t* ws, F2LargeLayout lay) {
+  __shared__ F2LScratch S;
+  __shared__ uint32_t s_cut[F2_LARGE_MAX / 32];
+  const F2LRows r = f2l_rows(ws, lay);
+  if (threadIdx.x == 0) { S.seg = r.seg; S.lpos = r.keep; S.rpos = r.rpos; S.cut_bits = s_cut; }
+  for (int i = threadIdx.x; i < n; i += F2L_T) { r.key[i] = match_sort_key(sim[i], tid_in[i]); r.perm[i] = (unsigned short)i; }
+  __syncthreads();
+  sortblk::sort<F2_LARGE_MAX>(r.key, r.perm, n, S, r.spill);
+  for (int i = threadIdx.x; i < n; i += F2L_T) perm[i] = r.perm[i];
+}
+
+template <int MODE, bool CLASSES>
+__device__ __forceinline__ void f2_large(const F2LargeParams& lp) {
+  constexpr bool SCORED = MODE != F2_SIMILARITY, NORMAL = MODE == F2_DEPTH_NORMAL;
+  constexpr int NMAX = F2_LARGE_MAX, T = F2L_T;
+  constexpr int PER = NMAX / T;   // items per thread where a thread owns a block of positions
+  constexpr int POS = 14;         // bits of a match's list position in a vote key
+  constexpr unsigned POS_MASK = (1u << POS) - 1u;
+  __shared__ F2LScratch S;
+  __shared__ uint32_t s_cut[NMAX / 32];
+  __shared__ double s_gscore[F2L_GCAP];
+  __shared__ unsigned short s_gperm[F2L_GCAP], s_gsup[F2L_GCAP];
+  __shared__ int s_n, s_nfinal, s_bad, s_valid, s_total, s_cbegin[F2_CLASSES + 1];
+  const F2Params& p = lp.p;
+  const int tid = threadIdx.x, frame = lp.frames[blockIdx.x];
+  const F2LRows r = f2l_rows(lp.ws + (size_t)blockIdx.x * lp.lay.bytes, lp.lay);
+  uint32_t* counts = p.out_counts + (size_t)blockIdx.x * 4;
+  const F2Class* const tab = p.classes;
+  if (tid == 0) { s_n = 0; s_nfinal = 0; s_bad = 0; s_valid = 0; }
+  __syncthreads();
+  // A: this frame's records (order arbitrary), identified by their index in the slot's list
+  const uint32_t n_total = min(p.hdr[1], p.cap);
+  for (uint32_t i = tid; i < n_total; i += T)
+    if (p.recs[i].frame == frame) {
+      const int pos = atomicAdd(&s_n, 1);
+      if (pos < NMAX) { r.key[pos] = p.recs[i].order_key; r.rec[pos] = (int)i; }
+    }
+  __syncthreads();
+  const int n = s_n;
+  if (n > NMAX) {   // the host finishes this frame
+    if (tid == 0) { counts[0] = (uint32_t)n; counts[1] = 0; counts[2] = 0; counts[3] = 1; }
+    return;
+  }
+  // B: insertion order.  The keys are unique: sort them alone and find each record's rank by binary search of its key (kept in spill)
+  int n2 = 1;
+  while (n2 < n) n2 <<= 1;
+  for (int i = tid; i < n2; i += T) {
+    if (i < n) r.spill[i] = r.key[i];
+    else r.key[i] = ~0ull;
+  }
+  __syncthreads();
+  bitonic_sort_u64(r.key, n2, tid, T);
+  for (int i = tid; i < n; i += T) {
+    const unsigned long long k = r.spill[i];
+    int lo = 0, hi = n - 1;
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (r.key[mid] < k) lo = mid + 1; else hi = mid; }
+    r.perm[lo] = (unsigned short)i;   // insertion position lo holds arrival slot i
+  }
+  __syncthreads();
+  for (int i = tid; i < n; i += T) r.tid[i] = r.rec[r.perm[i]];   // record index by insertion position (tid borrowed)
+  __syncthreads();
+  for (int i = tid; i < n; i += T) {
+    const int ri = r.tid[i];
+    const lmx_raw_match_t m = p.recs[ri];
+    r.rec[i] = ri;
+    r.sim[i] = m.similarity; r.tid[i] = m.template_id; r.x[i] = (short)m.x; r.y[i] = (short)m.y; r.cls[i] = (unsigned short)m.class_index;
+  }
+  __syncthreads();
+  // C: std::sort with Match::operator<, order of ties as libstdc++ leaves it
+  if (tid == 0) { S.seg = r.seg; S.lpos = r.keep; S.rpos = r.rpos; S.cut_bits = s_cut; }
+  for (int i = tid; i < n; i += T) { r.key[i] = match_sort_key(r.sim[i], r.tid[i]); r.perm[i] = (unsigned short)i; }
+  __syncthreads();
+  sortblk::sort<NMAX>(r.key, r.perm, n, S, r.spill);
+  // D: std::unique.  Thread t owns positions t * PER .. t * PER + PER - 1; the kept elements' output positions come from a block scan
+  {
+    uint32_t kf[PER], sc[PER];
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+      const int j = tid * PER + q;
+      bool keep = j < n;
+      if (keep && j > 0) {
+        const int a = r.perm[j - 1], b = r.perm[j];
+        keep = !(r.x[a] == r.x[b] && r.y[a] == r.y[b] && r.sim[a] == r.sim[b] && r.cls[a] == r.cls[b]);
+      }
+      kf[q] = keep ? 1u : 0u;
+      sc[q] = kf[q];
+    }
+    sortblk::block_scan_inclusive<PER>(sc, S.wave_sum, tid);
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+      const int j = tid * PER + q;
+      if (j < n) r.keep[j] = (unsigned short)(kf[q] ? sc[q] - 1u : 0xffffu);
+      if (j == n - 1) s_nfinal = (int)sc[q];
+    }
+  }
+  __syncthreads();
+  const int nf = s_nfinal;
+  // the final list, with each match's diffs next to it: written once, read by E - G
+  for (int j = tid; j < n; j += T) {
+    const int d = r.keep[j];
+    if (d == 0xffff) continue;
+    const int src = r.perm[j];
+    lmx_match_t m;
+    m.x = r.x[src]; m.y = r.y[src]; m.similarity = r.sim[src]; m.template_id = r.tid[src]; m.class_index = r.cls[src];
+    r.out_m[d] = m;
+    if constexpr (SCORED) r.out_d[d] = p.diffs[r.rec[src]];
+    if constexpr (NORMAL) r.out_n[d] = p.ndiffs[r.rec[src]];
+  }
+  __syncthreads();
+  if (!p.do_clusters) {
+    if (tid == 0) { counts[0] = (uint32_t)nf; counts[1] = 0; counts[2] = 0; counts[3] = 0; }
+    return;
+  }
+  // E: rcd_voting keys, offset-binary fields; padding and (classed) matches whose class has no side-car get the all-ones key
+  int nf2 = 1;
+  while (nf2 < nf) nf2 <<= 1;
+  for (int j = tid; j < nf2; j += T) {
+    unsigned long long key = ~0ull;
+    if (j < nf) {
+      const lmx_match_t m = r.out_m[j];
+      const int t = m.template_id;
+      if constexpr (CLASSES) {
+        const int c = m.class_index;
+        if (c < F2_CLASSES && tab[c].n_templates != 0) {
+          if (t < 0 || (uint32_t)t >= tab[c].n_templates) atomicOr(&s_bad, 1);
+          else {
+            const int iy = m.y / tab[c].step, ix = m.x / tab[c].step;
+            const float depth = (float)tab[c].dists[t];
+            const float ring_step = (float)tab[c].radius_step;
+            const int ring = (int)((depth - tab[c].radius_min) / ring_step);   // float - double -> double, / float -> double, like the reference
+            const long long fr = (long long)ring + (1 << 13);
+            if (fr < 0 || fr >= (1 << 14)) atomicOr(&s_bad, 2);
+            else {
+              key = ((unsigned long long)c << 60) | ((unsigned long long)(iy + (1 << 15)) << 44) | ((unsigned long long)(ix + (1 << 15)) << 28) |
+                    ((unsigned long long)fr << POS) | (unsigned long long)j;
+              atomicAdd(&s_valid, 1);
+            }
+          }
+        }
+      } else {
+        if (t < 0 || (uint32_t)t >= p.n_templates) atomicOr(&s_bad, 1);
+        else {
+          const int iy = m.y / p.step, ix = m.x / p.step;
+          const float depth = (float)p.dists[t];
+          const float ring_step = (float)p.radius_step;
+          const int ring = (int)((depth - p.radius_min) / ring_step);
+          const long long fr = (long long)ring + (1 << 17);
+          if (fr < 0 || fr >= (1 << 18)) atomicOr(&s_bad, 2);
+          else key = ((unsigned long long)(iy + (1 << 15)) << 48) | ((unsigned long long)(ix + (1 << 15)) << 32) | ((unsigned long long)fr << POS) | (unsigned long long)j;
+        }
+      }
+    }
+    r.key[j] = key;
+  }
+  __syncthreads();
+  if (s_bad) {   // side-car too short / ring outside the packed range: host path
+    if (tid == 0) { counts[0] = (uint32_t)nf; counts[1] = 0; counts[2] = 0; counts[3] = 2; }
+    return;
+  }
+  bitonic_sort_u64(r.key, nf2, tid, T);
+  const int nv = CLASSES ? s_valid : nf;   // the sorted keys 0 .. nv - 1 are the matches that vote
+  // F: clusters in std::map order = runs of equal key above the position bits.  Run starts (seg is free again), then the runs that pass
+  // cluster_filter compacted in order, then one thread per surviving run
+  unsigned short* const run_start = r.seg;
+  {
+    uint32_t fl[PER], sc[PER];
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+      const int k = tid * PER + q;
+      fl[q] = (k < nv && (k == 0 || (r.key[k] >> POS) != (r.key[k - 1] >> POS))) ? 1u : 0u;
+      sc[q] = fl[q];
+    }
+    sortblk::block_scan_inclusive<PER>(sc, S.wave_sum, tid);
+#pragma unroll
+    for (int q = 0; q < PER; ++q)
+      if (fl[q]) run_start[sc[q] - 1u] = (unsigned short)(tid * PER + q);
+    if (tid == T - 1) s_total = (int)sc[PER - 1];
+  }
+  __syncthreads();
+  const int n_runs = s_total;
+  __syncthreads();
+  {
+    uint32_t fl[PER], sc[PER], rb[PER], rc[PER];
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+      const int k = tid * PER + q;
+      fl[q] = 0; rb[q] = 0; rc[q] = 0;
+      if (k < n_runs) {
+        rb[q] = run_start[k];
+        rc[q] = (uint32_t)(k + 1 < n_runs ? run_start[k + 1] : nv) - rb[q];
+        const int thresh = CLASSES ? tab[r.key[rb[q]] >> 60].size_thresh : p.size_thresh;
+        fl[q] = (int)rc[q] > thresh ? 1u : 0u;   // cluster_filter: drop clusters with size <= thresh
+      }
+      sc[q] = fl[q];
+    }
+    sortblk::block_scan_inclusive<PER>(sc, S.wave_sum, tid);
+#pragma unroll
+    for (int q = 0; q < PER; ++q)
+      if (fl[q]) r.c_range[sc[q] - 1u] = ((unsigned long long)rb[q] << 32) | rc[q];   // begin << 32 | count
+    if (tid == T - 1) s_total = (int)sc[PER - 1];
+    if (tid <= F2_CLASSES) s_cbegin[tid] = -1;
+  }
+  __syncthreads();
+  const int nc = s_total;
+  for (int ci = tid; ci < nc; ci += T) {
+    const int b = (int)(r.c_range[ci] >> 32), cnt = (int)(r.c_range[ci] & 0xffffffffu);
+    const int32_t* rects = p.rects;
+    if constexpr (CLASSES) {
+      const int c = (int)(r.key[b] >> 60);
+      rects = tab[c].rects;
+      if (ci == 0 || (int)(r.key[(int)(r.c_range[ci - 1] >> 32)] >> 60) != c) s_cbegin[c] = ci;   // the class's first cluster
+    }
+    double sum = 0.0;
+    int X = 0, Y = 0, Wd = 0, Ht = 0;
+    for (int k = b; k < b + cnt; ++k) {
+      const int j = (int)(r.key[k] & POS_MASK);
+      const lmx_match_t m = r.out_m[j];
+      if constexpr (NORMAL) sum += nv::value(r.out_d[j], r.out_n[j], p.no_value);
+      else if constexpr (SCORED) sum += dv::value(r.out_d[j], p.no_value);
+      else sum += (double)m.similarity;
+      const int32_t* rr = rects + (size_t)m.template_id * 4;
+      X += m.x; Y += m.y; Wd += rr[2]; Ht += rr[3];
+    }
+    r.c_score[ci] = sum / cnt;
+    // upstream: `int X; ... X /= matches.size();` -- see div_by_size
+    r.c_rect[4 * ci + 0] = div_by_size(X, cnt); r.c_rect[4 * ci + 1] = div_by_size(Y, cnt);
+    r.c_rect[4 * ci + 2] = div_by_size(Wd, cnt); r.c_rect[4 * ci + 3] = div_by_size(Ht, cnt);
+  }
+  __syncthreads();
+  // G, one class's clusters at a time (un-classed: all of them): std::sort by score on one lane, greedy NMS with the suppression tests
+  // of a kept cluster across the workgroup, survivors placed by a block scan
+  int n_out = 0, n_mem = 0;
+  for (int c = 0; c < (CLASSES ? F2_CLASSES : 1); ++c) {
+    int cb = 0, ce = nc;
+    if constexpr (CLASSES) {
+      cb = s_cbegin[c];
+      if (cb < 0) continue;
+      for (int c2 = c + 1; c2 < F2_CLASSES; ++c2)
+        if (s_cbegin[c2] >= 0) { ce = s_cbegin[c2]; break; }
+    }
+    const int m = ce - cb;
+    if (m <= 0) continue;
+    // order and suppression flags: LDS, or the rows the big sort is done with
+    double* const gscore = m <= F2L_GCAP ? s_gscore : r.c_score + cb;
+    unsigned short* const gperm = m <= F2L_GCAP ? s_gperm : r.perm;
+    unsigned short* const gsup = m <= F2L_GCAP ? s_gsup : r.keep;
+    const int* const crect = r.c_rect + 4 * (size_t)cb;
+    for (int i = tid; i < m; i += T) {
+      if (m <= F2L_GCAP) gscore[i] = r.c_score[cb + i];
+      gperm[i] = (unsigned short)i; gsup[i] = 0;
+    }
+    __syncthreads();
+    if (tid == 0) sortemu::sort(gperm, m, [&](unsigned short a, unsigned short b) { return gscore[a] > gscore[b]; });
+    __syncthreads();
+    for (int a = 0; a < m; ++a) {
+      const int pa = gperm[a];
+      if (gsup[pa]) continue;   // the same for every thread: flags are written before a barrier, read after it
+      for (int q = a + 1 + tid; q < m; q += T) {
+        const int pq = gperm[q];
+        if (!gsup[pq]) {
+          const double v = (double)box_iou(&crect[4 * pa], &crect[4 * pq]);
+          if (v > 0.4) gsup[pq] = 1;
+        }
+      }
+      __syncthreads();
+    }
+    // survivors in sorted order; a thread owns PER consecutive ranks.  One scan of kept << 0 | members << 16 (both <= 16384)
+    {
+      uint32_t fl[PER], sc[PER];
+#pragma unroll
+      for (int q = 0; q < PER; ++q) {
+        const int a = tid * PER + q;
+        fl[q] = 0;
+        if (a < m && !gsup[gperm[a]]) fl[q] = 1u | ((uint32_t)(r.c_range[cb + gperm[a]] & 0xffffffffu) << 16);
+        sc[q] = fl[q];
+      }
+      sortblk::block_scan_inclusive<PER>(sc, S.wave_sum, tid);
+#pragma unroll
+      for (int q = 0; q < PER; ++q) {
+        if (!fl[q]) continue;
+        const int ci = cb + gperm[tid * PER + q];
+        const int first = (int)(r.c_range[ci] >> 32), cnt = (int)(fl[q] >> 16);
+        const int at = n_out + (int)(sc[q] & 0xffffu) - 1, mem_at = n_mem + (int)(sc[q] >> 16) - cnt;
+        lmx_cluster_t o;
+        const unsigned long long key = r.key[first];
+        if constexpr (CLASSES) {
+          o.index[0] = (int)((key >> 44) & 0xffff) - (1 << 15);
+          o.index[1] = (int)((key >> 28) & 0xffff) - (1 << 15);
+          o.index[2] = (int)((key >> POS) & 0x3fff) - (1 << 13);
+          r.out_cls[at] = c;
+        } else {
+          o.index[0] = (int)((key >> 48) & 0xffff) - (1 << 15);
+          o.index[1] = (int)((key >> 32) & 0xffff) - (1 << 15);
+          o.index[2] = (int)((key >> POS) & 0x3ffff) - (1 << 17);
+        }
+        for (int k = 0; k < 4; ++k) o.rect[k] = r.c_rect[4 * ci + k];
+        o.score = r.c_score[ci];
+        o.member_begin = mem_at; o.member_count = cnt;
+        for (int k = 0; k < cnt; ++k) r.out_mem[mem_at + k] = (int32_t)(r.key[first + k] & POS_MASK);
+        r.out_c[at] = o;
+      }
+      if (tid == T - 1) s_total = (int)sc[PER - 1];
+      __syncthreads();
+      n_out += s_total & 0xffff; n_mem += s_total >> 16;
+      __syncthreads();
+    }
+  }
+  if (tid == 0) { counts[0] = (uint32_t)nf; counts[1] = (uint32_t)n_out; counts[2] = (uint32_t)n_mem; counts[3] = 0; }
+}
+
+__global__ __launch_bounds__(F2L_T) void k_f2_large(F2LargeParams p) { f2_large<F2_SIMILARITY, false>(p); }
+__global__ __launch_bounds__(F2L_T) void k_f2_large_scored(F2LargeParams p) { f2_large<F2_DEPTH, false>(p); }
+__global__ __launch_bounds__(F2L_T) void k_f2_large_normal(F2LargeParams p) { f2_large<F2_DEPTH_NORMAL, false>(p); }
+__global__ __launch_bounds__(F2L_T) void k_f2_large_classes(F2LargeParams p) { f2_large<F2_SIMILARITY, true>(p); }
+__global__ __launch_bounds__(F2L_T) void k_f2_large_classes_scored(F2LargeParams p) { f2_large<F2_DEPTH, true>(p); }
+__global__ __launch_bounds__(F2L_T) void k_f2_large_classes_normal(F2LargeParams p) { f2_large<F2_DEPTH_NORMAL, true>(p); }
+
+void launch_debug_block_sort_large(hipStream_t s, const float* sim, const int* tid, int n, int* perm, uint8_t* ws) {
+  hipLaunchKernelGGL(k_debug_block_sort_large, dim3(1), dim3(F2L_T), 0, s, sim, tid, n, perm, ws, f2_large_layout(false, false));
+}
+
+void launch_f2_large(hipStream_t s, const F2LargeParams& p, int n_listed, int mode, bool classes) {
+  const dim3 grid((unsigned)n_listed), block(F2L_T);
+  if (classes) {
+    if (mode == F2_DEPTH_NORMAL) hipLaunchKernelGGL(k_f2_large_classes_normal, grid, block, 0, s, p);
+    else if (mode == F2_DEPTH) hipLaunchKernelGGL(k_f2_large_classes_scored, grid, block, 0, s, p);
+    else hipLaunchKernelGGL(k_f2_large_classes, grid, block, 0, s, p);
+  } else {
+    if (mode == F2_DEPTH_NORMAL) hipLaunchKernelGGL(k_f2_large_normal, grid, block, 0, s, p);
+    else if (mode == F2_DEPTH) hipLaunchKernelGGL(k_f2_large_scored, grid, block, 0, s, p);
+    else hipLaunchKernelGGL(k_f2_large, grid, block, 0, s, p);
+  }
+}
 
 void launch_debug_block_sort(hipStream_t s, const float* sim, const int* tid, int n, int* perm, unsigned long long* spill) {
   hipLaunchKernelGGL(k_debug_block_sort, dim3(1), dim3(256), 0, s, sim, tid, n, perm, spill);

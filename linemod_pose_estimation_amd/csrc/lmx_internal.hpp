@@ -308,7 +308,7 @@ void launch_depth_quantize(hipStream_t s, const uint16_t* depth, uint8_t* quant,
                            int difference_threshold, const uint8_t* lut_bins /* device, [LMX_NORMAL_LUT_SIZE] median bins */,
                            uint32_t* clear16 = nullptr);
 // device form of "finalise + cluster" (lmx_f2.hip)
-constexpr int F2_MAX = 2048;   // records per frame the LDS path takes; larger frames are finished by the host
+constexpr int F2_MAX = 2048;   // records per frame the LDS path takes; larger frames go to the large-frame kernels (F2_LARGE_MAX) or the host
 // One class's side-car as the CLASSES forms read it; n_templates 0: the class has none, its matches are listed and belong to no cluster
 constexpr int F2_CLASSES = 16;
 struct F2Class {
@@ -351,6 +351,38 @@ void launch_f2_scored(hipStream_t s, const F2Params& p);
 void launch_f2_normal(hipStream_t s, const F2Params& p);
 // the per-class chain (lmx_ctx_collect_clusters_classes); mode 0 mean similarity, 1 depth score, 2 depth + normal score
 void launch_f2_classes(hipStream_t s, const F2Params& p, int mode);
+
+// The large-frame form of the same chain (k_f2_large*, lmx_f2.hip): frames of up to F2_LARGE_MAX raw records, one workgroup of 1024
+// threads per LISTED frame, every per-record row in that frame's part of a device-memory workspace (a record costs 8 bytes of LDS in the
+// kernels above; 16384 of them do not fit).  A frame's part holds its outputs and the kernel's scratch rows at the offsets of
+// F2LargeLayout; the host reads back what the count words say.
+constexpr int F2_LARGE_MAX = 16384;
+struct F2LargeLayout {   // byte offsets into one frame's part of the workspace; rows of F2_LARGE_MAX elements
+  uint32_t matches, clusters, members, cluster_class, diffs, ndiffs;   // outputs (diffs / ndiffs: the scored / normal forms only)
+  uint32_t key, spill, sim, tid, rec, x, y, cls, perm, keep, seg, rpos, c_score, c_range, c_rect;
+  uint32_t bytes;        // one frame's part, a multiple of 256
+};
+inline F2LargeLayout f2_large_layout(bool scored, bool normal) {
+  F2LargeLayout l{};
+  uint32_t at = 0;
+  auto row = [&](uint32_t elem) { const uint32_t o = at; at += (uint32_t)F2_LARGE_MAX * elem; return o; };
+  l.matches = row(sizeof(lmx_match_t)); l.clusters = row(sizeof(lmx_cluster_t)); l.members = row(4); l.cluster_class = row(4);
+  l.diffs = scored ? row(sizeof(lmx_depth_diff_t)) : 0; l.ndiffs = normal ? row(sizeof(lmx_normal_diff_t)) : 0;
+  l.key = row(8); l.spill = row(8); l.c_score = row(8); l.c_range = row(8); l.c_rect = row(16);
+  l.sim = row(4); l.tid = row(4); l.rec = row(4);
+  l.x = row(2); l.y = row(2); l.cls = row(2); l.perm = row(2); l.keep = row(2); l.seg = row(2); l.rpos = row(2);
+  l.bytes = (at + 255u) & ~255u;
+  return l;
+}
+struct F2LargeParams {
+  F2Params p;              // recs .. no_value and classes as above; out_counts is [n listed frames][4] (status as above, never 1 for a frame of
+                           // <= F2_LARGE_MAX records); the other out_* pointers and the scratch pointers are not used
+  const int32_t* frames;   // [grid] the frames to finish, device memory; workgroup i takes frames[i] and part i of the workspace
+  uint8_t* ws;             // [grid][lay.bytes] device memory
+  F2LargeLayout lay;
+};
+void launch_f2_large(hipStream_t s, const F2LargeParams& p, int n_listed, int mode, bool classes);
+void launch_debug_block_sort_large(hipStream_t s, const float* sim, const int* tid, int n, int* perm, uint8_t* ws /* f2_large_layout(false, false).bytes */);
 
 // ---- depth check against a resident scene (lmx_verify.hip), for the scored consumer chain (lmx_collect.cpp, lmx_debug.cpp) --------------
 struct DepthSceneInfo { int32_t device, count, n_frames, W, H, normals; };   // n_frames 0: no scene uploaded; normals: enable_normals was called

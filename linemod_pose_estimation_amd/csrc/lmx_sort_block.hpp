@@ -35,7 +35,12 @@ constexpr int kThreads = 256;
 constexpr int kLeaf = 16;          // libstdc++'s _S_threshold
 constexpr int kMaxRanges = 128;    // ranges of > 16 elements among <= 2048
 
-struct Scratch {                   // LDS, besides key[] / tag[] themselves
+// RANGES: ranges of > 16 elements a level can hold (<= NMAX / 17); THREADS: the workgroup's size.  The large-frame chain (lmx_f2.hip,
+// 16384 elements, 1024 threads) uses ScratchT<1024, 1024>; key[], tag[], seg, lpos and rpos may then lie in device memory -- every
+// write is separated from its reads by a __syncthreads(), and only this workgroup touches them
+template <int RANGES, int THREADS>
+struct ScratchT {                  // LDS, besides key[] / tag[] themselves
+  static constexpr int kMaxRanges = RANGES, kThreads = THREADS;
   unsigned short* seg;             // [n] range of the level an element belongs to, 0xffff = none
   unsigned short* lpos;            // [n]
   unsigned short* rpos;            // [n]
@@ -47,6 +52,7 @@ struct Scratch {                   // LDS, besides key[] / tag[] themselves
   uint32_t wave_sum[kThreads / 64];
   int n_next;
 };
+using Scratch = ScratchT<kMaxRanges, kThreads>;
 
 // inclusive sum over the block of `v[0..PER)` per thread (thread t owns elements t*PER .. t*PER+PER-1): v becomes the inclusive scan
 template <int PER>
@@ -71,8 +77,10 @@ __device__ __forceinline__ void block_scan_inclusive(uint32_t (&v)[PER], uint32_
 
 // key[0..n), tag[0..n) in LDS -> sorted exactly as std::sort would leave them.  All kThreads threads of the workgroup call it.
 // `spill` (global memory, >= 8 * n bytes per workgroup) is used by the heap-sort fallback only.
-template <int NMAX>
-__device__ void sort(unsigned long long* key, unsigned short* tag, int n, Scratch& S, unsigned long long* spill) {
+template <int NMAX, typename SCRATCH = Scratch>
+__device__ void sort(unsigned long long* key, unsigned short* tag, int n, SCRATCH& S, unsigned long long* spill) {
+  constexpr int kThreads = SCRATCH::kThreads;
+  static_assert(NMAX <= 17 * SCRATCH::kMaxRanges && NMAX < 0xffff, "a level's ranges and the 16-bit positions");
   constexpr int PER = NMAX / kThreads;
   static_assert(NMAX % kThreads == 0, "whole elements per thread");
   const int tid = threadIdx.x;

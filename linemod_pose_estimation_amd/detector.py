@@ -613,6 +613,14 @@ class Detector:
         _lib.check(_lib.lib().lmx_ctx_stats(self.h, C.byref(a), C.byref(b)))
         return {"candidates": a.value, "raw_matches": b.value}
 
+    def chain_stats(self):
+        """Which path completed the frames of the last collect_clusters* call (lmx_ctx_chain_stats): frames, frames_lds (at most F2_MAX raw
+        records), frames_large (up to F2_LARGE_MAX, the large-frame kernel), frames_host_records, frames_host_other (side-car / ring range),
+        max_frame_records (largest raw count among the frames beyond F2_MAX; 0: none) and large_workspace_bytes."""
+        s = _lib.ChainStats()
+        _lib.check(_lib.lib().lmx_ctx_chain_stats(self.h, C.byref(s)))
+        return {k: int(getattr(s, k)) for k, _ in _lib.ChainStats._fields_}
+
     def set_profiling(self, on=True):
         """on: True = every kernel, False = none, or a kernel name / list of names (only those get HIP events)."""
         L = _lib.lib()
@@ -990,11 +998,12 @@ class DepthTemplates:
             pass
 
 
-F2_MAX = 2048   # records per frame the device chain takes (csrc/lmx_internal.hpp)
+F2_MAX = 2048   # records per frame the device chain's LDS kernels take (csrc/lmx_internal.hpp)
+F2_LARGE_MAX = 16384   # ... and its large-frame kernels; beyond it the host finishes the frame
 
 
 def debug_device_finalize_cluster(records, n_frames, obj_origin_dists, rects, vote_row_col_step, renderer_radius_min, renderer_radius_step,
-                                  cluster_size_thresh=2, device=0, with_counts=False):
+                                  cluster_size_thresh=2, device=0, with_counts=False, large=False):
     """Test hook (lmx_debug_device_finalize_cluster): the kernel behind Detector.collect_clusters on a caller's RAW_MATCH_DTYPE records
     (all frames in one list, tagged by `frame`) -> list per frame of (matches, clusters, members, status), cut to the counts the
     kernel reported and otherwise as it wrote them: no host completion.  status 1 (more than F2_MAX records): all three are empty;
@@ -1004,12 +1013,14 @@ def debug_device_finalize_cluster(records, n_frames, obj_origin_dists, rects, vo
     rects = np.ascontiguousarray(rects, np.int32).reshape(-1, 4)
     pp = _lib.ClusterParams(int(vote_row_col_step), float(renderer_radius_min), float(renderer_radius_step), int(cluster_size_thresh))
     nf = max(1, int(n_frames))
-    m = np.zeros((nf, F2_MAX), MATCH_DTYPE)
-    cl = np.zeros((nf, F2_MAX), CLUSTER_DTYPE)
-    mem = np.zeros((nf, F2_MAX), np.int32)
+    rows = F2_LARGE_MAX if large else F2_MAX   # large: the large-frame kernel on every frame (the *_large hooks below)
+    m = np.zeros((nf, rows), MATCH_DTYPE)
+    cl = np.zeros((nf, rows), CLUSTER_DTYPE)
+    mem = np.zeros((nf, rows), np.int32)
     counts = np.zeros((nf, 4), np.uint32)
-    _lib.check(_lib.lib().lmx_debug_device_finalize_cluster(device, records.ctypes.data, len(records), int(n_frames), dists.ctypes.data, rects.ctypes.data,
-                                                            len(dists), C.byref(pp), m.ctypes.data, cl.ctypes.data, mem.ctypes.data, counts.ctypes.data))
+    hook = _lib.lib().lmx_debug_device_finalize_cluster_large if large else _lib.lib().lmx_debug_device_finalize_cluster
+    _lib.check(hook(device, records.ctypes.data, len(records), int(n_frames), dists.ctypes.data, rects.ctypes.data,
+                    len(dists), C.byref(pp), m.ctypes.data, cl.ctypes.data, mem.ctypes.data, counts.ctypes.data))
     out = []
     for f in range(n_frames):
         n_m, n_c, n_mem, status = (int(v) for v in counts[f])
@@ -1020,7 +1031,7 @@ def debug_device_finalize_cluster(records, n_frames, obj_origin_dists, rects, vo
 
 
 def debug_device_finalize_cluster_depth(records, n_frames, templates, depth_frames, obj_origin_dists, rects, vote_row_col_step, renderer_radius_min,
-                                        renderer_radius_step, cluster_size_thresh=2, class_index=-1, no_value=-np.inf, device=0, with_counts=False):
+                                        renderer_radius_step, cluster_size_thresh=2, class_index=-1, no_value=-np.inf, device=0, with_counts=False, large=False):
     """Test hook (lmx_debug_device_finalize_cluster_depth): debug_device_finalize_cluster for the kernels behind
     Detector.collect_clusters_depth; depth_frames (one per frame) become `templates`' uploaded scene.  -> list per frame of
     (matches, diffs, clusters, members, status)."""
@@ -1032,14 +1043,16 @@ def debug_device_finalize_cluster_depth(records, n_frames, templates, depth_fram
     if len(frames) != n_frames:
         raise ValueError("one depth frame per frame")
     nf = max(1, int(n_frames))
-    m = np.zeros((nf, F2_MAX), MATCH_DTYPE)
-    d = np.zeros((nf, F2_MAX), DEPTH_DIFF_DTYPE)
-    cl = np.zeros((nf, F2_MAX), CLUSTER_DTYPE)
-    mem = np.zeros((nf, F2_MAX), np.int32)
+    rows = F2_LARGE_MAX if large else F2_MAX   # large: the large-frame kernel on every frame (the *_large hooks below)
+    m = np.zeros((nf, rows), MATCH_DTYPE)
+    d = np.zeros((nf, rows), DEPTH_DIFF_DTYPE)
+    cl = np.zeros((nf, rows), CLUSTER_DTYPE)
+    mem = np.zeros((nf, rows), np.int32)
     counts = np.zeros((nf, 4), np.uint32)
-    _lib.check(_lib.lib().lmx_debug_device_finalize_cluster_depth(device, records.ctypes.data, len(records), int(n_frames), templates.h, imgs, int(class_index),
-                                                                  float(no_value), dists.ctypes.data, rects.ctypes.data, len(dists), C.byref(pp), m.ctypes.data,
-                                                                  d.ctypes.data, cl.ctypes.data, mem.ctypes.data, counts.ctypes.data))
+    hook = _lib.lib().lmx_debug_device_finalize_cluster_large_depth if large else _lib.lib().lmx_debug_device_finalize_cluster_depth
+    _lib.check(hook(device, records.ctypes.data, len(records), int(n_frames), templates.h, imgs, int(class_index),
+                    float(no_value), dists.ctypes.data, rects.ctypes.data, len(dists), C.byref(pp), m.ctypes.data,
+                    d.ctypes.data, cl.ctypes.data, mem.ctypes.data, counts.ctypes.data))
     out = []
     for f in range(n_frames):
         n_m, n_c, n_mem, status = (int(v) for v in counts[f])
@@ -1050,17 +1063,18 @@ def debug_device_finalize_cluster_depth(records, n_frames, templates, depth_fram
 
 
 def debug_device_finalize_cluster_classes(records, n_frames, classes, templates=None, class_base=None, depth_frames=None, normals=False, no_value=-np.inf,
-                                          device=0, with_counts=False):
+                                          device=0, with_counts=False, large=False):
     """Test hook (lmx_debug_device_finalize_cluster_classes): the kernels behind Detector.collect_clusters_classes on a caller's records;
     classes as cluster_matches_classes takes them.  -> list per frame of (matches, diffs, ndiffs, clusters, cluster_class, members, status);
     diffs / ndiffs are None without templates / normals.  No host completion."""
     records = np.ascontiguousarray(records, RAW_MATCH_DTYPE)
     arr, keep = _class_sidecars(classes)
     nf = max(1, int(n_frames))
-    m = np.zeros((nf, F2_MAX), MATCH_DTYPE)
-    cl = np.zeros((nf, F2_MAX), CLUSTER_DTYPE)
-    cc = np.zeros((nf, F2_MAX), np.int32)
-    mem = np.zeros((nf, F2_MAX), np.int32)
+    rows = F2_LARGE_MAX if large else F2_MAX   # large: the large-frame kernel on every frame (the *_large hooks below)
+    m = np.zeros((nf, rows), MATCH_DTYPE)
+    cl = np.zeros((nf, rows), CLUSTER_DTYPE)
+    cc = np.zeros((nf, rows), np.int32)
+    mem = np.zeros((nf, rows), np.int32)
     counts = np.zeros((nf, 4), np.uint32)
     d = nd = score = imgs = None
     if templates is not None:
@@ -1068,13 +1082,14 @@ def debug_device_finalize_cluster_classes(records, n_frames, classes, templates=
         frames, imgs = _depth_images(depth_frames)
         if len(frames) != n_frames or len(base) < 2:
             raise ValueError("one depth frame per frame, one class_base entry per class plus one")
-        d = np.zeros((nf, F2_MAX), DEPTH_DIFF_DTYPE)
-        nd = np.zeros((nf, F2_MAX), NORMAL_DIFF_DTYPE) if normals else None
+        d = np.zeros((nf, rows), DEPTH_DIFF_DTYPE)
+        nd = np.zeros((nf, rows), NORMAL_DIFF_DTYPE) if normals else None
         score = C.byref(_lib.ClassScore(templates.h, base.ctypes.data, len(base) - 1, int(bool(normals)), float(no_value)))
-    _lib.check(_lib.lib().lmx_debug_device_finalize_cluster_classes(device, records.ctypes.data, len(records), int(n_frames), arr, len(classes), score, imgs,
-                                                                    m.ctypes.data, d.ctypes.data if d is not None else None,
-                                                                    nd.ctypes.data if nd is not None else None, cl.ctypes.data, cc.ctypes.data,
-                                                                    mem.ctypes.data, counts.ctypes.data))
+    hook = _lib.lib().lmx_debug_device_finalize_cluster_large_classes if large else _lib.lib().lmx_debug_device_finalize_cluster_classes
+    _lib.check(hook(device, records.ctypes.data, len(records), int(n_frames), arr, len(classes), score, imgs,
+                    m.ctypes.data, d.ctypes.data if d is not None else None,
+                    nd.ctypes.data if nd is not None else None, cl.ctypes.data, cc.ctypes.data,
+                    mem.ctypes.data, counts.ctypes.data))
     del keep
     out = []
     for f in range(n_frames):
@@ -1084,6 +1099,23 @@ def debug_device_finalize_cluster_classes(records, n_frames, classes, templates=
         out.append((m[f, :n_m].copy(), d[f, :n_m].copy() if d is not None else None, nd[f, :n_m].copy() if nd is not None else None, cl[f, :n_c].copy(),
                     cc[f, :n_c].copy(), mem[f, :n_mem].copy(), status))
     return (out, counts) if with_counts else out
+
+
+def debug_device_finalize_cluster_large(*args, **kw):
+    """debug_device_finalize_cluster on the large-frame kernel (lmx_debug_device_finalize_cluster_large): every frame, whatever its size, in
+    rows of F2_LARGE_MAX; status 1 only beyond F2_LARGE_MAX records, status 2 also for a ring outside -2^17 .. 2^17 - 1."""
+    return debug_device_finalize_cluster(*args, large=True, **kw)
+
+
+def debug_device_finalize_cluster_large_depth(*args, **kw):
+    """debug_device_finalize_cluster_depth on the large-frame kernel (lmx_debug_device_finalize_cluster_large_depth)."""
+    return debug_device_finalize_cluster_depth(*args, large=True, **kw)
+
+
+def debug_device_finalize_cluster_large_classes(*args, **kw):
+    """debug_device_finalize_cluster_classes on the large-frame kernels (lmx_debug_device_finalize_cluster_large_classes); status 2 also for
+    a ring outside -2^13 .. 2^13 - 1."""
+    return debug_device_finalize_cluster_classes(*args, large=True, **kw)
 
 
 GATHER_HEADER_BYTES = 64

@@ -108,6 +108,7 @@ def main():
                 tc.append(t1 - t0)
                 tf.append(t2 - t1)
             st = det.stats()
+            cs = det.chain_stats()      # of the last fused call
             diff = 1e3 * (np.asarray(tc) - np.asarray(tf))
             iqr = 1e3 * (np.percentile(tc, 75) - np.percentile(tc, 25))
             part = 1e3 * np.median(np.asarray(parts), axis=0)
@@ -117,9 +118,12 @@ def main():
                       "                 of it, medians: enqueue + collect %.3f ms, DepthTemplates.diff %.3f ms, the per-frame cluster_matches_scored loop %.3f ms"
                       % (part[0], part[1], part[2]),
                       "    fused        %s" % spread(tf),
+                      "                 its frames by path: LDS kernel %d, large-frame kernel %d, host for the record count %d, host for side-car / range %d; "
+                      "largest frame beyond 2048 records: %d; large-path workspace %.1f MB"
+                      % (cs["frames_lds"], cs["frames_large"], cs["frames_host_records"], cs["frames_host_other"], cs["max_frame_records"], cs["large_workspace_bytes"] / 1e6),
                       "    composition - fused, pair by pair: median %.3f ms (quartiles %.3f .. %.3f); the composition's own interquartile range is %.3f ms"
                       % (np.median(diff), np.percentile(diff, 25), np.percentile(diff, 75), iqr)]
-            print("\n".join(lines[-5:]), flush=True)
+            print("\n".join(lines[-6:]), flush=True)
             det.close()
     t.close()
     text = "\n".join(lines) + "\n"
