@@ -245,6 +245,13 @@ static lmx_status ctx_create_impl(lmx_ctx* c) {
         const LevelGeom& g = c->kp.geom[l];
         if (md.type == LMX_MOD_COLOR_GRADIENT && l > 0 && (st = dev_alloc(c, &c->lane_bgr[lane][m][l], (size_t)F * g.W * g.H * c->color_ch, false)) != LMX_OK) return st;
         if ((st = dev_alloc(c, &fb.quant[l][m], (size_t)F * g.W * g.H, false)) != LMX_OK) return st;
+        // k_spread_linearize_t loads a banded level's label rows 16 bytes at a time: every row of every frame must start on a 16-byte
+        // boundary.  Wc % 16 == 0 gives W = T * Wc that width and the image is an allocation of its own; were either ever not so, the
+        // kernel would drop to its dword loop unseen, so the context does not come up.
+        if (g.ls_bands != 0 && (g.W % 16 != 0 || (reinterpret_cast<uintptr_t>(fb.quant[l][m]) & 15) != 0)) {
+          set_error("banded level %d: label image of width %d is not 16-byte aligned", l, g.W);
+          return LMX_ERR_SHAPE;
+        }
         // pads must read as zero: clear once, kernels only ever write the matrices.  Byte + nibble-packed response memories
         // exist for the coarsest level only; finer levels keep the linearised spread image
         if (l == c->L - 1) {

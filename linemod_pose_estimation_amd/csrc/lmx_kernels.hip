@@ -24,6 +24,7 @@
 // divide/sqrt (depth_lut_index_lean spells the same two expansions out without their out-of-range steps).
 
 #include <algorithm>
+#include <cassert>
 #include <type_traits>
 
 #include "lmx_internal.hpp"
@@ -614,6 +615,9 @@ struct RowCol {
 //   output stage as the generic kernel.
 //   lmn != null (coarsest level, Wc % 8 == 0): the eight response maps are written nibble-packed straight away (8 cells ->
 //   one dword per orientation); no byte-wide linear memories and no separate packing pass exist in that case.
+//   The load phase moves 16 bytes per item when W % 16 == 0 (always so on the banded path).  The same width in the banded output stage
+//   (16 cells per item, two 16-byte stores) took another 100 VALU instructions out of every wave and no time out of the kernel, and made
+//   the 1280 x 960 two-bank workload slower beside the other lanes' kernels: not kept (profiles/r12_spread_wide_ab.txt).
 template <int T>
 __device__ __forceinline__ void spread_linearize_t_body(const uint3 bid, const SpreadBatch& batch, const LevelGeom& g, int n_frames_x) {
   // bid.y = modality (all modalities of a level share one launch)
@@ -656,7 +660,35 @@ __device__ __forceinline__ void spread_linearize_t_body(const uint3 bid, const S
   if (ls == nullptr) {
     s_tab[tid] = c_resp_tab.v[tid];
   }
-  {
+  if ((W & 15) == 0 && (reinterpret_cast<uintptr_t>(quant) & 15) == 0) {
+    // Every image row starts on a 16-byte boundary (always so on the banded path: the context checks it where it allocates the images): one item is
+    // four dwords of a row, one global_load_dwordx4.  A thread issues the loads of two items before it writes the first to the LDS.
+    // Staged rows are Wd dwords: with ND == 4 (T = 8) they keep the 16-byte alignment and an item is one ds_write_b128; with ND == 3
+    // (T = 4, 5) they are only dword-aligned, the item is written as four dwords and the compiler pairs them into two ds_write2_b32.
+    const int W16 = W >> 4, n_items = RI * W16;
+    if (tid < RI * ND) s_src[(tid / ND) * Wd + W4 + tid % ND] = 0u;   // the dwords behind the image
+    RowCol rc(tid, W16);
+    for (int i = tid; i < n_items; i += 512) {
+      uint4 v[2];
+      int at[2];
+#pragma unroll
+      for (int u = 0; u < 2; ++u, rc.next()) {
+        at[u] = i + 256 * u < n_items ? rc.row * Wd + 4 * rc.col : -1;
+        v[u] = make_uint4(0u, 0u, 0u, 0u);
+        if (at[u] >= 0 && y0 + rc.row < H) v[u] = reinterpret_cast<const uint4*>(quant + (size_t)(y0 + rc.row) * W)[rc.col];
+      }
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        if (at[u] < 0) continue;
+        uint32_t* p = s_src + at[u];
+        if constexpr (ND % 4 == 0) {
+          *reinterpret_cast<uint4*>(p) = v[u];
+        } else {
+          p[0] = v[u].x; p[1] = v[u].y; p[2] = v[u].z; p[3] = v[u].w;
+        }
+      }
+    }
+  } else {
     RowCol rc(tid, Wd);
     for (int i = tid; i < RI * Wd; i += 256, rc.next()) {
       const int y = y0 + rc.row;
@@ -1953,6 +1985,10 @@ template <int T>
 static void launch_spread_linearize_t(hipStream_t s, const SpreadBatch& b, int n_mod, const LevelGeom& g, int n_frames) {
   constexpr int ND = (T + 2) / 4 + 2;
   const int Wd = g.W / 4 + ND;
+  // The load phase moves 16 bytes per item where W % 16 == 0 and the label image is 16-byte aligned (the kernel tests both and keeps
+  // the dword loop otherwise).  A banded level always qualifies by its width: Wc % 16 == 0, so W = T * Wc is a multiple of 16.
+  // Width and base address are checked once more, in every build, where the context allocates the label images (lmx_ctx.cpp).
+  assert(g.ls_bands == 0 || g.W % 16 == 0);
   size_t smem = 2048 + (size_t)(2 * T - 1 + T) * Wd * 4 + (size_t)T * g.W;
   if (n_frames >= 8)
     hipLaunchKernelGGL(k_spread_linearize_t<T>, dim3((unsigned)(g.Hc * 8 * ((n_frames + 7) / 8)), n_mod, 1), dim3(256), smem, s, b, g, n_frames);
