@@ -149,7 +149,9 @@ lmx_status lmx_bank_add_class(lmx_bank* bank, const char* class_id, int32_t n_py
  * (reference call sites src/renderer.cpp:308, src/renderer_only_image.cpp:266).  The per-pixel work (quantised orientations
  * with their magnitudes, quantised normals, the pyrDown chain) runs on the device with the same kernels match() uses; the
  * greedy scattered feature selection (extractTemplate / selectScatteredFeatures / cropTemplates) is sequential host code.
- * Sources as for match() (8UC3 / 16UC1 mm, any size: no T divisibility is needed to train); object_mask 8UC1 or NULL.
+ * Sources as for match() (8UC3 / 16UC1 mm, any size from 16x16 up, odd widths and heights included: no T divisibility is
+ * needed to train); object_mask 8UC1 or NULL.  Every modality's num_features must leave 1 .. 63 features at every pyramid level
+ * (it is halved per level): LMX_ERR_SHAPE otherwise, here and in lmx_bank_train_mesh.
  * *template_id is the new id within the class, or -1 when some level has fewer candidates than num_features (upstream
  * returns -1 and adds nothing); bounding_box = {x, y, w, h} of cropTemplates. */
 lmx_status lmx_bank_add_template(lmx_bank* bank, int32_t device, const lmx_image* sources, int32_t n_sources, const char* class_id,

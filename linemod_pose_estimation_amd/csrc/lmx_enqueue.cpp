@@ -73,7 +73,7 @@ static lmx_status issue_pre(lmx_ctx* c, int32_t n_frames, hipStream_t s) {
           // done by the level-0 kernel
         } else {
           ScopedKernel k(c, K_NN_DOWN);
-          launch_nn_down2(s, c->kp.fb.quant[l - 1][m], c->kp.fb.quant[l][m], g.H, g.W, n_frames);
+          launch_nn_down2(s, c->kp.fb.quant[l - 1][m], c->kp.fb.quant[l][m], c->kp.geom[l - 1].H, c->kp.geom[l - 1].W, g.H, g.W, n_frames);
         }
       }
     }

@@ -416,7 +416,7 @@ void launch_publish_blocks(hipStream_t s, void* dst, const void* src, int n_bloc
 constexpr int kPullMax = 16;
 struct PullSources { const void* src[kPullMax]; };   // passed by value: the source blocks of k_pull_blocks
 void launch_pull_blocks(hipStream_t s, void* dst, const PullSources& srcs, int n_blocks, size_t block_bytes, uint32_t max_records);
-void launch_nn_down2(hipStream_t s, const uint8_t* src, uint8_t* dst, int Hd, int Wd, int n_frames);
+void launch_nn_down2(hipStream_t s, const uint8_t* src /* Hs x Ws */, uint8_t* dst /* Hd x Wd = Hs / 2 x Ws / 2 */, int Hs, int Ws, int Hd, int Wd, int n_frames);
 void launch_apply_mask(hipStream_t s, uint8_t* quant, const uint8_t* mask0, int Hl, int Wl, int W0, int H0, int level, int n_frames);
 bool spread_writes_nibbles(const LevelGeom& g);
 int score_kernel_variant(const DeviceBankView& bank);

@@ -481,14 +481,16 @@ __global__ __launch_bounds__(256) void k_small_depth_color(SmallQuantArgs a) {
 }
 
 
-__global__ __launch_bounds__(256) void k_nn_down2(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int Hd, int Wd) {
+// dst (Hd x Wd, Hd = Hs / 2, Wd = Ws / 2) = every second pixel of every second row of src (Hs x Ws).  The source's own width and height give
+// its row and frame strides: an odd Ws or Hs leaves a last column or row that is never read.
+__global__ __launch_bounds__(256) void k_nn_down2(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int Hs, int Ws, int Hd, int Wd) {
   const int frame = blockIdx.z;
-  src += (size_t)frame * Hd * Wd * 4;
+  src += (size_t)frame * Hs * Ws;
   dst += (size_t)frame * Hd * Wd;
   const int x = blockIdx.x * 64 + (threadIdx.x & 63);
   const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (x >= Wd || y >= Hd) return;
-  dst[(size_t)y * Wd + x] = src[(size_t)(2 * y) * (Wd * 2) + 2 * x];
+  dst[(size_t)y * Wd + x] = src[(size_t)(2 * y) * Ws + 2 * x];
 }
 
 // =========================================================================================================
@@ -1976,9 +1978,10 @@ void launch_apply_mask(hipStream_t s, uint8_t* quant, const uint8_t* mask0, int 
   hipLaunchKernelGGL(k_apply_mask, dim3((unsigned)((Wl + 1023) / 1024), (unsigned)Hl, (unsigned)n_frames), dim3(256), 0, s, quant, mask0, Hl, Wl, W0, H0, level);
 }
 
-void launch_nn_down2(hipStream_t s, const uint8_t* src, uint8_t* dst, int Hd, int Wd, int n_frames) {
+void launch_nn_down2(hipStream_t s, const uint8_t* src, uint8_t* dst, int Hs, int Ws, int Hd, int Wd, int n_frames) {
+  if (Hd < 1 || Wd < 1 || 2 * Hd > Hs || 2 * Wd > Ws) return;   // the reads (2y, 2x), y < Hd, x < Wd, must lie inside the source
   dim3 grid((Wd + 63) / 64, (Hd + 3) / 4, n_frames);
-  hipLaunchKernelGGL(k_nn_down2, grid, dim3(256), 0, s, src, dst, Hd, Wd);
+  hipLaunchKernelGGL(k_nn_down2, grid, dim3(256), 0, s, src, dst, Hs, Ws, Hd, Wd);
 }
 
 template <int T>

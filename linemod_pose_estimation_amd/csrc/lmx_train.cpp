@@ -17,6 +17,7 @@
 
 #include "lmx_internal.hpp"
 #include "lmx_mesh_raster.hpp"
+#include "lmx_train_select.hpp"
 
 namespace lmx {
 namespace {
@@ -30,140 +31,12 @@ namespace {
     }                                                                                      \
   } while (0)
 
-struct Cand { int x, y, label; float score; };
-struct Feat { int x, y, label; };
+using namespace train_select;
 
-inline int label_of(uint8_t q) {  // upstream getLabel(): one-hot byte -> bin
-  for (int k = 0; k < 8; ++k)
-    if (q == (1u << k)) return k;
-  return -1;
-}
-
-// 3x3 minimum with BORDER_REPLICATE (cv::erode with the default 3x3 rectangle)
-std::vector<uint8_t> erode3(const std::vector<uint8_t>& m, int H, int W) {
-  std::vector<uint8_t> out((size_t)H * W);
-  for (int y = 0; y < H; ++y)
-    for (int x = 0; x < W; ++x) {
-      uint8_t v = 255;
-      for (int dy = -1; dy <= 1; ++dy) {
-        const int yy = std::min(std::max(y + dy, 0), H - 1);
-        for (int dx = -1; dx <= 1; ++dx) v = std::min(v, m[(size_t)yy * W + std::min(std::max(x + dx, 0), W - 1)]);
-      }
-      out[(size_t)y * W + x] = v;
-    }
-  return out;
-}
-
-// distanceTransform(src, dst, DIST_C, 3): chessboard distance to the nearest zero pixel (two-pass 8-neighbour chamfer with unit
-// weights, exact for that metric); a component without any zero pixel in the image keeps a huge value, like upstream's
-// initial distance.
-std::vector<float> dist_chessboard(const std::vector<uint8_t>& nz, int H, int W) {
-  const int INF = 1 << 28;
-  std::vector<int> d((size_t)H * W);
-  for (size_t i = 0; i < d.size(); ++i) d[i] = nz[i] ? INF : 0;
-  auto at = [&](int y, int x) -> int { return (y < 0 || y >= H || x < 0 || x >= W) ? INF : d[(size_t)y * W + x]; };
-  for (int y = 0; y < H; ++y)
-    for (int x = 0; x < W; ++x) {
-      int v = d[(size_t)y * W + x];
-      v = std::min(v, std::min(std::min(at(y - 1, x - 1), at(y - 1, x)), std::min(at(y - 1, x + 1), at(y, x - 1))) + 1);
-      d[(size_t)y * W + x] = v;
-    }
-  for (int y = H - 1; y >= 0; --y)
-    for (int x = W - 1; x >= 0; --x) {
-      int v = d[(size_t)y * W + x];
-      v = std::min(v, std::min(std::min(at(y + 1, x + 1), at(y + 1, x)), std::min(at(y + 1, x - 1), at(y, x + 1))) + 1);
-      d[(size_t)y * W + x] = v;
-    }
-  std::vector<float> out(d.size());
-  for (size_t i = 0; i < d.size(); ++i) out[i] = (float)d[i];
-  return out;
-}
-
-// QuantizedPyramid::selectScatteredFeatures
-void select_scattered(const std::vector<Cand>& cands, std::vector<Feat>& feats, size_t num_features, float distance) {
-  feats.clear();
-  float distance_sq = distance * distance;
-  int i = 0;
-  while (feats.size() < num_features) {
-    const Cand& c = cands[i];
-    bool keep = true;
-    for (size_t j = 0; j < feats.size() && keep; ++j) {
-      const int dx = c.x - feats[j].x, dy = c.y - feats[j].y;
-      keep = (float)(dx * dx + dy * dy) >= distance_sq;
-    }
-    if (keep) feats.push_back(Feat{c.x, c.y, c.label});
-    if (++i == (int)cands.size()) {
-      i = 0;
-      distance -= 1.0f;
-      distance_sq = distance * distance;
-    }
-  }
-}
-
-bool by_score_desc(const Cand& a, const Cand& b) { return a.score > b.score; }  // Candidate::operator<
-
-// ColorGradientPyramid::extractTemplate
-bool extract_color(const std::vector<uint8_t>& angle, const std::vector<float>& mag, const std::vector<uint8_t>& mask, int H, int W,
-                   size_t num_features, float strong_threshold, std::vector<Feat>& out) {
-  std::vector<uint8_t> local;
-  const bool no_mask = mask.empty();
-  if (!no_mask) {
-    std::vector<uint8_t> er = erode3(mask, H, W);
-    local.resize(mask.size());
-    for (size_t i = 0; i < mask.size(); ++i) local[i] = (uint8_t)(mask[i] > er[i] ? mask[i] - er[i] : 0);  // subtract saturates
-  }
-  const float threshold_sq = strong_threshold * strong_threshold;
-  std::vector<Cand> cands;
-  for (int r = 0; r < H; ++r)
-    for (int c = 0; c < W; ++c) {
-      const size_t i = (size_t)r * W + c;
-      if (!no_mask && !local[i]) continue;
-      const uint8_t q = angle[i];
-      if (q > 0 && mag[i] > threshold_sq) cands.push_back(Cand{c, r, label_of(q), mag[i]});
-    }
-  if (cands.size() < num_features) return false;
-  std::stable_sort(cands.begin(), cands.end(), by_score_desc);
-  const float distance = static_cast<float>(cands.size() / num_features + 1);
-  select_scattered(cands, out, num_features, distance);
-  return true;
-}
-
-// DepthNormalPyramid::extractTemplate
-bool extract_depth(const std::vector<uint8_t>& normal, const std::vector<uint8_t>& mask, int H, int W, size_t num_features,
-                   int extract_threshold, std::vector<Feat>& out) {
-  std::vector<uint8_t> local;
-  const bool no_mask = mask.empty();
-  if (!no_mask) local = erode3(erode3(mask, H, W), H, W);  // erode(..., iterations = 2, BORDER_REPLICATE)
-  std::vector<float> dist[8];
-  std::vector<uint8_t> temp((size_t)H * W);
-  for (int k = 0; k < 8; ++k) {
-    for (size_t i = 0; i < temp.size(); ++i) temp[i] = (uint8_t)(((no_mask || local[i]) ? (1u << k) : 0u) & normal[i]);
-    dist[k] = dist_chessboard(temp, H, W);
-  }
-  int label_counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  std::vector<Cand> cands;
-  for (int r = 0; r < H; ++r)
-    for (int c = 0; c < W; ++c) {
-      const size_t i = (size_t)r * W + c;
-      if (!no_mask && !local[i]) continue;
-      const uint8_t q = normal[i];
-      if (q == 0 || q == 255) continue;
-      const int label = label_of(q);
-      if (label < 0) continue;
-      const float score = dist[label][i];
-      if (score >= (float)extract_threshold) {
-        cands.push_back(Cand{c, r, label, score});
-        ++label_counts[label];
-      }
-    }
-  if (cands.size() < num_features) return false;
-  for (Cand& c : cands) c.score /= (float)label_counts[c.label];
-  std::stable_sort(cands.begin(), cands.end(), by_score_desc);
-  size_t area = normal.size();
-  if (!no_mask) { area = 0; for (uint8_t v : local) area += v != 0; }
-  const float distance = sqrtf((float)area) / sqrtf((float)num_features) + 1.5f;
-  select_scattered(cands, out, num_features, distance);
-  return true;
+std::vector<Modality> select_modalities(const lmx_bank* bank) {
+  std::vector<Modality> mods;
+  for (const lmx_modality_desc& md : bank->mods) mods.push_back(Modality{md.type == LMX_MOD_COLOR_GRADIENT, md.num_features, md.strong_threshold, md.extract_threshold});
+  return mods;
 }
 
 }  // namespace
@@ -174,6 +47,8 @@ lmx_status train_add_template(lmx_bank* bank, int device, const lmx_image* sourc
   if (n_sources != M) { set_error("sources.size()=%d != modalities.size()=%d", n_sources, M); return LMX_ERR_SHAPE; }
   const int H0 = sources[0].rows, W0 = sources[0].cols;
   if (H0 < 16 || W0 < 16) { set_error("source image too small"); return LMX_ERR_SHAPE; }
+  const std::vector<Modality> sel_mods = select_modalities(bank);
+  { std::string why; if (!check_num_features(sel_mods, L, &why)) { set_error("lmx_bank_add_template: %s", why.c_str()); return LMX_ERR_SHAPE; } }
   // ColorGradient sources are 8UC3, or 8UC1 (a gray image: the one-plane quantiser, whose templates equal those of the image copied into
   // B, G and R)
   for (int m = 0; m < M; ++m) {
@@ -230,6 +105,7 @@ lmx_status train_add_template(lmx_bank* bank, int device, const lmx_image* sourc
       uint8_t* d_cur_src = (uint8_t*)d_src;
       int h = H0, w = W0;
       for (int l = 0; l < L; ++l) {
+        const int prev_h = h, prev_w = w;
         if (l > 0) { h /= 2; w /= 2; }
         if (h < 1 || w < 1) { set_error("image too small for %d pyramid levels", L); return LMX_ERR_SHAPE; }
         uint8_t* d_q = (uint8_t*)dmalloc((size_t)h * w);
@@ -253,7 +129,7 @@ lmx_status train_add_template(lmx_bank* bank, int device, const lmx_image* sourc
             TR_HIP(hipMemcpy(d_bins, bins.data(), bins.size(), hipMemcpyHostToDevice));
             launch_depth_quantize(nullptr, (const uint16_t*)d_src, d_q, nullptr, h, w, 1, md.distance_threshold, md.difference_threshold, d_bins);
           }
-          else launch_nn_down2(nullptr, d_prev_q, d_q, h, w, 1);
+          else launch_nn_down2(nullptr, d_prev_q, d_q, prev_h, prev_w, h, w, 1);
           TR_HIP(hipDeviceSynchronize());
         }
         TR_HIP(hipMemcpy(labels[m][l].data(), d_q, (size_t)h * w, hipMemcpyDeviceToHost));
@@ -266,92 +142,32 @@ lmx_status train_add_template(lmx_bank* bank, int device, const lmx_image* sourc
   cleanup();
   if (st != LMX_OK) return st;
 
-  // ---- host: extractTemplate per (level, modality), cropTemplates ------------------------------------------------------------
-  // With an object mask (what the reference's trainers pass: the rendered silhouette) everything extractTemplate looks at lies inside
-  // the mask's bounding box: candidates exist only where the eroded mask is set, and the erosions and the chessboard distance
-  // transforms at those pixels depend only on pixels within 2 of the box (outside the mask every intermediate image is zero).  The
-  // stages therefore run on the box grown by 2 pixels (clamped to the image, where BORDER_REPLICATE keeps its meaning) instead of the
-  // whole frame -- the same values, the same candidate order (raster order is preserved), 10-20x fewer pixels for a rendered object:
-  // eight full-frame distance transforms were most of the 16 ms a 640x480 RGB-D view took (round 3).
-  std::vector<std::vector<Feat>> tp((size_t)L * M);
+  // ---- host: extractTemplate per (level, modality) on each level's window, cropTemplates (lmx_train_select.hpp) -----------------------
   *template_id = -1;
-  struct Win { int x0, y0, w, h; };
-  std::vector<Win> wins(L);
+  std::vector<LevelArrays> levels(L);
   for (int l = 0, h = H0, w = W0; l < L; ++l) {
     if (l > 0) { h /= 2; w /= 2; }
-    Win win{0, 0, w, h};
-    if (!masks[l].empty()) {
-      int bx0 = w, by0 = h, bx1 = -1, by1 = -1;
-      for (int y = 0; y < h; ++y)
-        for (int x = 0; x < w; ++x)
-          if (masks[l][(size_t)y * w + x]) { bx0 = std::min(bx0, x); bx1 = std::max(bx1, x); by0 = std::min(by0, y); by1 = std::max(by1, y); }
-      if (bx1 >= 0) {
-        win.x0 = std::max(0, bx0 - 2); win.y0 = std::max(0, by0 - 2);
-        win.w = std::min(w, bx1 + 3) - win.x0; win.h = std::min(h, by1 + 3) - win.y0;
-      } else {
-        win = Win{0, 0, std::min(w, 4), std::min(h, 4)};   // an all-zero mask: no candidates anywhere, any window shows that
-      }
-    }
-    wins[l] = win;
-  }
-  auto crop_u8 = [](const std::vector<uint8_t>& v, int w, const Win& win) {
-    std::vector<uint8_t> out((size_t)win.w * win.h);
-    for (int y = 0; y < win.h; ++y) std::memcpy(&out[(size_t)y * win.w], &v[(size_t)(win.y0 + y) * w + win.x0], (size_t)win.w);
-    return out;
-  };
-  for (int m = 0; m < M; ++m) {
-    const lmx_modality_desc& md = bank->mods[m];
-    size_t num_features = (size_t)md.num_features;
-    int extract_threshold = md.extract_threshold;
-    int h = H0, w = W0;
-    for (int l = 0; l < L; ++l) {
-      if (l > 0) { h /= 2; w /= 2; num_features /= 2; extract_threshold /= 2; }
-      if (num_features > 63) { set_error("num_features %zu > 63", num_features); return LMX_ERR_SHAPE; }
-      const Win& win = wins[l];
-      const bool whole = win.w == w && win.h == h;
-      std::vector<Feat>& out = tp[(size_t)l * M + m];
-      bool ok;
-      if (whole) {
-        if (md.type == LMX_MOD_COLOR_GRADIENT) ok = extract_color(labels[m][l], mags[m][l], masks[l], h, w, num_features, md.strong_threshold, out);
-        else ok = extract_depth(labels[m][l], masks[l], h, w, num_features, extract_threshold, out);
-      } else {
-        const std::vector<uint8_t> lab = crop_u8(labels[m][l], w, win), msk = crop_u8(masks[l], w, win);
-        if (md.type == LMX_MOD_COLOR_GRADIENT) {
-          std::vector<float> mg((size_t)win.w * win.h);
-          for (int y = 0; y < win.h; ++y) std::memcpy(&mg[(size_t)y * win.w], &mags[m][l][(size_t)(win.y0 + y) * w + win.x0], (size_t)win.w * sizeof(float));
-          ok = extract_color(lab, mg, msk, win.h, win.w, num_features, md.strong_threshold, out);
-        } else {
-          ok = extract_depth(lab, msk, win.h, win.w, num_features, extract_threshold, out);
-        }
-        for (Feat& f : out) { f.x += win.x0; f.y += win.y0; }
-      }
-      if (!ok) return LMX_OK;  // upstream: addTemplate returns -1, nothing is added
+    LevelArrays& lv = levels[l];
+    lv.w = w; lv.h = h;
+    lv.mask = masks[l].empty() ? nullptr : masks[l].data();
+    for (int m = 0; m < M; ++m) {
+      lv.label.push_back(labels[m][l].data());
+      lv.mag.push_back(mags[m][l].empty() ? nullptr : mags[m][l].data());
     }
   }
-  int min_x = INT32_MAX, min_y = INT32_MAX, max_x = INT32_MIN, max_y = INT32_MIN;
-  for (int k = 0; k < L * M; ++k) {
-    const int level = k / M;
-    for (const Feat& f : tp[k]) {
-      const int x = f.x << level, y = f.y << level;
-      min_x = std::min(min_x, x); min_y = std::min(min_y, y); max_x = std::max(max_x, x); max_y = std::max(max_y, y);
-    }
-  }
-  if (min_x % 2 == 1) --min_x;
-  if (min_y % 2 == 1) --min_y;
-  std::vector<int32_t> templates, features;
-  int32_t fb = 0;
-  for (int k = 0; k < L * M; ++k) {
-    const int level = k / M;
-    const int ox = min_x >> level, oy = min_y >> level;
-    templates.insert(templates.end(), {(max_x - min_x) >> level, (max_y - min_y) >> level, level, fb, (int32_t)tp[k].size()});
-    for (const Feat& f : tp[k]) features.insert(features.end(), {f.x - ox, f.y - oy, f.label});
-    fb += (int32_t)tp[k].size();
-  }
+  Pyramid pyr;
+  std::string why;
+  const Status sel = select_pyramid(levels, sel_mods, &pyr, &why);
+  if (sel == BAD_ARGUMENT) { set_error("lmx_bank_add_template: %s", why.c_str()); return LMX_ERR_SHAPE; }
+  if (sel == REJECTED) return LMX_OK;  // upstream: addTemplate returns -1, nothing is added
+  const std::vector<int32_t>& templates = pyr.templates;
+  const std::vector<int32_t>& features = pyr.features;
+  const int32_t fb = (int32_t)(features.size() / 3);
   const int32_t existing = lmx_bank_num_templates(bank, class_id);
   st = lmx_bank_add_class(bank, class_id, 1, templates.data(), features.data(), fb);
   if (st != LMX_OK) return st;
   *template_id = existing;
-  if (bounding_box) { bounding_box[0] = min_x; bounding_box[1] = min_y; bounding_box[2] = max_x - min_x; bounding_box[3] = max_y - min_y; }
+  if (bounding_box) std::memcpy(bounding_box, pyr.bounding_box, sizeof(pyr.bounding_box));
   return LMX_OK;
 }
 
@@ -361,7 +177,7 @@ lmx_status train_add_template(lmx_bank* bank, int device, const lmx_image* sourc
 // per pass: k_mesh_* render gray / depth / mask into device memory, the quantisers run with n_frames = B (the gray render through the
 // one-plane colour quantiser), k_mesh_pack writes each view's windows (silhouette box grown by 2, per level: the same window
 // train_add_template derives on the host) of magnitudes, labels and mask into a pinned host buffer.  One stream, one synchronisation per
-// batch; the host half (extract_color / extract_depth / select_scattered / crop: the functions above, unchanged) runs on a few threads,
+// batch; the host half (select_pyramid of lmx_train_select.hpp) runs on a few threads,
 // one view each, while the device works on the next batch.  Templates are appended to the bank in view order when every batch is done.
 namespace {
 
@@ -380,62 +196,28 @@ void select_view(const lmx_bank* bank, const uint8_t* slot, const int32_t* state
   const int L = (int)bank->T.size(), M = (int)bank->mods.size();
   int n_cg = 0;
   for (int m = 0; m < M; ++m) n_cg += bank->mods[m].type == LMX_MOD_COLOR_GRADIENT;
-  struct Win { int x0, y0, w, h; size_t off; };
-  std::vector<Win> wins(L);
+  std::vector<LevelArrays> levels(L);
   size_t off = 0;
   for (int l = 0; l < L; ++l) {
-    Win& w = wins[l];
-    mesh_window(state + MS_LEVEL + 4 * l, W0 >> l, H0 >> l, &w.x0, &w.y0, &w.w, &w.h);
-    w.off = off;
-    off += mesh_pack_level_bytes(w.w, w.h, M, n_cg);
-  }
-  std::vector<std::vector<Feat>> tp((size_t)L * M);
-  for (int m = 0, cg_index = 0; m < M; ++m) {
-    const lmx_modality_desc& md = bank->mods[m];
-    const bool cg = md.type == LMX_MOD_COLOR_GRADIENT;
-    size_t num_features = (size_t)md.num_features;
-    int extract_threshold = md.extract_threshold;
-    for (int l = 0; l < L; ++l) {
-      if (l > 0) { num_features /= 2; extract_threshold /= 2; }
-      if (num_features > 63) { out.status = LMX_ERR_SHAPE; out.error = "num_features " + std::to_string(num_features) + " > 63"; return; }
-      const Win& w = wins[l];
-      const size_t n = (size_t)w.w * w.h;
-      const uint8_t* base = slot + w.off;
-      const uint8_t* labp = base + n * 4 * n_cg + n * m;
-      const uint8_t* mskp = base + n * 4 * n_cg + n * M;
-      const std::vector<uint8_t> lab(labp, labp + n), msk(mskp, mskp + n);
-      std::vector<Feat>& f = tp[(size_t)l * M + m];
-      bool ok;
-      if (cg) {
-        const float* mgp = reinterpret_cast<const float*>(base + n * 4 * cg_index);
-        const std::vector<float> mg(mgp, mgp + n);
-        ok = extract_color(lab, mg, msk, w.h, w.w, num_features, md.strong_threshold, f);
-      } else {
-        ok = extract_depth(lab, msk, w.h, w.w, num_features, extract_threshold, f);
-      }
-      for (Feat& ft : f) { ft.x += w.x0; ft.y += w.y0; }
-      if (!ok) return;   // upstream: addTemplate returns -1, nothing is added
+    LevelArrays& lv = levels[l];
+    mesh_window(state + MS_LEVEL + 4 * l, W0 >> l, H0 >> l, &lv.x0, &lv.y0, &lv.w, &lv.h);
+    const size_t n = (size_t)lv.w * lv.h;
+    const uint8_t* base = slot + off;
+    for (int m = 0, cg_index = 0; m < M; ++m) {
+      const bool cg = bank->mods[m].type == LMX_MOD_COLOR_GRADIENT;
+      lv.label.push_back(base + n * 4 * n_cg + n * m);
+      lv.mag.push_back(cg ? reinterpret_cast<const float*>(base + n * 4 * cg_index) : nullptr);
+      cg_index += cg;
     }
-    cg_index += cg;
+    lv.mask = base + n * 4 * n_cg + n * M;
+    off += mesh_pack_level_bytes(lv.w, lv.h, M, n_cg);
   }
-  int min_x = INT32_MAX, min_y = INT32_MAX, max_x = INT32_MIN, max_y = INT32_MIN;
-  for (int k = 0; k < L * M; ++k) {
-    const int level = k / M;
-    for (const Feat& f : tp[k]) {
-      const int x = f.x << level, y = f.y << level;
-      min_x = std::min(min_x, x); min_y = std::min(min_y, y); max_x = std::max(max_x, x); max_y = std::max(max_y, y);
-    }
-  }
-  if (min_x % 2 == 1) --min_x;
-  if (min_y % 2 == 1) --min_y;
-  int32_t fb = 0;
-  for (int k = 0; k < L * M; ++k) {
-    const int level = k / M;
-    const int ox = min_x >> level, oy = min_y >> level;
-    out.templates.insert(out.templates.end(), {(max_x - min_x) >> level, (max_y - min_y) >> level, level, fb, (int32_t)tp[k].size()});
-    for (const Feat& f : tp[k]) out.features.insert(out.features.end(), {f.x - ox, f.y - oy, f.label});
-    fb += (int32_t)tp[k].size();
-  }
+  Pyramid pyr;
+  const Status sel = select_pyramid(levels, select_modalities(bank), &pyr, &out.error);
+  if (sel == BAD_ARGUMENT) { out.status = LMX_ERR_SHAPE; return; }
+  if (sel == REJECTED) return;   // upstream: addTemplate returns -1, nothing is added
+  out.templates.swap(pyr.templates);
+  out.features.swap(pyr.features);
   out.accepted = true;
 }
 
@@ -459,6 +241,7 @@ lmx_status train_mesh(lmx_bank* bank, int device, const double* triangles, int n
   if (H0 < 16 || W0 < 16) { set_error("source image too small"); return LMX_ERR_SHAPE; }
   if (L < 1 || L > kMaxLevels || M < 1 || M > kMaxModalities) { set_error("lmx_bank_train_mesh: %d pyramid levels x %d modalities are not supported", L, M); return LMX_ERR_SHAPE; }
   if ((H0 >> (L - 1)) < 1 || (W0 >> (L - 1)) < 1) { set_error("image too small for %d pyramid levels", L); return LMX_ERR_SHAPE; }
+  { std::string why; if (!check_num_features(select_modalities(bank), L, &why)) { set_error("lmx_bank_train_mesh: %s", why.c_str()); return LMX_ERR_SHAPE; } }
   int n_cg = 0;
   bool any_dn = false;
   for (int m = 0; m < M; ++m) {

@@ -1382,6 +1382,78 @@ int lmo_detector_get_template(void* h, const char* class_id, int template_id, in
   for (size_t i = 0; i < t.features.size(); ++i) { feats[3 * i] = t.features[i].x; feats[3 * i + 1] = t.features[i].y; feats[3 * i + 2] = t.features[i].label; }
   return (int)t.features.size();
 }
+
+// The two extractTemplate's on given arrays, the whole frame as upstream runs them (tests/test_train_select_host.py: the reference of the
+// product's host half, csrc/lmx_train_select.hpp).  Labels must be 0, a one-hot byte or (normals) 255: getLabel indexes out of range on
+// anything else, like upstream's CV_Error.  mask may be null.  Returns the feature count (== num_features), or -1 when the level is rejected.
+static int features_out(const Template& t, int32_t* feats) {
+  for (size_t i = 0; i < t.features.size(); ++i) { feats[3 * i] = t.features[i].x; feats[3 * i + 1] = t.features[i].y; feats[3 * i + 2] = t.features[i].label; }
+  return (int)t.features.size();
+}
+int lmo_extract_color(const unsigned char* angle, const float* magnitude, const unsigned char* mask, int rows, int cols, int num_features,
+                      float strong_threshold, int32_t* feats /* [num_features][3] */) {
+  ColorGradientPyramid qp;
+  const size_t n = (size_t)rows * cols;
+  qp.rows = rows; qp.cols = cols; qp.pyramid_level = 0; qp.weak_threshold = 0.0f; qp.num_features = (size_t)num_features; qp.strong_threshold = strong_threshold;
+  qp.angle.assign(angle, angle + n); qp.magnitude.assign(magnitude, magnitude + n);
+  if (mask) qp.mask.assign(mask, mask + n);
+  Template t;
+  if (!qp.extractTemplate(t)) return -1;
+  return features_out(t, feats);
+}
+int lmo_extract_depth(const unsigned char* normal, const unsigned char* mask, int rows, int cols, int num_features, int extract_threshold,
+                      int32_t* feats /* [num_features][3] */) {
+  DepthNormalPyramid qp;
+  const size_t n = (size_t)rows * cols;
+  qp.rows = rows; qp.cols = cols; qp.pyramid_level = 0; qp.num_features = (size_t)num_features; qp.extract_threshold = extract_threshold;
+  qp.normal.assign(normal, normal + n);
+  if (mask) qp.mask.assign(mask, mask + n);
+  Template t;
+  if (!qp.extractTemplate(t)) return -1;
+  return features_out(t, feats);
+}
+
+// Detector::addTemplate after the per-pixel stages: extractTemplate per (modality, level) on the given level arrays (label[l * M + m],
+// magnitude[l * M + m] or null, mask[l] or null; rows[l] x cols[l]), num_features and extract_threshold halved per level as pyrDown does,
+// then cropTemplates.  Returns 1 and fills templates [L*M][5] {width, height, level, feat_begin, feat_count}, features [n][3] and bb, or 0
+// when some level is rejected.
+int lmo_extract_pyramid(int n_levels, int n_mod, const int* is_color, const int* rows, const int* cols, const void* const* label, const void* const* magnitude,
+                        const void* const* mask, const int* num_features, const float* strong_threshold, const int* extract_threshold, int32_t* templates,
+                        int32_t* features, int* bb) {
+  TemplatePyramid tp((size_t)n_mod * n_levels);
+  for (int i = 0; i < n_mod; ++i) {
+    size_t nf = (size_t)num_features[i];
+    int et = extract_threshold[i];
+    for (int l = 0; l < n_levels; ++l) {
+      if (l > 0) { nf /= 2; et /= 2; }
+      const size_t n = (size_t)rows[l] * cols[l];
+      const uchar* lab = (const uchar*)label[l * n_mod + i];
+      const uchar* msk = (const uchar*)mask[l];
+      if (is_color[i]) {
+        ColorGradientPyramid qp;
+        qp.rows = rows[l]; qp.cols = cols[l]; qp.pyramid_level = l; qp.weak_threshold = 0.0f; qp.num_features = nf; qp.strong_threshold = strong_threshold[i];
+        const float* mg = (const float*)magnitude[l * n_mod + i];
+        qp.angle.assign(lab, lab + n); qp.magnitude.assign(mg, mg + n);
+        if (msk) qp.mask.assign(msk, msk + n);
+        if (!qp.extractTemplate(tp[l * n_mod + i])) return 0;
+      } else {
+        DepthNormalPyramid qp;
+        qp.rows = rows[l]; qp.cols = cols[l]; qp.pyramid_level = l; qp.num_features = nf; qp.extract_threshold = et;
+        qp.normal.assign(lab, lab + n);
+        if (msk) qp.mask.assign(msk, msk + n);
+        if (!qp.extractTemplate(tp[l * n_mod + i])) return 0;
+      }
+    }
+  }
+  cropTemplates(tp, bb);
+  int32_t fb = 0;
+  for (size_t k = 0; k < tp.size(); ++k) {
+    const int32_t row[5] = {tp[k].width, tp[k].height, tp[k].pyramid_level, fb, (int32_t)tp[k].features.size()};
+    std::memcpy(templates + 5 * k, row, sizeof(row));
+    fb += features_out(tp[k], features + 3 * (size_t)fb);
+  }
+  return 1;
+}
 }  // extern "C"
 
 // libstdc++'s std::sort itself, on (similarity, template_id) records with Match::operator< and on scores with the reference's

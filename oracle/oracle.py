@@ -243,6 +243,84 @@ def similarity_local(lm, size_wh, T, feats, center_xy):
     return out
 
 
+# ---- trainer: extractTemplate / cropTemplates on given arrays ---------------------------------------
+def _u8_or_none(a, shape):
+    if a is None:
+        return None
+    a = np.ascontiguousarray(a, np.uint8)
+    assert a.shape == shape
+    return a
+
+
+def extract_color(angle, magnitude, mask, num_features, strong_threshold=55.0):
+    """ColorGradientPyramid::extractTemplate on the whole frame -> features int32 [num_features, 3] in selection order, or None (rejected).
+    angle: one-hot bytes or 0; magnitude: float32 squared magnitudes; mask: uint8 or None."""
+    angle = np.ascontiguousarray(angle, np.uint8)
+    magnitude = np.ascontiguousarray(magnitude, np.float32)
+    mask = _u8_or_none(mask, angle.shape)
+    assert magnitude.shape == angle.shape and num_features >= 1
+    feats = np.zeros((num_features, 3), np.int32)
+    L = lib()
+    L.lmo_extract_color.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p]
+    n = L.lmo_extract_color(_p(angle), _p(magnitude), None if mask is None else _p(mask), angle.shape[0], angle.shape[1], int(num_features),
+                            C.c_float(strong_threshold), _p(feats))
+    return None if n < 0 else feats[:n]
+
+
+def extract_depth(normal, mask, num_features, extract_threshold=2):
+    """DepthNormalPyramid::extractTemplate on the whole frame -> features or None.  normal: one-hot bytes, 0 or 255."""
+    normal = np.ascontiguousarray(normal, np.uint8)
+    mask = _u8_or_none(mask, normal.shape)
+    assert num_features >= 1
+    feats = np.zeros((num_features, 3), np.int32)
+    L = lib()
+    L.lmo_extract_depth.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    n = L.lmo_extract_depth(_p(normal), None if mask is None else _p(mask), normal.shape[0], normal.shape[1], int(num_features), int(extract_threshold), _p(feats))
+    return None if n < 0 else feats[:n]
+
+
+def extract_pyramid(modalities, labels, magnitudes, masks):
+    """Detector::addTemplate after the per-pixel stages.  modalities: list of dicts (type, num_features, strong_threshold / extract_threshold);
+    labels[l][m], magnitudes[l][m] (None for DepthNormal), masks[l] (or masks = None).
+    -> None (rejected) or (templates int32 [L*M, 5], features int32 [n, 3], bounding box (x, y, w, h))."""
+    n_levels, n_mod = len(labels), len(modalities)
+    keep, lab_p, mag_p, mask_p = [], [], [], []
+    rows = np.asarray([np.shape(labels[l][0])[0] for l in range(n_levels)], np.int32)
+    cols = np.asarray([np.shape(labels[l][0])[1] for l in range(n_levels)], np.int32)
+    for l in range(n_levels):
+        shape = (int(rows[l]), int(cols[l]))
+        for m in range(n_mod):
+            a = _u8_or_none(labels[l][m], shape)
+            keep.append(a)
+            lab_p.append(a.ctypes.data)
+            if modalities[m]["type"] == "ColorGradient":
+                g = np.ascontiguousarray(magnitudes[l][m], np.float32)
+                assert g.shape == shape
+                keep.append(g)
+                mag_p.append(g.ctypes.data)
+            else:
+                mag_p.append(None)
+        k = None if masks is None else _u8_or_none(masks[l], shape)
+        keep.append(k)
+        mask_p.append(None if k is None else k.ctypes.data)
+    per = n_levels * n_mod
+    is_color = np.asarray([m["type"] == "ColorGradient" for m in modalities], np.int32)
+    nf = np.asarray([m.get("num_features", 63) for m in modalities], np.int32)
+    strong = np.asarray([m.get("strong_threshold", 55.0) for m in modalities], np.float32)
+    et = np.asarray([m.get("extract_threshold", 2) for m in modalities], np.int32)
+    assert all(int(v) >> l >= 1 for v in nf for l in range(n_levels)), "a level with 0 features divides by zero upstream"
+    templates = np.zeros((per, 5), np.int32)
+    features = np.zeros((int(nf.sum()) * n_levels, 3), np.int32)
+    bb = np.zeros(4, np.int32)
+    L = lib()
+    L.lmo_extract_pyramid.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 12
+    ok = L.lmo_extract_pyramid(n_levels, n_mod, _p(is_color), _p(rows), _p(cols), (C.c_void_p * per)(*lab_p), (C.c_void_p * per)(*mag_p),
+                               (C.c_void_p * n_levels)(*mask_p), _p(nf), _p(strong), _p(et), _p(templates), _p(features), _p(bb))
+    if not ok:
+        return None
+    return templates, features[:int(templates[:, 4].sum())].copy(), tuple(int(v) for v in bb)
+
+
 # ---- detector ---------------------------------------------------------------------------------------
 def _modality_desc(modalities):
     rows = []

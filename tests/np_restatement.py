@@ -597,3 +597,85 @@ def coarse_group_plan(nibble, valid):
         group_class[rows[sel], n[sel]] = k; group_real[rows[sel], n[sel]] = left[sel, k]
         n += sel
     return n_fast, group_class, group_real, n
+
+
+# ---- A.11: the trainer's extractTemplate, brute force ------------------------------------------------------------------
+TRAIN_NO_ZERO = float(1 << 28)   # the distance where an image has no zero pixel at all (upstream: the transform's initial value)
+
+
+def erode3(mask):
+    """cv::erode, 3x3 rectangle, BORDER_REPLICATE: the minimum over the nine shifted copies of the edge-padded image."""
+    p = np.pad(np.asarray(mask, np.uint8), 1, mode="edge")
+    H, W = mask.shape
+    return np.min([p[dy:dy + H, dx:dx + W] for dy in range(3) for dx in range(3)], axis=0)
+
+
+def chessboard_distance(img):
+    """distanceTransform(DIST_C): per pixel the minimum of max(|dx|, |dy|) over ALL zero pixels of img, no propagation."""
+    H, W = img.shape
+    zy, zx = np.nonzero(img == 0)
+    if len(zy) == 0:
+        return np.full((H, W), TRAIN_NO_ZERO, F32)
+    y, x = np.mgrid[0:H, 0:W]
+    d = np.maximum(np.abs(y[:, :, None] - zy[None, None, :]), np.abs(x[:, :, None] - zx[None, None, :])).min(axis=2)
+    return d.astype(F32)
+
+
+def select_scattered(xs, ys, labels, num_features, distance):
+    """selectScatteredFeatures: candidates in ranked order; a candidate is kept when it is at least `distance` (float32) away from every kept
+    one; at the end of the list the distance drops by one and the walk restarts -> int32 [num_features, 3]."""
+    kept = []
+    distance = F32(distance)
+    i = 0
+    while len(kept) < num_features:
+        dsq = F32(distance * distance)
+        if all(F32((int(xs[i]) - kx) ** 2 + (int(ys[i]) - ky) ** 2) >= dsq for kx, ky, _ in kept):
+            kept.append((int(xs[i]), int(ys[i]), int(labels[i])))
+        i += 1
+        if i == len(xs):
+            i = 0
+            distance = F32(distance - F32(1.0))
+    return np.asarray(kept, np.int32).reshape(-1, 3)
+
+
+def _bin_of(q):
+    return int(q).bit_length() - 1
+
+
+def extract_color(angle, magnitude, mask, num_features, strong_threshold):
+    """ColorGradientPyramid::extractTemplate -> features or None."""
+    angle, magnitude = np.asarray(angle, np.uint8), np.asarray(magnitude, F32)
+    ok = (angle > 0) & (magnitude > F32(strong_threshold) * F32(strong_threshold))
+    if mask is not None:
+        m = np.asarray(mask, np.uint8)
+        ok &= (m.astype(np.int32) - erode3(m).astype(np.int32)) > 0         # the mask's inner contour
+    ys, xs = np.nonzero(ok)                                                 # raster order
+    if len(ys) < num_features:
+        return None
+    order = np.argsort(-magnitude[ys, xs], kind="stable")                   # high magnitude first, ties in raster order
+    ys, xs = ys[order], xs[order]
+    labels = [_bin_of(angle[y, x]) for y, x in zip(ys, xs)]
+    return select_scattered(xs, ys, labels, num_features, F32(len(ys) // num_features + 1))
+
+
+def extract_depth(normal, mask, num_features, extract_threshold):
+    """DepthNormalPyramid::extractTemplate -> features or None."""
+    normal = np.asarray(normal, np.uint8)
+    inside = np.ones(normal.shape, bool) if mask is None else erode3(erode3(np.asarray(mask, np.uint8))) > 0
+    score = np.zeros(normal.shape, F32)
+    label = np.full(normal.shape, -1)
+    for k in range(8):
+        here = inside & (normal == (1 << k))
+        d = chessboard_distance(np.where(inside, normal & (1 << k), 0))     # 255 carries every bit: it is no zero pixel of any label's image
+        score[here], label[here] = d[here], k
+    ok = (label >= 0) & (score >= F32(extract_threshold))
+    ys, xs = np.nonzero(ok)
+    if len(ys) < num_features:
+        return None
+    lab = label[ys, xs]
+    counts = np.bincount(lab, minlength=8)
+    s = (score[ys, xs] / counts[lab].astype(F32)).astype(F32)
+    order = np.argsort(-s, kind="stable")
+    ys, xs, lab = ys[order], xs[order], lab[order]
+    distance = F32(np.sqrt(F32(int(inside.sum()))) / np.sqrt(F32(num_features)) + F32(1.5))
+    return select_scattered(xs, ys, lab, num_features, distance)
