@@ -588,6 +588,35 @@ lmx_status lmx_mesh_render(int32_t device, const double* triangles /*[n][3][3] m
 lmx_status lmx_bank_train_mesh(lmx_bank* bank, int32_t device, const double* triangles, int32_t n_triangles, const lmx_mesh_camera* cam,
                                const lmx_mesh_view* views, int32_t n_views, const char* class_id,
                                int32_t* template_ids /*[n_views], -1 = rejected; may be NULL*/, lmx_renderer_params** side_car /*may be NULL*/);
+/* The same trainer with options and statistics; opts == NULL is lmx_bank_train_mesh.  The bank, template ids, acceptance and side-car
+ * are identical whatever the options say.
+ * candidates = LMX_TRAIN_CANDIDATES_DEVICE: extractTemplate's per-pixel half (the mask erosions, DepthNormal's eight chessboard distance
+ * transforms, the raster scan for candidates) runs on the device too, one workgroup per (view, pyramid level, modality) (csrc/
+ * lmx_train_cand.hip), and only each window's candidate list crosses PCIe: 8-byte records in raster order {x | y << 14 | label << 28,
+ * float score} behind a 64-byte header (count, area, label counts, status, offset; csrc/lmx_train_cand.hpp).  The host keeps the
+ * division by the label counts, the stable sort, the scattered selection and cropTemplates.  Fallback rule: a view with a window (the
+ * silhouette box grown by 2, per level) whose image, rows padded to 4 pixels, exceeds 65 536 bytes (every window of up to 40 000 pixels
+ * fits, and square ones up to 256 x 256), or whose list does not fit the batch's record buffer, is rendered again after the regular
+ * batches and trained through the packed read-back and the host's per-pixel code (n_fallback_views).
+ * stats (may be NULL): n_device_views + n_fallback_views == n_views on the device path, both 0 on the host path; n_candidates and
+ * list_bytes (headers + records) count the lists of the device views; the times are those of the LMX_MESH_TRAIN_TIMING line. */
+#define LMX_TRAIN_CANDIDATES_HOST 0
+#define LMX_TRAIN_CANDIDATES_DEVICE 1
+typedef struct lmx_train_mesh_opts  { uint32_t struct_size; /* sizeof(lmx_train_mesh_opts) */ int32_t candidates; } lmx_train_mesh_opts;
+typedef struct lmx_train_mesh_stats { int32_t n_views, n_accepted, n_device_views, n_fallback_views; int64_t n_candidates, list_bytes;
+                                      double total_ms, device_wait_ms, host_select_ms; } lmx_train_mesh_stats;
+lmx_status lmx_bank_train_mesh_opts(lmx_bank* bank, int32_t device, const double* triangles, int32_t n_triangles, const lmx_mesh_camera* cam,
+                                    const lmx_mesh_view* views, int32_t n_views, const char* class_id, int32_t* template_ids,
+                                    lmx_renderer_params** side_car, const lmx_train_mesh_opts* opts /*NULL = host*/,
+                                    lmx_train_mesh_stats* stats /*may be NULL*/);
+/* Test hook: the production candidate kernel on one caller-supplied window (the whole H x W image; mag == NULL: DepthNormal, mask ==
+ * NULL: no object mask), then the production rank-and-select.  -> the list (records [n_records][2] words, label_counts[8], area) and
+ * the selection (features [n_features][3], accepted).  LMX_ERR_SHAPE: the window is too large for the device path (the rule above) or
+ * num_features is outside 1 .. 63; LMX_ERR_OVERFLOW: more than cap candidates. */
+lmx_status lmx_debug_train_extract(int32_t device, const uint8_t* label, const float* mag, const uint8_t* mask, int32_t H, int32_t W,
+                                   int32_t num_features, float strong_threshold, int32_t extract_threshold, uint32_t* records, size_t cap,
+                                   size_t* n_records, uint32_t* label_counts, uint32_t* area, int32_t* features, int32_t* n_features,
+                                   int32_t* accepted);
 
 /* ---- depth check of matches against the rendered depth of their templates ------------------------------------------------------------
  * The depth half of the reference's depth_normal_diff_calc (src/rgbdDetector.cpp:147-282): lay the template's rendered depth over the

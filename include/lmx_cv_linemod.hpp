@@ -363,11 +363,14 @@ class Detector {
   // `triangles` ([n][3][3] doubles, metres) from every view on the device and adds a template per view addTemplate accepts, in view order.
   // -> the template id per view (-1: rejected); *side_car (may be NULL; lmx_renderer_params_free) = the renderer-params of the accepted views.
   std::vector<int> addTemplatesFromMesh(const std::vector<double>& triangles, const lmx_mesh_camera& camera, const std::vector<lmx_mesh_view>& views,
-                                        const String& class_id, lmx_renderer_params** side_car = NULL) {
+                                        const String& class_id, lmx_renderer_params** side_car = NULL,
+                                        const lmx_train_mesh_opts* opts = NULL /* e.g. candidates = LMX_TRAIN_CANDIDATES_DEVICE; NULL: the host path */,
+                                        lmx_train_mesh_stats* stats = NULL) {
     if (triangles.size() % 9 != 0) LMX_CV_THROW(LMX_ERR_SHAPE, "addTemplatesFromMesh: triangles must hold 9 doubles per triangle");
     std::vector<int32_t> ids(views.size(), -1);
-    lmx_check(lmx_bank_train_mesh(mutable_bank(), device_, triangles.empty() ? NULL : &triangles[0], (int32_t)(triangles.size() / 9), &camera,
-                                  views.empty() ? NULL : &views[0], (int32_t)views.size(), class_id.c_str(), ids.empty() ? NULL : &ids[0], side_car));
+    lmx_check(lmx_bank_train_mesh_opts(mutable_bank(), device_, triangles.empty() ? NULL : &triangles[0], (int32_t)(triangles.size() / 9), &camera,
+                                       views.empty() ? NULL : &views[0], (int32_t)views.size(), class_id.c_str(), ids.empty() ? NULL : &ids[0], side_car,
+                                       opts, stats));
     invalidate();
     return std::vector<int>(ids.begin(), ids.end());
   }

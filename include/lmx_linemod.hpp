@@ -121,11 +121,13 @@ class Detector {
   // the device and adds a template per view addTemplate accepts, in view order.  -> the template id per view (-1: rejected).  `side_car`
   // (may be null) receives the renderer-params side-car of the accepted views; free it with lmx_renderer_params_free.
   std::vector<int> addTemplatesFromMesh(const std::vector<double>& triangles, const lmx_mesh_camera& camera, const std::vector<lmx_mesh_view>& views,
-                                        const std::string& class_id, lmx_renderer_params** side_car = nullptr) {
+                                        const std::string& class_id, lmx_renderer_params** side_car = nullptr,
+                                        const lmx_train_mesh_opts* opts = nullptr /* e.g. candidates = LMX_TRAIN_CANDIDATES_DEVICE; null: the host path */,
+                                        lmx_train_mesh_stats* stats = nullptr) {
     if (triangles.size() % 9 != 0) throw Exception(LMX_ERR_SHAPE, "addTemplatesFromMesh: triangles must hold 9 doubles per triangle");
     std::vector<int32_t> ids(views.size(), -1);
-    check(lmx_bank_train_mesh(bank_, device_, triangles.data(), (int32_t)(triangles.size() / 9), &camera, views.data(), (int32_t)views.size(),
-                              class_id.c_str(), ids.data(), side_car));
+    check(lmx_bank_train_mesh_opts(bank_, device_, triangles.data(), (int32_t)(triangles.size() / 9), &camera, views.data(), (int32_t)views.size(),
+                                   class_id.c_str(), ids.data(), side_car, opts, stats));
     return std::vector<int>(ids.begin(), ids.end());
   }
 

@@ -31,6 +31,7 @@ SYMBOLS = [
     "lmx_debug_device_sort_perm_large", "lmx_debug_device_finalize_cluster_large", "lmx_debug_device_finalize_cluster_large_depth",
     "lmx_debug_device_finalize_cluster_large_classes", "lmx_ctx_chain_stats",
     "lmx_ctx_enqueue_thresholds", "lmx_match_thresholds", "lmx_match_batch_thresholds", "lmx_match_masked_thresholds", "lmx_group_submit_thresholds",
+    "lmx_bank_train_mesh_opts", "lmx_debug_train_extract",
 ]
 
 (LMX_OK, LMX_ERR_INVALID_ARG, LMX_ERR_SHAPE, LMX_ERR_NO_DEVICE, LMX_ERR_HIP, LMX_ERR_OVERFLOW, LMX_ERR_IO,
@@ -43,6 +44,7 @@ LMX_DBG_DEPTH_INT, LMX_DBG_DEPTH_INT64, LMX_DBG_DEPTH_PIPELINED = 0, 1, 2   # va
  LMX_TAB_SUMMARY) = range(9)
 LMX_CTX_GRAY = 8   # include/lmx.h: ColorGradient sources are 8UC1 (gray), the colour pyramid one byte per pixel
 LMX_NORMAL_LUT_SIZE = 8000
+LMX_TRAIN_CANDIDATES_HOST, LMX_TRAIN_CANDIDATES_DEVICE = 0, 1
 LMX_LUT_DEFAULT, LMX_LUT_USER, LMX_LUT_SIDECAR, LMX_LUT_UNKNOWN = range(4)
 
 
@@ -100,6 +102,15 @@ class MeshCamera(C.Structure):
 
 class MeshView(C.Structure):
     _fields_ = [("R", C.c_double * 9), ("distance", C.c_double)]
+
+
+class TrainMeshOpts(C.Structure):    # lmx_train_mesh_opts
+    _fields_ = [("struct_size", C.c_uint32), ("candidates", C.c_int32)]
+
+
+class TrainMeshStats(C.Structure):   # lmx_train_mesh_stats
+    _fields_ = [("n_views", C.c_int32), ("n_accepted", C.c_int32), ("n_device_views", C.c_int32), ("n_fallback_views", C.c_int32),
+                ("n_candidates", C.c_int64), ("list_bytes", C.c_int64), ("total_ms", C.c_double), ("device_wait_ms", C.c_double), ("host_select_ms", C.c_double)]
 
 
 class DepthDiff(C.Structure):
@@ -169,6 +180,9 @@ def lib():
     L.lmx_mesh_render.argtypes = [C.c_int32, vp, C.c_int32, C.POINTER(MeshCamera), C.POINTER(MeshView), C.c_int32, vp, vp, vp, vp]
     L.lmx_bank_train_mesh.argtypes = [vp, C.c_int32, vp, C.c_int32, C.POINTER(MeshCamera), C.POINTER(MeshView), C.c_int32, C.c_char_p, vp,
                                       C.POINTER(C.POINTER(RendererParams))]
+    L.lmx_bank_train_mesh_opts.argtypes = L.lmx_bank_train_mesh.argtypes + [C.POINTER(TrainMeshOpts), C.POINTER(TrainMeshStats)]
+    L.lmx_debug_train_extract.argtypes = [C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, vp, vp,
+                                          i32p, i32p]
     L.lmx_default_normal_lut.argtypes = [vp]
     L.lmx_bank_set_normal_lut.argtypes = [vp, vp]
     L.lmx_bank_get_normal_lut.argtypes = [vp, vp]

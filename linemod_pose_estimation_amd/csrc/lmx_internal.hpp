@@ -500,6 +500,25 @@ void launch_mesh_raster(hipStream_t s, const double* d_tri, int n_tri, const mr:
                         int n_levels, mr::Tri* d_work /* [n_views][n_tri] */, int32_t* d_state /* [n_views][kMeshStateWords] */,
                         uint8_t* gray, uint16_t* depth, uint8_t* mask /* [n_views][H][W] each, any may be null */);
 void launch_mesh_pack(hipStream_t s, const MeshPackArgs& a, int n_views);
+// The device path of the mesh trainer (lmx_train_cand.hip; formats in lmx_train_cand.hpp): per (view, level, modality) the candidate list of
+// the window k_mesh_pack would copy.  Lists are reserved on `bump` (zeroed per batch) in `records` (device memory, `cap` records, even).
+namespace train_cand { struct ListHeader; struct Record; }
+struct TrainCandArgs {
+  const uint8_t* quant[kMaxLevels][kMaxModalities];   // as MeshPackArgs
+  const float* mag[kMaxLevels][kMaxModalities];       // non-null: the modality is ColorGradient
+  const uint8_t* mask0;                               // null: no object mask (lmx_debug_train_extract only)
+  const int32_t* state;
+  train_cand::ListHeader* headers;                    // device, [n_views][n_levels][n_mod]
+  train_cand::Record* records;
+  uint32_t* bump;
+  uint32_t cap;
+  float strong_threshold[kMaxModalities];
+  int32_t extract_threshold[kMaxModalities];          // at level 0; halved per level
+  int32_t n_levels, n_mod, W, H;
+};
+void launch_train_candidates(hipStream_t s, const TrainCandArgs& a, int n_views);
+// copies records [0, min(*bump, cap)) to `host_dst` (device-visible pinned memory of cap records)
+void launch_train_cand_copy(hipStream_t s, const TrainCandArgs& a, train_cand::Record* host_dst);
 lmx_status mesh_check_args(const char* what, const double* triangles, int32_t n_triangles, const lmx_mesh_camera* cam, const lmx_mesh_view* views,
                            int32_t n_views, mr::Camera* out);
 int mesh_first_invalid_view(const double* triangles, int32_t n_triangles, const lmx_mesh_view* views, int32_t n_views);

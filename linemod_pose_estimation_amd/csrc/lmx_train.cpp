@@ -17,6 +17,7 @@
 
 #include "lmx_internal.hpp"
 #include "lmx_mesh_raster.hpp"
+#include "lmx_train_cand.hpp"
 #include "lmx_train_select.hpp"
 
 namespace lmx {
@@ -179,6 +180,9 @@ lmx_status train_add_template(lmx_bank* bank, int device, const lmx_image* sourc
 // train_add_template derives on the host) of magnitudes, labels and mask into a pinned host buffer.  One stream, one synchronisation per
 // batch; the host half (select_pyramid of lmx_train_select.hpp) runs on a few threads,
 // one view each, while the device works on the next batch.  Templates are appended to the bank in view order when every batch is done.
+// With device candidates (lmx_bank_train_mesh_opts) k_train_candidates takes k_mesh_pack's place: per (view, level, modality) it leaves the
+// window's candidate list (lmx_train_cand.hpp) and only the lists are read back; the host half is then select_view_from_lists -- decode,
+// rank, select, crop.  Views whose lists carry a status are rendered again in a second pass through the packed read-back.
 namespace {
 
 constexpr int kMeshTrainBatch = 32;   // views per pass: 32 x ~100 covered tiles fill the 256 CUs; two pinned read-back buffers of 32 worst-case slots
@@ -221,6 +225,36 @@ void select_view(const lmx_bank* bank, const uint8_t* slot, const int32_t* state
   out.accepted = true;
 }
 
+// The same from the device's candidate lists (lmx_train_cand.hpp; hd = the view's [L][M] headers, recs = the batch's records): decode each
+// list, shift it by its window's origin, rank and select (select_from_list), cropTemplates.  -> false: a list carries a status (window too
+// large for the kernel, record buffer full) and the view must go through the pack-and-host path; nothing of `out` is set then.
+bool select_view_from_lists(const lmx_bank* bank, const train_cand::ListHeader* hd, const train_cand::Record* recs, uint32_t cap, const int32_t* state, int W0,
+                            int H0, ViewResult& out) {
+  const int L = (int)bank->T.size(), M = (int)bank->mods.size();
+  for (int k = 0; k < L * M; ++k) {
+    if (hd[k].status) return false;
+    if ((uint64_t)hd[k].offset + hd[k].n_cands > (uint64_t)cap) throw std::runtime_error("candidate list outside the record buffer");
+  }
+  const std::vector<Modality> mods = select_modalities(bank);
+  std::vector<std::vector<Feat>> tp((size_t)L * M);
+  for (int m = 0; m < M; ++m) {
+    size_t num_features = (size_t)mods[m].num_features;
+    for (int l = 0; l < L; ++l) {
+      if (l > 0) num_features /= 2;
+      int x0, y0, w, h;
+      mesh_window(state + MS_LEVEL + 4 * l, W0 >> l, H0 >> l, &x0, &y0, &w, &h);
+      const train_cand::ListHeader& lh = hd[(size_t)l * M + m];
+      if (!select_from_list(mods[m].color, lh, recs + lh.offset, x0, y0, num_features, tp[(size_t)l * M + m])) return true;   // rejected
+    }
+  }
+  Pyramid pyr;
+  crop_templates(tp, M, &pyr);
+  out.templates.swap(pyr.templates);
+  out.features.swap(pyr.features);
+  out.accepted = true;
+  return true;
+}
+
 struct MeshTrainBuffers {   // everything a call allocates: freed in one place
   std::vector<void*> dev, pinned;
   hipStream_t stream = nullptr;
@@ -235,9 +269,11 @@ struct MeshTrainBuffers {   // everything a call allocates: freed in one place
 }  // namespace
 
 lmx_status train_mesh(lmx_bank* bank, int device, const double* triangles, int n_tri, const lmx_mesh_camera* cam, const mr::Camera& dc,
-                      const lmx_mesh_view* views, int n_views, const char* class_id, int32_t* template_ids, lmx_renderer_params** side_car) {
+                      const lmx_mesh_view* views, int n_views, const char* class_id, int32_t* template_ids, lmx_renderer_params** side_car,
+                      bool device_candidates, lmx_train_mesh_stats* stats) {
   const int L = (int)bank->T.size(), M = (int)bank->mods.size();
   const int W0 = dc.W, H0 = dc.H;
+  if (stats) { std::memset(stats, 0, sizeof(*stats)); stats->n_views = n_views; }
   if (H0 < 16 || W0 < 16) { set_error("source image too small"); return LMX_ERR_SHAPE; }
   if (L < 1 || L > kMaxLevels || M < 1 || M > kMaxModalities) { set_error("lmx_bank_train_mesh: %d pyramid levels x %d modalities are not supported", L, M); return LMX_ERR_SHAPE; }
   if ((H0 >> (L - 1)) < 1 || (W0 >> (L - 1)) < 1) { set_error("image too small for %d pyramid levels", L); return LMX_ERR_SHAPE; }
@@ -321,17 +357,52 @@ lmx_status train_mesh(lmx_bank* bank, int device, const double* triangles, int n
   }
   uint8_t* h_pack[2] = {nullptr, nullptr};
   int32_t* h_state[2] = {nullptr, nullptr};
-  for (int k = 0; k < (n_views > B ? 2 : 1); ++k) {
+  size_t pinned_bytes = 0;
+  auto pinned = [&](size_t bytes) -> void* {
     void* p = nullptr;
-    TR_HIP(hipHostMalloc(&p, slot_bytes * B, hipHostMallocDefault));
-    buf.pinned.push_back(p); h_pack[k] = (uint8_t*)p;
-    TR_HIP(hipHostMalloc(&p, (size_t)B * kMeshStateWords * 4, hipHostMallocDefault));
-    buf.pinned.push_back(p); h_state[k] = (int32_t*)p;
-  }
+    if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) { set_error("hipHostMalloc of %zu bytes failed", bytes); return nullptr; }
+    buf.pinned.push_back(p); pinned_bytes += bytes;
+    return p;
+  };
+  // the packed read-back of the host path: for every view, or (device candidates) only once a view has to fall back to it
+  auto alloc_pack = [&](int n_buffers) -> bool {
+    for (int k = 0; k < n_buffers; ++k)
+      if (!h_pack[k] && !(h_pack[k] = (uint8_t*)pinned(slot_bytes * B))) return false;
+    return true;
+  };
+  const int n_buffers = n_views > B ? 2 : 1;
+  for (int k = 0; k < n_buffers; ++k)
+    if (!(h_state[k] = (int32_t*)pinned((size_t)B * kMeshStateWords * 4))) return LMX_ERR_HIP;
+  if (!device_candidates && !alloc_pack(n_buffers)) return LMX_ERR_HIP;
   pa.mask0 = d_mask; pa.state = d_state; pa.slot_bytes = slot_bytes; pa.n_levels = L; pa.n_mod = M; pa.n_cg = n_cg; pa.W = W0; pa.H = H0;
+  // device candidates: per batch one record buffer in device memory, lists reserved on a bump counter, copied to a pinned buffer by a
+  // kernel; sized for every window the kernel takes (<= kMaxWindowPixels records each), so a list that does not fit is not expected
+  TrainCandArgs ca;
+  std::memset(&ca, 0, sizeof(ca));
+  train_cand::ListHeader* h_headers[2] = {nullptr, nullptr};
+  train_cand::Record* h_records[2] = {nullptr, nullptr};
+  const size_t lists_per_view = (size_t)L * M;
+  if (device_candidates) {
+    size_t per_view = 0;
+    for (int l = 0; l < L; ++l) per_view += (size_t)M * std::min<size_t>((size_t)(W0 >> l) * (H0 >> l), train_cand::kMaxWindowPixels);
+    const size_t cap = (per_view * B + 1) & ~(size_t)1;
+    TM_ALLOC(d_headers, train_cand::ListHeader*, (size_t)B * lists_per_view * sizeof(train_cand::ListHeader));
+    TM_ALLOC(d_records, train_cand::Record*, cap * sizeof(train_cand::Record));
+    TM_ALLOC(d_bump, uint32_t*, 4);
+    for (int k = 0; k < n_buffers; ++k) {
+      h_headers[k] = (train_cand::ListHeader*)pinned((size_t)B * lists_per_view * sizeof(train_cand::ListHeader));
+      h_records[k] = (train_cand::Record*)pinned(cap * sizeof(train_cand::Record));
+      if (!h_headers[k] || !h_records[k]) return LMX_ERR_HIP;
+    }
+    std::memcpy(ca.quant, pa.quant, sizeof(ca.quant)); std::memcpy(ca.mag, pa.mag, sizeof(ca.mag));
+    ca.mask0 = d_mask; ca.state = d_state; ca.headers = d_headers; ca.records = d_records; ca.bump = d_bump; ca.cap = (uint32_t)cap;
+    ca.n_levels = L; ca.n_mod = M; ca.W = W0; ca.H = H0;
+    for (int m = 0; m < M; ++m) { ca.strong_threshold[m] = bank->mods[m].strong_threshold; ca.extract_threshold[m] = bank->mods[m].extract_threshold; }
+  }
 
-  auto issue = [&](int first, int n, int k) -> lmx_status {
-    TR_HIP(hipMemcpyAsync(d_views, views + first, (size_t)n * 10 * sizeof(double), hipMemcpyHostToDevice, s));
+  // renders and quantises `n` views and queues the read-back into buffer k: the candidate lists, or the packed windows
+  auto issue = [&](const lmx_mesh_view* vsrc, int n, int k, bool lists) -> lmx_status {
+    TR_HIP(hipMemcpyAsync(d_views, vsrc, (size_t)n * 10 * sizeof(double), hipMemcpyHostToDevice, s));
     launch_mesh_raster(s, d_tri, n_tri, dc, d_views, n, L, d_work, d_state, d_gray, d_depth, d_mask);
     for (int m = 0; m < M; ++m) {
       const lmx_modality_desc& md = bank->mods[m];
@@ -346,11 +417,19 @@ lmx_status train_mesh(lmx_bank* bank, int device, const double* triangles, int n
         launch_depth_quantize(s, d_depth, (uint8_t*)pa.quant[0][m], nullptr, H0, W0, n, md.distance_threshold, md.difference_threshold, d_bins);
       }
     }
-    MeshPackArgs a = pa;
     void* dp = nullptr;
-    TR_HIP(hipHostGetDevicePointer(&dp, h_pack[k], 0));
-    a.out = (uint8_t*)dp;
-    launch_mesh_pack(s, a, n);
+    if (lists) {
+      TR_HIP(hipMemsetAsync(ca.bump, 0, 4, s));
+      launch_train_candidates(s, ca, n);
+      TR_HIP(hipHostGetDevicePointer(&dp, h_records[k], 0));
+      launch_train_cand_copy(s, ca, (train_cand::Record*)dp);
+      TR_HIP(hipMemcpyAsync(h_headers[k], ca.headers, (size_t)n * lists_per_view * sizeof(train_cand::ListHeader), hipMemcpyDeviceToHost, s));
+    } else {
+      MeshPackArgs a = pa;
+      TR_HIP(hipHostGetDevicePointer(&dp, h_pack[k], 0));
+      a.out = (uint8_t*)dp;
+      launch_mesh_pack(s, a, n);
+    }
     TR_HIP(hipGetLastError());
     TR_HIP(hipMemcpyAsync(h_state[k], d_state, (size_t)n * kMeshStateWords * 4, hipMemcpyDeviceToHost, s));
     return LMX_OK;
@@ -373,48 +452,95 @@ lmx_status train_mesh(lmx_bank* bank, int device, const double* triangles, int n
   std::vector<uint16_t> acc_centre;
   const int32_t existing = lmx_bank_num_templates(bank, class_id);
   int32_t next_id = existing, fb = 0;
-  lmx_status st = issue(0, std::min(B, n_views), 0);
+  // what a pass leaves per view; the templates are collected in view order when every pass is done
+  std::vector<ViewResult> all((size_t)n_views);
+  std::vector<int32_t> view_box((size_t)n_views * 4);
+  std::vector<uint16_t> view_centre((size_t)n_views);
+  std::vector<int> fallback;                 // views whose lists carry a status: trained by the pack-and-host path in a second pass
+  int64_t n_candidates = 0, list_bytes = 0;
+  // One pass over views[idx[0 .. nv)] (idx == null: all views) in batches of B, the read-back of batch b + 1 queued while the host selects
+  // on batch b.
+  auto run_pass = [&](const int* idx, int nv, bool lists) -> lmx_status {
+    std::vector<lmx_mesh_view> picked;
+    const lmx_mesh_view* vsrc = views;
+    if (idx) {
+      picked.resize((size_t)nv);
+      for (int i = 0; i < nv; ++i) picked[(size_t)i] = views[idx[i]];
+      vsrc = picked.data();
+    }
+    lmx_status st = issue(vsrc, std::min(B, nv), 0, lists);
+    if (st != LMX_OK) return st;
+    for (int first = 0, k = 0; first < nv; first += B, k ^= 1) {
+      const int n = std::min(B, nv - first);
+      const clk::time_point t_wait = clk::now();
+      TR_HIP(hipStreamSynchronize(s));   // batch `first` is in buffer k (h_pack or h_records / h_headers, h_state); the device buffers are free again
+      wait_ms += ms_since(t_wait); ++n_batches;
+      if (first + B < nv) {
+        st = issue(vsrc + first + B, std::min(B, nv - first - B), k ^ 1, lists);
+        if (st != LMX_OK) return st;
+      }
+      const int32_t* stw = h_state[k];
+      auto view_of = [&](int i) { return idx ? idx[first + i] : first + i; };
+      for (int i = 0; i < n; ++i)
+        if (stw[(size_t)i * kMeshStateWords + MS_INVALID]) {
+          set_error("lmx_bank_train_mesh: view %d puts a vertex at or behind the camera (Z <= 0.01); nothing was added", view_of(i));
+          return LMX_ERR_INVALID_ARG;
+        }
+      const uint8_t* pack = h_pack[k];
+      const train_cand::ListHeader* headers = h_headers[k];
+      const train_cand::Record* records = h_records[k];
+      std::vector<uint8_t> needs_pack((size_t)n, 0);
+      const clk::time_point t_sel = clk::now();
+      pool.parallel_for(n, [&](int i) {
+        ViewResult& r = all[(size_t)view_of(i)];
+        try {
+          if (lists) needs_pack[(size_t)i] = !select_view_from_lists(bank, headers + (size_t)i * lists_per_view, records, ca.cap, stw + (size_t)i * kMeshStateWords, W0, H0, r);
+          else select_view(bank, pack + (size_t)i * slot_bytes, stw + (size_t)i * kMeshStateWords, W0, H0, r);
+        } catch (const std::exception& e) {
+          r.status = LMX_ERR_INVALID_ARG; r.error = e.what();
+        }
+      });
+      select_ms += ms_since(t_sel);
+      for (int i = 0; i < n; ++i) {
+        const int v = view_of(i);
+        const ViewResult& r = all[(size_t)v];
+        if (r.status != LMX_OK) { set_error("lmx_bank_train_mesh: view %d: %s", v, r.error.c_str()); return r.status; }
+        std::memcpy(&view_box[(size_t)v * 4], stw + (size_t)i * kMeshStateWords + MS_LEVEL, 16);
+        view_centre[(size_t)v] = (uint16_t)stw[(size_t)i * kMeshStateWords + MS_CENTRE_DEPTH];
+        if (needs_pack[(size_t)i]) { fallback.push_back(v); continue; }
+        if (lists) {
+          list_bytes += (int64_t)(lists_per_view * sizeof(train_cand::ListHeader));
+          for (size_t j = 0; j < lists_per_view; ++j) {
+            const uint32_t nc = headers[(size_t)i * lists_per_view + j].n_cands;
+            n_candidates += nc; list_bytes += (int64_t)nc * (int64_t)sizeof(train_cand::Record);
+          }
+        }
+      }
+    }
+    return LMX_OK;
+  };
+  lmx_status st = run_pass(nullptr, n_views, device_candidates);
   if (st != LMX_OK) return st;
-  for (int first = 0, k = 0; first < n_views; first += B, k ^= 1) {
-    const int n = std::min(B, n_views - first);
-    const clk::time_point t_wait = clk::now();
-    TR_HIP(hipStreamSynchronize(s));   // batch `first` is in h_pack[k] / h_state[k]; the device buffers are free again
-    wait_ms += ms_since(t_wait); ++n_batches;
-    if (first + B < n_views) {
-      st = issue(first + B, std::min(B, n_views - first - B), k ^ 1);
-      if (st != LMX_OK) return st;
-    }
-    std::vector<ViewResult> res((size_t)n);
-    const int32_t* stw = h_state[k];
-    for (int i = 0; i < n; ++i)
-      if (stw[(size_t)i * kMeshStateWords + MS_INVALID]) {
-        set_error("lmx_bank_train_mesh: view %d puts a vertex at or behind the camera (Z <= 0.01); nothing was added", first + i);
-        return LMX_ERR_INVALID_ARG;
-      }
-    const uint8_t* pack = h_pack[k];
-    const clk::time_point t_sel = clk::now();
-    pool.parallel_for(n, [&](int i) {
-      try {
-        select_view(bank, pack + (size_t)i * slot_bytes, stw + (size_t)i * kMeshStateWords, W0, H0, res[(size_t)i]);
-      } catch (const std::exception& e) {
-        res[(size_t)i].status = LMX_ERR_INVALID_ARG; res[(size_t)i].error = e.what();
-      }
-    });
-    select_ms += ms_since(t_sel);
-    for (int i = 0; i < n; ++i) {
-      ViewResult& r = res[(size_t)i];
-      if (r.status != LMX_OK) { set_error("lmx_bank_train_mesh: view %d: %s", first + i, r.error.c_str()); return r.status; }
-      if (!r.accepted) continue;
-      for (size_t t = 0; t < r.templates.size(); t += 5) r.templates[t + 3] += fb;
-      templates.insert(templates.end(), r.templates.begin(), r.templates.end());
-      features.insert(features.end(), r.features.begin(), r.features.end());
-      fb += (int32_t)(r.features.size() / 3);
-      ids[(size_t)(first + i)] = next_id++;
-      accepted_views.push_back(first + i);
-      const int32_t* b = stw + (size_t)i * kMeshStateWords + MS_LEVEL;
-      acc_rect.insert(acc_rect.end(), {b[0], b[1], b[2] - b[0] + 1, b[3] - b[1] + 1});   // an accepted view has covered pixels
-      acc_centre.push_back((uint16_t)stw[(size_t)i * kMeshStateWords + MS_CENTRE_DEPTH]);
-    }
+  const int n_fallback = (int)fallback.size();
+  if (n_fallback) {   // the rasteriser is deterministic: these views are simply rendered again, for the packed read-back
+    if (!alloc_pack(std::min(n_buffers, n_fallback > B ? 2 : 1))) return LMX_ERR_HIP;
+    const std::vector<int> again(fallback);
+    st = run_pass(again.data(), n_fallback, false);
+    if (st != LMX_OK) return st;
+  }
+  for (int v = 0; v < n_views; ++v) {
+    ViewResult& r = all[(size_t)v];
+    if (!r.accepted) continue;
+    for (size_t t = 0; t < r.templates.size(); t += 5) r.templates[t + 3] += fb;
+    templates.insert(templates.end(), r.templates.begin(), r.templates.end());
+    features.insert(features.end(), r.features.begin(), r.features.end());
+    fb += (int32_t)(r.features.size() / 3);
+    ids[(size_t)v] = next_id++;
+    accepted_views.push_back(v);
+    const int32_t* b = &view_box[(size_t)v * 4];
+    acc_rect.insert(acc_rect.end(), {b[0], b[1], b[2] - b[0] + 1, b[3] - b[1] + 1});   // an accepted view has covered pixels
+    acc_centre.push_back(view_centre[(size_t)v]);
+    std::vector<int32_t>().swap(r.templates); std::vector<int32_t>().swap(r.features);
   }
   const size_t n_acc = accepted_views.size();
   if (side_car) {
@@ -439,10 +565,19 @@ lmx_status train_mesh(lmx_bank* bank, int device, const double* triangles, int n
   }
   if (template_ids) std::memcpy(template_ids, ids.data(), ids.size() * sizeof(int32_t));
   if (side_car) *side_car = side.release();
+  const double total_ms = ms_since(t_call);
+  if (stats) {
+    stats->n_accepted = (int32_t)n_acc;
+    stats->n_device_views = device_candidates ? n_views - n_fallback : 0;
+    stats->n_fallback_views = n_fallback;
+    stats->n_candidates = n_candidates; stats->list_bytes = list_bytes;
+    stats->total_ms = total_ms; stats->device_wait_ms = wait_ms; stats->host_select_ms = select_ms;
+  }
   if (timing)
     std::fprintf(stderr, "lmx_bank_train_mesh timing: views %d accepted %zu batches %d of %d total_ms %.3f device_wait_ms %.3f host_select_ms %.3f (%d threads) "
-                 "device_bytes %zu pinned_bytes %zu\n", n_views, n_acc, n_batches, B, ms_since(t_call), wait_ms, select_ms, pool.threads(), device_bytes,
-                 (slot_bytes * B + (size_t)B * kMeshStateWords * 4) * (n_views > B ? 2 : 1));
+                 "device_bytes %zu pinned_bytes %zu candidates %s device_views %d fallback_views %d n_candidates %lld list_bytes %lld\n", n_views, n_acc, n_batches, B,
+                 total_ms, wait_ms, select_ms, pool.threads(), device_bytes, pinned_bytes, device_candidates ? "device" : "host",
+                 device_candidates ? n_views - n_fallback : 0, n_fallback, (long long)n_candidates, (long long)list_bytes);
   return LMX_OK;
 }
 #undef TM_ALLOC
@@ -465,6 +600,81 @@ extern "C" lmx_status lmx_bank_train_mesh(lmx_bank* bank, int32_t device, const 
   lmx::mr::Camera dc;
   const lmx_status st = lmx::mesh_check_args("lmx_bank_train_mesh", triangles, n_triangles, cam, views, n_views, &dc);
   if (st != LMX_OK) return st;
-  return lmx::train_mesh(bank, device, triangles, n_triangles, cam, dc, views, n_views, class_id, template_ids, side_car);
+  return lmx::train_mesh(bank, device, triangles, n_triangles, cam, dc, views, n_views, class_id, template_ids, side_car, false, nullptr);
+  });
+}
+
+extern "C" lmx_status lmx_bank_train_mesh_opts(lmx_bank* bank, int32_t device, const double* triangles, int32_t n_triangles, const lmx_mesh_camera* cam,
+                                               const lmx_mesh_view* views, int32_t n_views, const char* class_id, int32_t* template_ids,
+                                               lmx_renderer_params** side_car, const lmx_train_mesh_opts* opts, lmx_train_mesh_stats* stats) {
+  return lmx::guarded("lmx_bank_train_mesh_opts", [&]() -> lmx_status {
+  if (!bank || !class_id) { lmx::set_error("lmx_bank_train_mesh: null argument"); return LMX_ERR_INVALID_ARG; }
+  if (opts && (opts->struct_size < sizeof(lmx_train_mesh_opts) || (opts->candidates != LMX_TRAIN_CANDIDATES_HOST && opts->candidates != LMX_TRAIN_CANDIDATES_DEVICE))) {
+    lmx::set_error("lmx_bank_train_mesh_opts: struct_size %u, candidates %d are not valid options", opts->struct_size, opts->candidates);
+    return LMX_ERR_INVALID_ARG;
+  }
+  lmx::mr::Camera dc;
+  const lmx_status st = lmx::mesh_check_args("lmx_bank_train_mesh", triangles, n_triangles, cam, views, n_views, &dc);
+  if (st != LMX_OK) return st;
+  return lmx::train_mesh(bank, device, triangles, n_triangles, cam, dc, views, n_views, class_id, template_ids, side_car,
+                         opts && opts->candidates == LMX_TRAIN_CANDIDATES_DEVICE, stats);
+  });
+}
+
+// The production kernel and the production rank-and-select on one caller-supplied window (the whole image): tests/test_gpu_train_candidates.py
+extern "C" lmx_status lmx_debug_train_extract(int32_t device, const uint8_t* label, const float* mag, const uint8_t* mask, int32_t H, int32_t W, int32_t num_features,
+                                              float strong_threshold, int32_t extract_threshold, uint32_t* records, size_t cap, size_t* n_records,
+                                              uint32_t* label_counts, uint32_t* area, int32_t* features, int32_t* n_features, int32_t* accepted) {
+  return lmx::guarded("lmx_debug_train_extract", [&]() -> lmx_status {
+    using namespace lmx;
+    namespace tc = train_cand;
+    if (!label || !records || !n_records || !label_counts || !area || !features || !n_features || !accepted) { set_error("lmx_debug_train_extract: null argument"); return LMX_ERR_INVALID_ARG; }
+    if (H < 1 || W < 1 || !tc::window_fits(W, H)) { set_error("lmx_debug_train_extract: a %d x %d window is outside the device path (rows padded to 4 pixels, at most %d bytes)", W, H, 4 * tc::kMaxWindowDwords); return LMX_ERR_SHAPE; }
+    { std::string why; if (!train_select::check_num_features({train_select::Modality{mag != nullptr, num_features, strong_threshold, extract_threshold}}, 1, &why)) { set_error("lmx_debug_train_extract: %s", why.c_str()); return LMX_ERR_SHAPE; } }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available; this library has no CPU path"); return LMX_ERR_NO_DEVICE; }
+    TR_HIP(hipSetDevice(device));
+    const size_t px = (size_t)H * W, cap_dev = std::min<size_t>((cap + 1) & ~(size_t)1, (size_t)tc::kMaxWindowPixels);
+    std::vector<void*> to_free;
+    struct Free { std::vector<void*>& v; ~Free() { for (void* p : v) (void)hipFree(p); } } free_all{to_free};
+    auto dmalloc = [&](size_t bytes) -> void* { void* p = nullptr; if (hipMalloc(&p, std::max<size_t>(bytes, 256) + 64) != hipSuccess) return nullptr; to_free.push_back(p); return p; };
+    uint8_t* d_label = (uint8_t*)dmalloc(px);
+    float* d_mag = mag ? (float*)dmalloc(px * 4) : nullptr;
+    uint8_t* d_mask = mask ? (uint8_t*)dmalloc(px) : nullptr;
+    int32_t* d_state = (int32_t*)dmalloc(kMeshStateWords * 4);
+    tc::ListHeader* d_header = (tc::ListHeader*)dmalloc(sizeof(tc::ListHeader));
+    tc::Record* d_records = (tc::Record*)dmalloc((cap_dev + 2) * sizeof(tc::Record));
+    uint32_t* d_bump = (uint32_t*)dmalloc(4);
+    if (!d_label || (mag && !d_mag) || (mask && !d_mask) || !d_state || !d_header || !d_records || !d_bump) { set_error("hipMalloc failed"); return LMX_ERR_HIP; }
+    int32_t state[kMeshStateWords] = {};
+    state[MS_LEVEL + 0] = 0; state[MS_LEVEL + 1] = 0; state[MS_LEVEL + 2] = W - 1; state[MS_LEVEL + 3] = H - 1;   // mesh_window: the whole image
+    TR_HIP(hipMemcpy(d_label, label, px, hipMemcpyHostToDevice));
+    if (mag) TR_HIP(hipMemcpy(d_mag, mag, px * 4, hipMemcpyHostToDevice));
+    if (mask) TR_HIP(hipMemcpy(d_mask, mask, px, hipMemcpyHostToDevice));
+    TR_HIP(hipMemcpy(d_state, state, sizeof(state), hipMemcpyHostToDevice));
+    TR_HIP(hipMemset(d_bump, 0, 4));
+    TR_HIP(hipMemset(d_header, 0xff, sizeof(tc::ListHeader)));
+    TrainCandArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.quant[0][0] = d_label; a.mag[0][0] = d_mag; a.mask0 = d_mask; a.state = d_state; a.headers = d_header; a.records = d_records; a.bump = d_bump;
+    a.cap = (uint32_t)cap_dev; a.strong_threshold[0] = strong_threshold; a.extract_threshold[0] = extract_threshold; a.n_levels = 1; a.n_mod = 1; a.W = W; a.H = H;
+    launch_train_candidates(nullptr, a, 1);
+    TR_HIP(hipGetLastError());
+    TR_HIP(hipDeviceSynchronize());
+    tc::ListHeader hd;
+    TR_HIP(hipMemcpy(&hd, d_header, sizeof(hd), hipMemcpyDeviceToHost));
+    if (hd.status == tc::ST_OVERFLOW || (hd.status == 0 && hd.n_cands > cap)) { set_error("lmx_debug_train_extract: %u candidates exceed the capacity %zu", hd.n_cands, cap); return LMX_ERR_OVERFLOW; }
+    if (hd.status != 0 || (uint64_t)hd.offset + hd.n_cands > cap_dev) { set_error("lmx_debug_train_extract: list status %u, offset %u", hd.status, hd.offset); return LMX_ERR_HIP; }
+    std::vector<tc::Record> recs(hd.n_cands);
+    if (hd.n_cands) TR_HIP(hipMemcpy(recs.data(), d_records + hd.offset, recs.size() * sizeof(tc::Record), hipMemcpyDeviceToHost));
+    if (hd.n_cands) std::memcpy(records, recs.data(), recs.size() * sizeof(tc::Record));
+    *n_records = hd.n_cands;
+    std::memcpy(label_counts, hd.label_counts, sizeof(hd.label_counts));
+    *area = hd.area;
+    std::vector<train_select::Feat> out;
+    *accepted = train_select::select_from_list(mag != nullptr, hd, recs.data(), 0, 0, (size_t)num_features, out) ? 1 : 0;
+    *n_features = *accepted ? (int32_t)out.size() : 0;
+    for (size_t i = 0; *accepted && i < out.size(); ++i) { features[3 * i] = out[i].x; features[3 * i + 1] = out[i].y; features[3 * i + 2] = out[i].label; }
+    return LMX_OK;
   });
 }

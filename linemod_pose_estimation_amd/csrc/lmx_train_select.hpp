@@ -3,6 +3,8 @@
 // lmx_train.cpp includes and that tests/cpp/train_select_host.cpp compiles with g++, so tests/test_train_select_host.py checks it against
 // the oracle on the CPU.  select_pyramid() is the one form of "per-level window, crop, extract, shift back, cropTemplates"; both trainers
 // (train_add_template on whole frames, select_view on the packed windows of the mesh trainer) only collect the arrays and call it.
+// The mesh trainer's device path delivers each window's candidate list instead of arrays (lmx_train_cand.hpp, which compiles as plain C++
+// too): select_from_list decodes it and runs rank_select_color / rank_select_depth, the sequential rest the two extract functions end in.
 #pragma once
 
 #include <stdint.h>
@@ -12,7 +14,10 @@
 #include <cmath>
 #include <cstring>
 #include <string>
+#include <stdexcept>
 #include <vector>
+
+#include "lmx_train_cand.hpp"
 
 namespace lmx {
 namespace train_select {
@@ -89,6 +94,41 @@ inline void select_scattered(const std::vector<Cand>& cands, std::vector<Feat>& 
 
 inline bool by_score_desc(const Cand& a, const Cand& b) { return a.score > b.score; }  // Candidate::operator<
 
+// The sequential rest of the two extractTemplates, on a candidate list in raster order: extract_color / extract_depth below collect the list
+// from images; the mesh trainer's device path (lmx_train_cand.hpp) delivers it ready-made.  `cands` is reordered (and, for DepthNormal,
+// its raw distances divided by the label counts).  false: fewer candidates than features, the template is rejected.
+inline bool rank_select_color(std::vector<Cand>& cands, size_t num_features, std::vector<Feat>& out) {
+  if (cands.size() < num_features) return false;
+  std::stable_sort(cands.begin(), cands.end(), by_score_desc);
+  const float distance = static_cast<float>(cands.size() / num_features + 1);
+  select_scattered(cands, out, num_features, distance);
+  return true;
+}
+inline bool rank_select_depth(std::vector<Cand>& cands, const int label_counts[8], size_t area, size_t num_features, std::vector<Feat>& out) {
+  if (cands.size() < num_features) return false;
+  for (Cand& c : cands) c.score /= (float)label_counts[c.label];
+  std::stable_sort(cands.begin(), cands.end(), by_score_desc);
+  const float distance = sqrtf((float)area) / sqrtf((float)num_features) + 1.5f;
+  select_scattered(cands, out, num_features, distance);
+  return true;
+}
+
+// One window's candidate list as the device path delivers it (lmx_train_cand.hpp) -> the selected features, shifted by the window's origin
+// (x0, y0) into level coordinates.  false: rejected.
+inline bool select_from_list(bool color, const train_cand::ListHeader& hd, const train_cand::Record* recs, int x0, int y0, size_t num_features,
+                             std::vector<Feat>& out) {
+  std::vector<Cand> cands(hd.n_cands);
+  for (size_t i = 0; i < cands.size(); ++i) {
+    const int label = train_cand::rec_label(recs[i].xyl);
+    if (!color && label < 0) throw std::runtime_error("candidate list holds a DepthNormal record without a label");
+    cands[i] = Cand{train_cand::rec_x(recs[i].xyl) + x0, train_cand::rec_y(recs[i].xyl) + y0, label, recs[i].score};
+  }
+  if (color) return rank_select_color(cands, num_features, out);
+  int label_counts[8];
+  for (int k = 0; k < 8; ++k) label_counts[k] = (int)hd.label_counts[k];
+  return rank_select_depth(cands, label_counts, (size_t)hd.area, num_features, out);
+}
+
 // ColorGradientPyramid::extractTemplate
 inline bool extract_color(const std::vector<uint8_t>& angle, const std::vector<float>& mag, const std::vector<uint8_t>& mask, int H, int W,
                           size_t num_features, float strong_threshold, std::vector<Feat>& out) {
@@ -108,11 +148,7 @@ inline bool extract_color(const std::vector<uint8_t>& angle, const std::vector<f
       const uint8_t q = angle[i];
       if (q > 0 && mag[i] > threshold_sq) cands.push_back(Cand{c, r, label_of(q), mag[i]});
     }
-  if (cands.size() < num_features) return false;
-  std::stable_sort(cands.begin(), cands.end(), by_score_desc);
-  const float distance = static_cast<float>(cands.size() / num_features + 1);
-  select_scattered(cands, out, num_features, distance);
-  return true;
+  return rank_select_color(cands, num_features, out);
 }
 
 // DepthNormalPyramid::extractTemplate
@@ -143,14 +179,9 @@ inline bool extract_depth(const std::vector<uint8_t>& normal, const std::vector<
         ++label_counts[label];
       }
     }
-  if (cands.size() < num_features) return false;
-  for (Cand& c : cands) c.score /= (float)label_counts[c.label];
-  std::stable_sort(cands.begin(), cands.end(), by_score_desc);
   size_t area = normal.size();
   if (!no_mask) { area = 0; for (uint8_t v : local) area += v != 0; }
-  const float distance = sqrtf((float)area) / sqrtf((float)num_features) + 1.5f;
-  select_scattered(cands, out, num_features, distance);
-  return true;
+  return rank_select_depth(cands, label_counts, area, num_features, out);
 }
 
 // The window rule.  With an object mask (what the reference's trainers pass: the rendered silhouette) everything extractTemplate looks at

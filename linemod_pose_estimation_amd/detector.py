@@ -179,18 +179,26 @@ class NativeBank:
         return tid.value, tuple(bb)
 
     def train_mesh(self, triangles, views, width=640, height=480, fx=826.119324, fy=826.119324, cx=None, cy=None, class_id="obj", light=MESH_LIGHT,
-                   device=0, save_side_car=None, side_car_scalars=None):
+                   device=0, save_side_car=None, side_car_scalars=None, device_candidates=False):
         """lmx_bank_train_mesh, the reference's trainer loop (src/renderer.cpp:262-329): renders every (R, distance) of `views` on the
         device and adds a template per view addTemplate accepts, in view order.  -> list of dicts per ACCEPTED view {view, rect, distance}
         (what meshsynth.train_bank returns); `.last_template_ids` = int32 [n_views] (-1: rejected), `.last_side_car` = the renderer-params
         side-car of the accepted views as a dict (obj_origin_dists, rects, distances, R, T, K, renderer_*).  save_side_car: also write it
-        as a *_renderer_params.yml, with `side_car_scalars` (renderer_n_points, renderer_radius_min, ...) set first."""
+        as a *_renderer_params.yml, with `side_car_scalars` (renderer_n_points, renderer_radius_min, ...) set first.
+        device_candidates: lmx_bank_train_mesh_opts with LMX_TRAIN_CANDIDATES_DEVICE -- the candidates of every window are found and
+        compacted on the device and only their lists are read back; the result is the same.  `.last_train_stats` = the call's
+        lmx_train_mesh_stats as a dict (n_views, n_accepted, n_device_views, n_fallback_views, n_candidates, list_bytes, total_ms,
+        device_wait_ms, host_select_ms)."""
         tri, cam, packed = _mesh_args(triangles, views, width, height, fx, fy, cx, cy, light)
         ids = np.full(len(views), -1, np.int32)
         side = C.POINTER(_lib.RendererParams)()
         L = _lib.lib()
-        _lib.check(L.lmx_bank_train_mesh(self.h, device, tri.ctypes.data, tri.shape[0], C.byref(cam), packed.ctypes.data_as(C.POINTER(_lib.MeshView)),
-                                         len(views), class_id.encode(), ids.ctypes.data, C.byref(side)))
+        opts = _lib.TrainMeshOpts(C.sizeof(_lib.TrainMeshOpts), _lib.LMX_TRAIN_CANDIDATES_DEVICE if device_candidates else _lib.LMX_TRAIN_CANDIDATES_HOST)
+        stats = _lib.TrainMeshStats()
+        self.last_train_stats = None
+        _lib.check(L.lmx_bank_train_mesh_opts(self.h, device, tri.ctypes.data, tri.shape[0], C.byref(cam), packed.ctypes.data_as(C.POINTER(_lib.MeshView)),
+                                              len(views), class_id.encode(), ids.ctypes.data, C.byref(side), C.byref(opts), C.byref(stats)))
+        self.last_train_stats = {k: getattr(stats, k) for k, _ in _lib.TrainMeshStats._fields_}
         try:
             for k, v in (side_car_scalars or {}).items():
                 setattr(side.contents, k, v)

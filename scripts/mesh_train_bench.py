@@ -9,7 +9,8 @@ view, NativeBank.add_template per view).  One box, one process, same run:
 and, from lmx_bank_train_mesh's own clock (LMX_MESH_TRAIN_TIMING=1), where a call's wall time goes: waiting for the device, host selection.
 --kernels: only run train_mesh on all 2652 views twice (the program for `rocprofv3 --kernel-trace --stats -- python scripts/mesh_train_bench.py
 --kernels`: kernel time per view = the k_mesh_* / k_color_quantize / k_depth_quantize totals divided by 2 x 2652).
-Needs a GPU.  usage: mesh_train_bench.py [--rounds 3] [--kernels]"""
+--device-candidates: the same with the candidates found and compacted on the device (device_candidates=True).
+Needs a GPU.  usage: mesh_train_bench.py [--rounds 3] [--kernels] [--device-candidates]"""
 import argparse
 import os
 import re
@@ -34,7 +35,7 @@ def same(a, b):
     return all(np.array_equal(x[1], y[1]) and np.array_equal(x[2], y[2]) for x, y in zip(a.classes, b.classes)) and len(a.classes) == len(b.classes)
 
 
-def timed_train_mesh(tri, views):
+def timed_train_mesh(tri, views, device_candidates=False):
     """-> (seconds, bank, the library's timing line as a dict)."""
     nb = fresh()
     sys.stderr.flush()
@@ -43,7 +44,7 @@ def timed_train_mesh(tri, views):
         os.dup2(tmp.fileno(), 2)
         try:
             t0 = time.perf_counter()
-            nb.train_mesh(tri, views)
+            nb.train_mesh(tri, views, device_candidates=device_candidates)
             dt = time.perf_counter() - t0
         finally:
             os.dup2(saved, 2)
@@ -59,6 +60,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--kernels", action="store_true")
+    ap.add_argument("--device-candidates", action="store_true", help="train_mesh with device_candidates=True (lmx_bank_train_mesh_opts, LMX_TRAIN_CANDIDATES_DEVICE)")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -69,12 +71,12 @@ def main():
     first = views[:442]
     if args.kernels:
         for _ in range(2):
-            dt, _, info = timed_train_mesh(chip, views)
+            dt, _, info = timed_train_mesh(chip, views, args.device_candidates)
             print("train_mesh 2652 views: %.3f s  %s" % (dt, info))
         return
     # warm: device, library, the C rasteriser
     ms.train_bank(fresh().add_template, chip, first[:8])
-    timed_train_mesh(chip, first[:40])
+    timed_train_mesh(chip, first[:40], args.device_candidates)
     base, feat, full, infos = [], [], [], []
     ref = None
     for r in range(args.rounds):
@@ -83,16 +85,17 @@ def main():
         meta = ms.train_bank(nb.add_template, chip, first)
         base.append(len(first) / (time.perf_counter() - t0))
         ref = nb
-        dt, got, _ = timed_train_mesh(chip, first)
+        dt, got, _ = timed_train_mesh(chip, first, args.device_candidates)
         feat.append(len(first) / dt)
         assert len(meta) == 442 and same(got, ref), "train_mesh differs from the per-view loop"
-        dt, _, info = timed_train_mesh(chip, views)
+        dt, _, info = timed_train_mesh(chip, views, args.device_candidates)
         full.append(len(views) / dt)
         infos.append(info)
     med = lambda xs: float(np.median(xs))  # noqa: E731
     ratio = med(feat) / med(base)
     print("mesh_train_bench  %s  device %s" % (time.strftime("%Y-%m-%d %H:%M"), torch.cuda.get_device_name(0)))
-    print("memoryChip2 (%d triangles), 640x480, ColorGradient + DepthNormal, T = (5, 8); median of %d rounds" % (len(chip), args.rounds))
+    print("memoryChip2 (%d triangles), 640x480, ColorGradient + DepthNormal, T = (5, 8); median of %d rounds; candidates on the %s" %
+          (len(chip), args.rounds, "device" if args.device_candidates else "host"))
     print("%-58s %12.1f views/s  (%.3f ms per view)" % ("baseline: meshsynth.train_bank(add_template), 442 views", med(base), 1e3 / med(base)))
     print("%-58s %12.1f views/s  (%.3f ms per view)" % ("feature:  train_mesh, the same 442 views", med(feat), 1e3 / med(feat)))
     print("%-58s %12.1f views/s  (%.3f ms per view)" % ("feature:  train_mesh, all 2652 views", med(full), 1e3 / med(full)))
@@ -103,6 +106,9 @@ def main():
               "%d batches of %d views" % (i["total_ms"], i["device_wait_ms"], i["host_select_ms"], int(i["threads"]) if "threads" in i else 8,
                                           100.0 * i["host_select_ms"] / i["total_ms"], int(i["batches"]), int(i.get("of", 32))))
         print("device memory of the call: %.1f MB, pinned read-back buffers: %.1f MB" % (i["device_bytes"] / 1e6, i["pinned_bytes"] / 1e6))
+        if args.device_candidates:
+            print("candidate lists: %d device views, %d fallback views, %d candidates, %.1f MB read back" %
+                  (int(i["device_views"]), int(i["fallback_views"]), int(i["n_candidates"]), i["list_bytes"] / 1e6))
     print("all rounds: baseline %s  feature442 %s  feature2652 %s" % ([round(x, 1) for x in base], [round(x, 1) for x in feat], [round(x, 1) for x in full]))
     assert ratio >= 5.0, "train_mesh is only %.2f x the per-view path" % ratio
 

@@ -55,6 +55,8 @@ def main(argv=None):
     ap.add_argument("--class-id", default="obj")
     ap.add_argument("--scale", type=float, default=1.0, help="factor from the mesh's unit to metres (0.001 for millimetres)")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--device-candidates", action="store_true",
+                    help="find and compact the feature candidates on the device (lmx_bank_train_mesh_opts); the bank and the side-car are the same")
     a = ap.parse_args(argv)
     tri = load_mesh(a.mesh) * a.scale
     n_r = int(round((a.radius_max - a.radius_min) / a.radius_step)) + 1
@@ -68,9 +70,13 @@ def main(argv=None):
     # the iterator scalars a view LIST can state: the radii (what the cluster chain reads); n_points / angle_step / near / far stay 0
     scalars = {"renderer_radius_min": a.radius_min, "renderer_radius_max": a.radius_max, "renderer_radius_step": a.radius_step}
     meta = nb.train_mesh(tri, views, a.width, a.height, a.fx, fy, class_id=a.class_id, device=a.device, save_side_car=a.out_renderer_params,
-                         side_car_scalars=scalars)
+                         side_car_scalars=scalars, device_candidates=a.device_candidates)
     nb.save_yaml(a.out_templates)
     print("train_mesh: %d triangles, %d views, %d templates -> %s, %s" % (len(tri), len(views), len(meta), a.out_templates, a.out_renderer_params))
+    if a.device_candidates:
+        st = nb.last_train_stats
+        print("train_mesh: candidates on the device for %d views (%d through the host path), %d candidates, %.1f MB of lists" %
+              (st["n_device_views"], st["n_fallback_views"], st["n_candidates"], st["list_bytes"] / 1e6))
     return 0
 
 
