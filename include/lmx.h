@@ -274,6 +274,28 @@ typedef struct lmx_pre_desc {
 } lmx_pre_desc;
 lmx_status lmx_ctx_upload_raw(lmx_ctx* ctx, int32_t n_frames, const lmx_image* sources, int32_t n_sources, const lmx_pre_desc* pre);
 
+/* Frames that already live in DEVICE memory (a decoder's, a simulator's, a torch tensor's, lmx_mesh_render's): lmx_image.data is a
+ * device pointer on the context's device, row_stride_bytes any value >= the row's bytes; the address and the stride are multiples of the
+ * element size (1, 2 or 4), nothing else is asked of alignment.  pre == NULL: frame-sized sources with the types lmx_ctx_upload takes,
+ * copied as they are.  With `pre`: exactly lmx_ctx_upload_raw's meaning (crop of a src_width x src_height source, or a frame-sized one
+ * taken as it is; 8UC3, or 8UC1 with `mono`; blur3 on the full frame; 16UC1 mm, or 32FC1 metres with depth_float_m), bit for bit.
+ * No byte crosses PCIe and the host touches none: one ingest kernel per modality (k_ingest, timed as "k_pre") reads the images in
+ * place and writes the next frame set's regular frame buffers, so enqueue, lmx_ctx_upload_masks (after this call), hipGraph contexts,
+ * lanes and every collect form work as after lmx_ctx_upload.
+ * Ordering (`stream` is the HIP stream that produces the frames; NULL = the null stream):
+ *   - the sources are read AFTER everything queued on `stream` before the call: the library records an event there and its own ingest
+ *     stream waits for it;
+ *   - the call does NOT wait on the host for the ingest (the one host wait is the frame set's usual one, for the set's PREVIOUS upload);
+ *   - before returning, `stream` is made to wait for the end of the ingest: work queued on `stream` afterwards may overwrite or free the
+ *     sources (a torch tensor released to the caching allocator on that stream is safe).  Any other stream, or the host, calls
+ *     lmx_ctx_upload_wait first: the end of the ingest is the set's transfer event.
+ * Refused before anything is queued, the context stays usable: a pointer hipPointerGetAttributes does not report as plain device memory
+ * of the context's device -- pageable, pinned, managed, another GPU's -- (LMX_ERR_INVALID_ARG, naming frame and source); an address or
+ * stride that is no multiple of the element size (LMX_ERR_INVALID_ARG); a crop outside the source, wrong sizes or types (LMX_ERR_SHAPE,
+ * as lmx_ctx_upload_raw); a `stream` that is being captured (LMX_ERR_INVALID_ARG); a context that is a member of a device group. */
+lmx_status lmx_ctx_upload_device(lmx_ctx* ctx, int32_t n_frames, const lmx_image* sources, int32_t n_sources,
+                                 const lmx_pre_desc* pre /* NULL: frame-sized sources taken as they are */, void* stream);
+
 /* The drop-in call.  Clears nothing on the caller's side: writes up to `cap` matches in upstream output order
  * (std::sort + std::unique applied) and the total in *n_out (LMX_ERR_OVERFLOW if more than cap).
  * class_ids == NULL / n_class_ids == 0 matches every class (what the reference always passes). */
@@ -691,6 +713,14 @@ double     lmx_depth_value(const lmx_depth_diff_t* diff, double no_value);
  * or its frame count / width / height differ from the enqueue's frame count / the context's frame size; lmx_depth_templates_count differs
  * from the side-car's n_templates; no_value is NaN.  The object's mutex is held for the whole call. */
 lmx_status lmx_depth_templates_upload_scene(lmx_depth_templates* templates, const lmx_image* depth, int32_t n_frames);
+/* upload_scene for depth frames in DEVICE memory on the object's device (16UC1, one size, any even row stride): pitch-aware
+ * device-to-device copies on the object's stream, no staging and no host wait, so the depth- and normal-scored chains run without a host
+ * frame.  Ordering as lmx_ctx_upload_device: the frames are read after everything queued on `stream` (NULL = the null stream) before the
+ * call; before returning, `stream` is made to wait for the copies, so work queued there afterwards may overwrite or free the frames; any
+ * other stream, or the host, first waits for a scored collect (which runs behind the copies).  The same refusals, before anything is
+ * queued: not plain device memory of the object's device, an odd address or stride, a capturing stream (LMX_ERR_INVALID_ARG); wrong
+ * types or sizes (LMX_ERR_SHAPE).  The scene is remembered and forgotten exactly as upload_scene's. */
+lmx_status lmx_depth_templates_upload_scene_device(lmx_depth_templates* templates, const lmx_image* depth, int32_t n_frames, void* stream);
 lmx_status lmx_ctx_collect_clusters_depth(lmx_ctx* ctx, int32_t n_frames, lmx_depth_templates* templates, int32_t class_index, double no_value,
                                           lmx_match_t* matches, size_t cap_matches, size_t* match_offsets,
                                           lmx_depth_diff_t* diffs /* parallel to matches; may be NULL */,

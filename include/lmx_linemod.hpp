@@ -275,6 +275,22 @@ class Detector {
                                        const std::vector<Image>& depth = std::vector<Image>(), bool normals = false, double no_value = -HUGE_VAL,
                                        size_t capacity = 1 << 16);
 
+  // Frames that already live in device memory, on the context's device (lmx_ctx_upload_device; include/lmx.h has the ordering contract):
+  // every Image's data is a device pointer, `stream` the stream that produced the frames (null: the null stream).  Without `pre` the
+  // sources are frame-sized (a context of their size is created if there is none); with it they go through the node-side steps of
+  // lmx_ctx_upload_raw into the current context.  Enqueue and collect through context() as after any upload.
+  void uploadDevice(const std::vector<std::vector<Image> >& frames, const lmx_pre_desc* pre = nullptr, void* stream = nullptr) {
+    if (frames.empty() || frames[0].empty()) throw Exception(LMX_ERR_SHAPE, "uploadDevice: no frames");
+    std::vector<lmx_image> imgs;
+    for (const std::vector<Image>& f : frames) {
+      if (f.size() != frames[0].size()) throw Exception(LMX_ERR_SHAPE, "uploadDevice: every frame needs the same sources");
+      for (const Image& s : f) imgs.push_back(s.c());
+    }
+    if (!pre) ensure_ctx(frames[0][0].cols, frames[0][0].rows, false);
+    else if (!ctx_) throw Exception(LMX_ERR_INVALID_ARG, "uploadDevice: raw frames need a context of the cropped size first");
+    check(lmx_ctx_upload_device(ctx_, (int32_t)frames.size(), imgs.data(), (int32_t)frames[0].size(), pre, stream));
+  }
+
   lmx_bank* bank() const { return bank_; }
   lmx_ctx* context() const { return ctx_; }
   // Which path completed the frames of the context's last lmx_ctx_collect_clusters* call, collectClustersClasses included
@@ -411,6 +427,14 @@ class DepthTemplates {
     std::vector<lmx_image> imgs;
     for (const Image& d : depth) imgs.push_back(d.c());
     check(lmx_depth_templates_upload_scene(h_, imgs.data(), (int32_t)imgs.size()));
+  }
+
+  // The same for depth frames in device memory (lmx_depth_templates_upload_scene_device): no host frame at all; `stream` as in
+  // Detector::uploadDevice.
+  void uploadSceneDevice(const std::vector<Image>& depth, void* stream = nullptr) {
+    std::vector<lmx_image> imgs;
+    for (const Image& d : depth) imgs.push_back(d.c());
+    check(lmx_depth_templates_upload_scene_device(h_, imgs.data(), (int32_t)imgs.size(), stream));
   }
 
   // Moves other's templates behind this object's (lmx_depth_templates_append): other's template i becomes template count() + i, other is

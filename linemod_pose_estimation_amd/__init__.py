@@ -10,3 +10,4 @@ from .detector import Detector, NativeBank, PinnedArena, linemod_detection, merg
 from .detector import DepthTemplates, DEPTH_DIFF_DTYPE, cluster_matches_scored, depth_values  # noqa: F401
 from .detector import NORMAL_DIFF_DTYPE, normal_values, normal_angle_table  # noqa: F401
 from .detector import cluster_matches_classes  # noqa: F401
+from .detector import device_images  # noqa: F401

@@ -17,13 +17,13 @@ SYMBOLS = [
     "lmx_bank_create", "lmx_bank_add_class", "lmx_bank_add_template", "lmx_mesh_render", "lmx_bank_train_mesh", "lmx_bank_load_yaml", "lmx_bank_save_yaml", "lmx_bank_destroy",
     "lmx_bank_pyramid_levels", "lmx_bank_T", "lmx_bank_num_modalities", "lmx_bank_modality", "lmx_bank_num_classes",
     "lmx_bank_class_id", "lmx_bank_num_templates", "lmx_bank_get_template",
-    "lmx_ctx_create", "lmx_ctx_destroy", "lmx_match", "lmx_match_batch", "lmx_ctx_upload", "lmx_ctx_upload_masks", "lmx_match_masked", "lmx_ctx_upload_wait", "lmx_host_alloc", "lmx_host_free", "lmx_ctx_upload_raw", "lmx_ctx_enqueue",
+    "lmx_ctx_create", "lmx_ctx_destroy", "lmx_match", "lmx_match_batch", "lmx_ctx_upload", "lmx_ctx_upload_masks", "lmx_match_masked", "lmx_ctx_upload_wait", "lmx_host_alloc", "lmx_host_free", "lmx_ctx_upload_raw", "lmx_ctx_upload_device", "lmx_ctx_enqueue",
     "lmx_ctx_collect", "lmx_ctx_collect_flat", "lmx_ctx_raw_matches", "lmx_merge_raw", "lmx_ctx_export_raw", "lmx_ctx_export_raw_on", "lmx_ctx_release", "lmx_ctx_max_outstanding", "lmx_stream_copy", "lmx_stream_copy_blocks", "lmx_merge_gathered", "lmx_ctx_sync", "lmx_renderer_params_load", "lmx_renderer_params_save", "lmx_renderer_params_free", "lmx_cluster_matches", "lmx_ctx_set_cluster_sidecar", "lmx_ctx_collect_clusters", "lmx_ctx_debug_read", "lmx_debug_orientation_labels", "lmx_debug_depth_normal_bins", "lmx_debug_introsort_perm", "lmx_debug_introsort_perm_score", "lmx_debug_device_sort_perm", "lmx_debug_device_finalize_cluster", "lmx_debug_bank_tables", "lmx_ctx_stats",
     "lmx_num_kernels", "lmx_kernel_name", "lmx_ctx_device_kernel_name", "lmx_ctx_set_profiling", "lmx_ctx_kernel_time", "lmx_ctx_reset_profiling",
     "lmx_ctx_algorithmic_bytes", "lmx_last_error", "lmx_version",
     "lmx_cluster_matches_scored", "lmx_depth_templates_from_mesh", "lmx_depth_templates_from_crops", "lmx_depth_templates_count", "lmx_depth_templates_rect",
     "lmx_depth_templates_get", "lmx_depth_templates_device_bytes", "lmx_depth_templates_free", "lmx_depth_diff_matches",
-    "lmx_depth_value", "lmx_depth_templates_upload_scene", "lmx_ctx_collect_clusters_depth", "lmx_debug_device_finalize_cluster_depth",
+    "lmx_depth_value", "lmx_depth_templates_upload_scene", "lmx_depth_templates_upload_scene_device", "lmx_ctx_collect_clusters_depth", "lmx_debug_device_finalize_cluster_depth",
     "lmx_normal_angle_table", "lmx_depth_templates_enable_normals", "lmx_depth_templates_get_normals", "lmx_normal_diff_matches", "lmx_match_value",
     "lmx_ctx_collect_clusters_depth_normal", "lmx_debug_scene_normals", "lmx_depth_templates_set_profiling", "lmx_depth_templates_kernel_time",
     "lmx_cluster_matches_classes", "lmx_ctx_set_cluster_sidecar_class", "lmx_ctx_collect_clusters_classes", "lmx_depth_templates_append",
@@ -263,6 +263,7 @@ def lib():
     L.lmx_host_free.argtypes = [vp]
     L.lmx_host_free.restype = None
     L.lmx_ctx_upload_raw.argtypes = [vp, C.c_int32, C.POINTER(Image), C.c_int32, C.POINTER(PreDesc)]
+    L.lmx_ctx_upload_device.argtypes = [vp, C.c_int32, C.POINTER(Image), C.c_int32, C.POINTER(PreDesc), vp]
     L.lmx_ctx_enqueue.argtypes = [vp, C.c_int32, C.c_float, C.POINTER(C.c_char_p), C.c_int32]
     f32p = C.POINTER(C.c_float)
     L.lmx_ctx_enqueue_thresholds.argtypes = [vp, C.c_int32, f32p, C.c_int32, C.POINTER(C.c_char_p), C.c_int32]
@@ -306,6 +307,7 @@ def lib():
     L.lmx_depth_value.argtypes = [C.POINTER(DepthDiff), C.c_double]
     L.lmx_depth_value.restype = C.c_double
     L.lmx_depth_templates_upload_scene.argtypes = [vp, C.POINTER(Image), C.c_int32]
+    L.lmx_depth_templates_upload_scene_device.argtypes = [vp, C.POINTER(Image), C.c_int32, vp]
     L.lmx_ctx_collect_clusters_depth.argtypes = [vp, C.c_int32, vp, C.c_int32, C.c_double, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, vp, C.c_size_t,
                                                  C.POINTER(C.c_size_t), vp, C.c_size_t]
     L.lmx_debug_device_finalize_cluster_depth.argtypes = [C.c_int32, vp, C.c_size_t, C.c_int32, vp, C.POINTER(Image), C.c_int32, C.c_double, vp, vp, C.c_size_t,

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "lmx_ctx.hpp"
+#include "lmx_ingest.hpp"
 
 using namespace lmx;
 
@@ -359,6 +360,7 @@ void lmx_ctx_destroy(lmx_ctx* c) {
   if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
   if (c->pre_stream) { (void)hipStreamSynchronize(c->pre_stream); (void)hipStreamDestroy(c->pre_stream); }
   if (c->raw_dma_done) (void)hipEventDestroy(c->raw_dma_done);
+  if (c->device_src_ready) (void)hipEventDestroy(c->device_src_ready);
   for (lmx_ctx::FrameSet& fs : c->sets) {
     if (fs.h_stage) (void)hipHostFree(fs.h_stage);
     if (fs.h_raw) (void)hipHostFree(fs.h_raw);
@@ -710,20 +712,10 @@ lmx_status ctx_drop_newest(lmx_ctx* c) {
 
 }  // namespace lmx
 
-extern "C" {
-
-lmx_status lmx_host_alloc(size_t bytes, void** out) {
-  if (!out || bytes == 0) { set_error("lmx_host_alloc: invalid argument"); return LMX_ERR_INVALID_ARG; }
-  LMX_HIP(hipHostMalloc(out, bytes, hipHostMallocDefault));
-  return LMX_OK;
-}
-void lmx_host_free(void* p) {
-  if (p) (void)hipHostFree(p);
-}
-
-lmx_status lmx_ctx_upload_raw(lmx_ctx* c, int32_t n_frames, const lmx_image* sources, int32_t n_sources, const lmx_pre_desc* pre) {
-  return lmx::guarded("lmx_ctx_upload_raw", [&]() -> lmx_status {
-  if (!c || !sources || !pre) { set_error("lmx_ctx_upload_raw: null argument"); return LMX_ERR_INVALID_ARG; }
+// What lmx_ctx_upload_raw and lmx_ctx_upload_device take with a lmx_pre_desc.  -> per modality: the element layout of the raw source and
+// whether it is full-size (cropped on the device at cx, cy) or already frame-size (cx = cy = 0)
+struct RawSource { int sh, sw, ch, es, cx, cy; size_t bytes; };
+static lmx_status check_raw_sources(lmx_ctx* c, int32_t n_frames, const lmx_image* sources, int32_t n_sources, const lmx_pre_desc* pre, std::vector<RawSource>& raw) {
   if (n_sources != c->M) {
     set_error("sources.size()=%d != modalities.size()=%d (upstream CV_Assert in Detector::match)", n_sources, c->M);
     return LMX_ERR_SHAPE;
@@ -735,11 +727,7 @@ lmx_status lmx_ctx_upload_raw(lmx_ctx* c, int32_t n_frames, const lmx_image* sou
     set_error("crop %dx%d at (%d,%d) does not fit the %dx%d source", W, H, pre->crop_x, pre->crop_y, pre->src_width, pre->src_height);
     return LMX_ERR_SHAPE;
   }
-  LMX_HIP(hipSetDevice(c->device));
-  // per modality: element layout of the raw source and whether it is full-size (cropped on device) or already frame-size
-  struct Raw { int sh, sw, ch, es, cx, cy; size_t bytes; };
-  std::vector<Raw> raw(c->M);
-  size_t total = 0;
+  raw.assign(c->M, RawSource());
   for (int m = 0; m < c->M; ++m) {
     const bool cg = c->bank->mods[m].type == LMX_MOD_COLOR_GRADIENT;
     const int ch = cg ? (pre->mono ? 1 : 3) : 1, es = cg ? 1 : (pre->depth_float_m ? 4 : 2);
@@ -754,15 +742,38 @@ lmx_status lmx_ctx_upload_raw(lmx_ctx* c, int32_t n_frames, const lmx_image* sou
       if (!im.data || !(full || fit)) { set_error("frame %d source %d: size %dx%d is neither the raw %dx%d nor the context %dx%d", f, m, im.cols, im.rows, pre->src_width, pre->src_height, W, H); return LMX_ERR_SHAPE; }
       if (im.channels != ch || im.elem_size != es) { set_error("frame %d source %d: expected %d channel(s) of %d byte(s)", f, m, ch, es); return LMX_ERR_SHAPE; }
       if (im.row_stride_bytes < (size_t)im.cols * ch * es) { set_error("frame %d source %d: row stride too small", f, m); return LMX_ERR_INVALID_ARG; }
-      if (f == 0) raw[m] = Raw{im.rows, im.cols, ch, es, full ? pre->crop_x : 0, full ? pre->crop_y : 0, (size_t)im.rows * im.cols * ch * es};
+      if (f == 0) raw[m] = RawSource{im.rows, im.cols, ch, es, full ? pre->crop_x : 0, full ? pre->crop_y : 0, (size_t)im.rows * im.cols * ch * es};
       else if (im.rows != raw[m].sh || im.cols != raw[m].sw) { set_error("frame %d source %d: size differs from frame 0", f, m); return LMX_ERR_SHAPE; }
     }
-    total += raw[m].bytes * n_frames;
   }
+  return LMX_OK;
+}
+
+extern "C" {
+
+lmx_status lmx_host_alloc(size_t bytes, void** out) {
+  if (!out || bytes == 0) { set_error("lmx_host_alloc: invalid argument"); return LMX_ERR_INVALID_ARG; }
+  LMX_HIP(hipHostMalloc(out, bytes, hipHostMallocDefault));
+  return LMX_OK;
+}
+void lmx_host_free(void* p) {
+  if (p) (void)hipHostFree(p);
+}
+
+lmx_status lmx_ctx_upload_raw(lmx_ctx* c, int32_t n_frames, const lmx_image* sources, int32_t n_sources, const lmx_pre_desc* pre) {
+  return lmx::guarded("lmx_ctx_upload_raw", [&]() -> lmx_status {
+  if (!c || !sources || !pre) { set_error("lmx_ctx_upload_raw: null argument"); return LMX_ERR_INVALID_ARG; }
+  const int W = c->desc.width, H = c->desc.height;
+  std::vector<RawSource> raw;
+  lmx_status st = check_raw_sources(c, n_frames, sources, n_sources, pre, raw);
+  if (st != LMX_OK) return st;
+  LMX_HIP(hipSetDevice(c->device));
+  size_t total = 0;
+  for (int m = 0; m < c->M; ++m) total += raw[m].bytes * n_frames;
   // next frame set: its previous transfer AND the pre-processing kernels behind it have finished (h2d_done is recorded behind them), so
   // the set's raw staging may be overwritten; the lanes that still read the set's frames are waited for on the copy stream
   const int set = (c->cur_set + 1) % c->n_sets;
-  lmx_status st = begin_set_upload(c, set);
+  st = begin_set_upload(c, set);
   if (st != LMX_OK) return st;
   lmx_ctx::FrameSet& fs = c->sets[set];
   fs.stored = false;   // the pre-processing kernels write the regular frame buffers
@@ -778,7 +789,7 @@ lmx_status lmx_ctx_upload_raw(lmx_ctx* c, int32_t n_frames, const lmx_image* sou
   std::vector<RowCopy> tasks;
   size_t off = 0;
   for (int m = 0; m < c->M; ++m) {
-    const Raw& r = raw[m];
+    const RawSource& r = raw[m];
     add_copy_tasks(tasks, sources, c->M, m, n_frames, fs.h_raw + off, r.bytes, (size_t)r.sw * r.ch * r.es, r.sh, 1);
     off += r.bytes * n_frames;
   }
@@ -798,7 +809,7 @@ lmx_status lmx_ctx_upload_raw(lmx_ctx* c, int32_t n_frames, const lmx_image* sou
   LMX_HIP(hipStreamWaitEvent(c->pre_stream, c->raw_dma_done, 0));
   off = 0;
   for (int m = 0; m < c->M; ++m) {
-    const Raw& r = raw[m];
+    const RawSource& r = raw[m];
     c->cur_stream = c->pre_stream;
     ScopedKernel k(c, K_PRE);
     if (c->bank->mods[m].type == LMX_MOD_COLOR_GRADIENT)
@@ -810,6 +821,94 @@ lmx_status lmx_ctx_upload_raw(lmx_ctx* c, int32_t n_frames, const lmx_image* sou
   LMX_HIP(hipGetLastError());
   fs.n_uploaded = n_frames;
   return end_set_upload(c, set, c->pre_stream);
+  });
+}
+
+// Frames that already live in device memory (include/lmx.h).  Every refusal comes before anything is queued or any set is opened.
+lmx_status lmx_ctx_upload_device(lmx_ctx* c, int32_t n_frames, const lmx_image* sources, int32_t n_sources, const lmx_pre_desc* pre, void* stream) {
+  return lmx::guarded("lmx_ctx_upload_device", [&]() -> lmx_status {
+  if (!c || !sources) { set_error("lmx_ctx_upload_device: null argument"); return LMX_ERR_INVALID_ARG; }
+  if (!c->sets[0].h_stage) { set_error("lmx_ctx_upload: this context is a member of a device group and is fed through lmx_group_upload"); return LMX_ERR_INVALID_ARG; }
+  const int W = c->desc.width, H = c->desc.height;
+  hipStream_t user = static_cast<hipStream_t>(stream);
+  struct Launch { int mode; ingest::Args a; };
+  std::vector<Launch> launch(c->M > 0 ? c->M : 0);
+  if (!pre) {
+    lmx_status st = lmx::ctx_check_sources(c, n_frames, sources, n_sources, 0);
+    if (st != LMX_OK) return st;
+    for (int m = 0; m < c->M; ++m) {
+      const bool cg = c->bank->mods[m].type == LMX_MOD_COLOR_GRADIENT;
+      launch[m].mode = ingest::plan(&launch[m].a, cg, c->color_ch, c->color_ch, false, false, H, W, H, W, 0, 0);
+    }
+  } else {
+    std::vector<RawSource> raw;
+    lmx_status st = check_raw_sources(c, n_frames, sources, n_sources, pre, raw);
+    if (st != LMX_OK) return st;
+    for (int m = 0; m < c->M; ++m) {
+      const RawSource& r = raw[m];
+      launch[m].mode = ingest::plan(&launch[m].a, c->bank->mods[m].type == LMX_MOD_COLOR_GRADIENT, r.ch, c->color_ch, pre->blur3 != 0, pre->depth_float_m != 0, r.sh, r.sw,
+                                    H, W, r.cx, r.cy);
+    }
+  }
+  LMX_HIP(hipSetDevice(c->device));
+  for (int f = 0; f < n_frames; ++f)
+    for (int m = 0; m < c->M; ++m) {
+      const lmx_image& im = sources[(size_t)f * c->M + m];
+      const size_t es = (size_t)im.elem_size;
+      if (((uintptr_t)im.data | im.row_stride_bytes) & (es - 1)) {
+        set_error("frame %d source %d: the address and the row stride must be multiples of the element size (%zu)", f, m, es);
+        return LMX_ERR_INVALID_ARG;
+      }
+      hipPointerAttribute_t attr;
+      if (hipPointerGetAttributes(&attr, im.data) != hipSuccess) {   // memory the runtime has never seen (malloc, a numpy array)
+        (void)hipGetLastError();
+        set_error("frame %d source %d: not device memory (lmx_ctx_upload takes host images)", f, m);
+        return LMX_ERR_INVALID_ARG;
+      }
+      if (attr.type != hipMemoryTypeDevice || attr.device != c->device) {
+        set_error("frame %d source %d: %s; lmx_ctx_upload_device reads plain device memory of device %d", f, m,
+                  attr.type == hipMemoryTypeDevice ? "memory of another device" : "pinned, managed or other host-visible memory", c->device);
+        return LMX_ERR_INVALID_ARG;
+      }
+    }
+  hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+  if (user && hipStreamIsCapturing(user, &capturing) != hipSuccess) { (void)hipGetLastError(); set_error("lmx_ctx_upload_device: invalid stream"); return LMX_ERR_INVALID_ARG; }
+  if (capturing != hipStreamCaptureStatusNone) { set_error("lmx_ctx_upload_device: the stream is being captured into a graph"); return LMX_ERR_INVALID_ARG; }
+  // next frame set: the only host wait is for the set's previous upload (whose kernel read this table); the lanes that still read the set's
+  // frames are waited for on the copy stream, and the ingest stream behind it
+  const int set = (c->cur_set + 1) % c->n_sets;
+  lmx_status st = begin_set_upload(c, set);
+  if (st != LMX_OK) return st;
+  lmx_ctx::FrameSet& fs = c->sets[set];
+  fs.stored = false;
+  for (int m = 0; m < c->M; ++m)
+    for (int f = 0; f < n_frames; ++f) {
+      const lmx_image& im = sources[(size_t)f * c->M + m];
+      fs.h_tab[(size_t)m * c->F + f] = PullEntry{(uint64_t)(uintptr_t)im.data, (uint64_t)im.row_stride_bytes};
+    }
+  if (!c->pre_stream) {
+    LMX_HIP(hipStreamCreateWithFlags(&c->pre_stream, hipStreamNonBlocking));
+    LMX_HIP(hipEventCreateWithFlags(&c->raw_dma_done, hipEventDisableTiming));
+  }
+  if (!c->device_src_ready) LMX_HIP(hipEventCreateWithFlags(&c->device_src_ready, hipEventDisableTiming));
+  LMX_HIP(hipEventRecord(c->raw_dma_done, c->copy_stream));
+  LMX_HIP(hipStreamWaitEvent(c->pre_stream, c->raw_dma_done, 0));
+  // the sources are read behind everything the caller queued on `stream` so far
+  LMX_HIP(hipEventRecord(c->device_src_ready, user));
+  LMX_HIP(hipStreamWaitEvent(c->pre_stream, c->device_src_ready, 0));
+  for (int m = 0; m < c->M; ++m) {
+    launch[m].a.dst = set_frames(c, fs, m);
+    c->cur_stream = c->pre_stream;
+    ScopedKernel k(c, K_PRE);
+    launch_ingest(c->pre_stream, launch[m].mode, launch[m].a, fs.d_tab + (size_t)m * c->F, n_frames);
+  }
+  LMX_HIP(hipGetLastError());
+  fs.n_uploaded = n_frames;
+  st = end_set_upload(c, set, c->pre_stream);
+  if (st != LMX_OK) return st;
+  // what the caller queues on `stream` from here on may overwrite or free the sources
+  LMX_HIP(hipStreamWaitEvent(user, fs.h2d_done, 0));
+  return LMX_OK;
   });
 }
 

@@ -148,6 +148,8 @@ struct lmx_ctx {
   // the next batch while they work (created on first use)
   hipStream_t pre_stream = nullptr;
   hipEvent_t raw_dma_done = nullptr;
+  // lmx_ctx_upload_device: the ingest kernels run on pre_stream as well, behind this event recorded on the caller's stream (created on first use)
+  hipEvent_t device_src_ready = nullptr;
   std::unique_ptr<lmx::CopyPool> pool;
   FrameBuffers lane_fb[kLanes];
   uint8_t* lane_bgr[kLanes][kMaxModalities][kMaxLevels] = {};

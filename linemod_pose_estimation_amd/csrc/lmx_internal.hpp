@@ -259,7 +259,7 @@ struct KernelParams {
 
 // kernel ids for profiling
 enum KernelId {
-  K_PRE = 0,  // node-side pre-processing (k_pre_color / k_pre_depth), only with lmx_ctx_upload_raw
+  K_PRE = 0,  // node-side pre-processing: k_pre_color / k_pre_depth with lmx_ctx_upload_raw, k_ingest with lmx_ctx_upload_device
   K_COLOR_QUANTIZE,
   K_DEPTH_QUANTIZE,
   K_NN_DOWN,
@@ -410,6 +410,9 @@ void launch_debug_block_sort(hipStream_t s, const float* sim, const int* tid, in
 struct PullEntry { uint64_t src; uint64_t row_stride; };  // one caller-owned pinned image (device-visible address)
 void launch_pull_frames(hipStream_t s, const PullEntry* tab /* device-visible */, uint8_t* dst, size_t frame_bytes, int rows, uint32_t row_bytes,
                         int n_frames);
+// lmx_ctx_upload_device (lmx_ingest.hip): one modality's frames from the caller's device images `tab` into a frame set; mode = ingest::Mode
+namespace ingest { struct Args; }
+void launch_ingest(hipStream_t s, int mode, const ingest::Args& a, const PullEntry* tab /* device-visible */, int n_frames);
 void launch_publish_records(hipStream_t s, void* dst, const void* src, uint32_t max_records, uint32_t cand_cap);
 void launch_copy_bytes(hipStream_t s, void* dst, const void* src, size_t bytes);
 void launch_publish_blocks(hipStream_t s, void* dst, const void* src, int n_blocks, size_t block_bytes, uint32_t max_records);

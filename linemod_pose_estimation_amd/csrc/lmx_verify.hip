@@ -291,6 +291,7 @@ struct lmx_depth_templates {
   // the scene lmx_depth_templates_upload_scene left on the device (scene_frames 0: none); scene_ready is recorded behind its copies
   int32_t scene_frames = 0, scene_W = 0, scene_H = 0;
   hipEvent_t scene_ready = nullptr;
+  hipEvent_t scene_src_ready = nullptr;  // lmx_depth_templates_upload_scene_device: recorded on the caller's stream in front of the copies
   bool scene_pending = false;            // scene_ready has been recorded and h_scene may still be read by a copy
   lmx::DepthJob *d_jobs = nullptr, *h_jobs = nullptr;
   lmx_depth_diff_t *d_out = nullptr, *h_out = nullptr;
@@ -451,6 +452,7 @@ struct lmx_depth_templates {
     (void)hipFree(d_angle); (void)hipFree(d_scene_normals); (void)hipFree(d_nout); (void)hipHostFree(h_nout);
     if (normals_ready) (void)hipEventDestroy(normals_ready);
     if (scene_ready) (void)hipEventDestroy(scene_ready);
+    if (scene_src_ready) (void)hipEventDestroy(scene_src_ready);
     if (s) (void)hipStreamDestroy(s);
   }
 };
@@ -776,6 +778,62 @@ extern "C" lmx_status lmx_depth_templates_upload_scene(lmx_depth_templates* t, c
     if (!t || !depth) { lmx::set_error("lmx_depth_templates_upload_scene: null argument"); return LMX_ERR_INVALID_ARG; }
     std::lock_guard<std::mutex> lk(t->m);
     return lmx::depth_upload_scene(t, depth, n_frames);
+  });
+}
+
+// The scene from device memory: pitch-aware device-to-device copies on the object's stream, between an event recorded on the caller's
+// stream (the copies read the frames behind everything queued there so far) and a wait of that stream for scene_ready (what is queued
+// there afterwards may overwrite or free the frames).  No staging buffer and no host wait; every refusal comes before anything is queued.
+extern "C" lmx_status lmx_depth_templates_upload_scene_device(lmx_depth_templates* t, const lmx_image* depth, int32_t n_frames, void* stream) {
+  return lmx::guarded("lmx_depth_templates_upload_scene_device", [&]() -> lmx_status {
+    using namespace lmx;
+    const char* what = "lmx_depth_templates_upload_scene_device";
+    if (!t || !depth) { set_error("%s: null argument", what); return LMX_ERR_INVALID_ARG; }
+    std::lock_guard<std::mutex> lk(t->m);
+    if (n_frames < 1) { set_error("%s: n_frames = %d", what, n_frames); return LMX_ERR_INVALID_ARG; }
+    if (lmx_status st = check_depth_frames(what, depth, n_frames)) return st;
+    if (lmx_status st = t->ensure_device()) return st;
+    hipStream_t user = static_cast<hipStream_t>(stream);
+    for (int32_t f = 0; f < n_frames; ++f) {
+      const lmx_image& im = depth[f];
+      if (((uintptr_t)im.data | im.row_stride_bytes) & 1u) { set_error("%s: depth image %d: the address and the row stride must be even", what, f); return LMX_ERR_INVALID_ARG; }
+      hipPointerAttribute_t attr;
+      if (hipPointerGetAttributes(&attr, im.data) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("%s: depth image %d is not device memory (lmx_depth_templates_upload_scene takes host images)", what, f);
+        return LMX_ERR_INVALID_ARG;
+      }
+      if (attr.type != hipMemoryTypeDevice || attr.device != t->device) {
+        set_error("%s: depth image %d is not plain device memory of device %d", what, f, t->device);
+        return LMX_ERR_INVALID_ARG;
+      }
+    }
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    if (user && hipStreamIsCapturing(user, &capturing) != hipSuccess) { (void)hipGetLastError(); set_error("%s: invalid stream", what); return LMX_ERR_INVALID_ARG; }
+    if (capturing != hipStreamCaptureStatusNone) { set_error("%s: the stream is being captured into a graph", what); return LMX_ERR_INVALID_ARG; }
+    const int32_t W = depth[0].cols, H = depth[0].rows;
+    const size_t frame_bytes = (size_t)W * H * sizeof(uint16_t);
+    t->scene_frames = 0;
+    t->scene_normals_valid = false;
+    if (lmx_status st = t->grow_scene(frame_bytes * (size_t)n_frames)) return st;
+    if (!t->scene_src_ready) DV_HIP(hipEventCreateWithFlags(&t->scene_src_ready, hipEventDisableTiming));
+    DV_HIP(hipEventRecord(t->scene_src_ready, user));
+    DV_HIP(hipStreamWaitEvent(t->s, t->scene_src_ready, 0));
+    for (int32_t f = 0; f < n_frames; ++f)
+      if (hipError_t e = hipMemcpy2DAsync(reinterpret_cast<uint8_t*>(t->d_scene) + frame_bytes * f, (size_t)W * 2, depth[f].data, depth[f].row_stride_bytes, (size_t)W * 2,
+                                          (size_t)H, hipMemcpyDeviceToDevice, t->s)) {
+        t->drain_after_error();
+        set_error("hipMemcpy2DAsync failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
+        return LMX_ERR_HIP;
+      }
+    if (hipError_t e = hipEventRecord(t->scene_ready, t->s)) {
+      t->drain_after_error();
+      set_error("hipEventRecord failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
+      return LMX_ERR_HIP;
+    }
+    t->scene_frames = n_frames; t->scene_W = W; t->scene_H = H;
+    DV_HIP(hipStreamWaitEvent(user, t->scene_ready, 0));
+    return LMX_OK;
   });
 }
 

@@ -44,6 +44,75 @@ def _images(frames):
     return arr, flat
 
 
+_DEVICE_DTYPES = {"uint8": 1, "uint16": 2, "int16": 2, "float32": 4}      # int16 is taken as its bit pattern (torch before 2.3 has no uint16)
+_CAI_TYPES = {"|u1": 1, "<u2": 2, "<i2": 2, "<f4": 4}
+
+
+def _device_view(s):
+    """One source in device memory -> (address, shape, strides in bytes, element size, device index or None, is a torch tensor).
+    torch tensors are recognised by their attributes (torch is not imported here); anything else needs __cuda_array_interface__."""
+    if hasattr(s, "data_ptr") and hasattr(s, "is_cuda"):
+        if not s.is_cuda:
+            raise ValueError("upload_device takes tensors in device memory: a CPU tensor goes through upload()")
+        es = _DEVICE_DTYPES.get(str(s.dtype).replace("torch.", ""))
+        if es is None:
+            raise ValueError("device sources are uint8, uint16 / int16 or float32, not %s" % (s.dtype,))
+        return int(s.data_ptr()), tuple(int(v) for v in s.shape), tuple(int(v) * es for v in s.stride()), es, s.device.index, True
+    try:
+        cai = s.__cuda_array_interface__
+    except AttributeError:
+        raise ValueError("a device source is a torch tensor on the GPU or an object with __cuda_array_interface__, not %s" % type(s).__name__)
+    es = _CAI_TYPES.get(cai["typestr"])
+    if es is None:
+        raise ValueError("device sources are uint8, uint16 / int16 or float32, not %r" % (cai["typestr"],))
+    shape = tuple(int(v) for v in cai["shape"])
+    strides = cai.get("strides")
+    if strides is None:     # C-contiguous
+        strides, run = [], es
+        for n in reversed(shape):
+            strides.insert(0, run)
+            run *= n
+    return int(cai["data"][0]), shape, tuple(int(v) for v in strides), es, None, False
+
+
+def device_images(frames, device=None):
+    """frames: list (per frame) of list (per modality) of sources in device memory -- torch tensors on one GPU (on `device` when given)
+    or objects with __cuda_array_interface__: uint8 HxWx3 / HxW, uint16 or int16 HxW, float32 HxW.  Views and slices are described in
+    place: the row stride is the source's own, the elements of a row must be contiguous.  -> (ctypes lmx_image array, keep-alive).
+    ValueError: a CPU tensor, a non-unit inner stride, a wrong dtype or rank, tensors on different devices."""
+    flat = [s for fr in frames for s in fr]
+    arr = (_lib.Image * max(1, len(flat)))()
+    seen = device
+    for i, s in enumerate(flat):
+        ptr, shape, strides, es, dev, _ = _device_view(s)
+        if len(shape) == 3 and es == 1 and shape[2] == 3:
+            ch, ok = 3, strides[2] == 1 and strides[1] == 3
+        elif len(shape) == 2:
+            ch, ok = 1, strides[1] == es
+        else:
+            raise ValueError("device sources are uint8 HxWx3 / HxW (colour) or uint16 / int16 / float32 HxW (depth), not shape %s of %d-byte elements" % (shape, es))
+        if not ok:
+            raise ValueError("the elements of a row must be contiguous (the row stride may be larger): strides %s bytes" % (strides,))
+        if strides[0] < shape[1] * ch * es:
+            raise ValueError("row stride %d bytes is below the row's %d bytes" % (strides[0], shape[1] * ch * es))
+        if dev is not None:
+            if seen is not None and dev != seen:
+                raise ValueError("device sources on different devices (%s and %s)" % (seen, dev))
+            seen = dev
+        arr[i] = _lib.Image(ptr, shape[0], shape[1], ch, es, strides[0])
+    return arr, flat
+
+
+def _device_stream(flat, stream):
+    """stream=None: the current torch stream of the tensors' device, or the null stream for other sources."""
+    if stream is not None:
+        return int(getattr(stream, "cuda_stream", stream))
+    if flat and hasattr(flat[0], "is_cuda"):
+        import torch
+        return int(torch.cuda.current_stream(flat[0].device).cuda_stream)
+    return 0
+
+
 class PreparedBatch:
     """lmx_image descriptors of a batch of host frames, built once (the arrays are kept alive by this object)."""
 
@@ -58,6 +127,15 @@ class PreparedBatch:
         out.keep = (self.imgs, self.keep)
         out.n_frames, out.n_sources = count, self.n_sources
         return out
+
+
+class PreparedDeviceBatch(PreparedBatch):
+    """The same for frames in device memory (device_images): what Detector.upload_device takes in place of the tensors when one batch is
+    uploaded again and again (a decoder's ring of output surfaces, the rate script)."""
+
+    def __init__(self, frames):
+        self.imgs, self.keep = device_images(frames)
+        self.n_frames, self.n_sources = len(frames), len(frames[0])
 
 
 MESH_LIGHT = (0.35, -0.45, -0.82)   # the light direction of the mesh renderer's default camera
@@ -457,6 +535,26 @@ class Detector:
         imgs, keep = _images(frames)
         _lib.check(_lib.lib().lmx_ctx_upload_raw(self.h, len(frames), imgs, len(frames[0]), C.byref(pre)))
         del keep
+
+    def upload_device(self, frames, src_size=None, crop_xy=(0, 0), blur3=False, mono=False, depth_float_m=False, stream=None):
+        """Frames that already live in this context's GPU memory (lmx_ctx_upload_device): list (per frame) of list (per modality) of torch
+        tensors or objects with __cuda_array_interface__ (device_images); nothing passes through the host.  src_size=None: frame-sized
+        sources copied as they are; with src_size=(width, height) the node-side steps of upload_raw (crop, blur3, mono, depth_float_m)
+        run on the way.  The sources are read behind what `stream` (default: the tensors' current torch stream, else the null stream)
+        holds at the call, and that stream then waits for the ingest: the tensors may be overwritten or freed on it right away.
+        `frames` may be a batch prepared once with prepare_device_batch."""
+        if isinstance(frames, PreparedDeviceBatch):     # descriptors built once (Detector.prepare_device_batch)
+            imgs, keep, n_frames, n_sources = frames.imgs, frames.keep, frames.n_frames, frames.n_sources
+        else:
+            imgs, keep = device_images(frames)
+            n_frames, n_sources = len(frames), len(frames[0])
+        pre = None if src_size is None else C.byref(_lib.PreDesc(src_size[0], src_size[1], crop_xy[0], crop_xy[1], int(blur3), int(mono), int(depth_float_m)))
+        _lib.check(_lib.lib().lmx_ctx_upload_device(self.h, n_frames, imgs, n_sources, pre, _device_stream(keep, stream)))
+        del keep
+
+    @staticmethod
+    def prepare_device_batch(frames):
+        return PreparedDeviceBatch(frames)
 
     def enqueue(self, n_frames, threshold, class_ids=()):
         if isinstance(threshold, Mapping):
@@ -986,6 +1084,16 @@ class DepthTemplates:
         frames, imgs = _depth_images(depth_frames)
         _lib.check(_lib.lib().lmx_depth_templates_upload_scene(self.h, imgs, len(frames)))
         self._scene_shape = tuple(frames[0].shape)
+
+    def upload_scene_device(self, depth_frames, stream=None):
+        """upload_scene for depth frames in this object's GPU memory (lmx_depth_templates_upload_scene_device): a uint16 / int16 [H, W]
+        tensor (or object with __cuda_array_interface__) or a list of them.  `stream` as in Detector.upload_device."""
+        frames = list(depth_frames) if isinstance(depth_frames, (list, tuple)) else [depth_frames]
+        imgs, keep = device_images([[d] for d in frames])
+        if any(im.elem_size != 2 or im.channels != 1 for im in imgs):
+            raise ValueError("depth frames must be uint16 / int16 HxW")
+        _lib.check(_lib.lib().lmx_depth_templates_upload_scene_device(self.h, imgs, len(frames), _device_stream(keep, stream)))
+        self._scene_shape = (int(imgs[0].rows), int(imgs[0].cols))
 
     def append(self, other):
         """Move `other`'s templates behind this object's (lmx_depth_templates_append): other's template i becomes template len(self) + i,
