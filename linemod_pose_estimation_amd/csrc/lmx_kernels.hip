@@ -1247,6 +1247,8 @@ typedef const uint32_t __attribute__((address_space(4))) lmx_cu32_const;   // co
 typedef const uint64_t __attribute__((address_space(4))) lmx_cu64_const;   // a ClassThreshold entry as one 8-byte scalar load
 
 constexpr int SB_FPW = 2;    // frames of its XCD slot that one wave scores (1, 2, 4 and 8 measured: profiles/r10_score_frames_ab.txt)
+constexpr int SB_TAIL_LANES = 31;                 // live dwords of a one-chunk tail that two frames of a wave score in one pass, a half-wave each
+constexpr uint32_t SB_TAIL_MAX_STRIDE = 1u << 26; // frame stride up to which the second half's lane offset (8 strides + its dword) stays far inside a descriptor
 constexpr int SB_SEG0 = 3;   // groups in the first of the two segments of a block behind the first one; the second takes the other SB_GROUPS - SB_SEG0
 
 // Groups [G0, G0 + NG) of one block: the loads of every live chunk are issued before the first add (one wave-uniform branch per
@@ -1277,9 +1279,16 @@ __device__ __forceinline__ void score_segment_sb(__amdgpu_buffer_rsrc_t rsrc, co
     }
 }
 
+// A one-chunk pass (NCH = 1) is the plain tail of `frame` (lane l owns dword l of the pass) or, with pair_off != 0, the merged tail of two
+// frames (see k_score_coarse_sb): lanes 0..31 hold the tail of `frame`, lanes 32..63 the same dwords of frame + 8, both through the ONE
+// descriptor based at `frame`; the second half carries pair_off = 8 * mod_stride in its lane offset.  At most 31 dwords are live there, so
+// lanes 31 and 63 own nothing and only supply their left neighbour's next dword -- of their own frame, since both load dword 31.  Live
+// flags are per lane and `need` is the template's: the chunk stays on while either half has a live lane, and the other half rides along
+// dead, which drops no live lane ever.  The lanes' dword and offset are worked out here and again at the append, from a lane index the
+// compiler cannot see through: kept across the frame loop they cost the two-chunk passes two VGPRs.
 template <int NCH, bool PRUNE>
 __device__ __forceinline__ void score_pass_sb(const ScoreParams& p, const uint8_t* lm_frame, lmx_cu32_const* row, int n_blocks, int g, int frame, int lane,
-                                              int pbase, int positions, int raw_threshold, int nf_total) {
+                                              int pbase, int positions, int raw_threshold, int nf_total, uint32_t pair_off = 0) {
   const unsigned long long wave_base = (unsigned long long)(lm_frame + (pbase >> 1));
   const uint32_t base_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)wave_base);
   const uint32_t base_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(wave_base >> 32));
@@ -1299,8 +1308,16 @@ __device__ __forceinline__ void score_pass_sb(const ScoreParams& p, const uint8_
 #pragma unroll
   for (int k = 0; k < NCH; ++k) {
     acc_lo[k] = acc_hi[k] = 0;
-    alive[k] = lane < SC_CHUNK_LANES && pbase + (k * SC_CHUNK_LANES + lane) * 8 < positions;
-    lane_off[k] = (uint32_t)(k * SC_CHUNK_LANES + lane) * 4u;
+    if constexpr (NCH == 1) {
+      int l = lane;
+      asm volatile("" : "+v"(l));
+      const int idx = l & (pair_off ? 31 : 63);
+      alive[k] = idx < SC_CHUNK_LANES && pbase + idx * 8 < positions;
+      lane_off[k] = (uint32_t)idx * 4u + (l >> 5 ? pair_off : 0u);
+    } else {
+      alive[k] = lane < SC_CHUNK_LANES && pbase + (k * SC_CHUNK_LANES + lane) * 8 < positions;
+      lane_off[k] = (uint32_t)(k * SC_CHUNK_LANES + lane) * 4u;
+    }
   }
   if (!refresh()) return;
   // One segment = NG whole groups of the block, then the exact bound test.  meta >> 25 counts the real features through the END of the
@@ -1345,19 +1362,27 @@ __device__ __forceinline__ void score_pass_sb(const ScoreParams& p, const uint8_
   // the last block's test ran with need = raw_threshold + 1 (every feature consumed): a lane is alive iff one of its placements passes
   // The few waves that come here work out their lane masks here: with a lane index it can see through, the compiler hoists two dozen
   // comparisons of the lane with constants in front of the pass and frame loops, and their masks then occupy SGPRs for the wave's whole life.
-  int lane_here = lane;
-  asm volatile("" : "+v"(lane_here));
+  // A merged tail appends once per half, each under its own frame: the stripe and the reservation stay one per (frame, chunk).  The second
+  // half takes the same code again (h = 1), lane index and sums read afresh, so that nothing but the two sums lives across the first append.
+#pragma unroll 1
+  for (int h = 0; h <= (NCH == 1 && pair_off ? 1 : 0); ++h) {
+    int lane_here = lane;
+    asm volatile("" : "+v"(lane_here));
 #pragma unroll
-  for (int k = 0; k < NCH; ++k) {
-    if (!chunk_on[k]) continue;   // uniform: the append below is a wave-wide operation (dead lanes pass nothing)
-    const int j0 = pbase + (k * SC_CHUNK_LANES + lane_here) * 8;
-    uint32_t raw8[8], pass = 0;
+    for (int k = 0; k < NCH; ++k) {
+      if (!chunk_on[k]) continue;   // uniform: the append below is a wave-wide operation (dead lanes pass nothing)
+      const int j0 = pbase + (NCH == 1 ? lane_here & (pair_off ? 31 : 63) : k * SC_CHUNK_LANES + lane_here) * 8;
+      uint32_t lo = acc_lo[k], hi = acc_hi[k];
+      if constexpr (NCH == 1) asm volatile("" : "+v"(lo), "+v"(hi));
+      const bool mine = alive[k] && (NCH > 1 || !pair_off || (lane_here >> 5) == h);
+      uint32_t raw8[8], pass = 0;
 #pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      raw8[q] = (((q & 1) ? acc_hi[k] : acc_lo[k]) >> (8 * (q >> 1))) & 0xffu;  // nibble q of the lane's dword
-      if (alive[k] && j0 + q < positions && (int)raw8[q] > raw_threshold) pass |= 1u << q;
+      for (int q = 0; q < 8; ++q) {
+        raw8[q] = (((q & 1) ? hi : lo) >> (8 * (q >> 1))) & 0xffu;  // nibble q of the lane's dword
+        if (mine && j0 + q < positions && (int)raw8[q] > raw_threshold) pass |= 1u << q;
+      }
+      append_candidates(p, g, frame + 8 * h, lane_here, j0, raw8, pass, (uint32_t)(pbase / SC_CHUNK_POS + k));
     }
-    append_candidates(p, g, frame, lane_here, j0, raw8, pass, (uint32_t)(pbase / SC_CHUNK_POS + k));
   }
 }
 
@@ -1369,7 +1394,7 @@ __device__ __forceinline__ void score_pass_sb(const ScoreParams& p, const uint8_
 // else x = template blocks and y = frames, FPW = 1.  No division anywhere: what is the same for every wave of the launch comes ready
 // from the host (threshold_frac, stripe_cap).  The passes run inside the frame loop, and a frame's first block comes from the scalar
 // cache again: the other order, with the first block's sixteen dwords and the pass's lane masks kept across the frames, needs more
-// SGPRs than there are (106 with 31-45 spilled to VGPR lanes, against 91 here).
+// SGPRs than there are (106 with 31-45 spilled to VGPR lanes, against 91 here; 95 with the merged tail below).
 // PER_CLASS: the threshold is the class's (ScoreParams::class_thr).  Its entry is asked for together with the class filter's word -- both
 // need the class index and nothing else -- so the chain of dependent round trips is as long as the uniform kernel's.
 template <bool PRUNE, int FPW, bool PER_CLASS = false>
@@ -1411,11 +1436,29 @@ __global__ __launch_bounds__(64 * SC_WAVES_PER_BLOCK) void k_score_coarse_sb(Sco
   // per frame only the base of the buffer descriptor moves; every accumulator and live flag starts afresh inside score_pass_sb
   const uint8_t* lm_frame = p.lm[0] + (size_t)frame0 * p.mod_stride;
   const int frame_end = FPW == 1 ? frame0 + 1 : min(p.n_frames, frame0 + 8 * FPW);
+  // The one-chunk pass behind the two-chunk passes is nearly empty when the template has a few placements more than a whole number of
+  // two-chunk passes (640x480: 150 dwords, so at most 24 of 63 lanes), and it still pays a whole first block and the pass's set-up.  With
+  // two frames to score and at most SB_TAIL_LANES live dwords, frame A leaves its tail open and the pass behind frame B's two-chunk passes
+  // scores both tails, a half-wave each (score_pass_sb).  Frame B's lanes reach their frame through the lane offset, so 8 * mod_stride and
+  // a lane's dword must stay inside the descriptor's 2^31 - 1 bytes: the range check sees the lane offset alone, and a level whose frames lie
+  // further apart than SB_TAIL_MAX_STRIDE keeps the plain tails, as do a wave with one frame and a tail of 32 lanes or more.
+  static_assert(FPW <= 2, "the merged tail pairs the two frames of a wave");
+  const int tail_pos = positions % (2 * SC_CHUNK_POS);   // placements of the one-chunk pass, if there is one (then 1 <= tail_pos <= SC_CHUNK_POS)
+  const bool merge = FPW == 2 && frame0 + 8 < frame_end && tail_pos >= 1 && tail_pos <= 8 * SB_TAIL_LANES && p.mod_stride <= SB_TAIL_MAX_STRIDE;
+  int tail_state = merge ? 1 : 0;   // 0: plain tails; 1: a merged pair, frame A's tail open; 2: frame B, whose tail pass scores both
 #pragma unroll 1
   for (int frame = frame0; frame < frame_end; frame += 8, lm_frame += 8 * (size_t)p.mod_stride) {
     int pbase = 0;
     for (; pbase + SC_CHUNK_POS < positions; pbase += 2 * SC_CHUNK_POS) score_pass_sb<2, PRUNE>(p, lm_frame, row, n_blocks, g, frame, lane, pbase, positions, raw_threshold, nf);
-    if (pbase < positions) score_pass_sb<1, PRUNE>(p, lm_frame, row, n_blocks, g, frame, lane, pbase, positions, raw_threshold, nf);
+    if (pbase < positions) {
+      if (tail_state == 1) {   // frame A of a merged pair: its tail is scored with frame B's
+        tail_state = 2;
+        continue;
+      }
+      const bool pair = tail_state == 2;
+      score_pass_sb<1, PRUNE>(p, pair ? lm_frame - 8 * (size_t)p.mod_stride : lm_frame, row, n_blocks, g, pair ? frame - 8 : frame, lane, pbase, positions,
+                              raw_threshold, nf, pair ? 8u * p.mod_stride : 0u);
+    }
   }
 }
 
