@@ -836,7 +836,13 @@ enum {
   LMX_DBG_QUANTIZED = 0,     /* u8 [H_l][W_l] one-hot labels after quantize(), A.2/A.4 */
   LMX_DBG_LINEAR_MEMORY = 1, /* u8 [8][T*T][W'H'] in upstream linearize() layout, A.7 */
   LMX_DBG_PYRAMID_BGR = 2,   /* u8 [H_l][W_l][3] colour source at level l (pyrDown chain), A.3; [H_l][W_l] on a gray context */
-  LMX_DBG_DEPTH = 3          /* u16 [H][W] level-0 depth in mm as the DepthNormal modality sees it */
+  LMX_DBG_DEPTH = 3,         /* u16 [H][W] level-0 depth in mm as the DepthNormal modality sees it */
+  /* Whole device allocations as they are, pads and tails included, every frame of the context: frame must be 0, nothing is launched or
+   * written.  A buffer that is too small is refused and the error text names the size. */
+  LMX_DBG_RAW_SPREAD = 4,    /* level < L-1: the spread image of (level, modality), max_batch * ls_stride + 8192 bytes */
+  LMX_DBG_RAW_NIBBLES = 5,   /* the coarsest level's nibble memories of all modalities, M * max_batch * nib_mod_stride + 8192 bytes (level, modality ignored) */
+  LMX_DBG_RAW_BYTES = 6      /* the coarsest level's byte-wide memories of `modality`, max_batch * mod_stride + 8192 bytes; they exist only where
+                                the spread kernel does not write nibbles itself (LMX_ERR_INVALID_ARG otherwise) */
 };
 lmx_status lmx_ctx_debug_read(lmx_ctx* ctx, int32_t frame, int32_t what, int32_t level, int32_t modality, void* out,
                               size_t out_bytes);

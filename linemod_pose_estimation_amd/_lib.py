@@ -38,6 +38,7 @@ SYMBOLS = [
  LMX_ERR_PARSE, LMX_ERR_NOT_FOUND) = range(9)
 LMX_MOD_COLOR_GRADIENT, LMX_MOD_DEPTH_NORMAL = 0, 1
 LMX_DBG_QUANTIZED, LMX_DBG_LINEAR_MEMORY, LMX_DBG_PYRAMID_BGR = 0, 1, 2
+LMX_DBG_RAW_SPREAD, LMX_DBG_RAW_NIBBLES, LMX_DBG_RAW_BYTES = 4, 5, 6   # whole allocations, pads and tails included
 LMX_DBG_DEPTH_INT, LMX_DBG_DEPTH_INT64, LMX_DBG_DEPTH_PIPELINED = 0, 1, 2   # variants of lmx_debug_depth_normal_bins
 # table selectors of lmx_debug_bank_tables
 (LMX_TAB_INFO, LMX_TAB_LINFO, LMX_TAB_COARSE_OFF, LMX_TAB_COARSE_UNI, LMX_TAB_COARSE_BLK, LMX_TAB_SINFO, LMX_TAB_FEAT, LMX_TAB_FEAT_COUNT,

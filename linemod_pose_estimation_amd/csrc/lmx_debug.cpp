@@ -67,6 +67,27 @@ lmx_status lmx_ctx_debug_read(lmx_ctx* c, int32_t frame, int32_t what, int32_t l
     const size_t n = (size_t)c->desc.width * c->desc.height * 2;
     if (out_bytes < n) { set_error("debug_read: buffer too small"); return LMX_ERR_INVALID_ARG; }
     LMX_HIP(hipMemcpy(out, (const uint8_t*)c->mb[modality].depth + (size_t)frame * n, n, hipMemcpyDeviceToHost));
+  } else if (what == LMX_DBG_RAW_SPREAD || what == LMX_DBG_RAW_NIBBLES || what == LMX_DBG_RAW_BYTES) {
+    // a whole allocation of lmx_ctx.cpp's frame buffers, untouched: the sizes are the ones dev_alloc got there
+    if (frame != 0) { set_error("debug_read: a raw read returns every frame, frame must be 0"); return LMX_ERR_INVALID_ARG; }
+    const LevelGeom& gc = c->kp.geom[c->L - 1];
+    const uint8_t* src = nullptr;
+    size_t n = 0;
+    if (what == LMX_DBG_RAW_SPREAD) {
+      if (level >= c->L - 1) { set_error("debug_read: the coarsest level %d keeps no spread image", level); return LMX_ERR_INVALID_ARG; }
+      src = c->kp.fb.ls[level][modality];
+      n = (size_t)c->F * g.ls_stride + 8192;
+    } else if (what == LMX_DBG_RAW_NIBBLES) {
+      src = c->kp.fb.lmn[0];
+      n = (size_t)c->M * c->F * gc.nib_mod_stride + 8192;
+    } else {
+      if (spread_writes_nibbles(gc)) { set_error("debug_read: this context keeps no byte-wide memories, its spread kernel writes the nibbles itself"); return LMX_ERR_INVALID_ARG; }
+      src = c->kp.fb.lm[c->L - 1][modality];
+      n = (size_t)c->F * gc.mod_stride + 8192;
+    }
+    if (!src) { set_error("debug_read: the context holds no such buffer"); return LMX_ERR_INVALID_ARG; }
+    if (out_bytes < n) { set_error("debug_read: buffer too small, the allocation has %zu bytes", n); return LMX_ERR_INVALID_ARG; }
+    LMX_HIP(hipMemcpy(out, src, n, hipMemcpyDeviceToHost));
   } else {
     set_error("debug_read: unknown item %d", what);
     return LMX_ERR_INVALID_ARG;

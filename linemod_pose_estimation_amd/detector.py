@@ -702,6 +702,14 @@ class Detector:
         _lib.check(_lib.lib().lmx_ctx_debug_read(self.h, frame, _lib.LMX_DBG_LINEAR_MEMORY, level, modality, out.ctypes.data, out.nbytes))
         return out
 
+    def debug_raw(self, what, nbytes, level=0, modality=0):
+        """Test hook: a whole device allocation as it is, pads and tails included, as nbytes uint8 (what = _lib.LMX_DBG_RAW_SPREAD of
+        (level, modality), LMX_DBG_RAW_NIBBLES, or LMX_DBG_RAW_BYTES of modality; include/lmx.h gives the sizes, which the caller works out
+        from the geometry in NativeBank.debug_tables' summary).  Too few bytes are refused, and the error names the size."""
+        out = np.empty(int(nbytes), np.uint8)
+        _lib.check(_lib.lib().lmx_ctx_debug_read(self.h, 0, int(what), level, modality, out.ctypes.data, out.nbytes))
+        return out
+
     def debug_depth(self, frame, modality):
         out = np.empty((self.height, self.width), np.uint16)
         _lib.check(_lib.lib().lmx_ctx_debug_read(self.h, frame, 3, 0, modality, out.ctypes.data, out.nbytes))

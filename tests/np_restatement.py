@@ -679,3 +679,113 @@ def extract_depth(normal, mask, num_features, extract_threshold):
     ys, xs, lab = ys[order], xs[order], lab[order]
     distance = F32(np.sqrt(F32(int(inside.sum()))) / np.sqrt(F32(num_features)) + F32(1.5))
     return select_scattered(xs, ys, lab, num_features, distance)
+
+
+# ---- the spread and response buffers of one (frame, modality), every byte (csrc/lmx_bank_tables.hpp: LevelGeom) ---------------------------
+# What the refinement and scoring kernels may read, restated from the layout comments: the payload, its second copy in the banded form, and
+# every pad, which must read as zero.  Each builder returns the expected bytes of one block and, per byte, which kind of place it is, so that
+# first_difference can name the place of a wrong byte.  tests/test_buffer_layout_host.py checks the builders against the debug reads' own
+# un-banding and unpacking and against k_refine's addressing; tests/test_gpu_buffer_bytes.py compares the device's allocations with them.
+BYTE_KINDS = ("payload", "own half", "duplicate half", "wrapped duplicate", "zero row", "zero run", "inter-orientation pad", "block tail", "tail")
+K_PAYLOAD, K_OWN, K_DUP, K_WRAP, K_ZERO_ROW, K_ZERO_RUN, K_ORI_PAD, K_BLOCK_TAIL, K_TAIL = range(len(BYTE_KINDS))
+ALLOC_TAIL = 8192   # zero bytes behind the last frame's block of every allocation
+
+
+def spread_block_index(g):
+    """Per byte of one (frame, modality) block of a finer level's spread image: the flat element (row * Wc + column of the matrix of
+    R = T * T * Hc rows, i.e. linearize()'s [T * T][cells] array read flat) it holds, -1 where it must be zero, and its kind.
+    Flat form: the elements, then zeros.  Banded form: byte k * ls_band_stride + r1 * 32 + c = element (r1 - 1) * Wc + 16 k + c where that
+    is an element, for r1 in [0, R + 17): the right halves repeat the next band's left halves, the last band's right half the first 16
+    columns of the NEXT row (one band row earlier than the others, hence band row 0), and band rows R + 1 .. R + 16 hold nothing."""
+    T, Wc, Hc, n = int(g["T"]), int(g["Wc"]), int(g["Hc"]), int(g["T"]) ** 2 * int(g["cells"])
+    idx = np.full(int(g["ls_stride"]), -1, np.int64)
+    kind = np.full(int(g["ls_stride"]), K_ZERO_RUN, np.uint8)
+    bands = int(g["ls_bands"])
+    if not bands:
+        idx[:n], kind[:n] = np.arange(n), K_PAYLOAD
+        return idx, kind
+    rows = T * T * Hc + 17
+    assert int(g["ls_band_stride"]) == rows * 32 and bands * 16 == Wc and bands * rows * 32 <= len(idx)
+    k, r1, c = np.meshgrid(np.arange(bands), np.arange(rows), np.arange(32), indexing="ij")
+    i = (r1 - 1) * Wc + 16 * k + c
+    ok = (i >= 0) & (i < n)
+    idx[:bands * rows * 32] = np.where(ok, i, -1).reshape(-1)
+    kind[:bands * rows * 32] = np.where(~ok, K_ZERO_ROW, np.where(c < 16, K_OWN, np.where(k == bands - 1, K_WRAP, K_DUP))).reshape(-1)
+    return idx, kind
+
+
+def spread_block(g, flat):
+    """flat: the oracle's linearize(spread(labels, T), T).  -> (bytes [ls_stride], kinds)."""
+    idx, kind = spread_block_index(g)
+    flat = np.asarray(flat, np.uint8).reshape(-1)
+    assert len(flat) == int(g["T"]) ** 2 * int(g["cells"])
+    return np.where(idx >= 0, flat[np.maximum(idx, 0)], 0).astype(np.uint8), kind
+
+
+def unband_spread_block(g, block):
+    """The flat spread image as the debug read takes it out of a block: the first 16 columns of band rows 1 .. R of every band."""
+    n = int(g["T"]) ** 2 * int(g["cells"])
+    if not g["ls_bands"]:
+        return block[:n].copy()
+    Wc, bs = int(g["Wc"]), int(g["ls_band_stride"])
+    out = np.empty(n, np.uint8)
+    for r in range(n // Wc):
+        for k in range(int(g["ls_bands"])):
+            out[r * Wc + 16 * k:r * Wc + 16 * k + 16] = block[k * bs + (r + 1) * 32:k * bs + (r + 1) * 32 + 16]
+    return out
+
+
+def nibble_block(g, lm):
+    """lm: the oracle's linear memories [8][T * T][cells] of the coarsest level (responses 0..4).  Orientation o at o * nib_ori_stride, byte i
+    = elem(2 i) | elem(2 i + 1) << 4 for i < (n + 1) / 2, zero everywhere else; the zero run the tables point at starts at nib_zero_off."""
+    n = int(g["T"]) ** 2 * int(g["cells"])
+    nb, os_, zo = (n + 1) // 2, int(g["nib_ori_stride"]), int(g["nib_zero_off"])
+    e = np.zeros((8, 2 * nb), np.uint8)
+    e[:, :n] = np.asarray(lm, np.uint8).reshape(8, n)
+    out = np.zeros(int(g["nib_mod_stride"]), np.uint8)
+    kind = np.full(len(out), K_BLOCK_TAIL, np.uint8)
+    kind[:8 * os_] = K_ORI_PAD
+    assert nb <= zo and zo + int(g["cells"]) // 2 + 2048 <= os_ and 8 * os_ <= len(out)
+    kind[zo:zo + int(g["cells"]) // 2 + 2048] = K_ZERO_RUN
+    for o in range(8):
+        out[o * os_:o * os_ + nb] = e[o, 0::2] | e[o, 1::2] << 4
+        kind[o * os_:o * os_ + nb] = K_PAYLOAD
+    return out, kind
+
+
+def unpack_nibble_block(g, block):
+    """-> [8][T * T * cells], as the debug read unpacks it."""
+    n = int(g["T"]) ** 2 * int(g["cells"])
+    i = np.arange(n)
+    return np.stack([block[o * int(g["nib_ori_stride"]) + i // 2] >> 4 * (i % 2) & 15 for o in range(8)]).astype(np.uint8)
+
+
+def byte_block(g, lm):
+    """The byte-wide memories of the generic coarsest-level path: orientation o's T * T * cells bytes at o * ori_stride, zero everywhere else
+    (k_pack_nibbles reads up to 15 bytes past each orientation's payload)."""
+    n, os_ = int(g["T"]) ** 2 * int(g["cells"]), int(g["ori_stride"])
+    out = np.zeros(int(g["mod_stride"]), np.uint8)
+    kind = np.full(len(out), K_BLOCK_TAIL, np.uint8)
+    kind[:8 * os_] = K_ORI_PAD
+    assert int(g["zero_off"]) == n and n <= os_ and 8 * os_ <= len(out)
+    kind[n:os_] = K_ZERO_RUN
+    for o in range(8):
+        out[o * os_:o * os_ + n] = np.asarray(lm, np.uint8).reshape(8, n)[o]
+        kind[o * os_:o * os_ + n] = K_PAYLOAD
+    return out, kind
+
+
+def allocation(blocks):
+    """[(bytes, kinds)] of an allocation's blocks in order -> (bytes, kinds) of the allocation: the blocks, then ALLOC_TAIL zero bytes."""
+    return (np.concatenate([b for b, _ in blocks] + [np.zeros(ALLOC_TAIL, np.uint8)]),
+            np.concatenate([k for _, k in blocks] + [np.full(ALLOC_TAIL, K_TAIL, np.uint8)]))
+
+
+def first_difference(got, want, kind):
+    """None where got == want, else (the kind of place of the first differing byte by name, its offset, got, want)."""
+    assert got.shape == want.shape == kind.shape, (got.shape, want.shape, kind.shape)
+    bad = np.flatnonzero(got != want)
+    if len(bad) == 0:
+        return None
+    i = int(bad[0])
+    return BYTE_KINDS[kind[i]], i, int(got[i]), int(want[i])
