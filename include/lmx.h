@@ -846,6 +846,11 @@ enum {
 };
 lmx_status lmx_ctx_debug_read(lmx_ctx* ctx, int32_t frame, int32_t what, int32_t level, int32_t modality, void* out,
                               size_t out_bytes);
+/* Test hook: the counters of the context's helper thread (the one-frame lmx_match / lmx_match_batch with host frames hands the rest of its
+ * chain to it; csrc/lmx_launch_helper.hpp).  out = {jobs run, times the helper went to sleep, wake-ups sent}: jobs - wake-ups is about the
+ * number of calls that found the helper still spinning.  All zero while the context has had no such call (it has no helper thread then) or
+ * when the path is switched off.  Call it between matches, from the thread that matches. */
+lmx_status lmx_debug_launch_helper_counters(lmx_ctx* ctx, uint64_t out[3]);
 /* Test hook for the float stage: the 16-bin orientation label (0..16, before upstream's '& 7') the device code assigns to
  * n gradients (dx[i], dy[i]) -- fastAtan2 in degrees, times 16/360, round half to even. */
 lmx_status lmx_debug_orientation_labels(int32_t device, const int16_t* dx, const int16_t* dy, size_t n, uint8_t* out);

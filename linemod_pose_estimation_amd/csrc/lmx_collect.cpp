@@ -106,7 +106,10 @@ static lmx_status collect_impl(lmx_ctx* c, int32_t n_frames, std::vector<std::ve
     return LMX_ERR_OVERFLOW;
   }
   if (n_match > first) {
-    // rare: more matches than the first slice; the slot's records are final (its event has completed)
+    // rare: more matches than the first slice.  The records behind it are read from the device slot itself, and when the header poll above
+    // saw the sequence word nobody has waited for the slot's event: the word says that k_refine's last workgroup is through, not that the
+    // stream's work on the slot has completed for a copy that does not run on that stream.  So wait for the event now, in that case only
+    if (seen) LMX_HIP(hipEventSynchronize(c->done[slot]));
     LMX_HIP(hipMemcpy(c->h_out + 64 + first * sizeof(lmx_raw_match_t), d_slot + 64 + first * sizeof(lmx_raw_match_t),
                       (n_match - first) * sizeof(lmx_raw_match_t), hipMemcpyDeviceToHost));
   }

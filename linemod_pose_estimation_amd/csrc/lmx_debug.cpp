@@ -95,6 +95,16 @@ lmx_status lmx_ctx_debug_read(lmx_ctx* c, int32_t frame, int32_t what, int32_t l
   return LMX_OK;
 }
 
+lmx_status lmx_debug_launch_helper_counters(lmx_ctx* c, uint64_t out[3]) {
+  if (!c || !out) { set_error("lmx_debug_launch_helper_counters: null argument"); return LMX_ERR_INVALID_ARG; }
+  out[0] = out[1] = out[2] = 0;   // no one-frame call yet: the context has no helper
+  if (c->launch_helper) {
+    const LaunchHelper::Counters k = c->launch_helper->counters();
+    out[0] = k.jobs; out[1] = k.sleeps; out[2] = k.notifies;
+  }
+  return LMX_OK;
+}
+
 lmx_status lmx_debug_orientation_labels(int32_t device, const int16_t* dx, const int16_t* dy, size_t n, uint8_t* out) {
   if (!dx || !dy || !out) { set_error("lmx_debug_orientation_labels: null argument"); return LMX_ERR_INVALID_ARG; }
   int ndev = 0;

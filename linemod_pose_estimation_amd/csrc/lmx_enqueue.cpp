@@ -228,11 +228,22 @@ static lmx_status issue_small(lmx_ctx* c, int slot, int32_t n_frames, float thre
         if (store_depth) c->store_modality_streamed(fs, 1, n_frames, sources, wd.seq, -1);
       }
     };
+    // The job writes through references into this frame, so the frame is never left before the helper is through with it: whatever this
+    // thread's stores throw, the guard's wait() comes first.
+    struct WaitGuard {
+      lmx::LaunchHelper* helper;
+      bool armed;
+      ~WaitGuard() { if (armed) (void)helper->wait(); }
+    } pending{c->launch_helper.get(), false};
     c->launch_helper->submit(&job);
+    pending.armed = true;
     c->store_modality_streamed(fs, 0, n_frames, sources, wc.seq, end);
     if (store_depth) c->store_modality_streamed(fs, 1, n_frames, sources, wd.seq, end);
-    c->launch_helper->wait();
+    pending.armed = false;
+    const bool job_returned = c->launch_helper->wait();
     lap(lmx_ctx::TM_STORE_COLOR);
+    // a job that threw on the helper thread: the status and message lmx::guarded gives an exception on the calling thread
+    if (!job_returned) return lmx::guarded("lmx_match (launch thread)", [&]() -> lmx_status { c->launch_helper->rethrow(); return LMX_ERR_HIP; });
     if (rest_st != LMX_OK) { set_error("%s", rest_msg.c_str()); return rest_st; }
     return LMX_OK;
   }

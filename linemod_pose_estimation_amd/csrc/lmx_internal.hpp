@@ -19,6 +19,7 @@
 
 #include "lmx.h"
 #include "lmx_bank_tables.hpp"   // the host bank, LevelGeom and the kernels' table entries (no HIP)
+#include "lmx_launch_helper.hpp"   // the one-frame call's helper thread (no HIP)
 
 namespace lmx {
 
@@ -96,57 +97,8 @@ class CopyPool {
 };
 
 
-// One persistent helper thread for the one-frame call (lmx_enqueue.cpp issue_small): the caller hands it a job (queue the rest of the kernel
-// chain, then store the depth frame) and stores the colour frame itself.  A job arrives every ~100 us when frames are matched back to back and
-// a condition-variable wake-up costs 10-50 us, so the helper SPINS for a bounded time after a job (300 us) before it goes to sleep: a caller in
-// a tight loop finds it awake, a 1 Hz caller (the reference's demo node) pays a wake-up it will not notice and no core is kept busy.
-class LaunchHelper {
- public:
-  LaunchHelper() : th_([this]() { run(); }) {}
-  ~LaunchHelper() {
-    { std::lock_guard<std::mutex> lk(m_); stop_ = true; gen_.fetch_add(1, std::memory_order_release); }
-    cv_.notify_all();
-    th_.join();
-  }
-  void submit(const std::function<void()>* job) {
-    job_ = job;
-    done_.store(false, std::memory_order_relaxed);
-    gen_.fetch_add(1, std::memory_order_release);
-    if (sleeping_.load(std::memory_order_acquire)) { std::lock_guard<std::mutex> lk(m_); cv_.notify_one(); }
-  }
-  void wait() const {
-    while (!done_.load(std::memory_order_acquire)) __builtin_ia32_pause();
-  }
-
- private:
-  void run() {
-    uint64_t seen = 0;
-    for (;;) {
-      const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-      int spins = 0;
-      while (gen_.load(std::memory_order_acquire) == seen) {
-        __builtin_ia32_pause();
-        if ((++spins & 255) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(300)) {
-          std::unique_lock<std::mutex> lk(m_);
-          sleeping_.store(true, std::memory_order_release);
-          cv_.wait(lk, [&]() { return gen_.load(std::memory_order_acquire) != seen; });
-          sleeping_.store(false, std::memory_order_release);
-        }
-      }
-      seen = gen_.load(std::memory_order_acquire);
-      { std::lock_guard<std::mutex> lk(m_); if (stop_) return; }
-      (*job_)();
-      done_.store(true, std::memory_order_release);
-    }
-  }
-  std::mutex m_;
-  std::condition_variable cv_;
-  std::atomic<uint64_t> gen_{0};
-  std::atomic<bool> done_{true}, sleeping_{false};
-  const std::function<void()>* job_ = nullptr;
-  bool stop_ = false;
-  std::thread th_;   // last: the thread starts with every other member constructed
-};
+// The helper thread of the one-frame call (LaunchHelper) lives in lmx_launch_helper.hpp: standard headers only, built and stressed on its own
+// by tests/test_launch_helper_host.py.
 
 // ---- hooks for device groups (lmx_group.cpp): several member contexts fed from ONE pinned staging area ------------------
 // A group stages a batch of host frames once (layout: modality m at offset sum_{m' < m} frame_bytes[m'] * max_batch, frames

@@ -727,6 +727,13 @@ class Detector:
         _lib.check(_lib.lib().lmx_ctx_stats(self.h, C.byref(a), C.byref(b)))
         return {"candidates": a.value, "raw_matches": b.value}
 
+    def launch_helper_counters(self):
+        """Test hook (lmx_debug_launch_helper_counters): the helper thread of the one-frame call with host frames -- jobs it ran, times it went
+        to sleep, wake-ups it was sent, and `awake` = jobs - notifies, the calls that found it still spinning.  All zero before the first such call."""
+        k = (C.c_uint64 * 3)()
+        _lib.check(_lib.lib().lmx_debug_launch_helper_counters(self.h, k))
+        return {"jobs": int(k[0]), "sleeps": int(k[1]), "notifies": int(k[2]), "awake": int(k[0]) - int(k[2])}
+
     def chain_stats(self):
         """Which path completed the frames of the last collect_clusters* call (lmx_ctx_chain_stats): frames, frames_lds (at most F2_MAX raw
         records), frames_large (up to F2_LARGE_MAX, the large-frame kernel), frames_host_records, frames_host_other (side-car / ring range),
