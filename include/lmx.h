@@ -383,6 +383,57 @@ lmx_status lmx_ctx_export_raw_on(lmx_ctx* ctx, void* d_block, size_t capacity_re
  * pipelined caller that finds, when it finishes batch i, that its gather block was too small re-exports batch i's records --
  * they stay in the output slot until the slot is released -- into a larger block while later batches are already enqueued. */
 lmx_status lmx_ctx_export_oldest_on(lmx_ctx* ctx, void* d_block, size_t capacity_records, void* stream);
+/* The FINAL results of an enqueue left in device memory, for a next stage that also runs on the GPU: per frame the match list
+ * Detector::match promises (insertion order restored, std::sort with libstdc++'s order of ties, std::unique) and, with `clusters`, the
+ * clusters and members of lmx_ctx_collect_clusters -- bit for bit and in order what lmx_ctx_collect_flat / lmx_ctx_collect_clusters
+ * return for the same enqueue, for every frame with status 0.  The counterpart of lmx_ctx_upload_device on the way out.
+ * The call consumes nothing: the enqueue stays outstanding until lmx_ctx_collect* or lmx_ctx_release ends it, so a frame the export did
+ * not finish can still go through the host path.
+ * Outputs (plain device memory of the context's device; `lmx_cluster_t` 8-byte aligned, the others 4):
+ *   header[16]        [0] n_frames, [1] flags, [2] total matches, [3] total clusters, [4] total members, [5] coarse candidates,
+ *                     [6] raw records, rest 0.  Flags: 1 the slot's candidate or record list overflowed (nothing is delivered, every frame
+ *                     has status 16, the totals are 0); 2 some frame was not finished (status 1 or 2); 4 some array did not fit.
+ *                     The totals are the true ones, whatever fitted.
+ *   frame_info[f][8]  {match_begin, match_count, cluster_begin, cluster_count, member_begin, member_count, status, raw_records}.
+ *                     Frames lie back to back in frame order: a frame's *_begin is the sum of the counts of the frames before it whether
+ *                     or not those fitted, and lmx_cluster_t.member_begin counts from the start of `members`, as lmx_ctx_collect_clusters
+ *                     lays them out.  A frame's range of an array is written iff the WHOLE range fits that array's capacity (clusters
+ *                     and members go together).  raw_records: the frame's records in the slot (0 with status 16).
+ *                     status 0 delivered; 1 not finished: more than 2048 raw records and either none of this call's max_large_frames
+ *                     left or more than 16384 records; 2 the chain's status 2 (a ring outside the packed range, `clusters` only); 4 / 8
+ *                     or-ed onto 0: the frame's matches / its clusters or members did not fit; 16 list overflow.  Frames with status 1, 2
+ *                     or 16 have counts 0 and add nothing to the offsets.
+ * A capacity of 0 is allowed (nothing fits, the counts are still true).
+ * Ordering (`stream` is the HIP stream that will consume the results; NULL = the null stream), lmx_ctx_upload_device's rules mirrored:
+ *   - the export's kernels run on a private stream of the context, which waits ON THE DEVICE for the chosen enqueue and for what
+ *     `stream` holds at the call (the outputs may still be in use there);
+ *   - the call waits for nothing on the host and reads no result on the host: which frames need the large-frame kernel, the offsets
+ *     and the fit tests are decided from device memory inside the kernels (the first call allocates the export's buffers, and a call
+ *     with a larger max_large_frames than any before grows its workspace: 2.4 MB per frame);
+ *   - before returning, `stream` is made to wait for the end of the export: work queued on `stream` afterwards may read the outputs.
+ *     Any other stream, or the host, synchronises with `stream`;
+ *   - lmx_ctx_release, every lmx_ctx_collect* form that ends the enqueue, lmx_ctx_sync and lmx_ctx_destroy wait (on the host) for the
+ *     exports that read its slot before the slot can be reused.
+ * Refused before anything is queued with LMX_ERR_INVALID_ARG, enqueue and context stay usable: a struct_size other than the struct's;
+ * nothing outstanding; n_frames different from the enqueue's; a null header, frame_info or matches; `clusters` without a side-car
+ * (lmx_ctx_set_cluster_sidecar) or with a null clusters_out or members; max_large_frames < 0; an output that hipPointerGetAttributes does
+ * not report as plain device memory of the context's device, or that is not aligned to its element; a `stream` that is being captured; a
+ * context that is a member of a device group. */
+typedef struct lmx_export_desc {
+  uint32_t struct_size;        /* sizeof(lmx_export_desc) */
+  int32_t oldest;              /* 0: the most recent enqueue (as lmx_ctx_export_raw_on); 1: the oldest outstanding one (as lmx_ctx_export_oldest_on) */
+  int32_t clusters;            /* 1: also voting .. NMS with the side-car of lmx_ctx_set_cluster_sidecar (mean similarity score) */
+  int32_t max_large_frames;    /* frames of 2049 .. 16384 raw records this call may finish with the large-frame kernel; 0: none */
+  uint32_t* header;            /* [16] */
+  int32_t* frame_info;         /* [n_frames][8] */
+  lmx_match_t* matches;
+  size_t cap_matches;
+  struct lmx_cluster_t* clusters_out;   /* clusters == 1 only */
+  size_t cap_clusters;
+  int32_t* members;            /* clusters == 1 only */
+  size_t cap_members;
+} lmx_export_desc;
+lmx_status lmx_ctx_export_matches_on(lmx_ctx* ctx, int32_t n_frames, const lmx_export_desc* desc, void* stream);
 /* Copy `bytes` (multiple of 16, both pointers 16-byte aligned) on `stream` with a kernel instead of a DMA engine; `dst` may
  * be pinned host memory.  For small latency-sensitive read-backs in a pipelined caller: hipMemcpyAsync(DeviceToHost) was
  * measured to block the submitting thread for milliseconds now and then when copies of several streams are in flight. */

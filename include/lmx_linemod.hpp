@@ -289,6 +289,17 @@ class Detector {
     if (!pre) ensure_ctx(frames[0][0].cols, frames[0][0].rows, false);
     else if (!ctx_) throw Exception(LMX_ERR_INVALID_ARG, "uploadDevice: raw frames need a context of the cropped size first");
     check(lmx_ctx_upload_device(ctx_, (int32_t)frames.size(), imgs.data(), (int32_t)frames[0].size(), pre, stream));
+    uploaded_frames_ = (int32_t)frames.size();
+  }
+
+  // The way out for a next stage on the GPU (lmx_ctx_export_matches_on; include/lmx.h has the layout and the ordering contract): the final
+  // matches -- with desc.clusters the clusters and members too -- of the current context's most recent (desc.oldest: oldest outstanding)
+  // enqueue into the caller's device arrays, valid for work queued on `stream` (null: the null stream) after the call.  Nothing waits on the
+  // host and the enqueue stays outstanding: lmx_ctx_release(context()) or a collect ends it.  desc.struct_size is the caller's to set.
+  // n_frames is the enqueue's frame count; 0: as many as the last uploadDevice brought.
+  void exportMatches(const lmx_export_desc& desc, void* stream = nullptr, int32_t n_frames = 0) {
+    if (!ctx_) throw Exception(LMX_ERR_INVALID_ARG, "exportMatches: no context, nothing was enqueued");
+    check(lmx_ctx_export_matches_on(ctx_, n_frames > 0 ? n_frames : uploaded_frames_, &desc, stream));
   }
 
   lmx_bank* bank() const { return bank_; }
@@ -335,6 +346,7 @@ class Detector {
   lmx_ctx* slot_[2] = {nullptr, nullptr};
   int device_ = 0, max_batch_ = 1, max_candidates_ = 0, w_[2] = {0, 0}, h_[2] = {0, 0};
   void* stream_ = nullptr;
+  int32_t uploaded_frames_ = 0;   // of the last uploadDevice: exportMatches' default frame count
   std::vector<lmx_match_t> buf_;
 };
 

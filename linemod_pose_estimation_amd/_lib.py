@@ -32,6 +32,7 @@ SYMBOLS = [
     "lmx_debug_device_finalize_cluster_large_classes", "lmx_ctx_chain_stats",
     "lmx_ctx_enqueue_thresholds", "lmx_match_thresholds", "lmx_match_batch_thresholds", "lmx_match_masked_thresholds", "lmx_group_submit_thresholds",
     "lmx_bank_train_mesh_opts", "lmx_debug_train_extract", "lmx_debug_launch_helper_counters",
+    "lmx_ctx_export_matches_on",
 ]
 
 (LMX_OK, LMX_ERR_INVALID_ARG, LMX_ERR_SHAPE, LMX_ERR_NO_DEVICE, LMX_ERR_HIP, LMX_ERR_OVERFLOW, LMX_ERR_IO,
@@ -86,6 +87,12 @@ class ClassScore(C.Structure):     # lmx_class_score
 class ChainStats(C.Structure):     # lmx_chain_stats
     _fields_ = [("frames", C.c_int32), ("frames_lds", C.c_int32), ("frames_large", C.c_int32), ("frames_host_records", C.c_int32),
                 ("frames_host_other", C.c_int32), ("max_frame_records", C.c_int32), ("large_workspace_bytes", C.c_int64)]
+
+
+class ExportDesc(C.Structure):     # lmx_export_desc
+    _fields_ = [("struct_size", C.c_uint32), ("oldest", C.c_int32), ("clusters", C.c_int32), ("max_large_frames", C.c_int32),
+                ("header", C.c_void_p), ("frame_info", C.c_void_p), ("matches", C.c_void_p), ("cap_matches", C.c_size_t),
+                ("clusters_out", C.c_void_p), ("cap_clusters", C.c_size_t), ("members", C.c_void_p), ("cap_members", C.c_size_t)]
 
 
 class RendererParams(C.Structure):
@@ -279,6 +286,7 @@ def lib():
     L.lmx_ctx_raw_matches.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.lmx_ctx_export_raw.argtypes = [vp, vp, C.c_size_t]
     L.lmx_ctx_export_raw_on.argtypes = [vp, vp, C.c_size_t, vp]
+    L.lmx_ctx_export_matches_on.argtypes = [vp, C.c_int32, C.POINTER(ExportDesc), vp]
     L.lmx_ctx_release.argtypes = [vp]
     L.lmx_ctx_max_outstanding.argtypes = [vp]
     L.lmx_stream_copy.argtypes = [vp, vp, C.c_size_t, vp]

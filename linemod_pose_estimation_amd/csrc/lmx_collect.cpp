@@ -1,6 +1,7 @@
 // liblmx.so, behind the kernel chain: read-back of an output slot and the host finalisation (restore upstream insertion order, then the
-// very std::sort / std::unique Detector::match applies), the device-side consumer chain (lmx_ctx_collect_clusters), and the
-// multi-GPU plumbing on one context's side: gather-block export, copies by kernel, the host merge of gathered blocks.
+// very std::sort / std::unique Detector::match applies), the device-side consumer chain (lmx_ctx_collect_clusters), its
+// form that leaves the results in the caller's device memory (lmx_ctx_export_matches_on), and the multi-GPU plumbing on one context's
+// side: gather-block export, copies by kernel, the host merge of gathered blocks.
 
 #include <algorithm>
 #include <atomic>
@@ -84,6 +85,7 @@ static lmx_status collect_impl(lmx_ctx* c, int32_t n_frames, std::vector<std::ve
   const clk::time_point t1 = clk::now();
   c->h_out = c->h_out_slot[slot];
   uint8_t* const d_slot = c->d_out_slot[slot];
+  if (lmx_status xs = wait_exports(c, slot)) return xs;   // an export may still read the slot this call frees
   c->outstanding -= 1;
   if (c->outstanding == 0) drain_profiling(c);  // every recorded event has completed
   const uint32_t n_cand = reinterpret_cast<uint32_t*>(c->h_out)[0];
@@ -367,6 +369,7 @@ static lmx_status collect_clusters_impl(const char* what, lmx_ctx* c, int32_t n_
     if (lmx_status st = dev_alloc(c, &c->d_f2_ndiff_scratch, F * 2 * F2_MAX, false)) return st;
   }
   LMX_HIP(hipEventSynchronize(c->done[slot]));
+  if (lmx_status xs = wait_exports(c, slot)) return xs;   // an export may still read the slot this call frees
   c->outstanding -= 1;
   if (c->outstanding == 0) drain_profiling(c);
   const uint32_t* h_hdr = reinterpret_cast<const uint32_t*>(c->h_out_slot[slot]);
@@ -656,6 +659,122 @@ lmx_status lmx_ctx_export_oldest_on(lmx_ctx* c, void* d_block, size_t capacity_r
   return LMX_OK;
 }
 
+// One output of lmx_ctx_export_matches_on: plain device memory of the context's device, aligned to its element.
+static lmx_status check_export_output(const lmx_ctx* c, const char* name, const void* p, size_t align) {
+  if ((uintptr_t)p & (align - 1)) { set_error("lmx_ctx_export_matches_on: %s must be aligned to %zu bytes", name, align); return LMX_ERR_INVALID_ARG; }
+  hipPointerAttribute_t attr;
+  if (hipPointerGetAttributes(&attr, p) != hipSuccess) {   // memory the runtime has never seen
+    (void)hipGetLastError();
+    set_error("lmx_ctx_export_matches_on: %s is not device memory", name);
+    return LMX_ERR_INVALID_ARG;
+  }
+  if (attr.type != hipMemoryTypeDevice || attr.device != c->device) {
+    set_error("lmx_ctx_export_matches_on: %s is %s; the outputs are plain device memory of device %d", name,
+              attr.type == hipMemoryTypeDevice ? "memory of another device" : "pageable, pinned, managed or other host memory", c->device);
+    return LMX_ERR_INVALID_ARG;
+  }
+  return LMX_OK;
+}
+
+// The final matches (and clusters) of an enqueue into the caller's device arrays (include/lmx.h; kernels: lmx_export.hip).  Every refusal
+// comes before anything is queued; nothing below waits on the host for the device except an allocation's first use.
+lmx_status lmx_ctx_export_matches_on(lmx_ctx* c, int32_t n_frames, const lmx_export_desc* d, void* stream) {
+  return lmx::guarded("lmx_ctx_export_matches_on", [&]() -> lmx_status {
+  const char* const what = "lmx_ctx_export_matches_on";
+  if (!c || !d) { set_error("%s: null argument", what); return LMX_ERR_INVALID_ARG; }
+  if (d->struct_size != sizeof(lmx_export_desc)) { set_error("%s: struct_size %u, not %zu", what, d->struct_size, sizeof(lmx_export_desc)); return LMX_ERR_INVALID_ARG; }
+  if (!c->sets[0].h_stage) { set_error("%s: this context is a member of a device group", what); return LMX_ERR_INVALID_ARG; }
+  if (c->outstanding < 1) { set_error("%s: nothing enqueued", what); return LMX_ERR_INVALID_ARG; }
+  const int slot = d->oldest ? (c->head + c->n_slots - c->outstanding) % c->n_slots : (c->head + c->n_slots - 1) % c->n_slots;
+  if (n_frames != c->slot_frames[slot]) { set_error("%s: n_frames=%d but the enqueue had %d", what, n_frames, c->slot_frames[slot]); return LMX_ERR_INVALID_ARG; }
+  if (!d->header || !d->frame_info || !d->matches) { set_error("%s: header, frame_info and matches must not be null", what); return LMX_ERR_INVALID_ARG; }
+  const bool clusters = d->clusters != 0;
+  if (clusters && !c->f2_sidecar) { set_error("%s: clusters: call lmx_ctx_set_cluster_sidecar first", what); return LMX_ERR_INVALID_ARG; }
+  if (clusters && (!d->clusters_out || !d->members)) { set_error("%s: clusters: clusters_out and members must not be null", what); return LMX_ERR_INVALID_ARG; }
+  if (d->max_large_frames < 0) { set_error("%s: max_large_frames %d is negative", what, d->max_large_frames); return LMX_ERR_INVALID_ARG; }
+  LMX_HIP(hipSetDevice(c->device));
+  hipStream_t user = static_cast<hipStream_t>(stream);
+  hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+  if (user && hipStreamIsCapturing(user, &capturing) != hipSuccess) { (void)hipGetLastError(); set_error("%s: invalid stream", what); return LMX_ERR_INVALID_ARG; }
+  if (capturing != hipStreamCaptureStatusNone) { set_error("%s: the stream is being captured into a graph", what); return LMX_ERR_INVALID_ARG; }
+  if (lmx_status st = check_export_output(c, "header", d->header, 4)) return st;
+  if (lmx_status st = check_export_output(c, "frame_info", d->frame_info, 4)) return st;
+  if (lmx_status st = check_export_output(c, "matches", d->matches, 4)) return st;
+  if (clusters) {
+    if (lmx_status st = check_export_output(c, "clusters_out", d->clusters_out, 8)) return st;
+    if (lmx_status st = check_export_output(c, "members", d->members, 4)) return st;
+  }
+  // the export's own buffers, on first use
+  const size_t F = (size_t)c->F;
+  const F2LargeLayout lay = f2_large_layout(false, false);
+  if (!c->d_xp_rows) {
+    const size_t off_clusters = F * F2_MAX * sizeof(lmx_match_t), off_members = off_clusters + F * F2_MAX * sizeof(lmx_cluster_t),
+                 off_counts = off_members + F * F2_MAX * sizeof(int32_t), off_list = off_counts + F * 4 * sizeof(uint32_t),
+                 off_listed = off_list + F * sizeof(int32_t), off_lcounts = (off_listed + sizeof(uint32_t) + 15) & ~(size_t)15,
+                 bytes = off_lcounts + F * 4 * sizeof(uint32_t);
+    static_assert((F2_MAX * sizeof(lmx_match_t)) % 16 == 0 && (F2_MAX * sizeof(lmx_cluster_t)) % 16 == 0, "the rows stay 16-byte aligned");
+    uint8_t* rows = nullptr;
+    lmx_status st;
+    if ((st = dev_alloc(c, &rows, bytes, false)) != LMX_OK) return st;
+    if ((st = dev_alloc(c, &c->d_xp_scratch, F * F2_MAX * 32, false)) != LMX_OK) return st;
+    LMX_HIP(hipStreamCreateWithFlags(&c->export_stream, hipStreamNonBlocking));
+    LMX_HIP(hipEventCreateWithFlags(&c->export_dst_ready, hipEventDisableTiming));
+    for (int i = 0; i < lmx_ctx::kSlots; ++i) LMX_HIP(hipEventCreateWithFlags(&c->export_done[i], hipEventDisableTiming));
+    c->d_xp_matches = reinterpret_cast<lmx_match_t*>(rows); c->d_xp_clusters = reinterpret_cast<lmx_cluster_t*>(rows + off_clusters);
+    c->d_xp_members = reinterpret_cast<int32_t*>(rows + off_members); c->d_xp_counts = reinterpret_cast<uint32_t*>(rows + off_counts);
+    c->d_xp_large_frames = reinterpret_cast<int32_t*>(rows + off_list); c->d_xp_large_listed = reinterpret_cast<uint32_t*>(rows + off_listed);
+    c->d_xp_large_counts = reinterpret_cast<uint32_t*>(rows + off_lcounts);
+    c->d_xp_rows = rows;
+  }
+  const int max_large = std::min<int>(d->max_large_frames, n_frames);
+  if (max_large > c->xp_large_parts) {   // an earlier export may still work on the old workspace
+    LMX_HIP(hipStreamSynchronize(c->export_stream));
+    if (c->d_xp_large_ws) (void)hipFree(c->d_xp_large_ws);
+    c->d_xp_large_ws = nullptr; c->xp_large_parts = 0;
+    LMX_HIP(hipMalloc((void**)&c->d_xp_large_ws, (size_t)max_large * lay.bytes));
+    c->xp_large_parts = max_large;
+  }
+  hipStream_t s = c->export_stream;
+  // behind the enqueue that fills the slot, and behind what the caller's stream still does with the outputs
+  LMX_HIP(hipStreamWaitEvent(s, c->done[slot], 0));
+  LMX_HIP(hipEventRecord(c->export_dst_ready, user));
+  LMX_HIP(hipStreamWaitEvent(s, c->export_dst_ready, 0));
+  F2Params p{};
+  p.recs = reinterpret_cast<const lmx_raw_match_t*>(c->d_out_slot[slot] + 64);
+  p.hdr = reinterpret_cast<const uint32_t*>(c->d_out_slot[slot]);
+  p.cap = c->cap_total; p.n_frames = n_frames;
+  p.out_matches = c->d_xp_matches; p.out_counts = c->d_xp_counts; p.out_clusters = c->d_xp_clusters; p.out_members = c->d_xp_members; p.scratch = c->d_xp_scratch;
+  p.do_clusters = clusters ? 1 : 0;
+  if (clusters) {
+    p.dists = c->d_f2_dists; p.rects = c->d_f2_rects; p.n_templates = (uint32_t)c->f2_templates;
+    p.step = c->f2_params.vote_row_col_step; p.size_thresh = c->f2_params.cluster_size_thresh;
+    p.radius_min = c->f2_params.renderer_radius_min; p.radius_step = c->f2_params.renderer_radius_step;
+  }
+  launch_f2(s, p);
+  ExportParams e{};
+  e.recs = p.recs; e.hdr = p.hdr; e.cap = p.cap; e.n_frames = n_frames; e.max_large = max_large;
+  e.rows_matches = c->d_xp_matches; e.rows_clusters = c->d_xp_clusters; e.rows_members = c->d_xp_members; e.counts = c->d_xp_counts;
+  e.large_ws = c->d_xp_large_ws; e.large_counts = c->d_xp_large_counts; e.lay = lay;
+  e.large_frames = c->d_xp_large_frames; e.large_listed = c->d_xp_large_listed;
+  e.header = d->header; e.frame_info = d->frame_info; e.matches = d->matches; e.cap_matches = d->cap_matches;
+  e.clusters = clusters ? d->clusters_out : nullptr; e.cap_clusters = clusters ? d->cap_clusters : 0;
+  e.members = clusters ? d->members : nullptr; e.cap_members = clusters ? d->cap_members : 0;
+  if (max_large > 0) {
+    launch_export_plan(s, e);
+    F2LargeParams lp{p, c->d_xp_large_frames, c->d_xp_large_ws, lay, c->d_xp_large_listed};
+    lp.p.out_counts = c->d_xp_large_counts;
+    launch_f2_large(s, lp, max_large, 0, false);
+  }
+  launch_export_pack(s, e);
+  LMX_HIP(hipGetLastError());
+  // the slot is not reused before this, and the caller's stream goes on behind it
+  LMX_HIP(hipEventRecord(c->export_done[slot], s));
+  c->export_pending[slot] = true;
+  LMX_HIP(hipStreamWaitEvent(user, c->export_done[slot], 0));
+  return LMX_OK;
+  });
+}
+
 lmx_status lmx_ctx_export_raw(lmx_ctx* c, void* d_block, size_t capacity_records) {
   return lmx_ctx_export_raw_on(c, d_block, capacity_records, c ? (void*)c->stream : nullptr);
 }
@@ -668,6 +787,7 @@ lmx_status lmx_ctx_release(lmx_ctx* c) {
   LMX_HIP(hipSetDevice(c->device));
   const int slot = (c->head + c->n_slots - c->outstanding) % c->n_slots;
   LMX_HIP(hipEventSynchronize(c->done[slot]));
+  if (lmx_status xs = wait_exports(c, slot)) return xs;   // a released slot is never read by a still-running export
   c->outstanding -= 1;
   if (c->outstanding == 0) drain_profiling(c);
   // the counters lmx_ctx_stats reports, as collect leaves them: the slot's pinned mirror holds the published header once its event has

@@ -77,6 +77,18 @@ lmx_status sync_lanes(lmx_ctx* c) {
   if (c->copy_stream) LMX_HIP(hipStreamSynchronize(c->copy_stream));
   if (c->pre_stream) LMX_HIP(hipStreamSynchronize(c->pre_stream));
   for (int lane = 0; lane < c->n_lanes; ++lane) LMX_HIP(hipStreamSynchronize(c->lane_stream[lane]));
+  if (c->export_stream) {   // lmx_ctx_export_matches_on: its chain reads output slots and the side-car
+    LMX_HIP(hipStreamSynchronize(c->export_stream));
+    for (bool& pending : c->export_pending) pending = false;
+  }
+  return LMX_OK;
+}
+
+// Host-side wait for the exports that read output slot `slot` (lmx_ctx_export_matches_on records export_done[slot] behind each).
+lmx_status wait_exports(lmx_ctx* c, int slot) {
+  if (!c->export_pending[slot]) return LMX_OK;
+  LMX_HIP(hipEventSynchronize(c->export_done[slot]));
+  c->export_pending[slot] = false;
   return LMX_OK;
 }
 
@@ -359,6 +371,11 @@ void lmx_ctx_destroy(lmx_ctx* c) {
     if (c->lane_stream[lane]) { (void)hipStreamSynchronize(c->lane_stream[lane]); (void)hipStreamDestroy(c->lane_stream[lane]); }
   if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
   if (c->pre_stream) { (void)hipStreamSynchronize(c->pre_stream); (void)hipStreamDestroy(c->pre_stream); }
+  if (c->export_stream) { (void)hipStreamSynchronize(c->export_stream); (void)hipStreamDestroy(c->export_stream); }   // before any buffer it works on is freed
+  if (c->export_dst_ready) (void)hipEventDestroy(c->export_dst_ready);
+  for (hipEvent_t e : c->export_done)
+    if (e) (void)hipEventDestroy(e);
+  if (c->d_xp_large_ws) (void)hipFree(c->d_xp_large_ws);
   if (c->raw_dma_done) (void)hipEventDestroy(c->raw_dma_done);
   if (c->device_src_ready) (void)hipEventDestroy(c->device_src_ready);
   for (lmx_ctx::FrameSet& fs : c->sets) {
@@ -704,6 +721,7 @@ lmx_status ctx_drop_newest(lmx_ctx* c) {
   LMX_HIP(hipSetDevice(c->device));
   const int slot = (c->head + c->n_slots - 1) % c->n_slots;
   LMX_HIP(hipEventSynchronize(c->done[slot]));
+  if (lmx_status xs = wait_exports(c, slot)) return xs;
   c->head = slot;
   c->outstanding -= 1;
   if (c->outstanding == 0) drain_profiling(c);

@@ -5,7 +5,8 @@
 //   lmx_ctx.cpp      context create / destroy, the upload of those tables, uploads (frames, masks, raw camera frames; one builder of
 //                    row-band copy tasks for all of them), the hooks device groups use (lmx_group.cpp)
 //   lmx_enqueue.cpp  the per-batch kernel chain (plain, small-batch, hipGraph), lmx_ctx_enqueue, lmx_match / lmx_match_batch
-//   lmx_collect.cpp  read-back and finalisation (std::sort + std::unique), the device-side consumer chain, gather-block export / merge
+//   lmx_collect.cpp  read-back and finalisation (std::sort + std::unique), the device-side consumer chain, the export of final matches into
+//                    device memory (kernels: lmx_export.hip), gather-block export / merge
 //   lmx_cluster.cpp  the reference's voting / cluster / NMS chain on the host
 //   lmx_cache.cpp    bank fingerprint, binary bank files, the per-request caches (lmx_bank_load_yaml_cached, lmx_ctx_acquire)
 //   lmx_debug.cpp    introspection, per-kernel timing, test hooks
@@ -260,6 +261,23 @@ struct lmx_ctx {
   int32_t* d_f2l_frames = nullptr;               // [F] the listed frames
   uint32_t* d_f2l_counts = nullptr;              // [F][4]
   lmx_chain_stats chain_stats{};                 // of the last lmx_ctx_collect_clusters* call (lmx_ctx_chain_stats)
+  // lmx_ctx_export_matches_on: a chain of its own on export_stream, on buffers of its own in plain device memory (an export may still run
+  // when a collect_clusters* of another slot launches on f2_stream).  Nothing is allocated before the first export
+  hipStream_t export_stream = nullptr;
+  hipEvent_t export_dst_ready = nullptr;         // recorded on the caller's stream: the outputs are written behind what it holds
+  hipEvent_t export_done[kSlots] = {};           // recorded behind the last export that reads the slot; waited for before the slot is freed
+  bool export_pending[kSlots] = {};
+  uint8_t* d_xp_rows = nullptr;                  // [F][F2_MAX] matches | [F][F2_MAX] clusters | [F][F2_MAX] members | [F][4] counts | list, count word, [F][4] large counts
+  lmx_match_t* d_xp_matches = nullptr;           // views into d_xp_rows
+  lmx_cluster_t* d_xp_clusters = nullptr;
+  int32_t* d_xp_members = nullptr;
+  uint32_t* d_xp_counts = nullptr;
+  int32_t* d_xp_large_frames = nullptr;
+  uint32_t* d_xp_large_listed = nullptr;
+  uint32_t* d_xp_large_counts = nullptr;
+  uint8_t* d_xp_scratch = nullptr;               // [F][F2_MAX] x 32 bytes
+  uint8_t* d_xp_large_ws = nullptr;              // [xp_large_parts][f2_large_layout(false, false).bytes], grown on demand, never shrunk
+  int xp_large_parts = 0;
   // stats / profiling
   int64_t stat_cands = 0, stat_matches = 0;
   uint32_t profiling = 0;  // bitmask over kernel ids
@@ -306,6 +324,7 @@ void drain_profiling(lmx_ctx* c);
 void select_lane(lmx_ctx* c, int lane);   // points the context's working view (kp.fb, derived colour pyramid levels, candidate list) at one lane's buffers
 void select_set(lmx_ctx* c, int set);     // points the level-0 frame pointers at one frame set
 lmx_status sync_lanes(lmx_ctx* c);        // host-side wait for everything queued on every lane and on the copy stream
+lmx_status wait_exports(lmx_ctx* c, int slot);   // host-side wait for the lmx_ctx_export_matches_on calls that read output slot `slot`: before the slot is freed
 int upload_threads(const lmx_ctx* c);
 void store_modality(lmx_ctx* c, lmx_ctx::FrameSet& fs, int m, int n_frames, const lmx_image* sources);
 // lmx_cluster.cpp

@@ -545,6 +545,7 @@ __device__ __forceinline__ void f2_large(const F2LargeParams& lp) {
   __shared__ unsigned short s_gperm[F2L_GCAP], s_gsup[F2L_GCAP];
   __shared__ int s_n, s_nfinal, s_bad, s_valid, s_total, s_cbegin[F2_CLASSES + 1];
   const F2Params& p = lp.p;
+  if (lp.n_listed && blockIdx.x >= *lp.n_listed) return;   // a list built on the device: the grid is its capacity (the whole workgroup leaves)
   const int tid = threadIdx.x, frame = lp.frames[blockIdx.x];
   const F2LRows r = f2l_rows(lp.ws + (size_t)blockIdx.x * lp.lay.bytes, lp.lay);
   uint32_t* counts = p.out_counts + (size_t)blockIdx.x * 4;

@@ -332,8 +332,36 @@ struct F2LargeParams {
   const int32_t* frames;   // [grid] the frames to finish, device memory; workgroup i takes frames[i] and part i of the workspace
   uint8_t* ws;             // [grid][lay.bytes] device memory
   F2LargeLayout lay;
+  const uint32_t* n_listed = nullptr;   // device memory, optional: workgroups at or above *n_listed leave at once (a list built on the device,
+                                        // lmx_export.hip); null: the grid is exact
 };
 void launch_f2_large(hipStream_t s, const F2LargeParams& p, int n_listed, int mode, bool classes);
+
+// lmx_ctx_export_matches_on (lmx_export.hip; the arithmetic is lmx_export_pack.hpp): everything is device memory
+struct ExportParams {
+  const lmx_raw_match_t* recs;   // the slot's records and header, as F2Params
+  const uint32_t* hdr;
+  uint32_t cap;
+  int32_t n_frames, max_large;
+  // what the chain's kernels wrote: the export's rows and counts, the large-frame workspace (f2_large_layout(false, false)) and its counts
+  const lmx_match_t* rows_matches;       // [n_frames][F2_MAX]
+  const lmx_cluster_t* rows_clusters;
+  const int32_t* rows_members;
+  const uint32_t* counts;                // [n_frames][4]
+  const uint8_t* large_ws;               // [max_large][lay.bytes]
+  const uint32_t* large_counts;          // [max_large][4]
+  F2LargeLayout lay;
+  int32_t* large_frames;                 // [max_large] written by k_export_plan, with the count word
+  uint32_t* large_listed;
+  // the caller's arrays
+  uint32_t* header;                      // [16]
+  int32_t* frame_info;                   // [n_frames][8]
+  lmx_match_t* matches; uint64_t cap_matches;
+  lmx_cluster_t* clusters; uint64_t cap_clusters;
+  int32_t* members; uint64_t cap_members;
+};
+void launch_export_plan(hipStream_t s, const ExportParams& e);   // max_large > 0 only
+void launch_export_pack(hipStream_t s, const ExportParams& e);
 void launch_debug_block_sort_large(hipStream_t s, const float* sim, const int* tid, int n, int* perm, uint8_t* ws /* f2_large_layout(false, false).bytes */);
 
 // ---- depth check against a resident scene (lmx_verify.hip), for the scored consumer chain (lmx_collect.cpp, lmx_debug.cpp) --------------

@@ -113,6 +113,97 @@ def _device_stream(flat, stream):
     return 0
 
 
+EXPORT_HEADER_WORDS, EXPORT_INFO_WORDS = 16, 8
+EXPORT_INFO_FIELDS = ("match_begin", "match_count", "cluster_begin", "cluster_count", "member_begin", "member_count", "status", "raw_records")
+# frame_info's status and header[1]'s flags (include/lmx.h, lmx_ctx_export_matches_on)
+EXPORT_DELIVERED, EXPORT_UNFINISHED, EXPORT_RANGE, EXPORT_MATCHES_NO_FIT, EXPORT_CLUSTERS_NO_FIT, EXPORT_OVERFLOW = 0, 1, 2, 4, 8, 16
+EXPORT_FLAG_OVERFLOW, EXPORT_FLAG_UNFINISHED, EXPORT_FLAG_NO_FIT = 1, 2, 4
+
+
+def export_layout(n_frames, clusters=False, caps=(1 << 16, 4096, 1 << 16)):
+    """The device arrays lmx_ctx_export_matches_on fills, as Detector.export_matches allocates them: name -> {"shape", "dtype" (a numpy
+    dtype name, the torch dtype of the same name), "nbytes", "align" (of the address, the C ABI's rule), "cap" (elements the call may
+    write)}.  caps = (cap_matches, cap_clusters, cap_members); the cluster and member arrays exist with clusters=True only.  A capacity of 0
+    is allowed: the array keeps one element so that it has an address, and nothing is written to it.
+    ValueError: n_frames < 1, a negative capacity, or a capacity whose offsets would not fit frame_info's int32."""
+    caps = tuple(int(v) for v in caps)
+    if n_frames < 1:
+        raise ValueError("n_frames must be at least 1")
+    if len(caps) != 3 or min(caps) < 0 or max(caps) >= 1 << 31:
+        raise ValueError("caps = (cap_matches, cap_clusters, cap_members), each 0 .. 2^31 - 1")
+
+    def entry(shape, dtype, align, cap):
+        return {"shape": shape, "dtype": dtype, "nbytes": int(np.prod(shape)) * np.dtype(dtype).itemsize, "align": align, "cap": cap}
+    out = {"header": entry((EXPORT_HEADER_WORDS,), "int32", 4, EXPORT_HEADER_WORDS),
+           "frame_info": entry((int(n_frames), EXPORT_INFO_WORDS), "int32", 4, int(n_frames)),
+           "matches": entry((max(caps[0], 1), MATCH_DTYPE.itemsize // 4), "int32", 4, caps[0])}
+    if clusters:
+        out["clusters"] = entry((max(caps[1], 1), CLUSTER_DTYPE.itemsize), "uint8", 8, caps[1])
+        out["members"] = entry((max(caps[2], 1),), "int32", 4, caps[2])
+    return out
+
+
+class ExportedMatches:
+    """What Detector.export_matches leaves on the GPU (lmx_ctx_export_matches_on): torch tensors on the context's device, valid for work
+    queued on `stream` after the call --
+      header      int32 [16]      [0] n_frames, [1] flags, [2] matches, [3] clusters, [4] members (true totals), [5] candidates, [6] raw records
+      frame_info  int32 [F, 8]    EXPORT_INFO_FIELDS per frame; status 0 = delivered
+      matches     int32 [cap, 5]  x, y, the similarity's bits, template_id, class_index; `similarity` is column 2 as float32
+      clusters    uint8 [cap, 48] lmx_cluster_t records (CLUSTER_DTYPE); members int32 [cap]   (None without clusters=True)
+    Any other stream, or the host, synchronises with `stream` first; to_host() does."""
+
+    def __init__(self, n_frames, clusters, caps, stream, device):
+        import torch
+        self.n_frames, self.with_clusters, self.stream = n_frames, bool(clusters), stream
+        lay = export_layout(n_frames, clusters, caps)
+        with torch.cuda.stream(stream):     # the caching allocator hands out memory that is free on this stream
+            t = {k: torch.empty(v["shape"], dtype=getattr(torch, v["dtype"]), device="cuda:%d" % device) for k, v in lay.items()}
+        self._backing = t
+        self.caps = tuple(lay[k]["cap"] if k in lay else 0 for k in ("matches", "clusters", "members"))
+        self.header, self.frame_info = t["header"], t["frame_info"]
+        self.matches = t["matches"][:self.caps[0]]
+        self.clusters = t["clusters"][:self.caps[1]] if clusters else None
+        self.members = t["members"][:self.caps[2]] if clusters else None
+
+    @property
+    def similarity(self):
+        import torch
+        return self.matches[:, 2].view(torch.float32)
+
+    def clone(self):
+        """A copy made on `stream` (behind the export, in front of whatever writes these tensors next): what a pipeline keeps of a result
+        whose buffers the next export(out=...) reuses.  Nothing waits on the host."""
+        import torch
+        out = ExportedMatches.__new__(ExportedMatches)
+        out.n_frames, out.with_clusters, out.stream, out.caps = self.n_frames, self.with_clusters, self.stream, self.caps
+        with torch.cuda.stream(self.stream):
+            out._backing = {k: v.clone() for k, v in self._backing.items()}
+        t = out._backing
+        out.header, out.frame_info, out.matches = t["header"], t["frame_info"], t["matches"][:self.caps[0]]
+        out.clusters = t["clusters"][:self.caps[1]] if self.with_clusters else None
+        out.members = t["members"][:self.caps[2]] if self.with_clusters else None
+        return out
+
+    def to_host(self):
+        """Synchronises `stream` -> list per frame of (matches, clusters, members) in collect_clusters' dtypes (MATCH_DTYPE, CLUSTER_DTYPE
+        whose member_begin indexes `members`, the batch's flat int32 member array; both empty without clusters=True), or None for a frame
+        whose status is not 0 (not finished, or an array of its did not fit)."""
+        self.stream.synchronize()
+        info = self.frame_info.cpu().numpy()
+        n_m, n_c, n_mem = (int(v) for v in self.header[2:5].cpu().numpy())
+        m = np.ascontiguousarray(self.matches[:min(n_m, self.caps[0])].cpu().numpy()).view(MATCH_DTYPE).reshape(-1)
+        if self.with_clusters:
+            cl = np.ascontiguousarray(self.clusters[:min(n_c, self.caps[1])].cpu().numpy()).view(CLUSTER_DTYPE).reshape(-1)
+            mem = np.ascontiguousarray(self.members[:min(n_mem, self.caps[2])].cpu().numpy())
+        else:
+            cl, mem = np.zeros(0, CLUSTER_DTYPE), np.zeros(0, np.int32)
+        out = []
+        for f in range(self.n_frames):
+            mb, mc, cb, cc, _, _, status, _ = (int(v) for v in info[f])
+            out.append((m[mb:mb + mc].copy(), cl[cb:cb + cc].copy(), mem) if status == EXPORT_DELIVERED else None)
+        return out
+
+
 class PreparedBatch:
     """lmx_image descriptors of a batch of host frames, built once (the arrays are kept alive by this object)."""
 
@@ -393,7 +484,7 @@ class Detector:
             self.bank = bank.to_bank()
         else:
             raise TypeError("bank must be a TemplateBank or NativeBank")
-        self.width, self.height, self.max_batch = width, height, max_batch
+        self.width, self.height, self.max_batch, self.device = width, height, max_batch, int(device)
         # gray (LMX_CTX_GRAY): ColorGradient sources are uint8 HxW (a MONO8 frame) instead of HxWx3; matches equal those of the frame copied into B, G, R
         self.gray = bool(gray)
         desc = _lib.CtxDesc(device, width, height, max_batch, max_candidates, shard_rank, shard_world, stream,
@@ -677,6 +768,35 @@ class Detector:
     def export_raw_on(self, d_block_ptr, capacity_records, stream):
         """The same copy on `stream` (a raw hipStream_t), which first waits on the device for the most recent enqueue."""
         _lib.check(_lib.lib().lmx_ctx_export_raw_on(self.h, d_block_ptr, capacity_records, stream))
+
+    def export_matches(self, n_frames, clusters=False, oldest=False, max_large_frames=0, cap_matches=1 << 16, cap_clusters=4096, cap_members=1 << 16,
+                       stream=None, out=None):
+        """The final matches of an enqueue -- and with clusters=True the clusters and members of collect_clusters -- left in GPU memory
+        (lmx_ctx_export_matches_on) -> ExportedMatches.  The most recent enqueue, or with oldest=True the oldest outstanding one; it stays
+        outstanding (release() or a collect ends it).  max_large_frames: frames of 2049 .. 16384 raw records this call may finish (2.4 MB of
+        workspace each); the others get status 1 and can go through collect.  Nothing waits on the host: the results are valid for work
+        queued afterwards on `stream` (a torch stream or a raw hipStream_t; default: the current torch stream of the context's device).
+        out: an ExportedMatches of an earlier call with the same n_frames and clusters, written again in place of fresh tensors (its
+        stream is used unless `stream` is given); the capacities are then the smaller of the arguments' and its own."""
+        import torch
+        if stream is None:
+            stream = out.stream if out is not None else torch.cuda.current_stream(self.device)
+        elif not hasattr(stream, "cuda_stream"):
+            stream = torch.cuda.ExternalStream(int(stream), device=self.device)
+        if out is None:
+            out = ExportedMatches(n_frames, clusters, (cap_matches, cap_clusters, cap_members), stream, self.device)
+            caps = out.caps
+        else:
+            if out.n_frames != n_frames or out.with_clusters != bool(clusters):
+                raise ValueError("out was made for %d frames, clusters=%s" % (out.n_frames, out.with_clusters))
+            caps = tuple(min(int(a), b) for a, b in zip((cap_matches, cap_clusters, cap_members), out.caps))
+            out.stream = stream
+        t = out._backing
+        desc = _lib.ExportDesc(C.sizeof(_lib.ExportDesc), int(bool(oldest)), int(bool(clusters)), int(max_large_frames), t["header"].data_ptr(),
+                               t["frame_info"].data_ptr(), t["matches"].data_ptr(), caps[0], t["clusters"].data_ptr() if clusters else None, caps[1],
+                               t["members"].data_ptr() if clusters else None, caps[2])
+        _lib.check(_lib.lib().lmx_ctx_export_matches_on(self.h, n_frames, C.byref(desc), int(stream.cuda_stream)))
+        return out
 
     def release(self):
         """Drop the oldest outstanding enqueue without a read-back (its records were consumed on the device)."""

@@ -1,0 +1,140 @@
+// A complete caller of the device-side way out: frames that live in device memory go in (Detector::uploadDevice), the final matches and
+// clusters stay in device memory (Detector::exportMatches) for a next stage on the caller's stream -- here a copy back on that same stream,
+// with ONE synchronisation, of the stream.  The same enqueue then goes through lmx_ctx_collect_clusters, and both results are printed for
+// tests/test_gpu_export_cpp.py to compare.
+//   export_matches_main <templates.yml> <sidecar.f64> <width> <height> <n_frames> <frames_bgr.u8> <frames_depth.u16> <threshold> <max_large_frames>
+// sidecar.f64: per template {origin distance, rect x, y, w, h} as doubles; the frame files hold n_frames dense frames one after the other.
+#include <hip/hip_runtime_api.h>
+
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <iterator>
+#include <string>
+#include <vector>
+
+#include "lmx_linemod.hpp"
+
+template <typename T>
+static std::vector<T> read_file(const char* path) {
+  std::ifstream f(path, std::ios::binary);
+  if (!f) { std::fprintf(stderr, "cannot open %s\n", path); std::exit(1); }
+  std::vector<char> raw((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+  std::vector<T> out(raw.size() / sizeof(T));
+  std::memcpy(out.data(), raw.data(), out.size() * sizeof(T));
+  return out;
+}
+
+#define HIP_OK(expr)                                                                                          \
+  do {                                                                                                        \
+    const hipError_t e_ = (expr);                                                                             \
+    if (e_ != hipSuccess) { std::fprintf(stderr, "%s: %s\n", #expr, hipGetErrorString(e_)); std::exit(1); }   \
+  } while (0)
+
+template <typename T>
+static T* device_array(size_t n) {
+  void* p = nullptr;
+  HIP_OK(hipMalloc(&p, (n ? n : 1) * sizeof(T)));
+  return static_cast<T*>(p);
+}
+
+static void print_frame(const char* who, int f, const lmx_match_t* m, size_t nm, const lmx_cluster_t* c, size_t nc, const int32_t* members) {
+  std::printf("%s frame %d matches %zu clusters %zu\n", who, f, nm, nc);
+  for (size_t i = 0; i < nm; ++i) std::printf("%s m %d %d %.9g %d %d\n", who, m[i].x, m[i].y, m[i].similarity, m[i].template_id, m[i].class_index);
+  for (size_t k = 0; k < nc; ++k) {
+    std::printf("%s c %d %d %d rect %d %d %d %d score %.17g members", who, c[k].index[0], c[k].index[1], c[k].index[2], c[k].rect[0], c[k].rect[1], c[k].rect[2],
+                c[k].rect[3], c[k].score);
+    for (int32_t j = 0; j < c[k].member_count; ++j) std::printf(" %d", members[c[k].member_begin + j]);
+    std::printf("\n");
+  }
+}
+
+int main(int argc, char** argv) {
+  if (argc != 10) {
+    std::fprintf(stderr, "usage: export_matches_main templates.yml sidecar.f64 width height n_frames frames_bgr.u8 frames_depth.u16 threshold max_large_frames\n");
+    return 2;
+  }
+  try {
+    const int W = std::atoi(argv[3]), H = std::atoi(argv[4]), F = std::atoi(argv[5]);
+    const std::vector<double> side = read_file<double>(argv[2]);
+    const std::vector<uint8_t> bgr = read_file<uint8_t>(argv[6]);
+    const std::vector<uint16_t> depth = read_file<uint16_t>(argv[7]);
+    const size_t px = (size_t)W * H;
+    if (F < 1 || bgr.size() != px * 3 * F || depth.size() != px * F) { std::fprintf(stderr, "the frame files do not hold %d frames of %d x %d\n", F, W, H); return 2; }
+    std::shared_ptr<lmx::linemod::Detector> det = lmx::linemod::readLinemod(argv[1]);
+    det->setDevice(0, F, 1 << 17);
+
+    hipStream_t stream;
+    HIP_OK(hipSetDevice(0));
+    HIP_OK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    // the frames reach device memory on the caller's stream, as a decoder's or a renderer's would
+    uint8_t* d_bgr = device_array<uint8_t>(bgr.size());
+    uint16_t* d_depth = device_array<uint16_t>(depth.size());
+    HIP_OK(hipMemcpyAsync(d_bgr, bgr.data(), bgr.size(), hipMemcpyHostToDevice, stream));
+    HIP_OK(hipMemcpyAsync(d_depth, depth.data(), depth.size() * 2, hipMemcpyHostToDevice, stream));
+    std::vector<std::vector<lmx::linemod::Image> > frames;
+    for (int f = 0; f < F; ++f)
+      frames.push_back({lmx::linemod::Image{d_bgr + px * 3 * f, H, W, 3, 1, (size_t)W * 3}, lmx::linemod::Image{d_depth + px * f, H, W, 1, 2, (size_t)W * 2}});
+    det->uploadDevice(frames, nullptr, stream);
+
+    // the consumer chain's side-car, then the enqueue
+    lmx_ctx* const ctx = det->context();
+    const size_t n_templates = side.size() / 5;
+    std::vector<double> dists(n_templates);
+    std::vector<int32_t> rects(n_templates * 4);
+    for (size_t i = 0; i < n_templates; ++i) {
+      dists[i] = side[5 * i];
+      for (int k = 0; k < 4; ++k) rects[4 * i + k] = (int32_t)side[5 * i + 1 + k];
+    }
+    lmx_cluster_params pp;
+    pp.vote_row_col_step = 10; pp.renderer_radius_min = 0.5; pp.renderer_radius_step = 0.1; pp.cluster_size_thresh = 2;
+    lmx::linemod::check(lmx_ctx_set_cluster_sidecar(ctx, dists.data(), rects.data(), n_templates, &pp));
+    lmx::linemod::check(lmx_ctx_enqueue(ctx, F, (float)std::atof(argv[8]), nullptr, 0));
+
+    // the results stay on the device, behind `stream`
+    const size_t cap = 1 << 15;
+    lmx_export_desc desc;
+    std::memset(&desc, 0, sizeof(desc));
+    desc.struct_size = sizeof(desc);
+    desc.clusters = 1;
+    desc.max_large_frames = std::atoi(argv[9]);
+    desc.header = device_array<uint32_t>(16);
+    desc.frame_info = device_array<int32_t>((size_t)F * 8);
+    desc.matches = device_array<lmx_match_t>(cap); desc.cap_matches = cap;
+    desc.clusters_out = device_array<lmx_cluster_t>(cap); desc.cap_clusters = cap;
+    desc.members = device_array<int32_t>(cap); desc.cap_members = cap;
+    det->exportMatches(desc, stream);
+    // "the next stage": here the copy back, on the same stream; the one synchronisation of this program
+    uint32_t header[16];
+    std::vector<int32_t> info((size_t)F * 8);
+    std::vector<lmx_match_t> matches(cap);
+    std::vector<lmx_cluster_t> clusters(cap);
+    std::vector<int32_t> members(cap);
+    HIP_OK(hipMemcpyAsync(header, desc.header, sizeof(header), hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipMemcpyAsync(info.data(), desc.frame_info, info.size() * 4, hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipMemcpyAsync(matches.data(), desc.matches, cap * sizeof(lmx_match_t), hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipMemcpyAsync(clusters.data(), desc.clusters_out, cap * sizeof(lmx_cluster_t), hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipMemcpyAsync(members.data(), desc.members, cap * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipStreamSynchronize(stream));
+    std::printf("header frames %u flags %u matches %u clusters %u members %u\n", header[0], header[1], header[2], header[3], header[4]);
+    for (int f = 0; f < F; ++f) {
+      const int32_t* fi = info.data() + (size_t)f * 8;
+      std::printf("export frame %d status %d raw_records %d\n", f, fi[6], fi[7]);
+      if (fi[6] == 0) print_frame("export", f, matches.data() + fi[0], (size_t)fi[1], clusters.data() + fi[2], (size_t)fi[3], members.data());
+    }
+
+    // the same enqueue through the host path
+    std::vector<size_t> mo((size_t)F + 1), co((size_t)F + 1);
+    lmx::linemod::check(lmx_ctx_collect_clusters(ctx, F, matches.data(), cap, mo.data(), clusters.data(), cap, co.data(), members.data(), cap));
+    for (int f = 0; f < F; ++f) print_frame("collect", f, matches.data() + mo[f], mo[f + 1] - mo[f], clusters.data() + co[f], co[f + 1] - co[f], members.data());
+
+    for (void* p : {(void*)desc.header, (void*)desc.frame_info, (void*)desc.matches, (void*)desc.clusters_out, (void*)desc.members, (void*)d_bgr, (void*)d_depth})
+      HIP_OK(hipFree(p));
+    HIP_OK(hipStreamDestroy(stream));
+  } catch (const std::exception& e) {
+    std::fprintf(stderr, "error: %s\n", e.what());
+    return 1;
+  }
+  return 0;
+}
