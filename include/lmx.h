@@ -897,6 +897,20 @@ enum {
 };
 lmx_status lmx_ctx_debug_read(lmx_ctx* ctx, int32_t frame, int32_t what, int32_t level, int32_t modality, void* out,
                               size_t out_bytes);
+/* Test hook: an enqueue whose chain starts at the LABEL IMAGES instead of the uploaded frames.  labels[l * n_modalities + m] is a host array
+ * u8 [n_frames][H_l][W_l] (packed, H_l = height >> l, W_l = width >> l) that is copied as it is into the context's label image of (level l,
+ * modality m) on the enqueue's stream; then the spread / linearise launches of every level, scoring, refinement and the read-back run as
+ * lmx_ctx_enqueue (thresholds null: `threshold` for every class) or lmx_ctx_enqueue_thresholds (thresholds[k] for class index k, `threshold`
+ * not read) launch them for n_frames: one or two frames of a two-level bank take the fused spread kernel of the one-frame call where it
+ * exists, everything else goes level by level.  No quantiser, pyramid or mask kernel runs; the slot's header and candidate counters, which
+ * the first quantiser clears otherwise, are cleared by a memset in stream order.  Always eager, also on a LMX_CTX_HIPGRAPH context, and no
+ * upload is needed.  The slot accounting is an enqueue's: lmx_ctx_collect*, lmx_ctx_export_raw, lmx_ctx_release and lmx_ctx_stats follow as
+ * usual, and lmx_ctx_debug_read returns the label images and memories of the call.  Any byte is accepted as a label (the quantisers write
+ * 0 or one bit).  The arrays must stay valid until the enqueue has been collected or released.
+ * LMX_ERR_INVALID_ARG: n_labels != levels * modalities, a null entry, n_frames outside [1, max_batch], a thresholds array that
+ * lmx_ctx_enqueue_thresholds would refuse, or as many enqueues outstanding as the context has slots. */
+lmx_status lmx_ctx_debug_enqueue_labels(lmx_ctx* ctx, int32_t n_frames, const uint8_t* const* labels, int32_t n_labels, float threshold,
+                                        const float* thresholds, int32_t n_thresholds, const char* const* class_ids, int32_t n_class_ids);
 /* Test hook: the counters of the context's helper thread (the one-frame lmx_match / lmx_match_batch with host frames hands the rest of its
  * chain to it; csrc/lmx_launch_helper.hpp).  out = {jobs run, times the helper went to sleep, wake-ups sent}: jobs - wake-ups is about the
  * number of calls that found the helper still spinning.  All zero while the context has had no such call (it has no helper thread then) or

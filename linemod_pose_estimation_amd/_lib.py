@@ -32,7 +32,7 @@ SYMBOLS = [
     "lmx_debug_device_finalize_cluster_large_classes", "lmx_ctx_chain_stats",
     "lmx_ctx_enqueue_thresholds", "lmx_match_thresholds", "lmx_match_batch_thresholds", "lmx_match_masked_thresholds", "lmx_group_submit_thresholds",
     "lmx_bank_train_mesh_opts", "lmx_debug_train_extract", "lmx_debug_launch_helper_counters",
-    "lmx_ctx_export_matches_on",
+    "lmx_ctx_export_matches_on", "lmx_ctx_debug_enqueue_labels",
 ]
 
 (LMX_OK, LMX_ERR_INVALID_ARG, LMX_ERR_SHAPE, LMX_ERR_NO_DEVICE, LMX_ERR_HIP, LMX_ERR_OVERFLOW, LMX_ERR_IO,
@@ -342,6 +342,7 @@ def lib():
     L.lmx_debug_device_finalize_cluster_classes.argtypes = [C.c_int32, vp, C.c_size_t, C.c_int32, C.POINTER(ClassSidecar), C.c_int32, C.POINTER(ClassScore),
                                                             C.POINTER(Image), vp, vp, vp, vp, vp, vp, vp]
     L.lmx_ctx_debug_read.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_size_t]
+    L.lmx_ctx_debug_enqueue_labels.argtypes = [vp, C.c_int32, C.POINTER(vp), C.c_int32, C.c_float, f32p, C.c_int32, C.POINTER(C.c_char_p), C.c_int32]
     L.lmx_debug_launch_helper_counters.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.lmx_debug_orientation_labels.argtypes = [C.c_int32, vp, vp, C.c_size_t, vp]
     L.lmx_debug_depth_normal_bins.argtypes = [C.c_int32, vp, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, vp, vp]

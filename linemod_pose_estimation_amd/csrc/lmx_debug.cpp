@@ -95,6 +95,21 @@ lmx_status lmx_ctx_debug_read(lmx_ctx* c, int32_t frame, int32_t what, int32_t l
   return LMX_OK;
 }
 
+lmx_status lmx_ctx_debug_enqueue_labels(lmx_ctx* c, int32_t n_frames, const uint8_t* const* labels, int32_t n_labels, float threshold, const float* thresholds,
+                                        int32_t n_thresholds, const char* const* class_ids, int32_t n_class_ids) {
+  return lmx::guarded("lmx_ctx_debug_enqueue_labels", [&]() -> lmx_status {
+  if (!c) { set_error("lmx_ctx_debug_enqueue_labels: null context"); return LMX_ERR_INVALID_ARG; }
+  if (n_frames < 1 || n_frames > c->F) { set_error("lmx_ctx_debug_enqueue_labels: n_frames=%d outside [1,%d]", n_frames, c->F); return LMX_ERR_INVALID_ARG; }
+  if (!labels || n_labels != c->L * c->M) {
+    set_error("lmx_ctx_debug_enqueue_labels: %d label arrays for %d levels x %d modalities (labels[level * n_modalities + modality])", labels ? n_labels : 0, c->L, c->M);
+    return LMX_ERR_INVALID_ARG;
+  }
+  for (int i = 0; i < n_labels; ++i)
+    if (!labels[i]) { set_error("lmx_ctx_debug_enqueue_labels: label array %d (level %d, modality %d) is null", i, i / c->M, i % c->M); return LMX_ERR_INVALID_ARG; }
+  return ctx_enqueue_labels(c, n_frames, labels, threshold, thresholds, n_thresholds, class_ids, n_class_ids);
+  });
+}
+
 lmx_status lmx_debug_launch_helper_counters(lmx_ctx* c, uint64_t out[3]) {
   if (!c || !out) { set_error("lmx_debug_launch_helper_counters: null argument"); return LMX_ERR_INVALID_ARG; }
   out[0] = out[1] = out[2] = 0;   // no one-frame call yet: the context has no helper

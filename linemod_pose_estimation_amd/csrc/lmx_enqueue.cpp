@@ -135,6 +135,19 @@ static bool small_chain_ok(const lmx_ctx* c, int n_frames) {
   return !c->env.no_small_chain;   // A/B switch (LMX_NO_SMALL_CHAIN, read when the context was created)
 }
 
+// Spread + linearise of both levels behind the quantisers of the one- and two-frame chain: the fused kernel where this pair of T and these
+// widths have one, else level by level like issue_pre.  issue_small and the label hook (ctx_enqueue_labels) both launch through here.
+static lmx_status issue_small_spread(lmx_ctx* c, hipStream_t s, int32_t n_frames) {
+  bool fused;
+  {
+    ScopedKernel k(c, K_SPREAD_LINEARIZE);
+    fused = launch_small_spread(s, spread_batch(c, 0), c->kp.geom[0], spread_batch(c, 1), c->kp.geom[1], c->M, n_frames);
+  }
+  for (int l = 0; l < 2 && !fused; ++l) issue_spread_level(c, s, l, n_frames);
+  LMX_HIP(hipGetLastError());
+  return LMX_OK;
+}
+
 static lmx_status issue_small(lmx_ctx* c, int slot, int32_t n_frames, float threshold, hipStream_t s, lmx_ctx::FrameSet& fs, const lmx_image* sources,
                               const ClassThreshold* thr_tab) {
   c->cur_stream = s;
@@ -181,14 +194,8 @@ static lmx_status issue_small(lmx_ctx* c, int slot, int32_t n_frames, float thre
   };
   // spread of both levels, score, refine (+ read-back)
   auto launch_rest = [&]() -> lmx_status {
-    bool fused;
-    {
-      ScopedKernel k(c, K_SPREAD_LINEARIZE);
-      fused = launch_small_spread(s, spread_batch(c, 0), g0, spread_batch(c, 1), g1, c->M, n_frames);
-    }
-    for (int l = 0; l < 2 && !fused; ++l) issue_spread_level(c, s, l, n_frames);   // no fused kernel for this pair of T / these widths: level by level, like issue_pre
-    LMX_HIP(hipGetLastError());
-    return issue_post(c, slot, n_frames, threshold, s, thr_tab);
+    const lmx_status sst = issue_small_spread(c, s, n_frames);
+    return sst != LMX_OK ? sst : issue_post(c, slot, n_frames, threshold, s, thr_tab);
   };
 
   if (sources && !stream) { store_modality(c, fs, 0, n_frames, sources); lap(lmx_ctx::TM_STORE_COLOR); }
@@ -343,8 +350,12 @@ lmx_status lmx::ctx_prepare_graph(lmx_ctx* c, int n_frames, float threshold, boo
 
 // lmx_ctx_enqueue (thresholds null: `threshold` for every class) and lmx_ctx_enqueue_thresholds (thresholds[k] for class index k, checked by
 // the caller) are one code path: the per-class form only adds the slot's table and hands it down the chain.
-static lmx_status enqueue_chain(lmx_ctx* c, int32_t n_frames, float threshold, const float* thresholds, const char* const* class_ids, int32_t n_class_ids) {
-  const char* const who = thresholds ? "lmx_ctx_enqueue_thresholds" : "lmx_ctx_enqueue";
+// labels (lmx_ctx_debug_enqueue_labels, L * M host arrays, checked by the caller): the chain behind the quantisers on these label images -- they are
+// copied into kp.fb.quant on the lane's stream, the slot's counters are cleared by a memset instead of the first quantiser, and the spread
+// launches, scoring, refinement and read-back follow eagerly; no uploaded frame is read.
+static lmx_status enqueue_chain(lmx_ctx* c, int32_t n_frames, float threshold, const float* thresholds, const char* const* class_ids, int32_t n_class_ids,
+                                const uint8_t* const* labels = nullptr) {
+  const char* const who = labels ? "lmx_ctx_debug_enqueue_labels" : thresholds ? "lmx_ctx_enqueue_thresholds" : "lmx_ctx_enqueue";
   if (n_frames < 1 || n_frames > c->F) { set_error("n_frames=%d outside [1,%d]", n_frames, c->F); return LMX_ERR_INVALID_ARG; }
   std::shared_lock<std::shared_mutex> launch_lock(g_capture_mutex);
   LMX_HIP(hipSetDevice(c->device));
@@ -376,11 +387,11 @@ static lmx_status enqueue_chain(lmx_ctx* c, int32_t n_frames, float threshold, c
   // the chain starts behind the upload of the frame set it reads (queued on the copy stream), not behind other lanes' kernels
   const int set = c->cur_set;
   lmx_ctx::FrameSet& fset = c->sets[set];
-  if (n_frames > fset.n_uploaded) {
+  if (!labels && n_frames > fset.n_uploaded) {
     set_error("%s: n_frames=%d but the most recent upload holds %d frame(s); an enqueue reads the frames of the latest upload", who, n_frames, fset.n_uploaded);
     return LMX_ERR_INVALID_ARG;
   }
-  if (fset.h2d_recorded) LMX_HIP(hipStreamWaitEvent(sa, fset.h2d_done, 0));
+  if (!labels && fset.h2d_recorded) LMX_HIP(hipStreamWaitEvent(sa, fset.h2d_done, 0));
   // Per-class thresholds: one table per output slot, written on the lane's stream in front of the chain that reads it, so enqueues still
   // outstanding (other slots, other tables) are not disturbed and nothing waits on the host.  The slot is free, so the last copy out of its
   // pinned mirror has finished; a table that already holds these values is left alone.
@@ -402,7 +413,24 @@ static lmx_status enqueue_chain(lmx_ctx* c, int32_t n_frames, float threshold, c
   // Buffer hazards: a lane's intermediates are rewritten by every enqueue on it, in stream order; outputs are per slot.
   bool masked = false;   // masks are rare: the batch then takes the plain chain (no graph, no fused small-batch launches)
   for (int m = 0; m < c->M; ++m) masked = masked || fset.masked[m];
-  if ((c->desc.flags & LMX_CTX_HIPGRAPH) && c->profiling == 0 && !masked) {
+  if (labels) {
+    c->cur_stream = sa;
+    for (int l = 0; l < c->L; ++l)
+      for (int m = 0; m < c->M; ++m)
+        LMX_HIP(hipMemcpyAsync(c->kp.fb.quant[l][m], labels[l * c->M + m], (size_t)n_frames * c->kp.geom[l].H * c->kp.geom[l].W, hipMemcpyHostToDevice, sa));
+    // what clear_slot_counters clears from the chain's first quantiser: the 16-dword header and the stripe counters in front of it (the rest
+    // of the counters' lines is padding)
+    LMX_HIP(hipMemsetAsync(reinterpret_cast<uint8_t*>(stripes_of_header(reinterpret_cast<uint32_t*>(c->d_out))), 0, kStripeAreaBytes + 64, sa));
+    lmx_status st = LMX_OK;
+    if (small_chain_ok(c, n_frames)) {   // the batches issue_small takes: its spread launches
+      st = issue_small_spread(c, sa, n_frames);
+    } else {                             // everything else: issue_pre's, level by level
+      for (int l = 0; l < c->L; ++l) issue_spread_level(c, sa, l, n_frames);
+    }
+    LMX_HIP(hipGetLastError());
+    if (st == LMX_OK) st = issue_post(c, slot, n_frames, threshold, sa, thr_tab);
+    if (st != LMX_OK) return st;
+  } else if ((c->desc.flags & LMX_CTX_HIPGRAPH) && c->profiling == 0 && !masked) {
     // the whole per-batch chain (memset, kernels, read-back) as ONE graph launch; captured once per (slot, n_frames, threshold)
     hipGraphExec_t exec = nullptr;
     launch_lock.unlock();
@@ -433,7 +461,7 @@ static lmx_status enqueue_chain(lmx_ctx* c, int32_t n_frames, float threshold, c
     if (st == LMX_OK) st = issue_post(c, slot, n_frames, threshold, sa, thr_tab);
     if (st != LMX_OK) return st;
   }
-  fset.read_recorded[lane] = true;
+  if (!labels) fset.read_recorded[lane] = true;
   hipStream_t s = sa;
   LMX_HIP(hipEventRecord(c->done[slot], s));
   c->last_threshold = threshold;
@@ -449,6 +477,13 @@ static lmx_status check_thresholds(const char* who, const lmx_ctx* c, const floa
   for (int k = 0; k < n_thresholds; ++k)
     if (thresholds[k] != thresholds[k]) { set_error("%s: the threshold of class %d (\"%s\") is not a number", who, k, c->class_names[(size_t)k].c_str()); return LMX_ERR_INVALID_ARG; }
   return LMX_OK;
+}
+
+lmx_status lmx::ctx_enqueue_labels(lmx_ctx* c, int n_frames, const uint8_t* const* labels, float threshold, const float* thresholds, int n_thresholds,
+                                   const char* const* class_ids, int n_class_ids) {
+  if (thresholds)
+    if (const lmx_status st = check_thresholds("lmx_ctx_debug_enqueue_labels", c, thresholds, n_thresholds)) return st;
+  return enqueue_chain(c, n_frames, thresholds ? 0.f : threshold, thresholds, class_ids, n_class_ids, labels);
 }
 
 // The synchronous composite behind lmx_match_batch (thresholds null) and lmx_match_batch_thresholds

@@ -116,6 +116,9 @@ void ctx_stage_sources(lmx_ctx* c, CopyPool* pool, uint8_t* base, int n_frames, 
 lmx_status ctx_begin_staged_upload(lmx_ctx* c);                                    // host: the next set's previous transfer has left the staging area
 lmx_status ctx_finish_staged_upload(lmx_ctx* c, int n_frames, const uint8_t* pinned, int first_frame, int stride_frames);  // queue the DMAs out of `pinned`, make the set current
 lmx_status ctx_prepare_graph(lmx_ctx* c, int n_frames, float threshold, bool per_class = false);   // LMX_CTX_HIPGRAPH: capture the next enqueue's chain now if it is not cached (per_class: the chain of lmx_ctx_enqueue_thresholds)
+// lmx_ctx_debug_enqueue_labels behind its argument checks: an enqueue whose chain starts at the label images (lmx_enqueue.cpp, enqueue_chain)
+lmx_status ctx_enqueue_labels(lmx_ctx* c, int n_frames, const uint8_t* const* labels, float threshold, const float* thresholds, int n_thresholds,
+                              const char* const* class_ids, int n_class_ids);
 lmx_status ctx_drop_newest(lmx_ctx* c);                                            // undo the most recent enqueue (waits for it, frees its slot)
 
 // Coarse candidate written by k_score_coarse, consumed by k_refine.

@@ -1471,7 +1471,8 @@ constexpr int RF_UNROLL = 8;  // gathers in flight per wave and batch; a wave's 
 
 // Response of orientation o to a spread byte v, without a table: with M_k[o] = the set of source bits whose response is >= k
 // (nested: M_4 in M_3 in M_2 in M_1, read off SIMILARITY_LUT, asymmetric high nibble included),
-//   max(LUT_lo[o][v & 15], LUT_hi[o][v >> 4]) = [v & M_1] + [v & M_2] + [v & M_3] + [v & M_4]     (verified for all 8 x 256 cases).
+//   max(LUT_lo[o][v & 15], LUT_hi[o][v >> 4]) = [v & M_1] + [v & M_2] + [v & M_3] + [v & M_4]     (verified for all 8 x 256 cases:
+//   tests/test_gpu_label_match.py, family r_fine of tests/label_cases.py).
 // Byte k-1 of c_resp_masks[o] is M_k[o].  On four packed spread bytes each indicator is the classic SWAR "byte is non-zero".
 __constant__ uint32_t c_resp_masks[8] = {0x0103070fu, 0x02070f1fu, 0x040e1f3fu, 0x081c3e7fu, 0x10387cfeu, 0x2070f8fdu, 0x40e0f1fbu, 0x80c1e3f7u};
 

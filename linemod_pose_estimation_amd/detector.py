@@ -842,6 +842,35 @@ class Detector:
         _lib.check(_lib.lib().lmx_ctx_debug_read(self.h, frame, _lib.LMX_DBG_PYRAMID_BGR, level, modality, out.ctypes.data, out.nbytes))
         return out
 
+    def debug_enqueue_labels(self, labels, threshold=None, thresholds=None, class_ids=()):
+        """Test hook (lmx_ctx_debug_enqueue_labels): an enqueue whose chain starts at the label images.  labels[level][modality] is a uint8
+        array [n_frames, H_l, W_l] (level_shape) that becomes the context's label image as it is; spread, scoring, refinement and read-back
+        then run as enqueue(n_frames, threshold) -- or, with `thresholds` (a mapping class id -> threshold), as the per-class enqueue --
+        launches them.  No upload is needed; collect / collect_clusters* / stats follow as after enqueue."""
+        L, M = len(self.bank.T), len(self.bank.modalities)
+        if len(labels) != L or any(len(p) != M for p in labels):
+            raise ValueError("labels: %d levels x %d modalities expected" % (L, M))
+        if (threshold is None) == (thresholds is None):
+            raise ValueError("give either threshold (a float) or thresholds (a mapping class id -> float)")
+        n_frames = int(np.shape(labels[0][0])[0]) if np.ndim(labels[0][0]) == 3 else 0
+        flat = []
+        for l, per_level in enumerate(labels):
+            for a in per_level:
+                a = np.ascontiguousarray(a, np.uint8)
+                if a.shape != (n_frames,) + tuple(self.level_shape(l)):
+                    raise ValueError("labels of level %d: shape %s, expected %s" % (l, a.shape, (n_frames,) + tuple(self.level_shape(l))))
+                flat.append(a)
+        ptrs = (C.c_void_p * len(flat))(*[a.ctypes.data for a in flat])
+        # read by the stream's copies: kept while the call can still be outstanding
+        self._label_keep = (getattr(self, "_label_keep", None) or []) + [flat]
+        del self._label_keep[:-max(1, self.max_outstanding)]
+        if thresholds is not None:
+            thr, cids, ncid = class_thresholds(self._class_ids, thresholds, class_ids)
+            _lib.check(_lib.lib().lmx_ctx_debug_enqueue_labels(self.h, n_frames, ptrs, len(flat), C.c_float(0.0), thr, len(thr), cids, ncid))
+            return
+        cids, ncid = self._cids(class_ids)
+        _lib.check(_lib.lib().lmx_ctx_debug_enqueue_labels(self.h, n_frames, ptrs, len(flat), C.c_float(threshold), None, 0, cids, ncid))
+
     def stats(self):
         a, b = C.c_int64(), C.c_int64()
         _lib.check(_lib.lib().lmx_ctx_stats(self.h, C.byref(a), C.byref(b)))

@@ -593,6 +593,46 @@ void match_class(Detector& det, const std::vector<LinearMemories>& lms /* [l*M+m
   }
 }
 
+// The part of the pyramid behind quantize(): labels of (level l, modality m) -> spread -> response maps -> linear memories, kept with the
+// labels as the intermediates of the last match.  q is swapped into det.last_quantized.
+void memories_from_labels(Detector& det, int l, int m, int H, int W, std::vector<uchar>& q) {
+  const int M = (int)det.modalities.size();
+  const int T = det.T_at_level[l];
+  std::vector<uchar> spr((size_t)H * W), maps((size_t)8 * H * W);
+  spread(q.data(), H, W, T, spr.data());
+  response_maps(spr.data(), H, W, maps.data());
+  LinearMemories& lm = det.last_lm[(size_t)l * M + m];
+  lm.T = T; lm.Wc = W / T; lm.Hc = H / T;
+  for (int o = 0; o < 8; ++o) {
+    lm.mem[o].resize((size_t)H * W);
+    linearize(maps.data() + (size_t)o * H * W, H, W, T, lm.mem[o].data());
+  }
+  det.last_quantized[(size_t)l * M + m].swap(q);
+}
+
+// The same from caller-supplied labels for every (level, modality): labels[l * M + m] is a packed [H0 >> l][W0 >> l] image.  Any byte is
+// taken as it is -- spread() ORs bytes, whatever they hold.
+int build_pyramid_from_labels(Detector& det, const uchar* const* labels, int H0, int W0) {
+  const int M = (int)det.modalities.size();
+  const int L = (int)det.T_at_level.size();
+  det.last_quantized.assign((size_t)L * M, std::vector<uchar>());
+  det.last_lm.assign((size_t)L * M, LinearMemories());
+  det.last_sizes.clear();
+  int H = H0, W = W0;
+  for (int l = 0; l < L; ++l) {
+    int T = det.T_at_level[l];
+    if (l > 0) { H /= 2; W /= 2; }
+    if (H % T != 0 || W % T != 0) return -3;      // linearize CV_Assert
+    if (((long)H * W) % 16 != 0) return -4;       // computeResponseMaps CV_Assert
+    for (int m = 0; m < M; ++m) {
+      std::vector<uchar> q(labels[(size_t)l * M + m], labels[(size_t)l * M + m] + (size_t)H * W);
+      memories_from_labels(det, l, m, H, W, q);
+    }
+    det.last_sizes.push_back(std::make_pair(W, H));
+  }
+  return 0;
+}
+
 // Build quantized images + linear memories for all levels/modalities (A.10 first half)
 // `masks` (or NULL): Detector::match's last argument, one packed level-0 mask per modality (empty = no mask).  Upstream keeps the mask in
 // the QuantizedPyramid: quantize() copies the level's labels THROUGH it (`angle.copyTo(dst, mask)` / `normal.copyTo(dst, mask)`), pyrDown()
@@ -659,21 +699,14 @@ int build_pyramid(Detector& det, const Source* sources, int n_sources, const std
         for (size_t i = 0; i < q.size(); ++i)
           if (!cur_mask[m][i]) q[i] = 0;   // quantize(): dst = zeros; labels.copyTo(dst, mask)
       }
-      std::vector<uchar> spr((size_t)H * W), maps((size_t)8 * H * W);
-      spread(q.data(), H, W, T, spr.data());
-      response_maps(spr.data(), H, W, maps.data());
-      LinearMemories& lm = det.last_lm[(size_t)l * M + m];
-      lm.T = T; lm.Wc = W / T; lm.Hc = H / T;
-      for (int o = 0; o < 8; ++o) {
-        lm.mem[o].resize((size_t)H * W);
-        linearize(maps.data() + (size_t)o * H * W, H, W, T, lm.mem[o].data());
-      }
-      det.last_quantized[(size_t)l * M + m].swap(q);
+      memories_from_labels(det, l, m, H, W, q);
     }
     det.last_sizes.push_back(std::make_pair(W, H));
   }
   return 0;
 }
+
+long match_memories(Detector& det, float threshold, const char* const* class_ids, int n_class_ids);
 
 }  // namespace
 
@@ -835,6 +868,24 @@ long lmo_detector_match_masked(void* h, const void* const* src_data, const int* 
       }
   int rc = build_pyramid(det, sources.data(), n_sources, mask_data ? &masks : NULL);
   if (rc != 0) return rc;
+  return match_memories(det, threshold, class_ids, n_class_ids);
+}
+// Detector::match from the label images on: labels[l * M + m] = packed u8 [rows >> l][cols >> l] of (level l, modality m); everything behind
+// quantize() runs as in lmo_detector_match, and the intermediates / raw matches / candidate count of "the last match" are this call's.
+long lmo_detector_match_labels(void* h, const unsigned char* const* labels, int n_labels, int rows, int cols, float threshold,
+                               const char* const* class_ids, int n_class_ids) {
+  Detector& det = *(Detector*)h;
+  det.last_matches.clear();
+  det.stat_candidates = 0;
+  if (n_labels != (int)(det.modalities.size() * det.T_at_level.size())) return -1;
+  int rc = build_pyramid_from_labels(det, labels, rows, cols);
+  if (rc != 0) return rc;
+  return match_memories(det, threshold, class_ids, n_class_ids);
+}
+}  // extern "C"
+namespace {
+// A.10 second half: matchClass per class on det.last_lm, then sort + unique
+long match_memories(Detector& det, float threshold, const char* const* class_ids, int n_class_ids) {
   det.class_names.clear();
   for (std::map<std::string, std::vector<TemplatePyramid> >::const_iterator it = det.class_templates.begin();
        it != det.class_templates.end(); ++it)
@@ -860,6 +911,8 @@ long lmo_detector_match_masked(void* h, const void* const* src_data, const int* 
   matches.erase(std::unique(matches.begin(), matches.end()), matches.end());
   return (long)matches.size();
 }
+}  // namespace
+extern "C" {
 
 long lmo_detector_get_matches(void* h, lmo_match_t* out, long cap) {
   Detector& det = *(Detector*)h;

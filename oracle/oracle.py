@@ -445,6 +445,29 @@ class OracleDetector:
             L.lmo_detector_get_matches(self.h, _p(out), rc)
         return out
 
+    def match_labels(self, labels, threshold, class_ids=()):
+        """match() from the label images on: labels[level][modality] is a uint8 (H_l, W_l) array (H_l = H_0 >> level) that stands where
+        quantize() would have put the one-hot labels; spread, response maps, linear memories and matching follow as in match().
+        last_raw() / last_candidates() / quantized() / linear_memory() then refer to this call."""
+        L = lib()
+        flat = [np.ascontiguousarray(a, np.uint8) for per_level in labels for a in per_level]
+        H, W = flat[0].shape
+        M = len(labels[0])
+        for l, per_level in enumerate(labels):
+            assert len(per_level) == M and all(np.shape(a) == (H >> l, W >> l) for a in per_level), "labels of level %d" % l
+        data = (C.c_void_p * len(flat))(*[a.ctypes.data for a in flat])
+        cids = (C.c_char_p * max(1, len(class_ids)))(*[c.encode() for c in class_ids])
+        L.lmo_detector_match_labels.restype = C.c_long
+        L.lmo_detector_match_labels.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int]
+        rc = L.lmo_detector_match_labels(self.h, data, len(flat), H, W, C.c_float(threshold), cids, len(class_ids))
+        if rc < 0:
+            raise ValueError({-1: "labels: one image per level and modality", -3: "image size not a multiple of T at some level",
+                              -4: "rows*cols not a multiple of 16"}.get(rc, "error %d" % rc))
+        out = np.zeros(rc, MATCH_DTYPE)
+        if rc:
+            L.lmo_detector_get_matches(self.h, _p(out), rc)
+        return out
+
     def last_raw(self):
         """Matches of the last match() in upstream insertion order, before sort/unique (lmx_raw_match_t layout)."""
         n = lib().lmo_detector_get_raw(self.h, None, 0)

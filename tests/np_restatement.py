@@ -341,19 +341,16 @@ def raw_threshold(nf, thr):
     return int(F32(2 * nf) + (F32(thr) / F32(100.0)) * F32(2 * nf) + F32(0.5))
 
 
-def match(bank, sources, threshold):
-    """Whole Detector::match for a TemplateBank; returns pre-sort matches as tuples
-    (x, y, similarity(float32), class_id, template_id) in upstream insertion order."""
+def quantize_pyramid(bank, sources):
+    """The label images of Detector::match, [level][modality] -> uint8 (H_l, W_l): quantize() and pyrDown() of every modality."""
     L, M = len(bank.T), len(bank.modalities)
-    lms, sizes = [], []
     color = [None] * M
     quant = [None] * M
     H, W = sources[0].shape[:2]
+    out = []
     for l in range(L):
-        T = bank.T[l]
         if l > 0:
             H, W = H // 2, W // 2
-        lv = []
         for m, mod in enumerate(bank.modalities):
             if mod["type"] == "ColorGradient":
                 color[m] = np.ascontiguousarray(sources[m]) if l == 0 else pyrdown(color[m])
@@ -363,13 +360,62 @@ def match(bank, sources, threshold):
                                       getattr(bank, "normal_lut", None))[0] \
                     if l == 0 else quant[m][::2, ::2][:H, :W].copy()
             quant[m] = q
-            r = response_maps(spread(q, T))
-            lv.append(np.stack([linearize(r[o], T) for o in range(8)], 0))
+        out.append(list(quant))
+    return out
+
+
+def match(bank, sources, threshold):
+    """Whole Detector::match for a TemplateBank; returns pre-sort matches as tuples
+    (x, y, similarity(float32), class_id, template_id) in upstream insertion order."""
+    return match_labels(bank, quantize_pyramid(bank, sources), threshold)
+
+
+def _local_sums(flat8, n, Wc, size_wh, T, feats, cx, cy):
+    """similarity_local for all features at once: flat8 = one modality's [8, n] memories read flat (zero past the end)."""
+    w, h = size_wh
+    if not len(feats):
+        return np.zeros((16, 16), np.int64)
+    f = np.asarray(feats, np.int64).reshape(-1, 3)
+    x, y = f[:, 0] + (int(cx / T) - 8) * T, f[:, 1] + (int(cy / T) - 8) * T    # int(): C++ truncation toward zero
+    ok = (x >= 0) & (y >= 0) & (x < w) & (y < h)
+    x, y, lab = x[ok], y[ok], f[ok, 2]
+    base = ((y % T) * T + x % T) * n + (y // T) * Wc + x // T
+    idx = base[:, None, None] + np.arange(16)[None, :, None] * Wc + np.arange(16)[None, None, :]
+    inside = (idx >= 0) & (idx < T * T * n)
+    v = np.where(inside, flat8[lab[:, None, None], np.clip(idx, 0, T * T * n - 1)], 0)
+    return v.sum(0).astype(np.int64)
+
+
+def match_labels(bank, labels, threshold, class_ids=(), mutant=None, lut=None, stats=None):
+    """Detector::match from the label images on: labels[level][modality] uint8 (H_l, W_l).  threshold: a float, or a mapping class id ->
+    float (classes it lacks are not matched).  -> pre-sort matches (x, y, similarity(float32), class_id, template_id) in upstream insertion
+    order; stats (a dict) gets "candidates".  lut: the response table instead of the rule's.  mutant: a deliberately wrong variant a test
+    must be able to tell from the real thing -- "coarse_ge" (>= at the coarse test), "last_max" (the last maximum of a patch), "refine_le"
+    (<= at the refinement test), "u8_wrap" (the sum over the modalities wraps at 256)."""
+    L, M = len(bank.T), len(bank.modalities)
+    H0, W0 = np.shape(labels[0][0])
+    sizes = [(W0 >> l, H0 >> l) for l in range(L)]
+    lms = []
+    for l in range(L):
+        lv = []
+        for m in range(M):
+            r = response_maps(spread(np.asarray(labels[l][m], np.uint8), bank.T[l]), lut)
+            lv.append(np.stack([linearize(r[o], bank.T[l]) for o in range(8)], 0))
         lms.append(lv)
-        sizes.append((W, H))
     out = []
+    n_cand = 0
     per = L * M
-    for cid, templates, feats in sorted(bank.classes, key=lambda c: c[0]):
+    order = sorted(bank.classes, key=lambda c: c[0])
+    if len(class_ids):
+        by_id = {c[0]: c for c in order}
+        order = [by_id[c] for c in class_ids if c in by_id]
+    for cid, templates, feats in order:
+        if isinstance(threshold, dict):
+            if cid not in threshold:
+                continue
+            thr = threshold[cid]
+        else:
+            thr = threshold
         for tid in range(templates.shape[0] // per):
             tp = [templates[tid * per + k] for k in range(per)]
             fl = [[tuple(int(v) for v in f) for f in feats[t[3]:t[3] + t[4]]] for t in tp]
@@ -382,42 +428,44 @@ def match(bank, sources, threshold):
                 s, _ = similarity(lms[-1][m], sizes[-1], Tl, (tp[k][0], tp[k][1]), fl[k])
                 tot += s
                 nf += len(fl[k])
-            rt = raw_threshold(nf, threshold)
-            cands = []
+            if mutant == "u8_wrap":
+                tot &= 255
+            rt = raw_threshold(nf, thr)
             off = Tl // 2 + (Tl % 2 - 1)
-            for r in range(tot.shape[0]):
-                for c in range(tot.shape[1]):
-                    if tot[r, c] > rt:
-                        sim = F32(F32(int(tot[r, c])) * F32(100.0) / F32(4 * nf)) + F32(0.5)
-                        cands.append([c * Tl + off, r * Tl + off, F32(sim)])
+            rr, cc = np.nonzero(tot >= rt if mutant == "coarse_ge" else tot > rt)
+            cands = [[int(c) * Tl + off, int(r) * Tl + off, F32(F32(int(tot[r, c])) * F32(100.0) / F32(4 * nf)) + F32(0.5)] for r, c in zip(rr, cc)]
+            n_cand += len(cands)
             for l in range(L - 2, -1, -1):
                 T = bank.T[l]
                 w, h = sizes[l]
+                n = (w // T) * (h // T)
+                flat = [lms[l][m].reshape(8, -1) for m in range(M)]
                 border, off = 8 * T, T // 2 + (T % 2 - 1)
                 max_x, max_y = w - tp[l * M][0] - border, h - tp[l * M][1] - border
+                nf2 = sum(len(fl[l * M + m]) for m in range(M))
                 keep = []
                 for x, y, _ in cands:
                     x, y = 2 * x + 1, 2 * y + 1
                     x, y = max(x, border), max(y, border)
                     x, y = min(x, max_x), min(y, max_y)
                     tot2 = np.zeros((16, 16), np.int64)
-                    nf2 = 0
                     for m in range(M):
-                        k = l * M + m
-                        tot2 += similarity_local(lms[l][m], sizes[l], T, fl[k], x, y)
-                        nf2 += len(fl[k])
-                    best, br, bc = 0, -1, -1
-                    for r in range(16):
-                        for c in range(16):
-                            if tot2[r, c] > best:
-                                best, br, bc = int(tot2[r, c]), r, c
+                        # one modality's patch wraps at 256 like upstream's uchar, the sum over modalities is a ushort
+                        tot2 += _local_sums(flat[m], n, w // T, sizes[l], T, fl[l * M + m], x, y) & 255
+                    best = int(tot2.max())
+                    br, bc = -1, -1
+                    if best > 0:
+                        hits = np.flatnonzero(tot2.reshape(-1) == best)
+                        br, bc = divmod(int(hits[-1] if mutant == "last_max" else hits[0]), 16)   # first maximum in row-major order
                     nx = (int(x / T) - 8 + bc) * T + off
                     ny = (int(y / T) - 8 + br) * T + off
                     sim = F32(F32(best) * F32(100.0) / F32(4 * nf2))
-                    if not sim < F32(threshold):
+                    if not (sim <= F32(thr) if mutant == "refine_le" else sim < F32(thr)):
                         keep.append([nx, ny, sim])
                 cands = keep
             out += [(x, y, F32(s), cid, tid) for x, y, s in cands]
+    if stats is not None:
+        stats["candidates"] = n_cand
     return out
 
 

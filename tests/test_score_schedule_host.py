@@ -136,8 +136,9 @@ def group_rows(t, g, flat, cells):
     return np.stack(out), consumed_end
 
 
-def segmented_pass(rows, pos, consumed_end, nf, raw_thr, stats):
-    """The kernel's pass over one template's `pos` placements -> boolean [pos]: the placements it would append."""
+def segmented_pass(rows, pos, consumed_end, nf, raw_thr, stats, need_offset=0):
+    """The kernel's pass over one template's `pos` placements -> boolean [pos]: the placements it would append.  need_offset = 1 is the
+    bound one too strict (tests/test_label_cases_host.py: the mutant that must lose a candidate)."""
     chunk_pos = CHUNK_LANES * LANE_POS
     passing = np.zeros(pos, bool)
     for c0 in range(0, pos, chunk_pos):
@@ -150,7 +151,7 @@ def segmented_pass(rows, pos, consumed_end, nf, raw_thr, stats):
         for b, end in enumerate(consumed_end):
             for g0, ng in ([(0, R.SB_GROUPS)] if b == 0 else zip(np.cumsum((0,) + SEGMENTS[:-1]), SEGMENTS)):
                 S[:n8] += rows[5 * b + g0:5 * b + g0 + ng, c0:c0 + n8].sum(0)
-                need = raw_thr + 1 - 4 * (nf - (end - 3 * (R.SB_GROUPS - g0 - ng)))
+                need = raw_thr + 1 - 4 * (nf - (end - 3 * (R.SB_GROUPS - g0 - ng))) + need_offset
                 if need <= 0:
                     continue
                 # dead lanes keep accumulating and are never revived; the placements of the last lane behind the template's last one
