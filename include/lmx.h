@@ -434,6 +434,8 @@ typedef struct lmx_export_desc {
   size_t cap_members;
 } lmx_export_desc;
 lmx_status lmx_ctx_export_matches_on(lmx_ctx* ctx, int32_t n_frames, const lmx_export_desc* desc, void* stream);
+/* The depth-scored, normal-scored and per-class clusters leave the same way: lmx_ctx_export_clusters_on, declared behind the types it
+ * needs (lmx_depth_templates, lmx_depth_diff_t, lmx_normal_diff_t), after lmx_depth_templates_append. */
 /* Copy `bytes` (multiple of 16, both pointers 16-byte aligned) on `stream` with a kernel instead of a DMA engine; `dst` may
  * be pinned host memory.  For small latency-sensitive read-backs in a pipelined caller: hipMemcpyAsync(DeviceToHost) was
  * measured to block the submitting thread for milliseconds now and then when copies of several streams are in flight. */
@@ -873,10 +875,80 @@ lmx_status lmx_ctx_collect_clusters_classes(lmx_ctx* ctx, int32_t n_frames, cons
  * device table is uploaded again on next use, its crop normals are recomputed on next need if normals are enabled, and a scene uploaded
  * to dst is forgotten: lmx_depth_templates_upload_scene comes before the next scored call. */
 lmx_status lmx_depth_templates_append(lmx_depth_templates* dst, lmx_depth_templates* src);
+/* ---- all six cluster chains left in device memory ---------------------------------------------------------------------------------------
+ * lmx_ctx_export_matches_on with `clusters` for every chain lmx_ctx_collect_clusters* offers: classes (0 the un-classed side-car of
+ * lmx_ctx_set_cluster_sidecar, 1 the per-class side-cars of lmx_ctx_set_cluster_sidecar_class) times score (0 mean similarity, 1 the depth
+ * score of lmx_ctx_collect_clusters_depth, 2 depth + normal of lmx_ctx_collect_clusters_depth_normal).  For every frame with status 0 the
+ * matches, diffs, ndiffs, clusters (score included), cluster_class and members are bit for bit, and in order, what the matching
+ * lmx_ctx_collect_clusters* call returns for the same enqueue; classes 0, score 0 equals lmx_ctx_export_matches_on with clusters = 1,
+ * header and frame_info included.  Layout, offsets, statuses, header words, capacities of 0 and the ordering rules are those documented
+ * there; in addition:
+ *   - diffs / ndiffs lie parallel to `matches` and share its capacity and fit decision (a frame's range is written iff its whole match
+ *     range fits); cluster_class lies parallel to `clusters_out` and shares the clusters' (and members') decision;
+ *   - frames the device chain hands back have status 1 or 2 and counts 0 as there: more than 16384 records, none of max_large_frames
+ *     left, a ring outside the packed range, and for classes = 1 a template_id outside its class's side-car.  The enqueue stays
+ *     outstanding, so lmx_ctx_collect_clusters_* can still finish them on the host;
+ *   - with a score the export stream also waits for the scene's event of `templates` (lmx_depth_templates_upload_scene* after the
+ *     enqueue, as for the collect calls), computes the scene's normals first if score = 2 and nobody has (k_normal_map_frames), and walks
+ *     the crops of the slot's raw records with k_walk_records_dev: a fixed grid of persistent workgroups that take the record count from
+ *     the slot's header on the device.  The object's mutex is held during the call, not until the kernels end: the object records an
+ *     event behind the walk instead.  lmx_depth_templates_upload_scene_device makes its copies wait for that event on the device;
+ *     lmx_depth_templates_upload_scene, lmx_depth_diff_matches / lmx_normal_diff_matches (when they stage frames), _enable_normals,
+ *     _append (both objects) and _free wait for it on the host before they change what the walk reads;
+ *   - memory: the first scored call allocates one lmx_depth_diff_t per record the slot can hold (max_batch x max_candidates: 16 B each,
+ *     16 MB for 64 frames at the default of 16384 per frame -- the count is not known on the host) and rows of [max_batch][2048] x 48 B;
+ *     the first with score = 2 the same again for lmx_normal_diff_t.  A large frame's workspace part is 2.46 MB, 2.72 MB with score 1, 2.98 MB with score 2;
+ *   - the first classed scored call, and one whose class_base differs from the previous call's, uploads class_base (a host wait for the
+ *     context's earlier exports; no other call waits).
+ * Refused before anything is queued, enqueue and context staying usable: everything lmx_ctx_export_matches_on refuses (exactly this
+ * struct's size is accepted); everything the matching lmx_ctx_collect_clusters* call refuses -- no side-car(s), templates of another
+ * device, a template count or class_base that does not match the side-car(s), score 2 before enable_normals, no scene or one whose
+ * frame count or size is not the enqueue's (LMX_ERR_INVALID_ARG), a no_value that is not a number; score outside 0 .. 2 or classes
+ * outside 0 .. 1; a null clusters_out or members, a null templates with a score, a null diffs with score >= 1, a null ndiffs with
+ * score 2, a null cluster_class or (with a score) class_base with classes; an output that is not plain device memory of the context's
+ * device or not aligned to its element (8 bytes for lmx_cluster_t, lmx_depth_diff_t and lmx_normal_diff_t, 4 otherwise).
+ * lmx_ctx_chain_stats is not touched: which path a frame took is known on the device alone (frame_info's status, and raw_records > 2048). */
+typedef struct lmx_export_clusters_desc {
+  uint32_t struct_size;        /* sizeof(lmx_export_clusters_desc) */
+  int32_t oldest;              /* as lmx_export_desc */
+  int32_t max_large_frames;    /* as lmx_export_desc */
+  int32_t classes;             /* 0: the un-classed chain; 1: the per-class chain */
+  int32_t score;               /* 0: mean similarity; 1: depth; 2: depth + normal */
+  int32_t class_index;         /* classes 0 with a score: as lmx_ctx_collect_clusters_depth takes it (-1: every class) */
+  int32_t n_classes;           /* classes 1 with a score: as lmx_class_score */
+  int32_t reserved;            /* 0 */
+  lmx_depth_templates* templates;   /* score >= 1 */
+  const int32_t* class_base;   /* classes 1 with a score: [n_classes + 1], host memory, as lmx_class_score */
+  double no_value;             /* score >= 1 */
+  uint32_t* header;            /* [16] */
+  int32_t* frame_info;         /* [n_frames][8] */
+  lmx_match_t* matches;
+  size_t cap_matches;
+  lmx_depth_diff_t* diffs;     /* score >= 1: parallel to matches */
+  lmx_normal_diff_t* ndiffs;   /* score == 2: parallel to matches */
+  lmx_cluster_t* clusters_out;
+  size_t cap_clusters;
+  int32_t* cluster_class;      /* classes == 1: parallel to clusters_out */
+  int32_t* members;
+  size_t cap_members;
+} lmx_export_clusters_desc;
+lmx_status lmx_ctx_export_clusters_on(lmx_ctx* ctx, int32_t n_frames, const lmx_export_clusters_desc* desc, void* stream);
+/* Test hook: k_walk_records_dev alone, on a slot the caller builds -- a header that says {n_candidates, header_count}, `records` behind it,
+ * list capacity `cap`, a grid of grid_workgroups (1 .. 65536) -- against the scene `templates` holds.  class_base NULL: the un-classed
+ * predicate with class_index; else the classed one (n_classes + 1 entries ending at the object's template count).  diffs[n_records] and,
+ * for both terms, ndiffs[n_records] (NULL: the depth term alone) go to the device as the caller filled them and come back as the kernel
+ * left them: entries at or above header_count, and every entry when header_count or n_candidates exceeds cap, keep the caller's bytes.
+ * LMX_ERR_INVALID_ARG when a header that did not overflow counts more records than were passed.
+ * lmx_debug_depth_walk_grid: the grid lmx_ctx_export_clusters_on launches for this object from now on (0: the default, a multiple of the
+ * device's compute units) -- for the measurement in profiles/export_clusters.txt. */
+lmx_status lmx_debug_depth_walk_records(lmx_depth_templates* templates, const lmx_raw_match_t* records, size_t n_records, uint32_t header_count,
+                                        uint32_t n_candidates, uint32_t cap, int32_t grid_workgroups, int32_t class_index,
+                                        const int32_t* class_base, int32_t n_classes, lmx_depth_diff_t* diffs, lmx_normal_diff_t* ndiffs);
+lmx_status lmx_debug_depth_walk_grid(lmx_depth_templates* templates, int32_t workgroups);
 /* Device time of the object's kernels that run per call: with profiling on, a pair of events surrounds each launch; kernel_time waits for
  * the launches in flight and returns the sum of their times and their number since profiling was switched on.  Off (the default) no
  * event is created or recorded. */
-enum { LMX_DT_K_NORMAL_MAP_FRAMES = 0, LMX_DT_K_VERIFY_DIFF_RECORDS = 1, LMX_DT_K_VERIFY_DIFF = 2, LMX_DT_K_DEPTH_DIFF_RECORDS = 3 };
+enum { LMX_DT_K_NORMAL_MAP_FRAMES = 0, LMX_DT_K_VERIFY_DIFF_RECORDS = 1, LMX_DT_K_VERIFY_DIFF = 2, LMX_DT_K_DEPTH_DIFF_RECORDS = 3, LMX_DT_K_WALK_RECORDS_DEV = 4 };
 lmx_status lmx_depth_templates_set_profiling(lmx_depth_templates* templates, int32_t on);
 lmx_status lmx_depth_templates_kernel_time(lmx_depth_templates* templates, int32_t kernel, double* total_ms, int64_t* launches);
 /* Test hook: the normals of frame `frame` of the uploaded scene as the device holds them (computed now if no call has needed them yet). */

@@ -302,6 +302,15 @@ class Detector {
     check(lmx_ctx_export_matches_on(ctx_, n_frames > 0 ? n_frames : uploaded_frames_, &desc, stream));
   }
 
+  // exportMatches for every cluster chain (lmx_ctx_export_clusters_on): desc.classes picks the un-classed or the per-class side-cars,
+  // desc.score mean similarity, the depth score or depth + normal against desc.templates (DepthTemplates::handle(), whose
+  // uploadScene / uploadSceneDevice followed the enqueue); diffs, ndiffs and cluster_class arrive next to the matches and clusters.
+  // Stream, frame count and the enqueue's fate as for exportMatches; desc.struct_size is the caller's to set.
+  void exportClusters(const lmx_export_clusters_desc& desc, void* stream = nullptr, int32_t n_frames = 0) {
+    if (!ctx_) throw Exception(LMX_ERR_INVALID_ARG, "exportClusters: no context, nothing was enqueued");
+    check(lmx_ctx_export_clusters_on(ctx_, n_frames > 0 ? n_frames : uploaded_frames_, &desc, stream));
+  }
+
   lmx_bank* bank() const { return bank_; }
   lmx_ctx* context() const { return ctx_; }
   // Which path completed the frames of the context's last lmx_ctx_collect_clusters* call, collectClustersClasses included

@@ -12,3 +12,4 @@ from .detector import NORMAL_DIFF_DTYPE, normal_values, normal_angle_table  # no
 from .detector import cluster_matches_classes  # noqa: F401
 from .detector import device_images  # noqa: F401
 from .detector import ExportedMatches, export_layout  # noqa: F401
+from .detector import ExportedClusters, export_clusters_layout  # noqa: F401

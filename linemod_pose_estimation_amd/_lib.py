@@ -33,6 +33,7 @@ SYMBOLS = [
     "lmx_ctx_enqueue_thresholds", "lmx_match_thresholds", "lmx_match_batch_thresholds", "lmx_match_masked_thresholds", "lmx_group_submit_thresholds",
     "lmx_bank_train_mesh_opts", "lmx_debug_train_extract", "lmx_debug_launch_helper_counters",
     "lmx_ctx_export_matches_on", "lmx_ctx_debug_enqueue_labels",
+    "lmx_ctx_export_clusters_on", "lmx_debug_depth_walk_records", "lmx_debug_depth_walk_grid",
 ]
 
 (LMX_OK, LMX_ERR_INVALID_ARG, LMX_ERR_SHAPE, LMX_ERR_NO_DEVICE, LMX_ERR_HIP, LMX_ERR_OVERFLOW, LMX_ERR_IO,
@@ -93,6 +94,14 @@ class ExportDesc(C.Structure):     # lmx_export_desc
     _fields_ = [("struct_size", C.c_uint32), ("oldest", C.c_int32), ("clusters", C.c_int32), ("max_large_frames", C.c_int32),
                 ("header", C.c_void_p), ("frame_info", C.c_void_p), ("matches", C.c_void_p), ("cap_matches", C.c_size_t),
                 ("clusters_out", C.c_void_p), ("cap_clusters", C.c_size_t), ("members", C.c_void_p), ("cap_members", C.c_size_t)]
+
+
+class ExportClustersDesc(C.Structure):     # lmx_export_clusters_desc
+    _fields_ = [("struct_size", C.c_uint32), ("oldest", C.c_int32), ("max_large_frames", C.c_int32), ("classes", C.c_int32), ("score", C.c_int32),
+                ("class_index", C.c_int32), ("n_classes", C.c_int32), ("reserved", C.c_int32), ("templates", C.c_void_p), ("class_base", C.c_void_p),
+                ("no_value", C.c_double), ("header", C.c_void_p), ("frame_info", C.c_void_p), ("matches", C.c_void_p), ("cap_matches", C.c_size_t),
+                ("diffs", C.c_void_p), ("ndiffs", C.c_void_p), ("clusters_out", C.c_void_p), ("cap_clusters", C.c_size_t), ("cluster_class", C.c_void_p),
+                ("members", C.c_void_p), ("cap_members", C.c_size_t)]
 
 
 class RendererParams(C.Structure):
@@ -287,6 +296,9 @@ def lib():
     L.lmx_ctx_export_raw.argtypes = [vp, vp, C.c_size_t]
     L.lmx_ctx_export_raw_on.argtypes = [vp, vp, C.c_size_t, vp]
     L.lmx_ctx_export_matches_on.argtypes = [vp, C.c_int32, C.POINTER(ExportDesc), vp]
+    L.lmx_ctx_export_clusters_on.argtypes = [vp, C.c_int32, C.POINTER(ExportClustersDesc), vp]
+    L.lmx_debug_depth_walk_records.argtypes = [vp, vp, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, vp, C.c_int32, vp, vp]
+    L.lmx_debug_depth_walk_grid.argtypes = [vp, C.c_int32]
     L.lmx_ctx_release.argtypes = [vp]
     L.lmx_ctx_max_outstanding.argtypes = [vp]
     L.lmx_stream_copy.argtypes = [vp, vp, C.c_size_t, vp]

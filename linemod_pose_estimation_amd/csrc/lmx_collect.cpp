@@ -1,6 +1,6 @@
 // liblmx.so, behind the kernel chain: read-back of an output slot and the host finalisation (restore upstream insertion order, then the
 // very std::sort / std::unique Detector::match applies), the device-side consumer chain (lmx_ctx_collect_clusters), its
-// form that leaves the results in the caller's device memory (lmx_ctx_export_matches_on), and the multi-GPU plumbing on one context's
+// forms that leave the results in the caller's device memory (lmx_ctx_export_matches_on, lmx_ctx_export_clusters_on), and the multi-GPU plumbing on one context's
 // side: gather-block export, copies by kernel, the host merge of gathered blocks.
 
 #include <algorithm>
@@ -283,6 +283,44 @@ struct DepthScore {
   lmx_normal_diff_t* ndiffs; // normal only: parallel to the caller's matches; may be null
 };
 
+// The refusals every cluster chain shares, collect and export (lmx_ctx_export_clusters_on) alike.  The side-car(s) of the chosen chain:
+static lmx_status check_chain_sidecar(const char* what, const lmx_ctx* c, bool classes) {
+  if (classes) {
+    bool any = false;
+    for (const lmx_ctx::ClassSidecar& k : c->f2_class) any = any || !k.dists.empty();
+    if (!any) { set_error("%s: call lmx_ctx_set_cluster_sidecar_class first", what); return LMX_ERR_INVALID_ARG; }
+  } else if (!c->f2_sidecar) { set_error("%s: call lmx_ctx_set_cluster_sidecar first", what); return LMX_ERR_INVALID_ARG; }
+  return LMX_OK;
+}
+
+// ... and what a score needs (depth null: nothing): the templates against the context and the side-car(s), the normals, the scene against
+// the enqueue of n_frames frames.  The caller holds the templates' mutex.
+static lmx_status check_chain_score(const char* what, const lmx_ctx* c, int32_t n_frames, const DepthScore* depth, const ClassChain* cls) {
+  if (!depth) return LMX_OK;
+  const DepthSceneInfo sc = depth_templates_scene(depth->templates);
+  if (sc.device != c->device) { set_error("%s: the templates live on device %d, the context on device %d", what, sc.device, c->device); return LMX_ERR_INVALID_ARG; }
+  if (cls) {   // the joined object holds exactly the classes' side-cars, one class after the other
+    const int32_t* cb = cls->class_base;
+    if (!cb || cls->n_classes < 1 || cls->n_classes > F2_CLASSES) { set_error("%s: class_base must hold n_classes + 1 entries, n_classes 1 .. %d", what, F2_CLASSES); return LMX_ERR_INVALID_ARG; }
+    if (cb[0] != 0) { set_error("%s: class_base[0] = %d, not 0", what, cb[0]); return LMX_ERR_INVALID_ARG; }
+    for (int k = 0; k < F2_CLASSES; ++k) {
+      const size_t have = c->f2_class[k].dists.size();
+      if (k >= cls->n_classes) {
+        if (have) { set_error("%s: class %d has a side-car of %zu templates but class_base ends at class %d", what, k, have, cls->n_classes - 1); return LMX_ERR_INVALID_ARG; }
+      } else if (cb[k + 1] < cb[k] || (size_t)(cb[k + 1] - cb[k]) != have) {
+        set_error("%s: class %d: class_base gives it templates %d .. %d but its side-car holds %zu templates", what, k, cb[k], cb[k + 1], have);
+        return LMX_ERR_INVALID_ARG;
+      }
+    }
+    if (cb[cls->n_classes] != sc.count) { set_error("%s: class_base ends at %d but the object holds %d depth templates", what, cb[cls->n_classes], sc.count); return LMX_ERR_INVALID_ARG; }
+  } else if ((size_t)sc.count != c->f2_templates) { set_error("%s: %d depth templates but the side-car holds %zu templates", what, sc.count, c->f2_templates); return LMX_ERR_INVALID_ARG; }
+  if (depth->normal && !sc.normals) { set_error("%s: call lmx_depth_templates_enable_normals first", what); return LMX_ERR_INVALID_ARG; }
+  if (sc.n_frames < 1) { set_error("%s: no scene uploaded: call lmx_depth_templates_upload_scene first", what); return LMX_ERR_INVALID_ARG; }
+  if (sc.n_frames != n_frames) { set_error("%s: the uploaded scene holds %d frames, the enqueue had %d", what, sc.n_frames, n_frames); return LMX_ERR_INVALID_ARG; }
+  if (sc.W != c->desc.width || sc.H != c->desc.height) { set_error("%s: the uploaded scene is %d x %d, the context's frames are %d x %d", what, sc.W, sc.H, c->desc.width, c->desc.height); return LMX_ERR_INVALID_ARG; }
+  return LMX_OK;
+}
+
 // Room for one result of `elem` bytes per raw record of the slot being collected (and, with elem 1, for the large-frame kernel's workspace).
 // Nothing reads the old buffer: every call ends synchronised.
 static lmx_status grow_rec_diffs(void** d, size_t* cap, size_t n, size_t elem) {
@@ -300,37 +338,11 @@ static lmx_status grow_rec_diffs(void** d, size_t* cap, size_t n, size_t elem) {
 static lmx_status collect_clusters_impl(const char* what, lmx_ctx* c, int32_t n_frames, const DepthScore* depth, const ClassChain* cls, lmx_match_t* matches, size_t cap_matches,
                                         size_t* match_offsets, lmx_cluster_t* clusters, size_t cap_clusters, size_t* cluster_offsets, int32_t* members,
                                         size_t cap_members) {
-  if (cls) {
-    bool any = false;
-    for (const lmx_ctx::ClassSidecar& k : c->f2_class) any = any || !k.dists.empty();
-    if (!any) { set_error("%s: call lmx_ctx_set_cluster_sidecar_class first", what); return LMX_ERR_INVALID_ARG; }
-  } else if (!c->f2_sidecar) { set_error("%s: call lmx_ctx_set_cluster_sidecar first", what); return LMX_ERR_INVALID_ARG; }
+  if (lmx_status st = check_chain_sidecar(what, c, cls != nullptr)) return st;
   if (c->outstanding < 1) { set_error("%s: nothing enqueued", what); return LMX_ERR_INVALID_ARG; }
   const int slot = (c->head + c->n_slots - c->outstanding) % c->n_slots;  // oldest outstanding enqueue
   if (n_frames != c->slot_frames[slot]) { set_error("%s: n_frames=%d but the enqueue had %d", what, n_frames, c->slot_frames[slot]); return LMX_ERR_INVALID_ARG; }
-  if (depth) {   // every refusal comes before the enqueue is consumed: it stays outstanding
-    const DepthSceneInfo sc = depth_templates_scene(depth->templates);
-    if (sc.device != c->device) { set_error("%s: the templates live on device %d, the context on device %d", what, sc.device, c->device); return LMX_ERR_INVALID_ARG; }
-    if (cls) {   // the joined object holds exactly the classes' side-cars, one class after the other
-      const int32_t* cb = cls->class_base;
-      if (!cb || cls->n_classes < 1 || cls->n_classes > F2_CLASSES) { set_error("%s: class_base must hold n_classes + 1 entries, n_classes 1 .. %d", what, F2_CLASSES); return LMX_ERR_INVALID_ARG; }
-      if (cb[0] != 0) { set_error("%s: class_base[0] = %d, not 0", what, cb[0]); return LMX_ERR_INVALID_ARG; }
-      for (int k = 0; k < F2_CLASSES; ++k) {
-        const size_t have = c->f2_class[k].dists.size();
-        if (k >= cls->n_classes) {
-          if (have) { set_error("%s: class %d has a side-car of %zu templates but class_base ends at class %d", what, k, have, cls->n_classes - 1); return LMX_ERR_INVALID_ARG; }
-        } else if (cb[k + 1] < cb[k] || (size_t)(cb[k + 1] - cb[k]) != have) {
-          set_error("%s: class %d: class_base gives it templates %d .. %d but its side-car holds %zu templates", what, k, cb[k], cb[k + 1], have);
-          return LMX_ERR_INVALID_ARG;
-        }
-      }
-      if (cb[cls->n_classes] != sc.count) { set_error("%s: class_base ends at %d but the object holds %d depth templates", what, cb[cls->n_classes], sc.count); return LMX_ERR_INVALID_ARG; }
-    } else if ((size_t)sc.count != c->f2_templates) { set_error("%s: %d depth templates but the side-car holds %zu templates", what, sc.count, c->f2_templates); return LMX_ERR_INVALID_ARG; }
-    if (depth->normal && !sc.normals) { set_error("%s: call lmx_depth_templates_enable_normals first", what); return LMX_ERR_INVALID_ARG; }
-    if (sc.n_frames < 1) { set_error("%s: no scene uploaded: call lmx_depth_templates_upload_scene first", what); return LMX_ERR_INVALID_ARG; }
-    if (sc.n_frames != n_frames) { set_error("%s: the uploaded scene holds %d frames, the enqueue had %d", what, sc.n_frames, n_frames); return LMX_ERR_INVALID_ARG; }
-    if (sc.W != c->desc.width || sc.H != c->desc.height) { set_error("%s: the uploaded scene is %d x %d, the context's frames are %d x %d", what, sc.W, sc.H, c->desc.width, c->desc.height); return LMX_ERR_INVALID_ARG; }
-  }
+  if (lmx_status st = check_chain_score(what, c, n_frames, depth, cls)) return st;   // every refusal comes before the enqueue is consumed: it stays outstanding
   LMX_HIP(hipSetDevice(c->device));
   for (int f = 0; f <= n_frames; ++f) match_offsets[f] = cluster_offsets[f] = 0;
   const size_t F = (size_t)c->F;
@@ -659,54 +671,88 @@ lmx_status lmx_ctx_export_oldest_on(lmx_ctx* c, void* d_block, size_t capacity_r
   return LMX_OK;
 }
 
-// One output of lmx_ctx_export_matches_on: plain device memory of the context's device, aligned to its element.
-static lmx_status check_export_output(const lmx_ctx* c, const char* name, const void* p, size_t align) {
-  if ((uintptr_t)p & (align - 1)) { set_error("lmx_ctx_export_matches_on: %s must be aligned to %zu bytes", name, align); return LMX_ERR_INVALID_ARG; }
+// One output of an export: plain device memory of the context's device, aligned to its element.
+static lmx_status check_export_output(const char* what, const lmx_ctx* c, const char* name, const void* p, size_t align) {
+  if ((uintptr_t)p & (align - 1)) { set_error("%s: %s must be aligned to %zu bytes", what, name, align); return LMX_ERR_INVALID_ARG; }
   hipPointerAttribute_t attr;
   if (hipPointerGetAttributes(&attr, p) != hipSuccess) {   // memory the runtime has never seen
     (void)hipGetLastError();
-    set_error("lmx_ctx_export_matches_on: %s is not device memory", name);
+    set_error("%s: %s is not device memory", what, name);
     return LMX_ERR_INVALID_ARG;
   }
   if (attr.type != hipMemoryTypeDevice || attr.device != c->device) {
-    set_error("lmx_ctx_export_matches_on: %s is %s; the outputs are plain device memory of device %d", name,
+    set_error("%s: %s is %s; the outputs are plain device memory of device %d", what, name,
               attr.type == hipMemoryTypeDevice ? "memory of another device" : "pageable, pinned, managed or other host memory", c->device);
     return LMX_ERR_INVALID_ARG;
   }
   return LMX_OK;
 }
 
-// The final matches (and clusters) of an enqueue into the caller's device arrays (include/lmx.h; kernels: lmx_export.hip).  Every refusal
+// What lmx_ctx_export_matches_on and lmx_ctx_export_clusters_on ask of export_impl: the fields of their structs.
+struct ExportRequest {
+  int32_t oldest, max_large_frames;
+  bool clusters, classes;
+  int score;                       // 0 mean similarity, 1 depth, 2 depth + normal
+  lmx_depth_templates* templates;  // with a score
+  int32_t class_index;
+  const int32_t* class_base;
+  int32_t n_classes;
+  double no_value;
+  uint32_t* header;
+  int32_t* frame_info;
+  lmx_match_t* matches; size_t cap_matches;
+  lmx_depth_diff_t* diffs;
+  lmx_normal_diff_t* ndiffs;
+  lmx_cluster_t* clusters_out; size_t cap_clusters;
+  int32_t* cluster_class;
+  int32_t* members; size_t cap_members;
+};
+
+// The body of both exports (include/lmx.h; kernels: lmx_export.hip, and for a score k_walk_records_dev of lmx_verify.hip).  Every refusal
 // comes before anything is queued; nothing below waits on the host for the device except an allocation's first use.
-lmx_status lmx_ctx_export_matches_on(lmx_ctx* c, int32_t n_frames, const lmx_export_desc* d, void* stream) {
-  return lmx::guarded("lmx_ctx_export_matches_on", [&]() -> lmx_status {
-  const char* const what = "lmx_ctx_export_matches_on";
-  if (!c || !d) { set_error("%s: null argument", what); return LMX_ERR_INVALID_ARG; }
-  if (d->struct_size != sizeof(lmx_export_desc)) { set_error("%s: struct_size %u, not %zu", what, d->struct_size, sizeof(lmx_export_desc)); return LMX_ERR_INVALID_ARG; }
+static lmx_status export_impl(const char* what, lmx_ctx* c, int32_t n_frames, const ExportRequest& q, void* stream) {
   if (!c->sets[0].h_stage) { set_error("%s: this context is a member of a device group", what); return LMX_ERR_INVALID_ARG; }
   if (c->outstanding < 1) { set_error("%s: nothing enqueued", what); return LMX_ERR_INVALID_ARG; }
-  const int slot = d->oldest ? (c->head + c->n_slots - c->outstanding) % c->n_slots : (c->head + c->n_slots - 1) % c->n_slots;
+  const int slot = q.oldest ? (c->head + c->n_slots - c->outstanding) % c->n_slots : (c->head + c->n_slots - 1) % c->n_slots;
   if (n_frames != c->slot_frames[slot]) { set_error("%s: n_frames=%d but the enqueue had %d", what, n_frames, c->slot_frames[slot]); return LMX_ERR_INVALID_ARG; }
-  if (!d->header || !d->frame_info || !d->matches) { set_error("%s: header, frame_info and matches must not be null", what); return LMX_ERR_INVALID_ARG; }
-  const bool clusters = d->clusters != 0;
-  if (clusters && !c->f2_sidecar) { set_error("%s: clusters: call lmx_ctx_set_cluster_sidecar first", what); return LMX_ERR_INVALID_ARG; }
-  if (clusters && (!d->clusters_out || !d->members)) { set_error("%s: clusters: clusters_out and members must not be null", what); return LMX_ERR_INVALID_ARG; }
-  if (d->max_large_frames < 0) { set_error("%s: max_large_frames %d is negative", what, d->max_large_frames); return LMX_ERR_INVALID_ARG; }
+  if (!q.header || !q.frame_info || !q.matches) { set_error("%s: header, frame_info and matches must not be null", what); return LMX_ERR_INVALID_ARG; }
+  const bool clusters = q.clusters, scored = q.score >= 1, normal = q.score == 2;
+  if (clusters)
+    if (lmx_status st = check_chain_sidecar(what, c, q.classes)) return st;
+  if (clusters && (!q.clusters_out || !q.members)) { set_error("%s: clusters: clusters_out and members must not be null", what); return LMX_ERR_INVALID_ARG; }
+  if (q.classes && !q.cluster_class) { set_error("%s: classes: cluster_class must not be null", what); return LMX_ERR_INVALID_ARG; }
+  if (scored && (!q.templates || !q.diffs)) { set_error("%s: score %d: templates and diffs must not be null", what, q.score); return LMX_ERR_INVALID_ARG; }
+  if (normal && !q.ndiffs) { set_error("%s: score 2: ndiffs must not be null", what); return LMX_ERR_INVALID_ARG; }
+  if (scored && q.no_value != q.no_value) { set_error("%s: no_value is not a number (the score order would be undefined)", what); return LMX_ERR_INVALID_ARG; }
+  if (q.max_large_frames < 0) { set_error("%s: max_large_frames %d is negative", what, q.max_large_frames); return LMX_ERR_INVALID_ARG; }
+  std::unique_lock<std::mutex> lk;   // held during the call: the scene and the object's buffers stay put until the walk is queued
+  if (scored) {
+    lk = std::unique_lock<std::mutex>(depth_templates_mutex(q.templates));
+    const DepthScore depth{q.templates, q.class_index, q.no_value, nullptr, normal, nullptr};
+    const ClassChain cls{q.class_base, q.n_classes, nullptr};
+    if (lmx_status st = check_chain_score(what, c, n_frames, &depth, q.classes ? &cls : nullptr)) return st;
+  }
   LMX_HIP(hipSetDevice(c->device));
   hipStream_t user = static_cast<hipStream_t>(stream);
   hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
   if (user && hipStreamIsCapturing(user, &capturing) != hipSuccess) { (void)hipGetLastError(); set_error("%s: invalid stream", what); return LMX_ERR_INVALID_ARG; }
   if (capturing != hipStreamCaptureStatusNone) { set_error("%s: the stream is being captured into a graph", what); return LMX_ERR_INVALID_ARG; }
-  if (lmx_status st = check_export_output(c, "header", d->header, 4)) return st;
-  if (lmx_status st = check_export_output(c, "frame_info", d->frame_info, 4)) return st;
-  if (lmx_status st = check_export_output(c, "matches", d->matches, 4)) return st;
+  if (lmx_status st = check_export_output(what, c, "header", q.header, 4)) return st;
+  if (lmx_status st = check_export_output(what, c, "frame_info", q.frame_info, 4)) return st;
+  if (lmx_status st = check_export_output(what, c, "matches", q.matches, 4)) return st;
   if (clusters) {
-    if (lmx_status st = check_export_output(c, "clusters_out", d->clusters_out, 8)) return st;
-    if (lmx_status st = check_export_output(c, "members", d->members, 4)) return st;
+    if (lmx_status st = check_export_output(what, c, "clusters_out", q.clusters_out, 8)) return st;
+    if (lmx_status st = check_export_output(what, c, "members", q.members, 4)) return st;
   }
+  if (scored)
+    if (lmx_status st = check_export_output(what, c, "diffs", q.diffs, 8)) return st;
+  if (normal)
+    if (lmx_status st = check_export_output(what, c, "ndiffs", q.ndiffs, 8)) return st;
+  if (q.classes)
+    if (lmx_status st = check_export_output(what, c, "cluster_class", q.cluster_class, 4)) return st;
   // the export's own buffers, on first use
   const size_t F = (size_t)c->F;
-  const F2LargeLayout lay = f2_large_layout(false, false);
+  const F2LargeLayout lay = f2_large_layout(scored, normal);
   if (!c->d_xp_rows) {
     const size_t off_clusters = F * F2_MAX * sizeof(lmx_match_t), off_members = off_clusters + F * F2_MAX * sizeof(lmx_cluster_t),
                  off_counts = off_members + F * F2_MAX * sizeof(int32_t), off_list = off_counts + F * 4 * sizeof(uint32_t),
@@ -726,13 +772,37 @@ lmx_status lmx_ctx_export_matches_on(lmx_ctx* c, int32_t n_frames, const lmx_exp
     c->d_xp_large_counts = reinterpret_cast<uint32_t*>(rows + off_lcounts);
     c->d_xp_rows = rows;
   }
-  const int max_large = std::min<int>(d->max_large_frames, n_frames);
-  if (max_large > c->xp_large_parts) {   // an earlier export may still work on the old workspace
+  // the scored forms' rows, plain device memory (the collect's are mapped pinned memory), and one result per record the slot can hold:
+  // the count is not known here
+  if (scored && !c->d_xp_diffs) {
+    lmx_status st;
+    if ((st = dev_alloc(c, &c->d_xp_rec_diffs, (size_t)c->cap_total, false)) != LMX_OK) return st;
+    if ((st = dev_alloc(c, &c->d_xp_diff_scratch, F * 2 * F2_MAX, false)) != LMX_OK) return st;
+    if ((st = dev_alloc(c, &c->d_xp_diffs, F * F2_MAX, false)) != LMX_OK) return st;
+  }
+  if (normal && !c->d_xp_ndiffs) {
+    lmx_status st;
+    if ((st = dev_alloc(c, &c->d_xp_rec_ndiffs, (size_t)c->cap_total, false)) != LMX_OK) return st;
+    if ((st = dev_alloc(c, &c->d_xp_ndiff_scratch, F * 2 * F2_MAX, false)) != LMX_OK) return st;
+    if ((st = dev_alloc(c, &c->d_xp_ndiffs, F * F2_MAX, false)) != LMX_OK) return st;
+  }
+  if (q.classes && !c->d_xp_cluster_class)
+    if (lmx_status st = dev_alloc(c, &c->d_xp_cluster_class, F * F2_MAX, false)) return st;
+  if (q.classes && scored && (c->xp_class_base.size() != (size_t)q.n_classes + 1 || !std::equal(c->xp_class_base.begin(), c->xp_class_base.end(), q.class_base))) {
+    if (!c->d_xp_class_base) {
+      if (lmx_status st = dev_alloc(c, &c->d_xp_class_base, (size_t)F2_CLASSES + 1, false)) return st;
+    }
+    LMX_HIP(hipStreamSynchronize(c->export_stream));   // an earlier export's walk may still read the old table
+    LMX_HIP(hipMemcpy(c->d_xp_class_base, q.class_base, ((size_t)q.n_classes + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
+    c->xp_class_base.assign(q.class_base, q.class_base + q.n_classes + 1);
+  }
+  const int max_large = std::min<int>(q.max_large_frames, n_frames);
+  if ((size_t)max_large * lay.bytes > c->xp_large_bytes) {   // an earlier export may still work on the old workspace
     LMX_HIP(hipStreamSynchronize(c->export_stream));
     if (c->d_xp_large_ws) (void)hipFree(c->d_xp_large_ws);
-    c->d_xp_large_ws = nullptr; c->xp_large_parts = 0;
+    c->d_xp_large_ws = nullptr; c->xp_large_bytes = 0;
     LMX_HIP(hipMalloc((void**)&c->d_xp_large_ws, (size_t)max_large * lay.bytes));
-    c->xp_large_parts = max_large;
+    c->xp_large_bytes = (size_t)max_large * lay.bytes;
   }
   hipStream_t s = c->export_stream;
   // behind the enqueue that fills the slot, and behind what the caller's stream still does with the outputs
@@ -745,25 +815,41 @@ lmx_status lmx_ctx_export_matches_on(lmx_ctx* c, int32_t n_frames, const lmx_exp
   p.cap = c->cap_total; p.n_frames = n_frames;
   p.out_matches = c->d_xp_matches; p.out_counts = c->d_xp_counts; p.out_clusters = c->d_xp_clusters; p.out_members = c->d_xp_members; p.scratch = c->d_xp_scratch;
   p.do_clusters = clusters ? 1 : 0;
-  if (clusters) {
+  if (clusters && !q.classes) {
     p.dists = c->d_f2_dists; p.rects = c->d_f2_rects; p.n_templates = (uint32_t)c->f2_templates;
     p.step = c->f2_params.vote_row_col_step; p.size_thresh = c->f2_params.cluster_size_thresh;
     p.radius_min = c->f2_params.renderer_radius_min; p.radius_step = c->f2_params.renderer_radius_step;
   }
-  launch_f2(s, p);
+  if (q.classes) { p.classes = c->d_f2_class_table; p.out_cluster_class = c->d_xp_cluster_class; }
+  if (scored) {
+    // the scene's copies, the walk over however many records the slot's header counts, then the scored chain on its results
+    const DepthWalkRecords w{p.hdr, p.recs, p.cap, q.class_index, q.classes ? c->d_xp_class_base : nullptr, q.classes ? q.n_classes : 0, c->d_xp_rec_diffs,
+                             normal ? c->d_xp_rec_ndiffs : nullptr, 0};
+    if (lmx_status st = depth_launch_records_dev(q.templates, s, w)) return st;
+    lk.unlock();
+    p.diffs = c->d_xp_rec_diffs; p.out_diffs = c->d_xp_diffs; p.diff_scratch = c->d_xp_diff_scratch; p.no_value = q.no_value;
+    if (normal) { p.ndiffs = c->d_xp_rec_ndiffs; p.out_ndiffs = c->d_xp_ndiffs; p.ndiff_scratch = c->d_xp_ndiff_scratch; }
+  }
+  if (q.classes) launch_f2_classes(s, p, q.score);
+  else if (normal) launch_f2_normal(s, p);
+  else if (scored) launch_f2_scored(s, p);
+  else launch_f2(s, p);
   ExportParams e{};
   e.recs = p.recs; e.hdr = p.hdr; e.cap = p.cap; e.n_frames = n_frames; e.max_large = max_large;
   e.rows_matches = c->d_xp_matches; e.rows_clusters = c->d_xp_clusters; e.rows_members = c->d_xp_members; e.counts = c->d_xp_counts;
   e.large_ws = c->d_xp_large_ws; e.large_counts = c->d_xp_large_counts; e.lay = lay;
   e.large_frames = c->d_xp_large_frames; e.large_listed = c->d_xp_large_listed;
-  e.header = d->header; e.frame_info = d->frame_info; e.matches = d->matches; e.cap_matches = d->cap_matches;
-  e.clusters = clusters ? d->clusters_out : nullptr; e.cap_clusters = clusters ? d->cap_clusters : 0;
-  e.members = clusters ? d->members : nullptr; e.cap_members = clusters ? d->cap_members : 0;
+  e.header = q.header; e.frame_info = q.frame_info; e.matches = q.matches; e.cap_matches = q.cap_matches;
+  e.clusters = clusters ? q.clusters_out : nullptr; e.cap_clusters = clusters ? q.cap_clusters : 0;
+  e.members = clusters ? q.members : nullptr; e.cap_members = clusters ? q.cap_members : 0;
+  if (scored) { e.rows_diffs = c->d_xp_diffs; e.diffs = q.diffs; }
+  if (normal) { e.rows_ndiffs = c->d_xp_ndiffs; e.ndiffs = q.ndiffs; }
+  if (q.classes) { e.rows_cluster_class = c->d_xp_cluster_class; e.cluster_class = q.cluster_class; }
   if (max_large > 0) {
     launch_export_plan(s, e);
     F2LargeParams lp{p, c->d_xp_large_frames, c->d_xp_large_ws, lay, c->d_xp_large_listed};
     lp.p.out_counts = c->d_xp_large_counts;
-    launch_f2_large(s, lp, max_large, 0, false);
+    launch_f2_large(s, lp, max_large, q.score, q.classes);
   }
   launch_export_pack(s, e);
   LMX_HIP(hipGetLastError());
@@ -772,6 +858,35 @@ lmx_status lmx_ctx_export_matches_on(lmx_ctx* c, int32_t n_frames, const lmx_exp
   c->export_pending[slot] = true;
   LMX_HIP(hipStreamWaitEvent(user, c->export_done[slot], 0));
   return LMX_OK;
+}
+
+lmx_status lmx_ctx_export_matches_on(lmx_ctx* c, int32_t n_frames, const lmx_export_desc* d, void* stream) {
+  return lmx::guarded("lmx_ctx_export_matches_on", [&]() -> lmx_status {
+  const char* const what = "lmx_ctx_export_matches_on";
+  if (!c || !d) { set_error("%s: null argument", what); return LMX_ERR_INVALID_ARG; }
+  if (d->struct_size != sizeof(lmx_export_desc)) { set_error("%s: struct_size %u, not %zu", what, d->struct_size, sizeof(lmx_export_desc)); return LMX_ERR_INVALID_ARG; }
+  ExportRequest q{};
+  q.oldest = d->oldest; q.max_large_frames = d->max_large_frames; q.clusters = d->clusters != 0;
+  q.header = d->header; q.frame_info = d->frame_info; q.matches = d->matches; q.cap_matches = d->cap_matches;
+  q.clusters_out = d->clusters_out; q.cap_clusters = d->cap_clusters; q.members = d->members; q.cap_members = d->cap_members;
+  return export_impl(what, c, n_frames, q, stream);
+  });
+}
+
+lmx_status lmx_ctx_export_clusters_on(lmx_ctx* c, int32_t n_frames, const lmx_export_clusters_desc* d, void* stream) {
+  return lmx::guarded("lmx_ctx_export_clusters_on", [&]() -> lmx_status {
+  const char* const what = "lmx_ctx_export_clusters_on";
+  if (!c || !d) { set_error("%s: null argument", what); return LMX_ERR_INVALID_ARG; }
+  if (d->struct_size != sizeof(lmx_export_clusters_desc)) { set_error("%s: struct_size %u, not %zu", what, d->struct_size, sizeof(lmx_export_clusters_desc)); return LMX_ERR_INVALID_ARG; }
+  if (d->score < 0 || d->score > 2) { set_error("%s: score %d outside 0 .. 2", what, d->score); return LMX_ERR_INVALID_ARG; }
+  if (d->classes < 0 || d->classes > 1) { set_error("%s: classes %d outside 0 .. 1", what, d->classes); return LMX_ERR_INVALID_ARG; }
+  ExportRequest q{};
+  q.oldest = d->oldest; q.max_large_frames = d->max_large_frames; q.clusters = true; q.classes = d->classes == 1; q.score = d->score;
+  q.templates = d->templates; q.class_index = d->classes ? -1 : d->class_index; q.class_base = d->class_base; q.n_classes = d->n_classes; q.no_value = d->no_value;
+  q.header = d->header; q.frame_info = d->frame_info; q.matches = d->matches; q.cap_matches = d->cap_matches;
+  q.diffs = d->diffs; q.ndiffs = d->ndiffs; q.clusters_out = d->clusters_out; q.cap_clusters = d->cap_clusters; q.cluster_class = d->cluster_class;
+  q.members = d->members; q.cap_members = d->cap_members;
+  return export_impl(what, c, n_frames, q, stream);
   });
 }
 

@@ -276,8 +276,19 @@ struct lmx_ctx {
   uint32_t* d_xp_large_listed = nullptr;
   uint32_t* d_xp_large_counts = nullptr;
   uint8_t* d_xp_scratch = nullptr;               // [F][F2_MAX] x 32 bytes
-  uint8_t* d_xp_large_ws = nullptr;              // [xp_large_parts][f2_large_layout(false, false).bytes], grown on demand, never shrunk
-  int xp_large_parts = 0;
+  uint8_t* d_xp_large_ws = nullptr;              // [max_large_frames of a call][its f2_large_layout(scored, normal).bytes], grown on demand, never shrunk
+  size_t xp_large_bytes = 0;
+  // lmx_ctx_export_clusters_on: the scored and classed forms' rows, plain device memory too, nothing allocated before the first call that
+  // needs them.  The count of raw records is not known on the host, so the per-record results have room for the slot's capacity
+  lmx_depth_diff_t* d_xp_rec_diffs = nullptr;    // [cap_total], written by k_walk_records_dev
+  lmx_depth_diff_t* d_xp_diff_scratch = nullptr; // [F][2][F2_MAX]
+  lmx_depth_diff_t* d_xp_diffs = nullptr;        // [F][F2_MAX] in final-match order
+  lmx_normal_diff_t* d_xp_rec_ndiffs = nullptr;  // the same three for score 2
+  lmx_normal_diff_t* d_xp_ndiff_scratch = nullptr;
+  lmx_normal_diff_t* d_xp_ndiffs = nullptr;
+  int32_t* d_xp_cluster_class = nullptr;         // [F][F2_MAX], next to d_xp_clusters
+  int32_t* d_xp_class_base = nullptr;            // [F2_CLASSES + 1]: the class_base of the last classed scored export
+  std::vector<int32_t> xp_class_base;            // what it holds
   // stats / profiling
   int64_t stat_cands = 0, stat_matches = 0;
   uint32_t profiling = 0;  // bitmask over kernel ids

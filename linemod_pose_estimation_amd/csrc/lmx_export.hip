@@ -10,7 +10,10 @@
 //                           status; at most max_batch short steps), the workgroup counts the frame's raw records in the slot's list and copies
 //                           the frame's matches, clusters (member_begin rebased to the flat member array) and members from its rows or from
 //                           its part of the large-frame workspace; lane 0 writes frame_info, and the last frame's workgroup the header.
-// The arithmetic is lmx_export_pack.hpp, shared with the CPU test.
+// lmx_ctx_export_clusters_on runs the same chain with the scored / classed forms of the two lmx_f2.hip kernels (behind the crop walk
+// k_walk_records_dev of lmx_verify.hip), and k_export_pack then also copies the frame's diffs and ndiffs (under the matches' fit decision)
+// and cluster_class (under the clusters'): xpack::side_slot.
+// The arithmetic is lmx_export_pack.hpp, shared with the CPU tests.
 #include <hip/hip_runtime.h>
 
 #include "lmx_internal.hpp"
@@ -21,6 +24,7 @@ namespace {
 
 static_assert(xpack::kSmallMax == (uint32_t)F2_MAX && xpack::kLargeMax == (uint32_t)F2_LARGE_MAX, "lmx_export_pack.hpp restates the chain's limits");
 static_assert(sizeof(lmx_match_t) == 20 && sizeof(lmx_cluster_t) == 48 && offsetof(lmx_cluster_t, member_begin) == 40, "the pack kernel copies dwords");
+static_assert(sizeof(lmx_depth_diff_t) == 4 * xpack::kDiffDwords && sizeof(lmx_normal_diff_t) == 4 * xpack::kDiffDwords, "the pack kernel copies dwords");
 
 constexpr int XP_T = 256;
 
@@ -96,6 +100,23 @@ __global__ __launch_bounds__(XP_T) void k_export_pack(ExportParams e) {
     for (uint32_t i = tid; i < n; i += XP_T) dst[i] = src[i] + (i % 12u == 10u ? (uint32_t)s.member_begin : 0u);
     if (s.n_members)
       copy_dwords(reinterpret_cast<uint32_t*>(e.members + s.member_begin), reinterpret_cast<const uint32_t*>(src_mem), s.n_members, tid);
+  }
+  // lmx_ctx_export_clusters_on: what lies parallel to the matches and to the clusters
+  const xpack::SideSlot o = xpack::side_slot(s, xpack::SideArrays{e.diffs != nullptr, e.ndiffs != nullptr, e.cluster_class != nullptr});
+  if (o.write_diffs && o.n_diffs) {
+    const lmx_depth_diff_t* src = s.part >= 0 ? reinterpret_cast<const lmx_depth_diff_t*>(e.large_ws + (size_t)s.part * e.lay.bytes + e.lay.diffs)
+                                              : e.rows_diffs + (size_t)frame * F2_MAX;
+    copy_dwords(reinterpret_cast<uint32_t*>(e.diffs + o.diff_begin), reinterpret_cast<const uint32_t*>(src), o.n_diffs * xpack::kDiffDwords, tid);
+  }
+  if (o.write_ndiffs && o.n_diffs) {
+    const lmx_normal_diff_t* src = s.part >= 0 ? reinterpret_cast<const lmx_normal_diff_t*>(e.large_ws + (size_t)s.part * e.lay.bytes + e.lay.ndiffs)
+                                               : e.rows_ndiffs + (size_t)frame * F2_MAX;
+    copy_dwords(reinterpret_cast<uint32_t*>(e.ndiffs + o.diff_begin), reinterpret_cast<const uint32_t*>(src), o.n_diffs * xpack::kDiffDwords, tid);
+  }
+  if (o.write_cluster_class && o.n_class) {
+    const int32_t* src = s.part >= 0 ? reinterpret_cast<const int32_t*>(e.large_ws + (size_t)s.part * e.lay.bytes + e.lay.cluster_class)
+                                     : e.rows_cluster_class + (size_t)frame * F2_MAX;
+    copy_dwords(reinterpret_cast<uint32_t*>(e.cluster_class + o.class_begin), reinterpret_cast<const uint32_t*>(src), o.n_class, tid);
   }
 }
 

@@ -1,7 +1,8 @@
 // The arithmetic of lmx_ctx_export_matches_on (include/lmx.h): which frames the large-frame kernel takes, where each frame's results come
 // from, where they go in the caller's flat arrays, whether they fit, and the status words -- the device form of the per-frame loop at the
 // end of collect_clusters_impl (lmx_collect.cpp).  Shared by the kernels of lmx_export.hip and by plain CPU builds (any compiler but hipcc:
-// tests/cpp/export_pack_host.cpp), so that the rules are tested without a GPU.
+// tests/cpp/export_pack_host.cpp), so that the rules are tested without a GPU.  lmx_ctx_export_clusters_on adds the arrays parallel to
+// the matches and the clusters: the last section (tests/cpp/export_clusters_pack_host.cpp).
 //
 // Inputs are the count words the chain's kernels leave behind:
 //   counts[f][4]   of k_f2_finalize_cluster, one row per frame: {final matches, clusters, members, status}; status 0 delivered, 1 more than
@@ -117,6 +118,31 @@ LMX_XP_FN void fill_header(uint32_t* header, const Walk& w, int32_t n_frames, ui
   header[H_FRAMES] = (uint32_t)n_frames; header[H_FLAGS] = w.flags;
   header[H_MATCHES] = (uint32_t)w.matches; header[H_CLUSTERS] = (uint32_t)w.clusters; header[H_MEMBERS] = (uint32_t)w.members;
   header[H_CANDIDATES] = n_candidates; header[H_RECORDS] = n_records;
+}
+
+// ---- lmx_ctx_export_clusters_on: the arrays that lie parallel to the matches and to the clusters ------------------------------------------
+// diffs and ndiffs share the matches' offsets, capacity and fit decision, cluster_class the clusters' (which the members decide too): a
+// frame's range of a side array is written iff the call has that array and the frame's range of its parent array is written.
+constexpr uint32_t kDiffDwords = 4;   // lmx_depth_diff_t and lmx_normal_diff_t, as the pack kernel copies them
+
+struct SideArrays { bool diffs, ndiffs, cluster_class; };   // which of them the call has
+
+struct SideSlot {
+  uint64_t diff_begin;    // = match_begin, in elements of diffs and of ndiffs
+  uint32_t n_diffs;       // = n_matches
+  uint64_t class_begin;   // = cluster_begin
+  uint32_t n_class;       // = n_clusters
+  bool write_diffs, write_ndiffs, write_cluster_class;
+};
+
+LMX_XP_FN SideSlot side_slot(const Slot& s, const SideArrays& has) {
+  SideSlot o;
+  o.diff_begin = s.match_begin; o.n_diffs = s.n_matches;
+  o.class_begin = s.cluster_begin; o.n_class = s.n_clusters;
+  o.write_diffs = has.diffs && s.write_matches;
+  o.write_ndiffs = has.ndiffs && s.write_matches;
+  o.write_cluster_class = has.cluster_class && s.write_clusters;
+  return o;
 }
 
 }  // namespace xpack

@@ -362,6 +362,14 @@ struct ExportParams {
   lmx_match_t* matches; uint64_t cap_matches;
   lmx_cluster_t* clusters; uint64_t cap_clusters;
   int32_t* members; uint64_t cap_members;
+  // lmx_ctx_export_clusters_on only (null otherwise): the rows next to rows_matches / rows_clusters (in a large frame's part: lay.diffs,
+  // lay.ndiffs, lay.cluster_class) and the caller's arrays parallel to `matches` / `clusters`
+  const lmx_depth_diff_t* rows_diffs;
+  const lmx_normal_diff_t* rows_ndiffs;
+  const int32_t* rows_cluster_class;
+  lmx_depth_diff_t* diffs;
+  lmx_normal_diff_t* ndiffs;
+  int32_t* cluster_class;
 };
 void launch_export_plan(hipStream_t s, const ExportParams& e);   // max_large > 0 only
 void launch_export_pack(hipStream_t s, const ExportParams& e);
@@ -388,6 +396,23 @@ lmx_status depth_launch_records_classes(lmx_depth_templates* t, hipStream_t s, c
                                         int32_t n_classes, lmx_depth_diff_t* d_diffs, lmx_normal_diff_t* d_ndiffs = nullptr);
 lmx_status depth_diff_resident_classes(lmx_depth_templates* t, const lmx_match_t* matches, size_t n, int32_t frame, const int32_t* class_base, int32_t n_classes,
                                        lmx_depth_diff_t* out, lmx_normal_diff_t* nout = nullptr);
+// depth_launch_records / _classes for a caller that has not read the slot's header (lmx_ctx_export_clusters_on): k_walk_records_dev, a
+// fixed grid of persistent workgroups that take the record count from hdr[1] on the device and walk nothing when hdr says that a list
+// overflowed `cap`.  d_diffs[i] (d_ndiffs[i]) for recs[i], i < hdr[1]: room for `cap` records.  d_class_base null: the un-classed
+// predicate with class_index; else the classed one.  `s` first waits for the scene's copies and for every earlier such walk of the object,
+// and the object remembers an event behind this one: what changes the crops, the scene or the normals waits for it.  Launches always.
+struct DepthWalkRecords {
+  const uint32_t* hdr;
+  const lmx_raw_match_t* recs;
+  uint32_t cap;
+  int32_t class_index;
+  const int32_t* d_class_base;
+  int32_t n_classes;
+  lmx_depth_diff_t* d_diffs;
+  lmx_normal_diff_t* d_ndiffs;   // null: the depth term alone
+  int32_t grid;                  // workgroups; 0: the object's (a multiple of the device's compute units)
+};
+lmx_status depth_launch_records_dev(lmx_depth_templates* t, hipStream_t s, const DepthWalkRecords& w);
 void launch_debug_block_sort(hipStream_t s, const float* sim, const int* tid, int n, int* perm, unsigned long long* spill);
 
 struct PullEntry { uint64_t src; uint64_t row_stride; };  // one caller-owned pinned image (device-visible address)

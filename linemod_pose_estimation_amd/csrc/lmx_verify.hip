@@ -22,6 +22,8 @@
 //                  call first needs them, on that call's stream behind the scene's event
 //   k_verify_diff / k_verify_diff_records   the NORMALS instantiation of the same walk, both terms in one pass (nv::add_vector): the two
 //                  stored normals of a pixel are read next to its two depths, their angle comes out of the chord table in global memory
+//   k_walk_records_dev   the record kernels for a caller that has not read the slot's header (lmx_ctx_export_clusters_on): persistent
+//                  workgroups that take the record count from device memory; see the kernel
 // The host half has one launch site for jobs (run_jobs) and one for records (depth_launch_records), one body for both match-list paths
 // (diff_selected) and one guard in front of every normal-scored call (need_normals).
 #include <algorithm>
@@ -34,6 +36,7 @@
 #include "lmx_depth_verify.hpp"
 #include "lmx_normal_verify.hpp"
 #include "lmx_mesh_raster.hpp"
+#include "lmx_export_pack.hpp"
 
 namespace lmx {
 namespace {
@@ -264,6 +267,55 @@ __global__ __launch_bounds__(256) void k_verify_diff_records_classes(const Depth
   diff_walk<true>(crops, normals, is_job, id, r.x, r.y, r.frame, scene, scene_normals, W, H, table, &diffs[blockIdx.x], &ndiffs[blockIdx.x]);
 }
 
+// The four record kernels again for a caller that does not know the record count (lmx_ctx_export_clusters_on: no host reads the slot):
+// a fixed grid of persistent workgroups, workgroup b walks records b, b + gridDim.x, ... below hdr[1], which every lane reads from the
+// slot's header in device memory; a list that overflowed is not walked at all (the pack kernel reports it).  Record i is a job or not by
+// the same two predicates, and gets the same 16 (32) bytes from the same diff_walk.
+// The one thing a second job of a workgroup adds: diff_walk's per-wave partial sums live in static LDS, and lane 0 still adds up the
+// first job's while the other waves go on.  So ONE barrier stands in front of a walk that follows an earlier walk of the same workgroup
+// (`dirty`), and none anywhere else: behind it lane 0 has left diff_walk, hence has read s_sum / s_count.  Records that are no job, and
+// jobs with an empty crop, touch no LDS and take no barrier, however many lie between two walks; a workgroup's first walk takes none
+// either.  Chosen over two alternating LDS sets: it leaves diff_walk as it is, and the wait is short -- the other waves spend it on
+// the next record's load, which is issued in front of the barrier.  n, i and `walks` depend on the header, blockIdx and record i alone:
+// every lane of a workgroup takes the same trips and the same branch around the barrier.
+struct WalkDev {
+  const DepthCrop* crops;
+  nv::Packed* const* normals;
+  const uint32_t* hdr;              // the slot's header: [0] candidates, [1] records
+  const lmx_raw_match_t* recs;
+  uint32_t cap;                     // of the slot's lists
+  int32_t count;                    // un-classed: templates in the table
+  int32_t class_index;              // un-classed: -1 = every class
+  const int32_t* class_base;        // CLASSES: n_classes + 1 entries
+  int32_t n_classes;
+  const uint16_t* scene;
+  const nv::Packed* scene_normals;
+  int32_t n_frames, W, H;
+  const uint32_t* table;
+  lmx_depth_diff_t* diffs;
+  lmx_normal_diff_t* ndiffs;
+};
+
+template <bool NORMALS, bool CLASSES>
+__global__ __launch_bounds__(256) void k_walk_records_dev(const WalkDev a) {
+  const uint32_t n_cand = a.hdr[0], n = a.hdr[1];
+  if (xpack::list_overflowed(n_cand, n, a.cap)) return;
+  bool dirty = false;   // an earlier walk of this workgroup used the LDS sums
+  for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
+    const lmx_raw_match_t r = a.recs[i];
+    int32_t id = r.template_id;
+    bool is_job;
+    if constexpr (CLASSES) is_job = record_class_job(r, a.class_base, a.n_classes, a.n_frames, &id);
+    else is_job = record_is_job(r, a.count, a.n_frames, a.class_index);
+    bool walks = false;
+    if (is_job) { const DepthCrop c = a.crops[id]; walks = c.w > 0 && c.h > 0; }
+    if (walks && dirty) __syncthreads();
+    diff_walk<NORMALS>(a.crops, a.normals, is_job, id, r.x, r.y, r.frame, a.scene, a.scene_normals, a.W, a.H, a.table, &a.diffs[i],
+                       NORMALS ? &a.ndiffs[i] : nullptr);
+    dirty = dirty || walks;
+  }
+}
+
 }  // namespace
 }  // namespace lmx
 
@@ -313,8 +365,15 @@ struct lmx_depth_templates {
   hipEvent_t normals_ready = nullptr;    // recorded behind the kernel that computed them (it may run on a caller's stream)
   lmx_normal_diff_t *d_nout = nullptr, *h_nout = nullptr;   // as d_out / h_out
   size_t nout_cap = 0;
+  // lmx_ctx_export_clusters_on: its walk reads the table, the crops, the scene and the normals on a context's export stream and nobody
+  // waits for it on the host.  export_read is recorded behind each such walk (an export's stream waits for the previous record first, so
+  // the last record stands behind all of them); whoever changes what the walk reads waits for it: wait_export_reads() on the host,
+  // lmx_depth_templates_upload_scene_device on the device
+  hipEvent_t export_read = nullptr;
+  bool export_read_pending = false;
+  int32_t walk_grid = 0;                 // workgroups of k_walk_records_dev; 0: not asked for yet (kWalkGridPerCU per compute unit)
   // lmx_depth_templates_set_profiling: a pair of events around each launch of the kernels below, read out by ..._kernel_time
-  enum { PK_NORMAL_MAP_FRAMES, PK_VERIFY_DIFF_RECORDS, PK_VERIFY_DIFF, PK_DEPTH_DIFF_RECORDS, PK_COUNT };
+  enum { PK_NORMAL_MAP_FRAMES, PK_VERIFY_DIFF_RECORDS, PK_VERIFY_DIFF, PK_DEPTH_DIFF_RECORDS, PK_WALK_RECORDS_DEV, PK_COUNT };
   struct ProfEvent { int kernel; hipEvent_t start, stop; };
   bool profiling = false;
   std::vector<ProfEvent> prof_pending;
@@ -357,6 +416,11 @@ struct lmx_depth_templates {
     }
     return LMX_OK;
   }
+  // Nothing an export queued still reads the crops, the table, the scene or the normals.
+  lmx_status wait_export_reads() {
+    if (export_read_pending) { DV_HIP(hipSetDevice(device)); DV_HIP(hipEventSynchronize(export_read)); export_read_pending = false; }
+    return LMX_OK;
+  }
   // The staging buffer is free again: the copies of the previous upload_scene have left it.
   lmx_status wait_scene_copies() {
     if (scene_pending) { DV_HIP(hipEventSynchronize(scene_ready)); scene_pending = false; }
@@ -368,6 +432,7 @@ struct lmx_depth_templates {
   lmx_status grow_scene(size_t bytes) {
     if (bytes <= scene_cap) return LMX_OK;
     DV_HIP(hipStreamSynchronize(s));     // nothing queued may still use the buffers that go
+    if (lmx_status st = wait_export_reads()) return st;
     (void)hipFree(d_scene); (void)hipHostFree(h_scene);
     d_scene = h_scene = nullptr; scene_cap = 0;
     const size_t cap = bytes;
@@ -398,7 +463,8 @@ struct lmx_depth_templates {
   // object's own stream that carries them); every later user waits for normals_ready.
   lmx_status compute_scene_normals(hipStream_t on, int32_t n_frames, int32_t W, int32_t H) {
     const size_t bytes = (size_t)W * H * (size_t)n_frames * sizeof(lmx::nv::Packed);
-    if (bytes > scene_normals_cap) {     // every call that read the old buffer ended synchronised
+    if (bytes > scene_normals_cap) {     // every call that read the old buffer ended synchronised, but for an export's walk
+      if (lmx_status st = wait_export_reads()) return st;
       (void)hipFree(d_scene_normals);
       d_scene_normals = nullptr; scene_normals_cap = 0;
       DV_HIP(hipMalloc(&d_scene_normals, bytes));
@@ -444,6 +510,8 @@ struct lmx_depth_templates {
   }
   ~lmx_depth_templates() {
     if (s) (void)hipStreamSynchronize(s);
+    (void)wait_export_reads();
+    if (export_read) (void)hipEventDestroy(export_read);
     for (void* p : chunks) (void)hipFree(p);
     (void)hipFree(d_table); (void)hipFree(d_scene); (void)hipFree(d_jobs); (void)hipFree(d_out);
     (void)hipHostFree(h_scene); (void)hipHostFree(h_jobs); (void)hipHostFree(h_out);
@@ -635,6 +703,7 @@ extern "C" lmx_status lmx_depth_templates_append(lmx_depth_templates* dst, lmx_d
       if (t->s) {
         DV_HIP(hipSetDevice(t->device));
         DV_HIP(hipStreamSynchronize(t->s));
+        if (lmx_status st = t->wait_export_reads()) return st;
         t->scene_pending = false;
         t->prof_drain();
       }
@@ -713,6 +782,7 @@ lmx_status compute_crop_normals(lmx_depth_templates* t) {
   if (lmx_status st = t->ensure_device()) return st;
   if (lmx_status st = t->ensure_normal_device()) return st;
   DV_HIP(hipStreamSynchronize(t->s));
+  if (lmx_status st = t->wait_export_reads()) return st;   // an export's walk may still read the normals that go
   t->free_normal_crops();
   t->ncrops_ready = false;
   const size_t n = t->table.size(), elems = t->atlas_bytes / sizeof(uint16_t);
@@ -819,6 +889,7 @@ extern "C" lmx_status lmx_depth_templates_upload_scene_device(lmx_depth_template
     if (!t->scene_src_ready) DV_HIP(hipEventCreateWithFlags(&t->scene_src_ready, hipEventDisableTiming));
     DV_HIP(hipEventRecord(t->scene_src_ready, user));
     DV_HIP(hipStreamWaitEvent(t->s, t->scene_src_ready, 0));
+    if (t->export_read_pending) DV_HIP(hipStreamWaitEvent(t->s, t->export_read, 0));   // on the device: an export's walk may still read the old scene
     for (int32_t f = 0; f < n_frames; ++f)
       if (hipError_t e = hipMemcpy2DAsync(reinterpret_cast<uint8_t*>(t->d_scene) + frame_bytes * f, (size_t)W * 2, depth[f].data, depth[f].row_stride_bytes, (size_t)W * 2,
                                           (size_t)H, hipMemcpyDeviceToDevice, t->s)) {
@@ -851,6 +922,7 @@ lmx_status depth_upload_scene(lmx_depth_templates* t, const lmx_image* depth, in
   const int32_t W = depth[0].cols, H = depth[0].rows;
   if (lmx_status st = t->ensure_device()) return st;
   if (lmx_status st = t->wait_scene_copies()) return st;   // the previous scene's copies still read the staging buffer
+  if (lmx_status st = t->wait_export_reads()) return st;   // an export's walk may still read the scene these copies overwrite
   t->scene_frames = 0;
   t->scene_normals_valid = false;
   if (lmx_status st = t->grow_scene((size_t)W * H * sizeof(uint16_t) * (size_t)n_frames)) return st;
@@ -930,6 +1002,48 @@ lmx_status depth_launch_records_classes(lmx_depth_templates* t, hipStream_t s, c
   return LMX_OK;
 }
 
+// Workgroups of the persistent walk per compute unit.  profiles/export_clusters.txt: the smallest of the grids measured whose time lies
+// within the run-to-run spread of the best.
+constexpr int kWalkGridPerCU = 4;
+
+lmx_status depth_launch_records_dev(lmx_depth_templates* t, hipStream_t s, const DepthWalkRecords& w) {
+  if (t->scene_frames < 1) { set_error("no scene uploaded: call lmx_depth_templates_upload_scene first"); return LMX_ERR_INVALID_ARG; }
+  if (w.d_ndiffs)
+    if (lmx_status st = need_normals(t, nullptr)) return st;
+  if (lmx_status st = t->ensure_device()) return st;   // the table, after an append
+  if (!t->export_read) DV_HIP(hipEventCreateWithFlags(&t->export_read, hipEventDisableTiming));
+  int32_t grid = w.grid;
+  if (grid <= 0) {
+    if (t->walk_grid <= 0) {
+      int cus = 0;
+      DV_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, t->device));
+      t->walk_grid = kWalkGridPerCU * std::max(cus, 1);
+    }
+    grid = t->walk_grid;
+  }
+  if (t->export_read_pending) DV_HIP(hipStreamWaitEvent(s, t->export_read, 0));   // the record below then stands behind every earlier walk too
+  DV_HIP(hipStreamWaitEvent(s, t->scene_ready, 0));
+  if (w.d_ndiffs)   // the scene's normals first, on this stream, if this is the scene's first normal-scored call
+    if (lmx_status st = t->scene_normals_on(s, nullptr, t->scene_frames, t->scene_W, t->scene_H)) return st;
+  const WalkDev a{t->d_table, t->d_ntable, w.hdr, w.recs, w.cap, (int32_t)t->table.size(), w.class_index, w.d_class_base, w.n_classes, t->d_scene,
+                  t->d_scene_normals, t->scene_frames, t->scene_W, t->scene_H, t->d_angle, w.d_diffs, w.d_ndiffs};
+  const bool classes = w.d_class_base != nullptr;
+  const int pe = t->prof_begin(lmx_depth_templates::PK_WALK_RECORDS_DEV, s);
+  const dim3 g((unsigned)grid), b(256);
+  if (w.d_ndiffs) {
+    if (classes) hipLaunchKernelGGL((k_walk_records_dev<true, true>), g, b, 0, s, a);
+    else hipLaunchKernelGGL((k_walk_records_dev<true, false>), g, b, 0, s, a);
+  } else {
+    if (classes) hipLaunchKernelGGL((k_walk_records_dev<false, true>), g, b, 0, s, a);
+    else hipLaunchKernelGGL((k_walk_records_dev<false, false>), g, b, 0, s, a);
+  }
+  t->prof_end(pe, s);
+  DV_HIP(hipGetLastError());
+  DV_HIP(hipEventRecord(t->export_read, s));
+  t->export_read_pending = true;
+  return LMX_OK;
+}
+
 lmx_status depth_diff_resident_classes(lmx_depth_templates* t, const lmx_match_t* matches, size_t n, int32_t frame, const int32_t* class_base, int32_t n_classes,
                                        lmx_depth_diff_t* out, lmx_normal_diff_t* nout) {
   // the matches with their crop's index in the joined object for a template id; what record_class_job leaves out becomes id -1: zeros
@@ -988,6 +1102,7 @@ lmx_status diff_matches_impl(const char* what, lmx_depth_templates* t, const lmx
     // the frames that have matches take the place of an uploaded scene: staged row by row into pinned memory, each on its way while the
     // next is staged
     if (lmx_status st = t->wait_scene_copies()) return st;
+    if (lmx_status st = t->wait_export_reads()) return st;   // an export's walk may still read the scene the staged frames replace
     t->scene_frames = 0;
     t->scene_normals_valid = false;
     if (lmx_status st = t->grow_scene(frame_bytes * n_slots)) return st;
@@ -1042,6 +1157,7 @@ extern "C" lmx_status lmx_depth_templates_enable_normals(lmx_depth_templates* t,
     std::lock_guard<std::mutex> lk(t->m);
     const nv::Params np = {fx, fy, params->difference_threshold, params->distance_threshold};
     if (t->normals_on && t->ncrops_ready && std::memcmp(&np, &t->nparams, sizeof(np)) == 0) return LMX_OK;
+    if (lmx_status st = t->wait_export_reads()) return st;   // the scene's normals are computed again: an export's walk may still read them
     t->nparams = np;
     t->normals_on = true;
     t->ncrops_ready = false;
@@ -1102,5 +1218,73 @@ extern "C" lmx_status lmx_debug_scene_normals(lmx_depth_templates* t, int32_t fr
     DV_HIP(hipMemcpyAsync(out, t->d_scene_normals + px * frame, px * sizeof(lmx::nv::Packed), hipMemcpyDeviceToHost, t->s));
     DV_HIP(hipStreamSynchronize(t->s));
     return LMX_OK;
+  });
+}
+
+extern "C" lmx_status lmx_debug_depth_walk_grid(lmx_depth_templates* t, int32_t workgroups) {
+  if (!t || workgroups < 0 || workgroups > 65536) { lmx::set_error("lmx_debug_depth_walk_grid: templates must not be null, workgroups 0 .. 65536"); return LMX_ERR_INVALID_ARG; }
+  std::lock_guard<std::mutex> lk(t->m);
+  t->walk_grid = workgroups;
+  return LMX_OK;
+}
+
+// The walk of lmx_ctx_export_clusters_on on a slot the caller builds: header {n_candidates, header_count}, the records behind it, a grid the
+// caller chooses.  diffs / ndiffs go to the device as they are and come back as the kernel left them.
+extern "C" lmx_status lmx_debug_depth_walk_records(lmx_depth_templates* t, const lmx_raw_match_t* records, size_t n_records, uint32_t header_count,
+                                                   uint32_t n_candidates, uint32_t cap, int32_t grid_workgroups, int32_t class_index, const int32_t* class_base,
+                                                   int32_t n_classes, lmx_depth_diff_t* diffs, lmx_normal_diff_t* ndiffs) {
+  return lmx::guarded("lmx_debug_depth_walk_records", [&]() -> lmx_status {
+    using namespace lmx;
+    const char* what = "lmx_debug_depth_walk_records";
+    if (!t || !diffs || (n_records && !records)) { set_error("%s: null argument", what); return LMX_ERR_INVALID_ARG; }
+    if (grid_workgroups < 1 || grid_workgroups > 65536) { set_error("%s: grid_workgroups %d outside 1 .. 65536", what, grid_workgroups); return LMX_ERR_INVALID_ARG; }
+    if (n_records > ((size_t)1 << 24)) { set_error("%s: at most 2^24 records", what); return LMX_ERR_INVALID_ARG; }
+    // the kernel walks header_count records unless the header says that a list overflowed: they must all be the caller's
+    if (!xpack::list_overflowed(n_candidates, header_count, cap) && header_count > n_records) {
+      set_error("%s: the header counts %u records, %zu were passed", what, header_count, n_records);
+      return LMX_ERR_INVALID_ARG;
+    }
+    std::lock_guard<std::mutex> lk(t->m);
+    if (class_base) {
+      if (n_classes < 1 || n_classes > F2_CLASSES || class_base[0] != 0) { set_error("%s: class_base: n_classes 1..%d, class_base[0] = 0", what, F2_CLASSES); return LMX_ERR_INVALID_ARG; }
+      for (int32_t k = 0; k < n_classes; ++k)
+        if (class_base[k + 1] < class_base[k]) { set_error("%s: class_base must not decrease", what); return LMX_ERR_INVALID_ARG; }
+      if ((size_t)class_base[n_classes] != t->table.size()) { set_error("%s: class_base ends at %d but the object holds %zu depth templates", what, class_base[n_classes], t->table.size()); return LMX_ERR_INVALID_ARG; }
+    }
+    if (ndiffs)
+      if (lmx_status st = need_normals(t, what, false)) return st;
+    if (t->scene_frames < 1) { set_error("%s: no scene uploaded: call lmx_depth_templates_upload_scene first", what); return LMX_ERR_INVALID_ARG; }
+    if (lmx_status st = t->ensure_device()) return st;
+    const size_t R = std::max<size_t>(n_records, 1);
+    DeviceBuffer d_hdr, d_recs, d_base, d_diffs, d_ndiffs;
+    uint32_t hdr[16] = {0};
+    hdr[0] = n_candidates; hdr[1] = header_count;
+    hipStream_t s = t->s;
+    DV_HIP(hipMalloc(&d_hdr.p, sizeof(hdr)));
+    DV_HIP(hipMalloc(&d_recs.p, R * sizeof(lmx_raw_match_t)));
+    DV_HIP(hipMalloc(&d_diffs.p, R * sizeof(lmx_depth_diff_t)));
+    DV_HIP(hipMemcpyAsync(d_hdr.p, hdr, sizeof(hdr), hipMemcpyHostToDevice, s));
+    if (n_records) {
+      DV_HIP(hipMemcpyAsync(d_recs.p, records, n_records * sizeof(lmx_raw_match_t), hipMemcpyHostToDevice, s));
+      DV_HIP(hipMemcpyAsync(d_diffs.p, diffs, n_records * sizeof(lmx_depth_diff_t), hipMemcpyHostToDevice, s));
+    }
+    if (ndiffs) {
+      DV_HIP(hipMalloc(&d_ndiffs.p, R * sizeof(lmx_normal_diff_t)));
+      if (n_records) DV_HIP(hipMemcpyAsync(d_ndiffs.p, ndiffs, n_records * sizeof(lmx_normal_diff_t), hipMemcpyHostToDevice, s));
+    }
+    if (class_base) {
+      DV_HIP(hipMalloc(&d_base.p, ((size_t)n_classes + 1) * sizeof(int32_t)));
+      DV_HIP(hipMemcpyAsync(d_base.p, class_base, ((size_t)n_classes + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    }
+    const DepthWalkRecords w{d_hdr.as<uint32_t>(), d_recs.as<lmx_raw_match_t>(), cap, class_index, d_base.as<int32_t>(), class_base ? n_classes : 0,
+                             d_diffs.as<lmx_depth_diff_t>(), d_ndiffs.as<lmx_normal_diff_t>(), grid_workgroups};
+    lmx_status st = depth_launch_records_dev(t, s, w);
+    if (st == LMX_OK && n_records) {
+      DV_HIP(hipMemcpyAsync(diffs, d_diffs.p, n_records * sizeof(lmx_depth_diff_t), hipMemcpyDeviceToHost, s));
+      if (ndiffs) DV_HIP(hipMemcpyAsync(ndiffs, d_ndiffs.p, n_records * sizeof(lmx_normal_diff_t), hipMemcpyDeviceToHost, s));
+    }
+    DV_HIP(hipStreamSynchronize(s));   // the scratch buffers go when this returns
+    t->export_read_pending = false;
+    return st;
   });
 }

@@ -204,6 +204,93 @@ class ExportedMatches:
         return out
 
 
+def export_clusters_layout(n_frames, score=0, classes=False, caps=(1 << 16, 4096, 1 << 16)):
+    """export_layout(clusters=True) plus the arrays lmx_ctx_export_clusters_on adds, as Detector.export_clusters allocates them: "diffs"
+    (score >= 1) and "ndiffs" (score == 2), 16-byte records parallel to "matches" with its capacity, as int64 [cap, 2] (8-byte aligned);
+    "cluster_class" (classes), int32 parallel to "clusters"."""
+    if score not in (0, 1, 2):
+        raise ValueError("score is 0 (mean similarity), 1 (depth) or 2 (depth + normal)")
+    out = export_layout(n_frames, True, caps)
+
+    def side(parent, shape_tail, dtype, align):
+        cap = out[parent]["cap"]
+        shape = (max(cap, 1),) + shape_tail
+        return {"shape": shape, "dtype": dtype, "nbytes": int(np.prod(shape)) * np.dtype(dtype).itemsize, "align": align, "cap": cap}
+    if score >= 1:
+        out["diffs"] = side("matches", (DEPTH_DIFF_DTYPE.itemsize // 8,), "int64", 8)
+    if score == 2:
+        out["ndiffs"] = side("matches", (NORMAL_DIFF_DTYPE.itemsize // 8,), "int64", 8)
+    if classes:
+        out["cluster_class"] = side("clusters", (), "int32", 4)
+    return out
+
+
+class ExportedClusters:
+    """What Detector.export_clusters leaves on the GPU (lmx_ctx_export_clusters_on): ExportedMatches' tensors with clusters, and next to
+    them, on the same device and valid for work queued on `stream` after the call --
+      diffs          int64 [cap, 2]  lmx_depth_diff_t records (DEPTH_DIFF_DTYPE) parallel to matches            (None with score 0)
+      ndiffs         int64 [cap, 2]  lmx_normal_diff_t records (NORMAL_DIFF_DTYPE) parallel to matches          (None unless score 2)
+      cluster_class  int32 [cap]     the class of each cluster, parallel to clusters                           (None without classes)
+    A frame's range of diffs / ndiffs is written iff its matches are, of cluster_class iff its clusters are."""
+
+    def __init__(self, n_frames, score, classes, caps, stream, device):
+        import torch
+        self.n_frames, self.score, self.with_classes, self.stream = n_frames, int(score), bool(classes), stream
+        lay = export_clusters_layout(n_frames, score, classes, caps)
+        with torch.cuda.stream(stream):     # the caching allocator hands out memory that is free on this stream
+            t = {k: torch.empty(v["shape"], dtype=getattr(torch, v["dtype"]), device="cuda:%d" % device) for k, v in lay.items()}
+        self._backing = t
+        self.caps = tuple(lay[k]["cap"] for k in ("matches", "clusters", "members"))
+        self._views()
+
+    def _views(self):
+        t, caps = self._backing, self.caps
+        self.header, self.frame_info = t["header"], t["frame_info"]
+        self.matches, self.clusters, self.members = t["matches"][:caps[0]], t["clusters"][:caps[1]], t["members"][:caps[2]]
+        self.diffs = t["diffs"][:caps[0]] if "diffs" in t else None
+        self.ndiffs = t["ndiffs"][:caps[0]] if "ndiffs" in t else None
+        self.cluster_class = t["cluster_class"][:caps[1]] if "cluster_class" in t else None
+
+    @property
+    def similarity(self):
+        import torch
+        return self.matches[:, 2].view(torch.float32)
+
+    def clone(self):
+        """A copy made on `stream`, as ExportedMatches.clone."""
+        import torch
+        out = ExportedClusters.__new__(ExportedClusters)
+        out.n_frames, out.score, out.with_classes, out.stream, out.caps = self.n_frames, self.score, self.with_classes, self.stream, self.caps
+        with torch.cuda.stream(self.stream):
+            out._backing = {k: v.clone() for k, v in self._backing.items()}
+        out._views()
+        return out
+
+    def to_host(self):
+        """Synchronises `stream` -> list per frame of (matches, diffs, ndiffs, clusters, cluster_class, members) in
+        collect_clusters_classes' shape and dtypes (diffs / ndiffs / cluster_class None where the call has none; CLUSTER_DTYPE's
+        member_begin indexes `members`, the batch's flat member array), or None for a frame whose status is not 0."""
+        self.stream.synchronize()
+        info = self.frame_info.cpu().numpy()
+        n_m, n_c, n_mem = (int(v) for v in self.header[2:5].cpu().numpy())
+        n_m, n_c, n_mem = min(n_m, self.caps[0]), min(n_c, self.caps[1]), min(n_mem, self.caps[2])
+        m = np.ascontiguousarray(self.matches[:n_m].cpu().numpy()).view(MATCH_DTYPE).reshape(-1)
+        d = np.ascontiguousarray(self.diffs[:n_m].cpu().numpy()).view(DEPTH_DIFF_DTYPE).reshape(-1) if self.diffs is not None else None
+        nd = np.ascontiguousarray(self.ndiffs[:n_m].cpu().numpy()).view(NORMAL_DIFF_DTYPE).reshape(-1) if self.ndiffs is not None else None
+        cl = np.ascontiguousarray(self.clusters[:n_c].cpu().numpy()).view(CLUSTER_DTYPE).reshape(-1)
+        cc = np.ascontiguousarray(self.cluster_class[:n_c].cpu().numpy()) if self.cluster_class is not None else None
+        mem = np.ascontiguousarray(self.members[:n_mem].cpu().numpy())
+        out = []
+        for f in range(self.n_frames):
+            mb, mc, cb, ncl, _, _, status, _ = (int(v) for v in info[f])
+            if status != EXPORT_DELIVERED:
+                out.append(None)
+                continue
+            out.append((m[mb:mb + mc].copy(), d[mb:mb + mc].copy() if d is not None else None, nd[mb:mb + mc].copy() if nd is not None else None,
+                        cl[cb:cb + ncl].copy(), cc[cb:cb + ncl].copy() if cc is not None else None, mem))
+        return out
+
+
 class PreparedBatch:
     """lmx_image descriptors of a batch of host frames, built once (the arrays are kept alive by this object)."""
 
@@ -798,6 +885,45 @@ class Detector:
         _lib.check(_lib.lib().lmx_ctx_export_matches_on(self.h, n_frames, C.byref(desc), int(stream.cuda_stream)))
         return out
 
+    def export_clusters(self, n_frames, templates=None, class_index=-1, normals=False, no_value=-np.inf, classes=False, class_base=None, oldest=False,
+                        max_large_frames=0, cap_matches=1 << 16, cap_clusters=4096, cap_members=1 << 16, stream=None, out=None):
+        """export_matches(clusters=True) for every cluster chain (lmx_ctx_export_clusters_on) -> ExportedClusters.  templates None: mean
+        similarity; a DepthTemplates whose upload_scene / upload_scene_device was called after the enqueue: the depth score, with
+        normals=True (after enable_normals) depth + normal.  classes=True: the per-class chain with the side-cars of
+        set_cluster_sidecar_class; with templates it also takes class_base as collect_clusters_classes does (class_index is then not
+        used).  Equal, for every delivered frame, to collect_clusters / _depth / _depth_normal / _classes of the same enqueue, which
+        stays outstanding.  Nothing waits on the host; the first scored call allocates 16 bytes per record the slot can hold
+        (max_batch x max_candidates; twice with normals).  stream, out, oldest, max_large_frames and the capacities as export_matches (diffs / ndiffs share cap_matches,
+        cluster_class cap_clusters)."""
+        import torch
+        score = 0 if templates is None else (2 if normals else 1)
+        if stream is None:
+            stream = out.stream if out is not None else torch.cuda.current_stream(self.device)
+        elif not hasattr(stream, "cuda_stream"):
+            stream = torch.cuda.ExternalStream(int(stream), device=self.device)
+        if out is None:
+            out = ExportedClusters(n_frames, score, classes, (cap_matches, cap_clusters, cap_members), stream, self.device)
+            caps = out.caps
+        else:
+            if out.n_frames != n_frames or out.score != score or out.with_classes != bool(classes):
+                raise ValueError("out was made for %d frames, score %d, classes=%s" % (out.n_frames, out.score, out.with_classes))
+            caps = tuple(min(int(a), b) for a, b in zip((cap_matches, cap_clusters, cap_members), out.caps))
+            out.stream = stream
+        base, n_classes = None, 0
+        if classes and score:
+            base = np.ascontiguousarray(class_base, np.int32).reshape(-1)
+            if len(base) < 2:
+                raise ValueError("class_base must hold one entry per class plus one")
+            n_classes = len(base) - 1
+        t = out._backing
+        ptr = lambda k: t[k].data_ptr() if k in t else None   # noqa: E731
+        desc = _lib.ExportClustersDesc(C.sizeof(_lib.ExportClustersDesc), int(bool(oldest)), int(max_large_frames), int(bool(classes)), score,
+                                       int(class_index), n_classes, 0, templates.h if score else None, base.ctypes.data if base is not None else None,
+                                       float(no_value), ptr("header"), ptr("frame_info"), ptr("matches"), caps[0], ptr("diffs"), ptr("ndiffs"),
+                                       ptr("clusters"), caps[1], ptr("cluster_class"), ptr("members"), caps[2])
+        _lib.check(_lib.lib().lmx_ctx_export_clusters_on(self.h, n_frames, C.byref(desc), int(stream.cuda_stream)))
+        return out
+
     def release(self):
         """Drop the oldest outstanding enqueue without a read-back (its records were consumed on the device)."""
         _lib.check(_lib.lib().lmx_ctx_release(self.h))
@@ -1218,7 +1344,7 @@ class DepthTemplates:
         _lib.check(_lib.lib().lmx_normal_diff_matches(self.h, imgs, len(frames), matches.ctypes.data, offs, int(class_index), dd.ctypes.data, nd.ctypes.data))
         return dd, nd
 
-    KERNELS = ("k_normal_map_frames", "k_verify_diff_records", "k_verify_diff", "k_depth_diff_records")
+    KERNELS = ("k_normal_map_frames", "k_verify_diff_records", "k_verify_diff", "k_depth_diff_records", "k_walk_records_dev")
 
     def set_profiling(self, on=True):
         """Time the object's per-call kernels with device events (lmx_depth_templates_set_profiling); switching it on clears the sums."""
@@ -1240,6 +1366,29 @@ class DepthTemplates:
         out = np.zeros(self._scene_shape + (4,), np.int16)
         _lib.check(_lib.lib().lmx_debug_scene_normals(self.h, int(frame), out.ctypes.data))
         return out
+
+    def debug_walk_records(self, records, header_count, n_candidates, cap, grid_workgroups, class_index=-1, class_base=None, normals=False,
+                           fill=None):
+        """Test hook (lmx_debug_depth_walk_records): the persistent walk of Detector.export_clusters on RAW_MATCH_DTYPE `records` behind a
+        header {n_candidates, header_count}, list capacity `cap`, against the uploaded scene -> (DEPTH_DIFF_DTYPE [n], NORMAL_DIFF_DTYPE [n]
+        or None).  fill: the byte every output entry holds before the kernel runs (default 0)."""
+        records = np.ascontiguousarray(records, RAW_MATCH_DTYPE)
+        n = len(records)
+        d = np.zeros(max(n, 1), DEPTH_DIFF_DTYPE)
+        nd = np.zeros(max(n, 1), NORMAL_DIFF_DTYPE) if normals else None
+        if fill is not None:
+            d.view(np.uint8)[:] = fill
+            if nd is not None:
+                nd.view(np.uint8)[:] = fill
+        base = np.ascontiguousarray(class_base, np.int32).reshape(-1) if class_base is not None else None
+        _lib.check(_lib.lib().lmx_debug_depth_walk_records(self.h, records.ctypes.data if n else None, n, int(header_count), int(n_candidates), int(cap),
+                                                           int(grid_workgroups), int(class_index), base.ctypes.data if base is not None else None,
+                                                           len(base) - 1 if base is not None else 0, d.ctypes.data, nd.ctypes.data if nd is not None else None))
+        return d[:n], (nd[:n] if nd is not None else None)
+
+    def debug_walk_grid(self, workgroups):
+        """Measurement hook (lmx_debug_depth_walk_grid): the grid of the persistent walk from now on; 0 = the default."""
+        _lib.check(_lib.lib().lmx_debug_depth_walk_grid(self.h, int(workgroups)))
 
     def upload_scene(self, depth_frames):
         """The scene of the next Detector.collect_clusters_depth (lmx_depth_templates_upload_scene): a uint16 [H, W] array or a list of
