@@ -948,11 +948,51 @@ lmx_status lmx_debug_depth_walk_grid(lmx_depth_templates* templates, int32_t wor
 /* Device time of the object's kernels that run per call: with profiling on, a pair of events surrounds each launch; kernel_time waits for
  * the launches in flight and returns the sum of their times and their number since profiling was switched on.  Off (the default) no
  * event is created or recorded. */
-enum { LMX_DT_K_NORMAL_MAP_FRAMES = 0, LMX_DT_K_VERIFY_DIFF_RECORDS = 1, LMX_DT_K_VERIFY_DIFF = 2, LMX_DT_K_DEPTH_DIFF_RECORDS = 3, LMX_DT_K_WALK_RECORDS_DEV = 4 };
+enum { LMX_DT_K_NORMAL_MAP_FRAMES = 0, LMX_DT_K_VERIFY_DIFF_RECORDS = 1, LMX_DT_K_VERIFY_DIFF = 2, LMX_DT_K_DEPTH_DIFF_RECORDS = 3, LMX_DT_K_WALK_RECORDS_DEV = 4, LMX_DT_K_POSE_REFINE = 5 };
 lmx_status lmx_depth_templates_set_profiling(lmx_depth_templates* templates, int32_t on);
 lmx_status lmx_depth_templates_kernel_time(lmx_depth_templates* templates, int32_t kernel, double* total_ms, int64_t* launches);
 /* Test hook: the normals of frame `frame` of the uploaded scene as the device holds them (computed now if no call has needed them yet). */
 lmx_status lmx_debug_scene_normals(lmx_depth_templates* templates, int32_t frame, int16_t* out /*[H][W][4]*/);
+
+/* ---- pose refinement of matches against the scene depth (the reference's step 7, icpPoseRefine) ------------------------------------------
+ * Turns "template i matched at (x, y)" into a rigid transform, on the device, from what the object already holds: the model cloud is
+ * template i's depth crop back-projected through the camera it was rendered with, the scene cloud is the scene depth back-projected.
+ * The start is the template's own view moved onto the scene by the centroids of the pixels that meet (the reference's
+ * getPositionBySurfaceCentroid); then up to max_iterations rounds of: projective association in a (2 search_radius + 1)^2 window, one
+ * linearised point-to-point step (6 x 6 Cholesky), quaternion update.  The definition, complete, is the opening comment of
+ * csrc/lmx_pose_refine.hpp: integer sums in 1/16 mm, doubles in one written order, no transcendental function; the device (k_pose_refine,
+ * one 256-lane workgroup per match, all iterations in one launch) equals the CPU build of that header bit for bit.  PCL is not part of
+ * the reference; INTEGRATION.md 3g lists the deviations (no kd-tree, no SVD, no RANSAC rejection).
+ * A record maps a point of the template's view (model camera frame, mm) into the scene camera frame: X_scene = R X_view + t_mm. */
+enum { LMX_POSE_NONE = 0, LMX_POSE_CONVERGED = 1, LMX_POSE_MAX_ITERATIONS = 2, LMX_POSE_NO_OVERLAP = 3, LMX_POSE_LOST = 4 };
+typedef struct lmx_pose_refine_params {
+  uint32_t struct_size;
+  double model_fx, model_fy, model_cx, model_cy;   /* the camera the crops were rendered with */
+  double scene_fx, scene_fy, scene_cx, scene_cy;   /* the depth frame's camera */
+  double max_dist_mm, eps_rot_rad, eps_trans_mm;   /* (0, 1024], >= 0, >= 0 */
+  int32_t max_iterations, min_pairs, search_radius;  /* 0..64, >= 3, 0..2 */
+  const int32_t* rects;                            /* [count][4], NULL: the object's own (lmx_depth_templates_rect) */
+} lmx_pose_refine_params;
+typedef struct lmx_pose_refine_t {
+  double R[9], t_mm[3];
+  double rms_first_mm, rms_last_mm;
+  int32_t n_model, n_pairs_first, n_pairs_last, iterations, status, reserved;
+} lmx_pose_refine_t;
+/* The arguments, staging, errors and scene-forgetting rule of lmx_depth_diff_matches; out[i] belongs to matches[i], matches of another
+ * class get zeroed records (status LMX_POSE_NONE), as does a match of an empty crop.  depth == NULL: the scene that upload_scene /
+ * upload_scene_device left in the object (n_frames must be its frame count); no frame is uploaded again and the scene stays.
+ * LMX_ERR_INVALID_ARG before any device work: a wrong struct_size; focal lengths that are NaN, not positive or outside [2^-10, 2^20];
+ * principal points outside +-2^20; a parameter outside the range noted above; a rect corner of a selected match outside +-2^17; frames
+ * wider or higher than 2^17; depth == NULL without an uploaded scene or with another frame count. */
+lmx_status lmx_pose_refine_matches(lmx_depth_templates* templates, const lmx_image* depth, int32_t n_frames, const lmx_match_t* matches,
+                                   const size_t* offsets, int32_t class_index, const lmx_pose_refine_params* params, lmx_pose_refine_t* out);
+/* The object's pose in the scene camera (the reference's it->pose = tf * it->pose): R_obj = R R_view, t_obj_m = (R (0, 0, 1000 distance) + t_mm) / 1000.
+ * A pure host function. */
+lmx_status lmx_pose_compose(const lmx_mesh_view* view, const lmx_pose_refine_t* refined, double R_obj[9], double t_obj_m[3]);
+/* Test hook: one match against one host frame; next to its record the integer sums of every pass the device ran, sums[max_iterations + 1][17]
+ * (rows of passes that did not run are zeros). */
+lmx_status lmx_debug_pose_refine_sums(lmx_depth_templates* templates, const lmx_image* depth, const lmx_match_t* match,
+                                      const lmx_pose_refine_params* params, lmx_pose_refine_t* out, int64_t* sums);
 
 /* ---- introspection (stage-level parity tests, profiling) ------------------------------------------------- */
 enum {

@@ -414,6 +414,36 @@ class DepthTemplates {
   // could be compared).
   static double value(const lmx_depth_diff_t& d, double no_value = -HUGE_VAL) { return lmx_depth_value(&d, no_value); }
 
+  // Pose refinement (lmx_pose_refine_matches, the reference's icpPoseRefine stage): out[i] belongs to matches[i]; R, t_mm map a point of
+  // the matched template's view (model camera frame, mm) into the scene camera frame.  params.struct_size is filled in here.  With
+  // `depth` one frame holding all matches; without, the scene uploadScene left in the object (one frame).
+  std::vector<lmx_pose_refine_t> refinePoses(const std::vector<lmx_match_t>& matches, lmx_pose_refine_params params, const Image* depth = nullptr,
+                                             int class_index = -1) {
+    std::vector<lmx_pose_refine_t> out(matches.size());
+    params.struct_size = (uint32_t)sizeof(lmx_pose_refine_params);
+    const size_t offsets[2] = {0, matches.size()};
+    lmx_image img;
+    if (depth) img = depth->c();
+    check(lmx_pose_refine_matches(h_, depth ? &img : nullptr, 1, matches.data(), offsets, class_index, &params, out.data()));
+    return out;
+  }
+  std::vector<lmx_pose_refine_t> refinePoses(const std::vector<lmx_match_t>& matches, const lmx_pose_refine_params& params, const Image& depth,
+                                             int class_index = -1) {
+    return refinePoses(matches, params, &depth, class_index);
+  }
+  // The parameters with the defaults of the Python front end; the cameras are the caller's to fill.
+  static lmx_pose_refine_params poseRefineDefaults() {
+    lmx_pose_refine_params p = lmx_pose_refine_params();
+    p.struct_size = (uint32_t)sizeof(lmx_pose_refine_params);
+    p.max_dist_mm = 10.0; p.eps_rot_rad = 1e-5; p.eps_trans_mm = 1e-3;
+    p.max_iterations = 20; p.min_pairs = 16; p.search_radius = 1;
+    return p;
+  }
+  // The object's pose in the scene camera from the matched template's view and its refinePoses record (lmx_pose_compose).
+  static void composePose(const lmx_mesh_view& view, const lmx_pose_refine_t& refined, double R_obj[9], double t_obj_m[3]) {
+    check(lmx_pose_compose(&view, &refined, R_obj, t_obj_m));
+  }
+
   // The normal term (lmx_depth_templates_enable_normals): computes and keeps the normals of every crop; needed before normals(),
   // normalDiff() and lmx_ctx_collect_clusters_depth_normal.  fx, fy: the focal lengths of the camera whose depth frames are checked.
   void enableNormals(double fx, double fy, int difference_threshold = 50, int distance_threshold = 2000) {

@@ -10,6 +10,7 @@ from .detector import Detector, NativeBank, PinnedArena, linemod_detection, merg
 from .detector import DepthTemplates, DEPTH_DIFF_DTYPE, cluster_matches_scored, depth_values  # noqa: F401
 from .detector import NORMAL_DIFF_DTYPE, normal_values, normal_angle_table  # noqa: F401
 from .detector import cluster_matches_classes  # noqa: F401
+from .detector import POSE_REFINE_DTYPE, compose_pose, cluster_leaders  # noqa: F401
 from .detector import device_images  # noqa: F401
 from .detector import ExportedMatches, export_layout  # noqa: F401
 from .detector import ExportedClusters, export_clusters_layout  # noqa: F401

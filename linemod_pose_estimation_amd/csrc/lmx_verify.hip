@@ -24,9 +24,13 @@
 //                  stored normals of a pixel are read next to its two depths, their angle comes out of the chord table in global memory
 //   k_walk_records_dev   the record kernels for a caller that has not read the slot's header (lmx_ctx_export_clusters_on): persistent
 //                  workgroups that take the record count from device memory; see the kernel
+// Pose refinement (lmx_pose_refine_matches; arithmetic and control: lmx_pose_refine.hpp), on the same table and scene:
+//   k_pose_refine  one 256-lane workgroup per match, the same walk over the crop's vectors once per pass, every pass of a job inside one
+//                  launch; see the kernel
 // The host half has one launch site for jobs (run_jobs) and one for records (depth_launch_records), one body for both match-list paths
 // (diff_selected) and one guard in front of every normal-scored call (need_normals).
 #include <algorithm>
+#include <cstddef>
 #include <cstring>
 #include <functional>
 #include <memory>
@@ -35,6 +39,7 @@
 #include "lmx_internal.hpp"
 #include "lmx_depth_verify.hpp"
 #include "lmx_normal_verify.hpp"
+#include "lmx_pose_refine.hpp"
 #include "lmx_mesh_raster.hpp"
 #include "lmx_export_pack.hpp"
 
@@ -316,6 +321,133 @@ __global__ __launch_bounds__(256) void k_walk_records_dev(const WalkDev a) {
   }
 }
 
+// ---- pose refinement (lmx_pose_refine_matches; arithmetic and control: lmx_pose_refine.hpp) ---------------------------------------------------------
+struct PoseJob { int32_t x, y, template_id, frame, rect_x, rect_y, pad0, pad1; };   // frame: as DepthJob's
+static_assert(sizeof(PoseJob) == 32 && sizeof(lmx_pose_refine_t) == 136 && sizeof(pr::Record) == sizeof(lmx_pose_refine_t), "layouts the kernel relies on");
+static_assert(offsetof(pr::Record, rms_first_mm) == offsetof(lmx_pose_refine_t, rms_first_mm) && offsetof(pr::Record, status) == offsetof(lmx_pose_refine_t, status),
+              "pr::Record is lmx_pose_refine_t");
+
+// Every crop pixel t != 0 once, f(i, j, t), spread over the workgroup the way diff_walk spreads them: lanes along the rows, one aligned
+// 16-byte vector each, a narrow crop's rows packed into a wave, waves taking rows (groups of rows) in turn.
+template <typename F>
+__device__ __forceinline__ void crop_pixels(const DepthCrop& c, int lane, int wave, F&& f) {
+  const int vpr = c.pitch / dv::kPitchAlign;
+  const int lanes_per_row = vpr < 64 ? vpr : 64;
+  const int rows_per_pass = 64 / lanes_per_row;
+  const int sub = lane / lanes_per_row, v0 = lane - sub * lanes_per_row;
+  for (int row0 = wave * rows_per_pass; row0 < c.h; row0 += 4 * rows_per_pass) {
+    const int i = row0 + sub;
+    if (sub >= rows_per_pass || i >= c.h) continue;
+    const uint16_t* trow = c.data + (size_t)i * c.pitch;
+    for (int v = v0; v < vpr; v += lanes_per_row) {
+      const int col0 = v * dv::kPitchAlign;
+      const uint4 q = load_global_16(trow + col0);    // past w: the padding, zeros
+      const unsigned long long lo = q.x | ((unsigned long long)q.y << 32), hi = q.z | ((unsigned long long)q.w << 32);
+#pragma unroll 1
+      for (int e = 0; e < dv::kPitchAlign; ++e) {   // one copy of f's code: a pixel's work is hundreds of instructions
+        const uint16_t t = (uint16_t)((e < 4 ? lo : hi) >> (16 * (e & 3)));
+        if (t != 0) f(i, col0 + e, t);
+      }
+    }
+  }
+}
+
+// The first n of a lane's sums added up over the wave, lane 0's totals into the wave's row of `part`; then the barrier behind which any
+// lane may add the four rows.
+__device__ __forceinline__ void wave_sums_to_lds(const int64_t* a, int n, long long (*part)[pr::kSums], int lane, int wave) {
+  for (int k = 0; k < n; ++k) {
+    const long long v = wave_sum<long long>((long long)a[k]);
+    if (lane == 0) part[wave][k] = v;
+  }
+  __syncthreads();
+}
+
+// One 256-lane workgroup per job, every pass of it in this one launch.  A pass: each lane walks its crop pixels under the pose in LDS
+// (pr::pass_pixel: projection, the window of scene reads under the in-image predicate, the pair, its 17 integer terms), wave shuffles,
+// LDS across the four waves; lane 0 adds them, solves, updates (pr::after_pass) and leaves the next pose, its centre and "more" in LDS;
+// a barrier; the next pass.  Integer sums: the result does not depend on which lane took which pixel.  No atomics, no workgroup waits
+// for another.  What is no job (template or frame outside the tables) or has an empty crop gets a zeroed record before any barrier.
+// dbg (null outside the test hook): pass k's sums of job 0 at dbg[k][17].
+__global__ __launch_bounds__(256) void k_pose_refine(const DepthCrop* __restrict__ crops, int32_t count, const PoseJob* __restrict__ jobs,
+                                                     const uint16_t* __restrict__ scene, int32_t n_frames, int W, int H, const pr::Params P,
+                                                     lmx_pose_refine_t* __restrict__ out, long long* __restrict__ dbg) {
+  __shared__ long long s_part[4][pr::kSums];
+  __shared__ pr::Pose s_pose;
+  __shared__ double s_c[3];
+  __shared__ long long s_C[3];
+  __shared__ int s_more;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const PoseJob job = jobs[blockIdx.x];
+  const bool is_job = job.template_id >= 0 && job.template_id < count && job.frame >= 0 && job.frame < n_frames;
+  const DepthCrop c = is_job ? crops[job.template_id] : DepthCrop{nullptr, 0, 0, 0, 0};
+  if (c.w <= 0 || c.h <= 0) {
+    if (tid < (int)(sizeof(lmx_pose_refine_t) / 8)) reinterpret_cast<long long*>(&out[blockIdx.x])[tid] = 0;
+    return;
+  }
+  const uint16_t* frame = scene + (size_t)job.frame * H * W;
+  // lane 0's own: the record, the pose it advances, the control state
+  pr::Record rec;
+  pr::Pose pose0;
+  pr::Control ctl = {0};
+  double m0[3] = {0.0, 0.0, 0.0};
+
+  int64_t a[pr::kSums];
+  for (int k = 0; k < pr::kSums; ++k) a[k] = 0;
+  crop_pixels(c, lane, wave, [&](int i, int j, uint16_t t) {
+    int32_t X = 0, Y = 0;
+    const bool met = dv::scene_row(job.y, i, H, &Y) && dv::scene_col(job.x, j, W, &X);
+    const uint16_t s = met ? frame[(size_t)Y * W + X] : (uint16_t)0;   // read only inside the image
+    pr::place_pixel(job.rect_x, job.rect_y, i, j, t, X, Y, s, a);
+  });
+  wave_sums_to_lds(a, pr::kPlaceSums, s_part, lane, wave);
+  if (tid == 0) {
+    int64_t place[pr::kPlaceSums];
+    for (int k = 0; k < pr::kPlaceSums; ++k) place[k] = s_part[0][k] + s_part[1][k] + s_part[2][k] + s_part[3][k];
+    const bool more = pr::placement(P, place, m0, &pose0, &rec, &ctl);
+    if (more) {
+      int64_t C[3];
+      pr::centre_of(pose0, m0, s_c, C);
+      s_pose = pose0;
+      for (int k = 0; k < 3; ++k) s_C[k] = C[k];
+    } else {
+      *reinterpret_cast<pr::Record*>(&out[blockIdx.x]) = rec;
+    }
+    s_more = more;
+  }
+  __syncthreads();
+  if (!s_more) return;
+  const int64_t dmax = pr::max_dist_ticks(P);
+  const pr::Inverse im = pr::inverse_of(P.model), is = pr::inverse_of(P.scene);
+  for (int32_t k = 0; k <= pr::kMaxIterations; ++k) {   // after_pass ends it after max_iterations + 1 passes at the latest
+    const pr::Pose pose = s_pose;
+    const int64_t C[3] = {s_C[0], s_C[1], s_C[2]};
+    for (int q = 0; q < pr::kSums; ++q) a[q] = 0;
+    crop_pixels(c, lane, wave, [&](int i, int j, uint16_t t) {
+      pr::pass_pixel(P, im, is, pose, C, dmax, job.rect_x, job.rect_y, i, j, t, frame, W, H, (size_t)W, a);
+    });
+    wave_sums_to_lds(a, pr::kSums, s_part, lane, wave);
+    if (tid == 0) {
+      int64_t total[pr::kSums];
+      for (int q = 0; q < pr::kSums; ++q) total[q] = s_part[0][q] + s_part[1][q] + s_part[2][q] + s_part[3][q];
+      if (dbg && blockIdx.x == 0)
+        for (int q = 0; q < pr::kSums; ++q) dbg[(size_t)k * pr::kSums + q] = total[q];
+      const double cc[3] = {s_c[0], s_c[1], s_c[2]};
+      const bool more = pr::after_pass(P, k, total, cc, &pose0, &rec, &ctl);
+      if (more) {
+        int64_t Cn[3];
+        pr::centre_of(pose0, m0, s_c, Cn);
+        s_pose = pose0;
+        for (int q = 0; q < 3; ++q) s_C[q] = Cn[q];
+      } else {
+        *reinterpret_cast<pr::Record*>(&out[blockIdx.x]) = rec;
+      }
+      s_more = more;
+    }
+    __syncthreads();
+    if (!s_more) return;
+  }
+}
+
 }  // namespace
 }  // namespace lmx
 
@@ -348,6 +480,9 @@ struct lmx_depth_templates {
   lmx::DepthJob *d_jobs = nullptr, *h_jobs = nullptr;
   lmx_depth_diff_t *d_out = nullptr, *h_out = nullptr;
   size_t jobs_cap = 0, out_cap = 0;      // entries
+  lmx::PoseJob *d_pjobs = nullptr, *h_pjobs = nullptr;   // lmx_pose_refine_matches: its jobs and records, as d_jobs / d_out
+  lmx_pose_refine_t *d_pout = nullptr, *h_pout = nullptr;
+  size_t pjobs_cap = 0, pout_cap = 0;
   std::vector<uint32_t> sel;             // scratch of a call: the matches it computes
   std::vector<int32_t> sel_slot;         // scratch of a call: the uploaded frame of each of them
   std::vector<int32_t> slot;             // scratch of a call: frame -> uploaded frame, or -1
@@ -373,7 +508,7 @@ struct lmx_depth_templates {
   bool export_read_pending = false;
   int32_t walk_grid = 0;                 // workgroups of k_walk_records_dev; 0: not asked for yet (kWalkGridPerCU per compute unit)
   // lmx_depth_templates_set_profiling: a pair of events around each launch of the kernels below, read out by ..._kernel_time
-  enum { PK_NORMAL_MAP_FRAMES, PK_VERIFY_DIFF_RECORDS, PK_VERIFY_DIFF, PK_DEPTH_DIFF_RECORDS, PK_WALK_RECORDS_DEV, PK_COUNT };
+  enum { PK_NORMAL_MAP_FRAMES, PK_VERIFY_DIFF_RECORDS, PK_VERIFY_DIFF, PK_DEPTH_DIFF_RECORDS, PK_WALK_RECORDS_DEV, PK_POSE_REFINE, PK_COUNT };
   struct ProfEvent { int kernel; hipEvent_t start, stop; };
   bool profiling = false;
   std::vector<ProfEvent> prof_pending;
@@ -515,6 +650,7 @@ struct lmx_depth_templates {
     for (void* p : chunks) (void)hipFree(p);
     (void)hipFree(d_table); (void)hipFree(d_scene); (void)hipFree(d_jobs); (void)hipFree(d_out);
     (void)hipHostFree(h_scene); (void)hipHostFree(h_jobs); (void)hipHostFree(h_out);
+    (void)hipFree(d_pjobs); (void)hipFree(d_pout); (void)hipHostFree(h_pjobs); (void)hipHostFree(h_pout);
     prof_drain();
     free_normal_crops();
     (void)hipFree(d_angle); (void)hipFree(d_scene_normals); (void)hipFree(d_nout); (void)hipHostFree(h_nout);
@@ -1287,4 +1423,141 @@ extern "C" lmx_status lmx_debug_depth_walk_records(lmx_depth_templates* t, const
     t->export_read_pending = false;
     return st;
   });
+}
+
+// ---- pose refinement: the host half -------------------------------------------------------------------------------------------------------------------
+namespace {
+// The parameters as the header takes them, or why they are refused: before any device work.
+lmx_status pose_params(const char* what, const lmx_pose_refine_params* p, lmx::pr::Params* out) {
+  using namespace lmx;
+  if (!p) { set_error("%s: null argument", what); return LMX_ERR_INVALID_ARG; }
+  if (p->struct_size != sizeof(lmx_pose_refine_params)) {
+    set_error("%s: params->struct_size = %u (expected %zu)", what, p->struct_size, sizeof(lmx_pose_refine_params));
+    return LMX_ERR_INVALID_ARG;
+  }
+  const pr::Params P = {{p->model_fx, p->model_fy, p->model_cx, p->model_cy}, {p->scene_fx, p->scene_fy, p->scene_cx, p->scene_cy},
+                        p->max_dist_mm, p->eps_rot_rad, p->eps_trans_mm, p->max_iterations, p->min_pairs, p->search_radius, 0};
+  if (const char* why = pr::check_params(P)) { set_error("%s: %s", what, why); return LMX_ERR_INVALID_ARG; }
+  *out = P;
+  return LMX_OK;
+}
+
+// The body of lmx_pose_refine_matches and of its test hook (dbg: the sums of job 0's passes, [max_iterations + 1][17]).
+lmx_status pose_refine_impl(const char* what, lmx_depth_templates* t, const lmx_image* depth, int32_t n_frames, const lmx_match_t* matches, const size_t* offsets,
+                            int32_t class_index, const lmx_pose_refine_params* params, lmx_pose_refine_t* out, int64_t* dbg) {
+  using namespace lmx;
+  if (!t) { set_error("%s: null argument", what); return LMX_ERR_INVALID_ARG; }
+  pr::Params P;
+  if (lmx_status st = pose_params(what, params, &P)) return st;
+  if (n_frames < 0) { set_error("%s: n_frames = %d", what, n_frames); return LMX_ERR_INVALID_ARG; }
+  if (n_frames == 0) return LMX_OK;
+  if (!offsets) { set_error("%s: null argument", what); return LMX_ERR_INVALID_ARG; }
+  if (offsets[0] != 0) { set_error("%s: offsets[0] = %zu (expected 0)", what, offsets[0]); return LMX_ERR_INVALID_ARG; }
+  for (int32_t f = 0; f < n_frames; ++f)
+    if (offsets[f + 1] < offsets[f]) { set_error("%s: offsets[%d] = %zu is below offsets[%d] = %zu", what, f + 1, offsets[f + 1], f, offsets[f]); return LMX_ERR_INVALID_ARG; }
+  if (depth)
+    if (lmx_status st = check_depth_frames(what, depth, n_frames)) return st;
+  std::lock_guard<std::mutex> lk(t->m);
+  if (!depth && t->scene_frames < 1) { set_error("%s: depth is null and no scene is uploaded: call lmx_depth_templates_upload_scene first", what); return LMX_ERR_INVALID_ARG; }
+  if (!depth && t->scene_frames != n_frames) { set_error("%s: depth is null and the uploaded scene holds %d frames, not %d", what, t->scene_frames, n_frames); return LMX_ERR_INVALID_ARG; }
+  const int32_t W = depth ? depth[0].cols : t->scene_W, H = depth ? depth[0].rows : t->scene_H;
+  if (W >= pr::kMaxCoord / 2 || H >= pr::kMaxCoord / 2) { set_error("%s: frames of %d x %d (sides below %d)", what, W, H, (int)(pr::kMaxCoord / 2)); return LMX_ERR_INVALID_ARG; }
+  const size_t n_matches = offsets[n_frames];
+  if (n_matches == 0) return LMX_OK;
+  if (!matches || !out) { set_error("%s: null argument", what); return LMX_ERR_INVALID_ARG; }
+  if (n_matches > 0x7fffffffull) { set_error("%s: %zu matches in one call", what, n_matches); return LMX_ERR_INVALID_ARG; }
+  const size_t count = t->table.size();
+  const int32_t* rects = params->rects ? params->rects : t->rects.data();
+  t->sel.clear();
+  t->sel_slot.clear();
+  t->slot.assign((size_t)n_frames, -1);
+  int32_t n_slots = 0;
+  for (int32_t f = 0; f < n_frames; ++f)
+    for (size_t i = offsets[f]; i < offsets[f + 1]; ++i) {
+      const lmx_match_t& m = matches[i];
+      if (class_index >= 0 && m.class_index != class_index) continue;
+      if (m.template_id < 0 || (size_t)m.template_id >= count) { set_error("%s: match %zu: template_id %d outside [0, %zu)", what, i, m.template_id, count); return LMX_ERR_INVALID_ARG; }
+      const int32_t* r = rects + (size_t)m.template_id * 4;
+      const int32_t lim = (int32_t)(pr::kMaxCoord / 2);   // a corner within +-2^17 and sides <= 2^14 keep |u|, |v| below 2^18
+      if (r[0] < -lim || r[0] > lim || r[1] < -lim || r[1] > lim) { set_error("%s: match %zu: the rect of template %d starts at (%d, %d) (within +-%d)", what, i, m.template_id, r[0], r[1], lim); return LMX_ERR_INVALID_ARG; }
+      if (t->slot[f] < 0) t->slot[f] = depth ? n_slots++ : f;
+      t->sel.push_back((uint32_t)i);
+      t->sel_slot.push_back(t->slot[f]);
+    }
+  if (!depth) n_slots = t->scene_frames;
+  std::memset(out, 0, n_matches * sizeof(lmx_pose_refine_t));
+  if (dbg) std::memset(dbg, 0, ((size_t)P.max_iterations + 1) * pr::kSums * sizeof(int64_t));
+  if (t->sel.empty()) return LMX_OK;
+  if (lmx_status st = t->ensure_device()) return st;
+  hipStream_t s = t->s;
+  if (depth) {
+    // the frames that have matches take the place of an uploaded scene, as in lmx_depth_diff_matches
+    const size_t frame_bytes = (size_t)W * H * sizeof(uint16_t);
+    if (lmx_status st = t->wait_scene_copies()) return st;
+    if (lmx_status st = t->wait_export_reads()) return st;   // an export's walk may still read the scene the staged frames replace
+    t->scene_frames = 0;
+    t->scene_normals_valid = false;
+    if (lmx_status st = t->grow_scene(frame_bytes * n_slots)) return st;
+    for (int32_t f = 0; f < n_frames; ++f)
+      if (t->slot[f] >= 0)
+        if (lmx_status st = queue_frame(t, depth[f], t->slot[f], W, H)) { t->drain_after_error(); return st; }
+  } else {
+    DV_HIP(hipStreamWaitEvent(s, t->scene_ready, 0));   // the resident scene: behind its copies, whichever stream queued them
+  }
+  const lmx_status st = [&]() -> lmx_status {
+    const size_t n = t->sel.size();
+    if (lmx_status g = lmx_depth_templates::grow_pair(t->d_pjobs, t->h_pjobs, t->pjobs_cap, n)) return g;
+    if (lmx_status g = lmx_depth_templates::grow_pair(t->d_pout, t->h_pout, t->pout_cap, n)) return g;
+    for (size_t k = 0; k < n; ++k) {
+      const lmx_match_t& m = matches[t->sel[k]];
+      const int32_t* r = rects + (size_t)m.template_id * 4;
+      t->h_pjobs[k] = PoseJob{m.x, m.y, m.template_id, t->sel_slot[k], r[0], r[1], 0, 0};
+    }
+    DeviceBuffer d_dbg;
+    const size_t dbg_bytes = ((size_t)P.max_iterations + 1) * pr::kSums * sizeof(int64_t);
+    if (dbg) {
+      DV_HIP(hipMalloc(&d_dbg.p, dbg_bytes));
+      DV_HIP(hipMemsetAsync(d_dbg.p, 0, dbg_bytes, s));
+    }
+    DV_HIP(hipMemcpyAsync(t->d_pjobs, t->h_pjobs, n * sizeof(PoseJob), hipMemcpyHostToDevice, s));
+    const int pe = t->prof_begin(lmx_depth_templates::PK_POSE_REFINE, s);
+    hipLaunchKernelGGL(k_pose_refine, dim3((unsigned)n), dim3(256), 0, s, t->d_table, (int32_t)count, t->d_pjobs, t->d_scene, n_slots, W, H, P, t->d_pout,
+                       d_dbg.as<long long>());
+    t->prof_end(pe, s);
+    DV_HIP(hipGetLastError());
+    DV_HIP(hipMemcpyAsync(t->h_pout, t->d_pout, n * sizeof(lmx_pose_refine_t), hipMemcpyDeviceToHost, s));
+    if (dbg) DV_HIP(hipMemcpyAsync(dbg, d_dbg.p, dbg_bytes, hipMemcpyDeviceToHost, s));
+    DV_HIP(hipStreamSynchronize(s));   // the results are here, the scratch buffer may go
+    for (size_t k = 0; k < n; ++k) out[t->sel[k]] = t->h_pout[k];
+    return LMX_OK;
+  }();
+  if (st != LMX_OK) t->drain_after_error();
+  return st;
+}
+}  // namespace
+
+extern "C" lmx_status lmx_pose_refine_matches(lmx_depth_templates* t, const lmx_image* depth, int32_t n_frames, const lmx_match_t* matches, const size_t* offsets,
+                                              int32_t class_index, const lmx_pose_refine_params* params, lmx_pose_refine_t* out) {
+  return lmx::guarded("lmx_pose_refine_matches", [&]() -> lmx_status {
+    return pose_refine_impl("lmx_pose_refine_matches", t, depth, n_frames, matches, offsets, class_index, params, out, nullptr);
+  });
+}
+
+extern "C" lmx_status lmx_debug_pose_refine_sums(lmx_depth_templates* t, const lmx_image* depth, const lmx_match_t* match, const lmx_pose_refine_params* params,
+                                                 lmx_pose_refine_t* out, int64_t* sums) {
+  return lmx::guarded("lmx_debug_pose_refine_sums", [&]() -> lmx_status {
+    if (!depth || !match || !out || !sums) { lmx::set_error("lmx_debug_pose_refine_sums: null argument"); return LMX_ERR_INVALID_ARG; }
+    const size_t offsets[2] = {0, 1};
+    return pose_refine_impl("lmx_debug_pose_refine_sums", t, depth, 1, match, offsets, -1, params, out, sums);
+  });
+}
+
+extern "C" lmx_status lmx_pose_compose(const lmx_mesh_view* view, const lmx_pose_refine_t* refined, double R_obj[9], double t_obj_m[3]) {
+  if (!view || !refined || !R_obj || !t_obj_m) { lmx::set_error("lmx_pose_compose: null argument"); return LMX_ERR_INVALID_ARG; }
+  const double* R = refined->R;
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) R_obj[3 * i + j] = (R[3 * i] * view->R[j] + R[3 * i + 1] * view->R[3 + j]) + R[3 * i + 2] * view->R[6 + j];
+  const double z = 1000.0 * view->distance;
+  for (int i = 0; i < 3; ++i) t_obj_m[i] = (R[3 * i + 2] * z + refined->t_mm[i]) / 1000.0;
+  return LMX_OK;
 }

@@ -1208,6 +1208,36 @@ def depth_values(diffs):
 
 NORMAL_DIFF_DTYPE = np.dtype([("sum_angle_urad", "<i8"), ("n_normal", "<i4"), ("reserved", "<i4")])
 
+# lmx_pose_refine_t; status: the LMX_POSE_* values
+POSE_REFINE_DTYPE = np.dtype([("R", "<f8", (9,)), ("t_mm", "<f8", (3,)), ("rms_first_mm", "<f8"), ("rms_last_mm", "<f8"), ("n_model", "<i4"),
+                              ("n_pairs_first", "<i4"), ("n_pairs_last", "<i4"), ("iterations", "<i4"), ("status", "<i4"), ("reserved", "<i4")])
+POSE_NONE, POSE_CONVERGED, POSE_MAX_ITERATIONS, POSE_NO_OVERLAP, POSE_LOST = range(5)
+
+
+def compose_pose(view, record):
+    """lmx_pose_compose: the object's pose in the scene camera from the matched template's view (R [3, 3] or 9 values, distance in
+    metres) and its DepthTemplates.refine_poses record -> (R_obj [3, 3], t_obj in metres)."""
+    R, distance = view
+    v = _lib.MeshView((C.c_double * 9)(*np.asarray(R, np.float64).reshape(9)), float(distance))
+    rec = np.zeros(1, POSE_REFINE_DTYPE)
+    rec[0] = record
+    R_obj, t_obj = np.zeros(9), np.zeros(3)
+    _lib.check(_lib.lib().lmx_pose_compose(C.byref(v), rec.ctypes.data, R_obj.ctypes.data, t_obj.ctypes.data))
+    return R_obj.reshape(3, 3), t_obj
+
+
+def cluster_leaders(clusters, members, matches):
+    """The match each cluster's pose is refined from: per cluster the index (into `matches`) of its member of highest similarity, the
+    first in member order on a tie -> int64 [len(clusters)]."""
+    members = np.asarray(members)
+    out = np.zeros(len(clusters), np.int64)
+    for k, c in enumerate(clusters):
+        mi = members[int(c["member_begin"]):int(c["member_begin"]) + int(c["member_count"])]
+        if len(mi) == 0:
+            raise ValueError("cluster %d has no members" % k)
+        out[k] = mi[int(np.argmax(np.asarray(matches)["similarity"][mi]))]
+    return out
+
 
 def normal_values(ddiffs, ndiffs):
     """Per-match values for cluster_matches_scored from DepthTemplates.normal_diff results (lmx_match_value): minus (the mean absolute depth
@@ -1344,7 +1374,59 @@ class DepthTemplates:
         _lib.check(_lib.lib().lmx_normal_diff_matches(self.h, imgs, len(frames), matches.ctypes.data, offs, int(class_index), dd.ctypes.data, nd.ctypes.data))
         return dd, nd
 
-    KERNELS = ("k_normal_map_frames", "k_verify_diff_records", "k_verify_diff", "k_depth_diff_records", "k_walk_records_dev")
+    def _pose_params(self, model_camera, scene_camera, max_dist_mm, max_iterations, min_pairs, search_radius, eps_rot_rad, eps_trans_mm, rects):
+        if model_camera is None or scene_camera is None:
+            raise ValueError("model_camera and scene_camera are (fx, fy, cx, cy)")
+        keep = np.ascontiguousarray(rects, np.int32).reshape(-1, 4) if rects is not None else None
+        if keep is not None and len(keep) != len(self):
+            raise ValueError("rects must hold one (x, y, w, h) per template")
+        p = _lib.PoseRefineParams(C.sizeof(_lib.PoseRefineParams), *[float(v) for v in tuple(model_camera) + tuple(scene_camera)], float(max_dist_mm),
+                                  float(eps_rot_rad), float(eps_trans_mm), int(max_iterations), int(min_pairs), int(search_radius),
+                                  keep.ctypes.data if keep is not None else None)
+        return p, keep
+
+    def refine_poses(self, matches, depth_frames=None, offsets=None, class_index=-1, model_camera=None, scene_camera=None, max_dist_mm=10.0,
+                     max_iterations=20, min_pairs=16, search_radius=1, eps_rot_rad=1e-5, eps_trans_mm=1e-3, rects=None):
+        """A rigid transform per match (lmx_pose_refine_matches; the reference's icpPoseRefine stage) -> POSE_REFINE_DTYPE array: R, t_mm map
+        a point of the matched template's view (model camera frame, mm) into the scene camera frame.  matches / offsets / class_index as
+        diff(); depth_frames None: the scene upload_scene / upload_scene_device left in the object, and offsets must then have one entry
+        per frame of it plus one.  model_camera / scene_camera: (fx, fy, cx, cy) of the camera the crops were rendered with and of the
+        depth frames.  rects: [n, 4] int32 instead of the object's own silhouette boxes (needed for an object made from_crops)."""
+        matches = np.ascontiguousarray(matches, MATCH_DTYPE)
+        if depth_frames is not None:
+            frames, imgs = _depth_images(depth_frames)
+            n_frames = len(frames)
+        else:
+            frames, imgs = None, None
+            n_frames = len(offsets) - 1 if offsets is not None else 1
+        if offsets is None:
+            if n_frames != 1:
+                raise ValueError("offsets are needed with more than one frame")
+            offsets = [0, len(matches)]
+        if len(offsets) != n_frames + 1 or int(offsets[-1]) != len(matches):
+            raise ValueError("offsets must have one entry per frame plus one and end at len(matches)")
+        offs = (C.c_size_t * len(offsets))(*[int(v) for v in offsets])
+        p, keep = self._pose_params(model_camera, scene_camera, max_dist_mm, max_iterations, min_pairs, search_radius, eps_rot_rad, eps_trans_mm, rects)
+        out = np.zeros(len(matches), POSE_REFINE_DTYPE)
+        _lib.check(_lib.lib().lmx_pose_refine_matches(self.h, imgs, n_frames, matches.ctypes.data, offs, int(class_index), C.byref(p), out.ctypes.data))
+        del keep, frames
+        return out
+
+    def debug_pose_refine_sums(self, depth_frame, match, **params):
+        """Test hook (lmx_debug_pose_refine_sums): one match against one host frame -> (its POSE_REFINE_DTYPE record, int64
+        [max_iterations + 1, 17]: the integer sums of every pass the device ran)."""
+        frames, imgs = _depth_images(depth_frame)
+        m = np.ascontiguousarray(match, MATCH_DTYPE).reshape(1)
+        args = dict(max_dist_mm=10.0, max_iterations=20, min_pairs=16, search_radius=1, eps_rot_rad=1e-5, eps_trans_mm=1e-3, rects=None)
+        args.update(params)
+        p, keep = self._pose_params(**args)
+        out = np.zeros(1, POSE_REFINE_DTYPE)
+        sums = np.zeros((int(args["max_iterations"]) + 1, 17), np.int64)
+        _lib.check(_lib.lib().lmx_debug_pose_refine_sums(self.h, imgs, m.ctypes.data, C.byref(p), out.ctypes.data, sums.ctypes.data))
+        del keep, frames
+        return out[0], sums
+
+    KERNELS = ("k_normal_map_frames", "k_verify_diff_records", "k_verify_diff", "k_depth_diff_records", "k_walk_records_dev", "k_pose_refine")
 
     def set_profiling(self, on=True):
         """Time the object's per-call kernels with device events (lmx_depth_templates_set_profiling); switching it on clears the sums."""
