@@ -3,7 +3,7 @@ LMX_CQ_HOST, the workgroup's threads emulated stage by stage) against the oracle
 SURVEY A.2), cv::pyrDown of the source (A.3) and the trainer's squared magnitudes, bit for bit -- image borders (replicate for the blur and
 Sobel, reflect-101 for pyrDown), sizes that are no multiple of the 64 x 16 / 64 x 32 tile, odd sizes, both tile heights.  This checks the
 device algorithm's index arithmetic and weight vectors in this container (no GPU); the machine instructions themselves are checked on the GPU
-by tests/test_gpu_parity.py."""
+by tests/test_gpu_parity.py (scenes) and tests/test_gpu_quantizer_images.py (these families and two more, every launch path)."""
 import ctypes as C
 import os
 import subprocess
@@ -13,6 +13,7 @@ import pytest
 
 from conftest import ROOT
 from oracle import oracle as o
+from quantizer_images import color_image as image   # the families "smooth", "noise", "extreme" (and the later ones) live there
 
 CSRC = os.path.join(ROOT, "linemod_pose_estimation_amd", "csrc")
 
@@ -39,20 +40,10 @@ def run(lib, bgr, th, weak=10.0, pyr=True, mag=False):
     return dst, pd, mg
 
 
-def image(rng, H, W, kind):
-    if kind == "noise":
-        return rng.integers(0, 256, (H, W, 3), dtype=np.uint8)
-    if kind == "smooth":   # gradients strong enough to pass the weak threshold, low-pass so that votes reach 5 of 9
-        a = rng.uniform(0, 255, (H // 8 + 2, W // 8 + 2, 3))
-        a = np.kron(a, np.ones((8, 8, 1)))[:H, :W]
-        return np.ascontiguousarray(np.clip(a + rng.normal(0, 3, a.shape), 0, 255).astype(np.uint8))
-    if kind == "extreme":  # saturating blocks: Sobel outputs reach +-1020, equal channel magnitudes (first-channel precedence)
-        a = (rng.integers(0, 2, (H // 4 + 1, W // 4 + 1, 1)) * 255).astype(np.uint8)
-        return np.ascontiguousarray(np.repeat(np.kron(a, np.ones((4, 4, 1), np.uint8))[:H, :W], 3, axis=2))
-    raise ValueError(kind)
+SIZES = [(96, 128), (64, 64), (37, 70), (33, 131), (16, 8), (5, 4), (4, 5), (130, 66), (67, 257), (240, 320)]
 
 
-@pytest.mark.parametrize("H,W", [(96, 128), (64, 64), (37, 70), (33, 131), (16, 8), (5, 4), (4, 5), (130, 66), (67, 257), (240, 320)])
+@pytest.mark.parametrize("H,W", SIZES)
 @pytest.mark.parametrize("th", [16, 32])
 def test_labels_and_pyrdown_equal_the_oracle(cq, H, W, th):
     rng = np.random.default_rng(H * 1000 + W + th)
