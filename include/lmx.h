@@ -948,7 +948,7 @@ lmx_status lmx_debug_depth_walk_grid(lmx_depth_templates* templates, int32_t wor
 /* Device time of the object's kernels that run per call: with profiling on, a pair of events surrounds each launch; kernel_time waits for
  * the launches in flight and returns the sum of their times and their number since profiling was switched on.  Off (the default) no
  * event is created or recorded. */
-enum { LMX_DT_K_NORMAL_MAP_FRAMES = 0, LMX_DT_K_VERIFY_DIFF_RECORDS = 1, LMX_DT_K_VERIFY_DIFF = 2, LMX_DT_K_DEPTH_DIFF_RECORDS = 3, LMX_DT_K_WALK_RECORDS_DEV = 4, LMX_DT_K_POSE_REFINE = 5 };
+enum { LMX_DT_K_NORMAL_MAP_FRAMES = 0, LMX_DT_K_VERIFY_DIFF_RECORDS = 1, LMX_DT_K_VERIFY_DIFF = 2, LMX_DT_K_DEPTH_DIFF_RECORDS = 3, LMX_DT_K_WALK_RECORDS_DEV = 4, LMX_DT_K_POSE_REFINE = 5, LMX_DT_K_POSE_VERIFY = 6 };
 lmx_status lmx_depth_templates_set_profiling(lmx_depth_templates* templates, int32_t on);
 lmx_status lmx_depth_templates_kernel_time(lmx_depth_templates* templates, int32_t kernel, double* total_ms, int64_t* launches);
 /* Test hook: the normals of frame `frame` of the uploaded scene as the device holds them (computed now if no call has needed them yet). */
@@ -993,6 +993,42 @@ lmx_status lmx_pose_compose(const lmx_mesh_view* view, const lmx_pose_refine_t* 
  * (rows of passes that did not run are zeros). */
 lmx_status lmx_debug_pose_refine_sums(lmx_depth_templates* templates, const lmx_image* depth, const lmx_match_t* match,
                                       const lmx_pose_refine_params* params, lmx_pose_refine_t* out, int64_t* sums);
+
+/* ---- verification of refined poses against the scene's voxel occupancy (the reference's hypothesisVerification) -------------------------
+ * The step after icpPoseRefine: the share of the posed model cloud's points that fall into a voxel holding a scene point.  The model
+ * cloud is the matched template's crop back-projected and moved by the pose of its lmx_pose_refine_t; the voxels form a lattice of side
+ * voxel_mm anchored at the camera origin; the scene points are those of the pixels around the posed model's projection (roi_margin
+ * pixels wider on every side, clipped to the image).  At most 2^18 voxels between the extreme model points (a 32 KiB bitmap); a job with
+ * more gets LMX_VERIFY_GRID_TOO_LARGE.  The definition, complete, is the opening comment of csrc/lmx_pose_verify.hpp; the device
+ * (k_pose_verify, one 256-lane workgroup per match, one launch) equals the CPU build of that header bit for bit.  INTEGRATION.md 3h
+ * lists the deviations from PCL's octree. */
+enum { LMX_VERIFY_NONE = 0, LMX_VERIFY_OK = 1, LMX_VERIFY_EMPTY = 2, LMX_VERIFY_GRID_TOO_LARGE = 3 };
+typedef struct lmx_pose_verify_params {
+  uint32_t struct_size;
+  double model_fx, model_fy, model_cx, model_cy;   /* the camera the crops were rendered with */
+  double scene_fx, scene_fy, scene_cx, scene_cy;   /* the depth frame's camera */
+  double voxel_mm;                                 /* [0.25, 64]; the reference uses 4 */
+  int32_t roi_margin;                              /* 0..64 pixels */
+  const int32_t* rects;                            /* [count][4], NULL: the object's own (lmx_depth_templates_rect) */
+} lmx_pose_verify_params;
+typedef struct lmx_pose_verify_t {
+  double rate;                                     /* n_occupied / n_model (0 without model points) */
+  int32_t n_model, n_tested, n_occupied, n_scene;  /* crop pixels != 0; those in front of the camera; those in a marked voxel; scene pixels that marked one */
+  int32_t cells, status;                           /* voxels between the extreme tested points, min(.., 2^31 - 1); LMX_VERIFY_* */
+  int32_t roi[4];                                  /* x, y, w, h of the scene pixels looked at; zeros: none */
+} lmx_pose_verify_t;
+/* The arguments, staging, depth == NULL rule, scene-forgetting rule and errors of lmx_pose_refine_matches; poses[i] and out[i] belong to
+ * matches[i] (poses: what lmx_pose_refine_matches returned for the same matches; only R and t_mm and status are read).  A match of another
+ * class, a match of an empty crop and a match whose pose has status LMX_POSE_NONE get zeroed records (LMX_VERIFY_NONE).
+ * LMX_ERR_INVALID_ARG before any device work, next to those of lmx_pose_refine_matches: voxel_mm or roi_margin outside its range; with
+ * the match's index in the message, a selected pose with an entry that is not finite, |R[k]| > 2 or |t_mm[k]| > 2^20; frames of more
+ * than 2^31 - 1 pixels. */
+lmx_status lmx_pose_verify_matches(lmx_depth_templates* templates, const lmx_image* depth, int32_t n_frames, const lmx_match_t* matches,
+                                   const size_t* offsets, int32_t class_index, const lmx_pose_refine_t* poses, const lmx_pose_verify_params* params,
+                                   lmx_pose_verify_t* out);
+/* The reference's erase rule (count / model_pts < thresh erases; 0.3 in the carmine node, 0.2 in the ensenso nodes):
+ * keep[i] = status == LMX_VERIFY_OK && !(rate < thresh).  A pure host function. */
+lmx_status lmx_pose_verify_keep(const lmx_pose_verify_t* records, size_t count, double thresh, uint8_t* keep);
 
 /* ---- introspection (stage-level parity tests, profiling) ------------------------------------------------- */
 enum {

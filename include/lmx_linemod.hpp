@@ -444,6 +444,38 @@ class DepthTemplates {
     check(lmx_pose_compose(&view, &refined, R_obj, t_obj_m));
   }
 
+  // Pose verification (lmx_pose_verify_matches, the reference's hypothesisVerification stage): out[i] belongs to matches[i] and poses[i],
+  // the refinePoses record of the same match.  params.struct_size is filled in here.  With `depth` one frame holding all matches;
+  // without, the scene uploadScene left in the object (one frame).
+  std::vector<lmx_pose_verify_t> verifyPoses(const std::vector<lmx_match_t>& matches, const std::vector<lmx_pose_refine_t>& poses, lmx_pose_verify_params params,
+                                             const Image* depth = nullptr, int class_index = -1) {
+    if (poses.size() != matches.size()) throw Exception(LMX_ERR_SHAPE, "DepthTemplates::verifyPoses: one pose per match");
+    std::vector<lmx_pose_verify_t> out(matches.size());
+    params.struct_size = (uint32_t)sizeof(lmx_pose_verify_params);
+    const size_t offsets[2] = {0, matches.size()};
+    lmx_image img;
+    if (depth) img = depth->c();
+    check(lmx_pose_verify_matches(h_, depth ? &img : nullptr, 1, matches.data(), offsets, class_index, poses.data(), &params, out.data()));
+    return out;
+  }
+  std::vector<lmx_pose_verify_t> verifyPoses(const std::vector<lmx_match_t>& matches, const std::vector<lmx_pose_refine_t>& poses, const lmx_pose_verify_params& params,
+                                             const Image& depth, int class_index = -1) {
+    return verifyPoses(matches, poses, params, &depth, class_index);
+  }
+  // The parameters with the defaults of the Python front end (the reference's 4 mm voxels); the cameras are the caller's to fill.
+  static lmx_pose_verify_params poseVerifyDefaults() {
+    lmx_pose_verify_params p = lmx_pose_verify_params();
+    p.struct_size = (uint32_t)sizeof(lmx_pose_verify_params);
+    p.voxel_mm = 4.0; p.roi_margin = 8;
+    return p;
+  }
+  // The reference's erase rule on verifyPoses records (lmx_pose_verify_keep): kept unless rate < thresh.
+  static std::vector<uint8_t> keepVerified(const std::vector<lmx_pose_verify_t>& records, double thresh) {
+    std::vector<uint8_t> keep(records.size());
+    check(lmx_pose_verify_keep(records.data(), records.size(), thresh, keep.data()));
+    return keep;
+  }
+
   // The normal term (lmx_depth_templates_enable_normals): computes and keeps the normals of every crop; needed before normals(),
   // normalDiff() and lmx_ctx_collect_clusters_depth_normal.  fx, fy: the focal lengths of the camera whose depth frames are checked.
   void enableNormals(double fx, double fy, int difference_threshold = 50, int distance_threshold = 2000) {

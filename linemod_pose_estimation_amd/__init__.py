@@ -11,6 +11,7 @@ from .detector import DepthTemplates, DEPTH_DIFF_DTYPE, cluster_matches_scored, 
 from .detector import NORMAL_DIFF_DTYPE, normal_values, normal_angle_table  # noqa: F401
 from .detector import cluster_matches_classes  # noqa: F401
 from .detector import POSE_REFINE_DTYPE, compose_pose, cluster_leaders  # noqa: F401
+from .detector import POSE_VERIFY_DTYPE, keep_verified  # noqa: F401
 from .detector import device_images  # noqa: F401
 from .detector import ExportedMatches, export_layout  # noqa: F401
 from .detector import ExportedClusters, export_clusters_layout  # noqa: F401

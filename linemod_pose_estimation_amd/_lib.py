@@ -35,6 +35,7 @@ SYMBOLS = [
     "lmx_ctx_export_matches_on", "lmx_ctx_debug_enqueue_labels",
     "lmx_ctx_export_clusters_on", "lmx_debug_depth_walk_records", "lmx_debug_depth_walk_grid",
     "lmx_pose_refine_matches", "lmx_pose_compose", "lmx_debug_pose_refine_sums",
+    "lmx_pose_verify_matches", "lmx_pose_verify_keep",
 ]
 
 (LMX_OK, LMX_ERR_INVALID_ARG, LMX_ERR_SHAPE, LMX_ERR_NO_DEVICE, LMX_ERR_HIP, LMX_ERR_OVERFLOW, LMX_ERR_IO,
@@ -148,6 +149,12 @@ class PoseRefineParams(C.Structure):   # lmx_pose_refine_params
                 ("scene_fx", C.c_double), ("scene_fy", C.c_double), ("scene_cx", C.c_double), ("scene_cy", C.c_double),
                 ("max_dist_mm", C.c_double), ("eps_rot_rad", C.c_double), ("eps_trans_mm", C.c_double),
                 ("max_iterations", C.c_int32), ("min_pairs", C.c_int32), ("search_radius", C.c_int32), ("rects", C.c_void_p)]
+
+
+class PoseVerifyParams(C.Structure):   # lmx_pose_verify_params
+    _fields_ = [("struct_size", C.c_uint32), ("model_fx", C.c_double), ("model_fy", C.c_double), ("model_cx", C.c_double), ("model_cy", C.c_double),
+                ("scene_fx", C.c_double), ("scene_fy", C.c_double), ("scene_cx", C.c_double), ("scene_cy", C.c_double),
+                ("voxel_mm", C.c_double), ("roi_margin", C.c_int32), ("rects", C.c_void_p)]
 
 
 class GroupDesc(C.Structure):
@@ -335,6 +342,8 @@ def lib():
     L.lmx_depth_diff_matches.argtypes = [vp, C.POINTER(Image), C.c_int32, vp, C.POINTER(C.c_size_t), C.c_int32, vp]
     L.lmx_pose_refine_matches.argtypes = [vp, C.POINTER(Image), C.c_int32, vp, C.POINTER(C.c_size_t), C.c_int32, C.POINTER(PoseRefineParams), vp]
     L.lmx_pose_compose.argtypes = [C.POINTER(MeshView), vp, vp, vp]
+    L.lmx_pose_verify_matches.argtypes = [vp, C.POINTER(Image), C.c_int32, vp, C.POINTER(C.c_size_t), C.c_int32, vp, C.POINTER(PoseVerifyParams), vp]
+    L.lmx_pose_verify_keep.argtypes = [vp, C.c_size_t, C.c_double, vp]
     L.lmx_debug_pose_refine_sums.argtypes = [vp, C.POINTER(Image), vp, C.POINTER(PoseRefineParams), vp, vp]
     L.lmx_depth_value.argtypes = [C.POINTER(DepthDiff), C.c_double]
     L.lmx_depth_value.restype = C.c_double

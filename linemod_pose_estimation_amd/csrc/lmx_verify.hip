@@ -27,8 +27,12 @@
 // Pose refinement (lmx_pose_refine_matches; arithmetic and control: lmx_pose_refine.hpp), on the same table and scene:
 //   k_pose_refine  one 256-lane workgroup per match, the same walk over the crop's vectors once per pass, every pass of a job inside one
 //                  launch; see the kernel
+// Pose verification (lmx_pose_verify_matches; arithmetic: lmx_pose_verify.hpp), the stage after it:
+//   k_pose_verify  one 256-lane workgroup per match: the crop walk for the voxel grid's extent, a 32 KiB occupancy bitmap in LDS marked
+//                  from the scene pixels of the posed model's region, the crop walk again to count the points in marked voxels; see the kernel
 // The host half has one launch site for jobs (run_jobs) and one for records (depth_launch_records), one body for both match-list paths
-// (diff_selected) and one guard in front of every normal-scored call (need_normals).
+// (diff_selected), one guard in front of every normal-scored call (need_normals) and one body around the launch of both pose stages
+// (pose_call).
 #include <algorithm>
 #include <cstddef>
 #include <cstring>
@@ -40,6 +44,7 @@
 #include "lmx_depth_verify.hpp"
 #include "lmx_normal_verify.hpp"
 #include "lmx_pose_refine.hpp"
+#include "lmx_pose_verify.hpp"
 #include "lmx_mesh_raster.hpp"
 #include "lmx_export_pack.hpp"
 
@@ -448,6 +453,117 @@ __global__ __launch_bounds__(256) void k_pose_refine(const DepthCrop* __restrict
   }
 }
 
+// ---- pose verification (lmx_pose_verify_matches; arithmetic: lmx_pose_verify.hpp) ---------------------------------------------------------------------
+struct VerifyJob { int32_t template_id, frame, rect_x, rect_y; double R[9], t_mm[3]; };   // frame: as DepthJob's
+static_assert(sizeof(VerifyJob) == 112 && sizeof(lmx_pose_verify_t) == 48 && sizeof(pv::Record) == sizeof(lmx_pose_verify_t), "layouts the kernel relies on");
+static_assert(offsetof(pv::Record, n_model) == offsetof(lmx_pose_verify_t, n_model) && offsetof(pv::Record, status) == offsetof(lmx_pose_verify_t, status) &&
+                  offsetof(pv::Record, roi) == offsetof(lmx_pose_verify_t, roi),
+              "pv::Record is lmx_pose_verify_t");
+
+__device__ __forceinline__ int wave_min(int v) {   // lane 0 gets the minimum over the wave's 64 lanes
+  for (int off = 32; off > 0; off >>= 1) { const int o = __shfl_down(v, off, 64); v = o < v ? o : v; }
+  return v;
+}
+__device__ __forceinline__ int wave_max(int v) {
+  for (int off = 32; off > 0; off >>= 1) { const int o = __shfl_down(v, off, 64); v = o > v ? o : v; }
+  return v;
+}
+
+// One 256-lane workgroup per job, four phases in one launch with a barrier between them:
+//   1  the crop walk of k_pose_refine under the job's pose: each lane's extent of keys and projections and its two counts (pv::bounds_pixel),
+//      wave shuffles, LDS across the four waves; lane 0 merges them and leaves the grid and the ROI in LDS (pv::grid_of), or the final
+//      record when there is nothing to test or the grid exceeds the bitmap
+//   2  the bitmap's ceil(cells / 32) words cleared
+//   3  the ROI's pixels in raster order over the workgroup, so that a wave reads runs of neighbouring uint16 of a scene row; every read lies
+//      inside the image (the ROI is clipped to it); a pixel that marks a cell sets its bit with an LDS atomic OR
+//   4  the crop walk again, every point recomputed from phase 1's expressions (no per-point state is kept: a crop holds far more points
+//      than the workgroup has lanes), its bit tested
+// The counts are integer sums and marking is idempotent: the result does not depend on which lane took which pixel.  What is no job
+// (template or frame outside the tables) or has an empty crop gets a zeroed record before any barrier.
+__global__ __launch_bounds__(256) void k_pose_verify(const DepthCrop* __restrict__ crops, int32_t count, const VerifyJob* __restrict__ jobs,
+                                                     const uint16_t* __restrict__ scene, int32_t n_frames, int W, int H, const pv::Params P,
+                                                     lmx_pose_verify_t* __restrict__ out) {
+  __shared__ uint32_t s_bits[pv::kBitmapWords];
+  static_assert(sizeof(s_bits) == 32768 && (size_t)pv::kMaxCells == 8 * sizeof(s_bits), "kMaxCells is the bitmap in LDS");
+  __shared__ pv::Bounds s_bounds[4];
+  __shared__ pv::Grid s_grid;
+  __shared__ int s_count[8];
+  __shared__ int s_more;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const VerifyJob* job = jobs + blockIdx.x;
+  const int32_t template_id = job->template_id, frame_id = job->frame, rect_x = job->rect_x, rect_y = job->rect_y;
+  const bool is_job = template_id >= 0 && template_id < count && frame_id >= 0 && frame_id < n_frames;
+  const DepthCrop c = is_job ? crops[template_id] : DepthCrop{nullptr, 0, 0, 0, 0};
+  if (c.w <= 0 || c.h <= 0) {
+    if (tid < (int)(sizeof(lmx_pose_verify_t) / 8)) reinterpret_cast<long long*>(&out[blockIdx.x])[tid] = 0;
+    return;
+  }
+  const uint16_t* frame = scene + (size_t)frame_id * H * W;
+  double R[9], t_mm[3];
+  for (int k = 0; k < 9; ++k) R[k] = job->R[k];
+  for (int k = 0; k < 3; ++k) t_mm[k] = job->t_mm[k];
+  const int32_t vt = pv::voxel_ticks(P);
+  const pr::Inverse im = pr::inverse_of(P.model), is = pr::inverse_of(P.scene);
+  pv::Record rec;   // lane 0's own
+
+  // 1
+  pv::Bounds b;
+  pv::bounds_init(&b);
+  crop_pixels(c, lane, wave, [&](int i, int j, uint16_t t) { pv::bounds_pixel(P, im, R, t_mm, vt, rect_x, rect_y, i, j, t, &b); });
+  for (int k = 0; k < 3; ++k) { b.lo[k] = wave_min(b.lo[k]); b.hi[k] = wave_max(b.hi[k]); }
+  b.xmin = wave_min(b.xmin); b.ymin = wave_min(b.ymin);
+  b.xmax = wave_max(b.xmax); b.ymax = wave_max(b.ymax);
+  b.n_model = wave_sum(b.n_model); b.n_tested = wave_sum(b.n_tested);
+  if (lane == 0) s_bounds[wave] = b;
+  __syncthreads();
+  if (tid == 0) {
+    pv::Bounds all = s_bounds[0];
+    for (int k = 1; k < 4; ++k) pv::bounds_merge(&all, s_bounds[k]);
+    pv::Grid g;
+    const bool more = pv::grid_of(P, all, W, H, &g, &rec);
+    if (more) s_grid = g;
+    else *reinterpret_cast<pv::Record*>(&out[blockIdx.x]) = rec;
+    s_more = more;
+  }
+  __syncthreads();
+  if (!s_more) return;
+  const pv::Grid g = s_grid;
+
+  // 2
+  const int words = pv::bitmap_words(g);   // <= kBitmapWords: grid_of refused more cells
+  for (int k = tid; k < words; k += 256) s_bits[k] = 0;
+  __syncthreads();
+
+  // 3
+  int n_scene = 0;
+  const int n_roi = g.roi_w * g.roi_h;   // at most W * H, which the host keeps inside an int32
+  for (int q = tid; q < n_roi; q += 256) {
+    const int row = q / g.roi_w, X = g.x0 + (q - row * g.roi_w), Y = g.y0 + row;
+    const uint16_t s = frame[(size_t)Y * W + X];
+    if (s == 0) continue;
+    const int32_t cell = pv::scene_cell(P, is, g, vt, X, Y, s);
+    if (cell < 0) continue;
+    atomicOr(&s_bits[cell >> 5], 1u << (cell & 31));
+    n_scene += 1;
+  }
+  __syncthreads();
+
+  // 4
+  int n_occupied = 0;
+  crop_pixels(c, lane, wave, [&](int i, int j, uint16_t t) {
+    const int32_t cell = pv::model_cell(P, im, R, t_mm, g, vt, rect_x, rect_y, i, j, t);
+    if (cell >= 0) n_occupied += (int)((s_bits[cell >> 5] >> (cell & 31)) & 1u);
+  });
+  n_scene = wave_sum(n_scene);
+  n_occupied = wave_sum(n_occupied);
+  if (lane == 0) { s_count[wave] = n_scene; s_count[4 + wave] = n_occupied; }
+  __syncthreads();
+  if (tid == 0) {
+    pv::finish(s_count[0] + s_count[1] + s_count[2] + s_count[3], s_count[4] + s_count[5] + s_count[6] + s_count[7], &rec);
+    *reinterpret_cast<pv::Record*>(&out[blockIdx.x]) = rec;
+  }
+}
+
 }  // namespace
 }  // namespace lmx
 
@@ -483,6 +599,9 @@ struct lmx_depth_templates {
   lmx::PoseJob *d_pjobs = nullptr, *h_pjobs = nullptr;   // lmx_pose_refine_matches: its jobs and records, as d_jobs / d_out
   lmx_pose_refine_t *d_pout = nullptr, *h_pout = nullptr;
   size_t pjobs_cap = 0, pout_cap = 0;
+  lmx::VerifyJob *d_vjobs = nullptr, *h_vjobs = nullptr;   // lmx_pose_verify_matches: the same pair
+  lmx_pose_verify_t *d_vout = nullptr, *h_vout = nullptr;
+  size_t vjobs_cap = 0, vout_cap = 0;
   std::vector<uint32_t> sel;             // scratch of a call: the matches it computes
   std::vector<int32_t> sel_slot;         // scratch of a call: the uploaded frame of each of them
   std::vector<int32_t> slot;             // scratch of a call: frame -> uploaded frame, or -1
@@ -508,7 +627,7 @@ struct lmx_depth_templates {
   bool export_read_pending = false;
   int32_t walk_grid = 0;                 // workgroups of k_walk_records_dev; 0: not asked for yet (kWalkGridPerCU per compute unit)
   // lmx_depth_templates_set_profiling: a pair of events around each launch of the kernels below, read out by ..._kernel_time
-  enum { PK_NORMAL_MAP_FRAMES, PK_VERIFY_DIFF_RECORDS, PK_VERIFY_DIFF, PK_DEPTH_DIFF_RECORDS, PK_WALK_RECORDS_DEV, PK_POSE_REFINE, PK_COUNT };
+  enum { PK_NORMAL_MAP_FRAMES, PK_VERIFY_DIFF_RECORDS, PK_VERIFY_DIFF, PK_DEPTH_DIFF_RECORDS, PK_WALK_RECORDS_DEV, PK_POSE_REFINE, PK_POSE_VERIFY, PK_COUNT };
   struct ProfEvent { int kernel; hipEvent_t start, stop; };
   bool profiling = false;
   std::vector<ProfEvent> prof_pending;
@@ -651,6 +770,7 @@ struct lmx_depth_templates {
     (void)hipFree(d_table); (void)hipFree(d_scene); (void)hipFree(d_jobs); (void)hipFree(d_out);
     (void)hipHostFree(h_scene); (void)hipHostFree(h_jobs); (void)hipHostFree(h_out);
     (void)hipFree(d_pjobs); (void)hipFree(d_pout); (void)hipHostFree(h_pjobs); (void)hipHostFree(h_pout);
+    (void)hipFree(d_vjobs); (void)hipFree(d_vout); (void)hipHostFree(h_vjobs); (void)hipHostFree(h_vout);
     prof_drain();
     free_normal_crops();
     (void)hipFree(d_angle); (void)hipFree(d_scene_normals); (void)hipFree(d_nout); (void)hipHostFree(h_nout);
@@ -1442,13 +1562,33 @@ lmx_status pose_params(const char* what, const lmx_pose_refine_params* p, lmx::p
   return LMX_OK;
 }
 
-// The body of lmx_pose_refine_matches and of its test hook (dbg: the sums of job 0's passes, [max_iterations + 1][17]).
-lmx_status pose_refine_impl(const char* what, lmx_depth_templates* t, const lmx_image* depth, int32_t n_frames, const lmx_match_t* matches, const size_t* offsets,
-                            int32_t class_index, const lmx_pose_refine_params* params, lmx_pose_refine_t* out, int64_t* dbg) {
+// What lmx_pose_refine_matches and lmx_pose_verify_matches share, everything around the launch: the argument checks, the selection of the
+// matches of the class (t->sel, t->sel_slot), the zeroed records, the staging of the frames that have matches or the wait for the
+// resident scene, the draining after an error.
+struct PoseCall {
+  const char* what;
+  lmx_depth_templates* t;
+  const lmx_image* depth;
+  int32_t n_frames;
+  const lmx_match_t* matches;
+  const size_t* offsets;
+  int32_t class_index;
+  const int32_t* rects;      // the caller's, or null for the object's own
+  void* out;
+  size_t record_bytes;
+  bool input_missing;        // another per-match array of the call is null
+  int64_t max_pixels;        // W * H may not exceed it (0: no such limit)
+};
+// select(i, m): 1 the match is computed, 0 it keeps its zeroed record, -1 it is refused (the error is set).  selected(): after the records
+// were zeroed, before any device work.  launch(W, H, n_slots, count, rects): queues the work on t->s behind the scene and waits for it.
+lmx_status pose_call(const PoseCall& a, const std::function<int(size_t, const lmx_match_t&)>& select, const std::function<void()>& selected,
+                     const std::function<lmx_status(int32_t, int32_t, int32_t, size_t, const int32_t*)>& launch) {
   using namespace lmx;
-  if (!t) { set_error("%s: null argument", what); return LMX_ERR_INVALID_ARG; }
-  pr::Params P;
-  if (lmx_status st = pose_params(what, params, &P)) return st;
+  const char* what = a.what;
+  lmx_depth_templates* t = a.t;
+  const lmx_image* depth = a.depth;
+  const int32_t n_frames = a.n_frames;
+  const size_t* offsets = a.offsets;
   if (n_frames < 0) { set_error("%s: n_frames = %d", what, n_frames); return LMX_ERR_INVALID_ARG; }
   if (n_frames == 0) return LMX_OK;
   if (!offsets) { set_error("%s: null argument", what); return LMX_ERR_INVALID_ARG; }
@@ -1462,31 +1602,35 @@ lmx_status pose_refine_impl(const char* what, lmx_depth_templates* t, const lmx_
   if (!depth && t->scene_frames != n_frames) { set_error("%s: depth is null and the uploaded scene holds %d frames, not %d", what, t->scene_frames, n_frames); return LMX_ERR_INVALID_ARG; }
   const int32_t W = depth ? depth[0].cols : t->scene_W, H = depth ? depth[0].rows : t->scene_H;
   if (W >= pr::kMaxCoord / 2 || H >= pr::kMaxCoord / 2) { set_error("%s: frames of %d x %d (sides below %d)", what, W, H, (int)(pr::kMaxCoord / 2)); return LMX_ERR_INVALID_ARG; }
+  if (a.max_pixels > 0 && (int64_t)W * H > a.max_pixels) { set_error("%s: frames of %d x %d (at most %lld pixels)", what, W, H, (long long)a.max_pixels); return LMX_ERR_INVALID_ARG; }
   const size_t n_matches = offsets[n_frames];
   if (n_matches == 0) return LMX_OK;
-  if (!matches || !out) { set_error("%s: null argument", what); return LMX_ERR_INVALID_ARG; }
+  if (!a.matches || !a.out || a.input_missing) { set_error("%s: null argument", what); return LMX_ERR_INVALID_ARG; }
   if (n_matches > 0x7fffffffull) { set_error("%s: %zu matches in one call", what, n_matches); return LMX_ERR_INVALID_ARG; }
   const size_t count = t->table.size();
-  const int32_t* rects = params->rects ? params->rects : t->rects.data();
+  const int32_t* rects = a.rects ? a.rects : t->rects.data();
   t->sel.clear();
   t->sel_slot.clear();
   t->slot.assign((size_t)n_frames, -1);
   int32_t n_slots = 0;
   for (int32_t f = 0; f < n_frames; ++f)
     for (size_t i = offsets[f]; i < offsets[f + 1]; ++i) {
-      const lmx_match_t& m = matches[i];
-      if (class_index >= 0 && m.class_index != class_index) continue;
+      const lmx_match_t& m = a.matches[i];
+      if (a.class_index >= 0 && m.class_index != a.class_index) continue;
       if (m.template_id < 0 || (size_t)m.template_id >= count) { set_error("%s: match %zu: template_id %d outside [0, %zu)", what, i, m.template_id, count); return LMX_ERR_INVALID_ARG; }
       const int32_t* r = rects + (size_t)m.template_id * 4;
       const int32_t lim = (int32_t)(pr::kMaxCoord / 2);   // a corner within +-2^17 and sides <= 2^14 keep |u|, |v| below 2^18
       if (r[0] < -lim || r[0] > lim || r[1] < -lim || r[1] > lim) { set_error("%s: match %zu: the rect of template %d starts at (%d, %d) (within +-%d)", what, i, m.template_id, r[0], r[1], lim); return LMX_ERR_INVALID_ARG; }
+      const int take = select ? select(i, m) : 1;
+      if (take < 0) return LMX_ERR_INVALID_ARG;
+      if (take == 0) continue;
       if (t->slot[f] < 0) t->slot[f] = depth ? n_slots++ : f;
       t->sel.push_back((uint32_t)i);
       t->sel_slot.push_back(t->slot[f]);
     }
   if (!depth) n_slots = t->scene_frames;
-  std::memset(out, 0, n_matches * sizeof(lmx_pose_refine_t));
-  if (dbg) std::memset(dbg, 0, ((size_t)P.max_iterations + 1) * pr::kSums * sizeof(int64_t));
+  std::memset(a.out, 0, n_matches * a.record_bytes);
+  if (selected) selected();
   if (t->sel.empty()) return LMX_OK;
   if (lmx_status st = t->ensure_device()) return st;
   hipStream_t s = t->s;
@@ -1504,35 +1648,63 @@ lmx_status pose_refine_impl(const char* what, lmx_depth_templates* t, const lmx_
   } else {
     DV_HIP(hipStreamWaitEvent(s, t->scene_ready, 0));   // the resident scene: behind its copies, whichever stream queued them
   }
-  const lmx_status st = [&]() -> lmx_status {
-    const size_t n = t->sel.size();
-    if (lmx_status g = lmx_depth_templates::grow_pair(t->d_pjobs, t->h_pjobs, t->pjobs_cap, n)) return g;
-    if (lmx_status g = lmx_depth_templates::grow_pair(t->d_pout, t->h_pout, t->pout_cap, n)) return g;
-    for (size_t k = 0; k < n; ++k) {
-      const lmx_match_t& m = matches[t->sel[k]];
-      const int32_t* r = rects + (size_t)m.template_id * 4;
-      t->h_pjobs[k] = PoseJob{m.x, m.y, m.template_id, t->sel_slot[k], r[0], r[1], 0, 0};
-    }
-    DeviceBuffer d_dbg;
-    const size_t dbg_bytes = ((size_t)P.max_iterations + 1) * pr::kSums * sizeof(int64_t);
-    if (dbg) {
-      DV_HIP(hipMalloc(&d_dbg.p, dbg_bytes));
-      DV_HIP(hipMemsetAsync(d_dbg.p, 0, dbg_bytes, s));
-    }
-    DV_HIP(hipMemcpyAsync(t->d_pjobs, t->h_pjobs, n * sizeof(PoseJob), hipMemcpyHostToDevice, s));
-    const int pe = t->prof_begin(lmx_depth_templates::PK_POSE_REFINE, s);
-    hipLaunchKernelGGL(k_pose_refine, dim3((unsigned)n), dim3(256), 0, s, t->d_table, (int32_t)count, t->d_pjobs, t->d_scene, n_slots, W, H, P, t->d_pout,
-                       d_dbg.as<long long>());
-    t->prof_end(pe, s);
-    DV_HIP(hipGetLastError());
-    DV_HIP(hipMemcpyAsync(t->h_pout, t->d_pout, n * sizeof(lmx_pose_refine_t), hipMemcpyDeviceToHost, s));
-    if (dbg) DV_HIP(hipMemcpyAsync(dbg, d_dbg.p, dbg_bytes, hipMemcpyDeviceToHost, s));
-    DV_HIP(hipStreamSynchronize(s));   // the results are here, the scratch buffer may go
-    for (size_t k = 0; k < n; ++k) out[t->sel[k]] = t->h_pout[k];
-    return LMX_OK;
-  }();
+  const lmx_status st = launch(W, H, n_slots, count, rects);
   if (st != LMX_OK) t->drain_after_error();
   return st;
+}
+
+// The body of lmx_pose_refine_matches and of its test hook (dbg: the sums of job 0's passes, [max_iterations + 1][17]).
+lmx_status pose_refine_impl(const char* what, lmx_depth_templates* t, const lmx_image* depth, int32_t n_frames, const lmx_match_t* matches, const size_t* offsets,
+                            int32_t class_index, const lmx_pose_refine_params* params, lmx_pose_refine_t* out, int64_t* dbg) {
+  using namespace lmx;
+  if (!t) { set_error("%s: null argument", what); return LMX_ERR_INVALID_ARG; }
+  pr::Params P;
+  if (lmx_status st = pose_params(what, params, &P)) return st;
+  const PoseCall call = {what, t, depth, n_frames, matches, offsets, class_index, params->rects, out, sizeof(lmx_pose_refine_t), false, 0};
+  return pose_call(
+      call, nullptr, [&]() { if (dbg) std::memset(dbg, 0, ((size_t)P.max_iterations + 1) * pr::kSums * sizeof(int64_t)); },
+      [&](int32_t W, int32_t H, int32_t n_slots, size_t count, const int32_t* rects) -> lmx_status {
+        hipStream_t s = t->s;
+        const size_t n = t->sel.size();
+        if (lmx_status g = lmx_depth_templates::grow_pair(t->d_pjobs, t->h_pjobs, t->pjobs_cap, n)) return g;
+        if (lmx_status g = lmx_depth_templates::grow_pair(t->d_pout, t->h_pout, t->pout_cap, n)) return g;
+        for (size_t k = 0; k < n; ++k) {
+          const lmx_match_t& m = matches[t->sel[k]];
+          const int32_t* r = rects + (size_t)m.template_id * 4;
+          t->h_pjobs[k] = PoseJob{m.x, m.y, m.template_id, t->sel_slot[k], r[0], r[1], 0, 0};
+        }
+        DeviceBuffer d_dbg;
+        const size_t dbg_bytes = ((size_t)P.max_iterations + 1) * pr::kSums * sizeof(int64_t);
+        if (dbg) {
+          DV_HIP(hipMalloc(&d_dbg.p, dbg_bytes));
+          DV_HIP(hipMemsetAsync(d_dbg.p, 0, dbg_bytes, s));
+        }
+        DV_HIP(hipMemcpyAsync(t->d_pjobs, t->h_pjobs, n * sizeof(PoseJob), hipMemcpyHostToDevice, s));
+        const int pe = t->prof_begin(lmx_depth_templates::PK_POSE_REFINE, s);
+        hipLaunchKernelGGL(k_pose_refine, dim3((unsigned)n), dim3(256), 0, s, t->d_table, (int32_t)count, t->d_pjobs, t->d_scene, n_slots, W, H, P, t->d_pout,
+                           d_dbg.as<long long>());
+        t->prof_end(pe, s);
+        DV_HIP(hipGetLastError());
+        DV_HIP(hipMemcpyAsync(t->h_pout, t->d_pout, n * sizeof(lmx_pose_refine_t), hipMemcpyDeviceToHost, s));
+        if (dbg) DV_HIP(hipMemcpyAsync(dbg, d_dbg.p, dbg_bytes, hipMemcpyDeviceToHost, s));
+        DV_HIP(hipStreamSynchronize(s));   // the results are here, the scratch buffer may go
+        for (size_t k = 0; k < n; ++k) out[t->sel[k]] = t->h_pout[k];
+        return LMX_OK;
+      });
+}
+
+// The parameters of lmx_pose_verify_matches as the header takes them, or why they are refused: before any device work.
+lmx_status verify_params(const char* what, const lmx_pose_verify_params* p, lmx::pv::Params* out) {
+  using namespace lmx;
+  if (!p) { set_error("%s: null argument", what); return LMX_ERR_INVALID_ARG; }
+  if (p->struct_size != sizeof(lmx_pose_verify_params)) {
+    set_error("%s: params->struct_size = %u (expected %zu)", what, p->struct_size, sizeof(lmx_pose_verify_params));
+    return LMX_ERR_INVALID_ARG;
+  }
+  const pv::Params P = {{p->model_fx, p->model_fy, p->model_cx, p->model_cy}, {p->scene_fx, p->scene_fy, p->scene_cx, p->scene_cy}, p->voxel_mm, p->roi_margin, 0};
+  if (const char* why = pv::check_params(P)) { set_error("%s: %s", what, why); return LMX_ERR_INVALID_ARG; }
+  *out = P;
+  return LMX_OK;
 }
 }  // namespace
 
@@ -1559,5 +1731,62 @@ extern "C" lmx_status lmx_pose_compose(const lmx_mesh_view* view, const lmx_pose
     for (int j = 0; j < 3; ++j) R_obj[3 * i + j] = (R[3 * i] * view->R[j] + R[3 * i + 1] * view->R[3 + j]) + R[3 * i + 2] * view->R[6 + j];
   const double z = 1000.0 * view->distance;
   for (int i = 0; i < 3; ++i) t_obj_m[i] = (R[3 * i + 2] * z + refined->t_mm[i]) / 1000.0;
+  return LMX_OK;
+}
+
+// ---- pose verification: the host half -----------------------------------------------------------------------------------------------------------------
+extern "C" lmx_status lmx_pose_verify_matches(lmx_depth_templates* t, const lmx_image* depth, int32_t n_frames, const lmx_match_t* matches, const size_t* offsets,
+                                              int32_t class_index, const lmx_pose_refine_t* poses, const lmx_pose_verify_params* params, lmx_pose_verify_t* out) {
+  return lmx::guarded("lmx_pose_verify_matches", [&]() -> lmx_status {
+    using namespace lmx;
+    const char* what = "lmx_pose_verify_matches";
+    if (!t) { set_error("%s: null argument", what); return LMX_ERR_INVALID_ARG; }
+    pv::Params P;
+    if (lmx_status st = verify_params(what, params, &P)) return st;
+    const PoseCall call = {what, t, depth, n_frames, matches, offsets, class_index, params->rects, out, sizeof(lmx_pose_verify_t), poses == nullptr, INT32_MAX};
+    return pose_call(
+        call,
+        [&](size_t i, const lmx_match_t&) -> int {
+          const lmx_pose_refine_t& p = poses[i];
+          if (p.status == LMX_POSE_NONE) return 0;   // nothing was refined: a zeroed record
+          if (const char* why = pv::check_pose(p.R, p.t_mm)) { set_error("%s: match %zu: %s", what, i, why); return -1; }
+          return 1;
+        },
+        nullptr,
+        [&](int32_t W, int32_t H, int32_t n_slots, size_t count, const int32_t* rects) -> lmx_status {
+          hipStream_t s = t->s;
+          const size_t n = t->sel.size();
+          if (lmx_status g = lmx_depth_templates::grow_pair(t->d_vjobs, t->h_vjobs, t->vjobs_cap, n)) return g;
+          if (lmx_status g = lmx_depth_templates::grow_pair(t->d_vout, t->h_vout, t->vout_cap, n)) return g;
+          for (size_t k = 0; k < n; ++k) {
+            const lmx_match_t& m = matches[t->sel[k]];
+            const lmx_pose_refine_t& p = poses[t->sel[k]];
+            const int32_t* r = rects + (size_t)m.template_id * 4;
+            VerifyJob& j = t->h_vjobs[k];
+            j.template_id = m.template_id; j.frame = t->sel_slot[k]; j.rect_x = r[0]; j.rect_y = r[1];
+            std::memcpy(j.R, p.R, sizeof(j.R));
+            std::memcpy(j.t_mm, p.t_mm, sizeof(j.t_mm));
+          }
+          DV_HIP(hipMemcpyAsync(t->d_vjobs, t->h_vjobs, n * sizeof(VerifyJob), hipMemcpyHostToDevice, s));
+          const int pe = t->prof_begin(lmx_depth_templates::PK_POSE_VERIFY, s);
+          hipLaunchKernelGGL(k_pose_verify, dim3((unsigned)n), dim3(256), 0, s, t->d_table, (int32_t)count, t->d_vjobs, t->d_scene, n_slots, W, H, P, t->d_vout);
+          t->prof_end(pe, s);
+          DV_HIP(hipGetLastError());
+          DV_HIP(hipMemcpyAsync(t->h_vout, t->d_vout, n * sizeof(lmx_pose_verify_t), hipMemcpyDeviceToHost, s));
+          DV_HIP(hipStreamSynchronize(s));
+          for (size_t k = 0; k < n; ++k) out[t->sel[k]] = t->h_vout[k];
+          return LMX_OK;
+        });
+  });
+}
+
+extern "C" lmx_status lmx_pose_verify_keep(const lmx_pose_verify_t* records, size_t count, double thresh, uint8_t* keep) {
+  if (count == 0) return LMX_OK;
+  if (!records || !keep) { lmx::set_error("lmx_pose_verify_keep: null argument"); return LMX_ERR_INVALID_ARG; }
+  for (size_t i = 0; i < count; ++i) {
+    lmx::pv::Record r;
+    std::memcpy(&r, &records[i], sizeof(r));
+    keep[i] = lmx::pv::keep(r, thresh) ? 1 : 0;
+  }
   return LMX_OK;
 }

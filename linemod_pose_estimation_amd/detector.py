@@ -1214,6 +1214,20 @@ POSE_REFINE_DTYPE = np.dtype([("R", "<f8", (9,)), ("t_mm", "<f8", (3,)), ("rms_f
 POSE_NONE, POSE_CONVERGED, POSE_MAX_ITERATIONS, POSE_NO_OVERLAP, POSE_LOST = range(5)
 
 
+# lmx_pose_verify_t; status: the LMX_VERIFY_* values
+POSE_VERIFY_DTYPE = np.dtype([("rate", "<f8"), ("n_model", "<i4"), ("n_tested", "<i4"), ("n_occupied", "<i4"), ("n_scene", "<i4"), ("cells", "<i4"),
+                              ("status", "<i4"), ("roi", "<i4", (4,))])
+VERIFY_NONE, VERIFY_OK, VERIFY_EMPTY, VERIFY_GRID_TOO_LARGE = range(4)
+
+
+def keep_verified(records, thresh):
+    """The reference's erase rule on DepthTemplates.verify_poses records (lmx_pose_verify_keep): kept iff status is VERIFY_OK and not
+    rate < thresh -> bool [len(records)]."""
+    records = np.asarray(records, POSE_VERIFY_DTYPE)
+    with np.errstate(invalid="ignore"):
+        return (records["status"] == VERIFY_OK) & ~(records["rate"] < float(thresh))
+
+
 def compose_pose(view, record):
     """lmx_pose_compose: the object's pose in the scene camera from the matched template's view (R [3, 3] or 9 values, distance in
     metres) and its DepthTemplates.refine_poses record -> (R_obj [3, 3], t_obj in metres)."""
@@ -1374,12 +1388,32 @@ class DepthTemplates:
         _lib.check(_lib.lib().lmx_normal_diff_matches(self.h, imgs, len(frames), matches.ctypes.data, offs, int(class_index), dd.ctypes.data, nd.ctypes.data))
         return dd, nd
 
-    def _pose_params(self, model_camera, scene_camera, max_dist_mm, max_iterations, min_pairs, search_radius, eps_rot_rad, eps_trans_mm, rects):
-        if model_camera is None or scene_camera is None:
-            raise ValueError("model_camera and scene_camera are (fx, fy, cx, cy)")
+    def _pose_frames(self, matches, depth_frames, offsets):
+        """The frame arguments of refine_poses / verify_poses -> (frames to keep alive, lmx_image array or None, n_frames, size_t offsets)."""
+        if depth_frames is not None:
+            frames, imgs = _depth_images(depth_frames)
+            n_frames = len(frames)
+        else:
+            frames, imgs = None, None
+            n_frames = len(offsets) - 1 if offsets is not None else 1
+        if offsets is None:
+            if n_frames != 1:
+                raise ValueError("offsets are needed with more than one frame")
+            offsets = [0, len(matches)]
+        if len(offsets) != n_frames + 1 or int(offsets[-1]) != len(matches):
+            raise ValueError("offsets must have one entry per frame plus one and end at len(matches)")
+        return frames, imgs, n_frames, (C.c_size_t * len(offsets))(*[int(v) for v in offsets])
+
+    def _pose_rects(self, rects):
         keep = np.ascontiguousarray(rects, np.int32).reshape(-1, 4) if rects is not None else None
         if keep is not None and len(keep) != len(self):
             raise ValueError("rects must hold one (x, y, w, h) per template")
+        return keep
+
+    def _pose_params(self, model_camera, scene_camera, max_dist_mm, max_iterations, min_pairs, search_radius, eps_rot_rad, eps_trans_mm, rects):
+        if model_camera is None or scene_camera is None:
+            raise ValueError("model_camera and scene_camera are (fx, fy, cx, cy)")
+        keep = self._pose_rects(rects)
         p = _lib.PoseRefineParams(C.sizeof(_lib.PoseRefineParams), *[float(v) for v in tuple(model_camera) + tuple(scene_camera)], float(max_dist_mm),
                                   float(eps_rot_rad), float(eps_trans_mm), int(max_iterations), int(min_pairs), int(search_radius),
                                   keep.ctypes.data if keep is not None else None)
@@ -1393,22 +1427,31 @@ class DepthTemplates:
         per frame of it plus one.  model_camera / scene_camera: (fx, fy, cx, cy) of the camera the crops were rendered with and of the
         depth frames.  rects: [n, 4] int32 instead of the object's own silhouette boxes (needed for an object made from_crops)."""
         matches = np.ascontiguousarray(matches, MATCH_DTYPE)
-        if depth_frames is not None:
-            frames, imgs = _depth_images(depth_frames)
-            n_frames = len(frames)
-        else:
-            frames, imgs = None, None
-            n_frames = len(offsets) - 1 if offsets is not None else 1
-        if offsets is None:
-            if n_frames != 1:
-                raise ValueError("offsets are needed with more than one frame")
-            offsets = [0, len(matches)]
-        if len(offsets) != n_frames + 1 or int(offsets[-1]) != len(matches):
-            raise ValueError("offsets must have one entry per frame plus one and end at len(matches)")
-        offs = (C.c_size_t * len(offsets))(*[int(v) for v in offsets])
+        frames, imgs, n_frames, offs = self._pose_frames(matches, depth_frames, offsets)
         p, keep = self._pose_params(model_camera, scene_camera, max_dist_mm, max_iterations, min_pairs, search_radius, eps_rot_rad, eps_trans_mm, rects)
         out = np.zeros(len(matches), POSE_REFINE_DTYPE)
         _lib.check(_lib.lib().lmx_pose_refine_matches(self.h, imgs, n_frames, matches.ctypes.data, offs, int(class_index), C.byref(p), out.ctypes.data))
+        del keep, frames
+        return out
+
+    def verify_poses(self, matches, poses, depth_frames=None, offsets=None, class_index=-1, model_camera=None, scene_camera=None, voxel_mm=4.0, roi_margin=8,
+                     rects=None):
+        """The voxel-occupancy check of refined poses (lmx_pose_verify_matches; the reference's hypothesisVerification stage) ->
+        POSE_VERIFY_DTYPE array.  poses: what refine_poses returned for the same matches; the other arguments as refine_poses.  voxel_mm:
+        the voxel's side; roi_margin: how many pixels around the posed model's projection the scene is looked at."""
+        matches = np.ascontiguousarray(matches, MATCH_DTYPE)
+        poses = np.ascontiguousarray(poses, POSE_REFINE_DTYPE)
+        if len(poses) != len(matches):
+            raise ValueError("poses must hold one record per match")
+        if model_camera is None or scene_camera is None:
+            raise ValueError("model_camera and scene_camera are (fx, fy, cx, cy)")
+        frames, imgs, n_frames, offs = self._pose_frames(matches, depth_frames, offsets)
+        keep = self._pose_rects(rects)
+        p = _lib.PoseVerifyParams(C.sizeof(_lib.PoseVerifyParams), *[float(v) for v in tuple(model_camera) + tuple(scene_camera)], float(voxel_mm), int(roi_margin),
+                                  keep.ctypes.data if keep is not None else None)
+        out = np.zeros(len(matches), POSE_VERIFY_DTYPE)
+        _lib.check(_lib.lib().lmx_pose_verify_matches(self.h, imgs, n_frames, matches.ctypes.data, offs, int(class_index), poses.ctypes.data, C.byref(p),
+                                                      out.ctypes.data))
         del keep, frames
         return out
 
@@ -1426,7 +1469,7 @@ class DepthTemplates:
         del keep, frames
         return out[0], sums
 
-    KERNELS = ("k_normal_map_frames", "k_verify_diff_records", "k_verify_diff", "k_depth_diff_records", "k_walk_records_dev", "k_pose_refine")
+    KERNELS = ("k_normal_map_frames", "k_verify_diff_records", "k_verify_diff", "k_depth_diff_records", "k_walk_records_dev", "k_pose_refine", "k_pose_verify")
 
     def set_profiling(self, on=True):
         """Time the object's per-call kernels with device events (lmx_depth_templates_set_profiling); switching it on clears the sums."""
