@@ -948,7 +948,8 @@ lmx_status lmx_debug_depth_walk_grid(lmx_depth_templates* templates, int32_t wor
 /* Device time of the object's kernels that run per call: with profiling on, a pair of events surrounds each launch; kernel_time waits for
  * the launches in flight and returns the sum of their times and their number since profiling was switched on.  Off (the default) no
  * event is created or recorded. */
-enum { LMX_DT_K_NORMAL_MAP_FRAMES = 0, LMX_DT_K_VERIFY_DIFF_RECORDS = 1, LMX_DT_K_VERIFY_DIFF = 2, LMX_DT_K_DEPTH_DIFF_RECORDS = 3, LMX_DT_K_WALK_RECORDS_DEV = 4, LMX_DT_K_POSE_REFINE = 5, LMX_DT_K_POSE_VERIFY = 6 };
+enum { LMX_DT_K_NORMAL_MAP_FRAMES = 0, LMX_DT_K_VERIFY_DIFF_RECORDS = 1, LMX_DT_K_VERIFY_DIFF = 2, LMX_DT_K_DEPTH_DIFF_RECORDS = 3, LMX_DT_K_WALK_RECORDS_DEV = 4, LMX_DT_K_POSE_REFINE = 5, LMX_DT_K_POSE_VERIFY = 6,
+       LMX_DT_K_POSE_REFINE_CLUSTERS = 7, LMX_DT_K_POSE_VERIFY_CLUSTERS = 8 };
 lmx_status lmx_depth_templates_set_profiling(lmx_depth_templates* templates, int32_t on);
 lmx_status lmx_depth_templates_kernel_time(lmx_depth_templates* templates, int32_t kernel, double* total_ms, int64_t* launches);
 /* Test hook: the normals of frame `frame` of the uploaded scene as the device holds them (computed now if no call has needed them yet). */
@@ -1029,6 +1030,68 @@ lmx_status lmx_pose_verify_matches(lmx_depth_templates* templates, const lmx_ima
 /* The reference's erase rule (count / model_pts < thresh erases; 0.3 in the carmine node, 0.2 in the ensenso nodes):
  * keep[i] = status == LMX_VERIFY_OK && !(rate < thresh).  A pure host function. */
 lmx_status lmx_pose_verify_keep(const lmx_pose_verify_t* records, size_t count, double thresh, uint8_t* keep);
+
+/* ---- both pose stages on the clusters an export left in device memory ------------------------------------------------------------------
+ * What lmx_ctx_export_matches_on (clusters = 1) or lmx_ctx_export_clusters_on wrote goes in; per exported cluster slot k the leader match
+ * (the member of highest similarity, the first on a tie: its index into `matches`), its lmx_pose_refine_t, its lmx_pose_verify_t and the
+ * keep decision of lmx_pose_verify_keep come out, in the caller's device arrays parallel to `clusters`, with no host wait in between: the
+ * counterpart, for a pipelined caller, of reading the clusters back, picking the leaders and calling lmx_pose_refine_matches and
+ * lmx_pose_verify_matches with depth == NULL -- and bit for bit what those return for the same lists and resident scene.  No arithmetic
+ * of its own: csrc/lmx_pose_refine.hpp and csrc/lmx_pose_verify.hpp define the records, csrc/lmx_pose_chain.hpp what is decided from the
+ * lists (k_pose_refine_clusters, k_pose_verify_clusters: one workgroup per slot, a grid of cap_clusters, three launches per call).
+ *   n_live = min(header[3], cap_clusters).  Slots at or above it are not written.  A slot below it whose frame has a status other than 0,
+ *   or a range beyond one of this call's capacities, is dead: leader -1, zeroed records, keep 0.  Every index read from device memory is
+ *   checked before it is used as an address: a cluster without members, a member range beyond min(header[4], cap_members), a member outside
+ *   its frame's matches (leader -1), a template_id outside the table -- with class_base a class outside [0, n_classes) or an id outside
+ *   its class's range --, a rect corner beyond +-2^17 (the leader's index) give zeroed records and flag 2.  A leader of another class than
+ *   class_index gets zeroed records, as in the host calls.  A refined pose that lmx_pose_verify_matches would refuse (an entry not finite,
+ *   |R| > 2, |t_mm| > 2^20) gets a zeroed verify record and flag 4.
+ *   chain_header[8]: [0] n_live, [1] flags (1: the export's list overflowed, or a capacity -- the export's or this call's -- cut live
+ *   slots; 2; 4), [2] slots whose pose status is not LMX_POSE_NONE, [3] slots verified LMX_VERIFY_OK, [4] slots kept, rest 0.
+ * The scene is the resident one (lmx_depth_templates_upload_scene / _device); n_frames must be its frame count.
+ * Ordering (`stream`: the HIP stream the export was given and that will consume the results; NULL = the null stream), as
+ * lmx_ctx_export_clusters_on: the kernels run on the object's own stream, which waits ON THE DEVICE for what `stream` holds at the call
+ * (the export made it wait for its own end) and for the scene's copies; before returning, `stream` is made to wait for the chain's end;
+ * every call that replaces or frees what the kernels read (the scene, the crops, the table) waits for them as it waits for an export's
+ * walk; nothing is waited for or read on the host.  The rects of both parameter sets and class_base are uploaded on the first call and
+ * when they differ from the previous call's (that upload waits for the previous chain).
+ * Refused before anything is queued with LMX_ERR_INVALID_ARG: a struct_size other than the struct's (the desc's or either params');
+ * everything lmx_pose_refine_matches and lmx_pose_verify_matches refuse of their parameters; a null input or output; an array that
+ * hipPointerGetAttributes does not report as plain device memory of the object's device, or that is not aligned to its element (8 bytes
+ * for clusters, poses and checks, 1 for keep, 4 otherwise); cap_clusters 0 or above 2^20; n_frames < 1; no resident scene or one of another
+ * frame count; a class_base that does not start at 0, decreases or does not end at the object's template count; a keep_thresh that is NaN;
+ * a `stream` that is being captured. */
+typedef struct lmx_pose_chain_desc {
+  uint32_t struct_size;            /* sizeof(lmx_pose_chain_desc) */
+  int32_t n_frames;
+  int32_t class_index;             /* as lmx_pose_refine_matches; ignored with class_base */
+  int32_t n_classes;               /* with class_base */
+  const int32_t* class_base;       /* host, [n_classes + 1], as lmx_class_score; NULL: template_id indexes the table directly */
+  const lmx_pose_refine_params* refine;
+  const lmx_pose_verify_params* verify;
+  double keep_thresh;              /* the reference: 0.3 carmine, 0.2 ensenso */
+  /* inputs: what the export wrote, device memory */
+  const uint32_t* header;          /* [16] */
+  const int32_t* frame_info;       /* [n_frames][8] */
+  const lmx_match_t* matches;
+  size_t cap_matches;
+  const lmx_cluster_t* clusters;
+  size_t cap_clusters;
+  const int32_t* members;
+  size_t cap_members;
+  /* outputs, device memory, [cap_clusters] each, parallel to `clusters` */
+  uint32_t* chain_header;          /* [8] */
+  int32_t* leaders;
+  lmx_pose_refine_t* poses;
+  lmx_pose_verify_t* checks;
+  uint8_t* keep;
+} lmx_pose_chain_desc;
+lmx_status lmx_pose_chain_on(lmx_depth_templates* templates, const lmx_pose_chain_desc* desc, void* stream);
+/* Test hook: the same two kernels on lists in HOST memory.  Every pointer of `desc` but class_base and the parameters' is a host array
+ * of the stated capacity (header [16], frame_info [n_frames][8], chain_header [8]; a capacity of 0: the array is not looked at); the five
+ * inputs are uploaded, the five outputs go to the device as they are and come back as the kernels left them: entries the kernels did
+ * not write keep the caller's bytes (chain_header is zeroed by the call itself). */
+lmx_status lmx_debug_pose_chain(lmx_depth_templates* templates, const lmx_pose_chain_desc* desc);
 
 /* ---- introspection (stage-level parity tests, profiling) ------------------------------------------------- */
 enum {

@@ -476,6 +476,18 @@ class DepthTemplates {
     return keep;
   }
 
+  // Both stages on the clusters an export left in device memory (lmx_pose_chain_on): per exported cluster the leader match, its
+  // refinePoses record, its verifyPoses record and the keepVerified decision, written to the caller's device arrays behind `stream` with
+  // no host wait -- what refinePoses / verifyPoses return for the leaders of the same lists, bit for bit.  desc: the export's five arrays
+  // and capacities, the five outputs ([cap_clusters] each, chain_header [8]), refine / verify (their struct_size is the caller's to set:
+  // poseRefineDefaults(), poseVerifyDefaults()), keep_thresh, class_index or class_base; desc.struct_size and, when 0, desc.n_frames (the
+  // frames of the resident scene: 1 unless n_frames says otherwise) are filled in here.  The scene: uploadScene / uploadSceneDevice.
+  void poseChain(lmx_pose_chain_desc desc, void* stream = nullptr, int32_t n_frames = 1) {
+    desc.struct_size = (uint32_t)sizeof(lmx_pose_chain_desc);
+    if (desc.n_frames == 0) desc.n_frames = n_frames;
+    check(lmx_pose_chain_on(h_, &desc, stream));
+  }
+
   // The normal term (lmx_depth_templates_enable_normals): computes and keeps the normals of every crop; needed before normals(),
   // normalDiff() and lmx_ctx_collect_clusters_depth_normal.  fx, fy: the focal lengths of the camera whose depth frames are checked.
   void enableNormals(double fx, double fy, int difference_threshold = 50, int distance_threshold = 2000) {

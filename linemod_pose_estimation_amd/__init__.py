@@ -15,3 +15,4 @@ from .detector import POSE_VERIFY_DTYPE, keep_verified  # noqa: F401
 from .detector import device_images  # noqa: F401
 from .detector import ExportedMatches, export_layout  # noqa: F401
 from .detector import ExportedClusters, export_clusters_layout  # noqa: F401
+from .detector import ExportedPoses, pose_chain_layout  # noqa: F401

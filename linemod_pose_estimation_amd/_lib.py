@@ -36,6 +36,7 @@ SYMBOLS = [
     "lmx_ctx_export_clusters_on", "lmx_debug_depth_walk_records", "lmx_debug_depth_walk_grid",
     "lmx_pose_refine_matches", "lmx_pose_compose", "lmx_debug_pose_refine_sums",
     "lmx_pose_verify_matches", "lmx_pose_verify_keep",
+    "lmx_pose_chain_on", "lmx_debug_pose_chain",
 ]
 
 (LMX_OK, LMX_ERR_INVALID_ARG, LMX_ERR_SHAPE, LMX_ERR_NO_DEVICE, LMX_ERR_HIP, LMX_ERR_OVERFLOW, LMX_ERR_IO,
@@ -155,6 +156,14 @@ class PoseVerifyParams(C.Structure):   # lmx_pose_verify_params
     _fields_ = [("struct_size", C.c_uint32), ("model_fx", C.c_double), ("model_fy", C.c_double), ("model_cx", C.c_double), ("model_cy", C.c_double),
                 ("scene_fx", C.c_double), ("scene_fy", C.c_double), ("scene_cx", C.c_double), ("scene_cy", C.c_double),
                 ("voxel_mm", C.c_double), ("roi_margin", C.c_int32), ("rects", C.c_void_p)]
+
+
+class PoseChainDesc(C.Structure):   # lmx_pose_chain_desc
+    _fields_ = [("struct_size", C.c_uint32), ("n_frames", C.c_int32), ("class_index", C.c_int32), ("n_classes", C.c_int32), ("class_base", C.c_void_p),
+                ("refine", C.POINTER(PoseRefineParams)), ("verify", C.POINTER(PoseVerifyParams)), ("keep_thresh", C.c_double),
+                ("header", C.c_void_p), ("frame_info", C.c_void_p), ("matches", C.c_void_p), ("cap_matches", C.c_size_t),
+                ("clusters", C.c_void_p), ("cap_clusters", C.c_size_t), ("members", C.c_void_p), ("cap_members", C.c_size_t),
+                ("chain_header", C.c_void_p), ("leaders", C.c_void_p), ("poses", C.c_void_p), ("checks", C.c_void_p), ("keep", C.c_void_p)]
 
 
 class GroupDesc(C.Structure):
@@ -344,6 +353,8 @@ def lib():
     L.lmx_pose_compose.argtypes = [C.POINTER(MeshView), vp, vp, vp]
     L.lmx_pose_verify_matches.argtypes = [vp, C.POINTER(Image), C.c_int32, vp, C.POINTER(C.c_size_t), C.c_int32, vp, C.POINTER(PoseVerifyParams), vp]
     L.lmx_pose_verify_keep.argtypes = [vp, C.c_size_t, C.c_double, vp]
+    L.lmx_pose_chain_on.argtypes = [vp, C.POINTER(PoseChainDesc), vp]
+    L.lmx_debug_pose_chain.argtypes = [vp, C.POINTER(PoseChainDesc)]
     L.lmx_debug_pose_refine_sums.argtypes = [vp, C.POINTER(Image), vp, C.POINTER(PoseRefineParams), vp, vp]
     L.lmx_depth_value.argtypes = [C.POINTER(DepthDiff), C.c_double]
     L.lmx_depth_value.restype = C.c_double

@@ -30,6 +30,9 @@
 // Pose verification (lmx_pose_verify_matches; arithmetic: lmx_pose_verify.hpp), the stage after it:
 //   k_pose_verify  one 256-lane workgroup per match: the crop walk for the voxel grid's extent, a 32 KiB occupancy bitmap in LDS marked
 //                  from the scene pixels of the posed model's region, the crop walk again to count the points in marked voxels; see the kernel
+// Both stages on the clusters an export left in device memory (lmx_pose_chain_on; the decisions on the lists: lmx_pose_chain.hpp):
+//   k_pose_refine_clusters / k_pose_verify_clusters   one workgroup per cluster slot, the leader and its job found on the device, then the
+//                  bodies of the two kernels above; see the kernels
 // The host half has one launch site for jobs (run_jobs) and one for records (depth_launch_records), one body for both match-list paths
 // (diff_selected), one guard in front of every normal-scored call (need_normals) and one body around the launch of both pose stages
 // (pose_call).
@@ -45,6 +48,7 @@
 #include "lmx_normal_verify.hpp"
 #include "lmx_pose_refine.hpp"
 #include "lmx_pose_verify.hpp"
+#include "lmx_pose_chain.hpp"
 #include "lmx_mesh_raster.hpp"
 #include "lmx_export_pack.hpp"
 
@@ -373,20 +377,21 @@ __device__ __forceinline__ void wave_sums_to_lds(const int64_t* a, int n, long l
 // a barrier; the next pass.  Integer sums: the result does not depend on which lane took which pixel.  No atomics, no workgroup waits
 // for another.  What is no job (template or frame outside the tables) or has an empty crop gets a zeroed record before any barrier.
 // dbg (null outside the test hook): pass k's sums of job 0 at dbg[k][17].
-__global__ __launch_bounds__(256) void k_pose_refine(const DepthCrop* __restrict__ crops, int32_t count, const PoseJob* __restrict__ jobs,
-                                                     const uint16_t* __restrict__ scene, int32_t n_frames, int W, int H, const pr::Params P,
-                                                     lmx_pose_refine_t* __restrict__ out, long long* __restrict__ dbg) {
+// pose_refine_body is that workgroup's work on one job and its record `out` (dbg: null, or where this job's sums go), shared by
+// k_pose_refine and k_pose_refine_clusters; forceinline: each kernel gets its own copy of the LDS arrays.
+__device__ __forceinline__ void pose_refine_body(const DepthCrop* __restrict__ crops, int32_t count, const PoseJob job, const uint16_t* __restrict__ scene,
+                                                 int32_t n_frames, int W, int H, const pr::Params& P, lmx_pose_refine_t* __restrict__ out,
+                                                 long long* __restrict__ dbg) {
   __shared__ long long s_part[4][pr::kSums];
   __shared__ pr::Pose s_pose;
   __shared__ double s_c[3];
   __shared__ long long s_C[3];
   __shared__ int s_more;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const PoseJob job = jobs[blockIdx.x];
   const bool is_job = job.template_id >= 0 && job.template_id < count && job.frame >= 0 && job.frame < n_frames;
   const DepthCrop c = is_job ? crops[job.template_id] : DepthCrop{nullptr, 0, 0, 0, 0};
   if (c.w <= 0 || c.h <= 0) {
-    if (tid < (int)(sizeof(lmx_pose_refine_t) / 8)) reinterpret_cast<long long*>(&out[blockIdx.x])[tid] = 0;
+    if (tid < (int)(sizeof(lmx_pose_refine_t) / 8)) reinterpret_cast<long long*>(out)[tid] = 0;
     return;
   }
   const uint16_t* frame = scene + (size_t)job.frame * H * W;
@@ -415,7 +420,7 @@ __global__ __launch_bounds__(256) void k_pose_refine(const DepthCrop* __restrict
       s_pose = pose0;
       for (int k = 0; k < 3; ++k) s_C[k] = C[k];
     } else {
-      *reinterpret_cast<pr::Record*>(&out[blockIdx.x]) = rec;
+      *reinterpret_cast<pr::Record*>(out) = rec;
     }
     s_more = more;
   }
@@ -434,7 +439,7 @@ __global__ __launch_bounds__(256) void k_pose_refine(const DepthCrop* __restrict
     if (tid == 0) {
       int64_t total[pr::kSums];
       for (int q = 0; q < pr::kSums; ++q) total[q] = s_part[0][q] + s_part[1][q] + s_part[2][q] + s_part[3][q];
-      if (dbg && blockIdx.x == 0)
+      if (dbg)
         for (int q = 0; q < pr::kSums; ++q) dbg[(size_t)k * pr::kSums + q] = total[q];
       const double cc[3] = {s_c[0], s_c[1], s_c[2]};
       const bool more = pr::after_pass(P, k, total, cc, &pose0, &rec, &ctl);
@@ -444,13 +449,19 @@ __global__ __launch_bounds__(256) void k_pose_refine(const DepthCrop* __restrict
         s_pose = pose0;
         for (int q = 0; q < 3; ++q) s_C[q] = Cn[q];
       } else {
-        *reinterpret_cast<pr::Record*>(&out[blockIdx.x]) = rec;
+        *reinterpret_cast<pr::Record*>(out) = rec;
       }
       s_more = more;
     }
     __syncthreads();
     if (!s_more) return;
   }
+}
+
+__global__ __launch_bounds__(256) void k_pose_refine(const DepthCrop* __restrict__ crops, int32_t count, const PoseJob* __restrict__ jobs,
+                                                     const uint16_t* __restrict__ scene, int32_t n_frames, int W, int H, const pr::Params P,
+                                                     lmx_pose_refine_t* __restrict__ out, long long* __restrict__ dbg) {
+  pose_refine_body(crops, count, jobs[blockIdx.x], scene, n_frames, W, H, P, &out[blockIdx.x], blockIdx.x == 0 ? dbg : nullptr);
 }
 
 // ---- pose verification (lmx_pose_verify_matches; arithmetic: lmx_pose_verify.hpp) ---------------------------------------------------------------------
@@ -480,9 +491,13 @@ __device__ __forceinline__ int wave_max(int v) {
 //      than the workgroup has lanes), its bit tested
 // The counts are integer sums and marking is idempotent: the result does not depend on which lane took which pixel.  What is no job
 // (template or frame outside the tables) or has an empty crop gets a zeroed record before any barrier.
-__global__ __launch_bounds__(256) void k_pose_verify(const DepthCrop* __restrict__ crops, int32_t count, const VerifyJob* __restrict__ jobs,
-                                                     const uint16_t* __restrict__ scene, int32_t n_frames, int W, int H, const pv::Params P,
-                                                     lmx_pose_verify_t* __restrict__ out) {
+// pose_verify_body is that workgroup's work on one job and its record `out`, shared by k_pose_verify and k_pose_verify_clusters.  job_R /
+// job_t: the pose, in device memory.  *rec0: lane 0's copy of the record it stored (zeros where the first lanes store zeros), for a caller
+// that goes on from it.
+__device__ __forceinline__ void pose_verify_body(const DepthCrop* __restrict__ crops, int32_t count, int32_t template_id, int32_t frame_id, int32_t rect_x,
+                                                 int32_t rect_y, const double* __restrict__ job_R, const double* __restrict__ job_t,
+                                                 const uint16_t* __restrict__ scene, int32_t n_frames, int W, int H, const pv::Params& P,
+                                                 lmx_pose_verify_t* __restrict__ out, pv::Record* rec0) {
   __shared__ uint32_t s_bits[pv::kBitmapWords];
   static_assert(sizeof(s_bits) == 32768 && (size_t)pv::kMaxCells == 8 * sizeof(s_bits), "kMaxCells is the bitmap in LDS");
   __shared__ pv::Bounds s_bounds[4];
@@ -490,21 +505,20 @@ __global__ __launch_bounds__(256) void k_pose_verify(const DepthCrop* __restrict
   __shared__ int s_count[8];
   __shared__ int s_more;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const VerifyJob* job = jobs + blockIdx.x;
-  const int32_t template_id = job->template_id, frame_id = job->frame, rect_x = job->rect_x, rect_y = job->rect_y;
   const bool is_job = template_id >= 0 && template_id < count && frame_id >= 0 && frame_id < n_frames;
   const DepthCrop c = is_job ? crops[template_id] : DepthCrop{nullptr, 0, 0, 0, 0};
   if (c.w <= 0 || c.h <= 0) {
-    if (tid < (int)(sizeof(lmx_pose_verify_t) / 8)) reinterpret_cast<long long*>(&out[blockIdx.x])[tid] = 0;
+    if (tid < (int)(sizeof(lmx_pose_verify_t) / 8)) reinterpret_cast<long long*>(out)[tid] = 0;
+    *rec0 = pv::Record{0.0, 0, 0, 0, 0, 0, pv::NONE, {0, 0, 0, 0}};
     return;
   }
   const uint16_t* frame = scene + (size_t)frame_id * H * W;
   double R[9], t_mm[3];
-  for (int k = 0; k < 9; ++k) R[k] = job->R[k];
-  for (int k = 0; k < 3; ++k) t_mm[k] = job->t_mm[k];
+  for (int k = 0; k < 9; ++k) R[k] = job_R[k];
+  for (int k = 0; k < 3; ++k) t_mm[k] = job_t[k];
   const int32_t vt = pv::voxel_ticks(P);
   const pr::Inverse im = pr::inverse_of(P.model), is = pr::inverse_of(P.scene);
-  pv::Record rec;   // lane 0's own
+  pv::Record& rec = *rec0;   // lane 0's own
 
   // 1
   pv::Bounds b;
@@ -522,7 +536,7 @@ __global__ __launch_bounds__(256) void k_pose_verify(const DepthCrop* __restrict
     pv::Grid g;
     const bool more = pv::grid_of(P, all, W, H, &g, &rec);
     if (more) s_grid = g;
-    else *reinterpret_cast<pv::Record*>(&out[blockIdx.x]) = rec;
+    else *reinterpret_cast<pv::Record*>(out) = rec;
     s_more = more;
   }
   __syncthreads();
@@ -560,7 +574,129 @@ __global__ __launch_bounds__(256) void k_pose_verify(const DepthCrop* __restrict
   __syncthreads();
   if (tid == 0) {
     pv::finish(s_count[0] + s_count[1] + s_count[2] + s_count[3], s_count[4] + s_count[5] + s_count[6] + s_count[7], &rec);
-    *reinterpret_cast<pv::Record*>(&out[blockIdx.x]) = rec;
+    *reinterpret_cast<pv::Record*>(out) = rec;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_pose_verify(const DepthCrop* __restrict__ crops, int32_t count, const VerifyJob* __restrict__ jobs,
+                                                     const uint16_t* __restrict__ scene, int32_t n_frames, int W, int H, const pv::Params P,
+                                                     lmx_pose_verify_t* __restrict__ out) {
+  const VerifyJob* job = jobs + blockIdx.x;
+  pv::Record rec;
+  pose_verify_body(crops, count, job->template_id, job->frame, job->rect_x, job->rect_y, job->R, job->t_mm, scene, n_frames, W, H, P, &out[blockIdx.x], &rec);
+}
+
+// ---- both stages on exported clusters (lmx_pose_chain_on; the decisions: lmx_pose_chain.hpp) -----------------------------------------------------------
+static_assert(sizeof(pc::Match) == sizeof(lmx_match_t) && offsetof(pc::Match, template_id) == offsetof(lmx_match_t, template_id) &&
+                  sizeof(pc::Cluster) == sizeof(lmx_cluster_t) && offsetof(pc::Cluster, member_begin) == offsetof(lmx_cluster_t, member_begin),
+              "pc::Match is lmx_match_t, pc::Cluster is lmx_cluster_t");
+struct ChainArgs {
+  pc::Lists L;                 // what an export wrote, device memory
+  pc::Table T;                 // rects and class_base in device memory
+  const DepthCrop* crops;
+  const uint16_t* scene;       // L.n_frames frames of W x H
+  int32_t W, H;
+  uint32_t* chain_header;      // [pc::C_WORDS], zeroed in front of the first kernel
+  int32_t* leaders;
+  lmx_pose_refine_t* poses;
+  lmx_pose_verify_t* checks;
+  uint8_t* keep;
+  double keep_thresh;
+};
+
+// Slot k as the 64 lanes of one wave decide it (every lane returns the same): the frames and the members spread over the lanes, the two
+// reductions by shuffles, everything else lmx_pose_chain.hpp.  The branches of slot_from_claims depend on k and on device memory alone,
+// so the wave stays together through the shuffles.
+__device__ __forceinline__ pc::Slot chain_slot(const ChainArgs& a, uint32_t k, int lane, bool pick, int32_t leader_in) {
+  int32_t claims = 0, first = INT32_MAX;
+  for (int32_t f = lane; f < a.L.n_frames; f += pc::kLanes)
+    if (pc::frame_claims(a.L, f, k)) { claims += 1; first = f < first ? f : first; }
+  claims = __shfl(wave_sum(claims), 0, 64);
+  first = __shfl(wave_min(first), 0, 64);
+  return pc::slot_from_claims(a.L, a.T, k, claims, first, pick, leader_in, [&](const pc::Frame& fr, const pc::Cluster& c) {
+    pc::Best b = pc::best_of_lane(a.L, fr, c, lane, pc::kLanes);
+    for (int off = 32; off > 0; off >>= 1) {
+      pc::Best o;
+      o.key = __shfl_down(b.key, off, 64); o.pos = __shfl_down(b.pos, off, 64); o.bad = __shfl_down(b.bad, off, 64);
+      b = pc::best_merge(b, o);   // a total order: whatever the upper lanes merge in, lane 0 ends with the wave's best
+    }
+    b.key = __shfl(b.key, 0, 64); b.pos = __shfl(b.pos, 0, 64); b.bad = __shfl(b.bad, 0, 64);
+    return b;
+  });
+}
+
+// The slot wave 0 left in LDS, told to the compiler as what it is: the same in every lane (scalar registers, none of the body's vector ones).
+__device__ __forceinline__ pc::Slot uniform_slot(const pc::Slot& v) {
+  pc::Slot s;
+  s.state = __builtin_amdgcn_readfirstlane(v.state); s.flags = (uint32_t)__builtin_amdgcn_readfirstlane((int)v.flags);
+  s.leader = __builtin_amdgcn_readfirstlane(v.leader); s.frame = __builtin_amdgcn_readfirstlane(v.frame);
+  s.x = __builtin_amdgcn_readfirstlane(v.x); s.y = __builtin_amdgcn_readfirstlane(v.y); s.template_id = __builtin_amdgcn_readfirstlane(v.template_id);
+  s.rect_x = __builtin_amdgcn_readfirstlane(v.rect_x); s.rect_y = __builtin_amdgcn_readfirstlane(v.rect_y);
+  return s;
+}
+
+// One 256-lane workgroup per cluster slot, a grid of cap_clusters: the count is in device memory, and a workgroup at or above n_live
+// leaves at once without a store.  Wave 0 decides the slot and leaves it in LDS; one barrier; then either the zeroed record (a dead slot,
+// a broken list, no job) or k_pose_refine's body on the leader's job.  Workgroup 0 also reports n_live and the header's flag; a slot's
+// flags go to chain_header[1] by a vector atomic OR of lane 0.  waves_per_eu(2): the body sits at 251 vector registers; without the
+// attribute the prologue's scalar spills take the kernel a few registers past 256 and to half of k_pose_refine's occupancy.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_pose_refine_clusters(const ChainArgs a, const pr::Params P) {
+  __shared__ pc::Slot s_slot;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const uint32_t k = blockIdx.x, n_live = pc::n_live(a.L);
+  if (k == 0 && tid == 0) {
+    a.chain_header[pc::C_LIVE] = n_live;
+    const uint32_t hf = pc::header_flags(a.L);
+    if (hf) atomicOr(&a.chain_header[pc::C_FLAGS], hf);
+  }
+  if (k >= n_live) return;
+  if (wave == 0) {
+    const pc::Slot s = chain_slot(a, k, lane, true, -1);
+    if (lane == 0) s_slot = s;
+  }
+  __syncthreads();
+  const pc::Slot s = uniform_slot(s_slot);
+  if (tid == 0) {
+    a.leaders[k] = s.leader;
+    if (s.flags) atomicOr(&a.chain_header[pc::C_FLAGS], s.flags);
+  }
+  if (s.state != pc::JOB) {
+    if (tid < (int)(sizeof(lmx_pose_refine_t) / 8)) reinterpret_cast<long long*>(&a.poses[k])[tid] = 0;
+    return;
+  }
+  const PoseJob job = {s.x, s.y, s.template_id, s.frame, s.rect_x, s.rect_y, 0, 0};
+  pose_refine_body(a.crops, a.T.count, job, a.scene, a.L.n_frames, a.W, a.H, P, &a.poses[k], nullptr);
+}
+
+// The same grid behind it.  Wave 0 decides the slot again from leaders[k] (the job is not kept between the kernels: a match, a frame and a
+// rect are cheaper to read again than to store), every lane reads the pose's status, R and t_mm from poses[k]; a slot without a job, a
+// pose of status LMX_POSE_NONE and one that pv::check_pose refuses (the host call refuses the whole call there; here: a flag) get the
+// zeroed record, the others k_pose_verify's body.  Lane 0 then has the record it stored: the keep decision, and the header's three counters
+// by vector atomic adds.
+__global__ __launch_bounds__(256) void k_pose_verify_clusters(const ChainArgs a, const pv::Params P) {
+  __shared__ pc::Slot s_slot;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const uint32_t k = blockIdx.x;
+  if (k >= pc::n_live(a.L)) return;
+  if (wave == 0) {
+    const pc::Slot s = chain_slot(a, k, lane, false, a.leaders[k]);
+    if (lane == 0) s_slot = s;
+  }
+  __syncthreads();
+  const pc::Slot s = uniform_slot(s_slot);
+  const lmx_pose_refine_t* pose = &a.poses[k];
+  const bool refined = s.state == pc::JOB && pose->status != LMX_POSE_NONE;
+  const bool pose_ok = refined && pv::check_pose(pose->R, pose->t_mm) == nullptr;
+  pv::Record rec = {0.0, 0, 0, 0, 0, 0, pv::NONE, {0, 0, 0, 0}};
+  if (pose_ok) pose_verify_body(a.crops, a.T.count, s.template_id, s.frame, s.rect_x, s.rect_y, pose->R, pose->t_mm, a.scene, a.L.n_frames, a.W, a.H, P, &a.checks[k], &rec);
+  else if (tid < (int)(sizeof(lmx_pose_verify_t) / 8)) reinterpret_cast<long long*>(&a.checks[k])[tid] = 0;
+  if (tid == 0) {
+    const bool kept = pv::keep(rec, a.keep_thresh);
+    a.keep[k] = kept ? 1 : 0;
+    if (refined) atomicAdd(&a.chain_header[pc::C_REFINED], 1u);
+    if (refined && !pose_ok) atomicOr(&a.chain_header[pc::C_FLAGS], (uint32_t)pc::FLAG_POSE);
+    if (rec.status == pv::OK) atomicAdd(&a.chain_header[pc::C_VERIFIED], 1u);
+    if (kept) atomicAdd(&a.chain_header[pc::C_KEPT], 1u);
   }
 }
 
@@ -625,9 +761,16 @@ struct lmx_depth_templates {
   // lmx_depth_templates_upload_scene_device on the device
   hipEvent_t export_read = nullptr;
   bool export_read_pending = false;
+  // lmx_pose_chain_on: its kernels run on `s` behind chain_src_ready (recorded on the caller's stream) and record export_read behind them, as
+  // an export's walk does: they read the same things.  The rects of both stages and class_base in device memory, uploaded on the first
+  // call and when they differ from the previous call's
+  struct DevInts { std::vector<int32_t> host; int32_t* dev = nullptr; size_t cap = 0; };
+  DevInts chain_rects_refine, chain_rects_verify, chain_base;
+  hipEvent_t chain_src_ready = nullptr;
   int32_t walk_grid = 0;                 // workgroups of k_walk_records_dev; 0: not asked for yet (kWalkGridPerCU per compute unit)
   // lmx_depth_templates_set_profiling: a pair of events around each launch of the kernels below, read out by ..._kernel_time
-  enum { PK_NORMAL_MAP_FRAMES, PK_VERIFY_DIFF_RECORDS, PK_VERIFY_DIFF, PK_DEPTH_DIFF_RECORDS, PK_WALK_RECORDS_DEV, PK_POSE_REFINE, PK_POSE_VERIFY, PK_COUNT };
+  enum { PK_NORMAL_MAP_FRAMES, PK_VERIFY_DIFF_RECORDS, PK_VERIFY_DIFF, PK_DEPTH_DIFF_RECORDS, PK_WALK_RECORDS_DEV, PK_POSE_REFINE, PK_POSE_VERIFY, PK_POSE_REFINE_CLUSTERS,
+         PK_POSE_VERIFY_CLUSTERS, PK_COUNT };
   struct ProfEvent { int kernel; hipEvent_t start, stop; };
   bool profiling = false;
   std::vector<ProfEvent> prof_pending;
@@ -766,6 +909,8 @@ struct lmx_depth_templates {
     if (s) (void)hipStreamSynchronize(s);
     (void)wait_export_reads();
     if (export_read) (void)hipEventDestroy(export_read);
+    if (chain_src_ready) (void)hipEventDestroy(chain_src_ready);
+    (void)hipFree(chain_rects_refine.dev); (void)hipFree(chain_rects_verify.dev); (void)hipFree(chain_base.dev);
     for (void* p : chunks) (void)hipFree(p);
     (void)hipFree(d_table); (void)hipFree(d_scene); (void)hipFree(d_jobs); (void)hipFree(d_out);
     (void)hipHostFree(h_scene); (void)hipHostFree(h_jobs); (void)hipHostFree(h_out);
@@ -1789,4 +1934,176 @@ extern "C" lmx_status lmx_pose_verify_keep(const lmx_pose_verify_t* records, siz
     keep[i] = lmx::pv::keep(r, thresh) ? 1 : 0;
   }
   return LMX_OK;
+}
+
+// ---- both stages on exported clusters: the host half --------------------------------------------------------------------------------------------------
+namespace {
+// `src` (n entries) in device memory at d.dev: uploaded on first use and when it differs from what the previous call left there.  The
+// previous chain's kernels may still read the old entries: the upload waits for them (they run on t->s).
+lmx_status chain_sync_ints(lmx_depth_templates* t, lmx_depth_templates::DevInts& d, const int32_t* src, size_t n) {
+  if (d.dev && d.host.size() == n && std::equal(d.host.begin(), d.host.end(), src)) return LMX_OK;
+  DV_HIP(hipStreamSynchronize(t->s));
+  if (n > d.cap || !d.dev) {
+    (void)hipFree(d.dev);
+    d.dev = nullptr; d.cap = 0; d.host.clear();
+    const size_t want = std::max<size_t>(n, 1);
+    DV_HIP(hipMalloc(&d.dev, want * sizeof(int32_t)));
+    d.cap = want;
+  }
+  d.host.clear();
+  if (n) DV_HIP(hipMemcpy(d.dev, src, n * sizeof(int32_t), hipMemcpyHostToDevice));
+  d.host.assign(src, src + n);
+  return LMX_OK;
+}
+
+// One array of a chain call: plain device memory of the object's device, aligned to its element.
+lmx_status check_chain_memory(const char* what, const lmx_depth_templates* t, const char* name, const void* p, size_t align) {
+  using namespace lmx;
+  if ((uintptr_t)p & (align - 1)) { set_error("%s: %s must be aligned to %zu bytes", what, name, align); return LMX_ERR_INVALID_ARG; }
+  hipPointerAttribute_t attr;
+  if (hipPointerGetAttributes(&attr, p) != hipSuccess) {   // memory the runtime has never seen
+    (void)hipGetLastError();
+    set_error("%s: %s is not device memory", what, name);
+    return LMX_ERR_INVALID_ARG;
+  }
+  if (attr.type != hipMemoryTypeDevice || attr.device != t->device) {
+    set_error("%s: %s is %s; the arrays are plain device memory of device %d", what, name,
+              attr.type == hipMemoryTypeDevice ? "memory of another device" : "pageable, pinned, managed or other host memory", t->device);
+    return LMX_ERR_INVALID_ARG;
+  }
+  return LMX_OK;
+}
+
+// Everything lmx_pose_chain_on refuses that does not depend on where the arrays live; t->m is held.
+lmx_status chain_check(const char* what, lmx_depth_templates* t, const lmx_pose_chain_desc* d, lmx::pr::Params* PR, lmx::pv::Params* PV) {
+  using namespace lmx;
+  if (d->struct_size != sizeof(lmx_pose_chain_desc)) { set_error("%s: struct_size %u, not %zu", what, d->struct_size, sizeof(lmx_pose_chain_desc)); return LMX_ERR_INVALID_ARG; }
+  if (lmx_status st = pose_params(what, d->refine, PR)) return st;
+  if (lmx_status st = verify_params(what, d->verify, PV)) return st;
+  if (!d->header || !d->frame_info || !d->matches || !d->clusters || !d->members) { set_error("%s: header, frame_info, matches, clusters and members must not be null", what); return LMX_ERR_INVALID_ARG; }
+  if (!d->chain_header || !d->leaders || !d->poses || !d->checks || !d->keep) { set_error("%s: chain_header, leaders, poses, checks and keep must not be null", what); return LMX_ERR_INVALID_ARG; }
+  if (d->cap_clusters < 1 || d->cap_clusters > pc::kMaxClusters) { set_error("%s: cap_clusters = %zu (1 .. 2^20)", what, d->cap_clusters); return LMX_ERR_INVALID_ARG; }
+  if (d->n_frames < 1) { set_error("%s: n_frames = %d", what, d->n_frames); return LMX_ERR_INVALID_ARG; }
+  if (d->keep_thresh != d->keep_thresh) { set_error("%s: keep_thresh is not a number", what); return LMX_ERR_INVALID_ARG; }
+  if (t->scene_frames < 1) { set_error("%s: no scene is uploaded: call lmx_depth_templates_upload_scene first", what); return LMX_ERR_INVALID_ARG; }
+  if (t->scene_frames != d->n_frames) { set_error("%s: the uploaded scene holds %d frames, not %d", what, t->scene_frames, d->n_frames); return LMX_ERR_INVALID_ARG; }
+  const int32_t W = t->scene_W, H = t->scene_H;
+  if (W >= pr::kMaxCoord / 2 || H >= pr::kMaxCoord / 2) { set_error("%s: frames of %d x %d (sides below %d)", what, W, H, (int)(pr::kMaxCoord / 2)); return LMX_ERR_INVALID_ARG; }
+  if ((int64_t)W * H > (int64_t)INT32_MAX) { set_error("%s: frames of %d x %d (at most %d pixels)", what, W, H, INT32_MAX); return LMX_ERR_INVALID_ARG; }
+  if (d->class_base) {
+    if (d->n_classes < 1 || d->n_classes > F2_CLASSES || d->class_base[0] != 0) { set_error("%s: class_base: n_classes 1..%d, class_base[0] = 0", what, F2_CLASSES); return LMX_ERR_INVALID_ARG; }
+    for (int32_t k = 0; k < d->n_classes; ++k)
+      if (d->class_base[k + 1] < d->class_base[k]) { set_error("%s: class_base must not decrease", what); return LMX_ERR_INVALID_ARG; }
+    if ((size_t)d->class_base[d->n_classes] != t->table.size()) { set_error("%s: class_base ends at %d but the object holds %zu depth templates", what, d->class_base[d->n_classes], t->table.size()); return LMX_ERR_INVALID_ARG; }
+  }
+  return LMX_OK;
+}
+
+// Queues the call (every array of `d` in device memory, chain_check passed, t->m held): the tables, the waits, the three launches, the
+// record behind them.  user: the caller's stream, with_user false: the test hook, which orders nothing but t->s itself.
+lmx_status chain_queue(lmx_depth_templates* t, const lmx_pose_chain_desc& d, const lmx::pr::Params& PR, const lmx::pv::Params& PV, hipStream_t user, bool with_user) {
+  using namespace lmx;
+  if (lmx_status st = t->ensure_device()) return st;
+  const size_t count = t->table.size();
+  const int32_t* rr = d.refine->rects ? d.refine->rects : t->rects.data();
+  const int32_t* rv = d.verify->rects ? d.verify->rects : t->rects.data();
+  if (lmx_status st = chain_sync_ints(t, t->chain_rects_refine, rr, count * 4)) return st;
+  const bool same_rects = rv == rr || std::equal(rr, rr + count * 4, rv);
+  if (!same_rects)
+    if (lmx_status st = chain_sync_ints(t, t->chain_rects_verify, rv, count * 4)) return st;
+  if (d.class_base)
+    if (lmx_status st = chain_sync_ints(t, t->chain_base, d.class_base, (size_t)d.n_classes + 1)) return st;
+  if (!t->export_read) DV_HIP(hipEventCreateWithFlags(&t->export_read, hipEventDisableTiming));
+  if (!t->chain_src_ready) DV_HIP(hipEventCreateWithFlags(&t->chain_src_ready, hipEventDisableTiming));
+  hipStream_t s = t->s;
+  if (with_user) {   // behind what the caller's stream holds: the export's end, and whatever still uses the outputs
+    DV_HIP(hipEventRecord(t->chain_src_ready, user));
+    DV_HIP(hipStreamWaitEvent(s, t->chain_src_ready, 0));
+  }
+  if (t->export_read_pending) DV_HIP(hipStreamWaitEvent(s, t->export_read, 0));   // the record below then stands behind every earlier walk too
+  DV_HIP(hipStreamWaitEvent(s, t->scene_ready, 0));
+  ChainArgs a;
+  a.L = pc::Lists{d.header, d.frame_info, d.n_frames, reinterpret_cast<const pc::Match*>(d.matches), reinterpret_cast<const pc::Cluster*>(d.clusters), d.members,
+                  (uint64_t)d.cap_matches, (uint64_t)d.cap_clusters, (uint64_t)d.cap_members};
+  a.T = pc::Table{(int32_t)count, t->chain_rects_refine.dev, d.class_base ? -1 : d.class_index, d.class_base ? t->chain_base.dev : nullptr, d.class_base ? d.n_classes : 0};
+  a.crops = t->d_table; a.scene = t->d_scene; a.W = t->scene_W; a.H = t->scene_H;
+  a.chain_header = d.chain_header; a.leaders = d.leaders; a.poses = d.poses; a.checks = d.checks; a.keep = d.keep; a.keep_thresh = d.keep_thresh;
+  const dim3 grid((unsigned)d.cap_clusters), block(256);
+  DV_HIP(hipMemsetAsync(d.chain_header, 0, pc::C_WORDS * sizeof(uint32_t), s));
+  int pe = t->prof_begin(lmx_depth_templates::PK_POSE_REFINE_CLUSTERS, s);
+  hipLaunchKernelGGL(k_pose_refine_clusters, grid, block, 0, s, a, PR);
+  t->prof_end(pe, s);
+  DV_HIP(hipGetLastError());
+  if (!same_rects) a.T.rects = t->chain_rects_verify.dev;
+  pe = t->prof_begin(lmx_depth_templates::PK_POSE_VERIFY_CLUSTERS, s);
+  hipLaunchKernelGGL(k_pose_verify_clusters, grid, block, 0, s, a, PV);
+  t->prof_end(pe, s);
+  DV_HIP(hipGetLastError());
+  DV_HIP(hipEventRecord(t->export_read, s));
+  t->export_read_pending = true;
+  if (with_user) DV_HIP(hipStreamWaitEvent(user, t->export_read, 0));
+  return LMX_OK;
+}
+}  // namespace
+
+extern "C" lmx_status lmx_pose_chain_on(lmx_depth_templates* t, const lmx_pose_chain_desc* d, void* stream) {
+  return lmx::guarded("lmx_pose_chain_on", [&]() -> lmx_status {
+    using namespace lmx;
+    const char* what = "lmx_pose_chain_on";
+    if (!t || !d) { set_error("%s: null argument", what); return LMX_ERR_INVALID_ARG; }
+    std::lock_guard<std::mutex> lk(t->m);
+    pr::Params PR;
+    pv::Params PV;
+    if (lmx_status st = chain_check(what, t, d, &PR, &PV)) return st;
+    if (lmx_status st = t->ensure_device()) return st;
+    hipStream_t user = static_cast<hipStream_t>(stream);
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    if (user && hipStreamIsCapturing(user, &capturing) != hipSuccess) { (void)hipGetLastError(); set_error("%s: invalid stream", what); return LMX_ERR_INVALID_ARG; }
+    if (capturing != hipStreamCaptureStatusNone) { set_error("%s: the stream is being captured into a graph", what); return LMX_ERR_INVALID_ARG; }
+    const struct { const char* name; const void* p; size_t align; } arrays[] = {
+        {"header", d->header, 4}, {"frame_info", d->frame_info, 4}, {"matches", d->matches, 4}, {"clusters", d->clusters, 8}, {"members", d->members, 4},
+        {"chain_header", d->chain_header, 4}, {"leaders", d->leaders, 4}, {"poses", d->poses, 8}, {"checks", d->checks, 8}, {"keep", d->keep, 1}};
+    for (const auto& arr : arrays)
+      if (lmx_status st = check_chain_memory(what, t, arr.name, arr.p, arr.align)) return st;
+    const lmx_status st = chain_queue(t, *d, PR, PV, user, true);
+    if (st != LMX_OK) t->drain_after_error();
+    return st;
+  });
+}
+
+extern "C" lmx_status lmx_debug_pose_chain(lmx_depth_templates* t, const lmx_pose_chain_desc* d) {
+  return lmx::guarded("lmx_debug_pose_chain", [&]() -> lmx_status {
+    using namespace lmx;
+    const char* what = "lmx_debug_pose_chain";
+    if (!t || !d) { set_error("%s: null argument", what); return LMX_ERR_INVALID_ARG; }
+    std::lock_guard<std::mutex> lk(t->m);
+    pr::Params PR;
+    pv::Params PV;
+    if (lmx_status st = chain_check(what, t, d, &PR, &PV)) return st;
+    if (d->cap_matches > ((size_t)1 << 24) || d->cap_members > ((size_t)1 << 24)) { set_error("%s: at most 2^24 matches and members", what); return LMX_ERR_INVALID_ARG; }
+    if (lmx_status st = t->ensure_device()) return st;
+    hipStream_t s = t->s;
+    const size_t C = d->cap_clusters;
+    // the ten arrays: host address, bytes, input (uploaded) or output (uploaded and read back; chain_header is zeroed by the call)
+    struct Arr { const void* host; size_t bytes; DeviceBuffer dev; };
+    Arr arr[10] = {{d->header, xpack::H_WORDS * sizeof(uint32_t), {}}, {d->frame_info, (size_t)d->n_frames * xpack::I_WORDS * sizeof(int32_t), {}},
+                   {d->matches, d->cap_matches * sizeof(lmx_match_t), {}}, {d->clusters, C * sizeof(lmx_cluster_t), {}}, {d->members, d->cap_members * sizeof(int32_t), {}},
+                   {d->chain_header, pc::C_WORDS * sizeof(uint32_t), {}}, {d->leaders, C * sizeof(int32_t), {}}, {d->poses, C * sizeof(lmx_pose_refine_t), {}},
+                   {d->checks, C * sizeof(lmx_pose_verify_t), {}}, {d->keep, C, {}}};
+    for (Arr& x : arr) {
+      DV_HIP(hipMalloc(&x.dev.p, std::max<size_t>(x.bytes, 16)));
+      if (x.bytes) DV_HIP(hipMemcpyAsync(x.dev.p, x.host, x.bytes, hipMemcpyHostToDevice, s));
+    }
+    lmx_pose_chain_desc dd = *d;
+    dd.header = arr[0].dev.as<uint32_t>(); dd.frame_info = arr[1].dev.as<int32_t>(); dd.matches = arr[2].dev.as<lmx_match_t>();
+    dd.clusters = arr[3].dev.as<lmx_cluster_t>(); dd.members = arr[4].dev.as<int32_t>(); dd.chain_header = arr[5].dev.as<uint32_t>();
+    dd.leaders = arr[6].dev.as<int32_t>(); dd.poses = arr[7].dev.as<lmx_pose_refine_t>(); dd.checks = arr[8].dev.as<lmx_pose_verify_t>();
+    dd.keep = arr[9].dev.as<uint8_t>();
+    lmx_status st = chain_queue(t, dd, PR, PV, nullptr, false);
+    if (st == LMX_OK)
+      for (int k = 5; k < 10; ++k) DV_HIP(hipMemcpyAsync(const_cast<void*>(arr[k].host), arr[k].dev.p, arr[k].bytes, hipMemcpyDeviceToHost, s));
+    DV_HIP(hipStreamSynchronize(s));   // the scratch buffers go when this returns
+    t->export_read_pending = false;
+    return st;
+  });
 }

@@ -291,6 +291,68 @@ class ExportedClusters:
         return out
 
 
+POSE_CHAIN_HEADER_WORDS = 8
+POSE_CHAIN_FLAG_CUT, POSE_CHAIN_FLAG_BOUNDS, POSE_CHAIN_FLAG_POSE = 1, 2, 4      # chain_header[1] (include/lmx.h, lmx_pose_chain_on)
+
+
+def pose_chain_layout(cap_clusters):
+    """The device arrays lmx_pose_chain_on fills, as DepthTemplates.pose_chain allocates them, parallel to an export's clusters: name ->
+    {"shape", "dtype", "nbytes", "align", "cap"} as export_layout.  ValueError: cap_clusters outside 1 .. 2^20."""
+    cap = int(cap_clusters)
+    if cap < 1 or cap > 1 << 20:
+        raise ValueError("cap_clusters must be 1 .. 2^20")
+
+    def entry(shape, dtype, align, n):
+        return {"shape": shape, "dtype": dtype, "nbytes": int(np.prod(shape)) * np.dtype(dtype).itemsize, "align": align, "cap": n}
+    return {"chain_header": entry((POSE_CHAIN_HEADER_WORDS,), "int32", 4, POSE_CHAIN_HEADER_WORDS),
+            "leaders": entry((cap,), "int32", 4, cap),
+            "poses": entry((cap, POSE_REFINE_DTYPE.itemsize // 8), "int64", 8, cap),
+            "checks": entry((cap, POSE_VERIFY_DTYPE.itemsize // 8), "int64", 8, cap),
+            "keep": entry((cap,), "uint8", 1, cap)}
+
+
+class ExportedPoses:
+    """What DepthTemplates.pose_chain leaves on the GPU (lmx_pose_chain_on): torch tensors on the object's device, parallel to the
+    clusters of the export they were computed from, valid for work queued on `stream` after the call --
+      chain_header  int32 [8]       [0] n_live, [1] flags, [2] slots refined, [3] verified OK, [4] kept
+      leaders       int32 [cap]     each cluster's leader, an index into the export's `matches`; -1: a dead slot or a broken list
+      poses         int64 [cap, 17] lmx_pose_refine_t records (POSE_REFINE_DTYPE)
+      checks        int64 [cap, 6]  lmx_pose_verify_t records (POSE_VERIFY_DTYPE)
+      keep          uint8 [cap]     the erase rule of keep_verified
+    Entries at or above n_live are not written.  Any other stream, or the host, synchronises with `stream` first; to_host() does."""
+
+    def __init__(self, cap_clusters, stream, device):
+        import torch
+        self.stream = stream
+        lay = pose_chain_layout(cap_clusters)
+        with torch.cuda.stream(stream):     # the caching allocator hands out memory that is free on this stream
+            t = {k: torch.empty(v["shape"], dtype=getattr(torch, v["dtype"]), device="cuda:%d" % device) for k, v in lay.items()}
+        self._backing = t
+        self.cap = lay["leaders"]["cap"]
+        self.chain_header, self.leaders, self.poses, self.checks, self.keep = (t[k] for k in ("chain_header", "leaders", "poses", "checks", "keep"))
+
+    def clone(self):
+        """A copy made on `stream`, as ExportedMatches.clone: what a pipeline keeps of a result whose tensors the next pose_chain(out=...)
+        writes again."""
+        import torch
+        out = ExportedPoses.__new__(ExportedPoses)
+        out.stream, out.cap = self.stream, self.cap
+        with torch.cuda.stream(self.stream):
+            out._backing = {k: v.clone() for k, v in self._backing.items()}
+        t = out._backing
+        out.chain_header, out.leaders, out.poses, out.checks, out.keep = (t[k] for k in ("chain_header", "leaders", "poses", "checks", "keep"))
+        return out
+
+    def to_host(self):
+        """Synchronises `stream` -> (chain_header int64 [8], leaders int32 [n_live], poses POSE_REFINE_DTYPE [n_live], checks
+        POSE_VERIFY_DTYPE [n_live], keep bool [n_live])."""
+        self.stream.synchronize()
+        hdr = self.chain_header.cpu().numpy().view(np.uint32).astype(np.int64)
+        n = min(int(hdr[0]), self.cap)
+        return (hdr, self.leaders[:n].cpu().numpy(), np.ascontiguousarray(self.poses[:n].cpu().numpy()).view(POSE_REFINE_DTYPE).reshape(-1),
+                np.ascontiguousarray(self.checks[:n].cpu().numpy()).view(POSE_VERIFY_DTYPE).reshape(-1), self.keep[:n].cpu().numpy().astype(bool))
+
+
 class PreparedBatch:
     """lmx_image descriptors of a batch of host frames, built once (the arrays are kept alive by this object)."""
 
@@ -1455,6 +1517,89 @@ class DepthTemplates:
         del keep, frames
         return out
 
+    def _pose_chain_desc(self, n_frames, keep_thresh, class_index, class_base, model_camera, scene_camera, max_dist_mm, max_iterations, min_pairs, search_radius,
+                         eps_rot_rad, eps_trans_mm, voxel_mm, roi_margin, rects):
+        """The parameters of pose_chain / debug_pose_chain -> (PoseChainDesc without its arrays, what it points to)."""
+        pr, keep = self._pose_params(model_camera, scene_camera, max_dist_mm, max_iterations, min_pairs, search_radius, eps_rot_rad, eps_trans_mm, rects)
+        pv = _lib.PoseVerifyParams(C.sizeof(_lib.PoseVerifyParams), *[float(v) for v in tuple(model_camera) + tuple(scene_camera)], float(voxel_mm), int(roi_margin),
+                                   keep.ctypes.data if keep is not None else None)
+        base = np.ascontiguousarray(class_base, np.int32).reshape(-1) if class_base is not None else None
+        if base is not None and len(base) < 2:
+            raise ValueError("class_base must hold one entry per class plus one")
+        d = _lib.PoseChainDesc()
+        d.struct_size, d.n_frames, d.class_index, d.n_classes = C.sizeof(_lib.PoseChainDesc), int(n_frames), int(class_index), len(base) - 1 if base is not None else 0
+        d.class_base = base.ctypes.data if base is not None else None
+        d.refine, d.verify, d.keep_thresh = C.pointer(pr), C.pointer(pv), float(keep_thresh)
+        return d, (pr, pv, keep, base)
+
+    def pose_chain(self, exported, keep_thresh, model_camera=None, scene_camera=None, max_dist_mm=10.0, max_iterations=20, min_pairs=16, search_radius=1,
+                   eps_rot_rad=1e-5, eps_trans_mm=1e-3, voxel_mm=4.0, roi_margin=8, rects=None, class_index=-1, class_base=None, stream=None, out=None):
+        """Both pose stages on the clusters an export left on the GPU (lmx_pose_chain_on) -> ExportedPoses: per exported cluster the
+        leader of cluster_leaders, its refine_poses record, its verify_poses record and the keep_verified decision, equal in every byte to
+        those four run on to_host()'s lists against the same resident scene -- with no host wait in between.  exported: an
+        ExportedMatches (clusters=True) or an ExportedClusters; the scene: what upload_scene / upload_scene_device left in this object, of
+        exported.n_frames frames.  keep_thresh: the reference's 0.3 (carmine) or 0.2 (ensenso).  The keywords of refine_poses and
+        verify_poses; class_base: the cumulative template counts of the classes joined in this object (append), a match's template_id is
+        then rebased by its class.  stream: default exported.stream.  out: an ExportedPoses of an earlier call with room for the export's
+        cluster capacity, written again in place of fresh tensors."""
+        import torch
+        if getattr(exported, "clusters", None) is None or exported.members is None:
+            raise ValueError("exported holds no clusters (export_matches(clusters=True) or export_clusters)")
+        if model_camera is None or scene_camera is None:
+            raise ValueError("model_camera and scene_camera are (fx, fy, cx, cy)")
+        device = exported.header.device.index
+        if stream is None:
+            stream = exported.stream
+        elif not hasattr(stream, "cuda_stream"):
+            stream = torch.cuda.ExternalStream(int(stream), device=device)
+        caps = exported.caps
+        if caps[1] < 1:
+            raise ValueError("the export has no room for clusters")
+        if out is None:
+            out = ExportedPoses(caps[1], stream, device)
+        else:
+            if out.cap < caps[1]:
+                raise ValueError("out was made for %d clusters, the export holds up to %d" % (out.cap, caps[1]))
+            out.stream = stream
+        d, alive = self._pose_chain_desc(exported.n_frames, keep_thresh, class_index, class_base, model_camera, scene_camera, max_dist_mm, max_iterations, min_pairs,
+                                         search_radius, eps_rot_rad, eps_trans_mm, voxel_mm, roi_margin, rects)
+        b = exported._backing
+        d.header, d.frame_info, d.matches, d.cap_matches = b["header"].data_ptr(), b["frame_info"].data_ptr(), b["matches"].data_ptr(), caps[0]
+        d.clusters, d.cap_clusters, d.members, d.cap_members = b["clusters"].data_ptr(), caps[1], b["members"].data_ptr(), caps[2]
+        t = out._backing
+        d.chain_header, d.leaders, d.poses, d.checks, d.keep = (t[k].data_ptr() for k in ("chain_header", "leaders", "poses", "checks", "keep"))
+        _lib.check(_lib.lib().lmx_pose_chain_on(self.h, C.byref(d), int(stream.cuda_stream)))
+        del alive
+        return out
+
+    def debug_pose_chain(self, header, frame_info, matches, clusters, members, keep_thresh, cap_clusters=None, fill=0, class_index=-1, class_base=None,
+                         model_camera=None, scene_camera=None, max_dist_mm=10.0, max_iterations=20, min_pairs=16, search_radius=1, eps_rot_rad=1e-5,
+                         eps_trans_mm=1e-3, voxel_mm=4.0, roi_margin=8, rects=None):
+        """Test hook (lmx_debug_pose_chain): pose_chain's two kernels on lists in host memory (header int32 / uint32 [16], frame_info int32
+        [F, 8], matches MATCH_DTYPE, clusters CLUSTER_DTYPE, members int32; their lengths are the capacities, cap_clusters may state a
+        smaller one) against the resident scene -> (chain_header uint32 [8], leaders int32, poses POSE_REFINE_DTYPE, checks
+        POSE_VERIFY_DTYPE, keep uint8), each [len(clusters)] and holding the byte `fill` wherever the kernels wrote nothing."""
+        header = np.ascontiguousarray(header).astype(np.uint32).reshape(16)
+        frame_info = np.ascontiguousarray(frame_info, np.int32).reshape(-1, 8)
+        matches = np.ascontiguousarray(matches, MATCH_DTYPE)
+        clusters = np.ascontiguousarray(clusters, CLUSTER_DTYPE)
+        members = np.ascontiguousarray(members, np.int32)
+        n = len(clusters)
+        hdr = np.zeros(POSE_CHAIN_HEADER_WORDS, np.uint32)
+        leaders, poses, checks, keep = np.zeros(n, np.int32), np.zeros(n, POSE_REFINE_DTYPE), np.zeros(n, POSE_VERIFY_DTYPE), np.zeros(n, np.uint8)
+        for a in (leaders, poses, checks, keep):
+            a.view(np.uint8)[:] = fill
+        d, alive = self._pose_chain_desc(len(frame_info), keep_thresh, class_index, class_base, model_camera, scene_camera, max_dist_mm, max_iterations, min_pairs,
+                                         search_radius, eps_rot_rad, eps_trans_mm, voxel_mm, roi_margin, rects)
+        d.header, d.frame_info, d.matches, d.cap_matches = header.ctypes.data, frame_info.ctypes.data, matches.ctypes.data, len(matches)
+        d.clusters, d.cap_clusters, d.members, d.cap_members = clusters.ctypes.data, n if cap_clusters is None else int(cap_clusters), members.ctypes.data, len(members)
+        if d.cap_clusters > n:
+            raise ValueError("cap_clusters exceeds len(clusters)")
+        d.chain_header, d.leaders, d.poses, d.checks, d.keep = hdr.ctypes.data, leaders.ctypes.data, poses.ctypes.data, checks.ctypes.data, keep.ctypes.data
+        _lib.check(_lib.lib().lmx_debug_pose_chain(self.h, C.byref(d)))
+        del alive
+        return hdr, leaders, poses, checks, keep
+
     def debug_pose_refine_sums(self, depth_frame, match, **params):
         """Test hook (lmx_debug_pose_refine_sums): one match against one host frame -> (its POSE_REFINE_DTYPE record, int64
         [max_iterations + 1, 17]: the integer sums of every pass the device ran)."""
@@ -1469,7 +1614,8 @@ class DepthTemplates:
         del keep, frames
         return out[0], sums
 
-    KERNELS = ("k_normal_map_frames", "k_verify_diff_records", "k_verify_diff", "k_depth_diff_records", "k_walk_records_dev", "k_pose_refine", "k_pose_verify")
+    KERNELS = ("k_normal_map_frames", "k_verify_diff_records", "k_verify_diff", "k_depth_diff_records", "k_walk_records_dev", "k_pose_refine", "k_pose_verify",
+               "k_pose_refine_clusters", "k_pose_verify_clusters")
 
     def set_profiling(self, on=True):
         """Time the object's per-call kernels with device events (lmx_depth_templates_set_profiling); switching it on clears the sums."""

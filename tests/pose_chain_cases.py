@@ -1,0 +1,124 @@
+"""The pose chain on exported clusters (csrc/lmx_pose_chain.hpp, lmx_pose_chain_on): builders of exported lists as include/lmx.h lays them
+out, the CPU build of the shared header (tests/cpp/pose_chain_host.cpp) and the host-staged yardstick -- cluster_leaders -> refine_poses ->
+verify_poses -> keep_verified on the same lists -- that tests/test_pose_chain_host.py and tests/test_gpu_pose_chain.py compare against."""
+import os
+import subprocess
+
+import numpy as np
+
+import pose_refine_cases as prc
+from linemod_pose_estimation_amd import MATCH_DTYPE, POSE_REFINE_DTYPE, POSE_VERIFY_DTYPE, cluster_leaders, keep_verified
+from linemod_pose_estimation_amd.detector import CLUSTER_DTYPE
+
+DEAD, BROKEN, NO_JOB_BOUNDS, NO_JOB_CLASS, JOB = range(5)          # pc::State
+FLAG_CUT, FLAG_BOUNDS, FLAG_POSE = 1, 2, 4
+HOST_SRC = os.path.join(prc.ROOT, "tests", "cpp", "pose_chain_host.cpp")
+HOST_FLAGS = prc.HOST_FLAGS
+SANITIZE = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan", "-g"]
+
+
+class Lists:
+    """header uint32 [16], frame_info int32 [F, 8], matches MATCH_DTYPE, clusters CLUSTER_DTYPE, members int32: the lengths are the capacities."""
+
+    def __init__(self, header, frame_info, matches, clusters, members):
+        self.header, self.frame_info, self.matches, self.clusters, self.members = header, frame_info, matches, clusters, members
+
+    def copy(self):
+        return Lists(self.header.copy(), self.frame_info.copy(), self.matches.copy(), self.clusters.copy(), self.members.copy())
+
+
+def matches_of(rows):
+    """rows of (x, y, similarity, template_id, class_index)"""
+    m = np.zeros(len(rows), MATCH_DTYPE)
+    for i, r in enumerate(rows):
+        m[i] = tuple(r)
+    return m
+
+
+def build_lists(frames):
+    """frames: (status, matches, [member list per cluster]) per frame, the members indexing the frame's own matches -> Lists as an export with
+    room for everything writes them: frames back to back, member_begin from the start of `members`; a frame of status 1, 2 or 16 has counts
+    0 and adds nothing; one of status 4 or 8 has its counts and its place."""
+    info = np.zeros((len(frames), 8), np.int32)
+    ms, cs, mem = [], [], []
+    pos = [0, 0, 0]
+    for f, (status, m, clusters) in enumerate(frames):
+        if status in (1, 2, 16):
+            info[f] = (pos[0], 0, pos[1], 0, pos[2], 0, status, len(m))
+            continue
+        c = np.zeros(len(clusters), CLUSTER_DTYPE)
+        n_mem = 0
+        for k, members in enumerate(clusters):
+            c[k]["member_begin"], c[k]["member_count"] = pos[2] + n_mem, len(members)
+            c[k]["index"], c[k]["score"] = (f, k, 0), float(k)
+            mem.extend(int(v) for v in members)
+            n_mem += len(members)
+        info[f] = (pos[0], len(m), pos[1], len(c), pos[2], n_mem, status, len(m))
+        ms.append(m)
+        cs.append(c)
+        pos = [pos[0] + len(m), pos[1] + len(c), pos[2] + n_mem]
+    header = np.zeros(16, np.uint32)
+    header[:5] = (len(frames), 0, pos[0], pos[1], pos[2])
+    return Lists(header, info, np.concatenate(ms) if ms else np.zeros(0, MATCH_DTYPE), np.concatenate(cs) if cs else np.zeros(0, CLUSTER_DTYPE),
+                 np.asarray(mem, np.int32))
+
+
+def frame_leaders(L, f):
+    """cluster_leaders on frame f's lists, as a caller of to_host() runs it -> indices into L.matches"""
+    mb, mc, cb, cc = (int(v) for v in L.frame_info[f, :4])
+    return cluster_leaders(L.clusters[cb:cb + cc], L.members, L.matches[mb:mb + mc]) + mb
+
+
+# ---- the CPU build of the header ------------------------------------------------------------------------------------------------------------
+
+def build_host(directory, sanitize=False):
+    exe = os.path.join(str(directory), "pose_chain_host" + ("_san" if sanitize else ""))
+    subprocess.check_call(["g++"] + HOST_FLAGS + (SANITIZE if sanitize else []) + [HOST_SRC, "-o", exe])
+    return exe
+
+
+def run_host(exe, path, L, rects, class_index=-1, class_base=None, caps=None):
+    """The header's decisions for every slot below n_live -> (n_live, header flags, [dict per slot]).  caps: (cap_matches, cap_clusters,
+    cap_members), each at most the array's length; the arrays are cut to them, so the program holds nothing beyond."""
+    caps = caps or (len(L.matches), len(L.clusters), len(L.members))
+    rects = np.ascontiguousarray(rects, np.int32).reshape(-1, 4)
+    base = np.ascontiguousarray(class_base, np.int32) if class_base is not None else np.zeros(0, np.int32)
+    head = np.asarray([len(L.frame_info), caps[0], caps[1], caps[2], len(rects), class_index, max(len(base) - 1, 0)], np.int32)
+    parts = [head, L.header.view(np.int32), L.frame_info.reshape(-1), np.ascontiguousarray(L.matches[:caps[0]]).view(np.int32).reshape(-1),
+             np.ascontiguousarray(L.clusters[:caps[1]]).view(np.int32).reshape(-1), L.members[:caps[2]], rects.reshape(-1), base]
+    with open(path, "wb") as fh:
+        fh.write(b"".join(np.ascontiguousarray(p, np.int32).tobytes() for p in parts))
+    res = subprocess.run([exe, str(path)], capture_output=True, text=True, timeout=120)
+    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
+    lines = res.stdout.split("\n")
+    live, flags = (int(v) for v in lines[0].split()[1:])
+    slots = []
+    for k in range(live):
+        w = lines[1 + k].split()
+        assert w[0] == "slot" and int(w[1]) == k
+        slots.append(dict(zip(("state", "flags", "leader", "frame", "x", "y", "template_id", "rect_x", "rect_y"), (int(v) for v in w[2:]))))
+    return live, flags, slots
+
+
+# ---- the host-staged yardstick ----------------------------------------------------------------------------------------------------------------
+
+def host_staged(t, L, frames, class_index, refine_kw, verify_kw, thresh, rects, class_base=None):
+    """The path that exists without the chain, for the frames in `frames` (those a caller of to_host() gets): the leaders of their clusters,
+    the leaders' matches through refine_poses and verify_poses against the resident scene, keep_verified -> {slot: (leader, pose record,
+    verify record, keep)}.  class_base: the template ids are rebased by hand and no class filter applies."""
+    n_frames = len(L.frame_info)
+    slots, leaders, offsets = [], [], [0]
+    for f in range(n_frames):
+        if f in frames:
+            cb, cc = int(L.frame_info[f, 2]), int(L.frame_info[f, 3])
+            slots.extend(range(cb, cb + cc))
+            leaders.extend(int(v) for v in frame_leaders(L, f))
+        offsets.append(len(leaders))
+    m = L.matches[np.asarray(leaders, np.int64)].copy() if leaders else np.zeros(0, MATCH_DTYPE)
+    if class_base is not None:
+        m["template_id"] += np.asarray(class_base, np.int32)[m["class_index"]]
+        class_index = -1
+    poses = t.refine_poses(m, None, offsets, class_index=class_index, rects=rects, **refine_kw) if leaders else np.zeros(0, POSE_REFINE_DTYPE)
+    checks = t.verify_poses(m, poses, None, offsets, class_index=class_index, rects=rects, **verify_kw) if leaders else np.zeros(0, POSE_VERIFY_DTYPE)
+    keep = keep_verified(checks, thresh)
+    return {k: (leaders[i], poses[i:i + 1], checks[i:i + 1], bool(keep[i])) for i, k in enumerate(slots)}
