@@ -697,7 +697,7 @@ lmx_status lmx_debug_train_extract(int32_t device, const uint8_t* label, const f
  * The depth half of the reference's depth_normal_diff_calc (src/rgbdDetector.cpp:147-282): lay the template's rendered depth over the
  * scene depth at the match position and average the absolute difference where both are valid.  Upstream re-renders the view per match;
  * a template's view never changes, so here the renders are made ONCE, cropped to their silhouette boxes and kept on the device
- * (lmx_depth_templates), and each match of a frame costs one pass over its crop (csrc/lmx_verify.hip, k_depth_diff: one workgroup per
+ * (lmx_depth_templates), and each match of a frame costs one pass over its crop (csrc/lmx_verify.hip, k_walk: one workgroup per
  * match).  Definition (csrc/lmx_depth_verify.hpp), for a crop t[h][w], a scene s[H][W] (both uint16 mm, 0 = not on the object / no
  * measurement) and a match at (x, y), any int32: crop pixel (i, j) meets scene pixel (x + j, y + i); it counts iff t != 0, the scene
  * pixel lies inside the image and s != 0.
@@ -750,11 +750,11 @@ double     lmx_depth_value(const lmx_depth_diff_t* diff, double no_value);
  * collect_clusters_depth: lmx_ctx_collect_clusters for the oldest outstanding enqueue (same outputs, same context locking) with
  *   diffs[i]          = the depth check of matches[i] against scene frame f (parallel to matches; may be NULL; written when matches is),
  *   clusters[k].score = the mean over the cluster's members, in voting order, of lmx_depth_value(diffs[i], no_value).
- * On the context's consumer stream: wait for the scene's event, k_depth_diff_records (one workgroup per RAW record: which of two duplicate
+ * On the context's consumer stream: wait for the scene's event, the record form of k_walk (one workgroup per RAW record: which of two duplicate
  * records std::unique keeps is decided by the sort that follows), the scored form of k_f2_finalize_cluster, one synchronisation.  Frames
  * of 2049 .. 16384 records are finished by the scored large-frame kernel from the same per-record results (lmx_ctx_chain_stats); frames
  * the device chain hands back (more than 16384 records, a ring outside the packed range) are finished on the host inside the call
- * (k_depth_diff on the resident scene + lmx_cluster_matches_scored), with the errors lmx_ctx_collect_clusters reports for them.
+ * (the job form of k_walk on the resident scene + lmx_cluster_matches_scored), with the errors lmx_ctx_collect_clusters reports for them.
  * For EVERY input matches, diffs, clusters (score included) and members equal, bit for bit,
  *     lmx_ctx_collect;  lmx_depth_diff_matches(templates, depth, n, matches, offsets, class_index, diffs);
  *     per frame lmx_cluster_matches_scored with match_values[i] = lmx_depth_value(&diffs[i], no_value)
@@ -813,7 +813,7 @@ lmx_status lmx_normal_angle_table(uint32_t* out /*[16385]*/);
 lmx_status lmx_depth_templates_enable_normals(lmx_depth_templates* templates, const lmx_normal_params* params);
 /* reads template id's normals back from the device; LMX_ERR_INVALID_ARG before enable_normals */
 lmx_status lmx_depth_templates_get_normals(const lmx_depth_templates* templates, int32_t id, int16_t* out /*[h][w][4]*/);
-/* lmx_depth_diff_matches with both terms in one pass over each crop (k_verify_diff): the same arguments, the same staging, the same rule
+/* lmx_depth_diff_matches with both terms in one pass over each crop (k_walk<NORMALS>): the same arguments, the same staging, the same rule
  * that the uploaded scene is forgotten, the same errors, plus LMX_ERR_INVALID_ARG before enable_normals.  out[i] and, unless it is NULL,
  * ddiffs[i] belong to matches[i]; ddiffs equals what lmx_depth_diff_matches gives, bit for bit. */
 lmx_status lmx_normal_diff_matches(lmx_depth_templates* templates, const lmx_image* depth, int32_t n_frames, const lmx_match_t* matches,
@@ -823,7 +823,7 @@ double     lmx_match_value(const lmx_depth_diff_t* ddiff, const lmx_normal_diff_
  *     lmx_ctx_enqueue;  lmx_depth_templates_upload_scene;  lmx_ctx_collect_clusters_depth_normal
  *   ndiffs[i]         = the normal sums of matches[i] (parallel to matches; may be NULL; written when matches is),
  *   clusters[k].score = the mean over the cluster's members, in voting order, of lmx_match_value(diffs[i], ndiffs[i], no_value).
- * On the consumer stream: wait for the scene's event, k_normal_map_frames if the scene has no normals yet, k_verify_diff_records, the
+ * On the consumer stream: wait for the scene's event, k_normal_map_frames if the scene has no normals yet, the record form of k_walk<NORMALS>, the
  * third form of k_f2_finalize_cluster, one synchronisation; frames the device chain hands back are finished on the host inside the call.
  * Equal, bit for bit, to lmx_ctx_collect + lmx_normal_diff_matches + per frame lmx_cluster_matches_scored on lmx_match_value.  Every
  * condition of lmx_ctx_collect_clusters_depth holds; LMX_ERR_INVALID_ARG, the enqueue staying outstanding, also before enable_normals. */
@@ -1165,7 +1165,7 @@ lmx_status lmx_debug_device_finalize_cluster(int32_t device, const lmx_raw_match
                                              const lmx_cluster_params* params, lmx_match_t* matches, lmx_cluster_t* clusters, int32_t* members,
                                              uint32_t* counts);
 /* The same hook for the scored form (lmx_ctx_collect_clusters_depth): depth[n_frames] becomes templates' uploaded scene, then
- * k_depth_diff_records and k_f2_finalize_cluster_scored run on the stand-alone slot.  diffs [n_frames][2048] comes back next to matches
+ * the record form of k_walk and the depth-scored k_f2_finalize_cluster run on the stand-alone slot.  diffs [n_frames][2048] comes back next to matches
  * (a frame's row is valid where its matches row is); everything else as above, again without host completion.  templates need not hold
  * n_templates crops: a record whose template_id it does not hold gets a zero diff. */
 lmx_status lmx_debug_device_finalize_cluster_depth(int32_t device, const lmx_raw_match_t* records, size_t n_records, int32_t n_frames,
@@ -1174,7 +1174,7 @@ lmx_status lmx_debug_device_finalize_cluster_depth(int32_t device, const lmx_raw
                                                    const lmx_cluster_params* params, lmx_match_t* matches, lmx_depth_diff_t* diffs,
                                                    lmx_cluster_t* clusters, int32_t* members, uint32_t* counts);
 /* The same hook for the CLASSES forms (lmx_ctx_collect_clusters_classes): `classes` as lmx_cluster_matches_classes takes them, n_classes
- * 1 .. 16, each validated as by lmx_ctx_set_cluster_sidecar_class.  score == NULL: k_f2_finalize_cluster_classes.  With a score: depth
+ * 1 .. 16, each validated as by lmx_ctx_set_cluster_sidecar_class.  score == NULL: the CLASSES form of k_f2_finalize_cluster.  With a score: depth
  * [n_frames] becomes score->templates' uploaded scene, then the classed record kernel and the scored (normals == 0) or normal-scored
  * classed chain; class_base is validated against the object's count only, so that a test can give a class a shorter range than its
  * side-car.  cluster_class [n_frames][2048] comes back next to clusters, diffs and ndiffs [n_frames][2048] next to matches (required with
@@ -1195,7 +1195,7 @@ enum { LMX_TAB_INFO = 0, LMX_TAB_LINFO, LMX_TAB_COARSE_OFF, LMX_TAB_COARSE_UNI, 
 lmx_status lmx_debug_bank_tables(const lmx_bank* bank, int32_t width, int32_t height, int32_t max_batch, int32_t shard_rank, int32_t shard_world,
                                  int32_t ls_flat, int32_t table, void* out, size_t out_bytes, size_t* n_bytes, uint64_t* fnv1a);
 /* The large-frame form of the four hooks above: the kernels lmx_ctx_collect_clusters* launch for the frames the LDS kernels hand back
- * (k_f2_large*, csrc/lmx_f2.hip: one workgroup of 1024 threads per frame, rows in device memory), here on EVERY frame whatever its size, with
+ * (k_f2_large, csrc/lmx_f2.hip: one workgroup of 1024 threads per frame, rows in device memory), here on EVERY frame whatever its size, with
  * the same arguments and no host completion.  Rows are [n_frames][16384].  Exactness: for every frame of at most 16384 records the outputs
  * equal the reference chain's bit for bit, as the LDS kernels' do -- the same permutation of ties from both sorts, the same double sums.
  *   status 0: complete;   status 1: more than 16384 records, counts[0] = the record count, nothing else written;

@@ -333,6 +333,21 @@ static lmx_status grow_rec_diffs(void** d, size_t* cap, size_t n, size_t elem) {
   return LMX_OK;
 }
 
+// What the chain's kernels take of context slot `slot`, whoever launches them: the slot, the caller's output rows, and the context's
+// un-classed side-car (not read by the CLASSES forms, nor with do_clusters 0).  The caller adds its score and class fields.
+static F2Params chain_slot_params(const lmx_ctx* c, int slot, int32_t n_frames, lmx_match_t* matches, uint32_t* counts, lmx_cluster_t* clusters, int32_t* members,
+                                  uint8_t* scratch, bool do_clusters) {
+  F2Params p{};
+  p.recs = reinterpret_cast<const lmx_raw_match_t*>(c->d_out_slot[slot] + 64);
+  p.hdr = reinterpret_cast<const uint32_t*>(c->d_out_slot[slot]);
+  p.cap = c->cap_total; p.n_frames = n_frames;
+  p.out_matches = matches; p.out_counts = counts; p.out_clusters = clusters; p.out_members = members; p.scratch = scratch;
+  p.dists = c->d_f2_dists; p.rects = c->d_f2_rects; p.n_templates = (uint32_t)c->f2_templates;
+  p.step = c->f2_params.vote_row_col_step; p.size_thresh = c->f2_params.cluster_size_thresh; p.do_clusters = do_clusters ? 1 : 0;
+  p.radius_min = c->f2_params.renderer_radius_min; p.radius_step = c->f2_params.renderer_radius_step;
+  return p;
+}
+
 // The body of lmx_ctx_collect_clusters and lmx_ctx_collect_clusters_depth (`what` names the entry point in messages).  With `depth`, the
 // caller holds the templates' mutex.
 static lmx_status collect_clusters_impl(const char* what, lmx_ctx* c, int32_t n_frames, const DepthScore* depth, const ClassChain* cls, lmx_match_t* matches, size_t cap_matches,
@@ -394,34 +409,23 @@ static lmx_status collect_clusters_impl(const char* what, lmx_ctx* c, int32_t n_
   // on its own stream: the slot's kernels have finished (its event was waited for above), and the lane's stream may already carry later
   // batches that this collect must not wait for
   hipStream_t s = c->f2_stream;
-  F2Params p{};
-  p.recs = reinterpret_cast<const lmx_raw_match_t*>(c->d_out_slot[slot] + 64);
-  p.hdr = reinterpret_cast<const uint32_t*>(c->d_out_slot[slot]);
-  p.cap = c->cap_total; p.n_frames = n_frames;
-  p.out_matches = c->d_f2_matches; p.out_counts = c->d_f2_counts; p.out_clusters = c->d_f2_clusters; p.out_members = c->d_f2_members; p.scratch = c->d_f2_scratch;
-  p.dists = c->d_f2_dists; p.rects = c->d_f2_rects; p.n_templates = (uint32_t)c->f2_templates;
-  p.step = c->f2_params.vote_row_col_step; p.size_thresh = c->f2_params.cluster_size_thresh; p.do_clusters = 1;
-  p.radius_min = c->f2_params.renderer_radius_min; p.radius_step = c->f2_params.renderer_radius_step;
+  const F2Score score = f2_score(depth != nullptr, depth && depth->normal);
+  F2Params p = chain_slot_params(c, slot, n_frames, c->d_f2_matches, c->d_f2_counts, c->d_f2_clusters, c->d_f2_members, c->d_f2_scratch, true);
   if (cls) { p.classes = c->d_f2_class_table; p.out_cluster_class = c->d_f2_cluster_class; }
   if (depth) {
     if (lmx_status st = grow_rec_diffs((void**)&c->d_f2_rec_diffs, &c->f2_rec_diffs_cap, n_match, sizeof(lmx_depth_diff_t))) return st;
     if (depth->normal)
       if (lmx_status st = grow_rec_diffs((void**)&c->d_f2_rec_ndiffs, &c->f2_rec_ndiffs_cap, n_match, sizeof(lmx_normal_diff_t))) return st;
     // the scene's copies, one workgroup per raw record (the count is the header's, read above), the scored chain: one synchronisation
-    if (lmx_status st = cls ? depth_launch_records_classes(depth->templates, s, p.recs, n_match, c->d_f2_class_base, cls->n_classes, c->d_f2_rec_diffs,
-                                                           depth->normal ? c->d_f2_rec_ndiffs : nullptr)
-                            : depth_launch_records(depth->templates, s, p.recs, n_match, depth->class_index, c->d_f2_rec_diffs,
-                                                   depth->normal ? c->d_f2_rec_ndiffs : nullptr)) return st;
+    DepthWalk w;
+    w.recs = p.recs; w.n = n_match; w.class_index = depth->class_index;
+    if (cls) { w.d_class_base = c->d_f2_class_base; w.n_classes = cls->n_classes; }
+    w.d_diffs = c->d_f2_rec_diffs; w.d_ndiffs = depth->normal ? c->d_f2_rec_ndiffs : nullptr;
+    if (lmx_status st = depth_launch_walk(depth->templates, s, w)) return st;
     p.diffs = c->d_f2_rec_diffs; p.out_diffs = c->d_f2_diffs; p.diff_scratch = c->d_f2_diff_scratch; p.no_value = depth->no_value;
-    if (depth->normal) {
-      p.ndiffs = c->d_f2_rec_ndiffs; p.out_ndiffs = c->d_f2_ndiffs; p.ndiff_scratch = c->d_f2_ndiff_scratch;
-      if (cls) launch_f2_classes(s, p, 2); else launch_f2_normal(s, p);
-    } else {
-      if (cls) launch_f2_classes(s, p, 1); else launch_f2_scored(s, p);
-    }
-  } else {
-    if (cls) launch_f2_classes(s, p, 0); else launch_f2(s, p);
+    if (depth->normal) { p.ndiffs = c->d_f2_rec_ndiffs; p.out_ndiffs = c->d_f2_ndiffs; p.ndiff_scratch = c->d_f2_ndiff_scratch; }
   }
+  launch_f2(s, p, score, cls != nullptr);
   LMX_HIP(hipGetLastError());
   LMX_HIP(hipStreamSynchronize(s));
   const uint32_t* counts = reinterpret_cast<const uint32_t*>(c->h_f2_out + off_counts);
@@ -438,14 +442,14 @@ static lmx_status collect_clusters_impl(const char* what, lmx_ctx* c, int32_t n_
     for (int f = 0; f < n_frames; ++f)
       if (counts[(size_t)f * 4 + 3] == 1 && counts[(size_t)f * 4] <= (uint32_t)F2_LARGE_MAX) { large_part[f] = (int)large.size(); large.push_back(f); }
   if (!large.empty()) {
-    lay = f2_large_layout(depth != nullptr, depth && depth->normal);
+    lay = f2_large_layout(score);
     if (lmx_status gs = grow_rec_diffs((void**)&c->d_f2l_ws, &c->f2l_ws_bytes, large.size() * (size_t)lay.bytes, 1)) return gs;
     if (!c->d_f2l_frames) LMX_HIP(hipMalloc((void**)&c->d_f2l_frames, F * sizeof(int32_t)));
     if (!c->d_f2l_counts) LMX_HIP(hipMalloc((void**)&c->d_f2l_counts, F * 4 * sizeof(uint32_t)));
     LMX_HIP(hipMemcpy(c->d_f2l_frames, large.data(), large.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     F2LargeParams lp{p, c->d_f2l_frames, c->d_f2l_ws, lay};
     lp.p.out_counts = c->d_f2l_counts;
-    launch_f2_large(s, lp, (int)large.size(), depth ? (depth->normal ? 2 : 1) : 0, cls != nullptr);
+    launch_f2_large(s, lp, (int)large.size(), score, cls != nullptr);
     LMX_HIP(hipGetLastError());
     LMX_HIP(hipStreamSynchronize(s));
     lcounts.resize(large.size() * 4);
@@ -522,7 +526,7 @@ static lmx_status collect_clusters_impl(const char* what, lmx_ctx* c, int32_t n_
       if (cls) fcls.resize(std::max<size_t>(nm, 1));
       size_t got = 0;
       lmx_status hs;
-      if (depth) {   // the final matches against the resident scene (k_depth_diff), then the host chain on their values
+      if (depth) {   // the final matches against the resident scene (the job form of k_walk), then the host chain on their values
         fd.resize(std::max<size_t>(nm, 1)); fv.resize(std::max<size_t>(nm, 1));
         if (depth->normal) fn.resize(std::max<size_t>(nm, 1));
         hs = cls ? depth_diff_resident_classes(depth->templates, fm.data(), nm, f, cls->class_base, cls->n_classes, fd.data(), depth->normal ? fn.data() : nullptr)
@@ -692,7 +696,7 @@ static lmx_status check_export_output(const char* what, const lmx_ctx* c, const 
 struct ExportRequest {
   int32_t oldest, max_large_frames;
   bool clusters, classes;
-  int score;                       // 0 mean similarity, 1 depth, 2 depth + normal
+  F2Score score;
   lmx_depth_templates* templates;  // with a score
   int32_t class_index;
   const int32_t* class_base;
@@ -708,7 +712,7 @@ struct ExportRequest {
   int32_t* members; size_t cap_members;
 };
 
-// The body of both exports (include/lmx.h; kernels: lmx_export.hip, and for a score k_walk_records_dev of lmx_verify.hip).  Every refusal
+// The body of both exports (include/lmx.h; kernels: lmx_export.hip, and for a score the device-count walk of lmx_verify.hip).  Every refusal
 // comes before anything is queued; nothing below waits on the host for the device except an allocation's first use.
 static lmx_status export_impl(const char* what, lmx_ctx* c, int32_t n_frames, const ExportRequest& q, void* stream) {
   if (!c->sets[0].h_stage) { set_error("%s: this context is a member of a device group", what); return LMX_ERR_INVALID_ARG; }
@@ -716,12 +720,12 @@ static lmx_status export_impl(const char* what, lmx_ctx* c, int32_t n_frames, co
   const int slot = q.oldest ? (c->head + c->n_slots - c->outstanding) % c->n_slots : (c->head + c->n_slots - 1) % c->n_slots;
   if (n_frames != c->slot_frames[slot]) { set_error("%s: n_frames=%d but the enqueue had %d", what, n_frames, c->slot_frames[slot]); return LMX_ERR_INVALID_ARG; }
   if (!q.header || !q.frame_info || !q.matches) { set_error("%s: header, frame_info and matches must not be null", what); return LMX_ERR_INVALID_ARG; }
-  const bool clusters = q.clusters, scored = q.score >= 1, normal = q.score == 2;
+  const bool clusters = q.clusters, scored = q.score != F2_SIMILARITY, normal = q.score == F2_DEPTH_NORMAL;
   if (clusters)
     if (lmx_status st = check_chain_sidecar(what, c, q.classes)) return st;
   if (clusters && (!q.clusters_out || !q.members)) { set_error("%s: clusters: clusters_out and members must not be null", what); return LMX_ERR_INVALID_ARG; }
   if (q.classes && !q.cluster_class) { set_error("%s: classes: cluster_class must not be null", what); return LMX_ERR_INVALID_ARG; }
-  if (scored && (!q.templates || !q.diffs)) { set_error("%s: score %d: templates and diffs must not be null", what, q.score); return LMX_ERR_INVALID_ARG; }
+  if (scored && (!q.templates || !q.diffs)) { set_error("%s: score %d: templates and diffs must not be null", what, (int)q.score); return LMX_ERR_INVALID_ARG; }
   if (normal && !q.ndiffs) { set_error("%s: score 2: ndiffs must not be null", what); return LMX_ERR_INVALID_ARG; }
   if (scored && q.no_value != q.no_value) { set_error("%s: no_value is not a number (the score order would be undefined)", what); return LMX_ERR_INVALID_ARG; }
   if (q.max_large_frames < 0) { set_error("%s: max_large_frames %d is negative", what, q.max_large_frames); return LMX_ERR_INVALID_ARG; }
@@ -752,7 +756,7 @@ static lmx_status export_impl(const char* what, lmx_ctx* c, int32_t n_frames, co
     if (lmx_status st = check_export_output(what, c, "cluster_class", q.cluster_class, 4)) return st;
   // the export's own buffers, on first use
   const size_t F = (size_t)c->F;
-  const F2LargeLayout lay = f2_large_layout(scored, normal);
+  const F2LargeLayout lay = f2_large_layout(q.score);
   if (!c->d_xp_rows) {
     const size_t off_clusters = F * F2_MAX * sizeof(lmx_match_t), off_members = off_clusters + F * F2_MAX * sizeof(lmx_cluster_t),
                  off_counts = off_members + F * F2_MAX * sizeof(int32_t), off_list = off_counts + F * 4 * sizeof(uint32_t),
@@ -809,31 +813,20 @@ static lmx_status export_impl(const char* what, lmx_ctx* c, int32_t n_frames, co
   LMX_HIP(hipStreamWaitEvent(s, c->done[slot], 0));
   LMX_HIP(hipEventRecord(c->export_dst_ready, user));
   LMX_HIP(hipStreamWaitEvent(s, c->export_dst_ready, 0));
-  F2Params p{};
-  p.recs = reinterpret_cast<const lmx_raw_match_t*>(c->d_out_slot[slot] + 64);
-  p.hdr = reinterpret_cast<const uint32_t*>(c->d_out_slot[slot]);
-  p.cap = c->cap_total; p.n_frames = n_frames;
-  p.out_matches = c->d_xp_matches; p.out_counts = c->d_xp_counts; p.out_clusters = c->d_xp_clusters; p.out_members = c->d_xp_members; p.scratch = c->d_xp_scratch;
-  p.do_clusters = clusters ? 1 : 0;
-  if (clusters && !q.classes) {
-    p.dists = c->d_f2_dists; p.rects = c->d_f2_rects; p.n_templates = (uint32_t)c->f2_templates;
-    p.step = c->f2_params.vote_row_col_step; p.size_thresh = c->f2_params.cluster_size_thresh;
-    p.radius_min = c->f2_params.renderer_radius_min; p.radius_step = c->f2_params.renderer_radius_step;
-  }
+  F2Params p = chain_slot_params(c, slot, n_frames, c->d_xp_matches, c->d_xp_counts, c->d_xp_clusters, c->d_xp_members, c->d_xp_scratch, clusters);
   if (q.classes) { p.classes = c->d_f2_class_table; p.out_cluster_class = c->d_xp_cluster_class; }
   if (scored) {
     // the scene's copies, the walk over however many records the slot's header counts, then the scored chain on its results
-    const DepthWalkRecords w{p.hdr, p.recs, p.cap, q.class_index, q.classes ? c->d_xp_class_base : nullptr, q.classes ? q.n_classes : 0, c->d_xp_rec_diffs,
-                             normal ? c->d_xp_rec_ndiffs : nullptr, 0};
-    if (lmx_status st = depth_launch_records_dev(q.templates, s, w)) return st;
+    DepthWalk w;
+    w.recs = p.recs; w.hdr = p.hdr; w.cap = p.cap; w.class_index = q.class_index;
+    if (q.classes) { w.d_class_base = c->d_xp_class_base; w.n_classes = q.n_classes; }
+    w.d_diffs = c->d_xp_rec_diffs; w.d_ndiffs = normal ? c->d_xp_rec_ndiffs : nullptr;
+    if (lmx_status st = depth_launch_walk(q.templates, s, w)) return st;
     lk.unlock();
     p.diffs = c->d_xp_rec_diffs; p.out_diffs = c->d_xp_diffs; p.diff_scratch = c->d_xp_diff_scratch; p.no_value = q.no_value;
     if (normal) { p.ndiffs = c->d_xp_rec_ndiffs; p.out_ndiffs = c->d_xp_ndiffs; p.ndiff_scratch = c->d_xp_ndiff_scratch; }
   }
-  if (q.classes) launch_f2_classes(s, p, q.score);
-  else if (normal) launch_f2_normal(s, p);
-  else if (scored) launch_f2_scored(s, p);
-  else launch_f2(s, p);
+  launch_f2(s, p, q.score, q.classes);
   ExportParams e{};
   e.recs = p.recs; e.hdr = p.hdr; e.cap = p.cap; e.n_frames = n_frames; e.max_large = max_large;
   e.rows_matches = c->d_xp_matches; e.rows_clusters = c->d_xp_clusters; e.rows_members = c->d_xp_members; e.counts = c->d_xp_counts;
@@ -881,7 +874,7 @@ lmx_status lmx_ctx_export_clusters_on(lmx_ctx* c, int32_t n_frames, const lmx_ex
   if (d->score < 0 || d->score > 2) { set_error("%s: score %d outside 0 .. 2", what, d->score); return LMX_ERR_INVALID_ARG; }
   if (d->classes < 0 || d->classes > 1) { set_error("%s: classes %d outside 0 .. 1", what, d->classes); return LMX_ERR_INVALID_ARG; }
   ExportRequest q{};
-  q.oldest = d->oldest; q.max_large_frames = d->max_large_frames; q.clusters = true; q.classes = d->classes == 1; q.score = d->score;
+  q.oldest = d->oldest; q.max_large_frames = d->max_large_frames; q.clusters = true; q.classes = d->classes == 1; q.score = (F2Score)d->score;   // the same 0 / 1 / 2, checked above
   q.templates = d->templates; q.class_index = d->classes ? -1 : d->class_index; q.class_base = d->class_base; q.n_classes = d->n_classes; q.no_value = d->no_value;
   q.header = d->header; q.frame_info = d->frame_info; q.matches = d->matches; q.cap_matches = d->cap_matches;
   q.diffs = d->diffs; q.ndiffs = d->ndiffs; q.clusters_out = d->clusters_out; q.cap_clusters = d->cap_clusters; q.cluster_class = d->cluster_class;

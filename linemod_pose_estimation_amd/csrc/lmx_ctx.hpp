@@ -254,7 +254,7 @@ struct lmx_ctx {
   std::vector<int32_t> f2_class_base;            // what d_f2_class_base holds
   int32_t* h_f2_cluster_class = nullptr;         // pinned, mapped: [F][F2_MAX], next to the clusters of h_f2_out
   int32_t* d_f2_cluster_class = nullptr;         // its device view
-  // the large-frame kernels (k_f2_large*, frames of F2_MAX + 1 .. F2_LARGE_MAX records): nothing allocated before the first such frame; the
+  // the large-frame kernels (k_f2_large, frames of F2_MAX + 1 .. F2_LARGE_MAX records): nothing allocated before the first such frame; the
   // workspace holds one part (F2LargeLayout::bytes) per large frame of a call and grows on demand, like d_f2_rec_diffs
   uint8_t* d_f2l_ws = nullptr;
   size_t f2l_ws_bytes = 0;
@@ -276,7 +276,7 @@ struct lmx_ctx {
   uint32_t* d_xp_large_listed = nullptr;
   uint32_t* d_xp_large_counts = nullptr;
   uint8_t* d_xp_scratch = nullptr;               // [F][F2_MAX] x 32 bytes
-  uint8_t* d_xp_large_ws = nullptr;              // [max_large_frames of a call][its f2_large_layout(scored, normal).bytes], grown on demand, never shrunk
+  uint8_t* d_xp_large_ws = nullptr;              // [max_large_frames of a call][its f2_large_layout(score).bytes], grown on demand, never shrunk
   size_t xp_large_bytes = 0;
   // lmx_ctx_export_clusters_on: the scored and classed forms' rows, plain device memory too, nothing allocated before the first call that
   // needs them.  The count of raw records is not known on the host, so the per-record results have room for the slot's capacity

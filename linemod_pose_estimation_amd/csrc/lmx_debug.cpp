@@ -3,6 +3,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <functional>
 #include <vector>
 
 #include "lmx_ctx.hpp"
@@ -354,7 +355,7 @@ lmx_status lmx_debug_device_sort_perm_large(int32_t device, const float* similar
   float* d_sim = nullptr; int* d_tid = nullptr; int* d_perm = nullptr; uint8_t* d_ws = nullptr;
   auto run = [&]() -> lmx_status {
     LMX_HIP(hipMalloc((void**)&d_sim, (size_t)n * 4)); LMX_HIP(hipMalloc((void**)&d_tid, (size_t)n * 4)); LMX_HIP(hipMalloc((void**)&d_perm, (size_t)n * 4));
-    LMX_HIP(hipMalloc((void**)&d_ws, f2_large_layout(false, false).bytes));
+    LMX_HIP(hipMalloc((void**)&d_ws, f2_large_layout(F2_SIMILARITY).bytes));
     LMX_HIP(hipMemcpy(d_sim, similarity, (size_t)n * 4, hipMemcpyHostToDevice));
     LMX_HIP(hipMemcpy(d_tid, template_id, (size_t)n * 4, hipMemcpyHostToDevice));
     launch_debug_block_sort_large(nullptr, d_sim, d_tid, n, d_perm, d_ws);
@@ -367,11 +368,22 @@ lmx_status lmx_debug_device_sort_perm_large(int32_t device, const float* similar
   (void)hipFree(d_sim); (void)hipFree(d_tid); (void)hipFree(d_perm); (void)hipFree(d_ws);
   return st;
 }
+// the chain's kernels keep x, y as int16 and class_index as uint16 in LDS
+static lmx_status check_hook_records(const char* what, const lmx_raw_match_t* records, size_t n_records) {
+  for (size_t i = 0; i < n_records; ++i) {
+    const lmx_raw_match_t& r = records[i];
+    if (r.x < -32768 || r.x > 32767 || r.y < -32768 || r.y > 32767 || r.class_index < 0 || r.class_index > 65535) {
+      set_error("%s: record %zu: x, y must fit an int16 and class_index a uint16", what, i);
+      return LMX_ERR_INVALID_ARG;
+    }
+  }
+  return LMX_OK;
+}
 // The large-frame kernels of a hook: every frame listed, one workspace part each (zeroed, as the LDS hooks zero their rows), then each
 // part's output rows copied to the caller's [n_frames][F2_LARGE_MAX] rows.  p.out_counts is the hook's device count words.
-static lmx_status debug_run_large(const F2Params& p, int32_t n_frames, int mode, bool classes, lmx_match_t* matches, lmx_depth_diff_t* diffs, lmx_normal_diff_t* ndiffs,
+static lmx_status debug_run_large(const F2Params& p, int32_t n_frames, F2Score score, bool classes, lmx_match_t* matches, lmx_depth_diff_t* diffs, lmx_normal_diff_t* ndiffs,
                                   lmx_cluster_t* clusters, int32_t* cluster_class, int32_t* members) {
-  const F2LargeLayout lay = f2_large_layout(mode >= 1, mode == 2);
+  const F2LargeLayout lay = f2_large_layout(score);
   const size_t F = (size_t)n_frames, N = (size_t)F2_LARGE_MAX;
   uint8_t* d_ws = nullptr;
   int32_t* d_frames = nullptr;
@@ -383,7 +395,7 @@ static lmx_status debug_run_large(const F2Params& p, int32_t n_frames, int mode,
     for (size_t f = 0; f < F; ++f) frames[f] = (int32_t)f;
     LMX_HIP(hipMemcpy(d_frames, frames.data(), F * sizeof(int32_t), hipMemcpyHostToDevice));
     const F2LargeParams lp{p, d_frames, d_ws, lay};
-    launch_f2_large(nullptr, lp, n_frames, mode, classes);
+    launch_f2_large(nullptr, lp, n_frames, score, classes);
     LMX_HIP(hipGetLastError());
     LMX_HIP(hipDeviceSynchronize());
     for (size_t f = 0; f < F; ++f) {
@@ -392,8 +404,8 @@ static lmx_status debug_run_large(const F2Params& p, int32_t n_frames, int mode,
       LMX_HIP(hipMemcpy(clusters + f * N, part + lay.clusters, N * sizeof(lmx_cluster_t), hipMemcpyDeviceToHost));
       LMX_HIP(hipMemcpy(members + f * N, part + lay.members, N * sizeof(int32_t), hipMemcpyDeviceToHost));
       if (cluster_class) LMX_HIP(hipMemcpy(cluster_class + f * N, part + lay.cluster_class, N * sizeof(int32_t), hipMemcpyDeviceToHost));
-      if (mode >= 1) LMX_HIP(hipMemcpy(diffs + f * N, part + lay.diffs, N * sizeof(lmx_depth_diff_t), hipMemcpyDeviceToHost));
-      if (mode == 2) LMX_HIP(hipMemcpy(ndiffs + f * N, part + lay.ndiffs, N * sizeof(lmx_normal_diff_t), hipMemcpyDeviceToHost));
+      if (score != F2_SIMILARITY) LMX_HIP(hipMemcpy(diffs + f * N, part + lay.diffs, N * sizeof(lmx_depth_diff_t), hipMemcpyDeviceToHost));
+      if (score == F2_DEPTH_NORMAL) LMX_HIP(hipMemcpy(ndiffs + f * N, part + lay.ndiffs, N * sizeof(lmx_normal_diff_t), hipMemcpyDeviceToHost));
     }
     return LMX_OK;
   };
@@ -402,11 +414,92 @@ static lmx_status debug_run_large(const F2Params& p, int32_t n_frames, int mode,
   (void)hipFree(d_ws); (void)hipFree(d_frames);
   return st;
 }
-// The whole device consumer chain (k_f2_finalize_cluster, as lmx_ctx_collect_clusters launches it) on a caller's record list: the records
-// become a raw-match slot of their own (16-dword header with [1] = n_records, cap = n_records), the kernel's outputs and per-frame count
-// words come back as written -- no host completion, so a test sees which path the kernel took.
-// templates != null: the scored form -- k_depth_diff_records on the stand-alone slot against the templates' resident scene, then
-// k_f2_finalize_cluster_scored; diffs [n_frames][2048] comes back next to matches.  The templates' mutex is the caller's to hold.
+// The body of the cluster-chain hooks, their arguments checked: the whole device consumer chain (k_f2_finalize_cluster, as
+// lmx_ctx_collect_clusters launches it) on a caller's record list.  The records become a raw-match slot of their own (16-dword header with
+// [1] = n_records, cap = n_records); `sidecar(dev, p, w)` uploads the hook's side-car through `dev` and names it in the kernel's parameters,
+// and says which records the walk takes; with a score the record walk runs on the stand-alone slot against the templates' resident scene
+// (their mutex is the caller's to hold) in front of the chain.  The kernel's outputs and per-frame count words come back as written -- no
+// host completion, so a test sees which path the kernel took; diffs / ndiffs [n_frames][2048] come back next to matches.
+// large: the large-frame kernels on every frame, rows of F2_LARGE_MAX.
+using HookAlloc = std::function<hipError_t(void**, size_t)>;
+using HookSidecar = std::function<lmx_status(const HookAlloc&, F2Params&, DepthWalk&)>;
+static lmx_status debug_chain(bool large, bool classes, F2Score score, const lmx_raw_match_t* records, size_t n_records, int32_t n_frames, lmx_depth_templates* templates,
+                              double no_value, const HookSidecar& sidecar, lmx_match_t* matches, lmx_depth_diff_t* diffs, lmx_normal_diff_t* ndiffs, lmx_cluster_t* clusters,
+                              int32_t* cluster_class, int32_t* members, uint32_t* counts) {
+  const bool scored = score != F2_SIMILARITY, normals = score == F2_DEPTH_NORMAL;
+  const size_t F = (size_t)n_frames, R = std::max<size_t>(n_records, 1), rows = F * F2_MAX;
+  std::vector<void*> owned;   // every device buffer of this call
+  const HookAlloc dev = [&](void** p, size_t bytes) -> hipError_t { const hipError_t e = hipMalloc(p, bytes); if (e == hipSuccess) owned.push_back(*p); return e; };
+  auto zeroed = [&](void** p, size_t bytes) -> hipError_t { const hipError_t e = dev(p, bytes); return e == hipSuccess ? hipMemset(*p, 0, bytes) : e; };
+  uint32_t hdr[16] = {0};
+  hdr[1] = (uint32_t)n_records;
+  uint32_t *d_hdr = nullptr, *d_counts = nullptr;
+  lmx_raw_match_t* d_recs = nullptr;
+  lmx_match_t* d_matches = nullptr;
+  lmx_cluster_t* d_clusters = nullptr;
+  int32_t *d_members = nullptr, *d_cluster_class = nullptr;
+  uint8_t* d_scratch = nullptr;
+  lmx_depth_diff_t *d_rec_diffs = nullptr, *d_diffs = nullptr, *d_diff_scratch = nullptr;
+  lmx_normal_diff_t *d_rec_ndiffs = nullptr, *d_ndiffs = nullptr, *d_ndiff_scratch = nullptr;
+  auto run = [&]() -> lmx_status {
+    LMX_HIP(dev((void**)&d_hdr, sizeof(hdr)));
+    LMX_HIP(dev((void**)&d_recs, R * sizeof(lmx_raw_match_t)));
+    LMX_HIP(zeroed((void**)&d_matches, rows * sizeof(lmx_match_t)));
+    LMX_HIP(zeroed((void**)&d_clusters, rows * sizeof(lmx_cluster_t)));
+    LMX_HIP(zeroed((void**)&d_members, rows * sizeof(int32_t)));
+    LMX_HIP(dev((void**)&d_counts, F * 4 * sizeof(uint32_t)));
+    LMX_HIP(dev((void**)&d_scratch, rows * 32));
+    LMX_HIP(hipMemcpy(d_hdr, hdr, sizeof(hdr), hipMemcpyHostToDevice));
+    if (n_records) LMX_HIP(hipMemcpy(d_recs, records, n_records * sizeof(lmx_raw_match_t), hipMemcpyHostToDevice));
+    LMX_HIP(hipMemset(d_counts, 0xff, F * 4 * sizeof(uint32_t)));   // a frame the kernel did not report on stays recognisable
+    F2Params p{};
+    p.recs = d_recs; p.hdr = d_hdr; p.cap = (uint32_t)n_records; p.n_frames = n_frames;
+    p.out_matches = d_matches; p.out_counts = d_counts; p.out_clusters = d_clusters; p.out_members = d_members; p.scratch = d_scratch;
+    p.do_clusters = 1;
+    DepthWalk w;
+    w.recs = d_recs; w.n = (uint32_t)n_records;
+    if (lmx_status ss = sidecar(dev, p, w)) return ss;
+    if (classes) {
+      LMX_HIP(zeroed((void**)&d_cluster_class, rows * sizeof(int32_t)));
+      p.out_cluster_class = d_cluster_class;
+    }
+    if (scored) {
+      LMX_HIP(dev((void**)&d_rec_diffs, R * sizeof(lmx_depth_diff_t)));
+      LMX_HIP(zeroed((void**)&d_diffs, rows * sizeof(lmx_depth_diff_t)));
+      LMX_HIP(dev((void**)&d_diff_scratch, 2 * rows * sizeof(lmx_depth_diff_t)));
+      if (normals) {
+        LMX_HIP(dev((void**)&d_rec_ndiffs, R * sizeof(lmx_normal_diff_t)));
+        LMX_HIP(zeroed((void**)&d_ndiffs, rows * sizeof(lmx_normal_diff_t)));
+        LMX_HIP(dev((void**)&d_ndiff_scratch, 2 * rows * sizeof(lmx_normal_diff_t)));
+      }
+      w.d_diffs = d_rec_diffs; w.d_ndiffs = d_rec_ndiffs;
+      if (lmx_status ds = depth_launch_walk(templates, nullptr, w)) return ds;
+      p.diffs = d_rec_diffs; p.out_diffs = d_diffs; p.diff_scratch = d_diff_scratch; p.no_value = no_value;
+      p.ndiffs = d_rec_ndiffs; p.out_ndiffs = d_ndiffs; p.ndiff_scratch = d_ndiff_scratch;
+    }
+    if (large) {
+      if (lmx_status ls = debug_run_large(p, n_frames, score, classes, matches, diffs, ndiffs, clusters, cluster_class, members)) return ls;
+      LMX_HIP(hipMemcpy(counts, d_counts, F * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+      return LMX_OK;
+    }
+    launch_f2(nullptr, p, score, classes);
+    LMX_HIP(hipGetLastError());
+    LMX_HIP(hipDeviceSynchronize());
+    if (scored) LMX_HIP(hipMemcpy(diffs, d_diffs, rows * sizeof(lmx_depth_diff_t), hipMemcpyDeviceToHost));
+    if (normals) LMX_HIP(hipMemcpy(ndiffs, d_ndiffs, rows * sizeof(lmx_normal_diff_t), hipMemcpyDeviceToHost));
+    LMX_HIP(hipMemcpy(matches, d_matches, rows * sizeof(lmx_match_t), hipMemcpyDeviceToHost));
+    LMX_HIP(hipMemcpy(clusters, d_clusters, rows * sizeof(lmx_cluster_t), hipMemcpyDeviceToHost));
+    if (classes) LMX_HIP(hipMemcpy(cluster_class, d_cluster_class, rows * sizeof(int32_t), hipMemcpyDeviceToHost));
+    LMX_HIP(hipMemcpy(members, d_members, rows * sizeof(int32_t), hipMemcpyDeviceToHost));
+    LMX_HIP(hipMemcpy(counts, d_counts, F * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return LMX_OK;
+  };
+  const lmx_status st = run();
+  if (st != LMX_OK) (void)hipDeviceSynchronize();
+  for (void* q : owned) (void)hipFree(q);
+  return st;
+}
+// The un-classed hook: one side-car, no normal form.  templates != null: the depth-scored form, the templates' mutex is the caller's to hold.
 static lmx_status debug_finalize_cluster(const char* what, int32_t device, const lmx_raw_match_t* records, size_t n_records, int32_t n_frames, lmx_depth_templates* templates,
                                          int32_t class_index, double no_value, const double* obj_origin_dists, const int32_t* rects, size_t n_templates,
                                          const lmx_cluster_params* params, lmx_match_t* matches, lmx_depth_diff_t* diffs, lmx_cluster_t* clusters,
@@ -420,83 +513,27 @@ static lmx_status debug_finalize_cluster(const char* what, int32_t device, const
   if (params->vote_row_col_step <= 0) { set_error("vote_row_col_step must be positive"); return LMX_ERR_INVALID_ARG; }
   if (params->cluster_size_thresh < 0) { set_error("cluster_size_thresh must not be negative"); return LMX_ERR_INVALID_ARG; }
   if (lmx_status vs = check_vote_rings(obj_origin_dists, n_templates, params)) return vs;
-  for (size_t i = 0; i < n_records; ++i) {   // the kernel keeps x, y as int16 and class_index as uint16 in LDS
-    const lmx_raw_match_t& r = records[i];
-    if (r.x < -32768 || r.x > 32767 || r.y < -32768 || r.y > 32767 || r.class_index < 0 || r.class_index > 65535) {
-      set_error("%s: record %zu: x, y must fit an int16 and class_index a uint16", what, i);
-      return LMX_ERR_INVALID_ARG;
-    }
-  }
+  if (lmx_status rs = check_hook_records(what, records, n_records)) return rs;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available; this library has no CPU path"); return LMX_ERR_NO_DEVICE; }
   LMX_HIP(hipSetDevice(device));
-  const size_t F = (size_t)n_frames;
-  uint32_t hdr[16] = {0};
-  hdr[1] = (uint32_t)n_records;
-  uint32_t *d_hdr = nullptr, *d_counts = nullptr;
-  lmx_raw_match_t* d_recs = nullptr;
-  lmx_match_t* d_matches = nullptr;
-  lmx_cluster_t* d_clusters = nullptr;
-  int32_t *d_members = nullptr, *d_rects = nullptr;
-  uint8_t* d_scratch = nullptr;
-  double* d_dists = nullptr;
-  lmx_depth_diff_t *d_rec_diffs = nullptr, *d_diffs = nullptr, *d_diff_scratch = nullptr;
-  auto run = [&]() -> lmx_status {
-    LMX_HIP(hipMalloc((void**)&d_hdr, sizeof(hdr)));
-    LMX_HIP(hipMalloc((void**)&d_recs, std::max<size_t>(n_records, 1) * sizeof(lmx_raw_match_t)));
-    LMX_HIP(hipMalloc((void**)&d_matches, F * F2_MAX * sizeof(lmx_match_t)));
-    LMX_HIP(hipMalloc((void**)&d_clusters, F * F2_MAX * sizeof(lmx_cluster_t)));
-    LMX_HIP(hipMalloc((void**)&d_members, F * F2_MAX * sizeof(int32_t)));
-    LMX_HIP(hipMalloc((void**)&d_counts, F * 4 * sizeof(uint32_t)));
-    LMX_HIP(hipMalloc((void**)&d_scratch, F * F2_MAX * 32));
-    LMX_HIP(hipMalloc((void**)&d_dists, n_templates * sizeof(double)));
-    LMX_HIP(hipMalloc((void**)&d_rects, n_templates * 4 * sizeof(int32_t)));
-    LMX_HIP(hipMemcpy(d_hdr, hdr, sizeof(hdr), hipMemcpyHostToDevice));
-    if (n_records) LMX_HIP(hipMemcpy(d_recs, records, n_records * sizeof(lmx_raw_match_t), hipMemcpyHostToDevice));
+  const HookSidecar sidecar = [&](const HookAlloc& dev, F2Params& p, DepthWalk& w) -> lmx_status {
+    double* d_dists = nullptr;
+    int32_t* d_rects = nullptr;
+    LMX_HIP(dev((void**)&d_dists, n_templates * sizeof(double)));
+    LMX_HIP(dev((void**)&d_rects, n_templates * 4 * sizeof(int32_t)));
     LMX_HIP(hipMemcpy(d_dists, obj_origin_dists, n_templates * sizeof(double), hipMemcpyHostToDevice));
     LMX_HIP(hipMemcpy(d_rects, rects, n_templates * 4 * sizeof(int32_t), hipMemcpyHostToDevice));
-    LMX_HIP(hipMemset(d_matches, 0, F * F2_MAX * sizeof(lmx_match_t)));
-    LMX_HIP(hipMemset(d_clusters, 0, F * F2_MAX * sizeof(lmx_cluster_t)));
-    LMX_HIP(hipMemset(d_members, 0, F * F2_MAX * sizeof(int32_t)));
-    LMX_HIP(hipMemset(d_counts, 0xff, F * 4 * sizeof(uint32_t)));   // a frame the kernel did not report on stays recognisable
-    if (templates) {
-      LMX_HIP(hipMalloc((void**)&d_rec_diffs, std::max<size_t>(n_records, 1) * sizeof(lmx_depth_diff_t)));
-      LMX_HIP(hipMalloc((void**)&d_diffs, F * F2_MAX * sizeof(lmx_depth_diff_t)));
-      LMX_HIP(hipMalloc((void**)&d_diff_scratch, F * 2 * F2_MAX * sizeof(lmx_depth_diff_t)));
-      LMX_HIP(hipMemset(d_diffs, 0, F * F2_MAX * sizeof(lmx_depth_diff_t)));
-    }
-    F2Params p{};
-    p.recs = d_recs; p.hdr = d_hdr; p.cap = (uint32_t)n_records; p.n_frames = n_frames;
-    p.out_matches = d_matches; p.out_counts = d_counts; p.out_clusters = d_clusters; p.out_members = d_members; p.scratch = d_scratch;
     p.dists = d_dists; p.rects = d_rects; p.n_templates = (uint32_t)n_templates;
-    p.step = params->vote_row_col_step; p.size_thresh = params->cluster_size_thresh; p.do_clusters = 1;
+    p.step = params->vote_row_col_step; p.size_thresh = params->cluster_size_thresh;
     p.radius_min = params->renderer_radius_min; p.radius_step = params->renderer_radius_step;
-    if (templates) {
-      if (lmx_status ds = depth_launch_records(templates, nullptr, d_recs, (uint32_t)n_records, class_index, d_rec_diffs)) return ds;
-      p.diffs = d_rec_diffs; p.out_diffs = d_diffs; p.diff_scratch = d_diff_scratch; p.no_value = no_value;
-      if (!large) launch_f2_scored(nullptr, p);
-    } else if (!large) {
-      launch_f2(nullptr, p);
-    }
-    if (large) {
-      if (lmx_status ls = debug_run_large(p, n_frames, templates ? 1 : 0, false, matches, diffs, nullptr, clusters, nullptr, members)) return ls;
-      LMX_HIP(hipMemcpy(counts, d_counts, F * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
-      return LMX_OK;
-    }
-    LMX_HIP(hipGetLastError());
-    LMX_HIP(hipDeviceSynchronize());
-    if (templates) LMX_HIP(hipMemcpy(diffs, d_diffs, F * F2_MAX * sizeof(lmx_depth_diff_t), hipMemcpyDeviceToHost));
-    LMX_HIP(hipMemcpy(matches, d_matches, F * F2_MAX * sizeof(lmx_match_t), hipMemcpyDeviceToHost));
-    LMX_HIP(hipMemcpy(clusters, d_clusters, F * F2_MAX * sizeof(lmx_cluster_t), hipMemcpyDeviceToHost));
-    LMX_HIP(hipMemcpy(members, d_members, F * F2_MAX * sizeof(int32_t), hipMemcpyDeviceToHost));
-    LMX_HIP(hipMemcpy(counts, d_counts, F * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    w.class_index = class_index;
     return LMX_OK;
   };
-  const lmx_status st = run();
-  (void)hipFree(d_hdr); (void)hipFree(d_recs); (void)hipFree(d_matches); (void)hipFree(d_clusters); (void)hipFree(d_members);
-  (void)hipFree(d_counts); (void)hipFree(d_scratch); (void)hipFree(d_dists); (void)hipFree(d_rects);
-  (void)hipFree(d_rec_diffs); (void)hipFree(d_diffs); (void)hipFree(d_diff_scratch);
-  return st;
+  return lmx::guarded(what, [&]() -> lmx_status {   // the body allocates on the host
+    return debug_chain(large, false, f2_score(templates != nullptr, false), records, n_records, n_frames, templates, no_value, sidecar, matches, diffs, nullptr, clusters,
+                       nullptr, members, counts);
+  });
 }
 lmx_status lmx_debug_device_finalize_cluster(int32_t device, const lmx_raw_match_t* records, size_t n_records, int32_t n_frames,
                                              const double* obj_origin_dists, const int32_t* rects, size_t n_templates, const lmx_cluster_params* params,
@@ -510,8 +547,8 @@ lmx_status lmx_debug_device_finalize_cluster_large(int32_t device, const lmx_raw
   return debug_finalize_cluster("lmx_debug_device_finalize_cluster_large", device, records, n_records, n_frames, nullptr, -1, 0.0, obj_origin_dists, rects, n_templates, params, matches,
                                 nullptr, clusters, members, counts, true);
 }
-// The scored form of the same hook: `depth` (n_frames 16UC1 host frames) becomes the templates' resident scene, then k_depth_diff_records and
-// k_f2_finalize_cluster_scored run on the stand-alone slot as lmx_ctx_collect_clusters_depth launches them.  No host completion.
+// The scored form of the same hook: `depth` (n_frames 16UC1 host frames) becomes the templates' resident scene, then the record walk and the
+// depth-scored chain run on the stand-alone slot as lmx_ctx_collect_clusters_depth launches them.  No host completion.
 static lmx_status debug_finalize_cluster_depth(const char* what, bool large, int32_t device, const lmx_raw_match_t* records, size_t n_records, int32_t n_frames,
                                                lmx_depth_templates* templates, const lmx_image* depth, int32_t class_index, double no_value,
                                                const double* obj_origin_dists, const int32_t* rects, size_t n_templates, const lmx_cluster_params* params,
@@ -565,13 +602,7 @@ static lmx_status debug_finalize_cluster_classes(const char* what, bool large, i
     else vs = check_vote_rings(sc.obj_origin_dists, sc.n_templates, &sc.params);
     if (vs != LMX_OK) { const std::string why = lmx_last_error(); set_error("%s: class %d: %s", what, k, why.c_str()); return vs; }
   }
-  for (size_t i = 0; i < n_records; ++i) {   // the kernel keeps x, y as int16 and class_index as uint16 in LDS
-    const lmx_raw_match_t& r = records[i];
-    if (r.x < -32768 || r.x > 32767 || r.y < -32768 || r.y > 32767 || r.class_index < 0 || r.class_index > 65535) {
-      set_error("%s: record %zu: x, y must fit an int16 and class_index a uint16", what, i);
-      return LMX_ERR_INVALID_ARG;
-    }
-  }
+  if (lmx_status rs = check_hook_records(what, records, n_records)) return rs;
   if (score) {
     if (score->no_value != score->no_value) { set_error("%s: no_value is not a number", what); return LMX_ERR_INVALID_ARG; }
     if (score->n_classes < 1 || score->n_classes > F2_CLASSES || score->class_base[0] != 0) { set_error("%s: class_base: n_classes 1..%d, class_base[0] = 0", what, F2_CLASSES); return LMX_ERR_INVALID_ARG; }
@@ -590,29 +621,8 @@ static lmx_status debug_finalize_cluster_classes(const char* what, bool large, i
     lk = std::unique_lock<std::mutex>(depth_templates_mutex(score->templates));
     if (lmx_status st = depth_upload_scene(score->templates, depth, n_frames)) return st;
   }
-  const size_t F = (size_t)n_frames, R = std::max<size_t>(n_records, 1);
-  std::vector<void*> owned;   // every device buffer of this call
-  auto dev = [&](void** p, size_t bytes) -> hipError_t { const hipError_t e = hipMalloc(p, bytes); if (e == hipSuccess) owned.push_back(*p); return e; };
-  uint32_t hdr[16] = {0};
-  hdr[1] = (uint32_t)n_records;
-  uint32_t *d_hdr = nullptr, *d_counts = nullptr;
-  lmx_raw_match_t* d_recs = nullptr;
-  lmx_match_t* d_matches = nullptr;
-  lmx_cluster_t* d_clusters = nullptr;
-  int32_t *d_members = nullptr, *d_cluster_class = nullptr, *d_class_base = nullptr;
-  uint8_t* d_scratch = nullptr;
-  F2Class* d_table = nullptr;
-  lmx_depth_diff_t *d_rec_diffs = nullptr, *d_diffs = nullptr, *d_diff_scratch = nullptr;
-  lmx_normal_diff_t *d_rec_ndiffs = nullptr, *d_ndiffs = nullptr, *d_ndiff_scratch = nullptr;
-  auto run = [&]() -> lmx_status {
-    LMX_HIP(dev((void**)&d_hdr, sizeof(hdr)));
-    LMX_HIP(dev((void**)&d_recs, R * sizeof(lmx_raw_match_t)));
-    LMX_HIP(dev((void**)&d_matches, F * F2_MAX * sizeof(lmx_match_t)));
-    LMX_HIP(dev((void**)&d_clusters, F * F2_MAX * sizeof(lmx_cluster_t)));
-    LMX_HIP(dev((void**)&d_cluster_class, F * F2_MAX * sizeof(int32_t)));
-    LMX_HIP(dev((void**)&d_members, F * F2_MAX * sizeof(int32_t)));
-    LMX_HIP(dev((void**)&d_counts, F * 4 * sizeof(uint32_t)));
-    LMX_HIP(dev((void**)&d_scratch, F * F2_MAX * 32));
+  const HookSidecar sidecar = [&](const HookAlloc& dev, F2Params& p, DepthWalk& w) -> lmx_status {
+    F2Class* d_table = nullptr;
     LMX_HIP(dev((void**)&d_table, F2_CLASSES * sizeof(F2Class)));
     F2Class tab[F2_CLASSES] = {};
     for (int32_t k = 0; k < n_classes; ++k) {
@@ -628,56 +638,17 @@ static lmx_status debug_finalize_cluster_classes(const char* what, bool large, i
                        sc.params.renderer_radius_step};
     }
     LMX_HIP(hipMemcpy(d_table, tab, sizeof(tab), hipMemcpyHostToDevice));
-    LMX_HIP(hipMemcpy(d_hdr, hdr, sizeof(hdr), hipMemcpyHostToDevice));
-    if (n_records) LMX_HIP(hipMemcpy(d_recs, records, n_records * sizeof(lmx_raw_match_t), hipMemcpyHostToDevice));
-    LMX_HIP(hipMemset(d_matches, 0, F * F2_MAX * sizeof(lmx_match_t)));
-    LMX_HIP(hipMemset(d_clusters, 0, F * F2_MAX * sizeof(lmx_cluster_t)));
-    LMX_HIP(hipMemset(d_cluster_class, 0, F * F2_MAX * sizeof(int32_t)));
-    LMX_HIP(hipMemset(d_members, 0, F * F2_MAX * sizeof(int32_t)));
-    LMX_HIP(hipMemset(d_counts, 0xff, F * 4 * sizeof(uint32_t)));   // a frame the kernel did not report on stays recognisable
-    F2Params p{};
-    p.recs = d_recs; p.hdr = d_hdr; p.cap = (uint32_t)n_records; p.n_frames = n_frames;
-    p.out_matches = d_matches; p.out_counts = d_counts; p.out_clusters = d_clusters; p.out_members = d_members; p.scratch = d_scratch;
-    p.do_clusters = 1; p.classes = d_table; p.out_cluster_class = d_cluster_class;
+    p.classes = d_table;
     if (score) {
+      int32_t* d_class_base = nullptr;
       LMX_HIP(dev((void**)&d_class_base, (F2_CLASSES + 1) * sizeof(int32_t)));
       LMX_HIP(hipMemcpy(d_class_base, score->class_base, ((size_t)score->n_classes + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
-      LMX_HIP(dev((void**)&d_rec_diffs, R * sizeof(lmx_depth_diff_t)));
-      LMX_HIP(dev((void**)&d_diffs, F * F2_MAX * sizeof(lmx_depth_diff_t)));
-      LMX_HIP(dev((void**)&d_diff_scratch, F * 2 * F2_MAX * sizeof(lmx_depth_diff_t)));
-      LMX_HIP(hipMemset(d_diffs, 0, F * F2_MAX * sizeof(lmx_depth_diff_t)));
-      if (normals) {
-        LMX_HIP(dev((void**)&d_rec_ndiffs, R * sizeof(lmx_normal_diff_t)));
-        LMX_HIP(dev((void**)&d_ndiffs, F * F2_MAX * sizeof(lmx_normal_diff_t)));
-        LMX_HIP(dev((void**)&d_ndiff_scratch, F * 2 * F2_MAX * sizeof(lmx_normal_diff_t)));
-        LMX_HIP(hipMemset(d_ndiffs, 0, F * F2_MAX * sizeof(lmx_normal_diff_t)));
-      }
-      if (lmx_status ds = depth_launch_records_classes(score->templates, nullptr, d_recs, (uint32_t)n_records, d_class_base, score->n_classes, d_rec_diffs,
-                                                       d_rec_ndiffs)) return ds;
-      p.diffs = d_rec_diffs; p.out_diffs = d_diffs; p.diff_scratch = d_diff_scratch; p.no_value = score->no_value;
-      p.ndiffs = d_rec_ndiffs; p.out_ndiffs = d_ndiffs; p.ndiff_scratch = d_ndiff_scratch;
+      w.d_class_base = d_class_base; w.n_classes = score->n_classes;
     }
-    if (large) {
-      if (lmx_status ls = debug_run_large(p, n_frames, score ? (normals ? 2 : 1) : 0, true, matches, diffs, ndiffs, clusters, cluster_class, members)) return ls;
-      LMX_HIP(hipMemcpy(counts, d_counts, F * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
-      return LMX_OK;
-    }
-    launch_f2_classes(nullptr, p, score ? (normals ? 2 : 1) : 0);
-    LMX_HIP(hipGetLastError());
-    LMX_HIP(hipDeviceSynchronize());
-    if (score) LMX_HIP(hipMemcpy(diffs, d_diffs, F * F2_MAX * sizeof(lmx_depth_diff_t), hipMemcpyDeviceToHost));
-    if (normals) LMX_HIP(hipMemcpy(ndiffs, d_ndiffs, F * F2_MAX * sizeof(lmx_normal_diff_t), hipMemcpyDeviceToHost));
-    LMX_HIP(hipMemcpy(matches, d_matches, F * F2_MAX * sizeof(lmx_match_t), hipMemcpyDeviceToHost));
-    LMX_HIP(hipMemcpy(clusters, d_clusters, F * F2_MAX * sizeof(lmx_cluster_t), hipMemcpyDeviceToHost));
-    LMX_HIP(hipMemcpy(cluster_class, d_cluster_class, F * F2_MAX * sizeof(int32_t), hipMemcpyDeviceToHost));
-    LMX_HIP(hipMemcpy(members, d_members, F * F2_MAX * sizeof(int32_t), hipMemcpyDeviceToHost));
-    LMX_HIP(hipMemcpy(counts, d_counts, F * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return LMX_OK;
   };
-  const lmx_status st = run();
-  if (st != LMX_OK) (void)hipDeviceSynchronize();
-  for (void* q : owned) (void)hipFree(q);
-  return st;
+  return debug_chain(large, true, f2_score(score != nullptr, normals), records, n_records, n_frames, score ? score->templates : nullptr, score ? score->no_value : 0.0,
+                     sidecar, matches, diffs, ndiffs, clusters, cluster_class, members, counts);
   });
 }
 lmx_status lmx_debug_device_finalize_cluster_classes(int32_t device, const lmx_raw_match_t* records, size_t n_records, int32_t n_frames,

@@ -1,5 +1,5 @@
 // Depth check of a match against the rendered depth of its template (lmx_depth_diff_matches, include/lmx.h): the arithmetic of one pixel,
-// one row and one match, shared by the HIP kernels (lmx_verify.hip, k_depth_diff and k_depth_diff_records; lmx_f2.hip for value()) and --
+// one row and one match, shared by the HIP kernels (lmx_verify.hip, k_walk and k_walk_records_dev; lmx_f2.hip for value()) and --
 // compiled with LMX_DV_HOST -- by plain CPU builds (tests/cpp/depth_verify_host.cpp, tests/cpp/depth_value_host.cpp).
 // The reference's form is depth_normal_diff_calc (src/rgbdDetector.cpp:147-282), the depth half.
 //

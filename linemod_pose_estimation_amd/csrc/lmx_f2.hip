@@ -83,8 +83,6 @@ __device__ __forceinline__ unsigned long long match_sort_key(float similarity, i
   return ((unsigned long long)(~b) << 32) | (unsigned long long)((uint32_t)template_id ^ 0x80000000u);
 }
 
-enum { F2_SIMILARITY = 0, F2_DEPTH = 1, F2_DEPTH_NORMAL = 2 };   // what a cluster's score is the mean of
-
 // test hook (lmx_debug_device_sort_perm): the permutation sortblk::sort produces for n <= F2_MAX (similarity, template_id) pairs
 __global__ __launch_bounds__(256) void k_debug_block_sort(const float* sim, const int* tid_in, int n, int* perm, unsigned long long* spill) {
   __shared__ unsigned long long s_key[F2_MAX];
@@ -467,14 +465,9 @@ __device__ __forceinline__ void f2_finalize_cluster(const F2Params& p) {
   }
 }
 
-// the three instantiations as kernels of their own (the unscored one keeps the name profiles know)
-__global__ __launch_bounds__(256) void k_f2_finalize_cluster(F2Params p) { f2_finalize_cluster<F2_SIMILARITY>(p); }
-__global__ __launch_bounds__(256) void k_f2_finalize_cluster_scored(F2Params p) { f2_finalize_cluster<F2_DEPTH>(p); }
-__global__ __launch_bounds__(256) void k_f2_finalize_cluster_normal(F2Params p) { f2_finalize_cluster<F2_DEPTH_NORMAL>(p); }
-// and their CLASSES forms
-__global__ __launch_bounds__(256) void k_f2_finalize_cluster_classes(F2Params p) { f2_finalize_cluster<F2_SIMILARITY, true>(p); }
-__global__ __launch_bounds__(256) void k_f2_finalize_cluster_classes_scored(F2Params p) { f2_finalize_cluster<F2_DEPTH, true>(p); }
-__global__ __launch_bounds__(256) void k_f2_finalize_cluster_classes_normal(F2Params p) { f2_finalize_cluster<F2_DEPTH_NORMAL, true>(p); }
+// every instantiation as a kernel of its own
+template <int MODE, bool CLASSES>
+__global__ __launch_bounds__(256) void k_f2_finalize_cluster(F2Params p) { f2_finalize_cluster<MODE, CLASSES>(p); }
 
 // ---- the large-frame form: frames of F2_MAX + 1 .. F2_LARGE_MAX records ------------------------------------------------------------------
 // The same stages with the same semantics and the same order of ties, for the frames the kernels above hand back with status 1.  What
@@ -832,27 +825,22 @@ __device__ __forceinline__ void f2_large(const F2LargeParams& lp) {
   if (tid == 0) { counts[0] = (uint32_t)nf; counts[1] = (uint32_t)n_out; counts[2] = (uint32_t)n_mem; counts[3] = 0; }
 }
 
-__global__ __launch_bounds__(F2L_T) void k_f2_large(F2LargeParams p) { f2_large<F2_SIMILARITY, false>(p); }
-__global__ __launch_bounds__(F2L_T) void k_f2_large_scored(F2LargeParams p) { f2_large<F2_DEPTH, false>(p); }
-__global__ __launch_bounds__(F2L_T) void k_f2_large_normal(F2LargeParams p) { f2_large<F2_DEPTH_NORMAL, false>(p); }
-__global__ __launch_bounds__(F2L_T) void k_f2_large_classes(F2LargeParams p) { f2_large<F2_SIMILARITY, true>(p); }
-__global__ __launch_bounds__(F2L_T) void k_f2_large_classes_scored(F2LargeParams p) { f2_large<F2_DEPTH, true>(p); }
-__global__ __launch_bounds__(F2L_T) void k_f2_large_classes_normal(F2LargeParams p) { f2_large<F2_DEPTH_NORMAL, true>(p); }
+template <int MODE, bool CLASSES>
+__global__ __launch_bounds__(F2L_T) void k_f2_large(F2LargeParams p) { f2_large<MODE, CLASSES>(p); }
 
 void launch_debug_block_sort_large(hipStream_t s, const float* sim, const int* tid, int n, int* perm, uint8_t* ws) {
-  hipLaunchKernelGGL(k_debug_block_sort_large, dim3(1), dim3(F2L_T), 0, s, sim, tid, n, perm, ws, f2_large_layout(false, false));
+  hipLaunchKernelGGL(k_debug_block_sort_large, dim3(1), dim3(F2L_T), 0, s, sim, tid, n, perm, ws, f2_large_layout(F2_SIMILARITY));
 }
 
-void launch_f2_large(hipStream_t s, const F2LargeParams& p, int n_listed, int mode, bool classes) {
+void launch_f2_large(hipStream_t s, const F2LargeParams& p, int n_listed, F2Score score, bool classes) {
   const dim3 grid((unsigned)n_listed), block(F2L_T);
-  if (classes) {
-    if (mode == F2_DEPTH_NORMAL) hipLaunchKernelGGL(k_f2_large_classes_normal, grid, block, 0, s, p);
-    else if (mode == F2_DEPTH) hipLaunchKernelGGL(k_f2_large_classes_scored, grid, block, 0, s, p);
-    else hipLaunchKernelGGL(k_f2_large_classes, grid, block, 0, s, p);
-  } else {
-    if (mode == F2_DEPTH_NORMAL) hipLaunchKernelGGL(k_f2_large_normal, grid, block, 0, s, p);
-    else if (mode == F2_DEPTH) hipLaunchKernelGGL(k_f2_large_scored, grid, block, 0, s, p);
-    else hipLaunchKernelGGL(k_f2_large, grid, block, 0, s, p);
+  switch (2 * score + (classes ? 1 : 0)) {
+    case 2 * F2_SIMILARITY: hipLaunchKernelGGL((k_f2_large<F2_SIMILARITY, false>), grid, block, 0, s, p); break;
+    case 2 * F2_SIMILARITY + 1: hipLaunchKernelGGL((k_f2_large<F2_SIMILARITY, true>), grid, block, 0, s, p); break;
+    case 2 * F2_DEPTH: hipLaunchKernelGGL((k_f2_large<F2_DEPTH, false>), grid, block, 0, s, p); break;
+    case 2 * F2_DEPTH + 1: hipLaunchKernelGGL((k_f2_large<F2_DEPTH, true>), grid, block, 0, s, p); break;
+    case 2 * F2_DEPTH_NORMAL: hipLaunchKernelGGL((k_f2_large<F2_DEPTH_NORMAL, false>), grid, block, 0, s, p); break;
+    case 2 * F2_DEPTH_NORMAL + 1: hipLaunchKernelGGL((k_f2_large<F2_DEPTH_NORMAL, true>), grid, block, 0, s, p); break;
   }
 }
 
@@ -860,22 +848,16 @@ void launch_debug_block_sort(hipStream_t s, const float* sim, const int* tid, in
   hipLaunchKernelGGL(k_debug_block_sort, dim3(1), dim3(256), 0, s, sim, tid, n, perm, spill);
 }
 
-void launch_f2(hipStream_t s, const F2Params& p) {
-  hipLaunchKernelGGL(k_f2_finalize_cluster, dim3((unsigned)p.n_frames), dim3(256), 0, s, p);
-}
-
-void launch_f2_scored(hipStream_t s, const F2Params& p) {
-  hipLaunchKernelGGL(k_f2_finalize_cluster_scored, dim3((unsigned)p.n_frames), dim3(256), 0, s, p);
-}
-
-void launch_f2_normal(hipStream_t s, const F2Params& p) {
-  hipLaunchKernelGGL(k_f2_finalize_cluster_normal, dim3((unsigned)p.n_frames), dim3(256), 0, s, p);
-}
-
-void launch_f2_classes(hipStream_t s, const F2Params& p, int mode) {
-  if (mode == F2_DEPTH_NORMAL) hipLaunchKernelGGL(k_f2_finalize_cluster_classes_normal, dim3((unsigned)p.n_frames), dim3(256), 0, s, p);
-  else if (mode == F2_DEPTH) hipLaunchKernelGGL(k_f2_finalize_cluster_classes_scored, dim3((unsigned)p.n_frames), dim3(256), 0, s, p);
-  else hipLaunchKernelGGL(k_f2_finalize_cluster_classes, dim3((unsigned)p.n_frames), dim3(256), 0, s, p);
+void launch_f2(hipStream_t s, const F2Params& p, F2Score score, bool classes) {
+  const dim3 grid((unsigned)p.n_frames), block(256);
+  switch (2 * score + (classes ? 1 : 0)) {
+    case 2 * F2_SIMILARITY: hipLaunchKernelGGL((k_f2_finalize_cluster<F2_SIMILARITY, false>), grid, block, 0, s, p); break;
+    case 2 * F2_SIMILARITY + 1: hipLaunchKernelGGL((k_f2_finalize_cluster<F2_SIMILARITY, true>), grid, block, 0, s, p); break;
+    case 2 * F2_DEPTH: hipLaunchKernelGGL((k_f2_finalize_cluster<F2_DEPTH, false>), grid, block, 0, s, p); break;
+    case 2 * F2_DEPTH + 1: hipLaunchKernelGGL((k_f2_finalize_cluster<F2_DEPTH, true>), grid, block, 0, s, p); break;
+    case 2 * F2_DEPTH_NORMAL: hipLaunchKernelGGL((k_f2_finalize_cluster<F2_DEPTH_NORMAL, false>), grid, block, 0, s, p); break;
+    case 2 * F2_DEPTH_NORMAL + 1: hipLaunchKernelGGL((k_f2_finalize_cluster<F2_DEPTH_NORMAL, true>), grid, block, 0, s, p); break;
+  }
 }
 
 }  // namespace lmx

@@ -263,6 +263,10 @@ void launch_depth_quantize(hipStream_t s, const uint16_t* depth, uint8_t* quant,
                            int difference_threshold, const uint8_t* lut_bins /* device, [LMX_NORMAL_LUT_SIZE] median bins */,
                            uint32_t* clear16 = nullptr);
 // device form of "finalise + cluster" (lmx_f2.hip)
+// What a cluster's score is the mean of: the one name of a chain variant, from the public `score` field of lmx_export_clusters_desc (the
+// same 0 / 1 / 2) down to the kernels' template argument
+enum F2Score : int32_t { F2_SIMILARITY = 0, F2_DEPTH = 1, F2_DEPTH_NORMAL = 2 };
+inline F2Score f2_score(bool depth, bool normal) { return depth ? (normal ? F2_DEPTH_NORMAL : F2_DEPTH) : F2_SIMILARITY; }
 constexpr int F2_MAX = 2048;   // records per frame the LDS path takes; larger frames go to the large-frame kernels (F2_LARGE_MAX) or the host
 // One class's side-car as the CLASSES forms read it; n_templates 0: the class has none, its matches are listed and belong to no cluster
 constexpr int F2_CLASSES = 16;
@@ -288,26 +292,23 @@ struct F2Params {
   uint32_t n_templates;
   int32_t step, size_thresh, do_clusters;
   double radius_min, radius_step;
-  // the SCORED form only (launch_f2_scored): a cluster's score is the mean of dv::value(diff, no_value) over its members
-  const lmx_depth_diff_t* diffs;     // per raw record of the slot (k_depth_diff_records), device memory
+  // F2_DEPTH and F2_DEPTH_NORMAL only: a cluster's score is the mean of dv::value(diff, no_value) over its members
+  const lmx_depth_diff_t* diffs;     // per raw record of the slot (the record walk of lmx_verify.hip), device memory
   lmx_depth_diff_t* out_diffs;       // [n_frames][F2_MAX] in final-match order, next to out_matches (written, never read: may be mapped host memory)
   lmx_depth_diff_t* diff_scratch;    // [n_frames][2][F2_MAX] device memory: a frame's diffs by insertion position, then by final position
   double no_value;
-  // the NORMAL form only (launch_f2_normal): the same three for the normal sums; the score is the mean of nv::value(diff, ndiff, no_value)
+  // F2_DEPTH_NORMAL only: the same three for the normal sums; the score is the mean of nv::value(diff, ndiff, no_value)
   const lmx_normal_diff_t* ndiffs;
   lmx_normal_diff_t* out_ndiffs;
   lmx_normal_diff_t* ndiff_scratch;
-  // the CLASSES forms only (launch_f2_classes): a side-car per class instead of dists .. radius_step above, and each cluster's class
+  // the CLASSES forms only: a side-car per class instead of dists .. radius_step above, and each cluster's class
   const F2Class* classes;            // [F2_CLASSES], device memory
   int32_t* out_cluster_class;        // [n_frames][F2_MAX], next to out_clusters
 };
-void launch_f2(hipStream_t s, const F2Params& p);
-void launch_f2_scored(hipStream_t s, const F2Params& p);
-void launch_f2_normal(hipStream_t s, const F2Params& p);
-// the per-class chain (lmx_ctx_collect_clusters_classes); mode 0 mean similarity, 1 depth score, 2 depth + normal score
-void launch_f2_classes(hipStream_t s, const F2Params& p, int mode);
+// k_f2_finalize_cluster<score, classes>, one workgroup per frame; classes: the per-class chain (lmx_ctx_collect_clusters_classes)
+void launch_f2(hipStream_t s, const F2Params& p, F2Score score, bool classes);
 
-// The large-frame form of the same chain (k_f2_large*, lmx_f2.hip): frames of up to F2_LARGE_MAX raw records, one workgroup of 1024
+// The large-frame form of the same chain (k_f2_large, lmx_f2.hip): frames of up to F2_LARGE_MAX raw records, one workgroup of 1024
 // threads per LISTED frame, every per-record row in that frame's part of a device-memory workspace (a record costs 8 bytes of LDS in the
 // kernels above; 16384 of them do not fit).  A frame's part holds its outputs and the kernel's scratch rows at the offsets of
 // F2LargeLayout; the host reads back what the count words say.
@@ -317,12 +318,12 @@ struct F2LargeLayout {   // byte offsets into one frame's part of the workspace;
   uint32_t key, spill, sim, tid, rec, x, y, cls, perm, keep, seg, rpos, c_score, c_range, c_rect;
   uint32_t bytes;        // one frame's part, a multiple of 256
 };
-inline F2LargeLayout f2_large_layout(bool scored, bool normal) {
+inline F2LargeLayout f2_large_layout(F2Score score) {
   F2LargeLayout l{};
   uint32_t at = 0;
   auto row = [&](uint32_t elem) { const uint32_t o = at; at += (uint32_t)F2_LARGE_MAX * elem; return o; };
   l.matches = row(sizeof(lmx_match_t)); l.clusters = row(sizeof(lmx_cluster_t)); l.members = row(4); l.cluster_class = row(4);
-  l.diffs = scored ? row(sizeof(lmx_depth_diff_t)) : 0; l.ndiffs = normal ? row(sizeof(lmx_normal_diff_t)) : 0;
+  l.diffs = score != F2_SIMILARITY ? row(sizeof(lmx_depth_diff_t)) : 0; l.ndiffs = score == F2_DEPTH_NORMAL ? row(sizeof(lmx_normal_diff_t)) : 0;
   l.key = row(8); l.spill = row(8); l.c_score = row(8); l.c_range = row(8); l.c_rect = row(16);
   l.sim = row(4); l.tid = row(4); l.rec = row(4);
   l.x = row(2); l.y = row(2); l.cls = row(2); l.perm = row(2); l.keep = row(2); l.seg = row(2); l.rpos = row(2);
@@ -338,7 +339,7 @@ struct F2LargeParams {
   const uint32_t* n_listed = nullptr;   // device memory, optional: workgroups at or above *n_listed leave at once (a list built on the device,
                                         // lmx_export.hip); null: the grid is exact
 };
-void launch_f2_large(hipStream_t s, const F2LargeParams& p, int n_listed, int mode, bool classes);
+void launch_f2_large(hipStream_t s, const F2LargeParams& p, int n_listed, F2Score score, bool classes);
 
 // lmx_ctx_export_matches_on (lmx_export.hip; the arithmetic is lmx_export_pack.hpp): everything is device memory
 struct ExportParams {
@@ -346,7 +347,7 @@ struct ExportParams {
   const uint32_t* hdr;
   uint32_t cap;
   int32_t n_frames, max_large;
-  // what the chain's kernels wrote: the export's rows and counts, the large-frame workspace (f2_large_layout(false, false)) and its counts
+  // what the chain's kernels wrote: the export's rows and counts, the large-frame workspace (f2_large_layout(F2_SIMILARITY)) and its counts
   const lmx_match_t* rows_matches;       // [n_frames][F2_MAX]
   const lmx_cluster_t* rows_clusters;
   const int32_t* rows_members;
@@ -373,46 +374,49 @@ struct ExportParams {
 };
 void launch_export_plan(hipStream_t s, const ExportParams& e);   // max_large > 0 only
 void launch_export_pack(hipStream_t s, const ExportParams& e);
-void launch_debug_block_sort_large(hipStream_t s, const float* sim, const int* tid, int n, int* perm, uint8_t* ws /* f2_large_layout(false, false).bytes */);
+void launch_debug_block_sort_large(hipStream_t s, const float* sim, const int* tid, int n, int* perm, uint8_t* ws /* f2_large_layout(F2_SIMILARITY).bytes */);
 
 // ---- depth check against a resident scene (lmx_verify.hip), for the scored consumer chain (lmx_collect.cpp, lmx_debug.cpp) --------------
 struct DepthSceneInfo { int32_t device, count, n_frames, W, H, normals; };   // n_frames 0: no scene uploaded; normals: enable_normals was called
 std::mutex& depth_templates_mutex(lmx_depth_templates* t);
-DepthSceneInfo depth_templates_scene(const lmx_depth_templates* t);   // the four below: the object's mutex is the caller's to hold
+DepthSceneInfo depth_templates_scene(const lmx_depth_templates* t);   // everything below: the object's mutex is the caller's to hold
 // lmx_depth_templates_upload_scene without taking the mutex (depth must not be null)
 lmx_status depth_upload_scene(lmx_depth_templates* t, const lmx_image* depth, int32_t n_frames);
-// `s` waits for the scene's copies, then k_depth_diff_records: d_diffs[i] for d_recs[i], i < n_records (no launch for 0).  With d_ndiffs:
-// the scene's normals on `s` if nobody has computed them, then k_verify_diff_records (the same walk with both terms), which fills both
-lmx_status depth_launch_records(lmx_depth_templates* t, hipStream_t s, const lmx_raw_match_t* d_recs, uint32_t n_records, int32_t class_index,
-                                lmx_depth_diff_t* d_diffs, lmx_normal_diff_t* d_ndiffs = nullptr);
-// host matches of scene frame `frame` through k_depth_diff (synchronous); other classes and template ids outside the table get zeros
-// (nout: the normal sums too, through k_verify_diff)
+// The one launch site of the crop walk (k_walk / k_walk_records_dev): d_diffs[i] (with d_ndiffs: both terms, d_ndiffs[i] too) for item i.
+// The items are one of
+//   jobs            lmx_verify.hip's own match-list path: n jobs on the object's stream, against the n_frames W x H frames their call staged
+//   recs, n         RAW records counted by the host against the uploaded scene: `s` waits for the scene's copies; no launch for n = 0
+//   recs, hdr, cap  the same for a caller that has not read the slot's header (lmx_ctx_export_clusters_on): a fixed grid of persistent
+//                   workgroups takes the count from hdr[1] on the device and walks nothing when hdr says that a list overflowed `cap`;
+//                   room for `cap` results.  Launches always.  `s` also waits for every earlier such walk of the object, and the object
+//                   remembers an event behind this one: what changes the crops, the scene or the normals waits for it
+// A record is a job by class_index (-1: every class), or with d_class_base (n_classes + 1 entries, device memory) for an object that
+// holds several classes' crops (lmx_depth_templates_append): class c's template i is crop class_base[c] + i; a class >= n_classes, a
+// template_id outside [0, class_base[c + 1] - class_base[c]) or a frame outside the scene gets zeros and is never walked.
+// With d_ndiffs the scene's normals are computed on `s` first if nobody has.
+struct DepthJob;
+struct DepthWalk {
+  const DepthJob* jobs = nullptr;
+  int32_t n_frames = 0, W = 0, H = 0;   // jobs only; records take the uploaded scene's
+  const lmx_raw_match_t* recs = nullptr;
+  uint32_t n = 0;                       // jobs, or records counted by the host
+  const uint32_t* hdr = nullptr;        // non-null: the records are counted on the device
+  uint32_t cap = 0;
+  int32_t grid = 0;                     // device count only: workgroups; 0: the object's (a multiple of the device's compute units)
+  int32_t class_index = -1;
+  const int32_t* d_class_base = nullptr;
+  int32_t n_classes = 0;
+  lmx_depth_diff_t* d_diffs = nullptr;
+  lmx_normal_diff_t* d_ndiffs = nullptr;   // null: the depth term alone
+};
+lmx_status depth_launch_walk(lmx_depth_templates* t, hipStream_t s, const DepthWalk& w);
+// host matches of scene frame `frame` through the job walk (synchronous); other classes and template ids outside the table get zeros
+// (nout: the normal sums too)
 lmx_status depth_diff_resident(lmx_depth_templates* t, const lmx_match_t* matches, size_t n, int32_t frame, int32_t class_index, lmx_depth_diff_t* out,
                                lmx_normal_diff_t* nout = nullptr);
-// The two above for an object that holds several classes' crops (lmx_depth_templates_append): class c's template i is crop class_base[c] + i.
-// A record or match whose class is >= n_classes, whose template_id is outside [0, class_base[c + 1] - class_base[c]) or whose frame is
-// outside the scene gets zeros and is never walked.  d_class_base: n_classes + 1 entries in device memory; class_base: the same on the host.
-lmx_status depth_launch_records_classes(lmx_depth_templates* t, hipStream_t s, const lmx_raw_match_t* d_recs, uint32_t n_records, const int32_t* d_class_base,
-                                        int32_t n_classes, lmx_depth_diff_t* d_diffs, lmx_normal_diff_t* d_ndiffs = nullptr);
+// the same under the classed predicate; class_base: n_classes + 1 entries on the host
 lmx_status depth_diff_resident_classes(lmx_depth_templates* t, const lmx_match_t* matches, size_t n, int32_t frame, const int32_t* class_base, int32_t n_classes,
                                        lmx_depth_diff_t* out, lmx_normal_diff_t* nout = nullptr);
-// depth_launch_records / _classes for a caller that has not read the slot's header (lmx_ctx_export_clusters_on): k_walk_records_dev, a
-// fixed grid of persistent workgroups that take the record count from hdr[1] on the device and walk nothing when hdr says that a list
-// overflowed `cap`.  d_diffs[i] (d_ndiffs[i]) for recs[i], i < hdr[1]: room for `cap` records.  d_class_base null: the un-classed
-// predicate with class_index; else the classed one.  `s` first waits for the scene's copies and for every earlier such walk of the object,
-// and the object remembers an event behind this one: what changes the crops, the scene or the normals waits for it.  Launches always.
-struct DepthWalkRecords {
-  const uint32_t* hdr;
-  const lmx_raw_match_t* recs;
-  uint32_t cap;
-  int32_t class_index;
-  const int32_t* d_class_base;
-  int32_t n_classes;
-  lmx_depth_diff_t* d_diffs;
-  lmx_normal_diff_t* d_ndiffs;   // null: the depth term alone
-  int32_t grid;                  // workgroups; 0: the object's (a multiple of the device's compute units)
-};
-lmx_status depth_launch_records_dev(lmx_depth_templates* t, hipStream_t s, const DepthWalkRecords& w);
 void launch_debug_block_sort(hipStream_t s, const float* sim, const int* tid, int n, int* perm, unsigned long long* spill);
 
 struct PullEntry { uint64_t src; uint64_t row_stride; };  // one caller-owned pinned image (device-visible address)

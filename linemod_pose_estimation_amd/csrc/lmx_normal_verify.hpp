@@ -1,6 +1,6 @@
 // Normal-difference term of a match (lmx_normal_diff_matches, include/lmx.h): the arithmetic of one pixel's normal, one pixel pair's angle,
 // one match's sums and one match's value, shared by the HIP kernels (lmx_verify.hip: k_normal_map_*, and add_vector as the inner step of
-// k_verify_diff and k_verify_diff_records; lmx_f2.hip for value()) and -- compiled with LMX_NV_HOST -- by plain CPU builds
+// the NORMALS forms of k_walk and k_walk_records_dev; lmx_f2.hip for value()) and -- compiled with LMX_NV_HOST -- by plain CPU builds
 // (tests/cpp/normal_verify_host.cpp).
 // The reference's form is depth_normal_diff_calc (src/rgbdDetector.cpp:147-359), the normal half: the mean angle between the surface normals
 // of the template's rendered depth and of the scene depth over the pixels both cover.  The reference takes its normals from OpenCV's rgbd

@@ -6,12 +6,13 @@
 //                  aligned, in chunks of device memory (from_mesh: one per render batch, sized to that batch's crops; from_crops: one);
 //                  a table entry per template {address, w, h, pitch}
 //   k_depth_crop   from_mesh: copies each view's silhouette box out of the batch's depth planes into its chunk, writing the padding
-//   k_depth_diff   one 256-lane workgroup per match.  Lanes run along crop rows, one aligned 16-byte vector (8 pixels) each; a crop
-//                  narrower than 64 vectors packs several rows into a wave; waves take rows (groups of rows) in turn.  Scene pixels are
-//                  read as uint16 under the in-image predicate of lmx_depth_verify.hpp and nowhere else.  Per-lane sums are 64-bit;
-//                  wave shuffles, then LDS across the four waves, then one 16-byte store.  No atomics, no workgroup waits for another.
-//   k_depth_diff_records   the same walk (diff_walk: one template for all four walk kernels), one workgroup per RAW record of an output slot, against
-//                  the scene lmx_depth_templates_upload_scene left on the device: the input of the scored consumer chain (lmx_f2.hip)
+//   k_walk<NORMALS, SRC>   the crop walk (diff_walk), one 256-lane workgroup per item.  Lanes run along crop rows, one aligned 16-byte vector
+//                  (8 pixels) each; a crop narrower than 64 vectors packs several rows into a wave; waves take rows (groups of rows) in
+//                  turn.  Scene pixels are read as uint16 under the in-image predicate of lmx_depth_verify.hpp and nowhere else.  Per-lane
+//                  sums are 64-bit; wave shuffles, then LDS across the four waves, then one 16-byte store.  No atomics, no workgroup waits
+//                  for another.  SRC says what an item is (walk_item): a job of the host's match list against the frames its call staged,
+//                  or a RAW record of an output slot -- un-classed or classed -- against the scene lmx_depth_templates_upload_scene left on
+//                  the device: the input of the scored consumer chain (lmx_f2.hip).  All take one argument struct (WalkArgs)
 //   scene          one pinned staging buffer and one device buffer per object.  lmx_depth_diff_matches stages the frames that have matches
 //                  and waits for its results; upload_scene stages all frames, records an event behind their copies and returns
 // The normal term (lmx_depth_templates_enable_normals, lmx_normal_diff_matches; arithmetic: lmx_normal_verify.hpp), only for an object that
@@ -20,10 +21,10 @@
 //                  in-image predicate, one 8-byte store per pixel.  Crops: once per enable_normals, all crops in one launch, into chunks that
 //                  mirror the depth chunks (same pitch: the padding's normals are zeros).  Scene frames: once per scene, when a normal-scored
 //                  call first needs them, on that call's stream behind the scene's event
-//   k_verify_diff / k_verify_diff_records   the NORMALS instantiation of the same walk, both terms in one pass (nv::add_vector): the two
-//                  stored normals of a pixel are read next to its two depths, their angle comes out of the chord table in global memory
-//   k_walk_records_dev   the record kernels for a caller that has not read the slot's header (lmx_ctx_export_clusters_on): persistent
-//                  workgroups that take the record count from device memory; see the kernel
+//   k_walk<true, SRC>   the NORMALS instantiations of the same walk, both terms in one pass (nv::add_vector): the two stored normals of a
+//                  pixel are read next to its two depths, their angle comes out of the chord table in global memory
+//   k_walk_records_dev<NORMALS, CLASSES>   the record sources for a caller that has not read the slot's header (lmx_ctx_export_clusters_on):
+//                  persistent workgroups that take the record count from device memory; see the kernel
 // Pose refinement (lmx_pose_refine_matches; arithmetic and control: lmx_pose_refine.hpp), on the same table and scene:
 //   k_pose_refine  one 256-lane workgroup per match, the same walk over the crop's vectors once per pass, every pass of a job inside one
 //                  launch; see the kernel
@@ -33,7 +34,7 @@
 // Both stages on the clusters an export left in device memory (lmx_pose_chain_on; the decisions on the lists: lmx_pose_chain.hpp):
 //   k_pose_refine_clusters / k_pose_verify_clusters   one workgroup per cluster slot, the leader and its job found on the device, then the
 //                  bodies of the two kernels above; see the kernels
-// The host half has one launch site for jobs (run_jobs) and one for records (depth_launch_records), one body for both match-list paths
+// The host half has one launch site for every walk kernel (depth_launch_walk), one body for both match-list paths
 // (diff_selected), one guard in front of every normal-scored call (need_normals) and one body around the launch of both pose stages
 // (pose_call).
 #include <algorithm>
@@ -53,13 +54,13 @@
 #include "lmx_export_pack.hpp"
 
 namespace lmx {
+struct DepthJob { int32_t x, y, template_id, frame; };   // frame: index among the frames uploaded for this call
 namespace {
 
 struct DepthCrop {          // table entry: 24 bytes per template
   const uint16_t* data;     // [h][pitch], 16-byte aligned; null for an empty crop
   int32_t w, h, pitch, pad;
 };
-struct DepthJob { int32_t x, y, template_id, frame; };   // frame: index among the frames uploaded for this call
 static_assert(sizeof(DepthCrop) == 24 && sizeof(DepthJob) == 16 && sizeof(lmx_depth_diff_t) == 16, "layouts the kernels rely on");
 static_assert(sizeof(lmx_normal_diff_t) == 16 && sizeof(nv::Packed) == 8, "layouts the kernels rely on");
 
@@ -137,7 +138,7 @@ __device__ __forceinline__ void store_sums(lmx_depth_diff_t* __restrict__ out, l
   if constexpr (NORMALS) *reinterpret_cast<int4*>(nout) = make_int4((int)(uint32_t)angle, (int)(uint32_t)(angle >> 32), n_normal, 0);
 }
 
-// The crop walk of one match of template `id` at (x, y) against scene frame `f`, by a whole 256-lane workgroup: all four kernels below end
+// The crop walk of one match of template `id` at (x, y) against scene frame `f`, by a whole 256-lane workgroup: every walk kernel below ends
 // in it.  Lanes run along crop rows, one aligned vector each (dv::add_vector).  With NORMALS both terms in the same pass (nv::add_vector):
 // a lane reads its eight crop normals as four aligned 16-byte vectors next to the crop's depths, the scene's normals next to the scene's
 // depths, the angles out of the chord table; without, normals / scene_normals / table / nout are not looked at.  What is no job (is_job
@@ -215,42 +216,9 @@ __device__ __forceinline__ bool record_is_job(const lmx_raw_match_t& r, int32_t 
   return r.template_id >= 0 && r.template_id < count && r.frame >= 0 && r.frame < n_frames && (class_index < 0 || r.class_index == class_index);
 }
 
-// The four kernels, one workgroup per match: the depth term alone or both terms, times the two ways of fetching a job -- job j of the host's
-// match list (its frame is its slot among the frames in `scene`), or RAW record j against the scene upload_scene left on the device.
-__global__ __launch_bounds__(256) void k_depth_diff(const DepthCrop* __restrict__ crops, const DepthJob* __restrict__ jobs,
-                                                    const uint16_t* __restrict__ scene, int W, int H, lmx_depth_diff_t* __restrict__ out) {
-  const DepthJob j = jobs[blockIdx.x];
-  diff_walk<false>(crops, nullptr, true, j.template_id, j.x, j.y, j.frame, scene, nullptr, W, H, nullptr, &out[blockIdx.x], nullptr);
-}
-
-__global__ __launch_bounds__(256) void k_depth_diff_records(const DepthCrop* __restrict__ crops, int32_t count, const lmx_raw_match_t* __restrict__ recs,
-                                                            const uint16_t* __restrict__ scene, int32_t n_frames, int W, int H, int32_t class_index,
-                                                            lmx_depth_diff_t* __restrict__ diffs) {
-  const lmx_raw_match_t r = recs[blockIdx.x];
-  diff_walk<false>(crops, nullptr, record_is_job(r, count, n_frames, class_index), r.template_id, r.x, r.y, r.frame, scene, nullptr, W, H, nullptr,
-                   &diffs[blockIdx.x], nullptr);
-}
-
-__global__ __launch_bounds__(256) void k_verify_diff(const DepthCrop* __restrict__ crops, nv::Packed* const* __restrict__ normals, const DepthJob* __restrict__ jobs,
-                                                     const uint16_t* __restrict__ scene, const nv::Packed* __restrict__ scene_normals, int W, int H,
-                                                     const uint32_t* __restrict__ table, lmx_depth_diff_t* __restrict__ out, lmx_normal_diff_t* __restrict__ nout) {
-  const DepthJob j = jobs[blockIdx.x];
-  diff_walk<true>(crops, normals, true, j.template_id, j.x, j.y, j.frame, scene, scene_normals, W, H, table, &out[blockIdx.x], &nout[blockIdx.x]);
-}
-
-__global__ __launch_bounds__(256) void k_verify_diff_records(const DepthCrop* __restrict__ crops, nv::Packed* const* __restrict__ normals, int32_t count,
-                                                             const lmx_raw_match_t* __restrict__ recs, const uint16_t* __restrict__ scene,
-                                                             const nv::Packed* __restrict__ scene_normals, int32_t n_frames, int W, int H, int32_t class_index,
-                                                             const uint32_t* __restrict__ table, lmx_depth_diff_t* __restrict__ diffs,
-                                                             lmx_normal_diff_t* __restrict__ ndiffs) {
-  const lmx_raw_match_t r = recs[blockIdx.x];
-  diff_walk<true>(crops, normals, record_is_job(r, count, n_frames, class_index), r.template_id, r.x, r.y, r.frame, scene, scene_normals, W, H, table,
-                  &diffs[blockIdx.x], &ndiffs[blockIdx.x]);
-}
-
-// The two record kernels for an object that holds several classes' crops one class after the other (lmx_depth_templates_append): class c's
-// template i is crop class_base[c] + i.  No job, hence zeros and no walk, for a class >= n_classes, a template_id outside its class's range
-// (it would be the next class's crop), a frame outside the scene.
+// The same for an object that holds several classes' crops one class after the other (lmx_depth_templates_append): class c's template i is
+// crop class_base[c] + i.  No job, hence zeros and no walk, for a class >= n_classes, a template_id outside its class's range (it would be
+// the next class's crop), a frame outside the scene.
 __device__ __forceinline__ bool record_class_job(const lmx_raw_match_t& r, const int32_t* __restrict__ class_base, int32_t n_classes, int32_t n_frames, int32_t* id) {
   *id = 0;
   if (r.class_index < 0 || r.class_index >= n_classes || r.frame < 0 || r.frame >= n_frames) return false;
@@ -260,28 +228,58 @@ __device__ __forceinline__ bool record_class_job(const lmx_raw_match_t& r, const
   return true;
 }
 
-__global__ __launch_bounds__(256) void k_depth_diff_records_classes(const DepthCrop* __restrict__ crops, const int32_t* __restrict__ class_base, int32_t n_classes,
-                                                                    const lmx_raw_match_t* __restrict__ recs, const uint16_t* __restrict__ scene, int32_t n_frames,
-                                                                    int W, int H, lmx_depth_diff_t* __restrict__ diffs) {
-  const lmx_raw_match_t r = recs[blockIdx.x];
-  int32_t id;
-  const bool is_job = record_class_job(r, class_base, n_classes, n_frames, &id);
-  diff_walk<false>(crops, nullptr, is_job, id, r.x, r.y, r.frame, scene, nullptr, W, H, nullptr, &diffs[blockIdx.x], nullptr);
+// What every walk kernel takes, by value.  The items come from one of three sources: job i of the host's match list (its frame is its slot
+// among the frames in `scene`), or RAW record i of an output slot against the scene upload_scene left on the device, under one of the two
+// predicates above.
+enum WalkSource { WALK_JOBS, WALK_RECORDS, WALK_RECORDS_CLASSES };
+struct WalkArgs {
+  const DepthCrop* crops;
+  nv::Packed* const* normals;
+  const uint32_t* hdr;              // k_walk_records_dev: the slot's header, [0] candidates, [1] records
+  const lmx_raw_match_t* recs;      // the two record sources
+  uint32_t cap;                     // k_walk_records_dev: of the slot's lists
+  int32_t count;                    // WALK_RECORDS: templates in the table
+  int32_t class_index;              // WALK_RECORDS: -1 = every class
+  const int32_t* class_base;        // WALK_RECORDS_CLASSES: n_classes + 1 entries
+  int32_t n_classes;
+  const uint16_t* scene;
+  const nv::Packed* scene_normals;
+  int32_t n_frames, W, H;
+  const uint32_t* table;
+  lmx_depth_diff_t* diffs;
+  lmx_normal_diff_t* ndiffs;
+  const DepthJob* jobs;             // WALK_JOBS; last, so the record kernels keep the argument offsets they had
+};
+struct WalkItem { bool is_job; int32_t id, x, y, frame; };
+
+// Item i of a source: walk_item; its record half, on a record the caller has loaded: record_item (k_walk_records_dev says why it loads itself).
+template <int SRC>
+__device__ __forceinline__ WalkItem record_item(const WalkArgs& a, const lmx_raw_match_t& r) {
+  WalkItem it{false, r.template_id, r.x, r.y, r.frame};
+  if constexpr (SRC == WALK_RECORDS_CLASSES) it.is_job = record_class_job(r, a.class_base, a.n_classes, a.n_frames, &it.id);
+  else it.is_job = record_is_job(r, a.count, a.n_frames, a.class_index);
+  return it;
+}
+template <int SRC>
+__device__ __forceinline__ WalkItem walk_item(const WalkArgs& a, uint32_t i) {
+  if constexpr (SRC == WALK_JOBS) {
+    const DepthJob j = a.jobs[i];
+    return WalkItem{true, j.template_id, j.x, j.y, j.frame};
+  } else {
+    const lmx_raw_match_t r = a.recs[i];
+    return record_item<SRC>(a, r);
+  }
 }
 
-__global__ __launch_bounds__(256) void k_verify_diff_records_classes(const DepthCrop* __restrict__ crops, nv::Packed* const* __restrict__ normals,
-                                                                     const int32_t* __restrict__ class_base, int32_t n_classes,
-                                                                     const lmx_raw_match_t* __restrict__ recs, const uint16_t* __restrict__ scene,
-                                                                     const nv::Packed* __restrict__ scene_normals, int32_t n_frames, int W, int H,
-                                                                     const uint32_t* __restrict__ table, lmx_depth_diff_t* __restrict__ diffs,
-                                                                     lmx_normal_diff_t* __restrict__ ndiffs) {
-  const lmx_raw_match_t r = recs[blockIdx.x];
-  int32_t id;
-  const bool is_job = record_class_job(r, class_base, n_classes, n_frames, &id);
-  diff_walk<true>(crops, normals, is_job, id, r.x, r.y, r.frame, scene, scene_normals, W, H, table, &diffs[blockIdx.x], &ndiffs[blockIdx.x]);
+// One workgroup per item: the depth term alone or both terms, times the three sources.  What is no job takes diff_walk's zero-store exit.
+template <bool NORMALS, int SRC>
+__global__ __launch_bounds__(256) void k_walk(const WalkArgs a) {
+  const WalkItem it = walk_item<SRC>(a, blockIdx.x);
+  diff_walk<NORMALS>(a.crops, a.normals, it.is_job, it.id, it.x, it.y, it.frame, a.scene, a.scene_normals, a.W, a.H, a.table, &a.diffs[blockIdx.x],
+                     NORMALS ? &a.ndiffs[blockIdx.x] : nullptr);
 }
 
-// The four record kernels again for a caller that does not know the record count (lmx_ctx_export_clusters_on: no host reads the slot):
+// The record kernels again for a caller that does not know the record count (lmx_ctx_export_clusters_on: no host reads the slot):
 // a fixed grid of persistent workgroups, workgroup b walks records b, b + gridDim.x, ... below hdr[1], which every lane reads from the
 // slot's header in device memory; a list that overflowed is not walked at all (the pack kernel reports it).  Record i is a job or not by
 // the same two predicates, and gets the same 16 (32) bytes from the same diff_walk.
@@ -292,39 +290,20 @@ __global__ __launch_bounds__(256) void k_verify_diff_records_classes(const Depth
 // either.  Chosen over two alternating LDS sets: it leaves diff_walk as it is, and the wait is short -- the other waves spend it on
 // the next record's load, which is issued in front of the barrier.  n, i and `walks` depend on the header, blockIdx and record i alone:
 // every lane of a workgroup takes the same trips and the same branch around the barrier.
-struct WalkDev {
-  const DepthCrop* crops;
-  nv::Packed* const* normals;
-  const uint32_t* hdr;              // the slot's header: [0] candidates, [1] records
-  const lmx_raw_match_t* recs;
-  uint32_t cap;                     // of the slot's lists
-  int32_t count;                    // un-classed: templates in the table
-  int32_t class_index;              // un-classed: -1 = every class
-  const int32_t* class_base;        // CLASSES: n_classes + 1 entries
-  int32_t n_classes;
-  const uint16_t* scene;
-  const nv::Packed* scene_normals;
-  int32_t n_frames, W, H;
-  const uint32_t* table;
-  lmx_depth_diff_t* diffs;
-  lmx_normal_diff_t* ndiffs;
-};
-
 template <bool NORMALS, bool CLASSES>
-__global__ __launch_bounds__(256) void k_walk_records_dev(const WalkDev a) {
+__global__ __launch_bounds__(256) void k_walk_records_dev(const WalkArgs a) {
   const uint32_t n_cand = a.hdr[0], n = a.hdr[1];
   if (xpack::list_overflowed(n_cand, n, a.cap)) return;
   bool dirty = false;   // an earlier walk of this workgroup used the LDS sums
   for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
+    // loaded here, not inside walk_item: there the compiler splits the record's 12-byte load of {template_id, class_index, frame} in three and
+    // puts the class's behind the template test -- a second memory round trip per record (profiles/walk_variants_refactor.txt)
     const lmx_raw_match_t r = a.recs[i];
-    int32_t id = r.template_id;
-    bool is_job;
-    if constexpr (CLASSES) is_job = record_class_job(r, a.class_base, a.n_classes, a.n_frames, &id);
-    else is_job = record_is_job(r, a.count, a.n_frames, a.class_index);
+    const WalkItem it = record_item<CLASSES ? WALK_RECORDS_CLASSES : WALK_RECORDS>(a, r);
     bool walks = false;
-    if (is_job) { const DepthCrop c = a.crops[id]; walks = c.w > 0 && c.h > 0; }
+    if (it.is_job) { const DepthCrop c = a.crops[it.id]; walks = c.w > 0 && c.h > 0; }
     if (walks && dirty) __syncthreads();
-    diff_walk<NORMALS>(a.crops, a.normals, is_job, id, r.x, r.y, r.frame, a.scene, a.scene_normals, a.W, a.H, a.table, &a.diffs[i],
+    diff_walk<NORMALS>(a.crops, a.normals, it.is_job, it.id, it.x, it.y, it.frame, a.scene, a.scene_normals, a.W, a.H, a.table, &a.diffs[i],
                        NORMALS ? &a.ndiffs[i] : nullptr);
     dirty = dirty || walks;
   }
@@ -1156,21 +1135,15 @@ lmx_status queue_frame(lmx_depth_templates* t, const lmx_image& im, int32_t slot
 }
 
 // The device half of a depth check on the host's match list: the first n entries of h_jobs against the W x H frames already in d_scene
-// (a job's frame is its slot there): job upload, k_depth_diff, read-back into h_out.  The object's mutex is the caller's to hold.
-// With `normals`: k_verify_diff instead, against the normals of the n_frames frames there (computed first if nobody has), h_nout too.
+// (a job's frame is its slot there): job upload, the walk (depth_launch_walk, the job form), read-back into h_out.  The object's mutex is
+// the caller's to hold.  With `normals`: both terms, against the normals of the n_frames frames there (computed first if nobody has), h_nout too.
 lmx_status run_jobs(lmx_depth_templates* t, size_t n, int32_t n_frames, int32_t W, int32_t H, bool normals) {
   hipStream_t s = t->s;
   DV_HIP(hipMemcpyAsync(t->d_jobs, t->h_jobs, n * sizeof(lmx::DepthJob), hipMemcpyHostToDevice, s));
-  if (normals)
-    if (lmx_status st = t->scene_normals_on(s, nullptr, n_frames, W, H)) return st;
-  const int pe = normals ? t->prof_begin(lmx_depth_templates::PK_VERIFY_DIFF, s) : -1;   // k_depth_diff has no bracket
-  if (normals)
-    hipLaunchKernelGGL(lmx::k_verify_diff, dim3((unsigned)n), dim3(256), 0, s, t->d_table, t->d_ntable, t->d_jobs, t->d_scene, t->d_scene_normals, W, H,
-                       t->d_angle, t->d_out, t->d_nout);
-  else
-    hipLaunchKernelGGL(lmx::k_depth_diff, dim3((unsigned)n), dim3(256), 0, s, t->d_table, t->d_jobs, t->d_scene, W, H, t->d_out);
-  t->prof_end(pe, s);
-  DV_HIP(hipGetLastError());
+  lmx::DepthWalk w;
+  w.jobs = t->d_jobs; w.n = (uint32_t)n; w.n_frames = n_frames; w.W = W; w.H = H;
+  w.d_diffs = t->d_out; w.d_ndiffs = normals ? t->d_nout : nullptr;
+  if (lmx_status st = lmx::depth_launch_walk(t, s, w)) return st;
   DV_HIP(hipMemcpyAsync(t->h_out, t->d_out, n * sizeof(lmx_depth_diff_t), hipMemcpyDeviceToHost, s));
   if (normals) DV_HIP(hipMemcpyAsync(t->h_nout, t->d_nout, n * sizeof(lmx_normal_diff_t), hipMemcpyDeviceToHost, s));
   DV_HIP(hipStreamSynchronize(s));
@@ -1339,28 +1312,6 @@ lmx_status depth_upload_scene(lmx_depth_templates* t, const lmx_image* depth, in
   return LMX_OK;   // no host synchronisation: the transfer overlaps whatever the caller queued before
 }
 
-lmx_status depth_launch_records(lmx_depth_templates* t, hipStream_t s, const lmx_raw_match_t* d_recs, uint32_t n_records, int32_t class_index,
-                                lmx_depth_diff_t* d_diffs, lmx_normal_diff_t* d_ndiffs) {
-  if (t->scene_frames < 1) { set_error("no scene uploaded: call lmx_depth_templates_upload_scene first"); return LMX_ERR_INVALID_ARG; }
-  if (d_ndiffs)
-    if (lmx_status st = need_normals(t, nullptr)) return st;
-  DV_HIP(hipStreamWaitEvent(s, t->scene_ready, 0));
-  if (n_records == 0) return LMX_OK;
-  if (d_ndiffs)   // the scene's normals first, on this stream, if this is the scene's first normal-scored call
-    if (lmx_status st = t->scene_normals_on(s, nullptr, t->scene_frames, t->scene_W, t->scene_H)) return st;
-  const int32_t count = (int32_t)t->table.size();
-  const int pe = t->prof_begin(d_ndiffs ? lmx_depth_templates::PK_VERIFY_DIFF_RECORDS : lmx_depth_templates::PK_DEPTH_DIFF_RECORDS, s);
-  if (d_ndiffs)
-    hipLaunchKernelGGL(k_verify_diff_records, dim3(n_records), dim3(256), 0, s, t->d_table, t->d_ntable, count, d_recs, t->d_scene, t->d_scene_normals,
-                       t->scene_frames, t->scene_W, t->scene_H, class_index, t->d_angle, d_diffs, d_ndiffs);
-  else
-    hipLaunchKernelGGL(k_depth_diff_records, dim3(n_records), dim3(256), 0, s, t->d_table, count, d_recs, t->d_scene, t->scene_frames, t->scene_W,
-                       t->scene_H, class_index, d_diffs);
-  t->prof_end(pe, s);
-  DV_HIP(hipGetLastError());
-  return LMX_OK;
-}
-
 lmx_status depth_diff_resident(lmx_depth_templates* t, const lmx_match_t* matches, size_t n, int32_t frame, int32_t class_index, lmx_depth_diff_t* out,
                                lmx_normal_diff_t* nout) {
   if (n == 0) return LMX_OK;
@@ -1373,7 +1324,7 @@ lmx_status depth_diff_resident(lmx_depth_templates* t, const lmx_match_t* matche
   for (size_t i = 0; i < n; ++i) {
     const lmx_match_t& m = matches[i];
     if (class_index >= 0 && m.class_index != class_index) continue;
-    if (m.template_id < 0 || (size_t)m.template_id >= count) continue;   // zeros, as k_depth_diff_records gives; the cluster step refuses the id
+    if (m.template_id < 0 || (size_t)m.template_id >= count) continue;   // zeros, as the record walk gives; the cluster step refuses the id
     t->sel.push_back((uint32_t)i);
   }
   if (t->sel.empty()) return LMX_OK;
@@ -1382,66 +1333,69 @@ lmx_status depth_diff_resident(lmx_depth_templates* t, const lmx_match_t* matche
   return diff_selected(t, matches, nullptr, frame, t->scene_frames, t->scene_W, t->scene_H, out, nout);   // on the object's stream, behind the scene's copies
 }
 
-lmx_status depth_launch_records_classes(lmx_depth_templates* t, hipStream_t s, const lmx_raw_match_t* d_recs, uint32_t n_records, const int32_t* d_class_base,
-                                        int32_t n_classes, lmx_depth_diff_t* d_diffs, lmx_normal_diff_t* d_ndiffs) {
-  if (t->scene_frames < 1) { set_error("no scene uploaded: call lmx_depth_templates_upload_scene first"); return LMX_ERR_INVALID_ARG; }
-  if (d_ndiffs)
-    if (lmx_status st = need_normals(t, nullptr)) return st;
-  DV_HIP(hipStreamWaitEvent(s, t->scene_ready, 0));
-  if (n_records == 0) return LMX_OK;
-  if (d_ndiffs)
-    if (lmx_status st = t->scene_normals_on(s, nullptr, t->scene_frames, t->scene_W, t->scene_H)) return st;
-  const int pe = t->prof_begin(d_ndiffs ? lmx_depth_templates::PK_VERIFY_DIFF_RECORDS : lmx_depth_templates::PK_DEPTH_DIFF_RECORDS, s);
-  if (d_ndiffs)
-    hipLaunchKernelGGL(k_verify_diff_records_classes, dim3(n_records), dim3(256), 0, s, t->d_table, t->d_ntable, d_class_base, n_classes, d_recs, t->d_scene,
-                       t->d_scene_normals, t->scene_frames, t->scene_W, t->scene_H, t->d_angle, d_diffs, d_ndiffs);
-  else
-    hipLaunchKernelGGL(k_depth_diff_records_classes, dim3(n_records), dim3(256), 0, s, t->d_table, d_class_base, n_classes, d_recs, t->d_scene, t->scene_frames,
-                       t->scene_W, t->scene_H, d_diffs);
-  t->prof_end(pe, s);
-  DV_HIP(hipGetLastError());
-  return LMX_OK;
-}
-
 // Workgroups of the persistent walk per compute unit.  profiles/export_clusters.txt: the smallest of the grids measured whose time lies
 // within the run-to-run spread of the best.
 constexpr int kWalkGridPerCU = 4;
 
-lmx_status depth_launch_records_dev(lmx_depth_templates* t, hipStream_t s, const DepthWalkRecords& w) {
-  if (t->scene_frames < 1) { set_error("no scene uploaded: call lmx_depth_templates_upload_scene first"); return LMX_ERR_INVALID_ARG; }
-  if (w.d_ndiffs)
-    if (lmx_status st = need_normals(t, nullptr)) return st;
-  if (lmx_status st = t->ensure_device()) return st;   // the table, after an append
-  if (!t->export_read) DV_HIP(hipEventCreateWithFlags(&t->export_read, hipEventDisableTiming));
-  int32_t grid = w.grid;
-  if (grid <= 0) {
-    if (t->walk_grid <= 0) {
+namespace {
+template <bool NORMALS>
+void launch_walk(hipStream_t s, unsigned grid, bool device_count, int src, const WalkArgs& a) {
+  const dim3 g(grid), b(256);
+  if (device_count) {
+    if (src == WALK_RECORDS_CLASSES) hipLaunchKernelGGL((k_walk_records_dev<NORMALS, true>), g, b, 0, s, a);
+    else hipLaunchKernelGGL((k_walk_records_dev<NORMALS, false>), g, b, 0, s, a);
+    return;
+  }
+  switch (src) {
+    case WALK_JOBS: hipLaunchKernelGGL((k_walk<NORMALS, WALK_JOBS>), g, b, 0, s, a); break;
+    case WALK_RECORDS: hipLaunchKernelGGL((k_walk<NORMALS, WALK_RECORDS>), g, b, 0, s, a); break;
+    default: hipLaunchKernelGGL((k_walk<NORMALS, WALK_RECORDS_CLASSES>), g, b, 0, s, a); break;
+  }
+}
+}  // namespace
+
+lmx_status depth_launch_walk(lmx_depth_templates* t, hipStream_t s, const DepthWalk& w) {
+  const bool jobs = w.jobs != nullptr, device_count = w.hdr != nullptr, normals = w.d_ndiffs != nullptr;
+  const int src = jobs ? WALK_JOBS : (w.d_class_base ? WALK_RECORDS_CLASSES : WALK_RECORDS);
+  int32_t n_frames = w.n_frames, W = w.W, H = w.H;
+  if (!jobs) {   // records walk against the uploaded scene; the job form's caller has staged frames that are no scene and made the device ready
+    if (t->scene_frames < 1) { set_error("no scene uploaded: call lmx_depth_templates_upload_scene first"); return LMX_ERR_INVALID_ARG; }
+    if (normals)
+      if (lmx_status st = need_normals(t, nullptr)) return st;
+    n_frames = t->scene_frames; W = t->scene_W; H = t->scene_H;
+  }
+  unsigned grid = w.n;
+  if (device_count) {
+    if (lmx_status st = t->ensure_device()) return st;   // the table, after an append: an export checks nothing else of the object first
+    if (!t->export_read) DV_HIP(hipEventCreateWithFlags(&t->export_read, hipEventDisableTiming));
+    if (w.grid <= 0 && t->walk_grid <= 0) {
       int cus = 0;
       DV_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, t->device));
       t->walk_grid = kWalkGridPerCU * std::max(cus, 1);
     }
-    grid = t->walk_grid;
+    grid = (unsigned)(w.grid > 0 ? w.grid : t->walk_grid);
+    // this form alone: nobody waits for it on the host, so the record below must stand behind every earlier such walk too.  A host-count
+    // walk ends synchronised, and the collect's stream must not start waiting for exports
+    if (t->export_read_pending) DV_HIP(hipStreamWaitEvent(s, t->export_read, 0));
   }
-  if (t->export_read_pending) DV_HIP(hipStreamWaitEvent(s, t->export_read, 0));   // the record below then stands behind every earlier walk too
-  DV_HIP(hipStreamWaitEvent(s, t->scene_ready, 0));
-  if (w.d_ndiffs)   // the scene's normals first, on this stream, if this is the scene's first normal-scored call
-    if (lmx_status st = t->scene_normals_on(s, nullptr, t->scene_frames, t->scene_W, t->scene_H)) return st;
-  const WalkDev a{t->d_table, t->d_ntable, w.hdr, w.recs, w.cap, (int32_t)t->table.size(), w.class_index, w.d_class_base, w.n_classes, t->d_scene,
-                  t->d_scene_normals, t->scene_frames, t->scene_W, t->scene_H, t->d_angle, w.d_diffs, w.d_ndiffs};
-  const bool classes = w.d_class_base != nullptr;
-  const int pe = t->prof_begin(lmx_depth_templates::PK_WALK_RECORDS_DEV, s);
-  const dim3 g((unsigned)grid), b(256);
-  if (w.d_ndiffs) {
-    if (classes) hipLaunchKernelGGL((k_walk_records_dev<true, true>), g, b, 0, s, a);
-    else hipLaunchKernelGGL((k_walk_records_dev<true, false>), g, b, 0, s, a);
-  } else {
-    if (classes) hipLaunchKernelGGL((k_walk_records_dev<false, true>), g, b, 0, s, a);
-    else hipLaunchKernelGGL((k_walk_records_dev<false, false>), g, b, 0, s, a);
-  }
+  if (!jobs) DV_HIP(hipStreamWaitEvent(s, t->scene_ready, 0));   // the job form runs on the stream that carries the frames' copies
+  if (!device_count && w.n == 0) return LMX_OK;   // a grid of 0 is no launch; the device-count form launches always: nobody here knows the count
+  if (normals)   // the scene's normals first, on this stream, if this is the scene's first normal-scored call
+    if (lmx_status st = t->scene_normals_on(s, nullptr, n_frames, W, H)) return st;
+  const WalkArgs a{t->d_table, t->d_ntable, w.hdr, w.recs, w.cap, (int32_t)t->table.size(), w.class_index, w.d_class_base, w.n_classes, t->d_scene,
+                   t->d_scene_normals, n_frames, W, H, t->d_angle, w.d_diffs, w.d_ndiffs, w.jobs};
+  using PK = lmx_depth_templates;
+  // the depth-only job walk has never had a bracket: the labels are public (DepthTemplates.KERNELS) and there is none for it
+  const int label = device_count ? PK::PK_WALK_RECORDS_DEV : jobs ? (normals ? PK::PK_VERIFY_DIFF : -1) : (normals ? PK::PK_VERIFY_DIFF_RECORDS : PK::PK_DEPTH_DIFF_RECORDS);
+  const int pe = label >= 0 ? t->prof_begin(label, s) : -1;
+  if (normals) launch_walk<true>(s, grid, device_count, src, a);
+  else launch_walk<false>(s, grid, device_count, src, a);
   t->prof_end(pe, s);
   DV_HIP(hipGetLastError());
-  DV_HIP(hipEventRecord(t->export_read, s));
-  t->export_read_pending = true;
+  if (device_count) {   // what changes the crops, the scene or the normals waits for this
+    DV_HIP(hipEventRecord(t->export_read, s));
+    t->export_read_pending = true;
+  }
   return LMX_OK;
 }
 
@@ -1677,9 +1631,11 @@ extern "C" lmx_status lmx_debug_depth_walk_records(lmx_depth_templates* t, const
       DV_HIP(hipMalloc(&d_base.p, ((size_t)n_classes + 1) * sizeof(int32_t)));
       DV_HIP(hipMemcpyAsync(d_base.p, class_base, ((size_t)n_classes + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
     }
-    const DepthWalkRecords w{d_hdr.as<uint32_t>(), d_recs.as<lmx_raw_match_t>(), cap, class_index, d_base.as<int32_t>(), class_base ? n_classes : 0,
-                             d_diffs.as<lmx_depth_diff_t>(), d_ndiffs.as<lmx_normal_diff_t>(), grid_workgroups};
-    lmx_status st = depth_launch_records_dev(t, s, w);
+    DepthWalk w;
+    w.recs = d_recs.as<lmx_raw_match_t>(); w.hdr = d_hdr.as<uint32_t>(); w.cap = cap; w.grid = grid_workgroups;
+    w.class_index = class_index; w.d_class_base = d_base.as<int32_t>(); w.n_classes = class_base ? n_classes : 0;
+    w.d_diffs = d_diffs.as<lmx_depth_diff_t>(); w.d_ndiffs = d_ndiffs.as<lmx_normal_diff_t>();
+    lmx_status st = depth_launch_walk(t, s, w);
     if (st == LMX_OK && n_records) {
       DV_HIP(hipMemcpyAsync(diffs, d_diffs.p, n_records * sizeof(lmx_depth_diff_t), hipMemcpyDeviceToHost, s));
       if (ndiffs) DV_HIP(hipMemcpyAsync(ndiffs, d_ndiffs.p, n_records * sizeof(lmx_normal_diff_t), hipMemcpyDeviceToHost, s));

@@ -1614,6 +1614,9 @@ class DepthTemplates:
         del keep, frames
         return out[0], sums
 
+    # Labels of the library's profiling brackets (its PK_* enum, in that order), not symbol names: "k_verify_diff_records", "k_verify_diff"
+    # and "k_depth_diff_records" are the record walk with both terms, the job walk with both terms and the depth-only record walk (all
+    # instantiations of k_walk, csrc/lmx_verify.hip); the depth-only job walk has no bracket.
     KERNELS = ("k_normal_map_frames", "k_verify_diff_records", "k_verify_diff", "k_depth_diff_records", "k_walk_records_dev", "k_pose_refine", "k_pose_verify",
                "k_pose_refine_clusters", "k_pose_verify_clusters")
 

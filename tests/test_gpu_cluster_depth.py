@@ -1,4 +1,4 @@
-"""Depth-scored clusters on the device (lmx_ctx_collect_clusters_depth: k_depth_diff_records, csrc/lmx_verify.hip, then the SCORED form of
+"""Depth-scored clusters on the device (lmx_ctx_collect_clusters_depth: the record form of k_walk, csrc/lmx_verify.hip, then the SCORED form of
 k_f2_finalize_cluster, csrc/lmx_f2.hip) against the three-call composition it replaces: lmx_ctx_collect + lmx_depth_diff_matches +
 lmx_cluster_matches_scored.  The expected values come from pieces the scored chain does not touch: cluster_cases.reference (numpy + the
 real std::sort) for the final matches and the status, depth_verify_cases.np_diff for every match's difference, depth_values and the host

@@ -1,4 +1,4 @@
-"""The scored and the per-class instantiations of the large-frame chain (k_f2_large_scored, k_f2_large_classes and its two scored forms)
+"""The scored and the per-class instantiations of the large-frame chain (k_f2_large with a score, with classes, and with both)
 through lmx_debug_device_finalize_cluster_large_depth and _large_classes, on two frames of 2049 and 4096 records from the lattice builders
 of tests/cluster_cases.py.  Expected values: the cases' library-independent final matches, then the host composition the scored tests of
 the LDS kernels use -- lmx_depth_diff_matches / lmx_normal_diff_matches on those matches and lmx_cluster_matches_scored, per class for the

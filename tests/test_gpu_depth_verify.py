@@ -1,4 +1,4 @@
-"""The depth check of matches on the device (csrc/lmx_verify.hip): k_depth_diff on constructed crops against the numpy restatement of
+"""The depth check of matches on the device (csrc/lmx_verify.hip): the job form of k_walk on constructed crops against the numpy restatement of
 tests/depth_verify_cases.py, every integer; the batch form; DepthTemplates.from_mesh (renderer + k_depth_crop) against
 meshsynth.render_view; renderer and kernel against each other; the chain train -> match -> depth check -> cluster from Python and from
 C++ (tests/cpp/depth_verify_main.cpp).  Integer outputs are compared exactly; nothing here has a tolerance."""

@@ -3,7 +3,7 @@ depth / depth + normal) left in device memory, and the kernel it adds, k_walk_re
 slot's raw records by persistent workgroups that read the record count from device memory.
 Yardsticks, all of them entry points and restatements that existed before: collect_clusters, collect_clusters_depth,
 collect_clusters_depth_normal and collect_clusters_classes of the SAME enqueue after the export (the export consumes nothing);
-depth_verify_cases.np_diff per record and DepthTemplates.normal_diff (k_verify_diff) for the walk alone.  Everything is compared bit for bit.
+depth_verify_cases.np_diff per record and DepthTemplates.normal_diff (the job form of k_walk) for the walk alone.  Everything is compared bit for bit.
 Configurations: tests/test_gpu_export_matches.py's (160 x 160, bank seed 91, 80 templates, threshold 45: frame A beyond 2048 raw records,
 Z none, B few) with one crop per template, and tests/test_gpu_cluster_classes.py's two-class fixture.
 Not reached: a frame beyond 16384 records and a device group's member context, as in tests/test_gpu_export_matches.py."""
@@ -94,7 +94,7 @@ def walk():
         for i, k in enumerate(ids):
             if k is not None and crops[k].size:
                 dd[i] = dvc.np_diff(crops[k], scenes[int(rec["frame"][i])], int(rec["x"][i]), int(rec["y"][i]))
-        # the old kernels on the jobs: k_verify_diff through normal_diff, frame by frame
+        # the one-workgroup-per-item kernels on the jobs: k_walk through normal_diff, frame by frame
         nd = np.zeros(n, NORMAL_DIFF_DTYPE)
         jobs = [i for i, k in enumerate(ids) if k is not None]
         order = sorted(jobs, key=lambda i: int(rec["frame"][i]))

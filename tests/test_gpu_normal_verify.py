@@ -1,5 +1,5 @@
-"""The normal term of a match on the device (csrc/lmx_verify.hip: k_normal_map_frames, k_normal_map_crops, k_verify_diff,
-k_verify_diff_records; csrc/lmx_f2.hip: the third form of k_f2_finalize_cluster) against the CPU build of the shared header and the numpy
+"""The normal term of a match on the device (csrc/lmx_verify.hip: k_normal_map_frames, k_normal_map_crops, the NORMALS
+forms of k_walk; csrc/lmx_f2.hip: the third form of k_f2_finalize_cluster) against the CPU build of the shared header and the numpy
 restatement of tests/normal_verify_cases.py.  Every output is integer or compared bit for bit; nothing here has a tolerance."""
 import os
 import subprocess
