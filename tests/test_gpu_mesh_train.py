@@ -22,9 +22,7 @@ def gpu_render(tri, cam, views):
     return render_views(tri, views, cam["width"], cam["height"], cam["fx"], cam["fy"], cam["cx"], cam["cy"], mc.LIGHT)
 
 
-def assert_render_equal(got, exp, what):
-    for name, a, b in zip(("rects", "mask", "depth", "gray"), (got[3], got[2], got[1], got[0]), (exp[3], exp[2], exp[1], exp[0])):
-        assert np.array_equal(a, b), (what, name, np.argwhere(a != b)[:5])
+assert_render_equal = mc.assert_render_equal
 
 
 CASES = mc.cases()
