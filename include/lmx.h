@@ -1093,6 +1093,96 @@ lmx_status lmx_pose_chain_on(lmx_depth_templates* templates, const lmx_pose_chai
  * not write keep the caller's bytes (chain_header is zeroed by the call itself). */
 lmx_status lmx_debug_pose_chain(lmx_depth_templates* templates, const lmx_pose_chain_desc* desc);
 
+/* ---- rough pose per cluster: mean view of the largest orientation group, the model rendered again ---------------------------------------
+ * The reference's getRoughPoseByClustering (src/rgbdDetector.cpp:586-865) in front of the two pose stages, where lmx_pose_chain_on takes
+ * the cluster's leader and its stored crop.  Per exported cluster slot: the members are grouped by the orientation of their views (first
+ * fit in member order against the member that created each group; two views are the same when the trace of R_a^T R_b exceeds trace_min
+ * = 1 + 2 cos(threshold), lmx_rough_trace_min); the largest group wins (what std::sort by size leaves first); its views' quaternions,
+ * distances, D and ori_dist and its matches' positions are averaged; the mesh is rendered at that mean view (the arithmetic of
+ * lmx_mesh_render, bit for bit) into the slot's window of the model object; that render, placed with the corner of its silhouette box at
+ * the mean position, is refined and verified as lmx_pose_refine_matches and lmx_pose_verify_matches would a stored crop of the same pixels.
+ * The definition, complete, is the opening comment of csrc/lmx_rough_pose.hpp; the device equals the CPU build of that header bit for
+ * bit.  INTEGRATION.md 3j lists the deviations from the reference.  One mesh and one view table per call: several objects with a
+ * class_base, as lmx_pose_chain_on has it, are deliberately out of scope -- call once per class with class_index.
+ *
+ * The model object holds in device memory the mesh, the view table (views[i] belongs to template_id i of the matches; D and ori_dists:
+ * the side-car's, NULL: zeros) and per slot a view, the rasteriser's state, a work row of n_triangles records (96 bytes each), a depth
+ * window of max_window_h rows of max_window_w pixels (rows padded to 16 bytes) and a crop table entry: lmx_rough_model_device_bytes says
+ * how much.  LMX_ERR_INVALID_ARG: what lmx_mesh_render refuses of a mesh, a camera and views; n_views < 1; a view whose R^T R - I has an
+ * entry beyond 1e-6; a D or ori_dist that is not finite; cap_slots outside 1 .. 2^16; a window side outside 1 .. the camera's.
+ * A model serves the calls of any lmx_depth_templates object of its device, one after the other (each call's stream waits for the previous
+ * call's end on the device); lmx_rough_model_free waits for the device. */
+typedef struct lmx_rough_model lmx_rough_model;
+lmx_status lmx_rough_model_create(int32_t device, const double* triangles /*[n][3][3] m*/, int32_t n_triangles, const lmx_mesh_camera* cam,
+                                  const lmx_mesh_view* views, int32_t n_views, const double* D /*[n_views], NULL ok*/,
+                                  const double* ori_dists /*[n_views], NULL ok*/, int32_t cap_slots, int32_t max_window_w, int32_t max_window_h,
+                                  lmx_rough_model** out);
+void lmx_rough_model_free(lmx_rough_model* model);
+size_t lmx_rough_model_device_bytes(const lmx_rough_model* model);
+/* trace_min = 1 + 2 cos(degrees pi / 180) for an angle inside (0, 180); anything else: LMX_ERR_INVALID_ARG.  A pure host function. */
+lmx_status lmx_rough_trace_min(double degrees, double* trace_min);
+
+enum { LMX_ROUGH_NONE = 0, LMX_ROUGH_OK = 1, LMX_ROUGH_TOO_MANY_GROUPS = 2, LMX_ROUGH_DEGENERATE = 3, LMX_ROUGH_INVALID_VIEW = 4,
+       LMX_ROUGH_WINDOW_TOO_LARGE = 5, LMX_ROUGH_EMPTY = 6 };
+/* R, distance: the mean view, an lmx_mesh_view for lmx_pose_compose.  x, y: the mean match position (truncating integer means).  front:
+ * the index into `matches` of the member that created the winning group; group: its index in creation order.  rect: x, y, w, h of the
+ * render's silhouette box in the model camera; n_model: its covered pixels.  Status: TOO_MANY_GROUPS more than 512 groups (n_members and
+ * n_groups = 512 set, the rest zero); DEGENERATE the quaternion sum has a squared norm of 0 or not finite (R zeros); INVALID_VIEW the mean
+ * view puts a vertex at Z <= 0.01; WINDOW_TOO_LARGE the union of the triangles' boxes exceeds the model's window; EMPTY no pixel is
+ * covered.  rect and n_model are zeros unless the status is OK. */
+typedef struct lmx_rough_pose_t {
+  double R[9], distance, D, ori_dist;
+  int32_t x, y, n_members, n_groups, group, n_group_members, front, center_hole;
+  int32_t rect[4];
+  int32_t n_model, status;
+} lmx_rough_pose_t;
+/* lmx_pose_chain_desc without class_base and n_classes, with trace_min, `rough` in place of `leaders` and member_group, parallel to
+ * `members`: the group (creation order) of every member of a slot whose members passed the index checks, -1 from the member on that
+ * would have created group 513.  refine->rects and verify->rects must be NULL: the rects are the rendered ones.
+ *   Slots, n_live, dead slots and the flags 1, 2 and 4 as lmx_pose_chain_on.  Checked before any value is used as an address, flag 2 and
+ *   an all-zero rough record each: a member outside its frame's matches; a member of another class than the first member's; a template_id
+ *   outside [0, n_views); a mean position beyond +-2^17.  With class_index >= 0 a first member of another class gives an all-zero record
+ *   and no flag.  A slot whose rough status is not LMX_ROUGH_OK gets zeroed pose and verify records and keep 0.
+ *   chain_header[8]: as lmx_pose_chain_on's, plus flag 8 (a slot that passed the checks ended with a rough status other than OK) and
+ *   [5] the slots of status LMX_ROUGH_OK.
+ * Ordering, the resident scene, the pointer and parameter checks are those of lmx_pose_chain_on (rough: 8-byte aligned, member_group: 4).
+ * Refused in addition, with LMX_ERR_INVALID_ARG before anything is queued: a model of another device; cap_clusters above the model's
+ * cap_slots; a model camera whose fx, fy, cx, cy differ from the model_* of either parameter set; a trace_min that is NaN; rects that
+ * are not NULL.  Six kernel launches per call, no host wait. */
+typedef struct lmx_rough_chain_desc {
+  uint32_t struct_size;            /* sizeof(lmx_rough_chain_desc) */
+  int32_t n_frames;
+  int32_t class_index;             /* >= 0: only clusters whose first member has this class; -1: every cluster */
+  int32_t reserved;
+  const lmx_pose_refine_params* refine;
+  const lmx_pose_verify_params* verify;
+  double keep_thresh;
+  double trace_min;                /* lmx_rough_trace_min(threshold in degrees) */
+  const uint32_t* header;          /* [16] */
+  const int32_t* frame_info;       /* [n_frames][8] */
+  const lmx_match_t* matches;
+  size_t cap_matches;
+  const lmx_cluster_t* clusters;
+  size_t cap_clusters;
+  const int32_t* members;
+  size_t cap_members;
+  /* outputs, device memory */
+  uint32_t* chain_header;          /* [8] */
+  lmx_rough_pose_t* rough;         /* [cap_clusters] */
+  int32_t* member_group;           /* [cap_members] */
+  lmx_pose_refine_t* poses;        /* [cap_clusters] */
+  lmx_pose_verify_t* checks;       /* [cap_clusters] */
+  uint8_t* keep;                   /* [cap_clusters] */
+} lmx_rough_chain_desc;
+lmx_status lmx_rough_pose_chain_on(lmx_depth_templates* templates, lmx_rough_model* model, const lmx_rough_chain_desc* desc, void* stream);
+/* Test hook: the same kernels on lists in HOST memory, staged exactly as lmx_debug_pose_chain stages them: the five inputs are uploaded,
+ * the six outputs go to the device as they are and come back as the kernels left them (chain_header is zeroed by the call itself). */
+lmx_status lmx_debug_rough_pose_chain(lmx_depth_templates* templates, lmx_rough_model* model, const lmx_rough_chain_desc* desc);
+/* Test hook: the render the last call left in `slot`, cut to its silhouette box: out [rect[3]][rect[2]] (room for max_window_w *
+ * max_window_h elements), rect = x, y, w, h in the model camera; zeros and nothing written for a slot without a render.  Waits for the
+ * device. */
+lmx_status lmx_debug_rough_crop(lmx_rough_model* model, int32_t slot, uint16_t* out, int32_t rect[4]);
+
 /* ---- introspection (stage-level parity tests, profiling) ------------------------------------------------- */
 enum {
   LMX_DBG_QUANTIZED = 0,     /* u8 [H_l][W_l] one-hot labels after quantize(), A.2/A.4 */

@@ -488,6 +488,16 @@ class DepthTemplates {
     check(lmx_pose_chain_on(h_, &desc, stream));
   }
 
+  // The rough pose stage in front of both (lmx_rough_pose_chain_on): per exported cluster the mean view of its largest orientation group,
+  // the mesh of `model` (lmx_rough_model_create; the caller's to free) rendered again at that view, that render refined and verified.
+  // desc: as poseChain's with rough and member_group in place of leaders and trace_min (lmx_rough_trace_min); the rects of refine and
+  // verify stay NULL.
+  void roughPoseChain(lmx_rough_model* model, lmx_rough_chain_desc desc, void* stream = nullptr, int32_t n_frames = 1) {
+    desc.struct_size = (uint32_t)sizeof(lmx_rough_chain_desc);
+    if (desc.n_frames == 0) desc.n_frames = n_frames;
+    check(lmx_rough_pose_chain_on(h_, model, &desc, stream));
+  }
+
   // The normal term (lmx_depth_templates_enable_normals): computes and keeps the normals of every crop; needed before normals(),
   // normalDiff() and lmx_ctx_collect_clusters_depth_normal.  fx, fy: the focal lengths of the camera whose depth frames are checked.
   void enableNormals(double fx, double fy, int difference_threshold = 50, int distance_threshold = 2000) {

@@ -16,3 +16,4 @@ from .detector import device_images  # noqa: F401
 from .detector import ExportedMatches, export_layout  # noqa: F401
 from .detector import ExportedClusters, export_clusters_layout  # noqa: F401
 from .detector import ExportedPoses, pose_chain_layout  # noqa: F401
+from .detector import RoughModel, ExportedRoughPoses, ROUGH_POSE_DTYPE, rough_pose_layout, rough_trace_min  # noqa: F401

@@ -37,6 +37,8 @@ SYMBOLS = [
     "lmx_pose_refine_matches", "lmx_pose_compose", "lmx_debug_pose_refine_sums",
     "lmx_pose_verify_matches", "lmx_pose_verify_keep",
     "lmx_pose_chain_on", "lmx_debug_pose_chain",
+    "lmx_rough_model_create", "lmx_rough_model_free", "lmx_rough_model_device_bytes", "lmx_rough_trace_min", "lmx_rough_pose_chain_on",
+    "lmx_debug_rough_pose_chain", "lmx_debug_rough_crop",
 ]
 
 (LMX_OK, LMX_ERR_INVALID_ARG, LMX_ERR_SHAPE, LMX_ERR_NO_DEVICE, LMX_ERR_HIP, LMX_ERR_OVERFLOW, LMX_ERR_IO,
@@ -164,6 +166,15 @@ class PoseChainDesc(C.Structure):   # lmx_pose_chain_desc
                 ("header", C.c_void_p), ("frame_info", C.c_void_p), ("matches", C.c_void_p), ("cap_matches", C.c_size_t),
                 ("clusters", C.c_void_p), ("cap_clusters", C.c_size_t), ("members", C.c_void_p), ("cap_members", C.c_size_t),
                 ("chain_header", C.c_void_p), ("leaders", C.c_void_p), ("poses", C.c_void_p), ("checks", C.c_void_p), ("keep", C.c_void_p)]
+
+
+class RoughChainDesc(C.Structure):   # lmx_rough_chain_desc
+    _fields_ = [("struct_size", C.c_uint32), ("n_frames", C.c_int32), ("class_index", C.c_int32), ("reserved", C.c_int32),
+                ("refine", C.POINTER(PoseRefineParams)), ("verify", C.POINTER(PoseVerifyParams)), ("keep_thresh", C.c_double), ("trace_min", C.c_double),
+                ("header", C.c_void_p), ("frame_info", C.c_void_p), ("matches", C.c_void_p), ("cap_matches", C.c_size_t),
+                ("clusters", C.c_void_p), ("cap_clusters", C.c_size_t), ("members", C.c_void_p), ("cap_members", C.c_size_t),
+                ("chain_header", C.c_void_p), ("rough", C.c_void_p), ("member_group", C.c_void_p), ("poses", C.c_void_p), ("checks", C.c_void_p),
+                ("keep", C.c_void_p)]
 
 
 class GroupDesc(C.Structure):
@@ -355,6 +366,16 @@ def lib():
     L.lmx_pose_verify_keep.argtypes = [vp, C.c_size_t, C.c_double, vp]
     L.lmx_pose_chain_on.argtypes = [vp, C.POINTER(PoseChainDesc), vp]
     L.lmx_debug_pose_chain.argtypes = [vp, C.POINTER(PoseChainDesc)]
+    L.lmx_rough_model_create.argtypes = [C.c_int32, vp, C.c_int32, C.POINTER(MeshCamera), C.POINTER(MeshView), C.c_int32, vp, vp, C.c_int32, C.c_int32, C.c_int32,
+                                         C.POINTER(vp)]
+    L.lmx_rough_model_free.argtypes = [vp]
+    L.lmx_rough_model_free.restype = None
+    L.lmx_rough_model_device_bytes.argtypes = [vp]
+    L.lmx_rough_model_device_bytes.restype = C.c_size_t
+    L.lmx_rough_trace_min.argtypes = [C.c_double, C.POINTER(C.c_double)]
+    L.lmx_rough_pose_chain_on.argtypes = [vp, vp, C.POINTER(RoughChainDesc), vp]
+    L.lmx_debug_rough_pose_chain.argtypes = [vp, vp, C.POINTER(RoughChainDesc)]
+    L.lmx_debug_rough_crop.argtypes = [vp, C.c_int32, vp, vp]
     L.lmx_debug_pose_refine_sums.argtypes = [vp, C.POINTER(Image), vp, C.POINTER(PoseRefineParams), vp, vp]
     L.lmx_depth_value.argtypes = [C.POINTER(DepthDiff), C.c_double]
     L.lmx_depth_value.restype = C.c_double

@@ -34,6 +34,8 @@
 // Both stages on the clusters an export left in device memory (lmx_pose_chain_on; the decisions on the lists: lmx_pose_chain.hpp):
 //   k_pose_refine_clusters / k_pose_verify_clusters   one workgroup per cluster slot, the leader and its job found on the device, then the
 //                  bodies of the two kernels above; see the kernels
+// The same two bodies behind the rough pose stage (lmx_rough_pose_chain_on; the stage itself: lmx_rough.hip, lmx_rough_pose.hpp):
+//   k_rough_refine_clusters / k_rough_verify_clusters   one workgroup per cluster slot on the job and the rendered crop the stage left
 // The host half has one launch site for every walk kernel (depth_launch_walk), one body for both match-list paths
 // (diff_selected), one guard in front of every normal-scored call (need_normals) and one body around the launch of both pose stages
 // (pose_call).
@@ -52,6 +54,7 @@
 #include "lmx_pose_chain.hpp"
 #include "lmx_mesh_raster.hpp"
 #include "lmx_export_pack.hpp"
+#include "lmx_rough.hpp"
 
 namespace lmx {
 struct DepthJob { int32_t x, y, template_id, frame; };   // frame: index among the frames uploaded for this call
@@ -668,6 +671,76 @@ __global__ __launch_bounds__(256) void k_pose_verify_clusters(const ChainArgs a,
   const bool pose_ok = refined && pv::check_pose(pose->R, pose->t_mm) == nullptr;
   pv::Record rec = {0.0, 0, 0, 0, 0, 0, pv::NONE, {0, 0, 0, 0}};
   if (pose_ok) pose_verify_body(a.crops, a.T.count, s.template_id, s.frame, s.rect_x, s.rect_y, pose->R, pose->t_mm, a.scene, a.L.n_frames, a.W, a.H, P, &a.checks[k], &rec);
+  else if (tid < (int)(sizeof(lmx_pose_verify_t) / 8)) reinterpret_cast<long long*>(&a.checks[k])[tid] = 0;
+  if (tid == 0) {
+    const bool kept = pv::keep(rec, a.keep_thresh);
+    a.keep[k] = kept ? 1 : 0;
+    if (refined) atomicAdd(&a.chain_header[pc::C_REFINED], 1u);
+    if (refined && !pose_ok) atomicOr(&a.chain_header[pc::C_FLAGS], (uint32_t)pc::FLAG_POSE);
+    if (rec.status == pv::OK) atomicAdd(&a.chain_header[pc::C_VERIFIED], 1u);
+    if (kept) atomicAdd(&a.chain_header[pc::C_KEPT], 1u);
+  }
+}
+
+// ---- both stages behind the rough pose stage (lmx_rough_pose_chain_on; lmx_rough.hip leaves a job and a crop table entry per slot) -------------------
+static_assert(sizeof(rp::CropEntry) == sizeof(DepthCrop) && offsetof(rp::CropEntry, w) == offsetof(DepthCrop, w) && offsetof(rp::CropEntry, pitch) == offsetof(DepthCrop, pitch),
+              "rp::CropEntry is DepthCrop");
+static_assert(sizeof(rp::Record) == sizeof(lmx_rough_pose_t) && offsetof(rp::Record, x) == offsetof(lmx_rough_pose_t, x) &&
+                  offsetof(rp::Record, rect) == offsetof(lmx_rough_pose_t, rect) && offsetof(rp::Record, status) == offsetof(lmx_rough_pose_t, status) &&
+                  alignof(lmx_rough_pose_t) == 8,
+              "rp::Record is lmx_rough_pose_t");
+struct RoughChainArgs {
+  const uint32_t* header;      // the export's
+  uint64_t cap_clusters;
+  const rp::Job* jobs;         // the model's, [cap_slots]
+  const DepthCrop* crops;      // the model's, [cap_slots]: slot k's render is template k
+  int32_t cap_slots;
+  const uint16_t* scene;
+  int32_t n_frames, W, H;
+  uint32_t* chain_header;
+  lmx_pose_refine_t* poses;
+  lmx_pose_verify_t* checks;
+  uint8_t* keep;
+  double keep_thresh;
+};
+
+__device__ __forceinline__ uint32_t rough_live(const RoughChainArgs& a) {
+  const uint32_t n = a.header[xpack::H_CLUSTERS];
+  return (uint64_t)n <= a.cap_clusters ? n : (uint32_t)a.cap_clusters;
+}
+
+// k_pose_refine_clusters' grid and body; the prologue is two loads: k_rough_finish decided the slot and left its job.  The job's fields
+// are told to the compiler as uniform, as uniform_slot does.  253 vector registers, 106 scalar, 592 bytes of scratch per lane (the body's
+// local arrays, as in k_pose_refine: 251, 106, 592), 2 waves per SIMD as k_pose_refine and k_pose_refine_clusters (255, 106, 592).
+// k_rough_verify_clusters: 67 vector registers, 106 scalar, no scratch, 4 waves per SIMD, as k_pose_verify_clusters.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_rough_refine_clusters(const RoughChainArgs a, const pr::Params P) {
+  const uint32_t k = blockIdx.x;
+  if (k >= rough_live(a)) return;
+  const rp::Job* j = a.jobs + k;
+  const int tid = threadIdx.x;
+  if (!__builtin_amdgcn_readfirstlane(j->run)) {
+    if (tid < (int)(sizeof(lmx_pose_refine_t) / 8)) reinterpret_cast<long long*>(&a.poses[k])[tid] = 0;
+    return;
+  }
+  const PoseJob job = {__builtin_amdgcn_readfirstlane(j->x), __builtin_amdgcn_readfirstlane(j->y), (int32_t)k, __builtin_amdgcn_readfirstlane(j->frame),
+                       __builtin_amdgcn_readfirstlane(j->rect_x), __builtin_amdgcn_readfirstlane(j->rect_y), 0, 0};
+  pose_refine_body(a.crops, a.cap_slots, job, a.scene, a.n_frames, a.W, a.H, P, &a.poses[k], nullptr);
+}
+
+// k_pose_verify_clusters behind it, on the same job.
+__global__ __launch_bounds__(256) void k_rough_verify_clusters(const RoughChainArgs a, const pv::Params P) {
+  const uint32_t k = blockIdx.x;
+  if (k >= rough_live(a)) return;
+  const rp::Job* j = a.jobs + k;
+  const int tid = threadIdx.x;
+  const bool run = __builtin_amdgcn_readfirstlane(j->run) != 0;
+  const lmx_pose_refine_t* pose = &a.poses[k];
+  const bool refined = run && pose->status != LMX_POSE_NONE;
+  const bool pose_ok = refined && pv::check_pose(pose->R, pose->t_mm) == nullptr;
+  pv::Record rec = {0.0, 0, 0, 0, 0, 0, pv::NONE, {0, 0, 0, 0}};
+  if (pose_ok)
+    pose_verify_body(a.crops, a.cap_slots, (int32_t)k, __builtin_amdgcn_readfirstlane(j->frame), __builtin_amdgcn_readfirstlane(j->rect_x),
+                     __builtin_amdgcn_readfirstlane(j->rect_y), pose->R, pose->t_mm, a.scene, a.n_frames, a.W, a.H, P, &a.checks[k], &rec);
   else if (tid < (int)(sizeof(lmx_pose_verify_t) / 8)) reinterpret_cast<long long*>(&a.checks[k])[tid] = 0;
   if (tid == 0) {
     const bool kept = pv::keep(rec, a.keep_thresh);
@@ -2060,6 +2133,140 @@ extern "C" lmx_status lmx_debug_pose_chain(lmx_depth_templates* t, const lmx_pos
       for (int k = 5; k < 10; ++k) DV_HIP(hipMemcpyAsync(const_cast<void*>(arr[k].host), arr[k].dev.p, arr[k].bytes, hipMemcpyDeviceToHost, s));
     DV_HIP(hipStreamSynchronize(s));   // the scratch buffers go when this returns
     t->export_read_pending = false;
+    return st;
+  });
+}
+
+// ---- the rough pose stage in front of both stages: the host half (the stage: lmx_rough.hip) ----------------------------------------------------------
+namespace {
+// lmx_pose_chain_on's checks on the fields the two descs share, then the stage's own; t->m and model->m are held.
+lmx_status rough_check(const char* what, lmx_depth_templates* t, lmx_rough_model* model, const lmx_rough_chain_desc* d, lmx::pr::Params* PR, lmx::pv::Params* PV) {
+  using namespace lmx;
+  if (d->struct_size != sizeof(lmx_rough_chain_desc)) { set_error("%s: struct_size %u, not %zu", what, d->struct_size, sizeof(lmx_rough_chain_desc)); return LMX_ERR_INVALID_ARG; }
+  if (!d->rough || !d->member_group) { set_error("%s: rough and member_group must not be null", what); return LMX_ERR_INVALID_ARG; }
+  lmx_pose_chain_desc pd = {};
+  pd.struct_size = sizeof(lmx_pose_chain_desc);
+  pd.n_frames = d->n_frames; pd.class_index = d->class_index; pd.refine = d->refine; pd.verify = d->verify; pd.keep_thresh = d->keep_thresh;
+  pd.header = d->header; pd.frame_info = d->frame_info; pd.matches = d->matches; pd.cap_matches = d->cap_matches; pd.clusters = d->clusters;
+  pd.cap_clusters = d->cap_clusters; pd.members = d->members; pd.cap_members = d->cap_members;
+  pd.chain_header = d->chain_header; pd.leaders = d->member_group; pd.poses = d->poses; pd.checks = d->checks; pd.keep = d->keep;
+  if (lmx_status st = chain_check(what, t, &pd, PR, PV)) return st;
+  if (d->refine->rects || d->verify->rects) { set_error("%s: rects must be NULL: the rects are the rendered ones", what); return LMX_ERR_INVALID_ARG; }
+  if (d->trace_min != d->trace_min) { set_error("%s: trace_min is not a number", what); return LMX_ERR_INVALID_ARG; }
+  if (model->device != t->device) { set_error("%s: the model lives on device %d, the depth templates on device %d", what, model->device, t->device); return LMX_ERR_INVALID_ARG; }
+  if (d->cap_clusters > (size_t)model->cap_slots) { set_error("%s: cap_clusters = %zu exceeds the model's cap_slots = %d", what, d->cap_clusters, model->cap_slots); return LMX_ERR_INVALID_ARG; }
+  const mr::Camera& c = model->cam;
+  const bool same_refine = d->refine->model_fx == c.fx && d->refine->model_fy == c.fy && d->refine->model_cx == c.cx && d->refine->model_cy == c.cy;
+  const bool same_verify = d->verify->model_fx == c.fx && d->verify->model_fy == c.fy && d->verify->model_cx == c.cx && d->verify->model_cy == c.cy;
+  if (!same_refine || !same_verify) {
+    set_error("%s: the model camera of the parameters is not the model's (%g, %g, %g, %g)", what, c.fx, c.fy, c.cx, c.cy);
+    return LMX_ERR_INVALID_ARG;
+  }
+  return LMX_OK;
+}
+
+// As chain_queue: the waits, the stage, the two pose kernels, the records behind them.
+lmx_status rough_queue(lmx_depth_templates* t, lmx_rough_model* model, const lmx_rough_chain_desc& d, const lmx::pr::Params& PR, const lmx::pv::Params& PV, hipStream_t user,
+                       bool with_user) {
+  using namespace lmx;
+  if (lmx_status st = t->ensure_device()) return st;
+  if (!t->export_read) DV_HIP(hipEventCreateWithFlags(&t->export_read, hipEventDisableTiming));
+  if (!t->chain_src_ready) DV_HIP(hipEventCreateWithFlags(&t->chain_src_ready, hipEventDisableTiming));
+  hipStream_t s = t->s;
+  if (with_user) {
+    DV_HIP(hipEventRecord(t->chain_src_ready, user));
+    DV_HIP(hipStreamWaitEvent(s, t->chain_src_ready, 0));
+  }
+  if (t->export_read_pending) DV_HIP(hipStreamWaitEvent(s, t->export_read, 0));
+  DV_HIP(hipStreamWaitEvent(s, t->scene_ready, 0));
+  if (model->done_pending) DV_HIP(hipStreamWaitEvent(s, model->done, 0));   // the model's arena serves one call at a time
+  rp::StageArgs a;
+  a.L = pc::Lists{d.header, d.frame_info, d.n_frames, reinterpret_cast<const pc::Match*>(d.matches), reinterpret_cast<const pc::Cluster*>(d.clusters), d.members,
+                  (uint64_t)d.cap_matches, (uint64_t)d.cap_clusters, (uint64_t)d.cap_members};
+  a.class_index = d.class_index; a.trace_min = d.trace_min; a.chain_header = d.chain_header;
+  a.rough = reinterpret_cast<rp::Record*>(d.rough); a.member_group = d.member_group;
+  DV_HIP(hipMemsetAsync(d.chain_header, 0, pc::C_WORDS * sizeof(uint32_t), s));
+  launch_rough_stage(s, model, a);
+  DV_HIP(hipGetLastError());
+  const RoughChainArgs c = {d.header, (uint64_t)d.cap_clusters, model->d_jobs, reinterpret_cast<const DepthCrop*>(model->d_crops), model->cap_slots, t->d_scene,
+                            d.n_frames, t->scene_W, t->scene_H, d.chain_header, d.poses, d.checks, d.keep, d.keep_thresh};
+  const dim3 grid((unsigned)d.cap_clusters), block(256);
+  hipLaunchKernelGGL(k_rough_refine_clusters, grid, block, 0, s, c, PR);
+  DV_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_rough_verify_clusters, grid, block, 0, s, c, PV);
+  DV_HIP(hipGetLastError());
+  DV_HIP(hipEventRecord(t->export_read, s));
+  t->export_read_pending = true;
+  DV_HIP(hipEventRecord(model->done, s));
+  model->done_pending = true;
+  if (with_user) DV_HIP(hipStreamWaitEvent(user, t->export_read, 0));
+  return LMX_OK;
+}
+}  // namespace
+
+extern "C" lmx_status lmx_rough_pose_chain_on(lmx_depth_templates* t, lmx_rough_model* model, const lmx_rough_chain_desc* d, void* stream) {
+  return lmx::guarded("lmx_rough_pose_chain_on", [&]() -> lmx_status {
+    using namespace lmx;
+    const char* what = "lmx_rough_pose_chain_on";
+    if (!t || !model || !d) { set_error("%s: null argument", what); return LMX_ERR_INVALID_ARG; }
+    std::lock_guard<std::mutex> lk(t->m);
+    std::lock_guard<std::mutex> lkm(model->m);
+    pr::Params PR;
+    pv::Params PV;
+    if (lmx_status st = rough_check(what, t, model, d, &PR, &PV)) return st;
+    if (lmx_status st = t->ensure_device()) return st;
+    hipStream_t user = static_cast<hipStream_t>(stream);
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    if (user && hipStreamIsCapturing(user, &capturing) != hipSuccess) { (void)hipGetLastError(); set_error("%s: invalid stream", what); return LMX_ERR_INVALID_ARG; }
+    if (capturing != hipStreamCaptureStatusNone) { set_error("%s: the stream is being captured into a graph", what); return LMX_ERR_INVALID_ARG; }
+    const struct { const char* name; const void* p; size_t align; } arrays[] = {
+        {"header", d->header, 4}, {"frame_info", d->frame_info, 4}, {"matches", d->matches, 4}, {"clusters", d->clusters, 8}, {"members", d->members, 4},
+        {"chain_header", d->chain_header, 4}, {"rough", d->rough, 8}, {"member_group", d->member_group, 4}, {"poses", d->poses, 8}, {"checks", d->checks, 8},
+        {"keep", d->keep, 1}};
+    for (const auto& arr : arrays)
+      if (lmx_status st = check_chain_memory(what, t, arr.name, arr.p, arr.align)) return st;
+    const lmx_status st = rough_queue(t, model, *d, PR, PV, user, true);
+    if (st != LMX_OK) t->drain_after_error();
+    return st;
+  });
+}
+
+extern "C" lmx_status lmx_debug_rough_pose_chain(lmx_depth_templates* t, lmx_rough_model* model, const lmx_rough_chain_desc* d) {
+  return lmx::guarded("lmx_debug_rough_pose_chain", [&]() -> lmx_status {
+    using namespace lmx;
+    const char* what = "lmx_debug_rough_pose_chain";
+    if (!t || !model || !d) { set_error("%s: null argument", what); return LMX_ERR_INVALID_ARG; }
+    std::lock_guard<std::mutex> lk(t->m);
+    std::lock_guard<std::mutex> lkm(model->m);
+    pr::Params PR;
+    pv::Params PV;
+    if (lmx_status st = rough_check(what, t, model, d, &PR, &PV)) return st;
+    if (d->cap_matches > ((size_t)1 << 24) || d->cap_members > ((size_t)1 << 24)) { set_error("%s: at most 2^24 matches and members", what); return LMX_ERR_INVALID_ARG; }
+    if (lmx_status st = t->ensure_device()) return st;
+    hipStream_t s = t->s;
+    const size_t C = d->cap_clusters;
+    // five inputs (uploaded), six outputs (uploaded and read back; chain_header is zeroed by the call)
+    struct Arr { const void* host; size_t bytes; DeviceBuffer dev; };
+    Arr arr[11] = {{d->header, xpack::H_WORDS * sizeof(uint32_t), {}}, {d->frame_info, (size_t)d->n_frames * xpack::I_WORDS * sizeof(int32_t), {}},
+                   {d->matches, d->cap_matches * sizeof(lmx_match_t), {}}, {d->clusters, C * sizeof(lmx_cluster_t), {}}, {d->members, d->cap_members * sizeof(int32_t), {}},
+                   {d->chain_header, pc::C_WORDS * sizeof(uint32_t), {}}, {d->rough, C * sizeof(lmx_rough_pose_t), {}}, {d->member_group, d->cap_members * sizeof(int32_t), {}},
+                   {d->poses, C * sizeof(lmx_pose_refine_t), {}}, {d->checks, C * sizeof(lmx_pose_verify_t), {}}, {d->keep, C, {}}};
+    for (Arr& x : arr) {
+      DV_HIP(hipMalloc(&x.dev.p, std::max<size_t>(x.bytes, 16)));
+      if (x.bytes) DV_HIP(hipMemcpyAsync(x.dev.p, x.host, x.bytes, hipMemcpyHostToDevice, s));
+    }
+    lmx_rough_chain_desc dd = *d;
+    dd.header = arr[0].dev.as<uint32_t>(); dd.frame_info = arr[1].dev.as<int32_t>(); dd.matches = arr[2].dev.as<lmx_match_t>();
+    dd.clusters = arr[3].dev.as<lmx_cluster_t>(); dd.members = arr[4].dev.as<int32_t>(); dd.chain_header = arr[5].dev.as<uint32_t>();
+    dd.rough = arr[6].dev.as<lmx_rough_pose_t>(); dd.member_group = arr[7].dev.as<int32_t>(); dd.poses = arr[8].dev.as<lmx_pose_refine_t>();
+    dd.checks = arr[9].dev.as<lmx_pose_verify_t>(); dd.keep = arr[10].dev.as<uint8_t>();
+    lmx_status st = rough_queue(t, model, dd, PR, PV, nullptr, false);
+    if (st == LMX_OK)
+      for (int k = 5; k < 11; ++k)
+        if (arr[k].bytes) DV_HIP(hipMemcpyAsync(const_cast<void*>(arr[k].host), arr[k].dev.p, arr[k].bytes, hipMemcpyDeviceToHost, s));
+    DV_HIP(hipStreamSynchronize(s));   // the scratch buffers go when this returns
+    t->export_read_pending = false;
+    model->done_pending = false;
     return st;
   });
 }

@@ -353,6 +353,73 @@ class ExportedPoses:
                 np.ascontiguousarray(self.checks[:n].cpu().numpy()).view(POSE_VERIFY_DTYPE).reshape(-1), self.keep[:n].cpu().numpy().astype(bool))
 
 
+# lmx_rough_pose_t; status: the LMX_ROUGH_* values
+ROUGH_POSE_DTYPE = np.dtype([("R", "<f8", (9,)), ("distance", "<f8"), ("D", "<f8"), ("ori_dist", "<f8"), ("x", "<i4"), ("y", "<i4"), ("n_members", "<i4"),
+                             ("n_groups", "<i4"), ("group", "<i4"), ("n_group_members", "<i4"), ("front", "<i4"), ("center_hole", "<i4"), ("rect", "<i4", (4,)),
+                             ("n_model", "<i4"), ("status", "<i4")])
+ROUGH_NONE, ROUGH_OK, ROUGH_TOO_MANY_GROUPS, ROUGH_DEGENERATE, ROUGH_INVALID_VIEW, ROUGH_WINDOW_TOO_LARGE, ROUGH_EMPTY = range(7)
+POSE_CHAIN_FLAG_ROUGH = 8          # chain_header[1] of lmx_rough_pose_chain_on: a slot ended with a rough status other than ROUGH_OK
+
+
+def rough_trace_min(threshold_deg):
+    """lmx_rough_trace_min: 1 + 2 cos(threshold) for a threshold inside (0, 180) degrees, what rough_pose_chain compares the trace of
+    R_a^T R_b with."""
+    out = C.c_double()
+    _lib.check(_lib.lib().lmx_rough_trace_min(float(threshold_deg), C.byref(out)))
+    return out.value
+
+
+def rough_pose_layout(cap_clusters, cap_members):
+    """The device arrays lmx_rough_pose_chain_on fills, as DepthTemplates.rough_pose_chain allocates them: pose_chain_layout's with `rough`
+    in place of `leaders`, and member_group parallel to the export's members."""
+    lay = pose_chain_layout(cap_clusters)
+    cap, n_mem = lay["leaders"]["cap"], max(int(cap_members), 1)
+    del lay["leaders"]
+    lay["rough"] = {"shape": (cap, ROUGH_POSE_DTYPE.itemsize // 8), "dtype": "int64", "nbytes": cap * ROUGH_POSE_DTYPE.itemsize, "align": 8, "cap": cap}
+    lay["member_group"] = {"shape": (n_mem,), "dtype": "int32", "nbytes": n_mem * 4, "align": 4, "cap": n_mem}
+    return lay
+
+
+class ExportedRoughPoses:
+    """What DepthTemplates.rough_pose_chain leaves on the GPU (lmx_rough_pose_chain_on): as ExportedPoses, with
+      chain_header  int32 [8]       [0] n_live, [1] flags, [2] slots refined, [3] verified OK, [4] kept, [5] slots of status ROUGH_OK
+      rough         int64 [cap, 19] lmx_rough_pose_t records (ROUGH_POSE_DTYPE)
+      member_group  int32 [cap_members]  the orientation group of every member, parallel to the export's members
+    in place of leaders."""
+    NAMES = ("chain_header", "rough", "member_group", "poses", "checks", "keep")
+
+    def __init__(self, cap_clusters, cap_members, stream, device):
+        import torch
+        self.stream = stream
+        lay = rough_pose_layout(cap_clusters, cap_members)
+        with torch.cuda.stream(stream):
+            t = {k: torch.empty(v["shape"], dtype=getattr(torch, v["dtype"]), device="cuda:%d" % device) for k, v in lay.items()}
+        self._backing = t
+        self.cap, self.cap_members = lay["rough"]["cap"], lay["member_group"]["cap"]
+        self.chain_header, self.rough, self.member_group, self.poses, self.checks, self.keep = (t[k] for k in self.NAMES)
+
+    def clone(self):
+        """A copy made on `stream`, as ExportedPoses.clone."""
+        import torch
+        out = ExportedRoughPoses.__new__(ExportedRoughPoses)
+        out.stream, out.cap, out.cap_members = self.stream, self.cap, self.cap_members
+        with torch.cuda.stream(self.stream):
+            out._backing = {k: v.clone() for k, v in self._backing.items()}
+        t = out._backing
+        out.chain_header, out.rough, out.member_group, out.poses, out.checks, out.keep = (t[k] for k in self.NAMES)
+        return out
+
+    def to_host(self):
+        """Synchronises `stream` -> (chain_header int64 [8], rough ROUGH_POSE_DTYPE [n_live], member_group int32 [cap_members], poses
+        POSE_REFINE_DTYPE [n_live], checks POSE_VERIFY_DTYPE [n_live], keep bool [n_live])."""
+        self.stream.synchronize()
+        hdr = self.chain_header.cpu().numpy().view(np.uint32).astype(np.int64)
+        n = min(int(hdr[0]), self.cap)
+        return (hdr, np.ascontiguousarray(self.rough[:n].cpu().numpy()).view(ROUGH_POSE_DTYPE).reshape(-1), self.member_group.cpu().numpy(),
+                np.ascontiguousarray(self.poses[:n].cpu().numpy()).view(POSE_REFINE_DTYPE).reshape(-1),
+                np.ascontiguousarray(self.checks[:n].cpu().numpy()).view(POSE_VERIFY_DTYPE).reshape(-1), self.keep[:n].cpu().numpy().astype(bool))
+
+
 class PreparedBatch:
     """lmx_image descriptors of a batch of host frames, built once (the arrays are kept alive by this object)."""
 
@@ -1600,6 +1667,85 @@ class DepthTemplates:
         del alive
         return hdr, leaders, poses, checks, keep
 
+    def _rough_chain_desc(self, model, n_frames, keep_thresh, threshold_deg, trace_min, class_index, model_camera, scene_camera, max_dist_mm, max_iterations,
+                          min_pairs, search_radius, eps_rot_rad, eps_trans_mm, voxel_mm, roi_margin):
+        """The parameters of rough_pose_chain / debug_rough_pose_chain -> (RoughChainDesc without its arrays, what it points to)."""
+        if model_camera is None:
+            model_camera = model.camera
+        if scene_camera is None:
+            raise ValueError("scene_camera is (fx, fy, cx, cy)")
+        pr, _ = self._pose_params(model_camera, scene_camera, max_dist_mm, max_iterations, min_pairs, search_radius, eps_rot_rad, eps_trans_mm, None)
+        pv = _lib.PoseVerifyParams(C.sizeof(_lib.PoseVerifyParams), *[float(v) for v in tuple(model_camera) + tuple(scene_camera)], float(voxel_mm), int(roi_margin), None)
+        d = _lib.RoughChainDesc()
+        d.struct_size, d.n_frames, d.class_index = C.sizeof(_lib.RoughChainDesc), int(n_frames), int(class_index)
+        d.refine, d.verify, d.keep_thresh = C.pointer(pr), C.pointer(pv), float(keep_thresh)
+        d.trace_min = float(trace_min) if trace_min is not None else rough_trace_min(threshold_deg)
+        return d, (pr, pv)
+
+    def rough_pose_chain(self, exported, model, keep_thresh, threshold_deg=10.0, scene_camera=None, model_camera=None, max_dist_mm=10.0, max_iterations=20, min_pairs=16,
+                         search_radius=1, eps_rot_rad=1e-5, eps_trans_mm=1e-3, voxel_mm=4.0, roi_margin=8, class_index=-1, trace_min=None, stream=None, out=None):
+        """The reference's getRoughPoseByClustering in front of both pose stages, on the clusters an export left on the GPU
+        (lmx_rough_pose_chain_on) -> ExportedRoughPoses: per exported cluster the mean view of its largest orientation group (views closer
+        than threshold_deg to the member that opened the group), the mesh of `model` (a RoughModel whose views are indexed by the matches'
+        template_id) rendered again at that view, that render refined and verified against the resident scene at the mean match
+        position, and the keep decision -- with no host wait in between.  model_camera: default the model's.  trace_min: in place of
+        threshold_deg, the bound itself.  The other keywords as pose_chain; rects are the rendered ones."""
+        import torch
+        if getattr(exported, "clusters", None) is None or exported.members is None:
+            raise ValueError("exported holds no clusters (export_matches(clusters=True) or export_clusters)")
+        device = exported.header.device.index
+        if stream is None:
+            stream = exported.stream
+        elif not hasattr(stream, "cuda_stream"):
+            stream = torch.cuda.ExternalStream(int(stream), device=device)
+        caps = exported.caps
+        if caps[1] < 1:
+            raise ValueError("the export has no room for clusters")
+        if out is None:
+            out = ExportedRoughPoses(caps[1], caps[2], stream, device)
+        else:
+            if out.cap < caps[1] or out.cap_members < caps[2]:
+                raise ValueError("out was made for %d clusters and %d members, the export holds up to %d and %d" % (out.cap, out.cap_members, caps[1], caps[2]))
+            out.stream = stream
+        d, alive = self._rough_chain_desc(model, exported.n_frames, keep_thresh, threshold_deg, trace_min, class_index, model_camera, scene_camera, max_dist_mm,
+                                          max_iterations, min_pairs, search_radius, eps_rot_rad, eps_trans_mm, voxel_mm, roi_margin)
+        b = exported._backing
+        d.header, d.frame_info, d.matches, d.cap_matches = b["header"].data_ptr(), b["frame_info"].data_ptr(), b["matches"].data_ptr(), caps[0]
+        d.clusters, d.cap_clusters, d.members, d.cap_members = b["clusters"].data_ptr(), caps[1], b["members"].data_ptr(), caps[2]
+        t = out._backing
+        d.chain_header, d.rough, d.member_group, d.poses, d.checks, d.keep = (t[k].data_ptr() for k in ExportedRoughPoses.NAMES)
+        _lib.check(_lib.lib().lmx_rough_pose_chain_on(self.h, model.h, C.byref(d), int(stream.cuda_stream)))
+        del alive
+        return out
+
+    def debug_rough_pose_chain(self, model, header, frame_info, matches, clusters, members, keep_thresh, threshold_deg=10.0, cap_clusters=None, fill=0, class_index=-1,
+                               trace_min=None, scene_camera=None, model_camera=None, max_dist_mm=10.0, max_iterations=20, min_pairs=16, search_radius=1,
+                               eps_rot_rad=1e-5, eps_trans_mm=1e-3, voxel_mm=4.0, roi_margin=8):
+        """Test hook (lmx_debug_rough_pose_chain): rough_pose_chain's kernels on lists in host memory, as debug_pose_chain takes them ->
+        (chain_header uint32 [8], rough ROUGH_POSE_DTYPE, member_group int32 [len(members)], poses, checks, keep), holding the byte `fill`
+        wherever the kernels wrote nothing."""
+        header = np.ascontiguousarray(header).astype(np.uint32).reshape(16)
+        frame_info = np.ascontiguousarray(frame_info, np.int32).reshape(-1, 8)
+        matches = np.ascontiguousarray(matches, MATCH_DTYPE)
+        clusters = np.ascontiguousarray(clusters, CLUSTER_DTYPE)
+        members = np.ascontiguousarray(members, np.int32)
+        n = len(clusters)
+        hdr = np.zeros(POSE_CHAIN_HEADER_WORDS, np.uint32)
+        rough, group = np.zeros(n, ROUGH_POSE_DTYPE), np.zeros(max(len(members), 1), np.int32)
+        poses, checks, keep = np.zeros(n, POSE_REFINE_DTYPE), np.zeros(n, POSE_VERIFY_DTYPE), np.zeros(n, np.uint8)
+        for a in (rough, group, poses, checks, keep):
+            a.view(np.uint8)[:] = fill
+        d, alive = self._rough_chain_desc(model, len(frame_info), keep_thresh, threshold_deg, trace_min, class_index, model_camera, scene_camera, max_dist_mm,
+                                          max_iterations, min_pairs, search_radius, eps_rot_rad, eps_trans_mm, voxel_mm, roi_margin)
+        d.header, d.frame_info, d.matches, d.cap_matches = header.ctypes.data, frame_info.ctypes.data, matches.ctypes.data, len(matches)
+        d.clusters, d.cap_clusters, d.members, d.cap_members = clusters.ctypes.data, n if cap_clusters is None else int(cap_clusters), members.ctypes.data, len(members)
+        if d.cap_clusters > n:
+            raise ValueError("cap_clusters exceeds len(clusters)")
+        d.chain_header, d.rough, d.member_group, d.poses, d.checks, d.keep = (a.ctypes.data for a in (hdr, rough, group, poses, checks, keep))
+        _lib.check(_lib.lib().lmx_debug_rough_pose_chain(self.h, model.h, C.byref(d)))
+        del alive
+        return hdr, rough, group[:len(members)], poses, checks, keep
+
     def debug_pose_refine_sums(self, depth_frame, match, **params):
         """Test hook (lmx_debug_pose_refine_sums): one match against one host frame -> (its POSE_REFINE_DTYPE record, int64
         [max_iterations + 1, 17]: the integer sums of every pass the device ran)."""
@@ -1692,6 +1838,53 @@ class DepthTemplates:
     def close(self):
         if getattr(self, "h", None):
             _lib.lib().lmx_depth_templates_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class RoughModel:
+    """The mesh, the view table and the per-slot render arena of DepthTemplates.rough_pose_chain (lmx_rough_model): views[i] = (R [3, 3],
+    distance in metres) belongs to template_id i of the matches -- for a bank from NativeBank.train_mesh, zip(last_side_car["R"],
+    last_side_car["T"][:, 2]); D and ori_dists: the side-car's, per view.  cap_slots: the most cluster slots a call may hold;
+    max_window: (w, h) of the largest render (the union of the triangles' pixel boxes) a slot can take."""
+
+    def __init__(self, triangles, views, width, height, fx, fy, cx=None, cy=None, D=None, ori_dists=None, cap_slots=4096, max_window=None, light=MESH_LIGHT,
+                 device=0):
+        views = list(views)
+        tri, cam, packed = _mesh_args(triangles, views, width, height, fx, fy, cx, cy, light)
+        side = []
+        for a in (D, ori_dists):
+            a = None if a is None else np.ascontiguousarray(a, np.float64).reshape(-1)
+            if a is not None and len(a) != len(views):
+                raise ValueError("D and ori_dists hold one value per view")
+            side.append(a)
+        w, h = (width, height) if max_window is None else max_window
+        self.h = C.c_void_p()
+        _lib.check(_lib.lib().lmx_rough_model_create(device, tri.ctypes.data, tri.shape[0], C.byref(cam), packed.ctypes.data_as(C.POINTER(_lib.MeshView)), len(views),
+                                                     side[0].ctypes.data if side[0] is not None else None, side[1].ctypes.data if side[1] is not None else None,
+                                                     int(cap_slots), int(w), int(h), C.byref(self.h)))
+        self.camera = (cam.fx, cam.fy, cam.cx, cam.cy)
+        self.cap_slots, self.max_window, self.n_views = int(cap_slots), (int(w), int(h)), len(views)
+
+    def device_bytes(self):
+        return int(_lib.lib().lmx_rough_model_device_bytes(self.h))
+
+    def debug_crop(self, slot):
+        """Test hook (lmx_debug_rough_crop): the render the last call left in `slot`, cut to its silhouette box -> (uint16 [h, w], rect
+        (x, y, w, h) in the model camera); ([0, 0], zeros) for a slot without a render."""
+        buf = np.zeros(self.max_window[0] * self.max_window[1], np.uint16)
+        rect = np.zeros(4, np.int32)
+        _lib.check(_lib.lib().lmx_debug_rough_crop(self.h, int(slot), buf.ctypes.data, rect.ctypes.data))
+        return buf[:rect[2] * rect[3]].reshape(rect[3], rect[2]).copy(), rect
+
+    def close(self):
+        if getattr(self, "h", None):
+            _lib.lib().lmx_rough_model_free(self.h)
             self.h = None
 
     def __del__(self):
