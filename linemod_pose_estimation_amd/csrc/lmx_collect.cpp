@@ -738,9 +738,7 @@ static lmx_status export_impl(const char* what, lmx_ctx* c, int32_t n_frames, co
   }
   LMX_HIP(hipSetDevice(c->device));
   hipStream_t user = static_cast<hipStream_t>(stream);
-  hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-  if (user && hipStreamIsCapturing(user, &capturing) != hipSuccess) { (void)hipGetLastError(); set_error("%s: invalid stream", what); return LMX_ERR_INVALID_ARG; }
-  if (capturing != hipStreamCaptureStatusNone) { set_error("%s: the stream is being captured into a graph", what); return LMX_ERR_INVALID_ARG; }
+  if (lmx_status st = check_user_stream(what, user)) return st;
   if (lmx_status st = check_export_output(what, c, "header", q.header, 4)) return st;
   if (lmx_status st = check_export_output(what, c, "frame_info", q.frame_info, 4)) return st;
   if (lmx_status st = check_export_output(what, c, "matches", q.matches, 4)) return st;

@@ -728,6 +728,13 @@ lmx_status ctx_drop_newest(lmx_ctx* c) {
   return LMX_OK;
 }
 
+lmx_status check_user_stream(const char* what, hipStream_t user) {
+  hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+  if (user && hipStreamIsCapturing(user, &capturing) != hipSuccess) { (void)hipGetLastError(); set_error("%s: invalid stream", what); return LMX_ERR_INVALID_ARG; }
+  if (capturing != hipStreamCaptureStatusNone) { set_error("%s: the stream is being captured into a graph", what); return LMX_ERR_INVALID_ARG; }
+  return LMX_OK;
+}
+
 }  // namespace lmx
 
 // What lmx_ctx_upload_raw and lmx_ctx_upload_device take with a lmx_pre_desc.  -> per modality: the element layout of the raw source and
@@ -889,9 +896,7 @@ lmx_status lmx_ctx_upload_device(lmx_ctx* c, int32_t n_frames, const lmx_image* 
         return LMX_ERR_INVALID_ARG;
       }
     }
-  hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-  if (user && hipStreamIsCapturing(user, &capturing) != hipSuccess) { (void)hipGetLastError(); set_error("lmx_ctx_upload_device: invalid stream"); return LMX_ERR_INVALID_ARG; }
-  if (capturing != hipStreamCaptureStatusNone) { set_error("lmx_ctx_upload_device: the stream is being captured into a graph"); return LMX_ERR_INVALID_ARG; }
+  if (lmx_status st = check_user_stream("lmx_ctx_upload_device", user)) return st;
   // next frame set: the only host wait is for the set's previous upload (whose kernel read this table); the lanes that still read the set's
   // frames are waited for on the copy stream, and the ingest stream behind it
   const int set = (c->cur_set + 1) % c->n_sets;

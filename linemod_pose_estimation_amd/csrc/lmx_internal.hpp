@@ -174,6 +174,37 @@ inline lmx_status guarded(const char* what, F&& body) noexcept {
   }
 }
 
+// A HIP call of an entry point that holds nothing a return would leak: the error text, then LMX_ERR_NO_DEVICE or LMX_ERR_HIP.
+#define HIP_RETURN(expr)                                                                           \
+  do {                                                                                             \
+    hipError_t e_ = (expr);                                                                        \
+    if (e_ != hipSuccess) {                                                                        \
+      lmx::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);    \
+      return e_ == hipErrorNoDevice ? LMX_ERR_NO_DEVICE : LMX_ERR_HIP;                             \
+    }                                                                                              \
+  } while (0)
+
+// The caller's stream of an entry point that orders its work against it (lmx_ctx.cpp): refused when it is no stream, and while it is
+// being captured into a graph (the calls record and wait for events of their own streams).  Null is the default stream.
+lmx_status check_user_stream(const char* what, hipStream_t user);
+
+#if defined(__HIPCC__)
+// Reductions over the wave's 64 lanes: lane 0 gets the result (the others partial ones; __shfl(.., 0, 64) tells every lane).
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  return v;
+}
+__device__ __forceinline__ int wave_min(int v) {
+  for (int off = 32; off > 0; off >>= 1) { const int o = __shfl_down(v, off, 64); v = o < v ? o : v; }
+  return v;
+}
+__device__ __forceinline__ int wave_max(int v) {
+  for (int off = 32; off > 0; off >>= 1) { const int o = __shfl_down(v, off, 64); v = o > v ? o : v; }
+  return v;
+}
+#endif
+
 struct DeviceBankView {
   int32_t G;                        // templates in this shard
   int32_t L, M;
@@ -487,6 +518,7 @@ constexpr int MS_INVALID = 0;        // a vertex at Z <= 0.01: the view is inval
 constexpr int MS_UNION = 1;          // union of the triangles' clamped boxes {x0, y0, x1, y1}: tiles outside it only write zeros
 constexpr int MS_LEVEL = 5;          // [kMaxLevels] silhouette boxes {xmin, ymin, xmax, ymax} of the mask at pyramid level l (xmax = -1: empty)
 constexpr int MS_CENTRE_DEPTH = 21;  // depth_mm[H / 2][W / 2] (the side-car's D)
+constexpr int MS_COUNT = 22;         // the covered pixels of the render (k_rough_raster alone counts them)
 // The window of a level the trainer's host half looks at: the silhouette box grown by 2, clamped (train_add_template derives the same on
 // the host); an empty mask gives a 4x4 corner, which shows "no candidates" like any other window.
 __host__ __device__ inline void mesh_window(const int32_t* box, int w, int h, int* x0, int* y0, int* ww, int* wh) {

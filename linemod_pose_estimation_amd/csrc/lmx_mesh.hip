@@ -13,55 +13,26 @@
 //                  sub-samplings of the mask) are min/max reductions: LDS atomics, then one global atomic set per workgroup.
 //   k_mesh_pack    per (view, level): copies the window the trainer's host half looks at (silhouette box grown by 2) of labels, magnitudes
 //                  and mask into the view's slot of a pinned host buffer.
-// No workgroup waits for another; every dependency is a kernel boundary on one stream.
+// No workgroup waits for another; every dependency is a kernel boundary on one stream.  The set-up body and the tile walk are
+// lmx_mesh_device.hpp's mesh_setup and mesh_tile_walk, which lmx_rough.hip runs per cluster slot.
 #include <cmath>
 #include <cstring>
 
-#include "lmx_internal.hpp"
-#include "lmx_mesh_raster.hpp"
+#include "lmx_mesh_device.hpp"
 
 namespace lmx {
 namespace {
 
-constexpr int MR_TW = 32, MR_TH = 8;   // tile of k_mesh_raster: 256 lanes, a wave = two rows of 32 pixels
-constexpr int MR_BIG = 0x7fffffff;
-
 __global__ __launch_bounds__(64) void k_mesh_init(int32_t* __restrict__ state, int n_views) {
   const int v = blockIdx.x, i = threadIdx.x;
   if (v >= n_views || i >= kMeshStateWords) return;
-  int32_t x = 0;
-  if (i >= MS_UNION && i < MS_LEVEL + 4 * kMaxLevels) x = ((i - MS_UNION) & 2) ? -1 : MR_BIG;   // {min, min, max, max}
-  state[(size_t)v * kMeshStateWords + i] = x;
+  state[(size_t)v * kMeshStateWords + i] = mesh_state_clear(i, 4 + 4 * kMaxLevels);   // the union box and every level's
 }
 
 __global__ __launch_bounds__(256) void k_mesh_setup(const double* __restrict__ tri, int n_tri, mr::Camera cam, const double* __restrict__ views,
                                                     mr::Tri* __restrict__ work, int32_t* __restrict__ state) {
-  __shared__ int s_box[4], s_bad;
   const int v = blockIdx.y, t = blockIdx.x * 256 + threadIdx.x;
-  if (threadIdx.x == 0) { s_box[0] = s_box[1] = MR_BIG; s_box[2] = s_box[3] = -1; s_bad = 0; }
-  __syncthreads();
-  if (t < n_tri) {
-    const double* vw = views + (size_t)v * 10;
-    double R[9];
-    for (int k = 0; k < 9; ++k) R[k] = vw[k];
-    mr::Tri rec;
-    const int rc = mr::setup_triangle(tri + (size_t)t * 9, R, vw[9], cam, rec);
-    if (rc != mr::TRI_OK) { rec = mr::Tri(); rec.x0 = 0; rec.x1 = -1; rec.y0 = 0; rec.y1 = -1; }   // an empty box: no pixel ever tests it
-    if (rc == mr::TRI_INVALID_VIEW) atomicOr(&s_bad, 1);
-    work[(size_t)v * n_tri + t] = rec;
-    if (rc == mr::TRI_OK && rec.x0 <= rec.x1 && rec.y0 <= rec.y1) {
-      atomicMin(&s_box[0], rec.x0); atomicMin(&s_box[1], rec.y0); atomicMax(&s_box[2], rec.x1); atomicMax(&s_box[3], rec.y1);
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int32_t* st = state + (size_t)v * kMeshStateWords;
-    if (s_bad) atomicOr(&st[MS_INVALID], 1);
-    if (s_box[2] >= 0) {
-      atomicMin(&st[MS_UNION + 0], s_box[0]); atomicMin(&st[MS_UNION + 1], s_box[1]);
-      atomicMax(&st[MS_UNION + 2], s_box[2]); atomicMax(&st[MS_UNION + 3], s_box[3]);
-    }
-  }
+  mesh_setup(tri, n_tri, cam, views + (size_t)v * 10, work + (size_t)v * n_tri, state + (size_t)v * kMeshStateWords, t);
 }
 
 __global__ __launch_bounds__(256) void k_mesh_raster(const mr::Tri* __restrict__ work, int n_tri, int W, int H, int n_levels, int32_t* __restrict__ state,
@@ -87,41 +58,11 @@ __global__ __launch_bounds__(256) void k_mesh_raster(const mr::Tri* __restrict__
     return;
   }
   if (tid < 4 * kMaxLevels) s_lbox[tid >> 2][tid & 3] = (tid & 2) ? -1 : MR_BIG;
-  double best_z = INFINITY, best_iz = -INFINITY;
-  int best_gray = 0;
-  const mr::Tri* vw = work + (size_t)v * n_tri;
-  const int lane = tid & 63, wave = tid >> 6;
-  for (int base = 0; base < n_tri; base += 256) {
-    const int t = base + tid;
-    bool hit = false;
-    if (t < n_tri) {
-      const int4 b = *reinterpret_cast<const int4*>(&vw[t].x0);   // x0, x1, y0, y1
-      hit = b.x <= tx1 && b.y >= tx0 && b.z <= ty1 && b.w >= ty0 && b.x <= b.y && b.z <= b.w;
-    }
-    const unsigned long long bal = __ballot(hit);
-    if (lane == 0) s_wave[wave] = __popcll(bal);
-    __syncthreads();   // also: the previous chunk's records have been read by every lane
-    int slot = __popcll(bal & ((1ull << lane) - 1ull));
-    int n_hit = 0;
-    for (int w = 0; w < 4; ++w) { const int c = s_wave[w]; if (w < wave) slot += c; n_hit += c; }
-    if (hit) s_tri[slot] = vw[t];
-    __syncthreads();
-    if (inside) {
-      for (int k = 0; k < n_hit; ++k) {
-        const mr::Tri& tr = s_tri[k];
-        double iz;
-        if (!mr::in_box(tr, x, y) || !mr::cover(tr, x, y, &iz)) continue;
-        // z = 1 / iz does not increase with iz: a triangle whose iz is not above the winner's cannot have a smaller z (the division is skipped)
-        if (!(iz > best_iz)) continue;
-        const double z = 1.0 / iz;
-        if (z < best_z) { best_z = z; best_iz = iz; best_gray = tr.gray; }
-      }
-    }
-  }
-  const bool cov = inside && best_z < INFINITY;
+  const MeshBest best = mesh_tile_walk<true>(work + (size_t)v * n_tri, n_tri, tx0, ty0, tx1, ty1, x, y, inside, s_tri, s_wave);
+  const bool cov = inside && best.z < INFINITY;
   if (inside) {
-    const uint16_t dmm = cov ? mr::depth_mm(best_z) : (uint16_t)0;
-    if (gray) gray[o] = cov ? (uint8_t)best_gray : (uint8_t)0;
+    const uint16_t dmm = cov ? mr::depth_mm(best.z) : (uint16_t)0;
+    if (gray) gray[o] = cov ? (uint8_t)best.gray : (uint8_t)0;
     if (depth) depth[o] = dmm;
     if (mask) mask[o] = cov ? 255 : 0;
     if (cov && x == W / 2 && y == H / 2) st[MS_CENTRE_DEPTH] = dmm;

@@ -80,10 +80,11 @@ struct Slot {
 };
 struct Frame { int32_t frame, match_begin, match_count; };
 
-LMX_PC_FN uint32_t n_live(const Lists& L) {
-  const uint32_t n = L.header[xpack::H_CLUSTERS];
-  return (uint64_t)n <= L.cap_clusters ? n : (uint32_t)L.cap_clusters;   // cap_clusters <= kMaxClusters
+LMX_PC_FN uint32_t n_live(const uint32_t* header, uint64_t cap_clusters) {
+  const uint32_t n = header[xpack::H_CLUSTERS];
+  return (uint64_t)n <= cap_clusters ? n : (uint32_t)cap_clusters;   // cap_clusters <= kMaxClusters
 }
+LMX_PC_FN uint32_t n_live(const Lists& L) { return n_live(L.header, L.cap_clusters); }
 
 // What block 0 reports whatever the slots say: the list overflowed, or clusters lie beyond cap_clusters.
 LMX_PC_FN uint32_t header_flags(const Lists& L) {

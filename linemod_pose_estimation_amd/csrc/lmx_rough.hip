@@ -11,8 +11,9 @@
 //                   alike from shuffles.  Lane 0 stores the record, the slot's view (the 10 doubles the setup reads) and its job; lanes
 //                   0..31 clear the slot's rasteriser state.  66 vector registers, 78 scalar, 46.5 KiB LDS (the fronts: 36 KiB), 1024 bytes of scratch
 //                   per lane: the emulated sort's explicit stack, which lane 0 alone touches.
-//   k_rough_setup   k_mesh_setup's body per (slot, triangle) for the slots that have a view.  44 vector registers, 62 scalar, no scratch.
-//   k_rough_raster  k_mesh_raster's walk per (slot, 32x8 tile of the slot's WINDOW): the window is the union box the setup folded, stored at
+//   k_rough_setup   k_mesh_setup's body (lmx_mesh_device.hpp: mesh_setup, the one both kernels call) per (slot, triangle) for the slots
+//                   that have a view.  44 vector registers, 62 scalar, no scratch.
+//   k_rough_raster  k_mesh_raster's walk (mesh_tile_walk, without the gray) per (slot, 32x8 tile of the slot's WINDOW): the window is the union box the setup folded, stored at
 //                   the slot's place in the arena with rows of crop_pitch(width) -- a 640x480 frame per slot would be 2.5 GB for 4096 slots.
 //                   Tiles beyond the window leave at once.  Silhouette box and pixel count: LDS atomics, one global atomic set per
 //                   workgroup.  53 vector registers, 54 scalar, no scratch, 24.0 KiB LDS.
@@ -25,12 +26,10 @@
 
 #include "lmx_rough.hpp"
 #include "lmx_depth_verify.hpp"
+#include "lmx_mesh_device.hpp"
 
 namespace lmx {
 namespace {
-
-constexpr int RT_W = 32, RT_H = 8;
-constexpr int R_BIG = 0x7fffffff;
 
 struct GroupArgs {
   rp::StageArgs a;
@@ -40,15 +39,6 @@ struct GroupArgs {
   int32_t* state;
   rp::Job* jobs;
 };
-
-__device__ __forceinline__ int wave_sum_i(int v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return __shfl(v, 0, 64);
-}
-__device__ __forceinline__ int wave_min_i(int v) {
-  for (int off = 32; off > 0; off >>= 1) { const int o = __shfl_down(v, off, 64); v = o < v ? o : v; }
-  return __shfl(v, 0, 64);
-}
 
 __global__ __launch_bounds__(64) void k_rough_group(const GroupArgs g) {
   __shared__ double s_front[9][rp::kMaxGroups];
@@ -67,8 +57,8 @@ __global__ __launch_bounds__(64) void k_rough_group(const GroupArgs g) {
   int32_t claims = 0, first = INT32_MAX;
   for (int32_t f = lane; f < L.n_frames; f += 64)
     if (pc::frame_claims(L, f, k)) { claims += 1; first = f < first ? f : first; }
-  claims = wave_sum_i(claims);
-  first = wave_min_i(first);
+  claims = __shfl(wave_sum(claims), 0, 64);
+  first = __shfl(wave_min(first), 0, 64);
   // the branches depend on k and on device memory alone: the wave stays together
   rp::Slot s = rp::slot_from_claims(L, g.a.class_index, k, claims, first, [&](const pc::Frame& fr, const pc::Cluster& c, int32_t first_class) {
     const rp::Scan one = rp::scan_of_lane(L, fr, c, g.n_views, first_class, lane, 64);
@@ -153,11 +143,7 @@ __global__ __launch_bounds__(64) void k_rough_group(const GroupArgs g) {
       }
     }
   }
-  if (lane < kMeshStateWords) {
-    int32_t x = 0;
-    if (lane >= MS_UNION && lane < MS_LEVEL + 4) x = ((lane - MS_UNION) & 2) ? -1 : R_BIG;   // {min, min, max, max}
-    g.state[(size_t)k * kMeshStateWords + lane] = x;
-  }
+  if (lane < kMeshStateWords) g.state[(size_t)k * kMeshStateWords + lane] = mesh_state_clear(lane, 8);   // the union box and level 0's
   const bool run = s.state == pc::JOB && rec.status == rp::OK;
   if (run && lane < 10) g.slot_view[(size_t)k * 10 + lane] = lane < 9 ? rec.R[lane] : rec.distance;
   if (lane == 0) {
@@ -183,40 +169,11 @@ struct RenderArgs {
   int32_t win_w, win_h;
 };
 
-__device__ __forceinline__ uint32_t render_live(const RenderArgs& a) {
-  const uint32_t n = a.header[xpack::H_CLUSTERS];
-  return (uint64_t)n <= a.cap_clusters ? n : (uint32_t)a.cap_clusters;
-}
-
 __global__ __launch_bounds__(256) void k_rough_setup(const RenderArgs a) {
-  __shared__ int s_box[4], s_bad;
   const uint32_t v = blockIdx.x;   // the slot in x: up to 2^16 of them
-  if (v >= render_live(a) || !a.jobs[v].run) return;
+  if (v >= pc::n_live(a.header, a.cap_clusters) || !a.jobs[v].run) return;
   const int t = blockIdx.y * 256 + threadIdx.x;
-  if (threadIdx.x == 0) { s_box[0] = s_box[1] = R_BIG; s_box[2] = s_box[3] = -1; s_bad = 0; }
-  __syncthreads();
-  if (t < a.n_tri) {
-    const double* vw = a.slot_view + (size_t)v * 10;
-    double R[9];
-    for (int k = 0; k < 9; ++k) R[k] = vw[k];
-    mr::Tri rec;
-    const int rc = mr::setup_triangle(a.tri + (size_t)t * 9, R, vw[9], a.cam, rec);
-    if (rc != mr::TRI_OK) { rec = mr::Tri(); rec.x0 = 0; rec.x1 = -1; rec.y0 = 0; rec.y1 = -1; }   // an empty box: no pixel ever tests it
-    if (rc == mr::TRI_INVALID_VIEW) atomicOr(&s_bad, 1);
-    a.work[(size_t)v * a.n_tri + t] = rec;
-    if (rc == mr::TRI_OK && rec.x0 <= rec.x1 && rec.y0 <= rec.y1) {
-      atomicMin(&s_box[0], rec.x0); atomicMin(&s_box[1], rec.y0); atomicMax(&s_box[2], rec.x1); atomicMax(&s_box[3], rec.y1);
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int32_t* st = a.state + (size_t)v * kMeshStateWords;
-    if (s_bad) atomicOr(&st[MS_INVALID], 1);
-    if (s_box[2] >= 0) {
-      atomicMin(&st[MS_UNION + 0], s_box[0]); atomicMin(&st[MS_UNION + 1], s_box[1]);
-      atomicMax(&st[MS_UNION + 2], s_box[2]); atomicMax(&st[MS_UNION + 3], s_box[3]);
-    }
-  }
+  mesh_setup(a.tri, a.n_tri, a.cam, a.slot_view + (size_t)v * 10, a.work + (size_t)v * a.n_tri, a.state + (size_t)v * kMeshStateWords, t);
 }
 
 // The slot's window, or false: no view, an invalid view, no triangle on the image, a union box larger than the model's window.
@@ -234,48 +191,20 @@ __global__ __launch_bounds__(256) void k_rough_raster(const RenderArgs a) {
   __shared__ int s_sbox[4], s_count;
   const uint32_t v = blockIdx.x;   // the slot in x: up to 2^16 of them
   const int tid = threadIdx.x;
-  if (v >= render_live(a) || !a.jobs[v].run) return;
+  if (v >= pc::n_live(a.header, a.cap_clusters) || !a.jobs[v].run) return;
   int ux0, uy0, uw, uh;
   if (!slot_window(a, v, &ux0, &uy0, &uw, &uh)) return;
-  const int wx0 = blockIdx.y * RT_W, wy0 = blockIdx.z * RT_H;
+  const int wx0 = blockIdx.y * MR_TW, wy0 = blockIdx.z * MR_TH;
   if (wx0 >= uw || wy0 >= uh) return;
   const int pitch = dv::crop_pitch(uw);
-  const int wx = wx0 + (tid & (RT_W - 1)), wy = wy0 + tid / RT_W;
+  const int wx = wx0 + (tid & (MR_TW - 1)), wy = wy0 + tid / MR_TW;
   const int x = ux0 + wx, y = uy0 + wy;
   const bool inside = wx < uw && wy < uh;
   const int tx0 = ux0 + wx0, ty0 = uy0 + wy0;
-  const int tx1 = min(tx0 + RT_W, ux0 + uw) - 1, ty1 = min(ty0 + RT_H, uy0 + uh) - 1;
-  if (tid < 4) s_sbox[tid] = (tid & 2) ? -1 : R_BIG;
+  const int tx1 = min(tx0 + MR_TW, ux0 + uw) - 1, ty1 = min(ty0 + MR_TH, uy0 + uh) - 1;
+  if (tid < 4) s_sbox[tid] = (tid & 2) ? -1 : MR_BIG;
   if (tid == 4) s_count = 0;
-  double best_z = INFINITY, best_iz = -INFINITY;
-  const mr::Tri* vw = a.work + (size_t)v * a.n_tri;
-  const int lane = tid & 63, wave = tid >> 6;
-  for (int base = 0; base < a.n_tri; base += 256) {
-    const int t = base + tid;
-    bool hit = false;
-    if (t < a.n_tri) {
-      const int4 b = *reinterpret_cast<const int4*>(&vw[t].x0);   // x0, x1, y0, y1
-      hit = b.x <= tx1 && b.y >= tx0 && b.z <= ty1 && b.w >= ty0 && b.x <= b.y && b.z <= b.w;
-    }
-    const unsigned long long bal = __ballot(hit);
-    if (lane == 0) s_wave[wave] = __popcll(bal);
-    __syncthreads();   // also: the previous chunk's records have been read by every lane
-    int slot = __popcll(bal & ((1ull << lane) - 1ull));
-    int n_hit = 0;
-    for (int w = 0; w < 4; ++w) { const int c = s_wave[w]; if (w < wave) slot += c; n_hit += c; }
-    if (hit) s_tri[slot] = vw[t];
-    __syncthreads();
-    if (inside) {
-      for (int k = 0; k < n_hit; ++k) {
-        const mr::Tri& tr = s_tri[k];
-        double iz;
-        if (!mr::in_box(tr, x, y) || !mr::cover(tr, x, y, &iz)) continue;
-        if (!(iz > best_iz)) continue;   // as k_mesh_raster: z = 1 / iz does not increase with iz
-        const double z = 1.0 / iz;
-        if (z < best_z) { best_z = z; best_iz = iz; }
-      }
-    }
-  }
+  const double best_z = mesh_tile_walk<false>(a.work + (size_t)v * a.n_tri, a.n_tri, tx0, ty0, tx1, ty1, x, y, inside, s_tri, s_wave).z;
   const bool cov = inside && best_z < INFINITY;
   if (wx < pitch && wy < uh) a.window[(size_t)v * a.win_stride + (size_t)wy * pitch + wx] = cov ? mr::depth_mm(best_z) : (uint16_t)0;   // past uw: the padding
   if (cov) {
@@ -288,7 +217,7 @@ __global__ __launch_bounds__(256) void k_rough_raster(const RenderArgs a) {
     if (tid < 2) atomicMin(&st[MS_LEVEL + tid], s_sbox[tid]);
     else atomicMax(&st[MS_LEVEL + tid], s_sbox[tid]);
   }
-  if (tid == 4 && s_count) atomicAdd(&st[rp::RS_COUNT], s_count);
+  if (tid == 4 && s_count) atomicAdd(&st[MS_COUNT], s_count);
 }
 
 struct FinishArgs {
@@ -302,7 +231,7 @@ struct FinishArgs {
 __global__ __launch_bounds__(64) void k_rough_finish(const FinishArgs f) {
   const RenderArgs& a = f.r;
   const uint32_t v = blockIdx.x * 64 + threadIdx.x;
-  if (v >= render_live(a)) return;
+  if (v >= pc::n_live(a.header, a.cap_clusters)) return;
   rp::CropEntry entry = {nullptr, 0, 0, 0, 0};
   rp::Job job = f.jobs[v];
   if (job.run) {
@@ -318,7 +247,7 @@ __global__ __launch_bounds__(64) void k_rough_finish(const FinishArgs f) {
     if (status == rp::OK) {
       const int32_t sx0 = st[MS_LEVEL + 0], sy0 = st[MS_LEVEL + 1];
       r->rect[0] = sx0; r->rect[1] = sy0; r->rect[2] = st[MS_LEVEL + 2] - sx0 + 1; r->rect[3] = st[MS_LEVEL + 3] - sy0 + 1;
-      r->n_model = st[rp::RS_COUNT];
+      r->n_model = st[MS_COUNT];
       entry = rp::CropEntry{a.window + (size_t)v * a.win_stride, uw, uh, dv::crop_pitch(uw), 0};
       job.x += ux0 - sx0; job.y += uy0 - sy0; job.rect_x = ux0; job.rect_y = uy0;
       atomicAdd(&f.chain_header[rp::C_ROUGH_OK], 1u);
@@ -340,22 +269,13 @@ void launch_rough_stage(hipStream_t s, const lmx_rough_model* m, const rp::Stage
   const RenderArgs r = {a.L.header, a.L.cap_clusters, m->d_jobs, m->d_tri, m->n_tri, m->cam, m->d_slot_view, m->d_work, m->d_state, m->d_window, m->win_stride,
                         m->win_w, m->win_h};
   hipLaunchKernelGGL(k_rough_setup, dim3(n_slots, (unsigned)((m->n_tri + 255) / 256)), dim3(256), 0, s, r);   // <= 2^14 blocks of triangles
-  const dim3 grid(n_slots, (unsigned)((m->win_w + RT_W - 1) / RT_W), (unsigned)((m->win_h + RT_H - 1) / RT_H));   // <= 512 x 2048 tiles
+  const dim3 grid(n_slots, (unsigned)((m->win_w + MR_TW - 1) / MR_TW), (unsigned)((m->win_h + MR_TH - 1) / MR_TH));   // <= 512 x 2048 tiles
   hipLaunchKernelGGL(k_rough_raster, grid, dim3(256), 0, s, r);
   const FinishArgs f = {r, a.rough, m->d_crops, m->d_jobs, a.chain_header};
   hipLaunchKernelGGL(k_rough_finish, dim3((n_slots + 63) / 64), dim3(64), 0, s, f);
 }
 
 }  // namespace lmx
-
-#define ROUGH_HIP(expr)                                                                            \
-  do {                                                                                             \
-    hipError_t e_ = (expr);                                                                        \
-    if (e_ != hipSuccess) {                                                                        \
-      lmx::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);    \
-      return e_ == hipErrorNoDevice ? LMX_ERR_NO_DEVICE : LMX_ERR_HIP;                             \
-    }                                                                                              \
-  } while (0)
 
 namespace {
 void rough_model_release(lmx_rough_model* m) {
@@ -367,27 +287,27 @@ void rough_model_release(lmx_rough_model* m) {
 
 lmx_status rough_model_fill(lmx_rough_model* m, const double* triangles, const std::vector<lmx::rp::View>& table) {
   using namespace lmx;
-  ROUGH_HIP(hipSetDevice(m->device));
+  HIP_RETURN(hipSetDevice(m->device));
   const size_t S = (size_t)m->cap_slots;
   const size_t b_tri = (size_t)m->n_tri * 9 * sizeof(double), b_views = table.size() * sizeof(rp::View), b_sv = S * 10 * sizeof(double),
                b_state = S * kMeshStateWords * sizeof(int32_t), b_work = S * (size_t)m->n_tri * sizeof(mr::Tri), b_win = S * m->win_stride * sizeof(uint16_t),
                b_crops = S * sizeof(rp::CropEntry), b_jobs = S * sizeof(rp::Job);
-  ROUGH_HIP(hipMalloc(&m->d_tri, b_tri));
-  ROUGH_HIP(hipMalloc(&m->d_views, b_views));
-  ROUGH_HIP(hipMalloc(&m->d_slot_view, b_sv));
-  ROUGH_HIP(hipMalloc(&m->d_state, b_state));
-  ROUGH_HIP(hipMalloc(&m->d_work, b_work));
-  ROUGH_HIP(hipMalloc(&m->d_window, b_win));
-  ROUGH_HIP(hipMalloc(&m->d_crops, b_crops));
-  ROUGH_HIP(hipMalloc(&m->d_jobs, b_jobs));
+  HIP_RETURN(hipMalloc(&m->d_tri, b_tri));
+  HIP_RETURN(hipMalloc(&m->d_views, b_views));
+  HIP_RETURN(hipMalloc(&m->d_slot_view, b_sv));
+  HIP_RETURN(hipMalloc(&m->d_state, b_state));
+  HIP_RETURN(hipMalloc(&m->d_work, b_work));
+  HIP_RETURN(hipMalloc(&m->d_window, b_win));
+  HIP_RETURN(hipMalloc(&m->d_crops, b_crops));
+  HIP_RETURN(hipMalloc(&m->d_jobs, b_jobs));
   m->bytes = b_tri + b_views + b_sv + b_state + b_work + b_win + b_crops + b_jobs;
-  ROUGH_HIP(hipMemcpy(m->d_tri, triangles, b_tri, hipMemcpyHostToDevice));
-  ROUGH_HIP(hipMemcpy(m->d_views, table.data(), b_views, hipMemcpyHostToDevice));
-  ROUGH_HIP(hipMemset(m->d_state, 0, b_state));
-  ROUGH_HIP(hipMemset(m->d_window, 0, b_win));
-  ROUGH_HIP(hipMemset(m->d_crops, 0, b_crops));   // no slot has a crop before the first call
-  ROUGH_HIP(hipMemset(m->d_jobs, 0, b_jobs));
-  ROUGH_HIP(hipEventCreateWithFlags(&m->done, hipEventDisableTiming));
+  HIP_RETURN(hipMemcpy(m->d_tri, triangles, b_tri, hipMemcpyHostToDevice));
+  HIP_RETURN(hipMemcpy(m->d_views, table.data(), b_views, hipMemcpyHostToDevice));
+  HIP_RETURN(hipMemset(m->d_state, 0, b_state));
+  HIP_RETURN(hipMemset(m->d_window, 0, b_win));
+  HIP_RETURN(hipMemset(m->d_crops, 0, b_crops));   // no slot has a crop before the first call
+  HIP_RETURN(hipMemset(m->d_jobs, 0, b_jobs));
+  HIP_RETURN(hipEventCreateWithFlags(&m->done, hipEventDisableTiming));
   return LMX_OK;
 }
 }  // namespace
@@ -459,12 +379,12 @@ extern "C" lmx_status lmx_debug_rough_crop(lmx_rough_model* m, int32_t slot, uin
     if (!m || !out || !rect) { set_error("%s: null argument", what); return LMX_ERR_INVALID_ARG; }
     if (slot < 0 || slot >= m->cap_slots) { set_error("%s: slot %d of %d", what, slot, m->cap_slots); return LMX_ERR_INVALID_ARG; }
     std::lock_guard<std::mutex> lk(m->m);
-    ROUGH_HIP(hipSetDevice(m->device));
-    ROUGH_HIP(hipDeviceSynchronize());
+    HIP_RETURN(hipSetDevice(m->device));
+    HIP_RETURN(hipDeviceSynchronize());
     rp::CropEntry e;
     int32_t st[kMeshStateWords];
-    ROUGH_HIP(hipMemcpy(&e, m->d_crops + slot, sizeof(e), hipMemcpyDeviceToHost));
-    ROUGH_HIP(hipMemcpy(st, m->d_state + (size_t)slot * kMeshStateWords, sizeof(st), hipMemcpyDeviceToHost));
+    HIP_RETURN(hipMemcpy(&e, m->d_crops + slot, sizeof(e), hipMemcpyDeviceToHost));
+    HIP_RETURN(hipMemcpy(st, m->d_state + (size_t)slot * kMeshStateWords, sizeof(st), hipMemcpyDeviceToHost));
     rect[0] = rect[1] = rect[2] = rect[3] = 0;
     if (!e.data || e.w <= 0 || e.h <= 0) return LMX_OK;
     const int32_t sx0 = st[MS_LEVEL + 0], sy0 = st[MS_LEVEL + 1], sw = st[MS_LEVEL + 2] - sx0 + 1, sh = st[MS_LEVEL + 3] - sy0 + 1;
@@ -474,7 +394,7 @@ extern "C" lmx_status lmx_debug_rough_crop(lmx_rough_model* m, int32_t slot, uin
       return LMX_ERR_INVALID_ARG;
     }
     std::vector<uint16_t> win((size_t)e.h * e.pitch);
-    ROUGH_HIP(hipMemcpy(win.data(), m->d_window + (size_t)slot * m->win_stride, win.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    HIP_RETURN(hipMemcpy(win.data(), m->d_window + (size_t)slot * m->win_stride, win.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
     for (int32_t i = 0; i < sh; ++i) std::memcpy(out + (size_t)i * sw, win.data() + (size_t)(oy + i) * e.pitch + ox, (size_t)sw * sizeof(uint16_t));
     rect[0] = sx0; rect[1] = sy0; rect[2] = sw; rect[3] = sh;
     return LMX_OK;

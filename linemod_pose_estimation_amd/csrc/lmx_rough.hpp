@@ -17,8 +17,6 @@ struct CropEntry { const uint16_t* data; int32_t w, h, pitch, pad; };   // the b
 struct Job { int32_t run, frame, x, y, rect_x, rect_y, pad0, pad1; };
 static_assert(sizeof(CropEntry) == 24 && sizeof(Job) == 32, "layouts the kernels rely on");
 
-constexpr int RS_COUNT = 22;   // state word behind MS_CENTRE_DEPTH: the covered pixels of the slot's render
-
 struct StageArgs {
   pc::Lists L;               // what an export wrote, device memory
   int32_t class_index;

@@ -127,10 +127,10 @@ __global__ __launch_bounds__(256) void k_normal_map_frames(const uint16_t* __res
 }
 
 // ---- the crop walk ------------------------------------------------------------------------------------------------------------------------------------
+// The zeroed record of what is no job: the record's 8-byte words over the first lanes of the workgroup.
 template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {   // lane 0 gets the sum over the wave's 64 lanes
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
+__device__ __forceinline__ void store_zero_record(T* p, int tid) {
+  if (tid < (int)(sizeof(T) / 8)) reinterpret_cast<long long*>(p)[tid] = 0;
 }
 
 // The 16-byte result of a match, and with NORMALS the 16 bytes of its normal term.
@@ -373,7 +373,7 @@ __device__ __forceinline__ void pose_refine_body(const DepthCrop* __restrict__ c
   const bool is_job = job.template_id >= 0 && job.template_id < count && job.frame >= 0 && job.frame < n_frames;
   const DepthCrop c = is_job ? crops[job.template_id] : DepthCrop{nullptr, 0, 0, 0, 0};
   if (c.w <= 0 || c.h <= 0) {
-    if (tid < (int)(sizeof(lmx_pose_refine_t) / 8)) reinterpret_cast<long long*>(out)[tid] = 0;
+    store_zero_record(out, tid);
     return;
   }
   const uint16_t* frame = scene + (size_t)job.frame * H * W;
@@ -453,15 +453,6 @@ static_assert(offsetof(pv::Record, n_model) == offsetof(lmx_pose_verify_t, n_mod
                   offsetof(pv::Record, roi) == offsetof(lmx_pose_verify_t, roi),
               "pv::Record is lmx_pose_verify_t");
 
-__device__ __forceinline__ int wave_min(int v) {   // lane 0 gets the minimum over the wave's 64 lanes
-  for (int off = 32; off > 0; off >>= 1) { const int o = __shfl_down(v, off, 64); v = o < v ? o : v; }
-  return v;
-}
-__device__ __forceinline__ int wave_max(int v) {
-  for (int off = 32; off > 0; off >>= 1) { const int o = __shfl_down(v, off, 64); v = o > v ? o : v; }
-  return v;
-}
-
 // One 256-lane workgroup per job, four phases in one launch with a barrier between them:
 //   1  the crop walk of k_pose_refine under the job's pose: each lane's extent of keys and projections and its two counts (pv::bounds_pixel),
 //      wave shuffles, LDS across the four waves; lane 0 merges them and leaves the grid and the ROI in LDS (pv::grid_of), or the final
@@ -490,7 +481,7 @@ __device__ __forceinline__ void pose_verify_body(const DepthCrop* __restrict__ c
   const bool is_job = template_id >= 0 && template_id < count && frame_id >= 0 && frame_id < n_frames;
   const DepthCrop c = is_job ? crops[template_id] : DepthCrop{nullptr, 0, 0, 0, 0};
   if (c.w <= 0 || c.h <= 0) {
-    if (tid < (int)(sizeof(lmx_pose_verify_t) / 8)) reinterpret_cast<long long*>(out)[tid] = 0;
+    store_zero_record(out, tid);
     *rec0 = pv::Record{0.0, 0, 0, 0, 0, 0, pv::NONE, {0, 0, 0, 0}};
     return;
   }
@@ -568,6 +559,29 @@ __global__ __launch_bounds__(256) void k_pose_verify(const DepthCrop* __restrict
   pose_verify_body(crops, count, job->template_id, job->frame, job->rect_x, job->rect_y, job->R, job->t_mm, scene, n_frames, W, H, P, &out[blockIdx.x], &rec);
 }
 
+// What the two cluster-chain verify kernels do for a slot once they know whether it has a job: every lane reads the pose's status, R and
+// t_mm from *pose; a slot without a job, a pose of status LMX_POSE_NONE and one that pv::check_pose refuses (the host call refuses the
+// whole call there; here: a flag) get the zeroed record, the others pose_verify_body.  Lane 0 then has the record it stored: the keep
+// decision, and the header's three counters by vector atomic adds.
+__device__ __forceinline__ void verify_tail(bool has_job, const DepthCrop* crops, int32_t count, int32_t template_id, int32_t frame, int32_t rect_x, int32_t rect_y,
+                                            const uint16_t* scene, int32_t n_frames, int W, int H, const pv::Params& P, const lmx_pose_refine_t* pose,
+                                            lmx_pose_verify_t* check, uint8_t* keep, double keep_thresh, uint32_t* chain_header) {
+  const int tid = threadIdx.x;
+  const bool refined = has_job && pose->status != LMX_POSE_NONE;
+  const bool pose_ok = refined && pv::check_pose(pose->R, pose->t_mm) == nullptr;
+  pv::Record rec = {0.0, 0, 0, 0, 0, 0, pv::NONE, {0, 0, 0, 0}};
+  if (pose_ok) pose_verify_body(crops, count, template_id, frame, rect_x, rect_y, pose->R, pose->t_mm, scene, n_frames, W, H, P, check, &rec);
+  else store_zero_record(check, tid);
+  if (tid == 0) {
+    const bool kept = pv::keep(rec, keep_thresh);
+    *keep = kept ? 1 : 0;
+    if (refined) atomicAdd(&chain_header[pc::C_REFINED], 1u);
+    if (refined && !pose_ok) atomicOr(&chain_header[pc::C_FLAGS], (uint32_t)pc::FLAG_POSE);
+    if (rec.status == pv::OK) atomicAdd(&chain_header[pc::C_VERIFIED], 1u);
+    if (kept) atomicAdd(&chain_header[pc::C_KEPT], 1u);
+  }
+}
+
 // ---- both stages on exported clusters (lmx_pose_chain_on; the decisions: lmx_pose_chain.hpp) -----------------------------------------------------------
 static_assert(sizeof(pc::Match) == sizeof(lmx_match_t) && offsetof(pc::Match, template_id) == offsetof(lmx_match_t, template_id) &&
                   sizeof(pc::Cluster) == sizeof(lmx_cluster_t) && offsetof(pc::Cluster, member_begin) == offsetof(lmx_cluster_t, member_begin),
@@ -643,7 +657,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
     if (s.flags) atomicOr(&a.chain_header[pc::C_FLAGS], s.flags);
   }
   if (s.state != pc::JOB) {
-    if (tid < (int)(sizeof(lmx_pose_refine_t) / 8)) reinterpret_cast<long long*>(&a.poses[k])[tid] = 0;
+    store_zero_record(&a.poses[k], tid);
     return;
   }
   const PoseJob job = {s.x, s.y, s.template_id, s.frame, s.rect_x, s.rect_y, 0, 0};
@@ -651,10 +665,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
 }
 
 // The same grid behind it.  Wave 0 decides the slot again from leaders[k] (the job is not kept between the kernels: a match, a frame and a
-// rect are cheaper to read again than to store), every lane reads the pose's status, R and t_mm from poses[k]; a slot without a job, a
-// pose of status LMX_POSE_NONE and one that pv::check_pose refuses (the host call refuses the whole call there; here: a flag) get the
-// zeroed record, the others k_pose_verify's body.  Lane 0 then has the record it stored: the keep decision, and the header's three counters
-// by vector atomic adds.
+// rect are cheaper to read again than to store), then verify_tail.
 __global__ __launch_bounds__(256) void k_pose_verify_clusters(const ChainArgs a, const pv::Params P) {
   __shared__ pc::Slot s_slot;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -666,20 +677,8 @@ __global__ __launch_bounds__(256) void k_pose_verify_clusters(const ChainArgs a,
   }
   __syncthreads();
   const pc::Slot s = uniform_slot(s_slot);
-  const lmx_pose_refine_t* pose = &a.poses[k];
-  const bool refined = s.state == pc::JOB && pose->status != LMX_POSE_NONE;
-  const bool pose_ok = refined && pv::check_pose(pose->R, pose->t_mm) == nullptr;
-  pv::Record rec = {0.0, 0, 0, 0, 0, 0, pv::NONE, {0, 0, 0, 0}};
-  if (pose_ok) pose_verify_body(a.crops, a.T.count, s.template_id, s.frame, s.rect_x, s.rect_y, pose->R, pose->t_mm, a.scene, a.L.n_frames, a.W, a.H, P, &a.checks[k], &rec);
-  else if (tid < (int)(sizeof(lmx_pose_verify_t) / 8)) reinterpret_cast<long long*>(&a.checks[k])[tid] = 0;
-  if (tid == 0) {
-    const bool kept = pv::keep(rec, a.keep_thresh);
-    a.keep[k] = kept ? 1 : 0;
-    if (refined) atomicAdd(&a.chain_header[pc::C_REFINED], 1u);
-    if (refined && !pose_ok) atomicOr(&a.chain_header[pc::C_FLAGS], (uint32_t)pc::FLAG_POSE);
-    if (rec.status == pv::OK) atomicAdd(&a.chain_header[pc::C_VERIFIED], 1u);
-    if (kept) atomicAdd(&a.chain_header[pc::C_KEPT], 1u);
-  }
+  verify_tail(s.state == pc::JOB, a.crops, a.T.count, s.template_id, s.frame, s.rect_x, s.rect_y, a.scene, a.L.n_frames, a.W, a.H, P, &a.poses[k], &a.checks[k],
+              &a.keep[k], a.keep_thresh, a.chain_header);
 }
 
 // ---- both stages behind the rough pose stage (lmx_rough_pose_chain_on; lmx_rough.hip leaves a job and a crop table entry per slot) -------------------
@@ -704,22 +703,17 @@ struct RoughChainArgs {
   double keep_thresh;
 };
 
-__device__ __forceinline__ uint32_t rough_live(const RoughChainArgs& a) {
-  const uint32_t n = a.header[xpack::H_CLUSTERS];
-  return (uint64_t)n <= a.cap_clusters ? n : (uint32_t)a.cap_clusters;
-}
-
 // k_pose_refine_clusters' grid and body; the prologue is two loads: k_rough_finish decided the slot and left its job.  The job's fields
 // are told to the compiler as uniform, as uniform_slot does.  253 vector registers, 106 scalar, 592 bytes of scratch per lane (the body's
 // local arrays, as in k_pose_refine: 251, 106, 592), 2 waves per SIMD as k_pose_refine and k_pose_refine_clusters (255, 106, 592).
 // k_rough_verify_clusters: 67 vector registers, 106 scalar, no scratch, 4 waves per SIMD, as k_pose_verify_clusters.
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_rough_refine_clusters(const RoughChainArgs a, const pr::Params P) {
   const uint32_t k = blockIdx.x;
-  if (k >= rough_live(a)) return;
+  if (k >= pc::n_live(a.header, a.cap_clusters)) return;
   const rp::Job* j = a.jobs + k;
   const int tid = threadIdx.x;
   if (!__builtin_amdgcn_readfirstlane(j->run)) {
-    if (tid < (int)(sizeof(lmx_pose_refine_t) / 8)) reinterpret_cast<long long*>(&a.poses[k])[tid] = 0;
+    store_zero_record(&a.poses[k], tid);
     return;
   }
   const PoseJob job = {__builtin_amdgcn_readfirstlane(j->x), __builtin_amdgcn_readfirstlane(j->y), (int32_t)k, __builtin_amdgcn_readfirstlane(j->frame),
@@ -730,39 +724,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
 // k_pose_verify_clusters behind it, on the same job.
 __global__ __launch_bounds__(256) void k_rough_verify_clusters(const RoughChainArgs a, const pv::Params P) {
   const uint32_t k = blockIdx.x;
-  if (k >= rough_live(a)) return;
+  if (k >= pc::n_live(a.header, a.cap_clusters)) return;
   const rp::Job* j = a.jobs + k;
-  const int tid = threadIdx.x;
-  const bool run = __builtin_amdgcn_readfirstlane(j->run) != 0;
-  const lmx_pose_refine_t* pose = &a.poses[k];
-  const bool refined = run && pose->status != LMX_POSE_NONE;
-  const bool pose_ok = refined && pv::check_pose(pose->R, pose->t_mm) == nullptr;
-  pv::Record rec = {0.0, 0, 0, 0, 0, 0, pv::NONE, {0, 0, 0, 0}};
-  if (pose_ok)
-    pose_verify_body(a.crops, a.cap_slots, (int32_t)k, __builtin_amdgcn_readfirstlane(j->frame), __builtin_amdgcn_readfirstlane(j->rect_x),
-                     __builtin_amdgcn_readfirstlane(j->rect_y), pose->R, pose->t_mm, a.scene, a.n_frames, a.W, a.H, P, &a.checks[k], &rec);
-  else if (tid < (int)(sizeof(lmx_pose_verify_t) / 8)) reinterpret_cast<long long*>(&a.checks[k])[tid] = 0;
-  if (tid == 0) {
-    const bool kept = pv::keep(rec, a.keep_thresh);
-    a.keep[k] = kept ? 1 : 0;
-    if (refined) atomicAdd(&a.chain_header[pc::C_REFINED], 1u);
-    if (refined && !pose_ok) atomicOr(&a.chain_header[pc::C_FLAGS], (uint32_t)pc::FLAG_POSE);
-    if (rec.status == pv::OK) atomicAdd(&a.chain_header[pc::C_VERIFIED], 1u);
-    if (kept) atomicAdd(&a.chain_header[pc::C_KEPT], 1u);
-  }
+  verify_tail(__builtin_amdgcn_readfirstlane(j->run) != 0, a.crops, a.cap_slots, (int32_t)k, __builtin_amdgcn_readfirstlane(j->frame),
+              __builtin_amdgcn_readfirstlane(j->rect_x), __builtin_amdgcn_readfirstlane(j->rect_y), a.scene, a.n_frames, a.W, a.H, P, &a.poses[k], &a.checks[k],
+              &a.keep[k], a.keep_thresh, a.chain_header);
 }
 
 }  // namespace
 }  // namespace lmx
-
-#define DV_HIP(expr)                                                                               \
-  do {                                                                                             \
-    hipError_t e_ = (expr);                                                                        \
-    if (e_ != hipSuccess) {                                                                        \
-      lmx::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);    \
-      return e_ == hipErrorNoDevice ? LMX_ERR_NO_DEVICE : LMX_ERR_HIP;                             \
-    }                                                                                              \
-  } while (0)
 
 struct lmx_depth_templates {
   int32_t device = 0;
@@ -855,24 +825,24 @@ struct lmx_depth_templates {
   lmx_status ensure_device() {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { lmx::set_error("no HIP device available; this library has no CPU path"); return LMX_ERR_NO_DEVICE; }
-    DV_HIP(hipSetDevice(device));
-    if (!s) DV_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    if (!scene_ready) DV_HIP(hipEventCreateWithFlags(&scene_ready, hipEventDisableTiming));
+    HIP_RETURN(hipSetDevice(device));
+    if (!s) HIP_RETURN(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    if (!scene_ready) HIP_RETURN(hipEventCreateWithFlags(&scene_ready, hipEventDisableTiming));
     if (!d_table && !table.empty()) {
-      DV_HIP(hipMalloc(&d_table, table.size() * sizeof(lmx::DepthCrop)));
-      DV_HIP(hipMemcpyAsync(d_table, table.data(), table.size() * sizeof(lmx::DepthCrop), hipMemcpyHostToDevice, s));
-      DV_HIP(hipStreamSynchronize(s));
+      HIP_RETURN(hipMalloc(&d_table, table.size() * sizeof(lmx::DepthCrop)));
+      HIP_RETURN(hipMemcpyAsync(d_table, table.data(), table.size() * sizeof(lmx::DepthCrop), hipMemcpyHostToDevice, s));
+      HIP_RETURN(hipStreamSynchronize(s));
     }
     return LMX_OK;
   }
   // Nothing an export queued still reads the crops, the table, the scene or the normals.
   lmx_status wait_export_reads() {
-    if (export_read_pending) { DV_HIP(hipSetDevice(device)); DV_HIP(hipEventSynchronize(export_read)); export_read_pending = false; }
+    if (export_read_pending) { HIP_RETURN(hipSetDevice(device)); HIP_RETURN(hipEventSynchronize(export_read)); export_read_pending = false; }
     return LMX_OK;
   }
   // The staging buffer is free again: the copies of the previous upload_scene have left it.
   lmx_status wait_scene_copies() {
-    if (scene_pending) { DV_HIP(hipEventSynchronize(scene_ready)); scene_pending = false; }
+    if (scene_pending) { HIP_RETURN(hipEventSynchronize(scene_ready)); scene_pending = false; }
     return LMX_OK;
   }
   // A call failed with copies of earlier frames possibly still queued: nothing may read the staging buffer once the call has returned, since
@@ -880,13 +850,13 @@ struct lmx_depth_templates {
   void drain_after_error() { (void)hipStreamSynchronize(s); }
   lmx_status grow_scene(size_t bytes) {
     if (bytes <= scene_cap) return LMX_OK;
-    DV_HIP(hipStreamSynchronize(s));     // nothing queued may still use the buffers that go
+    HIP_RETURN(hipStreamSynchronize(s));     // nothing queued may still use the buffers that go
     if (lmx_status st = wait_export_reads()) return st;
     (void)hipFree(d_scene); (void)hipHostFree(h_scene);
     d_scene = h_scene = nullptr; scene_cap = 0;
     const size_t cap = bytes;
-    DV_HIP(hipMalloc(&d_scene, cap));
-    DV_HIP(hipHostMalloc(&h_scene, cap, hipHostMallocDefault));
+    HIP_RETURN(hipMalloc(&d_scene, cap));
+    HIP_RETURN(hipHostMalloc(&h_scene, cap, hipHostMallocDefault));
     scene_cap = cap;
     return LMX_OK;
   }
@@ -897,8 +867,8 @@ struct lmx_depth_templates {
     (void)hipFree(d); (void)hipHostFree(h);
     d = h = nullptr; cap = 0;
     const size_t want = std::max(n, (size_t)1024);
-    DV_HIP(hipMalloc(&d, want * sizeof(T)));
-    DV_HIP(hipHostMalloc(&h, want * sizeof(T), hipHostMallocDefault));
+    HIP_RETURN(hipMalloc(&d, want * sizeof(T)));
+    HIP_RETURN(hipHostMalloc(&h, want * sizeof(T), hipHostMallocDefault));
     cap = want;
     return LMX_OK;
   }
@@ -916,34 +886,34 @@ struct lmx_depth_templates {
       if (lmx_status st = wait_export_reads()) return st;
       (void)hipFree(d_scene_normals);
       d_scene_normals = nullptr; scene_normals_cap = 0;
-      DV_HIP(hipMalloc(&d_scene_normals, bytes));
+      HIP_RETURN(hipMalloc(&d_scene_normals, bytes));
       scene_normals_cap = bytes;
     }
     const unsigned gx = (unsigned)std::min<size_t>(((size_t)W * H + 255) / 256, 4096);
     const int pe = prof_begin(PK_NORMAL_MAP_FRAMES, on);
     hipLaunchKernelGGL(lmx::k_normal_map_frames, dim3(gx, (unsigned)n_frames), dim3(256), 0, on, d_scene, W, H, d_scene_normals, nparams);
     prof_end(pe, on);
-    DV_HIP(hipGetLastError());
-    DV_HIP(hipEventRecord(normals_ready, on));
+    HIP_RETURN(hipGetLastError());
+    HIP_RETURN(hipEventRecord(normals_ready, on));
     return LMX_OK;
   }
   // what every normal-scored call needs next to ensure_device(): the angle table and the event
   lmx_status ensure_normal_device() {
-    if (!normals_ready) DV_HIP(hipEventCreateWithFlags(&normals_ready, hipEventDisableTiming));
+    if (!normals_ready) HIP_RETURN(hipEventCreateWithFlags(&normals_ready, hipEventDisableTiming));
     if (!d_angle) {
       std::vector<uint32_t> tab(lmx::nv::kAngleTableSize);
       lmx::nv::build_angle_table(tab.data());
-      DV_HIP(hipMalloc(&d_angle, tab.size() * sizeof(uint32_t)));
-      DV_HIP(hipMemcpyAsync(d_angle, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-      DV_HIP(hipStreamSynchronize(s));   // tab goes when this returns
+      HIP_RETURN(hipMalloc(&d_angle, tab.size() * sizeof(uint32_t)));
+      HIP_RETURN(hipMemcpyAsync(d_angle, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+      HIP_RETURN(hipStreamSynchronize(s));   // tab goes when this returns
     }
     return LMX_OK;
   }
   // Stream `on` is about to read the normals of the n_frames W x H frames in d_scene: compute them there if nobody has (behind the scene's
   // copies: `behind_copies` is null when `on` is the stream that carries them), or wait for whoever did.
   lmx_status scene_normals_on(hipStream_t on, hipEvent_t behind_copies, int32_t n_frames, int32_t W, int32_t H) {
-    if (scene_normals_valid) { DV_HIP(hipStreamWaitEvent(on, normals_ready, 0)); return LMX_OK; }
-    if (behind_copies) DV_HIP(hipStreamWaitEvent(on, behind_copies, 0));
+    if (scene_normals_valid) { HIP_RETURN(hipStreamWaitEvent(on, normals_ready, 0)); return LMX_OK; }
+    if (behind_copies) HIP_RETURN(hipStreamWaitEvent(on, behind_copies, 0));
     if (lmx_status st = compute_scene_normals(on, n_frames, W, H)) return st;
     scene_normals_valid = true;
     return LMX_OK;
@@ -1008,20 +978,20 @@ extern "C" lmx_status lmx_depth_templates_from_mesh(int32_t device, const double
     DeviceBuffer d_tri, d_views, d_work, d_state, d_depth;
     std::vector<int32_t> state((size_t)B * kMeshStateWords);
     hipStream_t s = t->s;
-    DV_HIP(hipMalloc(&d_tri.p, (size_t)n_triangles * 9 * sizeof(double)));
-    DV_HIP(hipMalloc(&d_views.p, (size_t)B * 10 * sizeof(double)));
-    DV_HIP(hipMalloc(&d_work.p, (size_t)B * n_triangles * sizeof(mr::Tri)));
-    DV_HIP(hipMalloc(&d_state.p, state.size() * 4));
-    DV_HIP(hipMalloc(&d_depth.p, px * B * sizeof(uint16_t)));
-    DV_HIP(hipMemcpyAsync(d_tri.p, triangles, (size_t)n_triangles * 9 * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_RETURN(hipMalloc(&d_tri.p, (size_t)n_triangles * 9 * sizeof(double)));
+    HIP_RETURN(hipMalloc(&d_views.p, (size_t)B * 10 * sizeof(double)));
+    HIP_RETURN(hipMalloc(&d_work.p, (size_t)B * n_triangles * sizeof(mr::Tri)));
+    HIP_RETURN(hipMalloc(&d_state.p, state.size() * 4));
+    HIP_RETURN(hipMalloc(&d_depth.p, px * B * sizeof(uint16_t)));
+    HIP_RETURN(hipMemcpyAsync(d_tri.p, triangles, (size_t)n_triangles * 9 * sizeof(double), hipMemcpyHostToDevice, s));
     for (int first = 0; first < n_views; first += B) {
       const int n = std::min(B, n_views - first);
-      DV_HIP(hipMemcpyAsync(d_views.p, views + first, (size_t)n * 10 * sizeof(double), hipMemcpyHostToDevice, s));
+      HIP_RETURN(hipMemcpyAsync(d_views.p, views + first, (size_t)n * 10 * sizeof(double), hipMemcpyHostToDevice, s));
       launch_mesh_raster(s, d_tri.as<double>(), n_triangles, dc, d_views.as<double>(), n, 1, d_work.as<mr::Tri>(), d_state.as<int32_t>(), nullptr,
                          d_depth.as<uint16_t>(), nullptr);
-      DV_HIP(hipGetLastError());
-      DV_HIP(hipMemcpyAsync(state.data(), d_state.p, (size_t)n * kMeshStateWords * 4, hipMemcpyDeviceToHost, s));
-      DV_HIP(hipStreamSynchronize(s));
+      HIP_RETURN(hipGetLastError());
+      HIP_RETURN(hipMemcpyAsync(state.data(), d_state.p, (size_t)n * kMeshStateWords * 4, hipMemcpyDeviceToHost, s));
+      HIP_RETURN(hipStreamSynchronize(s));
       CropBatch where;
       std::memset(&where, 0, sizeof(where));
       size_t elems = 0;
@@ -1034,11 +1004,11 @@ extern "C" lmx_status lmx_depth_templates_from_mesh(int32_t device, const double
       }
       uint16_t* chunk = nullptr;
       if (elems) {
-        DV_HIP(hipMalloc(&chunk, elems * sizeof(uint16_t)));
+        HIP_RETURN(hipMalloc(&chunk, elems * sizeof(uint16_t)));
         t->chunks.push_back(chunk);
         t->atlas_bytes += elems * sizeof(uint16_t);
         hipLaunchKernelGGL(k_depth_crop, dim3(16, (unsigned)n), dim3(256), 0, s, d_depth.as<uint16_t>(), d_state.as<int32_t>(), dc.W, dc.H, chunk, where);
-        DV_HIP(hipGetLastError());
+        HIP_RETURN(hipGetLastError());
       }
       for (int i = 0; i < n; ++i) {
         const int32_t* b = &state[(size_t)i * kMeshStateWords] + MS_LEVEL;
@@ -1051,7 +1021,7 @@ extern "C" lmx_status lmx_depth_templates_from_mesh(int32_t device, const double
         }
       }
     }
-    DV_HIP(hipStreamSynchronize(s));   // the scratch buffers go when this returns
+    HIP_RETURN(hipStreamSynchronize(s));   // the scratch buffers go when this returns
     *out = t.release();
     return LMX_OK;
   });
@@ -1080,7 +1050,7 @@ extern "C" lmx_status lmx_depth_templates_from_crops(int32_t device, const uint1
     if (bytes) {
       if (lmx_status st = t->ensure_device()) return st;
       packed.assign(bytes / sizeof(uint16_t), 0);   // the padding is zeros
-      DV_HIP(hipMalloc(&chunk, bytes));
+      HIP_RETURN(hipMalloc(&chunk, bytes));
       t->chunks.push_back(chunk);
       t->atlas_bytes = bytes;
     }
@@ -1098,8 +1068,8 @@ extern "C" lmx_status lmx_depth_templates_from_crops(int32_t device, const uint1
       }
     }
     if (bytes) {
-      DV_HIP(hipMemcpyAsync(chunk, packed.data(), bytes, hipMemcpyHostToDevice, t->s));
-      DV_HIP(hipStreamSynchronize(t->s));
+      HIP_RETURN(hipMemcpyAsync(chunk, packed.data(), bytes, hipMemcpyHostToDevice, t->s));
+      HIP_RETURN(hipStreamSynchronize(t->s));
     }
     *out = t.release();
     return LMX_OK;
@@ -1125,8 +1095,8 @@ extern "C" lmx_status lmx_depth_templates_get(const lmx_depth_templates* ct, int
     if (!out) { lmx::set_error("lmx_depth_templates_get: null argument"); return LMX_ERR_INVALID_ARG; }
     std::lock_guard<std::mutex> lk(t->m);
     if (lmx_status st = t->ensure_device()) return st;
-    DV_HIP(hipMemcpy2DAsync(out, (size_t)c.w * 2, c.data, (size_t)c.pitch * 2, (size_t)c.w * 2, (size_t)c.h, hipMemcpyDeviceToHost, t->s));
-    DV_HIP(hipStreamSynchronize(t->s));
+    HIP_RETURN(hipMemcpy2DAsync(out, (size_t)c.w * 2, c.data, (size_t)c.pitch * 2, (size_t)c.w * 2, (size_t)c.h, hipMemcpyDeviceToHost, t->s));
+    HIP_RETURN(hipStreamSynchronize(t->s));
     return LMX_OK;
   });
 }
@@ -1154,8 +1124,8 @@ extern "C" lmx_status lmx_depth_templates_append(lmx_depth_templates* dst, lmx_d
     // nothing queued may still read a table or the normals that go
     for (lmx_depth_templates* t : {dst, src})
       if (t->s) {
-        DV_HIP(hipSetDevice(t->device));
-        DV_HIP(hipStreamSynchronize(t->s));
+        HIP_RETURN(hipSetDevice(t->device));
+        HIP_RETURN(hipStreamSynchronize(t->s));
         if (lmx_status st = t->wait_export_reads()) return st;
         t->scene_pending = false;
         t->prof_drain();
@@ -1203,7 +1173,7 @@ lmx_status queue_frame(lmx_depth_templates* t, const lmx_image& im, int32_t slot
   const size_t frame_bytes = (size_t)W * H * sizeof(uint16_t);
   uint8_t* h = reinterpret_cast<uint8_t*>(t->h_scene) + frame_bytes * slot;
   lmx::copy_rows(h, im.data, (size_t)W * 2, im.row_stride_bytes, H);
-  DV_HIP(hipMemcpyAsync(reinterpret_cast<uint8_t*>(t->d_scene) + frame_bytes * slot, h, frame_bytes, hipMemcpyHostToDevice, t->s));
+  HIP_RETURN(hipMemcpyAsync(reinterpret_cast<uint8_t*>(t->d_scene) + frame_bytes * slot, h, frame_bytes, hipMemcpyHostToDevice, t->s));
   return LMX_OK;
 }
 
@@ -1212,14 +1182,14 @@ lmx_status queue_frame(lmx_depth_templates* t, const lmx_image& im, int32_t slot
 // the caller's to hold.  With `normals`: both terms, against the normals of the n_frames frames there (computed first if nobody has), h_nout too.
 lmx_status run_jobs(lmx_depth_templates* t, size_t n, int32_t n_frames, int32_t W, int32_t H, bool normals) {
   hipStream_t s = t->s;
-  DV_HIP(hipMemcpyAsync(t->d_jobs, t->h_jobs, n * sizeof(lmx::DepthJob), hipMemcpyHostToDevice, s));
+  HIP_RETURN(hipMemcpyAsync(t->d_jobs, t->h_jobs, n * sizeof(lmx::DepthJob), hipMemcpyHostToDevice, s));
   lmx::DepthWalk w;
   w.jobs = t->d_jobs; w.n = (uint32_t)n; w.n_frames = n_frames; w.W = W; w.H = H;
   w.d_diffs = t->d_out; w.d_ndiffs = normals ? t->d_nout : nullptr;
   if (lmx_status st = lmx::depth_launch_walk(t, s, w)) return st;
-  DV_HIP(hipMemcpyAsync(t->h_out, t->d_out, n * sizeof(lmx_depth_diff_t), hipMemcpyDeviceToHost, s));
-  if (normals) DV_HIP(hipMemcpyAsync(t->h_nout, t->d_nout, n * sizeof(lmx_normal_diff_t), hipMemcpyDeviceToHost, s));
-  DV_HIP(hipStreamSynchronize(s));
+  HIP_RETURN(hipMemcpyAsync(t->h_out, t->d_out, n * sizeof(lmx_depth_diff_t), hipMemcpyDeviceToHost, s));
+  if (normals) HIP_RETURN(hipMemcpyAsync(t->h_nout, t->d_nout, n * sizeof(lmx_normal_diff_t), hipMemcpyDeviceToHost, s));
+  HIP_RETURN(hipStreamSynchronize(s));
   return LMX_OK;
 }
 
@@ -1228,14 +1198,14 @@ lmx_status compute_crop_normals(lmx_depth_templates* t) {
   using namespace lmx;
   if (lmx_status st = t->ensure_device()) return st;
   if (lmx_status st = t->ensure_normal_device()) return st;
-  DV_HIP(hipStreamSynchronize(t->s));
+  HIP_RETURN(hipStreamSynchronize(t->s));
   if (lmx_status st = t->wait_export_reads()) return st;   // an export's walk may still read the normals that go
   t->free_normal_crops();
   t->ncrops_ready = false;
   const size_t n = t->table.size(), elems = t->atlas_bytes / sizeof(uint16_t);
   if (n == 0) { t->ncrops_ready = true; return LMX_OK; }
-  if (elems) DV_HIP(hipMalloc(&t->d_ncrops, elems * sizeof(nv::Packed)));
-  DV_HIP(hipMalloc(&t->d_ntable, n * sizeof(nv::Packed*)));
+  if (elems) HIP_RETURN(hipMalloc(&t->d_ncrops, elems * sizeof(nv::Packed)));
+  HIP_RETURN(hipMalloc(&t->d_ntable, n * sizeof(nv::Packed*)));
   t->ntable.assign(n, nullptr);
   size_t at = 0;
   for (size_t i = 0; i < n; ++i) {
@@ -1244,13 +1214,13 @@ lmx_status compute_crop_normals(lmx_depth_templates* t) {
     t->ntable[i] = t->d_ncrops + at;
     at += (size_t)c.h * (size_t)c.pitch;
   }
-  DV_HIP(hipMemcpyAsync(t->d_ntable, t->ntable.data(), n * sizeof(nv::Packed*), hipMemcpyHostToDevice, t->s));
+  HIP_RETURN(hipMemcpyAsync(t->d_ntable, t->ntable.data(), n * sizeof(nv::Packed*), hipMemcpyHostToDevice, t->s));
   for (size_t first = 0; first < n; first += 32768) {   // blockIdx.y: at most 65535
     const unsigned cnt = (unsigned)std::min<size_t>(32768, n - first);
     hipLaunchKernelGGL(k_normal_map_crops, dim3(32, cnt), dim3(256), 0, t->s, t->d_table + first, t->d_ntable + first, t->nparams);
-    DV_HIP(hipGetLastError());
+    HIP_RETURN(hipGetLastError());
   }
-  DV_HIP(hipStreamSynchronize(t->s));   // ntable's bytes have left the host
+  HIP_RETURN(hipStreamSynchronize(t->s));   // ntable's bytes have left the host
   t->ncrops_ready = true;
   return LMX_OK;
 }
@@ -1325,18 +1295,16 @@ extern "C" lmx_status lmx_depth_templates_upload_scene_device(lmx_depth_template
         return LMX_ERR_INVALID_ARG;
       }
     }
-    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    if (user && hipStreamIsCapturing(user, &capturing) != hipSuccess) { (void)hipGetLastError(); set_error("%s: invalid stream", what); return LMX_ERR_INVALID_ARG; }
-    if (capturing != hipStreamCaptureStatusNone) { set_error("%s: the stream is being captured into a graph", what); return LMX_ERR_INVALID_ARG; }
+    if (lmx_status st = check_user_stream(what, user)) return st;
     const int32_t W = depth[0].cols, H = depth[0].rows;
     const size_t frame_bytes = (size_t)W * H * sizeof(uint16_t);
     t->scene_frames = 0;
     t->scene_normals_valid = false;
     if (lmx_status st = t->grow_scene(frame_bytes * (size_t)n_frames)) return st;
-    if (!t->scene_src_ready) DV_HIP(hipEventCreateWithFlags(&t->scene_src_ready, hipEventDisableTiming));
-    DV_HIP(hipEventRecord(t->scene_src_ready, user));
-    DV_HIP(hipStreamWaitEvent(t->s, t->scene_src_ready, 0));
-    if (t->export_read_pending) DV_HIP(hipStreamWaitEvent(t->s, t->export_read, 0));   // on the device: an export's walk may still read the old scene
+    if (!t->scene_src_ready) HIP_RETURN(hipEventCreateWithFlags(&t->scene_src_ready, hipEventDisableTiming));
+    HIP_RETURN(hipEventRecord(t->scene_src_ready, user));
+    HIP_RETURN(hipStreamWaitEvent(t->s, t->scene_src_ready, 0));
+    if (t->export_read_pending) HIP_RETURN(hipStreamWaitEvent(t->s, t->export_read, 0));   // on the device: an export's walk may still read the old scene
     for (int32_t f = 0; f < n_frames; ++f)
       if (hipError_t e = hipMemcpy2DAsync(reinterpret_cast<uint8_t*>(t->d_scene) + frame_bytes * f, (size_t)W * 2, depth[f].data, depth[f].row_stride_bytes, (size_t)W * 2,
                                           (size_t)H, hipMemcpyDeviceToDevice, t->s)) {
@@ -1350,7 +1318,7 @@ extern "C" lmx_status lmx_depth_templates_upload_scene_device(lmx_depth_template
       return LMX_ERR_HIP;
     }
     t->scene_frames = n_frames; t->scene_W = W; t->scene_H = H;
-    DV_HIP(hipStreamWaitEvent(user, t->scene_ready, 0));
+    HIP_RETURN(hipStreamWaitEvent(user, t->scene_ready, 0));
     return LMX_OK;
   });
 }
@@ -1440,18 +1408,18 @@ lmx_status depth_launch_walk(lmx_depth_templates* t, hipStream_t s, const DepthW
   unsigned grid = w.n;
   if (device_count) {
     if (lmx_status st = t->ensure_device()) return st;   // the table, after an append: an export checks nothing else of the object first
-    if (!t->export_read) DV_HIP(hipEventCreateWithFlags(&t->export_read, hipEventDisableTiming));
+    if (!t->export_read) HIP_RETURN(hipEventCreateWithFlags(&t->export_read, hipEventDisableTiming));
     if (w.grid <= 0 && t->walk_grid <= 0) {
       int cus = 0;
-      DV_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, t->device));
+      HIP_RETURN(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, t->device));
       t->walk_grid = kWalkGridPerCU * std::max(cus, 1);
     }
     grid = (unsigned)(w.grid > 0 ? w.grid : t->walk_grid);
     // this form alone: nobody waits for it on the host, so the record below must stand behind every earlier such walk too.  A host-count
     // walk ends synchronised, and the collect's stream must not start waiting for exports
-    if (t->export_read_pending) DV_HIP(hipStreamWaitEvent(s, t->export_read, 0));
+    if (t->export_read_pending) HIP_RETURN(hipStreamWaitEvent(s, t->export_read, 0));
   }
-  if (!jobs) DV_HIP(hipStreamWaitEvent(s, t->scene_ready, 0));   // the job form runs on the stream that carries the frames' copies
+  if (!jobs) HIP_RETURN(hipStreamWaitEvent(s, t->scene_ready, 0));   // the job form runs on the stream that carries the frames' copies
   if (!device_count && w.n == 0) return LMX_OK;   // a grid of 0 is no launch; the device-count form launches always: nobody here knows the count
   if (normals)   // the scene's normals first, on this stream, if this is the scene's first normal-scored call
     if (lmx_status st = t->scene_normals_on(s, nullptr, n_frames, W, H)) return st;
@@ -1464,9 +1432,9 @@ lmx_status depth_launch_walk(lmx_depth_templates* t, hipStream_t s, const DepthW
   if (normals) launch_walk<true>(s, grid, device_count, src, a);
   else launch_walk<false>(s, grid, device_count, src, a);
   t->prof_end(pe, s);
-  DV_HIP(hipGetLastError());
+  HIP_RETURN(hipGetLastError());
   if (device_count) {   // what changes the crops, the scene or the normals waits for this
-    DV_HIP(hipEventRecord(t->export_read, s));
+    HIP_RETURN(hipEventRecord(t->export_read, s));
     t->export_read_pending = true;
   }
   return LMX_OK;
@@ -1607,8 +1575,8 @@ extern "C" lmx_status lmx_depth_templates_get_normals(const lmx_depth_templates*
     if (!out) { lmx::set_error("lmx_depth_templates_get_normals: null argument"); return LMX_ERR_INVALID_ARG; }
     std::lock_guard<std::mutex> lk(t->m);
     if (lmx_status st = need_normals(t, "lmx_depth_templates_get_normals")) return st;
-    DV_HIP(hipMemcpy2DAsync(out, (size_t)c.w * 8, t->ntable[id], (size_t)c.pitch * 8, (size_t)c.w * 8, (size_t)c.h, hipMemcpyDeviceToHost, t->s));
-    DV_HIP(hipStreamSynchronize(t->s));
+    HIP_RETURN(hipMemcpy2DAsync(out, (size_t)c.w * 8, t->ntable[id], (size_t)c.pitch * 8, (size_t)c.w * 8, (size_t)c.h, hipMemcpyDeviceToHost, t->s));
+    HIP_RETURN(hipStreamSynchronize(t->s));
     return LMX_OK;
   });
 }
@@ -1643,8 +1611,8 @@ extern "C" lmx_status lmx_debug_scene_normals(lmx_depth_templates* t, int32_t fr
     if (lmx_status st = need_normals(t, "lmx_debug_scene_normals")) return st;
     if (lmx_status st = t->scene_normals_on(t->s, nullptr, t->scene_frames, t->scene_W, t->scene_H)) return st;
     const size_t px = (size_t)t->scene_W * t->scene_H;
-    DV_HIP(hipMemcpyAsync(out, t->d_scene_normals + px * frame, px * sizeof(lmx::nv::Packed), hipMemcpyDeviceToHost, t->s));
-    DV_HIP(hipStreamSynchronize(t->s));
+    HIP_RETURN(hipMemcpyAsync(out, t->d_scene_normals + px * frame, px * sizeof(lmx::nv::Packed), hipMemcpyDeviceToHost, t->s));
+    HIP_RETURN(hipStreamSynchronize(t->s));
     return LMX_OK;
   });
 }
@@ -1688,21 +1656,21 @@ extern "C" lmx_status lmx_debug_depth_walk_records(lmx_depth_templates* t, const
     uint32_t hdr[16] = {0};
     hdr[0] = n_candidates; hdr[1] = header_count;
     hipStream_t s = t->s;
-    DV_HIP(hipMalloc(&d_hdr.p, sizeof(hdr)));
-    DV_HIP(hipMalloc(&d_recs.p, R * sizeof(lmx_raw_match_t)));
-    DV_HIP(hipMalloc(&d_diffs.p, R * sizeof(lmx_depth_diff_t)));
-    DV_HIP(hipMemcpyAsync(d_hdr.p, hdr, sizeof(hdr), hipMemcpyHostToDevice, s));
+    HIP_RETURN(hipMalloc(&d_hdr.p, sizeof(hdr)));
+    HIP_RETURN(hipMalloc(&d_recs.p, R * sizeof(lmx_raw_match_t)));
+    HIP_RETURN(hipMalloc(&d_diffs.p, R * sizeof(lmx_depth_diff_t)));
+    HIP_RETURN(hipMemcpyAsync(d_hdr.p, hdr, sizeof(hdr), hipMemcpyHostToDevice, s));
     if (n_records) {
-      DV_HIP(hipMemcpyAsync(d_recs.p, records, n_records * sizeof(lmx_raw_match_t), hipMemcpyHostToDevice, s));
-      DV_HIP(hipMemcpyAsync(d_diffs.p, diffs, n_records * sizeof(lmx_depth_diff_t), hipMemcpyHostToDevice, s));
+      HIP_RETURN(hipMemcpyAsync(d_recs.p, records, n_records * sizeof(lmx_raw_match_t), hipMemcpyHostToDevice, s));
+      HIP_RETURN(hipMemcpyAsync(d_diffs.p, diffs, n_records * sizeof(lmx_depth_diff_t), hipMemcpyHostToDevice, s));
     }
     if (ndiffs) {
-      DV_HIP(hipMalloc(&d_ndiffs.p, R * sizeof(lmx_normal_diff_t)));
-      if (n_records) DV_HIP(hipMemcpyAsync(d_ndiffs.p, ndiffs, n_records * sizeof(lmx_normal_diff_t), hipMemcpyHostToDevice, s));
+      HIP_RETURN(hipMalloc(&d_ndiffs.p, R * sizeof(lmx_normal_diff_t)));
+      if (n_records) HIP_RETURN(hipMemcpyAsync(d_ndiffs.p, ndiffs, n_records * sizeof(lmx_normal_diff_t), hipMemcpyHostToDevice, s));
     }
     if (class_base) {
-      DV_HIP(hipMalloc(&d_base.p, ((size_t)n_classes + 1) * sizeof(int32_t)));
-      DV_HIP(hipMemcpyAsync(d_base.p, class_base, ((size_t)n_classes + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+      HIP_RETURN(hipMalloc(&d_base.p, ((size_t)n_classes + 1) * sizeof(int32_t)));
+      HIP_RETURN(hipMemcpyAsync(d_base.p, class_base, ((size_t)n_classes + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
     }
     DepthWalk w;
     w.recs = d_recs.as<lmx_raw_match_t>(); w.hdr = d_hdr.as<uint32_t>(); w.cap = cap; w.grid = grid_workgroups;
@@ -1710,10 +1678,10 @@ extern "C" lmx_status lmx_debug_depth_walk_records(lmx_depth_templates* t, const
     w.d_diffs = d_diffs.as<lmx_depth_diff_t>(); w.d_ndiffs = d_ndiffs.as<lmx_normal_diff_t>();
     lmx_status st = depth_launch_walk(t, s, w);
     if (st == LMX_OK && n_records) {
-      DV_HIP(hipMemcpyAsync(diffs, d_diffs.p, n_records * sizeof(lmx_depth_diff_t), hipMemcpyDeviceToHost, s));
-      if (ndiffs) DV_HIP(hipMemcpyAsync(ndiffs, d_ndiffs.p, n_records * sizeof(lmx_normal_diff_t), hipMemcpyDeviceToHost, s));
+      HIP_RETURN(hipMemcpyAsync(diffs, d_diffs.p, n_records * sizeof(lmx_depth_diff_t), hipMemcpyDeviceToHost, s));
+      if (ndiffs) HIP_RETURN(hipMemcpyAsync(ndiffs, d_ndiffs.p, n_records * sizeof(lmx_normal_diff_t), hipMemcpyDeviceToHost, s));
     }
-    DV_HIP(hipStreamSynchronize(s));   // the scratch buffers go when this returns
+    HIP_RETURN(hipStreamSynchronize(s));   // the scratch buffers go when this returns
     t->export_read_pending = false;
     return st;
   });
@@ -1820,7 +1788,7 @@ lmx_status pose_call(const PoseCall& a, const std::function<int(size_t, const lm
       if (t->slot[f] >= 0)
         if (lmx_status st = queue_frame(t, depth[f], t->slot[f], W, H)) { t->drain_after_error(); return st; }
   } else {
-    DV_HIP(hipStreamWaitEvent(s, t->scene_ready, 0));   // the resident scene: behind its copies, whichever stream queued them
+    HIP_RETURN(hipStreamWaitEvent(s, t->scene_ready, 0));   // the resident scene: behind its copies, whichever stream queued them
   }
   const lmx_status st = launch(W, H, n_slots, count, rects);
   if (st != LMX_OK) t->drain_after_error();
@@ -1850,18 +1818,18 @@ lmx_status pose_refine_impl(const char* what, lmx_depth_templates* t, const lmx_
         DeviceBuffer d_dbg;
         const size_t dbg_bytes = ((size_t)P.max_iterations + 1) * pr::kSums * sizeof(int64_t);
         if (dbg) {
-          DV_HIP(hipMalloc(&d_dbg.p, dbg_bytes));
-          DV_HIP(hipMemsetAsync(d_dbg.p, 0, dbg_bytes, s));
+          HIP_RETURN(hipMalloc(&d_dbg.p, dbg_bytes));
+          HIP_RETURN(hipMemsetAsync(d_dbg.p, 0, dbg_bytes, s));
         }
-        DV_HIP(hipMemcpyAsync(t->d_pjobs, t->h_pjobs, n * sizeof(PoseJob), hipMemcpyHostToDevice, s));
+        HIP_RETURN(hipMemcpyAsync(t->d_pjobs, t->h_pjobs, n * sizeof(PoseJob), hipMemcpyHostToDevice, s));
         const int pe = t->prof_begin(lmx_depth_templates::PK_POSE_REFINE, s);
         hipLaunchKernelGGL(k_pose_refine, dim3((unsigned)n), dim3(256), 0, s, t->d_table, (int32_t)count, t->d_pjobs, t->d_scene, n_slots, W, H, P, t->d_pout,
                            d_dbg.as<long long>());
         t->prof_end(pe, s);
-        DV_HIP(hipGetLastError());
-        DV_HIP(hipMemcpyAsync(t->h_pout, t->d_pout, n * sizeof(lmx_pose_refine_t), hipMemcpyDeviceToHost, s));
-        if (dbg) DV_HIP(hipMemcpyAsync(dbg, d_dbg.p, dbg_bytes, hipMemcpyDeviceToHost, s));
-        DV_HIP(hipStreamSynchronize(s));   // the results are here, the scratch buffer may go
+        HIP_RETURN(hipGetLastError());
+        HIP_RETURN(hipMemcpyAsync(t->h_pout, t->d_pout, n * sizeof(lmx_pose_refine_t), hipMemcpyDeviceToHost, s));
+        if (dbg) HIP_RETURN(hipMemcpyAsync(dbg, d_dbg.p, dbg_bytes, hipMemcpyDeviceToHost, s));
+        HIP_RETURN(hipStreamSynchronize(s));   // the results are here, the scratch buffer may go
         for (size_t k = 0; k < n; ++k) out[t->sel[k]] = t->h_pout[k];
         return LMX_OK;
       });
@@ -1941,13 +1909,13 @@ extern "C" lmx_status lmx_pose_verify_matches(lmx_depth_templates* t, const lmx_
             std::memcpy(j.R, p.R, sizeof(j.R));
             std::memcpy(j.t_mm, p.t_mm, sizeof(j.t_mm));
           }
-          DV_HIP(hipMemcpyAsync(t->d_vjobs, t->h_vjobs, n * sizeof(VerifyJob), hipMemcpyHostToDevice, s));
+          HIP_RETURN(hipMemcpyAsync(t->d_vjobs, t->h_vjobs, n * sizeof(VerifyJob), hipMemcpyHostToDevice, s));
           const int pe = t->prof_begin(lmx_depth_templates::PK_POSE_VERIFY, s);
           hipLaunchKernelGGL(k_pose_verify, dim3((unsigned)n), dim3(256), 0, s, t->d_table, (int32_t)count, t->d_vjobs, t->d_scene, n_slots, W, H, P, t->d_vout);
           t->prof_end(pe, s);
-          DV_HIP(hipGetLastError());
-          DV_HIP(hipMemcpyAsync(t->h_vout, t->d_vout, n * sizeof(lmx_pose_verify_t), hipMemcpyDeviceToHost, s));
-          DV_HIP(hipStreamSynchronize(s));
+          HIP_RETURN(hipGetLastError());
+          HIP_RETURN(hipMemcpyAsync(t->h_vout, t->d_vout, n * sizeof(lmx_pose_verify_t), hipMemcpyDeviceToHost, s));
+          HIP_RETURN(hipStreamSynchronize(s));
           for (size_t k = 0; k < n; ++k) out[t->sel[k]] = t->h_vout[k];
           return LMX_OK;
         });
@@ -1971,16 +1939,16 @@ namespace {
 // previous chain's kernels may still read the old entries: the upload waits for them (they run on t->s).
 lmx_status chain_sync_ints(lmx_depth_templates* t, lmx_depth_templates::DevInts& d, const int32_t* src, size_t n) {
   if (d.dev && d.host.size() == n && std::equal(d.host.begin(), d.host.end(), src)) return LMX_OK;
-  DV_HIP(hipStreamSynchronize(t->s));
+  HIP_RETURN(hipStreamSynchronize(t->s));
   if (n > d.cap || !d.dev) {
     (void)hipFree(d.dev);
     d.dev = nullptr; d.cap = 0; d.host.clear();
     const size_t want = std::max<size_t>(n, 1);
-    DV_HIP(hipMalloc(&d.dev, want * sizeof(int32_t)));
+    HIP_RETURN(hipMalloc(&d.dev, want * sizeof(int32_t)));
     d.cap = want;
   }
   d.host.clear();
-  if (n) DV_HIP(hipMemcpy(d.dev, src, n * sizeof(int32_t), hipMemcpyHostToDevice));
+  if (n) HIP_RETURN(hipMemcpy(d.dev, src, n * sizeof(int32_t), hipMemcpyHostToDevice));
   d.host.assign(src, src + n);
   return LMX_OK;
 }
@@ -2003,22 +1971,51 @@ lmx_status check_chain_memory(const char* what, const lmx_depth_templates* t, co
   return LMX_OK;
 }
 
+// What the checks read of the fields lmx_pose_chain_desc and lmx_rough_chain_desc share.  outputs: the call's own second output stands in
+// for `leaders` (the rough chain's member_group).
+struct ChainFields {
+  const lmx_pose_refine_params* refine;
+  const lmx_pose_verify_params* verify;
+  bool lists, outputs;   // none of header, frame_info, matches, clusters, members / of chain_header, leaders, poses, checks, keep is null
+  size_t cap_clusters;
+  int32_t n_frames;
+  double keep_thresh;
+};
+template <typename Desc>
+ChainFields chain_fields(const Desc* d, const void* leaders) {
+  return {d->refine, d->verify, d->header && d->frame_info && d->matches && d->clusters && d->members, d->chain_header && leaders && d->poses && d->checks && d->keep,
+          d->cap_clusters, d->n_frames, d->keep_thresh};
+}
+template <typename Desc>
+lmx::pc::Lists chain_lists(const Desc& d) {
+  using namespace lmx;
+  return pc::Lists{d.header, d.frame_info, d.n_frames, reinterpret_cast<const pc::Match*>(d.matches), reinterpret_cast<const pc::Cluster*>(d.clusters), d.members,
+                   (uint64_t)d.cap_matches, (uint64_t)d.cap_clusters, (uint64_t)d.cap_members};
+}
+
+// What both chain calls refuse of the shared fields, whatever memory the arrays live in; t->m is held.
+lmx_status chain_check_fields(const char* what, lmx_depth_templates* t, const ChainFields& d, lmx::pr::Params* PR, lmx::pv::Params* PV) {
+  using namespace lmx;
+  if (lmx_status st = pose_params(what, d.refine, PR)) return st;
+  if (lmx_status st = verify_params(what, d.verify, PV)) return st;
+  if (!d.lists) { set_error("%s: header, frame_info, matches, clusters and members must not be null", what); return LMX_ERR_INVALID_ARG; }
+  if (!d.outputs) { set_error("%s: chain_header, leaders, poses, checks and keep must not be null", what); return LMX_ERR_INVALID_ARG; }
+  if (d.cap_clusters < 1 || d.cap_clusters > pc::kMaxClusters) { set_error("%s: cap_clusters = %zu (1 .. 2^20)", what, d.cap_clusters); return LMX_ERR_INVALID_ARG; }
+  if (d.n_frames < 1) { set_error("%s: n_frames = %d", what, d.n_frames); return LMX_ERR_INVALID_ARG; }
+  if (d.keep_thresh != d.keep_thresh) { set_error("%s: keep_thresh is not a number", what); return LMX_ERR_INVALID_ARG; }
+  if (t->scene_frames < 1) { set_error("%s: no scene is uploaded: call lmx_depth_templates_upload_scene first", what); return LMX_ERR_INVALID_ARG; }
+  if (t->scene_frames != d.n_frames) { set_error("%s: the uploaded scene holds %d frames, not %d", what, t->scene_frames, d.n_frames); return LMX_ERR_INVALID_ARG; }
+  const int32_t W = t->scene_W, H = t->scene_H;
+  if (W >= pr::kMaxCoord / 2 || H >= pr::kMaxCoord / 2) { set_error("%s: frames of %d x %d (sides below %d)", what, W, H, (int)(pr::kMaxCoord / 2)); return LMX_ERR_INVALID_ARG; }
+  if ((int64_t)W * H > (int64_t)INT32_MAX) { set_error("%s: frames of %d x %d (at most %d pixels)", what, W, H, INT32_MAX); return LMX_ERR_INVALID_ARG; }
+  return LMX_OK;
+}
+
 // Everything lmx_pose_chain_on refuses that does not depend on where the arrays live; t->m is held.
 lmx_status chain_check(const char* what, lmx_depth_templates* t, const lmx_pose_chain_desc* d, lmx::pr::Params* PR, lmx::pv::Params* PV) {
   using namespace lmx;
   if (d->struct_size != sizeof(lmx_pose_chain_desc)) { set_error("%s: struct_size %u, not %zu", what, d->struct_size, sizeof(lmx_pose_chain_desc)); return LMX_ERR_INVALID_ARG; }
-  if (lmx_status st = pose_params(what, d->refine, PR)) return st;
-  if (lmx_status st = verify_params(what, d->verify, PV)) return st;
-  if (!d->header || !d->frame_info || !d->matches || !d->clusters || !d->members) { set_error("%s: header, frame_info, matches, clusters and members must not be null", what); return LMX_ERR_INVALID_ARG; }
-  if (!d->chain_header || !d->leaders || !d->poses || !d->checks || !d->keep) { set_error("%s: chain_header, leaders, poses, checks and keep must not be null", what); return LMX_ERR_INVALID_ARG; }
-  if (d->cap_clusters < 1 || d->cap_clusters > pc::kMaxClusters) { set_error("%s: cap_clusters = %zu (1 .. 2^20)", what, d->cap_clusters); return LMX_ERR_INVALID_ARG; }
-  if (d->n_frames < 1) { set_error("%s: n_frames = %d", what, d->n_frames); return LMX_ERR_INVALID_ARG; }
-  if (d->keep_thresh != d->keep_thresh) { set_error("%s: keep_thresh is not a number", what); return LMX_ERR_INVALID_ARG; }
-  if (t->scene_frames < 1) { set_error("%s: no scene is uploaded: call lmx_depth_templates_upload_scene first", what); return LMX_ERR_INVALID_ARG; }
-  if (t->scene_frames != d->n_frames) { set_error("%s: the uploaded scene holds %d frames, not %d", what, t->scene_frames, d->n_frames); return LMX_ERR_INVALID_ARG; }
-  const int32_t W = t->scene_W, H = t->scene_H;
-  if (W >= pr::kMaxCoord / 2 || H >= pr::kMaxCoord / 2) { set_error("%s: frames of %d x %d (sides below %d)", what, W, H, (int)(pr::kMaxCoord / 2)); return LMX_ERR_INVALID_ARG; }
-  if ((int64_t)W * H > (int64_t)INT32_MAX) { set_error("%s: frames of %d x %d (at most %d pixels)", what, W, H, INT32_MAX); return LMX_ERR_INVALID_ARG; }
+  if (lmx_status st = chain_check_fields(what, t, chain_fields(d, d->leaders), PR, PV)) return st;
   if (d->class_base) {
     if (d->n_classes < 1 || d->n_classes > F2_CLASSES || d->class_base[0] != 0) { set_error("%s: class_base: n_classes 1..%d, class_base[0] = 0", what, F2_CLASSES); return LMX_ERR_INVALID_ARG; }
     for (int32_t k = 0; k < d->n_classes; ++k)
@@ -2028,8 +2025,31 @@ lmx_status chain_check(const char* what, lmx_depth_templates* t, const lmx_pose_
   return LMX_OK;
 }
 
-// Queues the call (every array of `d` in device memory, chain_check passed, t->m held): the tables, the waits, the three launches, the
-// record behind them.  user: the caller's stream, with_user false: the test hook, which orders nothing but t->s itself.
+// The front of a chain call's work on t->s: behind what the caller's stream holds (the export's end, and whatever still uses the
+// outputs), behind every earlier walk of the export and behind the scene's upload.  user: the caller's stream, with_user false: a test
+// hook, which orders nothing but t->s itself.
+lmx_status chain_begin(lmx_depth_templates* t, hipStream_t user, bool with_user) {
+  if (!t->export_read) HIP_RETURN(hipEventCreateWithFlags(&t->export_read, hipEventDisableTiming));
+  if (!t->chain_src_ready) HIP_RETURN(hipEventCreateWithFlags(&t->chain_src_ready, hipEventDisableTiming));
+  if (with_user) {
+    HIP_RETURN(hipEventRecord(t->chain_src_ready, user));
+    HIP_RETURN(hipStreamWaitEvent(t->s, t->chain_src_ready, 0));
+  }
+  if (t->export_read_pending) HIP_RETURN(hipStreamWaitEvent(t->s, t->export_read, 0));   // chain_end's record then stands behind every earlier walk too
+  HIP_RETURN(hipStreamWaitEvent(t->s, t->scene_ready, 0));
+  return LMX_OK;
+}
+
+// Its end: the record the next export's writes wait for, and the caller's stream behind it.
+lmx_status chain_end(lmx_depth_templates* t, hipStream_t user, bool with_user) {
+  HIP_RETURN(hipEventRecord(t->export_read, t->s));
+  t->export_read_pending = true;
+  if (with_user) HIP_RETURN(hipStreamWaitEvent(user, t->export_read, 0));
+  return LMX_OK;
+}
+
+// Queues the call (every array of `d` in device memory, chain_check passed, t->m held): the tables, chain_begin, the three launches,
+// chain_end.
 lmx_status chain_queue(lmx_depth_templates* t, const lmx_pose_chain_desc& d, const lmx::pr::Params& PR, const lmx::pv::Params& PV, hipStream_t user, bool with_user) {
   using namespace lmx;
   if (lmx_status st = t->ensure_device()) return st;
@@ -2042,37 +2062,51 @@ lmx_status chain_queue(lmx_depth_templates* t, const lmx_pose_chain_desc& d, con
     if (lmx_status st = chain_sync_ints(t, t->chain_rects_verify, rv, count * 4)) return st;
   if (d.class_base)
     if (lmx_status st = chain_sync_ints(t, t->chain_base, d.class_base, (size_t)d.n_classes + 1)) return st;
-  if (!t->export_read) DV_HIP(hipEventCreateWithFlags(&t->export_read, hipEventDisableTiming));
-  if (!t->chain_src_ready) DV_HIP(hipEventCreateWithFlags(&t->chain_src_ready, hipEventDisableTiming));
+  if (lmx_status st = chain_begin(t, user, with_user)) return st;
   hipStream_t s = t->s;
-  if (with_user) {   // behind what the caller's stream holds: the export's end, and whatever still uses the outputs
-    DV_HIP(hipEventRecord(t->chain_src_ready, user));
-    DV_HIP(hipStreamWaitEvent(s, t->chain_src_ready, 0));
-  }
-  if (t->export_read_pending) DV_HIP(hipStreamWaitEvent(s, t->export_read, 0));   // the record below then stands behind every earlier walk too
-  DV_HIP(hipStreamWaitEvent(s, t->scene_ready, 0));
   ChainArgs a;
-  a.L = pc::Lists{d.header, d.frame_info, d.n_frames, reinterpret_cast<const pc::Match*>(d.matches), reinterpret_cast<const pc::Cluster*>(d.clusters), d.members,
-                  (uint64_t)d.cap_matches, (uint64_t)d.cap_clusters, (uint64_t)d.cap_members};
-  a.T = pc::Table{(int32_t)count, t->chain_rects_refine.dev, d.class_base ? -1 : d.class_index, d.class_base ? t->chain_base.dev : nullptr, d.class_base ? d.n_classes : 0};
+  a.L = chain_lists(d);
+  a.T =pc::Table{(int32_t)count, t->chain_rects_refine.dev, d.class_base ? -1 : d.class_index, d.class_base ? t->chain_base.dev : nullptr, d.class_base ? d.n_classes : 0};
   a.crops = t->d_table; a.scene = t->d_scene; a.W = t->scene_W; a.H = t->scene_H;
   a.chain_header = d.chain_header; a.leaders = d.leaders; a.poses = d.poses; a.checks = d.checks; a.keep = d.keep; a.keep_thresh = d.keep_thresh;
   const dim3 grid((unsigned)d.cap_clusters), block(256);
-  DV_HIP(hipMemsetAsync(d.chain_header, 0, pc::C_WORDS * sizeof(uint32_t), s));
+  HIP_RETURN(hipMemsetAsync(d.chain_header, 0, pc::C_WORDS * sizeof(uint32_t), s));
   int pe = t->prof_begin(lmx_depth_templates::PK_POSE_REFINE_CLUSTERS, s);
   hipLaunchKernelGGL(k_pose_refine_clusters, grid, block, 0, s, a, PR);
   t->prof_end(pe, s);
-  DV_HIP(hipGetLastError());
+  HIP_RETURN(hipGetLastError());
   if (!same_rects) a.T.rects = t->chain_rects_verify.dev;
   pe = t->prof_begin(lmx_depth_templates::PK_POSE_VERIFY_CLUSTERS, s);
   hipLaunchKernelGGL(k_pose_verify_clusters, grid, block, 0, s, a, PV);
   t->prof_end(pe, s);
-  DV_HIP(hipGetLastError());
-  DV_HIP(hipEventRecord(t->export_read, s));
-  t->export_read_pending = true;
-  if (with_user) DV_HIP(hipStreamWaitEvent(user, t->export_read, 0));
-  return LMX_OK;
+  HIP_RETURN(hipGetLastError());
+  return chain_end(t, user, with_user);
 }
+
+// The arrays of a test hook's call, which lie in host memory: {host address, bytes, uploaded only or read back as well}.  upload:
+// each in a device buffer of its own, filled on s; at(i): that buffer, for the desc the hook hands on; finish: the outputs back (where
+// the call was queued) and the stream drained -- the buffers go with this object.
+struct HookArray { const void* host; size_t bytes; bool is_output; };
+template <int N>
+struct HookArrays {
+  const HookArray* arr = nullptr;
+  DeviceBuffer dev[N];
+  lmx_status upload(const HookArray (&a)[N], hipStream_t s) {
+    arr = a;
+    for (int k = 0; k < N; ++k) {
+      HIP_RETURN(hipMalloc(&dev[k].p, std::max<size_t>(a[k].bytes, 16)));
+      if (a[k].bytes) HIP_RETURN(hipMemcpyAsync(dev[k].p, a[k].host, a[k].bytes, hipMemcpyHostToDevice, s));
+    }
+    return LMX_OK;
+  }
+  template <typename T> T* at(int k) const { return dev[k].template as<T>(); }
+  lmx_status finish(hipStream_t s, bool queued) {
+    for (int k = 0; k < N && queued; ++k)
+      if (arr[k].is_output && arr[k].bytes) HIP_RETURN(hipMemcpyAsync(const_cast<void*>(arr[k].host), dev[k].p, arr[k].bytes, hipMemcpyDeviceToHost, s));
+    HIP_RETURN(hipStreamSynchronize(s));
+    return LMX_OK;
+  }
+};
 }  // namespace
 
 extern "C" lmx_status lmx_pose_chain_on(lmx_depth_templates* t, const lmx_pose_chain_desc* d, void* stream) {
@@ -2086,9 +2120,7 @@ extern "C" lmx_status lmx_pose_chain_on(lmx_depth_templates* t, const lmx_pose_c
     if (lmx_status st = chain_check(what, t, d, &PR, &PV)) return st;
     if (lmx_status st = t->ensure_device()) return st;
     hipStream_t user = static_cast<hipStream_t>(stream);
-    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    if (user && hipStreamIsCapturing(user, &capturing) != hipSuccess) { (void)hipGetLastError(); set_error("%s: invalid stream", what); return LMX_ERR_INVALID_ARG; }
-    if (capturing != hipStreamCaptureStatusNone) { set_error("%s: the stream is being captured into a graph", what); return LMX_ERR_INVALID_ARG; }
+    if (lmx_status st = check_user_stream(what, user)) return st;
     const struct { const char* name; const void* p; size_t align; } arrays[] = {
         {"header", d->header, 4}, {"frame_info", d->frame_info, 4}, {"matches", d->matches, 4}, {"clusters", d->clusters, 8}, {"members", d->members, 4},
         {"chain_header", d->chain_header, 4}, {"leaders", d->leaders, 4}, {"poses", d->poses, 8}, {"checks", d->checks, 8}, {"keep", d->keep, 1}};
@@ -2113,25 +2145,20 @@ extern "C" lmx_status lmx_debug_pose_chain(lmx_depth_templates* t, const lmx_pos
     if (lmx_status st = t->ensure_device()) return st;
     hipStream_t s = t->s;
     const size_t C = d->cap_clusters;
-    // the ten arrays: host address, bytes, input (uploaded) or output (uploaded and read back; chain_header is zeroed by the call)
-    struct Arr { const void* host; size_t bytes; DeviceBuffer dev; };
-    Arr arr[10] = {{d->header, xpack::H_WORDS * sizeof(uint32_t), {}}, {d->frame_info, (size_t)d->n_frames * xpack::I_WORDS * sizeof(int32_t), {}},
-                   {d->matches, d->cap_matches * sizeof(lmx_match_t), {}}, {d->clusters, C * sizeof(lmx_cluster_t), {}}, {d->members, d->cap_members * sizeof(int32_t), {}},
-                   {d->chain_header, pc::C_WORDS * sizeof(uint32_t), {}}, {d->leaders, C * sizeof(int32_t), {}}, {d->poses, C * sizeof(lmx_pose_refine_t), {}},
-                   {d->checks, C * sizeof(lmx_pose_verify_t), {}}, {d->keep, C, {}}};
-    for (Arr& x : arr) {
-      DV_HIP(hipMalloc(&x.dev.p, std::max<size_t>(x.bytes, 16)));
-      if (x.bytes) DV_HIP(hipMemcpyAsync(x.dev.p, x.host, x.bytes, hipMemcpyHostToDevice, s));
-    }
+    // five inputs, five outputs (chain_header is zeroed by the call)
+    const HookArray arr[10] = {{d->header, xpack::H_WORDS * sizeof(uint32_t), false}, {d->frame_info, (size_t)d->n_frames * xpack::I_WORDS * sizeof(int32_t), false},
+                               {d->matches, d->cap_matches * sizeof(lmx_match_t), false}, {d->clusters, C * sizeof(lmx_cluster_t), false},
+                               {d->members, d->cap_members * sizeof(int32_t), false}, {d->chain_header, pc::C_WORDS * sizeof(uint32_t), true},
+                               {d->leaders, C * sizeof(int32_t), true}, {d->poses, C * sizeof(lmx_pose_refine_t), true}, {d->checks, C * sizeof(lmx_pose_verify_t), true},
+                               {d->keep, C, true}};
+    HookArrays<10> h;
+    if (lmx_status st = h.upload(arr, s)) return st;
     lmx_pose_chain_desc dd = *d;
-    dd.header = arr[0].dev.as<uint32_t>(); dd.frame_info = arr[1].dev.as<int32_t>(); dd.matches = arr[2].dev.as<lmx_match_t>();
-    dd.clusters = arr[3].dev.as<lmx_cluster_t>(); dd.members = arr[4].dev.as<int32_t>(); dd.chain_header = arr[5].dev.as<uint32_t>();
-    dd.leaders = arr[6].dev.as<int32_t>(); dd.poses = arr[7].dev.as<lmx_pose_refine_t>(); dd.checks = arr[8].dev.as<lmx_pose_verify_t>();
-    dd.keep = arr[9].dev.as<uint8_t>();
-    lmx_status st = chain_queue(t, dd, PR, PV, nullptr, false);
-    if (st == LMX_OK)
-      for (int k = 5; k < 10; ++k) DV_HIP(hipMemcpyAsync(const_cast<void*>(arr[k].host), arr[k].dev.p, arr[k].bytes, hipMemcpyDeviceToHost, s));
-    DV_HIP(hipStreamSynchronize(s));   // the scratch buffers go when this returns
+    dd.header = h.at<uint32_t>(0); dd.frame_info = h.at<int32_t>(1); dd.matches = h.at<lmx_match_t>(2); dd.clusters = h.at<lmx_cluster_t>(3);
+    dd.members = h.at<int32_t>(4); dd.chain_header = h.at<uint32_t>(5); dd.leaders = h.at<int32_t>(6); dd.poses = h.at<lmx_pose_refine_t>(7);
+    dd.checks = h.at<lmx_pose_verify_t>(8); dd.keep = h.at<uint8_t>(9);
+    const lmx_status st = chain_queue(t, dd, PR, PV, nullptr, false);
+    if (lmx_status e = h.finish(s, st == LMX_OK)) return e;
     t->export_read_pending = false;
     return st;
   });
@@ -2144,13 +2171,7 @@ lmx_status rough_check(const char* what, lmx_depth_templates* t, lmx_rough_model
   using namespace lmx;
   if (d->struct_size != sizeof(lmx_rough_chain_desc)) { set_error("%s: struct_size %u, not %zu", what, d->struct_size, sizeof(lmx_rough_chain_desc)); return LMX_ERR_INVALID_ARG; }
   if (!d->rough || !d->member_group) { set_error("%s: rough and member_group must not be null", what); return LMX_ERR_INVALID_ARG; }
-  lmx_pose_chain_desc pd = {};
-  pd.struct_size = sizeof(lmx_pose_chain_desc);
-  pd.n_frames = d->n_frames; pd.class_index = d->class_index; pd.refine = d->refine; pd.verify = d->verify; pd.keep_thresh = d->keep_thresh;
-  pd.header = d->header; pd.frame_info = d->frame_info; pd.matches = d->matches; pd.cap_matches = d->cap_matches; pd.clusters = d->clusters;
-  pd.cap_clusters = d->cap_clusters; pd.members = d->members; pd.cap_members = d->cap_members;
-  pd.chain_header = d->chain_header; pd.leaders = d->member_group; pd.poses = d->poses; pd.checks = d->checks; pd.keep = d->keep;
-  if (lmx_status st = chain_check(what, t, &pd, PR, PV)) return st;
+  if (lmx_status st = chain_check_fields(what, t, chain_fields(d, d->member_group), PR, PV)) return st;
   if (d->refine->rects || d->verify->rects) { set_error("%s: rects must be NULL: the rects are the rendered ones", what); return LMX_ERR_INVALID_ARG; }
   if (d->trace_min != d->trace_min) { set_error("%s: trace_min is not a number", what); return LMX_ERR_INVALID_ARG; }
   if (model->device != t->device) { set_error("%s: the model lives on device %d, the depth templates on device %d", what, model->device, t->device); return LMX_ERR_INVALID_ARG; }
@@ -2165,42 +2186,31 @@ lmx_status rough_check(const char* what, lmx_depth_templates* t, lmx_rough_model
   return LMX_OK;
 }
 
-// As chain_queue: the waits, the stage, the two pose kernels, the records behind them.
+// As chain_queue: chain_begin, the stage, the two pose kernels, chain_end; and the model's own record, in front of and behind its kernels.
 lmx_status rough_queue(lmx_depth_templates* t, lmx_rough_model* model, const lmx_rough_chain_desc& d, const lmx::pr::Params& PR, const lmx::pv::Params& PV, hipStream_t user,
                        bool with_user) {
   using namespace lmx;
   if (lmx_status st = t->ensure_device()) return st;
-  if (!t->export_read) DV_HIP(hipEventCreateWithFlags(&t->export_read, hipEventDisableTiming));
-  if (!t->chain_src_ready) DV_HIP(hipEventCreateWithFlags(&t->chain_src_ready, hipEventDisableTiming));
+  if (lmx_status st = chain_begin(t, user, with_user)) return st;
   hipStream_t s = t->s;
-  if (with_user) {
-    DV_HIP(hipEventRecord(t->chain_src_ready, user));
-    DV_HIP(hipStreamWaitEvent(s, t->chain_src_ready, 0));
-  }
-  if (t->export_read_pending) DV_HIP(hipStreamWaitEvent(s, t->export_read, 0));
-  DV_HIP(hipStreamWaitEvent(s, t->scene_ready, 0));
-  if (model->done_pending) DV_HIP(hipStreamWaitEvent(s, model->done, 0));   // the model's arena serves one call at a time
+  if (model->done_pending) HIP_RETURN(hipStreamWaitEvent(s, model->done, 0));   // the model's arena serves one call at a time
   rp::StageArgs a;
-  a.L = pc::Lists{d.header, d.frame_info, d.n_frames, reinterpret_cast<const pc::Match*>(d.matches), reinterpret_cast<const pc::Cluster*>(d.clusters), d.members,
-                  (uint64_t)d.cap_matches, (uint64_t)d.cap_clusters, (uint64_t)d.cap_members};
+  a.L = chain_lists(d);
   a.class_index = d.class_index; a.trace_min = d.trace_min; a.chain_header = d.chain_header;
   a.rough = reinterpret_cast<rp::Record*>(d.rough); a.member_group = d.member_group;
-  DV_HIP(hipMemsetAsync(d.chain_header, 0, pc::C_WORDS * sizeof(uint32_t), s));
+  HIP_RETURN(hipMemsetAsync(d.chain_header, 0, pc::C_WORDS * sizeof(uint32_t), s));
   launch_rough_stage(s, model, a);
-  DV_HIP(hipGetLastError());
+  HIP_RETURN(hipGetLastError());
   const RoughChainArgs c = {d.header, (uint64_t)d.cap_clusters, model->d_jobs, reinterpret_cast<const DepthCrop*>(model->d_crops), model->cap_slots, t->d_scene,
                             d.n_frames, t->scene_W, t->scene_H, d.chain_header, d.poses, d.checks, d.keep, d.keep_thresh};
   const dim3 grid((unsigned)d.cap_clusters), block(256);
   hipLaunchKernelGGL(k_rough_refine_clusters, grid, block, 0, s, c, PR);
-  DV_HIP(hipGetLastError());
+  HIP_RETURN(hipGetLastError());
   hipLaunchKernelGGL(k_rough_verify_clusters, grid, block, 0, s, c, PV);
-  DV_HIP(hipGetLastError());
-  DV_HIP(hipEventRecord(t->export_read, s));
-  t->export_read_pending = true;
-  DV_HIP(hipEventRecord(model->done, s));
+  HIP_RETURN(hipGetLastError());
+  HIP_RETURN(hipEventRecord(model->done, s));
   model->done_pending = true;
-  if (with_user) DV_HIP(hipStreamWaitEvent(user, t->export_read, 0));
-  return LMX_OK;
+  return chain_end(t, user, with_user);
 }
 }  // namespace
 
@@ -2216,9 +2226,7 @@ extern "C" lmx_status lmx_rough_pose_chain_on(lmx_depth_templates* t, lmx_rough_
     if (lmx_status st = rough_check(what, t, model, d, &PR, &PV)) return st;
     if (lmx_status st = t->ensure_device()) return st;
     hipStream_t user = static_cast<hipStream_t>(stream);
-    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    if (user && hipStreamIsCapturing(user, &capturing) != hipSuccess) { (void)hipGetLastError(); set_error("%s: invalid stream", what); return LMX_ERR_INVALID_ARG; }
-    if (capturing != hipStreamCaptureStatusNone) { set_error("%s: the stream is being captured into a graph", what); return LMX_ERR_INVALID_ARG; }
+    if (lmx_status st = check_user_stream(what, user)) return st;
     const struct { const char* name; const void* p; size_t align; } arrays[] = {
         {"header", d->header, 4}, {"frame_info", d->frame_info, 4}, {"matches", d->matches, 4}, {"clusters", d->clusters, 8}, {"members", d->members, 4},
         {"chain_header", d->chain_header, 4}, {"rough", d->rough, 8}, {"member_group", d->member_group, 4}, {"poses", d->poses, 8}, {"checks", d->checks, 8},
@@ -2245,26 +2253,20 @@ extern "C" lmx_status lmx_debug_rough_pose_chain(lmx_depth_templates* t, lmx_rou
     if (lmx_status st = t->ensure_device()) return st;
     hipStream_t s = t->s;
     const size_t C = d->cap_clusters;
-    // five inputs (uploaded), six outputs (uploaded and read back; chain_header is zeroed by the call)
-    struct Arr { const void* host; size_t bytes; DeviceBuffer dev; };
-    Arr arr[11] = {{d->header, xpack::H_WORDS * sizeof(uint32_t), {}}, {d->frame_info, (size_t)d->n_frames * xpack::I_WORDS * sizeof(int32_t), {}},
-                   {d->matches, d->cap_matches * sizeof(lmx_match_t), {}}, {d->clusters, C * sizeof(lmx_cluster_t), {}}, {d->members, d->cap_members * sizeof(int32_t), {}},
-                   {d->chain_header, pc::C_WORDS * sizeof(uint32_t), {}}, {d->rough, C * sizeof(lmx_rough_pose_t), {}}, {d->member_group, d->cap_members * sizeof(int32_t), {}},
-                   {d->poses, C * sizeof(lmx_pose_refine_t), {}}, {d->checks, C * sizeof(lmx_pose_verify_t), {}}, {d->keep, C, {}}};
-    for (Arr& x : arr) {
-      DV_HIP(hipMalloc(&x.dev.p, std::max<size_t>(x.bytes, 16)));
-      if (x.bytes) DV_HIP(hipMemcpyAsync(x.dev.p, x.host, x.bytes, hipMemcpyHostToDevice, s));
-    }
+    // five inputs, six outputs (chain_header is zeroed by the call)
+    const HookArray arr[11] = {{d->header, xpack::H_WORDS * sizeof(uint32_t), false}, {d->frame_info, (size_t)d->n_frames * xpack::I_WORDS * sizeof(int32_t), false},
+                               {d->matches, d->cap_matches * sizeof(lmx_match_t), false}, {d->clusters, C * sizeof(lmx_cluster_t), false},
+                               {d->members, d->cap_members * sizeof(int32_t), false}, {d->chain_header, pc::C_WORDS * sizeof(uint32_t), true},
+                               {d->rough, C * sizeof(lmx_rough_pose_t), true}, {d->member_group, d->cap_members * sizeof(int32_t), true},
+                               {d->poses, C * sizeof(lmx_pose_refine_t), true}, {d->checks, C * sizeof(lmx_pose_verify_t), true}, {d->keep, C, true}};
+    HookArrays<11> h;
+    if (lmx_status st = h.upload(arr, s)) return st;
     lmx_rough_chain_desc dd = *d;
-    dd.header = arr[0].dev.as<uint32_t>(); dd.frame_info = arr[1].dev.as<int32_t>(); dd.matches = arr[2].dev.as<lmx_match_t>();
-    dd.clusters = arr[3].dev.as<lmx_cluster_t>(); dd.members = arr[4].dev.as<int32_t>(); dd.chain_header = arr[5].dev.as<uint32_t>();
-    dd.rough = arr[6].dev.as<lmx_rough_pose_t>(); dd.member_group = arr[7].dev.as<int32_t>(); dd.poses = arr[8].dev.as<lmx_pose_refine_t>();
-    dd.checks = arr[9].dev.as<lmx_pose_verify_t>(); dd.keep = arr[10].dev.as<uint8_t>();
-    lmx_status st = rough_queue(t, model, dd, PR, PV, nullptr, false);
-    if (st == LMX_OK)
-      for (int k = 5; k < 11; ++k)
-        if (arr[k].bytes) DV_HIP(hipMemcpyAsync(const_cast<void*>(arr[k].host), arr[k].dev.p, arr[k].bytes, hipMemcpyDeviceToHost, s));
-    DV_HIP(hipStreamSynchronize(s));   // the scratch buffers go when this returns
+    dd.header = h.at<uint32_t>(0); dd.frame_info = h.at<int32_t>(1); dd.matches = h.at<lmx_match_t>(2); dd.clusters = h.at<lmx_cluster_t>(3);
+    dd.members = h.at<int32_t>(4); dd.chain_header = h.at<uint32_t>(5); dd.rough = h.at<lmx_rough_pose_t>(6); dd.member_group = h.at<int32_t>(7);
+    dd.poses = h.at<lmx_pose_refine_t>(8); dd.checks = h.at<lmx_pose_verify_t>(9); dd.keep = h.at<uint8_t>(10);
+    const lmx_status st = rough_queue(t, model, dd, PR, PV, nullptr, false);
+    if (lmx_status e = h.finish(s, st == LMX_OK)) return e;
     t->export_read_pending = false;
     model->done_pending = false;
     return st;

@@ -4,13 +4,15 @@ DepthTemplates.debug_rough_pose_chain and RoughModel.debug_crop.  Nothing here h
   the records and member groups    equal the CPU build of the header on every case of tests/rough_pose_cases.py, byte for byte
   the render                       equals lmx_mesh_render (itself pinned to meshraster.c) at the record's view
   the poses, checks, keep          equal the existing refine_poses -> verify_poses -> keep_verified on the read-back crops and rects
-Frames of 96 x 72, a 12-triangle box and a tetrahedron, 16 slots, a window of 64 x 64."""
+Frames of 96 x 72, a 12-triangle box and a tetrahedron, 16 slots, a window of 64 x 64; and the constructed meshes of tests/mesh_cases.py
+that fill more than one staging chunk, on their own 75 x 41 camera."""
 import ctypes as C
 
 import numpy as np
 import pytest
 import torch
 
+import mesh_cases as mc
 import pose_chain_cases as pcc
 import pose_refine_cases as prc
 import pose_verify_cases as pvc
@@ -140,6 +142,41 @@ def test_render_equals_lmx_mesh_render(blank, mesh, cam):
         assert not outside.any() and rough["n_model"][k] == np.count_nonzero(depth[0]) > 0, k
         touches = touches or x == 0 or y + h == H
     assert touches == (cam != CAM)
+
+
+@pytest.mark.parametrize("name", ["roof_ab_after_255", "roof_ab_after_256", "roof_fan_600_order_0"])
+def test_render_of_constructed_meshes_equals_lmx_mesh_render(blank, name):
+    """More than one staging chunk of 256 records in k_rough_raster (the box and the tetrahedron never fill one): the roof whose two faces
+    sit at the indices 255, 256 (the last slot of chunk 0 and the first of chunk 1) and 256, 257, and 600 faces on one ridge (three
+    chunks, hits in every wave).  One view, the identity at distance 1; one cluster of one match, so the slot's view is that view bit for
+    bit (the mean of one unit quaternion: the CPU build of the header, rough_pose_cases.run_host, gives the same), and the window is the whole 75 x 41
+    frame.  The render equals lmx_mesh_render's at the record's view and meshraster.c's (mesh_cases.constructed_expected) on every pixel,
+    the ridge's 33 exact z ties included.  What this can show is a record that is never walked or staged in a wrong slot (a walk that stops
+    after its first chunk fails all three cases).  Which face wins a tie it cannot show: this path stores depth alone, and equal z is equal
+    depth (a walk that lets the higher index win, or stages the waves in reverse order, passes; tests/test_gpu_mesh_render_constructed.py
+    sees both through the gray of the same shared walk)."""
+    _, tri, cam, _ = next(c for c in mc.constructed_cases() if c[0] == name)
+    Wc, Hc, camt = cam["width"], cam["height"], (cam["fx"], cam["fy"], cam["cx"], cam["cy"])
+    views = rpc.Views([np.eye(3)], 1.0)
+    L = rpc.members_lists([[0]], extra_front=False, tail_frame=True)
+    model = RoughModel(tri, views.pairs(), Wc, Hc, *camt, D=views.D, ori_dists=views.ori_dist, cap_slots=4, max_window=(Wc, Hc))
+    try:
+        hdr, rough, _, _, _, _ = run_hook(blank, model, L, rpc.trace_min_of(5.0), room=0, model_camera=camt, scene_camera=camt)
+        crop, rect = model.debug_crop(0)
+    finally:
+        model.close()
+    assert hdr[0] == 1 and hdr[1] == 0 and hdr[5] == 1 and rough["status"][0] == OK
+    assert rough["R"][0].tobytes() == np.eye(3).tobytes() and rough["distance"][0] == 1.0
+    _, depth, _, rects = render_views(tri, [(rough["R"][0].reshape(3, 3), float(rough["distance"][0]))], Wc, Hc, *camt)
+    x, y, w, h = (int(v) for v in rects[0])
+    assert rect.tolist() == [x, y, w, h] == rough["rect"][0].tolist(), (rect, rects[0])
+    assert crop.tobytes() == np.ascontiguousarray(depth[0, y:y + h, x:x + w]).tobytes()
+    assert rough["n_model"][0] == np.count_nonzero(depth[0]) > 0
+    want = mc.constructed_expected(name)[1][0]
+    rows, col = slice(mc.ROOF_ROWS[0], mc.ROOF_ROWS[1] + 1), mc.ROOF_COLUMN
+    assert x <= col < x + w and y <= rows.start and rows.stop <= y + h and want[rows, col].all()
+    assert np.array_equal(crop[rows.start - y:rows.stop - y, col - x], want[rows, col])        # the ridge: the lower-indexed face's depth
+    assert np.array_equal(crop, want[y:y + h, x:x + w]) and np.count_nonzero(want) == rough["n_model"][0]
 
 
 # ---- the chain -----------------------------------------------------------------------------------------------------------------------------------
