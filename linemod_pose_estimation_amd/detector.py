@@ -6,6 +6,7 @@
   detector.classIds(), getTemplates(), numTemplates(), getT(), pyramidLevels()
 Everything computes through the C ABI of liblmx.so (include/lmx.h) on a gfx950 device; there is no CPU path here.
 """
+import copy
 import ctypes as C
 from collections.abc import Mapping
 
@@ -17,6 +18,12 @@ from .bank import TemplateBank
 MATCH_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("similarity", "<f4"), ("template_id", "<i4"), ("class_index", "<i4")])
 RAW_MATCH_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("similarity", "<f4"), ("template_id", "<i4"),
                             ("class_index", "<i4"), ("frame", "<i4"), ("order_key", "<u8")])
+CLUSTER_DTYPE = np.dtype([("index", "<i4", (3,)), ("rect", "<i4", (4,)), ("score", "<f8"), ("member_begin", "<i4"), ("member_count", "<i4")],
+                         align=True)
+DEPTH_DIFF_DTYPE = np.dtype([("sum_abs_mm", "<i8"), ("n_valid", "<i4"), ("n_template", "<i4")])
+NORMAL_DIFF_DTYPE = np.dtype([("sum_angle_urad", "<i8"), ("n_normal", "<i4"), ("reserved", "<i4")])
+# the host lists of the collect_clusters* calls and of the debug_device_finalize_cluster* hooks, by the short names their helpers take
+_LIST_DTYPES = {"m": MATCH_DTYPE, "d": DEPTH_DIFF_DTYPE, "nd": NORMAL_DIFF_DTYPE, "cl": CLUSTER_DTYPE, "cc": np.int32, "mem": np.int32}
 
 
 def _images(frames):
@@ -120,6 +127,77 @@ EXPORT_DELIVERED, EXPORT_UNFINISHED, EXPORT_RANGE, EXPORT_MATCHES_NO_FIT, EXPORT
 EXPORT_FLAG_OVERFLOW, EXPORT_FLAG_UNFINISHED, EXPORT_FLAG_NO_FIT = 1, 2, 4
 
 
+def _entry(shape, dtype, align, cap):
+    """One array of a layout, as export_layout describes it."""
+    return {"shape": shape, "dtype": dtype, "nbytes": int(np.prod(shape)) * np.dtype(dtype).itemsize, "align": align, "cap": cap}
+
+
+def _records(t, n, dtype):
+    """The first n records of the tensor t (on the GPU or the CPU; a record is a row, or an element of a 1-D tensor) -> numpy array [n]
+    of `dtype`, whose itemsize is the record's."""
+    return np.ascontiguousarray(t[:n].cpu().numpy()).view(dtype).reshape(-1)
+
+
+def _torch_stream(stream, default, device):
+    """The stream argument of the export and chain calls -> a torch stream: a torch stream as it is, a raw hipStream_t wrapped; None:
+    `default`, or without one the current torch stream of `device`."""
+    import torch
+    if stream is None:
+        return default if default is not None else torch.cuda.current_stream(device)
+    return stream if hasattr(stream, "cuda_stream") else torch.cuda.ExternalStream(int(stream), device=device)
+
+
+class _Exported:
+    """What the Exported* classes share: tensors allocated from a layout on a stream (`_backing`, name -> tensor), the named views of them
+    that a subclass's _views() binds, and the copy."""
+
+    def _allocate(self, lay, stream, device):
+        import torch
+        self.stream = stream
+        with torch.cuda.stream(stream):     # the caching allocator hands out memory that is free on this stream
+            self._backing = {k: torch.empty(v["shape"], dtype=getattr(torch, v["dtype"]), device="cuda:%d" % device) for k, v in lay.items()}
+        self._views()
+
+    @property
+    def similarity(self):
+        import torch
+        return self.matches[:, 2].view(torch.float32)
+
+    def _delivered(self):
+        """Synchronises `stream` -> (an export's frame_info on the host, how many matches, clusters and members its tensors hold)."""
+        self.stream.synchronize()
+        return self.frame_info.cpu().numpy(), tuple(min(int(v), cap) for v, cap in zip(self.header[2:5].cpu().numpy(), self.caps))
+
+    def _live(self):
+        """Synchronises `stream` -> (a chain's chain_header as int64 [8], how many of its slots the tensors hold)."""
+        self.stream.synchronize()
+        hdr = self.chain_header.cpu().numpy().view(np.uint32).astype(np.int64)
+        return hdr, min(int(hdr[0]), self.cap)
+
+    def clone(self):
+        """A copy made on `stream` (behind the call that wrote these tensors, in front of whatever writes them next): what a pipeline
+        keeps of a result whose buffers the next call with out=... reuses.  Nothing waits on the host."""
+        import torch
+        out = copy.copy(self)       # the plain attributes; the tensors are replaced below
+        with torch.cuda.stream(self.stream):
+            out._backing = {k: v.clone() for k, v in self._backing.items()}
+        out._views()
+        return out
+
+    @classmethod
+    def _fresh_or(cls, out, made_for, caps, stream, device):
+        """What an export writes and the capacities it may use.  out None: a fresh object for `made_for`, the constructor's arguments in
+        front of caps, with its own capacities; else `out`, which must have been made for the same, with the smaller of `caps` and its
+        own, and `stream` from now on."""
+        if out is None:
+            out = cls(*made_for, caps, stream, device)
+            return out, out.caps
+        if out._made_for() != made_for:
+            raise ValueError(cls.MADE_FOR % out._made_for())
+        out.stream = stream
+        return out, tuple(min(int(a), b) for a, b in zip(caps, out.caps))
+
+
 def export_layout(n_frames, clusters=False, caps=(1 << 16, 4096, 1 << 16)):
     """The device arrays lmx_ctx_export_matches_on fills, as Detector.export_matches allocates them: name -> {"shape", "dtype" (a numpy
     dtype name, the torch dtype of the same name), "nbytes", "align" (of the address, the C ABI's rule), "cap" (elements the call may
@@ -131,19 +209,16 @@ def export_layout(n_frames, clusters=False, caps=(1 << 16, 4096, 1 << 16)):
         raise ValueError("n_frames must be at least 1")
     if len(caps) != 3 or min(caps) < 0 or max(caps) >= 1 << 31:
         raise ValueError("caps = (cap_matches, cap_clusters, cap_members), each 0 .. 2^31 - 1")
-
-    def entry(shape, dtype, align, cap):
-        return {"shape": shape, "dtype": dtype, "nbytes": int(np.prod(shape)) * np.dtype(dtype).itemsize, "align": align, "cap": cap}
-    out = {"header": entry((EXPORT_HEADER_WORDS,), "int32", 4, EXPORT_HEADER_WORDS),
-           "frame_info": entry((int(n_frames), EXPORT_INFO_WORDS), "int32", 4, int(n_frames)),
-           "matches": entry((max(caps[0], 1), MATCH_DTYPE.itemsize // 4), "int32", 4, caps[0])}
+    out = {"header": _entry((EXPORT_HEADER_WORDS,), "int32", 4, EXPORT_HEADER_WORDS),
+           "frame_info": _entry((int(n_frames), EXPORT_INFO_WORDS), "int32", 4, int(n_frames)),
+           "matches": _entry((max(caps[0], 1), MATCH_DTYPE.itemsize // 4), "int32", 4, caps[0])}
     if clusters:
-        out["clusters"] = entry((max(caps[1], 1), CLUSTER_DTYPE.itemsize), "uint8", 8, caps[1])
-        out["members"] = entry((max(caps[2], 1),), "int32", 4, caps[2])
+        out["clusters"] = _entry((max(caps[1], 1), CLUSTER_DTYPE.itemsize), "uint8", 8, caps[1])
+        out["members"] = _entry((max(caps[2], 1),), "int32", 4, caps[2])
     return out
 
 
-class ExportedMatches:
+class ExportedMatches(_Exported):
     """What Detector.export_matches leaves on the GPU (lmx_ctx_export_matches_on): torch tensors on the context's device, valid for work
     queued on `stream` after the call --
       header      int32 [16]      [0] n_frames, [1] flags, [2] matches, [3] clusters, [4] members (true totals), [5] candidates, [6] raw records
@@ -152,49 +227,31 @@ class ExportedMatches:
       clusters    uint8 [cap, 48] lmx_cluster_t records (CLUSTER_DTYPE); members int32 [cap]   (None without clusters=True)
     Any other stream, or the host, synchronises with `stream` first; to_host() does."""
 
+    MADE_FOR = "out was made for %d frames, clusters=%s"
+
     def __init__(self, n_frames, clusters, caps, stream, device):
-        import torch
-        self.n_frames, self.with_clusters, self.stream = n_frames, bool(clusters), stream
+        self.n_frames, self.with_clusters = n_frames, bool(clusters)
         lay = export_layout(n_frames, clusters, caps)
-        with torch.cuda.stream(stream):     # the caching allocator hands out memory that is free on this stream
-            t = {k: torch.empty(v["shape"], dtype=getattr(torch, v["dtype"]), device="cuda:%d" % device) for k, v in lay.items()}
-        self._backing = t
         self.caps = tuple(lay[k]["cap"] if k in lay else 0 for k in ("matches", "clusters", "members"))
-        self.header, self.frame_info = t["header"], t["frame_info"]
-        self.matches = t["matches"][:self.caps[0]]
-        self.clusters = t["clusters"][:self.caps[1]] if clusters else None
-        self.members = t["members"][:self.caps[2]] if clusters else None
+        self._allocate(lay, stream, device)
 
-    @property
-    def similarity(self):
-        import torch
-        return self.matches[:, 2].view(torch.float32)
+    def _made_for(self):
+        return self.n_frames, self.with_clusters
 
-    def clone(self):
-        """A copy made on `stream` (behind the export, in front of whatever writes these tensors next): what a pipeline keeps of a result
-        whose buffers the next export(out=...) reuses.  Nothing waits on the host."""
-        import torch
-        out = ExportedMatches.__new__(ExportedMatches)
-        out.n_frames, out.with_clusters, out.stream, out.caps = self.n_frames, self.with_clusters, self.stream, self.caps
-        with torch.cuda.stream(self.stream):
-            out._backing = {k: v.clone() for k, v in self._backing.items()}
-        t = out._backing
-        out.header, out.frame_info, out.matches = t["header"], t["frame_info"], t["matches"][:self.caps[0]]
-        out.clusters = t["clusters"][:self.caps[1]] if self.with_clusters else None
-        out.members = t["members"][:self.caps[2]] if self.with_clusters else None
-        return out
+    def _views(self):
+        t, caps = self._backing, self.caps
+        self.header, self.frame_info, self.matches = t["header"], t["frame_info"], t["matches"][:caps[0]]
+        self.clusters = t["clusters"][:caps[1]] if self.with_clusters else None
+        self.members = t["members"][:caps[2]] if self.with_clusters else None
 
     def to_host(self):
         """Synchronises `stream` -> list per frame of (matches, clusters, members) in collect_clusters' dtypes (MATCH_DTYPE, CLUSTER_DTYPE
         whose member_begin indexes `members`, the batch's flat int32 member array; both empty without clusters=True), or None for a frame
         whose status is not 0 (not finished, or an array of its did not fit)."""
-        self.stream.synchronize()
-        info = self.frame_info.cpu().numpy()
-        n_m, n_c, n_mem = (int(v) for v in self.header[2:5].cpu().numpy())
-        m = np.ascontiguousarray(self.matches[:min(n_m, self.caps[0])].cpu().numpy()).view(MATCH_DTYPE).reshape(-1)
+        info, (n_m, n_c, n_mem) = self._delivered()
+        m = _records(self.matches, n_m, MATCH_DTYPE)
         if self.with_clusters:
-            cl = np.ascontiguousarray(self.clusters[:min(n_c, self.caps[1])].cpu().numpy()).view(CLUSTER_DTYPE).reshape(-1)
-            mem = np.ascontiguousarray(self.members[:min(n_mem, self.caps[2])].cpu().numpy())
+            cl, mem = _records(self.clusters, n_c, CLUSTER_DTYPE), _records(self.members, n_mem, np.int32)
         else:
             cl, mem = np.zeros(0, CLUSTER_DTYPE), np.zeros(0, np.int32)
         out = []
@@ -211,21 +268,17 @@ def export_clusters_layout(n_frames, score=0, classes=False, caps=(1 << 16, 4096
     if score not in (0, 1, 2):
         raise ValueError("score is 0 (mean similarity), 1 (depth) or 2 (depth + normal)")
     out = export_layout(n_frames, True, caps)
-
-    def side(parent, shape_tail, dtype, align):
-        cap = out[parent]["cap"]
-        shape = (max(cap, 1),) + shape_tail
-        return {"shape": shape, "dtype": dtype, "nbytes": int(np.prod(shape)) * np.dtype(dtype).itemsize, "align": align, "cap": cap}
+    cap_m, cap_c = out["matches"]["cap"], out["clusters"]["cap"]
     if score >= 1:
-        out["diffs"] = side("matches", (DEPTH_DIFF_DTYPE.itemsize // 8,), "int64", 8)
+        out["diffs"] = _entry((max(cap_m, 1), DEPTH_DIFF_DTYPE.itemsize // 8), "int64", 8, cap_m)
     if score == 2:
-        out["ndiffs"] = side("matches", (NORMAL_DIFF_DTYPE.itemsize // 8,), "int64", 8)
+        out["ndiffs"] = _entry((max(cap_m, 1), NORMAL_DIFF_DTYPE.itemsize // 8), "int64", 8, cap_m)
     if classes:
-        out["cluster_class"] = side("clusters", (), "int32", 4)
+        out["cluster_class"] = _entry((max(cap_c, 1),), "int32", 4, cap_c)
     return out
 
 
-class ExportedClusters:
+class ExportedClusters(_Exported):
     """What Detector.export_clusters leaves on the GPU (lmx_ctx_export_clusters_on): ExportedMatches' tensors with clusters, and next to
     them, on the same device and valid for work queued on `stream` after the call --
       diffs          int64 [cap, 2]  lmx_depth_diff_t records (DEPTH_DIFF_DTYPE) parallel to matches            (None with score 0)
@@ -233,15 +286,16 @@ class ExportedClusters:
       cluster_class  int32 [cap]     the class of each cluster, parallel to clusters                           (None without classes)
     A frame's range of diffs / ndiffs is written iff its matches are, of cluster_class iff its clusters are."""
 
+    MADE_FOR = "out was made for %d frames, score %d, classes=%s"
+
     def __init__(self, n_frames, score, classes, caps, stream, device):
-        import torch
-        self.n_frames, self.score, self.with_classes, self.stream = n_frames, int(score), bool(classes), stream
+        self.n_frames, self.score, self.with_classes = n_frames, int(score), bool(classes)
         lay = export_clusters_layout(n_frames, score, classes, caps)
-        with torch.cuda.stream(stream):     # the caching allocator hands out memory that is free on this stream
-            t = {k: torch.empty(v["shape"], dtype=getattr(torch, v["dtype"]), device="cuda:%d" % device) for k, v in lay.items()}
-        self._backing = t
         self.caps = tuple(lay[k]["cap"] for k in ("matches", "clusters", "members"))
-        self._views()
+        self._allocate(lay, stream, device)
+
+    def _made_for(self):
+        return self.n_frames, self.score, self.with_classes
 
     def _views(self):
         t, caps = self._backing, self.caps
@@ -251,35 +305,17 @@ class ExportedClusters:
         self.ndiffs = t["ndiffs"][:caps[0]] if "ndiffs" in t else None
         self.cluster_class = t["cluster_class"][:caps[1]] if "cluster_class" in t else None
 
-    @property
-    def similarity(self):
-        import torch
-        return self.matches[:, 2].view(torch.float32)
-
-    def clone(self):
-        """A copy made on `stream`, as ExportedMatches.clone."""
-        import torch
-        out = ExportedClusters.__new__(ExportedClusters)
-        out.n_frames, out.score, out.with_classes, out.stream, out.caps = self.n_frames, self.score, self.with_classes, self.stream, self.caps
-        with torch.cuda.stream(self.stream):
-            out._backing = {k: v.clone() for k, v in self._backing.items()}
-        out._views()
-        return out
-
     def to_host(self):
         """Synchronises `stream` -> list per frame of (matches, diffs, ndiffs, clusters, cluster_class, members) in
         collect_clusters_classes' shape and dtypes (diffs / ndiffs / cluster_class None where the call has none; CLUSTER_DTYPE's
         member_begin indexes `members`, the batch's flat member array), or None for a frame whose status is not 0."""
-        self.stream.synchronize()
-        info = self.frame_info.cpu().numpy()
-        n_m, n_c, n_mem = (int(v) for v in self.header[2:5].cpu().numpy())
-        n_m, n_c, n_mem = min(n_m, self.caps[0]), min(n_c, self.caps[1]), min(n_mem, self.caps[2])
-        m = np.ascontiguousarray(self.matches[:n_m].cpu().numpy()).view(MATCH_DTYPE).reshape(-1)
-        d = np.ascontiguousarray(self.diffs[:n_m].cpu().numpy()).view(DEPTH_DIFF_DTYPE).reshape(-1) if self.diffs is not None else None
-        nd = np.ascontiguousarray(self.ndiffs[:n_m].cpu().numpy()).view(NORMAL_DIFF_DTYPE).reshape(-1) if self.ndiffs is not None else None
-        cl = np.ascontiguousarray(self.clusters[:n_c].cpu().numpy()).view(CLUSTER_DTYPE).reshape(-1)
-        cc = np.ascontiguousarray(self.cluster_class[:n_c].cpu().numpy()) if self.cluster_class is not None else None
-        mem = np.ascontiguousarray(self.members[:n_mem].cpu().numpy())
+        info, (n_m, n_c, n_mem) = self._delivered()
+        m = _records(self.matches, n_m, MATCH_DTYPE)
+        d = _records(self.diffs, n_m, DEPTH_DIFF_DTYPE) if self.diffs is not None else None
+        nd = _records(self.ndiffs, n_m, NORMAL_DIFF_DTYPE) if self.ndiffs is not None else None
+        cl = _records(self.clusters, n_c, CLUSTER_DTYPE)
+        cc = _records(self.cluster_class, n_c, np.int32) if self.cluster_class is not None else None
+        mem = _records(self.members, n_mem, np.int32)
         out = []
         for f in range(self.n_frames):
             mb, mc, cb, ncl, _, _, status, _ = (int(v) for v in info[f])
@@ -301,17 +337,14 @@ def pose_chain_layout(cap_clusters):
     cap = int(cap_clusters)
     if cap < 1 or cap > 1 << 20:
         raise ValueError("cap_clusters must be 1 .. 2^20")
-
-    def entry(shape, dtype, align, n):
-        return {"shape": shape, "dtype": dtype, "nbytes": int(np.prod(shape)) * np.dtype(dtype).itemsize, "align": align, "cap": n}
-    return {"chain_header": entry((POSE_CHAIN_HEADER_WORDS,), "int32", 4, POSE_CHAIN_HEADER_WORDS),
-            "leaders": entry((cap,), "int32", 4, cap),
-            "poses": entry((cap, POSE_REFINE_DTYPE.itemsize // 8), "int64", 8, cap),
-            "checks": entry((cap, POSE_VERIFY_DTYPE.itemsize // 8), "int64", 8, cap),
-            "keep": entry((cap,), "uint8", 1, cap)}
+    return {"chain_header": _entry((POSE_CHAIN_HEADER_WORDS,), "int32", 4, POSE_CHAIN_HEADER_WORDS),
+            "leaders": _entry((cap,), "int32", 4, cap),
+            "poses": _entry((cap, POSE_REFINE_DTYPE.itemsize // 8), "int64", 8, cap),
+            "checks": _entry((cap, POSE_VERIFY_DTYPE.itemsize // 8), "int64", 8, cap),
+            "keep": _entry((cap,), "uint8", 1, cap)}
 
 
-class ExportedPoses:
+class ExportedPoses(_Exported):
     """What DepthTemplates.pose_chain leaves on the GPU (lmx_pose_chain_on): torch tensors on the object's device, parallel to the
     clusters of the export they were computed from, valid for work queued on `stream` after the call --
       chain_header  int32 [8]       [0] n_live, [1] flags, [2] slots refined, [3] verified OK, [4] kept
@@ -321,36 +354,26 @@ class ExportedPoses:
       keep          uint8 [cap]     the erase rule of keep_verified
     Entries at or above n_live are not written.  Any other stream, or the host, synchronises with `stream` first; to_host() does."""
 
-    def __init__(self, cap_clusters, stream, device):
-        import torch
-        self.stream = stream
-        lay = pose_chain_layout(cap_clusters)
-        with torch.cuda.stream(stream):     # the caching allocator hands out memory that is free on this stream
-            t = {k: torch.empty(v["shape"], dtype=getattr(torch, v["dtype"]), device="cuda:%d" % device) for k, v in lay.items()}
-        self._backing = t
-        self.cap = lay["leaders"]["cap"]
-        self.chain_header, self.leaders, self.poses, self.checks, self.keep = (t[k] for k in ("chain_header", "leaders", "poses", "checks", "keep"))
+    NAMES = ("chain_header", "leaders", "poses", "checks", "keep")
 
-    def clone(self):
-        """A copy made on `stream`, as ExportedMatches.clone: what a pipeline keeps of a result whose tensors the next pose_chain(out=...)
-        writes again."""
-        import torch
-        out = ExportedPoses.__new__(ExportedPoses)
-        out.stream, out.cap = self.stream, self.cap
-        with torch.cuda.stream(self.stream):
-            out._backing = {k: v.clone() for k, v in self._backing.items()}
-        t = out._backing
-        out.chain_header, out.leaders, out.poses, out.checks, out.keep = (t[k] for k in ("chain_header", "leaders", "poses", "checks", "keep"))
-        return out
+    def __init__(self, cap_clusters, stream, device):
+        lay = pose_chain_layout(cap_clusters)
+        self.cap = lay["leaders"]["cap"]
+        self._allocate(lay, stream, device)
+
+    def _views(self):
+        self.chain_header, self.leaders, self.poses, self.checks, self.keep = (self._backing[k] for k in self.NAMES)
+
+    def _fits(self, caps):
+        if self.cap < caps[1]:
+            raise ValueError("out was made for %d clusters, the export holds up to %d" % (self.cap, caps[1]))
 
     def to_host(self):
         """Synchronises `stream` -> (chain_header int64 [8], leaders int32 [n_live], poses POSE_REFINE_DTYPE [n_live], checks
         POSE_VERIFY_DTYPE [n_live], keep bool [n_live])."""
-        self.stream.synchronize()
-        hdr = self.chain_header.cpu().numpy().view(np.uint32).astype(np.int64)
-        n = min(int(hdr[0]), self.cap)
-        return (hdr, self.leaders[:n].cpu().numpy(), np.ascontiguousarray(self.poses[:n].cpu().numpy()).view(POSE_REFINE_DTYPE).reshape(-1),
-                np.ascontiguousarray(self.checks[:n].cpu().numpy()).view(POSE_VERIFY_DTYPE).reshape(-1), self.keep[:n].cpu().numpy().astype(bool))
+        hdr, n = self._live()
+        return (hdr, _records(self.leaders, n, np.int32), _records(self.poses, n, POSE_REFINE_DTYPE), _records(self.checks, n, POSE_VERIFY_DTYPE),
+                _records(self.keep, n, np.uint8).astype(bool))
 
 
 # lmx_rough_pose_t; status: the LMX_ROUGH_* values
@@ -375,12 +398,12 @@ def rough_pose_layout(cap_clusters, cap_members):
     lay = pose_chain_layout(cap_clusters)
     cap, n_mem = lay["leaders"]["cap"], max(int(cap_members), 1)
     del lay["leaders"]
-    lay["rough"] = {"shape": (cap, ROUGH_POSE_DTYPE.itemsize // 8), "dtype": "int64", "nbytes": cap * ROUGH_POSE_DTYPE.itemsize, "align": 8, "cap": cap}
-    lay["member_group"] = {"shape": (n_mem,), "dtype": "int32", "nbytes": n_mem * 4, "align": 4, "cap": n_mem}
+    lay["rough"] = _entry((cap, ROUGH_POSE_DTYPE.itemsize // 8), "int64", 8, cap)
+    lay["member_group"] = _entry((n_mem,), "int32", 4, n_mem)
     return lay
 
 
-class ExportedRoughPoses:
+class ExportedRoughPoses(_Exported):
     """What DepthTemplates.rough_pose_chain leaves on the GPU (lmx_rough_pose_chain_on): as ExportedPoses, with
       chain_header  int32 [8]       [0] n_live, [1] flags, [2] slots refined, [3] verified OK, [4] kept, [5] slots of status ROUGH_OK
       rough         int64 [cap, 19] lmx_rough_pose_t records (ROUGH_POSE_DTYPE)
@@ -389,35 +412,23 @@ class ExportedRoughPoses:
     NAMES = ("chain_header", "rough", "member_group", "poses", "checks", "keep")
 
     def __init__(self, cap_clusters, cap_members, stream, device):
-        import torch
-        self.stream = stream
         lay = rough_pose_layout(cap_clusters, cap_members)
-        with torch.cuda.stream(stream):
-            t = {k: torch.empty(v["shape"], dtype=getattr(torch, v["dtype"]), device="cuda:%d" % device) for k, v in lay.items()}
-        self._backing = t
         self.cap, self.cap_members = lay["rough"]["cap"], lay["member_group"]["cap"]
-        self.chain_header, self.rough, self.member_group, self.poses, self.checks, self.keep = (t[k] for k in self.NAMES)
+        self._allocate(lay, stream, device)
 
-    def clone(self):
-        """A copy made on `stream`, as ExportedPoses.clone."""
-        import torch
-        out = ExportedRoughPoses.__new__(ExportedRoughPoses)
-        out.stream, out.cap, out.cap_members = self.stream, self.cap, self.cap_members
-        with torch.cuda.stream(self.stream):
-            out._backing = {k: v.clone() for k, v in self._backing.items()}
-        t = out._backing
-        out.chain_header, out.rough, out.member_group, out.poses, out.checks, out.keep = (t[k] for k in self.NAMES)
-        return out
+    def _views(self):
+        self.chain_header, self.rough, self.member_group, self.poses, self.checks, self.keep = (self._backing[k] for k in self.NAMES)
+
+    def _fits(self, caps):
+        if self.cap < caps[1] or self.cap_members < caps[2]:
+            raise ValueError("out was made for %d clusters and %d members, the export holds up to %d and %d" % (self.cap, self.cap_members, caps[1], caps[2]))
 
     def to_host(self):
         """Synchronises `stream` -> (chain_header int64 [8], rough ROUGH_POSE_DTYPE [n_live], member_group int32 [cap_members], poses
         POSE_REFINE_DTYPE [n_live], checks POSE_VERIFY_DTYPE [n_live], keep bool [n_live])."""
-        self.stream.synchronize()
-        hdr = self.chain_header.cpu().numpy().view(np.uint32).astype(np.int64)
-        n = min(int(hdr[0]), self.cap)
-        return (hdr, np.ascontiguousarray(self.rough[:n].cpu().numpy()).view(ROUGH_POSE_DTYPE).reshape(-1), self.member_group.cpu().numpy(),
-                np.ascontiguousarray(self.poses[:n].cpu().numpy()).view(POSE_REFINE_DTYPE).reshape(-1),
-                np.ascontiguousarray(self.checks[:n].cpu().numpy()).view(POSE_VERIFY_DTYPE).reshape(-1), self.keep[:n].cpu().numpy().astype(bool))
+        hdr, n = self._live()
+        return (hdr, _records(self.rough, n, ROUGH_POSE_DTYPE), _records(self.member_group, self.cap_members, np.int32), _records(self.poses, n, POSE_REFINE_DTYPE),
+                _records(self.checks, n, POSE_VERIFY_DTYPE), _records(self.keep, n, np.uint8).astype(bool))
 
 
 class PreparedBatch:
@@ -684,6 +695,38 @@ def class_thresholds(bank_class_ids, thresholds, class_ids=()):
     return arr, cids, len(visit)
 
 
+def _cluster_params(vote_row_col_step, renderer_radius_min, renderer_radius_step, cluster_size_thresh):
+    return _lib.ClusterParams(int(vote_row_col_step), float(renderer_radius_min), float(renderer_radius_step), int(cluster_size_thresh))
+
+
+def _side_car(obj_origin_dists, rects):
+    """A side-car's per-template arrays -> (float64 [n], int32 [n, 4])."""
+    return np.ascontiguousarray(obj_origin_dists, np.float64).reshape(-1), np.ascontiguousarray(rects, np.int32).reshape(-1, 4)
+
+
+def _class_base(class_base):
+    """The cumulative template counts of the classes joined in one DepthTemplates -> int32 [n_classes + 1]."""
+    base = np.ascontiguousarray(class_base, np.int32).reshape(-1)
+    if len(base) < 2:
+        raise ValueError("class_base must hold one entry per class plus one")
+    return base
+
+
+def _collect_buffers(n_frames, cap_total, names):
+    """The host lists of one collect_clusters* call and their cut per frame.  names: the result tuple in order, of _LIST_DTYPES' keys --
+    "m", "d", "nd" parallel to the matches, "cl", "cc" to the clusters, "mem" flat and returned whole -- or None for a list this call has
+    not.  -> (name -> address of a list of cap_total elements, with "mo" / "co", the size_t [n_frames + 1] offsets of the two families,
+    which the library fills; cut() -> list per frame of the tuple, each range a copy)."""
+    b = {k: np.zeros(cap_total, _LIST_DTYPES[k]) for k in names if k}
+    ptr = {k: a.ctypes.data for k, a in b.items()}
+    ptr["mo"], ptr["co"] = (C.c_size_t * (n_frames + 1))(), (C.c_size_t * (n_frames + 1))()
+
+    def cut():
+        offs = {k: ptr["co"] if k in ("cl", "cc") else ptr["mo"] for k in b}
+        return [tuple(None if k is None else b[k] if k == "mem" else b[k][offs[k][f]:offs[k][f + 1]].copy() for k in names) for f in range(n_frames)]
+    return ptr, cut
+
+
 class Detector:
     """Device-resident detector: a template bank (or one rank's shard of it) in HBM plus per-frame workspaces.
 
@@ -881,66 +924,45 @@ class Detector:
 
     def set_cluster_sidecar(self, obj_origin_dists, rects, vote_row_col_step, renderer_radius_min, renderer_radius_step, cluster_size_thresh=2):
         """Side-car of the device-side consumer chain (lmx_ctx_set_cluster_sidecar): per-template origin distances and rects."""
-        d = np.ascontiguousarray(obj_origin_dists, np.float64)
-        r = np.ascontiguousarray(rects, np.int32).reshape(-1, 4)
-        pp = _lib.ClusterParams(int(vote_row_col_step), float(renderer_radius_min), float(renderer_radius_step), int(cluster_size_thresh))
+        d, r = _side_car(obj_origin_dists, rects)
+        pp = _cluster_params(vote_row_col_step, renderer_radius_min, renderer_radius_step, cluster_size_thresh)
         _lib.check(_lib.lib().lmx_ctx_set_cluster_sidecar(self.h, d.ctypes.data, r.ctypes.data, len(d), C.byref(pp)))
 
     def collect_clusters(self, n_frames, cap_total=1 << 16):
         """Device-side std::sort + std::unique + rcd_voting/filter/scoring/IoU-NMS on the oldest outstanding enqueue
         (lmx_ctx_collect_clusters) -> list per frame of (matches, clusters, members)."""
-        m = np.zeros(cap_total, MATCH_DTYPE)
-        cl = np.zeros(cap_total, CLUSTER_DTYPE)
-        mem = np.zeros(cap_total, np.int32)
-        mo = (C.c_size_t * (n_frames + 1))()
-        co = (C.c_size_t * (n_frames + 1))()
-        _lib.check(_lib.lib().lmx_ctx_collect_clusters(self.h, n_frames, m.ctypes.data, cap_total, mo, cl.ctypes.data, cap_total, co, mem.ctypes.data, cap_total))
-        out = []
-        for f in range(n_frames):
-            c = cl[co[f]:co[f + 1]].copy()
-            out.append((m[mo[f]:mo[f + 1]].copy(), c, mem))
-        return out
+        p, cut = _collect_buffers(n_frames, cap_total, ("m", "cl", "mem"))
+        _lib.check(_lib.lib().lmx_ctx_collect_clusters(self.h, n_frames, p["m"], cap_total, p["mo"], p["cl"], cap_total, p["co"], p["mem"], cap_total))
+        return cut()
 
     def collect_clusters_depth(self, n_frames, templates, class_index=-1, no_value=-np.inf, cap_total=1 << 16):
         """collect_clusters with the clusters ranked by the depth score (lmx_ctx_collect_clusters_depth): `templates` is a DepthTemplates
         whose upload_scene(depth_frames) was called after the enqueue.  -> list per frame of (matches, diffs, clusters, members), equal
         to collect + templates.diff + cluster_matches_scored(depth_values(diffs)) bit for bit; no_value is what a match with nothing to
         compare contributes to its cluster's mean."""
-        m = np.zeros(cap_total, MATCH_DTYPE)
-        d = np.zeros(cap_total, DEPTH_DIFF_DTYPE)
-        cl = np.zeros(cap_total, CLUSTER_DTYPE)
-        mem = np.zeros(cap_total, np.int32)
-        mo = (C.c_size_t * (n_frames + 1))()
-        co = (C.c_size_t * (n_frames + 1))()
-        _lib.check(_lib.lib().lmx_ctx_collect_clusters_depth(self.h, n_frames, templates.h, int(class_index), float(no_value), m.ctypes.data, cap_total, mo,
-                                                             d.ctypes.data, cl.ctypes.data, cap_total, co, mem.ctypes.data, cap_total))
-        return [(m[mo[f]:mo[f + 1]].copy(), d[mo[f]:mo[f + 1]].copy(), cl[co[f]:co[f + 1]].copy(), mem) for f in range(n_frames)]
+        p, cut = _collect_buffers(n_frames, cap_total, ("m", "d", "cl", "mem"))
+        _lib.check(_lib.lib().lmx_ctx_collect_clusters_depth(self.h, n_frames, templates.h, int(class_index), float(no_value), p["m"], cap_total, p["mo"],
+                                                             p["d"], p["cl"], cap_total, p["co"], p["mem"], cap_total))
+        return cut()
 
     def collect_clusters_depth_normal(self, n_frames, templates, class_index=-1, no_value=-np.inf, cap_total=1 << 16):
         """collect_clusters_depth with the normal term in the score (lmx_ctx_collect_clusters_depth_normal): `templates` is a DepthTemplates
         after enable_normals whose upload_scene(depth_frames) was called after the enqueue.  -> list per frame of (matches, diffs, ndiffs,
         clusters, members), equal to collect + templates.normal_diff + cluster_matches_scored(normal_values(diffs, ndiffs)) bit for bit.
         exp(score) is the reference's getClusterScore when every member has something to compare."""
-        m = np.zeros(cap_total, MATCH_DTYPE)
-        d = np.zeros(cap_total, DEPTH_DIFF_DTYPE)
-        nd = np.zeros(cap_total, NORMAL_DIFF_DTYPE)
-        cl = np.zeros(cap_total, CLUSTER_DTYPE)
-        mem = np.zeros(cap_total, np.int32)
-        mo = (C.c_size_t * (n_frames + 1))()
-        co = (C.c_size_t * (n_frames + 1))()
-        _lib.check(_lib.lib().lmx_ctx_collect_clusters_depth_normal(self.h, n_frames, templates.h, int(class_index), float(no_value), m.ctypes.data, cap_total,
-                                                                    mo, d.ctypes.data, nd.ctypes.data, cl.ctypes.data, cap_total, co, mem.ctypes.data, cap_total))
-        return [(m[mo[f]:mo[f + 1]].copy(), d[mo[f]:mo[f + 1]].copy(), nd[mo[f]:mo[f + 1]].copy(), cl[co[f]:co[f + 1]].copy(), mem) for f in range(n_frames)]
+        p, cut = _collect_buffers(n_frames, cap_total, ("m", "d", "nd", "cl", "mem"))
+        _lib.check(_lib.lib().lmx_ctx_collect_clusters_depth_normal(self.h, n_frames, templates.h, int(class_index), float(no_value), p["m"], cap_total,
+                                                                    p["mo"], p["d"], p["nd"], p["cl"], cap_total, p["co"], p["mem"], cap_total))
+        return cut()
 
     def set_cluster_sidecar_class(self, class_index, obj_origin_dists, rects, vote_row_col_step=1, renderer_radius_min=0.0, renderer_radius_step=1.0,
                                   cluster_size_thresh=2):
         """Class class_index's side-car of the per-class device chain (lmx_ctx_set_cluster_sidecar_class), class_index 0 .. 15; empty
         obj_origin_dists remove it.  The un-classed side-car of set_cluster_sidecar is separate state."""
-        d = np.ascontiguousarray(obj_origin_dists, np.float64).reshape(-1)
-        r = np.ascontiguousarray(rects, np.int32).reshape(-1, 4)
+        d, r = _side_car(obj_origin_dists, rects)
         if len(r) != len(d):
             raise ValueError("one rect per origin distance")
-        pp = _lib.ClusterParams(int(vote_row_col_step), float(renderer_radius_min), float(renderer_radius_step), int(cluster_size_thresh))
+        pp = _cluster_params(vote_row_col_step, renderer_radius_min, renderer_radius_step, cluster_size_thresh)
         _lib.check(_lib.lib().lmx_ctx_set_cluster_sidecar_class(self.h, int(class_index), d.ctypes.data if len(d) else None, r.ctypes.data if len(d) else None,
                                                                 len(d), C.byref(pp)))
 
@@ -952,25 +974,14 @@ class Detector:
         class_base[c]:class_base[c + 1], whose upload_scene was called after the enqueue; normals adds the normal term (ndiffs is None
         without).  Equal to collect + per-class diffs + cluster_matches_classes bit for bit; not to two single-class detectors, whose std::unique
         may keep other templates of a duplicate (include/lmx.h)."""
-        m = np.zeros(cap_total, MATCH_DTYPE)
-        cl = np.zeros(cap_total, CLUSTER_DTYPE)
-        cc = np.zeros(cap_total, np.int32)
-        mem = np.zeros(cap_total, np.int32)
-        mo = (C.c_size_t * (n_frames + 1))()
-        co = (C.c_size_t * (n_frames + 1))()
-        d = nd = score = None
-        if templates is not None:
-            base = np.ascontiguousarray(class_base, np.int32).reshape(-1)
-            if len(base) < 2:
-                raise ValueError("class_base must hold one entry per class plus one")
-            d = np.zeros(cap_total, DEPTH_DIFF_DTYPE)
-            nd = np.zeros(cap_total, NORMAL_DIFF_DTYPE) if normals else None
+        score, scored = None, templates is not None
+        if scored:
+            base = _class_base(class_base)
             score = C.byref(_lib.ClassScore(templates.h, base.ctypes.data, len(base) - 1, int(bool(normals)), float(no_value)))
-        _lib.check(_lib.lib().lmx_ctx_collect_clusters_classes(self.h, n_frames, score, m.ctypes.data, cap_total, mo, d.ctypes.data if d is not None else None,
-                                                               nd.ctypes.data if nd is not None else None, cl.ctypes.data, cc.ctypes.data, cap_total, co,
-                                                               mem.ctypes.data, cap_total))
-        return [(m[mo[f]:mo[f + 1]].copy(), d[mo[f]:mo[f + 1]].copy() if d is not None else None, nd[mo[f]:mo[f + 1]].copy() if nd is not None else None,
-                 cl[co[f]:co[f + 1]].copy(), cc[co[f]:co[f + 1]].copy(), mem) for f in range(n_frames)]
+        p, cut = _collect_buffers(n_frames, cap_total, ("m", "d" if scored else None, "nd" if scored and normals else None, "cl", "cc", "mem"))
+        _lib.check(_lib.lib().lmx_ctx_collect_clusters_classes(self.h, n_frames, score, p["m"], cap_total, p["mo"], p.get("d"), p.get("nd"), p["cl"], p["cc"],
+                                                               cap_total, p["co"], p["mem"], cap_total))
+        return cut()
 
     def raw_matches_ptrs(self):
         rec, cnt, cap = C.c_void_p(), C.c_void_p(), C.c_size_t()
@@ -994,19 +1005,8 @@ class Detector:
         queued afterwards on `stream` (a torch stream or a raw hipStream_t; default: the current torch stream of the context's device).
         out: an ExportedMatches of an earlier call with the same n_frames and clusters, written again in place of fresh tensors (its
         stream is used unless `stream` is given); the capacities are then the smaller of the arguments' and its own."""
-        import torch
-        if stream is None:
-            stream = out.stream if out is not None else torch.cuda.current_stream(self.device)
-        elif not hasattr(stream, "cuda_stream"):
-            stream = torch.cuda.ExternalStream(int(stream), device=self.device)
-        if out is None:
-            out = ExportedMatches(n_frames, clusters, (cap_matches, cap_clusters, cap_members), stream, self.device)
-            caps = out.caps
-        else:
-            if out.n_frames != n_frames or out.with_clusters != bool(clusters):
-                raise ValueError("out was made for %d frames, clusters=%s" % (out.n_frames, out.with_clusters))
-            caps = tuple(min(int(a), b) for a, b in zip((cap_matches, cap_clusters, cap_members), out.caps))
-            out.stream = stream
+        stream = _torch_stream(stream, out.stream if out is not None else None, self.device)
+        out, caps = ExportedMatches._fresh_or(out, (n_frames, bool(clusters)), (cap_matches, cap_clusters, cap_members), stream, self.device)
         t = out._backing
         desc = _lib.ExportDesc(C.sizeof(_lib.ExportDesc), int(bool(oldest)), int(bool(clusters)), int(max_large_frames), t["header"].data_ptr(),
                                t["frame_info"].data_ptr(), t["matches"].data_ptr(), caps[0], t["clusters"].data_ptr() if clusters else None, caps[1],
@@ -1024,25 +1024,12 @@ class Detector:
         stays outstanding.  Nothing waits on the host; the first scored call allocates 16 bytes per record the slot can hold
         (max_batch x max_candidates; twice with normals).  stream, out, oldest, max_large_frames and the capacities as export_matches (diffs / ndiffs share cap_matches,
         cluster_class cap_clusters)."""
-        import torch
         score = 0 if templates is None else (2 if normals else 1)
-        if stream is None:
-            stream = out.stream if out is not None else torch.cuda.current_stream(self.device)
-        elif not hasattr(stream, "cuda_stream"):
-            stream = torch.cuda.ExternalStream(int(stream), device=self.device)
-        if out is None:
-            out = ExportedClusters(n_frames, score, classes, (cap_matches, cap_clusters, cap_members), stream, self.device)
-            caps = out.caps
-        else:
-            if out.n_frames != n_frames or out.score != score or out.with_classes != bool(classes):
-                raise ValueError("out was made for %d frames, score %d, classes=%s" % (out.n_frames, out.score, out.with_classes))
-            caps = tuple(min(int(a), b) for a, b in zip((cap_matches, cap_clusters, cap_members), out.caps))
-            out.stream = stream
+        stream = _torch_stream(stream, out.stream if out is not None else None, self.device)
+        out, caps = ExportedClusters._fresh_or(out, (n_frames, score, bool(classes)), (cap_matches, cap_clusters, cap_members), stream, self.device)
         base, n_classes = None, 0
         if classes and score:
-            base = np.ascontiguousarray(class_base, np.int32).reshape(-1)
-            if len(base) < 2:
-                raise ValueError("class_base must hold one entry per class plus one")
+            base = _class_base(class_base)
             n_classes = len(base) - 1
         t = out._backing
         ptr = lambda k: t[k].data_ptr() if k in t else None   # noqa: E731
@@ -1239,8 +1226,11 @@ class PinnedArena:
             pass
 
 
-CLUSTER_DTYPE = np.dtype([("index", "<i4", (3,)), ("rect", "<i4", (4,)), ("score", "<f8"), ("member_begin", "<i4"), ("member_count", "<i4")],
-                         align=True)
+def _cluster_outputs(n_matches):
+    """What the cluster_matches* calls write -> (clusters CLUSTER_DTYPE and members int32, each with room for every match; the size_t
+    the library leaves the number of clusters in)."""
+    n = max(1, n_matches)
+    return np.zeros(n, CLUSTER_DTYPE), np.zeros(n, np.int32), C.c_size_t()
 
 
 def cluster_matches(matches, obj_origin_dists, rects, vote_row_col_step, renderer_radius_min, renderer_radius_step, cluster_size_thresh=2):
@@ -1248,12 +1238,9 @@ def cluster_matches(matches, obj_origin_dists, rects, vote_row_col_step, rendere
     (reference: src/linemod_ensenso_detect_3_mult_detect_service.cpp:376-447).  Returns (clusters, members): clusters is a
     CLUSTER_DTYPE array in upstream's final order, members holds indices into `matches`."""
     matches = np.ascontiguousarray(matches, MATCH_DTYPE)
-    dists = np.ascontiguousarray(obj_origin_dists, np.float64)
-    rects = np.ascontiguousarray(rects, np.int32).reshape(-1, 4)
-    pp = _lib.ClusterParams(int(vote_row_col_step), float(renderer_radius_min), float(renderer_radius_step), int(cluster_size_thresh))
-    clusters = np.zeros(max(1, len(matches)), CLUSTER_DTYPE)
-    members = np.zeros(max(1, len(matches)), np.int32)
-    n = C.c_size_t()
+    dists, rects = _side_car(obj_origin_dists, rects)
+    pp = _cluster_params(vote_row_col_step, renderer_radius_min, renderer_radius_step, cluster_size_thresh)
+    clusters, members, n = _cluster_outputs(len(matches))
     _lib.check(_lib.lib().lmx_cluster_matches(matches.ctypes.data, len(matches), dists.ctypes.data, rects.ctypes.data, len(dists), C.byref(pp),
                                               clusters.ctypes.data, len(clusters), C.byref(n), members.ctypes.data, len(members)))
     return clusters[:n.value].copy(), members
@@ -1267,12 +1254,9 @@ def cluster_matches_scored(matches, match_values, obj_origin_dists, rects, vote_
     values = np.ascontiguousarray(match_values, np.float64)
     if values.shape != (len(matches),):
         raise ValueError("match_values must hold one value per match")
-    dists = np.ascontiguousarray(obj_origin_dists, np.float64)
-    rects = np.ascontiguousarray(rects, np.int32).reshape(-1, 4)
-    pp = _lib.ClusterParams(int(vote_row_col_step), float(renderer_radius_min), float(renderer_radius_step), int(cluster_size_thresh))
-    clusters = np.zeros(max(1, len(matches)), CLUSTER_DTYPE)
-    members = np.zeros(max(1, len(matches)), np.int32)
-    n = C.c_size_t()
+    dists, rects = _side_car(obj_origin_dists, rects)
+    pp = _cluster_params(vote_row_col_step, renderer_radius_min, renderer_radius_step, cluster_size_thresh)
+    clusters, members, n = _cluster_outputs(len(matches))
     _lib.check(_lib.lib().lmx_cluster_matches_scored(matches.ctypes.data, len(matches), values.ctypes.data, dists.ctypes.data, rects.ctypes.data, len(dists),
                                                      C.byref(pp), clusters.ctypes.data, len(clusters), C.byref(n), members.ctypes.data, len(members)))
     return clusters[:n.value].copy(), members
@@ -1286,14 +1270,11 @@ def _class_sidecars(classes):
     for k, c in enumerate(classes):
         if c is None:
             continue
-        dists, rects, step, rmin, rstep, thresh = c
-        d = np.ascontiguousarray(dists, np.float64).reshape(-1)
-        r = np.ascontiguousarray(rects, np.int32).reshape(-1, 4)
+        d, r = _side_car(c[0], c[1])
         if len(r) != len(d):
             raise ValueError("class %d: one rect per origin distance" % k)
         keep += [d, r]
-        arr[k] = _lib.ClassSidecar(d.ctypes.data if len(d) else None, r.ctypes.data if len(d) else None, len(d),
-                                   _lib.ClusterParams(int(step), float(rmin), float(rstep), int(thresh)))
+        arr[k] = _lib.ClassSidecar(d.ctypes.data if len(d) else None, r.ctypes.data if len(d) else None, len(d), _cluster_params(*c[2:]))
     return arr, keep
 
 
@@ -1309,18 +1290,13 @@ def cluster_matches_classes(matches, classes, match_values=None):
         if values.shape != (len(matches),):
             raise ValueError("match_values must hold one value per match")
     arr, keep = _class_sidecars(classes)
-    clusters = np.zeros(max(1, len(matches)), CLUSTER_DTYPE)
-    cluster_class = np.zeros(max(1, len(matches)), np.int32)
-    members = np.zeros(max(1, len(matches)), np.int32)
-    n = C.c_size_t()
+    clusters, members, n = _cluster_outputs(len(matches))
+    cluster_class = np.zeros(len(clusters), np.int32)
     _lib.check(_lib.lib().lmx_cluster_matches_classes(matches.ctypes.data, len(matches), values.ctypes.data if values is not None else None, arr, len(classes),
                                                       clusters.ctypes.data, cluster_class.ctypes.data, len(clusters), C.byref(n), members.ctypes.data,
                                                       len(members)))
     del keep
     return clusters[:n.value].copy(), cluster_class[:n.value].copy(), members
-
-
-DEPTH_DIFF_DTYPE = np.dtype([("sum_abs_mm", "<i8"), ("n_valid", "<i4"), ("n_template", "<i4")])
 
 
 def depth_values(diffs):
@@ -1334,8 +1310,6 @@ def depth_values(diffs):
     out[ok] = -(diffs["sum_abs_mm"][ok].astype(np.float64) / (diffs["n_valid"][ok].astype(np.float64) * 1000.0))
     return out
 
-
-NORMAL_DIFF_DTYPE = np.dtype([("sum_angle_urad", "<i8"), ("n_normal", "<i4"), ("reserved", "<i4")])
 
 # lmx_pose_refine_t; status: the LMX_POSE_* values
 POSE_REFINE_DTYPE = np.dtype([("R", "<f8", (9,)), ("t_mm", "<f8", (3,)), ("rms_first_mm", "<f8"), ("rms_last_mm", "<f8"), ("n_model", "<i4"),
@@ -1415,6 +1389,73 @@ def _depth_images(depth_frames):
     return frames, (_lib.Image * max(1, len(frames)))(*[_lib.Image(d.ctypes.data, d.shape[0], d.shape[1], 1, 2, d.strides[0]) for d in frames])
 
 
+def _frame_offsets(offsets, n_frames, n_matches):
+    """Where each frame's matches begin in a list of all frames' back to back (default: one frame holding all) -> size_t [n_frames + 1]."""
+    if offsets is None:
+        if n_frames != 1:
+            raise ValueError("offsets are needed with more than one frame")
+        offsets = [0, n_matches]
+    if len(offsets) != n_frames + 1 or int(offsets[-1]) != n_matches:
+        raise ValueError("offsets must have one entry per frame plus one and end at len(matches)")
+    return (C.c_size_t * len(offsets))(*[int(v) for v in offsets])
+
+
+# ---- the array fields of a chain descriptor (PoseChainDesc, RoughChainDesc): eight of input, and the outputs a result class's NAMES name ----
+_CHAIN_HOST_DTYPES = {"chain_header": np.uint32, "leaders": np.int32, "rough": ROUGH_POSE_DTYPE, "member_group": np.int32, "poses": POSE_REFINE_DTYPE,
+                      "checks": POSE_VERIFY_DTYPE, "keep": np.uint8}
+
+
+def _chain_room(exported, out):
+    """What a chain call needs of the export it reads and of the `out` it is to write again (None: a fresh one) -> the export's caps."""
+    if getattr(exported, "clusters", None) is None or exported.members is None:
+        raise ValueError("exported holds no clusters (export_matches(clusters=True) or export_clusters)")
+    if exported.caps[1] < 1:
+        raise ValueError("the export has no room for clusters")
+    if out is not None:
+        out._fits(exported.caps)
+    return exported.caps
+
+
+def _chain_inputs(d, exported):
+    """The eight input fields of d from an export's tensors and capacities."""
+    b, caps = exported._backing, exported.caps
+    d.header, d.frame_info, d.matches, d.cap_matches = b["header"].data_ptr(), b["frame_info"].data_ptr(), b["matches"].data_ptr(), caps[0]
+    d.clusters, d.cap_clusters, d.members, d.cap_members = b["clusters"].data_ptr(), caps[1], b["members"].data_ptr(), caps[2]
+
+
+def _chain_inputs_host(d, lists, cap_clusters=None):
+    """The same from lists = (header, frame_info, matches, clusters, members) in host memory, whose lengths are the capacities; cap_clusters
+    may state a smaller one.  -> the lists as the arrays d points to: uint32 [16], int32 [F, 8], MATCH_DTYPE, CLUSTER_DTYPE, int32."""
+    header, frame_info, matches, clusters, members = lists
+    header = np.ascontiguousarray(header).astype(np.uint32).reshape(16)
+    frame_info = np.ascontiguousarray(frame_info, np.int32).reshape(-1, 8)
+    matches = np.ascontiguousarray(matches, MATCH_DTYPE)
+    clusters = np.ascontiguousarray(clusters, CLUSTER_DTYPE)
+    members = np.ascontiguousarray(members, np.int32)
+    d.header, d.frame_info, d.matches, d.cap_matches = header.ctypes.data, frame_info.ctypes.data, matches.ctypes.data, len(matches)
+    d.clusters, d.cap_clusters, d.members, d.cap_members = clusters.ctypes.data, len(clusters) if cap_clusters is None else int(cap_clusters), members.ctypes.data, len(members)
+    if d.cap_clusters > len(clusters):
+        raise ValueError("cap_clusters exceeds len(clusters)")
+    return header, frame_info, matches, clusters, members
+
+
+def _chain_outputs_host(names, n_clusters, n_members, fill):
+    """The arrays a debug chain hook writes, name -> array: chain_header zeroed, the others -- one entry per cluster, member_group per
+    member (at least one) -- holding the byte `fill`."""
+    out = {k: np.zeros(POSE_CHAIN_HEADER_WORDS if k == "chain_header" else max(n_members, 1) if k == "member_group" else n_clusters, _CHAIN_HOST_DTYPES[k])
+           for k in names}
+    for k in names:
+        if k != "chain_header":
+            out[k].view(np.uint8)[:] = fill
+    return out
+
+
+def _chain_outputs(d, names, address):
+    """The output fields `names` of d from a mapping name -> address."""
+    for k in names:
+        setattr(d, k, address[k])
+
+
 class DepthTemplates:
     """Device-resident depth renders of a bank's templates, cropped to their silhouette boxes (lmx_depth_templates), and the depth check
     of matches against them (lmx_depth_diff_matches): the depth half of the reference's depth_normal_diff_calc
@@ -1476,13 +1517,7 @@ class DepthTemplates:
         record per match; with class_index >= 0 the matches of other classes get zeros."""
         frames, imgs = _depth_images(depth_frames)
         matches = np.ascontiguousarray(matches, MATCH_DTYPE)
-        if offsets is None:
-            if len(frames) != 1:
-                raise ValueError("offsets are needed with more than one frame")
-            offsets = [0, len(matches)]
-        if len(offsets) != len(frames) + 1 or int(offsets[-1]) != len(matches):
-            raise ValueError("offsets must have one entry per frame plus one and end at len(matches)")
-        offs = (C.c_size_t * len(offsets))(*[int(v) for v in offsets])
+        offs = _frame_offsets(offsets, len(frames), len(matches))
         out = np.zeros(len(matches), DEPTH_DIFF_DTYPE)
         _lib.check(_lib.lib().lmx_depth_diff_matches(self.h, imgs, len(frames), matches.ctypes.data, offs, int(class_index), out.ctypes.data))
         return out
@@ -1505,13 +1540,7 @@ class DepthTemplates:
         per match each; the first equals diff()'s result."""
         frames, imgs = _depth_images(depth_frames)
         matches = np.ascontiguousarray(matches, MATCH_DTYPE)
-        if offsets is None:
-            if len(frames) != 1:
-                raise ValueError("offsets are needed with more than one frame")
-            offsets = [0, len(matches)]
-        if len(offsets) != len(frames) + 1 or int(offsets[-1]) != len(matches):
-            raise ValueError("offsets must have one entry per frame plus one and end at len(matches)")
-        offs = (C.c_size_t * len(offsets))(*[int(v) for v in offsets])
+        offs = _frame_offsets(offsets, len(frames), len(matches))
         dd = np.zeros(len(matches), DEPTH_DIFF_DTYPE)
         nd = np.zeros(len(matches), NORMAL_DIFF_DTYPE)
         _lib.check(_lib.lib().lmx_normal_diff_matches(self.h, imgs, len(frames), matches.ctypes.data, offs, int(class_index), dd.ctypes.data, nd.ctypes.data))
@@ -1525,13 +1554,7 @@ class DepthTemplates:
         else:
             frames, imgs = None, None
             n_frames = len(offsets) - 1 if offsets is not None else 1
-        if offsets is None:
-            if n_frames != 1:
-                raise ValueError("offsets are needed with more than one frame")
-            offsets = [0, len(matches)]
-        if len(offsets) != n_frames + 1 or int(offsets[-1]) != len(matches):
-            raise ValueError("offsets must have one entry per frame plus one and end at len(matches)")
-        return frames, imgs, n_frames, (C.c_size_t * len(offsets))(*[int(v) for v in offsets])
+        return frames, imgs, n_frames, _frame_offsets(offsets, n_frames, len(matches))
 
     def _pose_rects(self, rects):
         keep = np.ascontiguousarray(rects, np.int32).reshape(-1, 4) if rects is not None else None
@@ -1547,6 +1570,12 @@ class DepthTemplates:
                                   float(eps_rot_rad), float(eps_trans_mm), int(max_iterations), int(min_pairs), int(search_radius),
                                   keep.ctypes.data if keep is not None else None)
         return p, keep
+
+    @staticmethod
+    def _verify_params(model_camera, scene_camera, voxel_mm, roi_margin, keep):
+        """keep: what _pose_rects returned."""
+        return _lib.PoseVerifyParams(C.sizeof(_lib.PoseVerifyParams), *[float(v) for v in tuple(model_camera) + tuple(scene_camera)], float(voxel_mm), int(roi_margin),
+                                     keep.ctypes.data if keep is not None else None)
 
     def refine_poses(self, matches, depth_frames=None, offsets=None, class_index=-1, model_camera=None, scene_camera=None, max_dist_mm=10.0,
                      max_iterations=20, min_pairs=16, search_radius=1, eps_rot_rad=1e-5, eps_trans_mm=1e-3, rects=None):
@@ -1576,8 +1605,7 @@ class DepthTemplates:
             raise ValueError("model_camera and scene_camera are (fx, fy, cx, cy)")
         frames, imgs, n_frames, offs = self._pose_frames(matches, depth_frames, offsets)
         keep = self._pose_rects(rects)
-        p = _lib.PoseVerifyParams(C.sizeof(_lib.PoseVerifyParams), *[float(v) for v in tuple(model_camera) + tuple(scene_camera)], float(voxel_mm), int(roi_margin),
-                                  keep.ctypes.data if keep is not None else None)
+        p = self._verify_params(model_camera, scene_camera, voxel_mm, roi_margin, keep)
         out = np.zeros(len(matches), POSE_VERIFY_DTYPE)
         _lib.check(_lib.lib().lmx_pose_verify_matches(self.h, imgs, n_frames, matches.ctypes.data, offs, int(class_index), poses.ctypes.data, C.byref(p),
                                                       out.ctypes.data))
@@ -1588,11 +1616,8 @@ class DepthTemplates:
                          eps_rot_rad, eps_trans_mm, voxel_mm, roi_margin, rects):
         """The parameters of pose_chain / debug_pose_chain -> (PoseChainDesc without its arrays, what it points to)."""
         pr, keep = self._pose_params(model_camera, scene_camera, max_dist_mm, max_iterations, min_pairs, search_radius, eps_rot_rad, eps_trans_mm, rects)
-        pv = _lib.PoseVerifyParams(C.sizeof(_lib.PoseVerifyParams), *[float(v) for v in tuple(model_camera) + tuple(scene_camera)], float(voxel_mm), int(roi_margin),
-                                   keep.ctypes.data if keep is not None else None)
-        base = np.ascontiguousarray(class_base, np.int32).reshape(-1) if class_base is not None else None
-        if base is not None and len(base) < 2:
-            raise ValueError("class_base must hold one entry per class plus one")
+        pv = self._verify_params(model_camera, scene_camera, voxel_mm, roi_margin, keep)
+        base = _class_base(class_base) if class_base is not None else None
         d = _lib.PoseChainDesc()
         d.struct_size, d.n_frames, d.class_index, d.n_classes = C.sizeof(_lib.PoseChainDesc), int(n_frames), int(class_index), len(base) - 1 if base is not None else 0
         d.class_base = base.ctypes.data if base is not None else None
@@ -1609,32 +1634,18 @@ class DepthTemplates:
         verify_poses; class_base: the cumulative template counts of the classes joined in this object (append), a match's template_id is
         then rebased by its class.  stream: default exported.stream.  out: an ExportedPoses of an earlier call with room for the export's
         cluster capacity, written again in place of fresh tensors."""
-        import torch
-        if getattr(exported, "clusters", None) is None or exported.members is None:
-            raise ValueError("exported holds no clusters (export_matches(clusters=True) or export_clusters)")
+        caps = _chain_room(exported, out)
         if model_camera is None or scene_camera is None:
             raise ValueError("model_camera and scene_camera are (fx, fy, cx, cy)")
         device = exported.header.device.index
-        if stream is None:
-            stream = exported.stream
-        elif not hasattr(stream, "cuda_stream"):
-            stream = torch.cuda.ExternalStream(int(stream), device=device)
-        caps = exported.caps
-        if caps[1] < 1:
-            raise ValueError("the export has no room for clusters")
+        stream = _torch_stream(stream, exported.stream, device)
         if out is None:
             out = ExportedPoses(caps[1], stream, device)
-        else:
-            if out.cap < caps[1]:
-                raise ValueError("out was made for %d clusters, the export holds up to %d" % (out.cap, caps[1]))
-            out.stream = stream
+        out.stream = stream
         d, alive = self._pose_chain_desc(exported.n_frames, keep_thresh, class_index, class_base, model_camera, scene_camera, max_dist_mm, max_iterations, min_pairs,
                                          search_radius, eps_rot_rad, eps_trans_mm, voxel_mm, roi_margin, rects)
-        b = exported._backing
-        d.header, d.frame_info, d.matches, d.cap_matches = b["header"].data_ptr(), b["frame_info"].data_ptr(), b["matches"].data_ptr(), caps[0]
-        d.clusters, d.cap_clusters, d.members, d.cap_members = b["clusters"].data_ptr(), caps[1], b["members"].data_ptr(), caps[2]
-        t = out._backing
-        d.chain_header, d.leaders, d.poses, d.checks, d.keep = (t[k].data_ptr() for k in ("chain_header", "leaders", "poses", "checks", "keep"))
+        _chain_inputs(d, exported)
+        _chain_outputs(d, out.NAMES, {k: v.data_ptr() for k, v in out._backing.items()})
         _lib.check(_lib.lib().lmx_pose_chain_on(self.h, C.byref(d), int(stream.cuda_stream)))
         del alive
         return out
@@ -1646,26 +1657,15 @@ class DepthTemplates:
         [F, 8], matches MATCH_DTYPE, clusters CLUSTER_DTYPE, members int32; their lengths are the capacities, cap_clusters may state a
         smaller one) against the resident scene -> (chain_header uint32 [8], leaders int32, poses POSE_REFINE_DTYPE, checks
         POSE_VERIFY_DTYPE, keep uint8), each [len(clusters)] and holding the byte `fill` wherever the kernels wrote nothing."""
-        header = np.ascontiguousarray(header).astype(np.uint32).reshape(16)
-        frame_info = np.ascontiguousarray(frame_info, np.int32).reshape(-1, 8)
-        matches = np.ascontiguousarray(matches, MATCH_DTYPE)
-        clusters = np.ascontiguousarray(clusters, CLUSTER_DTYPE)
-        members = np.ascontiguousarray(members, np.int32)
-        n = len(clusters)
-        hdr = np.zeros(POSE_CHAIN_HEADER_WORDS, np.uint32)
-        leaders, poses, checks, keep = np.zeros(n, np.int32), np.zeros(n, POSE_REFINE_DTYPE), np.zeros(n, POSE_VERIFY_DTYPE), np.zeros(n, np.uint8)
-        for a in (leaders, poses, checks, keep):
-            a.view(np.uint8)[:] = fill
-        d, alive = self._pose_chain_desc(len(frame_info), keep_thresh, class_index, class_base, model_camera, scene_camera, max_dist_mm, max_iterations, min_pairs,
+        d, alive = self._pose_chain_desc(0, keep_thresh, class_index, class_base, model_camera, scene_camera, max_dist_mm, max_iterations, min_pairs,
                                          search_radius, eps_rot_rad, eps_trans_mm, voxel_mm, roi_margin, rects)
-        d.header, d.frame_info, d.matches, d.cap_matches = header.ctypes.data, frame_info.ctypes.data, matches.ctypes.data, len(matches)
-        d.clusters, d.cap_clusters, d.members, d.cap_members = clusters.ctypes.data, n if cap_clusters is None else int(cap_clusters), members.ctypes.data, len(members)
-        if d.cap_clusters > n:
-            raise ValueError("cap_clusters exceeds len(clusters)")
-        d.chain_header, d.leaders, d.poses, d.checks, d.keep = hdr.ctypes.data, leaders.ctypes.data, poses.ctypes.data, checks.ctypes.data, keep.ctypes.data
+        lists = _chain_inputs_host(d, (header, frame_info, matches, clusters, members), cap_clusters)
+        d.n_frames = len(lists[1])
+        out = _chain_outputs_host(ExportedPoses.NAMES, len(lists[3]), len(lists[4]), fill)
+        _chain_outputs(d, ExportedPoses.NAMES, {k: a.ctypes.data for k, a in out.items()})
         _lib.check(_lib.lib().lmx_debug_pose_chain(self.h, C.byref(d)))
-        del alive
-        return hdr, leaders, poses, checks, keep
+        del alive, lists
+        return tuple(out[k] for k in ExportedPoses.NAMES)
 
     def _rough_chain_desc(self, model, n_frames, keep_thresh, threshold_deg, trace_min, class_index, model_camera, scene_camera, max_dist_mm, max_iterations,
                           min_pairs, search_radius, eps_rot_rad, eps_trans_mm, voxel_mm, roi_margin):
@@ -1675,7 +1675,7 @@ class DepthTemplates:
         if scene_camera is None:
             raise ValueError("scene_camera is (fx, fy, cx, cy)")
         pr, _ = self._pose_params(model_camera, scene_camera, max_dist_mm, max_iterations, min_pairs, search_radius, eps_rot_rad, eps_trans_mm, None)
-        pv = _lib.PoseVerifyParams(C.sizeof(_lib.PoseVerifyParams), *[float(v) for v in tuple(model_camera) + tuple(scene_camera)], float(voxel_mm), int(roi_margin), None)
+        pv = self._verify_params(model_camera, scene_camera, voxel_mm, roi_margin, None)
         d = _lib.RoughChainDesc()
         d.struct_size, d.n_frames, d.class_index = C.sizeof(_lib.RoughChainDesc), int(n_frames), int(class_index)
         d.refine, d.verify, d.keep_thresh = C.pointer(pr), C.pointer(pv), float(keep_thresh)
@@ -1690,30 +1690,16 @@ class DepthTemplates:
         template_id) rendered again at that view, that render refined and verified against the resident scene at the mean match
         position, and the keep decision -- with no host wait in between.  model_camera: default the model's.  trace_min: in place of
         threshold_deg, the bound itself.  The other keywords as pose_chain; rects are the rendered ones."""
-        import torch
-        if getattr(exported, "clusters", None) is None or exported.members is None:
-            raise ValueError("exported holds no clusters (export_matches(clusters=True) or export_clusters)")
+        caps = _chain_room(exported, out)
         device = exported.header.device.index
-        if stream is None:
-            stream = exported.stream
-        elif not hasattr(stream, "cuda_stream"):
-            stream = torch.cuda.ExternalStream(int(stream), device=device)
-        caps = exported.caps
-        if caps[1] < 1:
-            raise ValueError("the export has no room for clusters")
+        stream = _torch_stream(stream, exported.stream, device)
         if out is None:
             out = ExportedRoughPoses(caps[1], caps[2], stream, device)
-        else:
-            if out.cap < caps[1] or out.cap_members < caps[2]:
-                raise ValueError("out was made for %d clusters and %d members, the export holds up to %d and %d" % (out.cap, out.cap_members, caps[1], caps[2]))
-            out.stream = stream
+        out.stream = stream
         d, alive = self._rough_chain_desc(model, exported.n_frames, keep_thresh, threshold_deg, trace_min, class_index, model_camera, scene_camera, max_dist_mm,
                                           max_iterations, min_pairs, search_radius, eps_rot_rad, eps_trans_mm, voxel_mm, roi_margin)
-        b = exported._backing
-        d.header, d.frame_info, d.matches, d.cap_matches = b["header"].data_ptr(), b["frame_info"].data_ptr(), b["matches"].data_ptr(), caps[0]
-        d.clusters, d.cap_clusters, d.members, d.cap_members = b["clusters"].data_ptr(), caps[1], b["members"].data_ptr(), caps[2]
-        t = out._backing
-        d.chain_header, d.rough, d.member_group, d.poses, d.checks, d.keep = (t[k].data_ptr() for k in ExportedRoughPoses.NAMES)
+        _chain_inputs(d, exported)
+        _chain_outputs(d, out.NAMES, {k: v.data_ptr() for k, v in out._backing.items()})
         _lib.check(_lib.lib().lmx_rough_pose_chain_on(self.h, model.h, C.byref(d), int(stream.cuda_stream)))
         del alive
         return out
@@ -1724,27 +1710,16 @@ class DepthTemplates:
         """Test hook (lmx_debug_rough_pose_chain): rough_pose_chain's kernels on lists in host memory, as debug_pose_chain takes them ->
         (chain_header uint32 [8], rough ROUGH_POSE_DTYPE, member_group int32 [len(members)], poses, checks, keep), holding the byte `fill`
         wherever the kernels wrote nothing."""
-        header = np.ascontiguousarray(header).astype(np.uint32).reshape(16)
-        frame_info = np.ascontiguousarray(frame_info, np.int32).reshape(-1, 8)
-        matches = np.ascontiguousarray(matches, MATCH_DTYPE)
-        clusters = np.ascontiguousarray(clusters, CLUSTER_DTYPE)
-        members = np.ascontiguousarray(members, np.int32)
-        n = len(clusters)
-        hdr = np.zeros(POSE_CHAIN_HEADER_WORDS, np.uint32)
-        rough, group = np.zeros(n, ROUGH_POSE_DTYPE), np.zeros(max(len(members), 1), np.int32)
-        poses, checks, keep = np.zeros(n, POSE_REFINE_DTYPE), np.zeros(n, POSE_VERIFY_DTYPE), np.zeros(n, np.uint8)
-        for a in (rough, group, poses, checks, keep):
-            a.view(np.uint8)[:] = fill
-        d, alive = self._rough_chain_desc(model, len(frame_info), keep_thresh, threshold_deg, trace_min, class_index, model_camera, scene_camera, max_dist_mm,
+        d, alive = self._rough_chain_desc(model, 0, keep_thresh, threshold_deg, trace_min, class_index, model_camera, scene_camera, max_dist_mm,
                                           max_iterations, min_pairs, search_radius, eps_rot_rad, eps_trans_mm, voxel_mm, roi_margin)
-        d.header, d.frame_info, d.matches, d.cap_matches = header.ctypes.data, frame_info.ctypes.data, matches.ctypes.data, len(matches)
-        d.clusters, d.cap_clusters, d.members, d.cap_members = clusters.ctypes.data, n if cap_clusters is None else int(cap_clusters), members.ctypes.data, len(members)
-        if d.cap_clusters > n:
-            raise ValueError("cap_clusters exceeds len(clusters)")
-        d.chain_header, d.rough, d.member_group, d.poses, d.checks, d.keep = (a.ctypes.data for a in (hdr, rough, group, poses, checks, keep))
+        lists = _chain_inputs_host(d, (header, frame_info, matches, clusters, members), cap_clusters)
+        d.n_frames = len(lists[1])
+        out = _chain_outputs_host(ExportedRoughPoses.NAMES, len(lists[3]), len(lists[4]), fill)
+        _chain_outputs(d, ExportedRoughPoses.NAMES, {k: a.ctypes.data for k, a in out.items()})
         _lib.check(_lib.lib().lmx_debug_rough_pose_chain(self.h, model.h, C.byref(d)))
-        del alive
-        return hdr, rough, group[:len(members)], poses, checks, keep
+        out["member_group"] = out["member_group"][:len(lists[4])]
+        del alive, lists
+        return tuple(out[k] for k in ExportedRoughPoses.NAMES)
 
     def debug_pose_refine_sums(self, depth_frame, match, **params):
         """Test hook (lmx_debug_pose_refine_sums): one match against one host frame -> (its POSE_REFINE_DTYPE record, int64
@@ -1898,6 +1873,29 @@ F2_MAX = 2048   # records per frame the device chain's LDS kernels take (csrc/lm
 F2_LARGE_MAX = 16384   # ... and its large-frame kernels; beyond it the host finishes the frame
 
 
+def _finalize_buffers(n_frames, large, names):
+    """The host lists of one debug_device_finalize_cluster* hook and their cut per frame.  names as _collect_buffers takes them -> (name ->
+    address of a list of one row per frame, with "counts", the kernel's uint32 [n_frames][4] count words; cut(with_counts) -> list per
+    frame of the tuple, each list cut to the count the kernel reported, with the frame's status behind; with_counts: (that, the words))."""
+    nf = max(1, int(n_frames))
+    rows = F2_LARGE_MAX if large else F2_MAX   # large: the large-frame kernel on every frame (the *_large hooks below)
+    b = {k: np.zeros((nf, rows), _LIST_DTYPES[k]) for k in names if k}
+    counts = np.zeros((nf, 4), np.uint32)
+    ptr = {k: a.ctypes.data for k, a in b.items()}
+    ptr["counts"] = counts.ctypes.data
+
+    def cut(with_counts):
+        out = []
+        for f in range(n_frames):
+            n_m, n_c, n_mem, status = (int(v) for v in counts[f])
+            if status == 1:   # counts[0] is the record count here, not a number of matches written
+                n_m = 0
+            n = {"m": n_m, "d": n_m, "nd": n_m, "cl": n_c, "cc": n_c, "mem": n_mem}
+            out.append(tuple(None if k is None else b[k][f, :n[k]].copy() for k in names) + (status,))
+        return (out, counts) if with_counts else out
+    return ptr, cut
+
+
 def debug_device_finalize_cluster(records, n_frames, obj_origin_dists, rects, vote_row_col_step, renderer_radius_min, renderer_radius_step,
                                   cluster_size_thresh=2, device=0, with_counts=False, large=False):
     """Test hook (lmx_debug_device_finalize_cluster): the kernel behind Detector.collect_clusters on a caller's RAW_MATCH_DTYPE records
@@ -1905,25 +1903,13 @@ def debug_device_finalize_cluster(records, n_frames, obj_origin_dists, rects, vo
     kernel reported and otherwise as it wrote them: no host completion.  status 1 (more than F2_MAX records): all three are empty;
     status 2 (side-car / range): matches only.  with_counts: also the kernel's count words, uint32 [n_frames][4]."""
     records = np.ascontiguousarray(records, RAW_MATCH_DTYPE)
-    dists = np.ascontiguousarray(obj_origin_dists, np.float64)
-    rects = np.ascontiguousarray(rects, np.int32).reshape(-1, 4)
-    pp = _lib.ClusterParams(int(vote_row_col_step), float(renderer_radius_min), float(renderer_radius_step), int(cluster_size_thresh))
-    nf = max(1, int(n_frames))
-    rows = F2_LARGE_MAX if large else F2_MAX   # large: the large-frame kernel on every frame (the *_large hooks below)
-    m = np.zeros((nf, rows), MATCH_DTYPE)
-    cl = np.zeros((nf, rows), CLUSTER_DTYPE)
-    mem = np.zeros((nf, rows), np.int32)
-    counts = np.zeros((nf, 4), np.uint32)
+    dists, rects = _side_car(obj_origin_dists, rects)
+    pp = _cluster_params(vote_row_col_step, renderer_radius_min, renderer_radius_step, cluster_size_thresh)
+    p, cut = _finalize_buffers(n_frames, large, ("m", "cl", "mem"))
     hook = _lib.lib().lmx_debug_device_finalize_cluster_large if large else _lib.lib().lmx_debug_device_finalize_cluster
     _lib.check(hook(device, records.ctypes.data, len(records), int(n_frames), dists.ctypes.data, rects.ctypes.data,
-                    len(dists), C.byref(pp), m.ctypes.data, cl.ctypes.data, mem.ctypes.data, counts.ctypes.data))
-    out = []
-    for f in range(n_frames):
-        n_m, n_c, n_mem, status = (int(v) for v in counts[f])
-        if status == 1:   # counts[0] is the record count here, not a number of matches written
-            n_m = 0
-        out.append((m[f, :n_m].copy(), cl[f, :n_c].copy(), mem[f, :n_mem].copy(), status))
-    return (out, counts) if with_counts else out
+                    len(dists), C.byref(pp), p["m"], p["cl"], p["mem"], p["counts"]))
+    return cut(with_counts)
 
 
 def debug_device_finalize_cluster_depth(records, n_frames, templates, depth_frames, obj_origin_dists, rects, vote_row_col_step, renderer_radius_min,
@@ -1932,30 +1918,16 @@ def debug_device_finalize_cluster_depth(records, n_frames, templates, depth_fram
     Detector.collect_clusters_depth; depth_frames (one per frame) become `templates`' uploaded scene.  -> list per frame of
     (matches, diffs, clusters, members, status)."""
     records = np.ascontiguousarray(records, RAW_MATCH_DTYPE)
-    dists = np.ascontiguousarray(obj_origin_dists, np.float64)
-    rects = np.ascontiguousarray(rects, np.int32).reshape(-1, 4)
-    pp = _lib.ClusterParams(int(vote_row_col_step), float(renderer_radius_min), float(renderer_radius_step), int(cluster_size_thresh))
+    dists, rects = _side_car(obj_origin_dists, rects)
+    pp = _cluster_params(vote_row_col_step, renderer_radius_min, renderer_radius_step, cluster_size_thresh)
     frames, imgs = _depth_images(depth_frames)
     if len(frames) != n_frames:
         raise ValueError("one depth frame per frame")
-    nf = max(1, int(n_frames))
-    rows = F2_LARGE_MAX if large else F2_MAX   # large: the large-frame kernel on every frame (the *_large hooks below)
-    m = np.zeros((nf, rows), MATCH_DTYPE)
-    d = np.zeros((nf, rows), DEPTH_DIFF_DTYPE)
-    cl = np.zeros((nf, rows), CLUSTER_DTYPE)
-    mem = np.zeros((nf, rows), np.int32)
-    counts = np.zeros((nf, 4), np.uint32)
+    p, cut = _finalize_buffers(n_frames, large, ("m", "d", "cl", "mem"))
     hook = _lib.lib().lmx_debug_device_finalize_cluster_large_depth if large else _lib.lib().lmx_debug_device_finalize_cluster_depth
     _lib.check(hook(device, records.ctypes.data, len(records), int(n_frames), templates.h, imgs, int(class_index),
-                    float(no_value), dists.ctypes.data, rects.ctypes.data, len(dists), C.byref(pp), m.ctypes.data,
-                    d.ctypes.data, cl.ctypes.data, mem.ctypes.data, counts.ctypes.data))
-    out = []
-    for f in range(n_frames):
-        n_m, n_c, n_mem, status = (int(v) for v in counts[f])
-        if status == 1:   # counts[0] is the record count here, not a number of matches written
-            n_m = 0
-        out.append((m[f, :n_m].copy(), d[f, :n_m].copy(), cl[f, :n_c].copy(), mem[f, :n_mem].copy(), status))
-    return (out, counts) if with_counts else out
+                    float(no_value), dists.ctypes.data, rects.ctypes.data, len(dists), C.byref(pp), p["m"], p["d"], p["cl"], p["mem"], p["counts"]))
+    return cut(with_counts)
 
 
 def debug_device_finalize_cluster_classes(records, n_frames, classes, templates=None, class_base=None, depth_frames=None, normals=False, no_value=-np.inf,
@@ -1965,36 +1937,20 @@ def debug_device_finalize_cluster_classes(records, n_frames, classes, templates=
     diffs / ndiffs are None without templates / normals.  No host completion."""
     records = np.ascontiguousarray(records, RAW_MATCH_DTYPE)
     arr, keep = _class_sidecars(classes)
-    nf = max(1, int(n_frames))
-    rows = F2_LARGE_MAX if large else F2_MAX   # large: the large-frame kernel on every frame (the *_large hooks below)
-    m = np.zeros((nf, rows), MATCH_DTYPE)
-    cl = np.zeros((nf, rows), CLUSTER_DTYPE)
-    cc = np.zeros((nf, rows), np.int32)
-    mem = np.zeros((nf, rows), np.int32)
-    counts = np.zeros((nf, 4), np.uint32)
-    d = nd = score = imgs = None
-    if templates is not None:
+    score = imgs = None
+    scored = templates is not None
+    if scored:
         base = np.ascontiguousarray(class_base, np.int32).reshape(-1)
         frames, imgs = _depth_images(depth_frames)
         if len(frames) != n_frames or len(base) < 2:
             raise ValueError("one depth frame per frame, one class_base entry per class plus one")
-        d = np.zeros((nf, rows), DEPTH_DIFF_DTYPE)
-        nd = np.zeros((nf, rows), NORMAL_DIFF_DTYPE) if normals else None
         score = C.byref(_lib.ClassScore(templates.h, base.ctypes.data, len(base) - 1, int(bool(normals)), float(no_value)))
+    p, cut = _finalize_buffers(n_frames, large, ("m", "d" if scored else None, "nd" if scored and normals else None, "cl", "cc", "mem"))
     hook = _lib.lib().lmx_debug_device_finalize_cluster_large_classes if large else _lib.lib().lmx_debug_device_finalize_cluster_classes
     _lib.check(hook(device, records.ctypes.data, len(records), int(n_frames), arr, len(classes), score, imgs,
-                    m.ctypes.data, d.ctypes.data if d is not None else None,
-                    nd.ctypes.data if nd is not None else None, cl.ctypes.data, cc.ctypes.data,
-                    mem.ctypes.data, counts.ctypes.data))
+                    p["m"], p.get("d"), p.get("nd"), p["cl"], p["cc"], p["mem"], p["counts"]))
     del keep
-    out = []
-    for f in range(n_frames):
-        n_m, n_c, n_mem, status = (int(v) for v in counts[f])
-        if status == 1:   # counts[0] is the record count here, not a number of matches written
-            n_m = 0
-        out.append((m[f, :n_m].copy(), d[f, :n_m].copy() if d is not None else None, nd[f, :n_m].copy() if nd is not None else None, cl[f, :n_c].copy(),
-                    cc[f, :n_c].copy(), mem[f, :n_mem].copy(), status))
-    return (out, counts) if with_counts else out
+    return cut(with_counts)
 
 
 def debug_device_finalize_cluster_large(*args, **kw):

@@ -7,7 +7,7 @@ import subprocess
 import numpy as np
 
 import pose_refine_cases as prc
-from linemod_pose_estimation_amd import MATCH_DTYPE, POSE_REFINE_DTYPE, POSE_VERIFY_DTYPE, cluster_leaders, keep_verified
+from linemod_pose_estimation_amd import MATCH_DTYPE, POSE_REFINE_DTYPE, POSE_VERIFY_DTYPE, ExportedMatches, cluster_leaders, keep_verified
 from linemod_pose_estimation_amd.detector import CLUSTER_DTYPE
 
 DEAD, BROKEN, NO_JOB_BOUNDS, NO_JOB_CLASS, JOB = range(5)          # pc::State
@@ -61,6 +61,19 @@ def build_lists(frames):
     header[:5] = (len(frames), 0, pos[0], pos[1], pos[2])
     return Lists(header, info, np.concatenate(ms) if ms else np.zeros(0, MATCH_DTYPE), np.concatenate(cs) if cs else np.zeros(0, CLUSTER_DTYPE),
                  np.asarray(mem, np.int32))
+
+
+def lists_on_device(L, stream):
+    """L as an export would have left it: an ExportedMatches with clusters whose capacities are the arrays' lengths"""
+    import torch
+    res = ExportedMatches(len(L.frame_info), True, (len(L.matches), len(L.clusters), len(L.members)), stream, torch.cuda.current_device())
+    with torch.cuda.stream(stream):
+        res.header.copy_(torch.from_numpy(L.header.view(np.int32)))
+        res.frame_info.copy_(torch.from_numpy(L.frame_info))
+        res.matches.copy_(torch.from_numpy(np.ascontiguousarray(L.matches).view(np.int32).reshape(-1, 5)))
+        res.clusters.copy_(torch.from_numpy(np.ascontiguousarray(L.clusters).view(np.uint8).reshape(-1, 48)))
+        res.members.copy_(torch.from_numpy(L.members))
+    return res
 
 
 def frame_leaders(L, f):

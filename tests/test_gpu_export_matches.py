@@ -342,3 +342,64 @@ def test_refusals_leave_the_enqueue_and_the_context_usable(cfg):
     same_matches(det.collect(1)[0], cfg.ref["B"][0], "collect after the refusals")
     del arena
     det.close()
+
+
+# ---- clone() of every exported result ------------------------------------------------------------------------------------------------------------
+CLONE_TENSORS = ("header", "frame_info", "matches", "clusters", "members", "diffs", "ndiffs", "cluster_class", "chain_header", "leaders", "rough", "member_group",
+                 "poses", "checks", "keep")
+CLONE_PLAIN = ("caps", "cap", "cap_members", "n_frames", "score", "with_clusters", "with_classes", "stream")
+# caps = (cap_matches, cap_clusters, cap_members) -> the objects to copy: every optional tensor present, and where the class has optional ones, absent
+CLONE_CASES = {
+    "ExportedMatches": lambda caps, *on: [D.ExportedMatches(2, True, caps, *on), D.ExportedMatches(2, False, caps, *on)],
+    "ExportedClusters": lambda caps, *on: [D.ExportedClusters(2, 2, True, caps, *on), D.ExportedClusters(2, 1, False, caps, *on), D.ExportedClusters(2, 0, False, caps, *on)],
+    "ExportedPoses": lambda caps, *on: [D.ExportedPoses(max(caps[1], 1), *on)],
+    "ExportedRoughPoses": lambda caps, *on: [D.ExportedRoughPoses(max(caps[1], 1), caps[2], *on)],
+}
+
+
+@pytest.mark.parametrize("name", sorted(CLONE_CASES))
+def test_clone_copies_every_tensor_and_attribute(name):
+    stream, dev = torch.cuda.Stream(), torch.cuda.current_device()
+    for caps in ((3, 2, 5), (0, 0, 0)):         # zero capacities: the tensor keeps one element, the view of it is empty
+        for src in CLONE_CASES[name](caps, stream, dev):
+            what = (name, caps, sorted(src._backing))
+            with torch.cuda.stream(stream):
+                for i, t in enumerate(src._backing.values()):
+                    t.view(torch.uint8).fill_(0x11 * (i + 1))
+            cp = src.clone()
+            stream.synchronize()
+            assert type(cp) is type(src) and sorted(vars(cp)) == sorted(vars(src)), what
+            for k in CLONE_PLAIN:
+                assert hasattr(cp, k) == hasattr(src, k), (what, k)
+                if hasattr(src, k):
+                    assert getattr(cp, k) == getattr(src, k) and type(getattr(cp, k)) is type(getattr(src, k)), (what, k)
+            assert list(cp._backing) == list(src._backing), what
+            seen = 0
+            for i, (k, t) in enumerate(cp._backing.items()):
+                assert t.shape == src._backing[k].shape and t.dtype == src._backing[k].dtype and t.device == src._backing[k].device, (what, k)
+                assert torch.equal(t, src._backing[k]) and bool((t.view(torch.uint8) == 0x11 * (i + 1)).all()), (what, k)
+            for k in CLONE_TENSORS:
+                assert hasattr(cp, k) == hasattr(src, k), (what, k)
+                a, b = getattr(src, k, None), getattr(cp, k, None)
+                assert (a is None) == (b is None), (what, k)
+                if a is None:
+                    continue
+                seen += 1
+                assert a.shape == b.shape and a.dtype == b.dtype and a.stride() == b.stride(), (what, k)
+                # each is its own object's tensor or a view of it (an empty view has no address to compare)
+                assert (b is cp._backing[k] or b._base is cp._backing[k]) and (a is src._backing[k] or a._base is src._backing[k]), (what, k)
+                assert a.numel() == 0 or (b.data_ptr() == cp._backing[k].data_ptr() and a.data_ptr() == src._backing[k].data_ptr()), (what, k)
+                assert torch.equal(a, b), (what, k)
+            assert seen == len(src._backing), what          # every tensor has its named view
+            if hasattr(src, "matches"):
+                assert src.similarity.dtype == torch.float32 and torch.equal(src.similarity.view(torch.int32), cp.similarity.view(torch.int32)), what
+            else:
+                assert not hasattr(cp, "similarity"), what
+            theirs = {t.data_ptr() for t in src._backing.values()}
+            assert 0 not in theirs and not theirs & {t.data_ptr() for t in cp._backing.values()}, what
+            assert not theirs & {getattr(cp, k).data_ptr() for k in CLONE_TENSORS if getattr(cp, k, None) is not None}, what
+            with torch.cuda.stream(stream):
+                for t in src._backing.values():         # what is written to the original afterwards does not reach the copy
+                    t.view(torch.uint8).fill_(0xEE)
+            stream.synchronize()
+            assert all(bool((t.view(torch.uint8) == 0x11 * (i + 1)).all()) for i, t in enumerate(cp._backing.values())), what

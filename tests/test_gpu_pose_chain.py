@@ -12,7 +12,8 @@ import torch
 import pose_chain_cases as pcc
 import pose_refine_cases as prc
 import pose_verify_cases as pvc
-from linemod_pose_estimation_amd import POSE_REFINE_DTYPE, POSE_VERIFY_DTYPE, DepthTemplates, ExportedMatches, _lib
+from linemod_pose_estimation_amd import POSE_REFINE_DTYPE, POSE_VERIFY_DTYPE, DepthTemplates, _lib
+from linemod_pose_estimation_amd.detector import _chain_inputs, _chain_outputs
 from test_gpu_export_clusters import FX, FY, S, cfg, collect, export, scene_of, upload_enqueue  # noqa: F401  (cfg is a fixture)
 
 pytestmark = pytest.mark.gpu
@@ -199,23 +200,10 @@ def test_end_to_end_without_the_host_in_between(cfg):  # noqa: F811
     assert kept[0][0].to_host()[2].tobytes() != kept[1][0].to_host()[2].tobytes()        # the two scenes gave different poses
 
 
-def lists_on_device(L, stream):
-    """L as an export would have left it: an ExportedMatches with clusters whose capacities are the arrays' lengths"""
-    dev = torch.cuda.current_device()
-    res = ExportedMatches(len(L.frame_info), True, (len(L.matches), len(L.clusters), len(L.members)), stream, dev)
-    with torch.cuda.stream(stream):
-        res.header.copy_(torch.from_numpy(L.header.view(np.int32)))
-        res.frame_info.copy_(torch.from_numpy(L.frame_info))
-        res.matches.copy_(torch.from_numpy(np.ascontiguousarray(L.matches).view(np.int32).reshape(-1, 5)))
-        res.clusters.copy_(torch.from_numpy(np.ascontiguousarray(L.clusters).view(np.uint8).reshape(-1, 48)))
-        res.members.copy_(torch.from_numpy(L.members))
-    return res
-
-
 def test_refusals_come_before_anything_is_queued(constructed):
     t, rects, L = constructed
     stream = torch.cuda.current_stream()
-    res = lists_on_device(L, stream)
+    res = pcc.lists_on_device(L, stream)
     want = pcc.host_staged(t, L, {0, 2}, 0, PR, PV, THRESH, rects)
     out = t.pose_chain(res, THRESH, class_index=0, rects=rects, **KW)
     first = out.to_host()
@@ -229,10 +217,8 @@ def test_refusals_come_before_anything_is_queued(constructed):
         args = dict(KW, class_index=0, rects=rects if templates is None else None)
         args.update(kw)
         d, alive = tt._pose_chain_desc(3, args.pop("keep_thresh", THRESH), args.pop("class_index"), args.pop("class_base", None), **args)
-        b, o = res._backing, out._backing
-        d.header, d.frame_info, d.matches, d.cap_matches = b["header"].data_ptr(), b["frame_info"].data_ptr(), b["matches"].data_ptr(), res.caps[0]
-        d.clusters, d.cap_clusters, d.members, d.cap_members = b["clusters"].data_ptr(), res.caps[1], b["members"].data_ptr(), res.caps[2]
-        d.chain_header, d.leaders, d.poses, d.checks, d.keep = (o[k].data_ptr() for k in ("chain_header", "leaders", "poses", "checks", "keep"))
+        _chain_inputs(d, res)
+        _chain_outputs(d, out.NAMES, {k: v.data_ptr() for k, v in out._backing.items()})
         if change:
             change(d, alive)
         with pytest.raises(_lib.LmxError) as e:

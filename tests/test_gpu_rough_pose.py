@@ -17,7 +17,8 @@ import pose_chain_cases as pcc
 import pose_refine_cases as prc
 import pose_verify_cases as pvc
 import rough_pose_cases as rpc
-from linemod_pose_estimation_amd import POSE_REFINE_DTYPE, DepthTemplates, ExportedMatches, ExportedRoughPoses, RoughModel, _lib, keep_verified, render_views
+from linemod_pose_estimation_amd import POSE_REFINE_DTYPE, DepthTemplates, ExportedRoughPoses, RoughModel, _lib, keep_verified, render_views
+from linemod_pose_estimation_amd.detector import _chain_inputs, _chain_outputs
 from rough_pose_cases import EMPTY, FLAG_ROUGH, INVALID_VIEW, JOB, OK, WINDOW_TOO_LARGE, rot
 from test_gpu_export_clusters import FX, FY, N_T, S, cfg, export, scene_of, upload_enqueue  # noqa: F401  (cfg is a fixture)
 
@@ -283,18 +284,6 @@ def test_real_export_equals_the_hook_on_the_same_lists(cfg):  # noqa: F811
 
 
 # ---- refusals ------------------------------------------------------------------------------------------------------------------------------------
-def lists_on_device(L, stream):
-    dev = torch.cuda.current_device()
-    res = ExportedMatches(len(L.frame_info), True, (len(L.matches), len(L.clusters), len(L.members)), stream, dev)
-    with torch.cuda.stream(stream):
-        res.header.copy_(torch.from_numpy(L.header.view(np.int32)))
-        res.frame_info.copy_(torch.from_numpy(L.frame_info))
-        res.matches.copy_(torch.from_numpy(np.ascontiguousarray(L.matches).view(np.int32).reshape(-1, 5)))
-        res.clusters.copy_(torch.from_numpy(np.ascontiguousarray(L.clusters).view(np.uint8).reshape(-1, 48)))
-        res.members.copy_(torch.from_numpy(L.members))
-    return res
-
-
 def test_refusals_come_before_anything_is_queued():
     tri, views, scene, L = chain_setup()
     model = model_of(views, tri=tri)
@@ -304,7 +293,7 @@ def test_refusals_come_before_anything_is_queued():
     try:
         t.upload_scene(scene)
         stream = torch.cuda.current_stream()
-        res = lists_on_device(L, stream)
+        res = pcc.lists_on_device(L, stream)
         out = t.rough_pose_chain(res, model, THRESH, **KW)
         first = out.to_host()
         hook = run_hook(t, model, L, rpc.trace_min_of(10.0), room=0)
@@ -317,10 +306,8 @@ def test_refusals_come_before_anything_is_queued():
             args.update(kw)
             d, alive = tt._rough_chain_desc(model, 3, args.pop("keep_thresh", THRESH), 10.0, args.pop("trace_min", None), args.pop("class_index", -1),
                                             args.pop("model_camera"), args.pop("scene_camera"), **args)
-            b, o = res._backing, out._backing
-            d.header, d.frame_info, d.matches, d.cap_matches = b["header"].data_ptr(), b["frame_info"].data_ptr(), b["matches"].data_ptr(), res.caps[0]
-            d.clusters, d.cap_clusters, d.members, d.cap_members = b["clusters"].data_ptr(), res.caps[1], b["members"].data_ptr(), res.caps[2]
-            d.chain_header, d.rough, d.member_group, d.poses, d.checks, d.keep = (o[k].data_ptr() for k in out.NAMES)
+            _chain_inputs(d, res)
+            _chain_outputs(d, out.NAMES, {k: v.data_ptr() for k, v in out._backing.items()})
             if change:
                 change(d, alive)
             with pytest.raises(_lib.LmxError) as e:
