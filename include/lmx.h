@@ -991,9 +991,32 @@ lmx_status lmx_pose_refine_matches(lmx_depth_templates* templates, const lmx_ima
  * A pure host function. */
 lmx_status lmx_pose_compose(const lmx_mesh_view* view, const lmx_pose_refine_t* refined, double R_obj[9], double t_obj_m[3]);
 /* Test hook: one match against one host frame; next to its record the integer sums of every pass the device ran, sums[max_iterations + 1][17]
- * (rows of passes that did not run are zeros). */
+ * (rows of passes that did not run are zeros); under a schedule sums[sum of the stages' max_iterations + 1][17], in the order the passes ran. */
 lmx_status lmx_debug_pose_refine_sums(lmx_depth_templates* templates, const lmx_image* depth, const lmx_match_t* match,
                                       const lmx_pose_refine_params* params, lmx_pose_refine_t* out, int64_t* sums);
+/* A refinement schedule: 1 to LMX_POSE_MAX_STAGES stages where lmx_pose_refine_params describes one -- the reference's icpPoseRefine runs a
+ * coarse alignment and a fine one that starts from it, over a thinned model cloud.  Every stage has its own correspondence distance,
+ * stopping rule, window and a stride in {1, 2, 4, 8}: its passes take only the crop pixels (i, j) with i % stride == 0 and
+ * j % stride == 0, and cost in proportion.  A stage starts from the pose the one before it left; all stages run inside the one launch.
+ * A stage that is not the last needs max_iterations >= 1 and runs no measuring pass; the last one behaves as a call without a schedule
+ * does.  In a record, iterations is the total over the stages, status that of the last stage that ran, and `reserved` the index of the
+ * stage that finished it.  The definition is the SCHEDULE paragraph of csrc/lmx_pose_refine.hpp; one stage of stride 1 that repeats the
+ * parameters gives the bytes of a call without a schedule.
+ * The schedule is a property of the object, like enable_normals; lmx_depth_templates_append keeps the destination's.  While one is set,
+ * lmx_pose_refine_matches, lmx_debug_pose_refine_sums, lmx_pose_chain_on, lmx_debug_pose_chain, lmx_rough_pose_chain_on and
+ * lmx_debug_rough_pose_chain refine by it: of their lmx_pose_refine_params they take the cameras, min_pairs and rects; max_dist_mm,
+ * eps_rot_rad, eps_trans_mm, max_iterations and search_radius are still range-checked but not read.  stages == NULL or n_stages == 0
+ * clears it.  The setter waits for nothing: a call reads the schedule on the host and hands it to its kernel by value, so work that is
+ * already queued is never affected.  LMX_ERR_INVALID_ARG, the previous schedule staying in place: n_stages outside 0..4; NULL stages with
+ * n_stages > 0; a field outside the range lmx_pose_refine_params gives it, or a NaN; another stride; a non-zero `reserved`; a stage in
+ * front of the last with max_iterations == 0.  get: the stages set (the rest of out[] zeroed) and their number, 0 for none. */
+typedef struct lmx_pose_refine_stage {
+  double max_dist_mm, eps_rot_rad, eps_trans_mm;
+  int32_t max_iterations, search_radius, stride, reserved;
+} lmx_pose_refine_stage;
+enum { LMX_POSE_MAX_STAGES = 4 };
+lmx_status lmx_depth_templates_set_refine_schedule(lmx_depth_templates* templates, const lmx_pose_refine_stage* stages, int32_t n_stages);
+lmx_status lmx_depth_templates_get_refine_schedule(const lmx_depth_templates* templates, lmx_pose_refine_stage out[LMX_POSE_MAX_STAGES], int32_t* n_stages);
 
 /* ---- verification of refined poses against the scene's voxel occupancy (the reference's hypothesisVerification) -------------------------
  * The step after icpPoseRefine: the share of the posed model cloud's points that fall into a voxel holding a scene point.  The model

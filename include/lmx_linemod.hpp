@@ -439,6 +439,18 @@ class DepthTemplates {
     p.max_iterations = 20; p.min_pairs = 16; p.search_radius = 1;
     return p;
   }
+  // The refinement schedule of this object (lmx_depth_templates_set_refine_schedule): 1 to 4 stages, each with its own correspondence
+  // distance, stopping rule, window and stride, fed into one another; an empty vector clears it.  While one is set, refinePoses and the
+  // chains refine by it and take the cameras, min_pairs and rects from their own parameters.
+  void setRefineSchedule(const std::vector<lmx_pose_refine_stage>& stages) {
+    check(lmx_depth_templates_set_refine_schedule(h_, stages.empty() ? nullptr : stages.data(), (int32_t)stages.size()));
+  }
+  std::vector<lmx_pose_refine_stage> refineSchedule() const {
+    lmx_pose_refine_stage out[LMX_POSE_MAX_STAGES];
+    int32_t n = 0;
+    check(lmx_depth_templates_get_refine_schedule(h_, out, &n));
+    return std::vector<lmx_pose_refine_stage>(out, out + n);
+  }
   // The object's pose in the scene camera from the matched template's view and its refinePoses record (lmx_pose_compose).
   static void composePose(const lmx_mesh_view& view, const lmx_pose_refine_t& refined, double R_obj[9], double t_obj_m[3]) {
     check(lmx_pose_compose(&view, &refined, R_obj, t_obj_m));

@@ -35,6 +35,7 @@ SYMBOLS = [
     "lmx_ctx_export_matches_on", "lmx_ctx_debug_enqueue_labels",
     "lmx_ctx_export_clusters_on", "lmx_debug_depth_walk_records", "lmx_debug_depth_walk_grid",
     "lmx_pose_refine_matches", "lmx_pose_compose", "lmx_debug_pose_refine_sums",
+    "lmx_depth_templates_set_refine_schedule", "lmx_depth_templates_get_refine_schedule",
     "lmx_pose_verify_matches", "lmx_pose_verify_keep",
     "lmx_pose_chain_on", "lmx_debug_pose_chain",
     "lmx_rough_model_create", "lmx_rough_model_free", "lmx_rough_model_device_bytes", "lmx_rough_trace_min", "lmx_rough_pose_chain_on",
@@ -152,6 +153,14 @@ class PoseRefineParams(C.Structure):   # lmx_pose_refine_params
                 ("scene_fx", C.c_double), ("scene_fy", C.c_double), ("scene_cx", C.c_double), ("scene_cy", C.c_double),
                 ("max_dist_mm", C.c_double), ("eps_rot_rad", C.c_double), ("eps_trans_mm", C.c_double),
                 ("max_iterations", C.c_int32), ("min_pairs", C.c_int32), ("search_radius", C.c_int32), ("rects", C.c_void_p)]
+
+
+class PoseRefineStage(C.Structure):   # lmx_pose_refine_stage
+    _fields_ = [("max_dist_mm", C.c_double), ("eps_rot_rad", C.c_double), ("eps_trans_mm", C.c_double),
+                ("max_iterations", C.c_int32), ("search_radius", C.c_int32), ("stride", C.c_int32), ("reserved", C.c_int32)]
+
+
+LMX_POSE_MAX_STAGES = 4
 
 
 class PoseVerifyParams(C.Structure):   # lmx_pose_verify_params
@@ -377,6 +386,8 @@ def lib():
     L.lmx_debug_rough_pose_chain.argtypes = [vp, vp, C.POINTER(RoughChainDesc)]
     L.lmx_debug_rough_crop.argtypes = [vp, C.c_int32, vp, vp]
     L.lmx_debug_pose_refine_sums.argtypes = [vp, C.POINTER(Image), vp, C.POINTER(PoseRefineParams), vp, vp]
+    L.lmx_depth_templates_set_refine_schedule.argtypes = [vp, C.POINTER(PoseRefineStage), C.c_int32]
+    L.lmx_depth_templates_get_refine_schedule.argtypes = [vp, C.POINTER(PoseRefineStage), C.POINTER(C.c_int32)]
     L.lmx_depth_value.argtypes = [C.POINTER(DepthDiff), C.c_double]
     L.lmx_depth_value.restype = C.c_double
     L.lmx_depth_templates_upload_scene.argtypes = [vp, C.POINTER(Image), C.c_int32]

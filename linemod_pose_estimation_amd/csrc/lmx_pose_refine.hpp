@@ -64,6 +64,23 @@
 //   n < min_pairs: status LOST, n_pairs_last = n, rms_last_mm = rms, the pose stays, stop.
 //   Solve, update, iterations = k + 1.  Converged: status CONVERGED, final.  Else k + 1 == max_iterations: final.
 //   So iterations + 1 passes run, the last one only fills n_pairs_last / rms_last_mm (unless LOST), and the record carries the last pose.
+//
+// SCHEDULE (refine_job_staged; lmx_depth_templates_set_refine_schedule)  1 to 4 stages where the above has one; the reference's icpPoseRefine
+//   runs a coarse and a fine alignment fed into one another (src/rgbdDetector.cpp:1314-1367) over a thinned model cloud (:1294-1295).  A stage
+//   has its own max_dist_mm, eps_rot_rad, eps_trans_mm, max_iterations, search_radius, each in the range above, and a stride in {1, 2, 4, 8};
+//   a stage that is not the last has max_iterations >= 1.  The cameras and min_pairs are those of the parameters, for every stage.
+//   STEP 0 is unchanged: every crop pixel takes part, n_model counts every pixel, m0 is the one centroid of all stages.
+//   The selected pixels of a stage are the crop pixels with t != 0, i % stride == 0 and j % stride == 0 (i, j crop-local: the rect plays
+//   no part; the crop of a rough pose, lmx_rough_pose_chain_on, is the silhouette box of its render, lmx_rough_pose_t's rect).  A pass of the stage is PASS k over the selected pixels alone, under the stage's dmax and search_radius; a selected pixel's
+//   arithmetic is unchanged.
+//   Control: stage 0 starts from the placement's pose, q included; inside a stage the passes count from k = 0 and the stage starts with
+//   status = MAX_ITERATIONS.  The first pass of stage 0 fills n_pairs_first / rms_first_mm.  n < min_pairs in any pass that would solve:
+//   status LOST, n_pairs_last = n, rms_last_mm = rms, the pose stays, everything stops.  A stage that is not the last: solve, update with the
+//   stage's eps, iterations += 1; converged: status CONVERGED; converged or k + 1 == max_iterations: the stage ends -- it runs no measuring
+//   pass, and pass 0 of the next stage runs under exactly the q, R, t it left.  The last stage is CONTROL with the stage's parameters, its
+//   measuring pass included.  iterations is the total over the stages, status that of the last stage that ran, reserved the index of the
+//   stage in which the record was finished (0 for NO_OVERLAP).  One stage of stride 1 is refine_job in every byte.
+//   The debug sums are [sum of max_iterations + 1][17], one row per pass in the order the passes ran.
 #pragma once
 
 #include <math.h>
@@ -118,6 +135,13 @@ struct Record {   // the bytes of lmx_pose_refine_t
   int32_t n_model, n_pairs_first, n_pairs_last, iterations, status, reserved;
 };
 struct Control { int32_t final_pass; };
+constexpr int kMaxStages = 4;
+struct Stage {   // the bytes of lmx_pose_refine_stage
+  double max_dist_mm, eps_rot_rad, eps_trans_mm;
+  int32_t max_iterations, search_radius, stride, pad;
+};
+struct Schedule { int32_t n_stages, pad; Stage stage[kMaxStages]; };
+struct StagedControl { int32_t stage, k, final_pass; };   // the stage, the pass inside it, "this pass only measures"
 
 LMX_PR_FN Inverse inverse_of(const Camera& cam) { return Inverse{1.0 / cam.fx, 1.0 / cam.fy}; }
 
@@ -188,7 +212,8 @@ LMX_PR_FN void centre_of(const Pose& pose, const double m0[3], double c[3], int6
   for (int k = 0; k < 3; ++k) C[k] = (int64_t)llrint(16.0 * c[k]);
 }
 
-LMX_PR_FN int64_t max_dist_ticks(const Params& P) { return (int64_t)llrint(16.0 * P.max_dist_mm); }
+LMX_PR_FN int64_t dist_ticks(double max_dist_mm) { return (int64_t)llrint(16.0 * max_dist_mm); }
+LMX_PR_FN int64_t max_dist_ticks(const Params& P) { return dist_ticks(P.max_dist_mm); }
 
 LMX_PR_FN bool within(double a, double bound) { return a >= -bound && a <= bound; }   // false for a NaN
 
@@ -245,13 +270,19 @@ LMX_PR_FN void pass_pixel_r(const Params& P, const Inverse& im, const Inverse& i
   a[16] += best;
 }
 
-LMX_PR_FN void pass_pixel(const Params& P, const Inverse& im, const Inverse& is, const Pose& pose, const int64_t C[3], int64_t dmax, int32_t rect_x, int32_t rect_y, int32_t i, int32_t j,
-                          uint16_t t, const uint16_t* frame, int32_t W, int32_t H, size_t scene_pitch, int64_t a[kSums]) {
-  switch (P.search_radius) {
+// radius: the search radius in force (a stage's, or the parameters'); of P the cameras alone are read.
+LMX_PR_FN void pass_pixel_rad(const Params& P, int32_t radius, const Inverse& im, const Inverse& is, const Pose& pose, const int64_t C[3], int64_t dmax, int32_t rect_x, int32_t rect_y,
+                              int32_t i, int32_t j, uint16_t t, const uint16_t* frame, int32_t W, int32_t H, size_t scene_pitch, int64_t a[kSums]) {
+  switch (radius) {
     case 0: pass_pixel_r<0>(P, im, is, pose, C, dmax, rect_x, rect_y, i, j, t, frame, W, H, scene_pitch, a); break;
     case 1: pass_pixel_r<1>(P, im, is, pose, C, dmax, rect_x, rect_y, i, j, t, frame, W, H, scene_pitch, a); break;
     default: pass_pixel_r<2>(P, im, is, pose, C, dmax, rect_x, rect_y, i, j, t, frame, W, H, scene_pitch, a); break;
   }
+}
+
+LMX_PR_FN void pass_pixel(const Params& P, const Inverse& im, const Inverse& is, const Pose& pose, const int64_t C[3], int64_t dmax, int32_t rect_x, int32_t rect_y, int32_t i, int32_t j,
+                          uint16_t t, const uint16_t* frame, int32_t W, int32_t H, size_t scene_pitch, int64_t a[kSums]) {
+  pass_pixel_rad(P, P.search_radius, im, is, pose, C, dmax, rect_x, rect_y, i, j, t, frame, W, H, scene_pitch, a);
 }
 
 LMX_PR_FN double rms_of(const int64_t a[kSums]) { return a[0] > 0 ? sqrt((double)a[16] / (double)a[0]) / 16.0 : 0.0; }
@@ -303,7 +334,7 @@ LMX_PR_FN void solve(const int64_t a[kSums], double w[3], double v[3]) {
 }
 
 // The pose after the step (w, v) about the centre c; true when the step is below both thresholds.
-LMX_PR_FN bool update(const Params& P, const double w[3], const double v[3], const double c[3], Pose* pose) {
+LMX_PR_FN bool update_eps(double eps_rot_rad, double eps_trans_mm, const double w[3], const double v[3], const double c[3], Pose* pose) {
   const double h[3] = {w[0] / 2.0, w[1] / 2.0, w[2] / 2.0};
   const double g = sqrt(((1.0 + h[0] * h[0]) + h[1] * h[1]) + h[2] * h[2]);
   const double dq[4] = {1.0 / g, h[0] / g, h[1] / g, h[2] / g};
@@ -320,7 +351,10 @@ LMX_PR_FN bool update(const Params& P, const double w[3], const double v[3], con
   for (int k = 0; k < 3; ++k) pose->t[k] = (c[k] + ((dR[3 * k] * e[0] + dR[3 * k + 1] * e[1]) + dR[3 * k + 2] * e[2])) + v[k] / 16.0;
   for (int k = 0; k < 4; ++k) pose->q[k] = n[k] / len;
   rotation_of(pose->q, pose->R);
-  return sqrt((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2]) <= P.eps_rot_rad && sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]) / 16.0 <= P.eps_trans_mm;
+  return sqrt((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2]) <= eps_rot_rad && sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]) / 16.0 <= eps_trans_mm;
+}
+LMX_PR_FN bool update(const Params& P, const double w[3], const double v[3], const double c[3], Pose* pose) {
+  return update_eps(P.eps_rot_rad, P.eps_trans_mm, w, v, c, pose);
 }
 
 // ---- control --------------------------------------------------------------------------------------------------------------------------
@@ -349,6 +383,100 @@ LMX_PR_FN bool after_pass(const Params& P, int32_t k, const int64_t a[kSums], co
     for (int q = 0; q < 3; ++q) r->t_mm[q] = pose->t[q];
   }
   return more;
+}
+
+// ---- the same under a schedule (SCHEDULE above) ---------------------------------------------------------------------------------------------
+// The one-stage schedule that is the parameters themselves: what a call without a schedule runs.
+LMX_PR_FN Schedule single_stage(const Params& P) {
+  Schedule S = {1, 0, {}};
+  for (int k = 0; k < kMaxStages; ++k) S.stage[k] = Stage{P.max_dist_mm, P.eps_rot_rad, P.eps_trans_mm, P.max_iterations, P.search_radius, 1, 0};
+  return S;
+}
+
+// Rows of the debug sums: the most passes a schedule can run.
+LMX_PR_FN int32_t schedule_passes(const Schedule& S) {
+  int32_t n = 1;
+  for (int32_t k = 0; k < S.n_stages; ++k) n += S.stage[k].max_iterations;
+  return n;
+}
+
+LMX_PR_FN void enter_stage(const Schedule& S, int32_t stage, Record* r, StagedControl* sc) {
+  sc->stage = stage;
+  sc->k = 0;
+  sc->final_pass = stage == S.n_stages - 1 && S.stage[stage].max_iterations == 0;
+  r->status = MAX_ITERATIONS;
+}
+
+// after_pass under a schedule: what follows pass sc->k of stage sc->stage.  True: another pass runs, of stage sc->stage as this leaves it.
+LMX_PR_FN bool after_pass_staged(const Params& P, const Schedule& S, const int64_t a[kSums], const double c[3], Pose* pose, Record* r, StagedControl* sc) {
+  const Stage& st = S.stage[sc->stage];
+  const bool last = sc->stage == S.n_stages - 1;
+  const int32_t n = (int32_t)a[0];
+  const double rms = rms_of(a);
+  bool more = false;
+  if (sc->stage == 0 && sc->k == 0) { r->n_pairs_first = n; r->rms_first_mm = rms; }
+  if (sc->final_pass) {
+    r->n_pairs_last = n; r->rms_last_mm = rms;
+  } else if (n < P.min_pairs) {
+    r->status = LOST; r->n_pairs_last = n; r->rms_last_mm = rms;
+  } else {
+    double w[3], v[3];
+    solve(a, w, v);
+    const bool converged = update_eps(st.eps_rot_rad, st.eps_trans_mm, w, v, c, pose);
+    r->iterations += 1;
+    if (converged) r->status = CONVERGED;
+    const bool done = converged || sc->k + 1 >= st.max_iterations;
+    sc->k += 1;
+    if (last) sc->final_pass = done;
+    else if (done) enter_stage(S, sc->stage + 1, r, sc);
+    more = true;
+  }
+  if (!more) {
+    r->reserved = sc->stage;
+    for (int q = 0; q < 9; ++q) r->R[q] = pose->R[q];
+    for (int q = 0; q < 3; ++q) r->t_mm[q] = pose->t[q];
+  }
+  return more;
+}
+
+// refine_job under a schedule.  sums (may be null): [schedule_passes(S)][kSums], one row per pass in the order the passes ran.
+LMX_PR_FN void refine_job_staged(const Params& P, const Schedule& S, const uint16_t* crop, int32_t w, int32_t h, int32_t pitch, int32_t rect_x, int32_t rect_y,
+                                 const uint16_t* scene, int32_t W, int32_t H, size_t scene_pitch, int32_t x, int32_t y, Record* r, int64_t* sums) {
+  int64_t place[kPlaceSums] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int32_t i = 0; i < h; ++i) {
+    int32_t Y = 0;
+    const bool row_in = dv::scene_row(y, i, H, &Y);
+    for (int32_t j = 0; j < w; ++j) {
+      const uint16_t t = crop[(size_t)i * (size_t)pitch + j];
+      if (t == 0) continue;
+      int32_t X = 0;
+      const bool met = row_in && dv::scene_col(x, j, W, &X);
+      place_pixel(rect_x, rect_y, i, j, t, X, Y, met ? scene[(size_t)Y * scene_pitch + (size_t)X] : (uint16_t)0, place);
+    }
+  }
+  Pose pose;
+  Control ctl = {0};
+  StagedControl sc = {0, 0, 0};
+  double m0[3];
+  if (!placement(P, place, m0, &pose, r, &ctl)) return;
+  enter_stage(S, 0, r, &sc);
+  const Inverse im = inverse_of(P.model), is = inverse_of(P.scene);
+  for (int32_t pass = 0;; ++pass) {
+    const Stage& st = S.stage[sc.stage];
+    const int64_t dmax = dist_ticks(st.max_dist_mm);
+    double c[3];
+    int64_t C[3], a[kSums];
+    for (int q = 0; q < kSums; ++q) a[q] = 0;
+    centre_of(pose, m0, c, C);
+    for (int32_t i = 0; i < h; i += st.stride)
+      for (int32_t j = 0; j < w; j += st.stride) {
+        const uint16_t t = crop[(size_t)i * (size_t)pitch + j];
+        if (t != 0) pass_pixel_rad(P, st.search_radius, im, is, pose, C, dmax, rect_x, rect_y, i, j, t, scene, W, H, scene_pitch, a);
+      }
+    if (sums)
+      for (int q = 0; q < kSums; ++q) sums[(size_t)pass * kSums + q] = a[q];
+    if (!after_pass_staged(P, S, a, c, &pose, r, &sc)) return;
+  }
 }
 
 // One whole job, pixel by pixel on one thread: the definition the kernel is tested against.  crop: [h][pitch]; scene: H rows of scene_pitch
@@ -401,6 +529,21 @@ LMX_PR_FN const char* check_params(const Params& P) {
   if (P.max_iterations < 0 || P.max_iterations > kMaxIterations) return "max_iterations must lie in 0 .. 64";
   if (P.min_pairs < 3) return "min_pairs must be >= 3";
   if (P.search_radius < 0 || P.search_radius > kMaxSearchRadius) return "search_radius must lie in 0 .. 2";
+  return nullptr;
+}
+
+// Why a schedule is refused (null: it is fine), its stages' fields in the ranges check_params gives them.
+LMX_PR_FN const char* check_schedule(const Schedule& S) {
+  if (S.n_stages < 1 || S.n_stages > kMaxStages) return "a schedule has 1 .. 4 stages";
+  for (int32_t k = 0; k < S.n_stages; ++k) {
+    const Stage& st = S.stage[k];
+    if (!(st.max_dist_mm > 0.0 && st.max_dist_mm <= kMaxDistMm)) return "a stage's max_dist_mm must lie in (0, 1024]";
+    if (!(st.eps_rot_rad >= 0.0) || !(st.eps_trans_mm >= 0.0)) return "a stage's eps_rot_rad and eps_trans_mm must be >= 0";
+    if (st.max_iterations < 0 || st.max_iterations > kMaxIterations) return "a stage's max_iterations must lie in 0 .. 64";
+    if (st.search_radius < 0 || st.search_radius > kMaxSearchRadius) return "a stage's search_radius must lie in 0 .. 2";
+    if (st.stride != 1 && st.stride != 2 && st.stride != 4 && st.stride != 8) return "a stage's stride must be 1, 2, 4 or 8";
+    if (k + 1 < S.n_stages && st.max_iterations < 1) return "a stage that is not the last needs max_iterations >= 1";
+  }
   return nullptr;
 }
 

@@ -249,7 +249,7 @@ __global__ __launch_bounds__(64) void k_rough_finish(const FinishArgs f) {
       r->rect[0] = sx0; r->rect[1] = sy0; r->rect[2] = st[MS_LEVEL + 2] - sx0 + 1; r->rect[3] = st[MS_LEVEL + 3] - sy0 + 1;
       r->n_model = st[MS_COUNT];
       entry = rp::CropEntry{a.window + (size_t)v * a.win_stride, uw, uh, dv::crop_pitch(uw), 0};
-      job.x += ux0 - sx0; job.y += uy0 - sy0; job.rect_x = ux0; job.rect_y = uy0;
+      job.x += ux0 - sx0; job.y += uy0 - sy0; job.rect_x = ux0; job.rect_y = uy0; job.lat_x = sx0 - ux0; job.lat_y = sy0 - uy0;
       atomicAdd(&f.chain_header[rp::C_ROUGH_OK], 1u);
     } else {
       job.run = 0;

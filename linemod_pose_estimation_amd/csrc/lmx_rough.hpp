@@ -13,8 +13,9 @@ namespace rp {
 
 struct CropEntry { const uint16_t* data; int32_t w, h, pitch, pad; };   // the bytes of lmx_verify.hip's DepthCrop
 // What the two pose kernels run for a slot.  run 0: zeroed records.  The crop is the slot's window: x, y place its corner in the scene,
-// rect_x, rect_y in the model camera.
-struct Job { int32_t run, frame, x, y, rect_x, rect_y, pad0, pad1; };
+// rect_x, rect_y in the model camera; lat_x, lat_y: the corner of the render's silhouette box inside the window, where the pixel lattice of
+// a refinement stage of stride > 1 starts (lmx_pose_refine.hpp, SCHEDULE: the crop of a rough pose is that box).
+struct Job { int32_t run, frame, x, y, rect_x, rect_y, lat_x, lat_y; };
 static_assert(sizeof(CropEntry) == 24 && sizeof(Job) == 32, "layouts the kernels rely on");
 
 struct StageArgs {

@@ -27,7 +27,8 @@
 //                  persistent workgroups that take the record count from device memory; see the kernel
 // Pose refinement (lmx_pose_refine_matches; arithmetic and control: lmx_pose_refine.hpp), on the same table and scene:
 //   k_pose_refine  one 256-lane workgroup per match, the same walk over the crop's vectors once per pass, every pass of a job inside one
-//                  launch; see the kernel
+//                  launch; under a refinement schedule (lmx_depth_templates_set_refine_schedule) every pass of every stage, a stage of
+//                  stride > 1 walking a pixel lattice spread over the lanes instead; see the kernel
 // Pose verification (lmx_pose_verify_matches; arithmetic: lmx_pose_verify.hpp), the stage after it:
 //   k_pose_verify  one 256-lane workgroup per match: the crop walk for the voxel grid's extent, a 32 KiB occupancy bitmap in LDS marked
 //                  from the scene pixels of the posed model's region, the crop walk again to count the points in marked voxels; see the kernel
@@ -313,10 +314,12 @@ __global__ __launch_bounds__(256) void k_walk_records_dev(const WalkArgs a) {
 }
 
 // ---- pose refinement (lmx_pose_refine_matches; arithmetic and control: lmx_pose_refine.hpp) ---------------------------------------------------------
-struct PoseJob { int32_t x, y, template_id, frame, rect_x, rect_y, pad0, pad1; };   // frame: as DepthJob's
+struct PoseJob { int32_t x, y, template_id, frame, rect_x, rect_y, lat_x, lat_y; };   // frame: as DepthJob's; lat_x, lat_y: lattice_pixels' origin
 static_assert(sizeof(PoseJob) == 32 && sizeof(lmx_pose_refine_t) == 136 && sizeof(pr::Record) == sizeof(lmx_pose_refine_t), "layouts the kernel relies on");
 static_assert(offsetof(pr::Record, rms_first_mm) == offsetof(lmx_pose_refine_t, rms_first_mm) && offsetof(pr::Record, status) == offsetof(lmx_pose_refine_t, status),
               "pr::Record is lmx_pose_refine_t");
+static_assert(sizeof(pr::Stage) == sizeof(lmx_pose_refine_stage) && offsetof(pr::Stage, stride) == offsetof(lmx_pose_refine_stage, stride) && (int)LMX_POSE_MAX_STAGES == pr::kMaxStages,
+              "pr::Stage is lmx_pose_refine_stage");
 
 // Every crop pixel t != 0 once, f(i, j, t), spread over the workgroup the way diff_walk spreads them: lanes along the rows, one aligned
 // 16-byte vector each, a narrow crop's rows packed into a wave, waves taking rows (groups of rows) in turn.
@@ -353,16 +356,45 @@ __device__ __forceinline__ void wave_sums_to_lds(const int64_t* a, int n, long l
   __syncthreads();
 }
 
-// One 256-lane workgroup per job, every pass of it in this one launch.  A pass: each lane walks its crop pixels under the pose in LDS
-// (pr::pass_pixel: projection, the window of scene reads under the in-image predicate, the pair, its 17 integer terms), wave shuffles,
-// LDS across the four waves; lane 0 adds them, solves, updates (pr::after_pass) and leaves the next pose, its centre and "more" in LDS;
-// a barrier; the next pass.  Integer sums: the result does not depend on which lane took which pixel.  No atomics, no workgroup waits
-// for another.  What is no job (template or frame outside the tables) or has an empty crop gets a zeroed record before any barrier.
-// dbg (null outside the test hook): pass k's sums of job 0 at dbg[k][17].
+// The selected pixels of a stage of stride > 1 (lmx_pose_refine.hpp, SCHEDULE), each once, f(i, j, t): the lattice positions numbered row-major
+// over ceil(h / stride) x ceil(w / stride), the 256 lanes striding over that index, one 2-byte load each (i < h, j < w <= pitch: inside the
+// crop).  crop_pixels would leave all but one lane in `stride` and all but one row in `stride` idle: a pass would cost what a full one costs.
+// (ox, oy): where the lattice starts.  (0, 0) for a stored crop; a rough pose's crop is the silhouette box of its render, which lies at
+// (ox, oy) inside the window the kernel walks (nothing but zeros lies in front of it).  Clamped into the crop: no index leaves it.
+template <typename F>
+__device__ __forceinline__ void lattice_pixels(const DepthCrop& c, int stride, int ox, int oy, int tid, F&& f) {
+  const int shift = 31 - __builtin_clz(stride);   // 1, 2 or 3
+  ox = ox < 0 ? 0 : ox > c.w ? c.w : ox;
+  oy = oy < 0 ? 0 : oy > c.h ? c.h : oy;
+  const int cols = (c.w - ox + stride - 1) >> shift, rows = (c.h - oy + stride - 1) >> shift;
+  const int total = rows * cols;                  // at most 2^26
+#pragma unroll 1
+  for (int p = tid; p < total; p += 256) {
+    const int li = p / cols, lj = p - li * cols;
+    const int i = oy + (li << shift), j = ox + (lj << shift);
+    const uint16_t t = c.data[(size_t)i * c.pitch + j];
+    if (t != 0) f(i, j, t);
+  }
+}
+
+// A value every lane holds alike, told to the compiler as that: scalar registers.
+__device__ __forceinline__ int64_t uniform_i64(int64_t v) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)v >> 32));
+  return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+// One 256-lane workgroup per job, every pass of every stage of it in this one launch.  A pass: each lane walks its crop pixels under the
+// pose in LDS (pr::pass_pixel_rad: projection, the window of scene reads under the in-image predicate, the pair, its 17 integer terms), wave
+// shuffles, LDS across the four waves; lane 0 adds them, solves, updates (pr::after_pass_staged) and leaves the next pose, its centre and
+// "the stage of the next pass, plus one" (0: none) in LDS; a barrier; the next pass.  The stage's parameters are read from the schedule
+// (a kernel argument) under that workgroup-uniform index: scalar loads, no vector registers.  A stage of stride 1 walks with crop_pixels,
+// any other with lattice_pixels.  Integer sums: the result does not depend on which lane took which pixel.  No atomics, no workgroup
+// waits for another.  What is no job (template or frame outside the tables) or has an empty crop gets a zeroed record before any barrier.
+// dbg (null outside the test hook): the sums of job 0's passes, one row of 17 per pass in the order they ran.
 // pose_refine_body is that workgroup's work on one job and its record `out` (dbg: null, or where this job's sums go), shared by
-// k_pose_refine and k_pose_refine_clusters; forceinline: each kernel gets its own copy of the LDS arrays.
+// k_pose_refine, k_pose_refine_clusters and k_rough_refine_clusters; forceinline: each kernel gets its own copy of the LDS arrays.
 __device__ __forceinline__ void pose_refine_body(const DepthCrop* __restrict__ crops, int32_t count, const PoseJob job, const uint16_t* __restrict__ scene,
-                                                 int32_t n_frames, int W, int H, const pr::Params& P, lmx_pose_refine_t* __restrict__ out,
+                                                 int32_t n_frames, int W, int H, const pr::Params& P, const pr::Schedule& S, lmx_pose_refine_t* __restrict__ out,
                                                  long long* __restrict__ dbg) {
   __shared__ long long s_part[4][pr::kSums];
   __shared__ pr::Pose s_pose;
@@ -381,6 +413,7 @@ __device__ __forceinline__ void pose_refine_body(const DepthCrop* __restrict__ c
   pr::Record rec;
   pr::Pose pose0;
   pr::Control ctl = {0};
+  pr::StagedControl sc = {0, 0, 0};
   double m0[3] = {0.0, 0.0, 0.0};
 
   int64_t a[pr::kSums];
@@ -398,6 +431,7 @@ __device__ __forceinline__ void pose_refine_body(const DepthCrop* __restrict__ c
     const bool more = pr::placement(P, place, m0, &pose0, &rec, &ctl);
     if (more) {
       int64_t C[3];
+      pr::enter_stage(S, 0, &rec, &sc);
       pr::centre_of(pose0, m0, s_c, C);
       s_pose = pose0;
       for (int k = 0; k < 3; ++k) s_C[k] = C[k];
@@ -408,23 +442,28 @@ __device__ __forceinline__ void pose_refine_body(const DepthCrop* __restrict__ c
   }
   __syncthreads();
   if (!s_more) return;
-  const int64_t dmax = pr::max_dist_ticks(P);
   const pr::Inverse im = pr::inverse_of(P.model), is = pr::inverse_of(P.scene);
-  for (int32_t k = 0; k <= pr::kMaxIterations; ++k) {   // after_pass ends it after max_iterations + 1 passes at the latest
+  int32_t stage = 0;
+  for (int32_t pass = 0; pass <= pr::kMaxStages * pr::kMaxIterations; ++pass) {   // after_pass_staged ends it after schedule_passes(S) passes at the latest
+    const pr::Stage& st = S.stage[stage];
+    const int64_t dmax = uniform_i64(pr::dist_ticks(st.max_dist_mm));
+    const int32_t radius = st.search_radius, stride = st.stride;
     const pr::Pose pose = s_pose;
     const int64_t C[3] = {s_C[0], s_C[1], s_C[2]};
     for (int q = 0; q < pr::kSums; ++q) a[q] = 0;
-    crop_pixels(c, lane, wave, [&](int i, int j, uint16_t t) {
-      pr::pass_pixel(P, im, is, pose, C, dmax, job.rect_x, job.rect_y, i, j, t, frame, W, H, (size_t)W, a);
-    });
+    auto pixel = [&](int i, int j, uint16_t t) {
+      pr::pass_pixel_rad(P, radius, im, is, pose, C, dmax, job.rect_x, job.rect_y, i, j, t, frame, W, H, (size_t)W, a);
+    };
+    if (stride == 1) crop_pixels(c, lane, wave, pixel);
+    else lattice_pixels(c, stride, job.lat_x, job.lat_y, tid, pixel);
     wave_sums_to_lds(a, pr::kSums, s_part, lane, wave);
     if (tid == 0) {
       int64_t total[pr::kSums];
       for (int q = 0; q < pr::kSums; ++q) total[q] = s_part[0][q] + s_part[1][q] + s_part[2][q] + s_part[3][q];
       if (dbg)
-        for (int q = 0; q < pr::kSums; ++q) dbg[(size_t)k * pr::kSums + q] = total[q];
+        for (int q = 0; q < pr::kSums; ++q) dbg[(size_t)pass * pr::kSums + q] = total[q];
       const double cc[3] = {s_c[0], s_c[1], s_c[2]};
-      const bool more = pr::after_pass(P, k, total, cc, &pose0, &rec, &ctl);
+      const bool more = pr::after_pass_staged(P, S, total, cc, &pose0, &rec, &sc);
       if (more) {
         int64_t Cn[3];
         pr::centre_of(pose0, m0, s_c, Cn);
@@ -433,17 +472,19 @@ __device__ __forceinline__ void pose_refine_body(const DepthCrop* __restrict__ c
       } else {
         *reinterpret_cast<pr::Record*>(out) = rec;
       }
-      s_more = more;
+      s_more = more ? sc.stage + 1 : 0;
     }
     __syncthreads();
-    if (!s_more) return;
+    const int next = __builtin_amdgcn_readfirstlane(s_more);
+    if (!next) return;
+    stage = next - 1;
   }
 }
 
 __global__ __launch_bounds__(256) void k_pose_refine(const DepthCrop* __restrict__ crops, int32_t count, const PoseJob* __restrict__ jobs,
-                                                     const uint16_t* __restrict__ scene, int32_t n_frames, int W, int H, const pr::Params P,
+                                                     const uint16_t* __restrict__ scene, int32_t n_frames, int W, int H, const pr::Params P, const pr::Schedule S,
                                                      lmx_pose_refine_t* __restrict__ out, long long* __restrict__ dbg) {
-  pose_refine_body(crops, count, jobs[blockIdx.x], scene, n_frames, W, H, P, &out[blockIdx.x], blockIdx.x == 0 ? dbg : nullptr);
+  pose_refine_body(crops, count, jobs[blockIdx.x], scene, n_frames, W, H, P, S, &out[blockIdx.x], blockIdx.x == 0 ? dbg : nullptr);
 }
 
 // ---- pose verification (lmx_pose_verify_matches; arithmetic: lmx_pose_verify.hpp) ---------------------------------------------------------------------
@@ -634,9 +675,9 @@ __device__ __forceinline__ pc::Slot uniform_slot(const pc::Slot& v) {
 // One 256-lane workgroup per cluster slot, a grid of cap_clusters: the count is in device memory, and a workgroup at or above n_live
 // leaves at once without a store.  Wave 0 decides the slot and leaves it in LDS; one barrier; then either the zeroed record (a dead slot,
 // a broken list, no job) or k_pose_refine's body on the leader's job.  Workgroup 0 also reports n_live and the header's flag; a slot's
-// flags go to chain_header[1] by a vector atomic OR of lane 0.  waves_per_eu(2): the body sits at 251 vector registers; without the
+// flags go to chain_header[1] by a vector atomic OR of lane 0.  waves_per_eu(2): the body sits at 247 vector registers; without the
 // attribute the prologue's scalar spills take the kernel a few registers past 256 and to half of k_pose_refine's occupancy.
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_pose_refine_clusters(const ChainArgs a, const pr::Params P) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_pose_refine_clusters(const ChainArgs a, const pr::Params P, const pr::Schedule S) {
   __shared__ pc::Slot s_slot;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const uint32_t k = blockIdx.x, n_live = pc::n_live(a.L);
@@ -661,7 +702,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
     return;
   }
   const PoseJob job = {s.x, s.y, s.template_id, s.frame, s.rect_x, s.rect_y, 0, 0};
-  pose_refine_body(a.crops, a.T.count, job, a.scene, a.L.n_frames, a.W, a.H, P, &a.poses[k], nullptr);
+  pose_refine_body(a.crops, a.T.count, job, a.scene, a.L.n_frames, a.W, a.H, P, S, &a.poses[k], nullptr);
 }
 
 // The same grid behind it.  Wave 0 decides the slot again from leaders[k] (the job is not kept between the kernels: a match, a frame and a
@@ -704,10 +745,11 @@ struct RoughChainArgs {
 };
 
 // k_pose_refine_clusters' grid and body; the prologue is two loads: k_rough_finish decided the slot and left its job.  The job's fields
-// are told to the compiler as uniform, as uniform_slot does.  253 vector registers, 106 scalar, 592 bytes of scratch per lane (the body's
-// local arrays, as in k_pose_refine: 251, 106, 592), 2 waves per SIMD as k_pose_refine and k_pose_refine_clusters (255, 106, 592).
+// are told to the compiler as uniform, as uniform_slot does.  247 vector registers, 106 scalar, 592 bytes of scratch per lane (the body's
+// local arrays, as in k_pose_refine: 247, 106, 592), 2 waves per SIMD as k_pose_refine and k_pose_refine_clusters (249, 106, 592);
+// the figures before the stage loop are in profiles/pose_refine_staged.txt.
 // k_rough_verify_clusters: 67 vector registers, 106 scalar, no scratch, 4 waves per SIMD, as k_pose_verify_clusters.
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_rough_refine_clusters(const RoughChainArgs a, const pr::Params P) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_rough_refine_clusters(const RoughChainArgs a, const pr::Params P, const pr::Schedule S) {
   const uint32_t k = blockIdx.x;
   if (k >= pc::n_live(a.header, a.cap_clusters)) return;
   const rp::Job* j = a.jobs + k;
@@ -717,8 +759,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
     return;
   }
   const PoseJob job = {__builtin_amdgcn_readfirstlane(j->x), __builtin_amdgcn_readfirstlane(j->y), (int32_t)k, __builtin_amdgcn_readfirstlane(j->frame),
-                       __builtin_amdgcn_readfirstlane(j->rect_x), __builtin_amdgcn_readfirstlane(j->rect_y), 0, 0};
-  pose_refine_body(a.crops, a.cap_slots, job, a.scene, a.n_frames, a.W, a.H, P, &a.poses[k], nullptr);
+                       __builtin_amdgcn_readfirstlane(j->rect_x), __builtin_amdgcn_readfirstlane(j->rect_y), __builtin_amdgcn_readfirstlane(j->lat_x),
+                       __builtin_amdgcn_readfirstlane(j->lat_y)};
+  pose_refine_body(a.crops, a.cap_slots, job, a.scene, a.n_frames, a.W, a.H, P, S, &a.poses[k], nullptr);
 }
 
 // k_pose_verify_clusters behind it, on the same job.
@@ -757,6 +800,9 @@ struct lmx_depth_templates {
   lmx::PoseJob *d_pjobs = nullptr, *h_pjobs = nullptr;   // lmx_pose_refine_matches: its jobs and records, as d_jobs / d_out
   lmx_pose_refine_t *d_pout = nullptr, *h_pout = nullptr;
   size_t pjobs_cap = 0, pout_cap = 0;
+  // lmx_depth_templates_set_refine_schedule (n_stages 0: none).  A call reads it under `m` and hands it to its kernel by value
+  lmx::pr::Schedule schedule = {0, 0, {}};
+  lmx::pr::Schedule schedule_for(const lmx::pr::Params& P) const { return schedule.n_stages > 0 ? schedule : lmx::pr::single_stage(P); }
   lmx::VerifyJob *d_vjobs = nullptr, *h_vjobs = nullptr;   // lmx_pose_verify_matches: the same pair
   lmx_pose_verify_t *d_vout = nullptr, *h_vout = nullptr;
   size_t vjobs_cap = 0, vout_cap = 0;
@@ -1795,7 +1841,8 @@ lmx_status pose_call(const PoseCall& a, const std::function<int(size_t, const lm
   return st;
 }
 
-// The body of lmx_pose_refine_matches and of its test hook (dbg: the sums of job 0's passes, [max_iterations + 1][17]).
+// The body of lmx_pose_refine_matches and of its test hook (dbg: the sums of job 0's passes, [max_iterations + 1][17], under a schedule
+// [sum of its max_iterations + 1][17]).
 lmx_status pose_refine_impl(const char* what, lmx_depth_templates* t, const lmx_image* depth, int32_t n_frames, const lmx_match_t* matches, const size_t* offsets,
                             int32_t class_index, const lmx_pose_refine_params* params, lmx_pose_refine_t* out, int64_t* dbg) {
   using namespace lmx;
@@ -1803,8 +1850,13 @@ lmx_status pose_refine_impl(const char* what, lmx_depth_templates* t, const lmx_
   pr::Params P;
   if (lmx_status st = pose_params(what, params, &P)) return st;
   const PoseCall call = {what, t, depth, n_frames, matches, offsets, class_index, params->rects, out, sizeof(lmx_pose_refine_t), false, 0};
+  pr::Schedule S = pr::single_stage(P);
   return pose_call(
-      call, nullptr, [&]() { if (dbg) std::memset(dbg, 0, ((size_t)P.max_iterations + 1) * pr::kSums * sizeof(int64_t)); },
+      call, nullptr,
+      [&]() {   // t->m is held from here on
+        S = t->schedule_for(P);
+        if (dbg) std::memset(dbg, 0, (size_t)pr::schedule_passes(S) * pr::kSums * sizeof(int64_t));
+      },
       [&](int32_t W, int32_t H, int32_t n_slots, size_t count, const int32_t* rects) -> lmx_status {
         hipStream_t s = t->s;
         const size_t n = t->sel.size();
@@ -1816,14 +1868,14 @@ lmx_status pose_refine_impl(const char* what, lmx_depth_templates* t, const lmx_
           t->h_pjobs[k] = PoseJob{m.x, m.y, m.template_id, t->sel_slot[k], r[0], r[1], 0, 0};
         }
         DeviceBuffer d_dbg;
-        const size_t dbg_bytes = ((size_t)P.max_iterations + 1) * pr::kSums * sizeof(int64_t);
+        const size_t dbg_bytes = (size_t)pr::schedule_passes(S) * pr::kSums * sizeof(int64_t);
         if (dbg) {
           HIP_RETURN(hipMalloc(&d_dbg.p, dbg_bytes));
           HIP_RETURN(hipMemsetAsync(d_dbg.p, 0, dbg_bytes, s));
         }
         HIP_RETURN(hipMemcpyAsync(t->d_pjobs, t->h_pjobs, n * sizeof(PoseJob), hipMemcpyHostToDevice, s));
         const int pe = t->prof_begin(lmx_depth_templates::PK_POSE_REFINE, s);
-        hipLaunchKernelGGL(k_pose_refine, dim3((unsigned)n), dim3(256), 0, s, t->d_table, (int32_t)count, t->d_pjobs, t->d_scene, n_slots, W, H, P, t->d_pout,
+        hipLaunchKernelGGL(k_pose_refine, dim3((unsigned)n), dim3(256), 0, s, t->d_table, (int32_t)count, t->d_pjobs, t->d_scene, n_slots, W, H, P, S, t->d_pout,
                            d_dbg.as<long long>());
         t->prof_end(pe, s);
         HIP_RETURN(hipGetLastError());
@@ -1863,6 +1915,41 @@ extern "C" lmx_status lmx_debug_pose_refine_sums(lmx_depth_templates* t, const l
     if (!depth || !match || !out || !sums) { lmx::set_error("lmx_debug_pose_refine_sums: null argument"); return LMX_ERR_INVALID_ARG; }
     const size_t offsets[2] = {0, 1};
     return pose_refine_impl("lmx_debug_pose_refine_sums", t, depth, 1, match, offsets, -1, params, out, sums);
+  });
+}
+
+extern "C" lmx_status lmx_depth_templates_set_refine_schedule(lmx_depth_templates* t, const lmx_pose_refine_stage* stages, int32_t n_stages) {
+  return lmx::guarded("lmx_depth_templates_set_refine_schedule", [&]() -> lmx_status {
+    using namespace lmx;
+    const char* what = "lmx_depth_templates_set_refine_schedule";
+    if (!t) { set_error("%s: null argument", what); return LMX_ERR_INVALID_ARG; }
+    if (n_stages < 0 || n_stages > LMX_POSE_MAX_STAGES) { set_error("%s: n_stages = %d (0 .. %d)", what, n_stages, (int)LMX_POSE_MAX_STAGES); return LMX_ERR_INVALID_ARG; }
+    if (n_stages > 0 && !stages) { set_error("%s: stages is null with n_stages = %d", what, n_stages); return LMX_ERR_INVALID_ARG; }
+    pr::Schedule S = {n_stages, 0, {}};
+    for (int32_t k = 0; k < n_stages; ++k) {
+      const lmx_pose_refine_stage& g = stages[k];
+      if (g.reserved != 0) { set_error("%s: stage %d: reserved = %d (must be 0)", what, k, g.reserved); return LMX_ERR_INVALID_ARG; }
+      S.stage[k] = pr::Stage{g.max_dist_mm, g.eps_rot_rad, g.eps_trans_mm, g.max_iterations, g.search_radius, g.stride, 0};
+    }
+    if (n_stages > 0)
+      if (const char* why = pr::check_schedule(S)) { set_error("%s: %s", what, why); return LMX_ERR_INVALID_ARG; }   // a NaN fails its range
+    std::lock_guard<std::mutex> lk(t->m);
+    t->schedule = S;   // queued work took its schedule by value: nothing to wait for
+    return LMX_OK;
+  });
+}
+
+extern "C" lmx_status lmx_depth_templates_get_refine_schedule(const lmx_depth_templates* t, lmx_pose_refine_stage out[LMX_POSE_MAX_STAGES], int32_t* n_stages) {
+  return lmx::guarded("lmx_depth_templates_get_refine_schedule", [&]() -> lmx_status {
+    if (!t || !out || !n_stages) { lmx::set_error("lmx_depth_templates_get_refine_schedule: null argument"); return LMX_ERR_INVALID_ARG; }
+    std::lock_guard<std::mutex> lk(const_cast<lmx_depth_templates*>(t)->m);
+    *n_stages = t->schedule.n_stages;
+    for (int32_t k = 0; k < LMX_POSE_MAX_STAGES; ++k) {
+      const lmx::pr::Stage z = {0.0, 0.0, 0.0, 0, 0, 0, 0};
+      const lmx::pr::Stage& g = k < t->schedule.n_stages ? t->schedule.stage[k] : z;
+      out[k] = lmx_pose_refine_stage{g.max_dist_mm, g.eps_rot_rad, g.eps_trans_mm, g.max_iterations, g.search_radius, g.stride, 0};
+    }
+    return LMX_OK;
   });
 }
 
@@ -2072,7 +2159,7 @@ lmx_status chain_queue(lmx_depth_templates* t, const lmx_pose_chain_desc& d, con
   const dim3 grid((unsigned)d.cap_clusters), block(256);
   HIP_RETURN(hipMemsetAsync(d.chain_header, 0, pc::C_WORDS * sizeof(uint32_t), s));
   int pe = t->prof_begin(lmx_depth_templates::PK_POSE_REFINE_CLUSTERS, s);
-  hipLaunchKernelGGL(k_pose_refine_clusters, grid, block, 0, s, a, PR);
+  hipLaunchKernelGGL(k_pose_refine_clusters, grid, block, 0, s, a, PR, t->schedule_for(PR));
   t->prof_end(pe, s);
   HIP_RETURN(hipGetLastError());
   if (!same_rects) a.T.rects = t->chain_rects_verify.dev;
@@ -2204,7 +2291,7 @@ lmx_status rough_queue(lmx_depth_templates* t, lmx_rough_model* model, const lmx
   const RoughChainArgs c = {d.header, (uint64_t)d.cap_clusters, model->d_jobs, reinterpret_cast<const DepthCrop*>(model->d_crops), model->cap_slots, t->d_scene,
                             d.n_frames, t->scene_W, t->scene_H, d.chain_header, d.poses, d.checks, d.keep, d.keep_thresh};
   const dim3 grid((unsigned)d.cap_clusters), block(256);
-  hipLaunchKernelGGL(k_rough_refine_clusters, grid, block, 0, s, c, PR);
+  hipLaunchKernelGGL(k_rough_refine_clusters, grid, block, 0, s, c, PR, t->schedule_for(PR));
   HIP_RETURN(hipGetLastError());
   hipLaunchKernelGGL(k_rough_verify_clusters, grid, block, 0, s, c, PV);
   HIP_RETURN(hipGetLastError());

@@ -1577,6 +1577,32 @@ class DepthTemplates:
         return _lib.PoseVerifyParams(C.sizeof(_lib.PoseVerifyParams), *[float(v) for v in tuple(model_camera) + tuple(scene_camera)], float(voxel_mm), int(roi_margin),
                                      keep.ctypes.data if keep is not None else None)
 
+    STAGE_FIELDS = ("max_dist_mm", "eps_rot_rad", "eps_trans_mm", "max_iterations", "search_radius", "stride")
+
+    def set_refine_schedule(self, stages):
+        """The refinement schedule of this object (lmx_depth_templates_set_refine_schedule): a list of 1 to 4 dicts with the keys
+        STAGE_FIELDS -- a stage's own correspondence distance, stopping rule, window and a stride in (1, 2, 4, 8) that thins the model
+        pixels to a lattice; each stage starts from the pose the one before it left.  None or []: no schedule.  While one is set,
+        refine_poses, debug_pose_refine_sums and the pose chains refine by it and take only the cameras, min_pairs and rects from their
+        own parameters.  Work already queued keeps the schedule it was queued under."""
+        stages = list(stages) if stages is not None else []
+        for st in stages:
+            if set(st) != set(self.STAGE_FIELDS):
+                raise ValueError("a stage is a dict with the keys %s" % (self.STAGE_FIELDS,))
+        arr = (_lib.PoseRefineStage * max(len(stages), 1))()
+        for k, st in enumerate(stages):
+            arr[k] = _lib.PoseRefineStage(float(st["max_dist_mm"]), float(st["eps_rot_rad"]), float(st["eps_trans_mm"]), int(st["max_iterations"]),
+                                          int(st["search_radius"]), int(st["stride"]), 0)
+        _lib.check(_lib.lib().lmx_depth_templates_set_refine_schedule(self.h, arr if stages else None, len(stages)))
+
+    @property
+    def refine_schedule(self):
+        """The schedule in force (lmx_depth_templates_get_refine_schedule): a list of dicts as set_refine_schedule takes them, [] for none."""
+        arr = (_lib.PoseRefineStage * _lib.LMX_POSE_MAX_STAGES)()
+        n = C.c_int32(0)
+        _lib.check(_lib.lib().lmx_depth_templates_get_refine_schedule(self.h, arr, C.byref(n)))
+        return [{k: getattr(arr[i], k) for k in self.STAGE_FIELDS} for i in range(n.value)]
+
     def refine_poses(self, matches, depth_frames=None, offsets=None, class_index=-1, model_camera=None, scene_camera=None, max_dist_mm=10.0,
                      max_iterations=20, min_pairs=16, search_radius=1, eps_rot_rad=1e-5, eps_trans_mm=1e-3, rects=None):
         """A rigid transform per match (lmx_pose_refine_matches; the reference's icpPoseRefine stage) -> POSE_REFINE_DTYPE array: R, t_mm map
@@ -1723,14 +1749,16 @@ class DepthTemplates:
 
     def debug_pose_refine_sums(self, depth_frame, match, **params):
         """Test hook (lmx_debug_pose_refine_sums): one match against one host frame -> (its POSE_REFINE_DTYPE record, int64
-        [max_iterations + 1, 17]: the integer sums of every pass the device ran)."""
+        [max_iterations + 1, 17]: the integer sums of every pass the device ran; under a schedule one row per pass of its stages, in the
+        order they ran, [sum of max_iterations + 1, 17])."""
         frames, imgs = _depth_images(depth_frame)
         m = np.ascontiguousarray(match, MATCH_DTYPE).reshape(1)
         args = dict(max_dist_mm=10.0, max_iterations=20, min_pairs=16, search_radius=1, eps_rot_rad=1e-5, eps_trans_mm=1e-3, rects=None)
         args.update(params)
         p, keep = self._pose_params(**args)
         out = np.zeros(1, POSE_REFINE_DTYPE)
-        sums = np.zeros((int(args["max_iterations"]) + 1, 17), np.int64)
+        sched = self.refine_schedule
+        sums = np.zeros(((sum(st["max_iterations"] for st in sched) if sched else int(args["max_iterations"])) + 1, 17), np.int64)
         _lib.check(_lib.lib().lmx_debug_pose_refine_sums(self.h, imgs, m.ctypes.data, C.byref(p), out.ctypes.data, sums.ctypes.data))
         del keep, frames
         return out[0], sums

@@ -11,7 +11,8 @@ from the object's event pairs (set_profiling), in blocks of steps so that the bl
 k_pose_refine + k_pose_verify of the staged leg against k_pose_refine_clusters + k_pose_verify_clusters of the chain, for the same jobs.
 The chain's grid is cap_clusters workgroups, of which those at or above the live count leave at once: every figure is taken for each
 --cap-clusters value.  These are recorded values, not thresholds.  Needs a GPU.
-usage: pose_chain_bench.py [--threshold 80] [--repeats 40] [--cap-clusters 4096 512] [--out profiles/pose_chain.txt]"""
+--schedule: every leg refines under that schedule (DepthTemplates.set_refine_schedule); the byte-for-byte check is the same.
+usage: pose_chain_bench.py [--threshold 80] [--repeats 40] [--cap-clusters 4096 512] [--schedule S] [--out profiles/pose_chain.txt]"""
 import argparse
 import os
 import sys
@@ -42,6 +43,7 @@ def main():
     ap.add_argument("--block-steps", type=int, default=10)
     ap.add_argument("--cap-clusters", type=int, nargs="+", default=[4096, 512])
     ap.add_argument("--max-candidates", type=int, default=1 << 19)
+    ap.add_argument("--schedule", default=None, help="stride:iterations:max_dist:radius,...: the refinement schedule every leg runs under")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pose_chain.txt"))
     args = ap.parse_args()
     import torch
@@ -54,6 +56,9 @@ def main():
     bank, rects, dists, view_of = ms.load_bank("memoryChip2")
     chip, cpu_mesh, grid = ms.load_mesh("memoryChip2"), ms.load_mesh("cpu_binary"), ms.view_grid()
     t = DepthTemplates.from_mesh(chip, [grid[int(v)] for v in view_of], W, H, F, F)
+    if args.schedule:
+        import pose_refine_staged_cases as psc
+        t.set_refine_schedule(psc.parse_schedule(args.schedule))
     distinct = [ms.make_scene(chip, grid, seed=7000 + f, n_instances=3, other_tri=cpu_mesh, n_other=2)[0] for f in range(16)]
     frames = [distinct[f % len(distinct)] for f in range(B)]
     depth = [np.ascontiguousarray(fr[1]) for fr in frames]
@@ -66,6 +71,8 @@ def main():
     stream = torch.cuda.Stream()
     lines = ["the pose stages behind one 64-frame export, memoryChip2 (%d templates) at %d x %d, threshold %g (scripts/pose_chain_bench.py): recorded values, not thresholds"
              % (len(rects), W, H, args.threshold)]
+    if args.schedule:
+        lines.append("refinement schedule of every leg: [%s]" % args.schedule)
 
     for cap in args.cap_clusters:
         state = {"res": None, "poses": None}

@@ -7,7 +7,8 @@ Device time per call from an event pair on the caller's stream around it (the ca
 waits the call queues), the two calls alternating, medians with quartiles and extremes.  These are recorded values, not thresholds.
 --kernels N: nothing is timed; N calls of each are made for a kernel trace taken from outside (rocprofv3 --kernel-trace --stats).
 Needs a GPU.
-usage: rough_pose_bench.py [--threshold 80] [--repeats 40] [--cap-clusters 512] [--window 320] [--degrees 10] [--out profiles/rough_pose.txt]"""
+--schedule: every leg refines under that schedule (DepthTemplates.set_refine_schedule).
+usage: rough_pose_bench.py [--threshold 80] [--repeats 40] [--cap-clusters 512] [--window 320] [--degrees 10] [--schedule S] [--out profiles/rough_pose.txt]"""
 import argparse
 import os
 import sys
@@ -37,6 +38,7 @@ def main():
     ap.add_argument("--degrees", type=float, default=10.0)
     ap.add_argument("--max-candidates", type=int, default=1 << 19)
     ap.add_argument("--kernels", type=int, default=0)
+    ap.add_argument("--schedule", default=None, help="stride:iterations:max_dist:radius,...: the refinement schedule every leg runs under")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rough_pose.txt"))
     args = ap.parse_args()
     import torch
@@ -50,6 +52,9 @@ def main():
     chip, cpu_mesh, grid = ms.load_mesh("memoryChip2"), ms.load_mesh("cpu_binary"), ms.view_grid()
     views = [grid[int(v)] for v in view_of]
     t = DepthTemplates.from_mesh(chip, views, W, H, F, F)
+    if args.schedule:
+        import pose_refine_staged_cases as psc
+        t.set_refine_schedule(psc.parse_schedule(args.schedule))
     model = RoughModel(chip, views, W, H, F, F, ori_dists=dists, cap_slots=args.cap_clusters, max_window=(args.window, args.window))
     distinct = [ms.make_scene(chip, grid, seed=7000 + f, n_instances=3, other_tri=cpu_mesh, n_other=2)[0] for f in range(16)]
     frames = [distinct[f % len(distinct)] for f in range(B)]
@@ -103,7 +108,7 @@ def main():
         ms_of["leader"].append(timed(leader))
         ms_of["rough"].append(timed(rough))
     lines = ["the rough pose stage behind one 64-frame export, memoryChip2 (%d templates, %d triangles) at %d x %d, threshold %g (scripts/rough_pose_bench.py): recorded values, "
-             "not thresholds" % (len(rects), len(chip), W, H, args.threshold), "",
+             "not thresholds" % (len(rects), len(chip), W, H, args.threshold)] + (["refinement schedule of every leg: [%s]" % args.schedule] if args.schedule else []) + ["",
              "cap_clusters %d (every kernel's grid), orientation threshold %g degrees, window %d x %d, the model object holds %.1f MB"
              % (args.cap_clusters, args.degrees, args.window, args.window, model.device_bytes() / 1e6),
              "%d live clusters of %d frames; members per cluster %d .. %d (mean %.1f), groups per cluster %d .. %d (mean %.1f), members of the winning group mean %.1f"
