@@ -1017,6 +1017,24 @@ typedef struct lmx_pose_refine_stage {
 enum { LMX_POSE_MAX_STAGES = 4 };
 lmx_status lmx_depth_templates_set_refine_schedule(lmx_depth_templates* templates, const lmx_pose_refine_stage* stages, int32_t n_stages);
 lmx_status lmx_depth_templates_get_refine_schedule(const lmx_depth_templates* templates, lmx_pose_refine_stage out[LMX_POSE_MAX_STAGES], int32_t* n_stages);
+/* The point-to-plane metric, per stage and opt-in: a stage with point_shift k in 0..20 minimises the distance of every pair along the
+ * scene's stored normal at the pair's scene pixel (the normals of lmx_depth_templates_enable_normals, computed once per scene on the
+ * device), kept well-posed by the point-to-point term weighted 2^-k; -1 is the point-to-point stage in every byte.  On flat, box-like
+ * parts a few plane passes end where many point passes end, since a model point may slide along the surface; with a small point weight
+ * (k >= 8) the pose can wander after about 5 passes, so use it with few iterations.  The definition is the PLANE paragraph of
+ * csrc/lmx_pose_refine.hpp.  rms_first_mm / rms_last_mm stay point-to-point distances; the records keep their layout.
+ * Entry s governs stage s of whatever schedule is in force; a call without a schedule is stage 0; stages beyond n_stages are -1.
+ * point_shift == NULL or n_stages == 0 clears the setting.  Like the schedule it is a property of the object, read on the host by
+ * lmx_pose_refine_matches, the pose chains and their hooks and handed to the kernel by value; a call in which no stage in force has a
+ * shift >= 0 launches the kernels a call on an object without the setting launches.  LMX_ERR_INVALID_ARG, the previous setting staying in
+ * place: n_stages outside 0..4; NULL with n_stages > 0; an entry outside -1..20; an entry >= 0 before lmx_depth_templates_enable_normals.
+ * get: all LMX_POSE_MAX_STAGES entries (-1 where none was set) and the number set, 0 for none. */
+lmx_status lmx_depth_templates_set_refine_plane(lmx_depth_templates* templates, const int32_t* point_shift, int32_t n_stages);
+lmx_status lmx_depth_templates_get_refine_plane(const lmx_depth_templates* templates, int32_t out[LMX_POSE_MAX_STAGES], int32_t* n_stages);
+/* Test hook: lmx_debug_pose_refine_sums with the 29 plane sums of every pass next to the 17, plane_sums[the same rows][29]; the rows of
+ * passes of a -1 stage, and of passes that did not run, are zeros. */
+lmx_status lmx_debug_pose_refine_plane_sums(lmx_depth_templates* templates, const lmx_image* depth, const lmx_match_t* match,
+                                            const lmx_pose_refine_params* params, lmx_pose_refine_t* out, int64_t* sums, int64_t* plane_sums);
 
 /* ---- verification of refined poses against the scene's voxel occupancy (the reference's hypothesisVerification) -------------------------
  * The step after icpPoseRefine: the share of the posed model cloud's points that fall into a voxel holding a scene point.  The model

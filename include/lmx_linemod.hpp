@@ -451,6 +451,17 @@ class DepthTemplates {
     check(lmx_depth_templates_get_refine_schedule(h_, out, &n));
     return std::vector<lmx_pose_refine_stage>(out, out + n);
   }
+  // The stages' point_shift (lmx_depth_templates_set_refine_plane): -1 point-to-point, 0..20 point-to-plane against the scene's normals
+  // (enableNormals first) with the point term weighted 2^-shift; entry s is stage s of the schedule in force, an empty vector clears it.
+  void setRefinePlane(const std::vector<int32_t>& point_shift) {
+    check(lmx_depth_templates_set_refine_plane(h_, point_shift.empty() ? nullptr : point_shift.data(), (int32_t)point_shift.size()));
+  }
+  std::vector<int32_t> refinePlane() const {
+    int32_t out[LMX_POSE_MAX_STAGES];
+    int32_t n = 0;
+    check(lmx_depth_templates_get_refine_plane(h_, out, &n));
+    return std::vector<int32_t>(out, out + n);
+  }
   // The object's pose in the scene camera from the matched template's view and its refinePoses record (lmx_pose_compose).
   static void composePose(const lmx_mesh_view& view, const lmx_pose_refine_t& refined, double R_obj[9], double t_obj_m[3]) {
     check(lmx_pose_compose(&view, &refined, R_obj, t_obj_m));

@@ -36,6 +36,7 @@ SYMBOLS = [
     "lmx_ctx_export_clusters_on", "lmx_debug_depth_walk_records", "lmx_debug_depth_walk_grid",
     "lmx_pose_refine_matches", "lmx_pose_compose", "lmx_debug_pose_refine_sums",
     "lmx_depth_templates_set_refine_schedule", "lmx_depth_templates_get_refine_schedule",
+    "lmx_depth_templates_set_refine_plane", "lmx_depth_templates_get_refine_plane", "lmx_debug_pose_refine_plane_sums",
     "lmx_pose_verify_matches", "lmx_pose_verify_keep",
     "lmx_pose_chain_on", "lmx_debug_pose_chain",
     "lmx_rough_model_create", "lmx_rough_model_free", "lmx_rough_model_device_bytes", "lmx_rough_trace_min", "lmx_rough_pose_chain_on",
@@ -388,6 +389,9 @@ def lib():
     L.lmx_debug_pose_refine_sums.argtypes = [vp, C.POINTER(Image), vp, C.POINTER(PoseRefineParams), vp, vp]
     L.lmx_depth_templates_set_refine_schedule.argtypes = [vp, C.POINTER(PoseRefineStage), C.c_int32]
     L.lmx_depth_templates_get_refine_schedule.argtypes = [vp, C.POINTER(PoseRefineStage), C.POINTER(C.c_int32)]
+    L.lmx_depth_templates_set_refine_plane.argtypes = [vp, C.POINTER(C.c_int32), C.c_int32]
+    L.lmx_depth_templates_get_refine_plane.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.lmx_debug_pose_refine_plane_sums.argtypes = [vp, C.POINTER(Image), vp, C.POINTER(PoseRefineParams), vp, vp, vp]
     L.lmx_depth_value.argtypes = [C.POINTER(DepthDiff), C.c_double]
     L.lmx_depth_value.restype = C.c_double
     L.lmx_depth_templates_upload_scene.argtypes = [vp, C.POINTER(Image), C.c_int32]

@@ -81,6 +81,29 @@
 //   measuring pass included.  iterations is the total over the stages, status that of the last stage that ran, reserved the index of the
 //   stage in which the record was finished (0 for NO_OVERLAP).  One stage of stride 1 is refine_job in every byte.
 //   The debug sums are [sum of max_iterations + 1][17], one row per pass in the order the passes ran.
+//
+// PLANE (refine_job_plane; lmx_depth_templates_set_refine_plane)  A stage has a point_shift.  With -1 it is the stage above in every byte.  With
+//   k in 0..20 the stage minimises the point-to-plane distance against the scene's stored normals (lmx_normal_verify.hpp, nv::Packed: the
+//   normal map of the job's frame, one element per scene pixel), held in place by the point-to-point term weighted 2^-k.
+//   Pass: PASS k is unchanged, its 17 sums included.  For every pair that enters the 17 sums let N = (Nx, Ny, Nz) be the stored normal at the
+//   scene pixel of the chosen candidate (inside the image by construction; one 8-byte load after the selection).  If N is valid, with int64
+//   and rs14(a) = (a + 8192) >> 14, an arithmetic shift:
+//     c = (rs14(P'y Nz - P'z Ny), rs14(P'z Nx - P'x Nz), rs14(P'x Ny - P'y Nx)),  r = rs14(D.x Nx + D.y Ny + D.z Nz),  g = (c.x, c.y, c.z, Nx, Ny, Nz)
+//   The 29 plane sums:  [0] n_plane   [1..21] sum g_i g_j for i <= j, row-major (00, 01, .., 05, 11, .., 55)   [22..27] sum g_i r   [28] sum r^2
+//   Bounds (static_asserted below): |P'| <= 2^15, |N| <= 2^14 and |D| <= 2^14 give |c|, |r| < 2^17, every product is below 2^34, and 2^28
+//   pixels keep every sum below 2^63.
+//   Step: n_plane < min_pairs: (w, v) is SOLVE's, bit for bit.  Otherwise, with SOLVE's integer matrix Ai and its right side b_pt:
+//     lambda = 1.0 / (double)(1 << k);   s_i = 1 for i < 3, 1.0 / 16384.0 for i >= 3
+//     G[i][j] = ((double)sum_ij * s_i) * s_j      h[i] = (double)sum_ir * s_i
+//     A[i][j] = G[i][j] + lambda * (double)Ai[i][j]      b[i] = h[i] + lambda * b_pt[i]
+//   then SOLVE's Cholesky, substitutions and acceptance test (every pivot > 0, w.w <= 1, v.v <= 2^48) on A, b; if any of them fails the step
+//   is SOLVE's, its translation-only fallback included.  w is in radians and v in ticks as in SOLVE: minimise sum (N . (w x P' + v - D))^2
+//   + lambda sum |w x P' + v - D|^2 with N a unit vector.  UPDATE, CONTROL and SCHEDULE are unchanged; rms_* stay the point-to-point
+//   distances, n < min_pairs still means LOST.
+//   Why the point term: on a flat patch all normals are parallel and the plane system alone has rank 3; the lambda-weighted point term keeps
+//   it positive definite wherever SOLVE's own system is.  The normal is this repository's own (deviations): it neglects the
+//   off-axis perspective terms; on consistent data the fixed point of the metric does not depend on the normals.
+//   The debug plane sums are [sum of max_iterations + 1][29], row for row next to the 17; the rows of passes of a -1 stage are left alone.
 #pragma once
 
 #include <math.h>
@@ -91,12 +114,16 @@
 #ifndef LMX_DV_HOST
 #define LMX_DV_HOST
 #endif
+#ifndef LMX_NV_HOST
+#define LMX_NV_HOST
+#endif
 #define LMX_PR_FN inline
 #else
 #define LMX_PR_FN __host__ __device__ __forceinline__
 #endif
 
 #include "lmx_depth_verify.hpp"
+#include "lmx_normal_verify.hpp"
 
 namespace lmx {
 namespace pr {
@@ -118,6 +145,19 @@ static_assert(kMaxCentredTicks * kMaxCentredTicks <= (INT64_MAX / kMaxPixels), "
 static_assert(2 * kMaxCentredTicks * kMaxDTicks <= (INT64_MAX / kMaxPixels), "sum P' x D fits int64");
 static_assert(3 * kMaxDTicks * kMaxDTicks <= (INT64_MAX / kMaxPixels), "sum |D|^2 fits int64");
 static_assert(kMaxCoord * 65535 <= (INT64_MAX / kMaxPixels), "the placement sums fit int64");
+
+// PLANE: the 29 sums, the shifts, the bounds of their terms
+constexpr int kPlaneSums = 29;
+constexpr int kAllSums = kSums + kPlaneSums;   // what a lane of a plane pass accumulates
+constexpr int kMaxPointShift = 20;
+constexpr int64_t kMaxNormal = (int64_t)nv::kUnit;                                        // |N| <= 2^14
+constexpr int64_t kMaxPlaneTerm = (int64_t)1 << 17;                                       // |c|, |r| stay below it
+static_assert(kMaxNormal == ((int64_t)1 << 14), "a stored normal's components lie within 2^14");
+static_assert(((2 * kMaxCentredTicks * kMaxNormal + 8192) >> 14) < kMaxPlaneTerm, "|c| < 2^17");
+static_assert(((3 * kMaxDTicks * kMaxNormal + 8192) >> 14) < kMaxPlaneTerm, "|r| < 2^17");
+static_assert(kMaxPlaneTerm * kMaxPlaneTerm <= (INT64_MAX / kMaxPixels), "the plane sums fit int64");
+static_assert(((int64_t)-1 >> 14) == -1 && (((int64_t)-8193 + 8192) >> 14) == -1 && (((int64_t)-24577 + 8192) >> 14) == -2 && (((int64_t)24575 + 8192) >> 14) == 1,
+              "rs14: >> of a negative int64 is an arithmetic shift");
 
 enum Status : int32_t { NONE = 0, CONVERGED = 1, MAX_ITERATIONS = 2, NO_OVERLAP = 3, LOST = 4 };
 
@@ -142,6 +182,13 @@ struct Stage {   // the bytes of lmx_pose_refine_stage
 };
 struct Schedule { int32_t n_stages, pad; Stage stage[kMaxStages]; };
 struct StagedControl { int32_t stage, k, final_pass; };   // the stage, the pass inside it, "this pass only measures"
+struct PlaneShifts { int32_t shift[kMaxStages]; };          // a stage's point_shift: -1 the point-to-point stage, 0..20 PLANE
+constexpr PlaneShifts kNoPlane = {{-1, -1, -1, -1}};
+LMX_PR_FN bool any_plane(const PlaneShifts& K, int32_t n_stages) {
+  bool any = false;
+  for (int32_t k = 0; k < n_stages && k < kMaxStages; ++k) any = any || K.shift[k] >= 0;
+  return any;
+}
 
 LMX_PR_FN Inverse inverse_of(const Camera& cam) { return Inverse{1.0 / cam.fx, 1.0 / cam.fy}; }
 
@@ -217,12 +264,30 @@ LMX_PR_FN int64_t max_dist_ticks(const Params& P) { return dist_ticks(P.max_dist
 
 LMX_PR_FN bool within(double a, double bound) { return a >= -bound && a <= bound; }   // false for a NaN
 
+// PLANE: the 29 terms of a pair (x, y, z) = P', D with the valid stored normal N.
+LMX_PR_FN int64_t rs14(int64_t a) { return (a + 8192) >> 14; }
+
+LMX_PR_FN void plane_terms(int64_t x, int64_t y, int64_t z, const int64_t D[3], nv::Packed N, int64_t pl[kPlaneSums]) {
+  const int64_t nx = nv::comp(N, 0), ny = nv::comp(N, 1), nz = nv::comp(N, 2);
+  const int64_t g[6] = {rs14(y * nz - z * ny), rs14(z * nx - x * nz), rs14(x * ny - y * nx), nx, ny, nz};
+  const int64_t r = rs14(D[0] * nx + D[1] * ny + D[2] * nz);
+  pl[0] += 1;
+  int q = 1;
+  for (int i = 0; i < 6; ++i)
+    for (int j = i; j < 6; ++j) pl[q++] += g[i] * g[j];
+  for (int i = 0; i < 6; ++i) pl[22 + i] += g[i] * r;
+  pl[28] += r * r;
+}
+
 // One model pixel (t != 0) of crop pixel (i, j) under `pose`.  frame: the scene, H rows of scene_pitch elements, read only inside the image.
 // RAD: the search radius as a constant, so that the window unrolls: its scene values are all loaded first (independent loads, one wait),
 // then the candidates are taken in raster order.
-template <int RAD>
-LMX_PR_FN void pass_pixel_r(const Params& P, const Inverse& im, const Inverse& is, const Pose& pose, const int64_t C[3], int64_t dmax, int32_t rect_x, int32_t rect_y, int32_t i, int32_t j,
-                            uint16_t t, const uint16_t* frame, int32_t W, int32_t H, size_t scene_pitch, int64_t a[kSums]) {
+// PLANE: the pair's 29 terms as well (pl), with the normal read at the chosen candidate's pixel of `normals` (the frame's normal map, rows
+// of scene_pitch elements like the frame's); without it neither is touched and the code is that of the 17 sums alone.
+template <int RAD, bool PLANE>
+LMX_PR_FN void pass_pixel_core(const Params& P, const Inverse& im, const Inverse& is, const Pose& pose, const int64_t C[3], int64_t dmax, int32_t rect_x, int32_t rect_y, int32_t i,
+                               int32_t j, uint16_t t, const uint16_t* frame, const nv::Packed* normals, int32_t W, int32_t H, size_t scene_pitch, int64_t a[kSums],
+                               int64_t* pl) {
   double M[3], p[3];
   back(P.model, im, (int64_t)rect_x + j, (int64_t)rect_y + i, t, M);
   mat_point(pose.R, M, pose.t, p);
@@ -244,6 +309,7 @@ LMX_PR_FN void pass_pixel_r(const Params& P, const Inverse& im, const Inverse& i
   }
   bool found = false;
   int64_t best = 0, D[3] = {0, 0, 0};
+  int bq = 0;   // PLANE: the chosen candidate's place in the window
 #ifndef LMX_PR_HOST
 #pragma unroll
 #endif
@@ -257,7 +323,7 @@ LMX_PR_FN void pass_pixel_r(const Params& P, const Inverse& im, const Inverse& i
     for (int k = 0; k < 3; ++k) d[k] = ticks_of(Q[k]) - Pt[k];
     if (d[0] < -dmax || d[0] > dmax || d[1] < -dmax || d[1] > dmax || d[2] < -dmax || d[2] > dmax) continue;
     const int64_t dd = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
-    if (!found || dd < best) { found = true; best = dd; D[0] = d[0]; D[1] = d[1]; D[2] = d[2]; }
+    if (!found || dd < best) { found = true; best = dd; D[0] = d[0]; D[1] = d[1]; D[2] = d[2]; if (PLANE) bq = q; }
   }
   if (!found || best > dmax * dmax) return;
   const int64_t x = Pt[0] - C[0], y = Pt[1] - C[1], z = Pt[2] - C[2];
@@ -268,6 +334,17 @@ LMX_PR_FN void pass_pixel_r(const Params& P, const Inverse& im, const Inverse& i
   a[7] += x * x; a[8] += x * y; a[9] += x * z; a[10] += y * y; a[11] += y * z; a[12] += z * z;
   a[13] += y * D[2] - z * D[1]; a[14] += z * D[0] - x * D[2]; a[15] += x * D[1] - y * D[0];
   a[16] += best;
+  if (PLANE) {
+    const int32_t X = X0 + (bq % SIDE - RAD), Y = Y0 + (bq / SIDE - RAD);   // a candidate's pixel: inside the image
+    const nv::Packed N = normals[(size_t)Y * scene_pitch + (size_t)X];
+    if (nv::valid(N)) plane_terms(x, y, z, D, N, pl);
+  }
+}
+
+template <int RAD>
+LMX_PR_FN void pass_pixel_r(const Params& P, const Inverse& im, const Inverse& is, const Pose& pose, const int64_t C[3], int64_t dmax, int32_t rect_x, int32_t rect_y, int32_t i, int32_t j,
+                            uint16_t t, const uint16_t* frame, int32_t W, int32_t H, size_t scene_pitch, int64_t a[kSums]) {
+  pass_pixel_core<RAD, false>(P, im, is, pose, C, dmax, rect_x, rect_y, i, j, t, frame, nullptr, W, H, scene_pitch, a, nullptr);
 }
 
 // radius: the search radius in force (a stage's, or the parameters'); of P the cameras alone are read.
@@ -277,6 +354,17 @@ LMX_PR_FN void pass_pixel_rad(const Params& P, int32_t radius, const Inverse& im
     case 0: pass_pixel_r<0>(P, im, is, pose, C, dmax, rect_x, rect_y, i, j, t, frame, W, H, scene_pitch, a); break;
     case 1: pass_pixel_r<1>(P, im, is, pose, C, dmax, rect_x, rect_y, i, j, t, frame, W, H, scene_pitch, a); break;
     default: pass_pixel_r<2>(P, im, is, pose, C, dmax, rect_x, rect_y, i, j, t, frame, W, H, scene_pitch, a); break;
+  }
+}
+
+// The plane form of a pass pixel: pass_pixel_rad's 17 sums into a, the pair's 29 plane sums into pl.
+LMX_PR_FN void pass_pixel_plane_rad(const Params& P, int32_t radius, const Inverse& im, const Inverse& is, const Pose& pose, const int64_t C[3], int64_t dmax, int32_t rect_x,
+                                    int32_t rect_y, int32_t i, int32_t j, uint16_t t, const uint16_t* frame, const nv::Packed* normals, int32_t W, int32_t H, size_t scene_pitch,
+                                    int64_t a[kSums], int64_t pl[kPlaneSums]) {
+  switch (radius) {
+    case 0: pass_pixel_core<0, true>(P, im, is, pose, C, dmax, rect_x, rect_y, i, j, t, frame, normals, W, H, scene_pitch, a, pl); break;
+    case 1: pass_pixel_core<1, true>(P, im, is, pose, C, dmax, rect_x, rect_y, i, j, t, frame, normals, W, H, scene_pitch, a, pl); break;
+    default: pass_pixel_core<2, true>(P, im, is, pose, C, dmax, rect_x, rect_y, i, j, t, frame, normals, W, H, scene_pitch, a, pl); break;
   }
 }
 
@@ -330,6 +418,73 @@ LMX_PR_FN void solve(const int64_t a[kSums], double w[3], double v[3]) {
   if (!ok) {
     const double N = (double)n;
     for (int k = 0; k < 3; ++k) { w[k] = 0.0; v[k] = (double)a[4 + k] / N; }
+  }
+}
+
+// PLANE's step of a pass with n > 0: a the 17 sums, pl the 29, k the stage's point_shift (0..20).  One copy of the Cholesky serves the
+// plane system and, where that is not taken, SOLVE's own (attempt 1: its matrix converted to double entry by entry, the same operations in
+// the same order, so the same bits as solve()); it runs in place, L in A's lower triangle, so that the device's private arrays stay small.
+LMX_PR_FN void solve_plane(const int64_t a[kSums], const int64_t pl[kPlaneSums], int32_t min_pairs, int32_t k, double w[3], double v[3]) {
+  const int64_t n = a[0], sx = a[1], sy = a[2], sz = a[3];
+  const double lambda = 1.0 / (double)((int64_t)1 << k);
+  bool ok = false;
+  for (int attempt = pl[0] >= (int64_t)min_pairs ? 0 : 1; attempt < 2 && !ok; ++attempt) {
+    const int64_t Ai[6][6] = {
+        {a[10] + a[12], -a[8], -a[9], 0, -sz, sy},
+        {-a[8], a[7] + a[12], -a[11], sz, 0, -sx},
+        {-a[9], -a[11], a[7] + a[10], -sy, sx, 0},
+        {0, sz, -sy, n, 0, 0},
+        {-sz, 0, sx, 0, n, 0},
+        {sy, -sx, 0, 0, 0, n}};
+    const double b_pt[6] = {(double)a[13], (double)a[14], (double)a[15], (double)a[4], (double)a[5], (double)a[6]};
+    double A[6][6], b[6];   // the lower triangle of A alone is filled and read
+    int q = 1;
+#ifndef LMX_PR_HOST
+#pragma unroll
+#endif
+    for (int i = 0; i < 6; ++i) {
+      const double si = i < 3 ? 1.0 : 1.0 / 16384.0;
+#ifndef LMX_PR_HOST
+#pragma unroll
+#endif
+      for (int j = i; j < 6; ++j) {
+        const double sj = j < 3 ? 1.0 : 1.0 / 16384.0;
+        const double G = ((double)pl[q++] * si) * sj;
+        A[j][i] = attempt == 0 ? G + lambda * (double)Ai[i][j] : (double)Ai[i][j];
+      }
+      b[i] = attempt == 0 ? (double)pl[22 + i] * si + lambda * b_pt[i] : b_pt[i];
+    }
+    ok = true;
+    for (int j = 0; j < 6 && ok; ++j) {
+      double d = A[j][j];
+      for (int m = 0; m < j; ++m) d = d - A[j][m] * A[j][m];
+      if (!(d > 0.0)) { ok = false; break; }
+      A[j][j] = sqrt(d);
+      for (int i = j + 1; i < 6; ++i) {
+        double e = A[i][j];
+        for (int m = 0; m < j; ++m) e = e - A[i][m] * A[j][m];
+        A[i][j] = e / A[j][j];
+      }
+    }
+    if (ok) {
+      double y[6], z[6];
+      for (int i = 0; i < 6; ++i) {
+        double e = b[i];
+        for (int m = 0; m < i; ++m) e = e - A[i][m] * y[m];
+        y[i] = e / A[i][i];
+      }
+      for (int i = 5; i >= 0; --i) {
+        double e = y[i];
+        for (int m = i + 1; m < 6; ++m) e = e - A[m][i] * z[m];
+        z[i] = e / A[i][i];
+      }
+      for (int m = 0; m < 3; ++m) { w[m] = z[m]; v[m] = z[3 + m]; }
+      ok = ((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2]) <= 1.0 && ((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]) <= kMaxStepTicksSq;
+    }
+  }
+  if (!ok) {   // SOLVE's translation-only step
+    const double N = (double)n;
+    for (int m = 0; m < 3; ++m) { w[m] = 0.0; v[m] = (double)a[4 + m] / N; }
   }
 }
 
@@ -408,6 +563,42 @@ LMX_PR_FN void enter_stage(const Schedule& S, int32_t stage, Record* r, StagedCo
 }
 
 // after_pass under a schedule: what follows pass sc->k of stage sc->stage.  True: another pass runs, of stage sc->stage as this leaves it.
+// K (null: no stage is PLANE): the stages' point_shift; pl: the 29 sums of the pass, read when its stage has a shift >= 0.
+LMX_PR_FN bool after_pass_plane(const Params& P, const Schedule& S, const PlaneShifts* K, const int64_t a[kSums], const int64_t* pl, const double c[3], Pose* pose, Record* r,
+                                StagedControl* sc) {
+  const Stage& st = S.stage[sc->stage];
+  const bool last = sc->stage == S.n_stages - 1;
+  const int32_t n = (int32_t)a[0];
+  const double rms = rms_of(a);
+  bool more = false;
+  if (sc->stage == 0 && sc->k == 0) { r->n_pairs_first = n; r->rms_first_mm = rms; }
+  if (sc->final_pass) {
+    r->n_pairs_last = n; r->rms_last_mm = rms;
+  } else if (n < P.min_pairs) {
+    r->status = LOST; r->n_pairs_last = n; r->rms_last_mm = rms;
+  } else {
+    double w[3], v[3];
+    const int32_t shift = K ? K->shift[sc->stage] : -1;
+    if (shift >= 0) solve_plane(a, pl, P.min_pairs, shift, w, v);
+    else solve(a, w, v);
+    const bool converged = update_eps(st.eps_rot_rad, st.eps_trans_mm, w, v, c, pose);
+    r->iterations += 1;
+    if (converged) r->status = CONVERGED;
+    const bool done = converged || sc->k + 1 >= st.max_iterations;
+    sc->k += 1;
+    if (last) sc->final_pass = done;
+    else if (done) enter_stage(S, sc->stage + 1, r, sc);
+    more = true;
+  }
+  if (!more) {
+    r->reserved = sc->stage;
+    for (int q = 0; q < 9; ++q) r->R[q] = pose->R[q];
+    for (int q = 0; q < 3; ++q) r->t_mm[q] = pose->t[q];
+  }
+  return more;
+}
+
+// after_pass_plane without a shift.  Written out, not forwarded: the point-to-point kernels keep the code they had before PLANE existed.
 LMX_PR_FN bool after_pass_staged(const Params& P, const Schedule& S, const int64_t a[kSums], const double c[3], Pose* pose, Record* r, StagedControl* sc) {
   const Stage& st = S.stage[sc->stage];
   const bool last = sc->stage == S.n_stages - 1;
@@ -439,9 +630,12 @@ LMX_PR_FN bool after_pass_staged(const Params& P, const Schedule& S, const int64
   return more;
 }
 
-// refine_job under a schedule.  sums (may be null): [schedule_passes(S)][kSums], one row per pass in the order the passes ran.
-LMX_PR_FN void refine_job_staged(const Params& P, const Schedule& S, const uint16_t* crop, int32_t w, int32_t h, int32_t pitch, int32_t rect_x, int32_t rect_y,
-                                 const uint16_t* scene, int32_t W, int32_t H, size_t scene_pitch, int32_t x, int32_t y, Record* r, int64_t* sums) {
+// refine_job under a schedule and the stages' point_shift K (PLANE above).  sums (may be null): [schedule_passes(S)][kSums], one row per pass
+// in the order the passes ran; plane_sums (may be null): [schedule_passes(S)][kPlaneSums], the rows of PLANE passes.  normals: the scene's
+// normal map, H rows of scene_pitch elements; null when no stage has a shift >= 0.  refine_job_staged is this with every shift -1.
+LMX_PR_FN void refine_job_plane(const Params& P, const Schedule& S, const PlaneShifts& K, const uint16_t* crop, int32_t w, int32_t h, int32_t pitch, int32_t rect_x, int32_t rect_y,
+                                const uint16_t* scene, const nv::Packed* normals, int32_t W, int32_t H, size_t scene_pitch, int32_t x, int32_t y, Record* r, int64_t* sums,
+                                int64_t* plane_sums) {
   int64_t place[kPlaceSums] = {0, 0, 0, 0, 0, 0, 0, 0};
   for (int32_t i = 0; i < h; ++i) {
     int32_t Y = 0;
@@ -465,18 +659,29 @@ LMX_PR_FN void refine_job_staged(const Params& P, const Schedule& S, const uint1
     const Stage& st = S.stage[sc.stage];
     const int64_t dmax = dist_ticks(st.max_dist_mm);
     double c[3];
-    int64_t C[3], a[kSums];
+    int64_t C[3], a[kSums], pl[kPlaneSums];
+    const bool plane = K.shift[sc.stage] >= 0;
     for (int q = 0; q < kSums; ++q) a[q] = 0;
+    for (int q = 0; q < kPlaneSums; ++q) pl[q] = 0;
     centre_of(pose, m0, c, C);
     for (int32_t i = 0; i < h; i += st.stride)
       for (int32_t j = 0; j < w; j += st.stride) {
         const uint16_t t = crop[(size_t)i * (size_t)pitch + j];
-        if (t != 0) pass_pixel_rad(P, st.search_radius, im, is, pose, C, dmax, rect_x, rect_y, i, j, t, scene, W, H, scene_pitch, a);
+        if (t == 0) continue;
+        if (plane) pass_pixel_plane_rad(P, st.search_radius, im, is, pose, C, dmax, rect_x, rect_y, i, j, t, scene, normals, W, H, scene_pitch, a, pl);
+        else pass_pixel_rad(P, st.search_radius, im, is, pose, C, dmax, rect_x, rect_y, i, j, t, scene, W, H, scene_pitch, a);
       }
     if (sums)
       for (int q = 0; q < kSums; ++q) sums[(size_t)pass * kSums + q] = a[q];
-    if (!after_pass_staged(P, S, a, c, &pose, r, &sc)) return;
+    if (plane_sums && plane)
+      for (int q = 0; q < kPlaneSums; ++q) plane_sums[(size_t)pass * kPlaneSums + q] = pl[q];
+    if (!after_pass_plane(P, S, &K, a, pl, c, &pose, r, &sc)) return;
   }
+}
+
+LMX_PR_FN void refine_job_staged(const Params& P, const Schedule& S, const uint16_t* crop, int32_t w, int32_t h, int32_t pitch, int32_t rect_x, int32_t rect_y,
+                                 const uint16_t* scene, int32_t W, int32_t H, size_t scene_pitch, int32_t x, int32_t y, Record* r, int64_t* sums) {
+  refine_job_plane(P, S, kNoPlane, crop, w, h, pitch, rect_x, rect_y, scene, nullptr, W, H, scene_pitch, x, y, r, sums, nullptr);
 }
 
 // One whole job, pixel by pixel on one thread: the definition the kernel is tested against.  crop: [h][pitch]; scene: H rows of scene_pitch
@@ -544,6 +749,15 @@ LMX_PR_FN const char* check_schedule(const Schedule& S) {
     if (st.stride != 1 && st.stride != 2 && st.stride != 4 && st.stride != 8) return "a stage's stride must be 1, 2, 4 or 8";
     if (k + 1 < S.n_stages && st.max_iterations < 1) return "a stage that is not the last needs max_iterations >= 1";
   }
+  return nullptr;
+}
+
+// Why a point_shift list is refused (null: it is fine): what lmx_depth_templates_set_refine_plane checks.
+LMX_PR_FN const char* check_plane(const int32_t* point_shift, int32_t n_stages) {
+  if (n_stages < 0 || n_stages > kMaxStages) return "n_stages must lie in 0 .. 4";
+  if (n_stages > 0 && !point_shift) return "point_shift is null with n_stages > 0";
+  for (int32_t k = 0; k < n_stages; ++k)
+    if (point_shift[k] < -1 || point_shift[k] > kMaxPointShift) return "a point_shift must lie in -1 .. 20";
   return nullptr;
 }
 

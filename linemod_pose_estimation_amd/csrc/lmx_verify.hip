@@ -28,7 +28,9 @@
 // Pose refinement (lmx_pose_refine_matches; arithmetic and control: lmx_pose_refine.hpp), on the same table and scene:
 //   k_pose_refine  one 256-lane workgroup per match, the same walk over the crop's vectors once per pass, every pass of a job inside one
 //                  launch; under a refinement schedule (lmx_depth_templates_set_refine_schedule) every pass of every stage, a stage of
-//                  stride > 1 walking a pixel lattice spread over the lanes instead; see the kernel
+//                  stride > 1 walking a pixel lattice spread over the lanes instead; see the kernel.  Its PLANE instantiation (and those
+//                  of the two cluster kernels below) runs only when a stage in force has a point_shift >= 0
+//                  (lmx_depth_templates_set_refine_plane): such a stage adds the 29 point-to-plane sums against the scene's normals
 // Pose verification (lmx_pose_verify_matches; arithmetic: lmx_pose_verify.hpp), the stage after it:
 //   k_pose_verify  one 256-lane workgroup per match: the crop walk for the voxel grid's extent, a 32 KiB occupancy bitmap in LDS marked
 //                  from the scene pixels of the posed model's region, the crop walk again to count the points in marked voxels; see the kernel
@@ -348,8 +350,10 @@ __device__ __forceinline__ void crop_pixels(const DepthCrop& c, int lane, int wa
 
 // The first n of a lane's sums added up over the wave, lane 0's totals into the wave's row of `part`; then the barrier behind which any
 // lane may add the four rows.
-__device__ __forceinline__ void wave_sums_to_lds(const int64_t* a, int n, long long (*part)[pr::kSums], int lane, int wave) {
-  for (int k = 0; k < n; ++k) {
+template <int ROW>
+__device__ __forceinline__ void wave_sums_to_lds(const int64_t* a, int n, long long (*part)[ROW], int lane, int wave) {
+#pragma unroll
+  for (int k = 0; k < n; ++k) {   // n is a constant at every call: the sums stay in registers
     const long long v = wave_sum<long long>((long long)a[k]);
     if (lane == 0) part[wave][k] = v;
   }
@@ -391,12 +395,19 @@ __device__ __forceinline__ int64_t uniform_i64(int64_t v) {
 // any other with lattice_pixels.  Integer sums: the result does not depend on which lane took which pixel.  No atomics, no workgroup
 // waits for another.  What is no job (template or frame outside the tables) or has an empty crop gets a zeroed record before any barrier.
 // dbg (null outside the test hook): the sums of job 0's passes, one row of 17 per pass in the order they ran.
+// PLANE (lmx_pose_refine.hpp, PLANE; launched only when a stage in force has a point_shift >= 0, K): whether a stage is a plane stage is a
+// workgroup-uniform branch.  A -1 stage runs the 17-sum pass above; a plane stage keeps 46 int64 sums per lane (the 17 and the 29), reads
+// the chosen candidate's stored normal from `normals` (the scene's, [frame][H][W], made ready on the launch stream by scene_normals_on),
+// reduces all 46 the same way and lane 0 takes solve_plane's step.  Its dbg rows are 46 wide, the 29 of a -1 stage's row left alone.
+// Without PLANE neither `normals` nor K is read and the code is what it was before the parameter existed.
 // pose_refine_body is that workgroup's work on one job and its record `out` (dbg: null, or where this job's sums go), shared by
 // k_pose_refine, k_pose_refine_clusters and k_rough_refine_clusters; forceinline: each kernel gets its own copy of the LDS arrays.
+template <bool PLANE>
 __device__ __forceinline__ void pose_refine_body(const DepthCrop* __restrict__ crops, int32_t count, const PoseJob job, const uint16_t* __restrict__ scene,
                                                  int32_t n_frames, int W, int H, const pr::Params& P, const pr::Schedule& S, lmx_pose_refine_t* __restrict__ out,
-                                                 long long* __restrict__ dbg) {
-  __shared__ long long s_part[4][pr::kSums];
+                                                 long long* __restrict__ dbg, const nv::Packed* __restrict__ normals, const pr::PlaneShifts& K) {
+  constexpr int ROW = PLANE ? pr::kAllSums : pr::kSums;
+  __shared__ long long s_part[4][ROW];
   __shared__ pr::Pose s_pose;
   __shared__ double s_c[3];
   __shared__ long long s_C[3];
@@ -416,7 +427,7 @@ __device__ __forceinline__ void pose_refine_body(const DepthCrop* __restrict__ c
   pr::StagedControl sc = {0, 0, 0};
   double m0[3] = {0.0, 0.0, 0.0};
 
-  int64_t a[pr::kSums];
+  int64_t a[ROW];
   for (int k = 0; k < pr::kSums; ++k) a[k] = 0;
   crop_pixels(c, lane, wave, [&](int i, int j, uint16_t t) {
     int32_t X = 0, Y = 0;
@@ -450,20 +461,37 @@ __device__ __forceinline__ void pose_refine_body(const DepthCrop* __restrict__ c
     const int32_t radius = st.search_radius, stride = st.stride;
     const pr::Pose pose = s_pose;
     const int64_t C[3] = {s_C[0], s_C[1], s_C[2]};
-    for (int q = 0; q < pr::kSums; ++q) a[q] = 0;
-    auto pixel = [&](int i, int j, uint16_t t) {
-      pr::pass_pixel_rad(P, radius, im, is, pose, C, dmax, job.rect_x, job.rect_y, i, j, t, frame, W, H, (size_t)W, a);
-    };
-    if (stride == 1) crop_pixels(c, lane, wave, pixel);
-    else lattice_pixels(c, stride, job.lat_x, job.lat_y, tid, pixel);
-    wave_sums_to_lds(a, pr::kSums, s_part, lane, wave);
+    const bool plane = PLANE && K.shift[stage] >= 0;   // workgroup-uniform
+    if (plane) {
+      for (int q = 0; q < ROW; ++q) a[q] = 0;
+      const nv::Packed* nframe = normals + (size_t)job.frame * H * W;
+      auto pixel = [&](int i, int j, uint16_t t) {
+        pr::pass_pixel_plane_rad(P, radius, im, is, pose, C, dmax, job.rect_x, job.rect_y, i, j, t, frame, nframe, W, H, (size_t)W, a, a + pr::kSums);
+      };
+      if (stride == 1) crop_pixels(c, lane, wave, pixel);
+      else lattice_pixels(c, stride, job.lat_x, job.lat_y, tid, pixel);
+      wave_sums_to_lds(a, ROW, s_part, lane, wave);
+    } else {
+      for (int q = 0; q < pr::kSums; ++q) a[q] = 0;
+      auto pixel = [&](int i, int j, uint16_t t) {
+        pr::pass_pixel_rad(P, radius, im, is, pose, C, dmax, job.rect_x, job.rect_y, i, j, t, frame, W, H, (size_t)W, a);
+      };
+      if (stride == 1) crop_pixels(c, lane, wave, pixel);
+      else lattice_pixels(c, stride, job.lat_x, job.lat_y, tid, pixel);
+      wave_sums_to_lds(a, pr::kSums, s_part, lane, wave);
+    }
     if (tid == 0) {
-      int64_t total[pr::kSums];
+      int64_t total[ROW];
       for (int q = 0; q < pr::kSums; ++q) total[q] = s_part[0][q] + s_part[1][q] + s_part[2][q] + s_part[3][q];
-      if (dbg)
-        for (int q = 0; q < pr::kSums; ++q) dbg[(size_t)pass * pr::kSums + q] = total[q];
+      if (plane)
+        for (int q = pr::kSums; q < ROW; ++q) total[q] = s_part[0][q] + s_part[1][q] + s_part[2][q] + s_part[3][q];
+      if (dbg) {
+        for (int q = 0; q < pr::kSums; ++q) dbg[(size_t)pass * ROW + q] = total[q];
+        if (plane)
+          for (int q = pr::kSums; q < ROW; ++q) dbg[(size_t)pass * ROW + q] = total[q];
+      }
       const double cc[3] = {s_c[0], s_c[1], s_c[2]};
-      const bool more = pr::after_pass_staged(P, S, total, cc, &pose0, &rec, &sc);
+      const bool more = PLANE ? pr::after_pass_plane(P, S, &K, total, total + pr::kSums, cc, &pose0, &rec, &sc) : pr::after_pass_staged(P, S, total, cc, &pose0, &rec, &sc);
       if (more) {
         int64_t Cn[3];
         pr::centre_of(pose0, m0, s_c, Cn);
@@ -481,10 +509,12 @@ __device__ __forceinline__ void pose_refine_body(const DepthCrop* __restrict__ c
   }
 }
 
+template <bool PLANE>
 __global__ __launch_bounds__(256) void k_pose_refine(const DepthCrop* __restrict__ crops, int32_t count, const PoseJob* __restrict__ jobs,
                                                      const uint16_t* __restrict__ scene, int32_t n_frames, int W, int H, const pr::Params P, const pr::Schedule S,
-                                                     lmx_pose_refine_t* __restrict__ out, long long* __restrict__ dbg) {
-  pose_refine_body(crops, count, jobs[blockIdx.x], scene, n_frames, W, H, P, S, &out[blockIdx.x], blockIdx.x == 0 ? dbg : nullptr);
+                                                     lmx_pose_refine_t* __restrict__ out, long long* __restrict__ dbg, const nv::Packed* __restrict__ normals,
+                                                     const pr::PlaneShifts K) {
+  pose_refine_body<PLANE>(crops, count, jobs[blockIdx.x], scene, n_frames, W, H, P, S, &out[blockIdx.x], blockIdx.x == 0 ? dbg : nullptr, normals, K);
 }
 
 // ---- pose verification (lmx_pose_verify_matches; arithmetic: lmx_pose_verify.hpp) ---------------------------------------------------------------------
@@ -677,7 +707,9 @@ __device__ __forceinline__ pc::Slot uniform_slot(const pc::Slot& v) {
 // a broken list, no job) or k_pose_refine's body on the leader's job.  Workgroup 0 also reports n_live and the header's flag; a slot's
 // flags go to chain_header[1] by a vector atomic OR of lane 0.  waves_per_eu(2): the body sits at 247 vector registers; without the
 // attribute the prologue's scalar spills take the kernel a few registers past 256 and to half of k_pose_refine's occupancy.
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_pose_refine_clusters(const ChainArgs a, const pr::Params P, const pr::Schedule S) {
+template <bool PLANE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PLANE ? 1 : 2))) void k_pose_refine_clusters(const ChainArgs a, const pr::Params P, const pr::Schedule S,
+                                                                                                      const nv::Packed* __restrict__ normals, const pr::PlaneShifts K) {
   __shared__ pc::Slot s_slot;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const uint32_t k = blockIdx.x, n_live = pc::n_live(a.L);
@@ -702,7 +734,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
     return;
   }
   const PoseJob job = {s.x, s.y, s.template_id, s.frame, s.rect_x, s.rect_y, 0, 0};
-  pose_refine_body(a.crops, a.T.count, job, a.scene, a.L.n_frames, a.W, a.H, P, S, &a.poses[k], nullptr);
+  pose_refine_body<PLANE>(a.crops, a.T.count, job, a.scene, a.L.n_frames, a.W, a.H, P, S, &a.poses[k], nullptr, normals, K);
 }
 
 // The same grid behind it.  Wave 0 decides the slot again from leaders[k] (the job is not kept between the kernels: a match, a frame and a
@@ -749,7 +781,9 @@ struct RoughChainArgs {
 // local arrays, as in k_pose_refine: 247, 106, 592), 2 waves per SIMD as k_pose_refine and k_pose_refine_clusters (249, 106, 592);
 // the figures before the stage loop are in profiles/pose_refine_staged.txt.
 // k_rough_verify_clusters: 67 vector registers, 106 scalar, no scratch, 4 waves per SIMD, as k_pose_verify_clusters.
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_rough_refine_clusters(const RoughChainArgs a, const pr::Params P, const pr::Schedule S) {
+template <bool PLANE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PLANE ? 1 : 2))) void k_rough_refine_clusters(const RoughChainArgs a, const pr::Params P, const pr::Schedule S,
+                                                                                                       const nv::Packed* __restrict__ normals, const pr::PlaneShifts K) {
   const uint32_t k = blockIdx.x;
   if (k >= pc::n_live(a.header, a.cap_clusters)) return;
   const rp::Job* j = a.jobs + k;
@@ -761,7 +795,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
   const PoseJob job = {__builtin_amdgcn_readfirstlane(j->x), __builtin_amdgcn_readfirstlane(j->y), (int32_t)k, __builtin_amdgcn_readfirstlane(j->frame),
                        __builtin_amdgcn_readfirstlane(j->rect_x), __builtin_amdgcn_readfirstlane(j->rect_y), __builtin_amdgcn_readfirstlane(j->lat_x),
                        __builtin_amdgcn_readfirstlane(j->lat_y)};
-  pose_refine_body(a.crops, a.cap_slots, job, a.scene, a.n_frames, a.W, a.H, P, S, &a.poses[k], nullptr);
+  pose_refine_body<PLANE>(a.crops, a.cap_slots, job, a.scene, a.n_frames, a.W, a.H, P, S, &a.poses[k], nullptr, normals, K);
 }
 
 // k_pose_verify_clusters behind it, on the same job.
@@ -803,6 +837,12 @@ struct lmx_depth_templates {
   // lmx_depth_templates_set_refine_schedule (n_stages 0: none).  A call reads it under `m` and hands it to its kernel by value
   lmx::pr::Schedule schedule = {0, 0, {}};
   lmx::pr::Schedule schedule_for(const lmx::pr::Params& P) const { return schedule.n_stages > 0 ? schedule : lmx::pr::single_stage(P); }
+  // lmx_depth_templates_set_refine_plane: entry s is stage s's point_shift of whatever schedule is in force (a call without one is stage 0),
+  // -1 beyond plane_stages; read under `m` like the schedule and handed to the kernel by value
+  lmx::pr::PlaneShifts plane = lmx::pr::kNoPlane;
+  int32_t plane_stages = 0;
+  // does a call under schedule S run the PLANE kernels?
+  bool plane_for(const lmx::pr::Schedule& S) const { return lmx::pr::any_plane(plane, S.n_stages); }
   lmx::VerifyJob *d_vjobs = nullptr, *h_vjobs = nullptr;   // lmx_pose_verify_matches: the same pair
   lmx_pose_verify_t *d_vout = nullptr, *h_vout = nullptr;
   size_t vjobs_cap = 0, vout_cap = 0;
@@ -963,6 +1003,13 @@ struct lmx_depth_templates {
     if (lmx_status st = compute_scene_normals(on, n_frames, W, H)) return st;
     scene_normals_valid = true;
     return LMX_OK;
+  }
+  // A PLANE launch on stream `on` reads the scene's normals: as a normal-scored walk, but it needs neither the crops' normals nor the
+  // angle table.  The setter saw enable_normals.
+  lmx_status plane_normals_on(hipStream_t on, int32_t n_frames, int32_t W, int32_t H) {
+    if (!normals_on) { lmx::set_error("a point_shift >= 0 is set and the normals are off: call lmx_depth_templates_enable_normals first"); return LMX_ERR_INVALID_ARG; }
+    if (!normals_ready) HIP_RETURN(hipEventCreateWithFlags(&normals_ready, hipEventDisableTiming));
+    return scene_normals_on(on, nullptr, n_frames, W, H);
   }
   void free_normal_crops() {
     (void)hipFree(d_ncrops); (void)hipFree(d_ntable);
@@ -1841,21 +1888,27 @@ lmx_status pose_call(const PoseCall& a, const std::function<int(size_t, const lm
   return st;
 }
 
-// The body of lmx_pose_refine_matches and of its test hook (dbg: the sums of job 0's passes, [max_iterations + 1][17], under a schedule
-// [sum of its max_iterations + 1][17]).
+// The body of lmx_pose_refine_matches and of its test hooks (dbg: the sums of job 0's passes, [max_iterations + 1][17], under a schedule
+// [sum of its max_iterations + 1][17]; dbg_plane, only next to dbg: the same rows of the 29 plane sums).  With a point_shift >= 0 in force
+// (lmx_depth_templates_set_refine_plane) the PLANE kernel runs, behind the normals of the frames in d_scene -- resident or staged.
 lmx_status pose_refine_impl(const char* what, lmx_depth_templates* t, const lmx_image* depth, int32_t n_frames, const lmx_match_t* matches, const size_t* offsets,
-                            int32_t class_index, const lmx_pose_refine_params* params, lmx_pose_refine_t* out, int64_t* dbg) {
+                            int32_t class_index, const lmx_pose_refine_params* params, lmx_pose_refine_t* out, int64_t* dbg, int64_t* dbg_plane = nullptr) {
   using namespace lmx;
   if (!t) { set_error("%s: null argument", what); return LMX_ERR_INVALID_ARG; }
   pr::Params P;
   if (lmx_status st = pose_params(what, params, &P)) return st;
   const PoseCall call = {what, t, depth, n_frames, matches, offsets, class_index, params->rects, out, sizeof(lmx_pose_refine_t), false, 0};
   pr::Schedule S = pr::single_stage(P);
+  pr::PlaneShifts K = pr::kNoPlane;
+  bool plane = false;
   return pose_call(
       call, nullptr,
       [&]() {   // t->m is held from here on
         S = t->schedule_for(P);
+        K = t->plane;
+        plane = t->plane_for(S);
         if (dbg) std::memset(dbg, 0, (size_t)pr::schedule_passes(S) * pr::kSums * sizeof(int64_t));
+        if (dbg_plane) std::memset(dbg_plane, 0, (size_t)pr::schedule_passes(S) * pr::kPlaneSums * sizeof(int64_t));
       },
       [&](int32_t W, int32_t H, int32_t n_slots, size_t count, const int32_t* rects) -> lmx_status {
         hipStream_t s = t->s;
@@ -1868,21 +1921,37 @@ lmx_status pose_refine_impl(const char* what, lmx_depth_templates* t, const lmx_
           t->h_pjobs[k] = PoseJob{m.x, m.y, m.template_id, t->sel_slot[k], r[0], r[1], 0, 0};
         }
         DeviceBuffer d_dbg;
-        const size_t dbg_bytes = (size_t)pr::schedule_passes(S) * pr::kSums * sizeof(int64_t);
+        const size_t rows = (size_t)pr::schedule_passes(S), row = plane ? pr::kAllSums : pr::kSums;   // the PLANE kernel's rows hold all 46
+        const size_t dbg_bytes = rows * row * sizeof(int64_t);
+        std::vector<int64_t> h_dbg;
+        if (plane)
+          if (lmx_status g = t->plane_normals_on(s, n_slots, W, H)) return g;
         if (dbg) {
           HIP_RETURN(hipMalloc(&d_dbg.p, dbg_bytes));
           HIP_RETURN(hipMemsetAsync(d_dbg.p, 0, dbg_bytes, s));
         }
         HIP_RETURN(hipMemcpyAsync(t->d_pjobs, t->h_pjobs, n * sizeof(PoseJob), hipMemcpyHostToDevice, s));
         const int pe = t->prof_begin(lmx_depth_templates::PK_POSE_REFINE, s);
-        hipLaunchKernelGGL(k_pose_refine, dim3((unsigned)n), dim3(256), 0, s, t->d_table, (int32_t)count, t->d_pjobs, t->d_scene, n_slots, W, H, P, S, t->d_pout,
-                           d_dbg.as<long long>());
+        if (plane)
+          hipLaunchKernelGGL(k_pose_refine<true>, dim3((unsigned)n), dim3(256), 0, s, t->d_table, (int32_t)count, t->d_pjobs, t->d_scene, n_slots, W, H, P, S, t->d_pout,
+                             d_dbg.as<long long>(), t->d_scene_normals, K);
+        else
+          hipLaunchKernelGGL(k_pose_refine<false>, dim3((unsigned)n), dim3(256), 0, s, t->d_table, (int32_t)count, t->d_pjobs, t->d_scene, n_slots, W, H, P, S, t->d_pout,
+                             d_dbg.as<long long>(), nullptr, K);
         t->prof_end(pe, s);
         HIP_RETURN(hipGetLastError());
         HIP_RETURN(hipMemcpyAsync(t->h_pout, t->d_pout, n * sizeof(lmx_pose_refine_t), hipMemcpyDeviceToHost, s));
-        if (dbg) HIP_RETURN(hipMemcpyAsync(dbg, d_dbg.p, dbg_bytes, hipMemcpyDeviceToHost, s));
+        if (dbg) {
+          if (plane) h_dbg.resize(rows * row);
+          HIP_RETURN(hipMemcpyAsync(plane ? h_dbg.data() : dbg, d_dbg.p, dbg_bytes, hipMemcpyDeviceToHost, s));
+        }
         HIP_RETURN(hipStreamSynchronize(s));   // the results are here, the scratch buffer may go
+        if (depth) t->scene_normals_valid = false;   // they belong to staged frames that are no scene
         for (size_t k = 0; k < n; ++k) out[t->sel[k]] = t->h_pout[k];
+        for (size_t r = 0; r < rows && dbg && plane; ++r) {
+          std::memcpy(dbg + r * pr::kSums, &h_dbg[r * row], pr::kSums * sizeof(int64_t));
+          if (dbg_plane) std::memcpy(dbg_plane + r * pr::kPlaneSums, &h_dbg[r * row + pr::kSums], pr::kPlaneSums * sizeof(int64_t));
+        }
         return LMX_OK;
       });
 }
@@ -1915,6 +1984,45 @@ extern "C" lmx_status lmx_debug_pose_refine_sums(lmx_depth_templates* t, const l
     if (!depth || !match || !out || !sums) { lmx::set_error("lmx_debug_pose_refine_sums: null argument"); return LMX_ERR_INVALID_ARG; }
     const size_t offsets[2] = {0, 1};
     return pose_refine_impl("lmx_debug_pose_refine_sums", t, depth, 1, match, offsets, -1, params, out, sums);
+  });
+}
+
+extern "C" lmx_status lmx_debug_pose_refine_plane_sums(lmx_depth_templates* t, const lmx_image* depth, const lmx_match_t* match, const lmx_pose_refine_params* params,
+                                                       lmx_pose_refine_t* out, int64_t* sums, int64_t* plane_sums) {
+  return lmx::guarded("lmx_debug_pose_refine_plane_sums", [&]() -> lmx_status {
+    if (!depth || !match || !out || !sums || !plane_sums) { lmx::set_error("lmx_debug_pose_refine_plane_sums: null argument"); return LMX_ERR_INVALID_ARG; }
+    const size_t offsets[2] = {0, 1};
+    return pose_refine_impl("lmx_debug_pose_refine_plane_sums", t, depth, 1, match, offsets, -1, params, out, sums, plane_sums);
+  });
+}
+
+extern "C" lmx_status lmx_depth_templates_set_refine_plane(lmx_depth_templates* t, const int32_t* point_shift, int32_t n_stages) {
+  return lmx::guarded("lmx_depth_templates_set_refine_plane", [&]() -> lmx_status {
+    using namespace lmx;
+    const char* what = "lmx_depth_templates_set_refine_plane";
+    if (!t) { set_error("%s: null argument", what); return LMX_ERR_INVALID_ARG; }
+    if (const char* why = pr::check_plane(point_shift, n_stages)) { set_error("%s: %s (n_stages = %d)", what, why, n_stages); return LMX_ERR_INVALID_ARG; }
+    pr::PlaneShifts K = pr::kNoPlane;
+    if (point_shift)
+      for (int32_t k = 0; k < n_stages; ++k) K.shift[k] = point_shift[k];
+    std::lock_guard<std::mutex> lk(t->m);
+    if (pr::any_plane(K, pr::kMaxStages) && !t->normals_on) {
+      set_error("%s: a point_shift >= 0 reads the scene's normals: call lmx_depth_templates_enable_normals first", what);
+      return LMX_ERR_INVALID_ARG;
+    }
+    t->plane = K;   // queued work took its shifts by value: nothing to wait for
+    t->plane_stages = point_shift ? n_stages : 0;
+    return LMX_OK;
+  });
+}
+
+extern "C" lmx_status lmx_depth_templates_get_refine_plane(const lmx_depth_templates* t, int32_t out[LMX_POSE_MAX_STAGES], int32_t* n_stages) {
+  return lmx::guarded("lmx_depth_templates_get_refine_plane", [&]() -> lmx_status {
+    if (!t || !out || !n_stages) { lmx::set_error("lmx_depth_templates_get_refine_plane: null argument"); return LMX_ERR_INVALID_ARG; }
+    std::lock_guard<std::mutex> lk(const_cast<lmx_depth_templates*>(t)->m);
+    *n_stages = t->plane_stages;
+    for (int32_t k = 0; k < LMX_POSE_MAX_STAGES; ++k) out[k] = t->plane.shift[k];
+    return LMX_OK;
   });
 }
 
@@ -2158,8 +2266,16 @@ lmx_status chain_queue(lmx_depth_templates* t, const lmx_pose_chain_desc& d, con
   a.chain_header = d.chain_header; a.leaders = d.leaders; a.poses = d.poses; a.checks = d.checks; a.keep = d.keep; a.keep_thresh = d.keep_thresh;
   const dim3 grid((unsigned)d.cap_clusters), block(256);
   HIP_RETURN(hipMemsetAsync(d.chain_header, 0, pc::C_WORDS * sizeof(uint32_t), s));
-  int pe = t->prof_begin(lmx_depth_templates::PK_POSE_REFINE_CLUSTERS, s);
-  hipLaunchKernelGGL(k_pose_refine_clusters, grid, block, 0, s, a, PR, t->schedule_for(PR));
+  int pe = -1;
+  const pr::Schedule S = t->schedule_for(PR);
+  if (t->plane_for(S)) {   // the scene's normals first, on this stream: an event wait or one launch, nothing on the host
+    if (lmx_status st = t->plane_normals_on(s, t->scene_frames, t->scene_W, t->scene_H)) return st;
+    pe = t->prof_begin(lmx_depth_templates::PK_POSE_REFINE_CLUSTERS, s);
+    hipLaunchKernelGGL(k_pose_refine_clusters<true>, grid, block, 0, s, a, PR, S, t->d_scene_normals, t->plane);
+  } else {
+    pe = t->prof_begin(lmx_depth_templates::PK_POSE_REFINE_CLUSTERS, s);
+    hipLaunchKernelGGL(k_pose_refine_clusters<false>, grid, block, 0, s, a, PR, S, nullptr, t->plane);
+  }
   t->prof_end(pe, s);
   HIP_RETURN(hipGetLastError());
   if (!same_rects) a.T.rects = t->chain_rects_verify.dev;
@@ -2291,7 +2407,13 @@ lmx_status rough_queue(lmx_depth_templates* t, lmx_rough_model* model, const lmx
   const RoughChainArgs c = {d.header, (uint64_t)d.cap_clusters, model->d_jobs, reinterpret_cast<const DepthCrop*>(model->d_crops), model->cap_slots, t->d_scene,
                             d.n_frames, t->scene_W, t->scene_H, d.chain_header, d.poses, d.checks, d.keep, d.keep_thresh};
   const dim3 grid((unsigned)d.cap_clusters), block(256);
-  hipLaunchKernelGGL(k_rough_refine_clusters, grid, block, 0, s, c, PR, t->schedule_for(PR));
+  const pr::Schedule S = t->schedule_for(PR);
+  if (t->plane_for(S)) {
+    if (lmx_status st = t->plane_normals_on(s, t->scene_frames, t->scene_W, t->scene_H)) return st;
+    hipLaunchKernelGGL(k_rough_refine_clusters<true>, grid, block, 0, s, c, PR, S, t->d_scene_normals, t->plane);
+  } else {
+    hipLaunchKernelGGL(k_rough_refine_clusters<false>, grid, block, 0, s, c, PR, S, nullptr, t->plane);
+  }
   HIP_RETURN(hipGetLastError());
   hipLaunchKernelGGL(k_rough_verify_clusters, grid, block, 0, s, c, PV);
   HIP_RETURN(hipGetLastError());

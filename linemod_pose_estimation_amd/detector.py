@@ -1603,6 +1603,21 @@ class DepthTemplates:
         _lib.check(_lib.lib().lmx_depth_templates_get_refine_schedule(self.h, arr, C.byref(n)))
         return [{k: getattr(arr[i], k) for k in self.STAGE_FIELDS} for i in range(n.value)]
 
+    def set_refine_plane(self, point_shift):
+        """The stages' point_shift (lmx_depth_templates_set_refine_plane): a list of up to 4 integers, entry s for stage s of the schedule in
+        force (a call without one is stage 0).  -1: the point-to-point stage; k in 0..20: point-to-plane against the scene's stored normals
+        (enable_normals first), the point term weighted 2**-k -- meant for few iterations.  None or []: clears the setting."""
+        shifts = [int(v) for v in point_shift] if point_shift is not None else []
+        arr = (C.c_int32 * max(len(shifts), 1))(*shifts)
+        _lib.check(_lib.lib().lmx_depth_templates_set_refine_plane(self.h, arr if shifts else None, len(shifts)))
+
+    def get_refine_plane(self):
+        """The point_shift list in force (lmx_depth_templates_get_refine_plane), [] for none."""
+        arr = (C.c_int32 * _lib.LMX_POSE_MAX_STAGES)()
+        n = C.c_int32(0)
+        _lib.check(_lib.lib().lmx_depth_templates_get_refine_plane(self.h, arr, C.byref(n)))
+        return [int(arr[i]) for i in range(n.value)]
+
     def refine_poses(self, matches, depth_frames=None, offsets=None, class_index=-1, model_camera=None, scene_camera=None, max_dist_mm=10.0,
                      max_iterations=20, min_pairs=16, search_radius=1, eps_rot_rad=1e-5, eps_trans_mm=1e-3, rects=None):
         """A rigid transform per match (lmx_pose_refine_matches; the reference's icpPoseRefine stage) -> POSE_REFINE_DTYPE array: R, t_mm map
@@ -1762,6 +1777,22 @@ class DepthTemplates:
         _lib.check(_lib.lib().lmx_debug_pose_refine_sums(self.h, imgs, m.ctypes.data, C.byref(p), out.ctypes.data, sums.ctypes.data))
         del keep, frames
         return out[0], sums
+
+    def debug_pose_refine_plane_sums(self, depth_frame, match, **params):
+        """Test hook (lmx_debug_pose_refine_plane_sums): debug_pose_refine_sums and, row for row, the 29 plane sums of every pass ->
+        (record, int64 [passes, 17], int64 [passes, 29]); the plane rows of point-to-point passes are zeros."""
+        frames, imgs = _depth_images(depth_frame)
+        m = np.ascontiguousarray(match, MATCH_DTYPE).reshape(1)
+        args = dict(max_dist_mm=10.0, max_iterations=20, min_pairs=16, search_radius=1, eps_rot_rad=1e-5, eps_trans_mm=1e-3, rects=None)
+        args.update(params)
+        p, keep = self._pose_params(**args)
+        out = np.zeros(1, POSE_REFINE_DTYPE)
+        sched = self.refine_schedule
+        rows = (sum(st["max_iterations"] for st in sched) if sched else int(args["max_iterations"])) + 1
+        sums, plane = np.zeros((rows, 17), np.int64), np.zeros((rows, 29), np.int64)
+        _lib.check(_lib.lib().lmx_debug_pose_refine_plane_sums(self.h, imgs, m.ctypes.data, C.byref(p), out.ctypes.data, sums.ctypes.data, plane.ctypes.data))
+        del keep, frames
+        return out[0], sums, plane
 
     # Labels of the library's profiling brackets (its PK_* enum, in that order), not symbol names: "k_verify_diff_records", "k_verify_diff"
     # and "k_depth_diff_records" are the record walk with both terms, the job walk with both terms and the depth-only record walk (all

@@ -12,7 +12,9 @@ k_pose_refine + k_pose_verify of the staged leg against k_pose_refine_clusters +
 The chain's grid is cap_clusters workgroups, of which those at or above the live count leave at once: every figure is taken for each
 --cap-clusters value.  These are recorded values, not thresholds.  Needs a GPU.
 --schedule: every leg refines under that schedule (DepthTemplates.set_refine_schedule); the byte-for-byte check is the same.
-usage: pose_chain_bench.py [--threshold 80] [--repeats 40] [--cap-clusters 4096 512] [--schedule S] [--out profiles/pose_chain.txt]"""
+--plane: every leg refines with those point_shift values, one per stage (DepthTemplates.set_refine_plane, after enable_normals with the
+scene camera's focal lengths); "--schedule 1:5:10:1 --plane 8" is the point-to-plane metric at 5 iterations.
+usage: pose_chain_bench.py [--threshold 80] [--repeats 40] [--cap-clusters 4096 512] [--schedule S] [--plane K[,K..]] [--out profiles/pose_chain.txt]"""
 import argparse
 import os
 import sys
@@ -44,6 +46,7 @@ def main():
     ap.add_argument("--cap-clusters", type=int, nargs="+", default=[4096, 512])
     ap.add_argument("--max-candidates", type=int, default=1 << 19)
     ap.add_argument("--schedule", default=None, help="stride:iterations:max_dist:radius,...: the refinement schedule every leg runs under")
+    ap.add_argument("--plane", default=None, help="point_shift per stage, comma-separated: -1 point-to-point, 0..20 point-to-plane")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pose_chain.txt"))
     args = ap.parse_args()
     import torch
@@ -59,6 +62,9 @@ def main():
     if args.schedule:
         import pose_refine_staged_cases as psc
         t.set_refine_schedule(psc.parse_schedule(args.schedule))
+    if args.plane:
+        t.enable_normals(F, F)
+        t.set_refine_plane([int(v) for v in args.plane.split(",")])
     distinct = [ms.make_scene(chip, grid, seed=7000 + f, n_instances=3, other_tri=cpu_mesh, n_other=2)[0] for f in range(16)]
     frames = [distinct[f % len(distinct)] for f in range(B)]
     depth = [np.ascontiguousarray(fr[1]) for fr in frames]
@@ -73,6 +79,8 @@ def main():
              % (len(rects), W, H, args.threshold)]
     if args.schedule:
         lines.append("refinement schedule of every leg: [%s]" % args.schedule)
+    if args.plane:
+        lines.append("point_shift of every leg's stages: [%s]" % args.plane)
 
     for cap in args.cap_clusters:
         state = {"res": None, "poses": None}

@@ -16,8 +16,12 @@ on the largest crop and the ground-truth errors under the schedule are recorded,
 --plain runs the rows without a schedule only, one line each with the rounds' values, and calls nothing a library without schedules
 lacks; with --package-root (another checkout's root, its own built library inside) it measures that checkout: scripts/ab_pose_refine.sh
 alternates two of them.
+--plane SHIFT[,SHIFT...] (DepthTemplates.set_refine_plane, one point_shift per stage of the first --schedule, or of the single stage):
+every row is measured point-to-point at the defaults' 20 iterations and point-to-plane at --plane-iterations, the two legs alternating
+round by round; the device's records under the setting are first compared with the host header's refine_job_plane, byte for byte; the
+ground-truth errors of both come from the same header.  The lines are printed, and written with --out.
 These are recorded values, not thresholds.  Needs a GPU.
-usage: pose_refine_bench.py [--repeats 20] [--rounds 3] [--schedule S [S ...]] [--plain] [--package-root DIR] [--out FILE]"""
+usage: pose_refine_bench.py [--repeats 20] [--rounds 3] [--schedule S [S ...]] [--plane K[,K..]] [--plane-iterations 5] [--plain] [--package-root DIR] [--out FILE]"""
 import argparse
 import ctypes as C
 import math
@@ -65,6 +69,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=3, help="alternations of the legs with --schedule, repetitions of a row with --plain")
     ap.add_argument("--schedule", nargs="+", default=[], help="stride:iterations:max_dist:radius,... per schedule")
+    ap.add_argument("--plane", default=None, help="point_shift per stage, comma-separated: -1 point-to-point, 0..20 point-to-plane")
+    ap.add_argument("--plane-iterations", type=int, default=5, help="max_iterations of the plane leg when no --schedule is given")
     ap.add_argument("--plain", action="store_true", help="only the rows without a schedule, one line each")
     ap.add_argument("--package-root", default=ROOT, help="the checkout whose package and library are measured")
     ap.add_argument("--out", default=None)
@@ -74,7 +80,7 @@ def main():
     sys.path.insert(0, os.path.join(root, "tests"))
     import pose_refine_cases as prc
     from linemod_pose_estimation_amd import MATCH_DTYPE, POSE_REFINE_DTYPE, DepthTemplates, meshsynth as ms
-    if args.out is None:
+    if args.out is None and not args.plane:
         args.out = os.path.join(ROOT, "profiles", "pose_refine_staged.txt" if args.schedule else "pose_refine.txt")
 
     F = ms.ENSENSO["fx"]
@@ -120,6 +126,64 @@ def main():
             vals = [kernel_ms(t, call, args.repeats) for _ in range(args.rounds)]
             print("%3d jobs: k_pose_refine without a schedule %s" % (n, fmt(vals)), flush=True)
         t.close()
+        return
+
+    if args.plane:
+        import pose_refine_plane_cases as ppc
+        import pose_refine_staged_cases as psc
+        shifts = [int(v) for v in args.plane.split(",")]
+        stages = psc.parse_schedule(args.schedule[0]) if args.schedule else None
+        Pp = dict(P, max_iterations=args.plane_iterations)
+        kwp = prc.refine_kwargs(Pp)
+        t.enable_normals(F, F)
+        with tempfile.TemporaryDirectory() as tmp:
+            phost = ppc.build_host(tmp)
+        normals = {}
+        lines.append("point-to-point at %d iterations against point_shift [%s] %s; legs alternate round by round: %d rounds of %d launches per leg, k_pose_refine's device time per launch"
+                     % (P["max_iterations"], args.plane, "under the schedule [%s]" % args.schedule[0] if stages else "at %d iterations" % args.plane_iterations, args.rounds, args.repeats))
+        for n, m, offsets in rows:
+            point_call = lambda: t.refine_poses(m, None, offsets, rects=rects, **kw)
+            plane_call = lambda: t.refine_poses(m, None, offsets, rects=rects, **kwp)
+            t.set_refine_schedule(None)
+            t.set_refine_plane(None)
+            point = point_call()
+            t.set_refine_schedule(stages)
+            t.set_refine_plane(shifts)
+            got = plane_call()
+            for i in list(range(0, n, max(1, n // 16)))[:16]:       # the header on the host is one core: a job of every template
+                f = int(m["template_id"][i])
+                if f not in normals:
+                    normals[f] = ppc.scene_normals(frames[f], fx=F, fy=F)
+                want = ppc.host_refine_plane(phost, Pp, stages, shifts, crops[f], rects[f, :2], frames[f], normals[f], m["x"][i], m["y"][i], POSE_REFINE_DTYPE)[0]
+                assert got[i:i + 1].tobytes() == want.tobytes(), "device and host records differ under the plane setting"
+            legs = {False: [], True: []}
+            for _ in range(args.rounds):
+                for on in (False, True):
+                    t.set_refine_schedule(stages if on else None)
+                    t.set_refine_plane(shifts if on else None)
+                    legs[on].append(kernel_ms(t, plane_call if on else point_call, args.repeats))
+            t.set_refine_schedule(None)
+            t.set_refine_plane(None)
+            lines.append("%3d jobs: point-to-point %s; plane %s: %.2f x" % (n, fmt(legs[False]), fmt(legs[True]), float(np.mean(legs[False]) / np.mean(legs[True]))))
+            lines.append("          statuses %s -> %s, iterations median %d -> %d, median rms_last %.3f -> %.3f mm; the device's records equal the host's refine_job_plane, byte for byte"
+                         % (np.bincount(point["status"], minlength=5).tolist(), np.bincount(got["status"], minlength=5).tolist(), int(np.median(point["iterations"])),
+                            int(np.median(got["iterations"])), float(np.median(point["rms_last_mm"])), float(np.median(got["rms_last_mm"]))))
+        t.close()
+        g = prc.ground_truth_case()
+        lines += ["", "ground-truth case of tests/pose_refine_cases.py, the host header (rotation error / translation error):"]
+        for (x, y) in ppc.ground_truth_placements():
+            out = []
+            G = prc.make_params(prc.GT_CAM, prc.GT_CAM)
+            for name, PP, st, sh in (("point-to-point", G, None, []), ("plane", dict(G, max_iterations=args.plane_iterations), stages, shifts)):
+                rec = ppc.host_refine_plane(phost, PP, st, sh, g["crop"], g["rect"][:2], g["scene"], ppc.ground_truth_normals(), x, y, POSE_REFINE_DTYPE)[0][0]
+                e = prc.pose_errors(*prc.compose(g["R_a"], g["distance"], rec), g["R_b"], g["T_b_m"])
+                out.append("%s: %d iterations, %.4f deg / %.4f mm" % (name, rec["iterations"], e[0], e[1]))
+            lines.append("  match (%d, %d): %s" % (x, y, "; ".join(out)))
+        text = "\n".join(lines) + "\n"
+        print(text)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(text)
         return
 
     vp = C.c_void_p
