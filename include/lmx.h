@@ -949,7 +949,7 @@ lmx_status lmx_debug_depth_walk_grid(lmx_depth_templates* templates, int32_t wor
  * the launches in flight and returns the sum of their times and their number since profiling was switched on.  Off (the default) no
  * event is created or recorded. */
 enum { LMX_DT_K_NORMAL_MAP_FRAMES = 0, LMX_DT_K_VERIFY_DIFF_RECORDS = 1, LMX_DT_K_VERIFY_DIFF = 2, LMX_DT_K_DEPTH_DIFF_RECORDS = 3, LMX_DT_K_WALK_RECORDS_DEV = 4, LMX_DT_K_POSE_REFINE = 5, LMX_DT_K_POSE_VERIFY = 6,
-       LMX_DT_K_POSE_REFINE_CLUSTERS = 7, LMX_DT_K_POSE_VERIFY_CLUSTERS = 8 };
+       LMX_DT_K_POSE_REFINE_CLUSTERS = 7, LMX_DT_K_POSE_VERIFY_CLUSTERS = 8, LMX_DT_K_SCENE_FILTER_SCORE = 9, LMX_DT_K_SCENE_FILTER_APPLY = 10 };
 lmx_status lmx_depth_templates_set_profiling(lmx_depth_templates* templates, int32_t on);
 lmx_status lmx_depth_templates_kernel_time(lmx_depth_templates* templates, int32_t kernel, double* total_ms, int64_t* launches);
 /* Test hook: the normals of frame `frame` of the uploaded scene as the device holds them (computed now if no call has needed them yet). */
@@ -1223,6 +1223,46 @@ lmx_status lmx_debug_rough_pose_chain(lmx_depth_templates* templates, lmx_rough_
  * max_window_h elements), rect = x, y, w, h in the model camera; zeros and nothing written for a slot without a render.  Waits for the
  * device. */
 lmx_status lmx_debug_rough_crop(lmx_rough_model* model, int32_t slot, uint16_t* out, int32_t rect[4]);
+
+/* ---- depth outlier filter of the scene ahead of the pose stages (the reference's statisticalOutlierRemoval) ----------------------------------
+ * The reference cleans every cluster's scene cloud with statisticalOutlierRemoval(scene_pc, 50, 1.0) (src/rgbdDetector.cpp:836) before it
+ * takes the surface centroid, runs ICP and checks the occupancy: the flying pixels a structured-light or stereo sensor leaves on depth
+ * discontinuities would otherwise enter all three.  This is that step as an opt-in property of a lmx_depth_templates object.  While it is
+ * set, lmx_pose_refine_matches, lmx_pose_verify_matches, lmx_pose_chain_on, lmx_rough_pose_chain_on and their debug hooks
+ * (lmx_debug_pose_refine_sums, lmx_debug_pose_refine_plane_sums, lmx_debug_pose_chain, lmx_debug_rough_pose_chain) read a filtered copy of
+ * the scene -- the resident one or the frames staged from `depth` alike -- in which every outlier pixel is 0, "no measurement", which the
+ * stages already skip.  The depth and normal cluster scores and the stored scene normals of the point-to-plane metric keep the raw scene.
+ * An object on which it was never set launches the kernels it launched before, with the same arguments.
+ *   The definition, complete, is the opening comment of csrc/lmx_scene_filter.hpp: for every valid pixel the mean distance to its k nearest
+ * of the (2 radius + 1)^2 window neighbours, over the pixel's own depth; a pixel with fewer than k neighbours within 1024 mm is removed as
+ * sparse; of the others, those whose score exceeds the frame's mean + stddev_mul standard deviations are removed.  Integer sums, a threshold
+ * formed on the device: the filtered copy is made once per scene, on the object's stream, when a pose stage first needs it, with nothing
+ * waited for on the host, and the device equals the CPU build of the header in every byte.  PCL is not part of the reference;
+ * INTEGRATION.md 3k and DESIGN.md section 7 list the deviations (window for kd-tree, frame-wide normalised statistics, convex corners with
+ * fewer than k same-surface neighbours, no voxel grid).
+ *   lmx_scene_filter_defaults fills struct_size, radius 3, k 15, stddev_mul 1.0 and a camera of zeros, which the caller must replace.
+ * lmx_depth_templates_set_scene_filter(t, NULL) turns the filter off.  A new setting (or NULL) takes effect with the next call; the copy is
+ * computed again.  Refused with LMX_ERR_INVALID_ARG, the previous setting left in place: a struct_size that is not
+ * sizeof(lmx_scene_filter_params); radius outside 1..7; k outside 1..(2 radius + 1)^2 - 1; stddev_mul outside [0, 16] or not a number;
+ * fx, fy, cx or cy not finite or not above 0; reserved != 0.  The camera is NOT compared with the scene camera of a later call's
+ * parameters: it is the caller's to pass the same one.  While the filter is set, the calls above refuse frames of more than 2^22 pixels
+ * (the frame's 64-bit sums hold that many scores). */
+typedef struct lmx_scene_filter_params {
+  uint32_t struct_size;
+  int32_t radius, k, reserved;   /* 1..7, 1..(2 radius + 1)^2 - 1, 0 */
+  double stddev_mul;             /* [0, 16] */
+  double fx, fy, cx, cy;         /* the depth frame's camera */
+} lmx_scene_filter_params;
+typedef struct lmx_scene_filter_info {   /* one frame's record, 56 bytes */
+  int64_t n_valid, n_sparse, n_scored, n_removed;   /* n_valid = n_sparse + n_scored; n_removed of the scored pixels exceed the threshold */
+  int64_t sum_q, sum_qq;                            /* over the scored pixels */
+  double threshold;                                 /* 2^20 for a frame with fewer than two scored pixels */
+} lmx_scene_filter_info;
+lmx_status lmx_scene_filter_defaults(lmx_scene_filter_params* out);
+lmx_status lmx_depth_templates_set_scene_filter(lmx_depth_templates* templates, const lmx_scene_filter_params* params);
+/* Test hook: the filtered copy of frame `frame` of the uploaded scene as the device holds it (computed now if no call has needed it yet) and
+ * the frame's record (out_info may be NULL).  LMX_ERR_INVALID_ARG without the setting or without a scene.  Waits for the device. */
+lmx_status lmx_debug_scene_filtered(lmx_depth_templates* templates, int32_t frame, uint16_t* out /*[H][W]*/, lmx_scene_filter_info* out_info);
 
 /* ---- introspection (stage-level parity tests, profiling) ------------------------------------------------- */
 enum {

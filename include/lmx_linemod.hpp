@@ -462,6 +462,20 @@ class DepthTemplates {
     check(lmx_depth_templates_get_refine_plane(h_, out, &n));
     return std::vector<int32_t>(out, out + n);
   }
+  // The scene's depth outlier filter ahead of the pose stages (lmx_depth_templates_set_scene_filter, the reference's
+  // statisticalOutlierRemoval): sceneFilterDefaults() with the depth frames' camera filled in, or nullptr to turn it off.  struct_size is
+  // filled in here.
+  static lmx_scene_filter_params sceneFilterDefaults() {
+    lmx_scene_filter_params p;
+    check(lmx_scene_filter_defaults(&p));
+    return p;
+  }
+  void setSceneFilter(const lmx_scene_filter_params* params) {
+    if (!params) { check(lmx_depth_templates_set_scene_filter(h_, nullptr)); return; }
+    lmx_scene_filter_params p = *params;
+    p.struct_size = (uint32_t)sizeof(lmx_scene_filter_params);
+    check(lmx_depth_templates_set_scene_filter(h_, &p));
+  }
   // The object's pose in the scene camera from the matched template's view and its refinePoses record (lmx_pose_compose).
   static void composePose(const lmx_mesh_view& view, const lmx_pose_refine_t& refined, double R_obj[9], double t_obj_m[3]) {
     check(lmx_pose_compose(&view, &refined, R_obj, t_obj_m));

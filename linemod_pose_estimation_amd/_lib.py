@@ -41,6 +41,7 @@ SYMBOLS = [
     "lmx_pose_chain_on", "lmx_debug_pose_chain",
     "lmx_rough_model_create", "lmx_rough_model_free", "lmx_rough_model_device_bytes", "lmx_rough_trace_min", "lmx_rough_pose_chain_on",
     "lmx_debug_rough_pose_chain", "lmx_debug_rough_crop",
+    "lmx_scene_filter_defaults", "lmx_depth_templates_set_scene_filter", "lmx_debug_scene_filtered",
 ]
 
 (LMX_OK, LMX_ERR_INVALID_ARG, LMX_ERR_SHAPE, LMX_ERR_NO_DEVICE, LMX_ERR_HIP, LMX_ERR_OVERFLOW, LMX_ERR_IO,
@@ -185,6 +186,16 @@ class RoughChainDesc(C.Structure):   # lmx_rough_chain_desc
                 ("clusters", C.c_void_p), ("cap_clusters", C.c_size_t), ("members", C.c_void_p), ("cap_members", C.c_size_t),
                 ("chain_header", C.c_void_p), ("rough", C.c_void_p), ("member_group", C.c_void_p), ("poses", C.c_void_p), ("checks", C.c_void_p),
                 ("keep", C.c_void_p)]
+
+
+class SceneFilterParams(C.Structure):   # lmx_scene_filter_params
+    _fields_ = [("struct_size", C.c_uint32), ("radius", C.c_int32), ("k", C.c_int32), ("reserved", C.c_int32), ("stddev_mul", C.c_double),
+                ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double)]
+
+
+class SceneFilterInfo(C.Structure):   # lmx_scene_filter_info
+    _fields_ = [("n_valid", C.c_int64), ("n_sparse", C.c_int64), ("n_scored", C.c_int64), ("n_removed", C.c_int64), ("sum_q", C.c_int64),
+                ("sum_qq", C.c_int64), ("threshold", C.c_double)]
 
 
 class GroupDesc(C.Structure):
@@ -386,6 +397,9 @@ def lib():
     L.lmx_rough_pose_chain_on.argtypes = [vp, vp, C.POINTER(RoughChainDesc), vp]
     L.lmx_debug_rough_pose_chain.argtypes = [vp, vp, C.POINTER(RoughChainDesc)]
     L.lmx_debug_rough_crop.argtypes = [vp, C.c_int32, vp, vp]
+    L.lmx_scene_filter_defaults.argtypes = [C.POINTER(SceneFilterParams)]
+    L.lmx_depth_templates_set_scene_filter.argtypes = [vp, C.POINTER(SceneFilterParams)]
+    L.lmx_debug_scene_filtered.argtypes = [vp, C.c_int32, vp, C.POINTER(SceneFilterInfo)]
     L.lmx_debug_pose_refine_sums.argtypes = [vp, C.POINTER(Image), vp, C.POINTER(PoseRefineParams), vp, vp]
     L.lmx_depth_templates_set_refine_schedule.argtypes = [vp, C.POINTER(PoseRefineStage), C.c_int32]
     L.lmx_depth_templates_get_refine_schedule.argtypes = [vp, C.POINTER(PoseRefineStage), C.POINTER(C.c_int32)]

@@ -39,6 +39,9 @@
 //                  bodies of the two kernels above; see the kernels
 // The same two bodies behind the rough pose stage (lmx_rough_pose_chain_on; the stage itself: lmx_rough.hip, lmx_rough_pose.hpp):
 //   k_rough_refine_clusters / k_rough_verify_clusters   one workgroup per cluster slot on the job and the rendered crop the stage left
+// The scene filter (lmx_depth_templates_set_scene_filter; arithmetic: lmx_scene_filter.hpp, kernels: lmx_scene_filter.hip), only for an object
+// that set it: a filtered copy of the scene next to d_scene, made once per scene on the object's stream when a pose stage first needs it
+// (pose_scene_on); the five pose launch sites pass it where they pass d_scene otherwise.
 // The host half has one launch site for every walk kernel (depth_launch_walk), one body for both match-list paths
 // (diff_selected), one guard in front of every normal-scored call (need_normals) and one body around the launch of both pose stages
 // (pose_call).
@@ -58,6 +61,7 @@
 #include "lmx_mesh_raster.hpp"
 #include "lmx_export_pack.hpp"
 #include "lmx_rough.hpp"
+#include "lmx_scene_filter.hpp"
 
 namespace lmx {
 struct DepthJob { int32_t x, y, template_id, frame; };   // frame: index among the frames uploaded for this call
@@ -863,6 +867,16 @@ struct lmx_depth_templates {
   hipEvent_t normals_ready = nullptr;    // recorded behind the kernel that computed them (it may run on a caller's stream)
   lmx_normal_diff_t *d_nout = nullptr, *h_nout = nullptr;   // as d_out / h_out
   size_t nout_cap = 0;
+  // the scene filter (lmx_depth_templates_set_scene_filter; lmx_scene_filter.hpp): nothing below is allocated, and no kernel of it launched,
+  // before that call.  While filter_on, the pose stages read d_scene_filtered where they read d_scene otherwise (pose_scene_on)
+  bool filter_on = false;
+  lmx::sf::Params fparams = {{0.0, 0.0, 0.0, 0.0}, 0.0, 0, 0};
+  uint16_t* d_scene_filtered = nullptr;     // [frames][H][W] next to d_scene, computed when first needed
+  uint32_t* d_scene_score = nullptr;        // [frames][H][W]: the score map between the two kernels
+  lmx::sf::Info* d_filter_info = nullptr;   // [frames]
+  size_t scene_filtered_cap = 0, filter_info_cap = 0;   // pixels, frames
+  bool scene_filtered_valid = false;        // they belong to the frames now in d_scene and to fparams
+  hipEvent_t filtered_ready = nullptr;      // recorded behind the kernels that computed them
   // lmx_ctx_export_clusters_on: its walk reads the table, the crops, the scene and the normals on a context's export stream and nobody
   // waits for it on the host.  export_read is recorded behind each such walk (an export's stream waits for the previous record first, so
   // the last record stands behind all of them); whoever changes what the walk reads waits for it: wait_export_reads() on the host,
@@ -878,7 +892,7 @@ struct lmx_depth_templates {
   int32_t walk_grid = 0;                 // workgroups of k_walk_records_dev; 0: not asked for yet (kWalkGridPerCU per compute unit)
   // lmx_depth_templates_set_profiling: a pair of events around each launch of the kernels below, read out by ..._kernel_time
   enum { PK_NORMAL_MAP_FRAMES, PK_VERIFY_DIFF_RECORDS, PK_VERIFY_DIFF, PK_DEPTH_DIFF_RECORDS, PK_WALK_RECORDS_DEV, PK_POSE_REFINE, PK_POSE_VERIFY, PK_POSE_REFINE_CLUSTERS,
-         PK_POSE_VERIFY_CLUSTERS, PK_COUNT };
+         PK_POSE_VERIFY_CLUSTERS, PK_SCENE_FILTER_SCORE, PK_SCENE_FILTER_APPLY, PK_COUNT };
   struct ProfEvent { int kernel; hipEvent_t start, stop; };
   bool profiling = false;
   std::vector<ProfEvent> prof_pending;
@@ -1011,6 +1025,51 @@ struct lmx_depth_templates {
     if (!normals_ready) HIP_RETURN(hipEventCreateWithFlags(&normals_ready, hipEventDisableTiming));
     return scene_normals_on(on, nullptr, n_frames, W, H);
   }
+  // The filtered copies of the first n_frames W x H frames of d_scene under fparams, on stream `on` (which carries the frames' copies or
+  // already waits for them); every later user waits for filtered_ready.  Nothing here waits on the host but a reallocation.
+  lmx_status compute_scene_filtered(hipStream_t on, int32_t n_frames, int32_t W, int32_t H) {
+    const size_t px = (size_t)W * H * (size_t)n_frames;
+    if (px > scene_filtered_cap || (size_t)n_frames > filter_info_cap) {   // as the normals: every reader ended synchronised, but for a chain's kernels
+      if (lmx_status st = wait_export_reads()) return st;
+      (void)hipFree(d_scene_filtered); (void)hipFree(d_scene_score); (void)hipFree(d_filter_info);
+      d_scene_filtered = nullptr; d_scene_score = nullptr; d_filter_info = nullptr;
+      scene_filtered_cap = filter_info_cap = 0;
+      HIP_RETURN(hipMalloc(&d_scene_filtered, px * sizeof(uint16_t)));
+      HIP_RETURN(hipMalloc(&d_scene_score, px * sizeof(uint32_t)));
+      HIP_RETURN(hipMalloc(&d_filter_info, (size_t)n_frames * sizeof(lmx::sf::Info)));
+      scene_filtered_cap = px; filter_info_cap = (size_t)n_frames;
+    }
+    HIP_RETURN(hipMemsetAsync(d_filter_info, 0, (size_t)n_frames * sizeof(lmx::sf::Info), on));
+    int pe = prof_begin(PK_SCENE_FILTER_SCORE, on);
+    lmx::launch_scene_filter_score(on, d_scene, n_frames, W, H, fparams, d_scene_score, d_filter_info);
+    prof_end(pe, on);
+    HIP_RETURN(hipGetLastError());
+    pe = prof_begin(PK_SCENE_FILTER_APPLY, on);
+    lmx::launch_scene_filter_apply(on, d_scene, d_scene_score, n_frames, W, H, fparams.stddev_mul, d_scene_filtered, d_filter_info);
+    prof_end(pe, on);
+    HIP_RETURN(hipGetLastError());
+    HIP_RETURN(hipEventRecord(filtered_ready, on));
+    return LMX_OK;
+  }
+  // The scene a pose stage on stream `on` reads, behind the copies of the n_frames W x H frames in d_scene: d_scene itself, or with the filter
+  // set their filtered copies, computed there if nobody has.  Without the setting this touches nothing.
+  lmx_status pose_scene_on(hipStream_t on, int32_t n_frames, int32_t W, int32_t H, const uint16_t** scene) {
+    *scene = d_scene;
+    if (!filter_on) return LMX_OK;
+    if ((int64_t)W * H > lmx::sf::kMaxFramePixels) {
+      lmx::set_error("frames of %d x %d: the scene filter takes at most 2^22 pixels a frame (lmx_depth_templates_set_scene_filter(NULL) turns it off)", W, H);
+      return LMX_ERR_INVALID_ARG;
+    }
+    if (!filtered_ready) HIP_RETURN(hipEventCreateWithFlags(&filtered_ready, hipEventDisableTiming));
+    if (scene_filtered_valid) {
+      HIP_RETURN(hipStreamWaitEvent(on, filtered_ready, 0));
+    } else {
+      if (lmx_status st = compute_scene_filtered(on, n_frames, W, H)) return st;
+      scene_filtered_valid = true;
+    }
+    *scene = d_scene_filtered;
+    return LMX_OK;
+  }
   void free_normal_crops() {
     (void)hipFree(d_ncrops); (void)hipFree(d_ntable);
     d_ncrops = nullptr; d_ntable = nullptr;
@@ -1035,6 +1094,8 @@ struct lmx_depth_templates {
     free_normal_crops();
     (void)hipFree(d_angle); (void)hipFree(d_scene_normals); (void)hipFree(d_nout); (void)hipHostFree(h_nout);
     if (normals_ready) (void)hipEventDestroy(normals_ready);
+    (void)hipFree(d_scene_filtered); (void)hipFree(d_scene_score); (void)hipFree(d_filter_info);
+    if (filtered_ready) (void)hipEventDestroy(filtered_ready);
     if (scene_ready) (void)hipEventDestroy(scene_ready);
     if (scene_src_ready) (void)hipEventDestroy(scene_src_ready);
     if (s) (void)hipStreamDestroy(s);
@@ -1235,7 +1296,7 @@ extern "C" lmx_status lmx_depth_templates_append(lmx_depth_templates* dst, lmx_d
       t->ncrops_ready = false;
     }
     dst->scene_frames = 0;                                                     // the scene is forgotten: upload_scene comes before the next scored call
-    dst->scene_normals_valid = false;
+    dst->scene_normals_valid = dst->scene_filtered_valid = false;
     return LMX_OK;
   });
 }
@@ -1392,7 +1453,7 @@ extern "C" lmx_status lmx_depth_templates_upload_scene_device(lmx_depth_template
     const int32_t W = depth[0].cols, H = depth[0].rows;
     const size_t frame_bytes = (size_t)W * H * sizeof(uint16_t);
     t->scene_frames = 0;
-    t->scene_normals_valid = false;
+    t->scene_normals_valid = t->scene_filtered_valid = false;
     if (lmx_status st = t->grow_scene(frame_bytes * (size_t)n_frames)) return st;
     if (!t->scene_src_ready) HIP_RETURN(hipEventCreateWithFlags(&t->scene_src_ready, hipEventDisableTiming));
     HIP_RETURN(hipEventRecord(t->scene_src_ready, user));
@@ -1432,7 +1493,7 @@ lmx_status depth_upload_scene(lmx_depth_templates* t, const lmx_image* depth, in
   if (lmx_status st = t->wait_scene_copies()) return st;   // the previous scene's copies still read the staging buffer
   if (lmx_status st = t->wait_export_reads()) return st;   // an export's walk may still read the scene these copies overwrite
   t->scene_frames = 0;
-  t->scene_normals_valid = false;
+  t->scene_normals_valid = t->scene_filtered_valid = false;
   if (lmx_status st = t->grow_scene((size_t)W * H * sizeof(uint16_t) * (size_t)n_frames)) return st;
   for (int32_t f = 0; f < n_frames; ++f)   // each frame on its way while the next is staged
     if (lmx_status st = queue_frame(t, depth[f], f, W, H)) { t->drain_after_error(); return st; }
@@ -1593,14 +1654,14 @@ lmx_status diff_matches_impl(const char* what, lmx_depth_templates* t, const lmx
     if (lmx_status st = t->wait_scene_copies()) return st;
     if (lmx_status st = t->wait_export_reads()) return st;   // an export's walk may still read the scene the staged frames replace
     t->scene_frames = 0;
-    t->scene_normals_valid = false;
+    t->scene_normals_valid = t->scene_filtered_valid = false;
     if (lmx_status st = t->grow_scene(frame_bytes * n_slots)) return st;
     for (int32_t f = 0; f < n_frames; ++f)
       if (t->slot[f] >= 0)
         if (lmx_status st = queue_frame(t, depth[f], t->slot[f], W, H)) { t->drain_after_error(); return st; }
     const lmx_status st = diff_selected(t, matches, t->sel_slot.data(), 0, n_slots, W, H, out, normals ? nout : nullptr);
     if (st != LMX_OK) t->drain_after_error();
-    t->scene_normals_valid = false;   // they belong to staged frames that are no scene
+    t->scene_normals_valid = t->scene_filtered_valid = false;   // they belong to staged frames that are no scene
     return st;
 }
 }  // namespace
@@ -1650,7 +1711,7 @@ extern "C" lmx_status lmx_depth_templates_enable_normals(lmx_depth_templates* t,
     t->nparams = np;
     t->normals_on = true;
     t->ncrops_ready = false;
-    t->scene_normals_valid = false;
+    t->scene_normals_valid = t->scene_filtered_valid = false;
     if (t->atlas_bytes == 0) return LMX_OK;   // no pixel to take a normal of: nothing needs the device yet
     if (lmx_status st = compute_crop_normals(t)) { t->normals_on = false; return st; }
     return LMX_OK;
@@ -1705,6 +1766,55 @@ extern "C" lmx_status lmx_debug_scene_normals(lmx_depth_templates* t, int32_t fr
     if (lmx_status st = t->scene_normals_on(t->s, nullptr, t->scene_frames, t->scene_W, t->scene_H)) return st;
     const size_t px = (size_t)t->scene_W * t->scene_H;
     HIP_RETURN(hipMemcpyAsync(out, t->d_scene_normals + px * frame, px * sizeof(lmx::nv::Packed), hipMemcpyDeviceToHost, t->s));
+    HIP_RETURN(hipStreamSynchronize(t->s));
+    return LMX_OK;
+  });
+}
+
+// ---- the scene filter: the host half (the kernels: lmx_scene_filter.hip) ------------------------------------------------------------------------------
+static_assert(sizeof(lmx_scene_filter_info) == sizeof(lmx::sf::Info) && sizeof(lmx_scene_filter_info) == 56 && sizeof(lmx_scene_filter_params) == 56, "layouts of the scene filter");
+
+extern "C" lmx_status lmx_scene_filter_defaults(lmx_scene_filter_params* out) {
+  if (!out) { lmx::set_error("lmx_scene_filter_defaults: null argument"); return LMX_ERR_INVALID_ARG; }
+  *out = lmx_scene_filter_params{(uint32_t)sizeof(lmx_scene_filter_params), 3, 15, 0, 1.0, 0.0, 0.0, 0.0, 0.0};
+  return LMX_OK;
+}
+
+extern "C" lmx_status lmx_depth_templates_set_scene_filter(lmx_depth_templates* t, const lmx_scene_filter_params* p) {
+  return lmx::guarded("lmx_depth_templates_set_scene_filter", [&]() -> lmx_status {
+    using namespace lmx;
+    const char* what = "lmx_depth_templates_set_scene_filter";
+    if (!t) { set_error("%s: null argument", what); return LMX_ERR_INVALID_ARG; }
+    sf::Params P = {{0.0, 0.0, 0.0, 0.0}, 0.0, 0, 0};
+    if (p) {
+      if (p->struct_size != sizeof(lmx_scene_filter_params)) { set_error("%s: params->struct_size = %u (expected %zu)", what, p->struct_size, sizeof(lmx_scene_filter_params)); return LMX_ERR_INVALID_ARG; }
+      if (p->reserved != 0) { set_error("%s: reserved = %d (must be 0)", what, p->reserved); return LMX_ERR_INVALID_ARG; }
+      P = sf::Params{{p->fx, p->fy, p->cx, p->cy}, p->stddev_mul, p->radius, p->k};
+      if (const char* why = sf::check_params(P)) { set_error("%s: %s (radius %d, k %d, stddev_mul %g, camera %g %g %g %g)", what, why, p->radius, p->k, p->stddev_mul, p->fx, p->fy, p->cx, p->cy); return LMX_ERR_INVALID_ARG; }
+    }
+    std::lock_guard<std::mutex> lk(t->m);
+    t->fparams = P;   // queued work reads the copy made under the old setting; the next call makes its own, behind it on the object's stream
+    t->filter_on = p != nullptr;
+    t->scene_filtered_valid = false;
+    return LMX_OK;
+  });
+}
+
+extern "C" lmx_status lmx_debug_scene_filtered(lmx_depth_templates* t, int32_t frame, uint16_t* out, lmx_scene_filter_info* out_info) {
+  return lmx::guarded("lmx_debug_scene_filtered", [&]() -> lmx_status {
+    const char* what = "lmx_debug_scene_filtered";
+    if (!t || !out) { lmx::set_error("%s: null argument", what); return LMX_ERR_INVALID_ARG; }
+    std::lock_guard<std::mutex> lk(t->m);
+    if (!t->filter_on) { lmx::set_error("%s: call lmx_depth_templates_set_scene_filter first", what); return LMX_ERR_INVALID_ARG; }
+    if (t->scene_frames < 1) { lmx::set_error("%s: no scene uploaded: call lmx_depth_templates_upload_scene first", what); return LMX_ERR_INVALID_ARG; }
+    if (frame < 0 || frame >= t->scene_frames) { lmx::set_error("%s: frame %d is not in the uploaded scene (%d frames)", what, frame, t->scene_frames); return LMX_ERR_INVALID_ARG; }
+    if (lmx_status st = t->ensure_device()) return st;
+    HIP_RETURN(hipStreamWaitEvent(t->s, t->scene_ready, 0));
+    const uint16_t* scene = nullptr;
+    if (lmx_status st = t->pose_scene_on(t->s, t->scene_frames, t->scene_W, t->scene_H, &scene)) return st;
+    const size_t px = (size_t)t->scene_W * t->scene_H;
+    HIP_RETURN(hipMemcpyAsync(out, scene + px * frame, px * sizeof(uint16_t), hipMemcpyDeviceToHost, t->s));
+    if (out_info) HIP_RETURN(hipMemcpyAsync(out_info, t->d_filter_info + frame, sizeof(lmx_scene_filter_info), hipMemcpyDeviceToHost, t->s));
     HIP_RETURN(hipStreamSynchronize(t->s));
     return LMX_OK;
   });
@@ -1838,6 +1948,7 @@ lmx_status pose_call(const PoseCall& a, const std::function<int(size_t, const lm
   const int32_t W = depth ? depth[0].cols : t->scene_W, H = depth ? depth[0].rows : t->scene_H;
   if (W >= pr::kMaxCoord / 2 || H >= pr::kMaxCoord / 2) { set_error("%s: frames of %d x %d (sides below %d)", what, W, H, (int)(pr::kMaxCoord / 2)); return LMX_ERR_INVALID_ARG; }
   if (a.max_pixels > 0 && (int64_t)W * H > a.max_pixels) { set_error("%s: frames of %d x %d (at most %lld pixels)", what, W, H, (long long)a.max_pixels); return LMX_ERR_INVALID_ARG; }
+  if (t->filter_on && (int64_t)W * H > sf::kMaxFramePixels) { set_error("%s: frames of %d x %d (at most 2^22 pixels while the scene filter is set)", what, W, H); return LMX_ERR_INVALID_ARG; }
   const size_t n_matches = offsets[n_frames];
   if (n_matches == 0) return LMX_OK;
   if (!a.matches || !a.out || a.input_missing) { set_error("%s: null argument", what); return LMX_ERR_INVALID_ARG; }
@@ -1875,7 +1986,7 @@ lmx_status pose_call(const PoseCall& a, const std::function<int(size_t, const lm
     if (lmx_status st = t->wait_scene_copies()) return st;
     if (lmx_status st = t->wait_export_reads()) return st;   // an export's walk may still read the scene the staged frames replace
     t->scene_frames = 0;
-    t->scene_normals_valid = false;
+    t->scene_normals_valid = t->scene_filtered_valid = false;
     if (lmx_status st = t->grow_scene(frame_bytes * n_slots)) return st;
     for (int32_t f = 0; f < n_frames; ++f)
       if (t->slot[f] >= 0)
@@ -1885,6 +1996,7 @@ lmx_status pose_call(const PoseCall& a, const std::function<int(size_t, const lm
   }
   const lmx_status st = launch(W, H, n_slots, count, rects);
   if (st != LMX_OK) t->drain_after_error();
+  if (depth) t->scene_filtered_valid = false;   // it belongs to staged frames that are no scene
   return st;
 }
 
@@ -1924,6 +2036,8 @@ lmx_status pose_refine_impl(const char* what, lmx_depth_templates* t, const lmx_
         const size_t rows = (size_t)pr::schedule_passes(S), row = plane ? pr::kAllSums : pr::kSums;   // the PLANE kernel's rows hold all 46
         const size_t dbg_bytes = rows * row * sizeof(int64_t);
         std::vector<int64_t> h_dbg;
+        const uint16_t* scene = nullptr;   // the frames in d_scene, or with the scene filter set their filtered copies
+        if (lmx_status g = t->pose_scene_on(s, n_slots, W, H, &scene)) return g;
         if (plane)
           if (lmx_status g = t->plane_normals_on(s, n_slots, W, H)) return g;
         if (dbg) {
@@ -1933,10 +2047,10 @@ lmx_status pose_refine_impl(const char* what, lmx_depth_templates* t, const lmx_
         HIP_RETURN(hipMemcpyAsync(t->d_pjobs, t->h_pjobs, n * sizeof(PoseJob), hipMemcpyHostToDevice, s));
         const int pe = t->prof_begin(lmx_depth_templates::PK_POSE_REFINE, s);
         if (plane)
-          hipLaunchKernelGGL(k_pose_refine<true>, dim3((unsigned)n), dim3(256), 0, s, t->d_table, (int32_t)count, t->d_pjobs, t->d_scene, n_slots, W, H, P, S, t->d_pout,
+          hipLaunchKernelGGL(k_pose_refine<true>, dim3((unsigned)n), dim3(256), 0, s, t->d_table, (int32_t)count, t->d_pjobs, scene, n_slots, W, H, P, S, t->d_pout,
                              d_dbg.as<long long>(), t->d_scene_normals, K);
         else
-          hipLaunchKernelGGL(k_pose_refine<false>, dim3((unsigned)n), dim3(256), 0, s, t->d_table, (int32_t)count, t->d_pjobs, t->d_scene, n_slots, W, H, P, S, t->d_pout,
+          hipLaunchKernelGGL(k_pose_refine<false>, dim3((unsigned)n), dim3(256), 0, s, t->d_table, (int32_t)count, t->d_pjobs, scene, n_slots, W, H, P, S, t->d_pout,
                              d_dbg.as<long long>(), nullptr, K);
         t->prof_end(pe, s);
         HIP_RETURN(hipGetLastError());
@@ -2104,9 +2218,11 @@ extern "C" lmx_status lmx_pose_verify_matches(lmx_depth_templates* t, const lmx_
             std::memcpy(j.R, p.R, sizeof(j.R));
             std::memcpy(j.t_mm, p.t_mm, sizeof(j.t_mm));
           }
+          const uint16_t* scene = nullptr;
+          if (lmx_status g = t->pose_scene_on(s, n_slots, W, H, &scene)) return g;
           HIP_RETURN(hipMemcpyAsync(t->d_vjobs, t->h_vjobs, n * sizeof(VerifyJob), hipMemcpyHostToDevice, s));
           const int pe = t->prof_begin(lmx_depth_templates::PK_POSE_VERIFY, s);
-          hipLaunchKernelGGL(k_pose_verify, dim3((unsigned)n), dim3(256), 0, s, t->d_table, (int32_t)count, t->d_vjobs, t->d_scene, n_slots, W, H, P, t->d_vout);
+          hipLaunchKernelGGL(k_pose_verify, dim3((unsigned)n), dim3(256), 0, s, t->d_table, (int32_t)count, t->d_vjobs, scene, n_slots, W, H, P, t->d_vout);
           t->prof_end(pe, s);
           HIP_RETURN(hipGetLastError());
           HIP_RETURN(hipMemcpyAsync(t->h_vout, t->d_vout, n * sizeof(lmx_pose_verify_t), hipMemcpyDeviceToHost, s));
@@ -2203,6 +2319,7 @@ lmx_status chain_check_fields(const char* what, lmx_depth_templates* t, const Ch
   const int32_t W = t->scene_W, H = t->scene_H;
   if (W >= pr::kMaxCoord / 2 || H >= pr::kMaxCoord / 2) { set_error("%s: frames of %d x %d (sides below %d)", what, W, H, (int)(pr::kMaxCoord / 2)); return LMX_ERR_INVALID_ARG; }
   if ((int64_t)W * H > (int64_t)INT32_MAX) { set_error("%s: frames of %d x %d (at most %d pixels)", what, W, H, INT32_MAX); return LMX_ERR_INVALID_ARG; }
+  if (t->filter_on && (int64_t)W * H > sf::kMaxFramePixels) { set_error("%s: frames of %d x %d (at most 2^22 pixels while the scene filter is set)", what, W, H); return LMX_ERR_INVALID_ARG; }
   return LMX_OK;
 }
 
@@ -2262,7 +2379,8 @@ lmx_status chain_queue(lmx_depth_templates* t, const lmx_pose_chain_desc& d, con
   ChainArgs a;
   a.L = chain_lists(d);
   a.T =pc::Table{(int32_t)count, t->chain_rects_refine.dev, d.class_base ? -1 : d.class_index, d.class_base ? t->chain_base.dev : nullptr, d.class_base ? d.n_classes : 0};
-  a.crops = t->d_table; a.scene = t->d_scene; a.W = t->scene_W; a.H = t->scene_H;
+  a.crops = t->d_table; a.W = t->scene_W; a.H = t->scene_H;
+  if (lmx_status st = t->pose_scene_on(s, t->scene_frames, t->scene_W, t->scene_H, &a.scene)) return st;   // an event wait or two launches, nothing on the host
   a.chain_header = d.chain_header; a.leaders = d.leaders; a.poses = d.poses; a.checks = d.checks; a.keep = d.keep; a.keep_thresh = d.keep_thresh;
   const dim3 grid((unsigned)d.cap_clusters), block(256);
   HIP_RETURN(hipMemsetAsync(d.chain_header, 0, pc::C_WORDS * sizeof(uint32_t), s));
@@ -2404,7 +2522,9 @@ lmx_status rough_queue(lmx_depth_templates* t, lmx_rough_model* model, const lmx
   HIP_RETURN(hipMemsetAsync(d.chain_header, 0, pc::C_WORDS * sizeof(uint32_t), s));
   launch_rough_stage(s, model, a);
   HIP_RETURN(hipGetLastError());
-  const RoughChainArgs c = {d.header, (uint64_t)d.cap_clusters, model->d_jobs, reinterpret_cast<const DepthCrop*>(model->d_crops), model->cap_slots, t->d_scene,
+  const uint16_t* scene = nullptr;
+  if (lmx_status st = t->pose_scene_on(s, t->scene_frames, t->scene_W, t->scene_H, &scene)) return st;
+  const RoughChainArgs c = {d.header, (uint64_t)d.cap_clusters, model->d_jobs, reinterpret_cast<const DepthCrop*>(model->d_crops), model->cap_slots, scene,
                             d.n_frames, t->scene_W, t->scene_H, d.chain_header, d.poses, d.checks, d.keep, d.keep_thresh};
   const dim3 grid((unsigned)d.cap_clusters), block(256);
   const pr::Schedule S = t->schedule_for(PR);

@@ -1798,7 +1798,7 @@ class DepthTemplates:
     # and "k_depth_diff_records" are the record walk with both terms, the job walk with both terms and the depth-only record walk (all
     # instantiations of k_walk, csrc/lmx_verify.hip); the depth-only job walk has no bracket.
     KERNELS = ("k_normal_map_frames", "k_verify_diff_records", "k_verify_diff", "k_depth_diff_records", "k_walk_records_dev", "k_pose_refine", "k_pose_verify",
-               "k_pose_refine_clusters", "k_pose_verify_clusters")
+               "k_pose_refine_clusters", "k_pose_verify_clusters", "k_scene_filter_score", "k_scene_filter_apply")
 
     def set_profiling(self, on=True):
         """Time the object's per-call kernels with device events (lmx_depth_templates_set_profiling); switching it on clears the sums."""
@@ -1820,6 +1820,38 @@ class DepthTemplates:
         out = np.zeros(self._scene_shape + (4,), np.int16)
         _lib.check(_lib.lib().lmx_debug_scene_normals(self.h, int(frame), out.ctypes.data))
         return out
+
+    SCENE_FILTER_INFO_FIELDS = ("n_valid", "n_sparse", "n_scored", "n_removed", "sum_q", "sum_qq", "threshold")
+
+    def set_scene_filter(self, radius=3, k=15, stddev_mul=1.0, camera=None):
+        """The depth outlier filter of the scene ahead of the pose stages (lmx_depth_templates_set_scene_filter; the reference's
+        statisticalOutlierRemoval).  While it is set, refine_poses, verify_poses, pose_chain, rough_pose_chain and their debug hooks read
+        a copy of the scene -- uploaded or passed as depth_frames -- in which every outlier pixel is 0; the cluster scores keep the raw
+        scene.  camera: (fx, fy, cx, cy) of the depth frames; it is not compared with a later call's scene_camera.  radius 1..7: the
+        window; k: how many nearest window neighbours a pixel's score averages (fewer within 1024 mm: the pixel goes); stddev_mul in
+        [0, 16]: pixels scoring above the frame's mean + stddev_mul standard deviations go.  set_scene_filter(None) turns it off."""
+        if radius is None:
+            if (k, stddev_mul, camera) != (15, 1.0, None):
+                raise ValueError("set_scene_filter(None) turns the filter off and takes no other argument")
+            _lib.check(_lib.lib().lmx_depth_templates_set_scene_filter(self.h, None))
+            return
+        if camera is None:
+            raise ValueError("camera is (fx, fy, cx, cy) of the depth frames")
+        p = _lib.SceneFilterParams()
+        _lib.check(_lib.lib().lmx_scene_filter_defaults(C.byref(p)))
+        p.radius, p.k, p.stddev_mul = int(radius), int(k), float(stddev_mul)
+        p.fx, p.fy, p.cx, p.cy = [float(v) for v in camera]
+        _lib.check(_lib.lib().lmx_depth_templates_set_scene_filter(self.h, C.byref(p)))
+
+    def debug_scene_filtered(self, frame):
+        """Test hook (lmx_debug_scene_filtered): the filtered copy of frame `frame` of the uploaded scene -> (uint16 [H, W], the frame's
+        record as a dict with the keys SCENE_FILTER_INFO_FIELDS)."""
+        if getattr(self, "_scene_shape", None) is None:
+            raise ValueError("no scene uploaded through this object")
+        out = np.zeros(self._scene_shape, np.uint16)
+        info = _lib.SceneFilterInfo()
+        _lib.check(_lib.lib().lmx_debug_scene_filtered(self.h, int(frame), out.ctypes.data, C.byref(info)))
+        return out, {k: getattr(info, k) for k in self.SCENE_FILTER_INFO_FIELDS}
 
     def debug_walk_records(self, records, header_count, n_candidates, cap, grid_workgroups, class_index=-1, class_base=None, normals=False,
                            fill=None):

@@ -47,6 +47,7 @@ def main():
     ap.add_argument("--max-candidates", type=int, default=1 << 19)
     ap.add_argument("--schedule", default=None, help="stride:iterations:max_dist:radius,...: the refinement schedule every leg runs under")
     ap.add_argument("--plane", default=None, help="point_shift per stage, comma-separated: -1 point-to-point, 0..20 point-to-plane")
+    ap.add_argument("--scene-filter", action="store_true", help="the pose stages read the filtered scene (DepthTemplates.set_scene_filter, the defaults)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pose_chain.txt"))
     args = ap.parse_args()
     import torch
@@ -65,6 +66,8 @@ def main():
     if args.plane:
         t.enable_normals(F, F)
         t.set_refine_plane([int(v) for v in args.plane.split(",")])
+    if args.scene_filter:
+        t.set_scene_filter(camera=cam)
     distinct = [ms.make_scene(chip, grid, seed=7000 + f, n_instances=3, other_tri=cpu_mesh, n_other=2)[0] for f in range(16)]
     frames = [distinct[f % len(distinct)] for f in range(B)]
     depth = [np.ascontiguousarray(fr[1]) for fr in frames]
@@ -81,6 +84,8 @@ def main():
         lines.append("refinement schedule of every leg: [%s]" % args.schedule)
     if args.plane:
         lines.append("point_shift of every leg's stages: [%s]" % args.plane)
+    if args.scene_filter:
+        lines.append("scene filter set (radius 3, k 15, stddev_mul 1.0): every leg's pose stages read the filtered scene")
 
     for cap in args.cap_clusters:
         state = {"res": None, "poses": None}

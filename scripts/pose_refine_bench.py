@@ -64,6 +64,40 @@ def fmt(vals):
     return "%.3f ms (rounds: %s)" % (float(np.mean(vals)), ", ".join("%.3f" % v for v in vals))
 
 
+def truth_with_flying_pixels(args, prc):
+    """The ground-truth case of tests/pose_refine_cases.py at its three placements, the object in front of a wall with --flying-pixels
+    outline pixels seeded midway, refined by the numpy restatement on the raw scene or (--scene-filter) on the scene the numpy
+    restatement of csrc/lmx_scene_filter.hpp leaves -> lines."""
+    import scene_filter_cases as sfc
+    g = prc.ground_truth_case()
+    obj = g["scene"] != 0
+    scene = np.where(obj, g["scene"], args.wall_mm).astype(np.uint16)
+    near = np.zeros_like(obj)
+    near[1:, :] |= obj[:-1, :]
+    near[:-1, :] |= obj[1:, :]
+    near[:, 1:] |= obj[:, :-1]
+    near[:, :-1] |= obj[:, 1:]
+    outline = np.argwhere(near & ~obj)
+    pick = outline[np.linspace(0, len(outline) - 1, args.flying_pixels).astype(int)] if args.flying_pixels else outline[:0]
+    mid = (int(np.median(g["scene"][obj])) + args.wall_mm) // 2
+    for y, x in pick:
+        scene[y, x] = mid
+    lines = ["ground-truth case, the object in front of a wall at %d mm, %d outline pixels at %d mm, scene filter %s (scripts/pose_refine_bench.py --flying-pixels):"
+             % (args.wall_mm, len(pick), mid, "on (r 3, k 15, 1.0)" if args.scene_filter else "off")]
+    if args.scene_filter:
+        scene, rec, _, _ = sfc.np_filter(scene, prc.GT_CAM)
+        gone = int(sum(scene[y, x] == 0 for y, x in pick))
+        lines.append("  filter: %d valid, %d sparse, %d scored, %d removed (threshold %.1f); %d of the %d seeded pixels removed, %d object pixels removed"
+                     % (rec["n_valid"], rec["n_sparse"], rec["n_scored"], rec["n_removed"], rec["threshold"], gone, len(pick), int((obj & (scene == 0)).sum())))
+    bx, by = g["rect_b"][:2]
+    for (x, y) in ((bx, by), (bx + 1, by), (bx, by + 1)):
+        rec, _ = prc.np_refine(prc.make_params(prc.GT_CAM, prc.GT_CAM), g["crop"], g["rect"][:2], scene, x, y)
+        e = prc.pose_errors(*prc.compose(g["R_a"], g["distance"], rec), g["R_b"], g["T_b_m"])
+        lines.append("  match (%d, %d): status %d, %2d iterations, pairs %d -> %d, rms %.4f -> %.4f mm, rotation error %.4f deg, translation error %.4f mm"
+                     % (x, y, rec["status"], rec["iterations"], rec["n_pairs_first"], rec["n_pairs_last"], rec["rms_first_mm"], rec["rms_last_mm"], e[0], e[1]))
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=20)
@@ -73,6 +107,10 @@ def main():
     ap.add_argument("--plane-iterations", type=int, default=5, help="max_iterations of the plane leg when no --schedule is given")
     ap.add_argument("--plain", action="store_true", help="only the rows without a schedule, one line each")
     ap.add_argument("--package-root", default=ROOT, help="the checkout whose package and library are measured")
+    ap.add_argument("--flying-pixels", type=int, default=0, help="only the ground-truth case, on the CPU: the object in front of a wall, this many pixels on its "
+                    "outline seeded midway between the two")
+    ap.add_argument("--scene-filter", action="store_true", help="with --flying-pixels: the scene goes through the depth outlier filter first (the defaults)")
+    ap.add_argument("--wall-mm", type=int, default=700, help="with --flying-pixels: the depth of the wall behind the object")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     root = os.path.abspath(args.package_root)
@@ -80,6 +118,13 @@ def main():
     sys.path.insert(0, os.path.join(root, "tests"))
     import pose_refine_cases as prc
     from linemod_pose_estimation_amd import MATCH_DTYPE, POSE_REFINE_DTYPE, DepthTemplates, meshsynth as ms
+    if args.flying_pixels or args.scene_filter:
+        text = "\n".join(truth_with_flying_pixels(args, prc)) + "\n"
+        print(text)
+        if args.out:
+            with open(args.out, "a") as f:
+                f.write(text)
+        return
     if args.out is None and not args.plane:
         args.out = os.path.join(ROOT, "profiles", "pose_refine_staged.txt" if args.schedule else "pose_refine.txt")
 

@@ -39,6 +39,7 @@ def main():
     ap.add_argument("--max-candidates", type=int, default=1 << 19)
     ap.add_argument("--kernels", type=int, default=0)
     ap.add_argument("--schedule", default=None, help="stride:iterations:max_dist:radius,...: the refinement schedule every leg runs under")
+    ap.add_argument("--scene-filter", action="store_true", help="the pose stages read the filtered scene (DepthTemplates.set_scene_filter, the defaults)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rough_pose.txt"))
     args = ap.parse_args()
     import torch
@@ -56,6 +57,8 @@ def main():
         import pose_refine_staged_cases as psc
         t.set_refine_schedule(psc.parse_schedule(args.schedule))
     model = RoughModel(chip, views, W, H, F, F, ori_dists=dists, cap_slots=args.cap_clusters, max_window=(args.window, args.window))
+    if args.scene_filter:
+        t.set_scene_filter(camera=cam)
     distinct = [ms.make_scene(chip, grid, seed=7000 + f, n_instances=3, other_tri=cpu_mesh, n_other=2)[0] for f in range(16)]
     frames = [distinct[f % len(distinct)] for f in range(B)]
     depth = [np.ascontiguousarray(fr[1]) for fr in frames]
