@@ -29,6 +29,11 @@ namespace dv {
 
 constexpr int kPitchAlign = 8;      // elements: 16 bytes, one uint4 load
 constexpr int kMaxCropSide = 16384; // so that h * pitch and n_template (<= 2^28) fit an int32
+// How lmx_verify.hip spreads the work (no part of the definition; the tests size their crops by them): the lanes of a wave that share a
+// crop row, each taking the vectors v0, v0 + kWalkLanes, .. of it; the workgroups of 256 lanes that copy one rendered view's crop, a
+// vector per lane and trip.
+constexpr int kWalkLanes = 64;      // one wave
+constexpr int kCropCopyGrid = 16;
 
 struct Sums {
   uint64_t sum_abs_mm;   // <= 2^28 pixels x 65535 < 2^44

@@ -42,6 +42,10 @@ namespace nv {
 constexpr int kTap = 5;                 // the taps of DepthNormal's least squares lie at offsets +-5
 constexpr int kUnit = 16384;            // a unit normal's component scale
 constexpr int kAngleTableSize = 16385;  // half chords 0 .. 16384
+// How lmx_verify.hip spreads the normal maps (no part of the definition; the tests size their images by them): workgroups of 256 lanes,
+// a pixel per lane and trip -- at most kFrameMapGridCap of them per scene frame, kCropMapGrid per crop (h * pitch elements).
+constexpr int kFrameMapGridCap = 4096;
+constexpr int kCropMapGrid = 32;
 
 struct Params {
   float fx, fy;

@@ -23,7 +23,8 @@
 namespace lmx {
 namespace {
 
-constexpr int kTileW = 32, kTileH = 8;
+using sf::kTileW;
+using sf::kTileH;
 constexpr int kMaxLdsW = kTileW + 2 * sf::kMaxRadius, kMaxLdsH = kTileH + 2 * sf::kMaxRadius;
 constexpr int kLdsPoints = kMaxLdsW * kMaxLdsH;
 static_assert(3 * kLdsPoints * sizeof(int32_t) < 12 * 1024, "the tile's points stay under 12 KiB of LDS");
@@ -118,12 +119,12 @@ __global__ __launch_bounds__(256) void k_scene_filter_apply(const uint16_t* __re
 
 void launch_scene_filter_score(hipStream_t s, const uint16_t* scene, int32_t n_frames, int32_t W, int32_t H, const sf::Params& P, uint32_t* score, sf::Info* info) {
   const int tiles = ((W + kTileW - 1) / kTileW) * ((H + kTileH - 1) / kTileH);
-  hipLaunchKernelGGL(k_scene_filter_score, dim3((unsigned)std::min(tiles, 1024), (unsigned)n_frames), dim3(256), 0, s, scene, W, H, P, score, info);
+  hipLaunchKernelGGL(k_scene_filter_score, dim3((unsigned)std::min(tiles, sf::kScoreGridCap), (unsigned)n_frames), dim3(256), 0, s, scene, W, H, P, score, info);
 }
 
 void launch_scene_filter_apply(hipStream_t s, const uint16_t* scene, const uint32_t* score, int32_t n_frames, int32_t W, int32_t H, double stddev_mul, uint16_t* filtered,
                                sf::Info* info) {
-  const unsigned gx = (unsigned)std::min<size_t>(((size_t)W * H + 255) / 256, 1024);
+  const unsigned gx = (unsigned)std::min<size_t>(((size_t)W * H + 255) / 256, (size_t)sf::kApplyGridCap);
   hipLaunchKernelGGL(k_scene_filter_apply, dim3(gx, (unsigned)n_frames), dim3(256), 0, s, scene, score, W, H, stddev_mul, filtered, info);
 }
 

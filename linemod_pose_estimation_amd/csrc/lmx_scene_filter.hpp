@@ -71,6 +71,12 @@ constexpr int64_t kMaxQ = ((int64_t)1 << 20) - 1;
 constexpr double kKeepAll = 1048576.0;                      // the threshold of a frame with fewer than two scored pixels
 constexpr int64_t kMaxFramePixels = (int64_t)1 << 22;
 constexpr uint32_t kInvalid = 0xffffffffu, kSparse = 0xfffffffeu;   // what a score map holds for a pixel without a score
+// How lmx_scene_filter.hip spreads a frame (no part of the definition; the tests size their frames by them): a workgroup of 256 lanes scores
+// tiles of kTileW x kTileH pixels, at most kScoreGridCap workgroups a frame, each taking the tiles blockIdx.x, + gridDim.x, ..; at most
+// kApplyGridCap workgroups a frame apply the threshold, 256 pixels a trip.
+constexpr int kTileW = 32, kTileH = 8;
+constexpr int kScoreGridCap = 1024;
+constexpr int kApplyGridCap = 1024;
 static_assert(16 * pr::kMaxScenePointMm + (double)kMaxDiffTicks < 2147483648.0 && 16 * 65535 < INT32_MAX, "points and their differences fit int32");
 static_assert(3ll * kMaxDiffTicks * kMaxDiffTicks < ((int64_t)1 << 30), "|D|^2 fits 32 bits, and isqrt32's argument stays below 2^30");
 static_assert(kMaxQ * kMaxQ <= INT64_MAX / kMaxFramePixels, "sum q^2 over the largest frame fits int64");

@@ -73,6 +73,7 @@ struct DepthCrop {          // table entry: 24 bytes per template
 };
 static_assert(sizeof(DepthCrop) == 24 && sizeof(DepthJob) == 16 && sizeof(lmx_depth_diff_t) == 16, "layouts the kernels rely on");
 static_assert(sizeof(lmx_normal_diff_t) == 16 && sizeof(nv::Packed) == 8, "layouts the kernels rely on");
+static_assert(dv::kWalkLanes == 64, "the lanes along a crop row are those of one wave (lane = tid & 63, wave_sum)");
 
 constexpr int kCropBatch = 32;   // views rendered per batch (as lmx_mesh_render)
 struct CropBatch { uint64_t dst_elem[kCropBatch]; };   // where view v's crop starts in the batch's chunk, in elements
@@ -168,8 +169,8 @@ __device__ __forceinline__ void diff_walk(const DepthCrop* __restrict__ crops, n
   }
   const uint16_t* frame = scene + (size_t)f * H * W;
   const int vpr = c.pitch / dv::kPitchAlign;        // vectors in a row
-  const int lanes_per_row = vpr < 64 ? vpr : 64;
-  const int rows_per_pass = 64 / lanes_per_row;     // rows a wave takes at once
+  const int lanes_per_row = vpr < dv::kWalkLanes ? vpr : dv::kWalkLanes;
+  const int rows_per_pass = dv::kWalkLanes / lanes_per_row;     // rows a wave takes at once
   const int sub = lane / lanes_per_row, v0 = lane - sub * lanes_per_row;
   dv::Sums a = {0, 0, 0};
   nv::Sums b = {0, 0};
@@ -332,8 +333,8 @@ static_assert(sizeof(pr::Stage) == sizeof(lmx_pose_refine_stage) && offsetof(pr:
 template <typename F>
 __device__ __forceinline__ void crop_pixels(const DepthCrop& c, int lane, int wave, F&& f) {
   const int vpr = c.pitch / dv::kPitchAlign;
-  const int lanes_per_row = vpr < 64 ? vpr : 64;
-  const int rows_per_pass = 64 / lanes_per_row;
+  const int lanes_per_row = vpr < dv::kWalkLanes ? vpr : dv::kWalkLanes;
+  const int rows_per_pass = dv::kWalkLanes / lanes_per_row;
   const int sub = lane / lanes_per_row, v0 = lane - sub * lanes_per_row;
   for (int row0 = wave * rows_per_pass; row0 < c.h; row0 += 4 * rows_per_pass) {
     const int i = row0 + sub;
@@ -989,7 +990,7 @@ struct lmx_depth_templates {
       HIP_RETURN(hipMalloc(&d_scene_normals, bytes));
       scene_normals_cap = bytes;
     }
-    const unsigned gx = (unsigned)std::min<size_t>(((size_t)W * H + 255) / 256, 4096);
+    const unsigned gx = (unsigned)std::min<size_t>(((size_t)W * H + 255) / 256, (size_t)lmx::nv::kFrameMapGridCap);
     const int pe = prof_begin(PK_NORMAL_MAP_FRAMES, on);
     hipLaunchKernelGGL(lmx::k_normal_map_frames, dim3(gx, (unsigned)n_frames), dim3(256), 0, on, d_scene, W, H, d_scene_normals, nparams);
     prof_end(pe, on);
@@ -1161,7 +1162,7 @@ extern "C" lmx_status lmx_depth_templates_from_mesh(int32_t device, const double
         HIP_RETURN(hipMalloc(&chunk, elems * sizeof(uint16_t)));
         t->chunks.push_back(chunk);
         t->atlas_bytes += elems * sizeof(uint16_t);
-        hipLaunchKernelGGL(k_depth_crop, dim3(16, (unsigned)n), dim3(256), 0, s, d_depth.as<uint16_t>(), d_state.as<int32_t>(), dc.W, dc.H, chunk, where);
+        hipLaunchKernelGGL(k_depth_crop, dim3(dv::kCropCopyGrid, (unsigned)n), dim3(256), 0, s, d_depth.as<uint16_t>(), d_state.as<int32_t>(), dc.W, dc.H, chunk, where);
         HIP_RETURN(hipGetLastError());
       }
       for (int i = 0; i < n; ++i) {
@@ -1371,7 +1372,7 @@ lmx_status compute_crop_normals(lmx_depth_templates* t) {
   HIP_RETURN(hipMemcpyAsync(t->d_ntable, t->ntable.data(), n * sizeof(nv::Packed*), hipMemcpyHostToDevice, t->s));
   for (size_t first = 0; first < n; first += 32768) {   // blockIdx.y: at most 65535
     const unsigned cnt = (unsigned)std::min<size_t>(32768, n - first);
-    hipLaunchKernelGGL(k_normal_map_crops, dim3(32, cnt), dim3(256), 0, t->s, t->d_table + first, t->d_ntable + first, t->nparams);
+    hipLaunchKernelGGL(k_normal_map_crops, dim3(nv::kCropMapGrid, cnt), dim3(256), 0, t->s, t->d_table + first, t->d_ntable + first, t->nparams);
     HIP_RETURN(hipGetLastError());
   }
   HIP_RETURN(hipStreamSynchronize(t->s));   // ntable's bytes have left the host

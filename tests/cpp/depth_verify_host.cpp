@@ -13,6 +13,9 @@ using lmx::dv::Sums;
 
 extern "C" int dv_host_pitch(int w) { return lmx::dv::crop_pitch(w); }
 
+// out = {crop-copy grid, lanes of a wave along a crop row, elements of a vector}: how the kernels spread a crop (tests/second_trip_cases.py)
+extern "C" void dv_host_launch_caps(int* out) { out[0] = lmx::dv::kCropCopyGrid; out[1] = lmx::dv::kWalkLanes; out[2] = lmx::dv::kPitchAlign; }
+
 // crop: [h][pitch].  vectors = 0: pixel by pixel over the w columns (the padding is not read); 1: whole vectors over the padded rows, as the
 // kernel walks them (the padding must be zeros).  out = {sum_abs_mm, n_valid, n_template}.
 extern "C" void dv_host_diff(const uint16_t* crop, int w, int h, int pitch, const uint16_t* scene, int W, int H, size_t scene_pitch, int x, int y,

@@ -14,6 +14,9 @@ namespace dv = lmx::dv;
 
 extern "C" void nv_host_table(uint32_t* out) { nv::build_angle_table(out); }
 
+// out = {frame-map grid cap, crop-map grid}: the workgroups of the normal-map kernels (tests/second_trip_cases.py)
+extern "C" void nv_host_launch_caps(int* out) { out[0] = nv::kFrameMapGridCap; out[1] = nv::kCropMapGrid; }
+
 // img: [h] rows of `pitch` elements; out: [h][w] packed normals (8 bytes each: four int16 {qx, qy, qz, valid})
 extern "C" void nv_host_normal_map(const uint16_t* img, int w, int h, size_t pitch, double fx, double fy, int difference_threshold, int distance_threshold,
                                    uint64_t* out) {

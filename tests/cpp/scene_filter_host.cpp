@@ -10,6 +10,9 @@ static sf::Params params_of(const double* v, int r, int k) { return sf::Params{{
 
 extern "C" int sf_host_info_bytes() { return (int)sizeof(sf::Info); }
 
+// out = {tile width, tile height, score-grid cap, apply-grid cap}: how the kernels spread a frame (tests/second_trip_cases.py)
+extern "C" void sf_host_launch_caps(int* out) { out[0] = sf::kTileW; out[1] = sf::kTileH; out[2] = sf::kScoreGridCap; out[3] = sf::kApplyGridCap; }
+
 // One frame: scene [H] rows of `pitch` elements, out [H][W], info: sizeof(sf::Info) bytes.  1: the parameters are refused, 2: the frame is too large.
 extern "C" int sf_host_filter(const uint16_t* scene, int W, int H, size_t pitch, const double* v, int r, int k, uint16_t* out, void* info) {
   const sf::Params P = params_of(v, r, k);

@@ -75,7 +75,7 @@ def test_two_frames_keep_their_own_sums_and_a_large_frame(plain, host):
     got = device_filter(plain, frames, cam)
     check_frames(host, got, frames, cam, what="two frames")
     assert got[0][1]["sum_q"] != got[1][1]["sum_q"] and got[0][1]["threshold"] != got[1][1]["threshold"] and got[0][1]["n_valid"] != got[1][1]["n_valid"]
-    for r, k in ((3, 15), (7, 100)):       # 321 x 241: 11 x 31 tiles, the last column and row of them cut, more tiles than one pass of a frame's workgroups
+    for r, k in ((3, 15), (7, 100)):       # 321 x 241: 11 x 31 = 341 tiles, the last column and row of them cut, one tile per workgroup (later trips: test_gpu_second_trips.py)
         big = sfc.large_frame()
         cam = sfc.scene_camera(big)
         got = device_filter(plain, [big], cam, r, k)
